@@ -20,7 +20,8 @@ Launch: `python bench.py --gpus N` starts its own N rank processes (fresh childr
 touches the GPU; the parent only relays rank 0's JSON line and the exit codes); under torch.distributed.run
 (RANK / LOCAL_RANK / WORLD_SIZE in the environment) the process IS one rank.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (MSM bucket accumulation,
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline; `--full` adds
+the rest below.  `roofline` is for the dominant kernel (MSM bucket accumulation,
 k_msm_accum0_f9), timed live with HIP events on the stream it is launched on; `roofline.kernels` holds the same
 figures for the HBM-bound kernels of the polynomial seam; `cpu_baseline` is the oracle's plain-C restatement
 (OpenMP, all host cores) on a bounded sample of the same workload, with the reference's own trace-derived
@@ -77,7 +78,19 @@ def parse_args(argv=None):
     ap.add_argument("--plumbing-only", action="store_true",
                     help="no proving: ranks rendezvous, run the barrier / max-over-ranks / digest-gather plumbing and rank 0 prints a JSON "
                          "line (the CPU test of the self-launch path; needs no GPU)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel HIP-event timing in the timed steps and the "
+                         "`roofline` block (with the multiplier micro-benchmark), the `full_step` leg and the `cpu_baseline` leg "
+                         "(--no-full-step / --no-cpu-baseline still drop those two); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the proof bytes of every proof in the step, "
+                         "as float32 byte values) to DIR/<name>.npy (rank 0)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return args
 
 
 def _free_port():
@@ -214,6 +227,9 @@ def run_rank(args):
             def last_error(self):
                 return party.last_error()
 
+            def proof_bytes(self, res):  # the participant is a libcozk harness handle: same accessor as Harness
+                return pkg.Harness.proof_bytes(party, res)
+
             def party_ctx_handle(self, _p=0):
                 return party.ctx_handle()
 
@@ -254,12 +270,14 @@ def run_rank(args):
         for _, eh in extra:
             eh.prove(verify=False)
 
-    hprof.prof_enable(h, 0, True)
+    if args.full:
+        hprof.prof_enable(h, 0, True)
     grp.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     phases = dict(commit=0.0, gp_construct=0.0, gp_prove=0.0, evaluate=0.0, open=0.0)
     hub_wait_ms, hub_exchanges = 0.0, 0
+    extra_res = {}
     for _ in range(args.steps):
         r = h.prove(verify=False)
         hub_wait_ms += getattr(r, "t_hub_wait_ms", 0.0)
@@ -272,7 +290,7 @@ def run_rank(args):
         if bytes(r.proof_digest) != digest0:
             raise SystemExit("non-deterministic proof across steps")
         for name, eh in extra:
-            er = eh.prove(verify=False)
+            er = extra_res[name] = eh.prove(verify=False)
             if bytes(er.proof_digest) != extra_digest[name]:
                 raise SystemExit("non-deterministic %s proof across steps" % name)
             if name == "lookups":
@@ -287,9 +305,10 @@ def run_rank(args):
     dt = time.perf_counter() - t0
     dt_local = dt
     dt = grp.max_over_ranks(dt)
-    prof = hprof.prof_read(h, 0)
-    kprof = hprof.prof_read_kernels(h, 0)
-    hprof.prof_enable(h, 0, False)
+    if args.full:
+        prof = hprof.prof_read(h, 0)
+        kprof = hprof.prof_read_kernels(h, 0)
+        hprof.prof_enable(h, 0, False)
     digests = grp.all_gather_bytes(digest0)
     # per-rank view (N > 1): every rank's phase times and the time its coordinator copy waited in the hub for the slowest participant
     # of each star exchange -- what makes a scaling curve interpretable (a rank that waits is not the one that limits the step)
@@ -302,7 +321,88 @@ def run_rank(args):
     value = cycles / dt
     ms_per_step = dt * 1e3 / args.steps
 
-    # ---- roofline of the dominant kernel
+    # ---- roofline of the dominant kernel and the per-kernel figures (--full: HIP events in the timed steps + a micro-benchmark)
+    roofline = _roofline_leg(pkg, dev, prof, kprof, dt, log_n, world) if args.full else None
+
+    out = {"metric": "RISC-V cycles proved/sec (co-Jolt hot path: PST13 commit + dense GKR grand product + openings)",
+           "value": round(value, 1), "unit": "cycles/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "u32-limb BN254 Fr/Fq (254-bit Montgomery integers)", "data": "synthetic",
+           "config": {"workload": "configs[1] restated (SURVEY 8d): 2^%d-cycle trace per GPU, plain prover, 128 polys "
+                                  "(64 Fr + 32 u16 + 16 u32 + 16 flags) PST13 batch commit, dense grand product 8 x 2^%d leaves, "
+                                  "batch evaluate + opening reduction + PST13 open" % (log_n, log_n + 1)
+                                  + ("; + 8(f)1 Lasso primary sumcheck (27 RV32I collations) and toggled grand product, 54 memories" if args.lookups else "")
+                                  + ("; + 8(f)2 whole Spartan worker on the Jolt constraint set (128 rows/step)" if args.outer else ""),
+                      "log_n": log_n, "polys": 128, "gp_batch": 8,
+                      "parallelism": ("single GPU" if world == 1 else
+                                      ("one proof of a 2^%d-cycle trace sharded over %d worker sub-nets (high-variable chunks), star all-gather per round" % (total_log_n, world)
+                                       if split else "independent trace segment per GPU")),
+                      "ranks_per_gpu": max(1, -(-world // ndev))},
+           "phases_ms_per_step": {k: round(v / args.steps, 3) for k, v in phases.items()},
+           "setup_s": round(t_setup, 2), "proof_bytes": int(res.proof_len), "proof_sha256": [d.hex()[:16] for d in digests]}
+    if roofline is not None:
+        out["roofline"] = roofline
+    if per_rank is not None:
+        out["per_rank"] = per_rank
+
+    # ---- host-resident witness: what the H2D leg adds when the boundary hands over host buffers (never part of `value`)
+    if args.host_witness and rank == 0 and world == 1:
+        out["host_witness"] = _host_witness_leg(pkg, torch, dev, log_n, ms_per_step)
+
+    if args.witness_scatter and rank == 0 and world == 1:
+        out["witness_scatter"] = _witness_scatter_leg(pkg, torch, dev, log_n)
+
+    # ---- full_step (N = 1): the one chained worker flow of co-jolt/src/jolt/vm/jolt/worker.rs:175-266 on the same trace length; its own
+    #      harness, run after the timed region of `value` (it is a different, larger unit of work than the metric's step)
+    if args.full and rank == 0 and world == 1 and not args.no_full_step:
+        out["full_step"] = _full_step_leg(importlib, torch, dev, log_n, h)
+        # the same flow on a witness with the widths of a real trace (a plain prover's commitments fill 2 of the 16 windows)
+        rw = _full_step_leg(importlib, torch, dev, log_n, h, small_witness=1)
+        out["full_step"]["real_width_witness"] = {k: rw[k] for k in ("witness", "ms", "cycles_per_s", "steps", "verified", "phases_ms", "proof_sha256")}
+
+    # ---- CPU baseline (rank 0, N = 1 only): the oracle's C restatement on a bounded sample
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        sys.path.insert(0, os.path.join(ROOT, "oracle"))
+        import coracle  # the checker, used here only as the timed CPU baseline
+        s = args.cpu_sample_log_n
+        cfg = dict(mode="plain", log_n=s, n_fr=64, n_u16=32, n_u32=16, n_flags=16, n_small=0, gp_batch=8, gp_log_leaves=s + 1, seed=2026)
+        cres, _ = coracle.pipeline(cfg, want_proof=False)
+        fr_scalar_muls = 64 * (1 << s)
+        out["cpu_baseline"] = {"value": round((1 << s) / cres.t_total_s, 1), "unit": "cycles/s", "cores": int(cres.threads), "kind": "port",
+                               "sample": "same pipeline and polynomial mix at a 2^%d-cycle trace (%.1f s of CPU work; plain-C OpenMP "
+                                         "restatement oracle/c, not arkworks: signed-digit Pippenger with XYZZ buckets on an unrolled no-carry "
+                                         "Montgomery product; batch commit = one polynomial's Pippenger per thread, as jolt-core's rayon "
+                                         "batch_msm; cores = the CPUs this process may use: affinity capped by the cgroup quota)" % (s, cres.t_total_s),
+                               "commit_share": round(cres.t_commit_s / cres.t_total_s, 3),
+                               "commit_fr_scalar_muls_per_s_per_core_lower_bound": round(fr_scalar_muls / cres.t_commit_s / max(1, int(cres.threads)), 1),
+                               "published": {"note": "the reference's own trace-derived numbers (BASELINE.md; FULL Jolt prover per party, AWS, "
+                                                     "not this sub-path): not comparable with `value`, quoted as the contract asks",
+                                             "2^20_cycles_8_vcpu": {"cycles_per_s": 5100, "prove_s": 204.6, "commit_s": 155.6},
+                                             "2^22_cycles_32_vcpu": {"cycles_per_s": 12200, "prove_s": 345.9, "commit_s": 146.0}}}
+    # nothing after the timed steps proves again on these harnesses: their last proofs are still the last timed step's
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, [("proof", h, r)] + [(name + "_proof", eh, extra_res[name]) for name, eh in extra])
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    for _, eh in extra:
+        eh.close()
+    h.close()
+    grp.close()
+
+
+def _dump_outputs(out_dir, proofs):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- each proof, serialized -- as
+    DIR/<name>.npy, one float32 per byte (exact), so that two builds can be compared output for output"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, harness, res in proofs:
+        data = np.frombuffer(harness.proof_bytes(res), dtype=np.uint8)
+        np.save(os.path.join(out_dir, name + ".npy"), data.astype(np.float32))
+
+
+def _roofline_leg(pkg, dev, prof, kprof, dt, log_n, world):
+    """`roofline`: the dominant kernel's HIP-event figures from the timed steps against HBM and integer-ALU peaks, plus the
+    HBM-bound kernels of the polynomial seam"""
     launches = max(1, prof["launches"])
     avg_ms = prof["total_ms"] / launches
     alg_per_launch = prof["alg_bytes"] / launches
@@ -366,67 +466,7 @@ def run_rank(args):
             roofline["int_alu"]["counters_source"] = "profiles/%s (%s); NOT measured in this run" % (sq_file, sq.get("measured_at", ""))
     except Exception:
         pass
-
-    out = {"metric": "RISC-V cycles proved/sec (co-Jolt hot path: PST13 commit + dense GKR grand product + openings)",
-           "value": round(value, 1), "unit": "cycles/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-           "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-           "dtype": "u32-limb BN254 Fr/Fq (254-bit Montgomery integers)", "data": "synthetic",
-           "config": {"workload": "configs[1] restated (SURVEY 8d): 2^%d-cycle trace per GPU, plain prover, 128 polys "
-                                  "(64 Fr + 32 u16 + 16 u32 + 16 flags) PST13 batch commit, dense grand product 8 x 2^%d leaves, "
-                                  "batch evaluate + opening reduction + PST13 open" % (log_n, log_n + 1)
-                                  + ("; + 8(f)1 Lasso primary sumcheck (27 RV32I collations) and toggled grand product, 54 memories" if args.lookups else "")
-                                  + ("; + 8(f)2 whole Spartan worker on the Jolt constraint set (128 rows/step)" if args.outer else ""),
-                      "log_n": log_n, "polys": 128, "gp_batch": 8,
-                      "parallelism": ("single GPU" if world == 1 else
-                                      ("one proof of a 2^%d-cycle trace sharded over %d worker sub-nets (high-variable chunks), star all-gather per round" % (total_log_n, world)
-                                       if split else "independent trace segment per GPU")),
-                      "ranks_per_gpu": max(1, -(-world // ndev))},
-           "phases_ms_per_step": {k: round(v / args.steps, 3) for k, v in phases.items()},
-           "setup_s": round(t_setup, 2), "proof_bytes": int(res.proof_len), "proof_sha256": [d.hex()[:16] for d in digests],
-           "roofline": roofline}
-    if per_rank is not None:
-        out["per_rank"] = per_rank
-
-    # ---- host-resident witness: what the H2D leg adds when the boundary hands over host buffers (never part of `value`)
-    if args.host_witness and rank == 0 and world == 1:
-        out["host_witness"] = _host_witness_leg(pkg, torch, dev, log_n, ms_per_step)
-
-    if args.witness_scatter and rank == 0 and world == 1:
-        out["witness_scatter"] = _witness_scatter_leg(pkg, torch, dev, log_n)
-
-    # ---- full_step (N = 1): the one chained worker flow of co-jolt/src/jolt/vm/jolt/worker.rs:175-266 on the same trace length; its own
-    #      harness, run after the timed region of `value` (it is a different, larger unit of work than the metric's step)
-    if rank == 0 and world == 1 and not args.no_full_step:
-        out["full_step"] = _full_step_leg(importlib, torch, dev, log_n, h)
-        # the same flow on a witness with the widths of a real trace (a plain prover's commitments fill 2 of the 16 windows)
-        rw = _full_step_leg(importlib, torch, dev, log_n, h, small_witness=1)
-        out["full_step"]["real_width_witness"] = {k: rw[k] for k in ("witness", "ms", "cycles_per_s", "steps", "verified", "phases_ms", "proof_sha256")}
-
-    # ---- CPU baseline (rank 0, N = 1 only): the oracle's C restatement on a bounded sample
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        sys.path.insert(0, os.path.join(ROOT, "oracle"))
-        import coracle  # the checker, used here only as the timed CPU baseline
-        s = args.cpu_sample_log_n
-        cfg = dict(mode="plain", log_n=s, n_fr=64, n_u16=32, n_u32=16, n_flags=16, n_small=0, gp_batch=8, gp_log_leaves=s + 1, seed=2026)
-        cres, _ = coracle.pipeline(cfg, want_proof=False)
-        fr_scalar_muls = 64 * (1 << s)
-        out["cpu_baseline"] = {"value": round((1 << s) / cres.t_total_s, 1), "unit": "cycles/s", "cores": int(cres.threads), "kind": "port",
-                               "sample": "same pipeline and polynomial mix at a 2^%d-cycle trace (%.1f s of CPU work; plain-C OpenMP "
-                                         "restatement oracle/c, not arkworks: signed-digit Pippenger with XYZZ buckets on an unrolled no-carry "
-                                         "Montgomery product; batch commit = one polynomial's Pippenger per thread, as jolt-core's rayon "
-                                         "batch_msm; cores = the CPUs this process may use: affinity capped by the cgroup quota)" % (s, cres.t_total_s),
-                               "commit_share": round(cres.t_commit_s / cres.t_total_s, 3),
-                               "commit_fr_scalar_muls_per_s_per_core_lower_bound": round(fr_scalar_muls / cres.t_commit_s / max(1, int(cres.threads)), 1),
-                               "published": {"note": "the reference's own trace-derived numbers (BASELINE.md; FULL Jolt prover per party, AWS, "
-                                                     "not this sub-path): not comparable with `value`, quoted as the contract asks",
-                                             "2^20_cycles_8_vcpu": {"cycles_per_s": 5100, "prove_s": 204.6, "commit_s": 155.6},
-                                             "2^22_cycles_32_vcpu": {"cycles_per_s": 12200, "prove_s": 345.9, "commit_s": 146.0}}}
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    for _, eh in extra:
-        eh.close()
-    h.close()
-    grp.close()
+    return roofline
 
 
 def _full_step_leg(importlib, torch, dev, log_n, main_harness, steps=3, small_witness=0):

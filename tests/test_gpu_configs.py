@@ -71,17 +71,20 @@ def test_config4_substitute_8_worker_split(cozk, log_n):
     h.close()
 
 
-def test_bench_four_ranks_share_the_gpu():
+def test_bench_four_ranks_share_the_gpu(tmp_path):
     """`bench.py --gpus 4 --log-n 14` starts its own four ranks (4 processes on the card: within the box's guard of 6; the 8-rank
     run is the driver's, on an 8-GPU node -- tests/test_dist_cpu.py rehearses its launch and hub on the CPU): ONE proof of a
-    2^16-cycle trace as 4 worker sub-nets, one JSON line, every rank assembled the same proof, per-rank phases and hub waits"""
+    2^16-cycle trace as 4 worker sub-nets, one JSON line, every rank assembled the same proof, per-rank phases and hub waits;
+    `--dump-outputs` writes rank 0's copy of that proof, whose SHA-256 is the line's proof_sha256"""
+    import hashlib
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--log-n", "14", "--steps", "2", "--warmup", "1"], env=env,
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--log-n", "14", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], env=env,
                        capture_output=True, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
@@ -90,3 +93,54 @@ def test_bench_four_ranks_share_the_gpu():
     assert out["n_gpus"] == 4 and out["scaling"] == "weak" and len(set(out["proof_sha256"])) == 1 and len(out["proof_sha256"]) == 4
     assert [r["rank"] for r in out["per_rank"]] == [0, 1, 2, 3]
     assert all(r["hub_exchanges_per_step"] > 0 and r["hub_wait_ms_per_step"] >= 0 for r in out["per_rank"])
+    import numpy as np
+    proof = np.load(tmp_path / "proof.npy")
+    assert proof.dtype == np.float32 and proof.size == out["proof_bytes"]
+    assert hashlib.sha256(proof.astype(np.uint8).tobytes()).hexdigest()[:16] == out["proof_sha256"][0]
+
+
+def test_bench_plain_run_dumps_the_last_proof(tmp_path):
+    """a plain `bench.py --gpus 1` run prints the headline line without the `--full` legs, and `--dump-outputs` writes the
+    last timed step's proof (one float32 per byte) whose SHA-256 is the line's proof_sha256"""
+    import hashlib
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--log-n", "14", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert all(k in out for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"))
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    assert not any(k in out for k in ("roofline", "cpu_baseline", "full_step"))
+    proof = np.load(tmp_path / "proof.npy")
+    assert proof.dtype == np.float32 and proof.size == out["proof_bytes"]
+    assert hashlib.sha256(proof.astype(np.uint8).tobytes()).hexdigest()[:16] == out["proof_sha256"][0]
+
+
+def test_bench_steps_sets_the_number_of_timed_steps():
+    """`--steps N` times N proofs: the MSM gather launches counted by the `--full` HIP events inside the timed region of a
+    3-step run are exactly three times those of a 1-step run (the count per proof is fixed), and the warm-up is not counted"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    launches = {}
+    for steps in (1, 3):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--log-n", "14", "--steps", str(steps), "--warmup", "2",
+                            "--full", "--no-full-step", "--no-cpu-baseline"], env=env, capture_output=True, timeout=600)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["steps"] == steps
+        launches[steps] = out["roofline"]["launches"]
+    assert launches[1] > 0 and launches[3] == 3 * launches[1]
