@@ -5,11 +5,14 @@
 // products: the saturated 8 x 32 product-scanning multiplier costs ~550-600 instructions per product in that context (128 mads, ~140
 // add-with-carry, ~180 register moves of the 96-bit column accumulators), and the kernels ran at 0.5-0.6 of the vector issue rate with
 // neither HBM nor the multiplier busy.  The 9 x 29 product is 162 mads + ~45 shifts / masks, and additions need no modular reduction:
-//   * VALUES are lazy: a product of inputs < A r and < B r is < r (1 + A B / 169) (r / R' < 1/169); sums simply grow (7 spare bits);
+//   * VALUES are lazy: a product of inputs < A r and < B r is < r (1 + A B / 169) (r / R' < 1/169); sums grow by ~1.06 r per term.
+//     Nothing else bounds them, so every round-sum accumulator is FOLDED every FR9_FOLD_PERIOD terms (fr9_fold: one product by
+//     R' mod r, the same element at < 1.82 r): the sums stay below ~138 r (top limb < 2^29.1), and the final product by a K constant
+//     below 1.82 r, which fr9_to_canonical needs (< 3 r).  tests/test_fr9_model.py proves these bounds for any number of terms;
 //     subtraction is a + C - b with C a multiple of r whose limbs dominate b's (fr9_consts.inc);
 //   * LIMBS are re-normalised (f9_norm: 25 instructions) where the next product needs it.  Column sums stay below 2^64 when
 //     9 max(a_i) max(b_i) + 9 * 2^58 < 2^64: every call site keeps its SECOND operand normalised (< 2^29) and its first below 2^30.6
-//     (below 2^30 for the two-product form).
+//     (below 1.5 * 2^30 for the two-product form).
 // Memory stays in the ordinary R = 2^256 Montgomery form (byte-identical to arkworks): values are re-limbed on load, and a stored value
 // is made canonical again (normalise, re-limb, two conditional subtractions).  A product of two R-form values under the R' reduction
 // carries lambda = R / R' = 2^-5: the bind multiplies by the challenge pre-scaled by 2^5 (exact R-form result), the cubic terms carry
@@ -30,7 +33,7 @@ static __device__ __forceinline__ f9 fr9_mul(const f9& a, const f9& b) {
     F9_MUL_BODY
     return r;
 }
-// (a * b + c * d) / R' mod r under one reduction; b, d normalised, a's and c's limbs < 2^30
+// (a * b + c * d) / R' mod r under one reduction; b, d normalised, a's and c's limbs < 1.5 * 2^30 (k_outer_round_act9's differences)
 static __device__ __forceinline__ f9 fr9_mul_add2(const f9& a, const f9& b, const f9& c, const f9& d) {
     const uint32_t(&F9_P)[9] = FR9_P;
     constexpr uint32_t F9_INV = FR9_INV;
@@ -40,7 +43,19 @@ static __device__ __forceinline__ f9 fr9_mul_add2(const f9& a, const f9& b, cons
     F9_MUL_ADD2_BODY
     return r;
 }
+// a * c / R' mod r for a wave-uniform constant c: its limbs are scalar-register operands of the chains, so a fold inside a loop holds
+// no vector registers for it
+static __device__ __forceinline__ f9 fr9_mul_sc(const f9& a, const f9& b) {
+    const uint32_t(&F9_P)[9] = FR9_P;
+    constexpr uint32_t F9_INV = FR9_INV;
+    uint64_t acc = 0;
+    uint32_t m[9];
+    f9 r;
+    F9_MUL_S_BODY
+    return r;
+}
 #else
+__device__ f9 fr9_mul_sc(const f9& a, const f9& b);
 __device__ f9 fr9_mul(const f9& a, const f9& b);
 __device__ f9 fr9_mul_add2(const f9& a, const f9& b, const f9& c, const f9& d);
 #endif
@@ -56,10 +71,15 @@ static __device__ __forceinline__ f9 fr9_zero() {
     for (int i = 0; i < 9; i++) r.l[i] = 0;
     return r;
 }
-// value < 2.1 r (any limbs < 2^31) -> the canonical 8 x 32 element
+// value < 3 r (two conditional subtractions; any limbs < 2^31) -> the canonical 8 x 32 element
 static __device__ __forceinline__ fe fr9_to_canonical(const f9& a) {
     return Fr::reduce_once(Fr::reduce_once(f9_to_fe(f9_norm(a))));
 }
+
+// lazy round-sum accumulators (terms of < ~1.06 r each) are folded once per FR9_FOLD_PERIOD terms: (1.82 + 128 x 1.06) r < 138 r
+static constexpr unsigned FR9_FOLD_PERIOD = 128;
+// the same element, value < r (1 + A / 169) < 1.82 r for A < 138; a's limbs < 2^30.6
+static __device__ __forceinline__ void fr9_fold(f9& a) { a = fr9_mul_sc(a, f9_const(FR9_RP)); }
 
 // NC components of a share in the lazy 9 x 29 form
 template <int NC>
@@ -103,7 +123,7 @@ static __device__ __forceinline__ Sh9<NC> sh9_add_norm(const Sh9<NC>& x, const S
     return o;
 }
 // Share x Share -> additive (mpc-types/src/protocols/rep3/arithmetic/ops.rs:71-78) as x.a (y.a + y.b) + x.b y.a under ONE reduction;
-// x's limbs < 2^30, y's any < 2^31 (normalised here); output normalised, carries lambda
+// x's limbs < 1.5 * 2^30, y's any < 2^31 (normalised here); output normalised, carries lambda
 template <int NC>
 static __device__ __forceinline__ f9 sh9_local_mul(const Sh9<NC>& x, const Sh9<NC>& y) {
     if (NC == 1) return fr9_mul(x.c[0], f9_norm(y.c[0]));

@@ -53,6 +53,14 @@ static inline unsigned grid_capped(size_t n) {
     size_t g = (n + PT - 1) / PT;
     return (unsigned)(g > MAXBLK ? MAXBLK : (g ? g : 1));
 }
+// COZK_SUM_GRID_MAX=n (n > 0): at most n workgroups for the grid-stride round-sum launches (layer cubic sums, fused bind + sums,
+// toggle and outer rounds), so that each lane adds thousands of terms -- what the lazy 9 x 29 sums are tested at.  Read on every
+// call: a test may set it for one proof.  Unset or 0: the grids are unchanged.
+static inline unsigned sum_grid(unsigned gx) {
+    const char* e = getenv("COZK_SUM_GRID_MAX");
+    const long n = e ? atol(e) : 0;
+    return n > 0 && (unsigned long)n < gx ? (unsigned)n : gx;
+}
 
 // Grid of a grid-stride kernel whose waves are long (thousands of instructions per element): exactly the workgroups the chip
 // holds at once (occupancy query x CUs), so that every wave is resident from the start and the last residency round is not a
@@ -511,6 +519,20 @@ static __device__ __forceinline__ void layer9_group_flush(Layer9Group& grp, cons
     s2 = f9_norm(fr9_add(s2, fr9_mul(grp.g2, sc)));
     s3 = f9_norm(fr9_add(s3, fr9_mul(grp.g3, sc)));
 }
+// the periodic fold of the lazy sums (fr9.hip.hpp): once per FR9_FOLD_PERIOD iterations of the wave-uniform chunk walk, each of
+// which adds at most one term to every sum (NESTED = 2: one to each group sum, at most one flush to each s)
+template <int NESTED>
+static __device__ __forceinline__ void layer9_fold(size_t it, f9& s0, f9& s2, f9& s3, Layer9Group& grp) {
+    if (it == 0 || (it & (FR9_FOLD_PERIOD - 1)) != 0) return;
+    fr9_fold(s0);
+    fr9_fold(s2);
+    fr9_fold(s3);
+    if (NESTED == 2) {
+        fr9_fold(grp.g0);
+        fr9_fold(grp.g2);
+        fr9_fold(grp.g3);
+    }
+}
 template <int NC, int NESTED>
 static __device__ __forceinline__ void layer9_terms(const Sh9<NC>& l0, const Sh9<NC>& r0, const Sh9<NC>& l1, const Sh9<NC>& r1, const fe* __restrict__ E1,
                                                     size_t E1_half, int e1_shift, const fe* __restrict__ E2, size_t c, f9& s0, f9& s2, f9& s3,
@@ -631,11 +653,14 @@ __global__ void __launch_bounds__(PT) k_layer_cubic9(const fe* __restrict__ a, c
     const int e1_shift = NESTED ? __ffsll((long long)E1_half) - 1 : 0;
     f9 s0 = fr9_zero(), s2 = fr9_zero(), s3 = fr9_zero();
     Layer9Group grp;
+    grp.g0 = grp.g2 = grp.g3 = fr9_zero();
     grp.x2 = (size_t)-1;
     size_t c_first, c_end, c_step;
     layer9_walk(NESTED, nch, c_first, c_end, c_step);
     // the trip count is per WAVE (c0 = the wave's first chunk): a wave whose 64 chunks are all inside the layer takes the staged path
-    for (size_t c0 = c_first; c0 < c_end; c0 += c_step) {
+    size_t it = 0;
+    for (size_t c0 = c_first; c0 < c_end; c0 += c_step, it++) {
+        layer9_fold<NESTED>(it, s0, s2, s3, grp);
         const size_t c = c0 + (threadIdx.x & 63);
         if (c0 + 64 <= nch && 4 * (c0 + 64) <= len) {
             Sh9<NC> q[4];
@@ -673,10 +698,13 @@ __global__ void __launch_bounds__(PT) k_layer_bind_cubic9(const fe* __restrict__
     __shared__ __attribute__((aligned(16))) char stage[PT / 64][ST_WAVE_BYTES];
     char* st = stage[threadIdx.x >> 6];
     Layer9Group grp;
+    grp.g0 = grp.g2 = grp.g3 = fr9_zero();
     grp.x2 = (size_t)-1;
     size_t c_first, c_end, c_step;
     layer9_walk(NESTED, nch_out, c_first, c_end, c_step);
-    for (size_t c0 = c_first; c0 < c_end; c0 += c_step) {
+    size_t it = 0;
+    for (size_t c0 = c_first; c0 < c_end; c0 += c_step, it++) {
+        layer9_fold<NESTED>(it, s0, s2, s3, grp);
         const size_t c = c0 + (threadIdx.x & 63);
         Sh9<NC> v[4];
         if (c0 + 64 <= nch_out && 8 * (c0 + 64) <= len_in) {
@@ -2214,6 +2242,7 @@ static void layer_cubic_sums(cozk_ctx* ctx, const cozk_layer* l, const cozk_spli
     size_t nch = (l->len + 3) / 4;
     unsigned gx = grid_capped(nch);
     if (gx > 1024) gx = 1024;
+    gx = sum_grid(gx);
     ctx->scratch.reserve((3 * (size_t)MAXBLK + 3) * sizeof(fe));
     fe* partial = ctx->scratch.as<fe>();
     fe* res = result_slot(ctx, 3);
@@ -2228,7 +2257,7 @@ static void layer_cubic_sums(cozk_ctx* ctx, const cozk_layer* l, const cozk_spli
         const int dev = ctx->device;
 #define COZK_CUBIC9(NC_, NE_, B_, E1H_)                                                                                             \
     do {                                                                                                                            \
-        gx = resident_grid((const void*)k_layer_cubic9<NC_, NE_>, need, dev);                                                        \
+        gx = sum_grid(resident_grid((const void*)k_layer_cubic9<NC_, NE_>, need, dev));                                              \
         k_layer_cubic9<NC_, NE_><<<gx, PT, 0, ctx->stream>>>(a, B_, l->len, E1, E1H_, E2, eq->E2_len, partial);                      \
     } while (0)
         static const bool group_env = !(getenv("COZK_LAYER_GROUPED") && atoi(getenv("COZK_LAYER_GROUPED")) == 0);
@@ -2294,6 +2323,7 @@ int cozk_layer_round(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const uint64
             size_t nch_out = (nout + 3) / 4;
             unsigned gx = grid_capped(nch_out);
             if (gx > 1024) gx = 1024;
+            gx = sum_grid(gx);
             ctx->scratch.reserve((3 * (size_t)MAXBLK + 3) * sizeof(fe));
             fe* partial = ctx->scratch.as<fe>();
             fe* res = result_slot(ctx, 3);
@@ -2316,7 +2346,7 @@ int cozk_layer_round(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const uint64
                 const int dev = ctx->device;
 #define COZK_BIND_CUBIC9(NC_, NE_, IB_, OB_, E1H_)                                                                                  \
     do {                                                                                                                            \
-        gx = resident_grid((const void*)k_layer_bind_cubic9<NC_, NE_>, need, dev);                                                   \
+        gx = sum_grid(resident_grid((const void*)k_layer_bind_cubic9<NC_, NE_>, need, dev));                                         \
         k_layer_bind_cubic9<NC_, NE_><<<gx, PT, 0, ctx->stream>>>(ia, IB_, oa, OB_, l->len, r5, E1, E1H_, E2, e->E2_len, partial);   \
     } while (0)
                 static const bool group_env = !(getenv("COZK_LAYER_GROUPED") && atoi(getenv("COZK_LAYER_GROUPED")) == 0);

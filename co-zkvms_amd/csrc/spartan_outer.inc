@@ -306,7 +306,13 @@ __global__ void __launch_bounds__(PT) k_outer_round_act9(const fe* __restrict__ 
     const size_t in_mask = ((size_t)1 << in_bits) - 1;
     const uint32_t act_pairs = (act + 1) / 2, pairs_per_step = per_step / 2;
     const size_t total = (size_t)num_steps * act_pairs;
-    for (size_t q = (size_t)blockIdx.x * PT + threadIdx.x; q < total; q += (size_t)gridDim.x * PT) {
+    unsigned it = 0;  // the periodic fold of the lazy sums (fr9.hip.hpp): one term per sum and iteration
+    for (size_t q = (size_t)blockIdx.x * PT + threadIdx.x; q < total; q += (size_t)gridDim.x * PT, it++) {
+        if (it != 0 && (it & (FR9_FOLD_PERIOD - 1)) == 0) {
+            fr9_fold(s0);
+            fr9_fold(s1);
+            fr9_fold(s2);
+        }
         const uint32_t step = (uint32_t)(q / act_pairs), pr = (uint32_t)(q - (size_t)step * act_pairs);
         const size_t k = (size_t)step * pairs_per_step + pr;
         const size_t si = (size_t)step * act + 2 * pr;
@@ -316,7 +322,7 @@ __global__ void __launch_bounds__(PT) k_outer_round_act9(const fe* __restrict__ 
         const Sh9<NC> a1 = sh9_load_or_zero<NC>(aza, azb, si + 1, has_hi ? (size_t)-1 : 0), b1 = sh9_load_or_zero<NC>(bza, bzb, si + 1, has_hi ? (size_t)-1 : 0);
         Sh9<NC> da, db;
         for (int c = 0; c < NC; c++) {
-            da.c[c] = f9_sub(a1.c[c], FR9_C2, a0.c[c]);  // canonical inputs: limbs < 2^30.3, fine as a product's first operand
+            da.c[c] = f9_sub(a1.c[c], FR9_C2, a0.c[c]);  // canonical inputs: limbs < 1.5 * 2^30, fine as a product's first operand
             db.c[c] = f9_sub(b1.c[c], FR9_C2, b0.c[c]);
         }
         s2 = f9_norm(fr9_add(s2, fr9_mul(e, sh9_local_mul<NC>(da, db))));
@@ -552,6 +558,7 @@ int cozk_outer_round(cozk_ctx* ctx, cozk_outer* st, const uint64_t* r, const uin
         const size_t num_steps = st->L / st->per_step;
         unsigned gx = grid_capped(act ? num_steps * ((st->act_rows + 1) / 2) : npairs);
         if (gx > 1024) gx = 1024;
+        gx = sum_grid(gx);
         ctx->scratch.reserve((3 * (size_t)gx + 3) * sizeof(fe));
         fe* partial = ctx->scratch.as<fe>();
         fe* res = result_slot(ctx, 3);

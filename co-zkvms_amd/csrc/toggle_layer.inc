@@ -208,9 +208,10 @@ __global__ void __launch_bounds__(PT) k_toggle_cubic9(const fe* __restrict__ pa,
     int qn = 0;  // wave-uniform
     const size_t stride = (size_t)gridDim.x * PT;
     const size_t wave_base0 = (size_t)blockIdx.x * PT + (size_t)wv * 64;
-    // X = 0, 2, 3 of the line through (v0, v1), lazily: normalised v0, v1 in, limbs < 2^30.6 out
-    auto line3 = [](const f9& v0, const f9& v1, f9& x0, f9& x2, f9& x3) {
-        const f9 m = f9_norm(f9_sub(v1, FR9_C2, v0));
+    // X = 0, 2, 3 of the line through (v0, v1), lazily: normalised v0, v1 in, limbs < 2^30.6 out; CS = FR9_C2 for canonical v0,
+    // FR9_C3 for a Rep3 sum a + b (< 2 r: its top limb can be one above FR9_C2's)
+    auto line3 = [](const f9& v0, const f9& v1, const uint32_t(&CS)[9], f9& x0, f9& x2, f9& x3) {
+        const f9 m = f9_norm(f9_sub(v1, CS, v0));
         x0 = v0;
         x2 = fr9_add(v1, m);
         x3 = fr9_add(x2, m);
@@ -220,14 +221,14 @@ __global__ void __launch_bounds__(PT) k_toggle_cubic9(const fe* __restrict__ pa,
         if (NESTED) {
             size_t x2i = j >> log_E1_half, x1 = j & (((size_t)1 << log_E1_half) - 1);
             f9 r0, r2, r3;
-            line3(f9_from_fe(fe_load(E1 + 2 * x1)), f9_from_fe(fe_load(E1 + 2 * x1 + 1)), r0, r2, r3);
+            line3(f9_from_fe(fe_load(E1 + 2 * x1)), f9_from_fe(fe_load(E1 + 2 * x1 + 1)), FR9_C2, r0, r2, r3);
             const f9 sc = f9_from_fe(fe_load(E2 + x2i));
             e0 = fr9_mul(r0, sc);
             e2 = fr9_mul(r2, sc);
             e3 = fr9_mul(r3, sc);
         } else {
             f9 r0, r2, r3;
-            line3(f9_from_fe(fe_load(E2 + 2 * j)), f9_from_fe(fe_load(E2 + 2 * j + 1)), r0, r2, r3);
+            line3(f9_from_fe(fe_load(E2 + 2 * j)), f9_from_fe(fe_load(E2 + 2 * j + 1)), FR9_C2, r0, r2, r3);
             e0 = r0;
             e2 = f9_norm(r2);
             e3 = f9_norm(r3);
@@ -240,13 +241,13 @@ __global__ void __launch_bounds__(PT) k_toggle_cubic9(const fe* __restrict__ pa,
         fe f0, f1;
         (void)toggle_flag_pair<FT>(fl, fj, f0, f1);
         f9 g0, g2, g3, p0, p2, p3;
-        line3(f9_from_fe(f0), f9_from_fe(f1), g0, g2, g3);
+        line3(f9_from_fe(f0), f9_from_fe(f1), FR9_C2, g0, g2, g3);
         {
             const Sh9<NC> q0 = sh9_load_or_zero<NC>(pa, pb, 2 * j, (size_t)-1), q1 = sh9_load_or_zero<NC>(pa, pb, 2 * j + 1, (size_t)-1);
             // (a + b) of a Rep3 fingerprint: < 2 r, limbs < 2^30 -- normalised for line3
             const f9 s0 = NC == 2 ? f9_norm(fr9_add(q0.c[0], q0.c[NC - 1])) : q0.c[0];
             const f9 s1 = NC == 2 ? f9_norm(fr9_add(q1.c[0], q1.c[NC - 1])) : q1.c[0];
-            line3(s0, s1, p0, p2, p3);
+            line3(s0, s1, NC == 2 ? FR9_C3 : FR9_C2, p0, p2, p3);
         }
         const f9 c0 = fr9_mul(g0, e0), c2 = fr9_mul(g2, e2), c3 = fr9_mul(g3, e3);  // flag x eq: normalised outputs
         C0 = f9_norm(fr9_add(C0, c0));
@@ -255,6 +256,19 @@ __global__ void __launch_bounds__(PT) k_toggle_cubic9(const fe* __restrict__ pa,
         A0 = f9_norm(fr9_add(A0, fr9_mul(p0, c0)));
         A2 = f9_norm(fr9_add(A2, fr9_mul(p2, c2)));
         A3 = f9_norm(fr9_add(A3, fr9_mul(p3, c3)));
+    };
+    // the periodic fold of the lazy sums (fr9.hip.hpp): a lane takes at most one heavy() per flush of the wave's queue
+    unsigned nflush = 0;  // wave-uniform
+    auto fold = [&]() {
+        if (nflush != 0 && (nflush & (FR9_FOLD_PERIOD - 1)) == 0) {
+            fr9_fold(A0);
+            fr9_fold(A2);
+            fr9_fold(A3);
+            fr9_fold(C0);
+            fr9_fold(C2);
+            fr9_fold(C3);
+        }
+        nflush++;
     };
     for (size_t jb = wave_base0; jb < npairs; jb += stride) {  // wave-uniform trip count
         const size_t j = jb + lane;
@@ -277,6 +291,7 @@ __global__ void __launch_bounds__(PT) k_toggle_cubic9(const fe* __restrict__ pa,
         qn += __popcll(m);
         __builtin_amdgcn_wave_barrier();  // the wave's LDS operations execute in program order; this keeps the compiler from moving them
         if (qn >= 64) {
+            fold();
             heavy(wave_base0 + (size_t)queue[wv][lane]);
             const uint32_t keep = lane < qn - 64 ? queue[wv][64 + lane] : 0u;
             __builtin_amdgcn_wave_barrier();
@@ -285,6 +300,7 @@ __global__ void __launch_bounds__(PT) k_toggle_cubic9(const fe* __restrict__ pa,
             qn -= 64;
         }
     }
+    if (qn > 0) fold();
     if (lane < qn) heavy(wave_base0 + (size_t)queue[wv][lane]);
     {
         // C carries lambda (lambda^2 nested), A one more
@@ -539,6 +555,7 @@ int cozk_toggle_round(cozk_ctx* ctx, cozk_toggle* t, cozk_spliteq* e, const uint
         COZK_REQUIRE(npairs >= 1, "toggle_round: fully bound");
         unsigned gx = grid_capped(npairs);
         if (gx > 1024) gx = 1024;
+        gx = sum_grid(gx);
         ctx->scratch.reserve((6 * (size_t)gx + 16) * sizeof(fe));
         fe* partial = ctx->scratch.as<fe>();
         fe* res = result_slot(ctx, 9);

@@ -133,6 +133,22 @@ class ToggleLayer:
         ctx.check(self._l.cozk_toggle_create(ctx.h, self.mode, arr, len(flags), fa.h, fb.h if fb is not None else None, 0, ctypes.byref(h)))
         self.h = h
 
+    @classmethod
+    def from_vecs(cls, ctx, flag_vecs, fp_a, fp_b=None):
+        """the same layer from device vectors (no host lists): one U8 Vec of N entries per pair of circuits, the fingerprints as FR
+        Vecs of 2 x pairs x N entries (fp_b: the second Rep3 component)"""
+        self = cls.__new__(cls)
+        self._l = _decl()
+        self.ctx = ctx
+        self.mode = L.MODE_REP3 if fp_b is not None else L.MODE_PLAIN
+        self._flag_vecs = list(flag_vecs)
+        self._fp_vecs = (fp_a, fp_b)
+        arr = (_vp * len(flag_vecs))(*[v.h for v in flag_vecs])
+        h = _vp()
+        ctx.check(self._l.cozk_toggle_create(ctx.h, self.mode, arr, len(flag_vecs), fp_a.h, fp_b.h if fp_b is not None else None, 0, ctypes.byref(h)))
+        self.h = h
+        return self
+
     def layer_output(self, party=0):
         from .poly import Rep3DenseInterleavedPolynomial
         h = _vp()
