@@ -157,3 +157,66 @@ def _declare(l):
         fn = getattr(l, name)
         fn.restype = res
         fn.argtypes = args
+
+
+class HarnessHandle:
+    """One in-process prove harness of the C ABI: `PREFIX_create / _error / _destroy / _prove / _proof_bytes` over the
+    CONFIG and RESULT structures.  A subclass fills a CONFIG and hands it to `_open`; EXTRA declares its other entry points
+    (full name -> (restype, argtypes))."""
+    PREFIX = CONFIG = RESULT = None
+    EXTRA = {}
+
+    @classmethod
+    def _decl(cls):
+        l = lib()
+        sigs = {"_create": (_i, [ctypes.POINTER(cls.CONFIG), _pp]), "_error": (ctypes.c_char_p, [_vp]), "_destroy": (_i, [_vp]),
+                "_prove": (_i, [_vp, _i, ctypes.POINTER(cls.RESULT)]), "_proof_bytes": (_i, [_vp, _vp, _sz])}
+        for name, (res, args) in [(cls.PREFIX + k, v) for k, v in sigs.items()] + list(cls.EXTRA.items()):
+            fn = getattr(l, name)
+            fn.restype = res
+            fn.argtypes = args
+        return l
+
+    def _f(self, suffix):
+        return getattr(self._l, self.PREFIX + suffix)
+
+    def _open(self, cfg, *args, create="_create"):
+        """create(&cfg, *args, &h); a harness that fails to build reports its error, is destroyed, and raises CozkError"""
+        self._l = self._decl()
+        self.cfg = cfg
+        h = ctypes.c_void_p()
+        rc = self._f(create)(ctypes.byref(cfg), *args, ctypes.byref(h))
+        self.h = h
+        if rc != OK:
+            msg = self.last_error() if h else ""
+            self.close()
+            raise CozkError(rc, msg or "?")
+
+    def prove(self, verify=True):
+        res = self.RESULT()
+        rc = self._f("_prove")(self.h, 1 if verify else 0, ctypes.byref(res))
+        if rc != OK:
+            raise CozkError(rc, self.last_error() or "?")
+        return res
+
+    def proof_bytes(self, res):
+        n = int(res.proof_len)
+        buf = (ctypes.c_uint8 * n)()
+        rc = self._f("_proof_bytes")(self.h, buf, n)
+        if rc != OK:
+            raise CozkError(rc, "proof_bytes")
+        return bytes(buf)
+
+    def last_error(self):
+        return (self._f("_error")(self.h) or b"").decode()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._f("_destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

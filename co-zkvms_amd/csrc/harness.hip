@@ -7,10 +7,8 @@
 //     GKR proof, final GKR claim == direct leaf evaluation, opening-reduction sumcheck, PST opening
 //     (pairing-free, trapdoor known).  Setup (SRS + witness resident in HBM) is separate from the
 //     timed `prove` step.
-#include <chrono>
-#include <thread>
-
 #include "host/prover.hpp"
+#include "host/runner.hpp"
 
 using namespace cozk;
 
@@ -59,10 +57,7 @@ __global__ void k_small_to_fr_u32(const uint32_t* in, fe* out, size_t n) {
 
 namespace {
 
-struct PartyState {
-    cozk_ctx* ctx = nullptr;
-    bool own_ctx = false;
-    int party = 0;
+struct PartyState : HarnessParty {
     // committed polynomials in commit order: first the shared (FR) ones, then the public ones
     std::vector<PolyH> polys;        // evaluation view (REP3 shares, or PLAIN Fr values for public polys)
     std::vector<VecH> commit_vecs;   // what the MSM consumes: share-a view (FR) or the compact small-scalar vector
@@ -73,8 +68,6 @@ struct PartyState {
     std::unique_ptr<PST13Setup> setup;
     // per-phase wall times of the last prove (ms)
     double t_commit = 0, t_construct = 0, t_gp = 0, t_eval = 0, t_open = 0, t_total = 0;
-    uint64_t star_up = 0, star_down = 0, ring_bytes = 0, star_msgs = 0;
-    std::string error;
 };
 
 struct ProofBundle {
@@ -112,21 +105,15 @@ struct ProofBundle {
     }
 };
 
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 }  // namespace
 
-struct cozk_harness {
+struct cozk_harness : HarnessHandle {
     cozk_harness_config cfg;
     int local_party = -1;  // >= 0: distributed form, only this (party, worker) participant lives in this process
     int local_worker = 0;
     int nparties = 1;
     size_t N = 0;
     std::vector<PartyState> parties;
-    std::string error;
-    Bytes last_proof;
 };
 
 // --------------------------------------------------------------------------- setup
@@ -411,10 +398,7 @@ static void worker_main(cozk_harness* h, PartyState& ps, StarNetWorker* star, Ri
     double t5 = now_ms();
     ps.t_open = t5 - t4;
     ps.t_total = t5 - t_start;
-    ps.star_up = star->bytes_up;
-    ps.star_down = star->bytes_down;
-    ps.star_msgs = star->n_msgs;
-    ps.ring_bytes = ring ? ring->bytes_sent : 0;
+    ps.record_net(star, ring);
 }
 
 // --------------------------------------------------------------------------- coordinator + verifier
@@ -630,208 +614,32 @@ static int coordinator_main(cozk_harness* h, StarNetCoordinator& net, ProofBundl
 #include "host/split_harness.hpp"
 
 // --------------------------------------------------------------------------- C ABI
-extern "C" {
-
-int cozk_harness_create(const cozk_harness_config* cfg, cozk_harness** out) {
-    if (!cfg || !out) return COZK_ERR_INVALID_ARG;
-    *out = nullptr;
-    cozk_harness* h = new cozk_harness();
-    h->cfg = *cfg;
-    try {
-        COZK_REQUIRE(cfg->mode == COZK_MODE_PLAIN || cfg->mode == COZK_MODE_REP3, "harness: bad mode");
-        COZK_REQUIRE(cfg->log_n >= 2 && cfg->log_n <= 24, "harness: log_n out of range");
-        COZK_REQUIRE(cfg->gp_batch >= 1 && cfg->gp_log_leaves >= 1, "harness: bad grand-product shape");
-        int gbits = 0;
-        while ((1 << gbits) < cfg->gp_batch) gbits++;
-        COZK_REQUIRE(gbits + cfg->gp_log_leaves >= cfg->log_n, "harness: grand-product point shorter than the opening point");
-        COZK_REQUIRE(cfg->n_fr + cfg->n_u16 + cfg->n_u32 + cfg->n_flags >= 1, "harness: no polynomials");
-        if (cfg->leaf_fingerprints)
-            COZK_REQUIRE(cfg->gp_log_leaves == cfg->log_n + 1 && cfg->n_fr >= 1 && cfg->log_workers == 0,
-                         "harness: leaf_fingerprints needs gp_log_leaves == log_n + 1, n_fr >= 1, log_workers == 0");
-        h->nparties = cfg->mode == COZK_MODE_REP3 ? 3 : 1;
-        h->N = (size_t)1 << cfg->log_n;
-        COZK_REQUIRE(cfg->log_workers >= 0 && cfg->log_workers <= 3, "harness: log_workers must be 0..3");
-        int W = 1 << cfg->log_workers;
-        if (W > 1) COZK_REQUIRE((cfg->gp_batch & (cfg->gp_batch - 1)) == 0, "split: gp_batch must be a power of two");
-        h->parties.resize((size_t)h->nparties * W);
-        for (int w = 0; w < W; w++)
-            for (int p = 0; p < h->nparties; p++) {
-                PartyState& ps = h->parties[(size_t)w * h->nparties + p];
-                ps.party = p;
-                int dev = cfg->mode == COZK_MODE_REP3 ? cfg->devices[p] : (W > 1 ? cfg->worker_devices[w] : cfg->devices[0]);
-                int rc = cozk_ctx_create(dev, &ps.ctx);
-                if (rc != COZK_OK) throw CozkError(rc, "harness: cannot create a context (no HIP device?)");
-                ps.own_ctx = true;
-                // several participants driven from this one process wait for each other's round messages: no resident
-                // round kernels (cozk_ctx_set_resident_rounds); a lone participant depends on nobody's GPU work, so it
-                // keeps them even when the host has other, unrelated contexts open on the device
-                cozk_ctx_set_resident_rounds(ps.ctx, h->nparties * W > 1 ? 0 : 1);
-                HIP_TRY(hipSetDevice(ps.ctx->device));
-                if (W > 1) setup_participant_split(h, ps, w);
-                else setup_party(h, ps);
-            }
-    } catch (const CozkError& e) {
-        h->error = e.what();
-        *out = h;  // caller reads the error, then destroys
-        return e.code;
-    } catch (const std::exception& e) {
-        h->error = e.what();
-        *out = h;
-        return COZK_ERR_INTERNAL;
-    }
-    *out = h;
-    return COZK_OK;
+// participant (party p, worker w): one context on its device; the worker sub-net (split) form when there are several workers
+static int participant_device(const cozk_harness_config& c, int party, int worker) {
+    return c.mode == COZK_MODE_REP3 ? c.devices[party] : (c.log_workers > 0 ? c.worker_devices[worker] : c.devices[0]);
 }
-
-const char* cozk_harness_error(const cozk_harness* h) { return h ? h->error.c_str() : "null harness"; }
-
-int cozk_harness_destroy(cozk_harness* h) {
-    if (!h) return COZK_OK;
-    for (auto& ps : h->parties) {
-        if (ps.ctx) (void)hipSetDevice(ps.ctx->device);
-        ps.polys.clear();
-        ps.commit_vecs.clear();
-        ps.small_polys.clear();
-        ps.small_commit_vecs.clear();
-        ps.leaves = LayerH();
-        ps.setup.reset();
-        if (ps.own_ctx && ps.ctx) cozk_ctx_destroy(ps.ctx);
-    }
-    delete h;
-    return COZK_OK;
+static void setup_participant(cozk_harness* h, PartyState& ps, int worker) {
+    if (h->cfg.log_workers > 0) setup_participant_split(h, ps, worker);
+    else setup_party(h, ps);
 }
-
-// one full pass of the hot path (the bench "step"); verify != 0 also runs the plain verifier
-int cozk_harness_prove(cozk_harness* h, int verify, cozk_harness_result* res) {
-    if (!h || !res) return COZK_ERR_INVALID_ARG;
-    memset(res, 0, sizeof *res);
-    res->verified = -1;
-    if (h->local_party >= 0) return COZK_ERR_INVALID_ARG;  // distributed harness: use cozk_harness_prove_distributed
-    const int W = 1 << h->cfg.log_workers;
-    const int nparty = h->nparties;
-    int np = nparty * W;  // participants: id = worker * nparty + party
-    InProcStar star(np);
-    std::vector<std::unique_ptr<InProcRing>> rings;  // one ring per worker index (its three parties)
-    for (int w = 0; w < W; w++) rings.emplace_back(new InProcRing(&star.abort));
-    std::vector<std::unique_ptr<InProcStarWorker>> sw;
-    std::vector<std::unique_ptr<InProcRingNet>> rn;
-    for (int p = 0; p < np; p++) {
-        sw.emplace_back(new InProcStarWorker(&star, p));
-        rn.emplace_back(nparty == 3 ? new InProcRingNet(rings[p / nparty].get(), p % nparty) : nullptr);
-        h->parties[p].error.clear();
-    }
-    std::vector<std::thread> threads;
-    double t0 = now_ms();
-    for (int p = 0; p < np; p++) {
-        threads.emplace_back([&, p] {
-            try {
-                if (W > 1) worker_main_split(h, h->parties[p], p / nparty, sw[p].get(), rn[p].get());
-                else worker_main(h, h->parties[p], sw[p].get(), rn[p].get());
-            } catch (const std::exception& e) {
-                h->parties[p].error = e.what();
-                star.abort.flag.store(true);
-            }
-        });
-    }
-    ProofBundle proof;
-    std::string why;
-    int verified = -1;
-    int rc = COZK_OK;
-    try {
-        InProcStarCoordinator coord(&star);
-        verified = W > 1 ? coordinator_main_split(h, coord, proof, verify != 0, why) : coordinator_main(h, coord, proof, verify != 0, why);
-    } catch (const std::exception& e) {
-        h->error = std::string("coordinator: ") + e.what();
-        star.abort.flag.store(true);
-        rc = COZK_ERR_INTERNAL;
-    }
-    for (auto& t : threads) t.join();
-    double t1 = now_ms();
-    for (int p = 0; p < np; p++) {
-        if (!h->parties[p].error.empty()) {
-            h->error = "participant " + std::to_string(p) + ": " + h->parties[p].error;
-            rc = COZK_ERR_INTERNAL;
-        }
-    }
-    if (rc != COZK_OK) return rc;
-    if (verified == 0) h->error = "verification failed: " + why;
-    res->verified = verified;
-    res->wall_ms = t1 - t0;
-    for (int p = 0; p < np; p++) {
-        PartyState& ps = h->parties[p];
-        res->t_commit_ms = std::max(res->t_commit_ms, ps.t_commit);
-        res->t_gp_construct_ms = std::max(res->t_gp_construct_ms, ps.t_construct);
-        res->t_gp_prove_ms = std::max(res->t_gp_prove_ms, ps.t_gp);
-        res->t_eval_ms = std::max(res->t_eval_ms, ps.t_eval);
-        res->t_open_ms = std::max(res->t_open_ms, ps.t_open);
-        res->t_worker_ms = std::max(res->t_worker_ms, ps.t_total);
-        res->bytes_star_up += ps.star_up;
-        res->bytes_star_down += ps.star_down;
-        res->bytes_ring += ps.ring_bytes;
-        res->star_messages += ps.star_msgs;
-    }
-    h->last_proof = proof.serialize();
-    res->proof_len = h->last_proof.size();
-    Sha256 s;
-    s.update(h->last_proof.data(), h->last_proof.size());
-    s.final(res->proof_digest);
-    return COZK_OK;
+static void participant_main(cozk_harness* h, PartyState& ps, int worker, StarNetWorker* star, RingNet* ring) {
+    if (h->cfg.log_workers > 0) worker_main_split(h, ps, worker, star, ring);
+    else worker_main(h, ps, star, ring);
 }
-
-// ---- distributed form: ONE party per process / GPU (BASELINE config 3: "one MI355X per party").
-// Every process runs its own copy of the (deterministic) coordinator: a "star" gather is an all-gather of
-// the parties' messages through the host's transport (`cozk_hub_net`, e.g. torch.distributed / RCCL), after
-// which each copy derives the same challenge -- no coordinator process, no extra hop.  The ring reshare goes
-// through `cozk_ring_net` on device pointers (an RCCL send/recv pair over xGMI).
-int cozk_harness_create_participant(const cozk_harness_config* cfg, int local_party, int local_worker, cozk_harness** out) {
-    if (!cfg || !out) return COZK_ERR_INVALID_ARG;
-    *out = nullptr;
-    cozk_harness* h = new cozk_harness();
-    h->cfg = *cfg;
-    try {
-        COZK_REQUIRE(cfg->mode == COZK_MODE_PLAIN || cfg->mode == COZK_MODE_REP3, "harness: bad mode");
-        int np = cfg->mode == COZK_MODE_REP3 ? 3 : 1;
-        COZK_REQUIRE(cfg->log_workers >= 0 && cfg->log_workers <= 3, "harness: log_workers must be 0..3");
-        int W = 1 << cfg->log_workers;
-        COZK_REQUIRE(local_party >= 0 && local_party < np && local_worker >= 0 && local_worker < W, "harness_create_participant: bad (party, worker)");
-        COZK_REQUIRE(cfg->log_n >= 2 && cfg->log_n <= 24 && cfg->gp_batch >= 1 && cfg->gp_log_leaves >= 1, "harness: bad shape");
-        if (cfg->leaf_fingerprints)
-            COZK_REQUIRE(cfg->gp_log_leaves == cfg->log_n + 1 && cfg->n_fr >= 1 && cfg->log_workers == 0,
-                         "harness: leaf_fingerprints needs gp_log_leaves == log_n + 1, n_fr >= 1, log_workers == 0");
-        int gbits = 0;
-        while ((1 << gbits) < cfg->gp_batch) gbits++;
-        COZK_REQUIRE(gbits + cfg->gp_log_leaves >= cfg->log_n, "harness: grand-product point shorter than the opening point");
-        if (W > 1) COZK_REQUIRE((cfg->gp_batch & (cfg->gp_batch - 1)) == 0, "split: gp_batch must be a power of two");
-        h->nparties = np;
-        h->local_party = local_party;
-        h->local_worker = local_worker;
-        h->N = (size_t)1 << cfg->log_n;
-        h->parties.resize((size_t)np * W);
-        for (int w = 0; w < W; w++)
-            for (int p = 0; p < np; p++) h->parties[(size_t)w * np + p].party = p;
-        PartyState& ps = h->parties[(size_t)local_worker * np + local_party];
-        int dev = cfg->mode == COZK_MODE_REP3 ? cfg->devices[local_party] : (W > 1 ? cfg->worker_devices[local_worker] : cfg->devices[0]);
-        int rc = cozk_ctx_create(dev, &ps.ctx);
-        if (rc != COZK_OK) throw CozkError(rc, "harness: cannot create a context (no HIP device?)");
-        ps.own_ctx = true;
-        HIP_TRY(hipSetDevice(ps.ctx->device));
-        if (W > 1) setup_participant_split(h, ps, local_worker);
-        else setup_party(h, ps);
-    } catch (const CozkError& e) {
-        h->error = e.what();
-        *out = h;
-        return e.code;
-    } catch (const std::exception& e) {
-        h->error = e.what();
-        *out = h;
-        return COZK_ERR_INTERNAL;
-    }
-    *out = h;
-    return COZK_OK;
+static int coordinate(cozk_harness* h, StarNetCoordinator& net, ProofBundle& proof, bool verify, std::string& why) {
+    return h->cfg.log_workers > 0 ? coordinator_main_split(h, net, proof, verify, why) : coordinator_main(h, net, proof, verify, why);
 }
-
-int cozk_harness_create_party(const cozk_harness_config* cfg, int local_party, cozk_harness** out) {
-    return cozk_harness_create_participant(cfg, local_party, 0, out);
+static void fold_participant(cozk_harness_result* res, const PartyState& ps) {
+    res->t_commit_ms = std::max(res->t_commit_ms, ps.t_commit);
+    res->t_gp_construct_ms = std::max(res->t_gp_construct_ms, ps.t_construct);
+    res->t_gp_prove_ms = std::max(res->t_gp_prove_ms, ps.t_gp);
+    res->t_eval_ms = std::max(res->t_eval_ms, ps.t_eval);
+    res->t_open_ms = std::max(res->t_open_ms, ps.t_open);
+    res->t_worker_ms = std::max(res->t_worker_ms, ps.t_total);
+    res->bytes_star_up += ps.star_up;
+    res->bytes_star_down += ps.star_down;
+    res->bytes_ring += ps.ring_bytes;
+    res->star_messages += ps.star_msgs;
 }
 
 namespace {
@@ -876,6 +684,121 @@ struct HubStarCoordinator : StarNetCoordinator {
 };
 }  // namespace
 
+extern "C" {
+
+int cozk_harness_create(const cozk_harness_config* cfg, cozk_harness** out) {
+    return harness_create(cfg, out, [&](cozk_harness* h) {
+        COZK_REQUIRE(cfg->mode == COZK_MODE_PLAIN || cfg->mode == COZK_MODE_REP3, "harness: bad mode");
+        COZK_REQUIRE(cfg->log_n >= 2 && cfg->log_n <= 24, "harness: log_n out of range");
+        COZK_REQUIRE(cfg->gp_batch >= 1 && cfg->gp_log_leaves >= 1, "harness: bad grand-product shape");
+        int gbits = 0;
+        while ((1 << gbits) < cfg->gp_batch) gbits++;
+        COZK_REQUIRE(gbits + cfg->gp_log_leaves >= cfg->log_n, "harness: grand-product point shorter than the opening point");
+        COZK_REQUIRE(cfg->n_fr + cfg->n_u16 + cfg->n_u32 + cfg->n_flags >= 1, "harness: no polynomials");
+        if (cfg->leaf_fingerprints)
+            COZK_REQUIRE(cfg->gp_log_leaves == cfg->log_n + 1 && cfg->n_fr >= 1 && cfg->log_workers == 0,
+                         "harness: leaf_fingerprints needs gp_log_leaves == log_n + 1, n_fr >= 1, log_workers == 0");
+        h->nparties = cfg->mode == COZK_MODE_REP3 ? 3 : 1;
+        h->N = (size_t)1 << cfg->log_n;
+        COZK_REQUIRE(cfg->log_workers >= 0 && cfg->log_workers <= 3, "harness: log_workers must be 0..3");
+        int W = 1 << cfg->log_workers;
+        if (W > 1) COZK_REQUIRE((cfg->gp_batch & (cfg->gp_batch - 1)) == 0, "split: gp_batch must be a power of two");
+        h->parties.resize((size_t)h->nparties * W);
+        for (int w = 0; w < W; w++)
+            for (int p = 0; p < h->nparties; p++) {
+                PartyState& ps = h->parties[(size_t)w * h->nparties + p];
+                ps.party = p;
+                ps.open_ctx(participant_device(*cfg, p, w), "harness: cannot create a context (no HIP device?)");
+                // several participants driven from this one process wait for each other's round messages: no resident
+                // round kernels (cozk_ctx_set_resident_rounds); a lone participant depends on nobody's GPU work, so it
+                // keeps them even when the host has other, unrelated contexts open on the device
+                cozk_ctx_set_resident_rounds(ps.ctx, h->nparties * W > 1 ? 0 : 1);
+                setup_participant(h, ps, w);
+            }
+    });
+}
+
+const char* cozk_harness_error(const cozk_harness* h) { return harness_error(h); }
+
+int cozk_harness_destroy(cozk_harness* h) {
+    if (!h) return COZK_OK;
+    release_parties(h->parties, [](PartyState& ps) {
+        ps.polys.clear();
+        ps.commit_vecs.clear();
+        ps.small_polys.clear();
+        ps.small_commit_vecs.clear();
+        ps.leaves = LayerH();
+        ps.setup.reset();
+    });
+    delete h;
+    return COZK_OK;
+}
+
+// one full pass of the hot path (the bench "step"); verify != 0 also runs the plain verifier
+int cozk_harness_prove(cozk_harness* h, int verify, cozk_harness_result* res) {
+    if (!h || !res) return COZK_ERR_INVALID_ARG;
+    memset(res, 0, sizeof *res);
+    res->verified = -1;
+    if (h->local_party >= 0) return COZK_ERR_INVALID_ARG;  // distributed harness: use cozk_harness_prove_distributed
+    const int nparty = h->nparties;
+    InProcNets nets((int)h->parties.size(), nparty == 3);  // participant id = worker * nparty + party; a ring per worker index
+    std::vector<Participant> parts;
+    add_participants(parts, "participant", h->parties,
+                     [&](PartyState& ps, int p) { participant_main(h, ps, p / nparty, nets.worker(p), nets.ring(p)); });
+    ProofBundle proof;
+    std::string why;
+    int verified = -1;
+    double wall_ms = 0;
+    int rc = run_in_process(nets, parts, [&] {
+        InProcStarCoordinator coord(&nets.star);
+        verified = coordinate(h, coord, proof, verify != 0, why);
+    }, h->error, wall_ms);
+    if (rc != COZK_OK) return rc;
+    if (verified == 0) h->error = "verification failed: " + why;
+    res->verified = verified;
+    res->wall_ms = wall_ms;
+    for (const PartyState& ps : h->parties) fold_participant(res, ps);
+    finish_proof(h, proof.serialize(), res);
+    return COZK_OK;
+}
+
+// ---- distributed form: ONE party per process / GPU (BASELINE config 3: "one MI355X per party").
+// Every process runs its own copy of the (deterministic) coordinator: a "star" gather is an all-gather of
+// the parties' messages through the host's transport (`cozk_hub_net`, e.g. torch.distributed / RCCL), after
+// which each copy derives the same challenge -- no coordinator process, no extra hop.  The ring reshare goes
+// through `cozk_ring_net` on device pointers (an RCCL send/recv pair over xGMI).
+int cozk_harness_create_participant(const cozk_harness_config* cfg, int local_party, int local_worker, cozk_harness** out) {
+    return harness_create(cfg, out, [&](cozk_harness* h) {
+        COZK_REQUIRE(cfg->mode == COZK_MODE_PLAIN || cfg->mode == COZK_MODE_REP3, "harness: bad mode");
+        int np = cfg->mode == COZK_MODE_REP3 ? 3 : 1;
+        COZK_REQUIRE(cfg->log_workers >= 0 && cfg->log_workers <= 3, "harness: log_workers must be 0..3");
+        int W = 1 << cfg->log_workers;
+        COZK_REQUIRE(local_party >= 0 && local_party < np && local_worker >= 0 && local_worker < W, "harness_create_participant: bad (party, worker)");
+        COZK_REQUIRE(cfg->log_n >= 2 && cfg->log_n <= 24 && cfg->gp_batch >= 1 && cfg->gp_log_leaves >= 1, "harness: bad shape");
+        if (cfg->leaf_fingerprints)
+            COZK_REQUIRE(cfg->gp_log_leaves == cfg->log_n + 1 && cfg->n_fr >= 1 && cfg->log_workers == 0,
+                         "harness: leaf_fingerprints needs gp_log_leaves == log_n + 1, n_fr >= 1, log_workers == 0");
+        int gbits = 0;
+        while ((1 << gbits) < cfg->gp_batch) gbits++;
+        COZK_REQUIRE(gbits + cfg->gp_log_leaves >= cfg->log_n, "harness: grand-product point shorter than the opening point");
+        if (W > 1) COZK_REQUIRE((cfg->gp_batch & (cfg->gp_batch - 1)) == 0, "split: gp_batch must be a power of two");
+        h->nparties = np;
+        h->local_party = local_party;
+        h->local_worker = local_worker;
+        h->N = (size_t)1 << cfg->log_n;
+        h->parties.resize((size_t)np * W);
+        for (int w = 0; w < W; w++)
+            for (int p = 0; p < np; p++) h->parties[(size_t)w * np + p].party = p;
+        PartyState& ps = h->parties[(size_t)local_worker * np + local_party];
+        ps.open_ctx(participant_device(*cfg, local_party, local_worker), "harness: cannot create a context (no HIP device?)");
+        setup_participant(h, ps, local_worker);
+    });
+}
+
+int cozk_harness_create_party(const cozk_harness_config* cfg, int local_party, cozk_harness** out) {
+    return cozk_harness_create_participant(cfg, local_party, 0, out);
+}
+
 int cozk_harness_prove_distributed(cozk_harness* h, const cozk_hub_net* hub, const cozk_ring_net* ring, int verify,
                                    cozk_harness_result* res) {
     if (!h || !hub || !res || h->local_party < 0) return COZK_ERR_INVALID_ARG;
@@ -885,64 +808,29 @@ int cozk_harness_prove_distributed(cozk_harness* h, const cozk_hub_net* hub, con
     if (hub->n_participants != nparty * W || hub->my_index != me || (nparty == 3 && !ring)) return COZK_ERR_INVALID_ARG;
     memset(res, 0, sizeof *res);
     res->verified = -1;
-    InProcStar star(nparty * W);
-    InProcStarWorker sw(&star, me);
+    InProcNets nets(nparty * W);  // only participant `me`'s end is used: the gathers and the ring go through the host's transports
     std::unique_ptr<CallbackRingNet> rnp(nparty == 3 ? new CallbackRingNet(*ring) : nullptr);
     PartyState& ps = h->parties[me];
-    ps.error.clear();
-    double t0 = now_ms();
-    std::thread worker([&] {
-        try {
-            if (W > 1) worker_main_split(h, ps, h->local_worker, &sw, rnp.get());
-            else worker_main(h, ps, &sw, rnp.get());
-        } catch (const std::exception& e) {
-            ps.error = e.what();
-            star.abort.flag.store(true);
-        }
-    });
+    std::vector<Participant> parts{{"participant", me, &ps, [&] { participant_main(h, ps, h->local_worker, nets.worker(me), rnp.get()); }}};
     ProofBundle proof;
     std::string why;
     int verified = -1;
-    int rc = COZK_OK;
-    double hub_wait = 0;
+    double wall_ms = 0, hub_wait = 0;
     uint64_t hub_n = 0;
-    try {
-        HubStarCoordinator coord(&star, *hub, me);
-        verified = W > 1 ? coordinator_main_split(h, coord, proof, verify != 0, why) : coordinator_main(h, coord, proof, verify != 0, why);
+    int rc = run_in_process(nets, parts, [&] {
+        HubStarCoordinator coord(&nets.star, *hub, me);
+        verified = coordinate(h, coord, proof, verify != 0, why);
         hub_wait = coord.t_wait_ms;
         hub_n = coord.n_exchanges;
-    } catch (const std::exception& e) {
-        h->error = std::string("coordinator: ") + e.what();
-        star.abort.flag.store(true);
-        rc = COZK_ERR_INTERNAL;
-    }
-    worker.join();
-    double t1 = now_ms();
-    if (!ps.error.empty()) {
-        h->error = "participant " + std::to_string(me) + ": " + ps.error;
-        rc = COZK_ERR_INTERNAL;
-    }
+    }, h->error, wall_ms);
     if (rc != COZK_OK) return rc;
     if (verified == 0) h->error = "verification failed: " + why;
     res->verified = verified;
-    res->wall_ms = t1 - t0;
-    res->t_commit_ms = ps.t_commit;
-    res->t_gp_construct_ms = ps.t_construct;
-    res->t_gp_prove_ms = ps.t_gp;
-    res->t_eval_ms = ps.t_eval;
-    res->t_open_ms = ps.t_open;
-    res->t_worker_ms = ps.t_total;
-    res->bytes_star_up = ps.star_up;
-    res->bytes_star_down = ps.star_down;
-    res->bytes_ring = ps.ring_bytes;
-    res->star_messages = ps.star_msgs;
+    res->wall_ms = wall_ms;
+    fold_participant(res, ps);
     res->t_hub_wait_ms = hub_wait;
     res->hub_exchanges = hub_n;
-    h->last_proof = proof.serialize();
-    res->proof_len = h->last_proof.size();
-    Sha256 s;
-    s.update(h->last_proof.data(), h->last_proof.size());
-    s.final(res->proof_digest);
+    finish_proof(h, proof.serialize(), res);
     return COZK_OK;
 }
 
@@ -959,17 +847,10 @@ int cozk_copy(cozk_ctx* ctx, void* dst, const void* src, size_t nbytes) {
 }
 
 // serialized proof of the last prove (cozk_harness_result.proof_len bytes)
-int cozk_harness_proof_bytes(const cozk_harness* h, uint8_t* out, size_t cap) {
-    if (!h || !out || cap < h->last_proof.size()) return COZK_ERR_INVALID_ARG;
-    memcpy(out, h->last_proof.data(), h->last_proof.size());
-    return COZK_OK;
-}
+int cozk_harness_proof_bytes(const cozk_harness* h, uint8_t* out, size_t cap) { return harness_proof_bytes(h, out, cap); }
 
 // context of party p (profiling hooks: cozk_prof_enable / cozk_prof_read)
-cozk_ctx* cozk_harness_ctx(cozk_harness* h, int party) {
-    if (!h || party < 0 || party >= (int)h->parties.size()) return nullptr;
-    return h->parties[party].ctx;
-}
+cozk_ctx* cozk_harness_ctx(cozk_harness* h, int party) { return h ? party_ctx(h->parties, party) : nullptr; }
 
 }  // extern "C"
 

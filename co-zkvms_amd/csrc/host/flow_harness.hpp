@@ -42,9 +42,7 @@ struct FlowIdx {
     }
 };
 
-struct FlowParty {
-    cozk_ctx* ctx = nullptr;
-    int party = 0;
+struct FlowParty : HarnessParty {
     std::vector<PolyH> polys;       // evaluation view (REP3 shares, or PLAIN Fr values for public polynomials), commit order
     std::vector<VecH> commit_vecs;  // what the MSM and the fingerprints consume: share-a view, or the compact public column
     std::vector<VecH> msm_vecs;     // PLAIN mode: a narrow (U32 / U64) copy of a secret column whose values fit, for the MSM only
@@ -57,11 +55,9 @@ struct FlowParty {
     VecH io_range, v_io;               // FR vectors of MEM entries (output check)
     double t_commit = 0, t_bytecode = 0, t_primary = 0, t_lookups_gp = 0, t_rw = 0, t_spartan = 0, t_open = 0, t_total = 0;
     SpartanTimes sp_times;
-    uint64_t star_up = 0, star_down = 0, star_msgs = 0, ring_bytes = 0;
-    std::string error;
 };
 
-struct cozk_flow {
+struct cozk_flow : HarnessHandle {
     cozk_flow_config cfg;
     int nparties = 1;
     size_t N = 0, M = 0, B = 0, MEM = 0;
@@ -77,8 +73,6 @@ struct cozk_flow {
     std::vector<size_t> lens;
     std::vector<std::vector<uint64_t>> bc_table_clear, subtables_clear;
     std::vector<fe> io_range_clear, v_io_clear;
-    std::string error;
-    Bytes last_proof;
 };
 
 namespace {
@@ -672,10 +666,7 @@ void flow_worker_main(cozk_flow* h, FlowParty& ps, StarNetWorker* star, RingNet*
     double t7 = now_ms();
     ps.t_open = t7 - t6;
     ps.t_total = t7 - t0;
-    ps.star_up = star->bytes_up;
-    ps.star_down = star->bytes_down;
-    ps.star_msgs = star->n_msgs;
-    ps.ring_bytes = ring ? ring->bytes_sent : 0;
+    ps.record_net(star, ring);
 }
 
 // ------------------------------------------------------------------------------------------------ coordinator
@@ -1069,11 +1060,7 @@ bool flow_verify(cozk_flow* h, const FlowProof& proof, std::string& why) {
 extern "C" {
 
 int cozk_flow_create(const cozk_flow_config* cfg, cozk_flow** out) {
-    if (!cfg || !out) return COZK_ERR_INVALID_ARG;
-    *out = nullptr;
-    cozk_flow* h = new cozk_flow();
-    h->cfg = *cfg;
-    try {
+    return harness_create(cfg, out, [&](cozk_flow* h) {
         COZK_REQUIRE(cfg->mode == COZK_MODE_PLAIN || cfg->mode == COZK_MODE_REP3, "flow: mode");
         COZK_REQUIRE(cfg->log_n >= 1 && cfg->log_n <= 22, "flow: log_n in 1..22");
         COZK_REQUIRE(cfg->log_m >= 1 && cfg->log_m <= cfg->log_n && cfg->log_b >= 1 && cfg->log_b <= cfg->log_n && cfg->log_mem >= 2 && cfg->log_mem <= cfg->log_n,
@@ -1091,31 +1078,18 @@ int cozk_flow_create(const cozk_flow_config* cfg, cozk_flow** out) {
         for (int p = 0; p < h->nparties; p++) {
             FlowParty& ps = h->parties[(size_t)p];
             ps.party = p;
-            int rc = cozk_ctx_create(cfg->devices[p], &ps.ctx);
-            if (rc != COZK_OK) throw CozkError(rc, "flow: cannot create a context (no HIP device?)");
+            ps.open_ctx(cfg->devices[p], "flow: cannot create a context (no HIP device?)");
             cozk_ctx_set_resident_rounds(ps.ctx, h->nparties > 1 ? 0 : 1);
-            HIP_TRY(hipSetDevice(ps.ctx->device));
             flow_setup_party(h, ps);
         }
-    } catch (const CozkError& e) {
-        h->error = e.what();
-        *out = h;
-        return e.code;
-    } catch (const std::exception& e) {
-        h->error = e.what();
-        *out = h;
-        return COZK_ERR_INTERNAL;
-    }
-    *out = h;
-    return COZK_OK;
+    });
 }
 
-const char* cozk_flow_error(const cozk_flow* h) { return h ? h->error.c_str() : "null harness"; }
+const char* cozk_flow_error(const cozk_flow* h) { return harness_error(h); }
 
 int cozk_flow_destroy(cozk_flow* h) {
     if (!h) return COZK_OK;
-    for (auto& ps : h->parties) {
-        if (ps.ctx) (void)hipSetDevice(ps.ctx->device);
+    release_parties(h->parties, [](FlowParty& ps) {
         ps.polys.clear();
         ps.commit_vecs.clear();
         ps.msm_vecs.clear();
@@ -1126,64 +1100,31 @@ int cozk_flow_destroy(cozk_flow* h) {
         ps.mem_flags.clear();
         ps.io_range = VecH();
         ps.v_io = VecH();
-        if (ps.ctx) cozk_ctx_destroy(ps.ctx);
-    }
+    });
     delete h;
     return COZK_OK;
 }
 
 size_t cozk_flow_num_polys(const cozk_flow* h) { return h ? (size_t)h->ix.count : 0; }
 
-cozk_ctx* cozk_flow_ctx(cozk_flow* h, int party) {
-    if (!h || party < 0 || party >= (int)h->parties.size()) return nullptr;
-    return h->parties[(size_t)party].ctx;
-}
+cozk_ctx* cozk_flow_ctx(cozk_flow* h, int party) { return h ? party_ctx(h->parties, party) : nullptr; }
 
 int cozk_flow_prove(cozk_flow* h, int verify, cozk_flow_result* res) {
     if (!h || !res) return COZK_ERR_INVALID_ARG;
     memset(res, 0, sizeof *res);
     res->verified = -1;
     const int np = h->nparties;
-    InProcStar star(np);
-    InProcRing ring(&star.abort);
-    std::vector<std::unique_ptr<InProcStarWorker>> sw;
-    std::vector<std::unique_ptr<InProcRingNet>> rn;
-    for (int p = 0; p < np; p++) {
-        sw.emplace_back(new InProcStarWorker(&star, p));
-        rn.emplace_back(np == 3 ? new InProcRingNet(&ring, p) : nullptr);
-        h->parties[(size_t)p].error.clear();
-    }
-    std::vector<std::thread> threads;
-    double t0 = now_ms();
-    for (int p = 0; p < np; p++) {
-        threads.emplace_back([&, p] {
-            try {
-                flow_worker_main(h, h->parties[(size_t)p], sw[(size_t)p].get(), rn[(size_t)p].get());
-            } catch (const std::exception& e) {
-                h->parties[(size_t)p].error = e.what();
-                star.abort.flag.store(true);
-            }
-        });
-    }
+    InProcNets nets(np, np == 3);
+    std::vector<Participant> parts;
+    add_participants(parts, "party", h->parties, [&](FlowParty& ps, int p) { flow_worker_main(h, ps, nets.worker(p), nets.ring(p)); });
     FlowProof proof;
-    int rc = COZK_OK;
-    try {
-        InProcStarCoordinator coord(&star);
+    double wall_ms = 0;
+    int rc = run_in_process(nets, parts, [&] {
+        InProcStarCoordinator coord(&nets.star);
         flow_coordinate(h, coord, proof);
-    } catch (const std::exception& e) {
-        h->error = std::string("coordinator: ") + e.what();
-        star.abort.flag.store(true);
-        rc = COZK_ERR_INTERNAL;
-    }
-    for (auto& t : threads) t.join();
-    double t1 = now_ms();
-    for (int p = 0; p < np; p++)
-        if (!h->parties[(size_t)p].error.empty()) {
-            h->error = "party " + std::to_string(p) + ": " + h->parties[(size_t)p].error;
-            rc = COZK_ERR_INTERNAL;
-        }
+    }, h->error, wall_ms);
     if (rc != COZK_OK) return rc;
-    res->wall_ms = t1 - t0;
+    res->wall_ms = wall_ms;  // the verifier below is outside the clock
     if (verify) {
         std::string why;
         try {
@@ -1195,8 +1136,7 @@ int cozk_flow_prove(cozk_flow* h, int verify, cozk_flow_result* res) {
         }
         if (res->verified == 0) h->error = "verification failed: " + why;
     }
-    for (int p = 0; p < np; p++) {
-        FlowParty& ps = h->parties[(size_t)p];
+    for (const FlowParty& ps : h->parties) {
         res->t_commit_ms = std::max(res->t_commit_ms, ps.t_commit);
         res->t_bytecode_ms = std::max(res->t_bytecode_ms, ps.t_bytecode);
         res->t_primary_ms = std::max(res->t_primary_ms, ps.t_primary);
@@ -1213,18 +1153,10 @@ int cozk_flow_prove(cozk_flow* h, int verify, cozk_flow_result* res) {
     }
     res->n_polys = (uint64_t)h->ix.count;
     res->n_openings = 10;
-    h->last_proof = proof.serialize();
-    res->proof_len = h->last_proof.size();
-    Sha256 s;
-    s.update(h->last_proof.data(), h->last_proof.size());
-    s.final(res->proof_digest);
+    finish_proof(h, proof.serialize(), res);
     return COZK_OK;
 }
 
-int cozk_flow_proof_bytes(const cozk_flow* h, uint8_t* out, size_t cap) {
-    if (!h || !out || cap < h->last_proof.size()) return COZK_ERR_INVALID_ARG;
-    memcpy(out, h->last_proof.data(), h->last_proof.size());
-    return COZK_OK;
-}
+int cozk_flow_proof_bytes(const cozk_flow* h, uint8_t* out, size_t cap) { return harness_proof_bytes(h, out, cap); }
 
 }  // extern "C"

@@ -11,10 +11,7 @@
 // zeros, as sparse_grand_product.rs:118-131 pads them).  oracle/pylookups.py restates the pipeline over the SPARSE oracle.
 #pragma once
 
-struct LookupsParty {
-    cozk_ctx* ctx = nullptr;
-    bool own_ctx = false;
-    int party = 0;
+struct LookupsParty : HarnessParty {
     std::vector<VecH> flags;  // n_pairs U8 columns
     VecH fp_a, fp_b;          // 2 * n_pairs circuits x N, circuit-major
     // primary sumcheck (cfg.primary): instruction flags, E polynomials, lookup_outputs
@@ -22,11 +19,9 @@ struct LookupsParty {
     std::vector<PolyH> E;
     PolyH outputs;
     double t_primary = 0, t_construct = 0, t_prove = 0, t_total = 0;
-    uint64_t star_up = 0, star_down = 0, star_msgs = 0, ring_bytes = 0;
-    std::string error;
 };
 
-struct cozk_lookups {
+struct cozk_lookups : HarnessHandle {
     cozk_lookups_config cfg;
     int nparties = 1;
     size_t N = 0, batch = 0;
@@ -39,8 +34,6 @@ struct cozk_lookups {
     std::vector<fe> outputs_plain;         // lookup_outputs in the clear (the dealer's view)
     std::vector<PolyH> v_E, v_iflags;
     PolyH v_outputs;
-    std::string error;
-    Bytes last_proof;
 };
 
 namespace {
@@ -444,10 +437,7 @@ void lookups_worker_main(cozk_lookups* h, LookupsParty& ps, StarNetWorker* star,
     double t2 = now_ms();
     ps.t_prove = t2 - t1;
     ps.t_total = t2 - tp0;
-    ps.star_up = star->bytes_up;
-    ps.star_down = star->bytes_down;
-    ps.star_msgs = star->n_msgs;
-    ps.ring_bytes = ring ? ring->bytes_sent : 0;
+    ps.record_net(star, ring);
 }
 
 // MLE of `polys` (per circuit, length N each, circuit-major, padded to L circuits with `pad`) at the big-endian point r
@@ -554,11 +544,7 @@ int lookups_coordinator_main(cozk_lookups* h, StarNetCoordinator& net, StarNetCo
 extern "C" {
 
 int cozk_lookups_create(const cozk_lookups_config* cfg, cozk_lookups** out) {
-    if (!cfg || !out) return COZK_ERR_INVALID_ARG;
-    *out = nullptr;
-    cozk_lookups* h = new cozk_lookups();
-    h->cfg = *cfg;
-    try {
+    return harness_create(cfg, out, [&](cozk_lookups* h) {
         COZK_REQUIRE(cfg->mode == COZK_MODE_PLAIN || cfg->mode == COZK_MODE_REP3, "lookups: mode");
         COZK_REQUIRE(cfg->log_workers >= 0 && cfg->log_workers <= 3 && cfg->log_workers < cfg->log_n, "lookups: log_workers in 0..3, below log_n");
         COZK_REQUIRE(cfg->log_n >= 1 && cfg->log_n <= 24 && cfg->n_pairs >= 1 && cfg->n_pairs <= 128 && cfg->density_pct >= 0 && cfg->density_pct <= 100,
@@ -572,11 +558,8 @@ int cozk_lookups_create(const cozk_lookups_config* cfg, cozk_lookups** out) {
         for (int p = 0; p < h->nparties; p++) {
             LookupsParty& ps = h->parties[p];
             ps.party = p;
-            int rc = cozk_ctx_create(cfg->devices[p], &ps.ctx);
-            if (rc != COZK_OK) throw CozkError(rc, "lookups: cannot create a context (no HIP device?)");
-            ps.own_ctx = true;
+            ps.open_ctx(cfg->devices[p], "lookups: cannot create a context (no HIP device?)");
             cozk_ctx_set_resident_rounds(ps.ctx, h->nparties > 1 ? 0 : 1);
-            HIP_TRY(hipSetDevice(ps.ctx->device));
             lookups_setup_party(h, ps);
             if (cfg->primary) lookups_setup_primary_party(h, ps);
         }
@@ -585,33 +568,21 @@ int cozk_lookups_create(const cozk_lookups_config* cfg, cozk_lookups** out) {
         HIP_TRY(hipSetDevice(h->vctx->device));
         lookups_setup_verifier(h);
         if (cfg->primary) lookups_setup_primary_verifier(h);
-    } catch (const CozkError& e) {
-        h->error = e.what();
-        *out = h;
-        return e.code;
-    } catch (const std::exception& e) {
-        h->error = e.what();
-        *out = h;
-        return COZK_ERR_INTERNAL;
-    }
-    *out = h;
-    return COZK_OK;
+    });
 }
 
-const char* cozk_lookups_error(const cozk_lookups* h) { return h ? h->error.c_str() : "null harness"; }
+const char* cozk_lookups_error(const cozk_lookups* h) { return harness_error(h); }
 
 int cozk_lookups_destroy(cozk_lookups* h) {
     if (!h) return COZK_OK;
-    for (auto& ps : h->parties) {
-        if (ps.ctx) (void)hipSetDevice(ps.ctx->device);
+    release_parties(h->parties, [](LookupsParty& ps) {
         ps.flags.clear();
         ps.fp_a = VecH();
         ps.fp_b = VecH();
         ps.instr_flags.clear();
         ps.E.clear();
         ps.outputs = PolyH();
-        if (ps.own_ctx && ps.ctx) cozk_ctx_destroy(ps.ctx);
-    }
+    });
     if (h->vctx) {
         (void)hipSetDevice(h->vctx->device);
         h->v_flags.clear();
@@ -629,62 +600,29 @@ int cozk_lookups_prove(cozk_lookups* h, int verify, cozk_lookups_result* res) {
     if (!h || !res) return COZK_ERR_INVALID_ARG;
     memset(res, 0, sizeof *res);
     res->verified = -1;
-    int np = h->nparties;
+    const int np = h->nparties;
     const int W = 1 << h->cfg.log_workers;
-    InProcStar star(np);
-    InProcStar pstar(np * W);  // the primary sumcheck's worker sub-nets: participant = worker * parties + party
-    pstar.abort.flag.store(false);
-    InProcRing ring(&star.abort);
-    std::vector<std::unique_ptr<InProcStarWorker>> sw, psw;
-    std::vector<std::unique_ptr<InProcRingNet>> rn;
-    for (int p = 0; p < np; p++) {
-        sw.emplace_back(new InProcStarWorker(&star, p));
-        rn.emplace_back(np == 3 ? new InProcRingNet(&ring, p) : nullptr);
-        h->parties[p].error.clear();
-    }
-    for (int id = 0; id < np * W; id++) psw.emplace_back(new InProcStarWorker(&pstar, id));
-    std::vector<std::thread> threads;
-    double t0 = now_ms();
-    for (int p = 0; p < np; p++) {
-        threads.emplace_back([&, p] {
-            try {
-                std::vector<StarNetWorker*> mine;
-                for (int w = 0; w < W; w++) mine.push_back(psw[(size_t)w * np + p].get());
-                lookups_worker_main(h, h->parties[p], sw[p].get(), mine, rn[p].get());
-            } catch (const std::exception& e) {
-                h->parties[p].error = e.what();
-                star.abort.flag.store(true);
-                pstar.abort.flag.store(true);
-            }
-        });
-    }
+    // second star: the primary sumcheck's worker sub-nets, participant = worker * parties + party
+    InProcNets nets(np, np == 3, np * W);
+    std::vector<Participant> parts;
+    add_participants(parts, "party", h->parties, [&](LookupsParty& ps, int p) {
+        std::vector<StarNetWorker*> mine;
+        for (int w = 0; w < W; w++) mine.push_back(nets.sub_worker(w * np + p));
+        lookups_worker_main(h, ps, nets.worker(p), mine, nets.ring(p));
+    });
     LookupsProof proof;
     std::string why;
     int verified = -1;
-    int rc = COZK_OK;
-    try {
-        InProcStarCoordinator coord(&star), pcoord(&pstar);
+    double wall_ms = 0;
+    int rc = run_in_process(nets, parts, [&] {
+        InProcStarCoordinator coord(&nets.star), pcoord(nets.sub.get());
         verified = lookups_coordinator_main(h, coord, pcoord, proof, verify != 0, why);
-    } catch (const std::exception& e) {
-        h->error = std::string("coordinator: ") + e.what();
-        star.abort.flag.store(true);
-        pstar.abort.flag.store(true);
-        rc = COZK_ERR_INTERNAL;
-    }
-    for (auto& t : threads) t.join();
-    double t1 = now_ms();
-    for (int p = 0; p < np; p++) {
-        if (!h->parties[p].error.empty()) {
-            h->error = "party " + std::to_string(p) + ": " + h->parties[p].error;
-            rc = COZK_ERR_INTERNAL;
-        }
-    }
+    }, h->error, wall_ms);
     if (rc != COZK_OK) return rc;
     if (verified == 0) h->error = "verification failed: " + why;
     res->verified = verified;
-    res->wall_ms = t1 - t0;
-    for (int p = 0; p < np; p++) {
-        LookupsParty& ps = h->parties[p];
+    res->wall_ms = wall_ms;
+    for (const LookupsParty& ps : h->parties) {
         res->t_primary_ms = std::max(res->t_primary_ms, ps.t_primary);
         res->t_construct_ms = std::max(res->t_construct_ms, ps.t_construct);
         res->t_prove_ms = std::max(res->t_prove_ms, ps.t_prove);
@@ -694,18 +632,10 @@ int cozk_lookups_prove(cozk_lookups* h, int verify, cozk_lookups_result* res) {
         res->bytes_ring += ps.ring_bytes;
         res->star_messages += ps.star_msgs;
     }
-    h->last_proof = proof.serialize();
-    res->proof_len = h->last_proof.size();
-    Sha256 s;
-    s.update(h->last_proof.data(), h->last_proof.size());
-    s.final(res->proof_digest);
+    finish_proof(h, proof.serialize(), res);
     return COZK_OK;
 }
 
-int cozk_lookups_proof_bytes(const cozk_lookups* h, uint8_t* out, size_t cap) {
-    if (!h || !out || cap < h->last_proof.size()) return COZK_ERR_INVALID_ARG;
-    memcpy(out, h->last_proof.data(), h->last_proof.size());
-    return COZK_OK;
-}
+int cozk_lookups_proof_bytes(const cozk_lookups* h, uint8_t* out, size_t cap) { return harness_proof_bytes(h, out, cap); }
 
 }  // extern "C"

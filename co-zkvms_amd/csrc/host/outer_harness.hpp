@@ -27,20 +27,15 @@
 #include "jolt_r1cs.hpp"
 #include "spartan_jolt.hpp"
 
-struct OuterParty {
-    cozk_ctx* ctx = nullptr;
-    bool own_ctx = false;
-    int party = 0;
+struct OuterParty : HarnessParty {
     std::vector<PolyH> cols;
     double t_build = 0, t_prove = 0, t_total = 0;
     SpartanTimes times;
-    uint64_t star_up = 0, star_down = 0, star_msgs = 0;
-    std::string error;
 };
 
 typedef jolt::System OuterSystem;
 
-struct cozk_outer_harness {
+struct cozk_outer_harness : HarnessHandle {
     cozk_outer_config cfg;
     int nparties = 1;
     size_t N = 0;
@@ -52,8 +47,6 @@ struct cozk_outer_harness {
     // the verifier's own view (cfg.full): the clear columns as plain polynomials on its own context, made at the first verify
     cozk_ctx* vctx = nullptr;
     std::vector<PolyH> v_cols;
-    std::string error;
-    Bytes last_proof;
 };
 
 namespace {
@@ -176,9 +169,7 @@ void outer_worker_main(cozk_outer_harness* h, OuterParty& ps, StarNetWorker* sta
         ps.t_prove = t2 - t1;
         ps.t_total = t2 - t0;
     }
-    ps.star_up = star->bytes_up;
-    ps.star_down = star->bytes_down;
-    ps.star_msgs = star->n_msgs;
+    ps.record_net(star);
 }
 
 // the dealer's Az, Bz, Cz in the clear, row by row, and their multilinear extensions at the big-endian point pt
@@ -316,11 +307,7 @@ int outer_coordinator_main(cozk_outer_harness* h, StarNetCoordinator& net, Outer
 extern "C" {
 
 int cozk_outer_harness_create(const cozk_outer_config* cfg, cozk_outer_harness** out) {
-    if (!cfg || !out) return COZK_ERR_INVALID_ARG;
-    *out = nullptr;
-    cozk_outer_harness* h = new cozk_outer_harness();
-    h->cfg = *cfg;
-    try {
+    return harness_create(cfg, out, [&](cozk_outer_harness* h) {
         COZK_REQUIRE(cfg->mode == COZK_MODE_PLAIN || cfg->mode == COZK_MODE_REP3, "outer harness: mode");
         COZK_REQUIRE(cfg->log_steps >= 0 && cfg->log_steps <= 22, "outer harness: log_steps in 0..22");
         COZK_REQUIRE((cfg->system == 0 || cfg->system == 1) && (cfg->full == 0 || cfg->full == 1), "outer harness: system / full are 0 or 1");
@@ -340,34 +327,17 @@ int cozk_outer_harness_create(const cozk_outer_config* cfg, cozk_outer_harness**
         for (int p = 0; p < h->nparties; p++) {
             OuterParty& ps = h->parties[p];
             ps.party = p;
-            int rc = cozk_ctx_create(cfg->devices[p], &ps.ctx);
-            if (rc != COZK_OK) throw CozkError(rc, "outer harness: cannot create a context (no HIP device?)");
-            ps.own_ctx = true;
-            HIP_TRY(hipSetDevice(ps.ctx->device));
+            ps.open_ctx(cfg->devices[p], "outer harness: cannot create a context (no HIP device?)");
             outer_setup_party(h, ps);
         }
-    } catch (const CozkError& e) {
-        h->error = e.what();
-        *out = h;
-        return e.code;
-    } catch (const std::exception& e) {
-        h->error = e.what();
-        *out = h;
-        return COZK_ERR_INTERNAL;
-    }
-    *out = h;
-    return COZK_OK;
+    });
 }
 
-const char* cozk_outer_harness_error(const cozk_outer_harness* h) { return h ? h->error.c_str() : "null harness"; }
+const char* cozk_outer_harness_error(const cozk_outer_harness* h) { return harness_error(h); }
 
 int cozk_outer_harness_destroy(cozk_outer_harness* h) {
     if (!h) return COZK_OK;
-    for (auto& ps : h->parties) {
-        if (ps.ctx) (void)hipSetDevice(ps.ctx->device);
-        ps.cols.clear();
-        if (ps.own_ctx && ps.ctx) cozk_ctx_destroy(ps.ctx);
-    }
+    release_parties(h->parties, [](OuterParty& ps) { ps.cols.clear(); });
     if (h->vctx) {
         (void)hipSetDevice(h->vctx->device);
         h->v_cols.clear();
@@ -381,51 +351,22 @@ int cozk_outer_harness_prove(cozk_outer_harness* h, int verify, cozk_outer_resul
     if (!h || !res) return COZK_ERR_INVALID_ARG;
     memset(res, 0, sizeof *res);
     res->verified = -1;
-    int np = h->nparties;
-    InProcStar star(np);
-    std::vector<std::unique_ptr<InProcStarWorker>> sw;
-    for (int p = 0; p < np; p++) {
-        sw.emplace_back(new InProcStarWorker(&star, p));
-        h->parties[p].error.clear();
-    }
-    std::vector<std::thread> threads;
-    double t0 = now_ms();
-    for (int p = 0; p < np; p++) {
-        threads.emplace_back([&, p] {
-            try {
-                outer_worker_main(h, h->parties[p], sw[p].get());
-            } catch (const std::exception& e) {
-                h->parties[p].error = e.what();
-                star.abort.flag.store(true);
-            }
-        });
-    }
+    InProcNets nets(h->nparties);
+    std::vector<Participant> parts;
+    add_participants(parts, "party", h->parties, [&](OuterParty& ps, int p) { outer_worker_main(h, ps, nets.worker(p)); });
     OuterProofBundle proof;
     std::string why;
     int verified = -1;
-    int rc = COZK_OK;
-    try {
-        InProcStarCoordinator coord(&star);
+    double wall_ms = 0;
+    int rc = run_in_process(nets, parts, [&] {
+        InProcStarCoordinator coord(&nets.star);
         verified = outer_coordinator_main(h, coord, proof, verify != 0, why);
-    } catch (const std::exception& e) {
-        h->error = std::string("coordinator: ") + e.what();
-        star.abort.flag.store(true);
-        rc = COZK_ERR_INTERNAL;
-    }
-    for (auto& t : threads) t.join();
-    double t1 = now_ms();
-    for (int p = 0; p < np; p++) {
-        if (!h->parties[p].error.empty()) {
-            h->error = "party " + std::to_string(p) + ": " + h->parties[p].error;
-            rc = COZK_ERR_INTERNAL;
-        }
-    }
+    }, h->error, wall_ms);
     if (rc != COZK_OK) return rc;
     if (verified == 0) h->error = "verification failed: " + why;
     res->verified = verified;
-    res->wall_ms = t1 - t0;
-    for (int p = 0; p < np; p++) {
-        OuterParty& ps = h->parties[p];
+    res->wall_ms = wall_ms;
+    for (const OuterParty& ps : h->parties) {
         res->t_build_ms = std::max(res->t_build_ms, ps.t_build);
         res->t_prove_ms = std::max(res->t_prove_ms, ps.t_prove);
         res->t_worker_ms = std::max(res->t_worker_ms, ps.t_total);
@@ -437,18 +378,10 @@ int cozk_outer_harness_prove(cozk_outer_harness* h, int verify, cozk_outer_resul
         res->bytes_star_down += ps.star_down;
         res->star_messages += ps.star_msgs;
     }
-    h->last_proof = proof.serialize();
-    res->proof_len = h->last_proof.size();
-    Sha256 s;
-    s.update(h->last_proof.data(), h->last_proof.size());
-    s.final(res->proof_digest);
+    finish_proof(h, proof.serialize(), res);
     return COZK_OK;
 }
 
-int cozk_outer_harness_proof_bytes(const cozk_outer_harness* h, uint8_t* out, size_t cap) {
-    if (!h || !out || cap < h->last_proof.size()) return COZK_ERR_INVALID_ARG;
-    memcpy(out, h->last_proof.data(), h->last_proof.size());
-    return COZK_OK;
-}
+int cozk_outer_harness_proof_bytes(const cozk_outer_harness* h, uint8_t* out, size_t cap) { return harness_proof_bytes(h, out, cap); }
 
 }  // extern "C"

@@ -25,10 +25,7 @@ static inline uint32_t synthetic_small_host(uint64_t seed, uint64_t i, int bits)
     return (uint32_t)(sm_next_host(s) & (((uint64_t)1 << bits) - 1ull));
 }
 
-struct SpartanParty {
-    cozk_ctx* ctx = nullptr;
-    bool own_ctx = false;
-    int party = 0;
+struct SpartanParty : HarnessParty {
     PolyH z;                               // witness shares (PLAIN: the witness itself)
     VecH row_ptr, col, va, vb, vc;         // CSR by row (zero_round)
     VecH t_ptr, t_row, t_va, t_vb, t_vc;   // CSR of the transpose: per column, the rows it touches (third_round)
@@ -41,20 +38,15 @@ struct SpartanParty {
     VecH freq_r, freq_c;                  // normalized_multiplicities of the padded rows / cols against the domain
     double t_lookup = 0;
     double t_zero = 0, t_commit = 0, t_sc1 = 0, t_build = 0, t_sc2 = 0, t_open = 0, t_total = 0;
-    uint64_t star_up = 0, star_down = 0, star_msgs = 0;
-    std::string error;
 };
 
 // cfg.log_pub_workers > 0: public worker j of 2^k with chunk j of the index (setup.rs split_ipk); own context and stream on
 // party 0's device, reading party 0's resident index through chunk views
-struct SpartanPubWorker {
-    cozk_ctx* ctx = nullptr;
+struct SpartanPubWorker : HarnessParty {
     int id = 0;
     std::unique_ptr<PST13Setup> setup_slice;  // split_ck: ck_index over the low qv - k variables, generator g^{eq(t_high, j)}
     VecH rows_pad, cols_pad;                  // rows / cols of the chunk, the padding spelled out with the first term (q_row, q_col)
     double t_lookup = 0;
-    uint64_t star_up = 0, star_down = 0, star_msgs = 0;
-    std::string error;
 };
 
 struct SpartanProof {
@@ -101,7 +93,7 @@ struct SpartanProof {
 
 }  // namespace
 
-struct cozk_spartan {
+struct cozk_spartan : HarnessHandle {
     cozk_spartan_config cfg;
     int nparties = 1;
     size_t n = 0;
@@ -112,8 +104,6 @@ struct cozk_spartan {
     std::vector<fe> h_va, h_vb, h_vc;
     int qv = 0;                          // num_variables_val: entries padded to 2^qv (lookup round)
     std::vector<g1_affine> val_oracles;  // IndexVerifierKey::val_{a,b,c}_oracle (indexer.rs:205-207)
-    std::string error;
-    Bytes last_proof;
 };
 
 namespace {
@@ -615,9 +605,7 @@ static void spartan_worker_main(cozk_spartan* h, SpartanParty& ps, StarNetWorker
         t6 = now_ms();
     }
     ps.t_total = t6 - t0;
-    ps.star_up = star->bytes_up;
-    ps.star_down = star->bytes_down;
-    ps.star_msgs = star->n_msgs;
+    ps.record_net(star);
 }
 
 // --------------------------------------------------------------------------- coordinator + verifier
@@ -977,11 +965,7 @@ static int spartan_coordinator_main(cozk_spartan* h, StarNetCoordinator& net, St
 extern "C" {
 
 int cozk_spartan_create(const cozk_spartan_config* cfg, cozk_spartan** out) {
-    if (!cfg || !out) return COZK_ERR_INVALID_ARG;
-    *out = nullptr;
-    cozk_spartan* h = new cozk_spartan();
-    h->cfg = *cfg;
-    try {
+    return harness_create(cfg, out, [&](cozk_spartan* h) {
         COZK_REQUIRE(cfg->mode == COZK_MODE_PLAIN || cfg->mode == COZK_MODE_REP3, "spartan: bad mode");
         COZK_REQUIRE(cfg->log_n >= 2 && cfg->log_n <= 24, "spartan: log_n out of range");
         COZK_REQUIRE(cfg->log_pub_workers >= 0 && cfg->log_pub_workers <= 3, "spartan: log_pub_workers out of range (0..3)");
@@ -995,10 +979,7 @@ int cozk_spartan_create(const cozk_spartan_config* cfg, cozk_spartan** out) {
         for (int p = 0; p < h->nparties; p++) {
             SpartanParty& ps = h->parties[p];
             ps.party = p;
-            int rc = cozk_ctx_create(cfg->devices[p], &ps.ctx);
-            if (rc != COZK_OK) throw CozkError(rc, "spartan: cannot create a context (no HIP device?)");
-            ps.own_ctx = true;
-            HIP_TRY(hipSetDevice(ps.ctx->device));
+            ps.open_ctx(cfg->devices[p], "spartan: cannot create a context (no HIP device?)");
             spartan_setup_party(h, ps, z_plain);
         }
         if (cfg->log_pub_workers > 0) {
@@ -1008,46 +989,30 @@ int cozk_spartan_create(const cozk_spartan_config* cfg, cozk_spartan** out) {
                 SpartanPubWorker& pw = h->pub[(size_t)j];
                 pw.id = j;
                 // party 0's device: the workers read its resident index in place
-                int rc = cozk_ctx_create(cfg->devices[0], &pw.ctx);
-                if (rc != COZK_OK) throw CozkError(rc, "spartan: cannot create a public worker's context");
-                HIP_TRY(hipSetDevice(pw.ctx->device));
+                pw.open_ctx(cfg->devices[0], "spartan: cannot create a public worker's context");
                 spartan_setup_pub_worker(h, pw);
             }
         }
-    } catch (const CozkError& e) {
-        h->error = e.what();
-        *out = h;
-        return e.code;
-    } catch (const std::exception& e) {
-        h->error = e.what();
-        *out = h;
-        return COZK_ERR_INTERNAL;
-    }
-    *out = h;
-    return COZK_OK;
+    });
 }
 
-const char* cozk_spartan_error(const cozk_spartan* h) { return h ? h->error.c_str() : "null harness"; }
+const char* cozk_spartan_error(const cozk_spartan* h) { return harness_error(h); }
 
 int cozk_spartan_destroy(cozk_spartan* h) {
     if (!h) return COZK_OK;
-    for (auto& pw : h->pub) {
-        if (pw.ctx) (void)hipSetDevice(pw.ctx->device);
+    release_parties(h->pub, [](SpartanPubWorker& pw) {
         pw.rows_pad = VecH();
         pw.cols_pad = VecH();
         pw.setup_slice.reset();
-        if (pw.ctx) cozk_ctx_destroy(pw.ctx);
-    }
-    for (auto& ps : h->parties) {
-        if (ps.ctx) (void)hipSetDevice(ps.ctx->device);
+    });
+    release_parties(h->parties, [](SpartanParty& ps) {
         ps.z = PolyH();
         for (VecH* v : {&ps.row_ptr, &ps.col, &ps.va, &ps.vb, &ps.vc, &ps.t_ptr, &ps.t_row, &ps.t_va, &ps.t_vb, &ps.t_vc}) *v = VecH();
         ps.setup.reset();
         for (VecH* v : {&ps.rows_u32, &ps.cols_u32, &ps.domain_u32, &ps.val_pad[0], &ps.val_pad[1], &ps.val_pad[2], &ps.freq_r, &ps.freq_c}) *v = VecH();
         for (int k = 0; k < 3; k++) ps.val_poly[k] = PolyH();
         ps.setup_idx.reset();
-        if (ps.own_ctx && ps.ctx) cozk_ctx_destroy(ps.ctx);
-    }
+    });
     delete h;
     return COZK_OK;
 }
@@ -1056,85 +1021,31 @@ int cozk_spartan_prove(cozk_spartan* h, int verify, cozk_spartan_result* res) {
     if (!h || !res) return COZK_ERR_INVALID_ARG;
     memset(res, 0, sizeof *res);
     res->verified = -1;
-    int np = h->nparties;
-    InProcStar star(np);
-    std::vector<std::unique_ptr<InProcStarWorker>> sw;
-    for (int p = 0; p < np; p++) {
-        sw.emplace_back(new InProcStarWorker(&star, p));
-        h->parties[p].error.clear();
-    }
-    // the public workers' own star (log_pub_workers > 0); one abort flag for both
     const int K = (int)h->pub.size();
-    InProcStar pstar(K > 0 ? K : 1);
-    for (auto& ch : pstar.up) ch.abort = &star.abort;
-    for (auto& ch : pstar.down) ch.abort = &star.abort;
-    std::vector<std::unique_ptr<InProcStarWorker>> psw;
-    for (int j = 0; j < K; j++) {
-        psw.emplace_back(new InProcStarWorker(&pstar, j));
-        h->pub[(size_t)j].error.clear();
-    }
-    std::vector<std::thread> threads;
-    double t0 = now_ms();
-    for (int p = 0; p < np; p++) {
-        threads.emplace_back([&, p] {
-            try {
-                spartan_worker_main(h, h->parties[p], sw[p].get());
-            } catch (const std::exception& e) {
-                h->parties[p].error = e.what();
-                star.abort.flag.store(true);
-            }
-        });
-    }
-    for (int j = 0; j < K; j++) {
-        threads.emplace_back([&, j] {
-            try {
-                spartan_pub_worker_main(h, h->pub[(size_t)j], psw[(size_t)j].get());
-            } catch (const std::exception& e) {
-                h->pub[(size_t)j].error = e.what();
-                star.abort.flag.store(true);
-            }
-        });
-    }
+    InProcNets nets(h->nparties, false, K);  // second star: the public workers' (log_pub_workers > 0)
+    std::vector<Participant> parts;
+    add_participants(parts, "party", h->parties, [&](SpartanParty& ps, int p) { spartan_worker_main(h, ps, nets.worker(p)); });
+    add_participants(parts, "public worker", h->pub, [&](SpartanPubWorker& pw, int j) { spartan_pub_worker_main(h, pw, nets.sub_worker(j)); });
     SpartanProof proof;
     std::string why;
     int verified = -1;
-    int rc = COZK_OK;
-    double t_prove_end = 0;
-    try {
-        InProcStarCoordinator coord(&star), pcoord(&pstar);
+    double wall_ms = 0;
+    int rc = run_in_process(nets, parts, [&] {
+        InProcStarCoordinator coord(&nets.star), pcoord(nets.sub.get());
         verified = spartan_coordinator_main(h, coord, K > 0 ? &pcoord : nullptr, proof, verify != 0, why);
-    } catch (const std::exception& e) {
-        h->error = std::string("coordinator: ") + e.what();
-        star.abort.flag.store(true);
-        rc = COZK_ERR_INTERNAL;
-    }
-    for (auto& t : threads) t.join();
-    t_prove_end = now_ms();
-    for (int p = 0; p < np; p++) {
-        if (!h->parties[p].error.empty()) {
-            h->error = "party " + std::to_string(p) + ": " + h->parties[p].error;
-            rc = COZK_ERR_INTERNAL;
-        }
-    }
-    for (int j = 0; j < K; j++) {
-        if (!h->pub[(size_t)j].error.empty()) {
-            h->error = "public worker " + std::to_string(j) + ": " + h->pub[(size_t)j].error;
-            rc = COZK_ERR_INTERNAL;
-        }
-    }
+    }, h->error, wall_ms);
     if (rc != COZK_OK) return rc;
     if (verified == 0) h->error = "verification failed: " + why;
     res->verified = verified;
-    res->wall_ms = t_prove_end - t0;
+    res->wall_ms = wall_ms;
     res->pub_workers = K > 0 ? K : (h->cfg.lookup_round ? 1 : 0);
-    for (auto& pw : h->pub) {
+    for (const SpartanPubWorker& pw : h->pub) {
         res->t_lookup_ms = std::max(res->t_lookup_ms, pw.t_lookup);
         res->pub_star_messages += pw.star_msgs;
         res->pub_bytes_up += pw.star_up;
         res->pub_bytes_down += pw.star_down;
     }
-    for (int p = 0; p < np; p++) {
-        SpartanParty& ps = h->parties[p];
+    for (const SpartanParty& ps : h->parties) {
         res->t_zero_round_ms = std::max(res->t_zero_round_ms, ps.t_zero);
         res->t_commit_ms = std::max(res->t_commit_ms, ps.t_commit);
         res->t_sumcheck1_ms = std::max(res->t_sumcheck1_ms, ps.t_sc1);
@@ -1147,18 +1058,10 @@ int cozk_spartan_prove(cozk_spartan* h, int verify, cozk_spartan_result* res) {
         res->bytes_star_down += ps.star_down;
         res->star_messages += ps.star_msgs;
     }
-    h->last_proof = proof.serialize();
-    res->proof_len = h->last_proof.size();
-    Sha256 s;
-    s.update(h->last_proof.data(), h->last_proof.size());
-    s.final(res->proof_digest);
+    finish_proof(h, proof.serialize(), res);
     return COZK_OK;
 }
 
-int cozk_spartan_proof_bytes(const cozk_spartan* h, uint8_t* out, size_t cap) {
-    if (!h || !out || cap < h->last_proof.size()) return COZK_ERR_INVALID_ARG;
-    memcpy(out, h->last_proof.data(), h->last_proof.size());
-    return COZK_OK;
-}
+int cozk_spartan_proof_bytes(const cozk_spartan* h, uint8_t* out, size_t cap) { return harness_proof_bytes(h, out, cap); }
 
 }  // extern "C"

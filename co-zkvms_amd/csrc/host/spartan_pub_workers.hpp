@@ -249,9 +249,7 @@ static void spartan_pub_worker_main(cozk_spartan* h, SpartanPubWorker& pw, StarN
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     pw.t_lookup = now_ms() - t0;
-    pw.star_up = star->bytes_up;
-    pw.star_down = star->bytes_down;
-    pw.star_msgs = star->n_msgs;
+    pw.record_net(star);
 }
 
 // the coordinator's side: fills the lookup part of the proof exactly as the one-worker path does

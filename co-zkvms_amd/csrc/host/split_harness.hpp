@@ -150,10 +150,7 @@ static void worker_main_split(cozk_harness* h, PartyState& ps, int worker, StarN
     double t5 = now_ms();
     ps.t_open = t5 - t4;
     ps.t_total = t5 - t_start;
-    ps.star_up = star->bytes_up;
-    ps.star_down = star->bytes_down;
-    ps.star_msgs = star->n_msgs;
-    ps.ring_bytes = ring ? ring->bytes_sent : 0;
+    ps.record_net(star, ring);
 }
 
 // commitments: entry i of every participant; shared (tag 2) entries and P0's public (tag 1) entries each sum over

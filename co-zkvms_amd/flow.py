@@ -22,28 +22,11 @@ FLOW_SYMBOLS = ["cozk_flow_create", "cozk_flow_error", "cozk_flow_destroy", "coz
 _vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
 
 
-def _decl():
-    l = L.lib()
-    l.cozk_flow_create.restype = _i
-    l.cozk_flow_create.argtypes = [ctypes.POINTER(FlowConfig), ctypes.POINTER(_vp)]
-    l.cozk_flow_error.restype = ctypes.c_char_p
-    l.cozk_flow_error.argtypes = [_vp]
-    l.cozk_flow_destroy.restype = _i
-    l.cozk_flow_destroy.argtypes = [_vp]
-    l.cozk_flow_num_polys.restype = _sz
-    l.cozk_flow_num_polys.argtypes = [_vp]
-    l.cozk_flow_ctx.restype = _vp
-    l.cozk_flow_ctx.argtypes = [_vp, _i]
-    l.cozk_flow_prove.restype = _i
-    l.cozk_flow_prove.argtypes = [_vp, _i, ctypes.POINTER(FlowResult)]
-    l.cozk_flow_proof_bytes.restype = _i
-    l.cozk_flow_proof_bytes.argtypes = [_vp, _vp, _sz]
-    return l
+class FlowHarness(L.HarnessHandle):
+    PREFIX, CONFIG, RESULT = "cozk_flow", FlowConfig, FlowResult
+    EXTRA = {"cozk_flow_num_polys": (_sz, [_vp]), "cozk_flow_ctx": (_vp, [_vp, _i])}
 
-
-class FlowHarness:
     def __init__(self, mode="plain", log_n=4, log_m=3, log_b=3, log_mem=3, n_mem=6, n_subtables=3, devices=(0, 0, 0), seed=1, precompute=1, small_witness=0):
-        self._l = _decl()
         cfg = FlowConfig()
         cfg.mode = L.MODE_PLAIN if mode == "plain" else L.MODE_REP3
         cfg.log_n, cfg.log_m, cfg.log_b, cfg.log_mem = log_n, log_m, log_b, log_mem
@@ -52,46 +35,10 @@ class FlowHarness:
         cfg.seed = seed
         cfg.precompute = precompute
         cfg.small_witness = small_witness
-        h = _vp()
-        rc = self._l.cozk_flow_create(ctypes.byref(cfg), ctypes.byref(h))
-        self.h = h
-        if rc != L.OK:
-            msg = (self._l.cozk_flow_error(h) or b"?").decode() if h else "?"
-            if h:
-                self._l.cozk_flow_destroy(h)
-                self.h = None
-            raise L.CozkError(rc, msg)
-
-    def prove(self, verify=True):
-        res = FlowResult()
-        rc = self._l.cozk_flow_prove(self.h, 1 if verify else 0, ctypes.byref(res))
-        if rc != L.OK:
-            raise L.CozkError(rc, (self._l.cozk_flow_error(self.h) or b"?").decode())
-        return res
-
-    def proof_bytes(self, res):
-        buf = (ctypes.c_uint8 * int(res.proof_len))()
-        rc = self._l.cozk_flow_proof_bytes(self.h, buf, int(res.proof_len))
-        if rc != L.OK:
-            raise L.CozkError(rc, "proof_bytes")
-        return bytes(buf)
+        self._open(cfg)
 
     def num_polys(self):
         return int(self._l.cozk_flow_num_polys(self.h))
 
     def ctx_handle(self, party=0):
         return self._l.cozk_flow_ctx(self.h, party)
-
-    def last_error(self):
-        return (self._l.cozk_flow_error(self.h) or b"").decode()
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._l.cozk_flow_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -32,16 +32,6 @@ _vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
 
 def _decl():
     l = L.lib()
-    l.cozk_lookups_create.restype = _i
-    l.cozk_lookups_create.argtypes = [ctypes.POINTER(LookupsConfig), ctypes.POINTER(_vp)]
-    l.cozk_lookups_error.restype = ctypes.c_char_p
-    l.cozk_lookups_error.argtypes = [_vp]
-    l.cozk_lookups_destroy.restype = _i
-    l.cozk_lookups_destroy.argtypes = [_vp]
-    l.cozk_lookups_prove.restype = _i
-    l.cozk_lookups_prove.argtypes = [_vp, _i, ctypes.POINTER(LookupsResult)]
-    l.cozk_lookups_proof_bytes.restype = _i
-    l.cozk_lookups_proof_bytes.argtypes = [_vp, _vp, _sz]
     l.cozk_toggle_create.restype = _i
     l.cozk_toggle_create.argtypes = [_vp, _i, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(_vp)]
     l.cozk_toggle_free.restype = _i
@@ -63,9 +53,10 @@ def _decl():
     return l
 
 
-class LookupsHarness:
+class LookupsHarness(L.HarnessHandle):
+    PREFIX, CONFIG, RESULT = "cozk_lookups", LookupsConfig, LookupsResult
+
     def __init__(self, mode="plain", log_n=6, n_pairs=2, density_pct=25, devices=(0, 0, 0), seed=1, primary=False, log_workers=0, mix="uniform"):
-        self._l = _decl()
         cfg = LookupsConfig()
         cfg.mix = 1 if mix == "sha2" else 0
         cfg.mode = L.MODE_PLAIN if mode == "plain" else L.MODE_REP3
@@ -74,43 +65,7 @@ class LookupsHarness:
         cfg.seed = seed
         cfg.primary = 1 if primary else 0
         cfg.log_workers = log_workers
-        h = _vp()
-        rc = self._l.cozk_lookups_create(ctypes.byref(cfg), ctypes.byref(h))
-        self.h = h
-        if rc != L.OK:
-            msg = (self._l.cozk_lookups_error(h) or b"?").decode() if h else "?"
-            if h:
-                self._l.cozk_lookups_destroy(h)
-                self.h = None
-            raise L.CozkError(rc, msg)
-
-    def prove(self, verify=True):
-        res = LookupsResult()
-        rc = self._l.cozk_lookups_prove(self.h, 1 if verify else 0, ctypes.byref(res))
-        if rc != L.OK:
-            raise L.CozkError(rc, (self._l.cozk_lookups_error(self.h) or b"?").decode())
-        return res
-
-    def proof_bytes(self, res):
-        buf = (ctypes.c_uint8 * int(res.proof_len))()
-        rc = self._l.cozk_lookups_proof_bytes(self.h, buf, int(res.proof_len))
-        if rc != L.OK:
-            raise L.CozkError(rc, "proof_bytes")
-        return bytes(buf)
-
-    def last_error(self):
-        return (self._l.cozk_lookups_error(self.h) or b"").decode()
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._l.cozk_lookups_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(cfg)
 
 
 class ToggleLayer:

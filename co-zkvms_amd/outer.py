@@ -38,16 +38,6 @@ _vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
 
 def _decl():
     l = L.lib()
-    l.cozk_outer_harness_create.restype = _i
-    l.cozk_outer_harness_create.argtypes = [ctypes.POINTER(OuterConfig), ctypes.POINTER(_vp)]
-    l.cozk_outer_harness_error.restype = ctypes.c_char_p
-    l.cozk_outer_harness_error.argtypes = [_vp]
-    l.cozk_outer_harness_destroy.restype = _i
-    l.cozk_outer_harness_destroy.argtypes = [_vp]
-    l.cozk_outer_harness_prove.restype = _i
-    l.cozk_outer_harness_prove.argtypes = [_vp, _i, ctypes.POINTER(OuterResult)]
-    l.cozk_outer_harness_proof_bytes.restype = _i
-    l.cozk_outer_harness_proof_bytes.argtypes = [_vp, _vp, _sz]
     l.cozk_outer_create.restype = _i
     l.cozk_outer_create.argtypes = [_vp, _i, _i, ctypes.POINTER(R1CS), _vp, _sz, _vp, _sz, ctypes.POINTER(_vp)]
     l.cozk_outer_free.restype = _i
@@ -63,11 +53,12 @@ def _decl():
     return l
 
 
-class OuterHarness:
+class OuterHarness(L.HarnessHandle):
+    PREFIX, CONFIG, RESULT = "cozk_outer_harness", OuterConfig, OuterResult
+
     def __init__(self, mode="plain", log_steps=4, devices=(0, 0, 0), seed=1, system="toy", full=False):
         """system = "jolt": the reference's constraint set (70 + 2 constraints, 78 inputs, 128 rows per step); full: the whole
         Spartan worker (outer + inner + shift sumchecks + the two opening appends)"""
-        self._l = _decl()
         cfg = OuterConfig()
         cfg.system = 1 if system == "jolt" else 0
         cfg.full = 1 if full else 0
@@ -75,43 +66,7 @@ class OuterHarness:
         cfg.log_steps = log_steps
         cfg.devices = (ctypes.c_int * 3)(*devices)
         cfg.seed = seed
-        h = _vp()
-        rc = self._l.cozk_outer_harness_create(ctypes.byref(cfg), ctypes.byref(h))
-        self.h = h
-        if rc != L.OK:
-            msg = (self._l.cozk_outer_harness_error(h) or b"?").decode() if h else "?"
-            if h:
-                self._l.cozk_outer_harness_destroy(h)
-                self.h = None
-            raise L.CozkError(rc, msg)
-
-    def prove(self, verify=True):
-        res = OuterResult()
-        rc = self._l.cozk_outer_harness_prove(self.h, 1 if verify else 0, ctypes.byref(res))
-        if rc != L.OK:
-            raise L.CozkError(rc, (self._l.cozk_outer_harness_error(self.h) or b"?").decode())
-        return res
-
-    def proof_bytes(self, res):
-        buf = (ctypes.c_uint8 * int(res.proof_len))()
-        rc = self._l.cozk_outer_harness_proof_bytes(self.h, buf, int(res.proof_len))
-        if rc != L.OK:
-            raise L.CozkError(rc, "proof_bytes")
-        return bytes(buf)
-
-    def last_error(self):
-        return (self._l.cozk_outer_harness_error(self.h) or b"").decode()
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._l.cozk_outer_harness_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(cfg)
 
 
 class SpartanOuter:

@@ -13,7 +13,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
-from .harness import HarnessConfig, HarnessResult, _decl
+from .harness import Harness, HarnessConfig, HarnessResult
 
 _AG = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
                        ctypes.POINTER(ctypes.c_size_t))
@@ -230,19 +230,17 @@ class NativeRing:
             self.ctx = None
 
 
-class DistributedParty:
+class DistributedParty(L.HarnessHandle):
     """this process's participant -- (party, worker) -- of one distributed proof
     (`cozk_harness_create_participant` / `cozk_harness_prove_distributed`): a party of a 3-party Rep3 run,
     and/or one worker sub-net (high-variable chunk) of the plain / Rep3 prover"""
+    PREFIX, CONFIG, RESULT = Harness.PREFIX, HarnessConfig, HarnessResult
+    EXTRA = dict(Harness.EXTRA, cozk_harness_create_participant=(ctypes.c_int, [ctypes.POINTER(HarnessConfig), ctypes.c_int, ctypes.c_int,
+                                                                                 ctypes.POINTER(ctypes.c_void_p)]),
+                 cozk_harness_prove_distributed=(ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HubNet), ctypes.POINTER(RingNetC), ctypes.c_int,
+                                                                ctypes.POINTER(HarnessResult)]))
 
     def __init__(self, party, device=0, worker=0, mode="rep3", log_workers=0, **cfgkw):
-        self._l = _decl()
-        self._l.cozk_harness_create_participant.restype = ctypes.c_int
-        self._l.cozk_harness_create_participant.argtypes = [ctypes.POINTER(HarnessConfig), ctypes.c_int, ctypes.c_int,
-                                                            ctypes.POINTER(ctypes.c_void_p)]
-        self._l.cozk_harness_prove_distributed.restype = ctypes.c_int
-        self._l.cozk_harness_prove_distributed.argtypes = [ctypes.c_void_p, ctypes.POINTER(HubNet), ctypes.POINTER(RingNetC), ctypes.c_int,
-                                                           ctypes.POINTER(HarnessResult)]
         cfg = HarnessConfig()
         cfg.mode = L.MODE_REP3 if mode == "rep3" else L.MODE_PLAIN
         cfg.log_n = cfgkw.get("log_n", 10)
@@ -259,12 +257,7 @@ class DistributedParty:
         self.party, self.worker = party, worker
         self.nparties = 3 if mode == "rep3" else 1
         self.index = worker * self.nparties + party
-        h = ctypes.c_void_p()
-        rc = self._l.cozk_harness_create_participant(ctypes.byref(cfg), party, worker, ctypes.byref(h))
-        self.h = h
-        if rc != L.OK:
-            msg = self._l.cozk_harness_error(h) if h else b"?"
-            raise L.CozkError(rc, (msg or b"?").decode())
+        self._open(cfg, party, worker, create="_create_participant")
 
     def ctx_handle(self):
         return self._l.cozk_harness_ctx(self.h, self.index)
@@ -279,13 +272,5 @@ class DistributedParty:
             for t in (hub, ring):
                 if t is not None and t.error is not None:
                     raise t.error
-            raise L.CozkError(rc, (self._l.cozk_harness_error(self.h) or b"?").decode())
+            raise L.CozkError(rc, self.last_error() or "?")
         return res
-
-    def last_error(self):
-        return (self._l.cozk_harness_error(self.h) or b"").decode()
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._l.cozk_harness_destroy(self.h)
-            self.h = None

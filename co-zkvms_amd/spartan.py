@@ -24,24 +24,10 @@ class SpartanResult(ctypes.Structure):
 SPARTAN_SYMBOLS = ["cozk_spartan_create", "cozk_spartan_error", "cozk_spartan_destroy", "cozk_spartan_prove", "cozk_spartan_proof_bytes"]
 
 
-def _decl():
-    l = L.lib()
-    l.cozk_spartan_create.restype = ctypes.c_int
-    l.cozk_spartan_create.argtypes = [ctypes.POINTER(SpartanConfig), ctypes.POINTER(ctypes.c_void_p)]
-    l.cozk_spartan_error.restype = ctypes.c_char_p
-    l.cozk_spartan_error.argtypes = [ctypes.c_void_p]
-    l.cozk_spartan_destroy.restype = ctypes.c_int
-    l.cozk_spartan_destroy.argtypes = [ctypes.c_void_p]
-    l.cozk_spartan_prove.restype = ctypes.c_int
-    l.cozk_spartan_prove.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(SpartanResult)]
-    l.cozk_spartan_proof_bytes.restype = ctypes.c_int
-    l.cozk_spartan_proof_bytes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
-    return l
+class SpartanHarness(L.HarnessHandle):
+    PREFIX, CONFIG, RESULT = "cozk_spartan", SpartanConfig, SpartanResult
 
-
-class SpartanHarness:
     def __init__(self, mode="plain", log_n=10, precompute=True, devices=(0, 0, 0), seed=1, lookup_round=False, log_pub_workers=0):
-        self._l = _decl()
         cfg = SpartanConfig()
         cfg.mode = L.MODE_PLAIN if mode == "plain" else L.MODE_REP3
         cfg.log_n = log_n
@@ -50,40 +36,4 @@ class SpartanHarness:
         cfg.seed = seed
         cfg.lookup_round = 1 if lookup_round else 0
         cfg.log_pub_workers = log_pub_workers
-        h = ctypes.c_void_p()
-        rc = self._l.cozk_spartan_create(ctypes.byref(cfg), ctypes.byref(h))
-        self.h = h
-        if rc != L.OK:
-            msg = (self._l.cozk_spartan_error(h) or b"?").decode() if h else "?"
-            if h:
-                self._l.cozk_spartan_destroy(h)
-                self.h = None
-            raise L.CozkError(rc, msg)
-
-    def prove(self, verify=True):
-        res = SpartanResult()
-        rc = self._l.cozk_spartan_prove(self.h, 1 if verify else 0, ctypes.byref(res))
-        if rc != L.OK:
-            raise L.CozkError(rc, (self._l.cozk_spartan_error(self.h) or b"?").decode())
-        return res
-
-    def proof_bytes(self, res):
-        buf = (ctypes.c_uint8 * int(res.proof_len))()
-        rc = self._l.cozk_spartan_proof_bytes(self.h, buf, int(res.proof_len))
-        if rc != L.OK:
-            raise L.CozkError(rc, "proof_bytes")
-        return bytes(buf)
-
-    def last_error(self):
-        return (self._l.cozk_spartan_error(self.h) or b"").decode()
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._l.cozk_spartan_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(cfg)

@@ -49,3 +49,24 @@ def test_product_never_imports_oracle():
                 txt = open(os.path.join(dp, f), errors="ignore").read()
                 assert "pyref" not in txt.replace("oracle/pyref.py", "") or f.endswith((".hip", ".hpp")), f
                 assert "import pyharness" not in txt and "coracle" not in txt and "liboracle" not in txt, f
+
+
+# one out-of-range config per harness: create rejects it before any context exists (no GPU needed), reports the check's
+# text through *_error and destroys the half-built harness
+_BAD_CONFIGS = [
+    ("harness", "Harness", dict(log_n=30), "harness: log_n out of range"),
+    ("spartan", "SpartanHarness", dict(log_n=4, log_pub_workers=4), "spartan: log_pub_workers out of range (0..3)"),
+    ("lookups", "LookupsHarness", dict(density_pct=101), "lookups: log_n in 1..24, n_pairs in 1..128, density_pct in 0..100"),
+    ("outer", "OuterHarness", dict(log_steps=23), "outer harness: log_steps in 0..22"),
+    ("flow", "FlowHarness", dict(log_n=23), "flow: log_n in 1..22"),
+    ("party_dist", "DistributedParty", dict(party=3), "harness_create_participant: bad (party, worker)"),
+]
+
+
+@pytest.mark.parametrize("module,cls,kw,text", _BAD_CONFIGS, ids=[c[1] for c in _BAD_CONFIGS])
+def test_harness_rejects_bad_config(cozk, module, cls, kw, text):
+    harness_cls = getattr(importlib.import_module("co-zkvms_amd." + module), cls)
+    with pytest.raises(cozk.CozkError) as e:
+        harness_cls(**kw)
+    assert e.value.code == -1  # COZK_ERR_INVALID_ARG
+    assert text in str(e.value)
