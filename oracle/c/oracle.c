@@ -30,8 +30,8 @@ void orc_fp_binop(int base_field, int op, const uint64_t* a, const uint64_t* b, 
         memcpy(out + 4 * i, r.l, 32);
     }
 }
-/* the cores this process may really use: the CPU affinity mask capped by the cgroup's CPU quota (a container on a 128-thread host
- * with a 16-CPU share runs 16 threads' worth of work, and 128 OpenMP threads only fight over them) */
+/* the cores this process may really use: the CPU affinity mask capped by the cgroup's CPU quota and by OMP_NUM_THREADS (a container
+ * on a 128-thread host with a 16-CPU share runs 16 threads' worth of work, and 128 OpenMP threads only fight over them) */
 static int effective_cpus(void) {
     int n = 0;
 #ifdef _OPENMP
@@ -49,6 +49,8 @@ static int effective_cpus(void) {
         }
         fclose(f);
     }
+    const char* o = getenv("OMP_NUM_THREADS");
+    if (o && atoi(o) >= 1 && atoi(o) < n) n = atoi(o);
     const char* e = getenv("ORC_THREADS");
     if (e && atoi(e) >= 1) n = atoi(e);
     return n;

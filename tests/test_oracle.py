@@ -183,3 +183,17 @@ def test_spartan_pipeline_oracle_self_consistent():
     c = pyspartan.run(dict(log_n=4, seed=12))
     assert a["verified"] and c["verified"]
     assert a["digest"] == b["digest"] != c["digest"]
+
+
+def test_scale_golden_2p16_row_regenerates_live():
+    """tests/golden/scale_pipelines.json holds the C oracle's digests of the bench mix at 2^16 / 2^18 / 2^20 (the GPU tier checks
+    the HIP proofs against the larger two): the generator's config and the C oracle reproduce the 2^16 row here"""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
+    import make_golden
+    rows = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "scale_pipelines.json")))["pipelines"]
+    assert [r["cfg"]["log_n"] for r in rows] == list(make_golden.SCALE_LOG_N)
+    row = rows[0]
+    assert row["cfg"] == make_golden.scale_cfg(16)
+    res, _ = coracle.pipeline(row["cfg"], want_proof=False)
+    assert bytes(res.digest).hex() == row["digest"] and res.proof_len == row["proof_len"]
