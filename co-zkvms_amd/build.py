@@ -1,4 +1,5 @@
-"""Build libcozk.so (all HIP kernels + the C ABI) for gfx950 with hipcc.  Cross-compiles without a GPU."""
+"""Build libcozk.so (all HIP kernels + the C ABI) for gfx950 with hipcc, and the test-only primitive harness
+tests/native/libcozk_prims.so (build_prims).  Cross-compiles without a GPU."""
 import os
 import subprocess
 import sys
@@ -6,6 +7,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libcozk.so")
+PRIMS_SRC = os.path.join(os.path.dirname(HERE), "tests", "native", "prims.hip")
+PRIMS_OUT = os.path.join(os.path.dirname(HERE), "tests", "native", "libcozk_prims.so")
+HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 SOURCES = ["capi.hip", "msm.hip", "poly.hip", "harness.hip", "shm_hub.hip", "ring.hip"]
 HEADERS = [os.path.join("host", "spartan_pub_workers.hpp"), "fr9.hip.hpp", "fr9_consts.inc", os.path.join("host", "flow_harness.hpp"), os.path.join("host", "jolt_r1cs.hpp"), os.path.join("host", "spartan_jolt.hpp"), "spartan_inner.inc", "ff.hip.hpp", "prf.hip.hpp", "ff_macc.inc", "ff_mul2.inc", "ec.hip.hpp", "fq9.hip.hpp", "fq9_consts.inc", "fq9_mac.inc", "fq9_mul.inc", "common.hpp", "poly.hip.hpp", "toggle_layer.inc", "primary_sumcheck.inc", "spartan_outer.inc", "logup.inc", os.path.join("host", "wire.hpp"), os.path.join("host", "net.hpp"), os.path.join("host", "prover.hpp"), os.path.join("host", "split.hpp"), os.path.join("host", "split_harness.hpp"), os.path.join("host", "spartan_harness.hpp"), os.path.join("host", "lookups_harness.hpp"), os.path.join("host", "outer_harness.hpp"), os.path.join("host", "runner.hpp"), os.path.join("..", "..", "include", "cozk.h")]
 
@@ -27,7 +31,7 @@ def build(force=False, verbose=True):
         o = os.path.join(HERE, "build", os.path.basename(s) + ".o")
         objs.append(o)
         if force or _newer(o, deps):
-            cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", s, "-o", o]
+            cmd = ["hipcc"] + HIPCC_FLAGS + ["-c", s, "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)
             procs.append((cmd, subprocess.Popen(cmd)))
@@ -39,8 +43,25 @@ def build(force=False, verbose=True):
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
+    build_prims(force, verbose)
     return OUT
 
 
+def build_prims(force=False, verbose=True):
+    """the test-only harness that puts the headers' field, curve and 9 x 29 operations behind element-wise kernels and host
+    wrappers (tests/test_gpu_prims.py, tests/test_host_prims.py); rebuilt when it or any header changes"""
+    if force or _newer(PRIMS_OUT, [PRIMS_SRC] + [os.path.join(CSRC, h) for h in HEADERS]):
+        tmp = PRIMS_OUT[:-3] + ".tmp.so"
+        cmd = ["hipcc"] + HIPCC_FLAGS + ["-shared", PRIMS_SRC, "-o", tmp]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+        os.replace(tmp, PRIMS_OUT)  # a killed compile leaves no library that looks fresh
+    return PRIMS_OUT
+
+
 if __name__ == "__main__":
-    build(force="--force" in sys.argv)
+    if "--prims" in sys.argv:
+        build_prims(force="--force" in sys.argv)
+    else:
+        build(force="--force" in sys.argv)

@@ -211,7 +211,7 @@ struct Field {
         return o;
     }
 #endif
-    // portable 8 x 32 CIOS (kept as the reference the 64-bit host path is checked against: tests/host_field_selftest)
+    // portable 8 x 32 CIOS (kept as the reference the 64-bit host path is checked against: tests/test_host_prims.py)
     static inline fe mul_host32(const fe& a, const fe& b) {
         uint32_t t[8];
         for (int i = 0; i < 8; i++) t[i] = 0;

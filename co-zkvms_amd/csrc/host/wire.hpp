@@ -151,8 +151,8 @@ struct Sha256 {
 #if COZK_HAVE_SHANI
     // One compression with the x86 SHA extensions (53 ns instead of 302 ns per block on the boxes' EPYC hosts): the transcript hashes
     // ~4 blocks per sumcheck round and a chained proof has ~1660 rounds whose coordinator sits on the workers' critical path.  The
-    // instructions keep the state as (ABEF, CDGH); checked against the portable code on random blocks (tests/test_wire_format.py
-    // pins the digests through the proofs).
+    // instructions keep the state as (ABEF, CDGH); tests/test_host_prims.py checks both block paths against hashlib, each in a
+    // process of its own (the choice below is a per-process static; COZK_NO_SHANI selects the portable code).
     __attribute__((target("sha,sse4.1,ssse3"))) static void block_shani(uint32_t h[8], const uint8_t* p, const uint32_t* K) {
         const __m128i bswap = _mm_set_epi64x(0x0c0d0e0f08090a0bULL, 0x0405060700010203ULL);
         __m128i t = _mm_loadu_si128((const __m128i*)&h[0]);
