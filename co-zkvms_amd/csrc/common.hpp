@@ -331,6 +331,7 @@ static int cozk_guard(cozk_ctx* ctx, F&& f) {
         // every entry point starts from a clean per-thread error state: a failed HIP call of the host's own (or of a
         // library it uses -- RCCL probes capabilities with calls that fail benignly) must not surface in our launch checks
         (void)hipGetLastError();
+        if (ctx) ctx->armed_seq = 0;  // ... and with no round publication left armed by a call that failed half-way
         f();
         return COZK_OK;
     } catch (const CozkError& e) {

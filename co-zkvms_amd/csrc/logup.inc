@@ -272,16 +272,11 @@ int cozk_prodlist_round(cozk_ctx* ctx, cozk_prodlist* pl, const uint64_t* r, uin
         HIP_TRY(hipMemcpyAsync(pl->d_desc, &pl->desc, sizeof(ProdListDev), hipMemcpyHostToDevice, ctx->stream));
         const size_t half = pl->n / 2;
         const int D = pl->desc.degree;
-        unsigned gx = grid_capped(half);
-        if (gx > 1024) gx = 1024;
-        ctx->scratch.reserve(((size_t)(D + 1) * gx + D + 1) * sizeof(fe));
-        fe* partial = ctx->scratch.as<fe>();
-        fe* res = result_slot(ctx, D + 1);
-        k_prodlist_round<<<gx, PT, 0, ctx->stream>>>(pl->d_desc, half, partial);
-        k_finish_sums<<<D + 1, PT, 0, ctx->stream>>>(partial, gx, Fr::one(), 0, res, arm_round_publish(ctx));
-        HIP_TRY(hipGetLastError());
+        const unsigned gx = grid_capped(half, ROUND_GRID_MAX);
+        const SumLaunch sl = sum_launch(ctx, D + 1, gx, D + 1);
+        k_prodlist_round<<<gx, PT, 0, ctx->stream>>>(pl->d_desc, half, sl.partial);
         fe s[PL_MAX_DEG + 1];
-        fetch_fe(ctx, res, D + 1, s);
+        finish_sums(ctx, sl, D + 1, gx, Fr::one(), 0, s);
         for (int t = 0; t <= D; t++) fe_to_u64x4(s[t], out_evals + 4 * t);
     });
 }

@@ -18,6 +18,11 @@
 
 static constexpr int PT = 256;      // threads per block
 static constexpr int MAXBLK = 2048; // grid cap for reducing kernels (>= 8 blocks per CU)
+static constexpr unsigned ROUND_GRID_MAX = 1024;       // workgroups of a round-sum launch that is not sized by resident_grid
+static constexpr unsigned BATCH_GRID_MAX = 512;        // ... of the batched reductions (dot product, opening, product and Spartan rounds)
+static constexpr unsigned EVAL_GRID_MAX = 192;         // ... of the evaluate / batched dot-product kernels (few, long lanes)
+static constexpr size_t LAYER_F9_MIN_CHUNKS = 1024;    // layers of this many 4-element chunks are throughput-bound: the 9 x 29 kernels
+static constexpr size_t LAYER_GROUPED_MIN_E1H = 512;   // E1_len / 2 from which the split-eq inner sums (NESTED = 2) pay
 
 struct cozk_poly {
     cozk_ctx* ctx;
@@ -49,9 +54,9 @@ struct cozk_spliteq {
 };
 
 static inline unsigned grid_for(size_t n) { return (unsigned)((n + PT - 1) / PT); }
-static inline unsigned grid_capped(size_t n) {
+static inline unsigned grid_capped(size_t n, unsigned cap = MAXBLK) {
     size_t g = (n + PT - 1) / PT;
-    return (unsigned)(g > MAXBLK ? MAXBLK : (g ? g : 1));
+    return (unsigned)(g > cap ? cap : (g ? g : 1));
 }
 // COZK_SUM_GRID_MAX=n (n > 0): at most n workgroups for the grid-stride round-sum launches (layer cubic sums, fused bind + sums,
 // toggle and outer rounds), so that each lane adds thousands of terms -- what the lazy 9 x 29 sums are tested at.  Read on every
@@ -60,6 +65,13 @@ static inline unsigned sum_grid(unsigned gx) {
     const char* e = getenv("COZK_SUM_GRID_MAX");
     const long n = e ? atol(e) : 0;
     return n > 0 && (unsigned long)n < gx ? (unsigned)n : gx;
+}
+
+// Few, long lanes for the evaluate kernel: a lane ends with one wide reduction per accumulator (8 products) + the block sums, which
+// would outweigh its multiply-add chains if it only had a handful of elements.  COZK_EVAL_GX=n: another cap, for A/B runs.
+static unsigned eval_grid_max() {
+    static const unsigned cap = getenv("COZK_EVAL_GX") ? (unsigned)atoi(getenv("COZK_EVAL_GX")) : EVAL_GRID_MAX;
+    return cap;
 }
 
 // Grid of a grid-stride kernel whose waves are long (thousands of instructions per element): exactly the workgroups the chip
@@ -1372,12 +1384,23 @@ __global__ void __launch_bounds__(1024) k_eq_build(EqBuildPoint pt, int nv, fe* 
 // from the pool of the context whose ABI call is running on this thread (cozk_guard)
 static fe* dev_alloc_fe(size_t n) { return (fe*)ctx_dev_alloc(t_cur_ctx, (n ? n : 1) * sizeof(fe)); }
 
+// COZK_SYNC_ROUNDS (set to anything): wait for round results with hipStreamSynchronize; nothing publishes or spins on the pinned word
+static bool sync_rounds() {
+    static const bool on = getenv("COZK_SYNC_ROUNDS") != nullptr;
+    return on;
+}
+// COZK_TRACE_ROUNDS (set to anything): the resident round kernel times its phases (it reads the 100 MHz clock four times per round)
+// and cozk_layer_prove_rounds prints them
+static bool trace_rounds() {
+    static const bool on = getenv("COZK_TRACE_ROUNDS") != nullptr;
+    return on;
+}
+
 // copy k small results from device scratch to host (sync)
 // the stream's work up to here has finished: a stream memory write of a sequence number + a host spin on that pinned word replaces
 // hipStreamSynchronize's event / interrupt path (tens of microseconds) with a cache-line hand-off (COZK_SYNC_ROUNDS: the blocking wait)
 static void stream_drain_by_flag(cozk_ctx* ctx) {
-    static const bool use_flag = getenv("COZK_SYNC_ROUNDS") == nullptr;
-    if (!use_flag) {
+    if (sync_rounds()) {
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         return;
     }
@@ -1396,8 +1419,8 @@ static void stream_drain_by_flag(cozk_ctx* ctx) {
 }
 // arm the finishing kernel's own publication of the round (COZK_FLAG_IN_FINISH=0 / COZK_SYNC_ROUNDS: not armed, fetch_fe drains the stream)
 static RoundPublish arm_round_publish(cozk_ctx* ctx) {
-    static const bool on = !(getenv("COZK_FLAG_IN_FINISH") && atoi(getenv("COZK_FLAG_IN_FINISH")) == 0) && getenv("COZK_SYNC_ROUNDS") == nullptr;
-    if (!on) return RoundPublish{nullptr, nullptr, 0};
+    static const bool on = !(getenv("COZK_FLAG_IN_FINISH") && atoi(getenv("COZK_FLAG_IN_FINISH")) == 0);
+    if (!on || sync_rounds()) return RoundPublish{nullptr, nullptr, 0};
     if (!ctx->round_flag) HIP_TRY(hipHostMalloc((void**)&ctx->round_flag, 64, hipHostMallocMapped | hipHostMallocCoherent));
     if (!ctx->finish_ticket) {
         HIP_TRY(hipMalloc((void**)&ctx->finish_ticket, 64));
@@ -1432,6 +1455,59 @@ static void fetch_fe(cozk_ctx* ctx, const fe* d, size_t k, fe* h) {
 }
 // where a finishing kernel should put k round results (pinned host memory, mapped into the device)
 static fe* result_slot(cozk_ctx* ctx, size_t k) { return (fe*)ctx_pinned(ctx, k * sizeof(fe)); }
+
+// The two-stage round sums: a kernel writes `rows` rows of gx block partials, k_finish_sums adds each row up into the pinned result
+// slot and publishes the round, the host fetches the results.  sum_launch makes the ONE scratch reservation of such a call: `meta_bytes`
+// for the caller's pointer tables (at `meta`), then, 32-byte aligned, rows * gx_max + rows partials; gx_max is the LARGEST grid the
+// caller may still pick.  `res` is the pinned slot for n_res results (a caller may have kernels of its own write results behind the
+// finished rows before it calls finish_sums).
+struct SumLaunch {
+    fe* partial;
+    fe* res;
+    char* meta;
+    size_t cap;    // partials reserved
+    size_t n_res;  // results fetched
+};
+static SumLaunch sum_launch(cozk_ctx* ctx, unsigned rows, unsigned gx_max, size_t n_res, size_t meta_bytes = 0) {
+    const size_t meta = (meta_bytes + 31) & ~(size_t)31, cap = (size_t)rows * gx_max;
+    ctx->scratch.reserve(meta + (cap + rows) * sizeof(fe));
+    char* base = (char*)ctx->scratch.p;
+    return SumLaunch{(fe*)(base + meta), result_slot(ctx, n_res), base, cap, n_res};
+}
+// k_finish_sums over `rows` rows of `gx` partials with the round's publication armed, the launch check, and the n_res results to
+// `out`.  ctx->armed_seq is 0 on every way out, so a failure here cannot make a later fetch_fe wait for a stale sequence number.
+static void finish_sums(cozk_ctx* ctx, const SumLaunch& sl, unsigned rows, unsigned gx, fe scale, int apply_scale, fe* out) {
+    COZK_REQUIRE((size_t)rows * gx <= sl.cap && rows <= sl.n_res, "finish_sums: more block partials than sum_launch reserved");
+    struct Disarm {
+        cozk_ctx* ctx;
+        ~Disarm() { ctx->armed_seq = 0; }
+    } disarm{ctx};
+    k_finish_sums<<<rows, PT, 0, ctx->stream>>>(sl.partial, gx, scale, apply_scale, sl.res, arm_round_publish(ctx));
+    HIP_TRY(hipGetLastError());
+    fetch_fe(ctx, sl.res, sl.n_res, out);
+}
+
+// make ping-pong side `which` of a polynomial or layer hold n elements (both components of a Rep3 object)
+template <class P>
+static void pingpong_ensure(P* p, int which, size_t n) {
+    if (p->cap[which] >= n) return;
+    for (int c = 0; c < 2; c++) {
+        if (p->buf[which][c]) ctx_dev_free(p->ctx, p->buf[which][c]);
+        p->buf[which][c] = nullptr;
+    }
+    p->buf[which][0] = dev_alloc_fe(n);
+    if (p->mode == COZK_MODE_REP3) p->buf[which][1] = dev_alloc_fe(n);
+    p->cap[which] = n;
+}
+
+// the round polynomial of compute_cubic through the evaluations [g0, claim - g0, g2, g3] (dense_interleaved_poly.rs:349-365): its four
+// additive coefficient shares, low to high
+static void cubic_coeffs_out(const fe s[3], const uint64_t prev_claim[4], uint64_t out_coeffs[16]) {
+    fe ev[4] = {s[0], Fr::sub(fe_from_u64x4(prev_claim), s[0]), s[1], s[2]};
+    fe cf[4];
+    unipoly_from_evals(ev, 4, cf);
+    for (int i = 0; i < 4; i++) fe_to_u64x4(cf[i], out_coeffs + 4 * i);
+}
 
 // build an eq table on device: out (len 2^nv) from point r (host), big-endian
 static void eq_evals_device(cozk_ctx* ctx, const fe* r, int nv, fe* out, fe* tmp) {
@@ -1548,15 +1624,7 @@ int cozk_poly_bind(cozk_ctx* ctx, cozk_poly* p, const uint64_t r[4], int order) 
             dst = p->cur;  // in place: lane i reads (i, i+n) and writes i
         } else {
             dst = p->cur < 0 ? 0 : 1 - p->cur;
-            if (p->cap[dst] < n) {
-                for (int c = 0; c < 2; c++) {
-                    if (p->buf[dst][c]) ctx_dev_free(p->ctx, p->buf[dst][c]);
-                    p->buf[dst][c] = nullptr;
-                }
-                p->buf[dst][0] = dev_alloc_fe(n);
-                if (p->mode == COZK_MODE_REP3) p->buf[dst][1] = dev_alloc_fe(n);
-                p->cap[dst] = n;
-            }
+            pingpong_ensure(p, dst, n);
         }
         fe* oa = p->buf[dst][0];
         fe* ob = p->buf[dst][1];
@@ -1619,19 +1687,11 @@ int cozk_poly_batch_evaluate_at_chi(cozk_ctx* ctx, const cozk_poly* const* polys
             hl[i] = polys[i]->len;
             if (hl[i] > maxlen) maxlen = hl[i];
         }
-        unsigned gx = grid_capped(maxlen);
-        // few, long lanes: a lane ends with one wide reduction per accumulator (8 products) + the block sums, which would outweigh
-        // its multiply-add chains if it only had a handful of elements (env COZK_EVAL_GX for A/B runs)
-        static const unsigned gx_cap = getenv("COZK_EVAL_GX") ? (unsigned)atoi(getenv("COZK_EVAL_GX")) : 192u;
-        if (gx > gx_cap) gx = gx_cap;
-        size_t meta = k * (2 * sizeof(void*) + sizeof(size_t));
-        ctx->scratch.reserve(meta + (k * gx + k) * sizeof(fe) + 64);
-        char* base = (char*)ctx->scratch.p;
-        const fe** da = (const fe**)base;
+        const unsigned gx = grid_capped(maxlen, eval_grid_max());
+        const SumLaunch sl = sum_launch(ctx, (unsigned)k, gx, k, k * (2 * sizeof(void*) + sizeof(size_t)));
+        const fe** da = (const fe**)sl.meta;
         const fe** db = da + k;
         size_t* dl = (size_t*)(db + k);
-        fe* partial = (fe*)(((uintptr_t)(dl + k) + 31) & ~(uintptr_t)31);
-        fe* res = result_slot(ctx, k);  // pinned: no device-to-host copy behind the finishing kernel
         HIP_TRY(hipMemcpyAsync(da, ha.data(), k * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipMemcpyAsync(db, hb.data(), k * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipMemcpyAsync(dl, hl.data(), k * sizeof(size_t), hipMemcpyHostToDevice, ctx->stream));
@@ -1642,13 +1702,11 @@ int cozk_poly_batch_evaluate_at_chi(cozk_ctx* ctx, const cozk_poly* const* polys
             uint64_t alg = (uint64_t)chi->n * 32;
             for (size_t i = 0; i < k; i++) alg += (uint64_t)hl[i] * (mode == COZK_MODE_REP3 ? 64 : 32);
             ProfScope prof(ctx, COZK_PROF_EVAL_CHI, alg);
-            if (mode == COZK_MODE_REP3) k_poly_eval_chi<2><<<grid, PT, 0, ctx->stream>>>(da, db, dl, (const fe*)chi->d, (int)k, partial);
-            else k_poly_eval_chi<1><<<grid, PT, 0, ctx->stream>>>(da, db, dl, (const fe*)chi->d, (int)k, partial);
+            if (mode == COZK_MODE_REP3) k_poly_eval_chi<2><<<grid, PT, 0, ctx->stream>>>(da, db, dl, (const fe*)chi->d, (int)k, sl.partial);
+            else k_poly_eval_chi<1><<<grid, PT, 0, ctx->stream>>>(da, db, dl, (const fe*)chi->d, (int)k, sl.partial);
         }
-        k_finish_sums<<<(unsigned)k, PT, 0, ctx->stream>>>(partial, gx, fr_two_inv(), mode == COZK_MODE_REP3 ? 1 : 0, res, arm_round_publish(ctx));
-        HIP_TRY(hipGetLastError());
         std::vector<fe> h(k);
-        fetch_fe(ctx, res, k, h.data());
+        finish_sums(ctx, sl, (unsigned)k, gx, fr_two_inv(), mode == COZK_MODE_REP3 ? 1 : 0, h.data());
         for (size_t i = 0; i < k; i++) fe_to_u64x4(h[i], out + 4 * i);
     });
 }
@@ -1657,18 +1715,13 @@ int cozk_poly_batch_evaluate_at_chi(cozk_ctx* ctx, const cozk_poly* const* polys
 int cozk_poly_dot_product_with_public(cozk_ctx* ctx, const cozk_poly* p, const cozk_vec* pub, uint64_t a[4], uint64_t b[4]) {
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(ctx && p && pub && a && pub->kind == COZK_SCALAR_FR && pub->n == p->len, "dot_product: length mismatch (zip_eq)");
-        unsigned gx = grid_capped(p->len);
-        if (gx > 512) gx = 512;
-        ctx->scratch.reserve((2 * gx + 2) * sizeof(fe));
-        fe* partial = ctx->scratch.as<fe>();
-        fe* res = result_slot(ctx, 2);
-        int nc = p->mode == COZK_MODE_REP3 ? 2 : 1;
-        if (nc == 2) k_poly_dot_public<2><<<gx, PT, 0, ctx->stream>>>(poly_a(p), poly_b(p), (const fe*)pub->d, p->len, partial);
-        else k_poly_dot_public<1><<<gx, PT, 0, ctx->stream>>>(poly_a(p), poly_b(p), (const fe*)pub->d, p->len, partial);
-        k_finish_sums<<<nc, PT, 0, ctx->stream>>>(partial, gx, Fr::one(), 0, res, arm_round_publish(ctx));
-        HIP_TRY(hipGetLastError());
+        const unsigned gx = grid_capped(p->len, BATCH_GRID_MAX);
+        const int nc = p->mode == COZK_MODE_REP3 ? 2 : 1;
+        const SumLaunch sl = sum_launch(ctx, nc, gx, nc);
+        if (nc == 2) k_poly_dot_public<2><<<gx, PT, 0, ctx->stream>>>(poly_a(p), poly_b(p), (const fe*)pub->d, p->len, sl.partial);
+        else k_poly_dot_public<1><<<gx, PT, 0, ctx->stream>>>(poly_a(p), poly_b(p), (const fe*)pub->d, p->len, sl.partial);
         fe h[2];
-        fetch_fe(ctx, res, nc, h);
+        finish_sums(ctx, sl, nc, gx, Fr::one(), 0, h);
         fe_to_u64x4(h[0], a);
         if (nc == 2 && b) fe_to_u64x4(h[1], b);
     });
@@ -1850,17 +1903,13 @@ int cozk_open_quadratic_evals(cozk_ctx* ctx, const cozk_poly* const* polys, cons
             hh[i] = polys[i]->len / 2;
             if (hh[i] > maxh) maxh = hh[i];
         }
-        unsigned gx = grid_capped(maxh);
-        if (gx > 512) gx = 512;
-        size_t meta = k * (3 * sizeof(void*) + sizeof(size_t));
-        ctx->scratch.reserve(meta + (2 * k * gx + 2 * k) * sizeof(fe) + 64);
-        char* base = (char*)ctx->scratch.p;
-        const fe** da = (const fe**)base;
+        const unsigned gx = grid_capped(maxh, BATCH_GRID_MAX);
+        const SumLaunch sl = sum_launch(ctx, (unsigned)(2 * k), gx, 2 * k, k * (3 * sizeof(void*) + sizeof(size_t)));
+        fe* partial = sl.partial;
+        const fe** da = (const fe**)sl.meta;
         const fe** db = da + k;
         const fe** de = db + k;
         size_t* dh = (size_t*)(de + k);
-        fe* partial = (fe*)(((uintptr_t)(dh + k) + 31) & ~(uintptr_t)31);
-        fe* res = result_slot(ctx, 2 * k);
         dim3 grid(gx, (unsigned)k);
         if (k <= 16) {
             OpenQuadArgs args;
@@ -1881,10 +1930,8 @@ int cozk_open_quadratic_evals(cozk_ctx* ctx, const cozk_poly* const* polys, cons
             if (mode == COZK_MODE_REP3) k_open_quadratic<2><<<grid, PT, 0, ctx->stream>>>(da, db, de, dh, partial);
             else k_open_quadratic<1><<<grid, PT, 0, ctx->stream>>>(da, db, de, dh, partial);
         }
-        k_finish_sums<<<(unsigned)(2 * k), PT, 0, ctx->stream>>>(partial, gx, fr_two_inv(), mode == COZK_MODE_REP3 ? 1 : 0, res, arm_round_publish(ctx));
-        HIP_TRY(hipGetLastError());
         std::vector<fe> h(2 * k);
-        fetch_fe(ctx, res, 2 * k, h.data());
+        finish_sums(ctx, sl, (unsigned)(2 * k), gx, fr_two_inv(), mode == COZK_MODE_REP3 ? 1 : 0, h.data());
         for (size_t i = 0; i < 2 * k; i++) fe_to_u64x4(h[i], out + 4 * i);
     });
 }
@@ -1909,27 +1956,19 @@ int cozk_prod_sumcheck_evals(cozk_ctx* ctx, const cozk_poly* const* polys, size_
             }
         }
         size_t half = len / 2;
-        unsigned gx = grid_capped(half);
-        if (gx > 512) gx = 512;
-        ctx->scratch.reserve((4 * (size_t)gx + 4) * sizeof(fe) + 64);
-        fe* partial = ctx->scratch.as<fe>();
-        fe* res = result_slot(ctx, 4);
+        const unsigned gx = grid_capped(half, BATCH_GRID_MAX);
+        const SumLaunch sl = sum_launch(ctx, 4, gx, (size_t)degree);
         ProdRoundPtrs tab;
         for (int j = 0; j < 4; j++) {
             tab.a[j] = ha[j];
             tab.b[j] = hb[j];
         }
-#define PROD_LAUNCH(NCV, MV) k_prod_round<NCV, MV><<<gx, PT, 0, ctx->stream>>>(tab, shared, half, degree, partial)
-        if (shared >= 0) {
-            switch (m) { case 1: PROD_LAUNCH(2, 1); break; case 2: PROD_LAUNCH(2, 2); break; case 3: PROD_LAUNCH(2, 3); break; default: PROD_LAUNCH(2, 4); }
-        } else {
-            switch (m) { case 1: PROD_LAUNCH(1, 1); break; case 2: PROD_LAUNCH(1, 2); break; case 3: PROD_LAUNCH(1, 3); break; default: PROD_LAUNCH(1, 4); }
-        }
-#undef PROD_LAUNCH
-        k_finish_sums<<<(unsigned)degree, PT, 0, ctx->stream>>>(partial, gx, fr_two_inv(), shared >= 0 ? 1 : 0, res, arm_round_publish(ctx));
-        HIP_TRY(hipGetLastError());
+        using ProdRoundKernel = void (*)(ProdRoundPtrs, int, size_t, int, fe*);
+        static const ProdRoundKernel kernels[2][4] = {{k_prod_round<1, 1>, k_prod_round<1, 2>, k_prod_round<1, 3>, k_prod_round<1, 4>},
+                                                      {k_prod_round<2, 1>, k_prod_round<2, 2>, k_prod_round<2, 3>, k_prod_round<2, 4>}};  // [shared][m - 1]
+        kernels[shared >= 0][m - 1]<<<gx, PT, 0, ctx->stream>>>(tab, shared, half, degree, sl.partial);
         fe h[4];
-        fetch_fe(ctx, res, (size_t)degree, h);
+        finish_sums(ctx, sl, (unsigned)degree, gx, fr_two_inv(), shared >= 0 ? 1 : 0, h);
         for (int e = 0; e < degree; e++) fe_to_u64x4(h[e], out + 4 * e);
     });
 }
@@ -1943,19 +1982,15 @@ int cozk_spartan_first_round(cozk_ctx* ctx, const cozk_poly* za, const cozk_poly
                          za->len == zb->len && za->len == zc->len && za->len == pub->len && za->len >= 2,
                      "spartan_first_round: bad argument");
         size_t half = za->len / 2;
-        unsigned gx = grid_capped(half);
-        if (gx > 512) gx = 512;
-        ctx->scratch.reserve((8 * (size_t)gx + 8) * sizeof(fe));
-        fe* partial = ctx->scratch.as<fe>();
-        fe* res = result_slot(ctx, 8);
+        const unsigned gx = grid_capped(half, BATCH_GRID_MAX);
+        const SumLaunch sl = sum_launch(ctx, 8, gx, 8);
+        fe* partial = sl.partial;
         if (za->mode == COZK_MODE_REP3)
             k_spartan_first<2><<<gx, PT, 0, ctx->stream>>>(poly_a(za), poly_b(za), poly_a(zb), poly_b(zb), poly_a(zc), poly_b(zc), poly_a(pub), half, partial);
         else
             k_spartan_first<1><<<gx, PT, 0, ctx->stream>>>(poly_a(za), nullptr, poly_a(zb), nullptr, poly_a(zc), nullptr, poly_a(pub), half, partial);
-        k_finish_sums<<<8, PT, 0, ctx->stream>>>(partial, gx, Fr::one(), 0, res, arm_round_publish(ctx));
-        HIP_TRY(hipGetLastError());
         fe h[8];
-        fetch_fe(ctx, res, 8, h);
+        finish_sums(ctx, sl, 8, gx, Fr::one(), 0, h);
         for (int e = 0; e < 4; e++) {
             fe c = za->mode == COZK_MODE_REP3 ? Fr::mul(h[4 + e], fr_two_inv()) : h[4 + e];
             fe_to_u64x4(Fr::sub(h[e], c), out + 4 * e);
@@ -1972,19 +2007,15 @@ int cozk_spartan_second_round(cozk_ctx* ctx, const cozk_poly* z, const cozk_poly
                          c->mode == COZK_MODE_PLAIN && z->len == a->len && z->len == b->len && z->len == c->len && z->len >= 2,
                      "spartan_second_round: bad argument");
         size_t half = z->len / 2;
-        unsigned gx = grid_capped(half);
-        if (gx > 512) gx = 512;
-        ctx->scratch.reserve((6 * (size_t)gx + 6) * sizeof(fe));
-        fe* partial = ctx->scratch.as<fe>();
-        fe* res = result_slot(ctx, 6);
-        int nc = z->mode == COZK_MODE_REP3 ? 2 : 1;
+        const unsigned gx = grid_capped(half, BATCH_GRID_MAX);
+        const int nc = z->mode == COZK_MODE_REP3 ? 2 : 1;
+        const SumLaunch sl = sum_launch(ctx, 3 * nc, gx, (size_t)(3 * nc));
+        fe* partial = sl.partial;
         fe c0 = fe_from_u64x4(coef), c1 = fe_from_u64x4(coef + 4), c2 = fe_from_u64x4(coef + 8);
         if (nc == 2) k_spartan_second<2><<<gx, PT, 0, ctx->stream>>>(poly_a(z), poly_b(z), poly_a(a), poly_a(b), poly_a(c), c0, c1, c2, half, partial);
         else k_spartan_second<1><<<gx, PT, 0, ctx->stream>>>(poly_a(z), nullptr, poly_a(a), poly_a(b), poly_a(c), c0, c1, c2, half, partial);
-        k_finish_sums<<<(unsigned)(3 * nc), PT, 0, ctx->stream>>>(partial, gx, Fr::one(), 0, res, arm_round_publish(ctx));
-        HIP_TRY(hipGetLastError());
         fe h[6];
-        fetch_fe(ctx, res, (size_t)(3 * nc), h);
+        finish_sums(ctx, sl, 3 * nc, gx, Fr::one(), 0, h);
         for (int e = 0; e < 3; e++) {
             fe_to_u64x4(h[e], out_a + 4 * e);
             if (nc == 2) fe_to_u64x4(h[3 + e], out_b + 4 * e);
@@ -2154,15 +2185,7 @@ int cozk_layer_bind(cozk_ctx* ctx, cozk_layer* l, const uint64_t r[4]) {
         size_t nch = (l->len + 3) / 4;
         size_t nout = 2 * nch;
         int dst = 1 - l->cur;
-        if (l->cap[dst] < nout) {
-            for (int c = 0; c < 2; c++) {
-                if (l->buf[dst][c]) ctx_dev_free(l->ctx, l->buf[dst][c]);
-                l->buf[dst][c] = nullptr;
-            }
-            l->buf[dst][0] = dev_alloc_fe(nout);
-            if (l->mode == COZK_MODE_REP3) l->buf[dst][1] = dev_alloc_fe(nout);
-            l->cap[dst] = nout;
-        }
+        pingpong_ensure(l, dst, nout);
         fe rr = fe_from_u64x4(r);
         if (l->mode == COZK_MODE_REP3)
             k_layer_bind<2><<<grid_for(nch), PT, 0, ctx->stream>>>(l->buf[l->cur][0], l->buf[l->cur][1], l->buf[dst][0], l->buf[dst][1], l->len, rr);
@@ -2236,51 +2259,56 @@ int cozk_spliteq_bind(cozk_ctx* ctx, cozk_spliteq* e, const uint64_t r[4]) {
     });
 }
 
+// Which kernel a layer of `chunks` 4-element chunks takes, for the sums alone (layer_cubic_kernel) and for bind + sums in one pass
+// (layer_bind_cubic_kernel).  F9: the 9 x 29 multiplier kernels (fr9.hip.hpp) for layers large enough to be throughput-bound;
+// COZK_LAYER_F9=0: the saturated kernels everywhere.  NESTED: 0 the eq table is E2 alone, 1 E1 x E2, 2 E1 x E2 with the split-eq
+// inner sums (layer9_terms) -- 9 x 29 plain kernels only, from E1_len / 2 >= LAYER_GROUPED_MIN_E1H (the Rep3 kernels lose with the
+// three group accumulators: 0.58 vs 0.52 ms, register pressure); COZK_LAYER_GROUPED=0 switches it off.
+struct LayerVariant {
+    bool f9;
+    int nested;
+};
+static LayerVariant layer_variant(const cozk_layer* l, const cozk_spliteq* e, size_t chunks) {
+    static const bool f9_env = (getenv("COZK_LAYER_F9") ? atoi(getenv("COZK_LAYER_F9")) : 1) != 0;
+    static const bool group_env = !(getenv("COZK_LAYER_GROUPED") && atoi(getenv("COZK_LAYER_GROUPED")) == 0);
+    const bool f9 = f9_env && chunks >= LAYER_F9_MIN_CHUNKS, nested = e->E1_len != 1;
+    const bool grouped = f9 && nested && group_env && l->mode == COZK_MODE_PLAIN && e->E1_len / 2 >= LAYER_GROUPED_MIN_E1H;
+    return LayerVariant{f9, grouped ? 2 : (nested ? 1 : 0)};
+}
+using LayerCubicKernel = void (*)(const fe*, const fe*, size_t, const fe*, size_t, const fe*, size_t, fe*);
+static LayerCubicKernel layer_cubic_kernel(int mode, LayerVariant v) {
+    if (mode == COZK_MODE_REP3) {
+        if (v.f9) return v.nested ? k_layer_cubic9<2, 1> : k_layer_cubic9<2, 0>;
+        return v.nested ? k_layer_cubic<2, 1> : k_layer_cubic<2, 0>;
+    }
+    if (v.f9) return v.nested == 2 ? k_layer_cubic9<1, 2> : (v.nested ? k_layer_cubic9<1, 1> : k_layer_cubic9<1, 0>);
+    return v.nested ? k_layer_cubic<1, 1> : k_layer_cubic<1, 0>;
+}
+using LayerBindCubicKernel = void (*)(const fe*, const fe*, fe*, fe*, size_t, fe, const fe*, size_t, const fe*, size_t, fe*);
+static LayerBindCubicKernel layer_bind_cubic_kernel(int mode, LayerVariant v) {
+    if (mode == COZK_MODE_REP3) {
+        if (v.f9) return v.nested ? k_layer_bind_cubic9<2, 1> : k_layer_bind_cubic9<2, 0>;
+        return v.nested ? k_layer_bind_cubic<2, 1> : k_layer_bind_cubic<2, 0>;
+    }
+    if (v.f9) return v.nested == 2 ? k_layer_bind_cubic9<1, 2> : (v.nested ? k_layer_bind_cubic9<1, 1> : k_layer_bind_cubic9<1, 0>);
+    return v.nested ? k_layer_bind_cubic<1, 1> : k_layer_bind_cubic<1, 0>;
+}
+// workgroups of a layer round-sum launch over `chunks` chunks: the 9 x 29 kernels fill the chip exactly (resident_grid)
+static unsigned layer_sum_grid(cozk_ctx* ctx, const void* kernel, bool f9, size_t chunks) {
+    return sum_grid(f9 ? resident_grid(kernel, (chunks + PT - 1) / PT, ctx->device) : grid_capped(chunks, ROUND_GRID_MAX));
+}
+
 // Rep3BatchedCubicSumcheckWorker::compute_cubic (dense_interleaved_poly.rs:210-365): returns the 4
 // additive coefficient shares of the round polynomial through evals [g0, claim - g0, g2, g3]
 static void layer_cubic_sums(cozk_ctx* ctx, const cozk_layer* l, const cozk_spliteq* eq, fe s[3]) {
-    size_t nch = (l->len + 3) / 4;
-    unsigned gx = grid_capped(nch);
-    if (gx > 1024) gx = 1024;
-    gx = sum_grid(gx);
-    ctx->scratch.reserve((3 * (size_t)MAXBLK + 3) * sizeof(fe));
-    fe* partial = ctx->scratch.as<fe>();
-    fe* res = result_slot(ctx, 3);
-    const fe* a = l->buf[l->cur][0];
-    const fe* b = l->buf[l->cur][1];
-    const fe* E1 = eq->E1[eq->c1];
-    const fe* E2 = eq->E2[eq->c2];
-    bool nested = eq->E1_len != 1;
-    static const int f9_env = getenv("COZK_LAYER_F9") ? atoi(getenv("COZK_LAYER_F9")) : 1;
-    if (f9_env != 0 && (l->len + 3) / 4 >= 1024) {  // the 9 x 29 multiplier kernels (fr9.hip.hpp) for throughput-bound layers
-        const size_t need = (nch + PT - 1) / PT;
-        const int dev = ctx->device;
-#define COZK_CUBIC9(NC_, NE_, B_, E1H_)                                                                                             \
-    do {                                                                                                                            \
-        gx = sum_grid(resident_grid((const void*)k_layer_cubic9<NC_, NE_>, need, dev));                                              \
-        k_layer_cubic9<NC_, NE_><<<gx, PT, 0, ctx->stream>>>(a, B_, l->len, E1, E1H_, E2, eq->E2_len, partial);                      \
-    } while (0)
-        static const bool group_env = !(getenv("COZK_LAYER_GROUPED") && atoi(getenv("COZK_LAYER_GROUPED")) == 0);
-        const bool grouped = nested && group_env && eq->E1_len / 2 >= 512;  // split-eq inner sums (layer9_terms, NESTED = 2)
-        if (l->mode == COZK_MODE_REP3) {  // (the Rep3 kernels lose with the three group accumulators: 0.58 vs 0.52 ms, register pressure)
-            if (nested) COZK_CUBIC9(2, 1, b, eq->E1_len / 2);
-            else COZK_CUBIC9(2, 0, b, 0);
-        } else {
-            if (grouped) COZK_CUBIC9(1, 2, b, eq->E1_len / 2);
-            else if (nested) COZK_CUBIC9(1, 1, b, eq->E1_len / 2);
-            else COZK_CUBIC9(1, 0, b, 0);
-        }
-#undef COZK_CUBIC9
-    } else if (l->mode == COZK_MODE_REP3) {
-        if (nested) k_layer_cubic<2, 1><<<gx, PT, 0, ctx->stream>>>(a, b, l->len, E1, eq->E1_len / 2, E2, eq->E2_len, partial);
-        else k_layer_cubic<2, 0><<<gx, PT, 0, ctx->stream>>>(a, b, l->len, E1, 0, E2, eq->E2_len, partial);
-    } else {
-        if (nested) k_layer_cubic<1, 1><<<gx, PT, 0, ctx->stream>>>(a, b, l->len, E1, eq->E1_len / 2, E2, eq->E2_len, partial);
-        else k_layer_cubic<1, 0><<<gx, PT, 0, ctx->stream>>>(a, b, l->len, E1, 0, E2, eq->E2_len, partial);
-    }
-    k_finish_sums<<<3, PT, 0, ctx->stream>>>(partial, gx, Fr::one(), 0, res, arm_round_publish(ctx));
-    HIP_TRY(hipGetLastError());
-    fetch_fe(ctx, res, 3, s);
+    const size_t nch = (l->len + 3) / 4;
+    const LayerVariant v = layer_variant(l, eq, nch);
+    const LayerCubicKernel kernel = layer_cubic_kernel(l->mode, v);
+    const unsigned gx = layer_sum_grid(ctx, (const void*)kernel, v.f9, nch);
+    const SumLaunch sl = sum_launch(ctx, 3, gx, 3);
+    kernel<<<gx, PT, 0, ctx->stream>>>(l->buf[l->cur][0], l->buf[l->cur][1], l->len, eq->E1[eq->c1], v.nested ? eq->E1_len / 2 : 0, eq->E2[eq->c2],
+                                       eq->E2_len, sl.partial);
+    finish_sums(ctx, sl, 3, gx, Fr::one(), 0, s);
 }
 
 int cozk_layer_compute_cubic(cozk_ctx* ctx, const cozk_layer* l, const cozk_spliteq* eq, const uint64_t prev_claim[4],
@@ -2289,10 +2317,7 @@ int cozk_layer_compute_cubic(cozk_ctx* ctx, const cozk_layer* l, const cozk_spli
         COZK_REQUIRE(ctx && l && eq && prev_claim && out_coeffs, "compute_cubic: bad argument");
         fe s[3];
         layer_cubic_sums(ctx, l, eq, s);
-        fe ev[4] = {s[0], Fr::sub(fe_from_u64x4(prev_claim), s[0]), s[1], s[2]};
-        fe cf[4];
-        unipoly_from_evals(ev, 4, cf);
-        for (int i = 0; i < 4; i++) fe_to_u64x4(cf[i], out_coeffs + 4 * i);
+        cubic_coeffs_out(s, prev_claim, out_coeffs);
     });
 }
 
@@ -2308,76 +2333,29 @@ int cozk_layer_round(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const uint64
         int rc = cozk_spliteq_bind(ctx, e, r);
         if (rc != COZK_OK) return rc;
         return cozk_guard(ctx, [&] {
-            size_t nch_in = (l->len + 3) / 4;
-            size_t nout = 2 * nch_in;
-            int dst = 1 - l->cur;
-            if (l->cap[dst] < nout) {
-                for (int c = 0; c < 2; c++) {
-                    if (l->buf[dst][c]) ctx_dev_free(l->ctx, l->buf[dst][c]);
-                    l->buf[dst][c] = nullptr;
-                }
-                l->buf[dst][0] = dev_alloc_fe(nout);
-                if (l->mode == COZK_MODE_REP3) l->buf[dst][1] = dev_alloc_fe(nout);
-                l->cap[dst] = nout;
-            }
-            size_t nch_out = (nout + 3) / 4;
-            unsigned gx = grid_capped(nch_out);
-            if (gx > 1024) gx = 1024;
-            gx = sum_grid(gx);
-            ctx->scratch.reserve((3 * (size_t)MAXBLK + 3) * sizeof(fe));
-            fe* partial = ctx->scratch.as<fe>();
-            fe* res = result_slot(ctx, 3);
+            const size_t nout = 2 * ((l->len + 3) / 4), nch_out = (nout + 3) / 4;
+            const int dst = 1 - l->cur;
+            pingpong_ensure(l, dst, nout);
+            const LayerVariant v = layer_variant(l, e, nch_out);
+            const LayerBindCubicKernel kernel = layer_bind_cubic_kernel(l->mode, v);
+            const unsigned gx = layer_sum_grid(ctx, (const void*)kernel, v.f9, nch_out);
+            const SumLaunch sl = sum_launch(ctx, 3, gx, 3);
             fe rr = fe_from_u64x4(r);
-            const fe *ia = l->buf[l->cur][0], *ib = l->buf[l->cur][1];
-            fe *oa = l->buf[dst][0], *ob = l->buf[dst][1];
-            const fe* E1 = e->E1[e->c1];
-            const fe* E2 = e->E2[e->c2];
-            bool nested = e->E1_len != 1;
+            if (v.f9)
+                for (int d = 0; d < 5; d++) rr = Fr::dbl(rr);  // the 9 x 29 kernels take the challenge times 2^5 = 1 / lambda (fr9.hip.hpp)
+            const bool rep3 = l->mode == COZK_MODE_REP3;
             {
-            // algorithmic bytes: the layer read once and its bound half written once (SURVEY 8d K3 + K4 fused), + the eq tables
-            const uint64_t S = l->mode == COZK_MODE_REP3 ? 64 : 32;
-            ProfScope prof(ctx, COZK_PROF_BIND_CUBIC, (uint64_t)l->len * S + (uint64_t)nout * S + (uint64_t)(e->E1_len + e->E2_len) * 32);
-            // 9 x 29 multiplier kernels for layers large enough to be throughput-bound (COZK_LAYER_F9=0: the saturated kernels)
-            static const int f9_env = getenv("COZK_LAYER_F9") ? atoi(getenv("COZK_LAYER_F9")) : 1;
-            if (f9_env != 0 && nch_out >= 1024) {
-                fe r5 = rr;
-                for (int d = 0; d < 5; d++) r5 = Fr::dbl(r5);  // the challenge times 2^5 = 1 / lambda (fr9.hip.hpp)
-                const size_t need = (nch_out + PT - 1) / PT;
-                const int dev = ctx->device;
-#define COZK_BIND_CUBIC9(NC_, NE_, IB_, OB_, E1H_)                                                                                  \
-    do {                                                                                                                            \
-        gx = sum_grid(resident_grid((const void*)k_layer_bind_cubic9<NC_, NE_>, need, dev));                                         \
-        k_layer_bind_cubic9<NC_, NE_><<<gx, PT, 0, ctx->stream>>>(ia, IB_, oa, OB_, l->len, r5, E1, E1H_, E2, e->E2_len, partial);   \
-    } while (0)
-                static const bool group_env = !(getenv("COZK_LAYER_GROUPED") && atoi(getenv("COZK_LAYER_GROUPED")) == 0);
-                const bool grouped = nested && group_env && e->E1_len / 2 >= 512;  // split-eq inner sums (layer9_terms, NESTED = 2)
-                if (l->mode == COZK_MODE_REP3) {  // (plain only: the Rep3 kernels lose with the group accumulators)
-                    if (nested) COZK_BIND_CUBIC9(2, 1, ib, ob, e->E1_len / 2);
-                    else COZK_BIND_CUBIC9(2, 0, ib, ob, 0);
-                } else {
-                    if (grouped) COZK_BIND_CUBIC9(1, 2, nullptr, nullptr, e->E1_len / 2);
-                    else if (nested) COZK_BIND_CUBIC9(1, 1, nullptr, nullptr, e->E1_len / 2);
-                    else COZK_BIND_CUBIC9(1, 0, nullptr, nullptr, 0);
-                }
-#undef COZK_BIND_CUBIC9
-            } else if (l->mode == COZK_MODE_REP3) {
-                if (nested) k_layer_bind_cubic<2, 1><<<gx, PT, 0, ctx->stream>>>(ia, ib, oa, ob, l->len, rr, E1, e->E1_len / 2, E2, e->E2_len, partial);
-                else k_layer_bind_cubic<2, 0><<<gx, PT, 0, ctx->stream>>>(ia, ib, oa, ob, l->len, rr, E1, 0, E2, e->E2_len, partial);
-            } else {
-                if (nested) k_layer_bind_cubic<1, 1><<<gx, PT, 0, ctx->stream>>>(ia, nullptr, oa, nullptr, l->len, rr, E1, e->E1_len / 2, E2, e->E2_len, partial);
-                else k_layer_bind_cubic<1, 0><<<gx, PT, 0, ctx->stream>>>(ia, nullptr, oa, nullptr, l->len, rr, E1, 0, E2, e->E2_len, partial);
+                // algorithmic bytes: the layer read once and its bound half written once (SURVEY 8d K3 + K4 fused), + the eq tables
+                const uint64_t S = rep3 ? 64 : 32;
+                ProfScope prof(ctx, COZK_PROF_BIND_CUBIC, (uint64_t)l->len * S + (uint64_t)nout * S + (uint64_t)(e->E1_len + e->E2_len) * 32);
+                kernel<<<gx, PT, 0, ctx->stream>>>(l->buf[l->cur][0], rep3 ? l->buf[l->cur][1] : nullptr, l->buf[dst][0], rep3 ? l->buf[dst][1] : nullptr, l->len, rr,
+                                                   e->E1[e->c1], v.nested ? e->E1_len / 2 : 0, e->E2[e->c2], e->E2_len, sl.partial);
             }
-            }
-            k_finish_sums<<<3, PT, 0, ctx->stream>>>(partial, gx, Fr::one(), 0, res, arm_round_publish(ctx));
-            HIP_TRY(hipGetLastError());
+            fe sres[3];
+            finish_sums(ctx, sl, 3, gx, Fr::one(), 0, sres);
             l->cur = dst;
             l->len = nout;
-            fe sres[3];
-            fetch_fe(ctx, res, 3, sres);
-            fe ev[4] = {sres[0], Fr::sub(fe_from_u64x4(prev_claim), sres[0]), sres[1], sres[2]};
-            fe cf[4];
-            unipoly_from_evals(ev, 4, cf);
-            for (int i = 0; i < 4; i++) fe_to_u64x4(cf[i], out_coeffs + 4 * i);
+            cubic_coeffs_out(sres, prev_claim, out_coeffs);
         });
     }
     return cozk_guard(ctx, [&] {
@@ -2394,15 +2372,7 @@ int cozk_layer_round(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const uint64
             rr = fe_from_u64x4(r);
             size_t nout = 2 * ((l->len + 3) / 4);
             int dst = 1 - l->cur;
-            if (l->cap[dst] < nout) {
-                for (int c = 0; c < 2; c++) {
-                    if (l->buf[dst][c]) ctx_dev_free(l->ctx, l->buf[dst][c]);
-                    l->buf[dst][c] = nullptr;
-                }
-                l->buf[dst][0] = dev_alloc_fe(nout);
-                if (l->mode == COZK_MODE_REP3) l->buf[dst][1] = dev_alloc_fe(nout);
-                l->cap[dst] = nout;
-            }
+            pingpong_ensure(l, dst, nout);
             oa = l->buf[dst][0];
             ob = l->buf[dst][1];
             l->cur = dst;
@@ -2442,10 +2412,7 @@ int cozk_layer_round(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const uint64
         HIP_TRY(hipGetLastError());
         fe sres[3];
         fetch_fe(ctx, res, 3, sres);
-        fe ev[4] = {sres[0], Fr::sub(fe_from_u64x4(prev_claim), sres[0]), sres[1], sres[2]};
-        fe cf[4];
-        unipoly_from_evals(ev, 4, cf);
-        for (int i = 0; i < 4; i++) fe_to_u64x4(cf[i], out_coeffs + 4 * i);
+        cubic_coeffs_out(sres, prev_claim, out_coeffs);
     });
 }
 
@@ -2459,7 +2426,7 @@ int cozk_layer_round(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const uint64
 int cozk_layer_prove_rounds(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const uint64_t claim[4], int num_rounds, cozk_round_cb cb,
                             void* user, uint64_t* out_r, uint64_t final_claims[16]) {
     if (!ctx || !l || !e || !claim || !cb || !final_claims || num_rounds < 0 || (num_rounds > 0 && !out_r)) return COZK_ERR_INVALID_ARG;
-    static const bool no_persist = getenv("COZK_NO_PERSIST") != nullptr;
+    static const bool no_persist = getenv("COZK_NO_PERSIST") != nullptr;  // set to anything: every round is its own launch
     uint64_t pc[4], rr[4], coeffs[16], nc[4];
     memcpy(pc, claim, sizeof pc);
     bool have_r = false;
@@ -2495,35 +2462,18 @@ int cozk_layer_prove_rounds(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const
         int rc = cozk_guard(ctx, [&] {
             const int nrem = num_rounds - round;
             // both ping-pong buffers of the layer must hold the current length
-            for (int w = 0; w < 2; w++) {
-                if (w != l->cur && l->cap[w] < l->len) {
-                    for (int c = 0; c < 2; c++) {
-                        if (l->buf[w][c]) ctx_dev_free(l->ctx, l->buf[w][c]);
-                        l->buf[w][c] = nullptr;
-                    }
-                    l->buf[w][0] = dev_alloc_fe(l->len);
-                    if (l->mode == COZK_MODE_REP3) l->buf[w][1] = dev_alloc_fe(l->len);
-                    l->cap[w] = l->len;
-                }
-            }
+            pingpong_ensure(l, 1 - l->cur, l->len);
             if (!ctx->mailbox) HIP_TRY(hipHostMalloc(&ctx->mailbox, sizeof(RoundMailbox), hipHostMallocMapped | hipHostMallocCoherent));
             RoundMailbox* mb = (RoundMailbox*)ctx->mailbox;
             memset(mb, 0, sizeof *mb);
             std::atomic_thread_fence(std::memory_order_seq_cst);
             fe r_first = have_r ? fe_from_u64x4(rr) : Fr::zero();
             const long long ticks = (long long)resident_timeout_s() * MB_TICKS_PER_S;
-            static const bool trace = getenv("COZK_TRACE_ROUNDS") != nullptr;  // the traced variant reads the 100 MHz clock four times per round
-#define COZK_RESIDENT(NC_, TR_, LB0_, LB1_)                                                                                                          \
-    k_layer_rounds_persistent<NC_, TR_><<<1, RT, 0, ctx->stream>>>(l->buf[0][0], LB0_, l->buf[1][0], LB1_, l->cur, l->len, e->E1[0], e->E1[1], e->c1, \
-                                                                   e->E1_len, e->E2[0], e->E2[1], e->c2, e->E2_len, nrem, have_r ? 1 : 0, r_first, mb, ticks)
-            if (l->mode == COZK_MODE_REP3) {
-                if (trace) COZK_RESIDENT(2, 1, l->buf[0][1], l->buf[1][1]);
-                else COZK_RESIDENT(2, 0, l->buf[0][1], l->buf[1][1]);
-            } else {
-                if (trace) COZK_RESIDENT(1, 1, nullptr, nullptr);
-                else COZK_RESIDENT(1, 0, nullptr, nullptr);
-            }
-#undef COZK_RESIDENT
+            const bool rep3 = l->mode == COZK_MODE_REP3;
+            auto* const kernel = rep3 ? (trace_rounds() ? k_layer_rounds_persistent<2, 1> : k_layer_rounds_persistent<2, 0>)
+                                      : (trace_rounds() ? k_layer_rounds_persistent<1, 1> : k_layer_rounds_persistent<1, 0>);
+            kernel<<<1, RT, 0, ctx->stream>>>(l->buf[0][0], rep3 ? l->buf[0][1] : nullptr, l->buf[1][0], rep3 ? l->buf[1][1] : nullptr, l->cur, l->len, e->E1[0],
+                                              e->E1[1], e->c1, e->E1_len, e->E2[0], e->E2[1], e->c2, e->E2_len, nrem, have_r ? 1 : 0, r_first, mb, ticks);
             HIP_TRY(hipGetLastError());
             volatile uint32_t* res_seq = &mb->res_seq;
             volatile uint32_t* status = &mb->status;
@@ -2566,11 +2516,8 @@ int cozk_layer_prove_rounds(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const
             bool alive = true;
             for (; j < nrem; j++) {
                 if (!(alive = wait_result((uint32_t)j + 1))) break;
-                fe s0 = mb->res[0], s2 = mb->res[1], s3 = mb->res[2];
-                fe ev[4] = {s0, Fr::sub(fe_from_u64x4(pc), s0), s2, s3};
-                fe cf[4];
-                unipoly_from_evals(ev, 4, cf);
-                for (int i = 0; i < 4; i++) fe_to_u64x4(cf[i], coeffs + 4 * i);
+                const fe sres[3] = {mb->res[0], mb->res[1], mb->res[2]};
+                cubic_coeffs_out(sres, pc, coeffs);
                 if (cb(user, round + j, coeffs, rr, nc) != 0) give_up("layer_prove_rounds: round callback failed");
                 memcpy(out_r + 4 * (round + j), rr, sizeof rr);
                 memcpy(pc, nc, sizeof pc);
@@ -2598,7 +2545,7 @@ int cozk_layer_prove_rounds(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const
                 return;
             }
             for (int k = 0; k < 4; k++) fe_to_u64x4(mb->res[k], final_claims + 4 * k);
-            if (getenv("COZK_TRACE_ROUNDS"))
+            if (trace_rounds())
                 fprintf(stderr, "[mailbox] %d rounds: device us/round: wait %.1f bind %.1f cubic %.1f publish %.1f\n", nrem,
                         mb->dbg[0] / 100.0 / (nrem + 1), mb->dbg[1] / 100.0 / (nrem + 1), mb->dbg[2] / 100.0 / nrem, mb->dbg[3] / 100.0 / nrem);
             mirror_binds(nrem + bind_first);

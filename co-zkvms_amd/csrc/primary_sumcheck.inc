@@ -796,20 +796,16 @@ int cozk_primary_round_begin(cozk_ctx* ctx, cozk_primary* p, const uint64_t* r, 
         const size_t cap = p->cap[p->cur];
         const int D = p->degree;
         // linear pass
-        unsigned gx = grid_capped(half);
-        if (gx > 1024) gx = 1024;
-        ctx->scratch.reserve(((size_t)2 * D * gx + 2 * D) * sizeof(fe));
-        fe* partial = ctx->scratch.as<fe>();
-        fe* res = result_slot(ctx, 4);
+        const unsigned gx = grid_capped(half, ROUND_GRID_MAX);
+        const SumLaunch sl = sum_launch(ctx, 4, gx, 4);
+        fe* partial = sl.partial;
         k_primary_mask<<<grid_for(half), PT, 0, ctx->stream>>>(st, cap, half, p->n_instr, p->d_live);
         uint64_t lin_bits = 0;  // the linear instructions as a bit set over the instruction indices (< 64: the live mask is one u64)
         for (int q : p->lin) lin_bits |= 1ull << q;
         if (NC == 2) k_primary_linear<2><<<gx, PT, 0, ctx->stream>>>(st, cap, half, p->n_instr, p->n_mem, D, p->d_instrs, lin_bits, p->d_live, partial);
         else k_primary_linear<1><<<gx, PT, 0, ctx->stream>>>(st, cap, half, p->n_instr, p->n_mem, D, p->d_instrs, lin_bits, p->d_live, partial);
-        k_finish_sums<<<4, PT, 0, ctx->stream>>>(partial, gx, Fr::one(), 0, res, arm_round_publish(ctx));
-        HIP_TRY(hipGetLastError());
         fe cf[4];
-        fetch_fe(ctx, res, 4, cf);
+        finish_sums(ctx, sl, 4, gx, Fr::one(), 0, cf);
         for (int k = 0; k < D; k++) {  // the cubic at X = 0, 2, 3, .., D (Horner; X as a field element)
             const fe X = Fr::from_u64(k == 0 ? 0 : (uint64_t)k + 1);
             p->lin_sums[k] = Fr::add(cf[0], Fr::mul(X, Fr::add(cf[1], Fr::mul(X, Fr::add(cf[2], Fr::mul(X, cf[3]))))));
@@ -936,11 +932,9 @@ int cozk_primary_round_finish(cozk_ctx* ctx, cozk_primary* p, uint64_t* out_eval
         if (p->n_items) {
             const fe* st = p->store[p->cur];
             const size_t cap = p->cap[p->cur];
-            unsigned gx = grid_capped(p->n_items);
-            if (gx > 1024) gx = 1024;
-            ctx->scratch.reserve(((size_t)2 * D * gx + 2 * D) * sizeof(fe));
-            fe* partial = ctx->scratch.as<fe>();
-            fe* res = result_slot(ctx, 2 * D);
+            const unsigned gx = grid_capped(p->n_items, ROUND_GRID_MAX);
+            const SumLaunch sl = sum_launch(ctx, 2 * D, gx, 2 * D);
+            fe* partial = sl.partial;
             PrimLevelPtrs P{};
             for (int t = 0; t < PRIM_MAX_LEVELS; t++) {
                 P.a[t] = p->P[t][0];
@@ -952,10 +946,8 @@ int cozk_primary_round_finish(cozk_ctx* ctx, cozk_primary* p, uint64_t* out_eval
             else
                 k_primary_final<1><<<dim3(gx, (unsigned)D), PT, 0, ctx->stream>>>(st, cap, p->n_instr, p->n_mem, D, p->party, p->d_instrs, p->d_mul, p->d_item_idx, p->d_item_slot, p->n_items,
                                                                 p->d_bases, P, partial);
-            k_finish_sums<<<2 * D, PT, 0, ctx->stream>>>(partial, gx, Fr::one(), 0, res, arm_round_publish(ctx));
-            HIP_TRY(hipGetLastError());
             fe s[2 * PRIM_MAX_DEG];
-            fetch_fe(ctx, res, 2 * D, s);
+            finish_sums(ctx, sl, 2 * D, gx, Fr::one(), 0, s);
             for (int k = 0; k < D; k++) {
                 ab[k] = Fr::add(ab[k], s[k]);
                 ad[k] = s[D + k];

@@ -104,24 +104,20 @@ int cozk_poly_batch_dot_public(cozk_ctx* ctx, const cozk_poly* const* polys, siz
             ha[i] = poly_a(polys[i]);
             hb[i] = polys[i]->mode == COZK_MODE_REP3 ? poly_b(polys[i]) : nullptr;
         }
-        unsigned gx = grid_capped(n);
-        if (gx > 192) gx = 192;  // few, long lanes: one wide reduction per accumulator per lane (as k_poly_eval_chi)
+        const unsigned gx = grid_capped(n, EVAL_GRID_MAX);  // few, long lanes: one wide reduction per accumulator per lane (as k_poly_eval_chi)
         const size_t n_out = k * n_pub * 2;
-        ctx->scratch.reserve(2 * k * sizeof(void*) + 64 + (n_out * gx + n_out) * sizeof(fe));
-        const fe** da = (const fe**)ctx->scratch.p;
+        const SumLaunch sl = sum_launch(ctx, (unsigned)n_out, gx, n_out, 2 * k * sizeof(void*));
+        fe* partial = sl.partial;
+        const fe** da = (const fe**)sl.meta;
         const fe** db = da + k;
-        fe* partial = (fe*)(((uintptr_t)(db + k) + 31) & ~(uintptr_t)31);
-        fe* res = result_slot(ctx, n_out);
         HIP_TRY(hipMemcpyAsync(da, ha.data(), k * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipMemcpyAsync(db, hb.data(), k * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));  // host vectors go out of scope
         dim3 grid(gx, (unsigned)k);
         if (n_pub == 2) k_poly_batch_dot_public<2><<<grid, PT, 0, ctx->stream>>>(da, db, n, (const fe*)pubs[0]->d, (const fe*)pubs[1]->d, partial);
         else k_poly_batch_dot_public<1><<<grid, PT, 0, ctx->stream>>>(da, db, n, (const fe*)pubs[0]->d, nullptr, partial);
-        k_finish_sums<<<(unsigned)n_out, PT, 0, ctx->stream>>>(partial, gx, Fr::one(), 0, res, arm_round_publish(ctx));
-        HIP_TRY(hipGetLastError());
         std::vector<fe> h(n_out);
-        fetch_fe(ctx, res, n_out, h.data());
+        finish_sums(ctx, sl, (unsigned)n_out, gx, Fr::one(), 0, h.data());
         for (size_t i = 0; i < n_out; i++) fe_to_u64x4(h[i], out + 4 * i);
     });
 }

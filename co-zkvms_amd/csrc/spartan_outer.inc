@@ -436,7 +436,7 @@ int cozk_outer_create(cozk_ctx* ctx, int mode, int party_id, const cozk_r1cs* sy
         }
         const int pub_comp = mode == COZK_MODE_PLAIN ? 0 : (party_id == 0 ? 0 : (party_id == 1 ? 1 : -1));
         // one thread per step once there are enough steps to fill the chip; thread per row below that (COZK_R1CS_BY_ROW=1 forces it)
-        static const bool by_row_env = getenv("COZK_R1CS_BY_ROW") != nullptr;
+        static const bool by_row_env = getenv("COZK_R1CS_BY_ROW") != nullptr;  // set to anything
         if (num_steps >= 32 && !by_row_env) {
             if (NC == 2)
                 k_r1cs_rows_step<2><<<grid_for(num_steps), PT, 0, ctx->stream>>>(d_rows, (int)rows.size(), padded, num_steps, d_var, d_kind, d_coef, d_va, d_vb, pub_comp,
@@ -544,6 +544,14 @@ static void outer_bind(cozk_ctx* ctx, cozk_outer* st, const fe& r) {
     else if (0 < st->current_index) st->n_out -= 1;
 }
 
+// The 9 x 29 kernel takes the rounds over compact (active-row) storage that are throughput-bound: OUTER_F9_MIN_PAIRS row pairs or
+// more.  COZK_OUTER_F9=0: the saturated kernel everywhere.
+static constexpr size_t OUTER_F9_MIN_PAIRS = 1024;
+static bool outer_use_f9(size_t act_pairs) {
+    static const bool f9_env = !(getenv("COZK_OUTER_F9") && atoi(getenv("COZK_OUTER_F9")) == 0);
+    return f9_env && act_pairs >= OUTER_F9_MIN_PAIRS;
+}
+
 // one round of prove_spartan_cubic_sumcheck: bind with the previous challenge (NULL in the first round), the quadratic
 // evaluations, and the cubic round polynomial as process_eq_sumcheck_round_worker forms it (sumcheck_spartan.rs:44-79).
 // claim = this party's additive share of the running claim; out_coeffs = 4 additive coefficient shares (low -> high).
@@ -556,38 +564,25 @@ int cozk_outer_round(cozk_ctx* ctx, cozk_outer* st, const uint64_t* r, const uin
         COZK_REQUIRE(npairs == ((size_t)1 << (st->n_in + st->n_out)), "outer_round: split-eq tables out of step with the layer");
         const bool act = st->per_step > 1;
         const size_t num_steps = st->L / st->per_step;
-        unsigned gx = grid_capped(act ? num_steps * ((st->act_rows + 1) / 2) : npairs);
-        if (gx > 1024) gx = 1024;
-        gx = sum_grid(gx);
-        ctx->scratch.reserve((3 * (size_t)gx + 3) * sizeof(fe));
-        fe* partial = ctx->scratch.as<fe>();
-        fe* res = result_slot(ctx, 3);
+        const size_t act_pairs = num_steps * ((st->act_rows + 1) / 2);
+        const unsigned gx = sum_grid(grid_capped(act ? act_pairs : npairs, ROUND_GRID_MAX));
+        const SumLaunch sl = sum_launch(ctx, 3, gx, 3);
         const fe* E_in = st->E_in + (((size_t)1 << st->n_in) - 1);
         const fe* E_out = st->E_out + (((size_t)1 << st->n_out) - 1);
         const int want_t0 = st->round > 0 ? 1 : 0;
+        const bool rep3 = st->mode == COZK_MODE_REP3;
         auto& b = st->buf[st->cur];
-        static const bool f9_env = !(getenv("COZK_OUTER_F9") && atoi(getenv("COZK_OUTER_F9")) == 0);
-        const bool f9 = act && f9_env && num_steps * ((st->act_rows + 1) / 2) >= 1024;  // the 9 x 29 kernel for throughput-bound rounds
-        if (f9 && st->mode == COZK_MODE_REP3)
-            k_outer_round_act9<2><<<gx, PT, 0, ctx->stream>>>(b[0][0], b[0][1], b[1][0], b[1][1], b[2][0], b[2][1], (uint32_t)num_steps, (uint32_t)st->per_step,
-                                                            (uint32_t)st->act_rows, E_in, (int)st->n_in, E_out, want_t0, partial);
-        else if (f9)
-            k_outer_round_act9<1><<<gx, PT, 0, ctx->stream>>>(b[0][0], nullptr, b[1][0], nullptr, b[2][0], nullptr, (uint32_t)num_steps, (uint32_t)st->per_step,
-                                                            (uint32_t)st->act_rows, E_in, (int)st->n_in, E_out, want_t0, partial);
-        else if (act && st->mode == COZK_MODE_REP3)
-            k_outer_round_act<2><<<gx, PT, 0, ctx->stream>>>(b[0][0], b[0][1], b[1][0], b[1][1], b[2][0], b[2][1], (uint32_t)num_steps, (uint32_t)st->per_step,
-                                                           (uint32_t)st->act_rows, E_in, (int)st->n_in, E_out, want_t0, partial);
-        else if (act)
-            k_outer_round_act<1><<<gx, PT, 0, ctx->stream>>>(b[0][0], nullptr, b[1][0], nullptr, b[2][0], nullptr, (uint32_t)num_steps, (uint32_t)st->per_step,
-                                                           (uint32_t)st->act_rows, E_in, (int)st->n_in, E_out, want_t0, partial);
-        else if (st->mode == COZK_MODE_REP3)
-            k_outer_round<2><<<gx, PT, 0, ctx->stream>>>(b[0][0], b[0][1], b[1][0], b[1][1], b[2][0], b[2][1], npairs, E_in, (int)st->n_in, E_out, want_t0, partial);
-        else
-            k_outer_round<1><<<gx, PT, 0, ctx->stream>>>(b[0][0], nullptr, b[1][0], nullptr, b[2][0], nullptr, npairs, E_in, (int)st->n_in, E_out, want_t0, partial);
-        k_finish_sums<<<3, PT, 0, ctx->stream>>>(partial, gx, Fr::one(), 0, res, arm_round_publish(ctx));
-        HIP_TRY(hipGetLastError());
+        const fe *az_b = rep3 ? b[0][1] : nullptr, *bz_b = rep3 ? b[1][1] : nullptr, *cz_b = rep3 ? b[2][1] : nullptr;
+        if (act) {
+            auto* const kernel = outer_use_f9(act_pairs) ? (rep3 ? k_outer_round_act9<2> : k_outer_round_act9<1>) : (rep3 ? k_outer_round_act<2> : k_outer_round_act<1>);
+            kernel<<<gx, PT, 0, ctx->stream>>>(b[0][0], az_b, b[1][0], bz_b, b[2][0], cz_b, (uint32_t)num_steps, (uint32_t)st->per_step, (uint32_t)st->act_rows, E_in,
+                                               (int)st->n_in, E_out, want_t0, sl.partial);
+        } else {
+            auto* const kernel = rep3 ? k_outer_round<2> : k_outer_round<1>;
+            kernel<<<gx, PT, 0, ctx->stream>>>(b[0][0], az_b, b[1][0], bz_b, b[2][0], cz_b, npairs, E_in, (int)st->n_in, E_out, want_t0, sl.partial);
+        }
         fe s[3];
-        fetch_fe(ctx, res, 3, s);
+        finish_sums(ctx, sl, 3, gx, Fr::one(), 0, s);
         fe t0 = Fr::zero();
         if (want_t0) t0 = Fr::sub(s[0], st->mode == COZK_MODE_REP3 ? Fr::mul(s[1], fr_two_inv()) : s[1]);
         fe tinf = s[2];

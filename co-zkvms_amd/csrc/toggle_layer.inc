@@ -539,6 +539,23 @@ int cozk_toggle_bind(cozk_ctx* ctx, cozk_toggle* t, const uint64_t r[4]) {
     });
 }
 
+// The cubic-sum kernel of a toggle round.  F9: the 9 x 29 kernel, which exists for the throughput-bound rounds only (nested eq tables,
+// TOGGLE_F9_MIN_PAIRS pairs or more); COZK_TOGGLE_F9=0: the saturated kernel everywhere.  u8: the flags are still the packed 0/1 bytes.
+static constexpr size_t TOGGLE_F9_MIN_PAIRS = 4096;
+using ToggleCubicKernel = void (*)(const fe*, const fe*, const void*, size_t, int, const fe*, int, const fe*, size_t, fe*);
+static ToggleCubicKernel toggle_cubic_kernel(int mode, bool nested, bool u8, size_t npairs) {
+    static const bool f9_env = !(getenv("COZK_TOGGLE_F9") && atoi(getenv("COZK_TOGGLE_F9")) == 0);
+    const bool f9 = f9_env && nested && npairs >= TOGGLE_F9_MIN_PAIRS;
+    if (mode == COZK_MODE_REP3) {
+        if (f9) return u8 ? k_toggle_cubic9<2, 1, 0> : k_toggle_cubic9<2, 1, 1>;
+        if (nested) return u8 ? k_toggle_cubic<2, 1, 0> : k_toggle_cubic<2, 1, 1>;
+        return u8 ? k_toggle_cubic<2, 0, 0> : k_toggle_cubic<2, 0, 1>;
+    }
+    if (f9) return u8 ? k_toggle_cubic9<1, 1, 0> : k_toggle_cubic9<1, 1, 1>;
+    if (nested) return u8 ? k_toggle_cubic<1, 1, 0> : k_toggle_cubic<1, 1, 1>;
+    return u8 ? k_toggle_cubic<1, 0, 0> : k_toggle_cubic<1, 0, 1>;
+}
+
 // one round of prove_sumcheck over the toggle layer: bind layer + split-eq tables with the previous challenge (NULL in
 // the first round), then the three round sums g(0), g(2), g(3) of compute_cubic as this party's additive shares
 int cozk_toggle_round(cozk_ctx* ctx, cozk_toggle* t, cozk_spliteq* e, const uint64_t* r, int party_id, uint64_t out_evals[12]) {
@@ -553,44 +570,22 @@ int cozk_toggle_round(cozk_ctx* ctx, cozk_toggle* t, cozk_spliteq* e, const uint
         const size_t npairs = t->coalesced ? t->L / 2 : t->batch * t->n_cur / 2;
         const int log_half_n = t->coalesced ? -1 : log2_sz(t->n_cur / 2);
         COZK_REQUIRE(npairs >= 1, "toggle_round: fully bound");
-        unsigned gx = grid_capped(npairs);
-        if (gx > 1024) gx = 1024;
-        gx = sum_grid(gx);
-        ctx->scratch.reserve((6 * (size_t)gx + 16) * sizeof(fe));
-        fe* partial = ctx->scratch.as<fe>();
-        fe* res = result_slot(ctx, 9);
+        const unsigned gx = sum_grid(grid_capped(npairs, ROUND_GRID_MAX));
+        const SumLaunch sl = sum_launch(ctx, 6, gx, 9);
         const bool nested = e->E1_len != 1;
         const fe* E1 = e->E1[e->c1];
         const fe* E2 = e->E2[e->c2];
         const int lg1 = nested ? log2_sz(e->E1_len / 2) : 0;
         const bool u8 = t->cur < 0;  // first round: the packed 0/1 bytes
         const void* fl = u8 ? (const void*)t->fl0 : (const void*)tg_fl(t);
-        // the 9 x 29 kernel for the throughput-bound (nested, large) rounds; COZK_TOGGLE_F9=0: the saturated kernel everywhere
-        static const bool f9_env = !(getenv("COZK_TOGGLE_F9") && atoi(getenv("COZK_TOGGLE_F9")) == 0);
-        const bool f9k = f9_env && nested && npairs >= 4096;
-#define COZK_TOGGLE_CUBIC(NC_, PB_)                                                                                                                     \
-    do {                                                                                                                                               \
-        if (nested) {                                                                                                                                  \
-            if (f9k && !u8) k_toggle_cubic9<NC_, 1, 1><<<gx, PT, 0, ctx->stream>>>(tg_fp(t, 0), PB_, fl, npairs, log_half_n, E1, lg1, E2, e->E2_len, partial); \
-            else if (f9k) k_toggle_cubic9<NC_, 1, 0><<<gx, PT, 0, ctx->stream>>>(tg_fp(t, 0), PB_, fl, npairs, log_half_n, E1, lg1, E2, e->E2_len, partial); \
-            else if (u8) k_toggle_cubic<NC_, 1, 0><<<gx, PT, 0, ctx->stream>>>(tg_fp(t, 0), PB_, fl, npairs, log_half_n, E1, lg1, E2, e->E2_len, partial);  \
-            else k_toggle_cubic<NC_, 1, 1><<<gx, PT, 0, ctx->stream>>>(tg_fp(t, 0), PB_, fl, npairs, log_half_n, E1, lg1, E2, e->E2_len, partial);     \
-        } else {                                                                                                                                       \
-            if (u8) k_toggle_cubic<NC_, 0, 0><<<gx, PT, 0, ctx->stream>>>(tg_fp(t, 0), PB_, fl, npairs, log_half_n, E1, 0, E2, e->E2_len, partial);    \
-            else k_toggle_cubic<NC_, 0, 1><<<gx, PT, 0, ctx->stream>>>(tg_fp(t, 0), PB_, fl, npairs, log_half_n, E1, 0, E2, e->E2_len, partial);       \
-        }                                                                                                                                              \
-    } while (0)
-        if (t->mode == COZK_MODE_REP3) COZK_TOGGLE_CUBIC(2, tg_fp(t, 1));
-        else COZK_TOGGLE_CUBIC(1, nullptr);
-#undef COZK_TOGGLE_CUBIC
+        const ToggleCubicKernel kernel = toggle_cubic_kernel(t->mode, nested, u8, npairs);
+        kernel<<<gx, PT, 0, ctx->stream>>>(tg_fp(t, 0), t->mode == COZK_MODE_REP3 ? tg_fp(t, 1) : nullptr, fl, npairs, log_half_n, E1, lg1, E2, e->E2_len, sl.partial);
         // S_all(X): the sums as if every node were one (the reference's eq_eval_sums / evals_assuming_all_ones); before the finishing
         // kernel, which publishes the round
-        if (nested) k_toggle_eq_sums<1><<<1, RT, 0, ctx->stream>>>(E1, lg1, E2, e->E2_len, npairs, res + 6);
-        else k_toggle_eq_sums<0><<<1, RT, 0, ctx->stream>>>(E1, 0, E2, e->E2_len, npairs, res + 6);
-        k_finish_sums<<<6, PT, 0, ctx->stream>>>(partial, gx, Fr::one(), 0, res, arm_round_publish(ctx));
-        HIP_TRY(hipGetLastError());
+        if (nested) k_toggle_eq_sums<1><<<1, RT, 0, ctx->stream>>>(E1, lg1, E2, e->E2_len, npairs, sl.res + 6);
+        else k_toggle_eq_sums<0><<<1, RT, 0, ctx->stream>>>(E1, 0, E2, e->E2_len, npairs, sl.res + 6);
         fe s[9];
-        fetch_fe(ctx, res, 9, s);
+        finish_sums(ctx, sl, 6, gx, Fr::one(), 0, s);
         const bool pub = t->mode == COZK_MODE_PLAIN || party_id == 0;  // additive::add_public: party 0 only
         for (int k = 0; k < 3; k++) {
             fe a = t->mode == COZK_MODE_REP3 ? Fr::mul(s[k], fr_two_inv()) : s[k];  // into_additive

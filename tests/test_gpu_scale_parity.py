@@ -74,11 +74,11 @@ def test_grand_product_harness_equals_c_oracle(cozk, shape, mode):
         (csrc/msm.hip:826); 64 FR + 64 small-value columns = 128 polynomials, so two launch sets of 64 pipelined on the
         second stream (csrc/msm.hip:985, 1047); fold levels k_msm_accumN once a bucket holds more than L0 = 8 references
         (csrc/msm.hip:930);
-      * GKR layers of len / 4 >= 1024 run the 9 x 29 kernels k_layer_cubic9 (csrc/poly.hip:2255); the plain prover's grouped
-        split-eq variant k_layer_cubic9<1, 2> once E1_len / 2 >= 512 (csrc/poly.hip:2264) -- reached by the 2^16 shape's
+      * GKR layers of len / 4 >= 1024 run the 9 x 29 kernels k_layer_cubic9 (LAYER_F9_MIN_CHUNKS); the plain prover's grouped
+        split-eq variant k_layer_cubic9<1, 2> once E1_len / 2 >= 512 (layer_variant) -- reached by the 2^16 shape's
         first round (8 x 2^17 leaves; one dispatch in a kernel trace);
-      * the resident round kernel below ROUND_PERSIST_MAX = 2048 elements (csrc/poly.hip:860, 2474);
-      * batch_evaluate over 2^14 / 2^16-element columns: k_poly_eval_chi capped at 192 workgroups (csrc/poly.hip:1625), so
+      * the resident round kernel below ROUND_PERSIST_MAX = 2048 elements (cozk_layer_prove_rounds);
+      * batch_evaluate over 2^14 / 2^16-element columns: k_poly_eval_chi capped at 192 workgroups (EVAL_GRID_MAX), so
         lanes hold several elements above 49 152."""
     cfg = GP_SHAPES[shape]
     h = cozk.Harness(mode=mode, **cfg)
@@ -112,7 +112,7 @@ def test_production_sizes_equal_committed_c_oracle_digests(cozk, log_n, mode):
     """the bench workload itself (2^20 cycles, bench.py) and the same mix at 2^18: digest and length == the C oracle's
     (tests/golden/scale_pipelines.json).  Beyond (a): the level-0 MSM segment length L0 = M >> 18 grows past 8 once a launch set
     holds more than 2^21 references (csrc/msm.hip:752) -- 64 FR columns x 2^18 scalars x 16 windows -- and the reducing
-    kernels stride their grid past MAXBLK = 2048 workgroups x 256 lanes = 2^19 elements (csrc/poly.hip:20, 54)."""
+    kernels stride their grid past MAXBLK = 2048 workgroups x 256 lanes = 2^19 elements (grid_capped)."""
     row = _scale_row(log_n)
     cfg = dict(row["cfg"])
     cfg.pop("mode")
@@ -125,7 +125,7 @@ def test_production_sizes_equal_committed_c_oracle_digests(cozk, log_n, mode):
 # ---------------------------------------------------------------- (c) Python-oracle pipelines past their thresholds
 def test_spartan_2p10_equals_python_oracle(cozk):
     """co-noir Spartan at log_n = 10 (oracle/pyspartan.py, live), plain and Rep3 == the oracle's bytes.  Over the log_n = 6
-    check this size adds multi-workgroup grids: round 0 of both sumchecks (k_spartan_first / k_spartan_second, csrc/poly.hip:1952)
+    check this size adds multi-workgroup grids: round 0 of both sumchecks (k_spartan_first / k_spartan_second, BATCH_GRID_MAX)
     on 2 workgroups and the transposed sparse mat-vec (k_sparse_matvec3_rows / _items) on about 50; the commit of z sorts its
     1024 scalars on one workgroup (csrc/msm.hip:826).  No 9 x 29 kernel runs at this size (kernel trace of one prove)."""
     import pyspartan
@@ -155,7 +155,7 @@ def test_spartan_2p10_lookup_round_equals_committed_oracle_digest(cozk):
 def test_lookups_primary_2p12_equals_python_oracle(cozk):
     """instruction lookups with the primary sumcheck, 54 memory pairs at 2^12 (oracle/pylookups.py), plain and Rep3 == the
     oracle's plain bytes (Rep3 == plain: tests/test_gpu_lookups.py).  The toggle layer holds 54 circuits x 2^12 leaves under a
-    nested split-eq, so its first rounds have 54 x 2^11 >= 4096 pairs and run k_toggle_cubic9 (csrc/toggle_layer.inc:570; six rounds in a
+    nested split-eq, so its first rounds have 54 x 2^11 >= 4096 pairs and run k_toggle_cubic9 (TOGGLE_F9_MIN_PAIRS; six rounds in a
     kernel trace, the first on the packed 0/1 bytes)."""
     import pylookups
     LK = importlib.import_module("co-zkvms_amd.lookups")
@@ -174,7 +174,7 @@ def test_jolt_spartan_worker_equals_python_oracle(cozk, log_steps):
     """the whole co-jolt Spartan worker (outer + inner + shift sumchecks) on the reference's constraint set at 2^10 / 2^12
     steps (oracle/pyspartan_outer.py run_full), plain and Rep3 == the oracle's plain bytes (Rep3 == plain:
     tests/test_gpu_outer.py).  The outer rounds over the active rows run k_outer_round_act9 once
-    num_steps * act_rows / 2 >= 1024 (csrc/spartan_outer.inc:570): its first rounds at both sizes (seven at 2^10 in a kernel
+    num_steps * act_rows / 2 >= 1024 (OUTER_F9_MIN_PAIRS): its first rounds at both sizes (seven at 2^10 in a kernel
     trace)."""
     import pyspartan_outer
     OU = importlib.import_module("co-zkvms_amd.outer")
@@ -191,7 +191,7 @@ def test_flow_2p8_jolt_memories_equals_committed_oracle_digest(cozk):
     """the chained worker flow at 2^8 cycles with Jolt's 54 memories and 26 subtables: oracle/pyflow.py takes over a minute
     here, so its digest is committed (tests/golden/scale_pipelines.json, "flow").  Plain and Rep3 == that digest and length
     (Rep3 == plain: tests/test_gpu_flow.py).  The lookup toggle layer has 54 x 2^7 >= 4096 pairs under a nested split-eq
-    (k_toggle_cubic9, csrc/toggle_layer.inc:570), its Spartan outer rounds run k_outer_round_act9 (csrc/spartan_outer.inc:570),
+    (k_toggle_cubic9, TOGGLE_F9_MIN_PAIRS), its Spartan outer rounds run k_outer_round_act9 (OUTER_F9_MIN_PAIRS),
     and its MSMs run the fold levels k_msm_accumN (csrc/msm.hip:930) -- all seen in a kernel trace of one prove."""
     FL = importlib.import_module("co-zkvms_amd.flow")
     rows = SCALE_GOLD["flow"]
@@ -425,9 +425,9 @@ def _poly_raw(p):
 @pytest.mark.parametrize("base_len", [3 * (1 << 15) + 5, (1 << 19) + 7])
 def test_reductions_past_grid_caps_equal_big_int_sums(cozk, ctx, mode, base_len):
     """batch_evaluate_at_chi, dot_product_with_public and linear_combination on ragged lengths around 3 * 2^15 + 5 and
-    2^19 + 7, with chi longer than every polynomial.  k_poly_eval_chi caps its grid at 192 workgroups (csrc/poly.hip:1625), so
+    2^19 + 7, with chi longer than every polynomial.  k_poly_eval_chi caps its grid at 192 workgroups (EVAL_GRID_MAX), so
     above 192 x 256 = 49 152 elements a lane holds several; the grid-capped reducing kernels (dot product, linear combination)
-    stop at MAXBLK = 2048 workgroups (csrc/poly.hip:20, 54) and stride past 2^19 elements."""
+    stop at MAXBLK = 2048 workgroups (grid_capped) and stride past 2^19 elements."""
     L = importlib.import_module("co-zkvms_amd._lib")
     md = L.MODE_PLAIN if mode == "plain" else L.MODE_REP3
     lens = [base_len, base_len - 6, base_len - 4097]
