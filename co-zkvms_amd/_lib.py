@@ -123,6 +123,13 @@ SIGNATURES = {
     "cozk_rep3_share_vec": (_i, [_vp, _vp, ctypes.c_char_p, ctypes.c_char_p, _u64, _i, _pp, _pp]),
     "cozk_rep3_scatter": (_i, [_vp, _vp, ctypes.c_char_p, ctypes.c_char_p, _u64, _vp, _i, _pp, _pp]),
     "cozk_vec_fill_prf": (_i, [_vp, _vp, ctypes.c_char_p, _u64]),
+    "cozk_vec_add_scalar": (_i, [_vp, _vp, _vp]),
+    "cozk_shamir_share_vec": (_i, [_vp, _vp, ctypes.c_char_p, _i, _i, _u64, _vp]),
+    "cozk_shamir_eval_vec": (_i, [_vp, _vp, _i, _i, _vp]),
+    "cozk_shamir_scatter": (_i, [_vp, _vp, ctypes.c_char_p, _i, _i, _u64, _vp, _vp]),
+    "cozk_shamir_lagrange": (_i, [_vp, _sz, _vp]),
+    "cozk_shamir_combine_vec": (_i, [_vp, _vp, _vp, _sz, _i, _pp]),
+    "cozk_shamir_combine_points": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, ctypes.POINTER(_i)]),
     "cozk_layer_round": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "cozk_fingerprint_leaves": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _i, _i, _vp, _vp, _sz, _sz]),
     "cozk_layer_prove_rounds": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

@@ -1,0 +1,423 @@
+// Shamir secret sharing on the device: deal a vector to n parties, open vectors and commitments with Lagrange coefficients
+// (mpc-types/src/protocols/shamir.rs).  A ShamirPrimeFieldShare is repr(transparent) over F (shamir/arithmetic/types.rs:
+// 10-30), so a party's share vector is a plain FR cozk_vec and the local operators are the existing element-wise kernels.
+#include "poly.hip.hpp"
+#include "prf.hip.hpp"
+
+#include <string.h>
+
+// ------------------------------------------------------------------ the small-multiplier Horner step
+// a * p + c mod r for canonical Montgomery residues a, c and a PLAIN integer p <= 32 (the evaluation point of party p):
+// the Montgomery residue of x * p is (x R) * p, so no Montgomery product is needed -- 8 multiply-adds give the 9-word value
+//   t = a p + c <= 32 (r - 1) + (r - 1) < 33 r < 2^260            (r < 2^254)
+// and one quotient estimate brings it back below r.  With T = floor(t / 2^228) (< 2^32) and D = floor(r / 2^228) + 1:
+//   q = floor(T / D) <= (t / 2^228) / (r / 2^228) = t / r, so q <= Q = floor(t / r) and t - q r >= 0;
+//   T > t / 2^228 - 1 and D <= r / 2^228 + 1 give t / r - T / D < (t / r + 1) / (r / 2^228) < 34 / (5 * 10^7) < 10^-6, so
+//   q > t / r - 1 - 10^-6, i.e. q >= Q - 1 and t - q r < 2 r < 2^255: it fits 8 words,
+// and ONE conditional subtraction (reduce_once) makes it canonical.  16 multiply-adds and 2 borrow chains instead of the
+// 128 multiply-adds of a Montgomery product.  Input bound: a, c < r and 0 <= p <= 32; output < r.
+static __device__ __forceinline__ fe fr_mul_small_add(const fe& a, uint32_t p, const fe& c) {
+    uint32_t t[9];
+    uint64_t carry = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        uint64_t m = (uint64_t)a.l[i] * p + c.l[i] + carry;  // < 2^32 * 32 + 2^32 + 2^38
+        t[i] = (uint32_t)m;
+        carry = m >> 32;
+    }
+    t[8] = (uint32_t)carry;
+    const uint32_t T = (t[8] << 28) | (t[7] >> 4);          // t >> 228 (t[7] holds bits 224..255); t < 2^260, so t[8] < 16
+    const uint32_t q = T / ((FrParams::MOD[7] >> 4) + 1u);  // <= 33
+    fe s;
+    uint64_t mc = 0, borrow = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        uint64_t m = (uint64_t)q * FrParams::MOD[i] + mc;
+        mc = m >> 32;
+        uint64_t d = (uint64_t)t[i] - (uint32_t)m - borrow;
+        s.l[i] = (uint32_t)d;
+        borrow = (d >> 63) & 1;
+    }
+    return Fr::reduce_once(s);  // word 8 of t - q r is zero (t - q r < 2^255)
+}
+
+// ------------------------------------------------------------------ share / eval: all parties in one pass
+// shares[p][i] = f_i(p + 1), f_i(x) = v[i] + sum_{c = 1..degree} coef_c[i] x^c (shamir.rs:190-207 `share`, :166-175
+// `evaluate_poly`).  A lane owns element i: it obtains its `degree` coefficients once (PRF blocks, or loads), keeps them
+// in registers, runs one Horner chain per party and stores n field elements: 32 B read and n * 32 B written per element.
+// prf_fr (prf.hip.hpp) with the two halves of the block read through constant indices: the same value, and fifteen inlined
+// copies of it keep their block words in registers
+static __device__ __forceinline__ fe shamir_prf_fr(const prf_key key, uint64_t j) {
+    for (uint32_t attempt = 0;; attempt++) {
+        uint32_t w[16];
+        chacha12_block(key, j, attempt, w);
+        fe lo, hi;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            lo.l[i] = w[i];
+            hi.l[i] = w[8 + i];
+        }
+        lo.l[7] &= 0x3fffffffu;
+        hi.l[7] &= 0x3fffffffu;
+        const bool ok_lo = !Fr::geq_mod(lo), ok_hi = !Fr::geq_mod(hi);
+        fe v;
+#pragma unroll
+        for (int i = 0; i < 8; i++) v.l[i] = ok_lo ? lo.l[i] : hi.l[i];
+        if (ok_lo || ok_hi) return Fr::to_mont(v);
+    }
+}
+
+struct ShamirOut {
+    fe* p[COZK_SHAMIR_MAX_PARTIES];
+};
+struct ShamirPrfSrc {  // coef_c[i] = PRF(keys[c - 1], counter + i)
+    const fe* v;
+    uint64_t counter;
+    prf_key keys[COZK_SHAMIR_MAX_DEGREE];
+    __device__ __forceinline__ fe coef(int c, size_t i) const {
+        prf_key key;  // a copy in scalar registers: no address of the kernel argument is taken
+#pragma unroll
+        for (int w = 0; w < 8; w++) key.k[w] = keys[c].k[w];
+        return shamir_prf_fr(key, counter + i);
+    }
+};
+struct ShamirVecSrc {  // the caller's coefficient vectors
+    const fe* v;
+    const fe* c[COZK_SHAMIR_MAX_DEGREE];
+    __device__ __forceinline__ fe coef(int k, size_t i) const { return fe_load(c[k] + i); }
+};
+
+// DEG = 1..7: the degree at compile time, c[k] = coefficient k + 1.  DEG = 0: degree 8..15 at run time; the coefficients are
+// then produced by ONE rolled loop (one copy of the ChaCha block, the key or pointer picked by a wave-uniform index) and pushed
+// into c[] as a shift register, so that c[] is only ever indexed with constants and stays in registers: after the loop
+// c[j] = coefficient deg - j, the leading one first, which is the order Horner consumes them in.
+template <int DEG, class Src>
+__global__ void __launch_bounds__(256) k_shamir_share(Src src, ShamirOut out, size_t n, int degree, int num_parties) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    constexpr int MAXD = DEG ? DEG : COZK_SHAMIR_MAX_DEGREE;
+    const int deg = DEG ? DEG : degree;
+    fe c[MAXD];
+    if (DEG) {
+#pragma unroll
+        for (int k = 0; k < MAXD; k++) c[MAXD - 1 - k] = src.coef(k, i);
+    } else {
+#pragma unroll
+        for (int k = 0; k < MAXD; k++) c[k] = Fr::zero();
+#pragma unroll 1
+        for (int k = 0; k < deg; k++) {
+            const fe next = src.coef(k, i);
+#pragma unroll
+            for (int m = MAXD - 1; m > 0; m--) c[m] = c[m - 1];
+            c[0] = next;
+        }
+    }
+    const fe v = fe_load(src.v + i);
+#pragma unroll 1  // one Horner chain at a time: the coefficients, not several parties' accumulators, own the registers
+    for (int p = 1; p <= num_parties; p++) {
+        fe acc = c[0];
+#pragma unroll
+        for (int m = 1; m < MAXD; m++)
+            if (m < deg) acc = fr_mul_small_add(acc, (uint32_t)p, c[m]);
+        fe_store(out.p[p - 1] + i, fr_mul_small_add(acc, (uint32_t)p, v));
+    }
+}
+
+template <class Src>
+static void launch_share(hipStream_t st, const Src& src, const ShamirOut& out, size_t n, int degree, int num_parties) {
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    switch (degree) {
+#define SHAMIR_CASE_(D) case D: k_shamir_share<D, Src><<<grid, 256, 0, st>>>(src, out, n, degree, num_parties); break
+        SHAMIR_CASE_(1);
+        SHAMIR_CASE_(2);
+        SHAMIR_CASE_(3);
+        SHAMIR_CASE_(4);
+        SHAMIR_CASE_(5);
+        SHAMIR_CASE_(6);
+        SHAMIR_CASE_(7);
+#undef SHAMIR_CASE_
+        default: k_shamir_share<0, Src><<<grid, 256, 0, st>>>(src, out, n, degree, num_parties); break;
+    }
+    HIP_TRY(hipGetLastError());
+}
+
+// ------------------------------------------------------------------ combine: out[i] = sum_j lambda_j s_j[i]
+// (shamir.rs:314-322 `reconstruct` per element).  lambda travels in the kernel arguments (uniform across the wave); the
+// products go into one wide accumulator and are reduced once per element (poly.hip.hpp FrWide, as k_poly_eval_chi and
+// k_poly_lincomb do).  k_poly_lincomb itself takes device-side pointer and coefficient tables over polynomial handles,
+// so it is not reused here.
+struct ShamirCombineArgs {
+    const fe* s[COZK_SHAMIR_MAX_PARTIES];
+    fe lambda[COZK_SHAMIR_MAX_PARTIES];
+};
+__global__ void __launch_bounds__(256) k_shamir_combine(ShamirCombineArgs a, int k, fe* __restrict__ out, size_t n) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    FrWide w;
+    fr_wide_zero(w);
+    for (int j = 0; j < k; j++) fr_wide_mac(w, fe_load(a.s[j] + i), a.lambda[j]);
+    fe_store(out + i, fr_wide_reduce(w));
+}
+
+__global__ void __launch_bounds__(256) k_fe_add_scalar(fe* __restrict__ v, size_t n, fe s) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) fe_store(v + i, Fr::add(fe_load(v + i), s));
+}
+
+// ------------------------------------------------------------------ host
+static fe fe_from_abi(const uint64_t s[4]) {
+    fe r;
+    for (int i = 0; i < 4; i++) {
+        r.l[2 * i] = (uint32_t)s[i];
+        r.l[2 * i + 1] = (uint32_t)(s[i] >> 32);
+    }
+    return r;
+}
+static void fe_to_abi(const fe& a, uint64_t s[4]) {
+    for (int i = 0; i < 4; i++) s[i] = (uint64_t)a.l[2 * i] | ((uint64_t)a.l[2 * i + 1] << 32);
+}
+
+static void require_points(const uint32_t* points, size_t k, const char* who) {
+    const std::string w(who);
+    COZK_REQUIRE(points, w + ": null points");
+    COZK_REQUIRE(k >= 1 && k <= COZK_SHAMIR_MAX_PARTIES, w + ": 1 <= k <= COZK_SHAMIR_MAX_PARTIES points");
+    uint64_t seen = 0;
+    for (size_t i = 0; i < k; i++) {
+        COZK_REQUIRE(points[i] >= 1 && points[i] <= COZK_SHAMIR_MAX_PARTIES, w + ": points must lie in 1..COZK_SHAMIR_MAX_PARTIES");
+        COZK_REQUIRE(!((seen >> points[i]) & 1), w + ": points must be distinct");
+        seen |= (uint64_t)1 << points[i];
+    }
+}
+
+// lagrange_from_coeff (shamir.rs:273-291): lambda_i = prod_{j != i} x_j / (x_j - x_i), Montgomery form
+static void lagrange_host(const uint32_t* points, size_t k, fe* out) {
+    for (size_t i = 0; i < k; i++) {
+        fe num = Fr::one(), den = Fr::one();
+        const fe xi = Fr::from_u64(points[i]);
+        for (size_t j = 0; j < k; j++) {
+            if (j == i) continue;
+            const fe xj = Fr::from_u64(points[j]);
+            num = Fr::mul(num, xj);
+            den = Fr::mul(den, Fr::sub(xj, xi));
+        }
+        out[i] = Fr::mul(num, Fr::inv(den));
+    }
+}
+
+static void require_share_args(const char* who, int degree, int num_parties) {
+    const std::string w(who);
+    COZK_REQUIRE(degree >= 1 && degree <= COZK_SHAMIR_MAX_DEGREE, w + ": 1 <= degree <= COZK_SHAMIR_MAX_DEGREE");
+    COZK_REQUIRE(num_parties > degree && num_parties <= COZK_SHAMIR_MAX_PARTIES, w + ": degree < num_parties <= COZK_SHAMIR_MAX_PARTIES");
+}
+
+static void free_all(cozk_vec** out, int n) {
+    for (int p = 0; p < n; p++) {
+        cozk_vec_free(out[p]);
+        out[p] = nullptr;
+    }
+}
+
+// the num_parties outputs, from ctxs[p]'s allocator (or from `one`'s for all of them); on failure none is left
+static int alloc_outputs(cozk_ctx* one, cozk_ctx* const* ctxs, size_t n, int num_parties, cozk_vec** out) {
+    for (int p = 0; p < num_parties; p++) {
+        int rc = cozk_vec_alloc(ctxs ? ctxs[p] : one, n, COZK_SCALAR_FR, &out[p]);
+        if (rc != COZK_OK) {
+            out[p] = nullptr;
+            free_all(out, num_parties);
+            return rc;
+        }
+    }
+    return COZK_OK;
+}
+
+static void clear_outputs(cozk_vec** out, int num_parties) {
+    if (num_parties >= 1 && num_parties <= COZK_SHAMIR_MAX_PARTIES)
+        for (int p = 0; p < num_parties; p++) out[p] = nullptr;
+}
+
+static ShamirPrfSrc prf_src(const cozk_vec* v, const uint8_t* keys, int degree, uint64_t counter) {
+    ShamirPrfSrc src;
+    memset(&src, 0, sizeof src);
+    src.v = (const fe*)v->d;
+    src.counter = counter;
+    for (int c = 0; c < degree; c++) src.keys[c] = prf_key_from_bytes(keys + (size_t)COZK_PRF_KEY_BYTES * c);
+    return src;
+}
+
+// a null output pointer is reported through cozk_last_error like every other bad argument
+static int require_out(cozk_ctx* ctx, const void* out, const char* msg) {
+    return cozk_guard(ctx, [&] { COZK_REQUIRE(out, msg); });
+}
+
+static ShamirOut out_table(cozk_vec* const* out, int num_parties) {
+    ShamirOut o;
+    memset(&o, 0, sizeof o);
+    for (int p = 0; p < num_parties; p++) o.p[p] = (fe*)out[p]->d;
+    return o;
+}
+
+extern "C" {
+
+int cozk_shamir_share_vec(cozk_ctx* ctx, const cozk_vec* v, const uint8_t* keys, int degree, int num_parties, uint64_t counter,
+                          cozk_vec** out) {
+    if (int rc0 = require_out(ctx, out, "shamir_share_vec: null output")) return rc0;
+    clear_outputs(out, num_parties);
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && v && keys, "shamir_share_vec: null argument");
+        COZK_REQUIRE(v->kind == COZK_SCALAR_FR, "shamir_share_vec: the secret must be an FR vector");
+        require_share_args("shamir_share_vec", degree, num_parties);
+    });
+    if (rc != COZK_OK) return rc;
+    rc = alloc_outputs(ctx, nullptr, v->n, num_parties, out);
+    if (rc != COZK_OK) return rc;
+    rc = cozk_guard(ctx, [&] {
+        if (v->n == 0) return;
+        launch_share(ctx->stream, prf_src(v, keys, degree, counter), out_table(out, num_parties), v->n, degree, num_parties);
+    });
+    if (rc != COZK_OK) free_all(out, num_parties);
+    return rc;
+}
+
+int cozk_shamir_eval_vec(cozk_ctx* ctx, const cozk_vec* const* coeffs, int degree, int num_parties, cozk_vec** out) {
+    if (int rc0 = require_out(ctx, out, "shamir_eval_vec: null output")) return rc0;
+    clear_outputs(out, num_parties);
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && coeffs, "shamir_eval_vec: null argument");
+        require_share_args("shamir_eval_vec", degree, num_parties);
+        for (int c = 0; c <= degree; c++) {
+            COZK_REQUIRE(coeffs[c] && coeffs[c]->kind == COZK_SCALAR_FR, "shamir_eval_vec: degree + 1 FR coefficient vectors");
+            COZK_REQUIRE(coeffs[c]->n == coeffs[0]->n, "shamir_eval_vec: coefficient vectors must have equal length");
+        }
+    });
+    if (rc != COZK_OK) return rc;
+    const size_t n = coeffs[0]->n;
+    rc = alloc_outputs(ctx, nullptr, n, num_parties, out);
+    if (rc != COZK_OK) return rc;
+    rc = cozk_guard(ctx, [&] {
+        if (n == 0) return;
+        ShamirVecSrc src;
+        memset(&src, 0, sizeof src);
+        src.v = (const fe*)coeffs[0]->d;
+        for (int c = 1; c <= degree; c++) src.c[c - 1] = (const fe*)coeffs[c]->d;
+        launch_share(ctx->stream, src, out_table(out, num_parties), n, degree, num_parties);
+    });
+    if (rc != COZK_OK) free_all(out, num_parties);
+    return rc;
+}
+
+// cozk_rep3_scatter for Shamir: party p's vector is a block of party_ctxs[p]'s allocator, written by the dealer's stream --
+// in place when the devices match, staged on the dealer and moved with one peer copy per party when they differ
+int cozk_shamir_scatter(cozk_ctx* dealer, const cozk_vec* v, const uint8_t* keys, int degree, int num_parties, uint64_t counter,
+                        cozk_ctx* const* party_ctxs, cozk_vec** out) {
+    if (int rc0 = require_out(dealer, out, "shamir_scatter: null output")) return rc0;
+    clear_outputs(out, num_parties);
+    int rc = cozk_guard(dealer, [&] {
+        COZK_REQUIRE(dealer && v && keys && party_ctxs, "shamir_scatter: null argument");
+        COZK_REQUIRE(v->kind == COZK_SCALAR_FR, "shamir_scatter: the secret must be an FR vector");
+        require_share_args("shamir_scatter", degree, num_parties);
+        for (int p = 0; p < num_parties; p++) COZK_REQUIRE(party_ctxs[p], "shamir_scatter: null party context");
+    });
+    if (rc != COZK_OK) return rc;
+    rc = alloc_outputs(nullptr, party_ctxs, v->n, num_parties, out);
+    if (rc != COZK_OK) return rc;
+    rc = cozk_guard(dealer, [&] {
+        const size_t n = v->n;
+        if (n == 0) return;
+        // the outputs come from the PARTIES' pools, whose blocks are ordered by the owning party's stream only (common.hpp):
+        // a block a party has just freed may still be read by a kernel in flight there, so the dealer's stream must not
+        // write it before that stream has drained
+        size_t remote = 0;
+        for (int p = 0; p < num_parties; p++) {
+            HIP_TRY(hipStreamSynchronize(party_ctxs[p]->stream));
+            remote += party_ctxs[p]->device != dealer->device;
+        }
+        fe* stage = remote ? (fe*)ctx_dev_alloc(dealer, remote * n * sizeof(fe)) : nullptr;
+        ShamirOut o = out_table(out, num_parties);
+        size_t r = 0;
+        for (int p = 0; p < num_parties; p++)
+            if (party_ctxs[p]->device != dealer->device) o.p[p] = stage + n * r++;
+        launch_share(dealer->stream, prf_src(v, keys, degree, counter), o, n, degree, num_parties);
+        for (int p = 0; p < num_parties; p++)
+            if (party_ctxs[p]->device != dealer->device)
+                HIP_TRY(hipMemcpyPeerAsync(out[p]->d, party_ctxs[p]->device, o.p[p], dealer->device, n * sizeof(fe), dealer->stream));
+        HIP_TRY(hipStreamSynchronize(dealer->stream));  // the parties' streams may use the shares as soon as this returns
+        if (stage) ctx_dev_free(dealer, stage);
+    });
+    if (rc != COZK_OK) free_all(out, num_parties);
+    return rc;
+}
+
+int cozk_shamir_lagrange(const uint32_t* points, size_t k, uint64_t* out) {
+    return cozk_guard(nullptr, [&] {
+        COZK_REQUIRE(out, "shamir_lagrange: null output");
+        require_points(points, k, "shamir_lagrange");
+        fe l[COZK_SHAMIR_MAX_PARTIES];
+        lagrange_host(points, k, l);
+        for (size_t i = 0; i < k; i++) fe_to_abi(l[i], out + 4 * i);
+    });
+}
+
+int cozk_shamir_combine_vec(cozk_ctx* ctx, const cozk_vec* const* shares, const uint32_t* points, size_t k, int degree,
+                            cozk_vec** out) {
+    if (int rc0 = require_out(ctx, out, "shamir_combine_vec: null output")) return rc0;
+    *out = nullptr;
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && shares, "shamir_combine_vec: null argument");
+        require_points(points, k, "shamir_combine_vec");
+        COZK_REQUIRE(degree >= 0 && (size_t)degree < k, "shamir_combine_vec: 0 <= degree < k (degree + 1 shares are needed)");
+        for (size_t j = 0; j < k; j++) {
+            COZK_REQUIRE(shares[j] && shares[j]->kind == COZK_SCALAR_FR, "shamir_combine_vec: k FR share vectors");
+            COZK_REQUIRE(shares[j]->n == shares[0]->n, "shamir_combine_vec: share vectors must have equal length");
+        }
+    });
+    if (rc != COZK_OK) return rc;
+    const size_t n = shares[0]->n;
+    rc = cozk_vec_alloc(ctx, n, COZK_SCALAR_FR, out);
+    if (rc != COZK_OK) return rc;
+    rc = cozk_guard(ctx, [&] {
+        if (n == 0) return;
+        ShamirCombineArgs a;
+        memset(&a, 0, sizeof a);
+        lagrange_host(points, (size_t)degree + 1, a.lambda);  // of points[..=degree]: only those shares are used
+        for (int j = 0; j <= degree; j++) a.s[j] = (const fe*)shares[j]->d;
+        k_shamir_combine<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(a, degree + 1, (fe*)(*out)->d, n);
+        HIP_TRY(hipGetLastError());
+    });
+    if (rc != COZK_OK) {
+        cozk_vec_free(*out);
+        *out = nullptr;
+    }
+    return rc;
+}
+
+int cozk_shamir_combine_points(cozk_ctx* ctx, const uint64_t* xy, const int* infinity, const uint32_t* points, size_t k, int degree,
+                               uint64_t out_xy[8], int* out_infinity) {
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(xy && out_xy && out_infinity, "shamir_combine_points: null argument");
+        require_points(points, k, "shamir_combine_points");
+        COZK_REQUIRE(degree >= 0 && (size_t)degree < k, "shamir_combine_points: 0 <= degree < k (degree + 1 shares are needed)");
+    });
+    if (rc != COZK_OK) return rc;
+    fe l[COZK_SHAMIR_MAX_PARTIES];
+    lagrange_host(points, (size_t)degree + 1, l);
+    uint64_t scaled[COZK_SHAMIR_MAX_PARTIES * 8];
+    int scaled_inf[COZK_SHAMIR_MAX_PARTIES];
+    for (int j = 0; j <= degree; j++) {  // reconstruct_point (shamir.rs:432-440): sum_j lambda_j P_j
+        uint64_t s[4];
+        fe_to_abi(l[j], s);
+        rc = cozk_g1_mul(ctx, xy + 8 * j, infinity ? infinity[j] : 0, s, scaled + 8 * j, &scaled_inf[j]);
+        if (rc != COZK_OK) return rc;
+    }
+    return cozk_g1_sum(ctx, scaled, scaled_inf, (size_t)degree + 1, out_xy, out_infinity);
+}
+
+int cozk_vec_add_scalar(cozk_ctx* ctx, cozk_vec* v, const uint64_t s[4]) {
+    return cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && v && s && v->kind == COZK_SCALAR_FR, "vec_add_scalar: bad argument");
+        if (v->n == 0) return;
+        k_fe_add_scalar<<<(unsigned)((v->n + 255) / 256), 256, 0, ctx->stream>>>((fe*)v->d, v->n, fe_from_abi(s));
+        HIP_TRY(hipGetLastError());
+    });
+}
+
+}  // extern "C"

@@ -284,6 +284,34 @@ class Vec:
         self.ctx.check(self.ctx._l.cozk_vec_binop(self.ctx.h, op, 1 if base_field else 0, self.h, other.h, out.h))
         return out
 
+    def scale(self, s):
+        """v[i] *= s in place (cozk_vec_scale): share x public; s = r - 1 negates"""
+        sm = fr_to_mont_limbs([s])[0]
+        self.ctx.check(self.ctx._l.cozk_vec_scale(self.ctx.h, self.h, sm.ctypes.data))
+        return self
+
+    def add_scalar(self, s):
+        """v[i] += s in place (cozk_vec_add_scalar): share + public"""
+        sm = fr_to_mont_limbs([s])[0]
+        self.ctx.check(self.ctx._l.cozk_vec_add_scalar(self.ctx.h, self.h, sm.ctypes.data))
+        return self
+
+    # ---- Shamir sharing (mpc-types/src/protocols/shamir.rs): party p's share vector evaluates at x = p + 1
+    def shamir_share(self, keys, degree, num_parties, counter=0):
+        """the num_parties Shamir share vectors of this secret vector (cozk_shamir_share_vec); keys = `degree` 32-byte PRF
+        keys, coefficient c of element i is PRF(keys[c - 1], counter + i)"""
+        out = (ctypes.c_void_p * max(num_parties, 1))()
+        self.ctx.check(self.ctx._l.cozk_shamir_share_vec(self.ctx.h, self.h, _shamir_keys(keys), degree, num_parties, counter, out))
+        return [Vec(self.ctx, ctypes.c_void_p(out[p]), L.SCALAR_FR) for p in range(num_parties)]
+
+    def shamir_scatter(self, keys, degree, party_ctxs, counter=0):
+        """shamir_share whose vector p is owned by party_ctxs[p] (same or another GPU): cozk_shamir_scatter"""
+        n = len(party_ctxs)
+        out = (ctypes.c_void_p * max(n, 1))()
+        ctxs = (ctypes.c_void_p * max(n, 1))(*[c.h for c in party_ctxs])
+        self.ctx.check(self.ctx._l.cozk_shamir_scatter(self.ctx.h, self.h, _shamir_keys(keys), degree, n, counter, ctxs, out))
+        return [Vec(party_ctxs[p], ctypes.c_void_p(out[p]), L.SCALAR_FR) for p in range(n)]
+
     def free(self):
         if self.h:
             self.ctx._l.cozk_vec_free(self.h)
@@ -294,6 +322,59 @@ class Vec:
             self.free()
         except Exception:
             pass
+
+
+def _shamir_keys(keys):
+    return b"".join(L.prf_key(k) for k in keys)
+
+
+def _points(points):
+    return np.ascontiguousarray(np.asarray(list(points), dtype=np.uint32))
+
+
+def shamir_eval(ctx, coeffs, num_parties):
+    """evaluate_poly at x = 1..=num_parties with the caller's coefficient vectors, coeffs[0] = the secret vector
+    (cozk_shamir_eval_vec) -> num_parties share vectors"""
+    k = len(coeffs)
+    arr = (ctypes.c_void_p * max(k, 1))(*[v.h for v in coeffs])
+    out = (ctypes.c_void_p * max(num_parties, 1))()
+    ctx.check(ctx._l.cozk_shamir_eval_vec(ctx.h, arr, k - 1, num_parties, out))
+    return [Vec(ctx, ctypes.c_void_p(out[p]), L.SCALAR_FR) for p in range(num_parties)]
+
+
+def shamir_lagrange(points):
+    """lagrange_from_coeff (cozk_shamir_lagrange; host only, no context) -> canonical ints"""
+    pts = _points(points)
+    out = np.zeros((max(len(pts), 1), 4), dtype=np.uint64)
+    rc = L.lib().cozk_shamir_lagrange(pts.ctypes.data if len(pts) else None, len(pts), out.ctypes.data)
+    if rc != L.OK:
+        raise L.CozkError(rc, "shamir_lagrange: 1..32 distinct points in 1..32")
+    return mont_limbs_to_int(out[:len(pts)])
+
+
+def shamir_combine(shares, points, degree):
+    """combine_field_elements (cozk_shamir_combine_vec): opens the first degree + 1 of the share vectors at `points`"""
+    ctx = shares[0].ctx
+    pts = _points(points)
+    arr = (ctypes.c_void_p * len(shares))(*[v.h for v in shares])
+    h = ctypes.c_void_p()
+    ctx.check(ctx._l.cozk_shamir_combine_vec(ctx.h, arr, pts.ctypes.data, len(shares), degree, ctypes.byref(h)))
+    return Vec(ctx, h, L.SCALAR_FR)
+
+
+def shamir_combine_points(ctx, points_g1, points, degree):
+    """combine_curve_point (cozk_shamir_combine_points): opens the parties' commitments; points_g1 = affine points or None"""
+    k = len(points_g1)
+    xy = np.zeros((max(k, 1), 8), dtype=np.uint64)
+    inf = np.zeros(max(k, 1), dtype=np.int32)
+    for i, p in enumerate(points_g1):
+        xy[i], inf[i] = point_to_abi(p)
+    pts = _points(points)
+    out = np.zeros(8, dtype=np.uint64)
+    oi = ctypes.c_int()
+    ctx.check(ctx._l.cozk_shamir_combine_points(ctx.h, xy.ctypes.data, inf.ctypes.data, pts.ctypes.data, k, degree, out.ctypes.data,
+                                                ctypes.byref(oi)))
+    return point_from_abi(out, oi.value)
 
 
 class Bases:

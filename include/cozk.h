@@ -129,6 +129,48 @@ int cozk_vec_binop(cozk_ctx* ctx, int op, int base_field, const cozk_vec* a, con
                    cozk_vec* out);
 /* v[i] *= s (Fr) in place */
 int cozk_vec_scale(cozk_ctx* ctx, cozk_vec* v, const uint64_t s[4]);
+/* v[i] += s (Fr) in place: share + public of the Shamir share type (mpc-types/src/protocols/shamir/arithmetic/ops.rs:41-61) */
+int cozk_vec_add_scalar(cozk_ctx* ctx, cozk_vec* v, const uint64_t s[4]);
+
+/* ---------------------------------------------------------------- Shamir shares ----------- */
+/* A ShamirPrimeFieldShare is repr(transparent) over F (mpc-types/src/protocols/shamir/arithmetic/types.rs:10-30): party p's
+ * share of a vector is ONE FR cozk_vec, its evaluation point is x = p + 1.  The local operators of
+ * shamir/arithmetic/ops.rs need no entry points of their own: share +- share and share x share (element-wise; "result has
+ * higher degree than the inputs", ops.rs:93-118) are cozk_vec_binop, share x public is cozk_vec_scale, negation is
+ * cozk_vec_scale by -1, share + public is cozk_vec_add_scalar; a party's commitment of its share vector is cozk_msm_vec.
+ * There is no Shamir network, degree reduction or prover in the reference, and none here. */
+#define COZK_SHAMIR_MAX_PARTIES 32
+#define COZK_SHAMIR_MAX_DEGREE 15 /* of a dealt sharing: 2t + 1 <= 32 parties can still open a product */
+/* share_field_elements (mpc-types/src/protocols/shamir.rs:58-77; `share` :190-207): out[p][i] = f_i(p + 1) with
+ * f_i(x) = v[i] + sum_{c=1..degree} coef_c[i] x^c and coef_c[i] = PRF(keys[c-1], counter + i); keys = degree x 32 bytes,
+ * out = num_parties handles.  One kernel writes all parties' vectors.  1 <= degree <= COZK_SHAMIR_MAX_DEGREE and
+ * degree < num_parties <= COZK_SHAMIR_MAX_PARTIES; on any failure no output handle is left allocated: out[0..num_parties)
+ * is NULL, except that out[] is not touched at all when num_parties itself is out of range (its length is then unknown). */
+int cozk_shamir_share_vec(cozk_ctx* ctx, const cozk_vec* v, const uint8_t* keys, int degree, int num_parties,
+                          uint64_t counter, cozk_vec** out);
+/* the same evaluation with the caller's own coefficient vectors, coeffs[0] = the secret vector, coeffs[1..=degree] drawn
+ * from the host's CryptoRng: evaluate_poly at x = 1..=num_parties (shamir.rs:166-175; test_shamir_poly :521-552) */
+int cozk_shamir_eval_vec(cozk_ctx* ctx, const cozk_vec* const* coeffs, int degree, int num_parties, cozk_vec** out);
+/* cozk_shamir_share_vec whose output p is a vector of party_ctxs[p] (the same or another GPU), as cozk_rep3_scatter does
+ * for Rep3: every party's stream is drained before the dealer's stream writes, vectors on another device are generated
+ * in the dealer's memory and moved by one peer copy each; returns after the copies have completed */
+int cozk_shamir_scatter(cozk_ctx* dealer, const cozk_vec* v, const uint8_t* keys, int degree, int num_parties,
+                        uint64_t counter, cozk_ctx* const* party_ctxs, cozk_vec** out);
+/* lagrange_from_coeff (shamir.rs:273-291): out[i] = prod_{j != i} x_j / (x_j - x_i), k x 4 u64 Montgomery.  Pure host, no
+ * context.  1 <= k <= COZK_SHAMIR_MAX_PARTIES; points distinct and in 1..COZK_SHAMIR_MAX_PARTIES (the reference would
+ * panic on the inverse of zero). */
+int cozk_shamir_lagrange(const uint32_t* points, size_t k, uint64_t* out);
+/* combine_field_elements (shamir.rs:80-124): out[i] = sum_{j<=degree} lambda_j * shares[j][i], lambda =
+ * lagrange(points[..=degree]); as in the reference only the first degree + 1 of the k shares are used.
+ * 0 <= degree < k <= COZK_SHAMIR_MAX_PARTIES (a product of two degree-15 sharings opens with degree 30 from 31 shares);
+ * k FR vectors of equal length; points as for cozk_shamir_lagrange. */
+int cozk_shamir_combine_vec(cozk_ctx* ctx, const cozk_vec* const* shares, const uint32_t* points, size_t k, int degree,
+                            cozk_vec** out);
+/* combine_curve_point (shamir.rs:138-163; reconstruct_point :432-440) for the parties' commitments of their share
+ * vectors: out = sum_{j<=degree} lambda_j * P_j; xy = k x 8 u64, infinity = k ints or NULL.  Host arithmetic (the code
+ * behind cozk_g1_mul / cozk_g1_sum); ctx only receives the error message and may be NULL. */
+int cozk_shamir_combine_points(cozk_ctx* ctx, const uint64_t* xy, const int* infinity, const uint32_t* points, size_t k,
+                               int degree, uint64_t out_xy[8], int* out_infinity);
 
 /* ---------------------------------------------------------------- MSM seam ---------------- */
 /* Upload SRS points (`ck.powers_of_g[i]`, co-jolt/src/poly/commitment/pst13.rs:286-287,461-462) once;
