@@ -78,29 +78,13 @@ struct ProofBundle {
     Bytes serialize() const {
         Writer w;
         w.u64(commitments.size());
-        for (auto& c : commitments) {
-            w.u64(c.nv);
-            w.g1(c.g_product);
-        }
+        for (auto& c : commitments) c.write(w);
         w.u64(small_commitments.size());
-        for (auto& c : small_commitments) {
-            w.u64(c.nv);
-            w.g1(c.g_product);
-        }
-        w.vec_fr(gp.outputs);
-        w.u64(gp.gkr_layers.size());
-        for (auto& l : gp.gkr_layers) {
-            w.u64(l.proof.compressed_polys.size());
-            for (auto& p : l.proof.compressed_polys) w.vec_fr(p);
-            w.fr(l.left_claim);
-            w.fr(l.right_claim);
-        }
+        for (auto& c : small_commitments) c.write(w);
+        gp.write(w);
         w.u64(opening_claims.size());
         for (auto& c : opening_claims) w.vec_fr(c);
-        w.u64(reduced.sumcheck_proof.compressed_polys.size());
-        for (auto& p : reduced.sumcheck_proof.compressed_polys) w.vec_fr(p);
-        w.vec_fr(reduced.sumcheck_claims);
-        w.vec_g1(reduced.joint_opening_proof);
+        reduced.write(w);
         return w.b;
     }
 };
@@ -132,22 +116,45 @@ static VecH vec_binop(cozk_ctx* ctx, int op, const VecH& a, const VecH& b) {
     return h;
 }
 
-// share components of the synthetic secret vector stream(seed) through the engine's witness scatter
-// (cozk_rep3_share_vec: t0 = PRF(k0, i), t1 = PRF(k1, i), t2 = v - t0 - t1; P0 = (t0, t2), P1 = (t1, t0), P2 = (t2, t1);
-// arithmetic.rs:21-33) with the harness keys (seed, 101) and (seed, 102)
+static VecH upload_vec(cozk_ctx* ctx, const void* ptr, size_t n, int kind, const char* what) {
+    cozk_vec* v = nullptr;
+    rc_check(cozk_vec_upload(ctx, ptr, n, kind, &v), ctx, what);
+    return VecH(v);
+}
+static PolyH plain_poly(cozk_ctx* ctx, const VecH& v) {
+    cozk_poly* p = nullptr;
+    rc_check(cozk_poly_create(ctx, COZK_MODE_PLAIN, v.h, nullptr, &p), ctx, "poly_create");
+    return PolyH(p);
+}
+// this party's share components of the secret vector `v` through the engine's witness scatter (cozk_rep3_share_vec: t0 = PRF(k0, i),
+// t1 = PRF(k1, i), t2 = v - t0 - t1; P0 = (t0, t2), P1 = (t1, t0), P2 = (t2, t1); arithmetic.rs:21-33) with the harness keys
+// (seed, 101) and (seed, 102)
+static std::pair<VecH, VecH> share_plain_vec(cozk_ctx* ctx, const VecH& v, uint64_t seed, int party) {
+    uint8_t k0[COZK_PRF_KEY_BYTES], k1[COZK_PRF_KEY_BYTES];
+    harness_prf_key(seed, 101, k0);
+    harness_prf_key(seed, 102, k1);
+    cozk_vec *sa = nullptr, *sb = nullptr;
+    rc_check(cozk_rep3_share_vec(ctx, v.h, k0, k1, 0, party, &sa, &sb), ctx, "rep3_share_vec");
+    return std::make_pair(VecH(sa), VecH(sb));
+}
+// a secret column as this party holds it: the plain polynomial itself, or the REP3 polynomial over its shares under `seed`
+static PolyH make_shared_poly(cozk_ctx* ctx, int mode, const VecH& plain, uint64_t seed, int party) {
+    if (mode == COZK_MODE_PLAIN) return plain_poly(ctx, plain);
+    std::pair<VecH, VecH> sh = share_plain_vec(ctx, plain, seed, party);
+    cozk_poly* p = nullptr;
+    rc_check(cozk_poly_create(ctx, COZK_MODE_REP3, sh.first.h, sh.second.h, &p), ctx, "poly_create");
+    return PolyH(p);
+}
+// share components of the synthetic secret vector stream(seed)
 static void make_share_vectors(cozk_ctx* ctx, size_t n, uint64_t seed, int party, int mode, VecH& a, VecH& b, int max_bits = 0) {
     if (mode == COZK_MODE_PLAIN) {
         a = make_vec_random(ctx, n, COZK_SCALAR_FR, seed, max_bits);
         return;
     }
     VecH v = make_vec_random(ctx, n, COZK_SCALAR_FR, seed, max_bits);
-    uint8_t k0[COZK_PRF_KEY_BYTES], k1[COZK_PRF_KEY_BYTES];
-    harness_prf_key(seed, 101, k0);
-    harness_prf_key(seed, 102, k1);
-    cozk_vec *sa = nullptr, *sb = nullptr;
-    rc_check(cozk_rep3_share_vec(ctx, v.h, k0, k1, 0, party, &sa, &sb), ctx, "rep3_share_vec");
-    a = VecH(sa);
-    b = VecH(sb);
+    std::pair<VecH, VecH> sh = share_plain_vec(ctx, v, seed, party);
+    a = std::move(sh.first);
+    b = std::move(sh.second);
 }
 
 static void setup_party(cozk_harness* h, PartyState& ps) {
@@ -184,9 +191,7 @@ static void setup_party(cozk_harness* h, PartyState& ps) {
             else if (sp.kind == COZK_SCALAR_U16) k_small_to_fr_u16<<<grid, 256, 0, ctx->stream>>>((const uint16_t*)cozk_vec_device_ptr(sv.h), (fe*)cozk_vec_device_ptr(fr.h), N);
             else k_small_to_fr_u32<<<grid, 256, 0, ctx->stream>>>((const uint32_t*)cozk_vec_device_ptr(sv.h), (fe*)cozk_vec_device_ptr(fr.h), N);
             HIP_TRY(hipGetLastError());
-            cozk_poly* p = nullptr;
-            rc_check(cozk_poly_create(ctx, COZK_MODE_PLAIN, fr.h, nullptr, &p), ctx, "poly_create");
-            ps.polys.push_back(PolyH(p));
+            ps.polys.push_back(plain_poly(ctx, fr));
             ps.commit_vecs.push_back(std::move(sv));
             ps.is_public.push_back(1);
         }
@@ -434,15 +439,6 @@ static std::vector<PST13Commitment> combine_commitments_from_parties(std::vector
     return out;
 }
 
-static fe eq_eval(const std::vector<fe>& a, const std::vector<fe>& b) {
-    fe one = Fr::one(), acc = one;
-    for (size_t i = 0; i < a.size(); i++) {
-        fe ab = Fr::mul(a[i], b[i]);
-        acc = Fr::mul(acc, Fr::add(Fr::sub(Fr::sub(one, a[i]), b[i]), Fr::dbl(ab)));
-    }
-    return acc;
-}
-
 static int coordinator_main(cozk_harness* h, StarNetCoordinator& net, ProofBundle& proof, bool verify, std::string& why) {
     const cozk_harness_config& c = h->cfg;
     int np = h->nparties;
@@ -513,25 +509,25 @@ static int coordinator_main(cozk_harness* h, StarNetCoordinator& net, ProofBundl
         why = "final GKR claim != direct evaluation of the leaves";
         return 0;
     }
-    // openings: points as the workers chose them
-    struct VOpen { std::vector<fe> point; std::vector<g1_affine> cs; std::vector<fe> claims; fe rho; };
-    std::vector<VOpen> vo;
+    // openings: points as the workers chose them, polynomials as indices into commitments || small_commitments
+    std::vector<PST13Commitment> all_commitments = proof.commitments;
+    all_commitments.insert(all_commitments.end(), proof.small_commitments.begin(), proof.small_commitments.end());
+    std::vector<VerifierOpening> vo;
     {
-        std::vector<fe> p1(v_r.end() - nv, v_r.end()), p2(v_r.begin(), v_r.begin() + nv);
-        VOpen o1;
-        o1.point = p1;
-        for (size_t i = 0; i < half; i++) o1.cs.push_back(proof.commitments[i].g_product);
+        VerifierOpening o1;
+        o1.point.assign(v_r.end() - nv, v_r.end());
+        for (size_t i = 0; i < half; i++) o1.polys.push_back(i);
         vo.push_back(o1);
         if (half < K) {
-            VOpen o2;
-            o2.point = p2;
-            for (size_t i = half; i < K; i++) o2.cs.push_back(proof.commitments[i].g_product);
+            VerifierOpening o2;
+            o2.point.assign(v_r.begin(), v_r.begin() + nv);
+            for (size_t i = half; i < K; i++) o2.polys.push_back(i);
             vo.push_back(o2);
         }
         if (c.n_small > 0) {
-            VOpen o3;
+            VerifierOpening o3;
             o3.point.assign(v_r.end() - (nv - 4), v_r.end());
-            for (auto& cm : proof.small_commitments) o3.cs.push_back(cm.g_product);
+            for (size_t i = 0; i < proof.small_commitments.size(); i++) o3.polys.push_back(K + i);
             vo.push_back(o3);
         }
     }
@@ -539,71 +535,18 @@ static int coordinator_main(cozk_harness* h, StarNetCoordinator& net, ProofBundl
         why = "opening count mismatch";
         return 0;
     }
-    std::vector<fe> batched_claims;
-    std::vector<g1_affine> batched_commitments;
     for (size_t a = 0; a < vo.size(); a++) {
         vo[a].claims = proof.opening_claims[a];
-        if (vo[a].claims.size() != vo[a].cs.size()) {
+        if (vo[a].claims.size() != vo[a].polys.size()) {
             why = "claims / commitments mismatch";
             return 0;
         }
         vo[a].rho = vt.challenge_scalar();
-        std::vector<fe> pw(1, Fr::one());
-        for (size_t i = 1; i < vo[a].claims.size(); i++) pw.push_back(Fr::mul(pw[i - 1], vo[a].rho));
-        fe bc = Fr::zero();
-        for (size_t i = 0; i < pw.size(); i++) bc = Fr::add(bc, Fr::mul(pw[i], vo[a].claims[i]));
-        batched_claims.push_back(bc);
-        batched_commitments.push_back(PST13::combine_commitments(vo[a].cs, pw));
     }
-    // reduction sumcheck
-    fe rho2 = vt.challenge_scalar();
-    size_t max_nv = 0;
-    for (auto& o : vo) max_nv = std::max(max_nv, o.point.size());
-    std::vector<fe> coeffs(1, Fr::one());
-    for (size_t i = 1; i < vo.size(); i++) coeffs.push_back(Fr::mul(coeffs[i - 1], rho2));
-    fe e = Fr::zero();
-    for (size_t i = 0; i < vo.size(); i++)
-        e = Fr::add(e, Fr::mul(coeffs[i], Fr::mul(batched_claims[i], fr_from_u64((uint64_t)1 << (max_nv - vo[i].point.size())))));
-    std::vector<fe> rs;
-    if (proof.reduced.sumcheck_proof.compressed_polys.size() != max_nv) {
-        why = "reduction sumcheck: wrong number of rounds";
-        return 0;
-    }
-    for (auto& comp : proof.reduced.sumcheck_proof.compressed_polys) {
-        std::vector<fe> poly = unipoly_decompress(comp, e);
-        vt.append_scalars(comp);
-        fe r_j = vt.challenge_scalar();
-        rs.push_back(r_j);
-        e = unipoly_eval(poly, r_j);
-    }
-    fe expect = Fr::zero();
-    for (size_t i = 0; i < vo.size(); i++) {
-        std::vector<fe> slice(rs.end() - vo[i].point.size(), rs.end());
-        expect = Fr::add(expect, Fr::mul(coeffs[i], Fr::mul(eq_eval(vo[i].point, slice), proof.reduced.sumcheck_claims[i])));
-    }
-    if (!Fr::eq(expect, e)) {
-        why = "reduction sumcheck: final check failed";
-        return 0;
-    }
-    vt.append_scalars(proof.reduced.sumcheck_claims);
-    fe vgamma = vt.challenge_scalar();
-    // joint commitment / claim
-    std::vector<fe> gp_pw(1, Fr::one());
-    for (size_t i = 1; i < vo.size(); i++) gp_pw.push_back(Fr::mul(gp_pw[i - 1], vgamma));
-    g1_affine joint_c = PST13::combine_commitments(batched_commitments, gp_pw);
-    fe joint_claim = Fr::zero();
-    fe one = Fr::one();
-    for (size_t i = 0; i < vo.size(); i++) {
-        fe sc = one;
-        for (size_t j = 0; j + vo[i].point.size() < max_nv; j++) sc = Fr::mul(sc, Fr::sub(one, rs[j]));
-        joint_claim = Fr::add(joint_claim, Fr::mul(gp_pw[i], Fr::mul(sc, proof.reduced.sumcheck_claims[i])));
-    }
-    std::vector<fe> rev(rs.rbegin(), rs.rend());
     const PST13Setup& vsetup = *h->parties[h->local_party >= 0 ? h->local_worker * h->nparties + h->local_party : 0].setup;  // same SRS everywhere
-    if (!PST13::check_with_trapdoor(vsetup, joint_c, rev, joint_claim, proof.reduced.joint_opening_proof)) {
-        why = "PST13 opening check failed";
+    if (!verify_reduced_opening(vo, all_commitments, vt, proof.reduced, vsetup, "reduction sumcheck: wrong number of rounds",
+                                "reduction sumcheck: final check failed", why))
         return 0;
-    }
     (void)tr_open_start;
     (void)rho_red;
     (void)gamma;
@@ -691,8 +634,7 @@ int cozk_harness_create(const cozk_harness_config* cfg, cozk_harness** out) {
         COZK_REQUIRE(cfg->mode == COZK_MODE_PLAIN || cfg->mode == COZK_MODE_REP3, "harness: bad mode");
         COZK_REQUIRE(cfg->log_n >= 2 && cfg->log_n <= 24, "harness: log_n out of range");
         COZK_REQUIRE(cfg->gp_batch >= 1 && cfg->gp_log_leaves >= 1, "harness: bad grand-product shape");
-        int gbits = 0;
-        while ((1 << gbits) < cfg->gp_batch) gbits++;
+        const int gbits = ceil_log2((size_t)cfg->gp_batch);
         COZK_REQUIRE(gbits + cfg->gp_log_leaves >= cfg->log_n, "harness: grand-product point shorter than the opening point");
         COZK_REQUIRE(cfg->n_fr + cfg->n_u16 + cfg->n_u32 + cfg->n_flags >= 1, "harness: no polynomials");
         if (cfg->leaf_fingerprints)
@@ -778,8 +720,7 @@ int cozk_harness_create_participant(const cozk_harness_config* cfg, int local_pa
         if (cfg->leaf_fingerprints)
             COZK_REQUIRE(cfg->gp_log_leaves == cfg->log_n + 1 && cfg->n_fr >= 1 && cfg->log_workers == 0,
                          "harness: leaf_fingerprints needs gp_log_leaves == log_n + 1, n_fr >= 1, log_workers == 0");
-        int gbits = 0;
-        while ((1 << gbits) < cfg->gp_batch) gbits++;
+        const int gbits = ceil_log2((size_t)cfg->gp_batch);
         COZK_REQUIRE(gbits + cfg->gp_log_leaves >= cfg->log_n, "harness: grand-product point shorter than the opening point");
         if (W > 1) COZK_REQUIRE((cfg->gp_batch & (cfg->gp_batch - 1)) == 0, "split: gp_batch must be a power of two");
         h->nparties = np;

@@ -84,16 +84,8 @@ struct MemCheckProof {
     void write(Writer& w) const {
         w.vec_fr(rw_hashes);
         w.vec_fr(if_hashes);
-        for (const GrandProductProof* g : {&rw, &init_final}) {
-            w.vec_fr(g->outputs);
-            w.u64(g->gkr_layers.size());
-            for (auto& l : g->gkr_layers) {
-                w.u64(l.proof.compressed_polys.size());
-                for (auto& p : l.proof.compressed_polys) w.vec_fr(p);
-                w.fr(l.left_claim);
-                w.fr(l.right_claim);
-            }
-        }
+        rw.write(w);
+        init_final.write(w);
         w.vec_fr(rw_claims);
         w.vec_fr(if_claims);
     }
@@ -111,25 +103,16 @@ struct FlowProof {
     Bytes serialize() const {
         Writer w;
         w.u64(commitments.size());
-        for (auto& c : commitments) {
-            w.u64(c.nv);
-            w.g1(c.g_product);
-        }
+        for (auto& c : commitments) c.write(w);
         bytecode.write(w);
-        w.u64(primary.compressed_polys.size());
-        for (auto& p : primary.compressed_polys) w.vec_fr(p);
-        w.vec_fr(primary.openings);
+        primary.write(w);
         w.vec_fr(primary_claims);
         lookups.write(w);
         rw.write(w);
-        w.u64(outputs.compressed_polys.size());
-        for (auto& p : outputs.compressed_polys) w.vec_fr(p);
+        outputs.write(w);
         w.vec_fr(outputs_claims);
         spartan.write(w);
-        w.u64(reduced.sumcheck_proof.compressed_polys.size());
-        for (auto& p : reduced.sumcheck_proof.compressed_polys) w.vec_fr(p);
-        w.vec_fr(reduced.sumcheck_claims);
-        w.vec_g1(reduced.joint_opening_proof);
+        reduced.write(w);
         return w.b;
     }
 };
@@ -139,11 +122,6 @@ inline bool flow_vec_eq(const std::vector<fe>& a, const std::vector<fe>& b) {
     for (size_t i = 0; i < a.size(); i++)
         if (!Fr::eq(a[i], b[i])) return false;
     return true;
-}
-inline int flow_log2(size_t n) {
-    int k = 0;
-    while (((size_t)1 << k) < n) k++;
-    return k;
 }
 
 // ------------------------------------------------------------------------------------------------ the dealer's view
@@ -258,9 +236,7 @@ template <typename T>
 VecH flow_upload_ints(cozk_ctx* ctx, const std::vector<uint64_t>& v, int kind) {
     std::vector<T> t(v.size());
     for (size_t i = 0; i < v.size(); i++) t[i] = (T)v[i];
-    cozk_vec* d = nullptr;
-    rc_check(cozk_vec_upload(ctx, t.data(), t.size(), kind, &d), ctx, "vec_upload(compact column)");
-    return VecH(d);
+    return upload_vec(ctx, t.data(), t.size(), kind, "vec_upload(compact column)");
 }
 VecH flow_upload_compact(cozk_ctx* ctx, const std::vector<uint64_t>& v, int bytes) {
     if (bytes == 1) return flow_upload_ints<uint8_t>(ctx, v, COZK_SCALAR_U8);
@@ -294,13 +270,9 @@ void flow_setup_party(cozk_flow* h, FlowParty& ps) {
             continue;
         }
         const std::vector<fe>& col = h->clear[(size_t)idx];
-        cozk_vec* pv = nullptr;
-        rc_check(cozk_vec_upload(ctx, col.data(), col.size(), COZK_SCALAR_FR, &pv), ctx, "vec_upload(column)");
-        VecH plain(pv);
-        cozk_poly* p = nullptr;
+        VecH plain = upload_vec(ctx, col.data(), col.size(), COZK_SCALAR_FR, "vec_upload(column)");
         if (h->is_public[(size_t)idx]) {
-            rc_check(cozk_poly_create(ctx, COZK_MODE_PLAIN, plain.h, nullptr, &p), ctx, "poly_create");
-            ps.polys.push_back(PolyH(p));
+            ps.polys.push_back(plain_poly(ctx, plain));
             std::vector<uint64_t> ints(col.size());
             for (size_t i = 0; i < col.size(); i++) {
                 fe v = Fr::from_mont(col[i]);
@@ -309,19 +281,8 @@ void flow_setup_party(cozk_flow* h, FlowParty& ps) {
             ps.commit_vecs.push_back(flow_upload_compact(ctx, ints, h->pub_bytes[(size_t)idx]));
             ps.msm_vecs.emplace_back();
         } else {
-            if (c.mode == COZK_MODE_PLAIN) {
-                rc_check(cozk_poly_create(ctx, COZK_MODE_PLAIN, plain.h, nullptr, &p), ctx, "poly_create");
-            } else {
-                uint8_t k0[COZK_PRF_KEY_BYTES], k1[COZK_PRF_KEY_BYTES];
-                const uint64_t s = flow_share_seed(h, idx);
-                harness_prf_key(s, 101, k0);
-                harness_prf_key(s, 102, k1);
-                cozk_vec *sa = nullptr, *sb = nullptr;
-                rc_check(cozk_rep3_share_vec(ctx, plain.h, k0, k1, 0, ps.party, &sa, &sb), ctx, "rep3_share_vec");
-                VecH a(sa), b(sb);
-                rc_check(cozk_poly_create(ctx, COZK_MODE_REP3, a.h, b.h, &p), ctx, "poly_create");
-            }
-            ps.polys.push_back(PolyH(p));
+            ps.polys.push_back(make_shared_poly(ctx, c.mode, plain, flow_share_seed(h, idx), ps.party));
+            cozk_poly* p = ps.polys.back().h;
             cozk_vec* view = nullptr;
             rc_check(cozk_poly_share_view(ctx, p, 0, &view), ctx, "share_view");
             ps.commit_vecs.push_back(VecH(view));
@@ -360,11 +321,8 @@ void flow_setup_party(cozk_flow* h, FlowParty& ps) {
         }
         ps.mem_flags.push_back(flow_upload_compact(ctx, col, 1));
     }
-    cozk_vec* v = nullptr;
-    rc_check(cozk_vec_upload(ctx, h->io_range_clear.data(), h->MEM, COZK_SCALAR_FR, &v), ctx, "vec_upload");
-    ps.io_range = VecH(v);
-    rc_check(cozk_vec_upload(ctx, h->v_io_clear.data(), h->MEM, COZK_SCALAR_FR, &v), ctx, "vec_upload");
-    ps.v_io = VecH(v);
+    ps.io_range = upload_vec(ctx, h->io_range_clear.data(), h->MEM, COZK_SCALAR_FR, "vec_upload");
+    ps.v_io = upload_vec(ctx, h->v_io_clear.data(), h->MEM, COZK_SCALAR_FR, "vec_upload");
     HIP_TRY(hipStreamSynchronize(ctx->stream));
 }
 
@@ -450,8 +408,8 @@ void flow_memory_checking(WorkerEnv& env, LayerH rw_leaves, size_t rw_batch, Tog
     }
     std::vector<fe> r_rw = tgp.toggle_layer.h ? tgp.prove_grand_product_worker(env) : rw.prove_grand_product_worker(env);
     std::vector<fe> r_if = inf.prove_grand_product_worker(env);
-    r_rw_open.assign(r_rw.begin() + flow_log2(rw_batch), r_rw.end());
-    r_if_open.assign(r_if.begin() + flow_log2(if_batch), r_if.end());
+    r_rw_open.assign(r_rw.begin() + ceil_log2(rw_batch), r_rw.end());
+    r_if_open.assign(r_if.begin() + ceil_log2(if_batch), r_if.end());
 }
 
 void flow_worker_main(cozk_flow* h, FlowParty& ps, StarNetWorker* star, RingNet* ring) {
@@ -727,7 +685,7 @@ void flow_coordinate(cozk_flow* h, StarNetCoordinator& net, FlowProof& proof) {
         Writer w;
         w.vec_fr(r_eq);
         net.broadcast_request(w.b);
-        (void)coordinate_prove_arbitrary(net, tr, c.log_mem, proof.outputs);
+        (void)coordinate_prove_arbitrary(net, tr, c.log_mem, proof.outputs.compressed_polys);
         proof.outputs_claims = Rep3ProverOpeningAccumulator::receive_claims(net, tr);
     }
     proof.spartan = coordinate_spartan(net, tr, h->sys, h->N);
@@ -737,12 +695,6 @@ void flow_coordinate(cozk_flow* h, StarNetCoordinator& net, FlowProof& proof) {
 }
 
 // ------------------------------------------------------------------------------------------------ plain verifier
-struct FlowVOpen {
-    std::vector<int> polys;  // indices into the commitments
-    std::vector<fe> point, claims;
-    fe rho;
-};
-
 fe flow_mle_host(const std::vector<fe>& vals, const std::vector<fe>& r) {
     std::vector<fe> eq = eq_evals_host(r);
     fe acc = Fr::zero();
@@ -774,11 +726,11 @@ bool flow_verify(cozk_flow* h, const FlowProof& proof, std::string& why) {
         return false;
     }
     for (auto& cm : proof.commitments) vt.append_point(cm.g_product);
-    std::vector<FlowVOpen> opens;
+    std::vector<VerifierOpening> opens;
     // one claim exchange (receive_claims): the batching challenge is drawn right after it (rho given: already drawn)
     auto take_claims = [&](const std::vector<int>& polys, const std::vector<fe>& point, const std::vector<fe>& claims, const fe* rho = nullptr) {
-        FlowVOpen o;
-        o.polys = polys;
+        VerifierOpening o;
+        o.polys.assign(polys.begin(), polys.end());
         o.point = point;
         o.claims = claims;
         o.rho = rho ? *rho : vt.challenge_scalar();
@@ -807,7 +759,7 @@ bool flow_verify(cozk_flow* h, const FlowProof& proof, std::string& why) {
         return verify_grand_product(mp.init_final, vt, if_claim, r_if);
     };
     auto split = [&](const std::vector<fe>& r, size_t batch, std::vector<fe>& hi, std::vector<fe>& lo) {
-        int k = flow_log2(batch);
+        int k = ceil_log2(batch);
         hi.assign(r.begin(), r.begin() + k);
         lo.assign(r.begin() + k, r.end());
     };
@@ -961,12 +913,11 @@ bool flow_verify(cozk_flow* h, const FlowProof& proof, std::string& why) {
         }
         std::vector<fe> r_eq = vt.challenge_vector((size_t)c.log_mem), r_out;
         fe claim = Fr::zero();
-        if (!spartan_verify_rounds(proof.outputs, (size_t)c.log_mem, 3, claim, vt, r_out) || proof.outputs_claims.size() != 1) {
+        if (!verify_sumcheck_rounds(proof.outputs.compressed_polys, (size_t)c.log_mem, 3, claim, vt, r_out) || proof.outputs_claims.size() != 1) {
             why = "output check: shape";
             return false;
         }
-        fe e = one;
-        for (size_t i = 0; i < r_eq.size(); i++) e = Fr::mul(e, Fr::add(Fr::sub(Fr::sub(one, r_eq[i]), r_out[i]), Fr::dbl(Fr::mul(r_eq[i], r_out[i]))));
+        fe e = eq_eval(r_eq, r_out);
         fe want = Fr::mul(Fr::mul(e, flow_mle_host(h->io_range_clear, r_out)), Fr::sub(proof.outputs_claims[0], flow_mle_host(h->v_io_clear, r_out)));
         if (!Fr::eq(want, claim)) {
             why = "output check: final claim";
@@ -986,71 +937,8 @@ bool flow_verify(cozk_flow* h, const FlowProof& proof, std::string& why) {
     }
     // ---- 6. the batched opening (opening_proof.rs:181-235 + the verifier's reduce_and_verify, out of tree): reduction sumcheck over
     //      all openings, then ONE PST13 check of the joint polynomial (pairing-free, trapdoor known)
-    {
-        std::vector<fe> batched_claims;
-        std::vector<std::vector<fe>> pws;
-        for (auto& o : opens) {
-            std::vector<fe> pw(1, one);
-            for (size_t i = 1; i < o.claims.size(); i++) pw.push_back(Fr::mul(pw[i - 1], o.rho));
-            fe bc = Fr::zero();
-            for (size_t i = 0; i < pw.size(); i++) bc = Fr::add(bc, Fr::mul(pw[i], o.claims[i]));
-            batched_claims.push_back(bc);
-            pws.push_back(pw);
-        }
-        fe rho2 = vt.challenge_scalar();
-        size_t max_nv = 0;
-        for (auto& o : opens) max_nv = std::max(max_nv, o.point.size());
-        std::vector<fe> coeffs(1, one);
-        for (size_t i = 1; i < opens.size(); i++) coeffs.push_back(Fr::mul(coeffs[i - 1], rho2));
-        fe e = Fr::zero();
-        for (size_t i = 0; i < opens.size(); i++)
-            e = Fr::add(e, Fr::mul(coeffs[i], Fr::mul(batched_claims[i], fr_from_u64((uint64_t)1 << (max_nv - opens[i].point.size())))));
-        std::vector<fe> rs;
-        if (!spartan_verify_rounds(proof.reduced.sumcheck_proof, max_nv, 2, e, vt, rs) || proof.reduced.sumcheck_claims.size() != opens.size()) {
-            why = "opening reduction: shape";
-            return false;
-        }
-        fe expect = Fr::zero();
-        for (size_t i = 0; i < opens.size(); i++) {
-            std::vector<fe> slice(rs.end() - (long)opens[i].point.size(), rs.end());
-            fe eqv = one;
-            for (size_t j = 0; j < slice.size(); j++)
-                eqv = Fr::mul(eqv, Fr::add(Fr::sub(Fr::sub(one, opens[i].point[j]), slice[j]), Fr::dbl(Fr::mul(opens[i].point[j], slice[j]))));
-            expect = Fr::add(expect, Fr::mul(coeffs[i], Fr::mul(eqv, proof.reduced.sumcheck_claims[i])));
-        }
-        if (!Fr::eq(expect, e)) {
-            why = "opening reduction: final check";
-            return false;
-        }
-        vt.append_scalars(proof.reduced.sumcheck_claims);
-        fe vgamma = vt.challenge_scalar();
-        // joint commitment = sum_i gamma^i sum_k rho_i^k C_(i,k): one scalar per commitment
-        std::vector<fe> scal((size_t)ix.count, Fr::zero());
-        fe gp = one, joint_claim = Fr::zero();
-        for (size_t i = 0; i < opens.size(); i++) {
-            for (size_t k = 0; k < opens[i].polys.size(); k++) {
-                fe& sc = scal[(size_t)opens[i].polys[k]];
-                sc = Fr::add(sc, Fr::mul(gp, pws[i][k]));
-            }
-            fe sc = one;
-            for (size_t j = 0; j + opens[i].point.size() < max_nv; j++) sc = Fr::mul(sc, Fr::sub(one, rs[j]));
-            joint_claim = Fr::add(joint_claim, Fr::mul(gp, Fr::mul(sc, proof.reduced.sumcheck_claims[i])));
-            gp = Fr::mul(gp, vgamma);
-        }
-        std::vector<g1_affine> cs;
-        std::vector<fe> ss;
-        for (int i = 0; i < ix.count; i++)
-            if (!Fr::is_zero(scal[(size_t)i])) {
-                cs.push_back(proof.commitments[(size_t)i].g_product);
-                ss.push_back(scal[(size_t)i]);
-            }
-        g1_affine joint_c = PST13::combine_commitments(cs, ss);
-        std::vector<fe> rev(rs.rbegin(), rs.rend());
-        if (!PST13::check_with_trapdoor(*h->parties[0].setup, joint_c, rev, joint_claim, proof.reduced.joint_opening_proof)) {
-            why = "PST13 opening check failed";
-            return false;
-        }
-    }
+    if (!verify_reduced_opening(opens, proof.commitments, vt, proof.reduced, *h->parties[0].setup, "opening reduction: shape", "opening reduction: final check", why))
+        return false;
     (void)M;
     return true;
 }

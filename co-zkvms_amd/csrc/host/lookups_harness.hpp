@@ -132,9 +132,7 @@ void lookups_setup_primary_party(cozk_lookups* h, LookupsParty& ps) {
     for (size_t i = 0; i < h->instrs.size(); i++) {
         std::vector<uint8_t> col(h->N);
         for (size_t x = 0; x < h->N; x++) col[x] = h->which[x] == i ? 1 : 0;
-        cozk_vec* v = nullptr;
-        rc_check(cozk_vec_upload(ctx, col.data(), h->N, COZK_SCALAR_U8, &v), ctx, "vec_upload(instruction flags)");
-        ps.instr_flags.push_back(VecH(v));
+        ps.instr_flags.push_back(upload_vec(ctx, col.data(), h->N, COZK_SCALAR_U8, "vec_upload(instruction flags)"));
     }
     for (int m = 0; m < c.n_pairs; m++) {
         VecH a, b;
@@ -143,45 +141,20 @@ void lookups_setup_primary_party(cozk_lookups* h, LookupsParty& ps) {
         rc_check(cozk_poly_create(ctx, c.mode, a.h, b.h, &p), ctx, "poly_create(E)");
         ps.E.push_back(PolyH(p));
     }
-    cozk_vec* ov = nullptr;
-    rc_check(cozk_vec_upload(ctx, h->outputs_plain.data(), h->N, COZK_SCALAR_FR, &ov), ctx, "vec_upload(outputs)");
-    VecH ovh(ov);
-    cozk_poly* op = nullptr;
-    if (c.mode == COZK_MODE_REP3) {
-        uint8_t k0[COZK_PRF_KEY_BYTES], k1[COZK_PRF_KEY_BYTES];
-        harness_prf_key(c.seed + 555ull, 101, k0);
-        harness_prf_key(c.seed + 555ull, 102, k1);
-        cozk_vec *sa = nullptr, *sb = nullptr;
-        rc_check(cozk_rep3_share_vec(ctx, ovh.h, k0, k1, 0, ps.party, &sa, &sb), ctx, "rep3_share_vec(outputs)");
-        VecH a(sa), b(sb);
-        rc_check(cozk_poly_create(ctx, COZK_MODE_REP3, a.h, b.h, &op), ctx, "poly_create(outputs)");
-    } else {
-        rc_check(cozk_poly_create(ctx, COZK_MODE_PLAIN, ovh.h, nullptr, &op), ctx, "poly_create(outputs)");
-    }
-    ps.outputs = PolyH(op);
+    VecH ovh = upload_vec(ctx, h->outputs_plain.data(), h->N, COZK_SCALAR_FR, "vec_upload(outputs)");
+    ps.outputs = make_shared_poly(ctx, c.mode, ovh, c.seed + 555ull, ps.party);
 }
 
 void lookups_setup_primary_verifier(cozk_lookups* h) {
     const cozk_lookups_config& c = h->cfg;
     cozk_ctx* ctx = h->vctx;
-    auto plain_poly = [&](const VecH& v) {
-        cozk_poly* p = nullptr;
-        rc_check(cozk_poly_create(ctx, COZK_MODE_PLAIN, v.h, nullptr, &p), ctx, "poly_create");
-        return PolyH(p);
-    };
-    for (int m = 0; m < c.n_pairs; m++) h->v_E.push_back(plain_poly(make_vec_random(ctx, h->N, COZK_SCALAR_FR, c.seed + 9000ull * (uint64_t)(m + 1), 0)));
+    for (int m = 0; m < c.n_pairs; m++) h->v_E.push_back(plain_poly(ctx, make_vec_random(ctx, h->N, COZK_SCALAR_FR, c.seed + 9000ull * (uint64_t)(m + 1), 0)));
     for (size_t i = 0; i < h->instrs.size(); i++) {
         std::vector<fe> f(h->N);
         for (size_t x = 0; x < h->N; x++) f[x] = h->which[x] == i ? Fr::one() : Fr::zero();
-        cozk_vec* v = nullptr;
-        rc_check(cozk_vec_upload(ctx, f.data(), h->N, COZK_SCALAR_FR, &v), ctx, "vec_upload");
-        VecH vh(v);
-        h->v_iflags.push_back(plain_poly(vh));
+        h->v_iflags.push_back(plain_poly(ctx, upload_vec(ctx, f.data(), h->N, COZK_SCALAR_FR, "vec_upload")));
     }
-    cozk_vec* ov = nullptr;
-    rc_check(cozk_vec_upload(ctx, h->outputs_plain.data(), h->N, COZK_SCALAR_FR, &ov), ctx, "vec_upload");
-    VecH ovh(ov);
-    h->v_outputs = plain_poly(ovh);
+    h->v_outputs = plain_poly(ctx, upload_vec(ctx, h->outputs_plain.data(), h->N, COZK_SCALAR_FR, "vec_upload"));
 }
 
 void lookups_setup_party(cozk_lookups* h, LookupsParty& ps) {
@@ -189,9 +162,7 @@ void lookups_setup_party(cozk_lookups* h, LookupsParty& ps) {
     cozk_ctx* ctx = ps.ctx;
     for (int q = 0; q < c.n_pairs; q++) {
         std::vector<uint8_t> col = lookups_flag_column(c, q, h->N);
-        cozk_vec* v = nullptr;
-        rc_check(cozk_vec_upload(ctx, col.data(), h->N, COZK_SCALAR_U8, &v), ctx, "vec_upload(flags)");
-        ps.flags.push_back(VecH(v));
+        ps.flags.push_back(upload_vec(ctx, col.data(), h->N, COZK_SCALAR_U8, "vec_upload(flags)"));
     }
     cozk_vec *fa = nullptr, *fb = nullptr;
     rc_check(cozk_vec_alloc(ctx, h->batch * h->N, COZK_SCALAR_FR, &fa), ctx, "vec_alloc");
@@ -218,18 +189,10 @@ void lookups_setup_verifier(cozk_lookups* h) {
         std::vector<uint8_t> col = lookups_flag_column(c, q, h->N);
         std::vector<fe> f(h->N);
         for (size_t i = 0; i < h->N; i++) f[i] = col[i] ? Fr::one() : Fr::zero();
-        cozk_vec* v = nullptr;
-        rc_check(cozk_vec_upload(ctx, f.data(), h->N, COZK_SCALAR_FR, &v), ctx, "vec_upload");
-        VecH vh(v);
-        cozk_poly* p = nullptr;
-        rc_check(cozk_poly_create(ctx, COZK_MODE_PLAIN, vh.h, nullptr, &p), ctx, "poly_create");
-        h->v_flags.push_back(PolyH(p));
+        h->v_flags.push_back(plain_poly(ctx, upload_vec(ctx, f.data(), h->N, COZK_SCALAR_FR, "vec_upload")));
     }
     for (size_t b = 0; b < h->batch; b++) {
-        VecH v = make_vec_random(ctx, h->N, COZK_SCALAR_FR, c.seed + 7000ull * (uint64_t)(b + 1), 0);
-        cozk_poly* p = nullptr;
-        rc_check(cozk_poly_create(ctx, COZK_MODE_PLAIN, v.h, nullptr, &p), ctx, "poly_create");
-        h->v_fps.push_back(PolyH(p));
+        h->v_fps.push_back(plain_poly(ctx, make_vec_random(ctx, h->N, COZK_SCALAR_FR, c.seed + 7000ull * (uint64_t)(b + 1), 0)));
     }
 }
 
@@ -239,19 +202,8 @@ struct LookupsProof {
     GrandProductProof gp;
     Bytes serialize() const {
         Writer w;
-        if (has_primary) {
-            w.u64(primary.compressed_polys.size());
-            for (auto& p : primary.compressed_polys) w.vec_fr(p);
-            w.vec_fr(primary.openings);
-        }
-        w.vec_fr(gp.outputs);
-        w.u64(gp.gkr_layers.size());
-        for (auto& l : gp.gkr_layers) {
-            w.u64(l.proof.compressed_polys.size());
-            for (auto& p : l.proof.compressed_polys) w.vec_fr(p);
-            w.fr(l.left_claim);
-            w.fr(l.right_claim);
-        }
+        if (has_primary) primary.write(w);
+        gp.write(w);
         return w.b;
     }
 };
@@ -444,8 +396,7 @@ void lookups_worker_main(cozk_lookups* h, LookupsParty& ps, StarNetWorker* star,
 fe lookups_eval_circuit_major(cozk_lookups* h, const std::vector<const cozk_poly*>& polys, const std::vector<fe>& r, bool pad_with_ones) {
     size_t L = 1;
     while (L < polys.size()) L <<= 1;
-    int hi = 0;
-    while (((size_t)1 << hi) < L) hi++;
+    const int hi = ceil_log2(L);
     COZK_REQUIRE(r.size() == (size_t)hi + (size_t)h->cfg.log_n, "lookups verifier: point length");
     std::vector<fe> r_hi(r.begin(), r.begin() + hi), r_lo(r.begin() + hi, r.end());
     std::vector<uint64_t> w = to_abi(r_lo);

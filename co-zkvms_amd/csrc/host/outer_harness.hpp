@@ -97,22 +97,9 @@ void outer_build_clear(cozk_outer_harness* h) {
 void outer_setup_party(cozk_outer_harness* h, OuterParty& ps) {
     cozk_ctx* ctx = ps.ctx;
     for (int v = 0; v < h->ncols; v++) {
-        cozk_vec* pv = nullptr;
-        rc_check(cozk_vec_upload(ctx, h->clear[v].data(), h->N, COZK_SCALAR_FR, &pv), ctx, "vec_upload(column)");
-        VecH plain(pv);
-        cozk_poly* p = nullptr;
-        if (h->is_public[v] || h->cfg.mode == COZK_MODE_PLAIN) {
-            rc_check(cozk_poly_create(ctx, COZK_MODE_PLAIN, plain.h, nullptr, &p), ctx, "poly_create");
-        } else {
-            uint8_t k0[COZK_PRF_KEY_BYTES], k1[COZK_PRF_KEY_BYTES];
-            harness_prf_key(h->cfg.seed + 100ull * (uint64_t)(v + 1), 101, k0);
-            harness_prf_key(h->cfg.seed + 100ull * (uint64_t)(v + 1), 102, k1);
-            cozk_vec *sa = nullptr, *sb = nullptr;
-            rc_check(cozk_rep3_share_vec(ctx, plain.h, k0, k1, 0, ps.party, &sa, &sb), ctx, "rep3_share_vec");
-            VecH a(sa), b(sb);
-            rc_check(cozk_poly_create(ctx, COZK_MODE_REP3, a.h, b.h, &p), ctx, "poly_create");
-        }
-        ps.cols.push_back(PolyH(p));
+        VecH plain = upload_vec(ctx, h->clear[v].data(), h->N, COZK_SCALAR_FR, "vec_upload(column)");
+        if (h->is_public[v]) ps.cols.push_back(plain_poly(ctx, plain));
+        else ps.cols.push_back(make_shared_poly(ctx, h->cfg.mode, plain, h->cfg.seed + 100ull * (uint64_t)(v + 1), ps.party));
     }
 }
 
@@ -126,9 +113,7 @@ struct OuterProofBundle {
             spartan.write(w);
             return w.b;
         }
-        w.u64(outer.compressed_polys.size());
-        for (auto& p : outer.compressed_polys) w.vec_fr(p);
-        w.vec_fr(outer.claims);
+        outer.write(w);
         return w.b;
     }
 };
@@ -224,12 +209,7 @@ void outer_setup_verifier(cozk_outer_harness* h) {
     if (rc != COZK_OK) throw CozkError(rc, "outer harness: cannot create the verifier's context");
     HIP_TRY(hipSetDevice(h->vctx->device));
     for (int v = 0; v < h->ncols; v++) {
-        cozk_vec* pv = nullptr;
-        rc_check(cozk_vec_upload(h->vctx, h->clear[v].data(), h->N, COZK_SCALAR_FR, &pv), h->vctx, "vec_upload(column)");
-        VecH plain(pv);
-        cozk_poly* p = nullptr;
-        rc_check(cozk_poly_create(h->vctx, COZK_MODE_PLAIN, plain.h, nullptr, &p), h->vctx, "poly_create");
-        h->v_cols.push_back(PolyH(p));
+        h->v_cols.push_back(plain_poly(h->vctx, upload_vec(h->vctx, h->clear[v].data(), h->N, COZK_SCALAR_FR, "vec_upload(column)")));
     }
 }
 
@@ -251,8 +231,7 @@ bool outer_check_openings(cozk_outer_harness* h, const std::vector<fe>& point, c
 }
 
 int outer_coordinator_main(cozk_outer_harness* h, StarNetCoordinator& net, OuterProofBundle& proof, bool verify, std::string& why) {
-    int constr_bits = 0;
-    while (((size_t)1 << constr_bits) < h->sys.padded) constr_bits++;
+    const int constr_bits = ceil_log2(h->sys.padded);
     if (h->cfg.full) {
         proof.full = true;
         Transcript tr("cozk-spartan");

@@ -23,64 +23,32 @@
 namespace cozk {
 
 // ---------------------------------------------------------------- RAII handles over the C ABI
-struct VecH {
-    cozk_vec* h = nullptr;
-    VecH() {}
-    explicit VecH(cozk_vec* v) : h(v) {}
-    VecH(const VecH&) = delete;
-    VecH& operator=(const VecH&) = delete;
-    VecH(VecH&& o) noexcept : h(o.h) { o.h = nullptr; }
-    VecH& operator=(VecH&& o) noexcept {
+// move-only owner of one C ABI handle
+template <class T, int (*Free)(T*)>
+struct Handle {
+    T* h = nullptr;
+    Handle() {}
+    explicit Handle(T* p) : h(p) {}
+    Handle(const Handle&) = delete;
+    Handle& operator=(const Handle&) = delete;
+    Handle(Handle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Handle& operator=(Handle&& o) noexcept {
         if (this != &o) {
-            cozk_vec_free(h);
+            Free(h);
             h = o.h;
             o.h = nullptr;
         }
         return *this;
     }
-    ~VecH() { cozk_vec_free(h); }
+    ~Handle() { Free(h); }
 };
-struct PolyH {
-    cozk_poly* h = nullptr;
-    PolyH() {}
-    explicit PolyH(cozk_poly* p) : h(p) {}
-    PolyH(const PolyH&) = delete;
-    PolyH& operator=(const PolyH&) = delete;
-    PolyH(PolyH&& o) noexcept : h(o.h) { o.h = nullptr; }
-    PolyH& operator=(PolyH&& o) noexcept {
-        if (this != &o) {
-            cozk_poly_free(h);
-            h = o.h;
-            o.h = nullptr;
-        }
-        return *this;
-    }
-    ~PolyH() { cozk_poly_free(h); }
-};
-struct LayerH {
-    cozk_layer* h = nullptr;
-    LayerH() {}
-    explicit LayerH(cozk_layer* p) : h(p) {}
-    LayerH(const LayerH&) = delete;
-    LayerH& operator=(const LayerH&) = delete;
-    LayerH(LayerH&& o) noexcept : h(o.h) { o.h = nullptr; }
-    LayerH& operator=(LayerH&& o) noexcept {
-        if (this != &o) {
-            cozk_layer_free(h);
-            h = o.h;
-            o.h = nullptr;
-        }
-        return *this;
-    }
-    ~LayerH() { cozk_layer_free(h); }
-};
-struct EqH {
-    cozk_spliteq* h = nullptr;
-    EqH() {}
-    EqH(const EqH&) = delete;
-    EqH& operator=(const EqH&) = delete;
-    ~EqH() { cozk_spliteq_free(h); }
-};
+typedef Handle<cozk_vec, cozk_vec_free> VecH;
+typedef Handle<cozk_poly, cozk_poly_free> PolyH;
+typedef Handle<cozk_layer, cozk_layer_free> LayerH;
+typedef Handle<cozk_spliteq, cozk_spliteq_free> EqH;
+typedef Handle<cozk_toggle, cozk_toggle_free> ToggleH;
+typedef Handle<cozk_primary, cozk_primary_free> PrimaryH;
+typedef Handle<cozk_outer, cozk_outer_free> OuterH;
 
 static inline std::vector<uint64_t> to_abi(const std::vector<fe>& v) {
     std::vector<uint64_t> o(4 * v.size());
@@ -210,28 +178,49 @@ static SumcheckResult prove_sumcheck(WorkerEnv& env, cozk_layer* layer, const fe
 
 struct SumcheckProof {
     std::vector<std::vector<fe>> compressed_polys;
+    void write(Writer& w) const {
+        w.u64(compressed_polys.size());
+        for (auto& p : compressed_polys) w.vec_fr(p);
+    }
 };
 
-// coordinate_prove_arbitrary (sumcheck.rs:134-165)
-static std::vector<fe> coordinate_prove_arbitrary(StarNetCoordinator& net, Transcript& tr, int num_rounds, SumcheckProof& proof) {
+// the parties' additive parts of one vector, summed: messages [first, first + count) of `msgs`, every party's response,
+// or the responses of participants 0 .. count-1
+static std::vector<fe> gather_additive(const std::vector<Bytes>& msgs, size_t first, size_t count) {
+    std::vector<std::vector<fe>> parts;
+    for (size_t i = first; i < first + count; i++) {
+        Reader rd(msgs[i]);
+        parts.push_back(rd.vec_fr());
+    }
+    return combine_additive(parts);
+}
+static std::vector<fe> gather_additive(StarNetCoordinator& net) {
+    std::vector<Bytes> msgs = net.receive_responses();
+    return gather_additive(msgs, 0, msgs.size());
+}
+static std::vector<fe> gather_additive(StarNetCoordinator& net, int count) {
+    std::vector<Bytes> msgs;
+    for (int id = 0; id < count; id++) msgs.push_back(net.receive_response(id));
+    return gather_additive(msgs, 0, msgs.size());
+}
+
+// coordinate_prove_arbitrary (sumcheck.rs:134-165).  The request is (r_j, claim); coordinate_eq_sumcheck_round
+// (sumcheck_spartan.rs:14-42) runs the same loop with the request written as (claim, r_j): `claim_first`.
+static std::vector<fe> coordinate_prove_arbitrary(StarNetCoordinator& net, Transcript& tr, int num_rounds, std::vector<std::vector<fe>>& compressed_polys,
+                                                  bool claim_first = false) {
     std::vector<fe> r;
     for (int round = 0; round < num_rounds; round++) {
-        std::vector<std::vector<fe>> parts;
-        for (Bytes& b : net.receive_responses()) {
-            Reader rd(b);
-            parts.push_back(rd.vec_fr());
-        }
-        std::vector<fe> poly = combine_additive(parts);
+        std::vector<fe> poly = gather_additive(net);
         std::vector<fe> comp = unipoly_compress(poly);
         tr.append_scalars(comp);
         fe r_j = tr.challenge_scalar();
         r.push_back(r_j);
         fe claim = unipoly_eval(poly, r_j);
         Writer w;
-        w.fr(r_j);
-        w.fr(claim);
+        w.fr(claim_first ? claim : r_j);
+        w.fr(claim_first ? r_j : claim);
         net.broadcast_request(w.b);
-        proof.compressed_polys.push_back(comp);
+        compressed_polys.push_back(comp);
     }
     return r;
 }
@@ -259,6 +248,15 @@ struct GrandProductLayerProof {
 struct GrandProductProof {
     std::vector<fe> outputs;
     std::vector<GrandProductLayerProof> gkr_layers;
+    void write(Writer& w) const {
+        w.vec_fr(outputs);
+        w.u64(gkr_layers.size());
+        for (auto& l : gkr_layers) {
+            l.proof.write(w);
+            w.fr(l.left_claim);
+            w.fr(l.right_claim);
+        }
+    }
 };
 
 struct Rep3BatchedDenseGrandProduct {
@@ -270,8 +268,7 @@ struct Rep3BatchedDenseGrandProduct {
         COZK_REQUIRE(batch_size > 0 && n % batch_size == 0, "grand product: leaves.len() % batch_size != 0");
         size_t per = n / batch_size;
         COZK_REQUIRE(per >= 2 && (per & (per - 1)) == 0, "grand product: leaves per circuit must be a power of two >= 2");
-        int num_layers = 0;
-        while (((size_t)1 << num_layers) < per) num_layers++;
+        const int num_layers = ceil_log2(per);
         Rep3BatchedDenseGrandProduct gp;
         gp.layers.push_back(std::move(leaves));
         for (int i = 0; i < num_layers - 1; i++) {
@@ -357,7 +354,7 @@ static GrandProductLayerProof coordinate_prove_layer(StarNetCoordinator& net, Tr
     Bytes nb = net.receive_response(0);
     Reader rd(nb);
     int num_rounds = (int)rd.u64();
-    std::vector<fe> r_sumcheck = coordinate_prove_arbitrary(net, tr, num_rounds, lp.proof);
+    std::vector<fe> r_sumcheck = coordinate_prove_arbitrary(net, tr, num_rounds, lp.proof.compressed_polys);
     receive_final_claims(net, lp.left_claim, lp.right_claim);
     tr.append_scalar(lp.left_claim);
     tr.append_scalar(lp.right_claim);
@@ -375,22 +372,10 @@ static GrandProductLayerProof coordinate_prove_layer(StarNetCoordinator& net, Tr
 static GrandProductProof coordinate_prove_grand_product(StarNetCoordinator& net, Transcript& tr, size_t num_layers, fe& claim_out,
                                                         std::vector<fe>& r_out) {
     GrandProductProof proof;
-    std::vector<std::vector<fe>> parts;
-    for (Bytes& b : net.receive_responses()) {
-        Reader rd(b);
-        parts.push_back(rd.vec_fr());
-    }
-    proof.outputs = combine_additive(parts);
+    proof.outputs = gather_additive(net);
     tr.append_scalars(proof.outputs);
-    // DensePolynomial::new_padded(outputs).evaluate(r)
-    std::vector<fe> padded = proof.outputs;
-    while (padded.size() & (padded.size() - 1)) padded.push_back(Fr::zero());
-    int nv = 0;
-    while (((size_t)1 << nv) < padded.size()) nv++;
-    std::vector<fe> r = tr.challenge_vector(nv);
-    std::vector<fe> eq = eq_evals_host(r);
-    fe claim = Fr::zero();
-    for (size_t i = 0; i < padded.size(); i++) claim = Fr::add(claim, Fr::mul(eq[i], padded[i]));
+    std::vector<fe> r;
+    fe claim = mle_claim_padded(proof.outputs, tr, r);
     Writer w;
     w.vec_fr(r);
     w.fr(claim);
@@ -405,35 +390,13 @@ static GrandProductProof coordinate_prove_grand_product(StarNetCoordinator& net,
 // decompression and the layer reduction eq(r, r') L R = g(r')).  Returns false on any mismatch.
 static bool verify_grand_product(const GrandProductProof& proof, Transcript& tr, fe& claim_out, std::vector<fe>& r_out) {
     tr.append_scalars(proof.outputs);
-    std::vector<fe> padded = proof.outputs;
-    while (padded.size() & (padded.size() - 1)) padded.push_back(Fr::zero());
-    int nv = 0;
-    while (((size_t)1 << nv) < padded.size()) nv++;
-    std::vector<fe> r = tr.challenge_vector(nv);
-    std::vector<fe> eqv = eq_evals_host(r);
-    fe claim = Fr::zero();
-    for (size_t i = 0; i < padded.size(); i++) claim = Fr::add(claim, Fr::mul(eqv[i], padded[i]));
-    fe one = Fr::one();
+    std::vector<fe> r;
+    fe claim = mle_claim_padded(proof.outputs, tr, r);
     for (const GrandProductLayerProof& lp : proof.gkr_layers) {
         std::vector<fe> rs;
         fe e = claim;
-        for (const auto& comp : lp.proof.compressed_polys) {
-            std::vector<fe> poly = unipoly_decompress(comp, e);
-            tr.append_scalars(comp);
-            fe r_j = tr.challenge_scalar();
-            rs.push_back(r_j);
-            e = unipoly_eval(poly, r_j);
-        }
-        if (rs.size() != r.size()) return false;
-        fe eq = one;
-        for (size_t i = 0; i < r.size(); i++) {
-            const fe& a = r[i];
-            const fe& b = rs[rs.size() - 1 - i];
-            fe ab = Fr::mul(a, b);
-            // a b + (1-a)(1-b) = 1 - a - b + 2ab
-            fe t = Fr::add(Fr::sub(Fr::sub(one, a), b), Fr::dbl(ab));
-            eq = Fr::mul(eq, t);
-        }
+        if (!verify_sumcheck_rounds(lp.proof.compressed_polys, r.size(), 3, e, tr, rs)) return false;
+        fe eq = eq_eval_rev(r, rs);
         if (!Fr::eq(Fr::mul(Fr::mul(eq, lp.left_claim), lp.right_claim), e)) return false;
         tr.append_scalar(lp.left_claim);
         tr.append_scalar(lp.right_claim);
@@ -452,24 +415,6 @@ static bool verify_grand_product(const GrandProductProof& proof, Transcript& tr,
 // fingerprints) under tree_depth Rep3SparseInterleavedPolynomial layers.  The sparse layers are kept dense on the device
 // (toggle_layer.inc), so they are exactly a Rep3BatchedDenseGrandProduct over the toggle layer's output; the toggle layer
 // has its own round function and, unlike a multiplication layer, no r_layer fold after its sumcheck (:850-873).
-struct ToggleH {
-    cozk_toggle* h = nullptr;
-    ToggleH() {}
-    explicit ToggleH(cozk_toggle* t) : h(t) {}
-    ToggleH(const ToggleH&) = delete;
-    ToggleH& operator=(const ToggleH&) = delete;
-    ToggleH(ToggleH&& o) noexcept : h(o.h) { o.h = nullptr; }
-    ToggleH& operator=(ToggleH&& o) noexcept {
-        if (this != &o) {
-            cozk_toggle_free(h);
-            h = o.h;
-            o.h = nullptr;
-        }
-        return *this;
-    }
-    ~ToggleH() { cozk_toggle_free(h); }
-};
-
 struct Rep3ToggledBatchedGrandProduct {
     ToggleH toggle_layer;
     Rep3BatchedDenseGrandProduct sparse_layers;
@@ -553,7 +498,7 @@ static GrandProductLayerProof coordinate_prove_toggle_layer(StarNetCoordinator& 
     Bytes nb = net.receive_response(0);
     Reader rd(nb);
     int num_rounds = (int)rd.u64();
-    std::vector<fe> r_sumcheck = coordinate_prove_arbitrary(net, tr, num_rounds, lp.proof);
+    std::vector<fe> r_sumcheck = coordinate_prove_arbitrary(net, tr, num_rounds, lp.proof.compressed_polys);
     receive_final_claims(net, lp.left_claim, lp.right_claim);
     tr.append_scalar(lp.left_claim);
     tr.append_scalar(lp.right_claim);
@@ -565,21 +510,10 @@ static GrandProductLayerProof coordinate_prove_toggle_layer(StarNetCoordinator& 
 // then the toggle layer.  flag_claim / fingerprint_claim = the toggle layer's final claims at r_out.
 static GrandProductProof coordinate_prove_toggled_grand_product(StarNetCoordinator& net, Transcript& tr, size_t num_layers, std::vector<fe>& r_out) {
     GrandProductProof proof;
-    std::vector<std::vector<fe>> parts;
-    for (Bytes& b : net.receive_responses()) {
-        Reader rd(b);
-        parts.push_back(rd.vec_fr());
-    }
-    proof.outputs = combine_additive(parts);
+    proof.outputs = gather_additive(net);
     tr.append_scalars(proof.outputs);
-    std::vector<fe> padded = proof.outputs;
-    while (padded.size() & (padded.size() - 1)) padded.push_back(Fr::zero());
-    int nv = 0;
-    while (((size_t)1 << nv) < padded.size()) nv++;
-    std::vector<fe> r = tr.challenge_vector(nv);
-    std::vector<fe> eq = eq_evals_host(r);
-    fe claim = Fr::zero();
-    for (size_t i = 0; i < padded.size(); i++) claim = Fr::add(claim, Fr::mul(eq[i], padded[i]));
+    std::vector<fe> r;
+    fe claim = mle_claim_padded(proof.outputs, tr, r);
     Writer w;
     w.vec_fr(r);
     w.fr(claim);
@@ -594,34 +528,15 @@ static GrandProductProof coordinate_prove_toggled_grand_product(StarNetCoordinat
 // eq * L * R and fold with r_layer, the toggle layer (last) checks eq * (flag * fingerprint + 1 - flag)
 static bool verify_toggled_grand_product(const GrandProductProof& proof, Transcript& tr, fe& flag_claim, fe& fingerprint_claim, std::vector<fe>& r_out) {
     tr.append_scalars(proof.outputs);
-    std::vector<fe> padded = proof.outputs;
-    while (padded.size() & (padded.size() - 1)) padded.push_back(Fr::zero());
-    int nv = 0;
-    while (((size_t)1 << nv) < padded.size()) nv++;
-    std::vector<fe> r = tr.challenge_vector(nv);
-    std::vector<fe> eqv = eq_evals_host(r);
-    fe claim = Fr::zero();
-    for (size_t i = 0; i < padded.size(); i++) claim = Fr::add(claim, Fr::mul(eqv[i], padded[i]));
-    fe one = Fr::one();
+    std::vector<fe> r;
+    fe claim = mle_claim_padded(proof.outputs, tr, r);
     if (proof.gkr_layers.empty()) return false;
     for (size_t li = 0; li < proof.gkr_layers.size(); li++) {
         const GrandProductLayerProof& lp = proof.gkr_layers[li];
         std::vector<fe> rs;
         fe e = claim;
-        for (const auto& comp : lp.proof.compressed_polys) {
-            std::vector<fe> poly = unipoly_decompress(comp, e);
-            tr.append_scalars(comp);
-            fe r_j = tr.challenge_scalar();
-            rs.push_back(r_j);
-            e = unipoly_eval(poly, r_j);
-        }
-        if (rs.size() != r.size()) return false;
-        fe eq = one;
-        for (size_t i = 0; i < r.size(); i++) {
-            const fe& a = r[i];
-            const fe& b = rs[rs.size() - 1 - i];
-            eq = Fr::mul(eq, Fr::add(Fr::sub(Fr::sub(one, a), b), Fr::dbl(Fr::mul(a, b))));
-        }
+        if (!verify_sumcheck_rounds(lp.proof.compressed_polys, r.size(), 3, e, tr, rs)) return false;
+        fe eq = eq_eval_rev(r, rs);
         tr.append_scalar(lp.left_claim);
         tr.append_scalar(lp.right_claim);
         r.assign(rs.rbegin(), rs.rend());
@@ -631,7 +546,7 @@ static bool verify_toggled_grand_product(const GrandProductProof& proof, Transcr
             claim = Fr::add(lp.left_claim, Fr::mul(r_layer, Fr::sub(lp.right_claim, lp.left_claim)));
             r.push_back(r_layer);
         } else {
-            fe node = Fr::add(Fr::mul(lp.left_claim, lp.right_claim), Fr::sub(one, lp.left_claim));
+            fe node = Fr::add(Fr::mul(lp.left_claim, lp.right_claim), Fr::sub(Fr::one(), lp.left_claim));
             if (!Fr::eq(Fr::mul(eq, node), e)) return false;
             flag_claim = lp.left_claim;
             fingerprint_claim = lp.right_claim;
@@ -642,16 +557,6 @@ static bool verify_toggled_grand_product(const GrandProductProof& proof, Transcr
 }
 
 // ================================================================= Lasso primary sumcheck (instruction lookups)
-struct PrimaryH {
-    cozk_primary* h = nullptr;
-    PrimaryH() {}
-    explicit PrimaryH(cozk_primary* p) : h(p) {}
-    PrimaryH(const PrimaryH&) = delete;
-    PrimaryH& operator=(const PrimaryH&) = delete;
-    PrimaryH(PrimaryH&& o) noexcept : h(o.h) { o.h = nullptr; }
-    ~PrimaryH() { cozk_primary_free(h); }
-};
-
 // UniPoly::from_evals for any number of points 0, 1, .., n-1 (Lagrange with small-integer denominators)
 static inline std::vector<fe> unipoly_from_evals_general(const std::vector<fe>& ev) {
     const size_t n = ev.size();
@@ -752,6 +657,11 @@ static std::vector<fe> prove_primary_sumcheck_worker(WorkerEnv& env, cozk_primar
 struct PrimarySumcheckProof {
     std::vector<std::vector<fe>> compressed_polys;
     std::vector<fe> openings;  // E(r) (n_mem), flags(r) (n_instr), lookup_outputs(r)
+    void write(Writer& w) const {
+        w.u64(compressed_polys.size());
+        for (auto& p : compressed_polys) w.vec_fr(p);
+        w.vec_fr(openings);
+    }
 };
 
 // prove_primary_sumcheck_rep3 (jolt/vm/instruction_lookups/coordinator.rs:97-150) + the final claims.  n_participants = parties x
@@ -764,18 +674,9 @@ static PrimarySumcheckProof coordinate_primary_sumcheck(StarNetCoordinator& net,
     r_out.clear();
     if (nparties <= 0) nparties = net.n_workers();
     const int all = net.n_workers();
-    auto gather = [&](int count) {
-        std::vector<std::vector<fe>> parts;
-        for (int id = 0; id < count; id++) {
-            Bytes b = net.receive_response(id);
-            Reader rd(b);
-            parts.push_back(rd.vec_fr());
-        }
-        return combine_additive(parts);
-    };
     for (int round = 0; round < num_rounds; round++) {
         const bool split_round = round < num_rounds - log_workers;
-        std::vector<fe> ev = gather(split_round ? all : nparties);
+        std::vector<fe> ev = gather_additive(net, split_round ? all : nparties);
         ev.insert(ev.begin() + 1, Fr::sub(previous_claim, ev[0]));  // round_evals.insert(1, previous_claim - round_evals[0])
         std::vector<fe> poly = unipoly_from_evals_general(ev);
         std::vector<fe> comp = unipoly_compress(poly);
@@ -788,7 +689,7 @@ static PrimarySumcheckProof coordinate_primary_sumcheck(StarNetCoordinator& net,
         r_out.push_back(r_j);
         previous_claim = unipoly_eval(poly, r_j);
     }
-    proof.openings = gather(nparties);
+    proof.openings = gather_additive(net, nparties);
     tr.append_scalars(proof.openings);
     return proof;
 }
@@ -902,39 +803,17 @@ static inline int primary_sumcheck_degree(const std::vector<cozk_primary_instr>&
 static bool verify_primary_sumcheck(const PrimarySumcheckProof& proof, const std::vector<cozk_primary_instr>& instrs, size_t n_mem, int degree,
                                     const std::vector<fe>& r_eq, Transcript& tr, std::vector<fe>& r_out) {
     fe claim = Fr::zero();
-    r_out.clear();
-    for (const auto& comp : proof.compressed_polys) {
-        if ((int)comp.size() != degree) return false;
-        std::vector<fe> poly = unipoly_decompress(comp, claim);
-        tr.append_scalars(comp);
-        fe r_j = tr.challenge_scalar();
-        r_out.push_back(r_j);
-        claim = unipoly_eval(poly, r_j);
-    }
-    if (proof.openings.size() != n_mem + instrs.size() + 1 || r_out.size() != r_eq.size()) return false;
+    if (!verify_sumcheck_rounds(proof.compressed_polys, r_eq.size(), (size_t)degree, claim, tr, r_out)) return false;
+    if (proof.openings.size() != n_mem + instrs.size() + 1) return false;
     tr.append_scalars(proof.openings);
     std::vector<fe> E(proof.openings.begin(), proof.openings.begin() + n_mem);
-    fe one = Fr::one(), eq = one;
-    for (size_t i = 0; i < r_eq.size(); i++) {
-        const fe& a = r_eq[i];
-        const fe& b = r_out[r_out.size() - 1 - i];
-        eq = Fr::mul(eq, Fr::add(Fr::sub(Fr::sub(one, a), b), Fr::dbl(Fr::mul(a, b))));
-    }
+    fe eq = eq_eval_rev(r_eq, r_out);
     fe acc = Fr::zero();
     for (size_t i = 0; i < instrs.size(); i++) acc = Fr::add(acc, Fr::mul(proof.openings[n_mem + i], primary_g_plain(instrs[i], E)));
     return Fr::eq(Fr::mul(eq, Fr::sub(acc, proof.openings.back())), claim);
 }
 
 // ================================================================= co-jolt Spartan outer sumcheck
-struct OuterH {
-    cozk_outer* h = nullptr;
-    OuterH() {}
-    explicit OuterH(cozk_outer* p) : h(p) {}
-    OuterH(const OuterH&) = delete;
-    OuterH& operator=(const OuterH&) = delete;
-    ~OuterH() { cozk_outer_free(h); }
-};
-
 // prove_spartan_cubic_sumcheck (co-jolt/src/r1cs/spartan/worker.rs:277-300): per round the cubic goes up
 // (process_eq_sumcheck_round_worker, subprotocols/sumcheck_spartan.rs:44-79), (next claim, r_i) comes down; at the end the
 // three final evaluations.  Returns the challenges in round order.
@@ -972,37 +851,19 @@ static std::vector<fe> prove_spartan_cubic_sumcheck_worker(WorkerEnv& env, cozk_
 struct OuterSumcheckProof {
     std::vector<std::vector<fe>> compressed_polys;
     std::vector<fe> claims;  // Az(r), Bz(r), Cz(r)
+    void write(Writer& w) const {
+        w.u64(compressed_polys.size());
+        for (auto& p : compressed_polys) w.vec_fr(p);
+        w.vec_fr(claims);
+    }
 };
 
 // coordinate_eq_sumcheck_round (subprotocols/sumcheck_spartan.rs:14-42) over all rounds + the outer claims
 // (r1cs/spartan/coordinator.rs:41-63)
 static OuterSumcheckProof coordinate_outer_sumcheck(StarNetCoordinator& net, Transcript& tr, int num_rounds, std::vector<fe>& r_out) {
     OuterSumcheckProof proof;
-    r_out.clear();
-    for (int round = 0; round < num_rounds; round++) {
-        std::vector<std::vector<fe>> parts;
-        for (Bytes& b : net.receive_responses()) {
-            Reader rd(b);
-            parts.push_back(rd.vec_fr());
-        }
-        std::vector<fe> poly = combine_additive(parts);
-        std::vector<fe> comp = unipoly_compress(poly);
-        tr.append_scalars(comp);
-        proof.compressed_polys.push_back(comp);
-        fe r_i = tr.challenge_scalar();
-        r_out.push_back(r_i);
-        fe claim = unipoly_eval(poly, r_i);
-        Writer w;
-        w.fr(claim);
-        w.fr(r_i);
-        net.broadcast_request(w.b);
-    }
-    std::vector<std::vector<fe>> parts;
-    for (Bytes& b : net.receive_responses()) {
-        Reader rd(b);
-        parts.push_back(rd.vec_fr());
-    }
-    proof.claims = combine_additive(parts);
+    r_out = coordinate_prove_arbitrary(net, tr, num_rounds, proof.compressed_polys, true);
+    proof.claims = gather_additive(net);
     tr.append_scalars(proof.claims);
     return proof;
 }
@@ -1010,23 +871,9 @@ static OuterSumcheckProof coordinate_outer_sumcheck(StarNetCoordinator& net, Tra
 // outer-sumcheck part of the plain verifier (jolt-core UniformSpartanProof::verify, out of tree)
 static bool verify_outer_sumcheck(const OuterSumcheckProof& proof, const std::vector<fe>& tau, Transcript& tr, std::vector<fe>& r_out) {
     fe claim = Fr::zero();
-    r_out.clear();
-    for (const auto& comp : proof.compressed_polys) {
-        if (comp.size() != 3) return false;
-        std::vector<fe> poly = unipoly_decompress(comp, claim);
-        tr.append_scalars(comp);
-        fe r_i = tr.challenge_scalar();
-        r_out.push_back(r_i);
-        claim = unipoly_eval(poly, r_i);
-    }
-    if (proof.claims.size() != 3 || r_out.size() != tau.size()) return false;
+    if (!verify_sumcheck_rounds(proof.compressed_polys, tau.size(), 3, claim, tr, r_out) || proof.claims.size() != 3) return false;
     tr.append_scalars(proof.claims);
-    fe one = Fr::one(), eq = one;
-    for (size_t i = 0; i < tau.size(); i++) {
-        const fe& a = tau[i];
-        const fe& b = r_out[r_out.size() - 1 - i];
-        eq = Fr::mul(eq, Fr::add(Fr::sub(Fr::sub(one, a), b), Fr::dbl(Fr::mul(a, b))));
-    }
+    fe eq = eq_eval_rev(tau, r_out);
     return Fr::eq(Fr::mul(eq, Fr::sub(Fr::mul(proof.claims[0], proof.claims[1]), proof.claims[2])), claim);
 }
 
@@ -1034,6 +881,10 @@ static bool verify_outer_sumcheck(const OuterSumcheckProof& proof, const std::ve
 struct PST13Commitment {
     uint64_t nv;
     g1_affine g_product;
+    void write(Writer& w) const {
+        w.u64(nv);
+        w.g1(g_product);
+    }
 };
 
 // SRS levels `ck.powers_of_g[i]` (size 2^(nv-i)) live concatenated in one device handle; `halves`
@@ -1111,9 +962,7 @@ struct PST13 {
         rc_check(cozk_batch_msm_slices(ctx, s.powers_all, offs.data(), polys.data(), nullptr, k, xy.data(), inf.data()), ctx, "batch_msm");
         for (size_t i = 0; i < k; i++) {
             size_t len = cozk_vec_len(polys[i]);
-            uint64_t nv = 0;
-            while (((size_t)1 << nv) < len) nv++;
-            out[i].nv = nv;
+            out[i].nv = (uint64_t)ceil_log2(len);
             out[i].g_product = abi_to_g1(xy.data() + 8 * i, inf[i]);
         }
         return out;
@@ -1243,6 +1092,11 @@ struct ReducedOpeningProof {
     SumcheckProof sumcheck_proof;
     std::vector<fe> sumcheck_claims;
     std::vector<g1_affine> joint_opening_proof;
+    void write(Writer& w) const {
+        sumcheck_proof.write(w);
+        w.vec_fr(sumcheck_claims);
+        w.vec_g1(joint_opening_proof);
+    }
 };
 
 struct Rep3ProverOpeningAccumulator {
@@ -1278,12 +1132,7 @@ struct Rep3ProverOpeningAccumulator {
 
     // receive_claims (opening_proof.rs:108-128), coordinator side
     static std::vector<fe> receive_claims(StarNetCoordinator& net, Transcript& tr) {
-        std::vector<std::vector<fe>> parts;
-        for (Bytes& b : net.receive_responses()) {
-            Reader rd(b);
-            parts.push_back(rd.vec_fr());
-        }
-        std::vector<fe> claims = combine_additive(parts);
+        std::vector<fe> claims = gather_additive(net);
         fe rho = tr.challenge_scalar();
         fe pw = Fr::one(), batched = Fr::zero();
         for (size_t i = 0; i < claims.size(); i++) {
@@ -1429,31 +1278,8 @@ struct Rep3ProverOpeningAccumulator {
         Bytes mb = net.receive_response(0);
         Reader mr(mb);
         size_t max_num_vars = (size_t)mr.u64();
-        std::vector<fe> r;
-        for (size_t round = 0; round < max_num_vars; round++) {
-            std::vector<std::vector<fe>> parts;
-            for (Bytes& b : net.receive_responses()) {
-                Reader rd(b);
-                parts.push_back(rd.vec_fr());
-            }
-            std::vector<fe> uni = combine_additive(parts);
-            std::vector<fe> comp = unipoly_compress(uni);
-            tr.append_scalars(comp);
-            fe r_j = tr.challenge_scalar();
-            r.push_back(r_j);
-            fe new_claim = unipoly_eval(uni, r_j);
-            Writer ww;
-            ww.fr(r_j);
-            ww.fr(new_claim);
-            net.broadcast_request(ww.b);
-            proof.sumcheck_proof.compressed_polys.push_back(comp);
-        }
-        std::vector<std::vector<fe>> parts;
-        for (Bytes& b : net.receive_responses()) {
-            Reader rd(b);
-            parts.push_back(rd.vec_fr());
-        }
-        proof.sumcheck_claims = combine_additive(parts);
+        std::vector<fe> r = coordinate_prove_arbitrary(net, tr, (int)max_num_vars, proof.sumcheck_proof.compressed_polys);
+        proof.sumcheck_claims = gather_additive(net);
         tr.append_scalars(proof.sumcheck_claims);
         fe gamma = tr.challenge_scalar();
         Writer gw;
@@ -1466,6 +1292,86 @@ struct Rep3ProverOpeningAccumulator {
         return proof;
     }
 };
+
+// One opening of the batch as the plain verifier sees it: the polynomials (indices into the list of commitments) opened at `point`,
+// their claimed evaluations, and the rho that receive_claims drew for them.
+struct VerifierOpening {
+    std::vector<fe> point;
+    std::vector<size_t> polys;
+    std::vector<fe> claims;
+    fe rho;
+};
+
+// plain verifier of reduce_and_prove (opening_proof.rs:181-235; the verifier's reduce_and_verify is out of tree): the reduction
+// sumcheck over all openings, its final claim against eq(point_i, r), then ONE PST13 check of the joint polynomial (pairing-free,
+// trapdoor known).  An opening shorter than the longest one uses the last point_i.size() challenges; its claim is scaled by
+// 2^(missing variables) going in and by prod (1 - r_j) over them in the joint claim.  joint commitment = sum_i gamma^i sum_k
+// rho_i^k C_(i,k), with one scalar multiplication per commitment.
+static bool verify_reduced_opening(const std::vector<VerifierOpening>& opens, const std::vector<PST13Commitment>& commitments, Transcript& tr,
+                                   const ReducedOpeningProof& proof, const PST13Setup& setup, const char* why_shape, const char* why_final,
+                                   std::string& why) {
+    const fe one = Fr::one();
+    std::vector<fe> batched_claims;
+    std::vector<std::vector<fe>> pws;
+    for (auto& o : opens) {
+        std::vector<fe> pw(1, one);
+        for (size_t i = 1; i < o.claims.size(); i++) pw.push_back(Fr::mul(pw[i - 1], o.rho));
+        fe bc = Fr::zero();
+        for (size_t i = 0; i < pw.size(); i++) bc = Fr::add(bc, Fr::mul(pw[i], o.claims[i]));
+        batched_claims.push_back(bc);
+        pws.push_back(pw);
+    }
+    fe rho2 = tr.challenge_scalar();
+    size_t max_nv = 0;
+    for (auto& o : opens) max_nv = std::max(max_nv, o.point.size());
+    std::vector<fe> coeffs(1, one);
+    for (size_t i = 1; i < opens.size(); i++) coeffs.push_back(Fr::mul(coeffs[i - 1], rho2));
+    fe e = Fr::zero();
+    for (size_t i = 0; i < opens.size(); i++)
+        e = Fr::add(e, Fr::mul(coeffs[i], Fr::mul(batched_claims[i], fr_from_u64((uint64_t)1 << (max_nv - opens[i].point.size())))));
+    std::vector<fe> rs;
+    if (!verify_sumcheck_rounds(proof.sumcheck_proof.compressed_polys, max_nv, 2, e, tr, rs) || proof.sumcheck_claims.size() != opens.size()) {
+        why = why_shape;
+        return false;
+    }
+    fe expect = Fr::zero();
+    for (size_t i = 0; i < opens.size(); i++) {
+        std::vector<fe> slice(rs.end() - (long)opens[i].point.size(), rs.end());
+        expect = Fr::add(expect, Fr::mul(coeffs[i], Fr::mul(eq_eval(opens[i].point, slice), proof.sumcheck_claims[i])));
+    }
+    if (!Fr::eq(expect, e)) {
+        why = why_final;
+        return false;
+    }
+    tr.append_scalars(proof.sumcheck_claims);
+    fe gamma = tr.challenge_scalar();
+    std::vector<fe> scal(commitments.size(), Fr::zero());
+    fe gp = one, joint_claim = Fr::zero();
+    for (size_t i = 0; i < opens.size(); i++) {
+        for (size_t k = 0; k < opens[i].polys.size(); k++) {
+            fe& sc = scal[opens[i].polys[k]];
+            sc = Fr::add(sc, Fr::mul(gp, pws[i][k]));
+        }
+        fe sc = one;
+        for (size_t j = 0; j + opens[i].point.size() < max_nv; j++) sc = Fr::mul(sc, Fr::sub(one, rs[j]));
+        joint_claim = Fr::add(joint_claim, Fr::mul(gp, Fr::mul(sc, proof.sumcheck_claims[i])));
+        gp = Fr::mul(gp, gamma);
+    }
+    std::vector<g1_affine> cs;
+    std::vector<fe> ss;
+    for (size_t i = 0; i < commitments.size(); i++)
+        if (!Fr::is_zero(scal[i])) {
+            cs.push_back(commitments[i].g_product);
+            ss.push_back(scal[i]);
+        }
+    g1_affine joint_c = PST13::combine_commitments(cs, ss);
+    std::vector<fe> rev(rs.rbegin(), rs.rend());
+    if (!PST13::check_with_trapdoor(setup, joint_c, rev, joint_claim, proof.joint_opening_proof)) {
+        why = "PST13 opening check failed";
+        return false;
+    }
+    return true;
+}
 
 // ================================================================= generic sumcheck (prove_arbitrary_worker)
 // co-jolt/src/subprotocols/sumcheck.rs:168-246 for comb_func = product of the polynomials (at most one shared
@@ -1530,8 +1436,7 @@ static ArbitraryResult prove_arbitrary_worker(WorkerEnv& env, const fe& claim, i
 static fe spartan_mask_additive(WorkerEnv& env);
 static std::vector<fe> rep3_first_sumcheck_worker(WorkerEnv& env, cozk_poly* za, cozk_poly* zb, cozk_poly* zc, cozk_poly* eq, std::vector<fe>& finals) {
     size_t len = cozk_poly_len(eq);
-    int num_vars = 0;
-    while (((size_t)1 << num_vars) < len) num_vars++;
+    const int num_vars = ceil_log2(len);
     std::vector<fe> point;
     for (int round = 0; round < num_vars; round++) {
         uint64_t ev[16];
@@ -1565,8 +1470,7 @@ static std::vector<fe> rep3_first_sumcheck_worker(WorkerEnv& env, cozk_poly* za,
 static std::vector<fe> rep3_second_sumcheck_worker(WorkerEnv& env, cozk_poly* z, cozk_poly* a, cozk_poly* b, cozk_poly* c, const fe coef[3],
                                                    std::vector<fe>& finals) {
     size_t len = cozk_poly_len(z);
-    int num_vars = 0;
-    while (((size_t)1 << num_vars) < len) num_vars++;
+    const int num_vars = ceil_log2(len);
     uint64_t cf[12];
     for (int i = 0; i < 3; i++) fe_to_u64x4(coef[i], cf + 4 * i);
     std::vector<fe> point;

@@ -131,22 +131,12 @@ static VecH eq_le_device(cozk_ctx* ctx, const std::vector<fe>& r) {
     return VecH(v);
 }
 
-static PolyH plain_poly_from(cozk_ctx* ctx, const VecH& v) {
-    cozk_poly* p = nullptr;
-    rc_check(cozk_poly_create(ctx, COZK_MODE_PLAIN, v.h, nullptr, &p), ctx, "poly_create");
-    return PolyH(p);
-}
-
 static VecH upload_fe(cozk_ctx* ctx, const std::vector<fe>& v) {
     std::vector<uint64_t> w = to_abi(v);
-    cozk_vec* d = nullptr;
-    rc_check(cozk_vec_upload(ctx, w.data(), v.size(), COZK_SCALAR_FR, &d), ctx, "vec_upload");
-    return VecH(d);
+    return upload_vec(ctx, w.data(), v.size(), COZK_SCALAR_FR, "vec_upload");
 }
 static VecH upload_u32(cozk_ctx* ctx, const std::vector<uint32_t>& v) {
-    cozk_vec* d = nullptr;
-    rc_check(cozk_vec_upload(ctx, v.data(), v.size(), COZK_SCALAR_U32, &d), ctx, "vec_upload");
-    return VecH(d);
+    return upload_vec(ctx, v.data(), v.size(), COZK_SCALAR_U32, "vec_upload");
 }
 
 // builds the instance on the host (every participant derives the same one), fills h->h_*
@@ -191,20 +181,7 @@ static void spartan_setup_party(cozk_spartan* h, SpartanParty& ps, const std::ve
     ps.setup = PST13::setup(ctx, t, c.precompute);
     // witness shares: P0 = (t0, t2), P1 = (t1, t0), P2 = (t2, t1), t2 = z - t0 - t1 (arithmetic.rs:21-33)
     VecH zv = upload_fe(ctx, z_plain);
-    if (c.mode == COZK_MODE_PLAIN) {
-        ps.z = plain_poly_from(ctx, zv);
-    } else {
-        // the witness scatter of the engine: t0 = PRF(k0, i), t1 = PRF(k1, i) (cozk_rep3_share_vec, ChaCha12)
-        uint8_t k0[COZK_PRF_KEY_BYTES], k1[COZK_PRF_KEY_BYTES];
-        harness_prf_key(c.seed + 1000ull, 101, k0);
-        harness_prf_key(c.seed + 1000ull, 102, k1);
-        cozk_vec *sa = nullptr, *sb = nullptr;
-        rc_check(cozk_rep3_share_vec(ctx, zv.h, k0, k1, 0, ps.party, &sa, &sb), ctx, "rep3_share_vec");
-        VecH a(sa), b(sb);
-        cozk_poly* p = nullptr;
-        rc_check(cozk_poly_create(ctx, COZK_MODE_REP3, a.h, b.h, &p), ctx, "poly_create");
-        ps.z = PolyH(p);
-    }
+    ps.z = make_shared_poly(ctx, c.mode, zv, c.seed + 1000ull, ps.party);
     // CSR by row: three entries per row
     std::vector<uint32_t> rp(n + 1);
     for (size_t i = 0; i <= n; i++) rp[i] = (uint32_t)(3 * i);
@@ -263,7 +240,7 @@ static void spartan_setup_party(cozk_spartan* h, SpartanParty& ps, const std::ve
             std::vector<fe> pad(*vals[k]);
             pad.resize(NZ, Fr::zero());
             ps.val_pad[k] = upload_fe(ctx, pad);
-            ps.val_poly[k] = plain_poly_from(ctx, ps.val_pad[k]);
+            ps.val_poly[k] = plain_poly(ctx, ps.val_pad[k]);
             vv.push_back(ps.val_pad[k].h);
         }
         h->val_oracles.clear();
@@ -541,7 +518,7 @@ static void spartan_worker_main(cozk_spartan* h, SpartanParty& ps, StarNetWorker
     std::vector<fe> rx, finals1;
     {
         VecH eqv = eq_le_device(ctx, tau);
-        PolyH eq = plain_poly_from(ctx, eqv);
+        PolyH eq = plain_poly(ctx, eqv);
         rx = rep3_first_sumcheck_worker(env, zah.h, zbh.h, zch.h, eq.h, finals1);
     }
     double t3 = now_ms();
@@ -559,7 +536,7 @@ static void spartan_worker_main(cozk_spartan* h, SpartanParty& ps, StarNetWorker
     cozk_poly *arx = nullptr, *brx = nullptr, *crx = nullptr;
     {
         VecH eqrx = eq_le_device(ctx, rx);
-        PolyH eqp = plain_poly_from(ctx, eqrx);
+        PolyH eqp = plain_poly(ctx, eqrx);
         rc_check(cozk_sparse_matvec3(ctx, ps.t_ptr.h, ps.t_row.h, ps.t_va.h, ps.t_vb.h, ps.t_vc.h, eqp.h, &arx, &brx, &crx), ctx, "A(rx,.) build");
     }
     PolyH arxh(arx), brxh(brx), crxh(crx);
@@ -609,10 +586,20 @@ static void spartan_worker_main(cozk_spartan* h, SpartanParty& ps, StarNetWorker
 }
 
 // --------------------------------------------------------------------------- coordinator + verifier
-static fe eval_points(const std::vector<fe>& ev, const fe& r) {
-    std::vector<fe> cf(ev.size());
-    unipoly_from_evals(ev.data(), (int)ev.size(), cf.data());
-    return unipoly_eval(cf, r);
+// Verifier replay of a sumcheck whose round messages are the evaluations g(0), .., g(n_points - 1): per round check the message's
+// length and g(0) + g(1) == claim, append it, draw r, claim = g(r).  Returns the first round that fails, or -1.
+static int verify_sumcheck_eval_rounds(const std::vector<std::vector<fe>>& msgs, size_t n_points, fe& claim, Transcript& tr, std::vector<fe>& rs) {
+    for (size_t j = 0; j < msgs.size(); j++) {
+        const std::vector<fe>& ev = msgs[j];
+        if (ev.size() != n_points || !Fr::eq(Fr::add(ev[0], ev[1]), claim)) return (int)j;
+        tr.append_scalars(ev);
+        fe r = tr.challenge_scalar();
+        rs.push_back(r);
+        std::vector<fe> cf(ev.size());
+        unipoly_from_evals(ev.data(), (int)ev.size(), cf.data());
+        claim = unipoly_eval(cf, r);
+    }
+    return -1;
 }
 
 static bool spartan_verify(cozk_spartan* h, const SpartanProof& pf, std::string& why) {
@@ -627,16 +614,10 @@ static bool spartan_verify(cozk_spartan* h, const SpartanProof& pf, std::string&
     }
     fe claim = Fr::zero();  // a satisfied instance: sum_x eq(tau, x) (Az Bz - Cz)(x) = 0
     std::vector<fe> rx;
-    for (int j = 0; j < nv; j++) {
-        const std::vector<fe>& ev = pf.sc1[j];
-        if (ev.size() != 4 || !Fr::eq(Fr::add(ev[0], ev[1]), claim)) {
-            why = "first sumcheck: round " + std::to_string(j) + " g(0) + g(1) != claim";
-            return false;
-        }
-        tr.append_scalars(ev);
-        fe r = tr.challenge_scalar();
-        rx.push_back(r);
-        claim = eval_points(ev, r);
+    int bad = verify_sumcheck_eval_rounds(pf.sc1, 4, claim, tr, rx);
+    if (bad >= 0) {
+        why = "first sumcheck: round " + std::to_string(bad) + " g(0) + g(1) != claim";
+        return false;
     }
     const fe &va = pf.sc1_finals[0], &vb = pf.sc1_finals[1], &vc = pf.sc1_finals[2], &veq = pf.sc1_finals[3];
     if (!Fr::eq(veq, eq_eval(tau, rx))) {
@@ -651,16 +632,10 @@ static bool spartan_verify(cozk_spartan* h, const SpartanProof& pf, std::string&
     std::vector<fe> abc = tr.challenge_vector(3);
     fe claim2 = Fr::add(Fr::add(Fr::mul(abc[0], va), Fr::mul(abc[1], vb)), Fr::mul(abc[2], vc));
     std::vector<fe> ry;
-    for (int j = 0; j < nv; j++) {
-        const std::vector<fe>& ev = pf.sc2[j];
-        if (ev.size() != 3 || !Fr::eq(Fr::add(ev[0], ev[1]), claim2)) {
-            why = "second sumcheck: round " + std::to_string(j) + " g(0) + g(1) != claim";
-            return false;
-        }
-        tr.append_scalars(ev);
-        fe r = tr.challenge_scalar();
-        ry.push_back(r);
-        claim2 = eval_points(ev, r);
+    bad = verify_sumcheck_eval_rounds(pf.sc2, 3, claim2, tr, ry);
+    if (bad >= 0) {
+        why = "second sumcheck: round " + std::to_string(bad) + " g(0) + g(1) != claim";
+        return false;
     }
     const fe &vz = pf.sc2_finals[0], &ar = pf.sc2_finals[1], &br = pf.sc2_finals[2], &cr = pf.sc2_finals[3];
     if (!Fr::eq(claim2, Fr::mul(vz, Fr::add(Fr::add(Fr::mul(abc[0], ar), Fr::mul(abc[1], br)), Fr::mul(abc[2], cr))))) {
@@ -719,16 +694,10 @@ static bool spartan_verify(cozk_spartan* h, const SpartanProof& pf, std::string&
         }
         fe expected = Fr::add(Fr::add(Fr::mul(abc[0], pf.val_abc[0]), Fr::mul(abc[1], pf.val_abc[1])), Fr::mul(abc[2], pf.val_abc[2]));
         std::vector<fe> point;
-        for (int j = 0; j < qv; j++) {
-            const std::vector<fe>& ev = pf.lk_msgs[j];
-            if (ev.size() != 4 || !Fr::eq(Fr::add(ev[0], ev[1]), expected)) {
-                why = "lookup sumcheck: round " + std::to_string(j) + " g(0) + g(1) != claim";
-                return false;
-            }
-            tr.append_scalars(ev);
-            fe r = tr.challenge_scalar();
-            point.push_back(r);
-            expected = eval_points(ev, r);
+        bad = verify_sumcheck_eval_rounds(pf.lk_msgs, 4, expected, tr, point);
+        if (bad >= 0) {
+            why = "lookup sumcheck: round " + std::to_string(bad) + " g(0) + g(1) != claim";
+            return false;
         }
         fe eta = tr.challenge_scalar();
         const std::vector<fe>& E = pf.lk_evals;

@@ -62,7 +62,7 @@ static inline fe eq_plus_one_point(const std::vector<fe>& x, const std::vector<f
     for (int k = 0; k < l; k++) {
         fe v = Fr::mul(Fr::sub(one, x[l - 1 - k]), y[l - 1 - k]);
         for (int j = 0; j < k; j++) v = Fr::mul(v, Fr::mul(x[l - 1 - j], Fr::sub(one, y[l - 1 - j])));
-        for (int j = 0; j < l - k - 1; j++) v = Fr::mul(v, Fr::add(Fr::sub(Fr::sub(one, x[j]), y[j]), Fr::dbl(Fr::mul(x[j], y[j]))));
+        for (int j = 0; j < l - k - 1; j++) v = Fr::mul(v, eq_term(x[j], y[j]));
         acc = Fr::add(acc, v);
     }
     return acc;
@@ -110,14 +110,10 @@ struct JoltSpartanProof {
     fe shift_claim;
     std::vector<fe> witness_evals, shift_witness_evals;
     void write(Writer& w) const {
-        w.u64(outer.compressed_polys.size());
-        for (auto& p : outer.compressed_polys) w.vec_fr(p);
-        w.vec_fr(outer.claims);
-        w.u64(inner.compressed_polys.size());
-        for (auto& p : inner.compressed_polys) w.vec_fr(p);
+        outer.write(w);
+        inner.write(w);
         w.fr(shift_claim);
-        w.u64(shift.compressed_polys.size());
-        for (auto& p : shift.compressed_polys) w.vec_fr(p);
+        shift.write(w);
         w.vec_fr(witness_evals);
         w.vec_fr(shift_witness_evals);
     }
@@ -164,10 +160,8 @@ static inline std::vector<fe> spartan_batch_evaluate(WorkerEnv& env, const std::
 static inline void prove_spartan_worker(WorkerEnv& env, const jolt::System& sys, const std::vector<cozk_poly*>& cols, size_t num_steps,
                                         Rep3ProverOpeningAccumulator& acc, SpartanTimes* times = nullptr) {
     const size_t V = spartan_vars_padded(sys);
-    int steps_bits = 0;
-    while (((size_t)1 << steps_bits) < num_steps) steps_bits++;
-    int constr_bits = 0;
-    while (((size_t)1 << constr_bits) < sys.padded) constr_bits++;
+    const int steps_bits = ceil_log2(num_steps);
+    const int constr_bits = ceil_log2(sys.padded);
     double t0 = spartan_now_ms();
     // ---- Sumcheck 1: outer
     std::vector<fe> tau;
@@ -224,8 +218,7 @@ static inline void prove_spartan_worker(WorkerEnv& env, const jolt::System& sys,
     std::vector<fe> inner_r;
     {
         fe previous_claim = env.additive_trivial(claim_inner_joint);
-        int rounds = 0;
-        while (((size_t)1 << rounds) < 4 * V) rounds++;
+        const int rounds = ceil_log2(4 * V);
         for (int round = 0; round < rounds; round++) {
             const size_t half = abc.size() / 2;
             fe e0 = Fr::zero(), e2 = Fr::zero();
@@ -307,10 +300,8 @@ static inline void prove_spartan_worker(WorkerEnv& env, const jolt::System& sys,
 static inline JoltSpartanProof coordinate_spartan(StarNetCoordinator& net, Transcript& tr, const jolt::System& sys, size_t num_steps) {
     JoltSpartanProof proof;
     const size_t V = spartan_vars_padded(sys);
-    int steps_bits = 0;
-    while (((size_t)1 << steps_bits) < num_steps) steps_bits++;
-    int constr_bits = 0;
-    while (((size_t)1 << constr_bits) < sys.padded) constr_bits++;
+    const int steps_bits = ceil_log2(num_steps);
+    const int constr_bits = ceil_log2(sys.padded);
     std::vector<fe> tau = tr.challenge_vector((size_t)(steps_bits + constr_bits));
     {
         Writer w;
@@ -327,32 +318,17 @@ static inline JoltSpartanProof coordinate_spartan(StarNetCoordinator& net, Trans
         w.fr(claim_inner);
         net.broadcast_request(w.b);
     }
-    int inner_rounds = 0;
-    while (((size_t)1 << inner_rounds) < 4 * V) inner_rounds++;
-    (void)coordinate_prove_arbitrary(net, tr, inner_rounds, proof.inner);
+    const int inner_rounds = ceil_log2(4 * V);
+    (void)coordinate_prove_arbitrary(net, tr, inner_rounds, proof.inner.compressed_polys);
     proof.shift_claim = Fr::zero();  // combine_additive_share; not appended to the transcript (coordinator.rs:113-117)
     for (Bytes& b : net.receive_responses()) {
         Reader rd(b);
         proof.shift_claim = Fr::add(proof.shift_claim, rd.fr());
     }
-    (void)coordinate_prove_arbitrary(net, tr, steps_bits, proof.shift);
+    (void)coordinate_prove_arbitrary(net, tr, steps_bits, proof.shift.compressed_polys);
     proof.witness_evals = Rep3ProverOpeningAccumulator::receive_claims(net, tr);
     proof.shift_witness_evals = Rep3ProverOpeningAccumulator::receive_claims(net, tr);
     return proof;
-}
-
-static inline bool spartan_verify_rounds(const SumcheckProof& p, size_t rounds, size_t degree, fe& claim, Transcript& tr, std::vector<fe>& rs) {
-    if (p.compressed_polys.size() != rounds) return false;
-    rs.clear();
-    for (const auto& comp : p.compressed_polys) {
-        if (comp.size() != degree) return false;
-        std::vector<fe> poly = unipoly_decompress(comp, claim);
-        tr.append_scalars(comp);
-        fe r_j = tr.challenge_scalar();
-        rs.push_back(r_j);
-        claim = unipoly_eval(poly, r_j);
-    }
-    return true;
 }
 
 // the sumcheck checks of the plain verifier (jolt-core UniformSpartanProof::verify, out of tree).  On success rx_step and
@@ -360,10 +336,8 @@ static inline bool spartan_verify_rounds(const SumcheckProof& p, size_t rounds, 
 static inline bool verify_spartan(const JoltSpartanProof& proof, const jolt::System& sys, size_t num_steps, Transcript& tr, std::vector<fe>& rx_step,
                                   std::vector<fe>& shift_r, fe rho[2], std::string& why) {
     const size_t V = spartan_vars_padded(sys), nvars = sys.num_vars;
-    int steps_bits = 0;
-    while (((size_t)1 << steps_bits) < num_steps) steps_bits++;
-    int constr_bits = 0;
-    while (((size_t)1 << constr_bits) < sys.padded) constr_bits++;
+    const int steps_bits = ceil_log2(num_steps);
+    const int constr_bits = ceil_log2(sys.padded);
     std::vector<fe> tau = tr.challenge_vector((size_t)(steps_bits + constr_bits)), rs;
     if (!verify_outer_sumcheck(proof.outer, tau, tr, rs)) {
         why = "spartan: outer sumcheck";
@@ -374,10 +348,9 @@ static inline bool verify_spartan(const JoltSpartanProof& proof, const jolt::Sys
     std::vector<fe> rx_constr(outer_r.begin() + steps_bits, outer_r.end());
     fe rlc = tr.challenge_scalar();
     fe claim = Fr::add(proof.outer.claims[0], Fr::add(Fr::mul(rlc, proof.outer.claims[1]), Fr::mul(Fr::mul(rlc, rlc), proof.outer.claims[2])));
-    int inner_rounds = 0;
-    while (((size_t)1 << inner_rounds) < 4 * V) inner_rounds++;
+    const int inner_rounds = ceil_log2(4 * V);
     std::vector<fe> inner_r;
-    if (!spartan_verify_rounds(proof.inner, (size_t)inner_rounds, 2, claim, tr, inner_r) || proof.witness_evals.size() != nvars ||
+    if (!verify_sumcheck_rounds(proof.inner.compressed_polys, (size_t)inner_rounds, 2, claim, tr, inner_r) || proof.witness_evals.size() != nvars ||
         proof.shift_witness_evals.size() != nvars) {
         why = "spartan: inner sumcheck shape";
         return false;
@@ -395,7 +368,7 @@ static inline bool verify_spartan(const JoltSpartanProof& proof, const jolt::Sys
         return false;
     }
     claim = proof.shift_claim;
-    if (!spartan_verify_rounds(proof.shift, (size_t)steps_bits, 2, claim, tr, shift_r)) {
+    if (!verify_sumcheck_rounds(proof.shift.compressed_polys, (size_t)steps_bits, 2, claim, tr, shift_r)) {
         why = "spartan: shift sumcheck shape";
         return false;
     }

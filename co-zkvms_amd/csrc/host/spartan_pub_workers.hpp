@@ -95,7 +95,7 @@ static void spartan_pub_worker_main(cozk_spartan* h, SpartanPubWorker& pw, StarN
     VecH freq_r = vec_window(p0.freq_r, off, Cn), freq_c = vec_window(p0.freq_c, off, Cn);
     VecH dom = vec_window(p0.domain_u32, off, Cn);
     PolyH val_poly[3];
-    for (int i = 0; i < 3; i++) val_poly[i] = plain_poly_from(ctx, val_w[i]);
+    for (int i = 0; i < 3; i++) val_poly[i] = plain_poly(ctx, val_w[i]);
     {
         cozk_vec* wv = nullptr;
         rc_check(cozk_vec_alloc(ctx, Cn, COZK_SCALAR_FR, &wv), ctx, "vec_alloc");

@@ -18,11 +18,6 @@
 
 namespace cozk {
 
-static inline fe eq1(const fe& a, const fe& b) {
-    fe one = Fr::one();
-    fe ab = Fr::mul(a, b);
-    return Fr::add(Fr::sub(Fr::sub(one, a), b), Fr::dbl(ab));
-}
 // eq(r[off .. off+k), bits of w) with r[off] pairing with the MOST significant of the k bits (big-endian)
 static inline fe eq_index_be(const std::vector<fe>& r, size_t off, int k, uint32_t w) {
     fe acc = Fr::one(), one = Fr::one();
@@ -150,24 +145,13 @@ static GrandProductProof coordinate_prove_grand_product_split(StarNetCoordinator
     {
         std::vector<Bytes> msgs = net.receive_responses();
         for (int w = 0; w < tp.W; w++) {
-            std::vector<std::vector<fe>> parts;
-            for (int p = 0; p < tp.np; p++) {
-                Reader rd(msgs[(size_t)w * tp.np + p]);
-                parts.push_back(rd.vec_fr());
-            }
-            std::vector<fe> o = combine_additive(parts);
+            std::vector<fe> o = gather_additive(msgs, (size_t)w * tp.np, (size_t)tp.np);
             proof.outputs.insert(proof.outputs.end(), o.begin(), o.end());
         }
     }
     tr.append_scalars(proof.outputs);
-    std::vector<fe> padded = proof.outputs;
-    while (padded.size() & (padded.size() - 1)) padded.push_back(Fr::zero());
-    int nv = 0;
-    while (((size_t)1 << nv) < padded.size()) nv++;
-    std::vector<fe> r = tr.challenge_vector(nv);
-    std::vector<fe> eqv = eq_evals_host(r);
-    fe claim = Fr::zero();
-    for (size_t i = 0; i < padded.size(); i++) claim = Fr::add(claim, Fr::mul(eqv[i], padded[i]));
+    std::vector<fe> r;
+    fe claim = mle_claim_padded(proof.outputs, tr, r);
     {
         Writer w;
         w.vec_fr(r);
@@ -217,8 +201,7 @@ static GrandProductProof coordinate_prove_grand_product_split(StarNetCoordinator
                 }
         }
         // eq over the worker bits, times the fully bound local eq
-        fe e_loc = Fr::one();
-        for (int i = 0; i < n_loc; i++) e_loc = Fr::mul(e_loc, eq1(r[k + i], c[n_loc - 1 - i]));
+        fe e_loc = eq_eval_rev(std::vector<fe>(r.begin() + k, r.end()), c);
         std::vector<fe> E(tp.W);
         for (int w = 0; w < tp.W; w++) E[w] = Fr::mul(eq_index_be(r, 0, k, (uint32_t)w), e_loc);
         std::vector<fe> extra;
@@ -340,8 +323,7 @@ static void split_reduce_and_prove_worker(SplitEnv& se, std::vector<SplitOpening
     std::vector<fe> coeffs(1, Fr::one());
     for (size_t i = 1; i < acc.size(); i++) coeffs.push_back(Fr::mul(coeffs[i - 1], rho));
     size_t len = cozk_poly_len(acc[0].polynomial.h);
-    int n_loc = 0;
-    while (((size_t)1 << n_loc) < len) n_loc++;
+    const int n_loc = ceil_log2(len);
     std::vector<const cozk_poly*> lp, le;
     for (auto& o : acc) {
         lp.push_back(o.polynomial.h);

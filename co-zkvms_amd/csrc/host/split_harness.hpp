@@ -209,12 +209,7 @@ static int coordinator_main_split(cozk_harness* h, StarNetCoordinator& net, Proo
     int nappend = half < K ? 2 : 1;
     std::vector<fe> batched_claims;
     for (int a = 0; a < nappend; a++) {
-        std::vector<std::vector<fe>> parts;
-        for (Bytes& b : net.receive_responses()) {
-            Reader rd(b);
-            parts.push_back(rd.vec_fr());
-        }
-        std::vector<fe> claims = combine_additive(parts);
+        std::vector<fe> claims = gather_additive(net);
         fe rho = tr.challenge_scalar();
         fe pw = Fr::one(), batched = Fr::zero();
         for (auto& cl : claims) {
@@ -395,16 +390,9 @@ static int coordinator_main_split(cozk_harness* h, StarNetCoordinator& net, Proo
     fe ve = Fr::zero();
     for (int i = 0; i < nappend; i++) ve = Fr::add(ve, Fr::mul(vco[i], vb[i]));
     std::vector<fe> rs;
-    if ((int)proof.reduced.sumcheck_proof.compressed_polys.size() != nv) {
+    if (!verify_sumcheck_rounds(proof.reduced.sumcheck_proof.compressed_polys, (size_t)nv, 2, ve, vt, rs)) {
         why = "reduction sumcheck: wrong number of rounds";
         return 0;
-    }
-    for (auto& comp : proof.reduced.sumcheck_proof.compressed_polys) {
-        std::vector<fe> poly = unipoly_decompress(comp, ve);
-        vt.append_scalars(comp);
-        fe r_j = vt.challenge_scalar();
-        rs.push_back(r_j);
-        ve = unipoly_eval(poly, r_j);
     }
     // variable order of the split sumcheck: rounds 0..n_loc-1 bind the local bits (HighToLow), then the worker bits
     std::vector<fe> vpoint(rs.begin() + n_loc, rs.end());

@@ -329,6 +329,41 @@ static inline std::vector<fe> unipoly_decompress(const std::vector<fe>& comp, co
     for (size_t i = 1; i < comp.size(); i++) o.push_back(comp[i]);
     return o;
 }
+// Verifier replay of a sumcheck in compressed form: per round decompress against the running claim, append the compressed
+// poly, draw r_j, evaluate.  False unless there are exactly `rounds` polys of `degree` coefficients each; `claim` ends as
+// the last round's g(r), `rs` as the challenges in round order.
+static inline bool verify_sumcheck_rounds(const std::vector<std::vector<fe>>& compressed_polys, size_t rounds, size_t degree, fe& claim,
+                                          Transcript& tr, std::vector<fe>& rs) {
+    if (compressed_polys.size() != rounds) return false;
+    rs.clear();
+    for (const auto& comp : compressed_polys) {
+        if (comp.size() != degree) return false;
+        std::vector<fe> poly = unipoly_decompress(comp, claim);
+        tr.append_scalars(comp);
+        fe r_j = tr.challenge_scalar();
+        rs.push_back(r_j);
+        claim = unipoly_eval(poly, r_j);
+    }
+    return true;
+}
+// eq(a, b) = prod_i (a_i b_i + (1 - a_i)(1 - b_i)) = prod_i (1 - a_i - b_i + 2 a_i b_i) over the first a.size() entries of b
+static inline fe eq_term(const fe& a, const fe& b) { return Fr::add(Fr::sub(Fr::sub(Fr::one(), a), b), Fr::dbl(Fr::mul(a, b))); }
+static inline fe eq_eval(const std::vector<fe>& a, const std::vector<fe>& b) {
+    fe acc = Fr::one();
+    for (size_t i = 0; i < a.size(); i++) acc = Fr::mul(acc, eq_term(a[i], b[i]));
+    return acc;
+}
+// eq(a, reverse(b)): a point against challenges bound in the opposite variable order
+static inline fe eq_eval_rev(const std::vector<fe>& a, const std::vector<fe>& b) {
+    fe acc = Fr::one();
+    for (size_t i = 0; i < a.size(); i++) acc = Fr::mul(acc, eq_term(a[i], b[b.size() - 1 - i]));
+    return acc;
+}
+static inline int ceil_log2(size_t n) {
+    int k = 0;
+    while (((size_t)1 << k) < n) k++;
+    return k;
+}
 // EqPolynomial::evals(r) on the host (big-endian)
 static inline std::vector<fe> eq_evals_host(const std::vector<fe>& r) {
     std::vector<fe> ev(1, Fr::one());
@@ -342,6 +377,15 @@ static inline std::vector<fe> eq_evals_host(const std::vector<fe>& r) {
         ev.swap(nx);
     }
     return ev;
+}
+// DensePolynomial::new_padded(outputs).evaluate(r) at a freshly drawn r: the outputs zero-padded to a power of two 2^nv, r =
+// nv challenges, claim = sum_i eq(r, i) padded[i]
+static inline fe mle_claim_padded(const std::vector<fe>& outputs, Transcript& tr, std::vector<fe>& r_out) {
+    r_out = tr.challenge_vector((size_t)ceil_log2(outputs.size()));
+    std::vector<fe> eq = eq_evals_host(r_out);
+    fe claim = Fr::zero();
+    for (size_t i = 0; i < outputs.size(); i++) claim = Fr::add(claim, Fr::mul(eq[i], outputs[i]));
+    return claim;
 }
 // additive::combine_additive_vec (mpc-core/src/protocols/additive.rs:103-114)
 static inline std::vector<fe> combine_additive(const std::vector<std::vector<fe>>& parts) {

@@ -396,4 +396,53 @@ int prims_transcript(const uint8_t* script, size_t len, uint32_t* out, size_t ma
     return nout;
 }
 
+// verify_sumcheck_rounds on a fresh Transcript("cozk"): n_polys compressed polys, poly k holding lens[k] Montgomery Fr coefficients,
+// concatenated in `coeffs`; `claim` in and out; the challenges drawn go to rs_out (room for n_polys of them) and one more challenge,
+// drawn after the replay, to next_out (the transcript's state).  Returns 1 when the replay accepts the shape, 0 when not.
+int prims_verify_sumcheck_rounds(const uint32_t* coeffs, const size_t* lens, size_t n_polys, size_t rounds, size_t degree, uint32_t claim[8],
+                                 uint32_t* rs_out, uint32_t next_out[8]) {
+    std::vector<std::vector<fe>> polys(n_polys);
+    for (size_t k = 0; k < n_polys; k++) {
+        polys[k].resize(lens[k]);
+        for (auto& x : polys[k]) {
+            memcpy(x.l, coeffs, 32);
+            coeffs += 8;
+        }
+    }
+    cozk::Transcript t;
+    fe c;
+    memcpy(c.l, claim, 32);
+    std::vector<fe> rs;
+    const bool ok = cozk::verify_sumcheck_rounds(polys, rounds, degree, c, t, rs);
+    memcpy(claim, c.l, 32);
+    for (size_t j = 0; j < rs.size(); j++) memcpy(rs_out + 8 * j, rs[j].l, 32);
+    const fe nx = t.challenge_scalar();
+    memcpy(next_out, nx.l, 32);
+    return ok ? 1 : 0;
+}
+
+// eq_eval(a, b) (rev == 0) or eq_eval_rev(a, b) of n Montgomery Fr values each
+void prims_eq_eval(const uint32_t* a, const uint32_t* b, size_t n, int rev, uint32_t out[8]) {
+    std::vector<fe> va(n), vb(n);
+    for (size_t i = 0; i < n; i++) {
+        memcpy(va[i].l, a + 8 * i, 32);
+        memcpy(vb[i].l, b + 8 * i, 32);
+    }
+    const fe e = rev ? cozk::eq_eval_rev(va, vb) : cozk::eq_eval(va, vb);
+    memcpy(out, e.l, 32);
+}
+
+// mle_claim_padded of n Montgomery Fr outputs on a fresh Transcript("cozk"): the claim to claim_out, the point drawn to r_out.
+// Returns the point's length, or -1 when it exceeds max_r.
+int prims_mle_claim_padded(const uint32_t* outputs, size_t n, uint32_t claim_out[8], uint32_t* r_out, size_t max_r) {
+    std::vector<fe> v(n), r;
+    for (size_t i = 0; i < n; i++) memcpy(v[i].l, outputs + 8 * i, 32);
+    cozk::Transcript t;
+    const fe claim = cozk::mle_claim_padded(v, t, r);
+    if (r.size() > max_r) return -1;
+    memcpy(claim_out, claim.l, 32);
+    for (size_t j = 0; j < r.size(); j++) memcpy(r_out + 8 * j, r[j].l, 32);
+    return (int)r.size();
+}
+
 }  // extern "C"

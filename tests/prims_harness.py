@@ -45,6 +45,10 @@ def lib():
         L.prims_sha256.argtypes = [vp, vp, sz, vp]
         L.prims_sha256.restype = None
         L.prims_transcript.argtypes = [vp, sz, vp, sz]
+        L.prims_verify_sumcheck_rounds.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp]
+        L.prims_eq_eval.argtypes = [vp, vp, sz, i, vp]
+        L.prims_eq_eval.restype = None
+        L.prims_mle_claim_padded.argtypes = [vp, sz, vp, vp, sz]
         _lib = L
     return _lib
 
@@ -265,6 +269,45 @@ def sha_leg():
         assert got == want, "transcript challenges differ from pyref.Transcript"
         nch += len(want)
     return {"shani": L.prims_sha_uses_shani(), "messages": nmsg, "challenges": nch}
+
+
+# ------------------------------------------------------------------------------------------------ host protocol helpers
+def _fr_mont(xs):
+    """canonical Fr values -> uint32[max(1, n), 8] Montgomery limbs"""
+    return to_limbs([x * MONT % O.R for x in xs] or [0])
+
+
+def _fr_canon(a):
+    ri = pow(MONT, -1, O.R)
+    return [v * ri % O.R for v in from_limbs(a)]
+
+
+def verify_sumcheck_rounds(polys, rounds, degree, claim):
+    """wire.hpp's verify_sumcheck_rounds on a fresh transcript -> (accepted, challenges, final claim, next challenge)"""
+    flat = _fr_mont([c for p in polys for c in p])
+    lens = np.array([len(p) for p in polys] or [0], dtype=np.uint64)
+    cl = _fr_mont([claim])
+    rs = np.zeros((max(1, len(polys)), 8), dtype=np.uint32)
+    nxt = np.zeros((1, 8), dtype=np.uint32)
+    ok = lib().prims_verify_sumcheck_rounds(_ptr(flat), _ptr(lens), len(polys), rounds, degree, _ptr(cl), _ptr(rs), _ptr(nxt))
+    return bool(ok), _fr_canon(rs), _fr_canon(cl)[0], _fr_canon(nxt)[0]
+
+
+def eq_eval(a, b, rev=False):
+    out = np.zeros((1, 8), dtype=np.uint32)
+    A, B = _fr_mont(a), _fr_mont(b)
+    lib().prims_eq_eval(_ptr(A), _ptr(B), len(a), 1 if rev else 0, _ptr(out))
+    return _fr_canon(out)[0]
+
+
+def mle_claim_padded(outputs):
+    """wire.hpp's mle_claim_padded on a fresh transcript -> (claim, point)"""
+    V = _fr_mont(outputs)
+    cl = np.zeros((1, 8), dtype=np.uint32)
+    r = np.zeros((64, 8), dtype=np.uint32)
+    n = lib().prims_mle_claim_padded(_ptr(V), len(outputs), _ptr(cl), _ptr(r), 64)
+    assert n >= 0
+    return _fr_canon(cl)[0], _fr_canon(r[:n]) if n else []
 
 
 if __name__ == "__main__":
