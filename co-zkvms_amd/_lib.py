@@ -129,6 +129,9 @@ SIGNATURES = {
     "cozk_shamir_scatter": (_i, [_vp, _vp, ctypes.c_char_p, _i, _i, _u64, _vp, _vp]),
     "cozk_shamir_lagrange": (_i, [_vp, _sz, _vp]),
     "cozk_shamir_combine_vec": (_i, [_vp, _vp, _vp, _sz, _i, _pp]),
+    "cozk_shamir_mul_deal": (_i, [_vp, _vp, _vp, ctypes.c_char_p, _i, _i, _u64, _vp]),
+    "cozk_shamir_mul_inproc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _u64, _vp]),
+    "cozk_shamir_mul_vec": (_i, [_vp, _vp, _vp, ctypes.c_char_p, _i, _u64, _pp]),
     "cozk_shamir_combine_points": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, ctypes.POINTER(_i)]),
     "cozk_layer_round": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "cozk_fingerprint_leaves": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _i, _i, _vp, _vp, _sz, _sz]),
@@ -152,6 +155,7 @@ SIGNATURES = {
     "cozk_ring_info": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_u64)]),
     "cozk_reshare": (_i, [_vp, _vp, _vp]),
     "cozk_rep3_mul_vec": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.c_char_p, ctypes.c_char_p, _u64, _pp, _pp]),
+    "cozk_ring_all_to_all": (_i, [_vp, _vp, _vp]),
     "cozk_ring_net_native": (_i, [_vp, _vp]),
     "cozk_wire_g1_encode": (_i, [_vp, _i, _vp]),
     "cozk_wire_g1_decode": (_i, [_vp, _vp, ctypes.POINTER(_i)]),

@@ -179,6 +179,41 @@ int cozk_reshare(cozk_ctx* ctx, const cozk_vec* send, cozk_vec* recv) {
     });
 }
 
+// every rank to every rank in one group: what the n-party resharing of cozk_shamir_mul_vec exchanges.  The own rank goes
+// through ncclSend / ncclRecv like any other, so a single-rank ring runs the real path (as ring_exchange does).
+int cozk_ring_all_to_all(cozk_ctx* ctx, const cozk_vec* const* send, cozk_vec* const* recv) {
+    return cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && send && recv, "ring_all_to_all: null argument");
+        COZK_REQUIRE(ctx->ring_comm, "ring_all_to_all: cozk_ring_init has not been called on this context");
+        const int n = ctx->ring_n, self = ctx->ring_rank;
+        size_t calls = 0;
+        for (int r = 0; r < n; r++) {
+            COZK_REQUIRE((!send[r] || send[r]->kind == COZK_SCALAR_FR) && (!recv[r] || recv[r]->kind == COZK_SCALAR_FR), "ring_all_to_all: entries must be FR vectors or NULL");
+            calls += (send[r] && send[r]->n) + (recv[r] && recv[r]->n);
+        }
+        COZK_REQUIRE(!send[self] == !recv[self] && (!send[self] || (send[self]->n == recv[self]->n && (send[self]->d != recv[self]->d || !send[self]->n))),
+                     "ring_all_to_all: the own rank's send / recv must be distinct vectors of one length, or both NULL");
+        if (!calls) return;
+        RcclApi& a = rccl_or_throw();
+        ncclComm_t comm = (ncclComm_t)ctx->ring_comm;
+        RCCL_TRY(a, a.GroupStart());
+        ncclResult_t res = ncclSuccess;
+        uint64_t sent = 0;
+        for (int r = 0; r < n && res == ncclSuccess; r++) {
+            if (send[r] && send[r]->n) {
+                res = a.Send(send[r]->d, send[r]->n * sizeof(fe), ncclUint8, r, comm, ctx->stream);
+                sent += send[r]->n * sizeof(fe);
+            }
+            if (recv[r] && recv[r]->n && res == ncclSuccess) res = a.Recv(recv[r]->d, recv[r]->n * sizeof(fe), ncclUint8, r, comm, ctx->stream);
+        }
+        ncclResult_t rg = a.GroupEnd();
+        if (res != ncclSuccess) throw CozkError(COZK_ERR_INTERNAL, std::string("ring_all_to_all: ncclSend/ncclRecv failed: ") + a.GetErrorString(res));
+        if (rg != ncclSuccess) throw CozkError(COZK_ERR_INTERNAL, std::string("ring_all_to_all: ncclGroupEnd failed: ") + a.GetErrorString(rg));
+        (void)hipGetLastError();  // (see ring_exchange)
+        ctx->ring_bytes += sent;
+    });
+}
+
 int cozk_rep3_mul_vec(cozk_ctx* ctx, const cozk_vec* xa, const cozk_vec* xb, const cozk_vec* ya, const cozk_vec* yb, const uint8_t* key_self,
                       const uint8_t* key_prev, uint64_t counter, cozk_vec** out_a, cozk_vec** out_b) {
     if (!out_a || !out_b) return COZK_ERR_INVALID_ARG;

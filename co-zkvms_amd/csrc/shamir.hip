@@ -6,6 +6,8 @@
 
 #include <string.h>
 
+#include <vector>
+
 // ------------------------------------------------------------------ the small-multiplier Horner step
 // a * p + c mod r for canonical Montgomery residues a, c and a PLAIN integer p <= 32 (the evaluation point of party p):
 // the Montgomery residue of x * p is (x R) * p, so no Montgomery product is needed -- 8 multiply-adds give the 9-word value
@@ -44,7 +46,8 @@ static __device__ __forceinline__ fe fr_mul_small_add(const fe& a, uint32_t p, c
 // ------------------------------------------------------------------ share / eval: all parties in one pass
 // shares[p][i] = f_i(p + 1), f_i(x) = v[i] + sum_{c = 1..degree} coef_c[i] x^c (shamir.rs:190-207 `share`, :166-175
 // `evaluate_poly`).  A lane owns element i: it obtains its `degree` coefficients once (PRF blocks, or loads), keeps them
-// in registers, runs one Horner chain per party and stores n field elements: 32 B read and n * 32 B written per element.
+// in registers, runs one Horner chain per party and stores n field elements: 32 B read and n * 32 B written per element
+// (64 B read where the secret is the product of two share vectors, ShamirMulPrfSrc: the re-deal of a multiplication).
 // prf_fr (prf.hip.hpp) with the two halves of the block read through constant indices: the same value, and fifteen inlined
 // copies of it keep their block words in registers
 static __device__ __forceinline__ fe shamir_prf_fr(const prf_key key, uint64_t j) {
@@ -70,8 +73,7 @@ static __device__ __forceinline__ fe shamir_prf_fr(const prf_key key, uint64_t j
 struct ShamirOut {
     fe* p[COZK_SHAMIR_MAX_PARTIES];
 };
-struct ShamirPrfSrc {  // coef_c[i] = PRF(keys[c - 1], counter + i)
-    const fe* v;
+struct ShamirPrfCoefs {  // coef_c[i] = PRF(keys[c - 1], counter + i)
     uint64_t counter;
     prf_key keys[COZK_SHAMIR_MAX_DEGREE];
     __device__ __forceinline__ fe coef(int c, size_t i) const {
@@ -81,10 +83,19 @@ struct ShamirPrfSrc {  // coef_c[i] = PRF(keys[c - 1], counter + i)
         return shamir_prf_fr(key, counter + i);
     }
 };
+struct ShamirPrfSrc : ShamirPrfCoefs {  // a secret vector, PRF coefficients
+    const fe* v;
+    __device__ __forceinline__ fe value(size_t i) const { return fe_load(v + i); }
+};
+struct ShamirMulPrfSrc : ShamirPrfCoefs {  // the secret is the product a[i] b[i] of two share vectors, never stored (GRR re-deal)
+    const fe *a, *b;
+    __device__ __forceinline__ fe value(size_t i) const { return Fr::mul(fe_load(a + i), fe_load(b + i)); }
+};
 struct ShamirVecSrc {  // the caller's coefficient vectors
     const fe* v;
     const fe* c[COZK_SHAMIR_MAX_DEGREE];
     __device__ __forceinline__ fe coef(int k, size_t i) const { return fe_load(c[k] + i); }
+    __device__ __forceinline__ fe value(size_t i) const { return fe_load(v + i); }
 };
 
 // DEG = 1..7: the degree at compile time, c[k] = coefficient k + 1.  DEG = 0: degree 8..15 at run time; the coefficients are
@@ -112,7 +123,7 @@ __global__ void __launch_bounds__(256) k_shamir_share(Src src, ShamirOut out, si
             c[0] = next;
         }
     }
-    const fe v = fe_load(src.v + i);
+    const fe v = src.value(i);
 #pragma unroll 1  // one Horner chain at a time: the coefficients, not several parties' accumulators, own the registers
     for (int p = 1; p <= num_parties; p++) {
         fe acc = c[0];
@@ -210,6 +221,17 @@ static void require_share_args(const char* who, int degree, int num_parties) {
     COZK_REQUIRE(num_parties > degree && num_parties <= COZK_SHAMIR_MAX_PARTIES, w + ": degree < num_parties <= COZK_SHAMIR_MAX_PARTIES");
 }
 
+static void require_mul_args(const char* who, int degree, int num_parties) {
+    require_share_args(who, degree, num_parties);
+    COZK_REQUIRE(2 * degree + 1 <= num_parties, std::string(who) + ": 2 * degree + 1 <= num_parties (that many parties re-deal the product)");
+}
+
+static void require_factors(const char* who, const cozk_vec* a, const cozk_vec* b) {
+    const std::string w(who);
+    COZK_REQUIRE(a->kind == COZK_SCALAR_FR && b->kind == COZK_SCALAR_FR, w + ": the factors must be FR vectors");
+    COZK_REQUIRE(a->n == b->n, w + ": the factors must have one length");
+}
+
 static void free_all(cozk_vec** out, int n) {
     for (int p = 0; p < n; p++) {
         cozk_vec_free(out[p]);
@@ -235,12 +257,23 @@ static void clear_outputs(cozk_vec** out, int num_parties) {
         for (int p = 0; p < num_parties; p++) out[p] = nullptr;
 }
 
-static ShamirPrfSrc prf_src(const cozk_vec* v, const uint8_t* keys, int degree, uint64_t counter) {
-    ShamirPrfSrc src;
+template <class Src>
+static void fill_prf_coefs(Src& src, const uint8_t* keys, int degree, uint64_t counter) {
     memset(&src, 0, sizeof src);
-    src.v = (const fe*)v->d;
     src.counter = counter;
     for (int c = 0; c < degree; c++) src.keys[c] = prf_key_from_bytes(keys + (size_t)COZK_PRF_KEY_BYTES * c);
+}
+static ShamirPrfSrc prf_src(const cozk_vec* v, const uint8_t* keys, int degree, uint64_t counter) {
+    ShamirPrfSrc src;
+    fill_prf_coefs(src, keys, degree, counter);
+    src.v = (const fe*)v->d;
+    return src;
+}
+static ShamirMulPrfSrc mul_prf_src(const cozk_vec* a, const cozk_vec* b, const uint8_t* keys, int degree, uint64_t counter) {
+    ShamirMulPrfSrc src;
+    fill_prf_coefs(src, keys, degree, counter);
+    src.a = (const fe*)a->d;
+    src.b = (const fe*)b->d;
     return src;
 }
 
@@ -409,6 +442,153 @@ int cozk_shamir_combine_points(cozk_ctx* ctx, const uint64_t* xy, const int* inf
         if (rc != COZK_OK) return rc;
     }
     return cozk_g1_sum(ctx, scaled, scaled_inf, (size_t)degree + 1, out_xy, out_infinity);
+}
+
+// ------------------------------------------------------------------ multiplication with degree reduction (GRR / BGW resharing)
+// c = a b as a degree-t sharing again: the dealers, parties 0..2t, each re-deal their local product a_p b_p with degree t
+// (one k_shamir_share<.., ShamirMulPrfSrc> launch), every party receives one vector from every dealer, and party q's result is
+// sum_p lambda_p h_{p -> q}, lambda = lagrange(1..2t + 1) -- which is cozk_shamir_combine_vec of the received vectors with
+// degree 2t.  The reference has no such step (no Shamir network at all); tests/shamir_mul_ref.py restates it.
+int cozk_shamir_mul_deal(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, const uint8_t* keys, int degree, int num_parties,
+                         uint64_t counter, cozk_vec** out) {
+    if (int rc0 = require_out(ctx, out, "shamir_mul_deal: null output")) return rc0;
+    clear_outputs(out, num_parties);
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && a && b && keys, "shamir_mul_deal: null argument");
+        require_factors("shamir_mul_deal", a, b);
+        require_mul_args("shamir_mul_deal", degree, num_parties);
+    });
+    if (rc != COZK_OK) return rc;
+    rc = alloc_outputs(ctx, nullptr, a->n, num_parties, out);
+    if (rc != COZK_OK) return rc;
+    rc = cozk_guard(ctx, [&] {
+        if (a->n == 0) return;
+        launch_share(ctx->stream, mul_prf_src(a, b, keys, degree, counter), out_table(out, num_parties), a->n, degree, num_parties);
+    });
+    if (rc != COZK_OK) free_all(out, num_parties);
+    return rc;
+}
+
+int cozk_shamir_mul_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* a, const cozk_vec* const* b, const uint8_t* const* keys,
+                           int degree, int num_parties, uint64_t counter, cozk_vec** out) {
+    cozk_ctx* const c0 = party_ctxs && num_parties >= 1 ? party_ctxs[0] : nullptr;  // receives the error message
+    if (int rc0 = require_out(c0, out, "shamir_mul_inproc: null output")) return rc0;
+    clear_outputs(out, num_parties);
+    const int dealers = 2 * degree + 1;
+    int rc = cozk_guard(c0, [&] {
+        COZK_REQUIRE(party_ctxs && a && b && keys, "shamir_mul_inproc: null argument");
+        require_mul_args("shamir_mul_inproc", degree, num_parties);
+        for (int p = 0; p < num_parties; p++) COZK_REQUIRE(party_ctxs[p], "shamir_mul_inproc: null party context");
+        for (int p = 0; p < dealers; p++) {
+            COZK_REQUIRE(a[p] && b[p], "shamir_mul_inproc: parties 0..2 * degree need both factors");
+            require_factors("shamir_mul_inproc", a[p], b[p]);
+            COZK_REQUIRE(a[p]->n == a[0]->n, "shamir_mul_inproc: the factors must have one length");
+            COZK_REQUIRE(a[p]->ctx == party_ctxs[p] && b[p]->ctx == party_ctxs[p], "shamir_mul_inproc: party p's factors must be vectors of party_ctxs[p]");
+            COZK_REQUIRE(keys[p], "shamir_mul_inproc: parties 0..2 * degree need their key block");
+        }
+    });
+    if (rc != COZK_OK) return rc;
+    const size_t n = a[0]->n;
+    std::vector<cozk_vec*> recv((size_t)num_parties * dealers, nullptr);  // recv[q * dealers + p] = h_{p -> q}, a block of party q
+    std::vector<fe*> stage(dealers, nullptr);
+    // a failure of party p's step leaves its text with party 0 and nothing allocated
+    auto fail = [&](int code, int p) {
+        if (party_ctxs[p] != c0) c0->last_error = party_ctxs[p]->last_error;
+        for (int q = 0; q < num_parties; q++) (void)hipStreamSynchronize(party_ctxs[q]->stream);
+        for (int d = 0; d < dealers; d++) ctx_dev_free(party_ctxs[d], stage[d]);
+        for (cozk_vec* v : recv) cozk_vec_free(v);
+        free_all(out, num_parties);
+        return code;
+    };
+    for (int q = 0; q < num_parties; q++)
+        for (int p = 0; p < dealers; p++)
+            if ((rc = cozk_vec_alloc(party_ctxs[q], n, COZK_SCALAR_FR, &recv[(size_t)q * dealers + p])) != COZK_OK) return fail(rc, q);
+    if (n) {
+        // the receive blocks are ordered by their owners' streams only (see cozk_shamir_scatter): every party's stream drains
+        // before any dealer's stream writes into another party's block
+        rc = cozk_guard(c0, [&] {
+            for (int q = 0; q < num_parties; q++) HIP_TRY(hipStreamSynchronize(party_ctxs[q]->stream));
+        });
+        if (rc != COZK_OK) return fail(rc, 0);
+        for (int p = 0; p < dealers; p++) {
+            cozk_ctx* dealer = party_ctxs[p];
+            rc = cozk_guard(dealer, [&] {
+                size_t remote = 0;
+                for (int q = 0; q < num_parties; q++) remote += party_ctxs[q]->device != dealer->device;
+                if (remote) stage[p] = (fe*)ctx_dev_alloc(dealer, remote * n * sizeof(fe));
+                ShamirOut o;
+                memset(&o, 0, sizeof o);
+                size_t r = 0;
+                for (int q = 0; q < num_parties; q++)
+                    o.p[q] = party_ctxs[q]->device != dealer->device ? stage[p] + n * r++ : (fe*)recv[(size_t)q * dealers + p]->d;
+                launch_share(dealer->stream, mul_prf_src(a[p], b[p], keys[p], degree, counter), o, n, degree, num_parties);
+                for (int q = 0; q < num_parties; q++)
+                    if (party_ctxs[q]->device != dealer->device)
+                        HIP_TRY(hipMemcpyPeerAsync(recv[(size_t)q * dealers + p]->d, party_ctxs[q]->device, o.p[q], dealer->device, n * sizeof(fe),
+                                                   dealer->stream));
+            });
+            if (rc != COZK_OK) return fail(rc, p);
+        }
+        for (int p = 0; p < dealers; p++) {  // the parties' streams may read what they received once the dealers' have drained
+            rc = cozk_guard(party_ctxs[p], [&] {
+                HIP_TRY(hipStreamSynchronize(party_ctxs[p]->stream));
+                ctx_dev_free(party_ctxs[p], stage[p]);
+                stage[p] = nullptr;
+            });
+            if (rc != COZK_OK) return fail(rc, p);
+        }
+    }
+    uint32_t points[COZK_SHAMIR_MAX_PARTIES];
+    for (int p = 0; p < dealers; p++) points[p] = (uint32_t)p + 1;
+    for (int q = 0; q < num_parties; q++) {  // the finish, on each party's own stream; its pool takes the blocks back behind it
+        rc = cozk_shamir_combine_vec(party_ctxs[q], &recv[(size_t)q * dealers], points, (size_t)dealers, 2 * degree, &out[q]);
+        if (rc != COZK_OK) return fail(rc, q);
+        for (int p = 0; p < dealers; p++) {
+            cozk_vec_free(recv[(size_t)q * dealers + p]);
+            recv[(size_t)q * dealers + p] = nullptr;
+        }
+    }
+    return COZK_OK;
+}
+
+int cozk_shamir_mul_vec(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, const uint8_t* keys, int degree, uint64_t counter, cozk_vec** out) {
+    if (int rc0 = require_out(ctx, out, "shamir_mul_vec: null output")) return rc0;
+    *out = nullptr;
+    bool dealer = false;
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && a, "shamir_mul_vec: null argument");
+        COZK_REQUIRE(a->kind == COZK_SCALAR_FR, "shamir_mul_vec: the factors must be FR vectors");
+        COZK_REQUIRE(ctx->ring_comm, "shamir_mul_vec: cozk_ring_init has not been called on this context");
+        require_mul_args("shamir_mul_vec (num_parties = ranks of the ring)", degree, ctx->ring_n);
+        dealer = ctx->ring_rank <= 2 * degree;
+        if (dealer) {
+            COZK_REQUIRE(b && keys, "shamir_mul_vec: null argument");
+            require_factors("shamir_mul_vec", a, b);
+        }
+    });
+    if (rc != COZK_OK) return rc;
+    const int num_parties = ctx->ring_n, dealers = 2 * degree + 1, self = ctx->ring_rank;
+    cozk_vec *dealt[COZK_SHAMIR_MAX_PARTIES] = {}, *recv[COZK_SHAMIR_MAX_PARTIES] = {};
+    const cozk_vec *send[COZK_SHAMIR_MAX_PARTIES] = {}, *shares[COZK_SHAMIR_MAX_PARTIES] = {};
+    uint32_t points[COZK_SHAMIR_MAX_PARTIES];
+    if (dealer) rc = cozk_shamir_mul_deal(ctx, a, b, keys, degree, num_parties, counter, dealt);
+    for (int p = 0; p < dealers && rc == COZK_OK; p++)
+        if (p != self) rc = cozk_vec_alloc(ctx, a->n, COZK_SCALAR_FR, &recv[p]);
+    if (rc == COZK_OK) {
+        for (int q = 0; q < num_parties; q++) send[q] = dealer && q != self ? dealt[q] : nullptr;  // the own slot stays local
+        rc = cozk_ring_all_to_all(ctx, send, recv);
+    }
+    if (rc == COZK_OK) {
+        for (int p = 0; p < dealers; p++) {
+            shares[p] = p == self ? dealt[p] : recv[p];
+            points[p] = (uint32_t)p + 1;
+        }
+        rc = cozk_shamir_combine_vec(ctx, shares, points, (size_t)dealers, 2 * degree, out);
+    }
+    // everything above is enqueued on the context's stream, and so is whatever reuses these blocks
+    free_all(dealt, num_parties);
+    free_all(recv, num_parties);
+    return rc;
 }
 
 int cozk_vec_add_scalar(cozk_ctx* ctx, cozk_vec* v, const uint64_t s[4]) {

@@ -143,6 +143,25 @@ class Context:
                                              ctypes.byref(a), ctypes.byref(b)))
         return Vec(self, a, L.SCALAR_FR), Vec(self, b, L.SCALAR_FR)
 
+    def all_to_all(self, send, recv_lens=None):
+        """every rank to every rank on the context's ring (cozk_ring_all_to_all): send[r] goes to rank r (None: nothing),
+        the returned list holds what rank r sent here.  recv_lens[r] = the length expected from rank r (None: nothing);
+        by default the pattern of `send` mirrored"""
+        if recv_lens is None:
+            recv_lens = [None if v is None else len(v) for v in send]
+        recv = [None if n is None else Vec.alloc(self, n, L.SCALAR_FR) for n in recv_lens]
+        ptrs = lambda vs: (ctypes.c_void_p * max(len(vs), 1))(*[None if v is None else v.h for v in vs])
+        self.check(self._l.cozk_ring_all_to_all(self.h, ptrs(send), ptrs(recv)))
+        return recv
+
+    def shamir_mul_vec(self, a, b, keys, degree, counter=0):
+        """this party's share of a x b as a degree-`degree` sharing again, one party per process over the context's ring
+        (cozk_shamir_mul_vec): party = ring rank, parties = ring size; b and keys may be None on a party > 2 * degree"""
+        h = ctypes.c_void_p()
+        self.check(self._l.cozk_shamir_mul_vec(self.h, a.h, None if b is None else b.h, None if keys is None else _shamir_keys(keys),
+                                               degree, counter, ctypes.byref(h)))
+        return Vec(self, h, L.SCALAR_FR)
+
     def close(self):
         if self.h:
             self._l.cozk_ctx_destroy(self.h)
@@ -312,6 +331,13 @@ class Vec:
         self.ctx.check(self.ctx._l.cozk_shamir_scatter(self.ctx.h, self.h, _shamir_keys(keys), degree, n, counter, ctxs, out))
         return [Vec(party_ctxs[p], ctypes.c_void_p(out[p]), L.SCALAR_FR) for p in range(n)]
 
+    def shamir_mul_deal(self, other, keys, degree, num_parties, counter=0):
+        """a dealer's step of the multiplication with degree reduction (cozk_shamir_mul_deal): the num_parties share vectors
+        of a fresh degree-`degree` sharing of self[i] * other[i], in one launch; keys = this party's `degree` private keys"""
+        out = (ctypes.c_void_p * max(num_parties, 1))()
+        self.ctx.check(self.ctx._l.cozk_shamir_mul_deal(self.ctx.h, self.h, other.h, _shamir_keys(keys), degree, num_parties, counter, out))
+        return [Vec(self.ctx, ctypes.c_void_p(out[p]), L.SCALAR_FR) for p in range(num_parties)]
+
     def free(self):
         if self.h:
             self.ctx._l.cozk_vec_free(self.h)
@@ -360,6 +386,22 @@ def shamir_combine(shares, points, degree):
     h = ctypes.c_void_p()
     ctx.check(ctx._l.cozk_shamir_combine_vec(ctx.h, arr, pts.ctypes.data, len(shares), degree, ctypes.byref(h)))
     return Vec(ctx, h, L.SCALAR_FR)
+
+
+def shamir_mul(party_ctxs, a_shares, b_shares, keys_per_party, degree, counter=0):
+    """share x share -> a degree-`degree` sharing of the product, all parties in this process (cozk_shamir_mul_inproc):
+    party p owns party_ctxs[p], a_shares[p], b_shares[p] and its `degree` keys keys_per_party[p]; for p > 2 * degree the
+    three may be None.  Returns one vector per party, owned by that party's context"""
+    n = len(party_ctxs)
+    arr = lambda hs: (ctypes.c_void_p * max(n, 1))(*hs)
+    ctxs = arr([c.h for c in party_ctxs])
+    a = arr([None if v is None else v.h for v in a_shares])
+    b = arr([None if v is None else v.h for v in b_shares])
+    blocks = [None if k is None else ctypes.create_string_buffer(_shamir_keys(k), max(32 * len(k), 1)) for k in keys_per_party]
+    keys = arr([None if k is None else ctypes.addressof(k) for k in blocks])
+    out = (ctypes.c_void_p * max(n, 1))()
+    party_ctxs[0].check(party_ctxs[0]._l.cozk_shamir_mul_inproc(ctxs, a, b, keys, degree, n, counter, out))
+    return [Vec(party_ctxs[p], ctypes.c_void_p(out[p]), L.SCALAR_FR) for p in range(n)]
 
 
 def shamir_combine_points(ctx, points_g1, points, degree):

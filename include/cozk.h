@@ -138,7 +138,10 @@ int cozk_vec_add_scalar(cozk_ctx* ctx, cozk_vec* v, const uint64_t s[4]);
  * shamir/arithmetic/ops.rs need no entry points of their own: share +- share and share x share (element-wise; "result has
  * higher degree than the inputs", ops.rs:93-118) are cozk_vec_binop, share x public is cozk_vec_scale, negation is
  * cozk_vec_scale by -1, share + public is cozk_vec_add_scalar; a party's commitment of its share vector is cozk_msm_vec.
- * There is no Shamir network, degree reduction or prover in the reference, and none here. */
+ * The element-wise product of two degree-t sharings has degree 2t and can only be opened (from 2t + 1 parties); a product
+ * that is a degree-t sharing again, so that products chain, is cozk_shamir_mul_{deal, inproc, vec} below.  The reference has
+ * no Shamir network, degree reduction or prover; the multiplication here is the classic one-round resharing (GRR / BGW),
+ * restated in tests/shamir_mul_ref.py; there is no Shamir prover. */
 #define COZK_SHAMIR_MAX_PARTIES 32
 #define COZK_SHAMIR_MAX_DEGREE 15 /* of a dealt sharing: 2t + 1 <= 32 parties can still open a product */
 /* share_field_elements (mpc-types/src/protocols/shamir.rs:58-77; `share` :190-207): out[p][i] = f_i(p + 1) with
@@ -171,6 +174,38 @@ int cozk_shamir_combine_vec(cozk_ctx* ctx, const cozk_vec* const* shares, const 
  * behind cozk_g1_mul / cozk_g1_sum); ctx only receives the error message and may be NULL. */
 int cozk_shamir_combine_points(cozk_ctx* ctx, const uint64_t* xy, const int* infinity, const uint32_t* points, size_t k,
                                int degree, uint64_t out_xy[8], int* out_infinity);
+
+/* Shamir multiplication with degree reduction, one round of resharing.  Parties 0..2t (t = degree; the first 2t + 1
+ * evaluation points, the convention of combine_field_elements) are the DEALERS: dealer p re-deals its local product
+ *   h_{p -> q}[i] = a_p[i] b_p[i] + sum_{c=1..t} PRF(keys_p[c-1], counter + i) (q + 1)^c,   q = 0..n-1,
+ * every party q receives h_{p -> q} from every dealer (its own slot stays local) and finishes with
+ *   c_q[i] = sum_{p=0..2t} lambda_p h_{p -> q}[i],   lambda = lagrange(1..2t + 1):
+ * c is a degree-t sharing of a b.  Traffic: a dealer sends (n - 1) x 32 B per element, one vector per peer.
+ *
+ * cozk_shamir_mul_deal is a dealer's first step: out[q] = h_{-> q}, num_parties handles in ctx, in ONE launch that folds the
+ * product into the dealing kernel of cozk_shamir_share_vec (64 B read, n x 32 B written per element; the product vector is
+ * never stored).  keys = this party's `degree` x 32 private bytes; counter discipline and argument rules as for
+ * cozk_shamir_share_vec, and in addition 2 * degree + 1 <= num_parties, and a, b are FR vectors of one length.  On any failure
+ * out[0..num_parties) is NULL (untouched when num_parties itself is out of range).
+ * The finish needs no entry point of its own: with recv[p] = what dealer p sent, it is
+ *   cozk_shamir_combine_vec(ctx, recv, points = {1, .., 2t + 1}, k = 2t + 1, degree = 2t, &c). */
+int cozk_shamir_mul_deal(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, const uint8_t* keys, int degree,
+                         int num_parties, uint64_t counter, cozk_vec** out);
+/* the whole multiplication for num_parties parties driven from the one thread that owns their contexts (the same or
+ * different GPUs), in the style of cozk_shamir_scatter: receive vectors come from each recipient's allocator, every party's
+ * stream is drained before a dealer's stream writes another party's blocks (in place on the dealer's device, staged and
+ * moved by one peer copy per recipient otherwise), the dealers' streams are synchronised, then each party's finish is
+ * enqueued on its own stream.  a[p], b[p]: party p's share vectors, vectors of party_ctxs[p]; keys[p]: party p's
+ * `degree` x 32 bytes; for p > 2 * degree none of the three is read and each may be NULL.  out[q] belongs to party_ctxs[q];
+ * failure rules as for cozk_shamir_mul_deal, the error text is left with party_ctxs[0]. */
+int cozk_shamir_mul_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* a, const cozk_vec* const* b,
+                           const uint8_t* const* keys, int degree, int num_parties, uint64_t counter, cozk_vec** out);
+/* one party per process over the context's ring (cozk_ring_init with num_parties ranks; this party = the context's rank):
+ * a dealer deals, exchanges (cozk_ring_all_to_all) and finishes, a party > 2 * degree receives and finishes; all of it is
+ * enqueued on the context's stream and nothing waits on the host.  A dealer needs a, b and keys; another party only a (for
+ * the length).  Refused without a ring and when 2 * degree + 1 exceeds the ring's ranks. */
+int cozk_shamir_mul_vec(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, const uint8_t* keys, int degree,
+                        uint64_t counter, cozk_vec** out);
 
 /* ---------------------------------------------------------------- MSM seam ---------------- */
 /* Upload SRS points (`ck.powers_of_g[i]`, co-jolt/src/poly/commitment/pst13.rs:286-287,461-462) once;
@@ -572,6 +607,12 @@ int cozk_reshare(cozk_ctx* ctx, const cozk_vec* send, cozk_vec* recv);
 int cozk_rep3_mul_vec(cozk_ctx* ctx, const cozk_vec* xa, const cozk_vec* xb, const cozk_vec* ya, const cozk_vec* yb,
                       const uint8_t* key_self, const uint8_t* key_prev, uint64_t counter, cozk_vec** out_a,
                       cozk_vec** out_b);
+/* every rank to every rank on the context's communicator (any number of ranks): ONE ncclGroupStart / ncclGroupEnd on the
+ * context's stream with ncclSend(send[r] -> rank r) for every non-NULL send[r] and ncclRecv(recv[r] <- rank r) for every
+ * non-NULL recv[r], r = 0..nranks-1; the own rank goes through the same calls (a single-rank ring runs the real path).
+ * Entries are FR vectors; that rank r receives exactly what rank s sends it (matching NULL patterns and lengths across
+ * ranks) is the caller's contract.  The exchange of cozk_shamir_mul_vec; 32 B per element per xGMI link there. */
+int cozk_ring_all_to_all(cozk_ctx* ctx, const cozk_vec* const* send, cozk_vec* const* recv);
 /* a cozk_ring_net backed by the context's native ring, for the worker drivers and cozk_harness_prove_distributed */
 int cozk_ring_net_native(cozk_ctx* ctx, cozk_ring_net* out);
 

@@ -5,7 +5,14 @@
   (iii) the per-party element-wise product of two shared vectors;
   (iv)  cozk_shamir_combine_vec of the products from 2T + 1 parties (of one sharing from T + 1 where 2T + 1 > parties).
 Device events around each repetition; enough repetitions of each leg to fill a second.  Fails without a device.
-  python tools/run_shamir.py --log-n 24 --parties 8 --degree 2 [--out FILE]"""
+  python tools/run_shamir.py --log-n 24 --parties 8 --degree 2 [--out FILE]
+With --mul, instead, the multiplication with degree reduction (needs 2 * degree + 1 <= parties):
+  (v)   the fused re-deal cozk_shamir_mul_deal, one kernel (product folded into the dealing);
+  (vi)  the same from the entry points that existed before it -- cozk_vec_binop(MUL), then cozk_shamir_share_vec -- alternating
+        with (v) in this process, outputs compared once;
+  (vii) the whole in-process multiplication cozk_shamir_mul_inproc, one context per party on this GPU: from a device event
+        recorded while every stream is idle to the last of the events recorded behind each party's finish.
+  python tools/run_shamir.py --mul --log-n 22 --parties 8 --degree 2 [--out FILE]"""
 import argparse, ctypes, importlib, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -17,6 +24,7 @@ ap.add_argument("--parties", type=int, default=8)
 ap.add_argument("--degree", type=int, default=2)
 ap.add_argument("--out", default=None)
 ap.add_argument("--min-seconds", type=float, default=1.0)
+ap.add_argument("--mul", action="store_true", help="time the multiplication with degree reduction instead")
 args = ap.parse_args()
 cozk = importlib.import_module("co-zkvms_amd")
 L = cozk._lib
@@ -82,6 +90,113 @@ def free(vs):
         v.free()
 
 
+def stats(ts):
+    ts = sorted(ts)
+    return {"median_ms": round(ts[len(ts) // 2], 4), "min_ms": round(ts[0], 4), "max_ms": round(ts[-1], 4), "repetitions": len(ts)}
+
+
+med = lambda ts: sorted(ts)[len(ts) // 2]
+
+
+def emit(res):
+    print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(json.dumps(res, indent=1) + "\n")
+
+
+def mul_legs():
+    if 2 * T + 1 > N:
+        raise SystemExit("run_shamir --mul: 2 * degree + 1 parties re-deal the product; %d > %d" % (2 * T + 1, N))
+
+    def fused_deal():
+        return A.shamir_mul_deal(B, keys_a, T, N, counter=0)
+
+    def composed_deal():
+        prod = A.binop(cozk.OP_MUL, B)
+        out = prod.shamir_share(keys_a, T, N, counter=0)
+        prod.free()
+        return out
+
+    f, c = fused_deal(), composed_deal()  # correctness once, which is also the warm-up of both legs
+    equal = all(np.array_equal(x.to_numpy(), y.to_numpy()) for x, y in zip(f, c))
+    free(f), free(c)
+    assert equal, "the fused re-deal and binop(MUL) + shamir_share differ"
+    for _ in range(2):
+        free(timed(fused_deal)[1]), free(timed(composed_deal)[1])
+    t_f, t_c = [], []
+    while sum(t_f) < args.min_seconds * 1e3 or sum(t_c) < args.min_seconds * 1e3 or len(t_f) < 5:  # alternating
+        ms, r = timed(fused_deal); t_f.append(ms); free(r)
+        ms, r = timed(composed_deal); t_c.append(ms); free(r)
+
+    # (vii): one context per party on this GPU; a, b dealt onto them
+    pcs = [cozk.Context(0) for _ in range(N)]
+    streams = []
+    for pc in pcs:
+        h = ctypes.c_void_p()
+        pc.check(pc._l.cozk_ctx_stream(pc.h, ctypes.byref(h)))
+        streams.append(torch.cuda.ExternalStream(h.value))
+    sa, sb = A.shamir_scatter(keys_a, T, pcs, counter=0), B.shamir_scatter(keys_b, T, pcs, counter=0)
+    party_keys = [[key(1000 + 16 * p + c) for c in range(T)] for p in range(N)]
+
+    def whole():
+        for pc in pcs:
+            pc.synchronize()
+        e0 = torch.cuda.Event(enable_timing=True)
+        e0.record(streams[0])  # every stream is idle: the call starts by draining them
+        out = cozk.shamir_mul(pcs, sa, sb, party_keys, T, counter=n)
+        ends = []
+        for st in streams:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record(st)
+            ends.append(e)
+        for e in ends:
+            e.synchronize()
+        return max(e0.elapsed_time(e) for e in ends), out
+
+    ms, out = whole()  # warm-up and correctness: t + 1 parties from the high end open a x b
+    for pc in pcs:
+        pc.synchronize()
+    pts = list(range(N, N - T - 1, -1))
+    opened = cozk.shamir_combine([out[p - 1] for p in pts], pts, T)
+    want = A.binop(cozk.OP_MUL, B)
+    opens = bool(np.array_equal(opened.to_numpy(), want.to_numpy()))
+    free([opened, want]), free(out)
+    assert opens, "the in-process multiplication did not open the product of the secrets from degree + 1 parties"
+    t_w = []
+    while sum(t_w) < args.min_seconds * 1e3 or len(t_w) < 5:
+        ms, out = whole(); t_w.append(ms); free(out)
+    free(sa), free(sb)
+    for pc in pcs:
+        pc.close()
+
+    D = 2 * T + 1
+    fused_bytes, comp_bytes = (2 + N) * 32 * n, (3 + 1 + N) * 32 * n
+    whole_bytes = D * (2 + N) * 32 * n + N * (D + 1) * 32 * n
+    spread = lambda ts: round((sorted(ts)[-1] - sorted(ts)[0]) / med(ts), 4)
+    emit({
+        "what": "Shamir multiplication with degree reduction: fused re-deal vs binop(MUL) + shamir_share, whole in-process multiplication",
+        "log_n": args.log_n, "parties": N, "degree": T, "dealers": D, "device": torch.cuda.get_device_name(0),
+        "fused_mul_deal": dict(stats(t_f), algorithmic_bytes=fused_bytes, bytes_per_s=round(fused_bytes / (med(t_f) * 1e-3), 1),
+                               spread_max_minus_min_over_median=spread(t_f), launches=1),
+        "composed_mul_then_share": dict(stats(t_c), bytes_moved_by_the_composition=comp_bytes, spread_max_minus_min_over_median=spread(t_c), launches=2),
+        "fused_vs_composed_speedup": round(med(t_c) / med(t_f), 3),
+        "fused_not_slower_beyond_spread": bool(med(t_f) <= med(t_c) + max(sorted(t_f)[-1] - sorted(t_f)[0], sorted(t_c)[-1] - sorted(t_c)[0])),
+        "outputs_equal": bool(equal),
+        "inproc_mul": dict(stats(t_w), algorithmic_bytes=whole_bytes, bytes_per_s=round(whole_bytes / (med(t_w) * 1e-3), 1),
+                           launches=D + N, contexts=N, opens_from_degree_plus_1=opens),
+        "timing": "device events around each repetition (allocation from the contexts' pools included); legs (v) and (vi) alternating on one stream; "
+                  "(vii) from an event on party 0's idle stream before the call to the last of the events behind the parties' finishes, host-side "
+                  "stream synchronisations of the call included",
+    })
+
+
+if args.mul:
+    mul_legs()
+    ctx.close()
+    raise SystemExit(0)
+
 # correctness once, which is also the warm-up of both legs
 f, c = fused(A, keys_a), composed(A, keys_a)
 equal = all(np.array_equal(x.to_numpy(), y.to_numpy()) for x, y in zip(f, c))
@@ -118,14 +233,8 @@ opens = bool(np.array_equal(opened.to_numpy(), (A.binop(cozk.OP_MUL, B) if OPEN_
 assert opens, "the combine leg did not open " + ("the product of the secrets" if OPEN_PRODUCT else "the secret")
 
 
-def stats(ts):
-    ts = sorted(ts)
-    return {"median_ms": round(ts[len(ts) // 2], 4), "min_ms": round(ts[0], 4), "max_ms": round(ts[-1], 4), "repetitions": len(ts)}
-
-
 share_bytes, comp_bytes = (1 + N) * 32 * n, 32 * T * n + N * T * (64 + 96) * n
 mul_bytes, comb_bytes = N * 96 * n, (K + 1) * 32 * n
-med = lambda ts: sorted(ts)[len(ts) // 2]
 share_bps = share_bytes / (med(t_f) * 1e-3)
 res = {
     "what": "Shamir seam: fused share vs the same sharing composed from earlier entry points, per-party product, combine",
@@ -142,10 +251,5 @@ res = {
     "combine_opens": "share x share, degree 2T" if OPEN_PRODUCT else "one sharing, degree T (2T + 1 > parties)", "combine_equals_expected": opens,
     "timing": "device events on the context's stream around each repetition (allocation from the context's pool included), legs (i) and (ii) alternating",
 }
-line = json.dumps(res)
-print(line, flush=True)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write(json.dumps(res, indent=1) + "\n")
+emit(res)
 ctx.close()
