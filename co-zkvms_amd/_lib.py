@@ -132,6 +132,13 @@ SIGNATURES = {
     "cozk_shamir_mul_deal": (_i, [_vp, _vp, _vp, ctypes.c_char_p, _i, _i, _u64, _vp]),
     "cozk_shamir_mul_inproc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _u64, _vp]),
     "cozk_shamir_mul_vec": (_i, [_vp, _vp, _vp, ctypes.c_char_p, _i, _u64, _pp]),
+    "cozk_shamir_rand_deal": (_i, [_vp, _sz, ctypes.c_char_p, _i, _i, _u64, _vp, _vp]),
+    "cozk_shamir_rand_extract": (_i, [_vp, _vp, _i, _i, _vp]),
+    "cozk_shamir_rand_inproc": (_i, [_vp, _vp, _sz, _i, _i, _u64, _vp, _vp]),
+    "cozk_shamir_rand_vec": (_i, [_vp, _sz, ctypes.c_char_p, _i, _u64, _vp, _vp]),
+    "cozk_shamir_mul_mask": (_i, [_vp, _vp, _vp, _vp, _pp]),
+    "cozk_shamir_mul_king_inproc": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "cozk_shamir_mul_king_vec": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _pp]),
     "cozk_shamir_combine_points": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, ctypes.POINTER(_i)]),
     "cozk_layer_round": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "cozk_fingerprint_leaves": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _i, _i, _vp, _vp, _sz, _sz]),

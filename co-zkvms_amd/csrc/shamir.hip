@@ -91,6 +91,15 @@ struct ShamirMulPrfSrc : ShamirPrfCoefs {  // the secret is the product a[i] b[i
     const fe *a, *b;
     __device__ __forceinline__ fe value(size_t i) const { return Fr::mul(fe_load(a + i), fe_load(b + i)); }
 };
+struct ShamirRandPrfSrc : ShamirPrfCoefs {  // the secret is itself a PRF element, never stored (double-random pairs, offline)
+    prf_key key0;
+    __device__ __forceinline__ fe value(size_t i) const {
+        prf_key key;
+#pragma unroll
+        for (int w = 0; w < 8; w++) key.k[w] = key0.k[w];
+        return shamir_prf_fr(key, counter + i);
+    }
+};
 struct ShamirVecSrc {  // the caller's coefficient vectors
     const fe* v;
     const fe* c[COZK_SHAMIR_MAX_DEGREE];
@@ -173,6 +182,53 @@ __global__ void __launch_bounds__(256) k_shamir_combine(ShamirCombineArgs a, int
 __global__ void __launch_bounds__(256) k_fe_add_scalar(fe* __restrict__ v, size_t n, fe s) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) fe_store(v + i, Fr::add(fe_load(v + i), s));
+}
+
+// ------------------------------------------------------------------ extract: out_k[i] = sum_j (j + 1)^k s_j[i]
+// The Vandermonde step of the double-random preprocessing (Damgard-Nielsen): count <= n - 1 <= 31 outputs from n <= 32
+// inputs.  k_shamir_combine would re-read every input once per output; here a lane owns element i, the rolled loop over j loads
+// s_j[i] ONCE per tile of SHAMIR_EXTRACT_TILE outputs into a running value w = s_j (j + 1)^k, and per output of the tile adds w to
+// that output's accumulator and steps w with fr_mul_small_add(w, j + 1, 0) (j + 1 <= 32: inside its proven input bound; the
+// result is canonical, so is every Fr::add of canonical values, so is every store).  A tile that does not begin at k = 0 starts
+// from w = s_j (j + 1)^k0 by ONE Montgomery product with a constant from the kernel arguments (the 8 k0 small steps it replaces
+// cost as much at k0 = 8 and more after).  Pointers and constants travel in the kernel arguments, indexed by the wave-uniform j.
+// The tile is 8 accumulators (64 VGPRs); the kernel compiles to 164 VGPRs (160 for the SCALED variant), 3 waves per SIMD, no
+// scratch.  A tile of 4 compiles to 116 (4 waves) and doubles the re-reads, 12 to 220 (2 waves), 16 to 256 (1 wave).
+#define SHAMIR_EXTRACT_TILE 8
+struct ShamirExtractArgs {
+    const fe* s[COZK_SHAMIR_MAX_PARTIES];
+    fe* out[SHAMIR_EXTRACT_TILE];
+    fe start[COZK_SHAMIR_MAX_PARTIES];  // (j + 1)^k0, Montgomery; read only by the SCALED variant
+};
+template <bool SCALED>  // a tile that begins at k0 > 0
+__global__ void __launch_bounds__(256) k_shamir_extract(ShamirExtractArgs a, int num_in, int cnt, size_t n) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fe acc[SHAMIR_EXTRACT_TILE];
+#pragma unroll
+    for (int k = 0; k < SHAMIR_EXTRACT_TILE; k++) acc[k] = Fr::zero();
+#pragma unroll 1
+    for (int j = 0; j < num_in; j++) {
+        fe w = fe_load(a.s[j] + i);
+        if (SCALED) w = Fr::mul(w, a.start[j]);
+#pragma unroll
+        for (int k = 0; k < SHAMIR_EXTRACT_TILE; k++)
+            if (k < cnt) {
+                acc[k] = Fr::add(acc[k], w);
+                if (k + 1 < cnt) w = fr_mul_small_add(w, (uint32_t)j + 1, Fr::zero());
+                __builtin_amdgcn_sched_barrier(0);  // keeps the scheduler from running the tile's powers of w ahead of their additions (176 VGPRs, 2 waves)
+            }
+    }
+#pragma unroll
+    for (int k = 0; k < SHAMIR_EXTRACT_TILE; k++)
+        if (k < cnt) fe_store(a.out[k] + i, acc[k]);
+}
+
+// out[i] = a[i] b[i] + c[i]: the mask of the king multiplication (96 B read, 32 B written; the product is never stored)
+__global__ void __launch_bounds__(256) k_fe_mul_add(const fe* __restrict__ a, const fe* __restrict__ b, const fe* __restrict__ c, fe* __restrict__ out,
+                                                    size_t n) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) fe_store(out + i, Fr::add(Fr::mul(fe_load(a + i), fe_load(b + i)), fe_load(c + i)));
 }
 
 // ------------------------------------------------------------------ host
@@ -588,6 +644,439 @@ int cozk_shamir_mul_vec(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, con
     // everything above is enqueued on the context's stream, and so is whatever reuses these blocks
     free_all(dealt, num_parties);
     free_all(recv, num_parties);
+    return rc;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ multiplication with a king and double-random pairs
+// (Damgard-Nielsen; semi-honest).  Offline, every party deals one random secret twice -- degree t and degree 2t, two launches of
+// the dealing kernel with the ShamirRandPrfSrc source, which recomputes the secret and never stores it -- everyone receives one
+// vector of each kind from everyone, and the (n - t) x n Vandermonde matrix on the points 1..n (k_shamir_extract) turns the n
+// received vectors into n - t pairs ([r]_t, [r]_2t) no t parties know.  Online, parties 0..2t send a b + r_2t to the king, who
+// opens z = a b + r with the degree-2t combine and sends it to everyone; party q keeps z - r_t.  The reference has none of it;
+// tests/shamir_dn_ref.py restates it.
+static void require_rand_args(const char* who, int degree, int num_parties) {
+    const std::string w(who);
+    COZK_REQUIRE(degree >= 1 && 2 * degree <= COZK_SHAMIR_MAX_DEGREE, w + ": 1 <= degree and 2 * degree <= COZK_SHAMIR_MAX_DEGREE (the degree-2t sharing is dealt too)");
+    COZK_REQUIRE(2 * degree + 1 <= num_parties && num_parties <= COZK_SHAMIR_MAX_PARTIES, w + ": 2 * degree + 1 <= num_parties <= COZK_SHAMIR_MAX_PARTIES");
+}
+
+// keys[0] = the secret stream; `degree` coefficient keys from keys[first]
+static ShamirRandPrfSrc rand_prf_src(const uint8_t* keys, int first, int degree, uint64_t counter) {
+    ShamirRandPrfSrc src;
+    fill_prf_coefs(src, keys + (size_t)COZK_PRF_KEY_BYTES * first, degree, counter);
+    src.key0 = prf_key_from_bytes(keys);
+    return src;
+}
+
+static void launch_extract(hipStream_t st, const fe* const* in, int num_in, int count, fe* const* out, size_t n) {
+    for (int k0 = 0; k0 < count; k0 += SHAMIR_EXTRACT_TILE) {
+        ShamirExtractArgs a;
+        memset(&a, 0, sizeof a);
+        const int cnt = count - k0 < SHAMIR_EXTRACT_TILE ? count - k0 : SHAMIR_EXTRACT_TILE;
+        for (int k = 0; k < cnt; k++) a.out[k] = out[k0 + k];
+        for (int j = 0; j < num_in; j++) {
+            a.s[j] = in[j];
+            if (!k0) continue;
+            const fe x = Fr::from_u64((uint64_t)j + 1);
+            fe pw = Fr::one();
+            for (int e = 0; e < k0; e++) pw = Fr::mul(pw, x);
+            a.start[j] = pw;
+        }
+        const unsigned grid = (unsigned)((n + 255) / 256);
+        if (k0) k_shamir_extract<true><<<grid, 256, 0, st>>>(a, num_in, cnt, n);
+        else k_shamir_extract<false><<<grid, 256, 0, st>>>(a, num_in, cnt, n);
+        HIP_TRY(hipGetLastError());
+    }
+}
+
+// both output tables are required; where only one is given it is still cleared
+static int require_out2(cozk_ctx* ctx, cozk_vec** x, cozk_vec** y, int len, const char* msg) {
+    int rc = cozk_guard(ctx, [&] { COZK_REQUIRE(x && y, msg); });
+    if (rc != COZK_OK) {
+        if (x) clear_outputs(x, len);
+        if (y) clear_outputs(y, len);
+    }
+    return rc;
+}
+
+static void require_own_vec(const char* who, const cozk_vec* v, const cozk_ctx* ctx, size_t n, const char* what) {
+    const std::string w(who);
+    COZK_REQUIRE(v, w + ": null " + what);
+    COZK_REQUIRE(v->kind == COZK_SCALAR_FR, w + ": " + what + " must be an FR vector");
+    COZK_REQUIRE(v->n == n, w + ": the factors and the pair must have one length");
+    COZK_REQUIRE(v->ctx == ctx, w + ": " + what + " must be a vector of its party's context");
+}
+
+static void launch_mul_add(hipStream_t st, const cozk_vec* a, const cozk_vec* b, const cozk_vec* c, fe* out) {
+    if (a->n == 0) return;
+    k_fe_mul_add<<<(unsigned)((a->n + 255) / 256), 256, 0, st>>>((const fe*)a->d, (const fe*)b->d, (const fe*)c->d, out, a->n);
+    HIP_TRY(hipGetLastError());
+}
+
+// one degree of cozk_shamir_rand_inproc: every party deals with `deg` coefficient keys from keys[p][first], every party
+// extracts np - t vectors into r[q * (np - t) + k].  On failure nothing of its own is left; the caller frees r.
+static int rand_pass(cozk_ctx* const* pcs, const uint8_t* const* keys, size_t n, int t, int first, int deg, int np, uint64_t counter, cozk_vec** r) {
+    cozk_ctx* const c0 = pcs[0];
+    std::vector<cozk_vec*> recv((size_t)np * np, nullptr);  // recv[q * np + p] = what party p dealt to party q, a block of party q
+    std::vector<fe*> stage(np, nullptr);
+    int rc = COZK_OK;
+    auto fail = [&](int code, int p) {
+        if (pcs[p] != c0) c0->last_error = pcs[p]->last_error;
+        for (int q = 0; q < np; q++) (void)hipStreamSynchronize(pcs[q]->stream);
+        for (int d = 0; d < np; d++) ctx_dev_free(pcs[d], stage[d]);
+        for (cozk_vec* v : recv) cozk_vec_free(v);
+        return code;
+    };
+    for (int q = 0; q < np; q++)
+        for (int p = 0; p < np; p++)
+            if ((rc = cozk_vec_alloc(pcs[q], n, COZK_SCALAR_FR, &recv[(size_t)q * np + p])) != COZK_OK) return fail(rc, q);
+    if (n) {
+        // the receive blocks are ordered by their owners' streams only (see cozk_shamir_scatter)
+        rc = cozk_guard(c0, [&] {
+            for (int q = 0; q < np; q++) HIP_TRY(hipStreamSynchronize(pcs[q]->stream));
+        });
+        if (rc != COZK_OK) return fail(rc, 0);
+        for (int p = 0; p < np; p++) {
+            cozk_ctx* dealer = pcs[p];
+            rc = cozk_guard(dealer, [&] {
+                size_t remote = 0;
+                for (int q = 0; q < np; q++) remote += pcs[q]->device != dealer->device;
+                if (remote) stage[p] = (fe*)ctx_dev_alloc(dealer, remote * n * sizeof(fe));
+                ShamirOut o;
+                memset(&o, 0, sizeof o);
+                size_t k = 0;
+                for (int q = 0; q < np; q++) o.p[q] = pcs[q]->device != dealer->device ? stage[p] + n * k++ : (fe*)recv[(size_t)q * np + p]->d;
+                launch_share(dealer->stream, rand_prf_src(keys[p], first, deg, counter), o, n, deg, np);
+                for (int q = 0; q < np; q++)
+                    if (pcs[q]->device != dealer->device)
+                        HIP_TRY(hipMemcpyPeerAsync(recv[(size_t)q * np + p]->d, pcs[q]->device, o.p[q], dealer->device, n * sizeof(fe), dealer->stream));
+            });
+            if (rc != COZK_OK) return fail(rc, p);
+        }
+        for (int p = 0; p < np; p++) {  // the parties' streams may read what they received once the dealers' have drained
+            rc = cozk_guard(pcs[p], [&] {
+                HIP_TRY(hipStreamSynchronize(pcs[p]->stream));
+                ctx_dev_free(pcs[p], stage[p]);
+                stage[p] = nullptr;
+            });
+            if (rc != COZK_OK) return fail(rc, p);
+        }
+    }
+    for (int q = 0; q < np; q++) {  // the extraction, on each party's own stream; its pool takes the blocks back behind it
+        rc = cozk_shamir_rand_extract(pcs[q], &recv[(size_t)q * np], np, np - t, &r[(size_t)q * (np - t)]);
+        if (rc != COZK_OK) return fail(rc, q);
+        for (int p = 0; p < np; p++) {
+            cozk_vec_free(recv[(size_t)q * np + p]);
+            recv[(size_t)q * np + p] = nullptr;
+        }
+    }
+    return COZK_OK;
+}
+
+extern "C" {
+
+int cozk_shamir_rand_deal(cozk_ctx* ctx, size_t n_elems, const uint8_t* keys, int degree, int num_parties, uint64_t counter, cozk_vec** out_t,
+                          cozk_vec** out_2t) {
+    if (int rc0 = require_out2(ctx, out_t, out_2t, num_parties, "shamir_rand_deal: null output")) return rc0;
+    clear_outputs(out_t, num_parties);
+    clear_outputs(out_2t, num_parties);
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && keys, "shamir_rand_deal: null argument");
+        require_rand_args("shamir_rand_deal", degree, num_parties);
+    });
+    if (rc != COZK_OK) return rc;
+    rc = alloc_outputs(ctx, nullptr, n_elems, num_parties, out_t);
+    if (rc != COZK_OK) return rc;
+    rc = alloc_outputs(ctx, nullptr, n_elems, num_parties, out_2t);
+    if (rc == COZK_OK)
+        rc = cozk_guard(ctx, [&] {
+            if (n_elems == 0) return;
+            launch_share(ctx->stream, rand_prf_src(keys, 1, degree, counter), out_table(out_t, num_parties), n_elems, degree, num_parties);
+            launch_share(ctx->stream, rand_prf_src(keys, 1 + degree, 2 * degree, counter), out_table(out_2t, num_parties), n_elems, 2 * degree, num_parties);
+        });
+    if (rc != COZK_OK) {
+        free_all(out_t, num_parties);
+        free_all(out_2t, num_parties);
+    }
+    return rc;
+}
+
+int cozk_shamir_rand_extract(cozk_ctx* ctx, const cozk_vec* const* recv, int num_parties, int count, cozk_vec** out) {
+    if (int rc0 = require_out(ctx, out, "shamir_rand_extract: null output")) return rc0;
+    clear_outputs(out, count);
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && recv, "shamir_rand_extract: null argument");
+        COZK_REQUIRE(num_parties >= 2 && num_parties <= COZK_SHAMIR_MAX_PARTIES, "shamir_rand_extract: 2 <= num_parties <= COZK_SHAMIR_MAX_PARTIES");
+        COZK_REQUIRE(count >= 1 && count <= num_parties - 1, "shamir_rand_extract: 1 <= count <= num_parties - 1");
+        for (int j = 0; j < num_parties; j++) {
+            COZK_REQUIRE(recv[j] && recv[j]->kind == COZK_SCALAR_FR, "shamir_rand_extract: num_parties FR vectors");
+            COZK_REQUIRE(recv[j]->n == recv[0]->n, "shamir_rand_extract: the vectors must have one length");
+        }
+    });
+    if (rc != COZK_OK) return rc;
+    const size_t n = recv[0]->n;
+    rc = alloc_outputs(ctx, nullptr, n, count, out);
+    if (rc != COZK_OK) return rc;
+    rc = cozk_guard(ctx, [&] {
+        if (n == 0) return;
+        const fe* in[COZK_SHAMIR_MAX_PARTIES];
+        fe* o[COZK_SHAMIR_MAX_PARTIES];
+        for (int j = 0; j < num_parties; j++) in[j] = (const fe*)recv[j]->d;
+        for (int k = 0; k < count; k++) o[k] = (fe*)out[k]->d;
+        launch_extract(ctx->stream, in, num_parties, count, o, n);
+    });
+    if (rc != COZK_OK) free_all(out, count);
+    return rc;
+}
+
+int cozk_shamir_rand_inproc(cozk_ctx* const* party_ctxs, const uint8_t* const* keys, size_t n_elems, int degree, int num_parties, uint64_t counter,
+                            cozk_vec** r_t, cozk_vec** r_2t) {
+    cozk_ctx* const c0 = party_ctxs && num_parties >= 1 ? party_ctxs[0] : nullptr;  // receives the error message
+    // n (n - t) handles per table: that length is known once 1 <= degree < num_parties <= COZK_SHAMIR_MAX_PARTIES
+    const bool known = num_parties >= 1 && num_parties <= COZK_SHAMIR_MAX_PARTIES && degree >= 1 && degree < num_parties;
+    const size_t len = known ? (size_t)num_parties * (num_parties - degree) : 0;
+    auto clear = [&](cozk_vec** t) {
+        for (size_t i = 0; t && i < len; i++) t[i] = nullptr;
+    };
+    clear(r_t), clear(r_2t);
+    int rc = cozk_guard(c0, [&] {
+        COZK_REQUIRE(r_t && r_2t, "shamir_rand_inproc: null output");
+        COZK_REQUIRE(party_ctxs && keys, "shamir_rand_inproc: null argument");
+        require_rand_args("shamir_rand_inproc", degree, num_parties);
+        for (int p = 0; p < num_parties; p++) COZK_REQUIRE(party_ctxs[p], "shamir_rand_inproc: null party context");
+        for (int p = 0; p < num_parties; p++) COZK_REQUIRE(keys[p], "shamir_rand_inproc: every party needs its key block");
+    });
+    if (rc != COZK_OK) return rc;
+    // one degree after the other: n^2 receive vectors are alive at a time, not 2 n^2
+    rc = rand_pass(party_ctxs, keys, n_elems, degree, 1, degree, num_parties, counter, r_t);
+    if (rc == COZK_OK) rc = rand_pass(party_ctxs, keys, n_elems, degree, 1 + degree, 2 * degree, num_parties, counter, r_2t);
+    if (rc != COZK_OK)
+        for (size_t i = 0; i < len; i++) {
+            cozk_vec_free(r_t[i]);
+            cozk_vec_free(r_2t[i]);
+            r_t[i] = r_2t[i] = nullptr;
+        }
+    return rc;
+}
+
+int cozk_shamir_rand_vec(cozk_ctx* ctx, size_t n_elems, const uint8_t* keys, int degree, uint64_t counter, cozk_vec** r_t, cozk_vec** r_2t) {
+    // ring ranks - degree handles per table: known once there is a ring and 1 <= degree < its ranks
+    const int count = ctx && ctx->ring_comm && degree >= 1 && degree < ctx->ring_n && ctx->ring_n <= COZK_SHAMIR_MAX_PARTIES ? ctx->ring_n - degree : 0;
+    if (int rc0 = require_out2(ctx, r_t, r_2t, count, "shamir_rand_vec: null output")) return rc0;
+    clear_outputs(r_t, count);
+    clear_outputs(r_2t, count);
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && keys, "shamir_rand_vec: null argument");
+        COZK_REQUIRE(ctx->ring_comm, "shamir_rand_vec: cozk_ring_init has not been called on this context");
+        require_rand_args("shamir_rand_vec (num_parties = ranks of the ring)", degree, ctx->ring_n);
+    });
+    if (rc != COZK_OK) return rc;
+    const int np = ctx->ring_n, self = ctx->ring_rank;
+    cozk_vec *dealt[2][COZK_SHAMIR_MAX_PARTIES] = {}, *recv[2][COZK_SHAMIR_MAX_PARTIES] = {};
+    rc = cozk_shamir_rand_deal(ctx, n_elems, keys, degree, np, counter, dealt[0], dealt[1]);
+    for (int h = 0; h < 2 && rc == COZK_OK; h++) {
+        for (int p = 0; p < np && rc == COZK_OK; p++)
+            if (p != self) rc = cozk_vec_alloc(ctx, n_elems, COZK_SCALAR_FR, &recv[h][p]);
+        if (rc != COZK_OK) break;
+        const cozk_vec *send[COZK_SHAMIR_MAX_PARTIES] = {}, *got[COZK_SHAMIR_MAX_PARTIES] = {};
+        for (int q = 0; q < np; q++) send[q] = q != self ? dealt[h][q] : nullptr;  // the own slot stays local
+        rc = cozk_ring_all_to_all(ctx, send, recv[h]);
+        if (rc != COZK_OK) break;
+        for (int p = 0; p < np; p++) got[p] = p == self ? dealt[h][p] : recv[h][p];
+        rc = cozk_shamir_rand_extract(ctx, got, np, count, h ? r_2t : r_t);
+    }
+    // everything above is enqueued on the context's stream, and so is whatever reuses these blocks
+    for (int h = 0; h < 2; h++) {
+        free_all(dealt[h], np);
+        free_all(recv[h], np);
+    }
+    if (rc != COZK_OK) {
+        free_all(r_t, count);
+        free_all(r_2t, count);
+    }
+    return rc;
+}
+
+int cozk_shamir_mul_mask(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, const cozk_vec* r_2t, cozk_vec** out) {
+    if (int rc0 = require_out(ctx, out, "shamir_mul_mask: null output")) return rc0;
+    *out = nullptr;
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && a && b && r_2t, "shamir_mul_mask: null argument");
+        COZK_REQUIRE(a->kind == COZK_SCALAR_FR && b->kind == COZK_SCALAR_FR && r_2t->kind == COZK_SCALAR_FR, "shamir_mul_mask: the factors and the mask must be FR vectors");
+        COZK_REQUIRE(a->n == b->n && a->n == r_2t->n, "shamir_mul_mask: the factors and the mask must have one length");
+    });
+    if (rc != COZK_OK) return rc;
+    rc = cozk_vec_alloc(ctx, a->n, COZK_SCALAR_FR, out);
+    if (rc != COZK_OK) return rc;
+    rc = cozk_guard(ctx, [&] { launch_mul_add(ctx->stream, a, b, r_2t, (fe*)(*out)->d); });
+    if (rc != COZK_OK) {
+        cozk_vec_free(*out);
+        *out = nullptr;
+    }
+    return rc;
+}
+
+int cozk_shamir_mul_king_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* a, const cozk_vec* const* b, const cozk_vec* const* r_t,
+                                const cozk_vec* const* r_2t, int degree, int num_parties, int king, cozk_vec** out) {
+    cozk_ctx* const c0 = party_ctxs && num_parties >= 1 ? party_ctxs[0] : nullptr;  // receives the error message
+    if (int rc0 = require_out(c0, out, "shamir_mul_king_inproc: null output")) return rc0;
+    clear_outputs(out, num_parties);
+    const int senders = 2 * degree + 1;
+    const char* who = "shamir_mul_king_inproc";
+    int rc = cozk_guard(c0, [&] {
+        COZK_REQUIRE(party_ctxs && a && b && r_t && r_2t, "shamir_mul_king_inproc: null argument");
+        require_rand_args(who, degree, num_parties);
+        COZK_REQUIRE(king >= 0 && king < num_parties, "shamir_mul_king_inproc: 0 <= king < num_parties");
+        for (int p = 0; p < num_parties; p++) COZK_REQUIRE(party_ctxs[p], "shamir_mul_king_inproc: null party context");
+        COZK_REQUIRE(r_t[0], "shamir_mul_king_inproc: null first half of the pair");
+        for (int p = 0; p < num_parties; p++) require_own_vec(who, r_t[p], party_ctxs[p], r_t[0]->n, "the first half of the pair");
+        for (int p = 0; p < senders; p++) {
+            require_own_vec(who, a[p], party_ctxs[p], r_t[0]->n, "a factor of parties 0..2 * degree");
+            require_own_vec(who, b[p], party_ctxs[p], r_t[0]->n, "a factor of parties 0..2 * degree");
+            require_own_vec(who, r_2t[p], party_ctxs[p], r_t[0]->n, "the second half of the pair of parties 0..2 * degree");
+        }
+    });
+    if (rc != COZK_OK) return rc;
+    const size_t n = r_t[0]->n;
+    cozk_ctx* const kc = party_ctxs[king];
+    cozk_vec* m[COZK_SHAMIR_MAX_PARTIES] = {};     // m[p] = a_p b_p + r2t_p, a block of the king
+    fe* stage[COZK_SHAMIR_MAX_PARTIES] = {};       // the same on a sender's other device
+    cozk_vec* zq[COZK_SHAMIR_MAX_PARTIES] = {};    // z on a party's other device, a block of that party
+    cozk_vec* z = nullptr;
+    auto fail = [&](int code, int p) {
+        if (party_ctxs[p] != c0) c0->last_error = party_ctxs[p]->last_error;
+        for (int q = 0; q < num_parties; q++) (void)hipStreamSynchronize(party_ctxs[q]->stream);
+        for (int s = 0; s < senders; s++) ctx_dev_free(party_ctxs[s], stage[s]);
+        free_all(m, senders);
+        free_all(zq, num_parties);
+        cozk_vec_free(z);
+        free_all(out, num_parties);
+        return code;
+    };
+    for (int p = 0; p < senders; p++)
+        if ((rc = cozk_vec_alloc(kc, n, COZK_SCALAR_FR, &m[p])) != COZK_OK) return fail(rc, king);
+    for (int q = 0; q < num_parties; q++) {
+        if (party_ctxs[q]->device != kc->device && (rc = cozk_vec_alloc(party_ctxs[q], n, COZK_SCALAR_FR, &zq[q])) != COZK_OK) return fail(rc, q);
+        if ((rc = cozk_vec_alloc(party_ctxs[q], n, COZK_SCALAR_FR, &out[q])) != COZK_OK) {
+            out[q] = nullptr;
+            return fail(rc, q);
+        }
+    }
+    if (n) {
+        // the king's blocks are ordered by the king's stream only (see cozk_shamir_scatter): every party's stream drains before a
+        // sender's stream writes into one
+        rc = cozk_guard(c0, [&] {
+            for (int q = 0; q < num_parties; q++) HIP_TRY(hipStreamSynchronize(party_ctxs[q]->stream));
+        });
+        if (rc != COZK_OK) return fail(rc, 0);
+        for (int p = 0; p < senders; p++) {  // step 1 and 2: the mask on each sender's own stream, into the king's memory
+            cozk_ctx* sc = party_ctxs[p];
+            rc = cozk_guard(sc, [&] {
+                const bool remote = sc->device != kc->device;
+                if (remote) stage[p] = (fe*)ctx_dev_alloc(sc, n * sizeof(fe));
+                launch_mul_add(sc->stream, a[p], b[p], r_2t[p], remote ? stage[p] : (fe*)m[p]->d);
+                if (remote) HIP_TRY(hipMemcpyPeerAsync(m[p]->d, kc->device, stage[p], sc->device, n * sizeof(fe), sc->stream));
+            });
+            if (rc != COZK_OK) return fail(rc, p);
+        }
+        for (int p = 0; p < senders; p++) {  // the king may read the masked products once the senders' streams have drained
+            rc = cozk_guard(party_ctxs[p], [&] {
+                HIP_TRY(hipStreamSynchronize(party_ctxs[p]->stream));
+                ctx_dev_free(party_ctxs[p], stage[p]);
+                stage[p] = nullptr;
+            });
+            if (rc != COZK_OK) return fail(rc, p);
+        }
+    }
+    uint32_t points[COZK_SHAMIR_MAX_PARTIES];
+    for (int p = 0; p < senders; p++) points[p] = (uint32_t)p + 1;
+    rc = cozk_shamir_combine_vec(kc, m, points, (size_t)senders, 2 * degree, &z);  // step 3, on the king's stream
+    if (rc != COZK_OK) return fail(rc, king);
+    free_all(m, senders);  // the king's pool takes them back behind the combine
+    if (n) {
+        rc = cozk_guard(kc, [&] {  // step 4: z to the other devices by the king's stream, then that stream drains
+            for (int q = 0; q < num_parties; q++)
+                if (zq[q]) HIP_TRY(hipMemcpyPeerAsync(zq[q]->d, party_ctxs[q]->device, z->d, kc->device, n * sizeof(fe), kc->stream));
+            HIP_TRY(hipStreamSynchronize(kc->stream));
+        });
+        if (rc != COZK_OK) return fail(rc, king);
+    }
+    for (int q = 0; q < num_parties; q++) {  // c_q = z - rt_q on each party's own stream
+        rc = cozk_vec_binop(party_ctxs[q], COZK_OP_SUB, 0, zq[q] ? zq[q] : z, r_t[q], out[q]);
+        if (rc != COZK_OK) return fail(rc, q);
+    }
+    free_all(zq, num_parties);
+    if (n) {
+        // z is the king's block and was read in place by the other parties of its device: their streams drain before the king's
+        // pool may hand it out again
+        rc = cozk_guard(c0, [&] {
+            for (int q = 0; q < num_parties; q++)
+                if (q != king && party_ctxs[q]->device == kc->device) HIP_TRY(hipStreamSynchronize(party_ctxs[q]->stream));
+        });
+        if (rc != COZK_OK) return fail(rc, 0);
+    }
+    cozk_vec_free(z);
+    return COZK_OK;
+}
+
+int cozk_shamir_mul_king_vec(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, const cozk_vec* r_t, const cozk_vec* r_2t, int degree, int king,
+                             cozk_vec** out) {
+    if (int rc0 = require_out(ctx, out, "shamir_mul_king_vec: null output")) return rc0;
+    *out = nullptr;
+    const char* who = "shamir_mul_king_vec";
+    bool sender = false;
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && r_t, "shamir_mul_king_vec: null argument");
+        COZK_REQUIRE(ctx->ring_comm, "shamir_mul_king_vec: cozk_ring_init has not been called on this context");
+        require_rand_args("shamir_mul_king_vec (num_parties = ranks of the ring)", degree, ctx->ring_n);
+        COZK_REQUIRE(king >= 0 && king < ctx->ring_n, "shamir_mul_king_vec: 0 <= king < ranks of the ring");
+        require_own_vec(who, r_t, ctx, r_t->n, "the first half of the pair");
+        sender = ctx->ring_rank <= 2 * degree;
+        if (sender) {
+            require_own_vec(who, a, ctx, r_t->n, "a factor of parties 0..2 * degree");
+            require_own_vec(who, b, ctx, r_t->n, "a factor of parties 0..2 * degree");
+            require_own_vec(who, r_2t, ctx, r_t->n, "the second half of the pair of parties 0..2 * degree");
+        }
+    });
+    if (rc != COZK_OK) return rc;
+    const int np = ctx->ring_n, senders = 2 * degree + 1, self = ctx->ring_rank;
+    const size_t n = r_t->n;
+    cozk_vec *m = nullptr, *z = nullptr, *recv[COZK_SHAMIR_MAX_PARTIES] = {};
+    const cozk_vec *send[COZK_SHAMIR_MAX_PARTIES] = {}, *shares[COZK_SHAMIR_MAX_PARTIES] = {};
+    if (sender) rc = cozk_shamir_mul_mask(ctx, a, b, r_2t, &m);
+    if (self == king)
+        for (int p = 0; p < senders && rc == COZK_OK; p++)
+            if (p != self) rc = cozk_vec_alloc(ctx, n, COZK_SCALAR_FR, &recv[p]);
+    if (rc == COZK_OK) {  // round 1: the gather to the king (its own slot stays local)
+        if (sender && self != king) send[king] = m;
+        rc = cozk_ring_all_to_all(ctx, send, recv);
+    }
+    if (rc == COZK_OK && self == king) {
+        uint32_t points[COZK_SHAMIR_MAX_PARTIES];
+        for (int p = 0; p < senders; p++) {
+            shares[p] = p == self ? m : recv[p];
+            points[p] = (uint32_t)p + 1;
+        }
+        rc = cozk_shamir_combine_vec(ctx, shares, points, (size_t)senders, 2 * degree, &z);
+    }
+    free_all(recv, np);
+    cozk_vec_free(m);
+    if (rc == COZK_OK && self != king) rc = cozk_vec_alloc(ctx, n, COZK_SCALAR_FR, &z);
+    if (rc == COZK_OK) {  // round 2: the king's fan-out
+        for (int q = 0; q < np; q++) send[q] = self == king && q != self ? z : nullptr;
+        if (self != king) recv[king] = z;
+        rc = cozk_ring_all_to_all(ctx, send, recv);
+    }
+    if (rc == COZK_OK) rc = cozk_vec_alloc(ctx, n, COZK_SCALAR_FR, out);
+    if (rc == COZK_OK) rc = cozk_vec_binop(ctx, COZK_OP_SUB, 0, z, r_t, *out);
+    // everything above is enqueued on the context's stream, and so is whatever reuses these blocks
+    cozk_vec_free(z);
+    if (rc != COZK_OK) {
+        cozk_vec_free(*out);
+        *out = nullptr;
+    }
     return rc;
 }
 

@@ -162,6 +162,24 @@ class Context:
                                                degree, counter, ctypes.byref(h)))
         return Vec(self, h, L.SCALAR_FR)
 
+    def shamir_rand_vec(self, n, keys, degree, counter=0):
+        """this party's halves of ranks - degree double-random pairs of n elements, one party per process over the context's
+        ring (cozk_shamir_rand_vec): keys = its 3 * degree + 1 private PRF keys; returns the list of (r_t, r_2t)"""
+        nr = ctypes.c_int(0)  # stays 0 without a ring: the call below then says so
+        self._l.cozk_ring_info(self.h, None, ctypes.byref(nr), None)
+        rt, r2t = (ctypes.c_void_p * 32)(), (ctypes.c_void_p * 32)()
+        self.check(self._l.cozk_shamir_rand_vec(self.h, n, _shamir_keys(keys), degree, counter, rt, r2t))
+        return [(Vec(self, ctypes.c_void_p(rt[k]), L.SCALAR_FR), Vec(self, ctypes.c_void_p(r2t[k]), L.SCALAR_FR)) for k in range(nr.value - degree)]
+
+    def shamir_mul_king_vec(self, a, b, r_t, r_2t, degree, king=0):
+        """this party's share of a x b as a degree-`degree` sharing again with a king and one double-random pair
+        (cozk_shamir_mul_king_vec), one party per process over the context's ring; a, b and r_2t may be None on a party
+        > 2 * degree.  The pair must not be used again"""
+        h = ctypes.c_void_p()
+        opt = lambda v: None if v is None else v.h
+        self.check(self._l.cozk_shamir_mul_king_vec(self.h, opt(a), opt(b), opt(r_t), opt(r_2t), degree, king, ctypes.byref(h)))
+        return Vec(self, h, L.SCALAR_FR)
+
     def close(self):
         if self.h:
             self._l.cozk_ctx_destroy(self.h)
@@ -338,6 +356,12 @@ class Vec:
         self.ctx.check(self.ctx._l.cozk_shamir_mul_deal(self.ctx.h, self.h, other.h, _shamir_keys(keys), degree, num_parties, counter, out))
         return [Vec(self.ctx, ctypes.c_void_p(out[p]), L.SCALAR_FR) for p in range(num_parties)]
 
+    def shamir_mul_mask(self, other, r_2t):
+        """self[i] * other[i] + r_2t[i] in one launch (cozk_shamir_mul_mask): what a party 0..2 * degree sends to the king"""
+        h = ctypes.c_void_p()
+        self.ctx.check(self.ctx._l.cozk_shamir_mul_mask(self.ctx.h, self.h, other.h, r_2t.h, ctypes.byref(h)))
+        return Vec(self.ctx, h, L.SCALAR_FR)
+
     def free(self):
         if self.h:
             self.ctx._l.cozk_vec_free(self.h)
@@ -401,6 +425,53 @@ def shamir_mul(party_ctxs, a_shares, b_shares, keys_per_party, degree, counter=0
     keys = arr([None if k is None else ctypes.addressof(k) for k in blocks])
     out = (ctypes.c_void_p * max(n, 1))()
     party_ctxs[0].check(party_ctxs[0]._l.cozk_shamir_mul_inproc(ctxs, a, b, keys, degree, n, counter, out))
+    return [Vec(party_ctxs[p], ctypes.c_void_p(out[p]), L.SCALAR_FR) for p in range(n)]
+
+
+def _handles(n, vs):
+    return (ctypes.c_void_p * max(n, 1))(*[None if v is None else v.h for v in vs])
+
+
+def shamir_rand_deal(ctx, n, keys, degree, num_parties, counter=0):
+    """one party's dealing of the double-random preprocessing (cozk_shamir_rand_deal): a PRF secret vector of n elements dealt
+    with degree `degree` and with 2 * degree; keys = 3 * degree + 1 PRF keys.  Returns (out_t, out_2t), num_parties vectors each"""
+    ot, o2 = (ctypes.c_void_p * max(num_parties, 1))(), (ctypes.c_void_p * max(num_parties, 1))()
+    ctx.check(ctx._l.cozk_shamir_rand_deal(ctx.h, n, _shamir_keys(keys), degree, num_parties, counter, ot, o2))
+    wrap = lambda t: [Vec(ctx, ctypes.c_void_p(t[p]), L.SCALAR_FR) for p in range(num_parties)]
+    return wrap(ot), wrap(o2)
+
+
+def shamir_rand_extract(ctx, recv, count):
+    """out[k] = sum_j (j + 1)^k recv[j], k < count (cozk_shamir_rand_extract): the Vandermonde step on the vectors one party
+    received; privacy needs count <= parties - degree"""
+    out = (ctypes.c_void_p * max(count, 1))()
+    ctx.check(ctx._l.cozk_shamir_rand_extract(ctx.h, _handles(len(recv), recv), len(recv), count, out))
+    return [Vec(ctx, ctypes.c_void_p(out[k]), L.SCALAR_FR) for k in range(count)]
+
+
+def shamir_rand(party_ctxs, keys_per_party, n, degree, counter=0):
+    """the double-random preprocessing with all parties in this process (cozk_shamir_rand_inproc): keys_per_party[p] = party p's
+    3 * degree + 1 keys.  Returns per party the list of its parties - degree pairs (r_t, r_2t), owned by that party's context"""
+    np_ = len(party_ctxs)
+    cnt = np_ - degree
+    ctxs = (ctypes.c_void_p * max(np_, 1))(*[c.h for c in party_ctxs])
+    blocks = [None if k is None else ctypes.create_string_buffer(_shamir_keys(k), max(32 * len(k), 1)) for k in keys_per_party]
+    keys = (ctypes.c_void_p * max(np_, 1))(*[None if k is None else ctypes.addressof(k) for k in blocks])
+    rt, r2t = (ctypes.c_void_p * max(np_ * cnt, 1))(), (ctypes.c_void_p * max(np_ * cnt, 1))()
+    party_ctxs[0].check(party_ctxs[0]._l.cozk_shamir_rand_inproc(ctxs, keys, n, degree, np_, counter, rt, r2t))
+    vec = lambda t, q, k: Vec(party_ctxs[q], ctypes.c_void_p(t[q * cnt + k]), L.SCALAR_FR)
+    return [[(vec(rt, q, k), vec(r2t, q, k)) for k in range(cnt)] for q in range(np_)]
+
+
+def shamir_mul_king(party_ctxs, a_shares, b_shares, r_t, r_2t, degree, king=0):
+    """share x share -> a degree-`degree` sharing of the product with a king and ONE double-random pair, all parties in this
+    process (cozk_shamir_mul_king_inproc): r_t[p], r_2t[p] = party p's halves of the pair; a_shares[p], b_shares[p], r_2t[p]
+    may be None for p > 2 * degree.  The pair must not be used again.  Returns one vector per party"""
+    n = len(party_ctxs)
+    ctxs = (ctypes.c_void_p * max(n, 1))(*[c.h for c in party_ctxs])
+    out = (ctypes.c_void_p * max(n, 1))()
+    party_ctxs[0].check(party_ctxs[0]._l.cozk_shamir_mul_king_inproc(ctxs, _handles(n, a_shares), _handles(n, b_shares), _handles(n, r_t),
+                                                                    _handles(n, r_2t), degree, n, king, out))
     return [Vec(party_ctxs[p], ctypes.c_void_p(out[p]), L.SCALAR_FR) for p in range(n)]
 
 

@@ -141,7 +141,8 @@ int cozk_vec_add_scalar(cozk_ctx* ctx, cozk_vec* v, const uint64_t s[4]);
  * The element-wise product of two degree-t sharings has degree 2t and can only be opened (from 2t + 1 parties); a product
  * that is a degree-t sharing again, so that products chain, is cozk_shamir_mul_{deal, inproc, vec} below.  The reference has
  * no Shamir network, degree reduction or prover; the multiplication here is the classic one-round resharing (GRR / BGW),
- * restated in tests/shamir_mul_ref.py; there is no Shamir prover. */
+ * restated in tests/shamir_mul_ref.py, and beside it the king variant with preprocessed double-random pairs
+ * (cozk_shamir_rand_*, cozk_shamir_mul_king_*; tests/shamir_dn_ref.py); there is no Shamir prover. */
 #define COZK_SHAMIR_MAX_PARTIES 32
 #define COZK_SHAMIR_MAX_DEGREE 15 /* of a dealt sharing: 2t + 1 <= 32 parties can still open a product */
 /* share_field_elements (mpc-types/src/protocols/shamir.rs:58-77; `share` :190-207): out[p][i] = f_i(p + 1) with
@@ -206,6 +207,79 @@ int cozk_shamir_mul_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* a
  * the length).  Refused without a ring and when 2 * degree + 1 exceeds the ring's ranks. */
 int cozk_shamir_mul_vec(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, const uint8_t* keys, int degree,
                         uint64_t counter, cozk_vec** out);
+
+/* Shamir multiplication with a king and preprocessed double-random pairs (Damgard-Nielsen; semi-honest like the rest of the
+ * Shamir seam; restated in tests/shamir_dn_ref.py, the reference has none of it).  Against the resharing above, the online step
+ * moves 2t vectors into one party and n - 1 out of it instead of (2t + 1)(n - 1), in two rounds instead of one, and everything
+ * that needs fresh randomness happens OFFLINE, before the factors exist.  t = degree, n = num_parties, with
+ *   1 <= t, 2t <= COZK_SHAMIR_MAX_DEGREE (the degree-2t sharing goes through the dealing kernel too), 2t + 1 <= n <= 32.
+ *
+ * Offline.  Party p holds 3t + 1 private PRF keys: keys[0] gives its secret stream s_p[i] = PRF(keys[0], counter + i),
+ * keys[1..t] the coefficients of a degree-t polynomial f_i, keys[t + 1..3t] those of a degree-2t polynomial g_i, with
+ * f_i(0) = g_i(0) = s_p[i] and coefficient c of element i = PRF(key_c, counter + i) as in cozk_shamir_share_vec.  It deals
+ * u_{p->q}[i] = f_i(q + 1) and w_{p->q}[i] = g_i(q + 1) to every q; party q then computes, for k = 0..n - t - 1,
+ *   rt_q^k[i] = sum_{p=0..n-1} (p + 1)^k u_{p->q}[i]   and likewise r2t_q^k from the w
+ * (the (n - t) x n Vandermonde matrix on the points 1..n).  Pair k is (rt^k, r2t^k): a degree-t and a degree-2t sharing of one
+ * value that no t parties know.  One exchange yields n - t pairs.  (key, counter range) pairs must not be reused, and A PAIR
+ * MUST NEVER BE USED TWICE: using it for two multiplications reveals the difference of the two products.  Both are the
+ * caller's contract; there is no pool or bookkeeping object for pairs.
+ *
+ * cozk_shamir_rand_deal: this party's dealing, out_t[q] = u_{->q} and out_2t[q] = w_{->q}, two tables of num_parties handles
+ * in ctx, in two launches of the dealing kernel (degree t, degree 2t) that both recompute the secret: it is never stored.
+ * keys = (3 * degree + 1) x 32 bytes.  On any failure both tables are NULL in [0, num_parties) (untouched when num_parties
+ * itself is out of range). */
+int cozk_shamir_rand_deal(cozk_ctx* ctx, size_t n_elems, const uint8_t* keys, int degree, int num_parties, uint64_t counter,
+                          cozk_vec** out_t, cozk_vec** out_2t);
+/* the Vandermonde step on ONE set of received vectors: out[k][i] = sum_{j < num_parties} (j + 1)^k recv[j][i], k < count;
+ * out = count handles in ctx.  One kernel reads every input once per tile of 8 outputs.  2 <= num_parties <= 32 FR vectors of
+ * one length, 1 <= count <= num_parties - 1.  PRIVACY NEEDS count <= n - t where t parties may collude: the drivers below
+ * call it once per degree with count = n - t; a larger count is arithmetic only.  As for cozk_shamir_combine_vec the inputs
+ * need not be vectors of ctx (a transport may have filled them): they are read on ctx's stream, and ordering that read behind
+ * whatever wrote a vector of another context is the caller's job.  On failure out[0..count) is NULL (untouched when count is
+ * outside 1..32). */
+int cozk_shamir_rand_extract(cozk_ctx* ctx, const cozk_vec* const* recv, int num_parties, int count, cozk_vec** out);
+/* the whole preprocessing for num_parties parties driven from the one thread that owns their contexts (the same or different
+ * GPUs), in the style of cozk_shamir_mul_inproc, one degree after the other: receive vectors from the recipients' allocators,
+ * every party's stream drained before a dealer's stream writes another party's block (in place on the dealer's device, staged
+ * and moved by one peer copy per recipient otherwise), the dealers' streams synchronised, then each party's extraction on its
+ * own stream.  keys[p] = party p's (3 * degree + 1) x 32 bytes.  r_t[q * (n - t) + k] and r_2t[q * (n - t) + k] are party q's
+ * halves of pair k, vectors of party_ctxs[q].  On failure both tables are NULL in [0, n (n - t)) (untouched when
+ * 1 <= degree < num_parties <= 32 does not hold: their length is then unknown); the error text is left with party_ctxs[0]. */
+int cozk_shamir_rand_inproc(cozk_ctx* const* party_ctxs, const uint8_t* const* keys, size_t n_elems, int degree,
+                            int num_parties, uint64_t counter, cozk_vec** r_t, cozk_vec** r_2t);
+/* one party per process over the context's ring (num_parties = its ranks, this party = the context's rank): deal, two
+ * cozk_ring_all_to_all (one per degree; the own slot stays local), two extractions; all of it is enqueued on the context's
+ * stream and nothing waits on the host.  r_t, r_2t: ranks - degree handles each; NULL on failure where that length is known
+ * (a ring and 1 <= degree < ranks), untouched otherwise. */
+int cozk_shamir_rand_vec(cozk_ctx* ctx, size_t n_elems, const uint8_t* keys, int degree, uint64_t counter, cozk_vec** r_t,
+                         cozk_vec** r_2t);
+/* Online, consuming ONE pair.  The SENDERS are parties 0..2t (the convention of combine_field_elements and of the dealers
+ * above); `king` is any party 0..n - 1.
+ *   1. sender p computes m_p[i] = a_p[i] b_p[i] + r2t_p[i] and (unless it is the king) sends it to the king;
+ *   2. the king opens z = sum_{p<=2t} lambda_p m_p, lambda = lagrange(1..2t + 1) (cozk_shamir_combine_vec at degree 2t):
+ *      z = a b + r is public;
+ *   3. the king sends z to everyone, and party q's result is c_q = z - rt_q: a degree-t sharing of a b.
+ * A party above 2t needs neither factors nor r2t (whether or not it is the king).
+ *
+ * cozk_shamir_mul_mask is step 1 in ONE launch, *out = a b + r_2t (96 B read, 32 B written per element; the product is never
+ * stored): three FR vectors of one length; *out is NULL on failure. */
+int cozk_shamir_mul_mask(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, const cozk_vec* r_2t, cozk_vec** out);
+/* the whole online step with all parties in this process: the mask on each sender's own stream, written into the king's
+ * memory (in place on the king's device, staged and peer-copied from another), the senders' streams synchronised, the combine
+ * on the king's stream, z copied to the parties of other devices by that stream, which is then synchronised (parties of the
+ * king's device read z in place), the subtraction on each party's own stream; the streams that read z in place are
+ * synchronised before the king's pool takes it back.  a[p], b[p], r_2t[p] (p <= 2 * degree) and r_t[p] (every p) must be FR
+ * vectors of party_ctxs[p] of one length; a[p], b[p], r_2t[p] are not read for p > 2 * degree and may be NULL.  out[q] belongs
+ * to party_ctxs[q]; on failure out[0..num_parties) is NULL (untouched when num_parties is outside 1..32); the error text is
+ * left with party_ctxs[0]. */
+int cozk_shamir_mul_king_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* a, const cozk_vec* const* b,
+                                const cozk_vec* const* r_t, const cozk_vec* const* r_2t, int degree, int num_parties, int king,
+                                cozk_vec** out);
+/* one party per process over the context's ring: two cozk_ring_all_to_all with empty slots -- the gather to the king, the
+ * king's fan-out -- around the king's combine, then the subtraction; stream-ordered, no host wait.  Every party needs r_t (it
+ * also gives the length); a party 0..2 * degree also a, b and r_2t; all must be vectors of ctx.  *out is NULL on failure. */
+int cozk_shamir_mul_king_vec(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, const cozk_vec* r_t, const cozk_vec* r_2t,
+                             int degree, int king, cozk_vec** out);
 
 /* ---------------------------------------------------------------- MSM seam ---------------- */
 /* Upload SRS points (`ck.powers_of_g[i]`, co-jolt/src/poly/commitment/pst13.rs:286-287,461-462) once;

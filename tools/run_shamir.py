@@ -12,7 +12,14 @@ With --mul, instead, the multiplication with degree reduction (needs 2 * degree 
         with (v) in this process, outputs compared once;
   (vii) the whole in-process multiplication cozk_shamir_mul_inproc, one context per party on this GPU: from a device event
         recorded while every stream is idle to the last of the events recorded behind each party's finish.
-  python tools/run_shamir.py --mul --log-n 22 --parties 8 --degree 2 [--out FILE]"""
+  python tools/run_shamir.py --mul --log-n 22 --parties 8 --degree 2 [--out FILE]
+With --mul --king, instead, the multiplication with a king and double-random pairs (needs 2 * degree <= 15 too):
+  (viii) the Vandermonde extraction cozk_shamir_rand_extract (parties inputs, parties - degree outputs) against the same from
+         cozk_vec_scale + cozk_vec_binop, alternating in this process, outputs compared once;
+  (ix)   the whole online step cozk_shamir_mul_king_inproc against the whole cozk_shamir_mul_inproc, one context per party on
+         this GPU, alternating, each timed as (vii) is; both open to the product of the secrets;
+  (x)    the whole offline step cozk_shamir_rand_inproc, timed the same way, and its cost per pair.
+  python tools/run_shamir.py --mul --king --log-n 22 --parties 8 --degree 2 [--out FILE]"""
 import argparse, ctypes, importlib, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -25,6 +32,7 @@ ap.add_argument("--degree", type=int, default=2)
 ap.add_argument("--out", default=None)
 ap.add_argument("--min-seconds", type=float, default=1.0)
 ap.add_argument("--mul", action="store_true", help="time the multiplication with degree reduction instead")
+ap.add_argument("--king", action="store_true", help="with --mul: time the king / double-random variant against the resharing")
 args = ap.parse_args()
 cozk = importlib.import_module("co-zkvms_amd")
 L = cozk._lib
@@ -191,6 +199,138 @@ def mul_legs():
                   "stream synchronisations of the call included",
     })
 
+
+def king_legs():
+    if 2 * T + 1 > N or 2 * T > 15:
+        raise SystemExit("run_shamir --mul --king: needs 2 * degree + 1 <= parties and 2 * degree <= 15")
+    CNT, D = N - T, 2 * T + 1
+    spread = lambda ts: round((sorted(ts)[-1] - sorted(ts)[0]) / med(ts), 4)
+
+    # (viii): extraction, one kernel against scale + binop
+    recv = [cozk.Vec.random(ctx, n, seed=3000 + j) for j in range(N)]
+    zero = cozk.Vec.from_numpy(ctx, np.zeros((n, 4), dtype=np.uint64))
+
+    def fused_extract():
+        return cozk.shamir_rand_extract(ctx, recv, CNT)
+
+    def composed_extract():
+        """w_j = s_j; per output: the sum of the w_j by binop(ADD), then w_j *= j + 1 by scale"""
+        w = [v.binop(cozk.OP_ADD, zero) for v in recv]  # copies: scale works in place
+        out = []
+        for k in range(CNT):
+            acc = w[0].binop(cozk.OP_ADD, w[1])
+            for j in range(2, N):
+                nxt = acc.binop(cozk.OP_ADD, w[j])
+                acc.free()
+                acc = nxt
+            out.append(acc)
+            if k + 1 < CNT:
+                for j in range(1, N):
+                    w[j].scale(j + 1)
+        free(w)
+        return out
+
+    f, c = fused_extract(), composed_extract()
+    equal = all(np.array_equal(x.to_numpy(), y.to_numpy()) for x, y in zip(f, c))
+    free(f), free(c)
+    assert equal, "the extraction kernel and scale + binop differ"
+    for _ in range(2):
+        free(timed(fused_extract)[1]), free(timed(composed_extract)[1])
+    t_f, t_c = [], []
+    while sum(t_f) < args.min_seconds * 1e3 or sum(t_c) < args.min_seconds * 1e3 or len(t_f) < 5:  # alternating
+        ms, r = timed(fused_extract); t_f.append(ms); free(r)
+        ms, r = timed(composed_extract); t_c.append(ms); free(r)
+    free(recv), free(zero)
+
+    # (ix), (x): one context per party on this GPU
+    pcs = [cozk.Context(0) for _ in range(N)]
+    streams = []
+    for pc in pcs:
+        h = ctypes.c_void_p()
+        pc.check(pc._l.cozk_ctx_stream(pc.h, ctypes.byref(h)))
+        streams.append(torch.cuda.ExternalStream(h.value))
+    sa, sb = A.shamir_scatter(keys_a, T, pcs, counter=0), B.shamir_scatter(keys_b, T, pcs, counter=0)
+    grr_keys = [[key(1000 + 16 * p + c) for c in range(T)] for p in range(N)]
+    dn_keys = [[key(2000 + 32 * p + c) for c in range(3 * T + 1)] for p in range(N)]
+
+    def whole(fn):
+        for pc in pcs:
+            pc.synchronize()
+        e0 = torch.cuda.Event(enable_timing=True)
+        e0.record(streams[0])  # every stream is idle: the call starts by draining them
+        out = fn()
+        ends = []
+        for st in streams:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record(st)
+            ends.append(e)
+        for e in ends:
+            e.synchronize()
+        return max(e0.elapsed_time(e) for e in ends), out
+
+    flat = lambda pairs: [h for p in pairs for xy in p for h in xy]
+    rand = lambda: cozk.shamir_rand(pcs, dn_keys, n, T, counter=0)
+    ms, pairs = whole(rand)  # warm-up; these pairs feed the online leg
+    r_t, r_2t = [p[0][0] for p in pairs], [p[0][1] for p in pairs]
+    grr = lambda: cozk.shamir_mul(pcs, sa, sb, grr_keys, T, counter=n)
+    king = lambda: cozk.shamir_mul_king(pcs, sa, sb, r_t, r_2t, T, king=0)  # the pair is reused across repetitions: timing only
+    pts = list(range(N, N - T - 1, -1))
+    want = A.binop(cozk.OP_MUL, B)
+    opens = {}
+    for name, fn in (("grr", grr), ("king", king)):  # warm-up and correctness: t + 1 parties from the high end open a x b
+        ms, out = whole(fn)
+        for pc in pcs:
+            pc.synchronize()
+        opened = cozk.shamir_combine([out[p - 1] for p in pts], pts, T)
+        opens[name] = bool(np.array_equal(opened.to_numpy(), want.to_numpy()))
+        free(opened), free(out)
+        assert opens[name], "the in-process %s multiplication did not open the product of the secrets from degree + 1 parties" % name
+    free(want)
+    t_g, t_k = [], []
+    while sum(t_g) < args.min_seconds * 1e3 or sum(t_k) < args.min_seconds * 1e3 or len(t_g) < 5:  # alternating
+        ms, out = whole(grr); t_g.append(ms); free(out)
+        ms, out = whole(king); t_k.append(ms); free(out)
+    t_r = []
+    while sum(t_r) < args.min_seconds * 1e3 or len(t_r) < 5:
+        ms, out = whole(rand); t_r.append(ms); free(flat(out))
+    free(flat(pairs)), free(sa), free(sb)
+    for pc in pcs:
+        pc.close()
+
+    ext_bytes = (N + CNT) * 32 * n
+    comp_bytes = (N * 96 + CNT * (N - 1) * 96 + (CNT - 1) * (N - 1) * 64) * n
+    grr_bytes = D * (2 + N) * 32 * n + N * (D + 1) * 32 * n
+    king_bytes = D * 128 * n + (D + 1) * 32 * n + N * 96 * n
+    rand_bytes = (N * N * 32 + N * (N + CNT) * 32) * 2 * n
+    emit({
+        "what": "Shamir multiplication with a king and double-random pairs: extraction kernel vs scale + binop, whole online step vs the "
+                "resharing multiplication, whole offline step",
+        "log_n": args.log_n, "parties": N, "degree": T, "senders": D, "pairs_per_exchange": CNT, "device": torch.cuda.get_device_name(0),
+        "extract": dict(stats(t_f), algorithmic_bytes=ext_bytes, bytes_per_s=round(ext_bytes / (med(t_f) * 1e-3), 1),
+                        spread_max_minus_min_over_median=spread(t_f), launches=-(-CNT // 8), inputs=N, outputs=CNT),
+        "composed_scale_and_add": dict(stats(t_c), bytes_moved_by_the_composition=comp_bytes, spread_max_minus_min_over_median=spread(t_c),
+                                       launches=N + CNT * (N - 1) + (CNT - 1) * (N - 1)),
+        "extract_vs_composed_speedup": round(med(t_c) / med(t_f), 3),
+        "outputs_equal": bool(equal),
+        "inproc_mul_king": dict(stats(t_k), algorithmic_bytes=king_bytes, bytes_per_s=round(king_bytes / (med(t_k) * 1e-3), 1),
+                                launches=D + 1 + N, contexts=N, king=0, opens_from_degree_plus_1=opens["king"]),
+        "inproc_mul_grr_same_run": dict(stats(t_g), algorithmic_bytes=grr_bytes, bytes_per_s=round(grr_bytes / (med(t_g) * 1e-3), 1),
+                                        launches=D + N, contexts=N, opens_from_degree_plus_1=opens["grr"]),
+        "king_vs_grr_time_ratio": round(med(t_k) / med(t_g), 3),
+        "vectors_on_the_online_path": {"king": 2 * T + N - 1, "grr": D * (N - 1)},
+        "inproc_rand": dict(stats(t_r), algorithmic_bytes=rand_bytes, bytes_per_s=round(rand_bytes / (med(t_r) * 1e-3), 1),
+                            launches=2 * N + 2 * N * -(-CNT // 8), contexts=N, pairs=CNT, median_ms_per_pair=round(med(t_r) / CNT, 4)),
+        "timing": "device events around each repetition (allocation from the contexts' pools included); the extraction legs alternating on one "
+                  "stream; the in-process legs from an event on party 0's idle stream before the call to the last of the events behind the "
+                  "parties' last kernels, host-side stream synchronisations of the call included, king and resharing alternating; the online "
+                  "leg reuses one pair across repetitions (timing only: a pair must never be used twice)",
+    })
+
+
+if args.mul and args.king:
+    king_legs()
+    ctx.close()
+    raise SystemExit(0)
 
 if args.mul:
     mul_legs()
