@@ -131,6 +131,18 @@ SIGNATURES = {
     "cozk_shamir_combine_vec": (_i, [_vp, _vp, _vp, _sz, _i, _pp]),
     "cozk_shamir_mul_deal": (_i, [_vp, _vp, _vp, ctypes.c_char_p, _i, _i, _u64, _vp]),
     "cozk_shamir_mul_inproc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _u64, _vp]),
+    "cozk_shamir_mul_deal_pairs": (_i, [_vp, _vp, ctypes.c_char_p, _i, _i, _u64, _vp]),
+    "cozk_shamir_mul_pairs_inproc": (_i, [_vp, _vp, _vp, _i, _i, _u64, _vp]),
+    "cozk_shamir_gp_prove_inproc": (_i, [_vp, _vp, _sz, _vp, _vp, _i, _i, _u64, _u64, ctypes.c_char_p, _i, _pp]),
+    "cozk_shamir_gp_free": (_i, [_vp]),
+    "cozk_shamir_gp_get_result": (_i, [_vp, _vp]),
+    "cozk_shamir_gp_proof_bytes": (_i, [_vp, _vp, _sz]),
+    "cozk_shamir_gp_point_len": (_sz, [_vp]),
+    "cozk_shamir_gp_final": (_i, [_vp, _vp, _vp]),
+    "cozk_shamir_gp_msgs_len": (_sz, [_vp]),
+    "cozk_shamir_gp_msgs": (_i, [_vp, _vp, _sz]),
+    "cozk_shamir_gp_finals_len": (_sz, [_vp]),
+    "cozk_shamir_gp_finals": (_i, [_vp, _vp, _sz]),
     "cozk_shamir_mul_vec": (_i, [_vp, _vp, _vp, ctypes.c_char_p, _i, _u64, _pp]),
     "cozk_shamir_rand_deal": (_i, [_vp, _sz, ctypes.c_char_p, _i, _i, _u64, _vp, _vp]),
     "cozk_shamir_rand_extract": (_i, [_vp, _vp, _i, _i, _vp]),

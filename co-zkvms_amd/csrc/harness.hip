@@ -909,3 +909,4 @@ int cozk_worker_spartan_second_sumcheck(cozk_ctx* ctx, const cozk_worker_params*
 #include "host/lookups_harness.hpp"
 #include "host/outer_harness.hpp"
 #include "host/flow_harness.hpp"
+#include "host/shamir_gp.hpp"

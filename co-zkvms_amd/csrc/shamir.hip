@@ -47,7 +47,9 @@ static __device__ __forceinline__ fe fr_mul_small_add(const fe& a, uint32_t p, c
 // shares[p][i] = f_i(p + 1), f_i(x) = v[i] + sum_{c = 1..degree} coef_c[i] x^c (shamir.rs:190-207 `share`, :166-175
 // `evaluate_poly`).  A lane owns element i: it obtains its `degree` coefficients once (PRF blocks, or loads), keeps them
 // in registers, runs one Horner chain per party and stores n field elements: 32 B read and n * 32 B written per element
-// (64 B read where the secret is the product of two share vectors, ShamirMulPrfSrc: the re-deal of a multiplication).
+// (64 B read where the secret is the product of two share vectors, ShamirMulPrfSrc: the re-deal of a multiplication; the
+// same 64 B, contiguous per lane, where the two factors are the interleaved halves L[i] = v[2 i], R[i] = v[2 i + 1] of one GKR
+// layer, ShamirPairsPrfSrc: the re-deal of a tree level of the grand product).
 // prf_fr (prf.hip.hpp) with the two halves of the block read through constant indices: the same value, and fifteen inlined
 // copies of it keep their block words in registers
 static __device__ __forceinline__ fe shamir_prf_fr(const prf_key key, uint64_t j) {
@@ -90,6 +92,10 @@ struct ShamirPrfSrc : ShamirPrfCoefs {  // a secret vector, PRF coefficients
 struct ShamirMulPrfSrc : ShamirPrfCoefs {  // the secret is the product a[i] b[i] of two share vectors, never stored (GRR re-deal)
     const fe *a, *b;
     __device__ __forceinline__ fe value(size_t i) const { return Fr::mul(fe_load(a + i), fe_load(b + i)); }
+};
+struct ShamirPairsPrfSrc : ShamirPrfCoefs {  // the secret is the product v[2 i] v[2 i + 1] of one interleaved GKR layer, never stored (a tree level)
+    const fe* v;
+    __device__ __forceinline__ fe value(size_t i) const { return Fr::mul(fe_load(v + 2 * i), fe_load(v + 2 * i + 1)); }
 };
 struct ShamirRandPrfSrc : ShamirPrfCoefs {  // the secret is itself a PRF element, never stored (double-random pairs, offline)
     prf_key key0;
@@ -288,6 +294,12 @@ static void require_factors(const char* who, const cozk_vec* a, const cozk_vec* 
     COZK_REQUIRE(a->n == b->n, w + ": the factors must have one length");
 }
 
+static void require_pairs(const char* who, const cozk_vec* v) {
+    const std::string w(who);
+    COZK_REQUIRE(v->kind == COZK_SCALAR_FR, w + ": the layer must be an FR vector");
+    COZK_REQUIRE(v->n % 2 == 0, w + ": the layer must have an even length (L[j] = v[2 j], R[j] = v[2 j + 1])");
+}
+
 static void free_all(cozk_vec** out, int n) {
     for (int p = 0; p < n; p++) {
         cozk_vec_free(out[p]);
@@ -330,6 +342,13 @@ static ShamirMulPrfSrc mul_prf_src(const cozk_vec* a, const cozk_vec* b, const u
     fill_prf_coefs(src, keys, degree, counter);
     src.a = (const fe*)a->d;
     src.b = (const fe*)b->d;
+    return src;
+}
+
+static ShamirPairsPrfSrc pairs_prf_src(const cozk_vec* v, const uint8_t* keys, int degree, uint64_t counter) {
+    ShamirPairsPrfSrc src;
+    fill_prf_coefs(src, keys, degree, counter);
+    src.v = (const fe*)v->d;
     return src;
 }
 
@@ -525,26 +544,15 @@ int cozk_shamir_mul_deal(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, co
     return rc;
 }
 
-int cozk_shamir_mul_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* a, const cozk_vec* const* b, const uint8_t* const* keys,
-                           int degree, int num_parties, uint64_t counter, cozk_vec** out) {
-    cozk_ctx* const c0 = party_ctxs && num_parties >= 1 ? party_ctxs[0] : nullptr;  // receives the error message
-    if (int rc0 = require_out(c0, out, "shamir_mul_inproc: null output")) return rc0;
-    clear_outputs(out, num_parties);
+}  // extern "C"
+
+// what cozk_shamir_mul_inproc and cozk_shamir_mul_pairs_inproc share, behind their argument checks: n elements per party,
+// src_of(p) = dealer p's source for the dealing kernel
+template <class SrcOf>
+static int mul_inproc_drive(cozk_ctx* const* party_ctxs, size_t n, int degree, int num_parties, cozk_vec** out, SrcOf src_of) {
+    cozk_ctx* const c0 = party_ctxs[0];
     const int dealers = 2 * degree + 1;
-    int rc = cozk_guard(c0, [&] {
-        COZK_REQUIRE(party_ctxs && a && b && keys, "shamir_mul_inproc: null argument");
-        require_mul_args("shamir_mul_inproc", degree, num_parties);
-        for (int p = 0; p < num_parties; p++) COZK_REQUIRE(party_ctxs[p], "shamir_mul_inproc: null party context");
-        for (int p = 0; p < dealers; p++) {
-            COZK_REQUIRE(a[p] && b[p], "shamir_mul_inproc: parties 0..2 * degree need both factors");
-            require_factors("shamir_mul_inproc", a[p], b[p]);
-            COZK_REQUIRE(a[p]->n == a[0]->n, "shamir_mul_inproc: the factors must have one length");
-            COZK_REQUIRE(a[p]->ctx == party_ctxs[p] && b[p]->ctx == party_ctxs[p], "shamir_mul_inproc: party p's factors must be vectors of party_ctxs[p]");
-            COZK_REQUIRE(keys[p], "shamir_mul_inproc: parties 0..2 * degree need their key block");
-        }
-    });
-    if (rc != COZK_OK) return rc;
-    const size_t n = a[0]->n;
+    int rc = COZK_OK;
     std::vector<cozk_vec*> recv((size_t)num_parties * dealers, nullptr);  // recv[q * dealers + p] = h_{p -> q}, a block of party q
     std::vector<fe*> stage(dealers, nullptr);
     // a failure of party p's step leaves its text with party 0 and nothing allocated
@@ -577,7 +585,7 @@ int cozk_shamir_mul_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* a
                 size_t r = 0;
                 for (int q = 0; q < num_parties; q++)
                     o.p[q] = party_ctxs[q]->device != dealer->device ? stage[p] + n * r++ : (fe*)recv[(size_t)q * dealers + p]->d;
-                launch_share(dealer->stream, mul_prf_src(a[p], b[p], keys[p], degree, counter), o, n, degree, num_parties);
+                launch_share(dealer->stream, src_of(p), o, n, degree, num_parties);
                 for (int q = 0; q < num_parties; q++)
                     if (party_ctxs[q]->device != dealer->device)
                         HIP_TRY(hipMemcpyPeerAsync(recv[(size_t)q * dealers + p]->d, party_ctxs[q]->device, o.p[q], dealer->device, n * sizeof(fe),
@@ -605,6 +613,71 @@ int cozk_shamir_mul_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* a
         }
     }
     return COZK_OK;
+}
+
+extern "C" {
+
+int cozk_shamir_mul_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* a, const cozk_vec* const* b, const uint8_t* const* keys,
+                           int degree, int num_parties, uint64_t counter, cozk_vec** out) {
+    cozk_ctx* const c0 = party_ctxs && num_parties >= 1 ? party_ctxs[0] : nullptr;  // receives the error message
+    if (int rc0 = require_out(c0, out, "shamir_mul_inproc: null output")) return rc0;
+    clear_outputs(out, num_parties);
+    const int dealers = 2 * degree + 1;
+    int rc = cozk_guard(c0, [&] {
+        COZK_REQUIRE(party_ctxs && a && b && keys, "shamir_mul_inproc: null argument");
+        require_mul_args("shamir_mul_inproc", degree, num_parties);
+        for (int p = 0; p < num_parties; p++) COZK_REQUIRE(party_ctxs[p], "shamir_mul_inproc: null party context");
+        for (int p = 0; p < dealers; p++) {
+            COZK_REQUIRE(a[p] && b[p], "shamir_mul_inproc: parties 0..2 * degree need both factors");
+            require_factors("shamir_mul_inproc", a[p], b[p]);
+            COZK_REQUIRE(a[p]->n == a[0]->n, "shamir_mul_inproc: the factors must have one length");
+            COZK_REQUIRE(a[p]->ctx == party_ctxs[p] && b[p]->ctx == party_ctxs[p], "shamir_mul_inproc: party p's factors must be vectors of party_ctxs[p]");
+            COZK_REQUIRE(keys[p], "shamir_mul_inproc: parties 0..2 * degree need their key block");
+        }
+    });
+    if (rc != COZK_OK) return rc;
+    return mul_inproc_drive(party_ctxs, a[0]->n, degree, num_parties, out, [&](int p) { return mul_prf_src(a[p], b[p], keys[p], degree, counter); });
+}
+
+int cozk_shamir_mul_deal_pairs(cozk_ctx* ctx, const cozk_vec* v, const uint8_t* keys, int degree, int num_parties, uint64_t counter, cozk_vec** out) {
+    if (int rc0 = require_out(ctx, out, "shamir_mul_deal_pairs: null output")) return rc0;
+    clear_outputs(out, num_parties);
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && v && keys, "shamir_mul_deal_pairs: null argument");
+        require_pairs("shamir_mul_deal_pairs", v);
+        require_mul_args("shamir_mul_deal_pairs", degree, num_parties);
+    });
+    if (rc != COZK_OK) return rc;
+    const size_t m = v->n / 2;
+    rc = alloc_outputs(ctx, nullptr, m, num_parties, out);
+    if (rc != COZK_OK) return rc;
+    rc = cozk_guard(ctx, [&] {
+        if (m == 0) return;
+        launch_share(ctx->stream, pairs_prf_src(v, keys, degree, counter), out_table(out, num_parties), m, degree, num_parties);
+    });
+    if (rc != COZK_OK) free_all(out, num_parties);
+    return rc;
+}
+
+int cozk_shamir_mul_pairs_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* v, const uint8_t* const* keys, int degree, int num_parties,
+                                 uint64_t counter, cozk_vec** out) {
+    cozk_ctx* const c0 = party_ctxs && num_parties >= 1 ? party_ctxs[0] : nullptr;  // receives the error message
+    if (int rc0 = require_out(c0, out, "shamir_mul_pairs_inproc: null output")) return rc0;
+    clear_outputs(out, num_parties);
+    int rc = cozk_guard(c0, [&] {
+        COZK_REQUIRE(party_ctxs && v && keys, "shamir_mul_pairs_inproc: null argument");
+        require_mul_args("shamir_mul_pairs_inproc", degree, num_parties);
+        for (int p = 0; p < num_parties; p++) COZK_REQUIRE(party_ctxs[p], "shamir_mul_pairs_inproc: null party context");
+        for (int p = 0; p < 2 * degree + 1; p++) {
+            COZK_REQUIRE(v[p], "shamir_mul_pairs_inproc: parties 0..2 * degree need their layer");
+            require_pairs("shamir_mul_pairs_inproc", v[p]);
+            COZK_REQUIRE(v[p]->n == v[0]->n, "shamir_mul_pairs_inproc: the layers must have one length");
+            COZK_REQUIRE(v[p]->ctx == party_ctxs[p], "shamir_mul_pairs_inproc: party p's layer must be a vector of party_ctxs[p]");
+            COZK_REQUIRE(keys[p], "shamir_mul_pairs_inproc: parties 0..2 * degree need their key block");
+        }
+    });
+    if (rc != COZK_OK) return rc;
+    return mul_inproc_drive(party_ctxs, v[0]->n / 2, degree, num_parties, out, [&](int p) { return pairs_prf_src(v[p], keys[p], degree, counter); });
 }
 
 int cozk_shamir_mul_vec(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, const uint8_t* keys, int degree, uint64_t counter, cozk_vec** out) {

@@ -356,6 +356,13 @@ class Vec:
         self.ctx.check(self.ctx._l.cozk_shamir_mul_deal(self.ctx.h, self.h, other.h, _shamir_keys(keys), degree, num_parties, counter, out))
         return [Vec(self.ctx, ctypes.c_void_p(out[p]), L.SCALAR_FR) for p in range(num_parties)]
 
+    def shamir_mul_deal_pairs(self, keys, degree, num_parties, counter=0):
+        """shamir_mul_deal of one interleaved GKR layer (cozk_shamir_mul_deal_pairs): the num_parties share vectors of a fresh
+        degree-`degree` sharing of self[2 j] * self[2 j + 1], in one launch; the length must be even"""
+        out = (ctypes.c_void_p * max(num_parties, 1))()
+        self.ctx.check(self.ctx._l.cozk_shamir_mul_deal_pairs(self.ctx.h, self.h, _shamir_keys(keys), degree, num_parties, counter, out))
+        return [Vec(self.ctx, ctypes.c_void_p(out[p]), L.SCALAR_FR) for p in range(num_parties)]
+
     def shamir_mul_mask(self, other, r_2t):
         """self[i] * other[i] + r_2t[i] in one launch (cozk_shamir_mul_mask): what a party 0..2 * degree sends to the king"""
         h = ctypes.c_void_p()
@@ -421,11 +428,88 @@ def shamir_mul(party_ctxs, a_shares, b_shares, keys_per_party, degree, counter=0
     ctxs = arr([c.h for c in party_ctxs])
     a = arr([None if v is None else v.h for v in a_shares])
     b = arr([None if v is None else v.h for v in b_shares])
-    blocks = [None if k is None else ctypes.create_string_buffer(_shamir_keys(k), max(32 * len(k), 1)) for k in keys_per_party]
-    keys = arr([None if k is None else ctypes.addressof(k) for k in blocks])
+    blocks, keys = _key_blocks(n, keys_per_party)
     out = (ctypes.c_void_p * max(n, 1))()
     party_ctxs[0].check(party_ctxs[0]._l.cozk_shamir_mul_inproc(ctxs, a, b, keys, degree, n, counter, out))
     return [Vec(party_ctxs[p], ctypes.c_void_p(out[p]), L.SCALAR_FR) for p in range(n)]
+
+
+def _key_blocks(n, keys_per_party):
+    """per-party key blocks for the in-process drivers: (the buffers, to be kept alive; the pointer table)"""
+    blocks = [None if k is None else ctypes.create_string_buffer(_shamir_keys(k), max(32 * len(k), 1)) for k in keys_per_party]
+    return blocks, (ctypes.c_void_p * max(n, 1))(*[None if k is None else ctypes.addressof(k) for k in blocks])
+
+
+def shamir_mul_pairs(party_ctxs, layers, keys_per_party, degree, counter=0):
+    """one tree level of a grand product, all parties in this process (cozk_shamir_mul_pairs_inproc): layers[p] = party p's share
+    vector of an interleaved layer (even length 2m); returns per party its share vector of the m products layer[2 j] * layer[2 j + 1],
+    a degree-`degree` sharing again.  layers[p] and keys_per_party[p] may be None for p > 2 * degree"""
+    n = len(party_ctxs)
+    ctxs = (ctypes.c_void_p * max(n, 1))(*[c.h for c in party_ctxs])
+    blocks, keys = _key_blocks(n, keys_per_party)
+    out = (ctypes.c_void_p * max(n, 1))()
+    party_ctxs[0].check(party_ctxs[0]._l.cozk_shamir_mul_pairs_inproc(ctxs, _handles(n, layers), keys, degree, n, counter, out))
+    return [Vec(party_ctxs[p], ctypes.c_void_p(out[p]), L.SCALAR_FR) for p in range(n)]
+
+
+class ShamirGpResult(ctypes.Structure):
+    """cozk_shamir_gp_result"""
+    _fields_ = [("verified", ctypes.c_int), ("n_layers", ctypes.c_int), ("proof_len", ctypes.c_uint64), ("n_opened", ctypes.c_uint64),
+                ("t_construct_ms", ctypes.c_double), ("t_prove_ms", ctypes.c_double)]
+
+
+class ShamirGpProof:
+    """what shamir_gp_prove returns: .proof_bytes, the final .claim and point .r (canonical ints), .result (ShamirGpResult), and
+    what went over the star -- .msgs[m][p], sender p's masked message of opening m, and .finals[layer, top first][p] = (L, R),
+    opener p's final-claim shares"""
+
+    def __init__(self, l, h, degree):
+        res = ShamirGpResult()
+        def ok(rc):
+            if rc != L.OK:
+                raise L.CozkError(rc, "shamir_gp accessor")
+
+        ok(l.cozk_shamir_gp_get_result(h, ctypes.byref(res)))
+        self.result = res
+        buf = (ctypes.c_uint8 * max(int(res.proof_len), 1))()
+        ok(l.cozk_shamir_gp_proof_bytes(h, buf, int(res.proof_len)))
+        self.proof_bytes = bytes(buf)[:int(res.proof_len)]
+        nr = l.cozk_shamir_gp_point_len(h)
+        claim, r = np.zeros(4, dtype=np.uint64), np.zeros((max(nr, 1), 4), dtype=np.uint64)
+        ok(l.cozk_shamir_gp_final(h, claim.ctypes.data, r.ctypes.data))
+        self.claim, self.r = mont_limbs_to_int(claim)[0], mont_limbs_to_int(r[:nr])
+
+        def table(length, get):
+            k = length(h)
+            raw = np.zeros((max(k, 1), 4), dtype=np.uint64)
+            ok(get(h, raw.ctypes.data, k))
+            return mont_limbs_to_int(raw[:k])
+
+        s = 2 * degree + 1
+        flat = table(l.cozk_shamir_gp_msgs_len, l.cozk_shamir_gp_msgs)
+        self.msgs = [flat[i:i + s] for i in range(0, len(flat), s)]
+        flat = table(l.cozk_shamir_gp_finals_len, l.cozk_shamir_gp_finals)
+        pairs = [(flat[i], flat[i + 1]) for i in range(0, len(flat), 2)]
+        self.finals = [pairs[i:i + degree + 1] for i in range(0, len(pairs), degree + 1)]
+
+
+def shamir_gp_prove(party_ctxs, leaves, batch_size, mul_keys, rand_keys, degree, mul_counter=0, rand_counter=0, label=b"cozk", verify=True):
+    """the dense batched grand product proved by len(party_ctxs) Shamir parties in this process (cozk_shamir_gp_prove_inproc):
+    leaves[p] = party p's share vector of the interleaved leaves (not modified), mul_keys[p] = its `degree` keys of the tree's
+    multiplications, rand_keys[p] = its 3 * degree + 1 keys of the opening masks.  The proof is the plain prover's, byte for byte.
+    (rand_keys, rand_counter) and (mul_keys, mul_counter) ranges must never be used again.  Returns a ShamirGpProof"""
+    n = len(party_ctxs)
+    l = party_ctxs[0]._l
+    ctxs = (ctypes.c_void_p * max(n, 1))(*[c.h for c in party_ctxs])
+    mb, mk = _key_blocks(n, mul_keys)
+    rb, rk = _key_blocks(n, rand_keys)
+    h = ctypes.c_void_p()
+    party_ctxs[0].check(l.cozk_shamir_gp_prove_inproc(ctxs, _handles(n, leaves), batch_size, mk, rk, degree, n, mul_counter, rand_counter,
+                                                      bytes(label), 1 if verify else 0, ctypes.byref(h)))
+    try:
+        return ShamirGpProof(l, h, degree)
+    finally:
+        l.cozk_shamir_gp_free(h)
 
 
 def _handles(n, vs):
@@ -455,8 +539,7 @@ def shamir_rand(party_ctxs, keys_per_party, n, degree, counter=0):
     np_ = len(party_ctxs)
     cnt = np_ - degree
     ctxs = (ctypes.c_void_p * max(np_, 1))(*[c.h for c in party_ctxs])
-    blocks = [None if k is None else ctypes.create_string_buffer(_shamir_keys(k), max(32 * len(k), 1)) for k in keys_per_party]
-    keys = (ctypes.c_void_p * max(np_, 1))(*[None if k is None else ctypes.addressof(k) for k in blocks])
+    blocks, keys = _key_blocks(np_, keys_per_party)
     rt, r2t = (ctypes.c_void_p * max(np_ * cnt, 1))(), (ctypes.c_void_p * max(np_ * cnt, 1))()
     party_ctxs[0].check(party_ctxs[0]._l.cozk_shamir_rand_inproc(ctxs, keys, n, degree, np_, counter, rt, r2t))
     vec = lambda t, q, k: Vec(party_ctxs[q], ctypes.c_void_p(t[q * cnt + k]), L.SCALAR_FR)

@@ -142,7 +142,8 @@ int cozk_vec_add_scalar(cozk_ctx* ctx, cozk_vec* v, const uint64_t s[4]);
  * that is a degree-t sharing again, so that products chain, is cozk_shamir_mul_{deal, inproc, vec} below.  The reference has
  * no Shamir network, degree reduction or prover; the multiplication here is the classic one-round resharing (GRR / BGW),
  * restated in tests/shamir_mul_ref.py, and beside it the king variant with preprocessed double-random pairs
- * (cozk_shamir_rand_*, cozk_shamir_mul_king_*; tests/shamir_dn_ref.py); there is no Shamir prover. */
+ * (cozk_shamir_rand_*, cozk_shamir_mul_king_*; tests/shamir_dn_ref.py).  The one Shamir prover is the dense batched grand
+ * product, cozk_shamir_gp_prove_inproc at the end of this section (tests/shamir_gp_ref.py). */
 #define COZK_SHAMIR_MAX_PARTIES 32
 #define COZK_SHAMIR_MAX_DEGREE 15 /* of a dealt sharing: 2t + 1 <= 32 parties can still open a product */
 /* share_field_elements (mpc-types/src/protocols/shamir.rs:58-77; `share` :190-207): out[p][i] = f_i(p + 1) with
@@ -201,6 +202,18 @@ int cozk_shamir_mul_deal(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, co
  * failure rules as for cozk_shamir_mul_deal, the error text is left with party_ctxs[0]. */
 int cozk_shamir_mul_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* a, const cozk_vec* const* b,
                            const uint8_t* const* keys, int degree, int num_parties, uint64_t counter, cozk_vec** out);
+/* cozk_shamir_mul_deal for one interleaved GKR layer (Rep3DenseInterleavedPolynomial's layout, L[j] = v[2j], R[j] = v[2j+1]):
+ *   out[q][j] = v[2j] v[2j+1] + sum_{c=1..t} PRF(keys[c-1], counter + j) (q + 1)^c,   j < m,
+ * for an FR vector v of even length 2m (0 included), in ONE launch of the dealing kernel: 64 B read, contiguous per lane, and
+ * n x 32 B written per element; the product vector -- what cozk_layer_output_local would write and cozk_shamir_share_vec read
+ * back -- is never stored.  Argument and failure rules as for cozk_shamir_mul_deal; an odd length is refused on the host. */
+int cozk_shamir_mul_deal_pairs(cozk_ctx* ctx, const cozk_vec* v, const uint8_t* keys, int degree, int num_parties,
+                               uint64_t counter, cozk_vec** out);
+/* the whole multiplication of one tree level, out[q][j] = party q's share of v[2j] v[2j+1], for all parties driven from one
+ * thread: cozk_shamir_mul_inproc with that source (one driver serves both).  v[p]: party p's share vector of the layer, a
+ * vector of party_ctxs[p]; v[p] and keys[p] are not read for p > 2 * degree and may be NULL. */
+int cozk_shamir_mul_pairs_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* v, const uint8_t* const* keys,
+                                 int degree, int num_parties, uint64_t counter, cozk_vec** out);
 /* one party per process over the context's ring (cozk_ring_init with num_parties ranks; this party = the context's rank):
  * a dealer deals, exchanges (cozk_ring_all_to_all) and finishes, a party > 2 * degree receives and finishes; all of it is
  * enqueued on the context's stream and nothing waits on the host.  A dealer needs a, b and keys; another party only a (for
@@ -280,6 +293,58 @@ int cozk_shamir_mul_king_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* con
  * also gives the length); a party 0..2 * degree also a, b and r_2t; all must be vectors of ctx.  *out is NULL on failure. */
 int cozk_shamir_mul_king_vec(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, const cozk_vec* r_t, const cozk_vec* r_2t,
                              int degree, int king, cozk_vec** out);
+
+/* The dense batched grand product (GKR; Rep3BatchedDenseGrandProduct, co-jolt/src/subprotocols/grand_product.rs) proved by n
+ * Shamir parties, semi-honest, all driven from the one thread that owns their contexts and plays the coordinator
+ * (csrc/host/shamir_gp.hpp; restated in tests/shamir_gp_ref.py; the reference has no Shamir prover).  Every sumcheck term
+ * multiplies at most two secret factors (eq is public), so each party runs the COZK_MODE_PLAIN layer kernels on its share
+ * vectors with the PUBLIC claim as prev_claim and holds a degree-2t sharing of the plain prover's message: THE PROOF IS
+ * BYTE-IDENTICAL TO THE PLAIN PROVER'S PROOF OF THE SAME WITNESS, transcript order and layout those of the Rep3 coordinator.
+ *   construct  layer[0] = leaves, layer[i+1] = cozk_shamir_mul_pairs_inproc(layer[i]), log2(per circuit) - 1 levels; level i
+ *              uses the counter mul_counter + sum of the earlier levels' output lengths.
+ *   masks      M = batch_size + 4 sum_layers rounds(layer) openings of degree 2t.  Opening a locally computed degree-2t
+ *              sharing leaks more than its value unless it is re-randomised: ONE cozk_shamir_rand_inproc of M elements at
+ *              rand_counter, pair 0 only, zero_p[m] = r2t_p^0[m] - rt_p^0[m] (a degree-2t sharing of zero).  As for
+ *              cozk_shamir_mul_king_*, A PAIR MUST NEVER BE USED TWICE: (rand_keys, rand_counter .. rand_counter + M) must
+ *              not be used again, by another proof or by a king multiplication -- the caller's contract, like
+ *              (mul_keys, mul_counter .. + sum of the levels' lengths).
+ *   openings   indexed m = 0, 1, .. in the order opened: the batch_size outputs (cozk_layer_claimed_outputs of the top layer),
+ *              then layer by layer from the top, round by round, coefficients 0..3 of cozk_layer_round.  Sender p <= 2t sends
+ *              local_p + zero_p[m]; the coordinator combines with lagrange(1..2t + 1).
+ *   finals     L, R of cozk_layer_final_claims after the last bind: linear combinations of freshly dealt degree-t sharings,
+ *              opened from parties 0..t with lagrange(1..t + 1), unmasked.
+ * Parties above 2t receive their share of every level and send nothing.  leaves[p]: party p's FR share vector of the
+ * interleaved leaves, a vector of party_ctxs[p], copied and never modified; mul_keys[p] = t x 32 bytes (both read for
+ * p <= 2t only); rand_keys[p] = (3t + 1) x 32 bytes, every party.  Preconditions: batch_size > 0 divides the length, leaves
+ * per circuit a power of two >= 2 (Rep3BatchedDenseGrandProduct::construct), 1 <= t, 2t <= COZK_SHAMIR_MAX_DEGREE,
+ * 2t + 1 <= n <= 32; everything is refused on the host before any launch.  On failure *out is NULL and the error text is left
+ * with party_ctxs[0].  verify != 0 replays the plain verifier on a fresh transcript with the same label. */
+typedef struct cozk_shamir_gp cozk_shamir_gp;
+typedef struct cozk_shamir_gp_result {
+    int verified;          /* 1 accepted, 0 rejected, -1 verifier not run */
+    int n_layers;
+    uint64_t proof_len;
+    uint64_t n_opened;     /* M */
+    double t_construct_ms; /* host clock around the construction, every party's stream drained at both ends */
+    double t_prove_ms;     /* the same around masks + openings + rounds; one thread drives the parties in turn: a SUM over parties */
+} cozk_shamir_gp_result;
+int cozk_shamir_gp_prove_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* leaves, size_t batch_size,
+                                const uint8_t* const* mul_keys, const uint8_t* const* rand_keys, int degree, int num_parties,
+                                uint64_t mul_counter, uint64_t rand_counter, const char* label, int verify,
+                                cozk_shamir_gp** out);
+int cozk_shamir_gp_free(cozk_shamir_gp* h);
+int cozk_shamir_gp_get_result(const cozk_shamir_gp* h, cozk_shamir_gp_result* res);
+int cozk_shamir_gp_proof_bytes(const cozk_shamir_gp* h, uint8_t* out, size_t cap); /* cap >= proof_len bytes */
+/* the final (claim, r): r = point_len x 4 u64 */
+size_t cozk_shamir_gp_point_len(const cozk_shamir_gp* h);
+int cozk_shamir_gp_final(const cozk_shamir_gp* h, uint64_t claim[4], uint64_t* r);
+/* what went over the star, for tests and audits: msgs[m][p] = sender p's masked message of opening m, M x (2t + 1) elements;
+ * finals[layer, top first][p][L, R] = opener p's final-claim shares, layers x (t + 1) x 2 elements.  *_len in elements;
+ * out = len x 4 u64 Montgomery, cap in elements. */
+size_t cozk_shamir_gp_msgs_len(const cozk_shamir_gp* h);
+int cozk_shamir_gp_msgs(const cozk_shamir_gp* h, uint64_t* out, size_t cap);
+size_t cozk_shamir_gp_finals_len(const cozk_shamir_gp* h);
+int cozk_shamir_gp_finals(const cozk_shamir_gp* h, uint64_t* out, size_t cap);
 
 /* ---------------------------------------------------------------- MSM seam ---------------- */
 /* Upload SRS points (`ck.powers_of_g[i]`, co-jolt/src/poly/commitment/pst13.rs:286-287,461-462) once;

@@ -19,8 +19,16 @@ With --mul --king, instead, the multiplication with a king and double-random pai
   (ix)   the whole online step cozk_shamir_mul_king_inproc against the whole cozk_shamir_mul_inproc, one context per party on
          this GPU, alternating, each timed as (vii) is; both open to the product of the secrets;
   (x)    the whole offline step cozk_shamir_rand_inproc, timed the same way, and its cost per pair.
-  python tools/run_shamir.py --mul --king --log-n 22 --parties 8 --degree 2 [--out FILE]"""
-import argparse, ctypes, importlib, json, os, sys
+  python tools/run_shamir.py --mul --king --log-n 22 --parties 8 --degree 2 [--out FILE]
+With --gp, instead, the Shamir grand product prover over 2^log_n interleaved leaves in --gp-batch circuits:
+  (xi)   the fused re-deal of a tree level cozk_shamir_mul_deal_pairs on the leaf layer against cozk_layer_output_local (PLAIN,
+         unmasked) + cozk_shamir_share_vec, alternating in this process, outputs compared raw;
+  (xii)  the whole construct: cozk_shamir_mul_pairs_inproc level by level, one context per party on this GPU, timed as (vii) is;
+  (xiii) the whole cozk_shamir_gp_prove_inproc (construct + masks + rounds), timed the same way, with the driver's own split, and as
+         context the PLAIN single-party grand product of the same opened leaves in the same run (this script drives its rounds
+         through cozk_layer_round and hashes the transcript itself: its proof must equal the Shamir parties' byte for byte).
+  python tools/run_shamir.py --gp --log-n 22 --parties 8 --degree 2 [--out FILE]"""
+import argparse, ctypes, hashlib, importlib, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
@@ -33,6 +41,8 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--min-seconds", type=float, default=1.0)
 ap.add_argument("--mul", action="store_true", help="time the multiplication with degree reduction instead")
 ap.add_argument("--king", action="store_true", help="with --mul: time the king / double-random variant against the resharing")
+ap.add_argument("--gp", action="store_true", help="time the Shamir grand product prover instead")
+ap.add_argument("--gp-batch", type=int, default=2, help="with --gp: circuits in the grand product")
 args = ap.parse_args()
 cozk = importlib.import_module("co-zkvms_amd")
 L = cozk._lib
@@ -326,6 +336,188 @@ def king_legs():
                   "leg reuses one pair across repetitions (timing only: a pair must never be used twice)",
     })
 
+
+def gp_legs():
+    if 2 * T + 1 > N or 2 * T > 15:
+        raise SystemExit("run_shamir --gp: needs 2 * degree + 1 <= parties and 2 * degree <= 15")
+    P = importlib.import_module("co-zkvms_amd.poly")
+    batch, m = args.gp_batch, n // 2
+    spread = lambda ts: round((sorted(ts)[-1] - sorted(ts)[0]) / med(ts), 4)
+
+    # (xi): the leaf layer, 2^log_n elements -> 2^(log_n - 1) products
+    layer = P.Rep3DenseInterleavedPolynomial.from_vecs(ctx, A)
+
+    def fused_deal():
+        return A.shamir_mul_deal_pairs(keys_a, T, N, counter=0)
+
+    def composed_deal():
+        prod = layer.layer_output_local()
+        out = prod.shamir_share(keys_a, T, N, counter=0)
+        prod.free()
+        return out
+
+    f, c = fused_deal(), composed_deal()  # correctness once, which is also the warm-up of both legs
+    equal = all(np.array_equal(x.to_numpy(), y.to_numpy()) for x, y in zip(f, c))
+    free(f), free(c)
+    assert equal, "the fused re-deal of a layer and layer_output_local + shamir_share differ"
+    for _ in range(2):
+        free(timed(fused_deal)[1]), free(timed(composed_deal)[1])
+    t_f, t_c = [], []
+    while sum(t_f) < args.min_seconds * 1e3 or sum(t_c) < args.min_seconds * 1e3 or len(t_f) < 5:  # alternating
+        ms, r = timed(fused_deal); t_f.append(ms); free(r)
+        ms, r = timed(composed_deal); t_c.append(ms); free(r)
+    layer.free()
+
+    # (xii), (xiii): one context per party on this GPU
+    pcs = [cozk.Context(0) for _ in range(N)]
+    streams = []
+    for pc in pcs:
+        h = ctypes.c_void_p()
+        pc.check(pc._l.cozk_ctx_stream(pc.h, ctypes.byref(h)))
+        streams.append(torch.cuda.ExternalStream(h.value))
+    leaves = A.shamir_scatter(keys_a, T, pcs, counter=0)
+    mul_keys = [[key(1000 + 16 * p + c) for c in range(T)] for p in range(N)]
+    rand_keys = [[key(2000 + 32 * p + c) for c in range(3 * T + 1)] for p in range(N)]
+    levels = (n // batch).bit_length() - 2  # multiplications: log2(leaves per circuit) - 1
+
+    def whole(fn):
+        for pc in pcs:
+            pc.synchronize()
+        e0 = torch.cuda.Event(enable_timing=True)
+        e0.record(streams[0])  # every stream is idle: the calls start by draining them
+        out = fn()
+        ends = []
+        for st in streams:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record(st)
+            ends.append(e)
+        for e in ends:
+            e.synchronize()
+        return max(e0.elapsed_time(e) for e in ends), out
+
+    def construct():
+        cur, ctr = leaves, 0
+        for _ in range(levels):
+            nxt = cozk.shamir_mul_pairs(pcs, cur, mul_keys, T, counter=ctr)
+            ctr += len(nxt[0])
+            if cur is not leaves:
+                free(cur)
+            cur = nxt
+        return cur
+
+    def prove():
+        return cozk.shamir_gp_prove(pcs, leaves, batch, mul_keys, rand_keys, T, mul_counter=0, rand_counter=0)  # keys reused across repetitions: timing only
+
+    # the PLAIN prover of the same leaves, driven from here: cozk_layer_output_local per level, cozk_layer_round per round
+    R_MOD = cozk.FR_MOD
+    ser = lambda xs: b"".join(int(x).to_bytes(32, "little") for x in xs)
+    u64 = lambda v: int(v).to_bytes(8, "little")
+
+    class Tr:  # the harness transcript: SHA-256 sponge, u32 round counter, 128-bit challenges
+        def __init__(self):
+            self.s, self.k = hashlib.sha256(b"cozk").digest(), 0
+
+        def absorb(self, data):
+            self.s = hashlib.sha256(self.s + self.k.to_bytes(4, "little") + data).digest()
+            self.k += 1
+
+        def challenge(self):
+            self.absorb(b"challenge")
+            return int.from_bytes(self.s[:16], "little")
+
+    def plain_prove():
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        layers = [P.Rep3DenseInterleavedPolynomial.from_vecs(ctx, A)]
+        for _ in range(levels):
+            layers.append(P.Rep3DenseInterleavedPolynomial.from_vecs(ctx, layers[-1].layer_output_local(), take_ownership=True))
+        ctx.synchronize()
+        t1 = time.perf_counter()
+        tr = Tr()
+        outs = layers[-1].claimed_outputs()
+        tr.absorb(ser(outs))
+        r = [tr.challenge() for _ in range((batch - 1).bit_length())]
+        eq = [1]
+        for rj in r:
+            eq = [x for e in eq for x in ((e - e * rj) % R_MOD, e * rj % R_MOD)]
+        claim = sum(e * v for e, v in zip(eq, outs)) % R_MOD
+        blob = u64(len(outs)) + ser(outs) + u64(len(layers))
+        for layer in reversed(layers):
+            eqp = P.SplitEqPolynomial(ctx, r)
+            rs, rj = [], None
+            blob += u64(len(r))
+            for _ in range(len(r)):
+                co = layer.round(eqp, rj, claim)
+                comp = [co[0], co[2], co[3]]
+                tr.absorb(ser(comp))
+                rj = tr.challenge()
+                rs.append(rj)
+                claim = (co[0] + rj * (co[1] + rj * (co[2] + rj * co[3]))) % R_MOD
+                blob += u64(3) + ser(comp)
+            if rs:
+                layer.bind(rj)
+            left, right = layer.final_claims()
+            tr.absorb(ser([left]))
+            tr.absorb(ser([right]))
+            rl = tr.challenge()
+            claim = (left + rl * (right - left)) % R_MOD
+            r = rs[::-1] + [rl]
+            blob += ser([left, right])
+            eqp.free()
+            layer.free()
+        ctx.synchronize()
+        return (t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3, blob
+
+    ms, top = whole(construct)  # warm-up
+    free(top)
+    ms, g = whole(prove)        # warm-up and correctness
+    assert g.result.verified == 1, "the Shamir grand product proof was rejected"
+    pc_ms, pp_ms, plain_blob = plain_prove()
+    same = plain_blob == g.proof_bytes
+    assert same, "the Shamir parties' proof differs from the plain prover's proof of the same leaves"
+    t_con, t_all, t_dc, t_dp, t_pc, t_pp = [], [], [], [], [], []
+    while sum(t_con) < args.min_seconds * 1e3 or len(t_con) < 5:
+        ms, top = whole(construct); t_con.append(ms); free(top)
+    while sum(t_all) < args.min_seconds * 1e3 or len(t_all) < 5:  # the Shamir prover and the plain prover alternating
+        ms, g = whole(prove); t_all.append(ms); t_dc.append(g.result.t_construct_ms); t_dp.append(g.result.t_prove_ms)
+        a, b, _ = plain_prove(); t_pc.append(a); t_pp.append(b)
+    free(leaves)
+    for pc in pcs:
+        pc.close()
+
+    D = 2 * T + 1
+    fused_bytes, comp_bytes = (2 + N) * 32 * m, (2 + 1 + 1 + N) * 32 * m
+    emit({
+        "what": "Shamir grand product prover: fused re-deal of a layer vs layer_output_local + shamir_share, whole construct, whole prove, "
+                "the PLAIN prover of the same leaves in the same run",
+        "log_n": args.log_n, "interleaved_leaves": n, "batch": batch, "layers": levels + 1, "parties": N, "degree": T, "senders": D,
+        "openings_of_degree_2t": int(g.result.n_opened), "proof_len": int(g.result.proof_len), "device": torch.cuda.get_device_name(0),
+        "fused_mul_deal_pairs": dict(stats(t_f), products=m, algorithmic_bytes=fused_bytes, bytes_per_s=round(fused_bytes / (med(t_f) * 1e-3), 1),
+                                     spread_max_minus_min_over_median=spread(t_f), launches=1),
+        "composed_output_local_then_share": dict(stats(t_c), bytes_moved_by_the_composition=comp_bytes, spread_max_minus_min_over_median=spread(t_c), launches=2),
+        "fused_vs_composed_speedup": round(med(t_c) / med(t_f), 3),
+        "fused_slower_than_composed_by_ms": round(med(t_f) - med(t_c), 4),
+        "composed_min_max_spread_ms": round(sorted(t_c)[-1] - sorted(t_c)[0], 4),
+        "fused_not_slower_beyond_composed_spread": bool(med(t_f) - med(t_c) <= sorted(t_c)[-1] - sorted(t_c)[0]),
+        "outputs_equal": bool(equal),
+        "inproc_construct": dict(stats(t_con), levels=levels, launches=levels * (D + N), contexts=N),
+        "inproc_prove_whole_call": dict(stats(t_all), contexts=N, verified=int(g.result.verified)),
+        "inproc_prove_driver_split": {"construct": stats(t_dc), "masks_openings_rounds": stats(t_dp),
+                                      "note": "the driver's host clock around stream-drained phases; one thread drives the parties in turn on "
+                                              "one GPU, so the rounds are a SUM over the 2t + 1 senders, not what one party per GPU would take"},
+        "plain_prover_same_run": {"construct": stats(t_pc), "prove": stats(t_pp), "proof_equals_shamir_proof": bool(same),
+                                  "note": "host clock; rounds driven from this script through cozk_layer_round (one launch and one fetch per "
+                                          "round, transcript hashed in Python): neither prover here uses the resident tail kernel"},
+        "timing": "device events around each repetition for (xi), legs alternating on one stream; (xii) and the whole call of (xiii) from an event "
+                  "on party 0's idle stream before the call to the last of the events behind the parties' streams, host-side synchronisations "
+                  "included; the Shamir and the PLAIN prover alternating; keys and counters reused across repetitions (timing only)",
+    })
+
+
+if args.gp:
+    gp_legs()
+    ctx.close()
+    raise SystemExit(0)
 
 if args.mul and args.king:
     king_legs()
