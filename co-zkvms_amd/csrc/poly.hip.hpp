@@ -121,7 +121,10 @@ static __device__ __forceinline__ void fr_wide_mac(FrWide& w, const fe& a, const
 }
 static __device__ __forceinline__ fe fr_wide_reduce(const FrWide& w) {
     uint32_t t[18];
-    uint64_t carry = 0;  // < 2^64: a column is < 2^96, so (column + carry) >> 32 < 2^64
+    // carry < 2^64 and h < 2^32 as long as column + carry < 2^96.  A column of n terms is <= 8 n (2^32 - 1)^2, so up to 2^29
+    // terms it is <= 2^96 - 2^65 + 2^32 and the carry (< 2^64) fits on top.  A column within 2^64 of 2^96 is NOT covered: its
+    // carry would need a 65th bit (and the total a word t[17])
+    uint64_t carry = 0;
 #pragma unroll
     for (int k = 0; k < 15; k++) {
         uint64_t s = w.lo[k] + carry;

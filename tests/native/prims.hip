@@ -1,6 +1,6 @@
 // Test-only harness over the product's arithmetic headers: element-wise kernels for the 8 x 32 Montgomery fields (canonical and
 // lazy operations), the XYZZ G1 formulas and the 9 x 29 layers, plus host wrappers for the host paths of the same headers (the
-// two host Montgomery products, SHA-256, the transcript).  The headers are included, never copied: what is tested is the code
+// two host Montgomery products, SHA-256, the transcript), and the wide dot-product accumulator FrWide of poly.hip.hpp.  The headers are included, never copied: what is tested is the code
 // the kernels inline.  Each device wrapper uploads host arrays of u32 limbs, launches, synchronises, downloads and returns the
 // HIP status.  Built by co-zkvms_amd/build.py (build_prims) into tests/native/libcozk_prims.so; driven by tests/test_gpu_prims.py
 // and tests/test_host_prims.py.
@@ -8,6 +8,7 @@
 
 #include "../../co-zkvms_amd/csrc/fr9.hip.hpp"
 #include "../../co-zkvms_amd/csrc/host/wire.hpp"
+#include "../../co-zkvms_amd/csrc/poly.hip.hpp"
 
 #define PRIMS_NAME_(n) #n ","
 
@@ -226,6 +227,39 @@ __global__ void k_madd9_chain(const uint32_t* pts, int k, uint32_t* out, size_t 
     o[68] = (uint32_t)fail;
 }
 
+// ------------------------------------------------------------------------------------------------ FrWide (poly.hip.hpp)
+// Per lane 61 words: the 15 columns as (low word of lo, high word of lo, hi), then a and b.  wide_reduce = fr_wide_reduce of the
+// columns as given; wide_mac adds ONE term a * b with fr_wide_mac first.  The caller keeps every column, with the carry that
+// reaches it, below 2^96: the range fr_wide_reduce is written for.
+#define WIDE_OPS(X) X(wide_reduce) X(wide_mac)
+#define WIDE_ENUM_(n) WIDE_##n,
+enum { WIDE_OPS(WIDE_ENUM_) WIDE_NOPS };
+static const char* const WIDE_NAMES = WIDE_OPS(PRIMS_NAME_);
+static constexpr int WIDE_IN = 15 * 3 + 8 + 8;
+
+__global__ void k_wide(int op, const uint32_t* in, uint32_t* out, uint32_t* ok, size_t n) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* p = in + (size_t)WIDE_IN * i;
+    FrWide w;
+#pragma unroll
+    for (int k = 0; k < 15; k++) {
+        w.lo[k] = (uint64_t)p[3 * k] | ((uint64_t)p[3 * k + 1] << 32);
+        w.hi[k] = p[3 * k + 2];
+    }
+    fe a, b;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        a.l[k] = p[45 + k];
+        b.l[k] = p[53 + k];
+    }
+    if (op == WIDE_wide_mac) fr_wide_mac(w, a, b);
+    ok[i] = op == WIDE_wide_reduce || op == WIDE_wide_mac ? 1u : 0u;
+    const fe r = fr_wide_reduce(w);
+#pragma unroll
+    for (int k = 0; k < 8; k++) out[8 * i + k] = r.l[k];
+}
+
 // ------------------------------------------------------------------------------------------------ host side of the wrappers
 namespace {
 struct Dev {
@@ -270,6 +304,7 @@ extern "C" {
 const char* prims_ff_ops() { return FF_NAMES; }
 const char* prims_g1_ops() { return G1_NAMES; }
 const char* prims_f9_ops() { return F9_NAMES; }
+const char* prims_wide_ops() { return WIDE_NAMES; }
 
 // field 0 = Fr, 1 = Fq; a..d: n x 8 limbs; out: n x 16 limbs (o1, o2); ok: n flags (0 = op not on the device)
 int prims_ff(int field, int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t* out,
@@ -327,6 +362,15 @@ int prims_madd9_chain(const uint32_t* pts, int k, uint32_t* out, size_t n) {
     return run(n, (size_t)18 * k, in, 1, MADD9_OUT, out, nullptr,
                [&](const uint32_t* A, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t* O, uint32_t*) {
                    k_madd9_chain<<<grid(n), BLOCK>>>(A, k, O, n);
+               });
+}
+
+// in: n x 61 words (k_wide); out: n x 8 limbs
+int prims_wide(int op, const uint32_t* in, uint32_t* out, uint32_t* ok, size_t n) {
+    const uint32_t* ins[4] = {in, nullptr, nullptr, nullptr};
+    return run(n, WIDE_IN, ins, 1, 8, out, ok,
+               [&](const uint32_t* A, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t* O, uint32_t* K) {
+                   k_wide<<<grid(n), BLOCK>>>(op, A, O, K, n);
                });
 }
 

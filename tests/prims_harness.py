@@ -1,6 +1,6 @@
 """ctypes front end of the primitive test harness tests/native/prims.hip (built into tests/native/libcozk_prims.so by
-co-zkvms_amd/build.py's build_prims): limb packing, the op tables the library exports, the edge operands and big-int expectations
-that tests/test_gpu_prims.py and tests/test_host_prims.py share, and the SHA-256 / transcript leg that test_host_prims.py runs in
+co-zkvms_amd/build.py's build_prims): limb packing, the op tables the library exports (the fields, G1, the 9 x 29 layers, the wide
+accumulator), the edge operands and big-int expectations that tests/test_gpu_prims.py and tests/test_host_prims.py share, and the SHA-256 / transcript leg that test_host_prims.py runs in
 fresh processes (`python prims_harness.py sha`)."""
 import ctypes
 import json
@@ -35,13 +35,14 @@ def lib():
         build()
         L = ctypes.CDLL(LIB_PATH)
         vp, sz, i = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-        for name in ("prims_ff_ops", "prims_g1_ops", "prims_f9_ops"):
+        for name in ("prims_ff_ops", "prims_g1_ops", "prims_f9_ops", "prims_wide_ops"):
             getattr(L, name).restype = ctypes.c_char_p
         L.prims_ff.argtypes = [i, i, vp, vp, vp, vp, vp, vp, sz]
         L.prims_ff_host.argtypes = [i, i, vp, vp, vp, vp, vp, sz]
         L.prims_g1.argtypes = [i, vp, vp, vp, vp, sz]
         L.prims_f9.argtypes = [i, vp, vp, vp, vp, vp, vp, i, sz]
         L.prims_madd9_chain.argtypes = [vp, i, vp, sz]
+        L.prims_wide.argtypes = [i, vp, vp, vp, sz]
         L.prims_sha256.argtypes = [vp, vp, sz, vp]
         L.prims_sha256.restype = None
         L.prims_transcript.argtypes = [vp, sz, vp, sz]
@@ -210,6 +211,25 @@ def madd9_chain(chains):
     assert rc == 0, "HIP error %d" % rc
     return [([row[9 * j:9 * j + 9].tolist() for j in range(4)], from_limbs(row[36:68].reshape(4, 8)), int(row[68]))
             for row in out]
+
+
+# ------------------------------------------------------------------------------------------------ FrWide
+def wide(op, columns, a=None, b=None):
+    """columns: lanes of 15 integers below 2^96 (the accumulator state); a, b: lanes of raw limb values.  "wide_reduce" ->
+    fr_wide_reduce of the state; "wide_mac" -> of the state after one fr_wide_mac(a, b)"""
+    n = len(columns)
+    z = [0] * n
+    rows = np.zeros((n, 61), dtype=np.uint32)
+    for k in range(15):
+        rows[:, 3 * k:3 * k + 3] = to_limbs([c[k] for c in columns], 3)
+    rows[:, 45:53] = to_limbs(a if a is not None else z)
+    rows[:, 53:61] = to_limbs(b if b is not None else z)
+    out = np.zeros((n, 8), dtype=np.uint32)
+    ok = np.zeros(n, dtype=np.uint32)
+    rc = lib().prims_wide(ops("wide")[op], _ptr(rows), _ptr(out), _ptr(ok), n)
+    assert rc == 0, "HIP error %d" % rc
+    assert ok.all(), "no device " + op
+    return from_limbs(out)
 
 
 # ------------------------------------------------------------------------------------------------ SHA-256 and the transcript

@@ -1,9 +1,12 @@
 """GPU parity of the polynomial seam (bind / evals / RLC / GKR layer ops) against oracle/pyref.py.
 Bit-exact bar; both share modes (Rep3 shares and plain values); ragged tails as the reference
 handles them (dense_interleaved_poly.rs:160-177,232-247)."""
+import numpy as np
 import pytest
 
+import prims_harness as H
 import pyref as O
+import reduction_ref as X
 
 pytestmark = pytest.mark.gpu
 
@@ -391,3 +394,93 @@ def test_open_quadratic_and_pst_fold(cozk, ctx):
     cozk.pst_fold(ctx, cozk.Vec.from_ints(ctx, r), pt, q, rn)
     assert q.to_ints() == [(r[2 * b + 1] - r[2 * b]) % O.R for b in range(32)]
     assert rn.to_ints() == [(r[2 * b] * (1 - pt) + r[2 * b + 1] * pt) % O.R for b in range(32)]
+
+
+# ------------------------------------------------------------------------------------------------ the wide accumulator in its kernels
+# FrWide (poly.hip.hpp) is reduced once per lane: its third word T2 is non-zero only from 28 worst-case terms per lane
+# (28 (r - 1)^2 >= 2^512), so these run the smallest sizes at which a lane of the default grids holds that many, on RAW residues
+# (Vec.from_numpy: the device multiplies exactly these words).  A Montgomery product of residues x, y is x y / R and the result
+# is read back through another 1 / R, hence the RINV^2 in every big-int expectation.
+WIDE_PERIOD = 49  # coprime to every grid stride (a power of two times 3): a lane walks through the whole pattern
+
+
+def _wide_pattern(seed):
+    """r - 1, a primitive-harness edge, a random residue, ... : 16 triples and one more r - 1"""
+    rng = O.SplitMix64(seed)
+    pat = [v for e in H.edges(O.R) for v in (O.R - 1, e, rng.field())] + [O.R - 1]
+    assert len(pat) == WIDE_PERIOD
+    return pat
+
+
+def _tiled(ctx, cozk, pattern, n):
+    return cozk.Vec.from_numpy(ctx, np.resize(X.to_raw(pattern), (n, 4)))
+
+
+def _tiled_dot(n, *patterns):
+    """sum_{i < n} prod_k patterns[k][i mod period] for patterns of one period, the sum of products in big ints"""
+    period = len(patterns[0])
+    total = 0
+    for j in range(period):
+        term = (n // period) + (j < n % period)
+        for p in patterns:
+            term *= p[j]
+        total += term
+    return total
+
+
+def _wide_inputs(fill, mode, seed, eval_sum):
+    """(a, b, public) patterns: all r - 1, or mixed.  Where the kernel multiplies a + b (eval_sum) the all-(r - 1) run keeps b
+    at zero so that the factor itself is r - 1"""
+    one = [O.R - 1] * WIDE_PERIOD
+    if fill == "all_r_minus_1":
+        return one, ([0] * WIDE_PERIOD if eval_sum else one) if mode == "rep3" else None, one
+    a, b, pub = _wide_pattern(seed), _wide_pattern(seed + 1)[::-1], _wide_pattern(seed + 2)
+    pub = pub[5:] + pub[:5]  # r - 1 meets r - 1, an edge and a random value
+    return a, b if mode == "rep3" else None, pub
+
+
+def _wide_poly(cozk, ctx, a, b, n):
+    return cozk.Rep3DensePolynomial.from_vec_shares(ctx, _tiled(ctx, cozk, a, n), _tiled(ctx, cozk, b, n) if b is not None else None)
+
+
+@pytest.mark.parametrize("fill", ["all_r_minus_1", "mixed"])
+@pytest.mark.parametrize("mode", ["rep3", "plain"])
+def test_evaluate_at_chi_many_worst_case_terms_per_lane(cozk, ctx, mode, fill):
+    """bound: three words T0 + T1 R + T2 R^2 of the lane's sum (poly.hip.hpp:84-90): 2^21 elements over the 192 x 256 lanes of
+    k_poly_eval_chi are 42 or 43 terms per lane, past the 28 at which T2 starts"""
+    n = 1 << 21
+    a, b, chi = _wide_inputs(fill, mode, 21, True)
+    got = _wide_poly(cozk, ctx, a, b, n).evaluate_at_chi(_tiled(ctx, cozk, chi, n))
+    if mode == "rep3":
+        want = _tiled_dot(n, [(x + y) % O.R for x, y in zip(a, b)], chi) * X.RINV * X.RINV * O.TWO_INV % O.R
+    else:
+        want = _tiled_dot(n, a, chi) * X.RINV * X.RINV % O.R
+    if fill == "all_r_minus_1":
+        assert _tiled_dot(n, a, chi) == n * (O.R - 1) ** 2  # the closed form
+    assert got == want
+
+
+@pytest.mark.parametrize("fill", ["all_r_minus_1", "mixed"])
+@pytest.mark.parametrize("mode", ["rep3", "plain"])
+def test_dot_product_with_public_many_worst_case_terms_per_lane(cozk, ctx, mode, fill):
+    """bound: as above (poly.hip.hpp:84-90): 2^22 elements over the 512 x 256 lanes of k_poly_dot_public are 32 terms per lane"""
+    n = 1 << 22
+    a, b, pub = _wide_inputs(fill, mode, 22, False)
+    got = _wide_poly(cozk, ctx, a, b, n).dot_product_with_public(_tiled(ctx, cozk, pub, n))
+    dot = lambda v: _tiled_dot(n, v, pub) * X.RINV * X.RINV % O.R
+    assert got == ((dot(a), dot(b)) if mode == "rep3" else dot(a))
+
+
+@pytest.mark.parametrize("k", [7, 8, 16, 32])
+@pytest.mark.parametrize("mode", ["rep3", "plain"])
+def test_linear_combination_wide_branch_all_r_minus_1(cozk, ctx, mode, k):
+    """bound: as above (poly.hip.hpp:84-90) in k_poly_lincomb's wide branch, k >= 8 (7 is the other side of the switch; 32
+    terms reach T2): every coefficient and value the residue r - 1, a length that is no multiple of the block, one shorter
+    polynomial among them"""
+    n, short = 1000 + 24, 1000
+    one = [O.R - 1] * WIDE_PERIOD
+    polys = [_wide_poly(cozk, ctx, one, one if mode == "rep3" else None, short if j == 3 else n) for j in range(k)]
+    cf = [(O.R - 1) * X.RINV % O.R] * k  # canonical values whose residue is r - 1
+    got = cozk.Rep3DensePolynomial.linear_combination(polys, cf).coeffs()
+    want = [(k if i < short else k - 1) * (O.R - 1) ** 2 * X.RINV * X.RINV % O.R for i in range(n)]
+    assert got == ([(w, w) for w in want] if mode == "rep3" else want)

@@ -4,7 +4,8 @@ headers), against big-int (oracle/pyref.py) and the 9 x 29 CPU models (test_fr9_
     bounds; the lazy zero test true for exactly 0 and m;
   * the XYZZ G1 formulas (ec.hip.hpp) on edge points, lazy coordinates, P + P, P - P, the identity and chains;
   * the 9 x 29 Fr / Fq layers (fr9.hip.hpp, fq9.hip.hpp) limb for limb against the models, the folded accumulator chain and the
-    madd9 chain.
+    madd9 chain;
+  * the wide dot-product accumulator (poly.hip.hpp FrWide) at the term counts and column states of its stated bound.
 Edge operands sit at the start and at the end of every launch.  The 8 x 32 launches put 2^16 random lanes between them, the
 9 x 29 launches 2^12, because each of their lanes also runs through the Python model."""
 import random
@@ -13,6 +14,7 @@ import pytest
 
 import prims_harness as H
 import pyref as O
+import reduction_ref as W
 import test_fq9_model as Q9
 import test_fr9_model as R9
 
@@ -367,3 +369,44 @@ def test_madd9_chain_matches_the_model_and_the_affine_sum():
         X, Y, ZZ, ZZZ = (v * RI % P for v in dxyzz)
         assert pow(ZZ, 3, P) == pow(ZZZ, 2, P), "lane %d: ZZ^3 != ZZZ^2" % i
         assert (X * pow(ZZ, -1, P) % P, Y * pow(ZZZ, -1, P) % P) == ref, "lane %d: not the affine sum" % i
+
+
+# ------------------------------------------------------------------------------------------------ FrWide
+# Only states the accumulator can reach are fed: N identical terms of a canonical pair, or the hand-made words below.  All columns
+# at 2^96 - 1 is NOT one of them: no sum of terms produces it, and its total needs a word t[17] that fr_wide_reduce sets to zero
+# by design.
+def _wide_pairs():
+    e = H.edges(R)
+    return [(a, b) for a in e for b in e]
+
+
+def test_wide_reduce_at_the_term_counts_of_its_bound():
+    """bound: 2^29 terms of 96-bit columns, three words T0 + T1 R + T2 R^2 (poly.hip.hpp:84-90 and the carry chain at
+    :123-137): N = 1, 27, 28 (T2 starts), 2^16, 2^29 and the last N that fits, every pair of edge operands"""
+    lanes = [(a, b, n) for a, b in _wide_pairs() for n in W.WIDE_N + (W.wide_n_max(a, b),)]
+    assert all(n >= 1 << 29 for _, _, n in lanes[5::6])
+    cols = [W.wide_columns(a, b, n) for a, b, n in lanes]
+    assert any(W.wide_value(c) >> 512 for c in cols)  # T2 is exercised
+    got = H.wide("wide_reduce", cols)
+    H.check("fr_wide_reduce", got, [n * a * b * W.RINV % R for a, b, n in lanes], *zip(*lanes))
+
+
+def test_wide_mac_onto_a_nearly_full_accumulator():
+    """bound: the last term that fits (poly.hip.hpp:86-87, fr_wide_mac's carry-out folded into hi): one real multiply-add onto the
+    state of wide_n_max - 1 terms, so every column's low 64 bits carry into its high word at the top of the range"""
+    pairs = _wide_pairs()
+    nmax = [W.wide_n_max(a, b) for a, b in pairs]
+    cols = [W.wide_columns(a, b, n - 1) for (a, b), n in zip(pairs, nmax)]
+    got = H.wide("wide_mac", cols, [a for a, _ in pairs], [b for _, b in pairs])
+    H.check("fr_wide_mac + fr_wide_reduce", got, [n * a * b * W.RINV % R for (a, b), n in zip(pairs, nmax)], *zip(*pairs))
+    few = [W.wide_columns(a, b, 27) for a, b in pairs]  # and across the 27 -> 28 step, where T2 becomes non-zero
+    got = H.wide("wide_mac", few, [a for a, _ in pairs], [b for _, b in pairs])
+    H.check("fr_wide_mac, term 28", got, [28 * a * b * W.RINV % R for a, b in pairs], *zip(*pairs))
+
+
+def test_wide_reduce_words_at_multiples_of_r():
+    """bound: from_mont(T0) and T1 mod r take ANY 256-bit word, not a canonical one (poly.hip.hpp:146-147): T0 and T1 at r, 2r, 3r, 4r, 5r (2^256 // r = 5) and 2^256 - 1, every combination, the other columns zero"""
+    words = (0,) + W.WIDE_WORDS
+    lanes = [(t0, t1) for t0 in words for t1 in words]
+    got = H.wide("wide_reduce", [W.wide_columns_of_words(t0, t1) for t0, t1 in lanes])
+    H.check("fr_wide_reduce (words)", got, [(t0 + (t1 << 256)) * W.RINV % R for t0, t1 in lanes], *zip(*lanes))

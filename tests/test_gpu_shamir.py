@@ -6,7 +6,9 @@ import ctypes
 import numpy as np
 import pytest
 
+import prims_harness as H
 import pyref as O
+import reduction_ref as X
 import shamir_ref as S
 
 pytestmark = pytest.mark.gpu
@@ -93,6 +95,75 @@ def test_eval_edge_operands_every_position_every_party(cozk, ctx, degree):
     assert (top <= np.uint64(R >> 192)).all()
     for row in raw[top == np.uint64(R >> 192)]:
         assert O.from_limbs64(row) < R
+
+
+# ------------------------------------------------------------------------------------------------ (c') the quotient estimate
+# Horner with a plain evaluation point is linear, so raw Montgomery residues go in (Vec.from_numpy) and the expectation is
+# S.eval_vec of the residues themselves; the raw words that come out are compared as they are, so every output is canonical.
+def _assert_canonical(raw):
+    """raw limbs (k x 4 u64) are below r as 256-bit integers"""
+    top = raw[:, 3]
+    assert (top <= np.uint64(R >> 192)).all()
+    for row in raw[top == np.uint64(R >> 192)]:
+        assert O.from_limbs64(row) < R
+
+
+def _eval_raw(cozk, ctx, cols, parties=32):
+    """cozk_shamir_eval_vec on residue columns cols[c][lane] -> (got, want)[party][lane], raw"""
+    out = cozk.shamir_eval(ctx, [cozk.Vec.from_numpy(ctx, X.to_raw(c)) for c in cols], parties)
+    raw = [g.to_numpy() for g in out]
+    _assert_canonical(np.concatenate(raw))
+    return [X.from_raw(r) for r in raw], S.eval_vec(cols, parties)
+
+
+def test_eval_small_multiplier_at_the_quotient_estimate_bound(cozk, ctx):
+    """bound: q = T / D is floor(t / r) or one less, one subtraction finishes (shamir.hip:14-20): t = a p + c on every multiple of
+    r a p <= 32 reaches, either side of it and of the delta where the estimate switches; the lane's own party p sits on it"""
+    cases = X.small_mul_add_cases()
+    got, want = _eval_raw(cozk, ctx, [[c for _, _, _, c in cases], [a for _, _, a, _ in cases]])
+    for party in range(32):
+        assert got[party] == want[party], "party %d" % party
+    for lane, (p, _, a, c) in enumerate(cases):  # what the directed lanes are for
+        assert got[p - 1][lane] == (a * p + c) % R
+
+
+@pytest.mark.parametrize("degree", [2, 7, 8, 15])
+def test_eval_quotient_estimate_bound_first_and_last_horner_step(cozk, ctx, degree):
+    """bound: as above (shamir.hip:14-20), in the unrolled (2, 7) and the rolled (8, 15) kernel: (a, c) as the two leading
+    coefficients (the first Horner step, whatever follows) and as coef_1 and the secret under zero coefficients (the last)"""
+    cases = X.small_mul_add_cases(X.small_boundary_deltas)
+    m = len(cases)
+    cols = [[0] * (2 * m) for _ in range(degree + 1)]
+    for lane, (_, _, a, c) in enumerate(cases):
+        cols[degree][lane], cols[degree - 1][lane] = a, c
+        cols[1][m + lane], cols[0][m + lane] = a, c
+    got, want = _eval_raw(cozk, ctx, cols)
+    for party in range(32):
+        assert got[party] == want[party], "party %d" % party
+    for lane, (p, _, a, c) in enumerate(cases):
+        assert got[p - 1][m + lane] == (a * p + c) % R
+
+
+def test_eval_limb_carry_operands(cozk, ctx):
+    """bound: the 8 multiply-adds' carries m < 2^38 (shamir.hip:26): every pair of the primitive harness' edge residues, among
+    them low limbs all ones (which EDGE lacks), as (a, c) at degree 1 for all 32 multipliers"""
+    e = H.edges(R)
+    got, want = _eval_raw(cozk, ctx, [[c for _ in e for c in e], [a for a in e for _ in e]])
+    for party in range(32):
+        assert got[party] == want[party], "party %d" % party
+
+
+def test_combine_31_shares_of_r_minus_1(cozk, ctx):
+    """bound: the wide accumulator's words T0 + T1 R + T2 R^2 (poly.hip.hpp:84-90) in k_shamir_combine: 31 terms lambda_j s_j with
+    every share the residue r - 1, at degree 30, more than one block and a ragged tail"""
+    n, pts = 300, list(range(1, 32))
+    share = X.to_raw([R - 1] * n)
+    got = cozk.shamir_combine([cozk.Vec.from_numpy(ctx, share) for _ in pts], pts, 30).to_numpy()
+    lam = S.lagrange_from_coeff(pts)
+    assert X.from_raw(got) == [sum(l * (R - 1) for l in lam) % R] * n  # lambda_j R * s_j / R: the residue of the sum
+    rev = list(range(32, 1, -1))  # the same shares at other points: other coefficients
+    got = cozk.shamir_combine([cozk.Vec.from_numpy(ctx, share) for _ in rev], rev, 30).to_numpy()
+    assert X.from_raw(got) == [sum(l * (R - 1) for l in S.lagrange_from_coeff(rev)) % R] * n
 
 
 # ------------------------------------------------------------------------------------------------ (d) local operators

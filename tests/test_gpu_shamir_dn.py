@@ -14,6 +14,7 @@ import pytest
 import torch  # noqa: F401 - a torch host maps its own librccl first; libcozk then reuses that copy (one RCCL per process)
 
 import pyref as O
+import reduction_ref as X
 import shamir_dn_ref as D
 import shamir_mul_ref as M
 import shamir_ref as S
@@ -104,6 +105,20 @@ def test_rand_extract_edge_operands(cozk, ctx, case):
     got = cozk.shamir_rand_extract(ctx, [cozk.Vec.from_ints(ctx, v) for v in ins], 31)
     assert _ints(got) == D.extract(ins, 31)
     _assert_canonical(np.concatenate([g.to_numpy() for g in got]))
+
+
+def test_rand_extract_first_power_step_at_the_quotient_estimate_bound(cozk, ctx):
+    """bound: q = T / D is floor(t / r) or one less (shamir.hip:14-20) in k_shamir_extract's power step w (j + 1): input j alone is
+    ceil(Q r / (j + 1)) or floor(Q r / (j + 1)), so the first step lands less than j + 1 above or below Q r.  The extraction is
+    linear: raw residues go in and the restatement runs on them"""
+    lanes = [(j, w) for j in range(32) for Q in range(1, j + 1) for w in (-(-Q * R // (j + 1)), Q * R // (j + 1))]
+    assert len(lanes) == 2 * sum(range(32)) and all(0 < w < R for _, w in lanes)
+    assert all(abs(w * (j + 1) - (w * (j + 1) + R // 2) // R * R) < j + 1 for j, w in lanes)
+    ins = [[w if j == k else 0 for j, w in lanes] for k in range(32)]
+    got = cozk.shamir_rand_extract(ctx, [cozk.Vec.from_numpy(ctx, X.to_raw(v)) for v in ins], 31)
+    raw = [g.to_numpy() for g in got]
+    _assert_canonical(np.concatenate(raw))
+    assert [X.from_raw(r) for r in raw] == D.extract(ins, 31)
 
 
 # ------------------------------------------------------------------------------------------------ (d) extract vs composition
