@@ -151,6 +151,13 @@ SIGNATURES = {
     "cozk_shamir_mul_mask": (_i, [_vp, _vp, _vp, _vp, _pp]),
     "cozk_shamir_mul_king_inproc": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "cozk_shamir_mul_king_vec": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _pp]),
+    "cozk_shamir_mul_mask_pairs": (_i, [_vp, _vp, _vp, _sz, _pp]),
+    "cozk_shamir_king_finish": (_i, [_vp, _vp, _i, _vp, _sz, _i, _vp, _vp]),
+    "cozk_shamir_mul_king_pairs_inproc": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "cozk_shamir_gp_prep_inproc": (_i, [_vp, _vp, _sz, _sz, _i, _i, _u64, _pp]),
+    "cozk_shamir_gp_prep_free": (_i, [_vp]),
+    "cozk_shamir_gp_prep_get_result": (_i, [_vp, _vp]),
+    "cozk_shamir_gp_prove_king_inproc": (_i, [_vp, _vp, _sz, _vp, _i, ctypes.c_char_p, _i, _pp]),
     "cozk_shamir_combine_points": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, ctypes.POINTER(_i)]),
     "cozk_layer_round": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "cozk_fingerprint_leaves": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _i, _i, _vp, _vp, _sz, _sz]),

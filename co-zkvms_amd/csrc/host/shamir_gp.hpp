@@ -19,9 +19,20 @@
 //               from parties 0..t with lagrange(1..t + 1), unmasked
 //   transcript  and proof layout: exactly coordinate_prove_grand_product / coordinate_prove_layer (prover.hpp)
 // Parties above 2t take part in the construction (they receive their shares of every level) and send nothing afterwards.
+//
+// The king variant (cozk_shamir_gp_prep_inproc + cozk_shamir_gp_prove_king_inproc; tests/shamir_gp_king_ref.py) moves everything
+// that needs fresh randomness before the witness: the masks above and two double-random pairs of n_leaves / 2 elements are dealt
+// into a preprocessing object, and the construct becomes layer[i + 1] = cozk_shamir_mul_king_pairs_inproc(layer[i]) on slices of
+// those pairs.  Both provers are one construct loop with the level's multiplication as a parameter (shamir_gp_construct) in front
+// of one copy of the openings, rounds, finals, transcript and proof (shamir_gp_prove_layers).
 #pragma once
 #include "prover.hpp"
 #include "runner.hpp"
+
+// shamir.hip: the double-random preprocessing that extracts only `count` pairs, the degree-t halves for parties 0..rcp_t - 1, the
+// degree-2t halves for the senders
+int shamir_rand_pairs_inproc(cozk_ctx* const* pcs, const uint8_t* const* keys, size_t n_elems, int t, int np, uint64_t counter, int count, int rcp_t,
+                             cozk_vec** r_t, cozk_vec** r_2t);
 
 struct cozk_shamir_gp {
     cozk::Bytes proof;
@@ -54,37 +65,40 @@ struct ShamirGpArgs {
     cozk_ctx* const* pcs;
     const cozk_vec* const* leaves;
     size_t batch_size;
-    const uint8_t* const* mul_keys;
-    const uint8_t* const* rand_keys;
     int t, n;
-    uint64_t mul_counter, rand_counter;
     const char* label;
     bool verify;
 };
 
-static void shamir_gp_prove(const ShamirGpArgs& a, cozk_shamir_gp& h) {
-    const int senders = 2 * a.t + 1, openers = a.t + 1;
-    const size_t len0 = a.leaves[0]->n, per = len0 / a.batch_size;
-    const int num_layers = ceil_log2(per);
-    const std::vector<fe> lam2t = shamir_lagrange_first(senders), lamt = shamir_lagrange_first(openers);
-    auto sync_all = [&] {
-        for (int p = 0; p < a.n; p++) rc_check(cozk_ctx_synchronize(a.pcs[p]), a.pcs[p], "ctx_synchronize");
-    };
+static inline void shamir_gp_sync_all(const ShamirGpArgs& a) {
+    for (int p = 0; p < a.n; p++) rc_check(cozk_ctx_synchronize(a.pcs[p]), a.pcs[p], "ctx_synchronize");
+}
 
-    // ---- construct: layers[i][p], senders only (a party above 2t re-deals nothing and opens nothing: its share of a level is dropped)
-    sync_all();
-    double t0 = now_ms();
-    std::vector<std::vector<LayerH>> layers((size_t)num_layers);
+// M = batch_size + 4 sum_layers rounds(layer): the openings of degree 2t of one proof
+static inline size_t shamir_gp_num_openings(size_t n_leaves, size_t batch_size) {
+    const int num_layers = ceil_log2(n_leaves / batch_size), nv_out = ceil_log2(batch_size);
+    size_t M = batch_size;
+    for (int k = 0; k < num_layers; k++) M += (size_t)4 * (size_t)(nv_out + k);
+    return M;
+}
+
+// ---- construct: layers[i][p], senders only (a party above 2t multiplies nothing and opens nothing: its share of a level is
+// dropped).  mul_level(i, v, next) is one tree level for all parties, next[q][j] = party q's share of v[2j] v[2j + 1]: the
+// resharing multiplication or the king's.  Every stream is drained at both ends; returns the host time between them.
+template <class MulLevel>
+static double shamir_gp_construct(const ShamirGpArgs& a, std::vector<std::vector<LayerH>>& layers, MulLevel mul_level) {
+    const int senders = 2 * a.t + 1;
+    const int num_layers = ceil_log2(a.leaves[0]->n / a.batch_size);
+    shamir_gp_sync_all(a);
+    const double t0 = now_ms();
+    layers.clear();
+    layers.resize((size_t)num_layers);
     std::vector<VecH> cur((size_t)a.n);  // level i as vectors (level 0: the caller's)
-    uint64_t ctr = a.mul_counter;
     for (int i = 0; i < num_layers; i++) {
         std::vector<const cozk_vec*> v((size_t)a.n, nullptr);
         for (int p = 0; p < senders; p++) v[(size_t)p] = i ? cur[(size_t)p].h : a.leaves[p];
         std::vector<cozk_vec*> next((size_t)a.n, nullptr);
-        if (i + 1 < num_layers) {
-            rc_check(cozk_shamir_mul_pairs_inproc(a.pcs, v.data(), a.mul_keys, a.t, a.n, ctr, next.data()), a.pcs[0], "shamir_mul_pairs_inproc");
-            ctr += v[0]->n / 2;
-        }
+        if (i + 1 < num_layers) mul_level(i, v.data(), next.data());
         std::vector<VecH> nx((size_t)a.n);
         for (int p = 0; p < a.n; p++) nx[(size_t)p] = VecH(next[(size_t)p]);
         for (int p = 0; p < senders; p++) {  // level 0 is copied (the caller keeps its leaves), a level of our own is adopted
@@ -95,37 +109,45 @@ static void shamir_gp_prove(const ShamirGpArgs& a, cozk_shamir_gp& h) {
         cur = std::move(nx);
     }
     cur.clear();
-    sync_all();
-    double t1 = now_ms();
-    h.res.t_construct_ms = t1 - t0;
+    shamir_gp_sync_all(a);
+    return now_ms() - t0;
+}
 
-    // ---- masks: pair 0 of one preprocessing call, as a sharing of zero of degree 2t
-    const int nv_out = ceil_log2(a.batch_size);
-    size_t M = a.batch_size;
-    for (int k = 0; k < num_layers; k++) M += (size_t)4 * (size_t)(nv_out + k);
+// ---- masks: pair 0 of one preprocessing call of M elements, as a sharing of zero of degree 2t; zero[p][m] for the senders.  Only
+// the senders' halves of that one pair are dealt to and extracted: the values are those of cozk_shamir_rand_inproc
+static std::vector<std::vector<fe>> shamir_gp_zero_masks(const ShamirGpArgs& a, const uint8_t* const* rand_keys, uint64_t rand_counter, size_t M) {
+    const int senders = 2 * a.t + 1;
     std::vector<std::vector<fe>> zero((size_t)senders, std::vector<fe>(M));
-    {
-        const size_t cnt = (size_t)(a.n - a.t), tbl = (size_t)a.n * cnt;
-        std::vector<cozk_vec*> rt(tbl, nullptr), r2t(tbl, nullptr);
-        rc_check(cozk_shamir_rand_inproc(a.pcs, a.rand_keys, M, a.t, a.n, a.rand_counter, rt.data(), r2t.data()), a.pcs[0], "shamir_rand_inproc");
-        std::vector<VecH> own;
-        for (size_t i = 0; i < tbl; i++) {
-            own.emplace_back(rt[i]);
-            own.emplace_back(r2t[i]);
-        }
-        for (int p = 0; p < senders; p++) {
-            cozk_vec* z = nullptr;
-            rc_check(cozk_vec_alloc(a.pcs[p], M, COZK_SCALAR_FR, &z), a.pcs[p], "vec_alloc");
-            VecH zh(z);
-            rc_check(cozk_vec_binop(a.pcs[p], COZK_OP_SUB, 0, r2t[(size_t)p * cnt], rt[(size_t)p * cnt], z), a.pcs[p], "vec_binop");
-            std::vector<uint64_t> raw(4 * M);
-            rc_check(cozk_vec_download(a.pcs[p], z, raw.data()), a.pcs[p], "vec_download");
-            for (size_t m = 0; m < M; m++) zero[(size_t)p][m] = fe_from_u64x4(raw.data() + 4 * m);
-        }
-        sync_all();  // the pairs go back to their parties' pools behind everything that read them
+    std::vector<cozk_vec*> rt((size_t)senders, nullptr), r2t((size_t)senders, nullptr);
+    rc_check(shamir_rand_pairs_inproc(a.pcs, rand_keys, M, a.t, a.n, rand_counter, 1, senders, rt.data(), r2t.data()), a.pcs[0], "shamir_rand_pairs_inproc");
+    std::vector<VecH> own;
+    for (int p = 0; p < senders; p++) {
+        own.emplace_back(rt[(size_t)p]);
+        own.emplace_back(r2t[(size_t)p]);
     }
+    for (int p = 0; p < senders; p++) {
+        cozk_vec* z = nullptr;
+        rc_check(cozk_vec_alloc(a.pcs[p], M, COZK_SCALAR_FR, &z), a.pcs[p], "vec_alloc");
+        VecH zh(z);
+        rc_check(cozk_vec_binop(a.pcs[p], COZK_OP_SUB, 0, r2t[(size_t)p], rt[(size_t)p], z), a.pcs[p], "vec_binop");
+        std::vector<uint64_t> raw(4 * M);
+        rc_check(cozk_vec_download(a.pcs[p], z, raw.data()), a.pcs[p], "vec_download");
+        for (size_t m = 0; m < M; m++) zero[(size_t)p][m] = fe_from_u64x4(raw.data() + 4 * m);
+    }
+    shamir_gp_sync_all(a);  // the pairs go back to their parties' pools behind everything that read them
+    return zero;
+}
 
-    // ---- the openings of degree 2t: local[p] = sender p's unmasked value of opening m
+// ---- openings, rounds, finals, transcript and proof on constructed layers with given masks: what both constructs share.
+// t_prove_ms runs from t_start (the caller's clock, every stream drained) to the drain behind the last round
+static void shamir_gp_prove_layers(const ShamirGpArgs& a, std::vector<std::vector<LayerH>>& layers, const std::vector<std::vector<fe>>& zero, double t_start,
+                                   cozk_shamir_gp& h) {
+    const int senders = 2 * a.t + 1, openers = a.t + 1;
+    const int num_layers = (int)layers.size();
+    const size_t M = zero[0].size();
+    const std::vector<fe> lam2t = shamir_lagrange_first(senders), lamt = shamir_lagrange_first(openers);
+
+    // the openings of degree 2t: local[p] = sender p's unmasked value of opening m
     size_t m_next = 0;
     h.msgs.assign(M * (size_t)senders, Fr::zero());
     auto open_2t = [&](const fe* local) {
@@ -200,8 +222,8 @@ static void shamir_gp_prove(const ShamirGpArgs& a, cozk_shamir_gp& h) {
         layers[(size_t)i].clear();  // bound: nothing reads it again
     }
     COZK_REQUIRE(m_next == M, "shamir_gp: fewer openings than masks");
-    sync_all();
-    h.res.t_prove_ms = now_ms() - t1;
+    shamir_gp_sync_all(a);
+    h.res.t_prove_ms = now_ms() - t_start;
 
     Writer wr;
     proof.write(wr);
@@ -222,9 +244,165 @@ static void shamir_gp_prove(const ShamirGpArgs& a, cozk_shamir_gp& h) {
     }
 }
 
+// what both provers require of their arguments once degree and num_parties are known to be in range
+static void shamir_gp_require_leaves(const std::string& w, cozk_ctx* const* party_ctxs, const cozk_vec* const* leaves, int degree, const char* missing) {
+    for (int p = 0; p <= 2 * degree; p++) {
+        COZK_REQUIRE(leaves[p], w + missing);
+        COZK_REQUIRE(leaves[p]->kind == COZK_SCALAR_FR, w + ": the leaves must be FR vectors");
+        COZK_REQUIRE(leaves[p]->n == leaves[0]->n, w + ": the leaves must have one length");
+        COZK_REQUIRE(leaves[p]->ctx == party_ctxs[p], w + ": party p's leaves must be a vector of party_ctxs[p]");
+    }
+}
+static void shamir_gp_require_shape(const std::string& w, size_t n, size_t batch_size) {
+    COZK_REQUIRE(batch_size > 0 && n > 0 && n % batch_size == 0, w + ": leaves.len() % batch_size != 0");
+    const size_t per = n / batch_size;
+    COZK_REQUIRE(per >= 2 && (per & (per - 1)) == 0, w + ": leaves per circuit must be a power of two >= 2");
+}
+static void shamir_gp_require_parties(const std::string& w, int degree, int num_parties) {
+    COZK_REQUIRE(degree >= 1 && 2 * degree <= COZK_SHAMIR_MAX_DEGREE, w + ": 1 <= degree and 2 * degree <= COZK_SHAMIR_MAX_DEGREE (the masks are dealt with degree 2t)");
+    COZK_REQUIRE(2 * degree + 1 <= num_parties && num_parties <= COZK_SHAMIR_MAX_PARTIES, w + ": 2 * degree + 1 <= num_parties <= COZK_SHAMIR_MAX_PARTIES");
+}
+
 }  // namespace cozk
 
+// The preprocessing of one king grand product (cozk_shamir_gp_prep_inproc): everything that needs fresh randomness, made before the
+// leaves exist.  (A) the opening masks of cozk_shamir_gp_prove_inproc, M elements at rand_counter, pair 0, held on the host as the
+// senders' sharings of zero; (B) ONE dealing of n_leaves / 2 elements at rand_counter + M, of which pair 0 serves level 0 whole and
+// pair 1 serves level i >= 1 at the element offset n_leaves / 2 - n_leaves / 2^i (the sum of the output lengths of levels 1..i - 1;
+// the last level ends at n_leaves / 2 - 2 batch_size).  Only what a proof uses is extracted: no pair for 2 leaves per circuit, one
+// for 4, two otherwise; the degree-2t halves for the senders only.
+struct cozk_shamir_gp_prep {
+    std::vector<cozk_ctx*> pcs;
+    int t = 0, n = 0, pairs = 0;
+    size_t n_leaves = 0, batch_size = 0, pair_elems = 0;
+    bool used = false;
+    double t_offline_ms = 0;
+    std::vector<std::vector<fe>> zero;  // [p <= 2t][m < M]
+    std::vector<cozk_vec*> rt, r2t;     // rt[q * pairs + k], every party; r2t[p * pairs + k], senders
+    void release_pairs() {
+        for (cozk_vec* v : rt) cozk_vec_free(v);
+        for (cozk_vec* v : r2t) cozk_vec_free(v);
+        rt.clear();
+        r2t.clear();
+    }
+    ~cozk_shamir_gp_prep() { release_pairs(); }
+};
+
 extern "C" {
+
+int cozk_shamir_gp_prep_inproc(cozk_ctx* const* party_ctxs, const uint8_t* const* rand_keys, size_t n_leaves, size_t batch_size, int degree,
+                               int num_parties, uint64_t rand_counter, cozk_shamir_gp_prep** prep) {
+    using namespace cozk;
+    cozk_ctx* const c0 = party_ctxs && num_parties >= 1 && num_parties <= COZK_SHAMIR_MAX_PARTIES ? party_ctxs[0] : nullptr;  // receives the error message
+    int rc = cozk_guard(c0, [&] { COZK_REQUIRE(prep, "shamir_gp_prep_inproc: null output"); });
+    if (rc != COZK_OK) return rc;
+    *prep = nullptr;
+    const std::string w = "shamir_gp_prep_inproc";
+    rc = cozk_guard(c0, [&] {
+        COZK_REQUIRE(party_ctxs && rand_keys, w + ": null argument");
+        shamir_gp_require_parties(w, degree, num_parties);
+        for (int p = 0; p < num_parties; p++) {
+            COZK_REQUIRE(party_ctxs[p], w + ": null party context");
+            COZK_REQUIRE(rand_keys[p], w + ": every party needs its mask key block");
+        }
+        shamir_gp_require_shape(w, n_leaves, batch_size);
+    });
+    if (rc != COZK_OK) return rc;
+    cozk_shamir_gp_prep* h = new cozk_shamir_gp_prep();
+    rc = cozk_guard(c0, [&] {
+        const ShamirGpArgs a{party_ctxs, nullptr, batch_size, degree, num_parties, nullptr, false};
+        const int senders = 2 * degree + 1, levels = ceil_log2(n_leaves / batch_size) - 1;
+        h->pcs.assign(party_ctxs, party_ctxs + num_parties);
+        h->t = degree, h->n = num_parties, h->n_leaves = n_leaves, h->batch_size = batch_size;
+        h->pairs = levels <= 0 ? 0 : levels == 1 ? 1 : 2;
+        h->pair_elems = h->pairs ? n_leaves / 2 : 0;
+        shamir_gp_sync_all(a);
+        const double t0 = now_ms();
+        const size_t M = shamir_gp_num_openings(n_leaves, batch_size);
+        h->zero = shamir_gp_zero_masks(a, rand_keys, rand_counter, M);
+        if (h->pairs) {
+            h->rt.assign((size_t)num_parties * h->pairs, nullptr);
+            h->r2t.assign((size_t)senders * h->pairs, nullptr);
+            rc_check(shamir_rand_pairs_inproc(party_ctxs, rand_keys, h->pair_elems, degree, num_parties, rand_counter + M, h->pairs, num_parties, h->rt.data(),
+                                              h->r2t.data()),
+                     c0, "shamir_rand_pairs_inproc");
+        }
+        shamir_gp_sync_all(a);
+        h->t_offline_ms = now_ms() - t0;
+    });
+    if (rc != COZK_OK) {
+        for (int p = 0; p < num_parties; p++) (void)hipStreamSynchronize(party_ctxs[p]->stream);
+        delete h;
+        return rc;
+    }
+    *prep = h;
+    return COZK_OK;
+}
+
+int cozk_shamir_gp_prep_free(cozk_shamir_gp_prep* prep) {
+    delete prep;
+    return COZK_OK;
+}
+
+int cozk_shamir_gp_prep_get_result(const cozk_shamir_gp_prep* prep, cozk_shamir_gp_prep_result* res) {
+    if (!prep || !res) return COZK_ERR_INVALID_ARG;
+    res->n_openings = prep->zero.empty() ? 0 : prep->zero[0].size();
+    res->pair_elems = prep->pair_elems;
+    res->pairs_held = (int)(prep->rt.size() / (size_t)prep->n);
+    res->used = prep->used ? 1 : 0;
+    res->t_offline_ms = prep->t_offline_ms;
+    return COZK_OK;
+}
+
+int cozk_shamir_gp_prove_king_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* leaves, size_t batch_size, cozk_shamir_gp_prep* prep, int king,
+                                     const char* label, int verify, cozk_shamir_gp** out) {
+    using namespace cozk;
+    cozk_ctx* const c0 = party_ctxs ? party_ctxs[0] : nullptr;  // receives the error message (a prover has at least three parties)
+    int rc = cozk_guard(c0, [&] { COZK_REQUIRE(out, "shamir_gp_prove_king_inproc: null output"); });
+    if (rc != COZK_OK) return rc;
+    *out = nullptr;
+    const std::string w = "shamir_gp_prove_king_inproc";
+    rc = cozk_guard(c0, [&] {
+        COZK_REQUIRE(party_ctxs && leaves && prep && label, w + ": null argument");
+        COZK_REQUIRE(king >= 0 && king < prep->n, w + ": 0 <= king < num_parties");
+        for (int p = 0; p < prep->n; p++) {
+            COZK_REQUIRE(party_ctxs[p], w + ": null party context");
+            COZK_REQUIRE(party_ctxs[p] == prep->pcs[(size_t)p], w + ": the preprocessing was made for other party contexts");
+        }
+        shamir_gp_require_leaves(w, party_ctxs, leaves, prep->t, ": parties 0..2 * degree need their leaves");
+        shamir_gp_require_shape(w, leaves[0]->n, batch_size);
+        COZK_REQUIRE(leaves[0]->n == prep->n_leaves && batch_size == prep->batch_size, w + ": the preprocessing was made for another (n_leaves, batch_size)");
+        COZK_REQUIRE(!prep->used, w + ": the preprocessing has been used (a pair must never be used twice)");
+    });
+    if (rc != COZK_OK) return rc;
+    const int num_parties = prep->n;
+    prep->used = true;
+    cozk_shamir_gp* h = new cozk_shamir_gp();
+    memset(&h->res, 0, sizeof h->res);
+    rc = cozk_guard(c0, [&] {
+        const ShamirGpArgs a{party_ctxs, leaves, batch_size, prep->t, num_parties, label, verify != 0};
+        const size_t half = prep->n_leaves / 2;
+        std::vector<std::vector<LayerH>> layers;
+        h->res.t_construct_ms = shamir_gp_construct(a, layers, [&](int i, const cozk_vec* const* v, cozk_vec** next) {
+            const int k = i ? 1 : 0;  // pair 0 serves level 0 whole, pair 1 the levels above at their offsets
+            std::vector<const cozk_vec*> rt((size_t)num_parties, nullptr), r2t((size_t)num_parties, nullptr);
+            for (int q = 0; q < num_parties; q++) rt[(size_t)q] = prep->rt[(size_t)q * prep->pairs + k];
+            for (int p = 0; p <= 2 * prep->t; p++) r2t[(size_t)p] = prep->r2t[(size_t)p * prep->pairs + k];
+            const size_t off = i ? half - (prep->n_leaves >> i) : 0;
+            rc_check(cozk_shamir_mul_king_pairs_inproc(party_ctxs, v, rt.data(), r2t.data(), off, prep->t, num_parties, king, next), c0,
+                     "shamir_mul_king_pairs_inproc");
+        });
+        prep->release_pairs();  // consumed: every stream has drained behind the construct
+        shamir_gp_prove_layers(a, layers, prep->zero, now_ms(), *h);
+    });
+    if (rc != COZK_OK) {
+        for (int p = 0; p < num_parties; p++) (void)hipStreamSynchronize(party_ctxs[p]->stream);
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return COZK_OK;
+}
 
 int cozk_shamir_gp_prove_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* leaves, size_t batch_size, const uint8_t* const* mul_keys,
                                 const uint8_t* const* rand_keys, int degree, int num_parties, uint64_t mul_counter, uint64_t rand_counter,
@@ -234,32 +412,32 @@ int cozk_shamir_gp_prove_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* con
     int rc = cozk_guard(c0, [&] { COZK_REQUIRE(out, "shamir_gp_prove_inproc: null output"); });
     if (rc != COZK_OK) return rc;
     *out = nullptr;
+    const std::string w = "shamir_gp_prove_inproc";
     rc = cozk_guard(c0, [&] {
         COZK_REQUIRE(party_ctxs && leaves && mul_keys && rand_keys && label, "shamir_gp_prove_inproc: null argument");
-        COZK_REQUIRE(degree >= 1 && 2 * degree <= COZK_SHAMIR_MAX_DEGREE,
-                     "shamir_gp_prove_inproc: 1 <= degree and 2 * degree <= COZK_SHAMIR_MAX_DEGREE (the masks are dealt with degree 2t)");
-        COZK_REQUIRE(2 * degree + 1 <= num_parties && num_parties <= COZK_SHAMIR_MAX_PARTIES,
-                     "shamir_gp_prove_inproc: 2 * degree + 1 <= num_parties <= COZK_SHAMIR_MAX_PARTIES");
+        shamir_gp_require_parties(w, degree, num_parties);
         for (int p = 0; p < num_parties; p++) {
             COZK_REQUIRE(party_ctxs[p], "shamir_gp_prove_inproc: null party context");
             COZK_REQUIRE(rand_keys[p], "shamir_gp_prove_inproc: every party needs its mask key block");
         }
-        for (int p = 0; p <= 2 * degree; p++) {
-            COZK_REQUIRE(leaves[p] && mul_keys[p], "shamir_gp_prove_inproc: parties 0..2 * degree need their leaves and their key block");
-            COZK_REQUIRE(leaves[p]->kind == COZK_SCALAR_FR, "shamir_gp_prove_inproc: the leaves must be FR vectors");
-            COZK_REQUIRE(leaves[p]->n == leaves[0]->n, "shamir_gp_prove_inproc: the leaves must have one length");
-            COZK_REQUIRE(leaves[p]->ctx == party_ctxs[p], "shamir_gp_prove_inproc: party p's leaves must be a vector of party_ctxs[p]");
-        }
-        const size_t n = leaves[0]->n;
-        COZK_REQUIRE(batch_size > 0 && n > 0 && n % batch_size == 0, "shamir_gp_prove_inproc: leaves.len() % batch_size != 0");
-        const size_t per = n / batch_size;
-        COZK_REQUIRE(per >= 2 && (per & (per - 1)) == 0, "shamir_gp_prove_inproc: leaves per circuit must be a power of two >= 2");
+        for (int p = 0; p <= 2 * degree; p++) COZK_REQUIRE(leaves[p] && mul_keys[p], "shamir_gp_prove_inproc: parties 0..2 * degree need their leaves and their key block");
+        shamir_gp_require_leaves(w, party_ctxs, leaves, degree, ": parties 0..2 * degree need their leaves and their key block");
+        shamir_gp_require_shape(w, leaves[0]->n, batch_size);
     });
     if (rc != COZK_OK) return rc;
     cozk_shamir_gp* h = new cozk_shamir_gp();
     memset(&h->res, 0, sizeof h->res);
     rc = cozk_guard(c0, [&] {
-        shamir_gp_prove(ShamirGpArgs{party_ctxs, leaves, batch_size, mul_keys, rand_keys, degree, num_parties, mul_counter, rand_counter, label, verify != 0}, *h);
+        const ShamirGpArgs a{party_ctxs, leaves, batch_size, degree, num_parties, label, verify != 0};
+        std::vector<std::vector<LayerH>> layers;
+        uint64_t ctr = mul_counter;  // level i: mul_counter + the sum of the earlier levels' output lengths
+        h->res.t_construct_ms = shamir_gp_construct(a, layers, [&](int, const cozk_vec* const* v, cozk_vec** next) {
+            rc_check(cozk_shamir_mul_pairs_inproc(party_ctxs, v, mul_keys, degree, num_parties, ctr, next), c0, "shamir_mul_pairs_inproc");
+            ctr += v[0]->n / 2;
+        });
+        const double t1 = now_ms();
+        const std::vector<std::vector<fe>> zero = shamir_gp_zero_masks(a, rand_keys, rand_counter, shamir_gp_num_openings(leaves[0]->n, batch_size));
+        shamir_gp_prove_layers(a, layers, zero, t1, *h);
     });
     if (rc != COZK_OK) {
         for (int p = 0; p < num_parties; p++) (void)hipStreamSynchronize(party_ctxs[p]->stream);

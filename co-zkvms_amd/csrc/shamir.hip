@@ -237,6 +237,39 @@ __global__ void __launch_bounds__(256) k_fe_mul_add(const fe* __restrict__ a, co
     if (i < n) fe_store(out + i, Fr::add(Fr::mul(fe_load(a + i), fe_load(b + i)), fe_load(c + i)));
 }
 
+// out[j] = v[2 j] v[2 j + 1] + r2t[j]: k_fe_mul_add for one interleaved GKR layer, the mask of a tree level of the king construct.
+// A lane owns product j and reads its 64 contiguous bytes of the layer: 96 B read, 32 B written, the product never stored.  The
+// caller passes r2t already advanced by its element offset into the half of the pair: no slice is copied.
+__global__ void __launch_bounds__(256) k_shamir_mask_pairs(const fe* __restrict__ v, const fe* __restrict__ r2t, fe* __restrict__ out, size_t m) {
+    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < m) fe_store(out + j, Fr::add(Fr::mul(fe_load(v + 2 * j), fe_load(v + 2 * j + 1)), fe_load(r2t + j)));
+}
+
+// ------------------------------------------------------------------ king finish: z = sum_p lambda_p m_p, c_q = z - rt_q for every q
+// The king's open and the unmask of every party of its device in ONE launch.  A lane owns element i: z as in k_shamir_combine
+// (lambda in the kernel arguments, one FrWide accumulator reduced once: canonical), then a ROLLED loop over the `count` recipients
+// whose pointers travel in the kernel arguments, indexed by the wave-uniform q as ShamirExtractArgs' are: one load, one Fr::sub
+// (canonical in, canonical out) and one store per recipient; z itself is stored only where the caller wants it (parties on other
+// devices).  rt[q] arrives advanced by the element offset into the half of the pair.  (k + count) x 32 B read and count x 32 B
+// (+ 32 B) written per element.
+struct ShamirKingFinishArgs {
+    const fe* m[COZK_SHAMIR_MAX_PARTIES];
+    fe lambda[COZK_SHAMIR_MAX_PARTIES];
+    const fe* rt[COZK_SHAMIR_MAX_PARTIES];
+    fe* out[COZK_SHAMIR_MAX_PARTIES];
+};
+__global__ void __launch_bounds__(256) k_shamir_king_finish(ShamirKingFinishArgs a, int k, int count, fe* __restrict__ z_out, size_t n) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    FrWide w;
+    fr_wide_zero(w);
+    for (int j = 0; j < k; j++) fr_wide_mac(w, fe_load(a.m[j] + i), a.lambda[j]);
+    const fe z = fr_wide_reduce(w);
+    if (z_out) fe_store(z_out + i, z);
+#pragma unroll 1
+    for (int q = 0; q < count; q++) fe_store(a.out[q] + i, Fr::sub(z, fe_load(a.rt[q] + i)));
+}
+
 // ------------------------------------------------------------------ host
 static fe fe_from_abi(const uint64_t s[4]) {
     fe r;
@@ -788,11 +821,13 @@ static void launch_mul_add(hipStream_t st, const cozk_vec* a, const cozk_vec* b,
     HIP_TRY(hipGetLastError());
 }
 
-// one degree of cozk_shamir_rand_inproc: every party deals with `deg` coefficient keys from keys[p][first], every party
-// extracts np - t vectors into r[q * (np - t) + k].  On failure nothing of its own is left; the caller frees r.
-static int rand_pass(cozk_ctx* const* pcs, const uint8_t* const* keys, size_t n, int t, int first, int deg, int np, uint64_t counter, cozk_vec** r) {
+// one degree of the preprocessing: every party deals with `deg` coefficient keys from keys[p][first] to parties 0..rcp - 1, each
+// of which extracts `count` vectors into r[q * count + k] (cozk_shamir_rand_inproc: rcp = np, count = np - t).  On failure nothing
+// of its own is left; the caller frees r.
+static int rand_pass(cozk_ctx* const* pcs, const uint8_t* const* keys, size_t n, int first, int deg, int np, int rcp, int count, uint64_t counter,
+                     cozk_vec** r) {
     cozk_ctx* const c0 = pcs[0];
-    std::vector<cozk_vec*> recv((size_t)np * np, nullptr);  // recv[q * np + p] = what party p dealt to party q, a block of party q
+    std::vector<cozk_vec*> recv((size_t)rcp * np, nullptr);  // recv[q * np + p] = what party p dealt to party q, a block of party q
     std::vector<fe*> stage(np, nullptr);
     int rc = COZK_OK;
     auto fail = [&](int code, int p) {
@@ -802,7 +837,7 @@ static int rand_pass(cozk_ctx* const* pcs, const uint8_t* const* keys, size_t n,
         for (cozk_vec* v : recv) cozk_vec_free(v);
         return code;
     };
-    for (int q = 0; q < np; q++)
+    for (int q = 0; q < rcp; q++)
         for (int p = 0; p < np; p++)
             if ((rc = cozk_vec_alloc(pcs[q], n, COZK_SCALAR_FR, &recv[(size_t)q * np + p])) != COZK_OK) return fail(rc, q);
     if (n) {
@@ -815,14 +850,14 @@ static int rand_pass(cozk_ctx* const* pcs, const uint8_t* const* keys, size_t n,
             cozk_ctx* dealer = pcs[p];
             rc = cozk_guard(dealer, [&] {
                 size_t remote = 0;
-                for (int q = 0; q < np; q++) remote += pcs[q]->device != dealer->device;
+                for (int q = 0; q < rcp; q++) remote += pcs[q]->device != dealer->device;
                 if (remote) stage[p] = (fe*)ctx_dev_alloc(dealer, remote * n * sizeof(fe));
                 ShamirOut o;
                 memset(&o, 0, sizeof o);
                 size_t k = 0;
-                for (int q = 0; q < np; q++) o.p[q] = pcs[q]->device != dealer->device ? stage[p] + n * k++ : (fe*)recv[(size_t)q * np + p]->d;
-                launch_share(dealer->stream, rand_prf_src(keys[p], first, deg, counter), o, n, deg, np);
-                for (int q = 0; q < np; q++)
+                for (int q = 0; q < rcp; q++) o.p[q] = pcs[q]->device != dealer->device ? stage[p] + n * k++ : (fe*)recv[(size_t)q * np + p]->d;
+                launch_share(dealer->stream, rand_prf_src(keys[p], first, deg, counter), o, n, deg, rcp);
+                for (int q = 0; q < rcp; q++)
                     if (pcs[q]->device != dealer->device)
                         HIP_TRY(hipMemcpyPeerAsync(recv[(size_t)q * np + p]->d, pcs[q]->device, o.p[q], dealer->device, n * sizeof(fe), dealer->stream));
             });
@@ -837,8 +872,8 @@ static int rand_pass(cozk_ctx* const* pcs, const uint8_t* const* keys, size_t n,
             if (rc != COZK_OK) return fail(rc, p);
         }
     }
-    for (int q = 0; q < np; q++) {  // the extraction, on each party's own stream; its pool takes the blocks back behind it
-        rc = cozk_shamir_rand_extract(pcs[q], &recv[(size_t)q * np], np, np - t, &r[(size_t)q * (np - t)]);
+    for (int q = 0; q < rcp; q++) {  // the extraction, on each party's own stream; its pool takes the blocks back behind it
+        rc = cozk_shamir_rand_extract(pcs[q], &recv[(size_t)q * np], np, count, &r[(size_t)q * count]);
         if (rc != COZK_OK) return fail(rc, q);
         for (int p = 0; p < np; p++) {
             cozk_vec_free(recv[(size_t)q * np + p]);
@@ -846,6 +881,24 @@ static int rand_pass(cozk_ctx* const* pcs, const uint8_t* const* keys, size_t n,
         }
     }
     return COZK_OK;
+}
+
+// the preprocessing of the king grand product (csrc/host/shamir_gp.hpp), which extracts only what it uses: `count` <= np - t pairs,
+// the degree-t halves for parties 0..rcp_t - 1 into r_t[q * count + k], the degree-2t halves for the senders 0..2t into
+// r_2t[p * count + k].  The values are those of cozk_shamir_rand_inproc at the same keys and counter (a party that is dealt
+// nothing changes no other party's vectors).  Arguments are the caller's to check; on failure both tables are NULL.
+int shamir_rand_pairs_inproc(cozk_ctx* const* pcs, const uint8_t* const* keys, size_t n_elems, int t, int np, uint64_t counter, int count, int rcp_t,
+                             cozk_vec** r_t, cozk_vec** r_2t) {
+    const int senders = 2 * t + 1;
+    for (int i = 0; i < rcp_t * count; i++) r_t[i] = nullptr;
+    for (int i = 0; i < senders * count; i++) r_2t[i] = nullptr;
+    int rc = rand_pass(pcs, keys, n_elems, 1, t, np, rcp_t, count, counter, r_t);
+    if (rc == COZK_OK) rc = rand_pass(pcs, keys, n_elems, 1 + t, 2 * t, np, senders, count, counter, r_2t);
+    if (rc != COZK_OK) {
+        free_all(r_t, rcp_t * count);
+        free_all(r_2t, senders * count);
+    }
+    return rc;
 }
 
 extern "C" {
@@ -923,8 +976,8 @@ int cozk_shamir_rand_inproc(cozk_ctx* const* party_ctxs, const uint8_t* const* k
     });
     if (rc != COZK_OK) return rc;
     // one degree after the other: n^2 receive vectors are alive at a time, not 2 n^2
-    rc = rand_pass(party_ctxs, keys, n_elems, degree, 1, degree, num_parties, counter, r_t);
-    if (rc == COZK_OK) rc = rand_pass(party_ctxs, keys, n_elems, degree, 1 + degree, 2 * degree, num_parties, counter, r_2t);
+    rc = rand_pass(party_ctxs, keys, n_elems, 1, degree, num_parties, num_parties, num_parties - degree, counter, r_t);
+    if (rc == COZK_OK) rc = rand_pass(party_ctxs, keys, n_elems, 1 + degree, 2 * degree, num_parties, num_parties, num_parties - degree, counter, r_2t);
     if (rc != COZK_OK)
         for (size_t i = 0; i < len; i++) {
             cozk_vec_free(r_t[i]);
@@ -1151,6 +1204,233 @@ int cozk_shamir_mul_king_vec(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b
         *out = nullptr;
     }
     return rc;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ the king multiplication of one interleaved GKR layer
+// (a tree level of the king grand product).  The halves of a pair are addressed by an element offset, so that one preprocessed
+// pair serves many levels; the king's open and the unmasks of its device are one launch (k_shamir_king_finish).
+static void launch_mask_pairs(hipStream_t st, const cozk_vec* v, const cozk_vec* r_2t, size_t off, fe* out) {
+    const size_t m = v->n / 2;
+    if (m == 0) return;
+    k_shamir_mask_pairs<<<(unsigned)((m + 255) / 256), 256, 0, st>>>((const fe*)v->d, (const fe*)r_2t->d + off, out, m);
+    HIP_TRY(hipGetLastError());
+}
+
+// z = sum_{j < k} lambda_j m[j], lambda = lagrange(1..k); out[q] = z - (rt[q] + off) for q < count; z_out may be null
+static void launch_king_finish(hipStream_t st, const fe* const* m, int k, const fe* const* rt, size_t off, int count, fe* const* out, fe* z_out, size_t n) {
+    if (n == 0) return;
+    ShamirKingFinishArgs a;
+    memset(&a, 0, sizeof a);
+    uint32_t points[COZK_SHAMIR_MAX_PARTIES];
+    for (int j = 0; j < k; j++) points[j] = (uint32_t)j + 1;
+    lagrange_host(points, (size_t)k, a.lambda);
+    for (int j = 0; j < k; j++) a.m[j] = m[j];
+    for (int q = 0; q < count; q++) {
+        a.rt[q] = rt[q] + off;
+        a.out[q] = out[q];
+    }
+    k_shamir_king_finish<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(a, k, count, z_out, n);
+    HIP_TRY(hipGetLastError());
+}
+
+// off + len <= have without overflow
+static bool slice_fits(size_t off, size_t len, size_t have) { return off <= have && len <= have - off; }
+
+extern "C" {
+
+int cozk_shamir_mul_mask_pairs(cozk_ctx* ctx, const cozk_vec* v, const cozk_vec* r_2t, size_t r_offset, cozk_vec** out) {
+    if (int rc0 = require_out(ctx, out, "shamir_mul_mask_pairs: null output")) return rc0;
+    *out = nullptr;
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && v && r_2t, "shamir_mul_mask_pairs: null argument");
+        require_pairs("shamir_mul_mask_pairs", v);
+        COZK_REQUIRE(r_2t->kind == COZK_SCALAR_FR, "shamir_mul_mask_pairs: the mask must be an FR vector");
+        COZK_REQUIRE(slice_fits(r_offset, v->n / 2, r_2t->n), "shamir_mul_mask_pairs: r_offset + len(v) / 2 <= len(r_2t)");
+    });
+    if (rc != COZK_OK) return rc;
+    rc = cozk_vec_alloc(ctx, v->n / 2, COZK_SCALAR_FR, out);
+    if (rc != COZK_OK) return rc;
+    rc = cozk_guard(ctx, [&] { launch_mask_pairs(ctx->stream, v, r_2t, r_offset, (fe*)(*out)->d); });
+    if (rc != COZK_OK) {
+        cozk_vec_free(*out);
+        *out = nullptr;
+    }
+    return rc;
+}
+
+int cozk_shamir_king_finish(cozk_ctx* ctx, const cozk_vec* const* masked, int degree, const cozk_vec* const* r_t, size_t r_offset, int count,
+                            cozk_vec** out, cozk_vec** z_out) {
+    if (z_out) *z_out = nullptr;
+    if (int rc0 = require_out(ctx, out, "shamir_king_finish: null output")) return rc0;
+    clear_outputs(out, count);
+    const int k = 2 * degree + 1;
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && masked && r_t, "shamir_king_finish: null argument");
+        COZK_REQUIRE(degree >= 1 && degree <= COZK_SHAMIR_MAX_DEGREE, "shamir_king_finish: 1 <= degree <= COZK_SHAMIR_MAX_DEGREE (2 * degree + 1 masked vectors)");
+        COZK_REQUIRE(count >= 1 && count <= COZK_SHAMIR_MAX_PARTIES, "shamir_king_finish: 1 <= count <= COZK_SHAMIR_MAX_PARTIES");
+        for (int j = 0; j < k; j++) {
+            COZK_REQUIRE(masked[j] && masked[j]->kind == COZK_SCALAR_FR, "shamir_king_finish: 2 * degree + 1 masked FR vectors");
+            COZK_REQUIRE(masked[j]->n == masked[0]->n, "shamir_king_finish: the masked vectors must have one length");
+        }
+        for (int q = 0; q < count; q++) {
+            COZK_REQUIRE(r_t[q] && r_t[q]->kind == COZK_SCALAR_FR, "shamir_king_finish: count FR first halves of the pair");
+            COZK_REQUIRE(slice_fits(r_offset, masked[0]->n, r_t[q]->n), "shamir_king_finish: r_offset + len(masked) <= len(r_t)");
+        }
+    });
+    if (rc != COZK_OK) return rc;
+    const size_t n = masked[0]->n;
+    rc = alloc_outputs(ctx, nullptr, n, count, out);
+    if (rc != COZK_OK) return rc;
+    if (z_out && (rc = cozk_vec_alloc(ctx, n, COZK_SCALAR_FR, z_out)) != COZK_OK) {
+        *z_out = nullptr;
+        free_all(out, count);
+        return rc;
+    }
+    rc = cozk_guard(ctx, [&] {
+        const fe *m[COZK_SHAMIR_MAX_PARTIES], *rt[COZK_SHAMIR_MAX_PARTIES];
+        fe* o[COZK_SHAMIR_MAX_PARTIES];
+        for (int j = 0; j < k; j++) m[j] = (const fe*)masked[j]->d;
+        for (int q = 0; q < count; q++) {
+            rt[q] = (const fe*)r_t[q]->d;
+            o[q] = (fe*)out[q]->d;
+        }
+        launch_king_finish(ctx->stream, m, k, rt, r_offset, count, o, z_out ? (fe*)(*z_out)->d : nullptr, n);
+    });
+    if (rc != COZK_OK) {
+        free_all(out, count);
+        if (z_out) {
+            cozk_vec_free(*z_out);
+            *z_out = nullptr;
+        }
+    }
+    return rc;
+}
+
+int cozk_shamir_mul_king_pairs_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* v, const cozk_vec* const* r_t, const cozk_vec* const* r_2t,
+                                      size_t r_offset, int degree, int num_parties, int king, cozk_vec** out) {
+    cozk_ctx* const c0 = party_ctxs && num_parties >= 1 ? party_ctxs[0] : nullptr;  // receives the error message
+    if (int rc0 = require_out(c0, out, "shamir_mul_king_pairs_inproc: null output")) return rc0;
+    clear_outputs(out, num_parties);
+    const int senders = 2 * degree + 1;
+    const char* who = "shamir_mul_king_pairs_inproc";
+    int rc = cozk_guard(c0, [&] {
+        COZK_REQUIRE(party_ctxs && v && r_t && r_2t, "shamir_mul_king_pairs_inproc: null argument");
+        require_rand_args(who, degree, num_parties);
+        COZK_REQUIRE(king >= 0 && king < num_parties, "shamir_mul_king_pairs_inproc: 0 <= king < num_parties");
+        for (int p = 0; p < num_parties; p++) COZK_REQUIRE(party_ctxs[p], "shamir_mul_king_pairs_inproc: null party context");
+        COZK_REQUIRE(v[0], "shamir_mul_king_pairs_inproc: parties 0..2 * degree need their layer");
+        COZK_REQUIRE(r_t[0], "shamir_mul_king_pairs_inproc: null first half of the pair");
+        for (int p = 0; p < num_parties; p++) {
+            COZK_REQUIRE(r_t[p], "shamir_mul_king_pairs_inproc: null first half of the pair");
+            COZK_REQUIRE(r_t[p]->kind == COZK_SCALAR_FR, "shamir_mul_king_pairs_inproc: the halves of the pair must be FR vectors");
+            COZK_REQUIRE(r_t[p]->n == r_t[0]->n, "shamir_mul_king_pairs_inproc: the halves of the pair must have one length");
+            COZK_REQUIRE(r_t[p]->ctx == party_ctxs[p], "shamir_mul_king_pairs_inproc: party p's halves of the pair must be vectors of party_ctxs[p]");
+        }
+        for (int p = 0; p < senders; p++) {
+            COZK_REQUIRE(v[p], "shamir_mul_king_pairs_inproc: parties 0..2 * degree need their layer");
+            require_pairs(who, v[p]);
+            COZK_REQUIRE(v[p]->n == v[0]->n, "shamir_mul_king_pairs_inproc: the layers must have one length");
+            COZK_REQUIRE(v[p]->ctx == party_ctxs[p], "shamir_mul_king_pairs_inproc: party p's layer must be a vector of party_ctxs[p]");
+            COZK_REQUIRE(r_2t[p], "shamir_mul_king_pairs_inproc: parties 0..2 * degree need the second half of the pair");
+            COZK_REQUIRE(r_2t[p]->kind == COZK_SCALAR_FR, "shamir_mul_king_pairs_inproc: the halves of the pair must be FR vectors");
+            COZK_REQUIRE(r_2t[p]->n == r_t[0]->n, "shamir_mul_king_pairs_inproc: the halves of the pair must have one length");
+            COZK_REQUIRE(r_2t[p]->ctx == party_ctxs[p], "shamir_mul_king_pairs_inproc: party p's halves of the pair must be vectors of party_ctxs[p]");
+        }
+        COZK_REQUIRE(slice_fits(r_offset, v[0]->n / 2, r_t[0]->n), "shamir_mul_king_pairs_inproc: r_offset + len(v) / 2 <= len of the halves of the pair");
+    });
+    if (rc != COZK_OK) return rc;
+    const size_t n = v[0]->n / 2;
+    cozk_ctx* const kc = party_ctxs[king];
+    cozk_vec* m[COZK_SHAMIR_MAX_PARTIES] = {};   // m[p] = v_p[2j] v_p[2j + 1] + r2t_p[off + j], a block of the king
+    fe* stage[COZK_SHAMIR_MAX_PARTIES] = {};     // the same on a sender's other device
+    cozk_vec* zq[COZK_SHAMIR_MAX_PARTIES] = {};  // z on a party's other device, a block of that party
+    cozk_vec* z = nullptr;                       // z on the king's device: only where some party lives on another
+    auto fail = [&](int code, int p) {
+        if (party_ctxs[p] != c0) c0->last_error = party_ctxs[p]->last_error;
+        for (int q = 0; q < num_parties; q++) (void)hipStreamSynchronize(party_ctxs[q]->stream);
+        for (int s = 0; s < senders; s++) ctx_dev_free(party_ctxs[s], stage[s]);
+        free_all(m, senders);
+        free_all(zq, num_parties);
+        cozk_vec_free(z);
+        free_all(out, num_parties);
+        return code;
+    };
+    bool any_remote = false;
+    for (int p = 0; p < senders; p++)
+        if ((rc = cozk_vec_alloc(kc, n, COZK_SCALAR_FR, &m[p])) != COZK_OK) return fail(rc, king);
+    for (int q = 0; q < num_parties; q++) {
+        if (party_ctxs[q]->device != kc->device) {
+            any_remote = true;
+            if ((rc = cozk_vec_alloc(party_ctxs[q], n, COZK_SCALAR_FR, &zq[q])) != COZK_OK) return fail(rc, q);
+        }
+        if ((rc = cozk_vec_alloc(party_ctxs[q], n, COZK_SCALAR_FR, &out[q])) != COZK_OK) {
+            out[q] = nullptr;
+            return fail(rc, q);
+        }
+    }
+    if (any_remote && (rc = cozk_vec_alloc(kc, n, COZK_SCALAR_FR, &z)) != COZK_OK) return fail(rc, king);
+    if (n == 0) {
+        free_all(m, senders);
+        free_all(zq, num_parties);
+        cozk_vec_free(z);
+        return COZK_OK;
+    }
+    // the king's blocks are ordered by the king's stream only, the recipients' by theirs (see cozk_shamir_scatter): every party's
+    // stream drains before a sender's stream writes into the king's blocks and before the king's stream writes into a recipient's
+    rc = cozk_guard(c0, [&] {
+        for (int q = 0; q < num_parties; q++) HIP_TRY(hipStreamSynchronize(party_ctxs[q]->stream));
+    });
+    if (rc != COZK_OK) return fail(rc, 0);
+    for (int p = 0; p < senders; p++) {  // the mask on each sender's own stream, into the king's memory
+        cozk_ctx* sc = party_ctxs[p];
+        rc = cozk_guard(sc, [&] {
+            const bool remote = sc->device != kc->device;
+            if (remote) stage[p] = (fe*)ctx_dev_alloc(sc, n * sizeof(fe));
+            launch_mask_pairs(sc->stream, v[p], r_2t[p], r_offset, remote ? stage[p] : (fe*)m[p]->d);
+            if (remote) HIP_TRY(hipMemcpyPeerAsync(m[p]->d, kc->device, stage[p], sc->device, n * sizeof(fe), sc->stream));
+        });
+        if (rc != COZK_OK) return fail(rc, p);
+    }
+    for (int p = 0; p < senders; p++) {  // the king may read the masked products once the senders' streams have drained
+        rc = cozk_guard(party_ctxs[p], [&] {
+            HIP_TRY(hipStreamSynchronize(party_ctxs[p]->stream));
+            ctx_dev_free(party_ctxs[p], stage[p]);
+            stage[p] = nullptr;
+        });
+        if (rc != COZK_OK) return fail(rc, p);
+    }
+    rc = cozk_guard(kc, [&] {  // ONE launch on the king's stream: the open, and c_q = z - rt_q for every party of the king's device
+        const fe *mp[COZK_SHAMIR_MAX_PARTIES], *rt[COZK_SHAMIR_MAX_PARTIES];
+        fe* o[COZK_SHAMIR_MAX_PARTIES];
+        int count = 0;
+        for (int p = 0; p < senders; p++) mp[p] = (const fe*)m[p]->d;
+        for (int q = 0; q < num_parties; q++)
+            if (!zq[q]) {
+                rt[count] = (const fe*)r_t[q]->d;
+                o[count++] = (fe*)out[q]->d;
+            }
+        launch_king_finish(kc->stream, mp, senders, rt, r_offset, count, o, z ? (fe*)z->d : nullptr, n);
+        for (int q = 0; q < num_parties; q++)  // z to the other devices by the king's stream
+            if (zq[q]) HIP_TRY(hipMemcpyPeerAsync(zq[q]->d, party_ctxs[q]->device, z->d, kc->device, n * sizeof(fe), kc->stream));
+        HIP_TRY(hipStreamSynchronize(kc->stream));  // the recipients' streams may use their blocks as soon as this returns
+    });
+    if (rc != COZK_OK) return fail(rc, king);
+    free_all(m, senders);
+    cozk_vec_free(z);
+    z = nullptr;
+    for (int q = 0; q < num_parties; q++) {  // a party of another device subtracts at the offset on its own stream: the same kernel, k = 1
+        if (!zq[q]) continue;
+        rc = cozk_guard(party_ctxs[q], [&] {
+            const fe *mp[1] = {(const fe*)zq[q]->d}, *rt[1] = {(const fe*)r_t[q]->d};
+            fe* o[1] = {(fe*)out[q]->d};
+            launch_king_finish(party_ctxs[q]->stream, mp, 1, rt, r_offset, 1, o, nullptr, n);  // lagrange(1) = 1
+        });
+        if (rc != COZK_OK) return fail(rc, q);
+    }
+    free_all(zq, num_parties);  // each behind its reader on its owner's stream
+    return COZK_OK;
 }
 
 int cozk_vec_add_scalar(cozk_ctx* ctx, cozk_vec* v, const uint64_t s[4]) {

@@ -369,6 +369,13 @@ class Vec:
         self.ctx.check(self.ctx._l.cozk_shamir_mul_mask(self.ctx.h, self.h, other.h, r_2t.h, ctypes.byref(h)))
         return Vec(self.ctx, h, L.SCALAR_FR)
 
+    def shamir_mul_mask_pairs(self, r_2t, r_offset=0):
+        """self[2 j] * self[2 j + 1] + r_2t[r_offset + j] in one launch (cozk_shamir_mul_mask_pairs): what a party 0..2 * degree
+        sends to the king for one interleaved GKR layer; the half of the pair is addressed by an element offset"""
+        h = ctypes.c_void_p()
+        self.ctx.check(self.ctx._l.cozk_shamir_mul_mask_pairs(self.ctx.h, self.h, r_2t.h, r_offset, ctypes.byref(h)))
+        return Vec(self.ctx, h, L.SCALAR_FR)
+
     def free(self):
         if self.h:
             self.ctx._l.cozk_vec_free(self.h)
@@ -556,6 +563,90 @@ def shamir_mul_king(party_ctxs, a_shares, b_shares, r_t, r_2t, degree, king=0):
     party_ctxs[0].check(party_ctxs[0]._l.cozk_shamir_mul_king_inproc(ctxs, _handles(n, a_shares), _handles(n, b_shares), _handles(n, r_t),
                                                                     _handles(n, r_2t), degree, n, king, out))
     return [Vec(party_ctxs[p], ctypes.c_void_p(out[p]), L.SCALAR_FR) for p in range(n)]
+
+
+def shamir_king_finish(ctx, masked, degree, r_t, r_offset=0, want_z=False):
+    """the king's open and len(r_t) parties' unmask in one launch (cozk_shamir_king_finish): z = the degree-2t opening of the
+    2 * degree + 1 masked vectors, out[q][i] = z[i] - r_t[q][r_offset + i].  Returns the list out, or (out, z) with want_z"""
+    count = len(r_t)
+    out = (ctypes.c_void_p * max(count, 1))()
+    z = ctypes.c_void_p()
+    ctx.check(ctx._l.cozk_shamir_king_finish(ctx.h, _handles(len(masked), masked), degree, _handles(count, r_t), r_offset, count, out,
+                                             ctypes.byref(z) if want_z else None))
+    vecs = [Vec(ctx, ctypes.c_void_p(out[q]), L.SCALAR_FR) for q in range(count)]
+    return (vecs, Vec(ctx, z, L.SCALAR_FR)) if want_z else vecs
+
+
+def shamir_mul_king_pairs(party_ctxs, layers, r_t, r_2t, degree, r_offset=0, king=0):
+    """one tree level of a grand product with a king, all parties in this process (cozk_shamir_mul_king_pairs_inproc): layers[p] =
+    party p's share vector of an interleaved layer (even length 2m); product j consumes element r_offset + j of the pair
+    (r_t[p], r_2t[p]).  layers[p] and r_2t[p] may be None for p > 2 * degree.  No element of a pair may be used twice"""
+    n = len(party_ctxs)
+    ctxs = (ctypes.c_void_p * max(n, 1))(*[c.h for c in party_ctxs])
+    out = (ctypes.c_void_p * max(n, 1))()
+    party_ctxs[0].check(party_ctxs[0]._l.cozk_shamir_mul_king_pairs_inproc(ctxs, _handles(n, layers), _handles(n, r_t), _handles(n, r_2t), r_offset,
+                                                                          degree, n, king, out))
+    return [Vec(party_ctxs[p], ctypes.c_void_p(out[p]), L.SCALAR_FR) for p in range(n)]
+
+
+class ShamirGpPrepResult(ctypes.Structure):
+    """cozk_shamir_gp_prep_result"""
+    _fields_ = [("n_openings", ctypes.c_uint64), ("pair_elems", ctypes.c_uint64), ("pairs_held", ctypes.c_int), ("used", ctypes.c_int),
+                ("t_offline_ms", ctypes.c_double)]
+
+
+class ShamirGpPrep:
+    """the preprocessing of ONE king grand product (cozk_shamir_gp_prep_inproc), made before the leaves exist; .result is a
+    ShamirGpPrepResult.  close() it before its party contexts"""
+
+    def __init__(self, party_ctxs, h, degree):
+        self.party_ctxs, self.h, self.degree = list(party_ctxs), h, degree
+
+    @property
+    def result(self):
+        res = ShamirGpPrepResult()
+        rc = self.party_ctxs[0]._l.cozk_shamir_gp_prep_get_result(self.h, ctypes.byref(res))
+        if rc != L.OK:
+            raise L.CozkError(rc, "shamir_gp_prep accessor")
+        return res
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.party_ctxs[0]._l.cozk_shamir_gp_prep_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def shamir_gp_prep(party_ctxs, rand_keys, n_leaves, batch_size, degree, rand_counter=0):
+    """everything a king grand product of n_leaves interleaved leaves in batch_size circuits needs before the leaves exist
+    (cozk_shamir_gp_prep_inproc): the opening masks and the double-random pairs of the tree.  rand_keys[p] = party p's
+    3 * degree + 1 keys; (rand_keys, rand_counter .. + M + n_leaves / 2) must never be used again.  Returns a ShamirGpPrep"""
+    n = len(party_ctxs)
+    ctxs = (ctypes.c_void_p * max(n, 1))(*[c.h for c in party_ctxs])
+    rb, rk = _key_blocks(n, rand_keys)
+    h = ctypes.c_void_p()
+    party_ctxs[0].check(party_ctxs[0]._l.cozk_shamir_gp_prep_inproc(ctxs, rk, n_leaves, batch_size, degree, n, rand_counter, ctypes.byref(h)))
+    return ShamirGpPrep(party_ctxs, h, degree)
+
+
+def shamir_gp_prove_king(party_ctxs, leaves, batch_size, prep, king=0, label=b"cozk", verify=True):
+    """shamir_gp_prove with the king construct, consuming the ShamirGpPrep `prep` (cozk_shamir_gp_prove_king_inproc): no fresh
+    randomness online.  The proof is the plain prover's, byte for byte; a prep serves one proof.  Returns a ShamirGpProof"""
+    n = len(party_ctxs)
+    l = party_ctxs[0]._l
+    ctxs = (ctypes.c_void_p * max(n, 1))(*[c.h for c in party_ctxs])
+    h = ctypes.c_void_p()
+    party_ctxs[0].check(l.cozk_shamir_gp_prove_king_inproc(ctxs, _handles(n, leaves), batch_size, prep.h, king, bytes(label), 1 if verify else 0,
+                                                           ctypes.byref(h)))
+    try:
+        return ShamirGpProof(l, h, prep.degree)
+    finally:
+        l.cozk_shamir_gp_free(h)
 
 
 def shamir_combine_points(ctx, points_g1, points, degree):

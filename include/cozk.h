@@ -143,7 +143,8 @@ int cozk_vec_add_scalar(cozk_ctx* ctx, cozk_vec* v, const uint64_t s[4]);
  * no Shamir network, degree reduction or prover; the multiplication here is the classic one-round resharing (GRR / BGW),
  * restated in tests/shamir_mul_ref.py, and beside it the king variant with preprocessed double-random pairs
  * (cozk_shamir_rand_*, cozk_shamir_mul_king_*; tests/shamir_dn_ref.py).  The one Shamir prover is the dense batched grand
- * product, cozk_shamir_gp_prove_inproc at the end of this section (tests/shamir_gp_ref.py). */
+ * product at the end of this section: cozk_shamir_gp_prove_inproc (tests/shamir_gp_ref.py) with the resharing construct, and
+ * cozk_shamir_gp_prep_inproc + cozk_shamir_gp_prove_king_inproc (tests/shamir_gp_king_ref.py) with the king's. */
 #define COZK_SHAMIR_MAX_PARTIES 32
 #define COZK_SHAMIR_MAX_DEGREE 15 /* of a dealt sharing: 2t + 1 <= 32 parties can still open a product */
 /* share_field_elements (mpc-types/src/protocols/shamir.rs:58-77; `share` :190-207): out[p][i] = f_i(p + 1) with
@@ -293,6 +294,35 @@ int cozk_shamir_mul_king_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* con
  * also gives the length); a party 0..2 * degree also a, b and r_2t; all must be vectors of ctx.  *out is NULL on failure. */
 int cozk_shamir_mul_king_vec(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, const cozk_vec* r_t, const cozk_vec* r_2t,
                              int degree, int king, cozk_vec** out);
+/* The king multiplication of one interleaved GKR layer (L[j] = v[2j], R[j] = v[2j+1]; a tree level of the king grand product
+ * below), with the halves of the pair addressed by an ELEMENT OFFSET so that one preprocessed pair serves many levels and no
+ * slice is copied.  Element off + j of a pair is used by product j; no element of a pair may be used twice.
+ *
+ * cozk_shamir_mul_mask_pairs: *out[j] = v[2j] v[2j+1] + r_2t[r_offset + j], len(v) / 2 elements in ONE launch (96 B read, 32 B
+ * written per product; the product is never stored).  v is an even-length FR vector, r_2t an FR vector with
+ * r_offset + len(v) / 2 <= len(r_2t).  *out is NULL on failure. */
+int cozk_shamir_mul_mask_pairs(cozk_ctx* ctx, const cozk_vec* v, const cozk_vec* r_2t, size_t r_offset, cozk_vec** out);
+/* the king's open and `count` parties' unmask in ONE launch: z[i] = sum_{p<=2t} lambda_p masked[p][i], lambda =
+ * lagrange(1..2t + 1), t = degree, and out[q][i] = z[i] - r_t[q][r_offset + i] for q < count; z itself is stored only when
+ * z_out is not NULL.  (2t + 1 + count) x 32 B read, count x 32 B written per element, every stored element canonical.
+ * 1 <= degree <= COZK_SHAMIR_MAX_DEGREE (arithmetic only, as for cozk_shamir_combine_vec), 1 <= count <= 32; masked: 2t + 1 FR
+ * vectors of one length n; r_t: count FR vectors with r_offset + n <= their lengths.  As for cozk_shamir_rand_extract the inputs
+ * need not be vectors of ctx (they are read on ctx's stream, and ordering that read is the caller's job); out[0..count) and
+ * *z_out are handles of ctx, NULL on failure (out untouched when count is outside 1..32). */
+int cozk_shamir_king_finish(cozk_ctx* ctx, const cozk_vec* const* masked, int degree, const cozk_vec* const* r_t, size_t r_offset,
+                            int count, cozk_vec** out, cozk_vec** z_out);
+/* one tree level for all parties in this process: out[q][j] = party q's share of v[2j] v[2j+1], a degree-t sharing again.  As
+ * cozk_shamir_mul_king_inproc: every stream drained, cozk_shamir_mul_mask_pairs' kernel on each sender's stream into the king's
+ * blocks (staged and peer-copied from another device), the senders' streams synchronised; then ONE cozk_shamir_king_finish
+ * launch on the king's stream serves every party of the king's device, writing into blocks of the recipients' allocators, and
+ * that stream is synchronised before return.  A party on another device gets z by peer copy and subtracts at the offset on its
+ * own stream.  v[p] (even length, one length) and r_2t[p] are read for p <= 2 * degree only and may be NULL above; r_t[p] for
+ * every p; all halves have one length >= r_offset + len(v) / 2 and are vectors of party_ctxs[p].  1 <= t, 2t <=
+ * COZK_SHAMIR_MAX_DEGREE, 2t + 1 <= n <= 32, 0 <= king < n.  On failure out[0..num_parties) is NULL (untouched when num_parties
+ * is outside 1..32); the error text is left with party_ctxs[0]. */
+int cozk_shamir_mul_king_pairs_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* v, const cozk_vec* const* r_t,
+                                      const cozk_vec* const* r_2t, size_t r_offset, int degree, int num_parties, int king,
+                                      cozk_vec** out);
 
 /* The dense batched grand product (GKR; Rep3BatchedDenseGrandProduct, co-jolt/src/subprotocols/grand_product.rs) proved by n
  * Shamir parties, semi-honest, all driven from the one thread that owns their contexts and plays the coordinator
@@ -345,6 +375,37 @@ size_t cozk_shamir_gp_msgs_len(const cozk_shamir_gp* h);
 int cozk_shamir_gp_msgs(const cozk_shamir_gp* h, uint64_t* out, size_t cap);
 size_t cozk_shamir_gp_finals_len(const cozk_shamir_gp* h);
 int cozk_shamir_gp_finals(const cozk_shamir_gp* h, uint64_t* out, size_t cap);
+
+/* The same proof with the KING construct and everything that needs fresh randomness moved OFFLINE, before the leaves exist.
+ * cozk_shamir_gp_prep_inproc makes the preprocessing object of ONE proof of (n_leaves, batch_size) by (num_parties, degree):
+ *   (A) the opening masks of cozk_shamir_gp_prove_inproc: M elements at rand_counter, pair 0 -- the same zero masks;
+ *   (B) one dealing of n_leaves / 2 elements at rand_counter + M: pair 0 serves tree level 0 whole, pair 1 serves level
+ *       i >= 1 at the element offset n_leaves / 2 - n_leaves / 2^i (the sum of the output lengths of levels 1..i - 1; the last
+ *       level ends at n_leaves / 2 - 2 batch_size).  Only what is used is extracted: no pair for 2 leaves per circuit, one for
+ *       4, two otherwise (fewer than n - t pairs of an exchange are still private), the degree-2t halves for parties 0..2t only.
+ * (rand_keys, rand_counter .. rand_counter + M + n_leaves / 2) must never be used again: the caller's contract.  rand_keys[p] =
+ * (3t + 1) x 32 bytes, every party.  The object holds vectors of party_ctxs: free it before those contexts are destroyed.
+ * cozk_shamir_gp_prove_king_inproc consumes it: construct layer[i+1] = cozk_shamir_mul_king_pairs_inproc(layer[i], ..) at
+ * those offsets; masks, openings, finals (unmasked: c_q = z - rt_q is a fresh uniformly random degree-t sharing), transcript
+ * and proof are those of cozk_shamir_gp_prove_inproc, so THE PROOF IS THE PLAIN PROVER'S, BYTE FOR BYTE, and the handle is the
+ * same cozk_shamir_gp with every getter above; t_construct_ms is the online construct alone (offline time lives in the prep's
+ * result).  party_ctxs, the length of the leaves and batch_size must be those the prep was made for; the prep is marked used
+ * before the first launch and a second proof with it is refused with COZK_ERR_INVALID_ARG.  Everything is refused on the host
+ * before any launch; on failure *prep / *out is NULL and the error text is left with party_ctxs[0]. */
+typedef struct cozk_shamir_gp_prep cozk_shamir_gp_prep;
+typedef struct cozk_shamir_gp_prep_result {
+    uint64_t n_openings; /* M */
+    uint64_t pair_elems; /* elements per construct pair: n_leaves / 2, or 0 where no pair is needed */
+    int pairs_held;      /* construct pairs still held: 0, 1 or 2; 0 once a proof has consumed them */
+    int used;            /* 1 once a proof has started with it */
+    double t_offline_ms; /* host clock around both dealings, every party's stream drained at both ends */
+} cozk_shamir_gp_prep_result;
+int cozk_shamir_gp_prep_inproc(cozk_ctx* const* party_ctxs, const uint8_t* const* rand_keys, size_t n_leaves, size_t batch_size,
+                               int degree, int num_parties, uint64_t rand_counter, cozk_shamir_gp_prep** prep);
+int cozk_shamir_gp_prep_free(cozk_shamir_gp_prep* prep);
+int cozk_shamir_gp_prep_get_result(const cozk_shamir_gp_prep* prep, cozk_shamir_gp_prep_result* res);
+int cozk_shamir_gp_prove_king_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* leaves, size_t batch_size,
+                                     cozk_shamir_gp_prep* prep, int king, const char* label, int verify, cozk_shamir_gp** out);
 
 /* ---------------------------------------------------------------- MSM seam ---------------- */
 /* Upload SRS points (`ck.powers_of_g[i]`, co-jolt/src/poly/commitment/pst13.rs:286-287,461-462) once;

@@ -27,7 +27,18 @@ With --gp, instead, the Shamir grand product prover over 2^log_n interleaved lea
   (xiii) the whole cozk_shamir_gp_prove_inproc (construct + masks + rounds), timed the same way, with the driver's own split, and as
          context the PLAIN single-party grand product of the same opened leaves in the same run (this script drives its rounds
          through cozk_layer_round and hashes the transcript itself: its proof must equal the Shamir parties' byte for byte).
-  python tools/run_shamir.py --gp --log-n 22 --parties 8 --degree 2 [--out FILE]"""
+  python tools/run_shamir.py --gp --log-n 22 --parties 8 --degree 2 [--out FILE]
+With --gp --king, instead, the king construct of that prover and its offline preprocessing, the legs of a pair alternating:
+  (xiv)   the mask of a tree level cozk_shamir_mul_mask_pairs on the leaf layer against cozk_layer_output_local (PLAIN, unmasked) +
+          cozk_vec_binop(ADD), outputs compared raw;
+  (xv)    the king's open and every party's unmask cozk_shamir_king_finish (2 * degree + 1 masked vectors, parties outputs) against
+          cozk_shamir_combine_vec + parties x cozk_vec_binop(SUB), outputs compared raw;
+  (xvi)   the whole king construct, cozk_shamir_mul_king_pairs_inproc level by level on preprocessed pairs, against the whole resharing
+          construct of (xii), timed as (vii) is; both top layers open to the same values;
+  (xvii)  the preprocessing cozk_shamir_gp_prep_inproc, reported on its own: offline time is never netted against online time;
+  (xviii) the whole cozk_shamir_gp_prove_king_inproc (a fresh preprocessing per repetition, made outside the timed call) against the
+          whole cozk_shamir_gp_prove_inproc; the proofs are equal byte for byte.
+  python tools/run_shamir.py --gp --king --log-n 22 --parties 8 --degree 2 [--out FILE]"""
 import argparse, ctypes, hashlib, importlib, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -40,7 +51,7 @@ ap.add_argument("--degree", type=int, default=2)
 ap.add_argument("--out", default=None)
 ap.add_argument("--min-seconds", type=float, default=1.0)
 ap.add_argument("--mul", action="store_true", help="time the multiplication with degree reduction instead")
-ap.add_argument("--king", action="store_true", help="with --mul: time the king / double-random variant against the resharing")
+ap.add_argument("--king", action="store_true", help="with --mul: time the king / double-random variant against the resharing; with --gp: the king construct")
 ap.add_argument("--gp", action="store_true", help="time the Shamir grand product prover instead")
 ap.add_argument("--gp-batch", type=int, default=2, help="with --gp: circuits in the grand product")
 args = ap.parse_args()
@@ -513,6 +524,197 @@ def gp_legs():
                   "included; the Shamir and the PLAIN prover alternating; keys and counters reused across repetitions (timing only)",
     })
 
+
+def party_contexts():
+    """one context per party on this GPU, and their streams"""
+    pcs = [cozk.Context(0) for _ in range(N)]
+    streams = []
+    for pc in pcs:
+        h = ctypes.c_void_p()
+        pc.check(pc._l.cozk_ctx_stream(pc.h, ctypes.byref(h)))
+        streams.append(torch.cuda.ExternalStream(h.value))
+    return pcs, streams
+
+
+def whole_call(pcs, streams, fn):
+    """fn() from an event on party 0's idle stream to the last of the events behind the parties' streams"""
+    for pc in pcs:
+        pc.synchronize()
+    e0 = torch.cuda.Event(enable_timing=True)
+    e0.record(streams[0])  # every stream is idle: the calls start by draining them
+    out = fn()
+    ends = []
+    for st in streams:
+        e = torch.cuda.Event(enable_timing=True)
+        e.record(st)
+        ends.append(e)
+    for e in ends:
+        e.synchronize()
+    return max(e0.elapsed_time(e) for e in ends), out
+
+
+def gp_king_legs():
+    if 2 * T + 1 > N or 2 * T > 15:
+        raise SystemExit("run_shamir --gp --king: needs 2 * degree + 1 <= parties and 2 * degree <= 15")
+    P = importlib.import_module("co-zkvms_amd.poly")
+    batch, m, D = args.gp_batch, n // 2, 2 * T + 1
+    levels = (n // batch).bit_length() - 2  # multiplications: log2(leaves per circuit) - 1
+    if levels < 2:
+        raise SystemExit("run_shamir --gp --king: needs at least 8 leaves per circuit (two tree levels)")
+    spread = lambda ts: round(sorted(ts)[-1] - sorted(ts)[0], 4)
+    raw_equal = lambda xs, ys: all(np.array_equal(x.to_numpy(), y.to_numpy()) for x, y in zip(xs, ys))
+
+    def pair_of_legs(fused, composed, what):
+        """both legs alternating on the context's stream; their outputs compared raw in the warm-up"""
+        f, c = fused(), composed()
+        equal = raw_equal(f, c)
+        free(f), free(c)
+        assert equal, what
+        for _ in range(2):
+            free(timed(fused)[1]), free(timed(composed)[1])
+        t_f, t_c = [], []
+        while sum(t_f) < args.min_seconds * 1e3 or sum(t_c) < args.min_seconds * 1e3 or len(t_f) < 5:
+            ms, r = timed(fused); t_f.append(ms); free(r)
+            ms, r = timed(composed); t_c.append(ms); free(r)
+        return t_f, t_c, equal
+
+    def verdict(t_f, t_c):
+        return {"fused_vs_composed_speedup": round(med(t_c) / med(t_f), 3), "fused_slower_than_composed_by_ms": round(med(t_f) - med(t_c), 4),
+                "composed_min_max_spread_ms": spread(t_c), "fused_not_slower_beyond_composed_spread": bool(med(t_f) - med(t_c) <= spread(t_c))}
+
+    # (xiv): the leaf layer, 2^log_n elements -> 2^(log_n - 1) masked products
+    layer = P.Rep3DenseInterleavedPolynomial.from_vecs(ctx, A)
+    mask = cozk.Vec.random(ctx, m + 3, seed=2028)
+    mask_cut = cozk.Vec.from_numpy(ctx, mask.to_numpy()[3:])
+
+    def composed_mask():
+        prod = layer.layer_output_local()
+        out = prod.binop(cozk.OP_ADD, mask_cut)
+        prod.free()
+        return [out]
+
+    t_mf, t_mc, mask_equal = pair_of_legs(lambda: [A.shamir_mul_mask_pairs(mask, 3)], composed_mask,
+                                          "the mask of a layer and layer_output_local + binop(ADD) differ")
+    layer.free(), free([mask, mask_cut])
+
+    # (xv): 2t + 1 masked vectors of 2^(log_n - 1) elements -> parties outputs
+    masked = [cozk.Vec.random(ctx, m, seed=3100 + j) for j in range(D)]
+    rts = [cozk.Vec.random(ctx, m, seed=3200 + q) for q in range(N)]
+    pts = list(range(1, D + 1))
+
+    def composed_finish():
+        z = cozk.shamir_combine(masked, pts, 2 * T)
+        out = [z.binop(cozk.OP_SUB, r) for r in rts]
+        z.free()
+        return out
+
+    t_ff, t_fc, finish_equal = pair_of_legs(lambda: cozk.shamir_king_finish(ctx, masked, T, rts), composed_finish,
+                                            "the king finish and combine + binop(SUB) differ")
+    free(masked), free(rts)
+
+    # (xvi) .. (xviii): one context per party on this GPU
+    pcs, streams = party_contexts()
+    whole = lambda fn: whole_call(pcs, streams, fn)
+    leaves = A.shamir_scatter(keys_a, T, pcs, counter=0)
+    mul_keys = [[key(1000 + 16 * p + c) for c in range(T)] for p in range(N)]
+    rand_keys = [[key(2000 + 32 * p + c) for c in range(3 * T + 1)] for p in range(N)]
+    pairs = cozk.shamir_rand(pcs, rand_keys, m, T, counter=1 << 40)  # reused across repetitions: timing only
+    flat = lambda ps: [h for p in ps for xy in p for h in xy]
+
+    def construct_grr():
+        cur, ctr = leaves, 0
+        for _ in range(levels):
+            nxt = cozk.shamir_mul_pairs(pcs, cur, mul_keys, T, counter=ctr)
+            ctr += len(nxt[0])
+            if cur is not leaves:
+                free(cur)
+            cur = nxt
+        return cur
+
+    def construct_king():
+        cur = leaves
+        for i in range(levels):
+            k, off = (1, m - (n >> i)) if i else (0, 0)
+            nxt = cozk.shamir_mul_king_pairs(pcs, cur, [p[k][0] for p in pairs], [p[k][1] for p in pairs], T, r_offset=off, king=0)
+            if cur is not leaves:
+                free(cur)
+            cur = nxt
+        return cur
+
+    high = list(range(N, N - T - 1, -1))
+    tops = []
+    for fn in (construct_grr, construct_king):  # warm-up and correctness: both top layers open to the same values
+        ms, top = whole(fn)
+        for pc in pcs:
+            pc.synchronize()
+        tops.append(cozk.shamir_combine([top[p - 1] for p in high], high, T))
+        free(top)
+    tops_equal = raw_equal(tops[:1], tops[1:])
+    free(tops)
+    assert tops_equal, "the king construct and the resharing construct open to different top layers"
+    t_cg, t_ck = [], []
+    while sum(t_cg) < args.min_seconds * 1e3 or sum(t_ck) < args.min_seconds * 1e3 or len(t_cg) < 5:  # alternating
+        ms, top = whole(construct_grr); t_cg.append(ms); free(top)
+        ms, top = whole(construct_king); t_ck.append(ms); free(top)
+    free(flat(pairs))
+
+    prove_grr = lambda: cozk.shamir_gp_prove(pcs, leaves, batch, mul_keys, rand_keys, T, mul_counter=0, rand_counter=0)  # keys reused: timing only
+    make_prep = lambda: cozk.shamir_gp_prep(pcs, rand_keys, n, batch, T, rand_counter=0)
+    t_prep, t_off, t_pg, t_pk, t_kc, t_kp, t_gc, t_gp = [], [], [], [], [], [], [], []
+    proofs_equal, first = True, True
+    while first or sum(t_pg) < args.min_seconds * 1e3 or sum(t_pk) < args.min_seconds * 1e3 or len(t_pg) < 6:
+        ms_prep, prep = whole(make_prep)
+        off_ms, held = prep.result.t_offline_ms, prep.result.pairs_held
+        ms_k, gk = whole(lambda: cozk.shamir_gp_prove_king(pcs, leaves, batch, prep, king=0))
+        prep.close()
+        ms_g, gg = whole(prove_grr)
+        assert gk.result.verified == 1 and gg.result.verified == 1, "a Shamir grand product proof was rejected"
+        proofs_equal = proofs_equal and gk.proof_bytes == gg.proof_bytes
+        assert proofs_equal, "the king prover's proof differs from the resharing prover's"
+        if first:  # warm-up
+            first = False
+            continue
+        t_prep.append(ms_prep); t_off.append(off_ms); t_pk.append(ms_k); t_pg.append(ms_g)
+        t_kc.append(gk.result.t_construct_ms); t_kp.append(gk.result.t_prove_ms); t_gc.append(gg.result.t_construct_ms); t_gp.append(gg.result.t_prove_ms)
+    free(leaves)
+    for pc in pcs:
+        pc.close()
+
+    M = int(gk.result.n_opened)
+    emit({
+        "what": "Shamir grand product, king construct: mask kernel vs layer_output_local + binop(ADD), finish kernel vs combine + subtractions, whole "
+                "king construct vs whole resharing construct, the preprocessing on its own, whole prove both ways",
+        "log_n": args.log_n, "interleaved_leaves": n, "batch": batch, "layers": levels + 1, "parties": N, "degree": T, "senders": D, "king": 0,
+        "openings_of_degree_2t": M, "proof_len": int(gk.result.proof_len), "device": torch.cuda.get_device_name(0),
+        "mask_pairs": dict(stats(t_mf), products=m, algorithmic_bytes=128 * m, bytes_per_s=round(128 * m / (med(t_mf) * 1e-3), 1), launches=1),
+        "composed_output_local_then_add": dict(stats(t_mc), bytes_moved_by_the_composition=(96 + 96) * m, launches=2),
+        "mask_verdict": verdict(t_mf, t_mc), "mask_outputs_equal": bool(mask_equal),
+        "king_finish": dict(stats(t_ff), elements=m, algorithmic_bytes=(D + 2 * N) * 32 * m, bytes_per_s=round((D + 2 * N) * 32 * m / (med(t_ff) * 1e-3), 1), launches=1),
+        "composed_combine_then_subtract": dict(stats(t_fc), bytes_moved_by_the_composition=((D + 1) * 32 + N * 96) * m, launches=1 + N),
+        "finish_verdict": verdict(t_ff, t_fc), "finish_outputs_equal": bool(finish_equal),
+        "inproc_construct_king": dict(stats(t_ck), levels=levels, launches=levels * (D + 1), contexts=N),
+        "inproc_construct_resharing_same_run": dict(stats(t_cg), levels=levels, launches=levels * (D + N), contexts=N),
+        "king_vs_resharing_construct_time_ratio": round(med(t_ck) / med(t_cg), 3),
+        "king_construct_not_slower_than_resharing": bool(med(t_ck) <= med(t_cg)),
+        "constructs_open_to_equal_top_layers": bool(tops_equal),
+        "offline_prep": dict(stats(t_prep), driver_host_clock=stats(t_off), mask_elements=M, pair_elements=m, pairs_extracted=int(held), contexts=N,
+                             note="reported on its own: never netted against an online figure"),
+        "inproc_prove_king_whole_call": dict(stats(t_pk), driver_split={"construct": stats(t_kc), "openings_rounds": stats(t_kp)}),
+        "inproc_prove_resharing_whole_call_same_run": dict(stats(t_pg), driver_split={"construct": stats(t_gc), "masks_openings_rounds": stats(t_gp)}),
+        "king_vs_resharing_prove_time_ratio": round(med(t_pk) / med(t_pg), 3),
+        "proofs_equal": bool(proofs_equal),
+        "timing": "device events around each repetition for (xiv) and (xv), legs alternating on one stream (allocation from the context's pool "
+                  "included); the in-process legs from an event on party 0's idle stream before the call to the last of the events behind the "
+                  "parties' streams, host-side synchronisations included, the legs of a pair alternating; the construct legs reuse two "
+                  "preprocessed pairs and the provers their keys and counters across repetitions (timing only: a pair must never be used twice); "
+                  "peer-copy legs (parties on other GPUs) are not exercised by a one-GPU run",
+    })
+
+
+if args.gp and args.king:
+    gp_king_legs()
+    ctx.close()
+    raise SystemExit(0)
 
 if args.gp:
     gp_legs()
