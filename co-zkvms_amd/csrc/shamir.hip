@@ -397,94 +397,222 @@ static ShamirOut out_table(cozk_vec* const* out, int num_parties) {
     return o;
 }
 
+// ------------------------------------------------------------------ the skeleton of an entry point of ONE context
+// An output table of such an entry point: `len` handles from ctx's pool (from owners[p]'s where the parties own them:
+// cozk_shamir_scatter); an optional table may be absent (the z of cozk_shamir_king_finish).
+struct OutTable {
+    cozk_vec** v;
+    int len;
+    bool optional = false;
+    cozk_ctx* const* owners = nullptr;
+};
+
+// Every table that is there is cleared (where its length is a count at all: slots of an unknown number stay untouched) and a
+// missing one is refused with `null_out`; check() throws on a bad argument and returns the element count n of every output; the
+// tables are allocated; launch(n) enqueues on ctx's stream, unless n = 0.  Whatever fails, no table is left holding a handle.
+template <class Check, class Launch>
+static int entry_point(cozk_ctx* ctx, const char* null_out, std::initializer_list<OutTable> tables, Check check, Launch launch) {
+    bool missing = false;
+    for (const OutTable& t : tables) {
+        if (t.v) clear_outputs(t.v, t.len);
+        else missing |= !t.optional;
+    }
+    size_t n = 0;
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(!missing, null_out);
+        n = check();
+    });
+    if (rc != COZK_OK) return rc;
+    auto drop = [&] {
+        for (const OutTable& t : tables)
+            if (t.v) free_all(t.v, t.len);
+    };
+    for (const OutTable& t : tables)
+        if (t.v && (rc = alloc_outputs(ctx, t.owners, n, t.len, t.v)) != COZK_OK) {
+            drop();
+            return rc;
+        }
+    rc = cozk_guard(ctx, [&] {
+        if (n) launch(n);
+    });
+    if (rc != COZK_OK) drop();
+    return rc;
+}
+
+// ------------------------------------------------------------------ one party's vector among the arguments of an in-process call
+// there, FR, (of an even length,) of n elements, a block of that party's context -- in this order.  The texts are the entry
+// point's own, behind its name
+struct OwnVecTexts {
+    std::string null, kind, even /* empty: either parity */, len, own;
+};
+static void require_own_vec(const char* who, const cozk_vec* v, const cozk_ctx* ctx, size_t n, const OwnVecTexts& t) {
+    const std::string w = std::string(who) + ": ";
+    COZK_REQUIRE(v, w + t.null);
+    COZK_REQUIRE(v->kind == COZK_SCALAR_FR, w + t.kind);
+    COZK_REQUIRE(t.even.empty() || v->n % 2 == 0, w + t.even);
+    COZK_REQUIRE(v->n == n, w + t.len);
+    COZK_REQUIRE(v->ctx == ctx, w + t.own);
+}
+// a factor or a half of the pair of the king multiplication
+static void require_own_vec(const char* who, const cozk_vec* v, const cozk_ctx* ctx, size_t n, const char* what) {
+    const std::string s(what);
+    require_own_vec(who, v, ctx, n, {"null " + s, s + " must be an FR vector", "", "the factors and the pair must have one length", s + " must be a vector of its party's context"});
+}
+// party p's interleaved GKR layer (require_pairs' texts)
+static const OwnVecTexts LAYER_TEXTS = {"parties 0..2 * degree need their layer", "the layer must be an FR vector",
+                                        "the layer must have an even length (L[j] = v[2 j], R[j] = v[2 j + 1])", "the layers must have one length",
+                                        "party p's layer must be a vector of party_ctxs[p]"};
+
+// ------------------------------------------------------------------ the in-process drivers: one thread, one context per party
+// Who may touch a block, and when.  A context's pool orders its blocks by that context's stream only (common.hpp): a block a
+// party has just freed may still be read by a kernel in flight on that party's stream, and a block handed out is assumed to be
+// used on that stream.  The drivers below let one context's stream write into another context's block, so they keep three rules:
+//   1. before any stream writes into a block of another context, the OWNER's stream has drained (every driver drains every
+//      party's stream once, after it has allocated and before the first launch);
+//   2. the owner's stream reads such a block only after the WRITER's stream has drained (the drain step after the launches,
+//      which also gives the writers' staging blocks back);
+//   3. a block returns to its pool only behind its last reader on the owner's stream, or after a drain.
+//
+// The staged fan-out: dealer's stream writes one vector of n elements for each of `count` recipients -- launch(table) is the
+// caller's dealing kernel -- into dst[q] in place where recipient q lives on the dealer's device, else into a slice of ONE
+// staging block of the dealer's followed by one peer copy.  The caller has seen to rule 1, drains the dealer's stream before
+// anybody reads (rule 2) and then frees *stage, also where this throws.
+template <class Launch>
+static void fan_out(cozk_ctx* dealer, cozk_ctx* const* rcp, fe* const* dst, int count, size_t n, fe** stage, Launch launch) {
+    size_t remote = 0;
+    for (int q = 0; q < count; q++) remote += rcp[q]->device != dealer->device;
+    if (remote) *stage = (fe*)ctx_dev_alloc(dealer, remote * n * sizeof(fe));
+    ShamirOut o;
+    memset(&o, 0, sizeof o);
+    size_t r = 0;
+    for (int q = 0; q < count; q++) o.p[q] = rcp[q]->device != dealer->device ? *stage + n * r++ : dst[q];
+    launch(o);
+    for (int q = 0; q < count; q++)
+        if (rcp[q]->device != dealer->device)
+            HIP_TRY(hipMemcpyPeerAsync(dst[q], rcp[q]->device, o.p[q], dealer->device, n * sizeof(fe), dealer->stream));
+}
+
+static int drain_all(cozk_ctx* const* pcs, int parties) {
+    return cozk_guard(pcs[0], [&] {
+        for (int q = 0; q < parties; q++) HIP_TRY(hipStreamSynchronize(pcs[q]->stream));
+    });
+}
+
+// the writers' streams drain (rule 2) and their staging blocks go back
+static int drain_writers(cozk_ctx* const* pcs, int writers, fe** stage, int* failed) {
+    for (int p = 0; p < writers; p++) {
+        int rc = cozk_guard(pcs[p], [&] {
+            HIP_TRY(hipStreamSynchronize(pcs[p]->stream));
+            ctx_dev_free(pcs[p], stage[p]);
+            stage[p] = nullptr;
+        });
+        if (rc != COZK_OK) {
+            *failed = p;
+            return rc;
+        }
+    }
+    return COZK_OK;
+}
+
+// The all-to-all deal: parties 0..dealers - 1 each deal n elements with `degree` coefficients to parties 0..rcp - 1 (one launch of
+// the dealing kernel with the source src_of(p) and one fan_out per dealer), then finish(q, row) enqueues recipient q's step on
+// its own stream -- row[p] = what dealer p dealt to q, a block of q -- and produces q's outputs; q's pool takes the row back
+// behind it (rule 3).  A failure of party p's step leaves its text with party 0 and nothing of the driver's own allocated; what
+// finish has produced by then is the caller's to free.
+template <class SrcOf, class Finish>
+static int deal_all_to_all(cozk_ctx* const* pcs, size_t n, int dealers, int rcp, int degree, SrcOf src_of, Finish finish) {
+    cozk_ctx* const c0 = pcs[0];
+    const int parties = dealers > rcp ? dealers : rcp;
+    int rc = COZK_OK;
+    std::vector<cozk_vec*> recv((size_t)rcp * dealers, nullptr);  // recv[q * dealers + p]
+    std::vector<fe*> stage(dealers, nullptr);
+    auto fail = [&](int code, int p) {
+        if (pcs[p] != c0) c0->last_error = pcs[p]->last_error;
+        for (int q = 0; q < parties; q++) (void)hipStreamSynchronize(pcs[q]->stream);
+        for (int d = 0; d < dealers; d++) ctx_dev_free(pcs[d], stage[d]);
+        for (cozk_vec* v : recv) cozk_vec_free(v);
+        return code;
+    };
+    for (int q = 0; q < rcp; q++)
+        for (int p = 0; p < dealers; p++)
+            if ((rc = cozk_vec_alloc(pcs[q], n, COZK_SCALAR_FR, &recv[(size_t)q * dealers + p])) != COZK_OK) return fail(rc, q);
+    if (n) {
+        if ((rc = drain_all(pcs, parties)) != COZK_OK) return fail(rc, 0);
+        for (int p = 0; p < dealers; p++) {
+            rc = cozk_guard(pcs[p], [&] {
+                fe* dst[COZK_SHAMIR_MAX_PARTIES];
+                for (int q = 0; q < rcp; q++) dst[q] = (fe*)recv[(size_t)q * dealers + p]->d;
+                fan_out(pcs[p], pcs, dst, rcp, n, &stage[p], [&](const ShamirOut& o) { launch_share(pcs[p]->stream, src_of(p), o, n, degree, rcp); });
+            });
+            if (rc != COZK_OK) return fail(rc, p);
+        }
+        int failed = 0;
+        if ((rc = drain_writers(pcs, dealers, stage.data(), &failed)) != COZK_OK) return fail(rc, failed);
+    }
+    for (int q = 0; q < rcp; q++) {
+        cozk_vec** row = &recv[(size_t)q * dealers];
+        if ((rc = finish(q, row)) != COZK_OK) return fail(rc, q);
+        free_all(row, dealers);
+    }
+    return COZK_OK;
+}
+
 extern "C" {
 
 int cozk_shamir_share_vec(cozk_ctx* ctx, const cozk_vec* v, const uint8_t* keys, int degree, int num_parties, uint64_t counter,
                           cozk_vec** out) {
-    if (int rc0 = require_out(ctx, out, "shamir_share_vec: null output")) return rc0;
-    clear_outputs(out, num_parties);
-    int rc = cozk_guard(ctx, [&] {
-        COZK_REQUIRE(ctx && v && keys, "shamir_share_vec: null argument");
-        COZK_REQUIRE(v->kind == COZK_SCALAR_FR, "shamir_share_vec: the secret must be an FR vector");
-        require_share_args("shamir_share_vec", degree, num_parties);
-    });
-    if (rc != COZK_OK) return rc;
-    rc = alloc_outputs(ctx, nullptr, v->n, num_parties, out);
-    if (rc != COZK_OK) return rc;
-    rc = cozk_guard(ctx, [&] {
-        if (v->n == 0) return;
-        launch_share(ctx->stream, prf_src(v, keys, degree, counter), out_table(out, num_parties), v->n, degree, num_parties);
-    });
-    if (rc != COZK_OK) free_all(out, num_parties);
-    return rc;
+    return entry_point(
+        ctx, "shamir_share_vec: null output", {{out, num_parties}},
+        [&] {
+            COZK_REQUIRE(ctx && v && keys, "shamir_share_vec: null argument");
+            COZK_REQUIRE(v->kind == COZK_SCALAR_FR, "shamir_share_vec: the secret must be an FR vector");
+            require_share_args("shamir_share_vec", degree, num_parties);
+            return v->n;
+        },
+        [&](size_t n) { launch_share(ctx->stream, prf_src(v, keys, degree, counter), out_table(out, num_parties), n, degree, num_parties); });
 }
 
 int cozk_shamir_eval_vec(cozk_ctx* ctx, const cozk_vec* const* coeffs, int degree, int num_parties, cozk_vec** out) {
-    if (int rc0 = require_out(ctx, out, "shamir_eval_vec: null output")) return rc0;
-    clear_outputs(out, num_parties);
-    int rc = cozk_guard(ctx, [&] {
-        COZK_REQUIRE(ctx && coeffs, "shamir_eval_vec: null argument");
-        require_share_args("shamir_eval_vec", degree, num_parties);
-        for (int c = 0; c <= degree; c++) {
-            COZK_REQUIRE(coeffs[c] && coeffs[c]->kind == COZK_SCALAR_FR, "shamir_eval_vec: degree + 1 FR coefficient vectors");
-            COZK_REQUIRE(coeffs[c]->n == coeffs[0]->n, "shamir_eval_vec: coefficient vectors must have equal length");
-        }
-    });
-    if (rc != COZK_OK) return rc;
-    const size_t n = coeffs[0]->n;
-    rc = alloc_outputs(ctx, nullptr, n, num_parties, out);
-    if (rc != COZK_OK) return rc;
-    rc = cozk_guard(ctx, [&] {
-        if (n == 0) return;
-        ShamirVecSrc src;
-        memset(&src, 0, sizeof src);
-        src.v = (const fe*)coeffs[0]->d;
-        for (int c = 1; c <= degree; c++) src.c[c - 1] = (const fe*)coeffs[c]->d;
-        launch_share(ctx->stream, src, out_table(out, num_parties), n, degree, num_parties);
-    });
-    if (rc != COZK_OK) free_all(out, num_parties);
-    return rc;
+    return entry_point(
+        ctx, "shamir_eval_vec: null output", {{out, num_parties}},
+        [&] {
+            COZK_REQUIRE(ctx && coeffs, "shamir_eval_vec: null argument");
+            require_share_args("shamir_eval_vec", degree, num_parties);
+            for (int c = 0; c <= degree; c++) {
+                COZK_REQUIRE(coeffs[c] && coeffs[c]->kind == COZK_SCALAR_FR, "shamir_eval_vec: degree + 1 FR coefficient vectors");
+                COZK_REQUIRE(coeffs[c]->n == coeffs[0]->n, "shamir_eval_vec: coefficient vectors must have equal length");
+            }
+            return coeffs[0]->n;
+        },
+        [&](size_t n) {
+            ShamirVecSrc src;
+            memset(&src, 0, sizeof src);
+            src.v = (const fe*)coeffs[0]->d;
+            for (int c = 1; c <= degree; c++) src.c[c - 1] = (const fe*)coeffs[c]->d;
+            launch_share(ctx->stream, src, out_table(out, num_parties), n, degree, num_parties);
+        });
 }
 
-// cozk_rep3_scatter for Shamir: party p's vector is a block of party_ctxs[p]'s allocator, written by the dealer's stream --
-// in place when the devices match, staged on the dealer and moved with one peer copy per party when they differ
+// cozk_rep3_scatter for Shamir: party p's vector is a block of party_ctxs[p]'s allocator, written by the dealer's stream (fan_out)
 int cozk_shamir_scatter(cozk_ctx* dealer, const cozk_vec* v, const uint8_t* keys, int degree, int num_parties, uint64_t counter,
                         cozk_ctx* const* party_ctxs, cozk_vec** out) {
-    if (int rc0 = require_out(dealer, out, "shamir_scatter: null output")) return rc0;
-    clear_outputs(out, num_parties);
-    int rc = cozk_guard(dealer, [&] {
-        COZK_REQUIRE(dealer && v && keys && party_ctxs, "shamir_scatter: null argument");
-        COZK_REQUIRE(v->kind == COZK_SCALAR_FR, "shamir_scatter: the secret must be an FR vector");
-        require_share_args("shamir_scatter", degree, num_parties);
-        for (int p = 0; p < num_parties; p++) COZK_REQUIRE(party_ctxs[p], "shamir_scatter: null party context");
-    });
-    if (rc != COZK_OK) return rc;
-    rc = alloc_outputs(nullptr, party_ctxs, v->n, num_parties, out);
-    if (rc != COZK_OK) return rc;
-    rc = cozk_guard(dealer, [&] {
-        const size_t n = v->n;
-        if (n == 0) return;
-        // the outputs come from the PARTIES' pools, whose blocks are ordered by the owning party's stream only (common.hpp):
-        // a block a party has just freed may still be read by a kernel in flight there, so the dealer's stream must not
-        // write it before that stream has drained
-        size_t remote = 0;
-        for (int p = 0; p < num_parties; p++) {
-            HIP_TRY(hipStreamSynchronize(party_ctxs[p]->stream));
-            remote += party_ctxs[p]->device != dealer->device;
-        }
-        fe* stage = remote ? (fe*)ctx_dev_alloc(dealer, remote * n * sizeof(fe)) : nullptr;
-        ShamirOut o = out_table(out, num_parties);
-        size_t r = 0;
-        for (int p = 0; p < num_parties; p++)
-            if (party_ctxs[p]->device != dealer->device) o.p[p] = stage + n * r++;
-        launch_share(dealer->stream, prf_src(v, keys, degree, counter), o, n, degree, num_parties);
-        for (int p = 0; p < num_parties; p++)
-            if (party_ctxs[p]->device != dealer->device)
-                HIP_TRY(hipMemcpyPeerAsync(out[p]->d, party_ctxs[p]->device, o.p[p], dealer->device, n * sizeof(fe), dealer->stream));
-        HIP_TRY(hipStreamSynchronize(dealer->stream));  // the parties' streams may use the shares as soon as this returns
-        if (stage) ctx_dev_free(dealer, stage);
-    });
-    if (rc != COZK_OK) free_all(out, num_parties);
+    fe* stage = nullptr;
+    int rc = entry_point(
+        dealer, "shamir_scatter: null output", {{out, num_parties, false, party_ctxs}},
+        [&] {
+            COZK_REQUIRE(dealer && v && keys && party_ctxs, "shamir_scatter: null argument");
+            COZK_REQUIRE(v->kind == COZK_SCALAR_FR, "shamir_scatter: the secret must be an FR vector");
+            require_share_args("shamir_scatter", degree, num_parties);
+            for (int p = 0; p < num_parties; p++) COZK_REQUIRE(party_ctxs[p], "shamir_scatter: null party context");
+            return v->n;
+        },
+        [&](size_t n) {
+            for (int p = 0; p < num_parties; p++) HIP_TRY(hipStreamSynchronize(party_ctxs[p]->stream));  // rule 1
+            fan_out(dealer, party_ctxs, out_table(out, num_parties).p, num_parties, n, &stage,
+                    [&](const ShamirOut& o) { launch_share(dealer->stream, prf_src(v, keys, degree, counter), o, n, degree, num_parties); });
+            HIP_TRY(hipStreamSynchronize(dealer->stream));  // rule 2: the parties' streams may use the shares as soon as this returns
+        });
+    ctx_dev_free(dealer, stage);
     return rc;
 }
 
@@ -500,35 +628,26 @@ int cozk_shamir_lagrange(const uint32_t* points, size_t k, uint64_t* out) {
 
 int cozk_shamir_combine_vec(cozk_ctx* ctx, const cozk_vec* const* shares, const uint32_t* points, size_t k, int degree,
                             cozk_vec** out) {
-    if (int rc0 = require_out(ctx, out, "shamir_combine_vec: null output")) return rc0;
-    *out = nullptr;
-    int rc = cozk_guard(ctx, [&] {
-        COZK_REQUIRE(ctx && shares, "shamir_combine_vec: null argument");
-        require_points(points, k, "shamir_combine_vec");
-        COZK_REQUIRE(degree >= 0 && (size_t)degree < k, "shamir_combine_vec: 0 <= degree < k (degree + 1 shares are needed)");
-        for (size_t j = 0; j < k; j++) {
-            COZK_REQUIRE(shares[j] && shares[j]->kind == COZK_SCALAR_FR, "shamir_combine_vec: k FR share vectors");
-            COZK_REQUIRE(shares[j]->n == shares[0]->n, "shamir_combine_vec: share vectors must have equal length");
-        }
-    });
-    if (rc != COZK_OK) return rc;
-    const size_t n = shares[0]->n;
-    rc = cozk_vec_alloc(ctx, n, COZK_SCALAR_FR, out);
-    if (rc != COZK_OK) return rc;
-    rc = cozk_guard(ctx, [&] {
-        if (n == 0) return;
-        ShamirCombineArgs a;
-        memset(&a, 0, sizeof a);
-        lagrange_host(points, (size_t)degree + 1, a.lambda);  // of points[..=degree]: only those shares are used
-        for (int j = 0; j <= degree; j++) a.s[j] = (const fe*)shares[j]->d;
-        k_shamir_combine<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(a, degree + 1, (fe*)(*out)->d, n);
-        HIP_TRY(hipGetLastError());
-    });
-    if (rc != COZK_OK) {
-        cozk_vec_free(*out);
-        *out = nullptr;
-    }
-    return rc;
+    return entry_point(
+        ctx, "shamir_combine_vec: null output", {{out, 1}},
+        [&] {
+            COZK_REQUIRE(ctx && shares, "shamir_combine_vec: null argument");
+            require_points(points, k, "shamir_combine_vec");
+            COZK_REQUIRE(degree >= 0 && (size_t)degree < k, "shamir_combine_vec: 0 <= degree < k (degree + 1 shares are needed)");
+            for (size_t j = 0; j < k; j++) {
+                COZK_REQUIRE(shares[j] && shares[j]->kind == COZK_SCALAR_FR, "shamir_combine_vec: k FR share vectors");
+                COZK_REQUIRE(shares[j]->n == shares[0]->n, "shamir_combine_vec: share vectors must have equal length");
+            }
+            return shares[0]->n;
+        },
+        [&](size_t n) {
+            ShamirCombineArgs a;
+            memset(&a, 0, sizeof a);
+            lagrange_host(points, (size_t)degree + 1, a.lambda);  // of points[..=degree]: only those shares are used
+            for (int j = 0; j <= degree; j++) a.s[j] = (const fe*)shares[j]->d;
+            k_shamir_combine<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(a, degree + 1, (fe*)(*out)->d, n);
+            HIP_TRY(hipGetLastError());
+        });
 }
 
 int cozk_shamir_combine_points(cozk_ctx* ctx, const uint64_t* xy, const int* infinity, const uint32_t* points, size_t k, int degree,
@@ -559,93 +678,31 @@ int cozk_shamir_combine_points(cozk_ctx* ctx, const uint64_t* xy, const int* inf
 // degree 2t.  The reference has no such step (no Shamir network at all); tests/shamir_mul_ref.py restates it.
 int cozk_shamir_mul_deal(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, const uint8_t* keys, int degree, int num_parties,
                          uint64_t counter, cozk_vec** out) {
-    if (int rc0 = require_out(ctx, out, "shamir_mul_deal: null output")) return rc0;
-    clear_outputs(out, num_parties);
-    int rc = cozk_guard(ctx, [&] {
-        COZK_REQUIRE(ctx && a && b && keys, "shamir_mul_deal: null argument");
-        require_factors("shamir_mul_deal", a, b);
-        require_mul_args("shamir_mul_deal", degree, num_parties);
-    });
-    if (rc != COZK_OK) return rc;
-    rc = alloc_outputs(ctx, nullptr, a->n, num_parties, out);
-    if (rc != COZK_OK) return rc;
-    rc = cozk_guard(ctx, [&] {
-        if (a->n == 0) return;
-        launch_share(ctx->stream, mul_prf_src(a, b, keys, degree, counter), out_table(out, num_parties), a->n, degree, num_parties);
-    });
-    if (rc != COZK_OK) free_all(out, num_parties);
-    return rc;
+    return entry_point(
+        ctx, "shamir_mul_deal: null output", {{out, num_parties}},
+        [&] {
+            COZK_REQUIRE(ctx && a && b && keys, "shamir_mul_deal: null argument");
+            require_factors("shamir_mul_deal", a, b);
+            require_mul_args("shamir_mul_deal", degree, num_parties);
+            return a->n;
+        },
+        [&](size_t n) { launch_share(ctx->stream, mul_prf_src(a, b, keys, degree, counter), out_table(out, num_parties), n, degree, num_parties); });
 }
 
 }  // extern "C"
 
 // what cozk_shamir_mul_inproc and cozk_shamir_mul_pairs_inproc share, behind their argument checks: n elements per party,
-// src_of(p) = dealer p's source for the dealing kernel
+// src_of(p) = dealer p's source for the dealing kernel, the finish = the degree-2t combine
 template <class SrcOf>
-static int mul_inproc_drive(cozk_ctx* const* party_ctxs, size_t n, int degree, int num_parties, cozk_vec** out, SrcOf src_of) {
-    cozk_ctx* const c0 = party_ctxs[0];
+static int mul_all_to_all(cozk_ctx* const* party_ctxs, size_t n, int degree, int num_parties, cozk_vec** out, SrcOf src_of) {
     const int dealers = 2 * degree + 1;
-    int rc = COZK_OK;
-    std::vector<cozk_vec*> recv((size_t)num_parties * dealers, nullptr);  // recv[q * dealers + p] = h_{p -> q}, a block of party q
-    std::vector<fe*> stage(dealers, nullptr);
-    // a failure of party p's step leaves its text with party 0 and nothing allocated
-    auto fail = [&](int code, int p) {
-        if (party_ctxs[p] != c0) c0->last_error = party_ctxs[p]->last_error;
-        for (int q = 0; q < num_parties; q++) (void)hipStreamSynchronize(party_ctxs[q]->stream);
-        for (int d = 0; d < dealers; d++) ctx_dev_free(party_ctxs[d], stage[d]);
-        for (cozk_vec* v : recv) cozk_vec_free(v);
-        free_all(out, num_parties);
-        return code;
-    };
-    for (int q = 0; q < num_parties; q++)
-        for (int p = 0; p < dealers; p++)
-            if ((rc = cozk_vec_alloc(party_ctxs[q], n, COZK_SCALAR_FR, &recv[(size_t)q * dealers + p])) != COZK_OK) return fail(rc, q);
-    if (n) {
-        // the receive blocks are ordered by their owners' streams only (see cozk_shamir_scatter): every party's stream drains
-        // before any dealer's stream writes into another party's block
-        rc = cozk_guard(c0, [&] {
-            for (int q = 0; q < num_parties; q++) HIP_TRY(hipStreamSynchronize(party_ctxs[q]->stream));
-        });
-        if (rc != COZK_OK) return fail(rc, 0);
-        for (int p = 0; p < dealers; p++) {
-            cozk_ctx* dealer = party_ctxs[p];
-            rc = cozk_guard(dealer, [&] {
-                size_t remote = 0;
-                for (int q = 0; q < num_parties; q++) remote += party_ctxs[q]->device != dealer->device;
-                if (remote) stage[p] = (fe*)ctx_dev_alloc(dealer, remote * n * sizeof(fe));
-                ShamirOut o;
-                memset(&o, 0, sizeof o);
-                size_t r = 0;
-                for (int q = 0; q < num_parties; q++)
-                    o.p[q] = party_ctxs[q]->device != dealer->device ? stage[p] + n * r++ : (fe*)recv[(size_t)q * dealers + p]->d;
-                launch_share(dealer->stream, src_of(p), o, n, degree, num_parties);
-                for (int q = 0; q < num_parties; q++)
-                    if (party_ctxs[q]->device != dealer->device)
-                        HIP_TRY(hipMemcpyPeerAsync(recv[(size_t)q * dealers + p]->d, party_ctxs[q]->device, o.p[q], dealer->device, n * sizeof(fe),
-                                                   dealer->stream));
-            });
-            if (rc != COZK_OK) return fail(rc, p);
-        }
-        for (int p = 0; p < dealers; p++) {  // the parties' streams may read what they received once the dealers' have drained
-            rc = cozk_guard(party_ctxs[p], [&] {
-                HIP_TRY(hipStreamSynchronize(party_ctxs[p]->stream));
-                ctx_dev_free(party_ctxs[p], stage[p]);
-                stage[p] = nullptr;
-            });
-            if (rc != COZK_OK) return fail(rc, p);
-        }
-    }
     uint32_t points[COZK_SHAMIR_MAX_PARTIES];
     for (int p = 0; p < dealers; p++) points[p] = (uint32_t)p + 1;
-    for (int q = 0; q < num_parties; q++) {  // the finish, on each party's own stream; its pool takes the blocks back behind it
-        rc = cozk_shamir_combine_vec(party_ctxs[q], &recv[(size_t)q * dealers], points, (size_t)dealers, 2 * degree, &out[q]);
-        if (rc != COZK_OK) return fail(rc, q);
-        for (int p = 0; p < dealers; p++) {
-            cozk_vec_free(recv[(size_t)q * dealers + p]);
-            recv[(size_t)q * dealers + p] = nullptr;
-        }
-    }
-    return COZK_OK;
+    int rc = deal_all_to_all(party_ctxs, n, dealers, num_parties, degree, src_of, [&](int q, cozk_vec* const* row) {
+        return cozk_shamir_combine_vec(party_ctxs[q], row, points, (size_t)dealers, 2 * degree, &out[q]);
+    });
+    if (rc != COZK_OK) free_all(out, num_parties);
+    return rc;
 }
 
 extern "C" {
@@ -669,27 +726,19 @@ int cozk_shamir_mul_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* a
         }
     });
     if (rc != COZK_OK) return rc;
-    return mul_inproc_drive(party_ctxs, a[0]->n, degree, num_parties, out, [&](int p) { return mul_prf_src(a[p], b[p], keys[p], degree, counter); });
+    return mul_all_to_all(party_ctxs, a[0]->n, degree, num_parties, out, [&](int p) { return mul_prf_src(a[p], b[p], keys[p], degree, counter); });
 }
 
 int cozk_shamir_mul_deal_pairs(cozk_ctx* ctx, const cozk_vec* v, const uint8_t* keys, int degree, int num_parties, uint64_t counter, cozk_vec** out) {
-    if (int rc0 = require_out(ctx, out, "shamir_mul_deal_pairs: null output")) return rc0;
-    clear_outputs(out, num_parties);
-    int rc = cozk_guard(ctx, [&] {
-        COZK_REQUIRE(ctx && v && keys, "shamir_mul_deal_pairs: null argument");
-        require_pairs("shamir_mul_deal_pairs", v);
-        require_mul_args("shamir_mul_deal_pairs", degree, num_parties);
-    });
-    if (rc != COZK_OK) return rc;
-    const size_t m = v->n / 2;
-    rc = alloc_outputs(ctx, nullptr, m, num_parties, out);
-    if (rc != COZK_OK) return rc;
-    rc = cozk_guard(ctx, [&] {
-        if (m == 0) return;
-        launch_share(ctx->stream, pairs_prf_src(v, keys, degree, counter), out_table(out, num_parties), m, degree, num_parties);
-    });
-    if (rc != COZK_OK) free_all(out, num_parties);
-    return rc;
+    return entry_point(
+        ctx, "shamir_mul_deal_pairs: null output", {{out, num_parties}},
+        [&] {
+            COZK_REQUIRE(ctx && v && keys, "shamir_mul_deal_pairs: null argument");
+            require_pairs("shamir_mul_deal_pairs", v);
+            require_mul_args("shamir_mul_deal_pairs", degree, num_parties);
+            return v->n / 2;
+        },
+        [&](size_t m) { launch_share(ctx->stream, pairs_prf_src(v, keys, degree, counter), out_table(out, num_parties), m, degree, num_parties); });
 }
 
 int cozk_shamir_mul_pairs_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* v, const uint8_t* const* keys, int degree, int num_parties,
@@ -701,16 +750,14 @@ int cozk_shamir_mul_pairs_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* co
         COZK_REQUIRE(party_ctxs && v && keys, "shamir_mul_pairs_inproc: null argument");
         require_mul_args("shamir_mul_pairs_inproc", degree, num_parties);
         for (int p = 0; p < num_parties; p++) COZK_REQUIRE(party_ctxs[p], "shamir_mul_pairs_inproc: null party context");
+        COZK_REQUIRE(v[0], "shamir_mul_pairs_inproc: parties 0..2 * degree need their layer");
         for (int p = 0; p < 2 * degree + 1; p++) {
-            COZK_REQUIRE(v[p], "shamir_mul_pairs_inproc: parties 0..2 * degree need their layer");
-            require_pairs("shamir_mul_pairs_inproc", v[p]);
-            COZK_REQUIRE(v[p]->n == v[0]->n, "shamir_mul_pairs_inproc: the layers must have one length");
-            COZK_REQUIRE(v[p]->ctx == party_ctxs[p], "shamir_mul_pairs_inproc: party p's layer must be a vector of party_ctxs[p]");
+            require_own_vec("shamir_mul_pairs_inproc", v[p], party_ctxs[p], v[0]->n, LAYER_TEXTS);
             COZK_REQUIRE(keys[p], "shamir_mul_pairs_inproc: parties 0..2 * degree need their key block");
         }
     });
     if (rc != COZK_OK) return rc;
-    return mul_inproc_drive(party_ctxs, v[0]->n / 2, degree, num_parties, out, [&](int p) { return pairs_prf_src(v[p], keys[p], degree, counter); });
+    return mul_all_to_all(party_ctxs, v[0]->n / 2, degree, num_parties, out, [&](int p) { return pairs_prf_src(v[p], keys[p], degree, counter); });
 }
 
 int cozk_shamir_mul_vec(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, const uint8_t* keys, int degree, uint64_t counter, cozk_vec** out) {
@@ -807,14 +854,6 @@ static int require_out2(cozk_ctx* ctx, cozk_vec** x, cozk_vec** y, int len, cons
     return rc;
 }
 
-static void require_own_vec(const char* who, const cozk_vec* v, const cozk_ctx* ctx, size_t n, const char* what) {
-    const std::string w(who);
-    COZK_REQUIRE(v, w + ": null " + what);
-    COZK_REQUIRE(v->kind == COZK_SCALAR_FR, w + ": " + what + " must be an FR vector");
-    COZK_REQUIRE(v->n == n, w + ": the factors and the pair must have one length");
-    COZK_REQUIRE(v->ctx == ctx, w + ": " + what + " must be a vector of its party's context");
-}
-
 static void launch_mul_add(hipStream_t st, const cozk_vec* a, const cozk_vec* b, const cozk_vec* c, fe* out) {
     if (a->n == 0) return;
     k_fe_mul_add<<<(unsigned)((a->n + 255) / 256), 256, 0, st>>>((const fe*)a->d, (const fe*)b->d, (const fe*)c->d, out, a->n);
@@ -822,65 +861,12 @@ static void launch_mul_add(hipStream_t st, const cozk_vec* a, const cozk_vec* b,
 }
 
 // one degree of the preprocessing: every party deals with `deg` coefficient keys from keys[p][first] to parties 0..rcp - 1, each
-// of which extracts `count` vectors into r[q * count + k] (cozk_shamir_rand_inproc: rcp = np, count = np - t).  On failure nothing
-// of its own is left; the caller frees r.
+// of which extracts `count` vectors into r[q * count + k] (cozk_shamir_rand_inproc: rcp = np, count = np - t).  The caller frees r.
 static int rand_pass(cozk_ctx* const* pcs, const uint8_t* const* keys, size_t n, int first, int deg, int np, int rcp, int count, uint64_t counter,
                      cozk_vec** r) {
-    cozk_ctx* const c0 = pcs[0];
-    std::vector<cozk_vec*> recv((size_t)rcp * np, nullptr);  // recv[q * np + p] = what party p dealt to party q, a block of party q
-    std::vector<fe*> stage(np, nullptr);
-    int rc = COZK_OK;
-    auto fail = [&](int code, int p) {
-        if (pcs[p] != c0) c0->last_error = pcs[p]->last_error;
-        for (int q = 0; q < np; q++) (void)hipStreamSynchronize(pcs[q]->stream);
-        for (int d = 0; d < np; d++) ctx_dev_free(pcs[d], stage[d]);
-        for (cozk_vec* v : recv) cozk_vec_free(v);
-        return code;
-    };
-    for (int q = 0; q < rcp; q++)
-        for (int p = 0; p < np; p++)
-            if ((rc = cozk_vec_alloc(pcs[q], n, COZK_SCALAR_FR, &recv[(size_t)q * np + p])) != COZK_OK) return fail(rc, q);
-    if (n) {
-        // the receive blocks are ordered by their owners' streams only (see cozk_shamir_scatter)
-        rc = cozk_guard(c0, [&] {
-            for (int q = 0; q < np; q++) HIP_TRY(hipStreamSynchronize(pcs[q]->stream));
-        });
-        if (rc != COZK_OK) return fail(rc, 0);
-        for (int p = 0; p < np; p++) {
-            cozk_ctx* dealer = pcs[p];
-            rc = cozk_guard(dealer, [&] {
-                size_t remote = 0;
-                for (int q = 0; q < rcp; q++) remote += pcs[q]->device != dealer->device;
-                if (remote) stage[p] = (fe*)ctx_dev_alloc(dealer, remote * n * sizeof(fe));
-                ShamirOut o;
-                memset(&o, 0, sizeof o);
-                size_t k = 0;
-                for (int q = 0; q < rcp; q++) o.p[q] = pcs[q]->device != dealer->device ? stage[p] + n * k++ : (fe*)recv[(size_t)q * np + p]->d;
-                launch_share(dealer->stream, rand_prf_src(keys[p], first, deg, counter), o, n, deg, rcp);
-                for (int q = 0; q < rcp; q++)
-                    if (pcs[q]->device != dealer->device)
-                        HIP_TRY(hipMemcpyPeerAsync(recv[(size_t)q * np + p]->d, pcs[q]->device, o.p[q], dealer->device, n * sizeof(fe), dealer->stream));
-            });
-            if (rc != COZK_OK) return fail(rc, p);
-        }
-        for (int p = 0; p < np; p++) {  // the parties' streams may read what they received once the dealers' have drained
-            rc = cozk_guard(pcs[p], [&] {
-                HIP_TRY(hipStreamSynchronize(pcs[p]->stream));
-                ctx_dev_free(pcs[p], stage[p]);
-                stage[p] = nullptr;
-            });
-            if (rc != COZK_OK) return fail(rc, p);
-        }
-    }
-    for (int q = 0; q < rcp; q++) {  // the extraction, on each party's own stream; its pool takes the blocks back behind it
-        rc = cozk_shamir_rand_extract(pcs[q], &recv[(size_t)q * np], np, count, &r[(size_t)q * count]);
-        if (rc != COZK_OK) return fail(rc, q);
-        for (int p = 0; p < np; p++) {
-            cozk_vec_free(recv[(size_t)q * np + p]);
-            recv[(size_t)q * np + p] = nullptr;
-        }
-    }
-    return COZK_OK;
+    return deal_all_to_all(
+        pcs, n, np, rcp, deg, [&](int p) { return rand_prf_src(keys[p], first, deg, counter); },
+        [&](int q, cozk_vec* const* row) { return cozk_shamir_rand_extract(pcs[q], row, np, count, &r[(size_t)q * count]); });
 }
 
 // the preprocessing of the king grand product (csrc/host/shamir_gp.hpp), which extracts only what it uses: `count` <= np - t pairs,
@@ -905,56 +891,39 @@ extern "C" {
 
 int cozk_shamir_rand_deal(cozk_ctx* ctx, size_t n_elems, const uint8_t* keys, int degree, int num_parties, uint64_t counter, cozk_vec** out_t,
                           cozk_vec** out_2t) {
-    if (int rc0 = require_out2(ctx, out_t, out_2t, num_parties, "shamir_rand_deal: null output")) return rc0;
-    clear_outputs(out_t, num_parties);
-    clear_outputs(out_2t, num_parties);
-    int rc = cozk_guard(ctx, [&] {
-        COZK_REQUIRE(ctx && keys, "shamir_rand_deal: null argument");
-        require_rand_args("shamir_rand_deal", degree, num_parties);
-    });
-    if (rc != COZK_OK) return rc;
-    rc = alloc_outputs(ctx, nullptr, n_elems, num_parties, out_t);
-    if (rc != COZK_OK) return rc;
-    rc = alloc_outputs(ctx, nullptr, n_elems, num_parties, out_2t);
-    if (rc == COZK_OK)
-        rc = cozk_guard(ctx, [&] {
-            if (n_elems == 0) return;
-            launch_share(ctx->stream, rand_prf_src(keys, 1, degree, counter), out_table(out_t, num_parties), n_elems, degree, num_parties);
-            launch_share(ctx->stream, rand_prf_src(keys, 1 + degree, 2 * degree, counter), out_table(out_2t, num_parties), n_elems, 2 * degree, num_parties);
+    return entry_point(
+        ctx, "shamir_rand_deal: null output", {{out_t, num_parties}, {out_2t, num_parties}},
+        [&] {
+            COZK_REQUIRE(ctx && keys, "shamir_rand_deal: null argument");
+            require_rand_args("shamir_rand_deal", degree, num_parties);
+            return n_elems;
+        },
+        [&](size_t n) {
+            launch_share(ctx->stream, rand_prf_src(keys, 1, degree, counter), out_table(out_t, num_parties), n, degree, num_parties);
+            launch_share(ctx->stream, rand_prf_src(keys, 1 + degree, 2 * degree, counter), out_table(out_2t, num_parties), n, 2 * degree, num_parties);
         });
-    if (rc != COZK_OK) {
-        free_all(out_t, num_parties);
-        free_all(out_2t, num_parties);
-    }
-    return rc;
 }
 
 int cozk_shamir_rand_extract(cozk_ctx* ctx, const cozk_vec* const* recv, int num_parties, int count, cozk_vec** out) {
-    if (int rc0 = require_out(ctx, out, "shamir_rand_extract: null output")) return rc0;
-    clear_outputs(out, count);
-    int rc = cozk_guard(ctx, [&] {
-        COZK_REQUIRE(ctx && recv, "shamir_rand_extract: null argument");
-        COZK_REQUIRE(num_parties >= 2 && num_parties <= COZK_SHAMIR_MAX_PARTIES, "shamir_rand_extract: 2 <= num_parties <= COZK_SHAMIR_MAX_PARTIES");
-        COZK_REQUIRE(count >= 1 && count <= num_parties - 1, "shamir_rand_extract: 1 <= count <= num_parties - 1");
-        for (int j = 0; j < num_parties; j++) {
-            COZK_REQUIRE(recv[j] && recv[j]->kind == COZK_SCALAR_FR, "shamir_rand_extract: num_parties FR vectors");
-            COZK_REQUIRE(recv[j]->n == recv[0]->n, "shamir_rand_extract: the vectors must have one length");
-        }
-    });
-    if (rc != COZK_OK) return rc;
-    const size_t n = recv[0]->n;
-    rc = alloc_outputs(ctx, nullptr, n, count, out);
-    if (rc != COZK_OK) return rc;
-    rc = cozk_guard(ctx, [&] {
-        if (n == 0) return;
-        const fe* in[COZK_SHAMIR_MAX_PARTIES];
-        fe* o[COZK_SHAMIR_MAX_PARTIES];
-        for (int j = 0; j < num_parties; j++) in[j] = (const fe*)recv[j]->d;
-        for (int k = 0; k < count; k++) o[k] = (fe*)out[k]->d;
-        launch_extract(ctx->stream, in, num_parties, count, o, n);
-    });
-    if (rc != COZK_OK) free_all(out, count);
-    return rc;
+    return entry_point(
+        ctx, "shamir_rand_extract: null output", {{out, count}},
+        [&] {
+            COZK_REQUIRE(ctx && recv, "shamir_rand_extract: null argument");
+            COZK_REQUIRE(num_parties >= 2 && num_parties <= COZK_SHAMIR_MAX_PARTIES, "shamir_rand_extract: 2 <= num_parties <= COZK_SHAMIR_MAX_PARTIES");
+            COZK_REQUIRE(count >= 1 && count <= num_parties - 1, "shamir_rand_extract: 1 <= count <= num_parties - 1");
+            for (int j = 0; j < num_parties; j++) {
+                COZK_REQUIRE(recv[j] && recv[j]->kind == COZK_SCALAR_FR, "shamir_rand_extract: num_parties FR vectors");
+                COZK_REQUIRE(recv[j]->n == recv[0]->n, "shamir_rand_extract: the vectors must have one length");
+            }
+            return recv[0]->n;
+        },
+        [&](size_t n) {
+            const fe* in[COZK_SHAMIR_MAX_PARTIES];
+            fe* o[COZK_SHAMIR_MAX_PARTIES];
+            for (int j = 0; j < num_parties; j++) in[j] = (const fe*)recv[j]->d;
+            for (int k = 0; k < count; k++) o[k] = (fe*)out[k]->d;
+            launch_extract(ctx->stream, in, num_parties, count, o, n);
+        });
 }
 
 int cozk_shamir_rand_inproc(cozk_ctx* const* party_ctxs, const uint8_t* const* keys, size_t n_elems, int degree, int num_parties, uint64_t counter,
@@ -1026,51 +995,67 @@ int cozk_shamir_rand_vec(cozk_ctx* ctx, size_t n_elems, const uint8_t* keys, int
 }
 
 int cozk_shamir_mul_mask(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, const cozk_vec* r_2t, cozk_vec** out) {
-    if (int rc0 = require_out(ctx, out, "shamir_mul_mask: null output")) return rc0;
-    *out = nullptr;
-    int rc = cozk_guard(ctx, [&] {
-        COZK_REQUIRE(ctx && a && b && r_2t, "shamir_mul_mask: null argument");
-        COZK_REQUIRE(a->kind == COZK_SCALAR_FR && b->kind == COZK_SCALAR_FR && r_2t->kind == COZK_SCALAR_FR, "shamir_mul_mask: the factors and the mask must be FR vectors");
-        COZK_REQUIRE(a->n == b->n && a->n == r_2t->n, "shamir_mul_mask: the factors and the mask must have one length");
-    });
-    if (rc != COZK_OK) return rc;
-    rc = cozk_vec_alloc(ctx, a->n, COZK_SCALAR_FR, out);
-    if (rc != COZK_OK) return rc;
-    rc = cozk_guard(ctx, [&] { launch_mul_add(ctx->stream, a, b, r_2t, (fe*)(*out)->d); });
-    if (rc != COZK_OK) {
-        cozk_vec_free(*out);
-        *out = nullptr;
-    }
-    return rc;
+    return entry_point(
+        ctx, "shamir_mul_mask: null output", {{out, 1}},
+        [&] {
+            COZK_REQUIRE(ctx && a && b && r_2t, "shamir_mul_mask: null argument");
+            COZK_REQUIRE(a->kind == COZK_SCALAR_FR && b->kind == COZK_SCALAR_FR && r_2t->kind == COZK_SCALAR_FR, "shamir_mul_mask: the factors and the mask must be FR vectors");
+            COZK_REQUIRE(a->n == b->n && a->n == r_2t->n, "shamir_mul_mask: the factors and the mask must have one length");
+            return a->n;
+        },
+        [&](size_t) { launch_mul_add(ctx->stream, a, b, r_2t, (fe*)(*out)->d); });
 }
 
-int cozk_shamir_mul_king_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* a, const cozk_vec* const* b, const cozk_vec* const* r_t,
-                                const cozk_vec* const* r_2t, int degree, int num_parties, int king, cozk_vec** out) {
-    cozk_ctx* const c0 = party_ctxs && num_parties >= 1 ? party_ctxs[0] : nullptr;  // receives the error message
-    if (int rc0 = require_out(c0, out, "shamir_mul_king_inproc: null output")) return rc0;
-    clear_outputs(out, num_parties);
+}  // extern "C"
+
+// ------------------------------------------------------------------ the online step with a king, in process
+// The halves of a pair are addressed by an element offset, so that one preprocessed pair serves many tree levels of the king
+// grand product; the king's open and the unmasks of its device are one launch (k_shamir_king_finish).
+static void launch_mask_pairs(hipStream_t st, const cozk_vec* v, const cozk_vec* r_2t, size_t off, fe* out) {
+    const size_t m = v->n / 2;
+    if (m == 0) return;
+    k_shamir_mask_pairs<<<(unsigned)((m + 255) / 256), 256, 0, st>>>((const fe*)v->d, (const fe*)r_2t->d + off, out, m);
+    HIP_TRY(hipGetLastError());
+}
+
+// z = sum_{j < k} lambda_j m[j], lambda = lagrange(1..k); out[q] = z - (rt[q] + off) for q < count; z_out may be null
+static void launch_king_finish(hipStream_t st, const fe* const* m, int k, const fe* const* rt, size_t off, int count, fe* const* out, fe* z_out, size_t n) {
+    if (n == 0) return;
+    ShamirKingFinishArgs a;
+    memset(&a, 0, sizeof a);
+    uint32_t points[COZK_SHAMIR_MAX_PARTIES];
+    for (int j = 0; j < k; j++) points[j] = (uint32_t)j + 1;
+    lagrange_host(points, (size_t)k, a.lambda);
+    for (int j = 0; j < k; j++) a.m[j] = m[j];
+    for (int q = 0; q < count; q++) {
+        a.rt[q] = rt[q] + off;
+        a.out[q] = out[q];
+    }
+    k_shamir_king_finish<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(a, k, count, z_out, n);
+    HIP_TRY(hipGetLastError());
+}
+
+// off + len <= have without overflow
+static bool slice_fits(size_t off, size_t len, size_t have) { return off <= have && len <= have - off; }
+
+// The king driver behind cozk_shamir_mul_king_inproc and cozk_shamir_mul_king_pairs_inproc: n products per party, the pair read from
+// element r_offset.  mask(p, dst) enqueues sender p's masked products m_p on p's stream into dst.  The fan-in mirrors fan_out:
+// dst is the king's block where sender p lives on the king's device, else a staging block of p's followed by one peer copy.  Then
+// ONE launch on the king's stream opens z = sum_p lambda_p m_p and writes c_q = z - rt_q for every party q of the king's device;
+// z itself is stored only where some party lives on another device, peer-copied there by the king's stream, and subtracted on
+// that party's own stream (the same kernel, k = 1).  The three rules above fan_out hold: rule 1 by the one drain of every stream
+// (the senders write into the king's blocks, the king into every recipient's), rule 2 by the senders' drain and the king's.
+template <class Mask>
+static int king_drive(cozk_ctx* const* party_ctxs, const cozk_vec* const* r_t, size_t n, size_t r_offset, int degree, int num_parties, int king,
+                      cozk_vec** out, Mask mask) {
+    cozk_ctx *const c0 = party_ctxs[0], *const kc = party_ctxs[king];
     const int senders = 2 * degree + 1;
-    const char* who = "shamir_mul_king_inproc";
-    int rc = cozk_guard(c0, [&] {
-        COZK_REQUIRE(party_ctxs && a && b && r_t && r_2t, "shamir_mul_king_inproc: null argument");
-        require_rand_args(who, degree, num_parties);
-        COZK_REQUIRE(king >= 0 && king < num_parties, "shamir_mul_king_inproc: 0 <= king < num_parties");
-        for (int p = 0; p < num_parties; p++) COZK_REQUIRE(party_ctxs[p], "shamir_mul_king_inproc: null party context");
-        COZK_REQUIRE(r_t[0], "shamir_mul_king_inproc: null first half of the pair");
-        for (int p = 0; p < num_parties; p++) require_own_vec(who, r_t[p], party_ctxs[p], r_t[0]->n, "the first half of the pair");
-        for (int p = 0; p < senders; p++) {
-            require_own_vec(who, a[p], party_ctxs[p], r_t[0]->n, "a factor of parties 0..2 * degree");
-            require_own_vec(who, b[p], party_ctxs[p], r_t[0]->n, "a factor of parties 0..2 * degree");
-            require_own_vec(who, r_2t[p], party_ctxs[p], r_t[0]->n, "the second half of the pair of parties 0..2 * degree");
-        }
-    });
-    if (rc != COZK_OK) return rc;
-    const size_t n = r_t[0]->n;
-    cozk_ctx* const kc = party_ctxs[king];
-    cozk_vec* m[COZK_SHAMIR_MAX_PARTIES] = {};     // m[p] = a_p b_p + r2t_p, a block of the king
-    fe* stage[COZK_SHAMIR_MAX_PARTIES] = {};       // the same on a sender's other device
-    cozk_vec* zq[COZK_SHAMIR_MAX_PARTIES] = {};    // z on a party's other device, a block of that party
-    cozk_vec* z = nullptr;
+    int rc = COZK_OK;
+    cozk_vec* m[COZK_SHAMIR_MAX_PARTIES] = {};   // m[p], a block of the king
+    fe* stage[COZK_SHAMIR_MAX_PARTIES] = {};     // the same on a sender's other device
+    cozk_vec* zq[COZK_SHAMIR_MAX_PARTIES] = {};  // z on a party's other device, a block of that party
+    cozk_vec* z = nullptr;                       // z on the king's device: only where some party lives on another
+    // a failure of party p's step leaves its text with party 0 and nothing allocated
     auto fail = [&](int code, int p) {
         if (party_ctxs[p] != c0) c0->last_error = party_ctxs[p]->last_error;
         for (int q = 0; q < num_parties; q++) (void)hipStreamSynchronize(party_ctxs[q]->stream);
@@ -1081,70 +1066,95 @@ int cozk_shamir_mul_king_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* con
         free_all(out, num_parties);
         return code;
     };
+    bool any_remote = false;
     for (int p = 0; p < senders; p++)
         if ((rc = cozk_vec_alloc(kc, n, COZK_SCALAR_FR, &m[p])) != COZK_OK) return fail(rc, king);
     for (int q = 0; q < num_parties; q++) {
-        if (party_ctxs[q]->device != kc->device && (rc = cozk_vec_alloc(party_ctxs[q], n, COZK_SCALAR_FR, &zq[q])) != COZK_OK) return fail(rc, q);
+        if (party_ctxs[q]->device != kc->device) {
+            any_remote = true;
+            if ((rc = cozk_vec_alloc(party_ctxs[q], n, COZK_SCALAR_FR, &zq[q])) != COZK_OK) return fail(rc, q);
+        }
         if ((rc = cozk_vec_alloc(party_ctxs[q], n, COZK_SCALAR_FR, &out[q])) != COZK_OK) {
             out[q] = nullptr;
             return fail(rc, q);
         }
     }
-    if (n) {
-        // the king's blocks are ordered by the king's stream only (see cozk_shamir_scatter): every party's stream drains before a
-        // sender's stream writes into one
-        rc = cozk_guard(c0, [&] {
-            for (int q = 0; q < num_parties; q++) HIP_TRY(hipStreamSynchronize(party_ctxs[q]->stream));
-        });
-        if (rc != COZK_OK) return fail(rc, 0);
-        for (int p = 0; p < senders; p++) {  // step 1 and 2: the mask on each sender's own stream, into the king's memory
-            cozk_ctx* sc = party_ctxs[p];
-            rc = cozk_guard(sc, [&] {
-                const bool remote = sc->device != kc->device;
-                if (remote) stage[p] = (fe*)ctx_dev_alloc(sc, n * sizeof(fe));
-                launch_mul_add(sc->stream, a[p], b[p], r_2t[p], remote ? stage[p] : (fe*)m[p]->d);
-                if (remote) HIP_TRY(hipMemcpyPeerAsync(m[p]->d, kc->device, stage[p], sc->device, n * sizeof(fe), sc->stream));
-            });
-            if (rc != COZK_OK) return fail(rc, p);
-        }
-        for (int p = 0; p < senders; p++) {  // the king may read the masked products once the senders' streams have drained
-            rc = cozk_guard(party_ctxs[p], [&] {
-                HIP_TRY(hipStreamSynchronize(party_ctxs[p]->stream));
-                ctx_dev_free(party_ctxs[p], stage[p]);
-                stage[p] = nullptr;
-            });
-            if (rc != COZK_OK) return fail(rc, p);
-        }
+    if (any_remote && (rc = cozk_vec_alloc(kc, n, COZK_SCALAR_FR, &z)) != COZK_OK) return fail(rc, king);
+    if (n == 0) {
+        free_all(m, senders);
+        free_all(zq, num_parties);
+        cozk_vec_free(z);
+        return COZK_OK;
     }
-    uint32_t points[COZK_SHAMIR_MAX_PARTIES];
-    for (int p = 0; p < senders; p++) points[p] = (uint32_t)p + 1;
-    rc = cozk_shamir_combine_vec(kc, m, points, (size_t)senders, 2 * degree, &z);  // step 3, on the king's stream
+    if ((rc = drain_all(party_ctxs, num_parties)) != COZK_OK) return fail(rc, 0);
+    for (int p = 0; p < senders; p++) {  // the fan-in: the mask on each sender's own stream, into the king's memory
+        cozk_ctx* sc = party_ctxs[p];
+        rc = cozk_guard(sc, [&] {
+            const bool remote = sc->device != kc->device;
+            if (remote) stage[p] = (fe*)ctx_dev_alloc(sc, n * sizeof(fe));
+            mask(p, remote ? stage[p] : (fe*)m[p]->d);
+            if (remote) HIP_TRY(hipMemcpyPeerAsync(m[p]->d, kc->device, stage[p], sc->device, n * sizeof(fe), sc->stream));
+        });
+        if (rc != COZK_OK) return fail(rc, p);
+    }
+    int failed = 0;
+    if ((rc = drain_writers(party_ctxs, senders, stage, &failed)) != COZK_OK) return fail(rc, failed);
+    rc = cozk_guard(kc, [&] {
+        const fe *mp[COZK_SHAMIR_MAX_PARTIES], *rt[COZK_SHAMIR_MAX_PARTIES];
+        fe* o[COZK_SHAMIR_MAX_PARTIES];
+        int count = 0;
+        for (int p = 0; p < senders; p++) mp[p] = (const fe*)m[p]->d;
+        for (int q = 0; q < num_parties; q++)
+            if (!zq[q]) {
+                rt[count] = (const fe*)r_t[q]->d;
+                o[count++] = (fe*)out[q]->d;
+            }
+        launch_king_finish(kc->stream, mp, senders, rt, r_offset, count, o, z ? (fe*)z->d : nullptr, n);
+        for (int q = 0; q < num_parties; q++)  // z to the other devices by the king's stream
+            if (zq[q]) HIP_TRY(hipMemcpyPeerAsync(zq[q]->d, party_ctxs[q]->device, z->d, kc->device, n * sizeof(fe), kc->stream));
+        HIP_TRY(hipStreamSynchronize(kc->stream));  // the recipients' streams may use their blocks as soon as this returns
+    });
     if (rc != COZK_OK) return fail(rc, king);
-    free_all(m, senders);  // the king's pool takes them back behind the combine
-    if (n) {
-        rc = cozk_guard(kc, [&] {  // step 4: z to the other devices by the king's stream, then that stream drains
-            for (int q = 0; q < num_parties; q++)
-                if (zq[q]) HIP_TRY(hipMemcpyPeerAsync(zq[q]->d, party_ctxs[q]->device, z->d, kc->device, n * sizeof(fe), kc->stream));
-            HIP_TRY(hipStreamSynchronize(kc->stream));
+    free_all(m, senders);
+    cozk_vec_free(z);
+    z = nullptr;
+    for (int q = 0; q < num_parties; q++) {
+        if (!zq[q]) continue;
+        rc = cozk_guard(party_ctxs[q], [&] {
+            const fe *mp[1] = {(const fe*)zq[q]->d}, *rt[1] = {(const fe*)r_t[q]->d};
+            fe* o[1] = {(fe*)out[q]->d};
+            launch_king_finish(party_ctxs[q]->stream, mp, 1, rt, r_offset, 1, o, nullptr, n);  // lagrange(1) = 1
         });
-        if (rc != COZK_OK) return fail(rc, king);
-    }
-    for (int q = 0; q < num_parties; q++) {  // c_q = z - rt_q on each party's own stream
-        rc = cozk_vec_binop(party_ctxs[q], COZK_OP_SUB, 0, zq[q] ? zq[q] : z, r_t[q], out[q]);
         if (rc != COZK_OK) return fail(rc, q);
     }
-    free_all(zq, num_parties);
-    if (n) {
-        // z is the king's block and was read in place by the other parties of its device: their streams drain before the king's
-        // pool may hand it out again
-        rc = cozk_guard(c0, [&] {
-            for (int q = 0; q < num_parties; q++)
-                if (q != king && party_ctxs[q]->device == kc->device) HIP_TRY(hipStreamSynchronize(party_ctxs[q]->stream));
-        });
-        if (rc != COZK_OK) return fail(rc, 0);
-    }
-    cozk_vec_free(z);
+    free_all(zq, num_parties);  // each behind its reader on its owner's stream
     return COZK_OK;
+}
+
+extern "C" {
+
+int cozk_shamir_mul_king_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* a, const cozk_vec* const* b, const cozk_vec* const* r_t,
+                                const cozk_vec* const* r_2t, int degree, int num_parties, int king, cozk_vec** out) {
+    cozk_ctx* const c0 = party_ctxs && num_parties >= 1 ? party_ctxs[0] : nullptr;  // receives the error message
+    if (int rc0 = require_out(c0, out, "shamir_mul_king_inproc: null output")) return rc0;
+    clear_outputs(out, num_parties);
+    const char* who = "shamir_mul_king_inproc";
+    int rc = cozk_guard(c0, [&] {
+        COZK_REQUIRE(party_ctxs && a && b && r_t && r_2t, "shamir_mul_king_inproc: null argument");
+        require_rand_args(who, degree, num_parties);
+        COZK_REQUIRE(king >= 0 && king < num_parties, "shamir_mul_king_inproc: 0 <= king < num_parties");
+        for (int p = 0; p < num_parties; p++) COZK_REQUIRE(party_ctxs[p], "shamir_mul_king_inproc: null party context");
+        COZK_REQUIRE(r_t[0], "shamir_mul_king_inproc: null first half of the pair");
+        for (int p = 0; p < num_parties; p++) require_own_vec(who, r_t[p], party_ctxs[p], r_t[0]->n, "the first half of the pair");
+        for (int p = 0; p < 2 * degree + 1; p++) {
+            require_own_vec(who, a[p], party_ctxs[p], r_t[0]->n, "a factor of parties 0..2 * degree");
+            require_own_vec(who, b[p], party_ctxs[p], r_t[0]->n, "a factor of parties 0..2 * degree");
+            require_own_vec(who, r_2t[p], party_ctxs[p], r_t[0]->n, "the second half of the pair of parties 0..2 * degree");
+        }
+    });
+    if (rc != COZK_OK) return rc;
+    return king_drive(party_ctxs, r_t, r_t[0]->n, 0, degree, num_parties, king, out,
+                      [&](int p, fe* dst) { launch_mul_add(party_ctxs[p]->stream, a[p], b[p], r_2t[p], dst); });
 }
 
 int cozk_shamir_mul_king_vec(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b, const cozk_vec* r_t, const cozk_vec* r_2t, int degree, int king,
@@ -1206,106 +1216,48 @@ int cozk_shamir_mul_king_vec(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* b
     return rc;
 }
 
-}  // extern "C"
-
-// ------------------------------------------------------------------ the king multiplication of one interleaved GKR layer
-// (a tree level of the king grand product).  The halves of a pair are addressed by an element offset, so that one preprocessed
-// pair serves many levels; the king's open and the unmasks of its device are one launch (k_shamir_king_finish).
-static void launch_mask_pairs(hipStream_t st, const cozk_vec* v, const cozk_vec* r_2t, size_t off, fe* out) {
-    const size_t m = v->n / 2;
-    if (m == 0) return;
-    k_shamir_mask_pairs<<<(unsigned)((m + 255) / 256), 256, 0, st>>>((const fe*)v->d, (const fe*)r_2t->d + off, out, m);
-    HIP_TRY(hipGetLastError());
-}
-
-// z = sum_{j < k} lambda_j m[j], lambda = lagrange(1..k); out[q] = z - (rt[q] + off) for q < count; z_out may be null
-static void launch_king_finish(hipStream_t st, const fe* const* m, int k, const fe* const* rt, size_t off, int count, fe* const* out, fe* z_out, size_t n) {
-    if (n == 0) return;
-    ShamirKingFinishArgs a;
-    memset(&a, 0, sizeof a);
-    uint32_t points[COZK_SHAMIR_MAX_PARTIES];
-    for (int j = 0; j < k; j++) points[j] = (uint32_t)j + 1;
-    lagrange_host(points, (size_t)k, a.lambda);
-    for (int j = 0; j < k; j++) a.m[j] = m[j];
-    for (int q = 0; q < count; q++) {
-        a.rt[q] = rt[q] + off;
-        a.out[q] = out[q];
-    }
-    k_shamir_king_finish<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(a, k, count, z_out, n);
-    HIP_TRY(hipGetLastError());
-}
-
-// off + len <= have without overflow
-static bool slice_fits(size_t off, size_t len, size_t have) { return off <= have && len <= have - off; }
-
-extern "C" {
-
 int cozk_shamir_mul_mask_pairs(cozk_ctx* ctx, const cozk_vec* v, const cozk_vec* r_2t, size_t r_offset, cozk_vec** out) {
-    if (int rc0 = require_out(ctx, out, "shamir_mul_mask_pairs: null output")) return rc0;
-    *out = nullptr;
-    int rc = cozk_guard(ctx, [&] {
-        COZK_REQUIRE(ctx && v && r_2t, "shamir_mul_mask_pairs: null argument");
-        require_pairs("shamir_mul_mask_pairs", v);
-        COZK_REQUIRE(r_2t->kind == COZK_SCALAR_FR, "shamir_mul_mask_pairs: the mask must be an FR vector");
-        COZK_REQUIRE(slice_fits(r_offset, v->n / 2, r_2t->n), "shamir_mul_mask_pairs: r_offset + len(v) / 2 <= len(r_2t)");
-    });
-    if (rc != COZK_OK) return rc;
-    rc = cozk_vec_alloc(ctx, v->n / 2, COZK_SCALAR_FR, out);
-    if (rc != COZK_OK) return rc;
-    rc = cozk_guard(ctx, [&] { launch_mask_pairs(ctx->stream, v, r_2t, r_offset, (fe*)(*out)->d); });
-    if (rc != COZK_OK) {
-        cozk_vec_free(*out);
-        *out = nullptr;
-    }
-    return rc;
+    return entry_point(
+        ctx, "shamir_mul_mask_pairs: null output", {{out, 1}},
+        [&] {
+            COZK_REQUIRE(ctx && v && r_2t, "shamir_mul_mask_pairs: null argument");
+            require_pairs("shamir_mul_mask_pairs", v);
+            COZK_REQUIRE(r_2t->kind == COZK_SCALAR_FR, "shamir_mul_mask_pairs: the mask must be an FR vector");
+            COZK_REQUIRE(slice_fits(r_offset, v->n / 2, r_2t->n), "shamir_mul_mask_pairs: r_offset + len(v) / 2 <= len(r_2t)");
+            return v->n / 2;
+        },
+        [&](size_t) { launch_mask_pairs(ctx->stream, v, r_2t, r_offset, (fe*)(*out)->d); });
 }
 
 int cozk_shamir_king_finish(cozk_ctx* ctx, const cozk_vec* const* masked, int degree, const cozk_vec* const* r_t, size_t r_offset, int count,
                             cozk_vec** out, cozk_vec** z_out) {
-    if (z_out) *z_out = nullptr;
-    if (int rc0 = require_out(ctx, out, "shamir_king_finish: null output")) return rc0;
-    clear_outputs(out, count);
     const int k = 2 * degree + 1;
-    int rc = cozk_guard(ctx, [&] {
-        COZK_REQUIRE(ctx && masked && r_t, "shamir_king_finish: null argument");
-        COZK_REQUIRE(degree >= 1 && degree <= COZK_SHAMIR_MAX_DEGREE, "shamir_king_finish: 1 <= degree <= COZK_SHAMIR_MAX_DEGREE (2 * degree + 1 masked vectors)");
-        COZK_REQUIRE(count >= 1 && count <= COZK_SHAMIR_MAX_PARTIES, "shamir_king_finish: 1 <= count <= COZK_SHAMIR_MAX_PARTIES");
-        for (int j = 0; j < k; j++) {
-            COZK_REQUIRE(masked[j] && masked[j]->kind == COZK_SCALAR_FR, "shamir_king_finish: 2 * degree + 1 masked FR vectors");
-            COZK_REQUIRE(masked[j]->n == masked[0]->n, "shamir_king_finish: the masked vectors must have one length");
-        }
-        for (int q = 0; q < count; q++) {
-            COZK_REQUIRE(r_t[q] && r_t[q]->kind == COZK_SCALAR_FR, "shamir_king_finish: count FR first halves of the pair");
-            COZK_REQUIRE(slice_fits(r_offset, masked[0]->n, r_t[q]->n), "shamir_king_finish: r_offset + len(masked) <= len(r_t)");
-        }
-    });
-    if (rc != COZK_OK) return rc;
-    const size_t n = masked[0]->n;
-    rc = alloc_outputs(ctx, nullptr, n, count, out);
-    if (rc != COZK_OK) return rc;
-    if (z_out && (rc = cozk_vec_alloc(ctx, n, COZK_SCALAR_FR, z_out)) != COZK_OK) {
-        *z_out = nullptr;
-        free_all(out, count);
-        return rc;
-    }
-    rc = cozk_guard(ctx, [&] {
-        const fe *m[COZK_SHAMIR_MAX_PARTIES], *rt[COZK_SHAMIR_MAX_PARTIES];
-        fe* o[COZK_SHAMIR_MAX_PARTIES];
-        for (int j = 0; j < k; j++) m[j] = (const fe*)masked[j]->d;
-        for (int q = 0; q < count; q++) {
-            rt[q] = (const fe*)r_t[q]->d;
-            o[q] = (fe*)out[q]->d;
-        }
-        launch_king_finish(ctx->stream, m, k, rt, r_offset, count, o, z_out ? (fe*)(*z_out)->d : nullptr, n);
-    });
-    if (rc != COZK_OK) {
-        free_all(out, count);
-        if (z_out) {
-            cozk_vec_free(*z_out);
-            *z_out = nullptr;
-        }
-    }
-    return rc;
+    return entry_point(
+        ctx, "shamir_king_finish: null output", {{out, count}, {z_out, 1, true}},
+        [&] {
+            COZK_REQUIRE(ctx && masked && r_t, "shamir_king_finish: null argument");
+            COZK_REQUIRE(degree >= 1 && degree <= COZK_SHAMIR_MAX_DEGREE, "shamir_king_finish: 1 <= degree <= COZK_SHAMIR_MAX_DEGREE (2 * degree + 1 masked vectors)");
+            COZK_REQUIRE(count >= 1 && count <= COZK_SHAMIR_MAX_PARTIES, "shamir_king_finish: 1 <= count <= COZK_SHAMIR_MAX_PARTIES");
+            for (int j = 0; j < k; j++) {
+                COZK_REQUIRE(masked[j] && masked[j]->kind == COZK_SCALAR_FR, "shamir_king_finish: 2 * degree + 1 masked FR vectors");
+                COZK_REQUIRE(masked[j]->n == masked[0]->n, "shamir_king_finish: the masked vectors must have one length");
+            }
+            for (int q = 0; q < count; q++) {
+                COZK_REQUIRE(r_t[q] && r_t[q]->kind == COZK_SCALAR_FR, "shamir_king_finish: count FR first halves of the pair");
+                COZK_REQUIRE(slice_fits(r_offset, masked[0]->n, r_t[q]->n), "shamir_king_finish: r_offset + len(masked) <= len(r_t)");
+            }
+            return masked[0]->n;
+        },
+        [&](size_t n) {
+            const fe *m[COZK_SHAMIR_MAX_PARTIES], *rt[COZK_SHAMIR_MAX_PARTIES];
+            fe* o[COZK_SHAMIR_MAX_PARTIES];
+            for (int j = 0; j < k; j++) m[j] = (const fe*)masked[j]->d;
+            for (int q = 0; q < count; q++) {
+                rt[q] = (const fe*)r_t[q]->d;
+                o[q] = (fe*)out[q]->d;
+            }
+            launch_king_finish(ctx->stream, m, k, rt, r_offset, count, o, z_out ? (fe*)(*z_out)->d : nullptr, n);
+        });
 }
 
 int cozk_shamir_mul_king_pairs_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* v, const cozk_vec* const* r_t, const cozk_vec* const* r_2t,
@@ -1313,7 +1265,6 @@ int cozk_shamir_mul_king_pairs_inproc(cozk_ctx* const* party_ctxs, const cozk_ve
     cozk_ctx* const c0 = party_ctxs && num_parties >= 1 ? party_ctxs[0] : nullptr;  // receives the error message
     if (int rc0 = require_out(c0, out, "shamir_mul_king_pairs_inproc: null output")) return rc0;
     clear_outputs(out, num_parties);
-    const int senders = 2 * degree + 1;
     const char* who = "shamir_mul_king_pairs_inproc";
     int rc = cozk_guard(c0, [&] {
         COZK_REQUIRE(party_ctxs && v && r_t && r_2t, "shamir_mul_king_pairs_inproc: null argument");
@@ -1322,115 +1273,19 @@ int cozk_shamir_mul_king_pairs_inproc(cozk_ctx* const* party_ctxs, const cozk_ve
         for (int p = 0; p < num_parties; p++) COZK_REQUIRE(party_ctxs[p], "shamir_mul_king_pairs_inproc: null party context");
         COZK_REQUIRE(v[0], "shamir_mul_king_pairs_inproc: parties 0..2 * degree need their layer");
         COZK_REQUIRE(r_t[0], "shamir_mul_king_pairs_inproc: null first half of the pair");
-        for (int p = 0; p < num_parties; p++) {
-            COZK_REQUIRE(r_t[p], "shamir_mul_king_pairs_inproc: null first half of the pair");
-            COZK_REQUIRE(r_t[p]->kind == COZK_SCALAR_FR, "shamir_mul_king_pairs_inproc: the halves of the pair must be FR vectors");
-            COZK_REQUIRE(r_t[p]->n == r_t[0]->n, "shamir_mul_king_pairs_inproc: the halves of the pair must have one length");
-            COZK_REQUIRE(r_t[p]->ctx == party_ctxs[p], "shamir_mul_king_pairs_inproc: party p's halves of the pair must be vectors of party_ctxs[p]");
-        }
-        for (int p = 0; p < senders; p++) {
-            COZK_REQUIRE(v[p], "shamir_mul_king_pairs_inproc: parties 0..2 * degree need their layer");
-            require_pairs(who, v[p]);
-            COZK_REQUIRE(v[p]->n == v[0]->n, "shamir_mul_king_pairs_inproc: the layers must have one length");
-            COZK_REQUIRE(v[p]->ctx == party_ctxs[p], "shamir_mul_king_pairs_inproc: party p's layer must be a vector of party_ctxs[p]");
-            COZK_REQUIRE(r_2t[p], "shamir_mul_king_pairs_inproc: parties 0..2 * degree need the second half of the pair");
-            COZK_REQUIRE(r_2t[p]->kind == COZK_SCALAR_FR, "shamir_mul_king_pairs_inproc: the halves of the pair must be FR vectors");
-            COZK_REQUIRE(r_2t[p]->n == r_t[0]->n, "shamir_mul_king_pairs_inproc: the halves of the pair must have one length");
-            COZK_REQUIRE(r_2t[p]->ctx == party_ctxs[p], "shamir_mul_king_pairs_inproc: party p's halves of the pair must be vectors of party_ctxs[p]");
+        OwnVecTexts half = {"null first half of the pair", "the halves of the pair must be FR vectors", "", "the halves of the pair must have one length",
+                            "party p's halves of the pair must be vectors of party_ctxs[p]"};
+        for (int p = 0; p < num_parties; p++) require_own_vec(who, r_t[p], party_ctxs[p], r_t[0]->n, half);
+        half.null = "parties 0..2 * degree need the second half of the pair";
+        for (int p = 0; p < 2 * degree + 1; p++) {
+            require_own_vec(who, v[p], party_ctxs[p], v[0]->n, LAYER_TEXTS);
+            require_own_vec(who, r_2t[p], party_ctxs[p], r_t[0]->n, half);
         }
         COZK_REQUIRE(slice_fits(r_offset, v[0]->n / 2, r_t[0]->n), "shamir_mul_king_pairs_inproc: r_offset + len(v) / 2 <= len of the halves of the pair");
     });
     if (rc != COZK_OK) return rc;
-    const size_t n = v[0]->n / 2;
-    cozk_ctx* const kc = party_ctxs[king];
-    cozk_vec* m[COZK_SHAMIR_MAX_PARTIES] = {};   // m[p] = v_p[2j] v_p[2j + 1] + r2t_p[off + j], a block of the king
-    fe* stage[COZK_SHAMIR_MAX_PARTIES] = {};     // the same on a sender's other device
-    cozk_vec* zq[COZK_SHAMIR_MAX_PARTIES] = {};  // z on a party's other device, a block of that party
-    cozk_vec* z = nullptr;                       // z on the king's device: only where some party lives on another
-    auto fail = [&](int code, int p) {
-        if (party_ctxs[p] != c0) c0->last_error = party_ctxs[p]->last_error;
-        for (int q = 0; q < num_parties; q++) (void)hipStreamSynchronize(party_ctxs[q]->stream);
-        for (int s = 0; s < senders; s++) ctx_dev_free(party_ctxs[s], stage[s]);
-        free_all(m, senders);
-        free_all(zq, num_parties);
-        cozk_vec_free(z);
-        free_all(out, num_parties);
-        return code;
-    };
-    bool any_remote = false;
-    for (int p = 0; p < senders; p++)
-        if ((rc = cozk_vec_alloc(kc, n, COZK_SCALAR_FR, &m[p])) != COZK_OK) return fail(rc, king);
-    for (int q = 0; q < num_parties; q++) {
-        if (party_ctxs[q]->device != kc->device) {
-            any_remote = true;
-            if ((rc = cozk_vec_alloc(party_ctxs[q], n, COZK_SCALAR_FR, &zq[q])) != COZK_OK) return fail(rc, q);
-        }
-        if ((rc = cozk_vec_alloc(party_ctxs[q], n, COZK_SCALAR_FR, &out[q])) != COZK_OK) {
-            out[q] = nullptr;
-            return fail(rc, q);
-        }
-    }
-    if (any_remote && (rc = cozk_vec_alloc(kc, n, COZK_SCALAR_FR, &z)) != COZK_OK) return fail(rc, king);
-    if (n == 0) {
-        free_all(m, senders);
-        free_all(zq, num_parties);
-        cozk_vec_free(z);
-        return COZK_OK;
-    }
-    // the king's blocks are ordered by the king's stream only, the recipients' by theirs (see cozk_shamir_scatter): every party's
-    // stream drains before a sender's stream writes into the king's blocks and before the king's stream writes into a recipient's
-    rc = cozk_guard(c0, [&] {
-        for (int q = 0; q < num_parties; q++) HIP_TRY(hipStreamSynchronize(party_ctxs[q]->stream));
-    });
-    if (rc != COZK_OK) return fail(rc, 0);
-    for (int p = 0; p < senders; p++) {  // the mask on each sender's own stream, into the king's memory
-        cozk_ctx* sc = party_ctxs[p];
-        rc = cozk_guard(sc, [&] {
-            const bool remote = sc->device != kc->device;
-            if (remote) stage[p] = (fe*)ctx_dev_alloc(sc, n * sizeof(fe));
-            launch_mask_pairs(sc->stream, v[p], r_2t[p], r_offset, remote ? stage[p] : (fe*)m[p]->d);
-            if (remote) HIP_TRY(hipMemcpyPeerAsync(m[p]->d, kc->device, stage[p], sc->device, n * sizeof(fe), sc->stream));
-        });
-        if (rc != COZK_OK) return fail(rc, p);
-    }
-    for (int p = 0; p < senders; p++) {  // the king may read the masked products once the senders' streams have drained
-        rc = cozk_guard(party_ctxs[p], [&] {
-            HIP_TRY(hipStreamSynchronize(party_ctxs[p]->stream));
-            ctx_dev_free(party_ctxs[p], stage[p]);
-            stage[p] = nullptr;
-        });
-        if (rc != COZK_OK) return fail(rc, p);
-    }
-    rc = cozk_guard(kc, [&] {  // ONE launch on the king's stream: the open, and c_q = z - rt_q for every party of the king's device
-        const fe *mp[COZK_SHAMIR_MAX_PARTIES], *rt[COZK_SHAMIR_MAX_PARTIES];
-        fe* o[COZK_SHAMIR_MAX_PARTIES];
-        int count = 0;
-        for (int p = 0; p < senders; p++) mp[p] = (const fe*)m[p]->d;
-        for (int q = 0; q < num_parties; q++)
-            if (!zq[q]) {
-                rt[count] = (const fe*)r_t[q]->d;
-                o[count++] = (fe*)out[q]->d;
-            }
-        launch_king_finish(kc->stream, mp, senders, rt, r_offset, count, o, z ? (fe*)z->d : nullptr, n);
-        for (int q = 0; q < num_parties; q++)  // z to the other devices by the king's stream
-            if (zq[q]) HIP_TRY(hipMemcpyPeerAsync(zq[q]->d, party_ctxs[q]->device, z->d, kc->device, n * sizeof(fe), kc->stream));
-        HIP_TRY(hipStreamSynchronize(kc->stream));  // the recipients' streams may use their blocks as soon as this returns
-    });
-    if (rc != COZK_OK) return fail(rc, king);
-    free_all(m, senders);
-    cozk_vec_free(z);
-    z = nullptr;
-    for (int q = 0; q < num_parties; q++) {  // a party of another device subtracts at the offset on its own stream: the same kernel, k = 1
-        if (!zq[q]) continue;
-        rc = cozk_guard(party_ctxs[q], [&] {
-            const fe *mp[1] = {(const fe*)zq[q]->d}, *rt[1] = {(const fe*)r_t[q]->d};
-            fe* o[1] = {(fe*)out[q]->d};
-            launch_king_finish(party_ctxs[q]->stream, mp, 1, rt, r_offset, 1, o, nullptr, n);  // lagrange(1) = 1
-        });
-        if (rc != COZK_OK) return fail(rc, q);
-    }
-    free_all(zq, num_parties);  // each behind its reader on its owner's stream
-    return COZK_OK;
+    return king_drive(party_ctxs, r_t, v[0]->n / 2, r_offset, degree, num_parties, king, out,
+                      [&](int p, fe* dst) { launch_mask_pairs(party_ctxs[p]->stream, v[p], r_2t[p], r_offset, dst); });
 }
 
 int cozk_vec_add_scalar(cozk_ctx* ctx, cozk_vec* v, const uint64_t s[4]) {

@@ -231,6 +231,38 @@ def test_rand_and_mul_king_inproc(cozk, ctx, party_ctxs, parties, degree, n, kin
             assert _ints(same) == got_ints
 
 
+@pytest.mark.parametrize("king_at", ["0", "n-1"])
+@pytest.mark.parametrize("n", [1, 255, 257])
+@pytest.mark.parametrize("parties,degree", [(3, 1), (8, 2)])
+def test_mul_king_inproc_equals_the_pairs_call_at_offset_zero(cozk, party_ctxs, parties, degree, n, king_at):
+    """cozk_shamir_mul_king_inproc(a, b, ..) and cozk_shamir_mul_king_pairs_inproc(v, .., r_offset = 0) with v[2j] = a[j],
+    v[2j + 1] = b[j] run one king driver and finish with one k_shamir_king_finish launch: equal raw words for every party, and the
+    restatement's.  Both are element-wise in the parties' vectors, which therefore need not be sharings: where the length allows,
+    the factors begin with all 144 pairs of the edge operands, the second factor's rotated by the party.  n - 1 is above 2t at (8, 2)"""
+    king = 0 if king_at == "0" else parties - 1
+    pcs, k = party_ctxs[:parties], D.senders(degree)
+    edge = EDGE + EDGE_MONT
+    ex, ey = [x for x in edge for _ in edge], [y for _ in edge for y in edge]
+    lead = lambda blk, p: (blk[p:] + blk[:p]) if n >= len(blk) else []
+    a = [(lead(ex, 0) + O.synthetic_fr(310 + p, n))[:n] for p in range(k)]
+    b = [(lead(ey, p) + O.synthetic_fr(320 + p, n))[:n] for p in range(k)]
+    v = [[z for xy in zip(a[p], b[p]) for z in xy] for p in range(k)]
+    rt = [([0, R - 1][q % 2:] + O.synthetic_fr(330 + q, n))[:n] for q in range(parties)]
+    r2t = [([R - 1, 0][p % 2:] + O.synthetic_fr(340 + p, n))[:n] for p in range(k)]
+    up = lambda vs: [cozk.Vec.from_ints(pcs[p], x) for p, x in enumerate(vs)] + [None] * (parties - len(vs))  # nothing above 2t
+    A, B, V, RT, R2T = up(a), up(b), up(v), up(rt), up(r2t)
+    plain = cozk.shamir_mul_king(pcs, A, B, RT, R2T, degree, king=king)
+    pairs = cozk.shamir_mul_king_pairs(pcs, V, RT, R2T, degree, r_offset=0, king=king)
+    want = D.mul_king(a + [None] * (parties - k), b + [None] * (parties - k), rt, r2t + [None] * (parties - k), degree, king=king)
+    for q in range(parties):
+        assert plain[q].ctx is pcs[q] and pairs[q].ctx is pcs[q] and len(plain[q]) == len(pairs[q]) == n
+        raw = plain[q].to_numpy()
+        assert np.array_equal(raw, pairs[q].to_numpy()), "party %d" % q  # raw Montgomery limbs
+        _assert_canonical(raw)
+    assert _ints(plain) == want and _ints(pairs) == want
+    assert _ints(A[:k]) == a and _ints(B[:k]) == b and _ints(V[:k]) == v and _ints(RT) == rt and _ints(R2T[:k]) == r2t  # only read
+
+
 def test_rand_and_mul_king_inproc_empty(cozk, ctx, party_ctxs):
     pcs = party_ctxs[:5]
     pairs = cozk.shamir_rand(pcs, D.party_keys(1, 5, 2), 0, 2)
