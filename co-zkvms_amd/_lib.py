@@ -16,6 +16,7 @@ ERR_NO_DEVICE = -5
 SCALAR_FR, SCALAR_U8, SCALAR_U16, SCALAR_U32, SCALAR_U64, SCALAR_I64 = range(6)
 LOW_TO_HIGH, HIGH_TO_LOW = 0, 1
 MODE_PLAIN, MODE_REP3 = 1, 2
+LAYER_GROUP_MAX = 32
 OP_ADD, OP_SUB, OP_MUL = 0, 1, 2
 
 
@@ -136,6 +137,7 @@ SIGNATURES = {
     "cozk_shamir_gp_prove_inproc": (_i, [_vp, _vp, _sz, _vp, _vp, _i, _i, _u64, _u64, ctypes.c_char_p, _i, _pp]),
     "cozk_shamir_gp_free": (_i, [_vp]),
     "cozk_shamir_gp_get_result": (_i, [_vp, _vp]),
+    "cozk_shamir_gp_get_stats": (_i, [_vp, _vp]),
     "cozk_shamir_gp_proof_bytes": (_i, [_vp, _vp, _sz]),
     "cozk_shamir_gp_point_len": (_sz, [_vp]),
     "cozk_shamir_gp_final": (_i, [_vp, _vp, _vp]),
@@ -163,6 +165,10 @@ SIGNATURES = {
     "cozk_fingerprint_leaves": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _i, _i, _vp, _vp, _sz, _sz]),
     "cozk_layer_prove_rounds": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "cozk_layer_final_claims": (_i, [_vp, _vp, _vp]),
+    "cozk_layer_group_create": (_i, [_vp, _vp, _i, _pp]),
+    "cozk_layer_group_round": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "cozk_layer_group_final": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "cozk_layer_group_free": (_i, [_vp]),
     "cozk_layer_output_local": (_i, [_vp, _vp, _i, ctypes.c_char_p, ctypes.c_char_p, _u64, _pp]),
     "cozk_rep3_mul_vec_local": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, ctypes.c_char_p, ctypes.c_char_p, _u64, _pp]),
     "cozk_layer_claimed_outputs": (_i, [_vp, _vp, _vp]),

@@ -19,6 +19,9 @@
 //               from parties 0..t with lagrange(1..t + 1), unmasked
 //   transcript  and proof layout: exactly coordinate_prove_grand_product / coordinate_prove_layer (prover.hpp)
 // Parties above 2t take part in the construction (they receive their shares of every level) and send nothing afterwards.
+// The senders' layers of one tree level share the public eq polynomial, the challenge and the claim: when their contexts are on one
+// device a layer's sumcheck runs as ONE layer group (cozk_layer_group_round / _final, poly.hip) with ONE eq on sender 0's context --
+// one launch and one fetch per round for all senders; otherwise sender by sender (shamir_gp_grouped).  Same bytes either way.
 //
 // The king variant (cozk_shamir_gp_prep_inproc + cozk_shamir_gp_prove_king_inproc; tests/shamir_gp_king_ref.py) moves everything
 // that needs fresh randomness before the witness: the masks above and two double-random pairs of n_leaves / 2 elements are dealt
@@ -41,6 +44,7 @@ struct cozk_shamir_gp {
     std::vector<fe> msgs;    // [m][p]: opening m, sender p <= 2t
     std::vector<fe> finals;  // [layer, top first][p <= t][L, R]
     cozk_shamir_gp_result res;
+    cozk_shamir_gp_stats stats{};
 };
 
 namespace cozk {
@@ -72,6 +76,20 @@ struct ShamirGpArgs {
 
 static inline void shamir_gp_sync_all(const ShamirGpArgs& a) {
     for (int p = 0; p < a.n; p++) rc_check(cozk_ctx_synchronize(a.pcs[p]), a.pcs[p], "ctx_synchronize");
+}
+
+typedef Handle<cozk_layer_group, cozk_layer_group_free> GroupH;
+
+// Whether the rounds run as layer groups (cozk_layer_group_*): one launch per round for all senders instead of one per sender, one
+// fold of the public eq tables instead of 2t + 1.  That needs every sender's context on ONE device (one group per device for
+// senders spread over several is not built).  COZK_SHAMIR_GP_GROUP=0: the per-sender loop, for A/B runs; read on every call, as
+// COZK_SUM_GRID_MAX is, so that one process can compare both.
+static inline bool shamir_gp_grouped(const ShamirGpArgs& a) {
+    const char* e = getenv("COZK_SHAMIR_GP_GROUP");
+    if (e && atoi(e) == 0) return false;
+    for (int p = 1; p <= 2 * a.t; p++)
+        if (a.pcs[p]->device != a.pcs[0]->device) return false;
+    return true;
 }
 
 // M = batch_size + 4 sum_layers rounds(layer): the openings of degree 2t of one proof
@@ -146,6 +164,7 @@ static void shamir_gp_prove_layers(const ShamirGpArgs& a, std::vector<std::vecto
     const int num_layers = (int)layers.size();
     const size_t M = zero[0].size();
     const std::vector<fe> lam2t = shamir_lagrange_first(senders), lamt = shamir_lagrange_first(openers);
+    const bool grouped = shamir_gp_grouped(a);
 
     // the openings of degree 2t: local[p] = sender p's unmasked value of opening m
     size_t m_next = 0;
@@ -176,19 +195,34 @@ static void shamir_gp_prove_layers(const ShamirGpArgs& a, std::vector<std::vecto
     for (int i = num_layers; i-- > 0;) {
         GrandProductLayerProof lp;
         const int num_rounds = (int)r.size();
-        std::vector<EqH> eqs((size_t)senders);
         std::vector<uint64_t> w = to_abi(r);
-        for (int p = 0; p < senders; p++) rc_check(cozk_spliteq_new(a.pcs[p], w.data(), num_rounds, &eqs[(size_t)p].h), a.pcs[p], "spliteq_new");
+        // grouped: ONE eq on sender 0's context and one group over the senders' layers; otherwise an eq per sender
+        std::vector<EqH> eqs((size_t)(grouped ? 1 : senders));
+        for (size_t p = 0; p < eqs.size(); p++) rc_check(cozk_spliteq_new(a.pcs[p], w.data(), num_rounds, &eqs[p].h), a.pcs[p], "spliteq_new");
+        GroupH group;
+        if (grouped) {
+            cozk_layer* members[COZK_SHAMIR_MAX_PARTIES];
+            for (int p = 0; p < senders; p++) members[p] = layers[(size_t)i][(size_t)p].h;
+            rc_check(cozk_layer_group_create(a.pcs[0], members, senders, &group.h), a.pcs[0], "layer_group_create");
+        }
         std::vector<fe> r_sumcheck;
         uint64_t rj[4], pc[4];
+        std::vector<uint64_t> co((size_t)16 * senders);
         for (int j = 0; j < num_rounds; j++) {
             fe_to_u64x4(claim, pc);  // every party's prev_claim is the public claim
             fe cf[4][COZK_SHAMIR_MAX_PARTIES];
-            for (int p = 0; p < senders; p++) {
-                uint64_t co[16];
-                rc_check(cozk_layer_round(a.pcs[p], layers[(size_t)i][(size_t)p].h, eqs[(size_t)p].h, j ? rj : nullptr, pc, co), a.pcs[p], "layer_round");
-                for (int k = 0; k < 4; k++) cf[k][p] = fe_from_u64x4(co + 4 * k);
+            if (grouped) {
+                rc_check(cozk_layer_group_round(group.h, eqs[0].h, j ? rj : nullptr, pc, co.data()), a.pcs[0], "layer_group_round");
+                h.stats.group_rounds++;
+            } else {
+                for (int p = 0; p < senders; p++) {
+                    rc_check(cozk_layer_round(a.pcs[p], layers[(size_t)i][(size_t)p].h, eqs[(size_t)p].h, j ? rj : nullptr, pc, co.data() + 16 * p), a.pcs[p],
+                             "layer_round");
+                    h.stats.single_rounds++;
+                }
             }
+            for (int p = 0; p < senders; p++)
+                for (int k = 0; k < 4; k++) cf[k][p] = fe_from_u64x4(co.data() + 16 * p + 4 * k);
             std::vector<fe> poly(4);
             for (int k = 0; k < 4; k++) poly[(size_t)k] = open_2t(cf[k]);
             std::vector<fe> comp = unipoly_compress(poly);
@@ -200,13 +234,21 @@ static void shamir_gp_prove_layers(const ShamirGpArgs& a, std::vector<std::vecto
             lp.proof.compressed_polys.push_back(comp);
         }
         fe fl[COZK_SHAMIR_MAX_PARTIES], fr[COZK_SHAMIR_MAX_PARTIES];
-        for (int p = 0; p < openers; p++) {  // the last bind and the final claims: the t + 1 openers only
-            cozk_layer* l = layers[(size_t)i][(size_t)p].h;
-            if (num_rounds) rc_check(cozk_layer_bind(a.pcs[p], l, rj), a.pcs[p], "layer_bind");
-            uint64_t fc[16];
-            rc_check(cozk_layer_final_claims(a.pcs[p], l, fc), a.pcs[p], "layer_final_claims");
-            fl[p] = fe_from_u64x4(fc);
-            fr[p] = fe_from_u64x4(fc + 8);
+        std::vector<uint64_t> fc((size_t)16 * openers);
+        if (grouped) {  // the last bind and the final claims: the t + 1 openers only
+            rc_check(cozk_layer_group_final(group.h, eqs[0].h, num_rounds ? rj : nullptr, openers, fc.data()), a.pcs[0], "layer_group_final");
+            h.stats.group_finals++;
+        } else {
+            for (int p = 0; p < openers; p++) {
+                cozk_layer* l = layers[(size_t)i][(size_t)p].h;
+                if (num_rounds) rc_check(cozk_layer_bind(a.pcs[p], l, rj), a.pcs[p], "layer_bind");
+                rc_check(cozk_layer_final_claims(a.pcs[p], l, fc.data() + 16 * p), a.pcs[p], "layer_final_claims");
+                h.stats.single_finals++;
+            }
+        }
+        for (int p = 0; p < openers; p++) {
+            fl[p] = fe_from_u64x4(fc.data() + 16 * p);
+            fr[p] = fe_from_u64x4(fc.data() + 16 * p + 8);
             h.finals.push_back(fl[p]);
             h.finals.push_back(fr[p]);
         }
@@ -456,6 +498,12 @@ int cozk_shamir_gp_free(cozk_shamir_gp* h) {
 int cozk_shamir_gp_get_result(const cozk_shamir_gp* h, cozk_shamir_gp_result* res) {
     if (!h || !res) return COZK_ERR_INVALID_ARG;
     *res = h->res;
+    return COZK_OK;
+}
+
+int cozk_shamir_gp_get_stats(const cozk_shamir_gp* h, cozk_shamir_gp_stats* stats) {
+    if (!h || !stats) return COZK_ERR_INVALID_ARG;
+    *stats = h->stats;
     return COZK_OK;
 }
 

@@ -839,6 +839,106 @@ __global__ void __launch_bounds__(RT) k_layer_round_small(const fe* __restrict__
     if (threadIdx.x == 0) fe_store(res + 2, s3);
 }
 
+// ------------------------------------------------------------------ layer groups (cozk_layer_group_*)
+// The same round for k SMALL layers of one length that share the public eq tables, the challenge and the claim (the senders of a
+// Shamir prover): ONE launch of k workgroups, workgroup m serving member m.  The members' pointers travel in the kernel arguments,
+// four tables of COZK_LAYER_GROUP_MAX pointers (1 KiB) indexed by the wave-uniform blockIdx.x as ShamirExtractArgs' are: scalar
+// loads, nothing staged.  Bind, barrier, sums and tails (sh_load_or_zero, the shorter side of layer and eq) are those of
+// k_layer_round_small; member m's sums go to res[3 m .. 3 m + 2] of the pinned result slot.  The eq fold is NOT in here: workgroups
+// cannot wait for each other, and a fold that all of them wrote would race with the ones that read it.  The caller folds the tables
+// once per round with the cozk_spliteq_bind launches in front of this one on the same stream (no host wait in between).
+struct LayerGroupArgs {
+    const fe* ia[COZK_LAYER_GROUP_MAX];
+    const fe* ib[COZK_LAYER_GROUP_MAX];
+    fe* oa[COZK_LAYER_GROUP_MAX];
+    fe* ob[COZK_LAYER_GROUP_MAX];
+};
+template <int NC>
+__global__ void __launch_bounds__(RT) k_layer_group_round_small(LayerGroupArgs a, size_t len_in, int do_bind, fe r, size_t len, const fe* E1, size_t E1_half,
+                                                             const fe* E2, size_t E2_len, int nested, fe* __restrict__ res) {
+    // len_in <= ROUND_SMALL_MAX = 2 RT: at most RT / 2 chunks, so a lane owns at most ONE chunk of the bind and ONE of the sums: no
+    // grid-stride loop, no accumulator.  With 1024 lanes a wave has 128 registers and k_layer_round_small's unrolled body spills
+    // (232 / 760 bytes per lane); here the two halves of the bind and the three points of the sums are ROLLED loops, so that one
+    // lerp or one point's products are in the register file at a time, each sum is reduced as soon as its term exists, and nothing
+    // but pointers lives across a barrier -- a point reloads its chunk and its eq pair, a few cache-resident kilobytes.
+    __shared__ fe sh16[16];
+    const unsigned m = blockIdx.x;
+    const size_t c = threadIdx.x;
+    const fe *ca = a.ia[m], *cb = a.ib[m];  // without a bind the sums read the member as it is
+    if (do_bind) {
+        const fe *ia = a.ia[m], *ib = a.ib[m];
+        fe *oa = a.oa[m], *ob = a.ob[m];
+        if (c < (len_in + 3) / 4) {
+#pragma unroll 1
+            for (int h = 0; h < 2; h++) {
+                const Sh<NC> lo = sh_load_or_zero<NC>(ia, ib, 4 * c + h, len_in), hi = sh_load_or_zero<NC>(ia, ib, 4 * c + 2 + h, len_in);
+                sh_store<NC>(oa, ob, 2 * c + h, sh_lerp<NC>(lo, hi, r));
+            }
+        }
+        __syncthreads();
+        ca = oa;
+        cb = ob;
+    }
+    size_t nch = (len + 3) / 4;
+    size_t limit = nested ? E1_half * E2_len : E2_len / 2;
+    if (nch > limit) nch = limit;  // zip() stops at the shorter side
+    const bool on = c < nch;
+    // The terms of k_layer_round_small, (L(X) x R(X)) eq(X) [E2[x2]] at X = 0, 2, 3, with the E2 factor multiplied into eq(X) first:
+    // the same field elements, and every stored result is canonical, so the bytes are the same.  The lane's eq pair, and (nested)
+    // the E2 entry that multiplies it:
+    const fe* ep = E2 + 2 * c;
+    const fe* sp = nullptr;
+    if (nested) {
+        ep = E1 + 2 * (c & (E1_half - 1));               // E1_half is a power of two
+        sp = E2 + (c >> (__ffsll((long long)E1_half) - 1));
+    }
+    // side(s, X): L (s = 0) or R (s = 1) of the lane's chunk at X, from its two elements
+    auto side = [&](int s, int X) {
+        const Sh<NC> v0 = sh_load_or_zero<NC>(ca, cb, 4 * c + s, len), v1 = sh_load_or_zero<NC>(ca, cb, 4 * c + 2 + s, len);
+        if (X == 0) return v0;
+        const Sh<NC> d = sh_sub<NC>(v1, v0);
+        Sh<NC> v = sh_add<NC>(v1, d);
+        if (X == 3) v = sh_add<NC>(v, d);
+        return v;
+    };
+#pragma unroll 1
+    for (int p = 0; p < 3; p++) {  // X = 0, 2, 3; rolled: one point's products at a time in the register file
+        const int X = p ? p + 1 : 0;
+        fe t = Fr::zero();
+        if (on) {
+            fe e = fe_load(ep);
+            if (X) {
+                const fe e1 = fe_load(ep + 1), d = Fr::sub(e1, e);
+                e = Fr::add(e1, d);
+                if (X == 3) e = Fr::add(e, d);
+            }
+            if (nested) e = Fr::mul(e, fe_load(sp));
+            t = Fr::mul(sh_local_mul<NC>(side(0, X), side(1, X)), e);
+        }
+        t = fr_block_sum(t, sh16);
+        if (threadIdx.x == 0) fe_store(res + 3 * m + p, t);
+    }
+}
+
+// The last bind and the final claims of the first gridDim.x members in one launch: workgroup m (one wave, lanes 0 and 1 at work)
+// binds member m's <= 4 elements to its two claims L, R (k_layer_bind on one chunk), stores them as the member's bound layer and
+// writes them to res[(2 m + side) NC + component] of the pinned slot.  do_bind = 0: the member is already down to (L, R).
+static constexpr int GFT = 64;
+template <int NC>
+__global__ void __launch_bounds__(GFT) k_layer_group_final(LayerGroupArgs a, size_t len_in, int do_bind, fe r, fe* __restrict__ res) {
+    const unsigned m = blockIdx.x, j = threadIdx.x;
+    if (j >= 2) return;
+    const fe *ia = a.ia[m], *ib = a.ib[m];
+    Sh<NC> v;
+    if (do_bind) {
+        v = sh_lerp<NC>(sh_load_or_zero<NC>(ia, ib, j, len_in), sh_load_or_zero<NC>(ia, ib, j + 2, len_in), r);
+        sh_store<NC>(a.oa[m], a.ob[m], j, v);
+    } else {
+        v = sh_load<NC>(ia, ib, j);
+    }
+    for (int c = 0; c < NC; c++) fe_store(res + (size_t)(2 * m + j) * NC + c, v.c[c]);
+}
+
 // ------------------------------------------------------------------ persistent round kernel (host mailbox)
 // A launch-and-drain costs ~38 us on this platform however small the kernel (measured per round, 2^3 .. 2^19
 // elements alike), and a grand product has ~170 rounds on layers of <= 2048 elements.  For those tails ONE
@@ -2238,24 +2338,28 @@ int cozk_spliteq_lens(const cozk_spliteq* e, size_t* e1_len, size_t* e2_len) {
 }
 
 // SplitEqPolynomial::bind(r)
+static bool spliteq_bound(const cozk_spliteq* e) { return e->E1_len == 1 && e->E2_len < 2; }
+// the fold launches of one bind on ctx's stream (one, or two when E1 collapses); the caller has checked !spliteq_bound(e)
+static void spliteq_bind_launch(cozk_ctx* ctx, cozk_spliteq* e, const fe& rr) {
+    if (e->E1_len == 1) {
+        size_t n = e->E2_len / 2;
+        k_fold_pairs<<<grid_for(n), PT, 0, ctx->stream>>>(e->E2[e->c2], e->E2[1 - e->c2], n, rr);
+        e->c2 = 1 - e->c2;
+        e->E2_len = n;
+    } else {
+        size_t n = e->E1_len / 2;
+        k_fold_pairs<<<grid_for(n), PT, 0, ctx->stream>>>(e->E1[e->c1], e->E1[1 - e->c1], n, rr);
+        e->c1 = 1 - e->c1;
+        e->E1_len = n;
+        if (n == 1) k_scale_by_first<<<grid_for(e->E2_len), PT, 0, ctx->stream>>>(e->E2[e->c2], e->E2_len, e->E1[e->c1]);
+    }
+    HIP_TRY(hipGetLastError());
+}
 int cozk_spliteq_bind(cozk_ctx* ctx, cozk_spliteq* e, const uint64_t r[4]) {
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(ctx && e && r, "spliteq_bind: bad argument");
-        fe rr = fe_from_u64x4(r);
-        if (e->E1_len == 1) {
-            COZK_REQUIRE(e->E2_len >= 2, "spliteq_bind: polynomial already fully bound");
-            size_t n = e->E2_len / 2;
-            k_fold_pairs<<<grid_for(n), PT, 0, ctx->stream>>>(e->E2[e->c2], e->E2[1 - e->c2], n, rr);
-            e->c2 = 1 - e->c2;
-            e->E2_len = n;
-        } else {
-            size_t n = e->E1_len / 2;
-            k_fold_pairs<<<grid_for(n), PT, 0, ctx->stream>>>(e->E1[e->c1], e->E1[1 - e->c1], n, rr);
-            e->c1 = 1 - e->c1;
-            e->E1_len = n;
-            if (n == 1) k_scale_by_first<<<grid_for(e->E2_len), PT, 0, ctx->stream>>>(e->E2[e->c2], e->E2_len, e->E1[e->c1]);
-        }
-        HIP_TRY(hipGetLastError());
+        COZK_REQUIRE(!spliteq_bound(e), "spliteq_bind: polynomial already fully bound");
+        spliteq_bind_launch(ctx, e, fe_from_u64x4(r));
     });
 }
 
@@ -2300,15 +2404,71 @@ static unsigned layer_sum_grid(cozk_ctx* ctx, const void* kernel, bool f9, size_
 
 // Rep3BatchedCubicSumcheckWorker::compute_cubic (dense_interleaved_poly.rs:210-365): returns the 4
 // additive coefficient shares of the round polynomial through evals [g0, claim - g0, g2, g3]
-static void layer_cubic_sums(cozk_ctx* ctx, const cozk_layer* l, const cozk_spliteq* eq, fe s[3]) {
+// The launch half of a large layer's round sums, on ctx's stream (the layer's own context, or the driver of a layer group): the
+// kernel and its grid are chosen first (they depend on the mode, the length and the eq tables only, so the members of a group
+// share them), the caller reserves gx block partials for each of the three rows, and the launch writes the rows at `partial`,
+// `partial + gx`, `partial + 2 gx`.  The finish half is finish_sums over all the rows of the reservation.
+struct LayerCubicPlan {
+    LayerVariant v;
+    LayerCubicKernel kernel;
+    unsigned gx;
+};
+static LayerCubicPlan layer_cubic_plan(cozk_ctx* ctx, const cozk_layer* l, const cozk_spliteq* eq) {
     const size_t nch = (l->len + 3) / 4;
     const LayerVariant v = layer_variant(l, eq, nch);
     const LayerCubicKernel kernel = layer_cubic_kernel(l->mode, v);
-    const unsigned gx = layer_sum_grid(ctx, (const void*)kernel, v.f9, nch);
-    const SumLaunch sl = sum_launch(ctx, 3, gx, 3);
-    kernel<<<gx, PT, 0, ctx->stream>>>(l->buf[l->cur][0], l->buf[l->cur][1], l->len, eq->E1[eq->c1], v.nested ? eq->E1_len / 2 : 0, eq->E2[eq->c2],
-                                       eq->E2_len, sl.partial);
-    finish_sums(ctx, sl, 3, gx, Fr::one(), 0, s);
+    return LayerCubicPlan{v, kernel, layer_sum_grid(ctx, (const void*)kernel, v.f9, nch)};
+}
+static void layer_cubic_launch(cozk_ctx* ctx, const cozk_layer* l, const cozk_spliteq* eq, const LayerCubicPlan& p, fe* partial) {
+    p.kernel<<<p.gx, PT, 0, ctx->stream>>>(l->buf[l->cur][0], l->buf[l->cur][1], l->len, eq->E1[eq->c1], p.v.nested ? eq->E1_len / 2 : 0, eq->E2[eq->c2],
+                                           eq->E2_len, partial);
+}
+static void layer_cubic_sums(cozk_ctx* ctx, const cozk_layer* l, const cozk_spliteq* eq, fe s[3]) {
+    const LayerCubicPlan p = layer_cubic_plan(ctx, l, eq);
+    const SumLaunch sl = sum_launch(ctx, 3, p.gx, 3);
+    layer_cubic_launch(ctx, l, eq, p, sl.partial);
+    finish_sums(ctx, sl, 3, p.gx, Fr::one(), 0, s);
+}
+
+// The same two halves for bind + sums in one pass (eq tables already folded by the caller).  The launch makes the other ping-pong
+// side hold the bound layer -- from the pool of the LAYER's context, whichever context drives the launch -- and moves the layer on.
+struct LayerBindCubicPlan {
+    LayerVariant v;
+    LayerBindCubicKernel kernel;
+    unsigned gx;
+};
+static LayerBindCubicPlan layer_bind_cubic_plan(cozk_ctx* ctx, const cozk_layer* l, const cozk_spliteq* e) {
+    const size_t nout = 2 * ((l->len + 3) / 4), nch_out = (nout + 3) / 4;
+    const LayerVariant v = layer_variant(l, e, nch_out);
+    const LayerBindCubicKernel kernel = layer_bind_cubic_kernel(l->mode, v);
+    return LayerBindCubicPlan{v, kernel, layer_sum_grid(ctx, (const void*)kernel, v.f9, nch_out)};
+}
+// allocations made for `c`'s objects while another context's ABI call runs on this thread
+struct PoolOf {
+    cozk_ctx* prev;
+    explicit PoolOf(cozk_ctx* c) : prev(t_cur_ctx) { t_cur_ctx = c; }
+    ~PoolOf() { t_cur_ctx = prev; }
+};
+static void layer_bind_cubic_launch(cozk_ctx* ctx, cozk_layer* l, const cozk_spliteq* e, const LayerBindCubicPlan& p, const uint64_t r[4], fe* partial) {
+    const size_t nout = 2 * ((l->len + 3) / 4);
+    const int dst = 1 - l->cur;
+    {
+        PoolOf own(l->ctx);
+        pingpong_ensure(l, dst, nout);
+    }
+    fe rr = fe_from_u64x4(r);
+    if (p.v.f9)
+        for (int d = 0; d < 5; d++) rr = Fr::dbl(rr);  // the 9 x 29 kernels take the challenge times 2^5 = 1 / lambda (fr9.hip.hpp)
+    const bool rep3 = l->mode == COZK_MODE_REP3;
+    {
+        // algorithmic bytes: the layer read once and its bound half written once (SURVEY 8d K3 + K4 fused), + the eq tables
+        const uint64_t S = rep3 ? 64 : 32;
+        ProfScope prof(ctx, COZK_PROF_BIND_CUBIC, (uint64_t)l->len * S + (uint64_t)nout * S + (uint64_t)(e->E1_len + e->E2_len) * 32);
+        p.kernel<<<p.gx, PT, 0, ctx->stream>>>(l->buf[l->cur][0], rep3 ? l->buf[l->cur][1] : nullptr, l->buf[dst][0], rep3 ? l->buf[dst][1] : nullptr, l->len, rr,
+                                               e->E1[e->c1], p.v.nested ? e->E1_len / 2 : 0, e->E2[e->c2], e->E2_len, partial);
+    }
+    l->cur = dst;
+    l->len = nout;
 }
 
 int cozk_layer_compute_cubic(cozk_ctx* ctx, const cozk_layer* l, const cozk_spliteq* eq, const uint64_t prev_claim[4],
@@ -2333,28 +2493,11 @@ int cozk_layer_round(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const uint64
         int rc = cozk_spliteq_bind(ctx, e, r);
         if (rc != COZK_OK) return rc;
         return cozk_guard(ctx, [&] {
-            const size_t nout = 2 * ((l->len + 3) / 4), nch_out = (nout + 3) / 4;
-            const int dst = 1 - l->cur;
-            pingpong_ensure(l, dst, nout);
-            const LayerVariant v = layer_variant(l, e, nch_out);
-            const LayerBindCubicKernel kernel = layer_bind_cubic_kernel(l->mode, v);
-            const unsigned gx = layer_sum_grid(ctx, (const void*)kernel, v.f9, nch_out);
-            const SumLaunch sl = sum_launch(ctx, 3, gx, 3);
-            fe rr = fe_from_u64x4(r);
-            if (v.f9)
-                for (int d = 0; d < 5; d++) rr = Fr::dbl(rr);  // the 9 x 29 kernels take the challenge times 2^5 = 1 / lambda (fr9.hip.hpp)
-            const bool rep3 = l->mode == COZK_MODE_REP3;
-            {
-                // algorithmic bytes: the layer read once and its bound half written once (SURVEY 8d K3 + K4 fused), + the eq tables
-                const uint64_t S = rep3 ? 64 : 32;
-                ProfScope prof(ctx, COZK_PROF_BIND_CUBIC, (uint64_t)l->len * S + (uint64_t)nout * S + (uint64_t)(e->E1_len + e->E2_len) * 32);
-                kernel<<<gx, PT, 0, ctx->stream>>>(l->buf[l->cur][0], rep3 ? l->buf[l->cur][1] : nullptr, l->buf[dst][0], rep3 ? l->buf[dst][1] : nullptr, l->len, rr,
-                                                   e->E1[e->c1], v.nested ? e->E1_len / 2 : 0, e->E2[e->c2], e->E2_len, sl.partial);
-            }
+            const LayerBindCubicPlan p = layer_bind_cubic_plan(ctx, l, e);
+            const SumLaunch sl = sum_launch(ctx, 3, p.gx, 3);
+            layer_bind_cubic_launch(ctx, l, e, p, r, sl.partial);
             fe sres[3];
-            finish_sums(ctx, sl, 3, gx, Fr::one(), 0, sres);
-            l->cur = dst;
-            l->len = nout;
+            finish_sums(ctx, sl, 3, p.gx, Fr::one(), 0, sres);
             cubic_coeffs_out(sres, prev_claim, out_coeffs);
         });
     }
@@ -2611,6 +2754,182 @@ int cozk_layer_final_claims(cozk_ctx* ctx, const cozk_layer* l, uint64_t out[16]
             fe_to_u64x4(h[1], out + 12);
         } else {
             for (int i = 0; i < 4; i++) out[4 + i] = out[12 + i] = 0;
+        }
+    });
+}
+
+// ------------------------------------------------------------------ C ABI: layer groups
+// k layers of one mode and one length that share the public eq polynomial, the challenge and the claim, driven as one unit of work
+// on the DRIVER's stream: one sumcheck round of all of them is 2 to 3 launches and one fetch instead of k launches and k fetches.
+// The members stay their owners' (their buffers come from and return to their own contexts' pools); the group only refers to them.
+struct cozk_layer_group {
+    cozk_ctx* driver;
+    int mode;
+    std::vector<cozk_layer*> m;
+};
+
+// the one current length of members 0..k - 1
+static size_t layer_group_len(const cozk_layer_group* g, size_t k, const char* what) {
+    for (size_t i = 1; i < k; i++) COZK_REQUIRE(g->m[i]->len == g->m[0]->len, std::string(what) + ": the members must have one length");
+    return k ? g->m[0]->len : 0;
+}
+
+int cozk_layer_group_create(cozk_ctx* driver, cozk_layer* const* layers, int k, cozk_layer_group** out) {
+    if (out) *out = nullptr;
+    return cozk_guard(driver, [&] {
+        COZK_REQUIRE(driver && layers && out, "layer_group_create: null argument");
+        COZK_REQUIRE(k >= 1 && k <= COZK_LAYER_GROUP_MAX, "layer_group_create: 1 <= k <= COZK_LAYER_GROUP_MAX");
+        for (int i = 0; i < k; i++) {
+            const cozk_layer* l = layers[i];
+            COZK_REQUIRE(l && l->ctx, "layer_group_create: null member");
+            COZK_REQUIRE(l->mode == layers[0]->mode, "layer_group_create: the members must have one mode");
+            COZK_REQUIRE(l->len == layers[0]->len && l->len >= 2, "layer_group_create: the members must have one length >= 2");
+            COZK_REQUIRE(l->ctx->device == driver->device, "layer_group_create: every member must live on the driver's device");
+            for (int j = 0; j < i; j++) COZK_REQUIRE(layers[j] != l, "layer_group_create: duplicate member");
+        }
+        // whatever the members' own streams still do to them precedes the driver's launches
+        for (int i = 0; i < k; i++) {
+            bool seen = false;
+            for (int j = 0; j < i; j++) seen = seen || layers[j]->ctx == layers[i]->ctx;
+            if (!seen) HIP_TRY(hipStreamSynchronize(layers[i]->ctx->stream));
+        }
+        for (int i = 0; i < k; i++) {  // the other ping-pong side, once: later rounds allocate nothing
+            cozk_layer* l = layers[i];
+            PoolOf own(l->ctx);
+            pingpong_ensure(l, 1 - l->cur, 2 * ((l->len + 3) / 4));
+        }
+        cozk_layer_group* g = new cozk_layer_group();
+        g->driver = driver;
+        g->mode = layers[0]->mode;
+        g->m.assign(layers, layers + k);
+        *out = g;
+    });
+}
+
+int cozk_layer_group_free(cozk_layer_group* g) {
+    delete g;
+    return COZK_OK;
+}
+
+int cozk_layer_group_round(cozk_layer_group* g, cozk_spliteq* e, const uint64_t* r, const uint64_t prev_claim[4], uint64_t* out_coeffs) {
+    if (!g) return COZK_ERR_INVALID_ARG;
+    cozk_ctx* const ctx = g->driver;
+    return cozk_guard(ctx, [&] {
+        COZK_REQUIRE(e && prev_claim && out_coeffs, "layer_group_round: null argument");
+        COZK_REQUIRE(e->ctx == ctx, "layer_group_round: the eq polynomial must be the driver's");
+        const unsigned k = (unsigned)g->m.size();
+        const size_t len = layer_group_len(g, k, "layer_group_round");
+        if (r) {
+            COZK_REQUIRE(len > 2, "layer_group_round: the members are already fully bound");
+            COZK_REQUIRE(!spliteq_bound(e), "layer_group_round: eq polynomial already fully bound");
+        }
+        const bool rep3 = g->mode == COZK_MODE_REP3;
+        fe s[3 * COZK_LAYER_GROUP_MAX];
+        if (len > ROUND_SMALL_MAX) {
+            // large members: the launches of cozk_layer_round back to back, member m on its own three rows of ONE reservation
+            // (all take the same grid: one length, one mode, one eq), ONE finishing kernel over the 3 k rows and ONE fetch
+            if (!r) {
+                const LayerCubicPlan p = layer_cubic_plan(ctx, g->m[0], e);
+                const SumLaunch sl = sum_launch(ctx, 3 * k, p.gx, 3 * k);
+                for (unsigned m = 0; m < k; m++) layer_cubic_launch(ctx, g->m[m], e, p, sl.partial + (size_t)3 * m * p.gx);
+                finish_sums(ctx, sl, 3 * k, p.gx, Fr::one(), 0, s);
+            } else {
+                spliteq_bind_launch(ctx, e, fe_from_u64x4(r));
+                const LayerBindCubicPlan p = layer_bind_cubic_plan(ctx, g->m[0], e);
+                const SumLaunch sl = sum_launch(ctx, 3 * k, p.gx, 3 * k);
+                for (unsigned m = 0; m < k; m++) layer_bind_cubic_launch(ctx, g->m[m], e, p, r, sl.partial + (size_t)3 * m * p.gx);
+                finish_sums(ctx, sl, 3 * k, p.gx, Fr::one(), 0, s);
+            }
+        } else {
+            const size_t nout = 2 * ((len + 3) / 4);
+            LayerGroupArgs a;
+            memset(&a, 0, sizeof a);
+            for (unsigned m = 0; m < k; m++) {
+                cozk_layer* l = g->m[m];
+                a.ia[m] = l->buf[l->cur][0];
+                a.ib[m] = rep3 ? l->buf[l->cur][1] : nullptr;
+                if (!r) continue;
+                {
+                    PoolOf own(l->ctx);
+                    pingpong_ensure(l, 1 - l->cur, nout);
+                }
+                a.oa[m] = l->buf[1 - l->cur][0];
+                a.ob[m] = rep3 ? l->buf[1 - l->cur][1] : nullptr;
+            }
+            fe rr = Fr::zero();
+            if (r) {
+                rr = fe_from_u64x4(r);
+                spliteq_bind_launch(ctx, e, rr);  // once for all members, in front of their launch on the same stream
+            }
+            const size_t len_now = r ? nout : len;
+            const int nested = e->E1_len != 1;
+            fe* res = result_slot(ctx, (size_t)3 * k);
+            auto* const kernel = rep3 ? k_layer_group_round_small<2> : k_layer_group_round_small<1>;
+            kernel<<<k, RT, 0, ctx->stream>>>(a, len, r != nullptr, rr, len_now, e->E1[e->c1], e->E1_len / 2, e->E2[e->c2], e->E2_len, nested, res);
+            HIP_TRY(hipGetLastError());
+            if (r)
+                for (cozk_layer* l : g->m) {
+                    l->cur = 1 - l->cur;
+                    l->len = nout;
+                }
+            fetch_fe(ctx, res, (size_t)3 * k, s);
+        }
+        for (unsigned m = 0; m < k; m++) cubic_coeffs_out(s + 3 * m, prev_claim, out_coeffs + 16 * m);
+    });
+}
+
+int cozk_layer_group_final(cozk_layer_group* g, cozk_spliteq* e, const uint64_t* r, int k_final, uint64_t* out_claims) {
+    if (!g) return COZK_ERR_INVALID_ARG;
+    cozk_ctx* const ctx = g->driver;
+    return cozk_guard(ctx, [&] {
+        COZK_REQUIRE(e && out_claims, "layer_group_final: null argument");
+        COZK_REQUIRE(e->ctx == ctx, "layer_group_final: the eq polynomial must be the driver's");
+        COZK_REQUIRE(k_final >= 0 && k_final <= (int)g->m.size(), "layer_group_final: 0 <= k_final <= k");
+        const size_t len = layer_group_len(g, (size_t)k_final, "layer_group_final");
+        COZK_REQUIRE(k_final == 0 || (r ? len <= 4 : len == 2), "layer_group_final: the members must be fully bound (len == 2) after the bind");
+        if (r) COZK_REQUIRE(!spliteq_bound(e), "layer_group_final: eq polynomial already fully bound");
+        const bool rep3 = g->mode == COZK_MODE_REP3;
+        const int nc = rep3 ? 2 : 1;
+        LayerGroupArgs a;
+        memset(&a, 0, sizeof a);
+        for (int m = 0; m < k_final; m++) {
+            cozk_layer* l = g->m[(size_t)m];
+            a.ia[m] = l->buf[l->cur][0];
+            a.ib[m] = rep3 ? l->buf[l->cur][1] : nullptr;
+            if (!r) continue;
+            {
+                PoolOf own(l->ctx);
+                pingpong_ensure(l, 1 - l->cur, 2);
+            }
+            a.oa[m] = l->buf[1 - l->cur][0];
+            a.ob[m] = rep3 ? l->buf[1 - l->cur][1] : nullptr;
+        }
+        fe rr = Fr::zero();
+        if (r) {
+            rr = fe_from_u64x4(r);
+            spliteq_bind_launch(ctx, e, rr);  // as cozk_layer_prove_rounds does behind its last round
+        }
+        if (k_final == 0) {
+            if (r) stream_drain_by_flag(ctx);
+            return;
+        }
+        const size_t n_res = (size_t)2 * nc * (size_t)k_final;
+        fe* res = result_slot(ctx, n_res);
+        auto* const kernel = rep3 ? k_layer_group_final<2> : k_layer_group_final<1>;
+        kernel<<<k_final, GFT, 0, ctx->stream>>>(a, len, r != nullptr, rr, res);
+        HIP_TRY(hipGetLastError());
+        if (r)
+            for (int m = 0; m < k_final; m++) {
+                g->m[(size_t)m]->cur = 1 - g->m[(size_t)m]->cur;
+                g->m[(size_t)m]->len = 2;
+            }
+        fe h[4 * COZK_LAYER_GROUP_MAX];
+        fetch_fe(ctx, res, n_res, h);
+        for (int m = 0; m < k_final; m++) {  // the layout of cozk_layer_final_claims: L.a, L.b, R.a, R.b (b = 0 for PLAIN)
+            uint64_t* out = out_claims + 16 * m;
+            for (int i = 0; i < 16; i++) out[i] = 0;
+            for (int side = 0; side < 2; side++)
+                for (int c = 0; c < nc; c++) fe_to_u64x4(h[(2 * m + side) * nc + c], out + 8 * side + 4 * c);
         }
     });
 }

@@ -465,6 +465,13 @@ class ShamirGpResult(ctypes.Structure):
                 ("t_construct_ms", ctypes.c_double), ("t_prove_ms", ctypes.c_double)]
 
 
+class ShamirGpStats(ctypes.Structure):
+    """cozk_shamir_gp_stats: how the rounds ran -- calls of cozk_layer_group_round / _final against per-sender cozk_layer_round
+    and per-opener final claims"""
+    _fields_ = [("group_rounds", ctypes.c_uint64), ("single_rounds", ctypes.c_uint64), ("group_finals", ctypes.c_uint64),
+                ("single_finals", ctypes.c_uint64)]
+
+
 class ShamirGpProof:
     """what shamir_gp_prove returns: .proof_bytes, the final .claim and point .r (canonical ints), .result (ShamirGpResult), and
     what went over the star -- .msgs[m][p], sender p's masked message of opening m, and .finals[layer, top first][p] = (L, R),
@@ -478,6 +485,8 @@ class ShamirGpProof:
 
         ok(l.cozk_shamir_gp_get_result(h, ctypes.byref(res)))
         self.result = res
+        self._stats = ShamirGpStats()
+        ok(l.cozk_shamir_gp_get_stats(h, ctypes.byref(self._stats)))
         buf = (ctypes.c_uint8 * max(int(res.proof_len), 1))()
         ok(l.cozk_shamir_gp_proof_bytes(h, buf, int(res.proof_len)))
         self.proof_bytes = bytes(buf)[:int(res.proof_len)]
@@ -498,6 +507,12 @@ class ShamirGpProof:
         flat = table(l.cozk_shamir_gp_finals_len, l.cozk_shamir_gp_finals)
         pairs = [(flat[i], flat[i + 1]) for i in range(0, len(flat), 2)]
         self.finals = [pairs[i:i + degree + 1] for i in range(0, len(pairs), degree + 1)]
+
+
+    @property
+    def stats(self):
+        """ShamirGpStats of the proof (cozk_shamir_gp_get_stats)"""
+        return self._stats
 
 
 def shamir_gp_prove(party_ctxs, leaves, batch_size, mul_keys, rand_keys, degree, mul_counter=0, rand_counter=0, label=b"cozk", verify=True):

@@ -374,6 +374,52 @@ class Rep3DenseInterleavedPolynomial:
             pass
 
 
+class LayerGroup:
+    """k layers of one mode and one length that share the public eq polynomial, the challenge and the claim, driven as one unit
+    of work on the stream of the driver `ctx` (cozk_layer_group_*): the senders of a Shamir prover.  The layers may belong to
+    other contexts on the same device; the group only refers to them and they must outlive it."""
+
+    def __init__(self, ctx, layers):
+        self.ctx = ctx
+        self.layers = list(layers)
+        self.mode = self.layers[0].mode if self.layers else L.MODE_PLAIN
+        h = ctypes.c_void_p()
+        ctx.check(ctx._l.cozk_layer_group_create(ctx.h, _ptr_array(self.layers), len(self.layers), ctypes.byref(h)))
+        self.h = h
+
+    def round(self, eq, r, claim):
+        """cozk_layer_round for every member at once: bind members + eq with r (None in round 0), then each member's 4
+        additive coefficient shares against the one public claim -> a list of k lists of 4"""
+        pc = _fr(claim)
+        rr = _fr(r) if r is not None else None
+        out = np.zeros((len(self.layers) * 4, 4), dtype=np.uint64)
+        self.ctx.check(self.ctx._l.cozk_layer_group_round(self.h, eq.h, rr.ctypes.data if rr is not None else None, pc.ctypes.data, out.ctypes.data))
+        v = mont_limbs_to_int(out)
+        return [v[4 * m:4 * m + 4] for m in range(len(self.layers))]
+
+    def final(self, eq, r, k_final):
+        """the last bind with r (None: no bind) and the final claims of members 0..k_final - 1, each as
+        Rep3DenseInterleavedPolynomial.final_claims returns them; binds eq too when r is given"""
+        rr = _fr(r) if r is not None else None
+        out = np.zeros((max(k_final, 1) * 4, 4), dtype=np.uint64)
+        self.ctx.check(self.ctx._l.cozk_layer_group_final(self.h, eq.h, rr.ctypes.data if rr is not None else None, k_final, out.ctypes.data))
+        v = mont_limbs_to_int(out)
+        if self.mode == L.MODE_REP3:
+            return [((v[4 * m], v[4 * m + 1]), (v[4 * m + 2], v[4 * m + 3])) for m in range(k_final)]
+        return [(v[4 * m], v[4 * m + 2]) for m in range(k_final)]
+
+    def free(self):
+        if self.h:
+            self.ctx._l.cozk_layer_group_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def rep3_mul_vec_local(ctx, xa, xb, ya, yb, key_self=None, key_prev=None, counter=0):
     """rep3::arithmetic::mul_vec, local half (cozk_rep3_mul_vec_local): out[j] = x[j] x y[j] as an additive share,
     plus the zero-sharing mask PRF(key_self, counter + j) - PRF(key_prev, counter + j) when keys are given.

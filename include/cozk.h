@@ -364,6 +364,16 @@ int cozk_shamir_gp_prove_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* con
                                 cozk_shamir_gp** out);
 int cozk_shamir_gp_free(cozk_shamir_gp* h);
 int cozk_shamir_gp_get_result(const cozk_shamir_gp* h, cozk_shamir_gp_result* res);
+/* How the rounds ran.  When the 2t + 1 senders' contexts are on one device, a layer's sumcheck is ONE layer group over the senders'
+ * layers with ONE eq polynomial on sender 0's context: a cozk_layer_group_round per round and a cozk_layer_group_final with
+ * k_final = t + 1 (group_*: calls made).  Otherwise, or with COZK_SHAMIR_GP_GROUP=0 in the environment (read on every call, for
+ * A/B runs within one process), every sender runs cozk_layer_round on an eq of its own and every opener cozk_layer_bind +
+ * cozk_layer_final_claims (single_rounds: per sender and round; single_finals: per opener and layer).  Proof, msgs and finals
+ * are the same bytes either way. */
+typedef struct cozk_shamir_gp_stats {
+    uint64_t group_rounds, single_rounds, group_finals, single_finals;
+} cozk_shamir_gp_stats;
+int cozk_shamir_gp_get_stats(const cozk_shamir_gp* h, cozk_shamir_gp_stats* stats);
 int cozk_shamir_gp_proof_bytes(const cozk_shamir_gp* h, uint8_t* out, size_t cap); /* cap >= proof_len bytes */
 /* the final (claim, r): r = point_len x 4 u64 */
 size_t cozk_shamir_gp_point_len(const cozk_shamir_gp* h);
@@ -568,6 +578,35 @@ int cozk_layer_compute_cubic_evals(cozk_ctx* ctx, const cozk_layer* l, const coz
                                    uint64_t out_evals[12]);
 /* final_claims (dense_interleaved_poly.rs:367-372): out = L.a, L.b, R.a, R.b (b = 0 for PLAIN) */
 int cozk_layer_final_claims(cozk_ctx* ctx, const cozk_layer* l, uint64_t out[16]);
+/* Layer groups: one sumcheck round of SEVERAL layers that share the public eq polynomial, the challenge and the claim, as one
+ * unit of work -- the senders of a Shamir prover (csrc/host/shamir_gp.hpp), each a party with a context of its own on one device.
+ * A group refers to k layers, 1 <= k <= COZK_LAYER_GROUP_MAX, of one mode (all PLAIN or all REP3) and one current length >= 2,
+ * pairwise distinct, each of a context on the DRIVER's device (the contexts may differ).  It does not own them: freeing the group
+ * leaves them valid, and they must outlive it.  create drains every member context's stream once and sizes each member's other
+ * ping-pong side, from that member's own pool, to 2 * ceil(len / 4) elements: later rounds allocate nothing.
+ *   round  cozk_layer_round for every member at once: with r != NULL every member and the ONE eq `e` (a spliteq of the driver) are
+ *          bound with r, then member m's four coefficient shares against that eq and the one public prev_claim go to
+ *          out_coeffs + 16 m (k x 16 u64).  Members of <= 2048 elements run as ONE launch of k workgroups behind the eq fold;
+ *          larger ones as their k launches back to back, one finishing kernel; either way ONE fetch.  Every launch goes on the
+ *          driver's stream and the call returns with that stream drained, so between two group calls a member may be driven by
+ *          the per-layer calls of its own context (and `e` by cozk_spliteq_bind) with the same results -- provided that context's
+ *          stream is drained before the next group call (cozk_layer_round and cozk_layer_final_claims leave it so).
+ *   final  for members 0 .. k_final - 1: the last bind with r (NULL: no bind, a layer that had no rounds) and the final claims,
+ *          out_claims + 16 m laid out as cozk_layer_final_claims' (k_final x 16 u64); with r it binds `e` too, as
+ *          cozk_layer_prove_rounds does behind its last round.  One launch, one fetch; members from k_final upwards are left
+ *          untouched.
+ * Refused on the host before any launch, with COZK_ERR_INVALID_ARG and the text left with the driver (*out is NULL): null
+ * arguments, k out of range, mixed modes or lengths, a duplicate member, a member on another device, an `e` that is not the
+ * driver's, a binding round on members that are down to their two claims or on a fully bound eq, k_final outside 0..k, a final on
+ * members that the bind does not leave at two elements. */
+#define COZK_LAYER_GROUP_MAX 32 /* = COZK_SHAMIR_MAX_PARTIES */
+typedef struct cozk_layer_group cozk_layer_group;
+int cozk_layer_group_create(cozk_ctx* driver, cozk_layer* const* layers, int k, cozk_layer_group** out);
+int cozk_layer_group_round(cozk_layer_group* g, cozk_spliteq* e, const uint64_t* r, const uint64_t prev_claim[4],
+                           uint64_t* out_coeffs /* k x 16 */);
+int cozk_layer_group_final(cozk_layer_group* g, cozk_spliteq* e, const uint64_t* r, int k_final,
+                           uint64_t* out_claims /* k_final x 16 */);
+int cozk_layer_group_free(cozk_layer_group* g);
 /* local half of layer_output -> mul_vec (dense_interleaved_poly.rs:122-141; local product
  * mpc-types/src/protocols/rep3/arithmetic/ops.rs:71-78): out[j] = L[j] x R[j] + mask_j, where
  * mask_j = PRF(key_self, counter + j) - PRF(key_prev, counter + j) when masked != 0 (key_self is shared with the

@@ -38,7 +38,13 @@ With --gp --king, instead, the king construct of that prover and its offline pre
   (xvii)  the preprocessing cozk_shamir_gp_prep_inproc, reported on its own: offline time is never netted against online time;
   (xviii) the whole cozk_shamir_gp_prove_king_inproc (a fresh preprocessing per repetition, made outside the timed call) against the
           whole cozk_shamir_gp_prove_inproc; the proofs are equal byte for byte.
-  python tools/run_shamir.py --gp --king --log-n 22 --parties 8 --degree 2 [--out FILE]"""
+  python tools/run_shamir.py --gp --king --log-n 22 --parties 8 --degree 2 [--out FILE]
+Both --gp and --gp --king end with a pair of legs of their prover:
+  (xix)   the whole prove with the rounds on layer groups (cozk_layer_group_round: one launch per round for all senders) against the
+          whole prove with COZK_SHAMIR_GP_GROUP=0 (the per-sender loop: one launch and one fetch per sender and round), alternating
+          in this process, proofs, messages and final-claim shares compared.
+--only-group runs nothing but (xix), for both provers:
+  python tools/run_shamir.py --gp --only-group --log-n 22 --parties 8 --degree 2 --out profiles/shamir_gp_group_2p22_n8_t2.json"""
 import argparse, ctypes, hashlib, importlib, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -54,6 +60,7 @@ ap.add_argument("--mul", action="store_true", help="time the multiplication with
 ap.add_argument("--king", action="store_true", help="with --mul: time the king / double-random variant against the resharing; with --gp: the king construct")
 ap.add_argument("--gp", action="store_true", help="time the Shamir grand product prover instead")
 ap.add_argument("--gp-batch", type=int, default=2, help="with --gp: circuits in the grand product")
+ap.add_argument("--only-group", action="store_true", help="with --gp: only the grouped against the ungrouped prove, resharing and king prover")
 args = ap.parse_args()
 cozk = importlib.import_module("co-zkvms_amd")
 L = cozk._lib
@@ -492,6 +499,7 @@ def gp_legs():
     while sum(t_all) < args.min_seconds * 1e3 or len(t_all) < 5:  # the Shamir prover and the plain prover alternating
         ms, g = whole(prove); t_all.append(ms); t_dc.append(g.result.t_construct_ms); t_dp.append(g.result.t_prove_ms)
         a, b, _ = plain_prove(); t_pc.append(a); t_pp.append(b)
+    grouped = group_pair(lambda: whole(prove))  # (xix)
     free(leaves)
     for pc in pcs:
         pc.close()
@@ -519,6 +527,7 @@ def gp_legs():
         "plain_prover_same_run": {"construct": stats(t_pc), "prove": stats(t_pp), "proof_equals_shamir_proof": bool(same),
                                   "note": "host clock; rounds driven from this script through cozk_layer_round (one launch and one fetch per "
                                           "round, transcript hashed in Python): neither prover here uses the resident tail kernel"},
+        "grouped_vs_ungrouped_rounds": grouped,
         "timing": "device events around each repetition for (xi), legs alternating on one stream; (xii) and the whole call of (xiii) from an event "
                   "on party 0's idle stream before the call to the last of the events behind the parties' streams, host-side synchronisations "
                   "included; the Shamir and the PLAIN prover alternating; keys and counters reused across repetitions (timing only)",
@@ -551,6 +560,83 @@ def whole_call(pcs, streams, fn):
     for e in ends:
         e.synchronize()
     return max(e0.elapsed_time(e) for e in ends), out
+
+
+GROUP_SWITCH = "COZK_SHAMIR_GP_GROUP"
+
+
+def group_pair(timed_prove):
+    """(xix): timed_prove() -> (ms, ShamirGpProof) with the rounds on layer groups and with COZK_SHAMIR_GP_GROUP=0, alternating.  The
+    yardstick is the ungrouped leg of this run; the verdict allows the grouped median that leg's own min .. max spread"""
+    def leg(ungrouped):
+        if ungrouped:
+            os.environ[GROUP_SWITCH] = "0"  # read by the library on every call
+        try:
+            return timed_prove()
+        finally:
+            os.environ.pop(GROUP_SWITCH, None)
+
+    calls = lambda g: {k: int(getattr(g.stats, k)) for k in ("group_rounds", "single_rounds", "group_finals", "single_finals")}
+    _, gg = leg(False)  # warm-up and correctness
+    _, gu = leg(True)
+    assert gg.result.verified == 1 and gu.result.verified == 1, "a Shamir grand product proof was rejected"
+    equal = gg.proof_bytes == gu.proof_bytes and gg.msgs == gu.msgs and gg.finals == gu.finals
+    assert equal, "the grouped and the ungrouped prove differ in proof, messages or final-claim shares"
+    assert gg.stats.single_rounds == 0 and gg.stats.group_rounds > 0 and gu.stats.group_rounds == 0, "the switch did not select the legs"
+    t_g, t_u, t_gc, t_gp, t_uc, t_up = [], [], [], [], [], []
+    while sum(t_g) < args.min_seconds * 1e3 or sum(t_u) < args.min_seconds * 1e3 or len(t_g) < 6:
+        ms, g = leg(False); t_g.append(ms); t_gc.append(g.result.t_construct_ms); t_gp.append(g.result.t_prove_ms)
+        equal = equal and g.proof_bytes == gu.proof_bytes
+        ms, g = leg(True); t_u.append(ms); t_uc.append(g.result.t_construct_ms); t_up.append(g.result.t_prove_ms)
+        equal = equal and g.proof_bytes == gu.proof_bytes
+    assert equal, "a repetition's proof differs"
+    spread_u = sorted(t_u)[-1] - sorted(t_u)[0]
+    return {
+        "grouped_whole_call": dict(stats(t_g), driver_split={"construct": stats(t_gc), "openings_rounds": stats(t_gp)}, calls=calls(gg)),
+        "ungrouped_whole_call_same_run": dict(stats(t_u), driver_split={"construct": stats(t_uc), "openings_rounds": stats(t_up)}, calls=calls(gu)),
+        "grouped_vs_ungrouped_speedup": round(med(t_u) / med(t_g), 3),
+        "openings_rounds_grouped_vs_ungrouped_speedup": round(med(t_up) / med(t_gp), 3),
+        "grouped_slower_than_ungrouped_by_ms": round(med(t_g) - med(t_u), 4),
+        "ungrouped_min_max_spread_ms": round(spread_u, 4),
+        "grouped_not_slower_beyond_ungrouped_spread": bool(med(t_g) - med(t_u) <= spread_u),
+        "proofs_messages_finals_equal": bool(equal),
+    }
+
+
+def group_legs_only():
+    """--only-group: (xix) for the resharing prover and for the king prover, one context per party on this GPU"""
+    if 2 * T + 1 > N or 2 * T > 15:
+        raise SystemExit("run_shamir --gp --only-group: needs 2 * degree + 1 <= parties and 2 * degree <= 15")
+    batch = args.gp_batch
+    pcs, streams = party_contexts()
+    whole = lambda fn: whole_call(pcs, streams, fn)
+    leaves = A.shamir_scatter(keys_a, T, pcs, counter=0)
+    mul_keys = [[key(1000 + 16 * p + c) for c in range(T)] for p in range(N)]
+    rand_keys = [[key(2000 + 32 * p + c) for c in range(3 * T + 1)] for p in range(N)]
+
+    def king_prove():  # a fresh preprocessing per repetition, made outside the timed call
+        prep = cozk.shamir_gp_prep(pcs, rand_keys, n, batch, T, rand_counter=0)
+        try:
+            return whole(lambda: cozk.shamir_gp_prove_king(pcs, leaves, batch, prep, king=0))
+        finally:
+            prep.close()
+
+    reshare = group_pair(lambda: whole(lambda: cozk.shamir_gp_prove(pcs, leaves, batch, mul_keys, rand_keys, T, mul_counter=0, rand_counter=0)))
+    king = group_pair(king_prove)
+    free(leaves)
+    for pc in pcs:
+        pc.close()
+    emit({
+        "what": "Shamir grand product provers: the rounds on layer groups (one launch per round for all senders) against the per-sender loop "
+                "(COZK_SHAMIR_GP_GROUP=0), whole prove, resharing and king construct",
+        "log_n": args.log_n, "interleaved_leaves": n, "batch": batch, "parties": N, "degree": T, "senders": 2 * T + 1, "king": 0,
+        "device": torch.cuda.get_device_name(0),
+        "resharing_prover": reshare, "king_prover": king,
+        "timing": "from an event on party 0's idle stream before the call to the last of the events behind the parties' streams, host-side "
+                  "synchronisations included; the grouped and the ungrouped leg alternating in one process, the ungrouped leg being the "
+                  "yardstick; keys and counters reused across repetitions (timing only); the king prover's preprocessing is made outside "
+                  "the timed call",
+    })
 
 
 def gp_king_legs():
@@ -676,6 +762,15 @@ def gp_king_legs():
             continue
         t_prep.append(ms_prep); t_off.append(off_ms); t_pk.append(ms_k); t_pg.append(ms_g)
         t_kc.append(gk.result.t_construct_ms); t_kp.append(gk.result.t_prove_ms); t_gc.append(gg.result.t_construct_ms); t_gp.append(gg.result.t_prove_ms)
+
+    def king_prove():  # (xix): a fresh preprocessing per repetition, made outside the timed call
+        prep = make_prep()
+        try:
+            return whole(lambda: cozk.shamir_gp_prove_king(pcs, leaves, batch, prep, king=0))
+        finally:
+            prep.close()
+
+    grouped = group_pair(king_prove)
     free(leaves)
     for pc in pcs:
         pc.close()
@@ -703,6 +798,7 @@ def gp_king_legs():
         "inproc_prove_resharing_whole_call_same_run": dict(stats(t_pg), driver_split={"construct": stats(t_gc), "masks_openings_rounds": stats(t_gp)}),
         "king_vs_resharing_prove_time_ratio": round(med(t_pk) / med(t_pg), 3),
         "proofs_equal": bool(proofs_equal),
+        "grouped_vs_ungrouped_rounds": grouped,
         "timing": "device events around each repetition for (xiv) and (xv), legs alternating on one stream (allocation from the context's pool "
                   "included); the in-process legs from an event on party 0's idle stream before the call to the last of the events behind the "
                   "parties' streams, host-side synchronisations included, the legs of a pair alternating; the construct legs reuse two "
@@ -710,6 +806,11 @@ def gp_king_legs():
                   "peer-copy legs (parties on other GPUs) are not exercised by a one-GPU run",
     })
 
+
+if args.gp and args.only_group:
+    group_legs_only()
+    ctx.close()
+    raise SystemExit(0)
 
 if args.gp and args.king:
     gp_king_legs()
