@@ -39,7 +39,7 @@ struct cozk_poly {
 struct cozk_layer {
     cozk_ctx* ctx;
     int mode;
-    fe* buf[2][2];       // ping-pong [which][component]
+    fe* buf[2][2];       // ping-pong [which][component]; component 1 of a PLAIN layer is null (the launch sites pass it as it is)
     size_t cap[2];
     int cur;
     size_t len;
@@ -381,17 +381,20 @@ __global__ void __launch_bounds__(PT) k_pst_fold(const fe* __restrict__ r, fe* _
 }
 
 // ------------------------------------------------------------------ kernels: interleaved GKR layer
-// bind 4 -> 2 with a zero-padded ragged tail (dense_interleaved_poly.rs:155-195)
+// The steps every Fr layer kernel below is made of (the 9 x 29 kernels have their own: layer9_terms .. layer9_finish).  Their shape
+// is the one at which every kernel keeps the registers, scratch and occupancy it had with the steps written out in its body; the
+// notes say where that decided something.
+// bind 4 -> 2 with a zero-padded ragged tail (dense_interleaved_poly.rs:155-195): input chunk ci becomes the bound elements
+// 2 ci and 2 ci + 1, stored (lo before hi is computed) and handed back
 template <int NC>
-__global__ void __launch_bounds__(PT) k_layer_bind(const fe* __restrict__ ia, const fe* __restrict__ ib, fe* oa, fe* ob,
-                                                size_t len, fe r) {
-    size_t c = (size_t)blockIdx.x * PT + threadIdx.x;
-    size_t nch = (len + 3) / 4;
-    if (c >= nch) return;
-    Sh<NC> u0 = sh_load_or_zero<NC>(ia, ib, 4 * c, len), u1 = sh_load_or_zero<NC>(ia, ib, 4 * c + 1, len);
-    Sh<NC> u2 = sh_load_or_zero<NC>(ia, ib, 4 * c + 2, len), u3 = sh_load_or_zero<NC>(ia, ib, 4 * c + 3, len);
-    sh_store<NC>(oa, ob, 2 * c, sh_lerp<NC>(u0, u2, r));
-    sh_store<NC>(oa, ob, 2 * c + 1, sh_lerp<NC>(u1, u3, r));
+static __device__ __forceinline__ void layer_bind_chunk(const fe* ia, const fe* ib, size_t len_in, size_t ci, const fe& r, fe* oa, fe* ob, Sh<NC>& lo,
+                                                        Sh<NC>& hi) {
+    Sh<NC> u0 = sh_load_or_zero<NC>(ia, ib, 4 * ci, len_in), u1 = sh_load_or_zero<NC>(ia, ib, 4 * ci + 1, len_in);
+    Sh<NC> u2 = sh_load_or_zero<NC>(ia, ib, 4 * ci + 2, len_in), u3 = sh_load_or_zero<NC>(ia, ib, 4 * ci + 3, len_in);
+    lo = sh_lerp<NC>(u0, u2, r);
+    sh_store<NC>(oa, ob, 2 * ci, lo);
+    hi = sh_lerp<NC>(u1, u3, r);
+    sh_store<NC>(oa, ob, 2 * ci + 1, hi);
 }
 
 // eq evaluations at 0, 2, 3 of the linear factor through (e0, e1)
@@ -402,51 +405,93 @@ static __device__ __forceinline__ void eq3(const fe& e0, const fe& e1, fe out[3]
     out[2] = Fr::add(out[1], m);
 }
 
+// chunks of 4 elements that a round sums over: zip() stops at the shorter side of the layer and the eq table
+static __device__ __forceinline__ size_t layer_chunk_count(size_t len, bool nested, size_t E1_half, size_t E2_len) {
+    size_t nch = (len + 3) / 4;
+    size_t limit = nested ? E1_half * E2_len : E2_len / 2;
+    return nch > limit ? limit : nch;
+}
+
+// the eq pair of chunk c at 0, 2, 3.  Not nested: E1 fully bound, the pair comes from E2 (dense_interleaved_poly.rs:218-268).
+// Nested: Dao-Thaler split, chunk c belongs to x2 = c / E1_half, x1 = c % E1_half (:269-356); `scale` = E2[x2] multiplies its terms.
+static __device__ __forceinline__ void layer_eq_at(bool nested, const fe* E1, size_t E1_half, const fe* E2, size_t c, fe e[3], fe& scale) {
+    if (nested) {
+        size_t x2 = c >> (__ffsll((long long)E1_half) - 1), x1 = c & (E1_half - 1);  // E1_half is a power of two
+        eq3(fe_load(E1 + 2 * x1), fe_load(E1 + 2 * x1 + 1), e);
+        scale = fe_load(E2 + x2);
+    } else {
+        eq3(fe_load(E2 + 2 * c), fe_load(E2 + 2 * c + 1), e);
+    }
+}
+
+// the three terms of one chunk (l0, r0, l1, r1): t_X = (L(X) x R(X)) e_X [scale] at X = 0, 2, 3.  The caller adds them to its sums
+// (with the sums taken by reference here, k_layer_cubic<2, 1> and k_layer_bind_cubic<1, 1> allocate other registers).
+template <int NC>
+static __device__ __forceinline__ void layer_terms(const Sh<NC>& l0, const Sh<NC>& r0, const Sh<NC>& l1, const Sh<NC>& r1, const fe e[3], bool nested,
+                                                   const fe& scale, fe& t0, fe& t2, fe& t3) {
+    Sh<NC> ml = sh_sub<NC>(l1, l0), mr = sh_sub<NC>(r1, r0);
+    Sh<NC> l2 = sh_add<NC>(l1, ml), r2 = sh_add<NC>(r1, mr);
+    Sh<NC> l3 = sh_add<NC>(l2, ml), r3 = sh_add<NC>(r2, mr);
+    t0 = Fr::mul(sh_local_mul<NC>(l0, r0), e[0]);
+    t2 = Fr::mul(sh_local_mul<NC>(l2, r2), e[1]);
+    t3 = Fr::mul(sh_local_mul<NC>(l3, r3), e[2]);
+    if (nested) {
+        t0 = Fr::mul(t0, scale);
+        t2 = Fr::mul(t2, scale);
+        t3 = Fr::mul(t3, scale);
+    }
+}
+
+// the workgroup's three sums, one after the other through `sh` (fr_block_sum); sum k = 0, 1, 2 goes to out(k), which is evaluated
+// behind the sum's barriers, where the kernels had their address arithmetic
+template <class Out>
+static __device__ __forceinline__ void layer_finish(fe s0, fe s2, fe s3, fe* sh, Out out) {
+    s0 = fr_block_sum(s0, sh);
+    if (threadIdx.x == 0) fe_store(out(0), s0);
+    s2 = fr_block_sum(s2, sh);
+    if (threadIdx.x == 0) fe_store(out(1), s2);
+    s3 = fr_block_sum(s3, sh);
+    if (threadIdx.x == 0) fe_store(out(2), s3);
+}
+
+// SplitEqPolynomial::bind of one pair: lo + (hi - lo) r
+static __device__ __forceinline__ fe fold_pair(const fe* in, size_t i, const fe& r) {
+    fe lo = fe_load(in + 2 * i), hi = fe_load(in + 2 * i + 1);
+    return Fr::add(lo, Fr::mul(Fr::sub(hi, lo), r));
+}
+
+template <int NC>
+__global__ void __launch_bounds__(PT) k_layer_bind(const fe* __restrict__ ia, const fe* __restrict__ ib, fe* oa, fe* ob,
+                                                size_t len, fe r) {
+    size_t c = (size_t)blockIdx.x * PT + threadIdx.x;
+    size_t nch = (len + 3) / 4;
+    if (c >= nch) return;
+    Sh<NC> lo, hi;
+    layer_bind_chunk<NC>(ia, ib, len, c, r, oa, ob, lo, hi);
+}
+
 // cubic round evaluations g(0), g(2), g(3) of sum eq * L * R  (compute_cubic,
-// dense_interleaved_poly.rs:210-356).  NESTED = 0: E1 fully bound, eq pairs come from E2 (:218-268);
-// NESTED = 1: Dao-Thaler split, chunk k belongs to x2 = k / (E1_len/2), x1 = k % (E1_len/2) (:269-356).
+// dense_interleaved_poly.rs:210-356).  NESTED: which form of the eq pair (layer_eq_at).
 template <int NC, int NESTED>
 __global__ void __launch_bounds__(PT) k_layer_cubic(const fe* __restrict__ a, const fe* __restrict__ b, size_t len,
                                                  const fe* __restrict__ E1, size_t E1_half, const fe* __restrict__ E2,
                                                  size_t E2_len, fe* __restrict__ partial) {
     __shared__ fe sh4[4];
-    size_t nch = (len + 3) / 4;
-    size_t limit = NESTED ? E1_half * E2_len : E2_len / 2;
-    if (nch > limit) nch = limit;  // zip() stops at the shorter side
+    const size_t nch = layer_chunk_count(len, NESTED, E1_half, E2_len);
     fe s0 = Fr::zero(), s2 = Fr::zero(), s3 = Fr::zero();
     for (size_t c = (size_t)blockIdx.x * PT + threadIdx.x; c < nch; c += (size_t)gridDim.x * PT) {
         fe e[3];
         fe scale;
-        if (NESTED) {
-            size_t x2 = c >> (__ffsll((long long)E1_half) - 1), x1 = c & (E1_half - 1);  // E1_half is a power of two
-            eq3(fe_load(E1 + 2 * x1), fe_load(E1 + 2 * x1 + 1), e);
-            scale = fe_load(E2 + x2);
-        } else {
-            eq3(fe_load(E2 + 2 * c), fe_load(E2 + 2 * c + 1), e);
-        }
+        layer_eq_at(NESTED, E1, E1_half, E2, c, e, scale);
         Sh<NC> l0 = sh_load_or_zero<NC>(a, b, 4 * c, len), r0 = sh_load_or_zero<NC>(a, b, 4 * c + 1, len);
         Sh<NC> l1 = sh_load_or_zero<NC>(a, b, 4 * c + 2, len), r1 = sh_load_or_zero<NC>(a, b, 4 * c + 3, len);
-        Sh<NC> ml = sh_sub<NC>(l1, l0), mr = sh_sub<NC>(r1, r0);
-        Sh<NC> l2 = sh_add<NC>(l1, ml), r2 = sh_add<NC>(r1, mr);
-        Sh<NC> l3 = sh_add<NC>(l2, ml), r3 = sh_add<NC>(r2, mr);
-        fe t0 = Fr::mul(sh_local_mul<NC>(l0, r0), e[0]);
-        fe t2 = Fr::mul(sh_local_mul<NC>(l2, r2), e[1]);
-        fe t3 = Fr::mul(sh_local_mul<NC>(l3, r3), e[2]);
-        if (NESTED) {
-            t0 = Fr::mul(t0, scale);
-            t2 = Fr::mul(t2, scale);
-            t3 = Fr::mul(t3, scale);
-        }
+        fe t0, t2, t3;
+        layer_terms<NC>(l0, r0, l1, r1, e, NESTED, scale, t0, t2, t3);
         s0 = Fr::add(s0, t0);
         s2 = Fr::add(s2, t2);
         s3 = Fr::add(s3, t3);
     }
-    s0 = fr_block_sum(s0, sh4);
-    if (threadIdx.x == 0) fe_store(partial + blockIdx.x, s0);
-    s2 = fr_block_sum(s2, sh4);
-    if (threadIdx.x == 0) fe_store(partial + gridDim.x + blockIdx.x, s2);
-    s3 = fr_block_sum(s3, sh4);
-    if (threadIdx.x == 0) fe_store(partial + 2 * gridDim.x + blockIdx.x, s3);
+    layer_finish(s0, s2, s3, sh4, [&](unsigned k) { return partial + k * gridDim.x + blockIdx.x; });
 }
 
 // bind + the next round's cubic sums in ONE pass over a large layer: a lane reads 8 unbound elements, writes the 4
@@ -460,7 +505,7 @@ __global__ void __launch_bounds__(PT) k_layer_bind_cubic(const fe* __restrict__ 
     const size_t nch_in = (len_in + 3) / 4;      // input chunks of 4 -> 2 bound elements each
     const size_t len_out = 2 * nch_in;
     const size_t nch_out = (len_out + 3) / 4;    // output chunks of 4 bound elements = 2 input chunks
-    size_t limit = NESTED ? E1_half * E2_len : E2_len / 2;
+    const size_t nsum = layer_chunk_count(len_out, NESTED, E1_half, E2_len);
     fe s0 = Fr::zero(), s2 = Fr::zero(), s3 = Fr::zero();
     for (size_t c = (size_t)blockIdx.x * PT + threadIdx.x; c < nch_out; c += (size_t)gridDim.x * PT) {
         Sh<NC> v[4];
@@ -468,49 +513,23 @@ __global__ void __launch_bounds__(PT) k_layer_bind_cubic(const fe* __restrict__ 
         for (int h = 0; h < 2; h++) {
             size_t ci = 2 * c + h;
             if (ci < nch_in) {
-                Sh<NC> u0 = sh_load_or_zero<NC>(ia, ib, 4 * ci, len_in), u1 = sh_load_or_zero<NC>(ia, ib, 4 * ci + 1, len_in);
-                Sh<NC> u2 = sh_load_or_zero<NC>(ia, ib, 4 * ci + 2, len_in), u3 = sh_load_or_zero<NC>(ia, ib, 4 * ci + 3, len_in);
-                v[2 * h] = sh_lerp<NC>(u0, u2, r);
-                v[2 * h + 1] = sh_lerp<NC>(u1, u3, r);
-                sh_store<NC>(oa, ob, 2 * ci, v[2 * h]);
-                sh_store<NC>(oa, ob, 2 * ci + 1, v[2 * h + 1]);
+                layer_bind_chunk<NC>(ia, ib, len_in, ci, r, oa, ob, v[2 * h], v[2 * h + 1]);
             } else {
                 for (int k = 0; k < NC; k++) v[2 * h].c[k] = v[2 * h + 1].c[k] = Fr::zero();
             }
         }
-        if (c < limit) {  // zip() stops at the shorter side (k_layer_cubic)
+        if (c < nsum) {  // every output chunk is bound and stored; only those on the shorter side are summed
             fe e[3];
             fe scale;
-            if (NESTED) {
-                size_t x2 = c >> (__ffsll((long long)E1_half) - 1), x1 = c & (E1_half - 1);  // E1_half is a power of two
-                eq3(fe_load(E1 + 2 * x1), fe_load(E1 + 2 * x1 + 1), e);
-                scale = fe_load(E2 + x2);
-            } else {
-                eq3(fe_load(E2 + 2 * c), fe_load(E2 + 2 * c + 1), e);
-            }
-            Sh<NC> l0 = v[0], r0 = v[1], l1 = v[2], r1 = v[3];
-            Sh<NC> ml = sh_sub<NC>(l1, l0), mr = sh_sub<NC>(r1, r0);
-            Sh<NC> l2 = sh_add<NC>(l1, ml), r2 = sh_add<NC>(r1, mr);
-            Sh<NC> l3 = sh_add<NC>(l2, ml), r3 = sh_add<NC>(r2, mr);
-            fe t0 = Fr::mul(sh_local_mul<NC>(l0, r0), e[0]);
-            fe t2 = Fr::mul(sh_local_mul<NC>(l2, r2), e[1]);
-            fe t3 = Fr::mul(sh_local_mul<NC>(l3, r3), e[2]);
-            if (NESTED) {
-                t0 = Fr::mul(t0, scale);
-                t2 = Fr::mul(t2, scale);
-                t3 = Fr::mul(t3, scale);
-            }
+            layer_eq_at(NESTED, E1, E1_half, E2, c, e, scale);
+            fe t0, t2, t3;
+            layer_terms<NC>(v[0], v[1], v[2], v[3], e, NESTED, scale, t0, t2, t3);
             s0 = Fr::add(s0, t0);
             s2 = Fr::add(s2, t2);
             s3 = Fr::add(s3, t3);
         }
     }
-    s0 = fr_block_sum(s0, sh4);
-    if (threadIdx.x == 0) fe_store(partial + blockIdx.x, s0);
-    s2 = fr_block_sum(s2, sh4);
-    if (threadIdx.x == 0) fe_store(partial + gridDim.x + blockIdx.x, s2);
-    s3 = fr_block_sum(s3, sh4);
-    if (threadIdx.x == 0) fe_store(partial + 2 * gridDim.x + blockIdx.x, s3);
+    layer_finish(s0, s2, s3, sh4, [&](unsigned k) { return partial + k * gridDim.x + blockIdx.x; });
 }
 
 // ---- the layer kernels on the 9 x 29 multiplier (round 3, fr9.hip.hpp): same thread mapping and tails as k_layer_cubic /
@@ -784,15 +803,10 @@ __global__ void __launch_bounds__(RT) k_layer_round_small(const fe* __restrict__
     if (do_bind) {
         size_t nch_in = (len_in + 3) / 4;
         for (size_t c = threadIdx.x; c < nch_in; c += RT) {
-            Sh<NC> u0 = sh_load_or_zero<NC>(ia, ib, 4 * c, len_in), u1 = sh_load_or_zero<NC>(ia, ib, 4 * c + 1, len_in);
-            Sh<NC> u2 = sh_load_or_zero<NC>(ia, ib, 4 * c + 2, len_in), u3 = sh_load_or_zero<NC>(ia, ib, 4 * c + 3, len_in);
-            sh_store<NC>(oa, ob, 2 * c, sh_lerp<NC>(u0, u2, r));
-            sh_store<NC>(oa, ob, 2 * c + 1, sh_lerp<NC>(u1, u3, r));
+            Sh<NC> lo, hi;
+            layer_bind_chunk<NC>(ia, ib, len_in, c, r, oa, ob, lo, hi);
         }
-        for (size_t i = threadIdx.x; i < fold_n; i += RT) {
-            fe lo = fe_load(fold_in + 2 * i), hi = fe_load(fold_in + 2 * i + 1);
-            fe_store(fold_out + i, Fr::add(lo, Fr::mul(Fr::sub(hi, lo), r)));
-        }
+        for (size_t i = threadIdx.x; i < fold_n; i += RT) fe_store(fold_out + i, fold_pair(fold_in, i, r));
         __syncthreads();
         if (scale_n) {  // E1 just collapsed to one value: it multiplies E2 from now on
             fe s = fe_load(fold_out);
@@ -800,6 +814,8 @@ __global__ void __launch_bounds__(RT) k_layer_round_small(const fe* __restrict__
             __syncthreads();
         }
     }
+    // This kernel spills (232 / 760 bytes per lane) and its spill size moves with layer_chunk_count and layer_eq_at in place of
+    // the next lines, so the clamp and the eq pair stay written out here until the kernel is out of scratch.
     size_t nch = (len + 3) / 4;
     size_t limit = nested ? E1_half * E2_len : E2_len / 2;
     if (nch > limit) nch = limit;
@@ -816,27 +832,13 @@ __global__ void __launch_bounds__(RT) k_layer_round_small(const fe* __restrict__
         }
         Sh<NC> l0 = sh_load_or_zero<NC>(ca, cb, 4 * c, len), r0 = sh_load_or_zero<NC>(ca, cb, 4 * c + 1, len);
         Sh<NC> l1 = sh_load_or_zero<NC>(ca, cb, 4 * c + 2, len), r1 = sh_load_or_zero<NC>(ca, cb, 4 * c + 3, len);
-        Sh<NC> ml = sh_sub<NC>(l1, l0), mr = sh_sub<NC>(r1, r0);
-        Sh<NC> l2 = sh_add<NC>(l1, ml), r2 = sh_add<NC>(r1, mr);
-        Sh<NC> l3 = sh_add<NC>(l2, ml), r3 = sh_add<NC>(r2, mr);
-        fe t0 = Fr::mul(sh_local_mul<NC>(l0, r0), e[0]);
-        fe t2 = Fr::mul(sh_local_mul<NC>(l2, r2), e[1]);
-        fe t3 = Fr::mul(sh_local_mul<NC>(l3, r3), e[2]);
-        if (nested) {
-            t0 = Fr::mul(t0, scale);
-            t2 = Fr::mul(t2, scale);
-            t3 = Fr::mul(t3, scale);
-        }
+        fe t0, t2, t3;
+        layer_terms<NC>(l0, r0, l1, r1, e, nested, scale, t0, t2, t3);
         s0 = Fr::add(s0, t0);
         s2 = Fr::add(s2, t2);
         s3 = Fr::add(s3, t3);
     }
-    s0 = fr_block_sum(s0, sh16);
-    if (threadIdx.x == 0) fe_store(res, s0);
-    s2 = fr_block_sum(s2, sh16);
-    if (threadIdx.x == 0) fe_store(res + 1, s2);
-    s3 = fr_block_sum(s3, sh16);
-    if (threadIdx.x == 0) fe_store(res + 2, s3);
+    layer_finish(s0, s2, s3, sh16, [&](unsigned k) { return res + k; });
 }
 
 // ------------------------------------------------------------------ layer groups (cozk_layer_group_*)
@@ -879,10 +881,7 @@ __global__ void __launch_bounds__(RT) k_layer_group_round_small(LayerGroupArgs a
         ca = oa;
         cb = ob;
     }
-    size_t nch = (len + 3) / 4;
-    size_t limit = nested ? E1_half * E2_len : E2_len / 2;
-    if (nch > limit) nch = limit;  // zip() stops at the shorter side
-    const bool on = c < nch;
+    const bool on = c < layer_chunk_count(len, nested, E1_half, E2_len);
     // The terms of k_layer_round_small, (L(X) x R(X)) eq(X) [E2[x2]] at X = 0, 2, 3, with the E2 factor multiplied into eq(X) first:
     // the same field elements, and every stored result is canonical, so the bytes are the same.  The lane's eq pair, and (nested)
     // the E2 entry that multiplies it:
@@ -1036,10 +1035,8 @@ __global__ void __launch_bounds__(RT) k_layer_rounds_persistent(fe* la0, fe* lb0
             fe *oa = la[1 - lcur], *ob = lb[1 - lcur];
             size_t nch_in = (len + 3) / 4;
             for (size_t c = threadIdx.x; c < nch_in; c += RT) {
-                Sh<NC> u0 = sh_load_or_zero<NC>(ia, ib, 4 * c, len), u1 = sh_load_or_zero<NC>(ia, ib, 4 * c + 1, len);
-                Sh<NC> u2 = sh_load_or_zero<NC>(ia, ib, 4 * c + 2, len), u3 = sh_load_or_zero<NC>(ia, ib, 4 * c + 3, len);
-                sh_store<NC>(oa, ob, 2 * c, sh_lerp<NC>(u0, u2, r));
-                sh_store<NC>(oa, ob, 2 * c + 1, sh_lerp<NC>(u1, u3, r));
+                Sh<NC> lo, hi;
+                layer_bind_chunk<NC>(ia, ib, len, c, r, oa, ob, lo, hi);
             }
             lcur = 1 - lcur;
             len = 2 * nch_in;
@@ -1050,10 +1047,7 @@ __global__ void __launch_bounds__(RT) k_layer_rounds_persistent(fe* la0, fe* lb0
                 fe* out = e2[1 - c2];
                 // from the LAST thread down: the fold runs on other waves than the layer's bind instead of behind it in the same
                 // lanes (a tiny round's bind phase was two dependent load -> product -> store chains back to back: 4.9 us)
-                for (size_t i = RT - 1 - threadIdx.x; i < n; i += RT) {
-                    fe lo = fe_load(in + 2 * i), hi = fe_load(in + 2 * i + 1);
-                    fe_store(out + i, Fr::add(lo, Fr::mul(Fr::sub(hi, lo), r)));
-                }
+                for (size_t i = RT - 1 - threadIdx.x; i < n; i += RT) fe_store(out + i, fold_pair(in, i, r));
                 c2 = 1 - c2;
                 E2_len = n;
                 __syncthreads();
@@ -1061,10 +1055,7 @@ __global__ void __launch_bounds__(RT) k_layer_rounds_persistent(fe* la0, fe* lb0
                 size_t n = E1_len / 2;
                 const fe* in = e1[c1];
                 fe* out = e1[1 - c1];
-                for (size_t i = RT - 1 - threadIdx.x; i < n; i += RT) {
-                    fe lo = fe_load(in + 2 * i), hi = fe_load(in + 2 * i + 1);
-                    fe_store(out + i, Fr::add(lo, Fr::mul(Fr::sub(hi, lo), r)));
-                }
+                for (size_t i = RT - 1 - threadIdx.x; i < n; i += RT) fe_store(out + i, fold_pair(in, i, r));
                 c1 = 1 - c1;
                 E1_len = n;
                 __syncthreads();
@@ -1104,9 +1095,7 @@ __global__ void __launch_bounds__(RT) k_layer_rounds_persistent(fe* la0, fe* lb0
         const fe *E1 = e1[c1], *E2 = e2[c2];
         const bool nested = E1_len != 1;
         const size_t E1_half = E1_len / 2;
-        size_t nch = (len + 3) / 4;
-        size_t limit = nested ? E1_half * E2_len : E2_len / 2;
-        if (nch > limit) nch = limit;
+        const size_t nch = layer_chunk_count(len, nested, E1_half, E2_len);
         const int wave = threadIdx.x >> 6;
         const int pt = wave / 5;  // 0, 1, 2 = evaluation at 0, 2, 3; wave 15 idles
         fe acc = Fr::zero();
@@ -1419,8 +1408,7 @@ __global__ void __launch_bounds__(PT) k_sparse_matvec3_rows(const uint32_t* __re
 __global__ void __launch_bounds__(PT) k_fold_pairs(const fe* __restrict__ in, fe* __restrict__ out, size_t n_out, fe r) {
     size_t i = (size_t)blockIdx.x * PT + threadIdx.x;
     if (i >= n_out) return;
-    fe lo = fe_load(in + 2 * i), hi = fe_load(in + 2 * i + 1);
-    fe_store(out + i, Fr::add(lo, Fr::mul(Fr::sub(hi, lo), r)));
+    fe_store(out + i, fold_pair(in, i, r));
 }
 __global__ void __launch_bounds__(PT) k_fold_halves(fe* __restrict__ v, size_t n_out, fe r) {
     size_t i = (size_t)blockIdx.x * PT + threadIdx.x;
@@ -1587,7 +1575,8 @@ static void finish_sums(cozk_ctx* ctx, const SumLaunch& sl, unsigned rows, unsig
     fetch_fe(ctx, sl.res, sl.n_res, out);
 }
 
-// make ping-pong side `which` of a polynomial or layer hold n elements (both components of a Rep3 object)
+// make ping-pong side `which` of a polynomial or layer hold n elements (both components of a Rep3 object), from and to the pool of
+// the object's own context, whichever context's call is running
 template <class P>
 static void pingpong_ensure(P* p, int which, size_t n) {
     if (p->cap[which] >= n) return;
@@ -1595,9 +1584,27 @@ static void pingpong_ensure(P* p, int which, size_t n) {
         if (p->buf[which][c]) ctx_dev_free(p->ctx, p->buf[which][c]);
         p->buf[which][c] = nullptr;
     }
-    p->buf[which][0] = dev_alloc_fe(n);
-    if (p->mode == COZK_MODE_REP3) p->buf[which][1] = dev_alloc_fe(n);
+    const size_t bytes = (n ? n : 1) * sizeof(fe);
+    p->buf[which][0] = (fe*)ctx_dev_alloc(p->ctx, bytes);
+    if (p->mode == COZK_MODE_REP3) p->buf[which][1] = (fe*)ctx_dev_alloc(p->ctx, bytes);
     p->cap[which] = n;
+}
+
+// One bind of a layer, everything but the kernel: the other ping-pong side is made to hold the bound layer, the layer moves on to it,
+// and the launcher gets what it reads and writes (component b null for PLAIN).
+struct LayerStep {
+    const fe *ia, *ib;
+    fe *oa, *ob;
+    size_t len_in, len_out;
+};
+static LayerStep layer_advance(cozk_layer* l) {
+    const int dst = 1 - l->cur;
+    const size_t len_out = 2 * ((l->len + 3) / 4);
+    pingpong_ensure(l, dst, len_out);
+    const LayerStep s{l->buf[l->cur][0], l->buf[l->cur][1], l->buf[dst][0], l->buf[dst][1], l->len, len_out};
+    l->cur = dst;
+    l->len = len_out;
+    return s;
 }
 
 // the round polynomial of compute_cubic through the evaluations [g0, claim - g0, g2, g3] (dense_interleaved_poly.rs:349-365): its four
@@ -2282,18 +2289,10 @@ int cozk_layer_as_poly(cozk_ctx* ctx, const cozk_layer* l, cozk_poly** out) {
 int cozk_layer_bind(cozk_ctx* ctx, cozk_layer* l, const uint64_t r[4]) {
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(ctx && l && r && l->len >= 2, "layer_bind: bad argument");
-        size_t nch = (l->len + 3) / 4;
-        size_t nout = 2 * nch;
-        int dst = 1 - l->cur;
-        pingpong_ensure(l, dst, nout);
-        fe rr = fe_from_u64x4(r);
-        if (l->mode == COZK_MODE_REP3)
-            k_layer_bind<2><<<grid_for(nch), PT, 0, ctx->stream>>>(l->buf[l->cur][0], l->buf[l->cur][1], l->buf[dst][0], l->buf[dst][1], l->len, rr);
-        else
-            k_layer_bind<1><<<grid_for(nch), PT, 0, ctx->stream>>>(l->buf[l->cur][0], nullptr, l->buf[dst][0], nullptr, l->len, rr);
+        const LayerStep b = layer_advance(l);
+        auto* const kernel = l->mode == COZK_MODE_REP3 ? k_layer_bind<2> : k_layer_bind<1>;
+        kernel<<<grid_for(b.len_out / 2), PT, 0, ctx->stream>>>(b.ia, b.ib, b.oa, b.ob, b.len_in, fe_from_u64x4(r));
         HIP_TRY(hipGetLastError());
-        l->cur = dst;
-        l->len = nout;
     });
 }
 
@@ -2339,20 +2338,43 @@ int cozk_spliteq_lens(const cozk_spliteq* e, size_t* e1_len, size_t* e2_len) {
 
 // SplitEqPolynomial::bind(r)
 static bool spliteq_bound(const cozk_spliteq* e) { return e->E1_len == 1 && e->E2_len < 2; }
-// the fold launches of one bind on ctx's stream (one, or two when E1 collapses); the caller has checked !spliteq_bound(e)
-static void spliteq_bind_launch(cozk_ctx* ctx, cozk_spliteq* e, const fe& rr) {
+// One bind, everything but the kernels, and the ONE place that does it: E1 folds until it is a single value, then E2; the folded
+// table flips its ping-pong side and halves.  The launcher gets the fold, and, when E1 has just collapsed, the vector that its last
+// value fold_out[0] multiplies from now on (E2).  The resident kernel does the same steps on the device; the host follows it with
+// this function.  The caller has checked !spliteq_bound(e).
+struct SpliteqStep {
+    const fe* fold_in;
+    fe* fold_out;
+    size_t fold_n;
+    fe* scale_vec;  // null unless E1 has just collapsed
+    size_t scale_n;
+};
+static SpliteqStep spliteq_advance(cozk_spliteq* e) {
+    SpliteqStep s{};
     if (e->E1_len == 1) {
-        size_t n = e->E2_len / 2;
-        k_fold_pairs<<<grid_for(n), PT, 0, ctx->stream>>>(e->E2[e->c2], e->E2[1 - e->c2], n, rr);
+        s.fold_in = e->E2[e->c2];
+        s.fold_out = e->E2[1 - e->c2];
+        s.fold_n = e->E2_len / 2;
         e->c2 = 1 - e->c2;
-        e->E2_len = n;
+        e->E2_len = s.fold_n;
     } else {
-        size_t n = e->E1_len / 2;
-        k_fold_pairs<<<grid_for(n), PT, 0, ctx->stream>>>(e->E1[e->c1], e->E1[1 - e->c1], n, rr);
+        s.fold_in = e->E1[e->c1];
+        s.fold_out = e->E1[1 - e->c1];
+        s.fold_n = e->E1_len / 2;
         e->c1 = 1 - e->c1;
-        e->E1_len = n;
-        if (n == 1) k_scale_by_first<<<grid_for(e->E2_len), PT, 0, ctx->stream>>>(e->E2[e->c2], e->E2_len, e->E1[e->c1]);
+        e->E1_len = s.fold_n;
+        if (s.fold_n == 1) {
+            s.scale_vec = e->E2[e->c2];
+            s.scale_n = e->E2_len;
+        }
     }
+    return s;
+}
+// the fold launches of one bind on ctx's stream (one, or two when E1 collapses)
+static void spliteq_bind_launch(cozk_ctx* ctx, cozk_spliteq* e, const fe& rr) {
+    const SpliteqStep s = spliteq_advance(e);
+    k_fold_pairs<<<grid_for(s.fold_n), PT, 0, ctx->stream>>>(s.fold_in, s.fold_out, s.fold_n, rr);
+    if (s.scale_n) k_scale_by_first<<<grid_for(s.scale_n), PT, 0, ctx->stream>>>(s.scale_vec, s.scale_n, s.fold_out);
     HIP_TRY(hipGetLastError());
 }
 int cozk_spliteq_bind(cozk_ctx* ctx, cozk_spliteq* e, const uint64_t r[4]) {
@@ -2443,19 +2465,8 @@ static LayerBindCubicPlan layer_bind_cubic_plan(cozk_ctx* ctx, const cozk_layer*
     const LayerBindCubicKernel kernel = layer_bind_cubic_kernel(l->mode, v);
     return LayerBindCubicPlan{v, kernel, layer_sum_grid(ctx, (const void*)kernel, v.f9, nch_out)};
 }
-// allocations made for `c`'s objects while another context's ABI call runs on this thread
-struct PoolOf {
-    cozk_ctx* prev;
-    explicit PoolOf(cozk_ctx* c) : prev(t_cur_ctx) { t_cur_ctx = c; }
-    ~PoolOf() { t_cur_ctx = prev; }
-};
 static void layer_bind_cubic_launch(cozk_ctx* ctx, cozk_layer* l, const cozk_spliteq* e, const LayerBindCubicPlan& p, const uint64_t r[4], fe* partial) {
-    const size_t nout = 2 * ((l->len + 3) / 4);
-    const int dst = 1 - l->cur;
-    {
-        PoolOf own(l->ctx);
-        pingpong_ensure(l, dst, nout);
-    }
+    const LayerStep b = layer_advance(l);
     fe rr = fe_from_u64x4(r);
     if (p.v.f9)
         for (int d = 0; d < 5; d++) rr = Fr::dbl(rr);  // the 9 x 29 kernels take the challenge times 2^5 = 1 / lambda (fr9.hip.hpp)
@@ -2463,12 +2474,10 @@ static void layer_bind_cubic_launch(cozk_ctx* ctx, cozk_layer* l, const cozk_spl
     {
         // algorithmic bytes: the layer read once and its bound half written once (SURVEY 8d K3 + K4 fused), + the eq tables
         const uint64_t S = rep3 ? 64 : 32;
-        ProfScope prof(ctx, COZK_PROF_BIND_CUBIC, (uint64_t)l->len * S + (uint64_t)nout * S + (uint64_t)(e->E1_len + e->E2_len) * 32);
-        p.kernel<<<p.gx, PT, 0, ctx->stream>>>(l->buf[l->cur][0], rep3 ? l->buf[l->cur][1] : nullptr, l->buf[dst][0], rep3 ? l->buf[dst][1] : nullptr, l->len, rr,
-                                               e->E1[e->c1], p.v.nested ? e->E1_len / 2 : 0, e->E2[e->c2], e->E2_len, partial);
+        ProfScope prof(ctx, COZK_PROF_BIND_CUBIC, (uint64_t)b.len_in * S + (uint64_t)b.len_out * S + (uint64_t)(e->E1_len + e->E2_len) * 32);
+        p.kernel<<<p.gx, PT, 0, ctx->stream>>>(b.ia, b.ib, b.oa, b.ob, b.len_in, rr, e->E1[e->c1], p.v.nested ? e->E1_len / 2 : 0, e->E2[e->c2], e->E2_len,
+                                               partial);
     }
-    l->cur = dst;
-    l->len = nout;
 }
 
 int cozk_layer_compute_cubic(cozk_ctx* ctx, const cozk_layer* l, const cozk_spliteq* eq, const uint64_t prev_claim[4],
@@ -2502,56 +2511,24 @@ int cozk_layer_round(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const uint64
         });
     }
     return cozk_guard(ctx, [&] {
-        const fe *ia = l->buf[l->cur][0], *ib = l->buf[l->cur][1];
-        fe *oa = nullptr, *ob = nullptr;
-        size_t len_in = l->len;
-        const fe* fold_in = nullptr;
-        fe* fold_out = nullptr;
-        size_t fold_n = 0, scale_n = 0;
-        fe* scale_vec = nullptr;
-        fe rr = Fr::zero();
+        // every refusal comes before the first change to the layer or the eq polynomial
         if (r) {
             COZK_REQUIRE(l->len >= 2, "layer_round: layer already fully bound");
-            rr = fe_from_u64x4(r);
-            size_t nout = 2 * ((l->len + 3) / 4);
-            int dst = 1 - l->cur;
-            pingpong_ensure(l, dst, nout);
-            oa = l->buf[dst][0];
-            ob = l->buf[dst][1];
-            l->cur = dst;
-            l->len = nout;
-            // SplitEqPolynomial::bind bookkeeping (cozk_spliteq_bind)
-            if (e->E1_len == 1) {
-                COZK_REQUIRE(e->E2_len >= 2, "layer_round: eq polynomial already fully bound");
-                fold_n = e->E2_len / 2;
-                fold_in = e->E2[e->c2];
-                fold_out = e->E2[1 - e->c2];
-                e->c2 = 1 - e->c2;
-                e->E2_len = fold_n;
-            } else {
-                fold_n = e->E1_len / 2;
-                fold_in = e->E1[e->c1];
-                fold_out = e->E1[1 - e->c1];
-                e->c1 = 1 - e->c1;
-                e->E1_len = fold_n;
-                if (fold_n == 1) {
-                    scale_vec = e->E2[e->c2];
-                    scale_n = e->E2_len;
-                }
-            }
+            COZK_REQUIRE(!spliteq_bound(e), "layer_round: eq polynomial already fully bound");
         }
-        const fe* ca = l->buf[l->cur][0];
-        const fe* cb = l->buf[l->cur][1];
-        const fe* E1 = e->E1[e->c1];
-        const fe* E2 = e->E2[e->c2];
-        int nested = e->E1_len != 1;
+        LayerStep b{};
+        SpliteqStep f{};
+        fe rr = Fr::zero();
+        if (r) {
+            rr = fe_from_u64x4(r);
+            b = layer_advance(l);
+            f = spliteq_advance(e);
+        }
         fe* res = result_slot(ctx, 3);
-        if (l->mode == COZK_MODE_REP3)
-            k_layer_round_small<2><<<1, RT, 0, ctx->stream>>>(ia, ib, oa, ob, len_in, r != nullptr, rr, fold_in, fold_out, fold_n, scale_vec, scale_n, ca, cb,
-                                                             l->len, E1, e->E1_len / 2, E2, e->E2_len, nested, res);
-        else
-            k_layer_round_small<1><<<1, RT, 0, ctx->stream>>>(ia, nullptr, oa, nullptr, len_in, r != nullptr, rr, fold_in, fold_out, fold_n, scale_vec, scale_n,
-                                                             ca, nullptr, l->len, E1, e->E1_len / 2, E2, e->E2_len, nested, res);
+        auto* const kernel = l->mode == COZK_MODE_REP3 ? k_layer_round_small<2> : k_layer_round_small<1>;
+        kernel<<<1, RT, 0, ctx->stream>>>(b.ia, b.ib, b.oa, b.ob, b.len_in, r != nullptr, rr, f.fold_in, f.fold_out, f.fold_n, f.scale_vec, f.scale_n,
+                                          l->buf[l->cur][0], l->buf[l->cur][1], l->len, e->E1[e->c1], e->E1_len / 2, e->E2[e->c2], e->E2_len, e->E1_len != 1,
+                                          res);
         HIP_TRY(hipGetLastError());
         fe sres[3];
         fetch_fe(ctx, res, 3, sres);
@@ -2615,8 +2592,8 @@ int cozk_layer_prove_rounds(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const
             const bool rep3 = l->mode == COZK_MODE_REP3;
             auto* const kernel = rep3 ? (trace_rounds() ? k_layer_rounds_persistent<2, 1> : k_layer_rounds_persistent<2, 0>)
                                       : (trace_rounds() ? k_layer_rounds_persistent<1, 1> : k_layer_rounds_persistent<1, 0>);
-            kernel<<<1, RT, 0, ctx->stream>>>(l->buf[0][0], rep3 ? l->buf[0][1] : nullptr, l->buf[1][0], rep3 ? l->buf[1][1] : nullptr, l->cur, l->len, e->E1[0],
-                                              e->E1[1], e->c1, e->E1_len, e->E2[0], e->E2[1], e->c2, e->E2_len, nrem, have_r ? 1 : 0, r_first, mb, ticks);
+            kernel<<<1, RT, 0, ctx->stream>>>(l->buf[0][0], l->buf[0][1], l->buf[1][0], l->buf[1][1], l->cur, l->len, e->E1[0], e->E1[1], e->c1, e->E1_len,
+                                              e->E2[0], e->E2[1], e->c2, e->E2_len, nrem, have_r ? 1 : 0, r_first, mb, ticks);
             HIP_TRY(hipGetLastError());
             volatile uint32_t* res_seq = &mb->res_seq;
             volatile uint32_t* status = &mb->status;
@@ -2640,18 +2617,12 @@ int cozk_layer_prove_rounds(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const
                 std::atomic_thread_fence(std::memory_order_acquire);
                 return true;
             };
-            // mirror the kernel's bookkeeping: one bind per completed round (+ the pending one it started with)
+            // mirror the kernel's bookkeeping: one bind per completed round (+ the pending one it started with), by the steps the
+            // launchers take (both ping-pong sides hold the layer already, so nothing is allocated)
             auto mirror_binds = [&](int binds) {
                 for (int b = 0; b < binds; b++) {
-                    l->len = 2 * ((l->len + 3) / 4);
-                    l->cur = 1 - l->cur;
-                    if (e->E1_len == 1) {
-                        e->E2_len /= 2;
-                        e->c2 = 1 - e->c2;
-                    } else {
-                        e->E1_len /= 2;
-                        e->c1 = 1 - e->c1;
-                    }
+                    (void)layer_advance(l);
+                    (void)spliteq_advance(e);
                 }
             };
             const int bind_first = have_r ? 1 : 0;
@@ -2795,7 +2766,6 @@ int cozk_layer_group_create(cozk_ctx* driver, cozk_layer* const* layers, int k, 
         }
         for (int i = 0; i < k; i++) {  // the other ping-pong side, once: later rounds allocate nothing
             cozk_layer* l = layers[i];
-            PoolOf own(l->ctx);
             pingpong_ensure(l, 1 - l->cur, 2 * ((l->len + 3) / 4));
         }
         cozk_layer_group* g = new cozk_layer_group();
@@ -2809,6 +2779,26 @@ int cozk_layer_group_create(cozk_ctx* driver, cozk_layer* const* layers, int k, 
 int cozk_layer_group_free(cozk_layer_group* g) {
     delete g;
     return COZK_OK;
+}
+
+// the pointer tables of one launch over members 0 .. k - 1; bind: every member moves on to its other ping-pong side (layer_advance)
+static LayerGroupArgs layer_group_args(const cozk_layer_group* g, size_t k, bool bind) {
+    LayerGroupArgs a;
+    memset(&a, 0, sizeof a);
+    for (size_t m = 0; m < k; m++) {
+        cozk_layer* l = g->m[m];
+        if (bind) {
+            const LayerStep b = layer_advance(l);
+            a.ia[m] = b.ia;
+            a.ib[m] = b.ib;
+            a.oa[m] = b.oa;
+            a.ob[m] = b.ob;
+        } else {
+            a.ia[m] = l->buf[l->cur][0];
+            a.ib[m] = l->buf[l->cur][1];
+        }
+    }
+    return a;
 }
 
 int cozk_layer_group_round(cozk_layer_group* g, cozk_spliteq* e, const uint64_t* r, const uint64_t prev_claim[4], uint64_t* out_coeffs) {
@@ -2841,37 +2831,18 @@ int cozk_layer_group_round(cozk_layer_group* g, cozk_spliteq* e, const uint64_t*
                 finish_sums(ctx, sl, 3 * k, p.gx, Fr::one(), 0, s);
             }
         } else {
-            const size_t nout = 2 * ((len + 3) / 4);
-            LayerGroupArgs a;
-            memset(&a, 0, sizeof a);
-            for (unsigned m = 0; m < k; m++) {
-                cozk_layer* l = g->m[m];
-                a.ia[m] = l->buf[l->cur][0];
-                a.ib[m] = rep3 ? l->buf[l->cur][1] : nullptr;
-                if (!r) continue;
-                {
-                    PoolOf own(l->ctx);
-                    pingpong_ensure(l, 1 - l->cur, nout);
-                }
-                a.oa[m] = l->buf[1 - l->cur][0];
-                a.ob[m] = rep3 ? l->buf[1 - l->cur][1] : nullptr;
-            }
+            const LayerGroupArgs a = layer_group_args(g, k, r != nullptr);
             fe rr = Fr::zero();
             if (r) {
                 rr = fe_from_u64x4(r);
                 spliteq_bind_launch(ctx, e, rr);  // once for all members, in front of their launch on the same stream
             }
-            const size_t len_now = r ? nout : len;
+            const size_t len_now = g->m[0]->len;
             const int nested = e->E1_len != 1;
             fe* res = result_slot(ctx, (size_t)3 * k);
             auto* const kernel = rep3 ? k_layer_group_round_small<2> : k_layer_group_round_small<1>;
             kernel<<<k, RT, 0, ctx->stream>>>(a, len, r != nullptr, rr, len_now, e->E1[e->c1], e->E1_len / 2, e->E2[e->c2], e->E2_len, nested, res);
             HIP_TRY(hipGetLastError());
-            if (r)
-                for (cozk_layer* l : g->m) {
-                    l->cur = 1 - l->cur;
-                    l->len = nout;
-                }
             fetch_fe(ctx, res, (size_t)3 * k, s);
         }
         for (unsigned m = 0; m < k; m++) cubic_coeffs_out(s + 3 * m, prev_claim, out_coeffs + 16 * m);
@@ -2890,20 +2861,7 @@ int cozk_layer_group_final(cozk_layer_group* g, cozk_spliteq* e, const uint64_t*
         if (r) COZK_REQUIRE(!spliteq_bound(e), "layer_group_final: eq polynomial already fully bound");
         const bool rep3 = g->mode == COZK_MODE_REP3;
         const int nc = rep3 ? 2 : 1;
-        LayerGroupArgs a;
-        memset(&a, 0, sizeof a);
-        for (int m = 0; m < k_final; m++) {
-            cozk_layer* l = g->m[(size_t)m];
-            a.ia[m] = l->buf[l->cur][0];
-            a.ib[m] = rep3 ? l->buf[l->cur][1] : nullptr;
-            if (!r) continue;
-            {
-                PoolOf own(l->ctx);
-                pingpong_ensure(l, 1 - l->cur, 2);
-            }
-            a.oa[m] = l->buf[1 - l->cur][0];
-            a.ob[m] = rep3 ? l->buf[1 - l->cur][1] : nullptr;
-        }
+        const LayerGroupArgs a = layer_group_args(g, (size_t)k_final, r != nullptr);  // len <= 4 binds to 2 elements
         fe rr = Fr::zero();
         if (r) {
             rr = fe_from_u64x4(r);
@@ -2918,11 +2876,6 @@ int cozk_layer_group_final(cozk_layer_group* g, cozk_spliteq* e, const uint64_t*
         auto* const kernel = rep3 ? k_layer_group_final<2> : k_layer_group_final<1>;
         kernel<<<k_final, GFT, 0, ctx->stream>>>(a, len, r != nullptr, rr, res);
         HIP_TRY(hipGetLastError());
-        if (r)
-            for (int m = 0; m < k_final; m++) {
-                g->m[(size_t)m]->cur = 1 - g->m[(size_t)m]->cur;
-                g->m[(size_t)m]->len = 2;
-            }
         fe h[4 * COZK_LAYER_GROUP_MAX];
         fetch_fe(ctx, res, n_res, h);
         for (int m = 0; m < k_final; m++) {  // the layout of cozk_layer_final_claims: L.a, L.b, R.a, R.b (b = 0 for PLAIN)

@@ -178,6 +178,26 @@ def test_layer_round_fused_equals_separate_calls(cozk, ctx, mode, length):
     assert fused.coeffs() == sep.coeffs()
 
 
+@pytest.mark.parametrize("mode", ["rep3", "plain"])
+def test_layer_round_refusal_leaves_layer_and_eq_untouched(cozk, ctx, mode):
+    """cozk_layer_round with a challenge and an eq polynomial that is already fully bound is refused before the layer or the eq
+    polynomial moves: 8 elements over one variable (E1_len = 2, E2_len = 1) are down to 4 elements and E1_len = 1 after the second
+    round, and the third call raises and leaves both exactly there."""
+    rng = O.SplitMix64(77 + (mode == "plain"))
+    layer = cozk.Rep3DenseInterleavedPolynomial.new(ctx, _shares(rng, 8, mode))
+    eq = cozk.SplitEqPolynomial(ctx, [rng.field()])
+    assert eq.lens() == (2, 1)
+    claim = rng.field()
+    layer.round(eq, None, claim)
+    layer.round(eq, rng.field(), claim)
+    coeffs, lens = layer.coeffs(), eq.lens()
+    assert len(coeffs) == 4 and lens == (1, 1)
+    with pytest.raises(cozk.CozkError):
+        layer.round(eq, rng.field(), claim)
+    assert layer.coeffs() == coeffs
+    assert eq.lens() == lens
+
+
 @pytest.mark.parametrize("resident", [True, False])
 @pytest.mark.parametrize("mode", ["rep3", "plain"])
 @pytest.mark.parametrize("length", [4, 6, 96, 2048, 4096 + 8, 1 << 14])
