@@ -10,7 +10,8 @@ from .engine import (Context, Vec, Bases, FR_MOD, FQ_MOD, fr_to_mont_limbs, mont
                      shamir_eval, shamir_lagrange, shamir_combine, shamir_combine_points, shamir_mul,
                      shamir_rand_deal, shamir_rand_extract, shamir_rand, shamir_mul_king, shamir_mul_pairs, shamir_gp_prove,
                      shamir_king_finish, shamir_mul_king_pairs, shamir_gp_prep, shamir_gp_prove_king, ShamirGpPrep, ShamirGpPrepResult,
-                     ShamirGpProof, ShamirGpResult, ShamirGpStats)
+                     ShamirGpProof, ShamirGpResult, ShamirGpStats, ShamirGpToggleStats, shamir_tgp_prove, shamir_tgp_prep,
+                     shamir_tgp_prove_king)
 from .poly import (Rep3DensePolynomial, Rep3DenseInterleavedPolynomial, SplitEqPolynomial, LayerGroup, eq_evals,
                    open_quadratic_evals, pst_fold, prod_sumcheck_evals, spartan_first_round, spartan_second_round,
                    sparse_matvec3, fingerprint_leaves, rep3_mul_vec_local)

@@ -160,6 +160,11 @@ SIGNATURES = {
     "cozk_shamir_gp_prep_free": (_i, [_vp]),
     "cozk_shamir_gp_prep_get_result": (_i, [_vp, _vp]),
     "cozk_shamir_gp_prove_king_inproc": (_i, [_vp, _vp, _sz, _vp, _i, ctypes.c_char_p, _i, _pp]),
+    "cozk_shamir_tgp_prove_inproc": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _i, _u64, _u64, ctypes.c_char_p, _i, _pp]),
+    "cozk_shamir_tgp_prep_inproc": (_i, [_vp, _vp, _sz, _sz, _i, _i, _u64, _pp]),
+    "cozk_shamir_tgp_prove_king_inproc": (_i, [_vp, _vp, _sz, _vp, _vp, _i, ctypes.c_char_p, _i, _pp]),
+    "cozk_shamir_gp_toggle_claims": (_i, [_vp, _vp, _vp]),
+    "cozk_shamir_gp_get_toggle_stats": (_i, [_vp, _vp]),
     "cozk_shamir_combine_points": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, ctypes.POINTER(_i)]),
     "cozk_layer_round": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "cozk_fingerprint_leaves": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _i, _i, _vp, _vp, _sz, _sz]),
@@ -169,6 +174,12 @@ SIGNATURES = {
     "cozk_layer_group_round": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "cozk_layer_group_final": (_i, [_vp, _vp, _vp, _i, _vp]),
     "cozk_layer_group_free": (_i, [_vp]),
+    "cozk_toggle_group_create": (_i, [_vp, _vp, _sz, _vp, _i, _i, _pp]),
+    "cozk_toggle_group_layer_outputs": (_i, [_vp, _vp, _vp]),
+    "cozk_toggle_group_round": (_i, [_vp, _vp, _vp, _vp]),
+    "cozk_toggle_group_bind": (_i, [_vp, _vp]),
+    "cozk_toggle_group_final_claims": (_i, [_vp, _vp, _vp, _i]),
+    "cozk_toggle_group_free": (_i, [_vp]),
     "cozk_layer_output_local": (_i, [_vp, _vp, _i, ctypes.c_char_p, ctypes.c_char_p, _u64, _pp]),
     "cozk_rep3_mul_vec_local": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, ctypes.c_char_p, ctypes.c_char_p, _u64, _pp]),
     "cozk_layer_claimed_outputs": (_i, [_vp, _vp, _vp]),

@@ -28,6 +28,15 @@
 // into a preprocessing object, and the construct becomes layer[i + 1] = cozk_shamir_mul_king_pairs_inproc(layer[i]) on slices of
 // those pairs.  Both provers are one construct loop with the level's multiplication as a parameter (shamir_gp_construct) in front
 // of one copy of the openings, rounds, finals, transcript and proof (shamir_gp_prove_layers).
+//
+// The TOGGLED grand product (cozk_shamir_tgp_*; tests/shamir_tgp_ref.py) puts the toggle layer of Lasso's read / write memory checking
+// under that tree.  Its flags are public, so its output flag ? fingerprint : 1 and its round polynomial eq (flag fingerprint + 1 - flag)
+// are AFFINE in the fingerprint share: a party that runs the PLAIN toggle calls on its degree-t share, with the public claim as its
+// previous claim, holds a degree-t sharing of the plain prover's values (the share of a public constant is that constant for every
+// party, which is what PLAIN mode adds).  Level 0 of the tree is the senders' toggle outputs; the dense layers run as above; the
+// toggle layer's nv + d rounds follow (no r_layer, no claim fold), opened from senders 0..2t with 4 (nv + d) more of the same zero
+// masks; the flag claim is public and the fingerprint claim is opened from parties 0..t, unmasked.  The senders' toggle layers run
+// as ONE cozk_toggle_group on sender 0's context under the same rule as the layer groups, otherwise as a cozk_toggle per sender.
 #pragma once
 #include "prover.hpp"
 #include "runner.hpp"
@@ -45,6 +54,9 @@ struct cozk_shamir_gp {
     std::vector<fe> finals;  // [layer, top first][p <= t][L, R]
     cozk_shamir_gp_result res;
     cozk_shamir_gp_stats stats{};
+    bool toggled = false;  // a toggled proof: the toggle layer's final claims and how its rounds ran
+    fe tg_flag, tg_fingerprint;
+    cozk_shamir_gp_toggle_stats tstats{};
 };
 
 namespace cozk {
@@ -72,6 +84,7 @@ struct ShamirGpArgs {
     int t, n;
     const char* label;
     bool verify;
+    bool adopt_leaves = false;  // the leaves are vectors of our own (a toggled proof's level 0): adopted, not copied
 };
 
 static inline void shamir_gp_sync_all(const ShamirGpArgs& a) {
@@ -79,6 +92,7 @@ static inline void shamir_gp_sync_all(const ShamirGpArgs& a) {
 }
 
 typedef Handle<cozk_layer_group, cozk_layer_group_free> GroupH;
+typedef Handle<cozk_toggle_group, cozk_toggle_group_free> ToggleGroupH;
 
 // Whether the rounds run as layer groups (cozk_layer_group_*): one launch per round for all senders instead of one per sender, one
 // fold of the public eq tables instead of 2t + 1.  That needs every sender's context on ONE device (one group per device for
@@ -119,9 +133,9 @@ static double shamir_gp_construct(const ShamirGpArgs& a, std::vector<std::vector
         if (i + 1 < num_layers) mul_level(i, v.data(), next.data());
         std::vector<VecH> nx((size_t)a.n);
         for (int p = 0; p < a.n; p++) nx[(size_t)p] = VecH(next[(size_t)p]);
-        for (int p = 0; p < senders; p++) {  // level 0 is copied (the caller keeps its leaves), a level of our own is adopted
+        for (int p = 0; p < senders; p++) {  // the caller's leaves are copied (it keeps them), a level of our own is adopted
             cozk_layer* l = nullptr;
-            rc_check(cozk_layer_create(a.pcs[p], COZK_MODE_PLAIN, v[(size_t)p], nullptr, i ? 1 : 0, &l), a.pcs[p], "layer_create");
+            rc_check(cozk_layer_create(a.pcs[p], COZK_MODE_PLAIN, v[(size_t)p], nullptr, i || a.adopt_leaves ? 1 : 0, &l), a.pcs[p], "layer_create");
             layers[(size_t)i].push_back(LayerH(l));
         }
         cur = std::move(nx);
@@ -156,10 +170,65 @@ static std::vector<std::vector<fe>> shamir_gp_zero_masks(const ShamirGpArgs& a, 
     return zero;
 }
 
+// ---- the toggle layer of a toggled proof: ONE group on sender 0's context (grouped) or a PLAIN cozk_toggle per sender, and the
+// senders' toggle outputs, level 0 of the tree
+struct ShamirToggleLayer {
+    ToggleGroupH group;
+    std::vector<ToggleH> toggles;
+    std::vector<VecH> outputs;  // [p <= 2t], a vector of pcs[p]
+    size_t rounds = 0;          // nv + d
+};
+
+// the openings the toggle layer adds to the dense tree's: 4 per round, nv + d rounds
+static inline size_t shamir_tgp_rounds(size_t n_pairs, size_t n_per) { return (size_t)(ceil_log2(2 * n_pairs) + ceil_log2(n_per)); }
+
+// flags: n_pairs U8 columns of pcs[0]; fingerprints[p]: sender p's shares.  Grouped: the group refers to the senders' fingerprints
+// (they are only read) and writes every sender's output in one launch.  Otherwise sender p gets the flags on its own context, a
+// toggle of its own for the rounds, and its output from a one-plane group driven by its own context (the one output kernel)
+static void shamir_tgp_make_toggle(const ShamirGpArgs& a, const cozk_vec* const* flags, size_t n_pairs, const cozk_vec* const* fingerprints, bool grouped,
+                                   ShamirToggleLayer& tg) {
+    const int senders = 2 * a.t + 1;
+    tg.rounds = shamir_tgp_rounds(n_pairs, fingerprints[0]->n / (2 * n_pairs));
+    tg.outputs.resize((size_t)senders);
+    shamir_gp_sync_all(a);
+    if (grouped) {
+        cozk_vec* fps[COZK_SHAMIR_MAX_PARTIES];
+        cozk_vec* outs[COZK_SHAMIR_MAX_PARTIES];
+        for (int p = 0; p < senders; p++) fps[p] = const_cast<cozk_vec*>(fingerprints[p]);  // take_ownership = 0: read only
+        rc_check(cozk_toggle_group_create(a.pcs[0], flags, n_pairs, fps, senders, 0, &tg.group.h), a.pcs[0], "toggle_group_create");
+        rc_check(cozk_toggle_group_layer_outputs(tg.group.h, a.pcs, outs), a.pcs[0], "toggle_group_layer_outputs");
+        for (int p = 0; p < senders; p++) tg.outputs[(size_t)p] = VecH(outs[p]);
+        return;
+    }
+    tg.toggles.resize((size_t)senders);
+    for (int p = 0; p < senders; p++) {
+        std::vector<VecH> own;  // the flags on sender p's context
+        std::vector<const cozk_vec*> fl(n_pairs);
+        for (size_t q = 0; q < n_pairs; q++) {
+            fl[q] = flags[q];
+            if (a.pcs[p] == a.pcs[0]) continue;
+            cozk_vec* c = nullptr;
+            rc_check(cozk_vec_alloc(a.pcs[p], flags[q]->n, COZK_SCALAR_U8, &c), a.pcs[p], "vec_alloc");
+            own.emplace_back(c);
+            HIP_TRY(hipMemcpy(c->d, flags[q]->d, flags[q]->n, hipMemcpyDefault));
+            fl[q] = c;
+        }
+        cozk_vec* fp = const_cast<cozk_vec*>(fingerprints[p]);
+        cozk_vec* out = nullptr;
+        ToggleGroupH one;
+        rc_check(cozk_toggle_group_create(a.pcs[p], fl.data(), n_pairs, &fp, 1, 0, &one.h), a.pcs[p], "toggle_group_create");
+        rc_check(cozk_toggle_group_layer_outputs(one.h, a.pcs + p, &out), a.pcs[p], "toggle_group_layer_outputs");
+        tg.outputs[(size_t)p] = VecH(out);
+        rc_check(cozk_toggle_create(a.pcs[p], COZK_MODE_PLAIN, fl.data(), n_pairs, fp, nullptr, 0, &tg.toggles[(size_t)p].h), a.pcs[p], "toggle_create");
+        rc_check(cozk_ctx_synchronize(a.pcs[p]), a.pcs[p], "ctx_synchronize");  // the copies of the flags go out of scope
+    }
+}
+
 // ---- openings, rounds, finals, transcript and proof on constructed layers with given masks: what both constructs share.
+// tg != null: a toggled proof -- the toggle layer's rounds and claims follow the dense layers
 // t_prove_ms runs from t_start (the caller's clock, every stream drained) to the drain behind the last round
 static void shamir_gp_prove_layers(const ShamirGpArgs& a, std::vector<std::vector<LayerH>>& layers, const std::vector<std::vector<fe>>& zero, double t_start,
-                                   cozk_shamir_gp& h) {
+                                   cozk_shamir_gp& h, ShamirToggleLayer* tg = nullptr) {
     const int senders = 2 * a.t + 1, openers = a.t + 1;
     const int num_layers = (int)layers.size();
     const size_t M = zero[0].size();
@@ -263,6 +332,78 @@ static void shamir_gp_prove_layers(const ShamirGpArgs& a, std::vector<std::vecto
         proof.gkr_layers.push_back(std::move(lp));
         layers[(size_t)i].clear();  // bound: nothing reads it again
     }
+    if (tg) {
+        // prove_layer of the toggle layer as coordinate_prove_toggle_layer sees it: nv + d rounds against eq(r), no r_layer and no claim
+        // fold.  Sender p's four coefficients are unipoly_from_evals(g0, claim - g0, g2, g3) of its PLAIN toggle round with the public
+        // claim: a degree-t sharing of the plain prover's, opened with the degree-2t zero masks from senders 0..2t
+        GrandProductLayerProof lp;
+        const int num_rounds = (int)r.size();
+        COZK_REQUIRE((size_t)num_rounds == tg->rounds, "shamir_tgp: the toggle layer's rounds do not match the point");
+        std::vector<uint64_t> w = to_abi(r);
+        std::vector<EqH> eqs((size_t)(grouped ? 1 : senders));
+        for (size_t p = 0; p < eqs.size(); p++) rc_check(cozk_spliteq_new(a.pcs[p], w.data(), num_rounds, &eqs[p].h), a.pcs[p], "spliteq_new");
+        std::vector<fe> r_sumcheck;
+        uint64_t rj[4];
+        std::vector<uint64_t> ev((size_t)12 * senders);
+        for (int j = 0; j < num_rounds; j++) {
+            fe cf[4][COZK_SHAMIR_MAX_PARTIES];
+            if (grouped) {
+                rc_check(cozk_toggle_group_round(tg->group.h, eqs[0].h, j ? rj : nullptr, ev.data()), a.pcs[0], "toggle_group_round");
+                h.tstats.toggle_group_rounds++;
+            } else {
+                for (int p = 0; p < senders; p++) {
+                    rc_check(cozk_toggle_round(a.pcs[p], tg->toggles[(size_t)p].h, eqs[(size_t)p].h, j ? rj : nullptr, 0, ev.data() + 12 * p), a.pcs[p],
+                             "toggle_round");
+                    h.tstats.toggle_single_rounds++;
+                }
+            }
+            for (int p = 0; p < senders; p++) {
+                const fe g0 = fe_from_u64x4(ev.data() + 12 * p);
+                const fe pts[4] = {g0, Fr::sub(claim, g0), fe_from_u64x4(ev.data() + 12 * p + 4), fe_from_u64x4(ev.data() + 12 * p + 8)};
+                fe c4[4];
+                unipoly_from_evals(pts, 4, c4);
+                for (int k = 0; k < 4; k++) cf[k][p] = c4[k];
+            }
+            std::vector<fe> poly(4);
+            for (int k = 0; k < 4; k++) poly[(size_t)k] = open_2t(cf[k]);
+            std::vector<fe> comp = unipoly_compress(poly);
+            tr.append_scalars(comp);
+            fe r_j = tr.challenge_scalar();
+            r_sumcheck.push_back(r_j);
+            fe_to_u64x4(r_j, rj);
+            claim = unipoly_eval(poly, r_j);
+            lp.proof.compressed_polys.push_back(comp);
+        }
+        // the last bind and the final claims: the flag is public, the fingerprint is opened from the t + 1 openers, unmasked
+        uint64_t flag[4], fps[4 * COZK_SHAMIR_MAX_PARTIES], unused[4];
+        if (grouped) {
+            rc_check(cozk_toggle_group_bind(tg->group.h, rj), a.pcs[0], "toggle_group_bind");
+            rc_check(cozk_toggle_group_final_claims(tg->group.h, flag, fps, openers), a.pcs[0], "toggle_group_final_claims");
+        } else {
+            for (int p = 0; p < openers; p++) {
+                cozk_toggle* t = tg->toggles[(size_t)p].h;
+                rc_check(cozk_toggle_bind(a.pcs[p], t, rj), a.pcs[p], "toggle_bind");
+                rc_check(cozk_toggle_final_claims(a.pcs[p], t, p ? unused : flag, fps + 4 * p, nullptr), a.pcs[p], "toggle_final_claims");
+            }
+        }
+        fe sh[COZK_SHAMIR_MAX_PARTIES];
+        lp.left_claim = fe_from_u64x4(flag);
+        for (int p = 0; p < openers; p++) {
+            sh[p] = fe_from_u64x4(fps + 4 * p);
+            h.finals.push_back(lp.left_claim);
+            h.finals.push_back(sh[p]);
+        }
+        lp.right_claim = shamir_open(lamt, sh);
+        tr.append_scalar(lp.left_claim);
+        tr.append_scalar(lp.right_claim);
+        r.assign(r_sumcheck.rbegin(), r_sumcheck.rend());
+        proof.gkr_layers.push_back(std::move(lp));
+        h.toggled = true;
+        h.tg_flag = proof.gkr_layers.back().left_claim;
+        h.tg_fingerprint = proof.gkr_layers.back().right_claim;
+        tg->group = ToggleGroupH();
+        tg->toggles.clear();
+    }
     COZK_REQUIRE(m_next == M, "shamir_gp: fewer openings than masks");
     shamir_gp_sync_all(a);
     h.res.t_prove_ms = now_ms() - t_start;
@@ -273,26 +414,33 @@ static void shamir_gp_prove_layers(const ShamirGpArgs& a, std::vector<std::vecto
     h.claim = claim;
     h.r = r;
     h.res.proof_len = h.proof.size();
-    h.res.n_layers = num_layers;
+    h.res.n_layers = num_layers + (tg ? 1 : 0);
     h.res.n_opened = M;
     h.res.verified = -1;
     if (a.verify) {
         Transcript vt(a.label);
         fe vc;
         std::vector<fe> vr;
-        bool ok = verify_grand_product(proof, vt, vc, vr) && Fr::eq(vc, claim) && vr.size() == r.size();
+        bool ok;
+        if (tg) {
+            fe vf, vp;
+            ok = verify_toggled_grand_product(proof, vt, vf, vp, vr) && Fr::eq(vf, h.tg_flag) && Fr::eq(vp, h.tg_fingerprint) && vr.size() == r.size();
+        } else {
+            ok = verify_grand_product(proof, vt, vc, vr) && Fr::eq(vc, claim) && vr.size() == r.size();
+        }
         for (size_t k = 0; ok && k < r.size(); k++) ok = Fr::eq(vr[k], r[k]);
         h.res.verified = ok ? 1 : 0;
     }
 }
 
 // what both provers require of their arguments once degree and num_parties are known to be in range
-static void shamir_gp_require_leaves(const std::string& w, cozk_ctx* const* party_ctxs, const cozk_vec* const* leaves, int degree, const char* missing) {
+static void shamir_gp_require_leaves(const std::string& w, cozk_ctx* const* party_ctxs, const cozk_vec* const* leaves, int degree, const char* missing,
+                                     const std::string& what = "leaves") {
     for (int p = 0; p <= 2 * degree; p++) {
         COZK_REQUIRE(leaves[p], w + missing);
-        COZK_REQUIRE(leaves[p]->kind == COZK_SCALAR_FR, w + ": the leaves must be FR vectors");
-        COZK_REQUIRE(leaves[p]->n == leaves[0]->n, w + ": the leaves must have one length");
-        COZK_REQUIRE(leaves[p]->ctx == party_ctxs[p], w + ": party p's leaves must be a vector of party_ctxs[p]");
+        COZK_REQUIRE(leaves[p]->kind == COZK_SCALAR_FR, w + ": the " + what + " must be FR vectors");
+        COZK_REQUIRE(leaves[p]->n == leaves[0]->n, w + ": the " + what + " must have one length");
+        COZK_REQUIRE(leaves[p]->ctx == party_ctxs[p], w + ": party p's " + what + " must be a vector of party_ctxs[p]");
     }
 }
 static void shamir_gp_require_shape(const std::string& w, size_t n, size_t batch_size) {
@@ -318,6 +466,7 @@ struct cozk_shamir_gp_prep {
     int t = 0, n = 0, pairs = 0;
     size_t n_leaves = 0, batch_size = 0, pair_elems = 0;
     bool used = false;
+    bool toggled = false;  // made by cozk_shamir_tgp_prep_inproc: 4 (nv + d) more masks, the construct pairs behind them
     double t_offline_ms = 0;
     std::vector<std::vector<fe>> zero;  // [p <= 2t][m < M]
     std::vector<cozk_vec*> rt, r2t;     // rt[q * pairs + k], every party; r2t[p * pairs + k], senders
@@ -330,16 +479,14 @@ struct cozk_shamir_gp_prep {
     ~cozk_shamir_gp_prep() { release_pairs(); }
 };
 
-extern "C" {
-
-int cozk_shamir_gp_prep_inproc(cozk_ctx* const* party_ctxs, const uint8_t* const* rand_keys, size_t n_leaves, size_t batch_size, int degree,
-                               int num_parties, uint64_t rand_counter, cozk_shamir_gp_prep** prep) {
+// both preps: the dense tree of (n_leaves, batch_size) with toggle_rounds more rounds' masks (0: a dense proof's prep)
+static int shamir_gp_prep_make(const std::string& w, cozk_ctx* const* party_ctxs, const uint8_t* const* rand_keys, size_t n_leaves, size_t batch_size,
+                               size_t toggle_rounds, bool toggled, int degree, int num_parties, uint64_t rand_counter, cozk_shamir_gp_prep** prep) {
     using namespace cozk;
     cozk_ctx* const c0 = party_ctxs && num_parties >= 1 && num_parties <= COZK_SHAMIR_MAX_PARTIES ? party_ctxs[0] : nullptr;  // receives the error message
-    int rc = cozk_guard(c0, [&] { COZK_REQUIRE(prep, "shamir_gp_prep_inproc: null output"); });
+    int rc = cozk_guard(c0, [&] { COZK_REQUIRE(prep, w + ": null output"); });
     if (rc != COZK_OK) return rc;
     *prep = nullptr;
-    const std::string w = "shamir_gp_prep_inproc";
     rc = cozk_guard(c0, [&] {
         COZK_REQUIRE(party_ctxs && rand_keys, w + ": null argument");
         shamir_gp_require_parties(w, degree, num_parties);
@@ -347,6 +494,7 @@ int cozk_shamir_gp_prep_inproc(cozk_ctx* const* party_ctxs, const uint8_t* const
             COZK_REQUIRE(party_ctxs[p], w + ": null party context");
             COZK_REQUIRE(rand_keys[p], w + ": every party needs its mask key block");
         }
+        if (toggled) COZK_REQUIRE(n_leaves > 0, w + ": n_pairs > 0 and N a power of two >= 2");
         shamir_gp_require_shape(w, n_leaves, batch_size);
     });
     if (rc != COZK_OK) return rc;
@@ -356,11 +504,12 @@ int cozk_shamir_gp_prep_inproc(cozk_ctx* const* party_ctxs, const uint8_t* const
         const int senders = 2 * degree + 1, levels = ceil_log2(n_leaves / batch_size) - 1;
         h->pcs.assign(party_ctxs, party_ctxs + num_parties);
         h->t = degree, h->n = num_parties, h->n_leaves = n_leaves, h->batch_size = batch_size;
+        h->toggled = toggled;
         h->pairs = levels <= 0 ? 0 : levels == 1 ? 1 : 2;
         h->pair_elems = h->pairs ? n_leaves / 2 : 0;
         shamir_gp_sync_all(a);
         const double t0 = now_ms();
-        const size_t M = shamir_gp_num_openings(n_leaves, batch_size);
+        const size_t M = shamir_gp_num_openings(n_leaves, batch_size) + 4 * toggle_rounds;
         h->zero = shamir_gp_zero_masks(a, rand_keys, rand_counter, M);
         if (h->pairs) {
             h->rt.assign((size_t)num_parties * h->pairs, nullptr);
@@ -379,6 +528,50 @@ int cozk_shamir_gp_prep_inproc(cozk_ctx* const* party_ctxs, const uint8_t* const
     }
     *prep = h;
     return COZK_OK;
+}
+
+// the king's tree level on slices of a prep's pairs: pair 0 serves level 0 whole, pair 1 the levels above at their offsets
+static auto shamir_gp_king_level(cozk_ctx* const* party_ctxs, cozk_shamir_gp_prep* prep, int king) {
+    return [=](int i, const cozk_vec* const* v, cozk_vec** next) {
+        const int k = i ? 1 : 0, num_parties = prep->n;
+        std::vector<const cozk_vec*> rt((size_t)num_parties, nullptr), r2t((size_t)num_parties, nullptr);
+        for (int q = 0; q < num_parties; q++) rt[(size_t)q] = prep->rt[(size_t)q * prep->pairs + k];
+        for (int p = 0; p <= 2 * prep->t; p++) r2t[(size_t)p] = prep->r2t[(size_t)p * prep->pairs + k];
+        const size_t off = i ? prep->n_leaves / 2 - (prep->n_leaves >> i) : 0;
+        cozk::rc_check(cozk_shamir_mul_king_pairs_inproc(party_ctxs, v, rt.data(), r2t.data(), off, prep->t, num_parties, king, next), party_ctxs[0],
+                       "shamir_mul_king_pairs_inproc");
+    };
+}
+
+// what the toggled provers require of the flags and the fingerprints once the parties are known to be in range
+static void shamir_tgp_require_inputs(const std::string& w, cozk_ctx* const* party_ctxs, const cozk_vec* const* flags, size_t n_pairs,
+                                      const cozk_vec* const* fingerprints, int degree) {
+    using namespace cozk;
+    COZK_REQUIRE(n_pairs > 0, w + ": n_pairs == 0");
+    shamir_gp_require_leaves(w, party_ctxs, fingerprints, degree, ": parties 0..2 * degree need their fingerprints", "fingerprints");
+    const size_t batch = 2 * n_pairs, total = fingerprints[0]->n;
+    COZK_REQUIRE(total % batch == 0, w + ": fingerprints.len() must be 2 * n_pairs * N");
+    const size_t per = total / batch;
+    COZK_REQUIRE(per >= 2 && (per & (per - 1)) == 0, w + ": fingerprints per circuit must be a power of two >= 2");
+    for (size_t q = 0; q < n_pairs; q++) {
+        COZK_REQUIRE(flags[q] && flags[q]->kind == COZK_SCALAR_U8 && flags[q]->n == per, w + ": every flag column is a U8 vector of N entries");
+        COZK_REQUIRE(flags[q]->ctx == party_ctxs[0], w + ": the flag columns must be vectors of party_ctxs[0]");
+    }
+}
+
+extern "C" {
+
+int cozk_shamir_gp_prep_inproc(cozk_ctx* const* party_ctxs, const uint8_t* const* rand_keys, size_t n_leaves, size_t batch_size, int degree,
+                               int num_parties, uint64_t rand_counter, cozk_shamir_gp_prep** prep) {
+    return shamir_gp_prep_make("shamir_gp_prep_inproc", party_ctxs, rand_keys, n_leaves, batch_size, 0, false, degree, num_parties, rand_counter, prep);
+}
+
+// n_per = N fingerprints per circuit: the dense tree above the toggle layer has 2 n_pairs N leaves in 2 n_pairs circuits
+int cozk_shamir_tgp_prep_inproc(cozk_ctx* const* party_ctxs, const uint8_t* const* rand_keys, size_t n_pairs, size_t n_per, int degree, int num_parties,
+                                uint64_t rand_counter, cozk_shamir_gp_prep** prep) {
+    const bool shape = n_pairs > 0 && n_per >= 2 && (n_per & (n_per - 1)) == 0;  // otherwise n_leaves = 0, refused with its text
+    return shamir_gp_prep_make("shamir_tgp_prep_inproc", party_ctxs, rand_keys, shape ? 2 * n_pairs * n_per : 0, 2 * n_pairs,
+                               shape ? cozk::shamir_tgp_rounds(n_pairs, n_per) : 0, true, degree, num_parties, rand_counter, prep);
 }
 
 int cozk_shamir_gp_prep_free(cozk_shamir_gp_prep* prep) {
@@ -406,6 +599,7 @@ int cozk_shamir_gp_prove_king_inproc(cozk_ctx* const* party_ctxs, const cozk_vec
     const std::string w = "shamir_gp_prove_king_inproc";
     rc = cozk_guard(c0, [&] {
         COZK_REQUIRE(party_ctxs && leaves && prep && label, w + ": null argument");
+        COZK_REQUIRE(!prep->toggled, w + ": the preprocessing was made for a toggled grand product (cozk_shamir_tgp_prove_king_inproc)");
         COZK_REQUIRE(king >= 0 && king < prep->n, w + ": 0 <= king < num_parties");
         for (int p = 0; p < prep->n; p++) {
             COZK_REQUIRE(party_ctxs[p], w + ": null party context");
@@ -423,17 +617,8 @@ int cozk_shamir_gp_prove_king_inproc(cozk_ctx* const* party_ctxs, const cozk_vec
     memset(&h->res, 0, sizeof h->res);
     rc = cozk_guard(c0, [&] {
         const ShamirGpArgs a{party_ctxs, leaves, batch_size, prep->t, num_parties, label, verify != 0};
-        const size_t half = prep->n_leaves / 2;
         std::vector<std::vector<LayerH>> layers;
-        h->res.t_construct_ms = shamir_gp_construct(a, layers, [&](int i, const cozk_vec* const* v, cozk_vec** next) {
-            const int k = i ? 1 : 0;  // pair 0 serves level 0 whole, pair 1 the levels above at their offsets
-            std::vector<const cozk_vec*> rt((size_t)num_parties, nullptr), r2t((size_t)num_parties, nullptr);
-            for (int q = 0; q < num_parties; q++) rt[(size_t)q] = prep->rt[(size_t)q * prep->pairs + k];
-            for (int p = 0; p <= 2 * prep->t; p++) r2t[(size_t)p] = prep->r2t[(size_t)p * prep->pairs + k];
-            const size_t off = i ? half - (prep->n_leaves >> i) : 0;
-            rc_check(cozk_shamir_mul_king_pairs_inproc(party_ctxs, v, rt.data(), r2t.data(), off, prep->t, num_parties, king, next), c0,
-                     "shamir_mul_king_pairs_inproc");
-        });
+        h->res.t_construct_ms = shamir_gp_construct(a, layers, shamir_gp_king_level(party_ctxs, prep, king));
         prep->release_pairs();  // consumed: every stream has drained behind the construct
         shamir_gp_prove_layers(a, layers, prep->zero, now_ms(), *h);
     });
@@ -487,6 +672,139 @@ int cozk_shamir_gp_prove_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* con
         return rc;
     }
     *out = h;
+    return COZK_OK;
+}
+
+}  // extern "C"
+
+// The toggled provers: the toggle layer and its outputs (level 0, adopted), the construct with the level's multiplication as a
+// parameter, the masks, and the one copy of the openings, rounds, finals, transcript and proof.  t_construct_ms includes the
+// toggle outputs.
+template <class MulLevel, class Masks>
+static void shamir_tgp_prove(const cozk::ShamirGpArgs& a0, const cozk_vec* const* flags, size_t n_pairs, const cozk_vec* const* fingerprints, MulLevel mul_level,
+                             Masks masks, cozk_shamir_gp& h) {
+    using namespace cozk;
+    shamir_gp_sync_all(a0);
+    const double t0 = now_ms();
+    ShamirToggleLayer tg;
+    shamir_tgp_make_toggle(a0, flags, n_pairs, fingerprints, shamir_gp_grouped(a0), tg);
+    std::vector<const cozk_vec*> level0((size_t)a0.n, nullptr);
+    for (int p = 0; p <= 2 * a0.t; p++) level0[(size_t)p] = tg.outputs[(size_t)p].h;
+    ShamirGpArgs a = a0;
+    a.leaves = level0.data();
+    a.adopt_leaves = true;
+    std::vector<std::vector<LayerH>> layers;
+    shamir_gp_construct(a, layers, mul_level);
+    tg.outputs.clear();  // adopted by level 0
+    h.res.t_construct_ms = now_ms() - t0;
+    const double t1 = now_ms();
+    const std::vector<std::vector<fe>>& zero = masks();
+    shamir_gp_prove_layers(a, layers, zero, t1, h, &tg);
+}
+
+extern "C" {
+
+int cozk_shamir_tgp_prove_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* flags, size_t n_pairs, const cozk_vec* const* fingerprints,
+                                 const uint8_t* const* mul_keys, const uint8_t* const* rand_keys, int degree, int num_parties, uint64_t mul_counter,
+                                 uint64_t rand_counter, const char* label, int verify, cozk_shamir_gp** out) {
+    using namespace cozk;
+    cozk_ctx* const c0 = party_ctxs && num_parties >= 1 && num_parties <= COZK_SHAMIR_MAX_PARTIES ? party_ctxs[0] : nullptr;  // receives the error message
+    const std::string w = "shamir_tgp_prove_inproc";
+    int rc = cozk_guard(c0, [&] { COZK_REQUIRE(out, w + ": null output"); });
+    if (rc != COZK_OK) return rc;
+    *out = nullptr;
+    rc = cozk_guard(c0, [&] {
+        COZK_REQUIRE(party_ctxs && flags && fingerprints && mul_keys && rand_keys && label, w + ": null argument");
+        shamir_gp_require_parties(w, degree, num_parties);
+        for (int p = 0; p < num_parties; p++) {
+            COZK_REQUIRE(party_ctxs[p], w + ": null party context");
+            COZK_REQUIRE(rand_keys[p], w + ": every party needs its mask key block");
+        }
+        for (int p = 0; p <= 2 * degree; p++) COZK_REQUIRE(fingerprints[p] && mul_keys[p], w + ": parties 0..2 * degree need their fingerprints and their key block");
+        shamir_tgp_require_inputs(w, party_ctxs, flags, n_pairs, fingerprints, degree);
+    });
+    if (rc != COZK_OK) return rc;
+    cozk_shamir_gp* h = new cozk_shamir_gp();
+    memset(&h->res, 0, sizeof h->res);
+    rc = cozk_guard(c0, [&] {
+        const size_t batch = 2 * n_pairs, n_leaves = fingerprints[0]->n;
+        const ShamirGpArgs a{party_ctxs, nullptr, batch, degree, num_parties, label, verify != 0};
+        uint64_t ctr = mul_counter;  // level i: mul_counter + the sum of the earlier levels' output lengths
+        std::vector<std::vector<fe>> zero;
+        shamir_tgp_prove(
+            a, flags, n_pairs, fingerprints,
+            [&](int, const cozk_vec* const* v, cozk_vec** next) {
+                rc_check(cozk_shamir_mul_pairs_inproc(party_ctxs, v, mul_keys, degree, num_parties, ctr, next), c0, "shamir_mul_pairs_inproc");
+                ctr += v[0]->n / 2;
+            },
+            [&]() -> const std::vector<std::vector<fe>>& {
+                zero = shamir_gp_zero_masks(a, rand_keys, rand_counter, shamir_gp_num_openings(n_leaves, batch) + 4 * shamir_tgp_rounds(n_pairs, n_leaves / batch));
+                return zero;
+            },
+            *h);
+    });
+    if (rc != COZK_OK) {
+        for (int p = 0; p < num_parties; p++) (void)hipStreamSynchronize(party_ctxs[p]->stream);
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return COZK_OK;
+}
+
+int cozk_shamir_tgp_prove_king_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* flags, size_t n_pairs, const cozk_vec* const* fingerprints,
+                                      cozk_shamir_gp_prep* prep, int king, const char* label, int verify, cozk_shamir_gp** out) {
+    using namespace cozk;
+    cozk_ctx* const c0 = party_ctxs ? party_ctxs[0] : nullptr;  // receives the error message (a prover has at least three parties)
+    const std::string w = "shamir_tgp_prove_king_inproc";
+    int rc = cozk_guard(c0, [&] { COZK_REQUIRE(out, w + ": null output"); });
+    if (rc != COZK_OK) return rc;
+    *out = nullptr;
+    rc = cozk_guard(c0, [&] {
+        COZK_REQUIRE(party_ctxs && flags && fingerprints && prep && label, w + ": null argument");
+        COZK_REQUIRE(prep->toggled, w + ": the preprocessing was made for a dense grand product (cozk_shamir_gp_prove_king_inproc)");
+        COZK_REQUIRE(king >= 0 && king < prep->n, w + ": 0 <= king < num_parties");
+        for (int p = 0; p < prep->n; p++) {
+            COZK_REQUIRE(party_ctxs[p], w + ": null party context");
+            COZK_REQUIRE(party_ctxs[p] == prep->pcs[(size_t)p], w + ": the preprocessing was made for other party contexts");
+        }
+        shamir_tgp_require_inputs(w, party_ctxs, flags, n_pairs, fingerprints, prep->t);
+        COZK_REQUIRE(fingerprints[0]->n == prep->n_leaves && 2 * n_pairs == prep->batch_size, w + ": the preprocessing was made for another (n_pairs, N)");
+        COZK_REQUIRE(!prep->used, w + ": the preprocessing has been used (a pair must never be used twice)");
+    });
+    if (rc != COZK_OK) return rc;
+    const int num_parties = prep->n;
+    prep->used = true;
+    cozk_shamir_gp* h = new cozk_shamir_gp();
+    memset(&h->res, 0, sizeof h->res);
+    rc = cozk_guard(c0, [&] {
+        const ShamirGpArgs a{party_ctxs, nullptr, 2 * n_pairs, prep->t, num_parties, label, verify != 0};
+        shamir_tgp_prove(a, flags, n_pairs, fingerprints, shamir_gp_king_level(party_ctxs, prep, king),
+                         [&]() -> const std::vector<std::vector<fe>>& {
+                             prep->release_pairs();  // consumed: every stream has drained behind the construct
+                             return prep->zero;
+                         },
+                         *h);
+    });
+    if (rc != COZK_OK) {
+        for (int p = 0; p < num_parties; p++) (void)hipStreamSynchronize(party_ctxs[p]->stream);
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return COZK_OK;
+}
+
+int cozk_shamir_gp_toggle_claims(const cozk_shamir_gp* h, uint64_t flag[4], uint64_t fingerprint[4]) {
+    if (!h || !flag || !fingerprint || !h->toggled) return COZK_ERR_INVALID_ARG;  // a dense proof has no toggle layer
+    fe_to_u64x4(h->tg_flag, flag);
+    fe_to_u64x4(h->tg_fingerprint, fingerprint);
+    return COZK_OK;
+}
+
+int cozk_shamir_gp_get_toggle_stats(const cozk_shamir_gp* h, cozk_shamir_gp_toggle_stats* stats) {
+    if (!h || !stats) return COZK_ERR_INVALID_ARG;
+    *stats = h->tstats;
     return COZK_OK;
 }
 

@@ -366,6 +366,182 @@ __global__ void __launch_bounds__(RT) k_toggle_eq_sums(const fe* __restrict__ E1
     }
 }
 
+// ------------------------------------------------------------------ toggle groups (cozk_toggle_group_*)
+// ONE PLAIN toggle layer with k fingerprint planes over ONE copy of the public flags: the senders of a Shamir prover
+// (csrc/host/shamir_gp.hpp).  The flags are public and the toggle layer's output and round polynomial are affine in the
+// fingerprints, so everything but the fingerprint loads and the products A_m(X) = sum eq * flag * fp_m is the same for every
+// member: the flag look, the compaction, the eq weights, the flag interpolation, C(X) and S_all(X) are done once.  The planes'
+// pointers travel in the kernel arguments as LayerGroupArgs' do (one table of COZK_LAYER_GROUP_MAX pointers, indexed by
+// wave-uniform values: scalar loads, nothing staged).
+struct ToggleGroupIn {
+    const fe* p[COZK_LAYER_GROUP_MAX];
+};
+struct ToggleGroupOut {
+    fe* p[COZK_LAYER_GROUP_MAX];
+};
+
+// k_toggle_output (PLAIN, one = 1) for every member: the flag byte is read once per element
+__global__ void __launch_bounds__(PT) k_toggle_group_output(ToggleGroupIn in, ToggleGroupOut out, const uint8_t* __restrict__ fl, int log_n, size_t total, int k) {
+    size_t idx = (size_t)blockIdx.x * PT + threadIdx.x;
+    if (idx >= total) return;
+    size_t b = idx >> log_n, i = idx & (((size_t)1 << log_n) - 1);
+    const bool on = fl[((b >> 1) << log_n) + i] != 0;
+    const fe one = Fr::one();
+    for (int m = 0; m < k; m++) fe_store(out.p[m] + idx, on ? fe_load(in.p[m] + idx) : one);
+}
+
+// k_toggle_bind for the k planes (blockIdx.y = member) and, by the workgroups of member 0, the one flag array.  CO = 1: the bind
+// that leaves one entry per circuit writes the coalesced vectors of k_toggle_coalesce directly -- n_fp = n_fl = L entries, circuit
+// c's flag the bound flag pair c >> 1, padded with ones (flags) and zeros (fingerprints) from `batch` upwards.
+template <int FT, int CO>
+__global__ void __launch_bounds__(PT) k_toggle_group_bind(ToggleGroupIn in, fe* __restrict__ out, size_t out_stride, size_t n_fp, const void* __restrict__ fin,
+                                                       fe* __restrict__ fout, size_t n_fl, size_t batch, fe r) {
+    const size_t i = (size_t)blockIdx.x * PT + threadIdx.x;
+    const unsigned m = blockIdx.y;
+    const fe* ia = in.p[m];
+    fe* oa = out + (size_t)m * out_stride;
+    if (CO) {
+        if (i >= n_fp) return;
+        const bool inb = i < batch;
+        if (inb) sh_store<1>(oa, nullptr, i, sh_lerp<1>(sh_load<1>(ia, nullptr, 2 * i), sh_load<1>(ia, nullptr, 2 * i + 1), r));
+        else fe_store(oa + i, Fr::zero());
+        if (m == 0) {
+            fe lo, hi, v = Fr::one();
+            if (inb) v = toggle_flag_pair<FT>(fin, i >> 1, lo, hi) ? Fr::add(lo, Fr::mul(Fr::sub(hi, lo), r)) : Fr::zero();
+            fe_store(fout + i, v);
+        }
+        return;
+    }
+    if (i < n_fp) sh_store<1>(oa, nullptr, i, sh_lerp<1>(sh_load<1>(ia, nullptr, 2 * i), sh_load<1>(ia, nullptr, 2 * i + 1), r));
+    if (m == 0 && i < n_fl) {
+        fe lo, hi;
+        if (toggle_flag_pair<FT>(fin, i, lo, hi)) fe_store(fout + i, Fr::add(lo, Fr::mul(Fr::sub(hi, lo), r)));
+        else fe_store(fout + i, Fr::zero());
+    }
+}
+
+// k_toggle_cubic (PLAIN, Montgomery path) for the members of one chunk: blockIdx.y selects members TOGGLE_GROUP_CHUNK y ..
+// TOGGLE_GROUP_CHUNK (y + 1) - 1 -- 31 members' accumulators (3 field elements each) do not fit a lane, a chunk's do.  The flag look, the
+// per-wave compaction and, per active pair, the eq weights, the flag interpolation and flag x eq are computed once per chunk; the
+// member loop does the two fingerprint loads, eq3 and three multiply-adds.  C(X) is accumulated by chunk 0 only.
+// partial rows: 3 m + X' for A_m (X' = 0, 1, 2 for X = 0, 2, 3), 3 k + X' for C.
+static constexpr int TOGGLE_GROUP_CHUNK = 4;
+template <int NESTED, int FT>
+__global__ void __launch_bounds__(PT) k_toggle_group_cubic(ToggleGroupIn in, int k, const void* __restrict__ fl, size_t npairs, int log_half_n,
+                                                        const fe* __restrict__ E1, int log_E1_half, const fe* __restrict__ E2, size_t E2_len,
+                                                        fe* __restrict__ partial) {
+    __shared__ fe sh4[4];
+    __shared__ uint32_t queue[PT / 64][128];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int m0 = (int)blockIdx.y * TOGGLE_GROUP_CHUNK;
+    const int nm = k - m0 < TOGGLE_GROUP_CHUNK ? k - m0 : TOGGLE_GROUP_CHUNK;  // workgroup-uniform
+    const bool first = blockIdx.y == 0;
+    size_t limit = NESTED ? ((size_t)E2_len << log_E1_half) : E2_len / 2;
+    if (npairs > limit) npairs = limit;
+    fe A[TOGGLE_GROUP_CHUNK][3], C[3];
+#pragma unroll
+    for (int w = 0; w < TOGGLE_GROUP_CHUNK; w++)
+#pragma unroll
+        for (int x = 0; x < 3; x++) A[w][x] = Fr::zero();
+#pragma unroll
+    for (int x = 0; x < 3; x++) C[x] = Fr::zero();
+    int qn = 0;  // wave-uniform
+    const size_t stride = (size_t)gridDim.x * PT;
+    const size_t wave_base0 = (size_t)blockIdx.x * PT + (size_t)wv * 64;
+    auto flag_index = [&](size_t j) {
+        if (log_half_n < 0) return j;
+        const size_t b = j >> log_half_n, i = j & (((size_t)1 << log_half_n) - 1);
+        return ((b >> 1) << log_half_n) + i;
+    };
+    auto heavy = [&](size_t j) __attribute__((always_inline)) {
+        fe e[3];
+        if (NESTED) {
+            size_t x2 = j >> log_E1_half, x1 = j & (((size_t)1 << log_E1_half) - 1);
+            eq3(fe_load(E1 + 2 * x1), fe_load(E1 + 2 * x1 + 1), e);
+            fe sc = fe_load(E2 + x2);
+#pragma unroll
+            for (int x = 0; x < 3; x++) e[x] = Fr::mul(e[x], sc);
+        } else {
+            eq3(fe_load(E2 + 2 * j), fe_load(E2 + 2 * j + 1), e);
+        }
+        fe f0, f1, f[3];
+        (void)toggle_flag_pair<FT>(fl, flag_index(j), f0, f1);
+        eq3(f0, f1, f);
+#pragma unroll
+        for (int x = 0; x < 3; x++) e[x] = Fr::mul(f[x], e[x]);  // flag x eq, once for all members
+        if (first) {
+#pragma unroll
+            for (int x = 0; x < 3; x++) C[x] = Fr::add(C[x], e[x]);
+        }
+#pragma unroll
+        for (int w = 0; w < TOGGLE_GROUP_CHUNK; w++) {
+            if (w < nm) {
+                const fe* pa = in.p[m0 + w];
+                fe p[3];
+                eq3(fe_load(pa + 2 * j), fe_load(pa + 2 * j + 1), p);
+#pragma unroll
+                for (int x = 0; x < 3; x++) A[w][x] = Fr::add(A[w][x], Fr::mul(e[x], p[x]));
+            }
+        }
+    };
+    // ONE call site of the heavy path, so that it is inlined and the accumulators stay in registers: the loop goes on, looking at no
+    // further pairs, until the wave's queue is empty
+    for (size_t jb = wave_base0;; jb += stride) {  // wave-uniform trip count
+        const bool more = jb < npairs;
+        if (more) {
+            const size_t j = jb + lane;
+            bool active = false;
+            if (j < npairs) {
+                const size_t fj = flag_index(j);
+                if (FT == 0) {
+                    active = *(const uint16_t*)((const uint8_t*)fl + 2 * fj) != 0;
+                } else {
+                    fe f0, f1;
+                    active = toggle_flag_pair<FT>(fl, fj, f0, f1);
+                }
+            }
+            const unsigned long long mask = __ballot(active);
+            if (active) queue[wv][qn + __popcll(mask & ((1ull << lane) - 1ull))] = (uint32_t)(j - wave_base0);
+            qn += __popcll(mask);
+            __builtin_amdgcn_wave_barrier();  // the wave's LDS operations execute in program order; this keeps the compiler from moving them
+        }
+        if (qn >= 64 || (!more && qn > 0)) {
+            const int take = qn < 64 ? qn : 64;
+            if (lane < take) heavy(wave_base0 + (size_t)queue[wv][lane]);
+            const uint32_t keep = lane < qn - take ? queue[wv][take + lane] : 0u;
+            __builtin_amdgcn_wave_barrier();
+            if (lane < qn - take) queue[wv][lane] = keep;
+            __builtin_amdgcn_wave_barrier();
+            qn -= take;
+        }
+        if (!more && qn == 0) break;
+    }
+#pragma unroll
+    for (int w = 0; w < TOGGLE_GROUP_CHUNK; w++) {
+        if (w < nm) {
+#pragma unroll
+            for (int x = 0; x < 3; x++) {
+                fe v = fr_block_sum(A[w][x], sh4);
+                if (threadIdx.x == 0) fe_store(partial + (size_t)(3 * (m0 + w) + x) * gridDim.x + blockIdx.x, v);
+            }
+        }
+    }
+    if (first) {
+#pragma unroll
+        for (int x = 0; x < 3; x++) {
+            fe v = fr_block_sum(C[x], sh4);
+            if (threadIdx.x == 0) fe_store(partial + (size_t)(3 * k + x) * gridDim.x + blockIdx.x, v);
+        }
+    }
+}
+
+// the final claims of a fully bound group into the pinned result slot: res[0] = the flag, res[1 + m] = member m's fingerprint
+__global__ void __launch_bounds__(64) k_toggle_group_claims(ToggleGroupIn in, const fe* __restrict__ fl, int k_final, fe* __restrict__ res) {
+    if (threadIdx.x != 0) return;  // one lane: the table is indexed by a uniform value
+    fe_store(res, fe_load(fl));
+    for (int m = 0; m < k_final; m++) fe_store(res + 1 + m, fe_load(in.p[m]));
+}
+
 static inline int log2_sz(size_t n) {
     int l = 0;
     while (((size_t)1 << l) < n) l++;
@@ -632,6 +808,259 @@ int cozk_toggle_download(cozk_ctx* ctx, const cozk_toggle* t, uint64_t* flags, u
         if (fp_b && t->mode == COZK_MODE_REP3) HIP_TRY(hipMemcpyAsync(fp_b, tg_fp(t, 1), nfp * sizeof(fe), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         for (size_t i = 0; i < raw.size(); i++) fe_to_u64x4(raw[i] ? Fr::one() : Fr::zero(), flags + 4 * i);
+    });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ C ABI: toggle groups
+struct cozk_toggle_group {
+    cozk_ctx* driver;
+    int k;
+    size_t batch, n0, n_cur, L;
+    bool coalesced;
+    const fe* fp0[COZK_LAYER_GROUP_MAX];  // unbound fingerprints: adopted (owner != null) or the caller's, which outlive the group
+    cozk_ctx* owner[COZK_LAYER_GROUP_MAX];
+    uint8_t* fl0;                         // packed 0/1 flags (owned)
+    fe* fp[2];                            // ping-pong bound planes: member m at fp[w] + m * fp_cap[w]
+    fe* fl[2];                            // ping-pong bound flags
+    size_t fp_cap[2], fl_cap[2];
+    int cur;                              // -1: unbound
+};
+
+static bool toggle_group_bound(const cozk_toggle_group* g) { return g->coalesced && g->L == 1; }
+static ToggleGroupIn toggle_group_in(const cozk_toggle_group* g) {
+    ToggleGroupIn a;
+    memset(&a, 0, sizeof a);
+    for (int m = 0; m < g->k; m++) a.p[m] = g->cur < 0 ? g->fp0[m] : g->fp[g->cur] + (size_t)m * g->fp_cap[g->cur];
+    return a;
+}
+
+// one bind of the planes and the flags: ONE launch, which at layer_len == 2 writes the coalesced vectors
+static void toggle_group_bind_launch(cozk_toggle_group* g, const fe& rr) {
+    cozk_ctx* const ctx = g->driver;
+    const int dst = g->cur < 0 ? 0 : 1 - g->cur;
+    const ToggleGroupIn in = toggle_group_in(g);
+    const bool u8 = g->cur < 0;  // the first bind reads the packed 0/1 bytes
+    const void* fin = u8 ? (const void*)g->fl0 : (const void*)g->fl[g->cur];
+    size_t n_fp, n_fl;
+    const bool to_coalesced = !g->coalesced && g->n_cur == 2;
+    if (g->coalesced) n_fp = n_fl = g->L / 2;
+    else if (to_coalesced) n_fp = n_fl = g->L;
+    else n_fp = g->batch * g->n_cur / 2, n_fl = (g->batch / 2) * g->n_cur / 2;
+    COZK_REQUIRE(n_fp <= g->fp_cap[dst] && n_fl <= g->fl_cap[dst], "toggle_group: bound planes larger than their storage");
+    const dim3 grid(grid_for(n_fp), (unsigned)g->k);
+    if (to_coalesced) {
+        if (u8) k_toggle_group_bind<0, 1><<<grid, PT, 0, ctx->stream>>>(in, g->fp[dst], g->fp_cap[dst], n_fp, fin, g->fl[dst], n_fl, g->batch, rr);
+        else k_toggle_group_bind<1, 1><<<grid, PT, 0, ctx->stream>>>(in, g->fp[dst], g->fp_cap[dst], n_fp, fin, g->fl[dst], n_fl, g->batch, rr);
+    } else {
+        if (u8) k_toggle_group_bind<0, 0><<<grid, PT, 0, ctx->stream>>>(in, g->fp[dst], g->fp_cap[dst], n_fp, fin, g->fl[dst], n_fl, g->batch, rr);
+        else k_toggle_group_bind<1, 0><<<grid, PT, 0, ctx->stream>>>(in, g->fp[dst], g->fp_cap[dst], n_fp, fin, g->fl[dst], n_fl, g->batch, rr);
+    }
+    HIP_TRY(hipGetLastError());
+    g->cur = dst;
+    if (g->coalesced) {
+        g->L /= 2;
+    } else {
+        g->n_cur /= 2;
+        if (to_coalesced) g->coalesced = true;
+    }
+}
+
+extern "C" {
+
+int cozk_toggle_group_free(cozk_toggle_group* g) {
+    if (!g) return COZK_OK;
+    for (int m = 0; m < g->k; m++)
+        if (g->owner[m]) ctx_dev_free(g->owner[m], (void*)g->fp0[m]);
+    if (g->fl0) ctx_dev_free(g->driver, g->fl0);
+    for (int w = 0; w < 2; w++) {
+        if (g->fp[w]) ctx_dev_free(g->driver, g->fp[w]);
+        if (g->fl[w]) ctx_dev_free(g->driver, g->fl[w]);
+    }
+    delete g;
+    return COZK_OK;
+}
+
+int cozk_toggle_group_create(cozk_ctx* driver, const cozk_vec* const* flags, size_t n_pairs, cozk_vec* const* fingerprints, int k, int take_ownership,
+                             cozk_toggle_group** out) {
+    if (out) *out = nullptr;
+    cozk_toggle_group* g = nullptr;
+    int rc = cozk_guard(driver, [&] {
+        COZK_REQUIRE(driver && flags && fingerprints && out && n_pairs > 0, "toggle_group_create: null argument");
+        COZK_REQUIRE(k >= 1 && k <= COZK_LAYER_GROUP_MAX, "toggle_group_create: 1 <= k <= COZK_LAYER_GROUP_MAX");
+        const size_t batch = 2 * n_pairs;
+        for (int m = 0; m < k; m++) {
+            const cozk_vec* v = fingerprints[m];
+            COZK_REQUIRE(v && v->ctx, "toggle_group_create: null fingerprint vector");
+            COZK_REQUIRE(v->kind == COZK_SCALAR_FR, "toggle_group_create: the fingerprints must be FR vectors");
+            COZK_REQUIRE(v->n == fingerprints[0]->n, "toggle_group_create: the fingerprint vectors must have one length");
+            COZK_REQUIRE(v->ctx->device == driver->device, "toggle_group_create: every fingerprint vector must live on the driver's device");
+            for (int j = 0; j < m; j++) COZK_REQUIRE(fingerprints[j] != v, "toggle_group_create: duplicate fingerprint vector");
+        }
+        const size_t total = fingerprints[0]->n;
+        COZK_REQUIRE(total % batch == 0, "toggle_group_create: fingerprints.len() must be 2 * n_pairs * N");
+        const size_t n0 = total / batch;
+        COZK_REQUIRE(n0 >= 2 && (n0 & (n0 - 1)) == 0, "toggle_group_create: fingerprints per circuit must be a power of two >= 2");
+        std::vector<const uint8_t*> cols(n_pairs);
+        for (size_t q = 0; q < n_pairs; q++) {
+            COZK_REQUIRE(flags[q] && flags[q]->ctx && flags[q]->kind == COZK_SCALAR_U8 && flags[q]->n == n0,
+                         "toggle_group_create: every flag column is a U8 vector of N entries");
+            COZK_REQUIRE(flags[q]->ctx->device == driver->device, "toggle_group_create: every flag column must live on the driver's device");
+            cols[q] = (const uint8_t*)flags[q]->d;
+        }
+        // whatever the inputs' own streams still do to them precedes the driver's launches
+        std::vector<cozk_ctx*> drained{driver};
+        auto drain = [&](cozk_ctx* c) {
+            for (cozk_ctx* d : drained)
+                if (d == c) return;
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            drained.push_back(c);
+        };
+        for (int m = 0; m < k; m++) drain(fingerprints[m]->ctx);
+        for (size_t q = 0; q < n_pairs; q++) drain(flags[q]->ctx);
+        g = new cozk_toggle_group();
+        g->driver = driver;
+        g->k = 0;
+        g->batch = batch;
+        g->n0 = g->n_cur = n0;
+        g->coalesced = false;
+        g->L = 1;
+        while (g->L < batch) g->L <<= 1;
+        g->cur = -1;
+        g->fl0 = nullptr;
+        for (int w = 0; w < 2; w++) g->fp[w] = g->fl[w] = nullptr, g->fp_cap[w] = g->fl_cap[w] = 0;
+        // both ping-pong sides, once, from the driver's pool: the first bind writes side 0, the second side 1, and every later
+        // bind no more than the one two before it; the coalesced vectors have L entries.  Later rounds allocate nothing.
+        for (int w = 0; w < 2; w++) {
+            const size_t fpn = batch * n0 >> (w + 1), fln = n_pairs * n0 >> (w + 1);
+            g->fp_cap[w] = fpn > g->L ? fpn : g->L;
+            g->fl_cap[w] = fln > g->L ? fln : g->L;
+            g->fp[w] = dev_alloc_fe((size_t)k * g->fp_cap[w]);
+            g->fl[w] = dev_alloc_fe(g->fl_cap[w]);
+        }
+        g->fl0 = (uint8_t*)ctx_dev_alloc(driver, n_pairs * n0 + 16);
+        driver->scratch2.reserve(n_pairs * sizeof(void*));
+        HIP_TRY(hipMemcpyAsync(driver->scratch2.p, cols.data(), n_pairs * sizeof(void*), hipMemcpyHostToDevice, driver->stream));
+        HIP_TRY(hipStreamSynchronize(driver->stream));  // `cols` lives on the stack of this call
+        k_toggle_flags_pack<<<grid_for(n_pairs * n0), PT, 0, driver->stream>>>((const uint8_t* const*)driver->scratch2.p, n0, n_pairs * n0, g->fl0);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(driver->stream));  // scratch2 is shared with other calls
+        for (int m = 0; m < k; m++) {  // nothing fails from here on: adopt
+            cozk_vec* v = fingerprints[m];
+            g->fp0[m] = (const fe*)v->d;
+            g->owner[m] = nullptr;
+            if (take_ownership && v->owned) {
+                g->owner[m] = v->ctx;
+                v->d = nullptr;
+                v->owned = false;
+                v->n = 0;
+                v->bytes = 0;
+            }
+        }
+        g->k = k;
+        *out = g;
+    });
+    if (rc != COZK_OK && g) {
+        (void)hipStreamSynchronize(driver->stream);
+        cozk_toggle_group_free(g);
+    }
+    return rc;
+}
+
+int cozk_toggle_group_layer_outputs(cozk_toggle_group* g, cozk_ctx* const* owners, cozk_vec** out) {
+    if (!g) return COZK_ERR_INVALID_ARG;
+    cozk_ctx* const ctx = g->driver;
+    if (out)
+        for (int m = 0; m < g->k; m++) out[m] = nullptr;
+    ToggleGroupOut o;
+    memset(&o, 0, sizeof o);
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(owners && out, "toggle_group_layer_outputs: null argument");
+        COZK_REQUIRE(g->cur < 0, "toggle_group_layer_outputs: needs an unbound group");
+        for (int m = 0; m < g->k; m++) {
+            COZK_REQUIRE(owners[m], "toggle_group_layer_outputs: null owner");
+            COZK_REQUIRE(owners[m]->device == ctx->device, "toggle_group_layer_outputs: every owner must live on the driver's device");
+        }
+        const size_t total = g->batch * g->n0;
+        for (int m = 0; m < g->k; m++) o.p[m] = (fe*)ctx_dev_alloc(owners[m], total * sizeof(fe));
+        k_toggle_group_output<<<grid_for(total), PT, 0, ctx->stream>>>(toggle_group_in(g), o, g->fl0, log2_sz(g->n0), total, g->k);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(ctx->stream));  // the outputs are their owners' from here on
+        for (int m = 0; m < g->k; m++) out[m] = new cozk_vec{owners[m], total, COZK_SCALAR_FR, o.p[m], total * sizeof(fe), true};
+    });
+    if (rc != COZK_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (int m = 0; m < g->k; m++) {
+            if (out && out[m]) delete out[m], out[m] = nullptr;
+            if (o.p[m] && owners && owners[m]) ctx_dev_free(owners[m], o.p[m]);
+        }
+    }
+    return rc;
+}
+
+int cozk_toggle_group_bind(cozk_toggle_group* g, const uint64_t r[4]) {
+    if (!g) return COZK_ERR_INVALID_ARG;
+    return cozk_guard(g->driver, [&] {
+        COZK_REQUIRE(r, "toggle_group_bind: null argument");
+        COZK_REQUIRE(!toggle_group_bound(g), "toggle_group_bind: the group is fully bound");
+        toggle_group_bind_launch(g, fe_from_u64x4(r));
+    });
+}
+
+int cozk_toggle_group_round(cozk_toggle_group* g, cozk_spliteq* e, const uint64_t* r, uint64_t* out_evals) {
+    if (!g) return COZK_ERR_INVALID_ARG;
+    cozk_ctx* const ctx = g->driver;
+    return cozk_guard(ctx, [&] {
+        COZK_REQUIRE(e && out_evals, "toggle_group_round: null argument");
+        COZK_REQUIRE(e->ctx == ctx, "toggle_group_round: the eq polynomial must be the driver's");
+        COZK_REQUIRE(!toggle_group_bound(g), "toggle_group_round: the group is fully bound");
+        if (r) {
+            COZK_REQUIRE(!spliteq_bound(e), "toggle_group_round: eq polynomial already fully bound");
+            COZK_REQUIRE(!(g->coalesced && g->L == 2), "toggle_group_round: the bind leaves the group fully bound, with no round to run (cozk_toggle_group_bind)");
+            const fe rr = fe_from_u64x4(r);
+            toggle_group_bind_launch(g, rr);
+            spliteq_bind_launch(ctx, e, rr);  // once for all members
+        }
+        const unsigned k = (unsigned)g->k;
+        const size_t npairs = g->coalesced ? g->L / 2 : g->batch * g->n_cur / 2;
+        const int log_half_n = g->coalesced ? -1 : log2_sz(g->n_cur / 2);
+        const unsigned gx = sum_grid(grid_capped(npairs, ROUND_GRID_MAX));
+        const unsigned rows = 3 * k + 3;
+        const SumLaunch sl = sum_launch(ctx, rows, gx, rows + 3);
+        const bool nested = e->E1_len != 1;
+        const fe* E1 = e->E1[e->c1];
+        const fe* E2 = e->E2[e->c2];
+        const int lg1 = nested ? log2_sz(e->E1_len / 2) : 0;
+        const bool u8 = g->cur < 0;  // first round: the packed 0/1 bytes
+        const void* fl = u8 ? (const void*)g->fl0 : (const void*)g->fl[g->cur];
+        const dim3 grid(gx, (k + TOGGLE_GROUP_CHUNK - 1) / TOGGLE_GROUP_CHUNK);
+        auto* const kernel = nested ? (u8 ? k_toggle_group_cubic<1, 0> : k_toggle_group_cubic<1, 1>) : (u8 ? k_toggle_group_cubic<0, 0> : k_toggle_group_cubic<0, 1>);
+        kernel<<<grid, PT, 0, ctx->stream>>>(toggle_group_in(g), (int)k, fl, npairs, log_half_n, E1, lg1, E2, e->E2_len, sl.partial);
+        // S_all(X) behind the finished rows, before the finishing kernel, which publishes the round
+        if (nested) k_toggle_eq_sums<1><<<1, RT, 0, ctx->stream>>>(E1, lg1, E2, e->E2_len, npairs, sl.res + rows);
+        else k_toggle_eq_sums<0><<<1, RT, 0, ctx->stream>>>(E1, 0, E2, e->E2_len, npairs, sl.res + rows);
+        fe s[3 * COZK_LAYER_GROUP_MAX + 6];
+        finish_sums(ctx, sl, rows, gx, Fr::one(), 0, s);
+        for (unsigned m = 0; m < k; m++)
+            for (int x = 0; x < 3; x++) fe_to_u64x4(Fr::add(s[3 * m + x], Fr::sub(s[rows + x], s[3 * k + x])), out_evals + 12 * m + 4 * x);
+    });
+}
+
+int cozk_toggle_group_final_claims(cozk_toggle_group* g, uint64_t flag[4], uint64_t* fingerprints, int k_final) {
+    if (!g) return COZK_ERR_INVALID_ARG;
+    cozk_ctx* const ctx = g->driver;
+    return cozk_guard(ctx, [&] {
+        COZK_REQUIRE(flag && (fingerprints || k_final == 0), "toggle_group_final_claims: null argument");
+        COZK_REQUIRE(k_final >= 0 && k_final <= g->k, "toggle_group_final_claims: 0 <= k_final <= k");
+        COZK_REQUIRE(toggle_group_bound(g), "toggle_group_final_claims: the group is not fully bound");
+        fe* res = result_slot(ctx, (size_t)k_final + 1);
+        k_toggle_group_claims<<<1, 64, 0, ctx->stream>>>(toggle_group_in(g), g->fl[g->cur], k_final, res);
+        HIP_TRY(hipGetLastError());
+        fe h[COZK_LAYER_GROUP_MAX + 1];
+        fetch_fe(ctx, res, (size_t)k_final + 1, h);
+        fe_to_u64x4(h[0], flag);
+        for (int m = 0; m < k_final; m++) fe_to_u64x4(h[1 + m], fingerprints + 4 * m);
     });
 }
 

@@ -472,6 +472,12 @@ class ShamirGpStats(ctypes.Structure):
                 ("single_finals", ctypes.c_uint64)]
 
 
+class ShamirGpToggleStats(ctypes.Structure):
+    """cozk_shamir_gp_toggle_stats: how the toggle layer's rounds ran -- calls of cozk_toggle_group_round against per-sender
+    cozk_toggle_round"""
+    _fields_ = [("toggle_group_rounds", ctypes.c_uint64), ("toggle_single_rounds", ctypes.c_uint64)]
+
+
 class ShamirGpProof:
     """what shamir_gp_prove returns: .proof_bytes, the final .claim and point .r (canonical ints), .result (ShamirGpResult), and
     what went over the star -- .msgs[m][p], sender p's masked message of opening m, and .finals[layer, top first][p] = (L, R),
@@ -507,12 +513,25 @@ class ShamirGpProof:
         flat = table(l.cozk_shamir_gp_finals_len, l.cozk_shamir_gp_finals)
         pairs = [(flat[i], flat[i + 1]) for i in range(0, len(flat), 2)]
         self.finals = [pairs[i:i + degree + 1] for i in range(0, len(pairs), degree + 1)]
+        # a toggled proof: the toggle layer's (flag, fingerprint) claims; None for a dense proof
+        self._toggle_stats = ShamirGpToggleStats()
+        ok(l.cozk_shamir_gp_get_toggle_stats(h, ctypes.byref(self._toggle_stats)))
+        fl, fp = np.zeros(4, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+        self.toggle_claims = None
+        if l.cozk_shamir_gp_toggle_claims(h, fl.ctypes.data, fp.ctypes.data) == L.OK:
+            self.toggle_claims = (mont_limbs_to_int(fl.reshape(1, 4))[0], mont_limbs_to_int(fp.reshape(1, 4))[0])
 
 
     @property
     def stats(self):
         """ShamirGpStats of the proof (cozk_shamir_gp_get_stats)"""
         return self._stats
+
+
+    @property
+    def toggle_stats(self):
+        """ShamirGpToggleStats of the proof (cozk_shamir_gp_get_toggle_stats); all zero for a dense proof"""
+        return self._toggle_stats
 
 
 def shamir_gp_prove(party_ctxs, leaves, batch_size, mul_keys, rand_keys, degree, mul_counter=0, rand_counter=0, label=b"cozk", verify=True):
@@ -658,6 +677,50 @@ def shamir_gp_prove_king(party_ctxs, leaves, batch_size, prep, king=0, label=b"c
     h = ctypes.c_void_p()
     party_ctxs[0].check(l.cozk_shamir_gp_prove_king_inproc(ctxs, _handles(n, leaves), batch_size, prep.h, king, bytes(label), 1 if verify else 0,
                                                            ctypes.byref(h)))
+    try:
+        return ShamirGpProof(l, h, prep.degree)
+    finally:
+        l.cozk_shamir_gp_free(h)
+
+
+def shamir_tgp_prove(party_ctxs, flags, fingerprints, mul_keys, rand_keys, degree, mul_counter=0, rand_counter=0, label=b"cozk", verify=True):
+    """the toggled batched grand product proved by len(party_ctxs) Shamir parties in this process (cozk_shamir_tgp_prove_inproc):
+    flags = one public 0/1 U8 Vec of N entries per pair of circuits, vectors of party_ctxs[0]; fingerprints[p] = party p's share
+    vector of the 2 * len(flags) * N fingerprints (not modified; may be None for p > 2 * degree); keys and counters as for
+    shamir_gp_prove.  The proof is the plain toggled prover's, byte for byte.  Returns a ShamirGpProof with .toggle_claims"""
+    n = len(party_ctxs)
+    l = party_ctxs[0]._l
+    ctxs = (ctypes.c_void_p * max(n, 1))(*[c.h for c in party_ctxs])
+    mb, mk = _key_blocks(n, mul_keys)
+    rb, rk = _key_blocks(n, rand_keys)
+    h = ctypes.c_void_p()
+    party_ctxs[0].check(l.cozk_shamir_tgp_prove_inproc(ctxs, _handles(len(flags), flags), len(flags), _handles(n, fingerprints), mk, rk, degree, n,
+                                                       mul_counter, rand_counter, bytes(label), 1 if verify else 0, ctypes.byref(h)))
+    try:
+        return ShamirGpProof(l, h, degree)
+    finally:
+        l.cozk_shamir_gp_free(h)
+
+
+def shamir_tgp_prep(party_ctxs, rand_keys, n_pairs, n_per, degree, rand_counter=0):
+    """shamir_gp_prep for a toggled grand product of n_pairs flag columns of n_per entries (cozk_shamir_tgp_prep_inproc): the masks
+    of the dense tree and of the toggle layer's rounds, the construct pairs behind them.  Serves shamir_tgp_prove_king only"""
+    n = len(party_ctxs)
+    ctxs = (ctypes.c_void_p * max(n, 1))(*[c.h for c in party_ctxs])
+    rb, rk = _key_blocks(n, rand_keys)
+    h = ctypes.c_void_p()
+    party_ctxs[0].check(party_ctxs[0]._l.cozk_shamir_tgp_prep_inproc(ctxs, rk, n_pairs, n_per, degree, n, rand_counter, ctypes.byref(h)))
+    return ShamirGpPrep(party_ctxs, h, degree)
+
+
+def shamir_tgp_prove_king(party_ctxs, flags, fingerprints, prep, king=0, label=b"cozk", verify=True):
+    """shamir_tgp_prove with the king construct, consuming the toggled ShamirGpPrep `prep` (cozk_shamir_tgp_prove_king_inproc)"""
+    n = len(party_ctxs)
+    l = party_ctxs[0]._l
+    ctxs = (ctypes.c_void_p * max(n, 1))(*[c.h for c in party_ctxs])
+    h = ctypes.c_void_p()
+    party_ctxs[0].check(l.cozk_shamir_tgp_prove_king_inproc(ctxs, _handles(len(flags), flags), len(flags), _handles(n, fingerprints), prep.h, king,
+                                                            bytes(label), 1 if verify else 0, ctypes.byref(h)))
     try:
         return ShamirGpProof(l, h, prep.degree)
     finally:

@@ -1,7 +1,7 @@
 """Instruction-lookups harness over the C ABI (`cozk_lookups_*`): SURVEY 8(f)1 restated synthetically -- the toggled /
 sparse batched grand product of Lasso's read / write memory checking (co-jolt/src/subprotocols/sparse_grand_product.rs)
 on the GPU(s), coordinator + verifier on the calling thread -- and thin wrappers of the toggle-layer entry points
-(`cozk_toggle_*`) for the kernel-level parity tests."""
+(`cozk_toggle_*`, `cozk_toggle_group_*`) for the kernel-level parity tests."""
 import ctypes
 
 import numpy as np
@@ -141,6 +141,62 @@ class ToggleLayer:
     def free(self):
         if getattr(self, "h", None):
             self._l.cozk_toggle_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class ToggleGroup:
+    """ONE PLAIN toggle layer with k fingerprint planes over one copy of the public flags, driven on the stream of the driver `ctx`
+    (`cozk_toggle_group_*`): the senders of a Shamir prover.  `flag_vecs` = one U8 Vec of N entries per pair of circuits,
+    `fp_vecs` = k FR Vecs of 2 x pairs x N entries, which may belong to other contexts on the same device.  Without
+    take_ownership the group only refers to the fingerprint Vecs: they are only read and must outlive it."""
+
+    def __init__(self, ctx, flag_vecs, fp_vecs, take_ownership=False):
+        self._l = L.lib()
+        self.ctx = ctx
+        self._flag_vecs, self._fp_vecs = list(flag_vecs), list(fp_vecs)
+        self.k = len(self._fp_vecs)
+        fl = (_vp * max(len(self._flag_vecs), 1))(*[None if v is None else v.h for v in self._flag_vecs])
+        fp = (_vp * max(self.k, 1))(*[None if v is None else v.h for v in self._fp_vecs])
+        h = _vp()
+        ctx.check(self._l.cozk_toggle_group_create(ctx.h, fl, len(self._flag_vecs), fp, self.k, 1 if take_ownership else 0, ctypes.byref(h)))
+        self.h = h
+
+    def layer_outputs(self, owners=None):
+        """every member's dense interleaved layer flag ? fingerprint : 1 in one launch -> k FR Vecs, member m's a vector of owners[m]
+        (default: the driver)"""
+        owners = list(owners) if owners is not None else [self.ctx] * self.k
+        out = (_vp * max(self.k, 1))()
+        self.ctx.check(self._l.cozk_toggle_group_layer_outputs(self.h, (_vp * max(self.k, 1))(*[c.h for c in owners]), out))
+        return [Vec(owners[m], _vp(out[m]), L.SCALAR_FR) for m in range(self.k)]
+
+    def round(self, eq, r=None):
+        """bind planes, flags and eq with r (None in the first round), then every member's g(0), g(2), g(3) -> k lists of 3"""
+        rr = fr_to_mont_limbs([r])[0] if r is not None else None
+        out = np.zeros((3 * self.k, 4), dtype=np.uint64)
+        self.ctx.check(self._l.cozk_toggle_group_round(self.h, eq.h, rr.ctypes.data if rr is not None else None, out.ctypes.data))
+        v = mont_limbs_to_int(out)
+        return [v[3 * m:3 * m + 3] for m in range(self.k)]
+
+    def bind(self, r):
+        rr = fr_to_mont_limbs([r])[0]
+        self.ctx.check(self._l.cozk_toggle_group_bind(self.h, rr.ctypes.data))
+
+    def final_claims(self, k_final=None):
+        """(the bound flag, the bound fingerprints of members 0..k_final - 1) of a fully bound group"""
+        k_final = self.k if k_final is None else k_final
+        fl, fp = np.zeros(4, dtype=np.uint64), np.zeros((max(k_final, 1), 4), dtype=np.uint64)
+        self.ctx.check(self._l.cozk_toggle_group_final_claims(self.h, fl.ctypes.data, fp.ctypes.data, k_final))
+        return mont_limbs_to_int(fl.reshape(1, 4))[0], mont_limbs_to_int(fp)[:max(k_final, 0)]
+
+    def free(self):
+        if getattr(self, "h", None):
+            self._l.cozk_toggle_group_free(self.h)
             self.h = None
 
     def __del__(self):

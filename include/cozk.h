@@ -417,6 +417,46 @@ int cozk_shamir_gp_prep_get_result(const cozk_shamir_gp_prep* prep, cozk_shamir_
 int cozk_shamir_gp_prove_king_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* leaves, size_t batch_size,
                                      cozk_shamir_gp_prep* prep, int king, const char* label, int verify, cozk_shamir_gp** out);
 
+/* The TOGGLED batched grand product (Rep3ToggledBatchedGrandProduct, co-jolt/src/subprotocols/sparse_grand_product.rs; the read /
+ * write half of Lasso's memory checking) proved by the same n Shamir parties (csrc/host/shamir_gp.hpp; restated in
+ * tests/shamir_tgp_ref.py).  flags: n_pairs public 0/1 U8 columns of N entries, vectors of party_ctxs[0]; fingerprints[p]: party
+ * p's FR share vector of the 2 n_pairs x N fingerprints, a vector of party_ctxs[p], read for p <= 2t and never modified.  The
+ * flags are public, so the toggle layer's output and round polynomial are affine in the fingerprint share: the PLAIN toggle calls
+ * on a degree-t share, with the public claim as previous claim, give a degree-t sharing of the plain prover's values.
+ *   construct  level 0 = the senders' toggle outputs (flag ? fingerprint : 1), adopted; above it the dense construct of
+ *              cozk_shamir_gp_prove_inproc, with either multiplication.
+ *   masks      batch B = 2 n_pairs, nv = ceil_log2(B), N = 2^d: the toggle layer has nv + d rounds, so M = M_dense(B N, B) +
+ *              4 (nv + d), still ONE dealing at rand_counter, pair 0.
+ *   rounds     the dense layers as they are; then the toggle layer as coordinate_prove_toggle_layer sees it (no r_layer, no claim
+ *              fold): each sender's four coefficients are unipoly_from_evals(g0, claim - g0, g2, g3) of its toggle round, opened
+ *              from senders 0..2t with the same zero masks, continuing the opening order.
+ *   finals     the flag claim is public; the fingerprint claim is opened from parties 0..t, unmasked; the t + 1 pairs
+ *              (flag, share) are appended to `finals`.
+ * Transcript and proof are those of the Rep3 coordinator's toggled prover, THE PROOF IS THE PLAIN PROVER'S, BYTE FOR BYTE, and
+ * verify != 0 replays the plain toggled verifier.  The handle is the same cozk_shamir_gp with every getter above (claim = the
+ * toggle sumcheck's last claim, r = its point); n_layers counts the toggle layer; t_construct_ms includes the toggle outputs.
+ * When the senders' contexts are on one device the toggle layer runs as ONE cozk_toggle_group on sender 0's context with one eq;
+ * otherwise, or with COZK_SHAMIR_GP_GROUP=0, every sender gets the flags on its own context and a PLAIN cozk_toggle of its own.
+ * cozk_shamir_tgp_prep_inproc (n_per = N) makes the king's preprocessing for this larger M, its pairs at rand_counter + M; it is
+ * marked toggled: cozk_shamir_gp_prove_king_inproc refuses it and cozk_shamir_tgp_prove_king_inproc refuses a dense one.
+ * Preconditions and failure behaviour are those of the dense provers. */
+int cozk_shamir_tgp_prove_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* flags, size_t n_pairs,
+                                 const cozk_vec* const* fingerprints, const uint8_t* const* mul_keys,
+                                 const uint8_t* const* rand_keys, int degree, int num_parties, uint64_t mul_counter,
+                                 uint64_t rand_counter, const char* label, int verify, cozk_shamir_gp** out);
+int cozk_shamir_tgp_prep_inproc(cozk_ctx* const* party_ctxs, const uint8_t* const* rand_keys, size_t n_pairs, size_t n_per,
+                                int degree, int num_parties, uint64_t rand_counter, cozk_shamir_gp_prep** prep);
+int cozk_shamir_tgp_prove_king_inproc(cozk_ctx* const* party_ctxs, const cozk_vec* const* flags, size_t n_pairs,
+                                      const cozk_vec* const* fingerprints, cozk_shamir_gp_prep* prep, int king,
+                                      const char* label, int verify, cozk_shamir_gp** out);
+/* the toggle layer's final claims of a toggled proof; COZK_ERR_INVALID_ARG on a dense proof's handle */
+int cozk_shamir_gp_toggle_claims(const cozk_shamir_gp* h, uint64_t flag[4], uint64_t fingerprint[4]);
+/* how the toggle layer's rounds ran: calls of cozk_toggle_group_round, and of cozk_toggle_round per sender and round */
+typedef struct cozk_shamir_gp_toggle_stats {
+    uint64_t toggle_group_rounds, toggle_single_rounds;
+} cozk_shamir_gp_toggle_stats;
+int cozk_shamir_gp_get_toggle_stats(const cozk_shamir_gp* h, cozk_shamir_gp_toggle_stats* stats);
+
 /* ---------------------------------------------------------------- MSM seam ---------------- */
 /* Upload SRS points (`ck.powers_of_g[i]`, co-jolt/src/poly/commitment/pst13.rs:286-287,461-462) once;
  * replaces the ICICLE `gpu_bases: Option<&[GpuBaseType]>` argument (pst13.rs:52-59,288,320).
@@ -649,6 +689,42 @@ int cozk_toggle_final_claims(cozk_ctx* ctx, const cozk_toggle* t, uint64_t flag[
 /* current (bound) flags and fingerprints -> host; any output pointer may be NULL */
 int cozk_toggle_download(cozk_ctx* ctx, const cozk_toggle* t, uint64_t* flags, uint64_t* fp_a, uint64_t* fp_b,
                          size_t* n_flags, size_t* n_fp);
+/* Toggle groups: ONE PLAIN toggle layer with k fingerprint planes over ONE copy of the public flags, as one unit of work -- the
+ * senders of a Shamir prover (csrc/host/shamir_gp.hpp).  The flags are public, so the layer's output flag ? fingerprint : 1 and
+ * its round polynomial eq (flag fingerprint + 1 - flag) are affine in the fingerprints: a party that runs the PLAIN toggle calls
+ * on its degree-t share holds a degree-t sharing of the plain prover's values, and everything but the fingerprint loads and the
+ * products sum eq flag fingerprint_m is the same for every party.  A group holds one copy of the packed 0/1 flags and of the
+ * bound flags and k fingerprint vectors of one shape, 1 <= k <= COZK_LAYER_GROUP_MAX, on the DRIVER's device; the ping-pong
+ * storage of the bound planes and flags comes from the driver's pool, both sides at create: later calls allocate nothing.  The
+ * rules for member contexts are those of the layer groups above: the vectors may belong to other contexts on the driver's device,
+ * create drains each such context's stream once, every launch goes on the driver's stream and every call returns with that stream
+ * drained.  take_ownership != 0 adopts the buffers of owned fingerprint vectors (they return to their own contexts' pools with
+ * the group); otherwise the group REFERS to them: they are only read and must outlive it.  The flag columns are copied.
+ *   layer_outputs  for every member m the dense interleaved layer of cozk_toggle_layer_output (PLAIN, one = 1) as an FR vector
+ *                  of owners[m] (a context on the driver's device; storage from its pool), in ONE launch that reads each flag
+ *                  byte once for all members.  Needs an unbound group.
+ *   round          cozk_toggle_round (PLAIN) for every member at once: with r != NULL the k planes, the one flag array and the
+ *                  ONE eq `e` (a spliteq of the driver) are bound with r -- planes and flags in one launch, including the switch
+ *                  to the coalesced vectors, padded with ones (flags) and zeros (fingerprints) -- then member m's g(0), g(2),
+ *                  g(3) go to out_evals + 12 m (k x 12 u64).  One round-sum launch for all members (a member-chunk grid
+ *                  dimension bounds the accumulators per lane; the flag look, the compaction, the eq weights and sum eq flag are
+ *                  done once per chunk), one closed-form sum over the eq tables, one finishing launch, ONE fetch.
+ *   bind           the bind alone (the last one of a sumcheck); `e` is not touched.
+ *   final_claims   of a fully bound group: the bound flag (public) and the bound fingerprints of members 0 .. k_final - 1
+ *                  (k_final x 4 u64).  One launch, one fetch.
+ * Refused on the host before any launch, with COZK_ERR_INVALID_ARG and the text left with the driver (*out / every out[] NULL):
+ * null arguments, k out of range, a fingerprint vector that is not FR, of another length, a duplicate or on another device, flag
+ * columns that are not U8 vectors of N entries on the driver's device, N not a power of two >= 2, owners on another device,
+ * layer_outputs of a bound group, an `e` that is not the driver's or is fully bound, a round or a bind on a fully bound group, a
+ * binding round whose bind leaves no round to run, final claims before the group is fully bound, k_final outside 0..k. */
+typedef struct cozk_toggle_group cozk_toggle_group;
+int cozk_toggle_group_create(cozk_ctx* driver, const cozk_vec* const* flags, size_t n_pairs, cozk_vec* const* fingerprints, int k,
+                             int take_ownership, cozk_toggle_group** out);
+int cozk_toggle_group_layer_outputs(cozk_toggle_group* g, cozk_ctx* const* owners, cozk_vec** out /* k */);
+int cozk_toggle_group_round(cozk_toggle_group* g, cozk_spliteq* e, const uint64_t* r, uint64_t* out_evals /* k x 12 */);
+int cozk_toggle_group_bind(cozk_toggle_group* g, const uint64_t r[4]);
+int cozk_toggle_group_final_claims(cozk_toggle_group* g, uint64_t flag[4], uint64_t* fingerprints /* k_final x 4 */, int k_final);
+int cozk_toggle_group_free(cozk_toggle_group* g);
 
 /* ---- Lasso's primary sumcheck of the instruction lookups (co-jolt/src/jolt/vm/instruction_lookups/worker.rs:180-720):
  *   sum_x eq(r, x) ( sum_i flag_i(x) g_i(E_1(x), .., E_alpha(x)) - lookup_output(x) ) = 0.

@@ -44,7 +44,15 @@ Both --gp and --gp --king end with a pair of legs of their prover:
           whole prove with COZK_SHAMIR_GP_GROUP=0 (the per-sender loop: one launch and one fetch per sender and round), alternating
           in this process, proofs, messages and final-claim shares compared.
 --only-group runs nothing but (xix), for both provers:
-  python tools/run_shamir.py --gp --only-group --log-n 22 --parties 8 --degree 2 --out profiles/shamir_gp_group_2p22_n8_t2.json"""
+  python tools/run_shamir.py --gp --only-group --log-n 22 --parties 8 --degree 2 --out profiles/shamir_gp_group_2p22_n8_t2.json
+With --tgp, instead, the TOGGLED Shamir grand product over --pairs flag columns of 2^log_n entries (2 * pairs circuits), a share of
+--density percent of the flags set; the resharing construct, or the king's with --king:
+  (xx)    the first round of the toggle layer as ONE cozk_toggle_group_round over the senders' fingerprints against the senders'
+          cozk_toggle_round calls, each with an eq of its own, alternating in this process, outputs compared raw;
+  (xxi)   the whole prove with the toggle layer as one toggle group and the dense rounds on layer groups against the whole prove with
+          COZK_SHAMIR_GP_GROUP=0, as (xix): alternating, proofs, messages, final-claim shares and toggle claims compared.
+--only-group runs nothing but (xxi):
+  python tools/run_shamir.py --tgp --only-group --log-n 18 --pairs 8 --density 10 --parties 8 --degree 2 --out profiles/shamir_tgp_group_2p18_p8_n8_t2.json"""
 import argparse, ctypes, hashlib, importlib, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -60,7 +68,10 @@ ap.add_argument("--mul", action="store_true", help="time the multiplication with
 ap.add_argument("--king", action="store_true", help="with --mul: time the king / double-random variant against the resharing; with --gp: the king construct")
 ap.add_argument("--gp", action="store_true", help="time the Shamir grand product prover instead")
 ap.add_argument("--gp-batch", type=int, default=2, help="with --gp: circuits in the grand product")
-ap.add_argument("--only-group", action="store_true", help="with --gp: only the grouped against the ungrouped prove, resharing and king prover")
+ap.add_argument("--only-group", action="store_true", help="with --gp: only the grouped against the ungrouped prove, resharing and king prover; with --tgp: only (xxi)")
+ap.add_argument("--tgp", action="store_true", help="time the toggled Shamir grand product prover instead (--king: the king construct)")
+ap.add_argument("--pairs", type=int, default=8, help="with --tgp: flag columns (pairs of circuits)")
+ap.add_argument("--density", type=int, default=10, help="with --tgp: percent of the flags that are set")
 args = ap.parse_args()
 cozk = importlib.import_module("co-zkvms_amd")
 L = cozk._lib
@@ -576,11 +587,19 @@ def group_pair(timed_prove):
         finally:
             os.environ.pop(GROUP_SWITCH, None)
 
-    calls = lambda g: {k: int(getattr(g.stats, k)) for k in ("group_rounds", "single_rounds", "group_finals", "single_finals")}
+    def calls(g):
+        c = {k: int(getattr(g.stats, k)) for k in ("group_rounds", "single_rounds", "group_finals", "single_finals")}
+        if g.toggle_claims is not None:  # a toggled proof: how the toggle layer's rounds ran
+            c.update({k: int(getattr(g.toggle_stats, k)) for k in ("toggle_group_rounds", "toggle_single_rounds")})
+        return c
+
     _, gg = leg(False)  # warm-up and correctness
     _, gu = leg(True)
     assert gg.result.verified == 1 and gu.result.verified == 1, "a Shamir grand product proof was rejected"
-    equal = gg.proof_bytes == gu.proof_bytes and gg.msgs == gu.msgs and gg.finals == gu.finals
+    equal = gg.proof_bytes == gu.proof_bytes and gg.msgs == gu.msgs and gg.finals == gu.finals and gg.toggle_claims == gu.toggle_claims
+    if gg.toggle_claims is not None:
+        assert gg.toggle_stats.toggle_single_rounds == 0 and gg.toggle_stats.toggle_group_rounds > 0 and gu.toggle_stats.toggle_group_rounds == 0, \
+            "the switch did not select the toggle legs"
     assert equal, "the grouped and the ungrouped prove differ in proof, messages or final-claim shares"
     assert gg.stats.single_rounds == 0 and gg.stats.group_rounds > 0 and gu.stats.group_rounds == 0, "the switch did not select the legs"
     t_g, t_u, t_gc, t_gp, t_uc, t_up = [], [], [], [], [], []
@@ -806,6 +825,70 @@ def gp_king_legs():
                   "peer-copy legs (parties on other GPUs) are not exercised by a one-GPU run",
     })
 
+
+def tgp_legs():
+    """--tgp: (xx) unless --only-group, then (xxi); one context per party on this GPU"""
+    if 2 * T + 1 > N or 2 * T > 15:
+        raise SystemExit("run_shamir --tgp: needs 2 * degree + 1 <= parties and 2 * degree <= 15")
+    lookups = importlib.import_module("co-zkvms_amd.lookups")
+    pairs, senders = args.pairs, 2 * T + 1
+    total = 2 * pairs * n
+    pcs, streams = party_contexts()
+    whole = lambda fn: whole_call(pcs, streams, fn)
+    rng = np.random.default_rng(2028)
+    flags = [cozk.Vec.from_ints(pcs[0], (rng.integers(0, 100, n) < args.density).astype(np.uint8).tolist(), kind=L.SCALAR_U8) for _ in range(pairs)]
+    fps = cozk.Vec.random(ctx, total, seed=2029).shamir_scatter(keys_a, T, pcs, counter=0)
+    mul_keys = [[key(1000 + 16 * p + c) for c in range(T)] for p in range(N)]
+    rand_keys = [[key(2000 + 32 * p + c) for c in range(3 * T + 1)] for p in range(N)]
+    res = {
+        "what": "toggled Shamir grand product: the toggle layer as one toggle group (one launch set and one fetch per round for all senders, one "
+                "pass over the public flags and eq tables) against a PLAIN toggle layer per sender (COZK_SHAMIR_GP_GROUP=0), "
+                + ("king construct" if args.king else "resharing construct"),
+        "log_n": args.log_n, "pairs": pairs, "circuits": 2 * pairs, "fingerprints": total, "density_pct": args.density, "parties": N, "degree": T,
+        "senders": senders, "device": torch.cuda.get_device_name(0),
+    }
+    if not args.only_group:
+        nv = (2 * pairs - 1).bit_length() + args.log_n
+        w = [pow(3, 5 + i, cozk.FR_MOD) for i in range(nv)]
+        group = lookups.ToggleGroup(pcs[0], flags, fps[:senders])
+        singles = [lookups.ToggleLayer.from_vecs(pcs[p], flags, fps[p]) for p in range(senders)]
+        eq_g = cozk.SplitEqPolynomial(pcs[0], w)
+        eq_s = [cozk.SplitEqPolynomial(pcs[p], w) for p in range(senders)]
+        run_g = lambda: whole(lambda: group.round(eq_g))
+        run_s = lambda: whole(lambda: [singles[p].round(eq_s[p]) for p in range(senders)])
+        assert run_g()[1] == run_s()[1], "the group round and the per-sender rounds differ"
+        t_g, t_s = [], []
+        while sum(t_g) < args.min_seconds * 1e3 or sum(t_s) < args.min_seconds * 1e3 or len(t_g) < 6:
+            t_g.append(run_g()[0])
+            t_s.append(run_s()[0])
+        res["first_round"] = {"group_round": stats(t_g), "per_sender_rounds_same_run": stats(t_s), "group_vs_per_sender_speedup": round(med(t_s) / med(t_g), 3),
+                              "outputs_equal": True}
+        group.free()
+        for t in singles:
+            t.free()
+
+    def king_prove():  # a fresh preprocessing per repetition, made outside the timed call
+        prep = cozk.shamir_tgp_prep(pcs, rand_keys, pairs, n, T, rand_counter=0)
+        try:
+            return whole(lambda: cozk.shamir_tgp_prove_king(pcs, flags, fps, prep, king=0))
+        finally:
+            prep.close()
+
+    prove = king_prove if args.king else (lambda: whole(lambda: cozk.shamir_tgp_prove(pcs, flags, fps, mul_keys, rand_keys, T, mul_counter=0, rand_counter=0)))
+    res["king_prover" if args.king else "resharing_prover"] = group_pair(prove)
+    res["timing"] = ("from an event on party 0's idle stream before the call to the last of the events behind the parties' streams, host-side "
+                     "synchronisations included; the grouped and the ungrouped leg alternating in one process, the ungrouped leg being the yardstick; "
+                     "keys and counters reused across repetitions (timing only); the king prover's preprocessing is made outside the timed call")
+    free(fps), free(flags)
+    for pc in pcs:
+        pc.close()
+    emit(res)
+
+
+if args.tgp:
+    tgp_legs()
+    ctx.close()
+    raise SystemExit(0)
 
 if args.gp and args.only_group:
     group_legs_only()
