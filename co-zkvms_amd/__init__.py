@@ -17,3 +17,4 @@ from .poly import (Rep3DensePolynomial, Rep3DenseInterleavedPolynomial, SplitEqP
                    sparse_matvec3, fingerprint_leaves, rep3_mul_vec_local)
 from .harness import Harness, HarnessConfig, HarnessResult
 from .spartan import SpartanHarness, SpartanConfig, SpartanResult
+from .lookups import SparseLayer, SparseStats, sparse_stats, sparse_reset_stats

@@ -180,6 +180,21 @@ SIGNATURES = {
     "cozk_toggle_group_bind": (_i, [_vp, _vp]),
     "cozk_toggle_group_final_claims": (_i, [_vp, _vp, _vp, _i]),
     "cozk_toggle_group_free": (_i, [_vp]),
+    "cozk_sparse_layer_create": (_i, [_vp, _i, _sz, _vp, _vp, _vp, _i, _pp]),
+    "cozk_toggle_sparse_output": (_i, [_vp, _vp, _i, _pp]),
+    "cozk_sparse_layer_free": (_i, [_vp]),
+    "cozk_sparse_layer_len": (_sz, [_vp]),
+    "cozk_sparse_layer_count": (_sz, [_vp]),
+    "cozk_sparse_layer_bytes": (_sz, [_vp]),
+    "cozk_sparse_layer_next_count": (_i, [_vp, _vp, ctypes.POINTER(_sz)]),
+    "cozk_sparse_layer_output_local": (_i, [_vp, _vp, _i, ctypes.c_char_p, ctypes.c_char_p, _u64, _pp]),
+    "cozk_sparse_layer_from_output": (_i, [_vp, _vp, _vp, _vp, _i, _pp]),
+    "cozk_sparse_layer_bind": (_i, [_vp, _vp, _vp]),
+    "cozk_sparse_layer_round": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
+    "cozk_sparse_layer_to_dense": (_i, [_vp, _vp, _i, _pp]),
+    "cozk_sparse_layer_download": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "cozk_sparse_get_stats": (_i, [_vp, _vp]),
+    "cozk_sparse_reset_stats": (_i, [_vp]),
     "cozk_layer_output_local": (_i, [_vp, _vp, _i, ctypes.c_char_p, ctypes.c_char_p, _u64, _pp]),
     "cozk_rep3_mul_vec_local": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, ctypes.c_char_p, ctypes.c_char_p, _u64, _pp]),
     "cozk_layer_claimed_outputs": (_i, [_vp, _vp, _vp]),

@@ -227,6 +227,7 @@ struct cozk_ctx {
     void* ring_comm = nullptr;
     int ring_rank = 0, ring_n = 0;
     uint64_t ring_bytes = 0;
+    cozk_sparse_stats sparse_stats{};  // cozk_sparse_get_stats (sparse_layer.inc)
 };
 
 // brackets ONE kernel launch with a pair of events on `st` while profiling is enabled (no-op otherwise)

@@ -589,4 +589,14 @@ int cozk_lookups_prove(cozk_lookups* h, int verify, cozk_lookups_result* res) {
 
 int cozk_lookups_proof_bytes(const cozk_lookups* h, uint8_t* out, size_t cap) { return harness_proof_bytes(h, out, cap); }
 
+int cozk_lookups_get_sparse_stats(const cozk_lookups* h, int party, cozk_sparse_stats* out) {
+    if (!h || !out || party < 0 || party >= h->nparties) return COZK_ERR_INVALID_ARG;
+    return cozk_sparse_get_stats(h->parties[party].ctx, out);
+}
+int cozk_lookups_reset_sparse_stats(cozk_lookups* h) {
+    if (!h) return COZK_ERR_INVALID_ARG;
+    for (LookupsParty& ps : h->parties) (void)cozk_sparse_reset_stats(ps.ctx);
+    return COZK_OK;
+}
+
 }  // extern "C"

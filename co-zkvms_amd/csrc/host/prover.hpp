@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include "net.hpp"
+#include "sparse_rule.hpp"
 #include "../prf.hip.hpp"
 
 namespace cozk {
@@ -47,6 +48,7 @@ typedef Handle<cozk_poly, cozk_poly_free> PolyH;
 typedef Handle<cozk_layer, cozk_layer_free> LayerH;
 typedef Handle<cozk_spliteq, cozk_spliteq_free> EqH;
 typedef Handle<cozk_toggle, cozk_toggle_free> ToggleH;
+typedef Handle<cozk_sparse_layer, cozk_sparse_layer_free> SparseH;
 typedef Handle<cozk_primary, cozk_primary_free> PrimaryH;
 typedef Handle<cozk_outer, cozk_outer_free> OuterH;
 
@@ -412,16 +414,36 @@ static bool verify_grand_product(const GrandProductProof& proof, Transcript& tr,
 
 // ================================================================= toggled (sparse) batched grand product
 // Rep3ToggledBatchedGrandProduct (co-jolt/src/subprotocols/sparse_grand_product.rs:890-1020): one toggle layer (flags x
-// fingerprints) under tree_depth Rep3SparseInterleavedPolynomial layers.  The sparse layers are kept dense on the device
-// (toggle_layer.inc), so they are exactly a Rep3BatchedDenseGrandProduct over the toggle layer's output; the toggle layer
+// fingerprints) under tree_depth Rep3SparseInterleavedPolynomial layers.  By default the sparse layers are kept dense on the
+// device (toggle_layer.inc), so they are exactly a Rep3BatchedDenseGrandProduct over the toggle layer's output; the toggle layer
 // has its own round function and, unlike a multiplication layer, no r_layer fold after its sumcheck (:850-873).
+//
+// COZK_TOGGLE_SPARSE=1 (read on every call, as COZK_SHAMIR_GP_GROUP is; unset or 0: the path above, untouched): the low-density
+// layers at the bottom of the tree are stored as sparse pair layers (cozk_sparse_layer, sparse_layer.inc) while the storage rule of
+// host/sparse_rule.hpp keeps them; the first layer that breaks it is scattered to a dense layer and the tree goes on dense.  A sparse
+// layer's sumcheck runs cozk_sparse_layer_round per round and hands over to cozk_layer_prove_rounds on the scattered layer once a bind
+// breaks the rule or reaches the reference's coalesce point.  The transcript, the messages' opened values and the proof are byte
+// for byte those of the dense path; a party's Rep3 shares and mask counters are not (cozk.h, "Sparse pair layers").
+static inline bool toggle_sparse_enabled() {
+    const char* e = getenv("COZK_TOGGLE_SPARSE");
+    return e && atoi(e) != 0;
+}
+
 struct Rep3ToggledBatchedGrandProduct {
     ToggleH toggle_layer;
-    Rep3BatchedDenseGrandProduct sparse_layers;
+    std::vector<SparseH> sparse_low;              // COZK_TOGGLE_SPARSE=1: the bottom layers of the tree that are stored as pairs
+    Rep3BatchedDenseGrandProduct sparse_layers;   // the layers above them (every layer with the switch off)
+    size_t batch = 0;
 
     // construct (sparse_grand_product.rs:905-930): sparse_layers[0] = toggle_layer.layer_output(), then layer_output up the tree
     static Rep3ToggledBatchedGrandProduct construct(WorkerEnv& env, ToggleH toggle) {
         Rep3ToggledBatchedGrandProduct gp;
+        gp.batch = cozk_toggle_batch(toggle.h);
+        if (toggle_sparse_enabled()) {
+            construct_sparse(env, gp, toggle.h);
+            gp.toggle_layer = std::move(toggle);
+            return gp;
+        }
         cozk_layer* l0 = nullptr;
         rc_check(cozk_toggle_layer_output(env.ctx, toggle.h, env.party, &l0), env.ctx, "toggle_layer_output");
         size_t batch = cozk_toggle_batch(toggle.h);
@@ -429,7 +451,98 @@ struct Rep3ToggledBatchedGrandProduct {
         gp.toggle_layer = std::move(toggle);
         return gp;
     }
-    size_t num_layers() const { return sparse_layers.layers.size() + 1; }
+    // the sparse path of construct: sparse layers up the tree (output_local, the ring reshare of the compact vector, from_output)
+    // until the rule stops one; that layer is scattered and Rep3BatchedDenseGrandProduct::construct continues from it
+    static void construct_sparse(WorkerEnv& env, Rep3ToggledBatchedGrandProduct& gp, cozk_toggle* toggle) {
+        cozk_sparse_layer* s0 = nullptr;
+        rc_check(cozk_toggle_sparse_output(env.ctx, toggle, env.party, &s0), env.ctx, "toggle_sparse_output");
+        SparseH cur(s0);
+        for (;;) {
+            if (!sparse_construct_keeps(cozk_sparse_layer_count(cur.h), cozk_sparse_layer_len(cur.h), gp.batch)) {
+                cozk_layer* l = nullptr;
+                rc_check(cozk_sparse_layer_to_dense(env.ctx, cur.h, env.party, &l), env.ctx, "sparse_layer_to_dense");
+                gp.sparse_layers = Rep3BatchedDenseGrandProduct::construct(env, LayerH(l), gp.batch);
+                return;
+            }
+            cozk_vec* ca = nullptr;
+            rc_check(cozk_sparse_layer_output_local(env.ctx, cur.h, env.mode == COZK_MODE_REP3 ? 1 : 0, env.key_self, env.key_prev, env.mask_ctr, &ca),
+                     env.ctx, "sparse_layer_output_local");
+            VecH va(ca), vb;
+            const size_t n_out = cozk_vec_len(va.h);
+            env.mask_ctr += n_out;
+            if (env.mode == COZK_MODE_REP3) {
+                cozk_vec* cb = nullptr;
+                rc_check(cozk_vec_alloc(env.ctx, n_out, COZK_SCALAR_FR, &cb), env.ctx, "vec_alloc");
+                vb = VecH(cb);
+                // ring reshare: own c.a -> next, c.b <- prev (arithmetic.rs:148-150); every party has the same n_out
+                if (n_out) env.ring->reshare(env.ctx, (const fe*)cozk_vec_device_ptr(va.h), (fe*)cozk_vec_device_ptr(vb.h), n_out);
+            }
+            cozk_sparse_layer* nx = nullptr;
+            rc_check(cozk_sparse_layer_from_output(env.ctx, cur.h, va.h, vb.h, 1, &nx), env.ctx, "sparse_layer_from_output");
+            gp.sparse_low.push_back(std::move(cur));
+            cur = SparseH(nx);
+        }
+    }
+    size_t num_layers() const { return sparse_low.size() + sparse_layers.layers.size() + 1; }
+
+    // prove_layer (grand_product.rs:186-217) of a layer stored sparse: prove_sumcheck (sumcheck.rs:96-131) over
+    // cozk_sparse_layer_round with the star exchange of prove_toggle_layer, then the hand-over to the dense round loop
+    static void prove_sparse_layer(WorkerEnv& env, cozk_sparse_layer* s, size_t batch, fe& claim, std::vector<fe>& r_grand_product) {
+        EqH eq;
+        std::vector<uint64_t> w = to_abi(r_grand_product);
+        const int num_rounds = (int)r_grand_product.size();
+        rc_check(cozk_spliteq_new(env.ctx, w.data(), num_rounds, &eq.h), env.ctx, "spliteq_new");
+        if (env.party == 0) {
+            Writer wr;
+            wr.u64((uint64_t)num_rounds);
+            env.star->send_response(wr.b);
+        }
+        fe previous_claim = claim;
+        std::vector<fe> rs;
+        uint64_t rr[4];
+        int round = 0;
+        bool handover = false;
+        while (round < num_rounds && !handover) {
+            uint64_t ev[12];
+            rc_check(cozk_sparse_layer_round(env.ctx, s, eq.h, round ? rr : nullptr, env.party, ev), env.ctx, "sparse_layer_round");
+            fe g0 = fe_from_u64x4(ev);
+            fe pts[4] = {g0, Fr::sub(previous_claim, g0), fe_from_u64x4(ev + 4), fe_from_u64x4(ev + 8)};
+            std::vector<fe> cf(4);
+            unipoly_from_evals(pts, 4, cf.data());
+            Writer wr;
+            wr.vec_fr(cf);
+            env.star->send_response(wr.b);
+            Bytes req = env.star->receive_request();
+            Reader rd(req);
+            fe r_j = rd.fr();
+            previous_claim = env.additive_trivial(rd.fr());
+            rs.push_back(r_j);
+            fe_to_u64x4(r_j, rr);
+            round++;
+            size_t next_cnt = 0;
+            rc_check(cozk_sparse_layer_next_count(env.ctx, s, &next_cnt), env.ctx, "sparse_layer_next_count");
+            handover = sparse_handover_after_bind(next_cnt, cozk_sparse_layer_len(s), batch);
+        }
+        COZK_REQUIRE(handover && round >= 1 && round < num_rounds, "toggled grand product: a sparse layer must hand over with a dense round left");
+        // the hand-over: bind layer and eq with the last challenge, scatter, and let the dense round loop run the rest
+        rc_check(cozk_sparse_layer_bind(env.ctx, s, rr), env.ctx, "sparse_layer_bind");
+        rc_check(cozk_spliteq_bind(env.ctx, eq.h, rr), env.ctx, "spliteq_bind");
+        cozk_layer* l = nullptr;
+        rc_check(cozk_sparse_layer_to_dense(env.ctx, s, env.party, &l), env.ctx, "sparse_layer_to_dense");
+        LayerH dense(l);
+        SumcheckResult sc = prove_sumcheck(env, dense.h, previous_claim, eq.h, num_rounds - round);
+        rs.insert(rs.end(), sc.r.begin(), sc.r.end());
+        r_grand_product.assign(rs.rbegin(), rs.rend());
+        Bytes req = env.star->receive_request();
+        Reader rd(req);
+        fe r_layer = rd.fr();
+        // claim = add_mul_public(left, right - left, r_layer).into_additive()
+        Share sh;
+        sh.a = Fr::add(sc.left.a, Fr::mul(Fr::sub(sc.right.a, sc.left.a), r_layer));
+        sh.b = Fr::add(sc.left.b, Fr::mul(Fr::sub(sc.right.b, sc.left.b), r_layer));
+        claim = env.into_additive(sh);
+        r_grand_product.push_back(r_layer);
+    }
 
     // prove_layer of the toggle layer (:850-873) with prove_sumcheck (sumcheck.rs:96-131) over cozk_toggle_round
     static void prove_toggle_layer(WorkerEnv& env, cozk_toggle* t, const fe& claim_in, std::vector<fe>& r_grand_product) {
@@ -487,6 +600,7 @@ struct Rep3ToggledBatchedGrandProduct {
         std::vector<fe> r = rd.vec_fr();
         fe claim = env.additive_trivial(rd.fr());
         for (size_t i = sparse_layers.layers.size(); i-- > 0;) Rep3BatchedDenseGrandProduct::prove_layer(env, sparse_layers.layers[i].h, claim, r);
+        for (size_t i = sparse_low.size(); i-- > 0;) prove_sparse_layer(env, sparse_low[i].h, batch, claim, r);
         prove_toggle_layer(env, toggle_layer.h, claim, r);
         return r;
     }

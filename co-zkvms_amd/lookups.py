@@ -25,7 +25,8 @@ class LookupsResult(ctypes.Structure):
 
 LOOKUPS_SYMBOLS = ["cozk_lookups_create", "cozk_lookups_error", "cozk_lookups_destroy", "cozk_lookups_prove", "cozk_lookups_proof_bytes",
                    "cozk_toggle_create", "cozk_toggle_free", "cozk_toggle_batch", "cozk_toggle_len", "cozk_toggle_layer_output", "cozk_toggle_bind",
-                   "cozk_toggle_round", "cozk_toggle_final_claims", "cozk_toggle_download"]
+                   "cozk_toggle_round", "cozk_toggle_final_claims", "cozk_toggle_download", "cozk_lookups_get_sparse_stats",
+                   "cozk_lookups_reset_sparse_stats"]
 
 _vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
 
@@ -53,8 +54,18 @@ def _decl():
     return l
 
 
+class SparseStats(ctypes.Structure):
+    """cozk_sparse_stats: the per-context counters of the sparse pair layers"""
+    _fields_ = [("layers_sparse", ctypes.c_uint64), ("layers_scattered", ctypes.c_uint64), ("sparse_rounds", ctypes.c_uint64),
+                ("handovers", ctypes.c_uint64), ("bytes_sparse", ctypes.c_uint64), ("bytes_dense_equivalent", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 class LookupsHarness(L.HarnessHandle):
     PREFIX, CONFIG, RESULT = "cozk_lookups", LookupsConfig, LookupsResult
+    EXTRA = {"cozk_lookups_get_sparse_stats": (_i, [_vp, _i, _vp]), "cozk_lookups_reset_sparse_stats": (_i, [_vp])}
 
     def __init__(self, mode="plain", log_n=6, n_pairs=2, density_pct=25, devices=(0, 0, 0), seed=1, primary=False, log_workers=0, mix="uniform"):
         cfg = LookupsConfig()
@@ -66,6 +77,16 @@ class LookupsHarness(L.HarnessHandle):
         cfg.primary = 1 if primary else 0
         cfg.log_workers = log_workers
         self._open(cfg)
+
+    def sparse_stats(self, party=0):
+        """the sparse pair layer counters of one party's context (all zero unless a prove ran with COZK_TOGGLE_SPARSE=1)"""
+        st = SparseStats()
+        if self._l.cozk_lookups_get_sparse_stats(self.h, party, ctypes.byref(st)) != L.OK:
+            raise L.CozkError(-1, "lookups_get_sparse_stats")
+        return st
+
+    def reset_sparse_stats(self):
+        self._l.cozk_lookups_reset_sparse_stats(self.h)
 
 
 class ToggleLayer:
@@ -197,6 +218,124 @@ class ToggleGroup:
     def free(self):
         if getattr(self, "h", None):
             self._l.cozk_toggle_group_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def sparse_stats(ctx):
+    st = SparseStats()
+    ctx.check(L.lib().cozk_sparse_get_stats(ctx.h, ctypes.byref(st)))
+    return st
+
+
+def sparse_reset_stats(ctx):
+    ctx.check(L.lib().cozk_sparse_reset_stats(ctx.h))
+
+
+class SparseLayer:
+    """Rep3SparseInterleavedPolynomial on the device as stored pairs (`cozk_sparse_layer`): a sorted list of pair indices and the
+    pairs' (L, R) values; a missing pair is the party's trivial share of one in both entries.  Build one with `from_toggle`,
+    `from_lists` or `from_output`."""
+
+    def __init__(self, ctx, h, mode):
+        self._l = L.lib()
+        self.ctx, self.h, self.mode = ctx, h, mode
+
+    @classmethod
+    def from_toggle(cls, ctx, toggle, party=0):
+        """layer_output of an unbound ToggleLayer: the pairs with a set flag"""
+        h = _vp()
+        ctx.check(L.lib().cozk_toggle_sparse_output(ctx.h, toggle.h, party, ctypes.byref(h)))
+        return cls(ctx, h, toggle.mode)
+
+    @classmethod
+    def from_lists(cls, ctx, n, idx, pairs):
+        """`idx` = strictly increasing pair indices, `pairs` = one (L, R) per index, ints (plain) or (a, b) tuples (Rep3)"""
+        rep3 = bool(pairs) and isinstance(pairs[0][0], tuple)
+        return cls.from_vecs(ctx, L.MODE_REP3 if rep3 else L.MODE_PLAIN, n, *cls._vecs(ctx, idx, pairs, rep3))
+
+    @staticmethod
+    def _vecs(ctx, idx, pairs, rep3):
+        flat = [v for pr in pairs for v in pr]
+        iv = Vec.from_ints(ctx, list(idx), kind=L.SCALAR_U32)
+        if rep3:
+            return iv, Vec.from_ints(ctx, [v[0] for v in flat]), Vec.from_ints(ctx, [v[1] for v in flat])
+        return iv, Vec.from_ints(ctx, flat), None
+
+    @classmethod
+    def from_vecs(cls, ctx, mode, n, idx, a, b=None, take_ownership=False):
+        h = _vp()
+        ctx.check(L.lib().cozk_sparse_layer_create(ctx.h, mode, n, idx.h, a.h, b.h if b is not None else None, 1 if take_ownership else 0,
+                                                   ctypes.byref(h)))
+        return cls(ctx, h, mode)
+
+    def __len__(self):
+        return self._l.cozk_sparse_layer_len(self.h)
+
+    @property
+    def count(self):
+        return self._l.cozk_sparse_layer_count(self.h)
+
+    @property
+    def nbytes(self):
+        return self._l.cozk_sparse_layer_bytes(self.h)
+
+    def next_count(self):
+        """stored pairs after a bind = stored pairs of the output layer"""
+        n = _sz()
+        self.ctx.check(self._l.cozk_sparse_layer_next_count(self.ctx.h, self.h, ctypes.byref(n)))
+        return n.value
+
+    def output_local(self, masked=False, key_self=None, key_prev=None, counter=0):
+        """the compact vector of 2 * next_count() additive products (+ the zero-sharing masks at counter + position)"""
+        h = _vp()
+        self.ctx.check(self._l.cozk_sparse_layer_output_local(self.ctx.h, self.h, 1 if masked else 0, L.prf_key(key_self), L.prf_key(key_prev), counter,
+                                                              ctypes.byref(h)))
+        return Vec(self.ctx, h, L.SCALAR_FR)
+
+    def from_output(self, va, vb=None, take_ownership=False):
+        """the next layer: the products of output_local (a) and, for Rep3, what the ring reshare gave (b)"""
+        h = _vp()
+        self.ctx.check(self._l.cozk_sparse_layer_from_output(self.ctx.h, self.h, va.h, vb.h if vb is not None else None, 1 if take_ownership else 0,
+                                                             ctypes.byref(h)))
+        return SparseLayer(self.ctx, h, self.mode)
+
+    def bind(self, r):
+        rr = fr_to_mont_limbs([r])[0]
+        self.ctx.check(self._l.cozk_sparse_layer_bind(self.ctx.h, self.h, rr.ctypes.data))
+
+    def round(self, eq, r=None, party=0):
+        """bind layer and eq with r (None in the first round), then this party's additive g(0), g(2), g(3)"""
+        rr = fr_to_mont_limbs([r])[0] if r is not None else None
+        out = np.zeros((3, 4), dtype=np.uint64)
+        self.ctx.check(self._l.cozk_sparse_layer_round(self.ctx.h, self.h, eq.h, rr.ctypes.data if rr is not None else None, party, out.ctypes.data))
+        return mont_limbs_to_int(out)
+
+    def to_dense(self, party=0):
+        from .poly import Rep3DenseInterleavedPolynomial
+        h = _vp()
+        self.ctx.check(self._l.cozk_sparse_layer_to_dense(self.ctx.h, self.h, party, ctypes.byref(h)))
+        return Rep3DenseInterleavedPolynomial(self.ctx, h, self.mode)
+
+    def download(self):
+        """(idx, pairs): the pair indices and one (L, R) per index"""
+        cnt = self.count
+        idx = np.zeros(max(cnt, 1), dtype=np.uint32)
+        a = np.zeros((max(2 * cnt, 1), 4), dtype=np.uint64)
+        b = np.zeros((max(2 * cnt, 1), 4), dtype=np.uint64)
+        self.ctx.check(self._l.cozk_sparse_layer_download(self.ctx.h, self.h, idx.ctypes.data, a.ctypes.data, b.ctypes.data))
+        va = mont_limbs_to_int(a)[:2 * cnt]
+        vals = list(zip(va, mont_limbs_to_int(b)[:2 * cnt])) if self.mode == L.MODE_REP3 else va
+        return [int(i) for i in idx[:cnt]], [(vals[2 * i], vals[2 * i + 1]) for i in range(cnt)]
+
+    def free(self):
+        if getattr(self, "h", None):
+            self._l.cozk_sparse_layer_free(self.h)
             self.h = None
 
     def __del__(self):

@@ -726,6 +726,71 @@ int cozk_toggle_group_bind(cozk_toggle_group* g, const uint64_t r[4]);
 int cozk_toggle_group_final_claims(cozk_toggle_group* g, uint64_t flag[4], uint64_t* fingerprints /* k_final x 4 */, int k_final);
 int cozk_toggle_group_free(cozk_toggle_group* g);
 
+/* ---- Sparse pair layers (co-jolt/src/poly/sparse_interleaved_poly.rs:28-737, Rep3SparseInterleavedPolynomial): the layers above
+ * the toggle layer kept SPARSE on the device.  A dense interleaved layer of length n is n / 2 pairs (L_j, R_j) at entries 2j,
+ * 2j + 1; a cozk_sparse_layer stores the pairs that are not (one, one): a sorted U32 array idx[count] of global pair indices and
+ * the values L, R interleaved in that order (one FR array of 2 * count, two -- a, b -- for COZK_MODE_REP3), and the dense length n.
+ * A missing pair is this party's trivial share of one in both entries.  n / 2 > 2^32 is refused.  Both structural maps merge
+ * neighbours with equal idx >> 1 into one item at idx >> 1 (a head flag, a scan, one lane per merged group):
+ *   bind          stored pairs 2k, 2k + 1 -> pair k: L' = lerp(L_2k, L_2k+1, r), R' likewise; a missing sibling is (one, one)
+ *   layer_output  pair j -> entry j of the next layer, i.e. half j & 1 of that layer's pair j >> 1
+ * The values are, entry by entry, those of the dense formulation restricted to the stored pairs; oracle/pysparse.py (SparseLayer,
+ * sparse_layer_output, toggled_construct) is the yardstick.  Per-party SHARES of a Rep3 layer may differ from the dense path's and
+ * the reference's: a pair (a, one) is multiplied here where the reference keeps it "ready" (:148-192), and the zero-sharing masks
+ * sit at other counters (counter + position in the compact vector).  Only opened values are fixed: transcripts, messages and
+ * proofs are byte for byte those of the dense path.
+ * The dense formulation pads a ragged tail with zeros (dense_interleaved_poly.rs:155-195), a sparse layer reads a missing pair as
+ * ones: bind, round and output are defined while n is a multiple of 4 (a binding round: of 8) -- every length of the toggled tree
+ * down to the reference's coalesce point (one pair per circuit), where a prover hands over with cozk_sparse_layer_to_dense.
+ * The party of a Rep3 layer is that of the toggle it came from or of the layer it is the output of; a layer from explicit lists
+ * learns it from its first round or to_dense call (bind and output_local before that are refused).
+ * Refused on the host before any launch, with COZK_ERR_INVALID_ARG and a text (*out NULL, the object usable): null arguments; an
+ * idx that is not U32, not strictly increasing or with an index >= n / 2; value vectors of the wrong kind or length; n odd or below
+ * 2; a round on an eq that is fully bound or not this context's; a bind that leaves fewer than one pair; a party other than the
+ * layer's; a length that is not a multiple of 4 where one is needed. */
+typedef struct cozk_sparse_layer cozk_sparse_layer;
+/* Rep3SparseInterleavedPolynomial::new (:40-75) from explicit lists; take_ownership != 0 adopts the buffers of owned vectors */
+int cozk_sparse_layer_create(cozk_ctx* ctx, int mode, size_t n, cozk_vec* idx, cozk_vec* a, cozk_vec* b, int take_ownership,
+                             cozk_sparse_layer** out);
+/* Rep3BatchedGrandProductToggleLayer::layer_output (sparse_grand_product.rs:76-97) of an unbound toggle: pair (i, i + 1) of
+ * circuit b is stored iff flag[b / 2][i] | flag[b / 2][i + 1]; each entry is flag ? fingerprint : trivial share of one */
+int cozk_toggle_sparse_output(cozk_ctx* ctx, const cozk_toggle* t, int party_id, cozk_sparse_layer** out);
+int cozk_sparse_layer_free(cozk_sparse_layer* s);
+size_t cozk_sparse_layer_len(const cozk_sparse_layer* s);   /* dense length n (:77-89 dense_len) */
+size_t cozk_sparse_layer_count(const cozk_sparse_layer* s); /* stored pairs */
+size_t cozk_sparse_layer_bytes(const cozk_sparse_layer* s); /* count * (64 * NC + 4), NC = 1 plain, 2 Rep3 */
+/* stored pairs after a bind = stored pairs of the output layer: the merged groups G, the same for every party */
+int cozk_sparse_layer_next_count(cozk_ctx* ctx, cozk_sparse_layer* s, size_t* out);
+/* local half of layer_output (:135-196) as a compact FR vector of 2 * G additive products: L_j x R_j for a stored pair, the
+ * additive trivial one (party 0 holds 1, the others 0) for the missing sibling, + PRF(key_self, c) - PRF(key_prev, c) at
+ * c = counter + position when masked != 0, as cozk_layer_output_local does.  The caller advances its mask counter by 2 * G. */
+int cozk_sparse_layer_output_local(cozk_ctx* ctx, cozk_sparse_layer* s, int masked, const uint8_t* key_self, const uint8_t* key_prev,
+                                   uint64_t counter, cozk_vec** out);
+/* the products of cozk_sparse_layer_output_local (va) and, for Rep3, what the ring reshare gave for them (vb) as the NEXT layer
+ * (:135-196): dense length n / 2, idx = the group indices; take_ownership != 0 adopts the buffers of owned vectors */
+int cozk_sparse_layer_from_output(cozk_ctx* ctx, cozk_sparse_layer* s, cozk_vec* va, cozk_vec* vb, int take_ownership,
+                                  cozk_sparse_layer** out);
+/* Rep3Bindable::bind (:198-380), LowToHigh; ping-pong storage from the context's pool */
+int cozk_sparse_layer_bind(cozk_ctx* ctx, cozk_sparse_layer* s, const uint64_t r[4]);
+/* one round of prove_sumcheck over the layer (compute_cubic, :415-715), the contract of cozk_toggle_round: bind layer and eq with
+ * r when non-NULL, then this party's additive g(0), g(2), g(3) in delta form: the all-ones sums in closed form over the layer's
+ * n / 4 quads + sum over the merged groups of eq_t(q) (L_t R_t - 1) */
+int cozk_sparse_layer_round(cozk_ctx* ctx, cozk_sparse_layer* s, cozk_spliteq* eq, const uint64_t* r, int party_id,
+                            uint64_t out_evals[12]);
+/* coalesce (:91-103): the dense interleaved layer (filled with trivial ones, then the stored pairs), an ordinary cozk_layer */
+int cozk_sparse_layer_to_dense(cozk_ctx* ctx, const cozk_sparse_layer* s, int party_id, cozk_layer** out);
+/* the lists -> host (:28-38 coeffs): idx count x u32, a / b 2 * count x 4 u64; any output pointer may be NULL */
+int cozk_sparse_layer_download(cozk_ctx* ctx, const cozk_sparse_layer* s, uint32_t* idx, uint64_t* a, uint64_t* b);
+/* per-context counters of the sparse layers (construct / prove_layer, sparse_grand_product.rs:905-1020 as the prover with
+ * COZK_TOGGLE_SPARSE=1 drives them): a layer counts as stored sparse when its first round runs -- its bytes then, and the bytes
+ * n x 32 x NC of the dense layer it stands for --, a to_dense before any round as a layer scattered at construct, a to_dense after
+ * a round as a mid-sumcheck handover */
+typedef struct cozk_sparse_stats {
+    uint64_t layers_sparse, layers_scattered, sparse_rounds, handovers, bytes_sparse, bytes_dense_equivalent;
+} cozk_sparse_stats;
+int cozk_sparse_get_stats(const cozk_ctx* ctx, cozk_sparse_stats* out);
+int cozk_sparse_reset_stats(cozk_ctx* ctx);
+
 /* ---- Lasso's primary sumcheck of the instruction lookups (co-jolt/src/jolt/vm/instruction_lookups/worker.rs:180-720):
  *   sum_x eq(r, x) ( sum_i flag_i(x) g_i(E_1(x), .., E_alpha(x)) - lookup_output(x) ) = 0.
  * cozk_primary holds eq (public), the instruction flags (public 0/1 U8 columns), the E polynomials and lookup_outputs
@@ -1129,6 +1194,10 @@ const char* cozk_lookups_error(const cozk_lookups* h);
 int cozk_lookups_destroy(cozk_lookups* h);
 int cozk_lookups_prove(cozk_lookups* h, int verify, cozk_lookups_result* res);
 int cozk_lookups_proof_bytes(const cozk_lookups* h, uint8_t* out, size_t cap);
+/* the sparse pair layer counters (cozk_sparse_stats) of party `party`'s context, accumulated over the harness's proves, and their
+ * reset for every party; all zero unless a prove ran with COZK_TOGGLE_SPARSE=1 */
+int cozk_lookups_get_sparse_stats(const cozk_lookups* h, int party, cozk_sparse_stats* out);
+int cozk_lookups_reset_sparse_stats(cozk_lookups* h);
 
 /* ---------------------------------------------------------------- Spartan outer-sumcheck harness ---- */
 /* SURVEY.md 8(f)2 restated synthetically: Az / Bz / Cz of a satisfied constraint system over 14 witness columns (shared and

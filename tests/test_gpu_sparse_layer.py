@@ -1,0 +1,318 @@
+"""GPU parity of the sparse pair layers (cozk_sparse_layer_*, csrc/sparse_layer.inc) with the oracle's LITERAL restatement of
+Rep3SparseInterleavedPolynomial (oracle/pysparse.py: SparseLayer, sparse_layer_output, toggled_construct).  The object is forced sparse
+whatever its density (the storage rule belongs to the prover): 0 % (nothing stored), 100 % (every pair stored), batches that are no
+power of two, and a layer that spans several workgroups and scan tiles.
+
+The dense formulation pads a ragged tail with zeros where a sparse layer reads a missing pair as ones, so a sparse layer runs the
+rounds whose length is a multiple of 4 -- every round down to the coalesce point, and every round of a power-of-two batch; the bind
+after the last such round is still compared with the oracle."""
+import copy
+import functools
+import importlib
+
+import pytest
+
+import pyref as O
+import pysparse as S
+
+pytestmark = pytest.mark.gpu
+R = O.R
+SHAPES = [(4, 16, 30, 3), (6, 8, 60, 1), (10, 4, 50, 1), (2, 2, 100, 3), (4, 8, 0, 1), (8, 256, 10, 3), (6, 4096, 10, 1)]
+REP3_SHAPES = [s for s in SHAPES if s[3] == 3]
+KEYS = [bytes([17 * (p + 1) + i for i in range(32)]) for p in range(3)]  # KEYS[p]: shared by party p and party p + 1
+
+
+def _instance(batch, n, density, seed, nparties):
+    """as tests/test_gpu_lookups.py builds its instances"""
+    rng = O.SplitMix64(seed)
+    cols = [[1 if rng.next() % 100 < density else 0 for _ in range(n)] for _ in range(batch // 2)]
+    vals = [[rng.field() for _ in range(n)] for _ in range(batch)]
+    if nparties == 1:
+        fps = [vals]
+    else:
+        sh = [[O.rep3_share(v, rng) for v in row] for row in vals]
+        fps = [[[s[p] for s in row] for row in sh] for p in range(3)]
+    return cols, vals, fps
+
+
+@functools.lru_cache(maxsize=None)
+def _case(batch, n, density, nparties):
+    """the instance and the oracle's tree, computed once per shape and never changed (the tests work on deep copies)"""
+    cols, vals, fps = _instance(batch, n, density, 100 + batch + n, nparties)
+    flag_indices = [[i for i, f in enumerate(c) if f] for c in cols]
+    toggles, sparse = S.toggled_construct(flag_indices, fps)
+    return cols, fps, sparse
+
+
+def _lk():
+    return importlib.import_module("co-zkvms_amd.lookups")
+
+
+def _stored_pairs(cols, batch, n):
+    return [b * (n // 2) + i // 2 for b in range(batch) for i in range(0, n, 2) if cols[b // 2][i] | cols[b // 2][i + 1]]
+
+
+def _opened(coeffs):
+    """the values a Rep3 vector of one party per row opens to: a_0 + a_1 + a_2"""
+    return [sum(c[0] for c in col) % R for col in zip(*coeffs)]
+
+
+def _sumcheck(cozk, ctx, devs, refs, seed, exact):
+    """every round of a sumcheck over one layer held by len(devs) parties.  exact: per party the round values and the bound layer equal
+    the oracle's bit for bit; else the sums over the parties and the opened layers do.  Returns the eq forms the rounds went through."""
+    nparties = len(devs)
+    n = refs[0].dense_len
+    assert len(devs[0]) == n
+    nv = max(1, (n // 2 - 1).bit_length())
+    rng = O.SplitMix64(seed)
+    w = [rng.field() for _ in range(nv)]
+    eq_refs = [O.SplitEq(w) for _ in range(nparties)]
+    eq_devs = [cozk.SplitEqPolynomial(ctx, w) for _ in range(nparties)]
+    claim = rng.field()
+    forms = set()
+
+    def check_dense():
+        got = [devs[p].to_dense(party=p) for p in range(nparties)]
+        want = [refs[p].coalesce() for p in range(nparties)]
+        if exact:
+            for p in range(nparties):
+                assert got[p].coeffs() == want[p], p
+        else:
+            assert _opened([g.coeffs() for g in got]) == _opened(want)
+        for g in got:
+            g.free()
+
+    pending = None
+    rounds = 0
+    while True:
+        n_round = n // 2 if pending is not None else n
+        if n_round < 4 or n_round % 4:
+            break
+        forms.add("flat" if eq_refs[0].E1_len == 1 else "nested")
+        evs = [refs[p].compute_cubic_evals(eq_refs[p], claim) for p in range(nparties)]
+        gots = [devs[p].round(eq_devs[p], pending, party=p) for p in range(nparties)]
+        n = n_round
+        if exact:
+            for p in range(nparties):
+                assert gots[p] == [evs[p][0], evs[p][2], evs[p][3]], (p, rounds)
+        else:
+            for k, kk in enumerate((0, 2, 3)):
+                assert sum(g[k] for g in gots) % R == sum(e[kk] for e in evs) % R, (rounds, kk)
+        if pending is not None:
+            assert len(devs[0]) == refs[0].dense_len
+            check_dense()
+        pending = rng.field()
+        for p in range(nparties):
+            refs[p].bind(pending)
+            eq_refs[p].bind(pending)
+        rounds += 1
+    assert rounds >= 1
+    if n >= 4 and n % 4 == 0:  # the bind after the last sparse round
+        for p in range(nparties):
+            devs[p].bind(pending)
+        check_dense()
+    for e in eq_devs:
+        e.free()
+    return forms
+
+
+@pytest.mark.parametrize("batch,n,density,nparties", SHAPES)
+def test_toggle_output_scattered_equals_the_dense_toggle_output(cozk, ctx, batch, n, density, nparties):
+    LK = _lk()
+    cols, fps, sparse = _case(batch, n, density, nparties)
+    want_idx = _stored_pairs(cols, batch, n)
+    for p in range(nparties):
+        tg = LK.ToggleLayer(ctx, cols, fps[p])
+        sp = LK.SparseLayer.from_toggle(ctx, tg, party=p)
+        assert len(sp) == batch * n
+        assert sp.count == len(want_idx)
+        assert sp.nbytes == len(want_idx) * (64 * (2 if nparties == 3 else 1) + 4)
+        idx, pairs = sp.download()
+        assert idx == want_idx
+        dense, ref = sp.to_dense(party=p), tg.layer_output(party=p)
+        got = dense.coeffs()
+        assert got == ref.coeffs()
+        assert got == sparse[0][p].coalesce()
+        assert pairs == [(got[2 * j], got[2 * j + 1]) for j in idx]
+        for o in (dense, ref, sp, tg):
+            o.free()
+
+
+@pytest.mark.parametrize("batch,n,density,nparties", SHAPES)
+def test_layer0_rounds_and_binds_match_the_sparse_oracle_per_party(cozk, ctx, batch, n, density, nparties):
+    LK = _lk()
+    cols, fps, sparse = _case(batch, n, density, nparties)
+    tgs = [LK.ToggleLayer(ctx, cols, fps[p]) for p in range(nparties)]
+    devs = [LK.SparseLayer.from_toggle(ctx, tgs[p], party=p) for p in range(nparties)]
+    forms = _sumcheck(cozk, ctx, devs, [copy.deepcopy(sparse[0][p]) for p in range(nparties)], 5, exact=True)
+    assert "nested" in forms
+    if batch & (batch - 1) == 0 and batch * n >= 16:  # a power-of-two batch runs to the last round: the flat table once E1 is bound
+        assert forms == {"flat", "nested"}
+    for o in devs + tgs:
+        o.free()
+
+
+def _climb(ctx, LK, sp, nparties, masked):
+    """one level up the tree for every party: output_local, the ring reshare of the compact vectors (Rep3), from_output"""
+    counter = 1000
+    vas = [sp[p].output_local(masked=masked, key_self=KEYS[p], key_prev=KEYS[(p + 2) % 3], counter=counter) for p in range(nparties)]
+    G = sp[0].next_count()
+    assert all(len(v) == 2 * G for v in vas)
+    if nparties == 1:
+        return [sp[0].from_output(vas[0])], vas
+    host = [v.to_numpy() for v in vas]
+    vbs = [cozk_vec_from(ctx, host[(p + 2) % 3]) for p in range(3)]  # c.b = the previous party's c.a
+    return [sp[p].from_output(vas[p], vbs[p]) for p in range(3)], vas
+
+
+def cozk_vec_from(ctx, limbs):
+    E = importlib.import_module("co-zkvms_amd.engine")
+    return E.Vec.from_numpy(ctx, limbs)
+
+
+@pytest.mark.parametrize("batch,n,density,nparties", SHAPES)
+def test_plain_higher_layers_match_the_sparse_oracle(cozk, ctx, batch, n, density, nparties):
+    LK = _lk()
+    cols, fps, sparse = _case(batch, n, density, 1)
+    tg = LK.ToggleLayer(ctx, cols, fps[0])
+    layers = [[LK.SparseLayer.from_toggle(ctx, tg, party=0)]]
+    for li in range(1, min(3, len(sparse))):  # layers 1 and 2, where the tree has them
+        nxt, _ = _climb(ctx, LK, layers[-1], 1, masked=False)
+        assert nxt[0].count == layers[-1][0].next_count() and len(nxt[0]) == len(layers[-1][0]) // 2
+        dense = nxt[0].to_dense(party=0)
+        assert dense.coeffs() == sparse[li][0].coalesce()
+        dense.free()
+        layers.append(nxt)
+    for li in range(1, len(layers)):
+        _sumcheck(cozk, ctx, layers[li], [copy.deepcopy(sparse[li][0])], 40 + li, exact=True)
+    for o in [l[0] for l in layers] + [tg]:
+        o.free()
+
+
+@pytest.mark.parametrize("batch,n,density,nparties", REP3_SHAPES)
+def test_rep3_higher_layers_open_to_the_oracle_and_the_masks_cancel(cozk, ctx, batch, n, density, nparties):
+    LK = _lk()
+    cols, fps, sparse = _case(batch, n, density, 3)
+    tgs = [LK.ToggleLayer(ctx, cols, fps[p]) for p in range(3)]
+    layers = [[LK.SparseLayer.from_toggle(ctx, tgs[p], party=p) for p in range(3)]]
+    for li in range(1, min(3, len(sparse))):
+        plain = [s.output_local(masked=False).to_ints() for s in layers[-1]]
+        nxt, vas = _climb(ctx, LK, layers[-1], 3, masked=True)
+        masked = [v.to_ints() for v in vas]
+        if masked[0]:
+            assert all(masked[p] != plain[p] for p in range(3))  # the masks are on ...
+        assert [sum(c) % R for c in zip(*masked)] == [sum(c) % R for c in zip(*plain)]  # ... and cancel
+        dense = [nxt[p].to_dense(party=p) for p in range(3)]
+        assert _opened([d.coeffs() for d in dense]) == _opened([sparse[li][p].coalesce() for p in range(3)])
+        for d in dense:
+            d.free()
+        layers.append(nxt)
+    for li in range(1, len(layers)):
+        _sumcheck(cozk, ctx, layers[li], [copy.deepcopy(sparse[li][p]) for p in range(3)], 60 + li, exact=False)
+    for o in [s for l in layers for s in l] + tgs:
+        o.free()
+
+
+def test_create_from_explicit_lists_round_trips_through_download(cozk, ctx):
+    LK = _lk()
+    rng = O.SplitMix64(9)
+    idx = [0, 1, 4, 7]
+    plain = [(rng.field(), rng.field()) for _ in idx]
+    sp = LK.SparseLayer.from_lists(ctx, 16, idx, plain)
+    assert (len(sp), sp.count, sp.nbytes, sp.next_count()) == (16, 4, 4 * 68, 3)
+    assert sp.download() == (idx, plain)
+    want = [1] * 16
+    for j, (l, r) in zip(idx, plain):
+        want[2 * j], want[2 * j + 1] = l, r
+    dense = sp.to_dense()
+    assert dense.coeffs() == want
+    dense.free()
+    sp.free()
+    shares = [((rng.field(), rng.field()), (rng.field(), rng.field())) for _ in idx]
+    sp = LK.SparseLayer.from_lists(ctx, 16, idx, shares)
+    assert (sp.count, sp.nbytes) == (4, 4 * 132)
+    assert sp.download() == (idx, shares)
+    dense = sp.to_dense(party=1)
+    got = dense.coeffs()
+    assert [got[2 * j] for j in idx] == [s[0] for s in shares] and got[4] == (0, 1)
+    dense.free()
+    sp.free()
+    empty = LK.SparseLayer.from_lists(ctx, 8, [], [])
+    assert (empty.count, empty.nbytes, empty.next_count()) == (0, 0, 0) and empty.download() == ([], [])
+    dense = empty.to_dense()
+    assert dense.coeffs() == [1] * 8
+    dense.free()
+    empty.free()
+
+
+def test_refusals_leave_out_null_and_the_object_usable(cozk, ctx):
+    LK = _lk()
+    E = importlib.import_module("co-zkvms_amd.engine")
+    LB = importlib.import_module("co-zkvms_amd._lib")
+    rng = O.SplitMix64(3)
+    idx = [0, 2, 3]
+    pairs = [(rng.field(), rng.field()) for _ in idx]
+    flat = [v for pr in pairs for v in pr]
+    iv, av = E.Vec.from_ints(ctx, idx, kind=LB.SCALAR_U32), E.Vec.from_ints(ctx, flat)
+
+    def refused(fn, *a, **k):
+        with pytest.raises(cozk.CozkError) as ei:
+            fn(*a, **k)
+        assert ei.value.code == -1 and len(str(ei.value)) > len("cozk error -1: ")
+
+    mk = LK.SparseLayer.from_vecs
+    refused(mk, ctx, LB.MODE_PLAIN, 8, E.Vec.from_ints(ctx, idx, kind=LB.SCALAR_U64), av)          # idx not U32
+    refused(mk, ctx, LB.MODE_PLAIN, 8, E.Vec.from_ints(ctx, [0, 3, 2], kind=LB.SCALAR_U32), av)    # not increasing
+    refused(mk, ctx, LB.MODE_PLAIN, 8, E.Vec.from_ints(ctx, [0, 2, 2], kind=LB.SCALAR_U32), av)    # not strictly
+    refused(mk, ctx, LB.MODE_PLAIN, 8, E.Vec.from_ints(ctx, [0, 2, 4], kind=LB.SCALAR_U32), av)    # index >= n / 2
+    refused(mk, ctx, LB.MODE_PLAIN, 8, iv, E.Vec.from_ints(ctx, flat[:5]))                         # wrong length
+    refused(mk, ctx, LB.MODE_PLAIN, 8, iv, E.Vec.from_ints(ctx, [1] * 6, kind=LB.SCALAR_U64))      # wrong kind
+    refused(mk, ctx, LB.MODE_REP3, 8, iv, av)                                                      # Rep3 without b
+    refused(mk, ctx, LB.MODE_REP3, 8, iv, av, E.Vec.from_ints(ctx, flat[:4]))                      # b of the wrong length
+    refused(mk, ctx, LB.MODE_PLAIN, 7, iv, av)                                                     # n odd
+    refused(mk, ctx, LB.MODE_PLAIN, 0, E.Vec.from_ints(ctx, [], kind=LB.SCALAR_U32), E.Vec.alloc(ctx, 0))  # n below 2
+    refused(mk, ctx, 7, 8, iv, av)                                                                 # no such mode
+    l = LB.lib()
+    import ctypes
+    h = ctypes.c_void_p(0x5A5A)
+    assert l.cozk_sparse_layer_create(ctx.h, LB.MODE_PLAIN, 8, iv.h, None, None, 0, ctypes.byref(h)) == -1 and h.value is None  # null values
+    h = ctypes.c_void_p(0x5A5A)
+    assert l.cozk_sparse_layer_create(ctx.h, LB.MODE_PLAIN, 7, iv.h, av.h, None, 0, ctypes.byref(h)) == -1 and h.value is None
+
+    sp = mk(ctx, LB.MODE_PLAIN, 8, iv, av)
+    w = [rng.field(), rng.field()]
+    eq = cozk.SplitEqPolynomial(ctx, w)
+    other = cozk.Context(0)
+    try:
+        foreign = cozk.SplitEqPolynomial(other, w)
+        refused(sp.round, foreign)                      # an eq of another context
+        foreign.free()
+    finally:
+        other.close()
+    first = sp.round(eq)
+    eq.bind(rng.field())
+    eq.bind(rng.field())
+    refused(sp.round, eq)                               # a fully bound eq
+    refused(sp.round, cozk.SplitEqPolynomial(ctx, w), party=5)
+    h = ctypes.c_void_p(0x5A5A)
+    assert l.cozk_sparse_layer_to_dense(ctx.h, sp.h, 9, ctypes.byref(h)) == -1 and h.value is None
+    h = ctypes.c_void_p(0x5A5A)
+    assert l.cozk_sparse_layer_from_output(ctx.h, sp.h, av.h, None, 0, ctypes.byref(h)) == -1 and h.value is None  # 6 values for 2 groups
+    r = rng.field()
+    sp.bind(r)                                          # 8 -> 4
+    assert (len(sp), sp.count) == (4, 2)
+    sp.bind(r)                                          # 4 -> 2: one pair
+    assert (len(sp), sp.count) == (2, 1)
+    refused(sp.bind, r)                                 # fewer than one pair
+    refused(sp.round, cozk.SplitEqPolynomial(ctx, w), r)
+    refused(sp.output_local)                            # a length that is no multiple of 4
+    assert (len(sp), sp.count) == (2, 1)
+    dense = sp.to_dense()
+    assert len(dense.coeffs()) == 2
+    dense.free()
+    sp.free()
+    # the object is usable after a refusal: the same round again gives the same values
+    sp = mk(ctx, LB.MODE_PLAIN, 8, iv, av)
+    refused(sp.round, cozk.SplitEqPolynomial(ctx, w), party=5)
+    assert sp.round(cozk.SplitEqPolynomial(ctx, w)) == first
+    sp.free()
