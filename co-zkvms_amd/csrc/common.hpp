@@ -269,6 +269,15 @@ struct cozk_vec {       // device array of field elements / small scalars
     size_t bytes;
     bool owned;
 };
+// take the buffer, leave an empty vector: the caller owns what is returned (through the pool of v->ctx)
+static inline void* vec_adopt(cozk_vec* v) {
+    void* d = v->d;
+    v->d = nullptr;
+    v->owned = false;
+    v->n = 0;
+    v->bytes = 0;
+    return d;
+}
 
 static inline size_t scalar_kind_bytes(int kind) {
     switch (kind) {

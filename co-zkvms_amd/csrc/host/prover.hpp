@@ -131,22 +131,25 @@ struct RoundCtx {
     WorkerEnv* env;
     std::string error;
 };
+// the star exchange of one round: this party's four coefficients out, (r_j, the next claim as this party's additive share) back
+static fe star_round_exchange(WorkerEnv& env, const fe cf[4], fe& next_claim) {
+    Writer w;
+    w.vec_fr(std::vector<fe>(cf, cf + 4));
+    env.star->send_response(w.b);
+    Bytes req = env.star->receive_request();
+    Reader rd(req);
+    const fe r_j = rd.fr();
+    next_claim = env.additive_trivial(rd.fr());
+    return r_j;
+}
 static int prove_sumcheck_round_cb(void* user, int /*round*/, const uint64_t coeffs[16], uint64_t r_out[4], uint64_t next_claim_out[4]) {
     RoundCtx* rc = static_cast<RoundCtx*>(user);
     try {
-        WorkerEnv& env = *rc->env;
         double tb = trace_now_us();
-        Writer w;
-        std::vector<fe> cf(4);
+        fe cf[4], next_claim;
         for (int i = 0; i < 4; i++) cf[i] = fe_from_u64x4(coeffs + 4 * i);
-        w.vec_fr(cf);
-        env.star->send_response(w.b);
-        Bytes req = env.star->receive_request();
-        Reader rd(req);
-        fe r_j = rd.fr();
-        fe next_claim = rd.fr();
-        fe_to_u64x4(r_j, r_out);
-        fe_to_u64x4(env.additive_trivial(next_claim), next_claim_out);
+        fe_to_u64x4(star_round_exchange(*rc->env, cf, next_claim), r_out);
+        fe_to_u64x4(next_claim, next_claim_out);
         t_round_trace.t_star += trace_now_us() - tb;
         t_round_trace.rounds++;
         return 0;
@@ -154,6 +157,37 @@ static int prove_sumcheck_round_cb(void* user, int /*round*/, const uint64_t coe
         rc->error = e.what();
         return 1;
     }
+}
+// prove_sumcheck over a round CALL (cozk_toggle_round, cozk_sparse_layer_round): round(r, ev) binds with the previous challenge
+// (null in the first round) and gives g(0), g(2), g(3); up to num_rounds rounds, or until stop() says so after a round's exchange.
+// Appends the challenges to rs, leaves the last one in rr and the running claim in `claim`; returns the rounds run.
+template <class Round, class Stop>
+static int prove_rounds_by_call(WorkerEnv& env, int num_rounds, fe& claim, std::vector<fe>& rs, uint64_t rr[4], Round round, Stop stop) {
+    int j = 0;
+    while (j < num_rounds) {
+        uint64_t ev[12];
+        round(j ? rr : nullptr, ev);
+        fe cf[4];
+        cubic_from_round_evals(claim, ev, cf);
+        const fe r_j = star_round_exchange(env, cf, claim);
+        rs.push_back(r_j);
+        fe_to_u64x4(r_j, rr);
+        j++;
+        if (stop()) break;
+    }
+    return j;
+}
+// the prologue of a layer's sumcheck: the split-eq polynomial of the point, and party 0 announces the number of rounds
+static int prove_layer_prologue(WorkerEnv& env, const std::vector<fe>& r_grand_product, EqH& eq) {
+    std::vector<uint64_t> w = to_abi(r_grand_product);
+    const int num_rounds = (int)r_grand_product.size();
+    rc_check(cozk_spliteq_new(env.ctx, w.data(), num_rounds, &eq.h), env.ctx, "spliteq_new");
+    if (env.party == 0) {
+        Writer wr;
+        wr.u64((uint64_t)num_rounds);
+        env.star->send_response(wr.b);
+    }
+    return num_rounds;
 }
 static SumcheckResult prove_sumcheck(WorkerEnv& env, cozk_layer* layer, const fe& claim, cozk_spliteq* eq, int num_rounds) {
     SumcheckResult res;
@@ -176,6 +210,20 @@ static SumcheckResult prove_sumcheck(WorkerEnv& env, cozk_layer* layer, const fe
     w.fr(res.right.b);
     env.star->send_response(w.b);
     return res;
+}
+
+// the epilogue of a multiplication layer (grand_product.rs:205-217): r_layer from the coordinator,
+// claim = add_mul_public(left, right - left, r_layer).into_additive(), and the point for the layer below
+static void fold_layer_claims(WorkerEnv& env, const SumcheckResult& sc, const std::vector<fe>& rs, fe& claim, std::vector<fe>& r_grand_product) {
+    r_grand_product.assign(rs.rbegin(), rs.rend());
+    Bytes req = env.star->receive_request();
+    Reader rd(req);
+    const fe r_layer = rd.fr();
+    Share s;
+    s.a = Fr::add(sc.left.a, Fr::mul(Fr::sub(sc.right.a, sc.left.a), r_layer));
+    s.b = Fr::add(sc.left.b, Fr::mul(Fr::sub(sc.right.b, sc.left.b), r_layer));
+    claim = env.into_additive(s);
+    r_grand_product.push_back(r_layer);
 }
 
 struct SumcheckProof {
@@ -274,28 +322,28 @@ struct Rep3BatchedDenseGrandProduct {
         Rep3BatchedDenseGrandProduct gp;
         gp.layers.push_back(std::move(leaves));
         for (int i = 0; i < num_layers - 1; i++) {
-            cozk_layer* prev = gp.layers[i].h;
-            size_t n_out = (cozk_layer_len(prev) + 1) / 2;
             cozk_vec* ca = nullptr;
-            rc_check(cozk_layer_output_local(env.ctx, prev, env.mode == COZK_MODE_REP3 ? 1 : 0, env.key_self, env.key_prev,
-                                             env.mask_ctr, &ca),
+            rc_check(cozk_layer_output_local(env.ctx, gp.layers[i].h, env.mode == COZK_MODE_REP3 ? 1 : 0, env.key_self, env.key_prev, env.mask_ctr, &ca),
                      env.ctx, "layer_output_local");
-            VecH va(ca);
-            env.mask_ctr += n_out;
+            VecH va(ca), vb;
+            reshare_output(env, va, vb);
             cozk_layer* nl = nullptr;
-            if (env.mode == COZK_MODE_REP3) {
-                cozk_vec* cb = nullptr;
-                rc_check(cozk_vec_alloc(env.ctx, n_out, COZK_SCALAR_FR, &cb), env.ctx, "vec_alloc");
-                VecH vb(cb);
-                // ring reshare: own c.a -> next, c.b <- prev (arithmetic.rs:148-150)
-                env.ring->reshare(env.ctx, (const fe*)cozk_vec_device_ptr(va.h), (fe*)cozk_vec_device_ptr(vb.h), n_out);
-                rc_check(cozk_layer_create(env.ctx, COZK_MODE_REP3, va.h, vb.h, 1, &nl), env.ctx, "layer_create");
-            } else {
-                rc_check(cozk_layer_create(env.ctx, COZK_MODE_PLAIN, va.h, nullptr, 1, &nl), env.ctx, "layer_create");
-            }
+            rc_check(cozk_layer_create(env.ctx, env.mode, va.h, vb.h, 1, &nl), env.ctx, "layer_create");
             gp.layers.push_back(LayerH(nl));
         }
         return gp;
+    }
+    // the second half of a construct step, dense or sparse: `va` is the local half of layer_output (masked with counters from
+    // env.mask_ctr on, which advances by its length); Rep3: vb = what the ring reshare gives for it, own c.a -> next, c.b <- prev
+    // (arithmetic.rs:148-150).  Every party has the same length, so an empty vector is skipped by all.
+    static void reshare_output(WorkerEnv& env, const VecH& va, VecH& vb) {
+        const size_t n_out = cozk_vec_len(va.h);
+        env.mask_ctr += n_out;
+        if (env.mode != COZK_MODE_REP3) return;
+        cozk_vec* cb = nullptr;
+        rc_check(cozk_vec_alloc(env.ctx, n_out, COZK_SCALAR_FR, &cb), env.ctx, "vec_alloc");
+        vb = VecH(cb);
+        if (n_out) env.ring->reshare(env.ctx, (const fe*)cozk_vec_device_ptr(va.h), (fe*)cozk_vec_device_ptr(vb.h), n_out);
     }
 
     size_t num_layers() const { return layers.size(); }
@@ -314,25 +362,9 @@ struct Rep3BatchedDenseGrandProduct {
     // prove_layer (grand_product.rs:186-217)
     static void prove_layer(WorkerEnv& env, cozk_layer* layer, fe& claim, std::vector<fe>& r_grand_product) {
         EqH eq;
-        std::vector<uint64_t> w = to_abi(r_grand_product);
-        rc_check(cozk_spliteq_new(env.ctx, w.data(), (int)r_grand_product.size(), &eq.h), env.ctx, "spliteq_new");
-        int num_rounds = (int)r_grand_product.size();
-        if (env.party == 0) {
-            Writer wr;
-            wr.u64((uint64_t)num_rounds);
-            env.star->send_response(wr.b);
-        }
+        const int num_rounds = prove_layer_prologue(env, r_grand_product, eq);
         SumcheckResult sc = prove_sumcheck(env, layer, claim, eq.h, num_rounds);
-        r_grand_product.assign(sc.r.rbegin(), sc.r.rend());
-        Bytes req = env.star->receive_request();
-        Reader rd(req);
-        fe r_layer = rd.fr();
-        // claim = add_mul_public(left, right - left, r_layer).into_additive()
-        Share s;
-        s.a = Fr::add(sc.left.a, Fr::mul(Fr::sub(sc.right.a, sc.left.a), r_layer));
-        s.b = Fr::add(sc.left.b, Fr::mul(Fr::sub(sc.right.b, sc.left.b), r_layer));
-        claim = env.into_additive(s);
-        r_grand_product.push_back(r_layer);
+        fold_layer_claims(env, sc, sc.r, claim, r_grand_product);
     }
 
     // prove_grand_product_worker (grand_product.rs:111-130).  Layers are bound destructively.
@@ -439,49 +471,36 @@ struct Rep3ToggledBatchedGrandProduct {
     static Rep3ToggledBatchedGrandProduct construct(WorkerEnv& env, ToggleH toggle) {
         Rep3ToggledBatchedGrandProduct gp;
         gp.batch = cozk_toggle_batch(toggle.h);
+        cozk_layer* l0 = nullptr;  // the lowest dense layer
         if (toggle_sparse_enabled()) {
-            construct_sparse(env, gp, toggle.h);
-            gp.toggle_layer = std::move(toggle);
-            return gp;
+            l0 = construct_sparse(env, gp, toggle.h);
+        } else {
+            rc_check(cozk_toggle_layer_output(env.ctx, toggle.h, env.party, &l0), env.ctx, "toggle_layer_output");
         }
-        cozk_layer* l0 = nullptr;
-        rc_check(cozk_toggle_layer_output(env.ctx, toggle.h, env.party, &l0), env.ctx, "toggle_layer_output");
-        size_t batch = cozk_toggle_batch(toggle.h);
-        gp.sparse_layers = Rep3BatchedDenseGrandProduct::construct(env, LayerH(l0), batch);
+        gp.sparse_layers = Rep3BatchedDenseGrandProduct::construct(env, LayerH(l0), gp.batch);
         gp.toggle_layer = std::move(toggle);
         return gp;
     }
     // the sparse path of construct: sparse layers up the tree (output_local, the ring reshare of the compact vector, from_output)
-    // until the rule stops one; that layer is scattered and Rep3BatchedDenseGrandProduct::construct continues from it
-    static void construct_sparse(WorkerEnv& env, Rep3ToggledBatchedGrandProduct& gp, cozk_toggle* toggle) {
+    // until the rule stops one; that layer is scattered and returned, for Rep3BatchedDenseGrandProduct::construct to continue from
+    static cozk_layer* construct_sparse(WorkerEnv& env, Rep3ToggledBatchedGrandProduct& gp, cozk_toggle* toggle) {
         cozk_sparse_layer* s0 = nullptr;
         rc_check(cozk_toggle_sparse_output(env.ctx, toggle, env.party, &s0), env.ctx, "toggle_sparse_output");
         SparseH cur(s0);
-        for (;;) {
-            if (!sparse_construct_keeps(cozk_sparse_layer_count(cur.h), cozk_sparse_layer_len(cur.h), gp.batch)) {
-                cozk_layer* l = nullptr;
-                rc_check(cozk_sparse_layer_to_dense(env.ctx, cur.h, env.party, &l), env.ctx, "sparse_layer_to_dense");
-                gp.sparse_layers = Rep3BatchedDenseGrandProduct::construct(env, LayerH(l), gp.batch);
-                return;
-            }
+        while (sparse_construct_keeps(cozk_sparse_layer_count(cur.h), cozk_sparse_layer_len(cur.h), gp.batch)) {
             cozk_vec* ca = nullptr;
             rc_check(cozk_sparse_layer_output_local(env.ctx, cur.h, env.mode == COZK_MODE_REP3 ? 1 : 0, env.key_self, env.key_prev, env.mask_ctr, &ca),
                      env.ctx, "sparse_layer_output_local");
             VecH va(ca), vb;
-            const size_t n_out = cozk_vec_len(va.h);
-            env.mask_ctr += n_out;
-            if (env.mode == COZK_MODE_REP3) {
-                cozk_vec* cb = nullptr;
-                rc_check(cozk_vec_alloc(env.ctx, n_out, COZK_SCALAR_FR, &cb), env.ctx, "vec_alloc");
-                vb = VecH(cb);
-                // ring reshare: own c.a -> next, c.b <- prev (arithmetic.rs:148-150); every party has the same n_out
-                if (n_out) env.ring->reshare(env.ctx, (const fe*)cozk_vec_device_ptr(va.h), (fe*)cozk_vec_device_ptr(vb.h), n_out);
-            }
+            Rep3BatchedDenseGrandProduct::reshare_output(env, va, vb);
             cozk_sparse_layer* nx = nullptr;
             rc_check(cozk_sparse_layer_from_output(env.ctx, cur.h, va.h, vb.h, 1, &nx), env.ctx, "sparse_layer_from_output");
             gp.sparse_low.push_back(std::move(cur));
             cur = SparseH(nx);
         }
+        cozk_layer* l = nullptr;
+        rc_check(cozk_sparse_layer_to_dense(env.ctx, cur.h, env.party, &l), env.ctx, "sparse_layer_to_dense");
+        return l;
     }
     size_t num_layers() const { return sparse_low.size() + sparse_layers.layers.size() + 1; }
 
@@ -489,40 +508,19 @@ struct Rep3ToggledBatchedGrandProduct {
     // cozk_sparse_layer_round with the star exchange of prove_toggle_layer, then the hand-over to the dense round loop
     static void prove_sparse_layer(WorkerEnv& env, cozk_sparse_layer* s, size_t batch, fe& claim, std::vector<fe>& r_grand_product) {
         EqH eq;
-        std::vector<uint64_t> w = to_abi(r_grand_product);
-        const int num_rounds = (int)r_grand_product.size();
-        rc_check(cozk_spliteq_new(env.ctx, w.data(), num_rounds, &eq.h), env.ctx, "spliteq_new");
-        if (env.party == 0) {
-            Writer wr;
-            wr.u64((uint64_t)num_rounds);
-            env.star->send_response(wr.b);
-        }
+        const int num_rounds = prove_layer_prologue(env, r_grand_product, eq);
         fe previous_claim = claim;
         std::vector<fe> rs;
         uint64_t rr[4];
-        int round = 0;
         bool handover = false;
-        while (round < num_rounds && !handover) {
-            uint64_t ev[12];
-            rc_check(cozk_sparse_layer_round(env.ctx, s, eq.h, round ? rr : nullptr, env.party, ev), env.ctx, "sparse_layer_round");
-            fe g0 = fe_from_u64x4(ev);
-            fe pts[4] = {g0, Fr::sub(previous_claim, g0), fe_from_u64x4(ev + 4), fe_from_u64x4(ev + 8)};
-            std::vector<fe> cf(4);
-            unipoly_from_evals(pts, 4, cf.data());
-            Writer wr;
-            wr.vec_fr(cf);
-            env.star->send_response(wr.b);
-            Bytes req = env.star->receive_request();
-            Reader rd(req);
-            fe r_j = rd.fr();
-            previous_claim = env.additive_trivial(rd.fr());
-            rs.push_back(r_j);
-            fe_to_u64x4(r_j, rr);
-            round++;
-            size_t next_cnt = 0;
-            rc_check(cozk_sparse_layer_next_count(env.ctx, s, &next_cnt), env.ctx, "sparse_layer_next_count");
-            handover = sparse_handover_after_bind(next_cnt, cozk_sparse_layer_len(s), batch);
-        }
+        const int round = prove_rounds_by_call(
+            env, num_rounds, previous_claim, rs, rr,
+            [&](const uint64_t* r, uint64_t* ev) { rc_check(cozk_sparse_layer_round(env.ctx, s, eq.h, r, env.party, ev), env.ctx, "sparse_layer_round"); },
+            [&] {
+                size_t next_cnt = 0;
+                rc_check(cozk_sparse_layer_next_count(env.ctx, s, &next_cnt), env.ctx, "sparse_layer_next_count");
+                return handover = sparse_handover_after_bind(next_cnt, cozk_sparse_layer_len(s), batch);
+            });
         COZK_REQUIRE(handover && round >= 1 && round < num_rounds, "toggled grand product: a sparse layer must hand over with a dense round left");
         // the hand-over: bind layer and eq with the last challenge, scatter, and let the dense round loop run the rest
         rc_check(cozk_sparse_layer_bind(env.ctx, s, rr), env.ctx, "sparse_layer_bind");
@@ -532,49 +530,20 @@ struct Rep3ToggledBatchedGrandProduct {
         LayerH dense(l);
         SumcheckResult sc = prove_sumcheck(env, dense.h, previous_claim, eq.h, num_rounds - round);
         rs.insert(rs.end(), sc.r.begin(), sc.r.end());
-        r_grand_product.assign(rs.rbegin(), rs.rend());
-        Bytes req = env.star->receive_request();
-        Reader rd(req);
-        fe r_layer = rd.fr();
-        // claim = add_mul_public(left, right - left, r_layer).into_additive()
-        Share sh;
-        sh.a = Fr::add(sc.left.a, Fr::mul(Fr::sub(sc.right.a, sc.left.a), r_layer));
-        sh.b = Fr::add(sc.left.b, Fr::mul(Fr::sub(sc.right.b, sc.left.b), r_layer));
-        claim = env.into_additive(sh);
-        r_grand_product.push_back(r_layer);
+        fold_layer_claims(env, sc, rs, claim, r_grand_product);
     }
 
     // prove_layer of the toggle layer (:850-873) with prove_sumcheck (sumcheck.rs:96-131) over cozk_toggle_round
     static void prove_toggle_layer(WorkerEnv& env, cozk_toggle* t, const fe& claim_in, std::vector<fe>& r_grand_product) {
         EqH eq;
-        std::vector<uint64_t> w = to_abi(r_grand_product);
-        int num_rounds = (int)r_grand_product.size();
-        rc_check(cozk_spliteq_new(env.ctx, w.data(), num_rounds, &eq.h), env.ctx, "spliteq_new");
-        if (env.party == 0) {
-            Writer wr;
-            wr.u64((uint64_t)num_rounds);
-            env.star->send_response(wr.b);
-        }
+        const int num_rounds = prove_layer_prologue(env, r_grand_product, eq);
         fe previous_claim = claim_in;
         std::vector<fe> rs;
         uint64_t rr[4];
-        for (int round = 0; round < num_rounds; round++) {
-            uint64_t ev[12];
-            rc_check(cozk_toggle_round(env.ctx, t, eq.h, round ? rr : nullptr, env.party, ev), env.ctx, "toggle_round");
-            fe g0 = fe_from_u64x4(ev);
-            fe pts[4] = {g0, Fr::sub(previous_claim, g0), fe_from_u64x4(ev + 4), fe_from_u64x4(ev + 8)};
-            std::vector<fe> cf(4);
-            unipoly_from_evals(pts, 4, cf.data());
-            Writer wr;
-            wr.vec_fr(cf);
-            env.star->send_response(wr.b);
-            Bytes req = env.star->receive_request();
-            Reader rd(req);
-            fe r_j = rd.fr();
-            previous_claim = env.additive_trivial(rd.fr());
-            rs.push_back(r_j);
-            fe_to_u64x4(r_j, rr);
-        }
+        prove_rounds_by_call(
+            env, num_rounds, previous_claim, rs, rr,
+            [&](const uint64_t* r, uint64_t* ev) { rc_check(cozk_toggle_round(env.ctx, t, eq.h, r, env.party, ev), env.ctx, "toggle_round"); },
+            [] { return false; });
         if (num_rounds > 0) rc_check(cozk_toggle_bind(env.ctx, t, rr), env.ctx, "toggle_bind");
         // final_claims (:825-835): (promote_to_trivial_share(flag), fingerprint)
         uint64_t fl[4], pa[4], pb[4];

@@ -358,10 +358,8 @@ static void shamir_gp_prove_layers(const ShamirGpArgs& a, std::vector<std::vecto
                 }
             }
             for (int p = 0; p < senders; p++) {
-                const fe g0 = fe_from_u64x4(ev.data() + 12 * p);
-                const fe pts[4] = {g0, Fr::sub(claim, g0), fe_from_u64x4(ev.data() + 12 * p + 4), fe_from_u64x4(ev.data() + 12 * p + 8)};
                 fe c4[4];
-                unipoly_from_evals(pts, 4, c4);
+                cubic_from_round_evals(claim, ev.data() + 12 * p, c4);
                 for (int k = 0; k < 4; k++) cf[k][p] = c4[k];
             }
             std::vector<fe> poly(4);

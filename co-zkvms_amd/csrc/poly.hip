@@ -412,16 +412,32 @@ static __device__ __forceinline__ size_t layer_chunk_count(size_t len, bool nest
     return nch > limit ? limit : nch;
 }
 
-// the eq pair of chunk c at 0, 2, 3.  Not nested: E1 fully bound, the pair comes from E2 (dense_interleaved_poly.rs:218-268).
-// Nested: Dao-Thaler split, chunk c belongs to x2 = c / E1_half, x1 = c % E1_half (:269-356); `scale` = E2[x2] multiplies its terms.
-static __device__ __forceinline__ void layer_eq_at(bool nested, const fe* E1, size_t E1_half, const fe* E2, size_t c, fe e[3], fe& scale) {
+// the eq pair of item c at 0, 2, 3 from split-eq tables, for the dense layers, the toggle layers and the sparse pair layers alike.
+// Not nested: E1 fully bound, the pair comes from E2 (dense_interleaved_poly.rs:218-268).  Nested: Dao-Thaler split, item c
+// belongs to x2 = c >> log_E1_half, x1 = c % E1_half (:269-356); `scale` = E2[x2] multiplies its terms -- handed back on its own,
+// so that a caller multiplies it into the weights or into its products, whichever keeps fewer values live.
+static __device__ __forceinline__ void split_eq_at(bool nested, const fe* E1, int log_E1_half, const fe* E2, size_t c, fe e[3], fe& scale) {
     if (nested) {
-        size_t x2 = c >> (__ffsll((long long)E1_half) - 1), x1 = c & (E1_half - 1);  // E1_half is a power of two
+        size_t x2 = c >> log_E1_half, x1 = c & (((size_t)1 << log_E1_half) - 1);
         eq3(fe_load(E1 + 2 * x1), fe_load(E1 + 2 * x1 + 1), e);
         scale = fe_load(E2 + x2);
     } else {
         eq3(fe_load(E2 + 2 * c), fe_load(E2 + 2 * c + 1), e);
     }
+}
+// the dense layer kernels carry E1_half itself, a power of two
+static __device__ __forceinline__ void layer_eq_at(bool nested, const fe* E1, size_t E1_half, const fe* E2, size_t c, fe e[3], fe& scale) {
+    split_eq_at(nested, E1, __ffsll((long long)E1_half) - 1, E2, c, e, scale);
+}
+// items a round over split-eq tables sums: zip() stops at the shorter side of the layer and the eq table
+template <int NESTED>
+static __device__ __forceinline__ size_t split_eq_limit(size_t E2_len, int log_E1_half) {
+    return NESTED ? ((size_t)E2_len << log_E1_half) : E2_len / 2;
+}
+// the workgroup's sum of v through `sh` (fr_block_sum) to row `row` of the partial sums, gridDim.x entries per row
+static __device__ __forceinline__ void partial_row_sum(fe v, fe* sh, fe* __restrict__ partial, size_t row) {
+    v = fr_block_sum(v, sh);
+    if (threadIdx.x == 0) fe_store(partial + row * gridDim.x + blockIdx.x, v);
 }
 
 // the three terms of one chunk (l0, r0, l1, r1): t_X = (L(X) x R(X)) e_X [scale] at X = 0, 2, 3.  The caller adds them to its sums

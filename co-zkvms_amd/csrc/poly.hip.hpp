@@ -223,4 +223,11 @@ static inline void unipoly_from_evals(const fe* ev, int n, fe* coeffs) {
     coeffs[2] = Fr::sub(h2, three_a3);
     coeffs[3] = a3;
 }
+// the cubic of a sumcheck round from what a round call returns, ev = g(0), g(2), g(3) as 4 x u64 each, and the running claim:
+// g(1) = claim - g(0)
+static inline void cubic_from_round_evals(const fe& claim, const uint64_t ev[12], fe coeffs[4]) {
+    const fe g0 = fe_from_u64x4(ev);
+    const fe pts[4] = {g0, Fr::sub(claim, g0), fe_from_u64x4(ev + 4), fe_from_u64x4(ev + 8)};
+    unipoly_from_evals(pts, 4, coeffs);
+}
 

@@ -265,7 +265,7 @@ __global__ void __launch_bounds__(PT) k_sparse_cubic(const uint32_t* __restrict_
                                                   fe one_a, fe one_b, fe sub_one, size_t nquads, const fe* __restrict__ E1, int log_E1_half,
                                                   const fe* __restrict__ E2, size_t E2_len, fe* __restrict__ partial) {
     __shared__ fe sh4[4];
-    const size_t limit = NESTED ? ((size_t)E2_len << log_E1_half) : E2_len / 2;
+    const size_t limit = split_eq_limit<NESTED>(E2_len, log_E1_half);
     if (nquads > limit) nquads = limit;
     const Sh<NC> one = sp_one<NC>(one_a, one_b);
     fe D0 = Fr::zero(), D2 = Fr::zero(), D3 = Fr::zero();
@@ -285,27 +285,20 @@ __global__ void __launch_bounds__(PT) k_sparse_cubic(const uint32_t* __restrict_
         L1 = sh_add<NC>(L1, ml);
         R1 = sh_add<NC>(R1, mr);
         fe t3 = Fr::sub(sh_local_mul<NC>(L1, R1), sub_one);
-        fe e[3];
+        fe e[3], sc;
+        split_eq_at(NESTED, E1, log_E1_half, E2, j, e, sc);
         if (NESTED) {
-            const size_t x2 = j >> log_E1_half, x1 = j & (((size_t)1 << log_E1_half) - 1);
-            eq3(fe_load(E1 + 2 * x1), fe_load(E1 + 2 * x1 + 1), e);
-            const fe sc = fe_load(E2 + x2);
             t0 = Fr::mul(t0, sc);
             t2 = Fr::mul(t2, sc);
             t3 = Fr::mul(t3, sc);
-        } else {
-            eq3(fe_load(E2 + 2 * j), fe_load(E2 + 2 * j + 1), e);
         }
         D0 = Fr::add(D0, Fr::mul(e[0], t0));
         D2 = Fr::add(D2, Fr::mul(e[1], t2));
         D3 = Fr::add(D3, Fr::mul(e[2], t3));
     }
-    fe v = fr_block_sum(D0, sh4);
-    if (threadIdx.x == 0) fe_store(partial + blockIdx.x, v);
-    v = fr_block_sum(D2, sh4);
-    if (threadIdx.x == 0) fe_store(partial + (size_t)gridDim.x + blockIdx.x, v);
-    v = fr_block_sum(D3, sh4);
-    if (threadIdx.x == 0) fe_store(partial + 2 * (size_t)gridDim.x + blockIdx.x, v);
+    partial_row_sum(D0, sh4, partial, 0);
+    partial_row_sum(D2, sh4, partial, 1);
+    partial_row_sum(D3, sh4, partial, 2);
 }
 
 // scatter to dense: fill with trivial ones, then the stored pairs
@@ -468,17 +461,9 @@ int cozk_sparse_layer_create(cozk_ctx* ctx, int mode, size_t n, cozk_vec* idx, c
         cozk_vec* src[2] = {a, mode == COZK_MODE_REP3 ? b : nullptr};
         const bool adopt = take_ownership && idx->owned && a->owned && (!src[1] || src[1]->owned) && idx->ctx == ctx && a->ctx == ctx && (!src[1] || src[1]->ctx == ctx);
         if (adopt) {
-            auto take = [](cozk_vec* v) {
-                void* d = v->d;
-                v->d = nullptr;
-                v->owned = false;
-                v->n = 0;
-                v->bytes = 0;
-                return d;
-            };
-            s->idx[0] = (uint32_t*)take(idx);
-            s->v[0][0] = (fe*)take(a);
-            if (src[1]) s->v[0][1] = (fe*)take(src[1]);
+            s->idx[0] = (uint32_t*)vec_adopt(idx);
+            s->v[0][0] = (fe*)vec_adopt(a);
+            if (src[1]) s->v[0][1] = (fe*)vec_adopt(src[1]);
             s->cap[0] = cnt;
         } else {
             sparse_reserve(s, 0, cnt);
@@ -499,8 +484,8 @@ int cozk_toggle_sparse_output(cozk_ctx* ctx, const cozk_toggle* t, int party_id,
     if (out) *out = nullptr;
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(ctx && t && out, "toggle_sparse_output: null argument");
-        COZK_REQUIRE(t->cur < 0 && party_id >= 0 && party_id < 3, "toggle_sparse_output: needs an unbound toggle layer and a party 0..2");
-        const size_t n = t->batch * t->n0, npairs = n / 2;
+        COZK_REQUIRE(t->s.cur < 0 && party_id >= 0 && party_id < 3, "toggle_sparse_output: needs an unbound toggle layer and a party 0..2");
+        const size_t n = t->s.batch * t->s.n0, npairs = n / 2;
         COZK_REQUIRE(npairs <= ((size_t)1 << 32), "toggle_sparse_output: more than 2^32 pairs");
         cozk_sparse_layer* s = sparse_new(ctx, t->mode, n);
         if (t->mode == COZK_MODE_REP3) s->party = party_id;
@@ -508,7 +493,7 @@ int cozk_toggle_sparse_output(cozk_ctx* ctx, const cozk_toggle* t, int party_id,
             cozk_sparse_layer* s;
             ~Guard() { if (s) cozk_sparse_layer_free(s); }
         } guard{s};
-        const SpToggleFlag f{t->fl0, log2_sz(t->n0)};
+        const SpToggleFlag f{t->fl0, log2_sz(t->s.n0)};
         const size_t tiles = sparse_tiles(npairs);
         unsigned long long* blk = (unsigned long long*)ctx_dev_alloc(ctx, (tiles + 1) * sizeof(unsigned long long));
         struct Blk {
@@ -521,10 +506,8 @@ int cozk_toggle_sparse_output(cozk_ctx* ctx, const cozk_toggle* t, int party_id,
         if (cnt) {
             fe one_a, one_b;
             sparse_ones(t->mode, party_id, one_a, one_b);
-            if (t->mode == COZK_MODE_REP3)
-                k_sparse_from_toggle<2><<<(unsigned)tiles, PT, 0, ctx->stream>>>(t->fp0[0], t->fp0[1], f, npairs, one_a, one_b, blk, s->idx[0], s->v[0][0], s->v[0][1]);
-            else
-                k_sparse_from_toggle<1><<<(unsigned)tiles, PT, 0, ctx->stream>>>(t->fp0[0], nullptr, f, npairs, one_a, one_b, blk, s->idx[0], s->v[0][0], nullptr);
+            auto* const kernel = t->mode == COZK_MODE_REP3 ? k_sparse_from_toggle<2> : k_sparse_from_toggle<1>;
+            kernel<<<(unsigned)tiles, PT, 0, ctx->stream>>>(t->fp0[0], t->fp0[1], f, npairs, one_a, one_b, blk, s->idx[0], s->v[0][0], s->v[0][1]);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(ctx->stream));  // blk returns to the pool with this call
         }
@@ -591,11 +574,7 @@ int cozk_sparse_layer_from_output(cozk_ctx* ctx, cozk_sparse_layer* s, cozk_vec*
         for (int c = 0; c < 2; c++) {
             if (!src[c]) continue;
             if (adopt) {
-                nx->v[0][c] = (fe*)src[c]->d;
-                src[c]->d = nullptr;
-                src[c]->owned = false;
-                src[c]->n = 0;
-                src[c]->bytes = 0;
+                nx->v[0][c] = (fe*)vec_adopt(src[c]);
             } else {
                 nx->v[0][c] = (fe*)ctx_dev_alloc(ctx, 2 * (G ? G : 1) * sizeof(fe));
                 if (G) HIP_TRY(hipMemcpyAsync(nx->v[0][c], src[c]->d, 2 * G * sizeof(fe), hipMemcpyDeviceToDevice, ctx->stream));
@@ -664,10 +643,7 @@ int cozk_sparse_layer_round(cozk_ctx* ctx, cozk_sparse_layer* s, cozk_spliteq* e
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(!spliteq_bound(e), "sparse_layer_round: the bind left no round to run");
         const size_t nquads = s->n / 4;
-        const bool nested = e->E1_len != 1;
-        const fe* E1 = e->E1[e->c1];
-        const fe* E2 = e->E2[e->c2];
-        const int lg1 = nested ? log2_sz(e->E1_len / 2) : 0;
+        const EqView v = eq_view(e);
         fe sums[6];  // D(0), D(2), D(3), S_all(0), S_all(2), S_all(3)
         // additive_sub_shared_by_public / additive_add_public: party 0 only (the plain prover is party 0)
         const bool pub = s->mode == COZK_MODE_PLAIN || party_id == 0;
@@ -677,23 +653,15 @@ int cozk_sparse_layer_round(cozk_ctx* ctx, cozk_sparse_layer* s, cozk_spliteq* e
             fe one_a, one_b;
             sparse_ones(s->mode, party_id, one_a, one_b);
             const fe sub_one = pub ? Fr::one() : Fr::zero();
-            const fe* vb = s->mode == COZK_MODE_REP3 ? sp_v(s, 1) : nullptr;
-            if (s->mode == COZK_MODE_REP3) {
-                if (nested) k_sparse_cubic<2, 1><<<gx, PT, 0, ctx->stream>>>(s->idx[s->cur], sp_v(s, 0), vb, s->cnt, one_a, one_b, sub_one, nquads, E1, lg1, E2, e->E2_len, sl.partial);
-                else k_sparse_cubic<2, 0><<<gx, PT, 0, ctx->stream>>>(s->idx[s->cur], sp_v(s, 0), vb, s->cnt, one_a, one_b, sub_one, nquads, E1, 0, E2, e->E2_len, sl.partial);
-            } else {
-                if (nested) k_sparse_cubic<1, 1><<<gx, PT, 0, ctx->stream>>>(s->idx[s->cur], sp_v(s, 0), vb, s->cnt, one_a, one_b, sub_one, nquads, E1, lg1, E2, e->E2_len, sl.partial);
-                else k_sparse_cubic<1, 0><<<gx, PT, 0, ctx->stream>>>(s->idx[s->cur], sp_v(s, 0), vb, s->cnt, one_a, one_b, sub_one, nquads, E1, 0, E2, e->E2_len, sl.partial);
-            }
+            const bool rep3 = s->mode == COZK_MODE_REP3;
+            auto* const kernel = rep3 ? (v.nested ? k_sparse_cubic<2, 1> : k_sparse_cubic<2, 0>) : (v.nested ? k_sparse_cubic<1, 1> : k_sparse_cubic<1, 0>);
+            kernel<<<gx, PT, 0, ctx->stream>>>(s->idx[s->cur], sp_v(s, 0), sp_v(s, 1), s->cnt, one_a, one_b, sub_one, nquads, v.E1, v.lg1, v.E2, v.E2_len, sl.partial);
             HIP_TRY(hipGetLastError());
-            if (nested) k_toggle_eq_sums<1><<<1, RT, 0, ctx->stream>>>(E1, lg1, E2, e->E2_len, nquads, sl.res + 3);
-            else k_toggle_eq_sums<0><<<1, RT, 0, ctx->stream>>>(E1, 0, E2, e->E2_len, nquads, sl.res + 3);
+            eq_sums_launch(ctx, v, nquads, sl.res + 3);
             finish_sums(ctx, sl, 3, gx, Fr::one(), 0, sums);
         } else {  // nothing stored: the all-ones sums alone, no launch of an empty grid
             fe* res = result_slot(ctx, 6);
-            if (nested) k_toggle_eq_sums<1><<<1, RT, 0, ctx->stream>>>(E1, lg1, E2, e->E2_len, nquads, res + 3);
-            else k_toggle_eq_sums<0><<<1, RT, 0, ctx->stream>>>(E1, 0, E2, e->E2_len, nquads, res + 3);
-            HIP_TRY(hipGetLastError());
+            eq_sums_launch(ctx, v, nquads, res + 3);
             fetch_fe(ctx, res, 6, sums);
             for (int k = 0; k < 3; k++) sums[k] = Fr::zero();
         }

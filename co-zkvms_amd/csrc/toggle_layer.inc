@@ -20,25 +20,66 @@
 // are the same); the oracle (oracle/pysparse.py) restates the SPARSE algorithms literally and the parity tests compare
 // against it.
 
+static inline int log2_sz(size_t n) {
+    int l = 0;
+    while (((size_t)1 << l) < n) l++;
+    return l;
+}
+
+// Where a toggle layer stands in its binds -- the ONE copy of the progression for cozk_toggle and cozk_toggle_group
+// (sparse_grand_product.rs:104-290): n_cur halves per bind; the bind that leaves one entry per circuit (layer_len == 2) coalesces to
+// per-circuit vectors of L = next_power_of_two(batch) entries, which then halve.
+struct ToggleShape {
+    size_t batch;    // circuits (2 per flag column)
+    size_t n0;       // fingerprints per circuit (power of two)
+    size_t n_cur;    // current per-circuit length (n0 / 2^binds) while not coalesced
+    size_t L;        // length of the coalesced vectors
+    bool coalesced;  // flags / fingerprints are per-circuit vectors of length L (:104-134)
+    int cur;         // -1: unbound (the packed 0/1 flag bytes); else which ping-pong side is live
+    void init(size_t batch_, size_t n0_) {
+        batch = batch_;
+        n0 = n_cur = n0_;
+        coalesced = false;
+        L = 1;
+        while (L < batch) L <<= 1;
+        cur = -1;
+    }
+    size_t npairs() const { return coalesced ? L / 2 : batch * n_cur / 2; }
+    int log_half_n() const { return coalesced ? -1 : log2_sz(n_cur / 2); }
+    bool bound() const { return coalesced && L == 1; }
+    bool last_bind() const { return coalesced && L == 2; }  // the bind that leaves no round to run
+    int dst() const { return cur < 0 ? 0 : 1 - cur; }
+    // entries the next bind writes, and whether it is the one that coalesces
+    struct BindSizes {
+        size_t n_fp, n_fl;
+        bool coalesces;
+    };
+    BindSizes bind_sizes() const {
+        if (coalesced) return BindSizes{L / 2, L / 2, false};
+        return BindSizes{batch * n_cur / 2, (batch / 2) * n_cur / 2, n_cur == 2};
+    }
+    void advance() {  // the bind went to side dst()
+        cur = dst();
+        if (coalesced) L /= 2;
+        else if ((n_cur /= 2) == 1) coalesced = true;
+    }
+};
+
 struct cozk_toggle {
     cozk_ctx* ctx;
     int mode;
-    size_t batch;        // circuits (2 per flag column)
-    size_t n0;           // fingerprints per circuit (power of two)
-    size_t n_cur;        // current per-circuit length (n0 / 2^binds) while not coalesced
-    bool coalesced;      // flags / fingerprints are per-circuit vectors of length L (sparse_grand_product.rs:104-134)
-    size_t L;            // next_power_of_two(batch)
+    ToggleShape s;
     fe* fp0[2];          // unbound fingerprints [component] (owned)
     uint8_t* fl0;        // unbound flags, packed 0/1 bytes, (batch / 2) x n0 (owned): 32x less traffic than field elements
                          // for the layer output, the first round and the first bind
     fe* fp[2][2];        // ping-pong bound fingerprints [which][component]
     fe* fl[2];           // ping-pong bound flags
     size_t fp_cap[2], fl_cap[2];
-    int cur;             // -1: unbound; else which ping-pong buffer is live
 };
 
-static const fe* tg_fp(const cozk_toggle* t, int c) { return t->cur < 0 ? t->fp0[c] : t->fp[t->cur][c]; }
-static const fe* tg_fl(const cozk_toggle* t) { return t->cur < 0 ? nullptr : t->fl[t->cur]; }  // bound flags (field elements)
+static const fe* tg_fp(const cozk_toggle* t, int c) { return t->s.cur < 0 ? t->fp0[c] : t->fp[t->s.cur][c]; }  // null for c = 1 of a plain layer
+// the flags the kernels read: the packed bytes while unbound (FT = 0), field elements after (FT = 1)
+static const void* tg_fl(const cozk_toggle* t) { return t->s.cur < 0 ? (const void*)t->fl0 : (const void*)t->fl[t->s.cur]; }
 
 // flags arrive as 0/1 bytes, one column of n0 entries per PAIR of circuits (the read and the write circuit of a memory
 // share their flags: sparse_grand_product.rs:84 `flag_indices[batch_index / 2]`); they are packed into one array
@@ -114,21 +155,103 @@ __global__ void __launch_bounds__(PT) k_toggle_coalesce(const fe* __restrict__ p
 // -- runs with all 64 lanes busy: with Jolt's ~10 % flag density ~19 % of the pairs are active in the first round, and
 // without the queue every wave would pay the full path for its few active lanes.
 // log_half_n = log2(pairs per circuit) selects the flag pair of circuit b >> 1; log_half_n < 0: coalesced vectors.
+
+// the flag pair of pair j: circuits 2q and 2q + 1 share the flags of memory q
+static __device__ __forceinline__ size_t toggle_flag_index(size_t j, int log_half_n) {
+    if (log_half_n < 0) return j;
+    const size_t b = j >> log_half_n, i = j & (((size_t)1 << log_half_n) - 1);
+    return ((b >> 1) << log_half_n) + i;
+}
+// the look: is one of the pair's two flags set?  Packed bytes: one 16-bit load and no field elements
+template <int FT>
+static __device__ __forceinline__ bool toggle_pair_active(const void* __restrict__ fl, size_t fj) {
+    if (FT == 0) return *(const uint16_t*)((const uint8_t*)fl + 2 * fj) != 0;
+    fe f0, f1;
+    return toggle_flag_pair<FT>(fl, fj, f0, f1);
+}
+
+// The wave queue, the ONE copy of the compaction: every wave walks its pairs in a grid-stride loop, look(j) says whether pair j is
+// active, the active pairs' offsets from the wave's first pair are enqueued by ballot (wave_queue_push), and whenever 64 are waiting
+// the wave runs heavy(j) on them with full lanes and carries the rest to the front (wave_queue_pop); what is left when the pairs run
+// out is flushed the same way.  `queue` is this wave's 128 entries, qn (wave-uniform) how many wait.  A wave's LDS operations
+// execute in program order; the wave barriers keep the compiler from moving them.
+
+// enqueue: the lanes with `active` append their pair's offset, in lane order
+static __device__ __forceinline__ void wave_queue_push(uint32_t* queue, int& qn, int lane, bool active, uint32_t off) {
+    const unsigned long long m = __ballot(active);
+    if (active) queue[qn + __popcll(m & ((1ull << lane) - 1ull))] = off;
+    qn += __popcll(m);
+    __builtin_amdgcn_wave_barrier();
+}
+// the first `take` entries are done: carry the rest (fewer than 64) to the front
+static __device__ __forceinline__ void wave_queue_pop(uint32_t* queue, int& qn, int lane, int take) {
+    const uint32_t keep = lane < qn - take ? queue[take + lane] : 0u;
+    __builtin_amdgcn_wave_barrier();
+    if (lane < qn - take) queue[lane] = keep;
+    __builtin_amdgcn_wave_barrier();
+    qn -= take;
+}
+// The two loop shapes over those steps.  TWO call sites of heavy, a full flush inside the loop and the remainder behind it, with
+// pre_flush() (wave-uniform; k_toggle_cubic9's periodic fold) in front of either: the single-layer kernels.  In the one-call-site
+// shape below their register allocation moves (VGPRs here -> there: k_toggle_cubic<1, 1, 0> 91 -> 98, occupancy 5 -> 4; <1, 0, 0>
+// 76 -> 90, occupancy 6 -> 5; <1, 1, 1> 86 -> 74; k_toggle_cubic9<2, 1, 0> 189 -> 178; <1, 1, 1> 165 -> 157).
+template <class Look, class Heavy, class PreFlush>
+static __device__ __forceinline__ void toggle_wave_queue(uint32_t* queue, size_t npairs, Look look, Heavy heavy, PreFlush pre_flush) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int qn = 0;  // wave-uniform
+    const size_t stride = (size_t)gridDim.x * PT;
+    const size_t wave_base0 = (size_t)blockIdx.x * PT + (size_t)wv * 64;
+    for (size_t jb = wave_base0; jb < npairs; jb += stride) {  // wave-uniform trip count
+        const size_t j = jb + lane;
+        bool active = false;
+        if (j < npairs) active = look(j);
+        wave_queue_push(queue, qn, lane, active, (uint32_t)(j - wave_base0));
+        if (qn >= 64) {
+            pre_flush();
+            heavy(wave_base0 + (size_t)queue[lane]);
+            wave_queue_pop(queue, qn, lane, 64);
+        }
+    }
+    if (qn > 0) pre_flush();
+    if (lane < qn) heavy(wave_base0 + (size_t)queue[lane]);
+}
+// ONE call site of heavy, so that it is inlined and the caller's accumulators stay in registers: k_toggle_group_cubic, with 15 of
+// them.  The loop goes on, looking at no further pairs, until the queue is empty.
+template <class Look, class Heavy>
+static __device__ __forceinline__ void toggle_wave_queue_one_site(uint32_t* queue, size_t npairs, Look look, Heavy heavy) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int qn = 0;  // wave-uniform
+    const size_t stride = (size_t)gridDim.x * PT;
+    const size_t wave_base0 = (size_t)blockIdx.x * PT + (size_t)wv * 64;
+    for (size_t jb = wave_base0;; jb += stride) {  // wave-uniform trip count
+        const bool more = jb < npairs;
+        if (more) {
+            const size_t j = jb + lane;
+            bool active = false;
+            if (j < npairs) active = look(j);
+            wave_queue_push(queue, qn, lane, active, (uint32_t)(j - wave_base0));
+        }
+        if (qn >= 64 || (!more && qn > 0)) {
+            const int take = qn < 64 ? qn : 64;
+            if (lane < take) heavy(wave_base0 + (size_t)queue[lane]);
+            wave_queue_pop(queue, qn, lane, take);
+        }
+        if (!more && qn == 0) break;
+    }
+}
+
 template <int NC, int NESTED, int FT>
 __global__ void __launch_bounds__(PT) k_toggle_cubic(const fe* __restrict__ pa, const fe* __restrict__ pb, const void* __restrict__ fl, size_t npairs,
                                                   int log_half_n, const fe* __restrict__ E1, int log_E1_half, const fe* __restrict__ E2, size_t E2_len,
                                                   fe* __restrict__ partial) {
     __shared__ fe sh4[4];
     __shared__ uint32_t queue[PT / 64][128];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    size_t limit = NESTED ? ((size_t)E2_len << log_E1_half) : E2_len / 2;
+    const size_t limit = split_eq_limit<NESTED>(E2_len, log_E1_half);
     if (npairs > limit) npairs = limit;
     fe A[3], C[3];
     for (int k = 0; k < 3; k++) A[k] = C[k] = Fr::zero();
-    int qn = 0;  // wave-uniform
-    const size_t stride = (size_t)gridDim.x * PT;
-    const size_t wave_base0 = (size_t)blockIdx.x * PT + (size_t)wv * 64;
     auto heavy = [&](size_t j) {
+        // split_eq_at and the E2 factor, written out: with the helper k_toggle_cubic<1, 0, 1> takes 73 VGPRs for 74
         fe e[3];
         if (NESTED) {
             size_t x2 = j >> log_E1_half, x1 = j & (((size_t)1 << log_E1_half) - 1);
@@ -138,13 +261,8 @@ __global__ void __launch_bounds__(PT) k_toggle_cubic(const fe* __restrict__ pa, 
         } else {
             eq3(fe_load(E2 + 2 * j), fe_load(E2 + 2 * j + 1), e);
         }
-        size_t fj = j;
-        if (log_half_n >= 0) {
-            size_t b = j >> log_half_n, i = j & (((size_t)1 << log_half_n) - 1);
-            fj = ((b >> 1) << log_half_n) + i;
-        }
         fe f0, f1;
-        (void)toggle_flag_pair<FT>(fl, fj, f0, f1);
+        (void)toggle_flag_pair<FT>(fl, toggle_flag_index(j, log_half_n), f0, f1);
         fe p0 = sh_ab_sum<NC>(sh_load<NC>(pa, pb, 2 * j)), p1 = sh_ab_sum<NC>(sh_load<NC>(pa, pb, 2 * j + 1));
         fe f[3], p[3];
         eq3(f0, f1, f);
@@ -155,41 +273,39 @@ __global__ void __launch_bounds__(PT) k_toggle_cubic(const fe* __restrict__ pa, 
             A[k] = Fr::add(A[k], Fr::mul(fe_k, p[k]));
         }
     };
-    for (size_t jb = wave_base0; jb < npairs; jb += stride) {  // wave-uniform trip count
-        const size_t j = jb + lane;
-        bool active = false;
-        if (j < npairs) {
-            size_t fj = j;
-            if (log_half_n >= 0) {
-                size_t b = j >> log_half_n, i = j & (((size_t)1 << log_half_n) - 1);
-                fj = ((b >> 1) << log_half_n) + i;
-            }
-            if (FT == 0) {
-                active = *(const uint16_t*)((const uint8_t*)fl + 2 * fj) != 0;
-            } else {
-                fe f0, f1;
-                active = toggle_flag_pair<FT>(fl, fj, f0, f1);
-            }
-        }
-        const unsigned long long m = __ballot(active);
-        if (active) queue[wv][qn + __popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)(j - wave_base0);
-        qn += __popcll(m);
-        __builtin_amdgcn_wave_barrier();  // the wave's LDS operations execute in program order; this keeps the compiler from moving them
-        if (qn >= 64) {
-            heavy(wave_base0 + (size_t)queue[wv][lane]);
-            const uint32_t keep = lane < qn - 64 ? queue[wv][64 + lane] : 0u;
-            __builtin_amdgcn_wave_barrier();
-            if (lane < qn - 64) queue[wv][lane] = keep;
-            __builtin_amdgcn_wave_barrier();
-            qn -= 64;
-        }
-    }
-    if (lane < qn) heavy(wave_base0 + (size_t)queue[wv][lane]);
-    for (int k = 0; k < 3; k++) {
+    toggle_wave_queue(queue[threadIdx.x >> 6], npairs, [&](size_t j) { return toggle_pair_active<FT>(fl, toggle_flag_index(j, log_half_n)); }, heavy, [] {});
+    for (int k = 0; k < 3; k++) {  // partial_row_sum, written out: with the helper <1, 1, 0> takes 88 VGPRs for 91 and <2, 1, 0> 110 for 112
         fe v = fr_block_sum(A[k], sh4);
         if (threadIdx.x == 0) fe_store(partial + (size_t)k * gridDim.x + blockIdx.x, v);
         v = fr_block_sum(C[k], sh4);
         if (threadIdx.x == 0) fe_store(partial + (size_t)(3 + k) * gridDim.x + blockIdx.x, v);
+    }
+}
+
+// X = 0, 2, 3 of the line through (v0, v1) on the 9 x 29 multiplier, lazily: normalised v0, v1 in, limbs < 2^30.6 out; CS = FR9_C2 for
+// canonical v0, FR9_C3 for a Rep3 sum a + b (< 2 r: its top limb can be one above FR9_C2's)
+static __device__ __forceinline__ void f9_line3(const f9& v0, const f9& v1, const uint32_t (&CS)[9], f9& x0, f9& x2, f9& x3) {
+    const f9 m = f9_norm(f9_sub(v1, CS, v0));
+    x0 = v0;
+    x2 = fr9_add(v1, m);
+    x3 = fr9_add(x2, m);
+}
+// split_eq_at on the 9 x 29 multiplier with the E2 factor multiplied in: normalised weights, which carry lambda when nested (the E2 product) and none when flat
+template <int NESTED>
+static __device__ __forceinline__ void split_eq_weights9(const fe* E1, int log_E1_half, const fe* E2, size_t j, f9& e0, f9& e2, f9& e3) {
+    f9 r0, r2, r3;
+    if (NESTED) {
+        const size_t x2i = j >> log_E1_half, x1 = j & (((size_t)1 << log_E1_half) - 1);
+        f9_line3(f9_from_fe(fe_load(E1 + 2 * x1)), f9_from_fe(fe_load(E1 + 2 * x1 + 1)), FR9_C2, r0, r2, r3);
+        const f9 sc = f9_from_fe(fe_load(E2 + x2i));
+        e0 = fr9_mul(r0, sc);
+        e2 = fr9_mul(r2, sc);
+        e3 = fr9_mul(r3, sc);
+    } else {
+        f9_line3(f9_from_fe(fe_load(E2 + 2 * j)), f9_from_fe(fe_load(E2 + 2 * j + 1)), FR9_C2, r0, r2, r3);
+        e0 = r0;
+        e2 = f9_norm(r2);
+        e3 = f9_norm(r3);
     }
 }
 
@@ -199,55 +315,24 @@ __global__ void __launch_bounds__(PT) k_toggle_cubic9(const fe* __restrict__ pa,
                                                   fe* __restrict__ partial) {
     __shared__ fe sh4[4];
     __shared__ uint32_t queue[PT / 64][128];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    size_t limit = NESTED ? ((size_t)E2_len << log_E1_half) : E2_len / 2;
+    const size_t limit = split_eq_limit<NESTED>(E2_len, log_E1_half);
     if (npairs > limit) npairs = limit;
     // the heavy path on the 9 x 29 multiplier (fr9.hip.hpp): C(X) = eq x flag carries lambda (lambda^2 with the E2 factor), A(X) =
     // C(X) x fingerprint one more; sums are lazy, one product with the matching constant per lane at the end
     f9 A0 = fr9_zero(), A2 = fr9_zero(), A3 = fr9_zero(), C0 = fr9_zero(), C2 = fr9_zero(), C3 = fr9_zero();
-    int qn = 0;  // wave-uniform
-    const size_t stride = (size_t)gridDim.x * PT;
-    const size_t wave_base0 = (size_t)blockIdx.x * PT + (size_t)wv * 64;
-    // X = 0, 2, 3 of the line through (v0, v1), lazily: normalised v0, v1 in, limbs < 2^30.6 out; CS = FR9_C2 for canonical v0,
-    // FR9_C3 for a Rep3 sum a + b (< 2 r: its top limb can be one above FR9_C2's)
-    auto line3 = [](const f9& v0, const f9& v1, const uint32_t(&CS)[9], f9& x0, f9& x2, f9& x3) {
-        const f9 m = f9_norm(f9_sub(v1, CS, v0));
-        x0 = v0;
-        x2 = fr9_add(v1, m);
-        x3 = fr9_add(x2, m);
-    };
     auto heavy = [&](size_t j) {
         f9 e0, e2, e3;
-        if (NESTED) {
-            size_t x2i = j >> log_E1_half, x1 = j & (((size_t)1 << log_E1_half) - 1);
-            f9 r0, r2, r3;
-            line3(f9_from_fe(fe_load(E1 + 2 * x1)), f9_from_fe(fe_load(E1 + 2 * x1 + 1)), FR9_C2, r0, r2, r3);
-            const f9 sc = f9_from_fe(fe_load(E2 + x2i));
-            e0 = fr9_mul(r0, sc);
-            e2 = fr9_mul(r2, sc);
-            e3 = fr9_mul(r3, sc);
-        } else {
-            f9 r0, r2, r3;
-            line3(f9_from_fe(fe_load(E2 + 2 * j)), f9_from_fe(fe_load(E2 + 2 * j + 1)), FR9_C2, r0, r2, r3);
-            e0 = r0;
-            e2 = f9_norm(r2);
-            e3 = f9_norm(r3);
-        }
-        size_t fj = j;
-        if (log_half_n >= 0) {
-            size_t b = j >> log_half_n, i = j & (((size_t)1 << log_half_n) - 1);
-            fj = ((b >> 1) << log_half_n) + i;
-        }
+        split_eq_weights9<NESTED>(E1, log_E1_half, E2, j, e0, e2, e3);
         fe f0, f1;
-        (void)toggle_flag_pair<FT>(fl, fj, f0, f1);
+        (void)toggle_flag_pair<FT>(fl, toggle_flag_index(j, log_half_n), f0, f1);
         f9 g0, g2, g3, p0, p2, p3;
-        line3(f9_from_fe(f0), f9_from_fe(f1), FR9_C2, g0, g2, g3);
+        f9_line3(f9_from_fe(f0), f9_from_fe(f1), FR9_C2, g0, g2, g3);
         {
             const Sh9<NC> q0 = sh9_load_or_zero<NC>(pa, pb, 2 * j, (size_t)-1), q1 = sh9_load_or_zero<NC>(pa, pb, 2 * j + 1, (size_t)-1);
-            // (a + b) of a Rep3 fingerprint: < 2 r, limbs < 2^30 -- normalised for line3
+            // (a + b) of a Rep3 fingerprint: < 2 r, limbs < 2^30 -- normalised for f9_line3
             const f9 s0 = NC == 2 ? f9_norm(fr9_add(q0.c[0], q0.c[NC - 1])) : q0.c[0];
             const f9 s1 = NC == 2 ? f9_norm(fr9_add(q1.c[0], q1.c[NC - 1])) : q1.c[0];
-            line3(s0, s1, NC == 2 ? FR9_C3 : FR9_C2, p0, p2, p3);
+            f9_line3(s0, s1, NC == 2 ? FR9_C3 : FR9_C2, p0, p2, p3);
         }
         const f9 c0 = fr9_mul(g0, e0), c2 = fr9_mul(g2, e2), c3 = fr9_mul(g3, e3);  // flag x eq: normalised outputs
         C0 = f9_norm(fr9_add(C0, c0));
@@ -270,38 +355,7 @@ __global__ void __launch_bounds__(PT) k_toggle_cubic9(const fe* __restrict__ pa,
         }
         nflush++;
     };
-    for (size_t jb = wave_base0; jb < npairs; jb += stride) {  // wave-uniform trip count
-        const size_t j = jb + lane;
-        bool active = false;
-        if (j < npairs) {
-            size_t fj = j;
-            if (log_half_n >= 0) {
-                size_t b = j >> log_half_n, i = j & (((size_t)1 << log_half_n) - 1);
-                fj = ((b >> 1) << log_half_n) + i;
-            }
-            if (FT == 0) {
-                active = *(const uint16_t*)((const uint8_t*)fl + 2 * fj) != 0;
-            } else {
-                fe f0, f1;
-                active = toggle_flag_pair<FT>(fl, fj, f0, f1);
-            }
-        }
-        const unsigned long long m = __ballot(active);
-        if (active) queue[wv][qn + __popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)(j - wave_base0);
-        qn += __popcll(m);
-        __builtin_amdgcn_wave_barrier();  // the wave's LDS operations execute in program order; this keeps the compiler from moving them
-        if (qn >= 64) {
-            fold();
-            heavy(wave_base0 + (size_t)queue[wv][lane]);
-            const uint32_t keep = lane < qn - 64 ? queue[wv][64 + lane] : 0u;
-            __builtin_amdgcn_wave_barrier();
-            if (lane < qn - 64) queue[wv][lane] = keep;
-            __builtin_amdgcn_wave_barrier();
-            qn -= 64;
-        }
-    }
-    if (qn > 0) fold();
-    if (lane < qn) heavy(wave_base0 + (size_t)queue[wv][lane]);
+    toggle_wave_queue(queue[threadIdx.x >> 6], npairs, [&](size_t j) { return toggle_pair_active<FT>(fl, toggle_flag_index(j, log_half_n)); }, heavy, fold);
     {
         // C carries lambda (lambda^2 nested), A one more
         const f9 KC = NESTED ? f9_const(FR9_K2) : f9_const(FR9_K1), KA = NESTED ? f9_const(FR9_K3) : f9_const(FR9_K2);
@@ -309,10 +363,8 @@ __global__ void __launch_bounds__(PT) k_toggle_cubic9(const fe* __restrict__ pa,
         const f9* Cs[3] = {&C0, &C2, &C3};
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            fe v = fr_block_sum(fr9_to_canonical(fr9_mul(*As[k], KA)), sh4);
-            if (threadIdx.x == 0) fe_store(partial + (size_t)k * gridDim.x + blockIdx.x, v);
-            v = fr_block_sum(fr9_to_canonical(fr9_mul(*Cs[k], KC)), sh4);
-            if (threadIdx.x == 0) fe_store(partial + (size_t)(3 + k) * gridDim.x + blockIdx.x, v);
+            partial_row_sum(fr9_to_canonical(fr9_mul(*As[k], KA)), sh4, partial, k);
+            partial_row_sum(fr9_to_canonical(fr9_mul(*Cs[k], KC)), sh4, partial, 3 + k);
         }
     }
 }
@@ -326,7 +378,7 @@ template <int NESTED>
 __global__ void __launch_bounds__(RT) k_toggle_eq_sums(const fe* __restrict__ E1, int log_E1_half, const fe* __restrict__ E2, size_t E2_len, size_t npairs,
                                                     fe* __restrict__ out) {
     __shared__ fe sh16[16];
-    size_t limit = NESTED ? ((size_t)E2_len << log_E1_half) : E2_len / 2;
+    const size_t limit = split_eq_limit<NESTED>(E2_len, log_E1_half);
     if (npairs > limit) npairs = limit;
     fe s[3], sp[3];
     for (int k = 0; k < 3; k++) s[k] = sp[k] = Fr::zero();
@@ -432,11 +484,10 @@ __global__ void __launch_bounds__(PT) k_toggle_group_cubic(ToggleGroupIn in, int
                                                         fe* __restrict__ partial) {
     __shared__ fe sh4[4];
     __shared__ uint32_t queue[PT / 64][128];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int m0 = (int)blockIdx.y * TOGGLE_GROUP_CHUNK;
     const int nm = k - m0 < TOGGLE_GROUP_CHUNK ? k - m0 : TOGGLE_GROUP_CHUNK;  // workgroup-uniform
     const bool first = blockIdx.y == 0;
-    size_t limit = NESTED ? ((size_t)E2_len << log_E1_half) : E2_len / 2;
+    const size_t limit = split_eq_limit<NESTED>(E2_len, log_E1_half);
     if (npairs > limit) npairs = limit;
     fe A[TOGGLE_GROUP_CHUNK][3], C[3];
 #pragma unroll
@@ -445,27 +496,15 @@ __global__ void __launch_bounds__(PT) k_toggle_group_cubic(ToggleGroupIn in, int
         for (int x = 0; x < 3; x++) A[w][x] = Fr::zero();
 #pragma unroll
     for (int x = 0; x < 3; x++) C[x] = Fr::zero();
-    int qn = 0;  // wave-uniform
-    const size_t stride = (size_t)gridDim.x * PT;
-    const size_t wave_base0 = (size_t)blockIdx.x * PT + (size_t)wv * 64;
-    auto flag_index = [&](size_t j) {
-        if (log_half_n < 0) return j;
-        const size_t b = j >> log_half_n, i = j & (((size_t)1 << log_half_n) - 1);
-        return ((b >> 1) << log_half_n) + i;
-    };
     auto heavy = [&](size_t j) __attribute__((always_inline)) {
-        fe e[3];
+        fe e[3], sc;
+        split_eq_at(NESTED, E1, log_E1_half, E2, j, e, sc);
         if (NESTED) {
-            size_t x2 = j >> log_E1_half, x1 = j & (((size_t)1 << log_E1_half) - 1);
-            eq3(fe_load(E1 + 2 * x1), fe_load(E1 + 2 * x1 + 1), e);
-            fe sc = fe_load(E2 + x2);
 #pragma unroll
             for (int x = 0; x < 3; x++) e[x] = Fr::mul(e[x], sc);
-        } else {
-            eq3(fe_load(E2 + 2 * j), fe_load(E2 + 2 * j + 1), e);
         }
         fe f0, f1, f[3];
-        (void)toggle_flag_pair<FT>(fl, flag_index(j), f0, f1);
+        (void)toggle_flag_pair<FT>(fl, toggle_flag_index(j, log_half_n), f0, f1);
         eq3(f0, f1, f);
 #pragma unroll
         for (int x = 0; x < 3; x++) e[x] = Fr::mul(f[x], e[x]);  // flag x eq, once for all members
@@ -484,69 +523,34 @@ __global__ void __launch_bounds__(PT) k_toggle_group_cubic(ToggleGroupIn in, int
             }
         }
     };
-    // ONE call site of the heavy path, so that it is inlined and the accumulators stay in registers: the loop goes on, looking at no
-    // further pairs, until the wave's queue is empty
-    for (size_t jb = wave_base0;; jb += stride) {  // wave-uniform trip count
-        const bool more = jb < npairs;
-        if (more) {
-            const size_t j = jb + lane;
-            bool active = false;
-            if (j < npairs) {
-                const size_t fj = flag_index(j);
-                if (FT == 0) {
-                    active = *(const uint16_t*)((const uint8_t*)fl + 2 * fj) != 0;
-                } else {
-                    fe f0, f1;
-                    active = toggle_flag_pair<FT>(fl, fj, f0, f1);
-                }
-            }
-            const unsigned long long mask = __ballot(active);
-            if (active) queue[wv][qn + __popcll(mask & ((1ull << lane) - 1ull))] = (uint32_t)(j - wave_base0);
-            qn += __popcll(mask);
-            __builtin_amdgcn_wave_barrier();  // the wave's LDS operations execute in program order; this keeps the compiler from moving them
-        }
-        if (qn >= 64 || (!more && qn > 0)) {
-            const int take = qn < 64 ? qn : 64;
-            if (lane < take) heavy(wave_base0 + (size_t)queue[wv][lane]);
-            const uint32_t keep = lane < qn - take ? queue[wv][take + lane] : 0u;
-            __builtin_amdgcn_wave_barrier();
-            if (lane < qn - take) queue[wv][lane] = keep;
-            __builtin_amdgcn_wave_barrier();
-            qn -= take;
-        }
-        if (!more && qn == 0) break;
-    }
+    toggle_wave_queue_one_site(queue[threadIdx.x >> 6], npairs, [&](size_t j) { return toggle_pair_active<FT>(fl, toggle_flag_index(j, log_half_n)); }, heavy);
 #pragma unroll
     for (int w = 0; w < TOGGLE_GROUP_CHUNK; w++) {
         if (w < nm) {
 #pragma unroll
-            for (int x = 0; x < 3; x++) {
-                fe v = fr_block_sum(A[w][x], sh4);
-                if (threadIdx.x == 0) fe_store(partial + (size_t)(3 * (m0 + w) + x) * gridDim.x + blockIdx.x, v);
-            }
+            for (int x = 0; x < 3; x++) partial_row_sum(A[w][x], sh4, partial, 3 * (m0 + w) + x);
         }
     }
     if (first) {
 #pragma unroll
-        for (int x = 0; x < 3; x++) {
-            fe v = fr_block_sum(C[x], sh4);
-            if (threadIdx.x == 0) fe_store(partial + (size_t)(3 * k + x) * gridDim.x + blockIdx.x, v);
-        }
+        for (int x = 0; x < 3; x++) partial_row_sum(C[x], sh4, partial, 3 * k + x);
     }
 }
 
-// the final claims of a fully bound group into the pinned result slot: res[0] = the flag, res[1 + m] = member m's fingerprint
+// the final claims of a fully bound layer or group into the pinned result slot: res[0] = the flag, res[1 + m] = plane m's fingerprint
 __global__ void __launch_bounds__(64) k_toggle_group_claims(ToggleGroupIn in, const fe* __restrict__ fl, int k_final, fe* __restrict__ res) {
     if (threadIdx.x != 0) return;  // one lane: the table is indexed by a uniform value
     fe_store(res, fe_load(fl));
     for (int m = 0; m < k_final; m++) fe_store(res + 1 + m, fe_load(in.p[m]));
 }
-
-static inline int log2_sz(size_t n) {
-    int l = 0;
-    while (((size_t)1 << l) < n) l++;
-    return l;
+// ... and to the host: h[0 .. k_final]
+static void toggle_claims_fetch(cozk_ctx* ctx, const ToggleGroupIn& in, const fe* fl, int k_final, fe* h) {
+    fe* res = result_slot(ctx, (size_t)k_final + 1);
+    k_toggle_group_claims<<<1, 64, 0, ctx->stream>>>(in, fl, k_final, res);
+    HIP_TRY(hipGetLastError());
+    fetch_fe(ctx, res, (size_t)k_final + 1, h);
 }
+
 static void toggle_reserve(cozk_toggle* t, int w, size_t n_fp, size_t n_fl) {
     if (t->fp_cap[w] < n_fp) {
         for (int c = 0; c < 2; c++) {
@@ -564,6 +568,67 @@ static void toggle_reserve(cozk_toggle* t, int w, size_t n_fp, size_t n_fl) {
     }
 }
 
+// the flag columns of a create, checked and packed into one array of n_pairs x n0 bytes from ctx's pool (*fl0, set as soon as it
+// exists so that the caller's clean-up finds it); `who` prefixes the messages
+static void toggle_pack_flags(cozk_ctx* ctx, const cozk_vec* const* flags, size_t n_pairs, size_t n0, const char* who, uint8_t** fl0) {
+    std::vector<const uint8_t*> cols(n_pairs);
+    for (size_t q = 0; q < n_pairs; q++) {
+        if (!(flags[q] && flags[q]->ctx && flags[q]->kind == COZK_SCALAR_U8 && flags[q]->n == n0))
+            throw CozkError(COZK_ERR_INVALID_ARG, std::string(who) + ": every flag column is a U8 vector of N entries");
+        cols[q] = (const uint8_t*)flags[q]->d;
+    }
+    *fl0 = (uint8_t*)ctx_dev_alloc(ctx, n_pairs * n0 + 16);
+    ctx->scratch2.reserve(n_pairs * sizeof(void*));
+    HIP_TRY(hipMemcpyAsync(ctx->scratch2.p, cols.data(), n_pairs * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // `cols` lives on the stack of this call
+    k_toggle_flags_pack<<<grid_for(n_pairs * n0), PT, 0, ctx->stream>>>((const uint8_t* const*)ctx->scratch2.p, n0, n_pairs * n0, *fl0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // scratch2 is shared with other calls
+}
+
+// the view of a split-eq polynomial that the round kernels take: nested = E1 is not yet a single value (lg1 = log2 of its pairs)
+struct EqView {
+    bool nested;
+    const fe* E1;
+    const fe* E2;
+    int lg1;
+    size_t E2_len;
+};
+static EqView eq_view(const cozk_spliteq* e) {
+    const bool nested = e->E1_len != 1;
+    return EqView{nested, e->E1[e->c1], e->E2[e->c2], nested ? log2_sz(e->E1_len / 2) : 0, e->E2_len};
+}
+// S_all(X) over the first n items into dst[0 .. 2]: the sums as if every node were one (the reference's eq_eval_sums /
+// evals_assuming_all_ones); in a round it goes before the finishing kernel, which publishes the round
+static void eq_sums_launch(cozk_ctx* ctx, const EqView& v, size_t n, fe* dst) {
+    auto* const kernel = v.nested ? k_toggle_eq_sums<1> : k_toggle_eq_sums<0>;
+    kernel<<<1, RT, 0, ctx->stream>>>(v.E1, v.lg1, v.E2, v.E2_len, n, dst);
+    HIP_TRY(hipGetLastError());
+}
+
+// Rep3Bindable::bind (sparse_grand_product.rs:153-290) incl. the switch to the coalesced vectors when layer_len reaches 2 (a second
+// launch; the group fuses it).  The caller has checked !t->s.bound().
+static void toggle_bind_launch(cozk_toggle* t, const fe& rr) {
+    cozk_ctx* const ctx = t->ctx;
+    const ToggleShape::BindSizes b = t->s.bind_sizes();
+    const int dst = t->s.dst();
+    const bool rep3 = t->mode == COZK_MODE_REP3, u8 = t->s.cur < 0;  // the first bind reads the packed 0/1 bytes
+    toggle_reserve(t, dst, b.n_fp, b.n_fl);
+    auto* const kernel = rep3 ? (u8 ? k_toggle_bind<2, 0> : k_toggle_bind<2, 1>) : (u8 ? k_toggle_bind<1, 0> : k_toggle_bind<1, 1>);
+    kernel<<<grid_for(b.n_fp), PT, 0, ctx->stream>>>(tg_fp(t, 0), tg_fp(t, 1), t->fp[dst][0], t->fp[dst][1], b.n_fp, tg_fl(t), t->fl[dst], b.n_fl, rr);
+    HIP_TRY(hipGetLastError());
+    t->s.advance();
+    if (b.coalesces) {  // layer_len == 2: coalesce, to the other side
+        const size_t L = t->s.L;
+        const int d2 = 1 - t->s.cur;
+        toggle_reserve(t, d2, L, L);
+        auto* const coalesce = rep3 ? k_toggle_coalesce<2> : k_toggle_coalesce<1>;
+        coalesce<<<grid_for(L), PT, 0, ctx->stream>>>(tg_fp(t, 0), tg_fp(t, 1), t->fl[t->s.cur], t->s.batch, L, t->fp[d2][0], t->fp[d2][1], t->fl[d2]);
+        HIP_TRY(hipGetLastError());
+        t->s.cur = d2;
+    }
+}
+
 extern "C" {
 
 int cozk_toggle_create(cozk_ctx* ctx, int mode, const cozk_vec* const* flags, size_t n_pairs, cozk_vec* fp_a, cozk_vec* fp_b, int take_ownership,
@@ -576,47 +641,26 @@ int cozk_toggle_create(cozk_ctx* ctx, int mode, const cozk_vec* const* flags, si
         COZK_REQUIRE(fp_a->n % batch == 0, "toggle_create: fingerprints.len() must be 2 * n_pairs * N");
         const size_t n0 = fp_a->n / batch;
         COZK_REQUIRE(n0 >= 2 && (n0 & (n0 - 1)) == 0, "toggle_create: fingerprints per circuit must be a power of two >= 2");
-        std::vector<const uint8_t*> cols(n_pairs);
-        for (size_t q = 0; q < n_pairs; q++) {
-            COZK_REQUIRE(flags[q] && flags[q]->kind == COZK_SCALAR_U8 && flags[q]->n == n0, "toggle_create: every flag column is a U8 vector of N entries");
-            cols[q] = (const uint8_t*)flags[q]->d;
-        }
-        cozk_toggle* t = new cozk_toggle();
+        cozk_toggle* t = new cozk_toggle();  // value-initialised: no buffers yet
+        struct Guard {
+            cozk_toggle* t;
+            ~Guard() { if (t) cozk_toggle_free(t); }
+        } guard{t};
         t->ctx = ctx;
         t->mode = mode;
-        t->batch = batch;
-        t->n0 = t->n_cur = n0;
-        t->coalesced = false;
-        t->L = 1;
-        while (t->L < batch) t->L <<= 1;
-        t->cur = -1;
-        for (int w = 0; w < 2; w++) {
-            t->fp[w][0] = t->fp[w][1] = nullptr;
-            t->fl[w] = nullptr;
-            t->fp_cap[w] = t->fl_cap[w] = 0;
-        }
-        t->fp0[0] = t->fp0[1] = nullptr;
+        t->s.init(batch, n0);
+        toggle_pack_flags(ctx, flags, n_pairs, n0, "toggle_create", &t->fl0);
         cozk_vec* src[2] = {fp_a, mode == COZK_MODE_REP3 ? fp_b : nullptr};
         for (int c = 0; c < 2; c++) {
             if (!src[c]) continue;
             if (take_ownership && src[c]->owned) {
-                t->fp0[c] = (fe*)src[c]->d;
-                src[c]->d = nullptr;
-                src[c]->owned = false;
-                src[c]->n = 0;
-                src[c]->bytes = 0;
+                t->fp0[c] = (fe*)vec_adopt(src[c]);
             } else {
                 t->fp0[c] = dev_alloc_fe(batch * n0);
                 HIP_TRY(hipMemcpyAsync(t->fp0[c], src[c]->d, batch * n0 * sizeof(fe), hipMemcpyDeviceToDevice, ctx->stream));
             }
         }
-        t->fl0 = (uint8_t*)ctx_dev_alloc(ctx, n_pairs * n0 + 16);
-        ctx->scratch2.reserve(n_pairs * sizeof(void*));
-        HIP_TRY(hipMemcpyAsync(ctx->scratch2.p, cols.data(), n_pairs * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));  // `cols` lives on the stack of this call
-        k_toggle_flags_pack<<<grid_for(n_pairs * n0), PT, 0, ctx->stream>>>((const uint8_t* const*)ctx->scratch2.p, n0, n_pairs * n0, t->fl0);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(ctx->stream));  // scratch2 is shared with other calls
+        guard.t = nullptr;
         *out = t;
     });
 }
@@ -635,14 +679,14 @@ int cozk_toggle_free(cozk_toggle* t) {
     return COZK_OK;
 }
 
-size_t cozk_toggle_batch(const cozk_toggle* t) { return t ? t->batch : 0; }
-size_t cozk_toggle_len(const cozk_toggle* t) { return t ? t->n0 : 0; }
+size_t cozk_toggle_batch(const cozk_toggle* t) { return t ? t->s.batch : 0; }
+size_t cozk_toggle_len(const cozk_toggle* t) { return t ? t->s.n0 : 0; }
 
 // layer_output (sparse_grand_product.rs:76-97) as the dense interleaved layer the sparse layers are kept as
 int cozk_toggle_layer_output(cozk_ctx* ctx, const cozk_toggle* t, int party_id, cozk_layer** out) {
     return cozk_guard(ctx, [&] {
-        COZK_REQUIRE(ctx && t && out && t->cur < 0 && party_id >= 0 && party_id < 3, "toggle_layer_output: needs an unbound toggle layer");
-        const size_t total = t->batch * t->n0;
+        COZK_REQUIRE(ctx && t && out && t->s.cur < 0 && party_id >= 0 && party_id < 3, "toggle_layer_output: needs an unbound toggle layer");
+        const size_t total = t->s.batch * t->s.n0;
         cozk_layer* l = new cozk_layer();
         l->ctx = ctx;
         l->mode = t->mode;
@@ -658,60 +702,18 @@ int cozk_toggle_layer_output(cozk_ctx* ctx, const cozk_toggle* t, int party_id, 
         // promote_to_trivial_share(party_id, one): P0 (1, 0), P1 (0, 1), P2 (0, 0); the plain prover's one is 1
         fe one_a = (t->mode == COZK_MODE_PLAIN || party_id == 0) ? Fr::one() : Fr::zero();
         fe one_b = (t->mode == COZK_MODE_REP3 && party_id == 1) ? Fr::one() : Fr::zero();
-        if (t->mode == COZK_MODE_REP3)
-            k_toggle_output<2><<<grid_for(total), PT, 0, ctx->stream>>>(t->fp0[0], t->fp0[1], t->fl0, log2_sz(t->n0), total, one_a, one_b, l->buf[0][0], l->buf[0][1]);
-        else
-            k_toggle_output<1><<<grid_for(total), PT, 0, ctx->stream>>>(t->fp0[0], nullptr, t->fl0, log2_sz(t->n0), total, one_a, one_b, l->buf[0][0], nullptr);
+        auto* const kernel = t->mode == COZK_MODE_REP3 ? k_toggle_output<2> : k_toggle_output<1>;
+        kernel<<<grid_for(total), PT, 0, ctx->stream>>>(t->fp0[0], t->fp0[1], t->fl0, log2_sz(t->s.n0), total, one_a, one_b, l->buf[0][0], l->buf[0][1]);
         HIP_TRY(hipGetLastError());
         *out = l;
     });
 }
 
-// Rep3Bindable::bind (sparse_grand_product.rs:153-290) incl. the switch to the coalesced vectors when layer_len reaches 2
 int cozk_toggle_bind(cozk_ctx* ctx, cozk_toggle* t, const uint64_t r[4]) {
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(ctx && t && r, "toggle_bind: bad argument");
-        fe rr = fe_from_u64x4(r);
-        const int dst = t->cur < 0 ? 0 : 1 - t->cur;
-        if (t->coalesced) {
-            COZK_REQUIRE(t->L >= 2, "toggle_bind: fully bound");
-            const size_t n = t->L / 2;
-            toggle_reserve(t, dst, n, n);
-            if (t->mode == COZK_MODE_REP3)
-                k_toggle_bind<2, 1><<<grid_for(n), PT, 0, ctx->stream>>>(tg_fp(t, 0), tg_fp(t, 1), t->fp[dst][0], t->fp[dst][1], n, tg_fl(t), t->fl[dst], n, rr);
-            else
-                k_toggle_bind<1, 1><<<grid_for(n), PT, 0, ctx->stream>>>(tg_fp(t, 0), nullptr, t->fp[dst][0], nullptr, n, tg_fl(t), t->fl[dst], n, rr);
-            HIP_TRY(hipGetLastError());
-            t->cur = dst;
-            t->L = n;
-            return;
-        }
-        COZK_REQUIRE(t->n_cur >= 2, "toggle_bind: nothing left to bind");
-        const size_t n_fp = t->batch * t->n_cur / 2, n_fl = (t->batch / 2) * t->n_cur / 2;
-        toggle_reserve(t, dst, n_fp, n_fl);
-        const bool u8 = t->cur < 0;  // the first bind reads the packed 0/1 bytes
-        const void* fin = u8 ? (const void*)t->fl0 : (const void*)tg_fl(t);
-        if (t->mode == COZK_MODE_REP3) {
-            if (u8) k_toggle_bind<2, 0><<<grid_for(n_fp), PT, 0, ctx->stream>>>(tg_fp(t, 0), tg_fp(t, 1), t->fp[dst][0], t->fp[dst][1], n_fp, fin, t->fl[dst], n_fl, rr);
-            else k_toggle_bind<2, 1><<<grid_for(n_fp), PT, 0, ctx->stream>>>(tg_fp(t, 0), tg_fp(t, 1), t->fp[dst][0], t->fp[dst][1], n_fp, fin, t->fl[dst], n_fl, rr);
-        } else {
-            if (u8) k_toggle_bind<1, 0><<<grid_for(n_fp), PT, 0, ctx->stream>>>(tg_fp(t, 0), nullptr, t->fp[dst][0], nullptr, n_fp, fin, t->fl[dst], n_fl, rr);
-            else k_toggle_bind<1, 1><<<grid_for(n_fp), PT, 0, ctx->stream>>>(tg_fp(t, 0), nullptr, t->fp[dst][0], nullptr, n_fp, fin, t->fl[dst], n_fl, rr);
-        }
-        HIP_TRY(hipGetLastError());
-        t->cur = dst;
-        t->n_cur /= 2;
-        if (t->n_cur == 1) {  // layer_len == 2: coalesce
-            const int d2 = 1 - t->cur;
-            toggle_reserve(t, d2, t->L, t->L);
-            if (t->mode == COZK_MODE_REP3)
-                k_toggle_coalesce<2><<<grid_for(t->L), PT, 0, ctx->stream>>>(tg_fp(t, 0), tg_fp(t, 1), tg_fl(t), t->batch, t->L, t->fp[d2][0], t->fp[d2][1], t->fl[d2]);
-            else
-                k_toggle_coalesce<1><<<grid_for(t->L), PT, 0, ctx->stream>>>(tg_fp(t, 0), nullptr, tg_fl(t), t->batch, t->L, t->fp[d2][0], nullptr, t->fl[d2]);
-            HIP_TRY(hipGetLastError());
-            t->cur = d2;
-            t->coalesced = true;
-        }
+        COZK_REQUIRE(!t->s.bound(), "toggle_bind: fully bound");
+        toggle_bind_launch(t, fe_from_u64x4(r));
     });
 }
 
@@ -733,33 +735,27 @@ static ToggleCubicKernel toggle_cubic_kernel(int mode, bool nested, bool u8, siz
 }
 
 // one round of prove_sumcheck over the toggle layer: bind layer + split-eq tables with the previous challenge (NULL in
-// the first round), then the three round sums g(0), g(2), g(3) of compute_cubic as this party's additive shares
+// the first round), then the three round sums g(0), g(2), g(3) of compute_cubic as this party's additive shares.  Every check comes
+// before the first bind: a refused call leaves the layer and the eq as they were.
 int cozk_toggle_round(cozk_ctx* ctx, cozk_toggle* t, cozk_spliteq* e, const uint64_t* r, int party_id, uint64_t out_evals[12]) {
     if (!ctx || !t || !e || !out_evals || party_id < 0 || party_id > 2) return COZK_ERR_INVALID_ARG;
-    if (r) {
-        int rc = cozk_toggle_bind(ctx, t, r);
-        if (rc != COZK_OK) return rc;
-        rc = cozk_spliteq_bind(ctx, e, r);
-        if (rc != COZK_OK) return rc;
-    }
     return cozk_guard(ctx, [&] {
-        const size_t npairs = t->coalesced ? t->L / 2 : t->batch * t->n_cur / 2;
-        const int log_half_n = t->coalesced ? -1 : log2_sz(t->n_cur / 2);
-        COZK_REQUIRE(npairs >= 1, "toggle_round: fully bound");
+        COZK_REQUIRE(e->ctx == ctx, "toggle_round: the eq polynomial belongs to another context");
+        COZK_REQUIRE(!t->s.bound(), "toggle_round: fully bound");
+        if (r) {
+            COZK_REQUIRE(!spliteq_bound(e), "toggle_round: eq polynomial already fully bound");
+            COZK_REQUIRE(!t->s.last_bind(), "toggle_round: the bind leaves the layer fully bound, with no round to run (cozk_toggle_bind)");
+            const fe rr = fe_from_u64x4(r);
+            toggle_bind_launch(t, rr);
+            spliteq_bind_launch(ctx, e, rr);
+        }
+        const size_t npairs = t->s.npairs();
         const unsigned gx = sum_grid(grid_capped(npairs, ROUND_GRID_MAX));
         const SumLaunch sl = sum_launch(ctx, 6, gx, 9);
-        const bool nested = e->E1_len != 1;
-        const fe* E1 = e->E1[e->c1];
-        const fe* E2 = e->E2[e->c2];
-        const int lg1 = nested ? log2_sz(e->E1_len / 2) : 0;
-        const bool u8 = t->cur < 0;  // first round: the packed 0/1 bytes
-        const void* fl = u8 ? (const void*)t->fl0 : (const void*)tg_fl(t);
-        const ToggleCubicKernel kernel = toggle_cubic_kernel(t->mode, nested, u8, npairs);
-        kernel<<<gx, PT, 0, ctx->stream>>>(tg_fp(t, 0), t->mode == COZK_MODE_REP3 ? tg_fp(t, 1) : nullptr, fl, npairs, log_half_n, E1, lg1, E2, e->E2_len, sl.partial);
-        // S_all(X): the sums as if every node were one (the reference's eq_eval_sums / evals_assuming_all_ones); before the finishing
-        // kernel, which publishes the round
-        if (nested) k_toggle_eq_sums<1><<<1, RT, 0, ctx->stream>>>(E1, lg1, E2, e->E2_len, npairs, sl.res + 6);
-        else k_toggle_eq_sums<0><<<1, RT, 0, ctx->stream>>>(E1, 0, E2, e->E2_len, npairs, sl.res + 6);
+        const EqView v = eq_view(e);
+        const ToggleCubicKernel kernel = toggle_cubic_kernel(t->mode, v.nested, t->s.cur < 0, npairs);
+        kernel<<<gx, PT, 0, ctx->stream>>>(tg_fp(t, 0), tg_fp(t, 1), tg_fl(t), npairs, t->s.log_half_n(), v.E1, v.lg1, v.E2, v.E2_len, sl.partial);
+        eq_sums_launch(ctx, v, npairs, sl.res + 6);
         fe s[9];
         finish_sums(ctx, sl, 6, gx, Fr::one(), 0, s);
         const bool pub = t->mode == COZK_MODE_PLAIN || party_id == 0;  // additive::add_public: party 0 only
@@ -773,20 +769,16 @@ int cozk_toggle_round(cozk_ctx* ctx, cozk_toggle* t, cozk_spliteq* e, const uint
 // final_claims (sparse_grand_product.rs:825-835): the bound flag (a public value) and the bound fingerprint share
 int cozk_toggle_final_claims(cozk_ctx* ctx, const cozk_toggle* t, uint64_t flag[4], uint64_t fp_a[4], uint64_t fp_b[4]) {
     return cozk_guard(ctx, [&] {
-        COZK_REQUIRE(ctx && t && flag && fp_a && t->coalesced && t->L == 1, "toggle_final_claims: the layer is not fully bound");
+        COZK_REQUIRE(ctx && t && flag && fp_a && t->s.bound(), "toggle_final_claims: the layer is not fully bound");
+        const int nc = t->mode == COZK_MODE_REP3 ? 2 : 1;
+        ToggleGroupIn in;
+        memset(&in, 0, sizeof in);
+        for (int c = 0; c < nc; c++) in.p[c] = tg_fp(t, c);
         fe h[3];
-        fe* res = result_slot(ctx, 3);
-        (void)res;
-        ctx->scratch.reserve(3 * sizeof(fe));
-        fe* d = ctx->scratch.as<fe>();
-        HIP_TRY(hipMemcpyAsync(d, tg_fl(t), sizeof(fe), hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(d + 1, tg_fp(t, 0), sizeof(fe), hipMemcpyDeviceToDevice, ctx->stream));
-        if (t->mode == COZK_MODE_REP3) HIP_TRY(hipMemcpyAsync(d + 2, tg_fp(t, 1), sizeof(fe), hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(h, d, 3 * sizeof(fe), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        toggle_claims_fetch(ctx, in, t->fl[t->s.cur], nc, h);
         fe_to_u64x4(h[0], flag);
         fe_to_u64x4(h[1], fp_a);
-        if (fp_b) fe_to_u64x4(t->mode == COZK_MODE_REP3 ? h[2] : Fr::zero(), fp_b);
+        if (fp_b) fe_to_u64x4(nc == 2 ? h[2] : Fr::zero(), fp_b);
     });
 }
 
@@ -794,15 +786,16 @@ int cozk_toggle_final_claims(cozk_ctx* ctx, const cozk_toggle* t, uint64_t flag[
 int cozk_toggle_download(cozk_ctx* ctx, const cozk_toggle* t, uint64_t* flags, uint64_t* fp_a, uint64_t* fp_b, size_t* n_flags, size_t* n_fp) {
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(ctx && t, "toggle_download: bad argument");
-        size_t nfp = t->coalesced ? t->L : t->batch * t->n_cur, nfl = t->coalesced ? t->L : (t->batch / 2) * t->n_cur;
+        const ToggleShape& sh = t->s;
+        size_t nfp = sh.coalesced ? sh.L : sh.batch * sh.n_cur, nfl = sh.coalesced ? sh.L : (sh.batch / 2) * sh.n_cur;
         if (n_flags) *n_flags = nfl;
         if (n_fp) *n_fp = nfp;
         std::vector<uint8_t> raw;
-        if (flags && t->cur < 0) {  // unbound: the packed bytes, expanded to field elements here
+        if (flags && sh.cur < 0) {  // unbound: the packed bytes, expanded to field elements here
             raw.resize(nfl);
             HIP_TRY(hipMemcpyAsync(raw.data(), t->fl0, nfl, hipMemcpyDeviceToHost, ctx->stream));
         } else if (flags) {
-            HIP_TRY(hipMemcpyAsync(flags, tg_fl(t), nfl * sizeof(fe), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(flags, t->fl[sh.cur], nfl * sizeof(fe), hipMemcpyDeviceToHost, ctx->stream));
         }
         if (fp_a) HIP_TRY(hipMemcpyAsync(fp_a, tg_fp(t, 0), nfp * sizeof(fe), hipMemcpyDeviceToHost, ctx->stream));
         if (fp_b && t->mode == COZK_MODE_REP3) HIP_TRY(hipMemcpyAsync(fp_b, tg_fp(t, 1), nfp * sizeof(fe), hipMemcpyDeviceToHost, ctx->stream));
@@ -817,54 +810,36 @@ int cozk_toggle_download(cozk_ctx* ctx, const cozk_toggle* t, uint64_t* flags, u
 struct cozk_toggle_group {
     cozk_ctx* driver;
     int k;
-    size_t batch, n0, n_cur, L;
-    bool coalesced;
+    ToggleShape s;
     const fe* fp0[COZK_LAYER_GROUP_MAX];  // unbound fingerprints: adopted (owner != null) or the caller's, which outlive the group
     cozk_ctx* owner[COZK_LAYER_GROUP_MAX];
     uint8_t* fl0;                         // packed 0/1 flags (owned)
     fe* fp[2];                            // ping-pong bound planes: member m at fp[w] + m * fp_cap[w]
     fe* fl[2];                            // ping-pong bound flags
     size_t fp_cap[2], fl_cap[2];
-    int cur;                              // -1: unbound
 };
 
-static bool toggle_group_bound(const cozk_toggle_group* g) { return g->coalesced && g->L == 1; }
 static ToggleGroupIn toggle_group_in(const cozk_toggle_group* g) {
     ToggleGroupIn a;
     memset(&a, 0, sizeof a);
-    for (int m = 0; m < g->k; m++) a.p[m] = g->cur < 0 ? g->fp0[m] : g->fp[g->cur] + (size_t)m * g->fp_cap[g->cur];
+    for (int m = 0; m < g->k; m++) a.p[m] = g->s.cur < 0 ? g->fp0[m] : g->fp[g->s.cur] + (size_t)m * g->fp_cap[g->s.cur];
     return a;
 }
+static const void* toggle_group_fl(const cozk_toggle_group* g) { return g->s.cur < 0 ? (const void*)g->fl0 : (const void*)g->fl[g->s.cur]; }
 
-// one bind of the planes and the flags: ONE launch, which at layer_len == 2 writes the coalesced vectors
+// one bind of the planes and the flags: ONE launch, which at layer_len == 2 writes the coalesced vectors (L entries each)
 static void toggle_group_bind_launch(cozk_toggle_group* g, const fe& rr) {
     cozk_ctx* const ctx = g->driver;
-    const int dst = g->cur < 0 ? 0 : 1 - g->cur;
-    const ToggleGroupIn in = toggle_group_in(g);
-    const bool u8 = g->cur < 0;  // the first bind reads the packed 0/1 bytes
-    const void* fin = u8 ? (const void*)g->fl0 : (const void*)g->fl[g->cur];
-    size_t n_fp, n_fl;
-    const bool to_coalesced = !g->coalesced && g->n_cur == 2;
-    if (g->coalesced) n_fp = n_fl = g->L / 2;
-    else if (to_coalesced) n_fp = n_fl = g->L;
-    else n_fp = g->batch * g->n_cur / 2, n_fl = (g->batch / 2) * g->n_cur / 2;
-    COZK_REQUIRE(n_fp <= g->fp_cap[dst] && n_fl <= g->fl_cap[dst], "toggle_group: bound planes larger than their storage");
-    const dim3 grid(grid_for(n_fp), (unsigned)g->k);
-    if (to_coalesced) {
-        if (u8) k_toggle_group_bind<0, 1><<<grid, PT, 0, ctx->stream>>>(in, g->fp[dst], g->fp_cap[dst], n_fp, fin, g->fl[dst], n_fl, g->batch, rr);
-        else k_toggle_group_bind<1, 1><<<grid, PT, 0, ctx->stream>>>(in, g->fp[dst], g->fp_cap[dst], n_fp, fin, g->fl[dst], n_fl, g->batch, rr);
-    } else {
-        if (u8) k_toggle_group_bind<0, 0><<<grid, PT, 0, ctx->stream>>>(in, g->fp[dst], g->fp_cap[dst], n_fp, fin, g->fl[dst], n_fl, g->batch, rr);
-        else k_toggle_group_bind<1, 0><<<grid, PT, 0, ctx->stream>>>(in, g->fp[dst], g->fp_cap[dst], n_fp, fin, g->fl[dst], n_fl, g->batch, rr);
-    }
+    ToggleShape::BindSizes b = g->s.bind_sizes();
+    if (b.coalesces) b.n_fp = b.n_fl = g->s.L;
+    const int dst = g->s.dst();
+    const bool u8 = g->s.cur < 0;  // the first bind reads the packed 0/1 bytes
+    COZK_REQUIRE(b.n_fp <= g->fp_cap[dst] && b.n_fl <= g->fl_cap[dst], "toggle_group: bound planes larger than their storage");
+    const dim3 grid(grid_for(b.n_fp), (unsigned)g->k);
+    auto* const kernel = b.coalesces ? (u8 ? k_toggle_group_bind<0, 1> : k_toggle_group_bind<1, 1>) : (u8 ? k_toggle_group_bind<0, 0> : k_toggle_group_bind<1, 0>);
+    kernel<<<grid, PT, 0, ctx->stream>>>(toggle_group_in(g), g->fp[dst], g->fp_cap[dst], b.n_fp, toggle_group_fl(g), g->fl[dst], b.n_fl, g->s.batch, rr);
     HIP_TRY(hipGetLastError());
-    g->cur = dst;
-    if (g->coalesced) {
-        g->L /= 2;
-    } else {
-        g->n_cur /= 2;
-        if (to_coalesced) g->coalesced = true;
-    }
+    g->s.advance();
 }
 
 extern "C" {
@@ -902,13 +877,6 @@ int cozk_toggle_group_create(cozk_ctx* driver, const cozk_vec* const* flags, siz
         COZK_REQUIRE(total % batch == 0, "toggle_group_create: fingerprints.len() must be 2 * n_pairs * N");
         const size_t n0 = total / batch;
         COZK_REQUIRE(n0 >= 2 && (n0 & (n0 - 1)) == 0, "toggle_group_create: fingerprints per circuit must be a power of two >= 2");
-        std::vector<const uint8_t*> cols(n_pairs);
-        for (size_t q = 0; q < n_pairs; q++) {
-            COZK_REQUIRE(flags[q] && flags[q]->ctx && flags[q]->kind == COZK_SCALAR_U8 && flags[q]->n == n0,
-                         "toggle_group_create: every flag column is a U8 vector of N entries");
-            COZK_REQUIRE(flags[q]->ctx->device == driver->device, "toggle_group_create: every flag column must live on the driver's device");
-            cols[q] = (const uint8_t*)flags[q]->d;
-        }
         // whatever the inputs' own streams still do to them precedes the driver's launches
         std::vector<cozk_ctx*> drained{driver};
         auto drain = [&](cozk_ctx* c) {
@@ -918,44 +886,31 @@ int cozk_toggle_group_create(cozk_ctx* driver, const cozk_vec* const* flags, siz
             drained.push_back(c);
         };
         for (int m = 0; m < k; m++) drain(fingerprints[m]->ctx);
-        for (size_t q = 0; q < n_pairs; q++) drain(flags[q]->ctx);
-        g = new cozk_toggle_group();
+        for (size_t q = 0; q < n_pairs; q++) {  // a column that is missing or of another shape is toggle_pack_flags' to refuse
+            if (!flags[q] || !flags[q]->ctx) continue;
+            COZK_REQUIRE(flags[q]->ctx->device == driver->device, "toggle_group_create: every flag column must live on the driver's device");
+            drain(flags[q]->ctx);
+        }
+        g = new cozk_toggle_group();  // value-initialised: k = 0, no buffers yet
         g->driver = driver;
-        g->k = 0;
-        g->batch = batch;
-        g->n0 = g->n_cur = n0;
-        g->coalesced = false;
-        g->L = 1;
-        while (g->L < batch) g->L <<= 1;
-        g->cur = -1;
-        g->fl0 = nullptr;
-        for (int w = 0; w < 2; w++) g->fp[w] = g->fl[w] = nullptr, g->fp_cap[w] = g->fl_cap[w] = 0;
+        g->s.init(batch, n0);
         // both ping-pong sides, once, from the driver's pool: the first bind writes side 0, the second side 1, and every later
         // bind no more than the one two before it; the coalesced vectors have L entries.  Later rounds allocate nothing.
         for (int w = 0; w < 2; w++) {
-            const size_t fpn = batch * n0 >> (w + 1), fln = n_pairs * n0 >> (w + 1);
-            g->fp_cap[w] = fpn > g->L ? fpn : g->L;
-            g->fl_cap[w] = fln > g->L ? fln : g->L;
+            const size_t fpn = batch * n0 >> (w + 1), fln = n_pairs * n0 >> (w + 1), L = g->s.L;
+            g->fp_cap[w] = fpn > L ? fpn : L;
+            g->fl_cap[w] = fln > L ? fln : L;
             g->fp[w] = dev_alloc_fe((size_t)k * g->fp_cap[w]);
             g->fl[w] = dev_alloc_fe(g->fl_cap[w]);
         }
-        g->fl0 = (uint8_t*)ctx_dev_alloc(driver, n_pairs * n0 + 16);
-        driver->scratch2.reserve(n_pairs * sizeof(void*));
-        HIP_TRY(hipMemcpyAsync(driver->scratch2.p, cols.data(), n_pairs * sizeof(void*), hipMemcpyHostToDevice, driver->stream));
-        HIP_TRY(hipStreamSynchronize(driver->stream));  // `cols` lives on the stack of this call
-        k_toggle_flags_pack<<<grid_for(n_pairs * n0), PT, 0, driver->stream>>>((const uint8_t* const*)driver->scratch2.p, n0, n_pairs * n0, g->fl0);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(driver->stream));  // scratch2 is shared with other calls
+        toggle_pack_flags(driver, flags, n_pairs, n0, "toggle_group_create", &g->fl0);
         for (int m = 0; m < k; m++) {  // nothing fails from here on: adopt
             cozk_vec* v = fingerprints[m];
             g->fp0[m] = (const fe*)v->d;
             g->owner[m] = nullptr;
             if (take_ownership && v->owned) {
                 g->owner[m] = v->ctx;
-                v->d = nullptr;
-                v->owned = false;
-                v->n = 0;
-                v->bytes = 0;
+                (void)vec_adopt(v);
             }
         }
         g->k = k;
@@ -977,14 +932,14 @@ int cozk_toggle_group_layer_outputs(cozk_toggle_group* g, cozk_ctx* const* owner
     memset(&o, 0, sizeof o);
     int rc = cozk_guard(ctx, [&] {
         COZK_REQUIRE(owners && out, "toggle_group_layer_outputs: null argument");
-        COZK_REQUIRE(g->cur < 0, "toggle_group_layer_outputs: needs an unbound group");
+        COZK_REQUIRE(g->s.cur < 0, "toggle_group_layer_outputs: needs an unbound group");
         for (int m = 0; m < g->k; m++) {
             COZK_REQUIRE(owners[m], "toggle_group_layer_outputs: null owner");
             COZK_REQUIRE(owners[m]->device == ctx->device, "toggle_group_layer_outputs: every owner must live on the driver's device");
         }
-        const size_t total = g->batch * g->n0;
+        const size_t total = g->s.batch * g->s.n0;
         for (int m = 0; m < g->k; m++) o.p[m] = (fe*)ctx_dev_alloc(owners[m], total * sizeof(fe));
-        k_toggle_group_output<<<grid_for(total), PT, 0, ctx->stream>>>(toggle_group_in(g), o, g->fl0, log2_sz(g->n0), total, g->k);
+        k_toggle_group_output<<<grid_for(total), PT, 0, ctx->stream>>>(toggle_group_in(g), o, g->fl0, log2_sz(g->s.n0), total, g->k);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(ctx->stream));  // the outputs are their owners' from here on
         for (int m = 0; m < g->k; m++) out[m] = new cozk_vec{owners[m], total, COZK_SCALAR_FR, o.p[m], total * sizeof(fe), true};
@@ -1003,7 +958,7 @@ int cozk_toggle_group_bind(cozk_toggle_group* g, const uint64_t r[4]) {
     if (!g) return COZK_ERR_INVALID_ARG;
     return cozk_guard(g->driver, [&] {
         COZK_REQUIRE(r, "toggle_group_bind: null argument");
-        COZK_REQUIRE(!toggle_group_bound(g), "toggle_group_bind: the group is fully bound");
+        COZK_REQUIRE(!g->s.bound(), "toggle_group_bind: the group is fully bound");
         toggle_group_bind_launch(g, fe_from_u64x4(r));
     });
 }
@@ -1014,32 +969,25 @@ int cozk_toggle_group_round(cozk_toggle_group* g, cozk_spliteq* e, const uint64_
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(e && out_evals, "toggle_group_round: null argument");
         COZK_REQUIRE(e->ctx == ctx, "toggle_group_round: the eq polynomial must be the driver's");
-        COZK_REQUIRE(!toggle_group_bound(g), "toggle_group_round: the group is fully bound");
+        COZK_REQUIRE(!g->s.bound(), "toggle_group_round: the group is fully bound");
         if (r) {
             COZK_REQUIRE(!spliteq_bound(e), "toggle_group_round: eq polynomial already fully bound");
-            COZK_REQUIRE(!(g->coalesced && g->L == 2), "toggle_group_round: the bind leaves the group fully bound, with no round to run (cozk_toggle_group_bind)");
+            COZK_REQUIRE(!g->s.last_bind(), "toggle_group_round: the bind leaves the group fully bound, with no round to run (cozk_toggle_group_bind)");
             const fe rr = fe_from_u64x4(r);
             toggle_group_bind_launch(g, rr);
             spliteq_bind_launch(ctx, e, rr);  // once for all members
         }
         const unsigned k = (unsigned)g->k;
-        const size_t npairs = g->coalesced ? g->L / 2 : g->batch * g->n_cur / 2;
-        const int log_half_n = g->coalesced ? -1 : log2_sz(g->n_cur / 2);
+        const size_t npairs = g->s.npairs();
         const unsigned gx = sum_grid(grid_capped(npairs, ROUND_GRID_MAX));
         const unsigned rows = 3 * k + 3;
         const SumLaunch sl = sum_launch(ctx, rows, gx, rows + 3);
-        const bool nested = e->E1_len != 1;
-        const fe* E1 = e->E1[e->c1];
-        const fe* E2 = e->E2[e->c2];
-        const int lg1 = nested ? log2_sz(e->E1_len / 2) : 0;
-        const bool u8 = g->cur < 0;  // first round: the packed 0/1 bytes
-        const void* fl = u8 ? (const void*)g->fl0 : (const void*)g->fl[g->cur];
+        const EqView v = eq_view(e);
+        const bool u8 = g->s.cur < 0;  // first round: the packed 0/1 bytes
         const dim3 grid(gx, (k + TOGGLE_GROUP_CHUNK - 1) / TOGGLE_GROUP_CHUNK);
-        auto* const kernel = nested ? (u8 ? k_toggle_group_cubic<1, 0> : k_toggle_group_cubic<1, 1>) : (u8 ? k_toggle_group_cubic<0, 0> : k_toggle_group_cubic<0, 1>);
-        kernel<<<grid, PT, 0, ctx->stream>>>(toggle_group_in(g), (int)k, fl, npairs, log_half_n, E1, lg1, E2, e->E2_len, sl.partial);
-        // S_all(X) behind the finished rows, before the finishing kernel, which publishes the round
-        if (nested) k_toggle_eq_sums<1><<<1, RT, 0, ctx->stream>>>(E1, lg1, E2, e->E2_len, npairs, sl.res + rows);
-        else k_toggle_eq_sums<0><<<1, RT, 0, ctx->stream>>>(E1, 0, E2, e->E2_len, npairs, sl.res + rows);
+        auto* const kernel = v.nested ? (u8 ? k_toggle_group_cubic<1, 0> : k_toggle_group_cubic<1, 1>) : (u8 ? k_toggle_group_cubic<0, 0> : k_toggle_group_cubic<0, 1>);
+        kernel<<<grid, PT, 0, ctx->stream>>>(toggle_group_in(g), (int)k, toggle_group_fl(g), npairs, g->s.log_half_n(), v.E1, v.lg1, v.E2, v.E2_len, sl.partial);
+        eq_sums_launch(ctx, v, npairs, sl.res + rows);  // behind the finished rows
         fe s[3 * COZK_LAYER_GROUP_MAX + 6];
         finish_sums(ctx, sl, rows, gx, Fr::one(), 0, s);
         for (unsigned m = 0; m < k; m++)
@@ -1053,12 +1001,9 @@ int cozk_toggle_group_final_claims(cozk_toggle_group* g, uint64_t flag[4], uint6
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(flag && (fingerprints || k_final == 0), "toggle_group_final_claims: null argument");
         COZK_REQUIRE(k_final >= 0 && k_final <= g->k, "toggle_group_final_claims: 0 <= k_final <= k");
-        COZK_REQUIRE(toggle_group_bound(g), "toggle_group_final_claims: the group is not fully bound");
-        fe* res = result_slot(ctx, (size_t)k_final + 1);
-        k_toggle_group_claims<<<1, 64, 0, ctx->stream>>>(toggle_group_in(g), g->fl[g->cur], k_final, res);
-        HIP_TRY(hipGetLastError());
+        COZK_REQUIRE(g->s.bound(), "toggle_group_final_claims: the group is not fully bound");
         fe h[COZK_LAYER_GROUP_MAX + 1];
-        fetch_fe(ctx, res, (size_t)k_final + 1, h);
+        toggle_claims_fetch(ctx, toggle_group_in(g), g->fl[g->s.cur], k_final, h);
         fe_to_u64x4(h[0], flag);
         for (int m = 0; m < k_final; m++) fe_to_u64x4(h[1 + m], fingerprints + 4 * m);
     });

@@ -681,7 +681,9 @@ int cozk_toggle_layer_output(cozk_ctx* ctx, const cozk_toggle* t, int party_id, 
 int cozk_toggle_bind(cozk_ctx* ctx, cozk_toggle* t, const uint64_t r[4]);
 /* one round of prove_sumcheck over the toggle layer (compute_cubic, :311-823): bind layer + split-eq tables with the
  * previous challenge r (NULL in the first round), then this party's additive g(0), g(2), g(3) of
- * sum_x eq(x) (flag(x) fingerprint(x) + 1 - flag(x)) */
+ * sum_x eq(x) (flag(x) fingerprint(x) + 1 - flag(x)).  The eq polynomial must be ctx's.  Every check comes before the bind: a call
+ * refused with COZK_ERR_INVALID_ARG (a fully bound layer or eq polynomial, a bind that would leave no round to run) leaves both
+ * as they were */
 int cozk_toggle_round(cozk_ctx* ctx, cozk_toggle* t, cozk_spliteq* eq, const uint64_t* r, int party_id,
                       uint64_t out_evals[12]);
 /* final_claims (:825-835): the bound flag (public) and the bound fingerprint share */

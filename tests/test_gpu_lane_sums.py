@@ -159,6 +159,39 @@ def test_toggle_rounds_at_one_workgroup_equal_the_sparse_oracle(cozk, ctx, monke
     eq_dev.free()
 
 
+@pytest.mark.parametrize("mode", ["plain", "rep3"])
+def test_toggle_montgomery_rounds_at_one_workgroup_equal_the_sparse_oracle(cozk, ctx, monkeypatch, mode):
+    """2^10 pairs (below TOGGLE_F9_MIN_PAIRS: k_toggle_cubic, the Montgomery kernel) at one workgroup, 60 % flags: every wave looks
+    four times in round 0 and carries what is left of its queue (64 < queue < 128) from one look to the next.  All 11 rounds -- u8 and
+    bound flags, nested and flat eq tables, the coalesced rounds -- against oracle/pysparse.py"""
+    LK = importlib.import_module("co-zkvms_amd.lookups")
+    n, batch, density = 1 << 9, 4, 60
+    rng = O.SplitMix64(405)
+    cols = [[1 if rng.next() % 100 < density else 0 for _ in range(n)] for _ in range(batch // 2)]
+    vals = [[rng.field() for _ in range(n)] for _ in range(batch)]
+    if mode == "plain":
+        fps, party, nparties = vals, 0, 1
+    else:
+        sh = [[O.rep3_share(v, rng) for v in row] for row in vals]
+        fps, party, nparties = [[s[1] for s in row] for row in sh], 1, 3
+    ref = S.ToggleLayer([[i for i, f in enumerate(c) if f] for c in cols], fps, party, nparties)
+    dev = LK.ToggleLayer(ctx, cols, fps)
+    nv = (batch * n).bit_length() - 1
+    assert nv == 11
+    w = [rng.field() for _ in range(nv)]
+    rs = [rng.field() for _ in range(nv)]
+    eq_ref, eq_dev = O.SplitEq(w), cozk.SplitEqPolynomial(ctx, w)
+    claim = rng.field()
+    for j in range(nv):
+        ev = ref.compute_cubic_evals(eq_ref, claim)
+        got = _pinned(monkeypatch, lambda: dev.round(eq_dev, rs[j - 1] if j else None, party=party))
+        assert got == [ev[0], ev[2], ev[3]], (mode, j)
+        ref.bind(rs[j])
+        eq_ref.bind(rs[j])
+    dev.free()
+    eq_dev.free()
+
+
 def _digests(monkeypatch, make, pinned):
     if pinned:
         monkeypatch.setenv(GRID, "1")

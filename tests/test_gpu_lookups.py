@@ -67,6 +67,43 @@ def test_toggle_layer_all_rounds_match_the_sparse_oracle(cozk, ctx, batch, n, de
         dev.free()
 
 
+@pytest.mark.parametrize("nparties", [1, 3])
+def test_toggle_round_refusal_leaves_toggle_and_eq_untouched(cozk, ctx, nparties):
+    """cozk_toggle_round makes every check before it binds: with a challenge and (a) an eq polynomial that is already fully bound,
+    (b) an eq polynomial of another context, it is refused with COZK_ERR_INVALID_ARG, and the layer and that eq are what they were;
+    the next valid round equals the same round on a twin that saw no refusal."""
+    LK = importlib.import_module("co-zkvms_amd.lookups")
+    batch, n = 2, 4
+    cols, vals, fps = _instance(batch, n, 60, 31, nparties)
+    party = 1 if nparties == 3 else 0
+    rng = O.SplitMix64(8)
+    w = [rng.field() for _ in range((batch * n).bit_length() - 1)]
+    r = rng.field()
+    dev, twin = LK.ToggleLayer(ctx, cols, fps[party]), LK.ToggleLayer(ctx, cols, fps[party])
+    eq, eq_twin = cozk.SplitEqPolynomial(ctx, w), cozk.SplitEqPolynomial(ctx, w)
+    assert dev.round(eq, None, party=party) == twin.round(eq_twin, None, party=party)
+    bound = cozk.SplitEqPolynomial(ctx, w[:1])
+    bound.bind(r)
+    assert bound.lens() == (1, 1)
+    other_ctx = cozk.Context(0)
+    foreign = cozk.SplitEqPolynomial(other_ctx, w)
+    before = dev.download()
+    for bad, text in ((bound, "toggle_round: eq polynomial already fully bound"), (foreign, "toggle_round: the eq polynomial belongs to another context")):
+        lens = bad.lens()
+        with pytest.raises(cozk.CozkError) as err:
+            dev.round(bad, r, party=party)
+        assert err.value.code == -1 and text in str(err.value)  # COZK_ERR_INVALID_ARG
+        assert dev.download() == before
+        assert bad.lens() == lens
+    assert eq.lens() == eq_twin.lens()
+    assert dev.round(eq, r, party=party) == twin.round(eq_twin, r, party=party)
+    assert dev.download() == twin.download() != before
+    foreign.free()
+    other_ctx.close()
+    for x in (dev, twin, eq, eq_twin, bound):
+        x.free()
+
+
 @pytest.mark.parametrize("batch,n,nparties", [(6, 16, 3), (4, 32, 1)])
 def test_sparse_layers_kept_dense_match_the_sparse_oracle(cozk, ctx, batch, n, nparties):
     """a Rep3SparseInterleavedPolynomial on the device is a cozk_layer with the ones stored: cubic round messages and
