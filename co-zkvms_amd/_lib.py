@@ -17,6 +17,7 @@ SCALAR_FR, SCALAR_U8, SCALAR_U16, SCALAR_U32, SCALAR_U64, SCALAR_I64 = range(6)
 LOW_TO_HIGH, HIGH_TO_LOW = 0, 1
 MODE_PLAIN, MODE_REP3 = 1, 2
 LAYER_GROUP_MAX = 32
+SPARTAN_GROUP_FIRST, SPARTAN_GROUP_SECOND = 1, 2
 OP_ADD, OP_SUB, OP_MUL = 0, 1, 2
 
 
@@ -174,6 +175,12 @@ SIGNATURES = {
     "cozk_layer_group_round": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "cozk_layer_group_final": (_i, [_vp, _vp, _vp, _i, _vp]),
     "cozk_layer_group_free": (_i, [_vp]),
+    "cozk_spartan_group_create": (_i, [_vp, _i, _vp, _i, _vp, _pp]),
+    "cozk_spartan_group_round": (_i, [_vp, _vp, _vp]),
+    "cozk_spartan_group_final": (_i, [_vp, _vp, _i, _vp]),
+    "cozk_spartan_group_len": (_sz, [_vp]),
+    "cozk_spartan_group_pub_download": (_i, [_vp, _vp]),
+    "cozk_spartan_group_free": (_i, [_vp]),
     "cozk_toggle_group_create": (_i, [_vp, _vp, _sz, _vp, _i, _i, _pp]),
     "cozk_toggle_group_layer_outputs": (_i, [_vp, _vp, _vp]),
     "cozk_toggle_group_round": (_i, [_vp, _vp, _vp, _vp]),

@@ -2975,6 +2975,7 @@ int cozk_layer_claimed_outputs(cozk_ctx* ctx, const cozk_layer* l, uint64_t* out
 }  // extern "C"
 
 #include "toggle_layer.inc"
+#include "spartan_group.inc"
 #include "sparse_layer.inc"
 #include "primary_sumcheck.inc"
 #include "spartan_outer.inc"

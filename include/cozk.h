@@ -142,7 +142,8 @@ int cozk_vec_add_scalar(cozk_ctx* ctx, cozk_vec* v, const uint64_t s[4]);
  * that is a degree-t sharing again, so that products chain, is cozk_shamir_mul_{deal, inproc, vec} below.  The reference has
  * no Shamir network, degree reduction or prover; the multiplication here is the classic one-round resharing (GRR / BGW),
  * restated in tests/shamir_mul_ref.py, and beside it the king variant with preprocessed double-random pairs
- * (cozk_shamir_rand_*, cozk_shamir_mul_king_*; tests/shamir_dn_ref.py).  The one Shamir prover is the dense batched grand
+ * (cozk_shamir_rand_*, cozk_shamir_mul_king_*; tests/shamir_dn_ref.py).  co-noir-spartan by n Shamir parties is cozk_shamir_spartan_*
+ * (behind the co-noir-spartan harness below).  The first Shamir prover is the dense batched grand
  * product at the end of this section: cozk_shamir_gp_prove_inproc (tests/shamir_gp_ref.py) with the resharing construct, and
  * cozk_shamir_gp_prep_inproc + cozk_shamir_gp_prove_king_inproc (tests/shamir_gp_king_ref.py) with the king's. */
 #define COZK_SHAMIR_MAX_PARTIES 32
@@ -647,6 +648,48 @@ int cozk_layer_group_round(cozk_layer_group* g, cozk_spliteq* e, const uint64_t*
 int cozk_layer_group_final(cozk_layer_group* g, cozk_spliteq* e, const uint64_t* r, int k_final,
                            uint64_t* out_claims /* k_final x 16 */);
 int cozk_layer_group_free(cozk_layer_group* g);
+/* Spartan groups: one round of a co-noir-spartan sumcheck (co-noir-spartan/co-spartan/src/sumcheck.rs:171-395) for SEVERAL members
+ * against ONE public polynomial, with one challenge, as one unit of work -- the senders of a Shamir prover
+ * (csrc/host/shamir_spartan.hpp).  Every step of that prover is linear in the witness share or multiplies two secret factors, so a
+ * party runs the PLAIN round on its shares.  A group has k members, 1 <= k <= COZK_LAYER_GROUP_MAX, of P PLAIN polynomials each
+ * ("planes", planes[P m + j] = plane j of member m), all of one current length, a power of two >= 2, pairwise distinct, each of a
+ * context on the DRIVER's device (the contexts may differ).
+ *   COZK_SPARTAN_GROUP_FIRST   P = 3 (za, zb, zc), public = eq:  g_m(X) = sum_b pub(X) (za_m(X) zb_m(X) - zc_m(X)) at X = 0, 1, 2, 3:
+ *                              cozk_spartan_first_round's out[] (LowToHigh pairs 2b, 2b + 1)
+ *   COZK_SPARTAN_GROUP_SECOND  P = 1 (z), public = ONE vector lin = alpha A + beta B + gamma C, formed once in front of the rounds
+ *                              (cozk_poly_linear_combination):  g_m(X) = sum_b pub(X) z_m(X) at X = 0, 1, 2: cozk_spartan_second_round's
+ *                              out_a[].  The three matrix columns are not bound per round: A(rx,ry), B(rx,ry), C(rx,ry) are one public
+ *                              evaluation at ry behind the rounds (cozk_poly_batch_evaluate_at_chi) -- the same field elements.
+ * The group REFERS to the members' polynomials: it does not own them, freeing it leaves them valid, they must outlive it.  It OWNS the
+ * public polynomial: create COPIES pub's current coefficients into ping-pong storage of the group's own (len and len / 2 elements from
+ * the driver's pool); `pub` itself is only read, by create, and may be freed right after.  create drains the stream of every context
+ * involved once and sizes both ping-pong sides of every plane for all binds to come, from the plane's own pool: later calls
+ * allocate nothing.
+ *   round  r == NULL (the first round): the sums of the members as they stand.  r != NULL: every plane and the group's public
+ *          polynomial are bound with r (cozk_poly_bind(.., COZK_LOW_TO_HIGH)), then the sums are taken.  Member m's evaluations go to
+ *          out_evals + 4 E m (E = 4 FIRST, 3 SECOND; k x E x 4 u64).  The bind is fused with the sums: ONE launch of gx x k workgroups
+ *          and ONE finishing launch whatever k is, ONE fetch; members of <= 2048 elements run as ONE launch of k workgroups.  The bound
+ *          public polynomial is written to the side of the group's ping-pong storage that no workgroup of the launch reads.
+ *   final  the last bind with r (len == 2; r == NULL: no bind, everything is down to one element already) of members 0 .. k_final - 1
+ *          and of the public polynomial; out = the P final values of member 0, .., of member k_final - 1, then the public polynomial's
+ *          ((P k_final + 1) x 4 u64).  One launch, one fetch; members from k_final upwards are left untouched.
+ *   len / pub_download  the current length, and the group's public polynomial as it stands (len x 4 u64).
+ * Every launch goes on the driver's stream and every call returns with that stream drained; when a call returns every bound plane is
+ * in the state cozk_poly_bind(.., COZK_LOW_TO_HIGH) on its own context would have left it in.
+ * Refused on the host before any launch, with COZK_ERR_INVALID_ARG and the text left with the driver (*out is NULL), the members and
+ * the public polynomial untouched: null arguments, an unknown kind, k out of range, a plane or a pub that is not PLAIN, unequal
+ * lengths, a length that is not a power of two or is below 2, a duplicate plane, a member or a pub on another device, a round on
+ * fully bound members or a binding round that would leave them so, k_final outside 0..k, a final that does not end at one element. */
+#define COZK_SPARTAN_GROUP_FIRST 1
+#define COZK_SPARTAN_GROUP_SECOND 2
+typedef struct cozk_spartan_group cozk_spartan_group;
+int cozk_spartan_group_create(cozk_ctx* driver, int kind, cozk_poly* const* planes /* k x P */, int k, const cozk_poly* pub,
+                              cozk_spartan_group** out);
+int cozk_spartan_group_round(cozk_spartan_group* g, const uint64_t* r, uint64_t* out_evals /* k x E x 4 */);
+int cozk_spartan_group_final(cozk_spartan_group* g, const uint64_t* r, int k_final, uint64_t* out /* (P k_final + 1) x 4 */);
+size_t cozk_spartan_group_len(const cozk_spartan_group* g);
+int cozk_spartan_group_pub_download(cozk_spartan_group* g, uint64_t* out);
+int cozk_spartan_group_free(cozk_spartan_group* g);
 /* local half of layer_output -> mul_vec (dense_interleaved_poly.rs:122-141; local product
  * mpc-types/src/protocols/rep3/arithmetic/ops.rs:71-78): out[j] = L[j] x R[j] + mask_j, where
  * mask_j = PRF(key_self, counter + j) - PRF(key_prev, counter + j) when masked != 0 (key_self is shared with the
@@ -1160,6 +1203,65 @@ const char* cozk_spartan_error(const cozk_spartan* h);
 int cozk_spartan_destroy(cozk_spartan* h);
 int cozk_spartan_prove(cozk_spartan* h, int verify, cozk_spartan_result* res);
 int cozk_spartan_proof_bytes(const cozk_spartan* h, uint8_t* out, size_t cap);
+
+/* ---------------------------------------------------------------- co-noir-spartan by n Shamir parties ---- */
+/* The harness above proved by n Shamir parties of degree t, semi-honest, all driven from the calling thread, which owns every party's
+ * context and plays the coordinator (csrc/host/shamir_spartan.hpp; restated in tests/shamir_spartan_ref.py; the reference has no Shamir
+ * prover).  The instance is cozk_spartan's for (seed, log_n).  Every step of the worker is linear in the witness share or multiplies at
+ * most two secret factors, so each party runs the COZK_MODE_PLAIN calls on its degree-t share of z: THE PROOF IS THE PLAIN PROVER'S, BYTE
+ * FOR BYTE (cozk_spartan with MODE_PLAIN, oracle/pyspartan.py), accepted by the same verifier.
+ *   witness    z is dealt once with cozk_shamir_share_vec's rule at share_counter: coefficient c of element i = PRF(share key c,
+ *              share_counter + i), share key c = the harness key (seed ^ 0x53484152, c), c = 0 .. t - 1 (harness keys: the 32 bytes
+ *              of four SplitMix64 steps from seed' ^ (0xC0DEC0DE + idx * 0x9E3779B97F4A7C15), as every in-process harness derives them)
+ *   zero_round per sender 0..2t, cozk_sparse_matvec3 on its share
+ *   commit     parties 0..t commit to their share; the points are combined with lagrange(1..t + 1) (cozk_shamir_combine_points)
+ *   masks      M = 4 log_n openings of degree 2t: ONE dealing (cozk_shamir_rand_inproc's rule) of M elements at rand_counter, pair 0
+ *              only, zero_p[m] = r2t_p^0[m] - rt_p^0[m].  Party p's (3t + 1) x 32 rand key bytes: key j = the harness key
+ *              (seed ^ 0x52414E44, 64 p + j).  As for the grand product A PAIR MUST NEVER BE USED TWICE: (seed, rand_counter ..
+ *              rand_counter + M) must not serve another proof -- the caller's contract.
+ *   sumcheck 1 sum_x eq(tau, x) (Az Bz - Cz)(x): sender p <= 2t sends g_p(0..3) + zero_p[4 round + e]; opened with lagrange(1..2t + 1).
+ *              za, zb, zc(rx) are opened from parties 0..t with lagrange(1..t + 1), unmasked; eq(tau, rx) is public
+ *   sumcheck 2 sum_y z(y) (alpha A + beta B + gamma C)(rx, y): the matrices are public, parties 0..t send g_p(0..2), opened with
+ *              lagrange(1..t + 1), unmasked, as z's final value is; A, B, C(rx, ry) are public
+ *   opening    z(ry) and PST13 open per party 0..t on its share; scalars and quotient commitments combined with lagrange(1..t + 1)
+ * When the senders' contexts are on one device each sumcheck runs as ONE cozk_spartan_group on sender 0's context (stats: group_rounds
+ * = 2 log_n, group_finals = 2); otherwise, or with COZK_SHAMIR_GP_GROUP=0 in the environment (read on every prove), every sender runs
+ * cozk_spartan_first_round / cozk_spartan_second_round and cozk_poly_bind (single_rounds = (2t + 1) log_n + (t + 1) log_n,
+ * single_finals = 2 (t + 1)).  Proof, msgs and finals are the same bytes either way.
+ * Refused by create before any launch (the handle is returned with its error text): 1 <= t, 2t <= COZK_SHAMIR_MAX_DEGREE,
+ * 2t + 1 <= n <= COZK_SHAMIR_MAX_PARTIES, 1 <= log_n <= 24.  Not built: the public lookup round, one party per process, groups over
+ * several GPUs, a king variant (no secret-by-secret multiplication is reshared here). */
+typedef struct cozk_shamir_spartan cozk_shamir_spartan;
+typedef struct cozk_shamir_spartan_config {
+    int log_n;
+    int precompute; /* window table for the SRS (as cozk_harness_config) */
+    int degree, num_parties;
+    int devices[COZK_SHAMIR_MAX_PARTIES]; /* one per party */
+    uint64_t seed;
+    uint64_t share_counter, rand_counter;
+} cozk_shamir_spartan_config;
+typedef struct cozk_shamir_spartan_result {
+    int verified; /* 1 ok, 0 rejected, -1 not run */
+    int grouped;  /* 1: the sumchecks ran as Spartan groups */
+    uint64_t proof_len;
+    uint8_t proof_digest[32]; /* SHA-256 of the serialized proof */
+    uint64_t n_opened;        /* M */
+    /* host clock, every party's stream drained at both ends; one thread drives the parties in turn: SUMS over parties */
+    double wall_ms, t_zero_round_ms, t_commit_ms, t_masks_ms, t_sumcheck1_ms, t_matrix_build_ms, t_sumcheck2_ms, t_open_ms;
+} cozk_shamir_spartan_result;
+int cozk_shamir_spartan_create(const cozk_shamir_spartan_config* cfg, cozk_shamir_spartan** out);
+const char* cozk_shamir_spartan_error(const cozk_shamir_spartan* h);
+int cozk_shamir_spartan_destroy(cozk_shamir_spartan* h);
+int cozk_shamir_spartan_prove(cozk_shamir_spartan* h, int verify, cozk_shamir_spartan_result* res);
+int cozk_shamir_spartan_proof_bytes(const cozk_shamir_spartan* h, uint8_t* out, size_t cap);
+/* the masked first-sumcheck messages [m][p <= 2t], m = 4 round + evaluation index (msgs_len = 4 log_n (2t + 1) elements x 4 u64) */
+size_t cozk_shamir_spartan_msgs_len(const cozk_shamir_spartan* h);
+int cozk_shamir_spartan_msgs(const cozk_shamir_spartan* h, uint64_t* out, size_t cap);
+/* the t + 1 openers' shares [value][p <= t] of: za(rx), zb(rx), zc(rx); round by round the second sumcheck's g(0), g(1), g(2); z's
+ * final value; z(ry) (finals_len = (3 log_n + 5)(t + 1) elements) */
+size_t cozk_shamir_spartan_finals_len(const cozk_shamir_spartan* h);
+int cozk_shamir_spartan_finals(const cozk_shamir_spartan* h, uint64_t* out, size_t cap);
+int cozk_shamir_spartan_get_stats(const cozk_shamir_spartan* h, cozk_shamir_gp_stats* stats);
 
 /* ---------------------------------------------------------------- instruction-lookups harness ---- */
 /* SURVEY.md 8(f)1 restated synthetically: the toggled / sparse batched grand product of Lasso's read / write memory

@@ -52,7 +52,15 @@ With --tgp, instead, the TOGGLED Shamir grand product over --pairs flag columns 
   (xxi)   the whole prove with the toggle layer as one toggle group and the dense rounds on layer groups against the whole prove with
           COZK_SHAMIR_GP_GROUP=0, as (xix): alternating, proofs, messages, final-claim shares and toggle claims compared.
 --only-group runs nothing but (xxi):
-  python tools/run_shamir.py --tgp --only-group --log-n 18 --pairs 8 --density 10 --parties 8 --degree 2 --out profiles/shamir_tgp_group_2p18_p8_n8_t2.json"""
+  python tools/run_shamir.py --tgp --only-group --log-n 18 --pairs 8 --density 10 --parties 8 --degree 2 --out profiles/shamir_tgp_group_2p18_p8_n8_t2.json
+With --spartan, instead, co-noir-spartan of 2^log_n constraints proved by the Shamir parties (cozk_shamir_spartan_*):
+  (xxii)  the first two rounds of the first sumcheck (the sums, then the bind with a challenge and the sums) as ONE cozk_spartan_group over
+          the senders' (za, zb, zc) against the senders' cozk_spartan_first_round + 4 x cozk_poly_bind calls, each with an eq of its own,
+          alternating in this process on fresh polynomials, outputs compared raw;
+  (xxiii) the whole prove with both sumchecks as Spartan groups against the whole prove with COZK_SHAMIR_GP_GROUP=0 (the per-poly calls),
+          alternating in this process, proofs, messages and final shares compared; the ungrouped leg is the yardstick.
+--only-group runs nothing but (xxiii):
+  python tools/run_shamir.py --spartan --only-group --log-n 18 --parties 8 --degree 2 --out FILE"""
 import argparse, ctypes, hashlib, importlib, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -70,6 +78,8 @@ ap.add_argument("--gp", action="store_true", help="time the Shamir grand product
 ap.add_argument("--gp-batch", type=int, default=2, help="with --gp: circuits in the grand product")
 ap.add_argument("--only-group", action="store_true", help="with --gp: only the grouped against the ungrouped prove, resharing and king prover; with --tgp: only (xxi)")
 ap.add_argument("--tgp", action="store_true", help="time the toggled Shamir grand product prover instead (--king: the king construct)")
+ap.add_argument("--spartan", action="store_true", help="time co-noir-spartan proved by the Shamir parties instead (--only-group: only the whole prove)")
+ap.add_argument("--seed", type=int, default=2030, help="with --spartan: the instance's seed")
 ap.add_argument("--pairs", type=int, default=8, help="with --tgp: flag columns (pairs of circuits)")
 ap.add_argument("--density", type=int, default=10, help="with --tgp: percent of the flags that are set")
 args = ap.parse_args()
@@ -884,6 +894,125 @@ def tgp_legs():
         pc.close()
     emit(res)
 
+
+def spartan_legs():
+    """--spartan: (xxii) unless --only-group, then (xxiii); the harness owns one context per party on this GPU"""
+    if 2 * T + 1 > N or 2 * T > 15:
+        raise SystemExit("run_shamir --spartan: needs 2 * degree + 1 <= parties and 2 * degree <= 15")
+    P = importlib.import_module("co-zkvms_amd.poly")
+    senders = 2 * T + 1
+    res = {
+        "what": "co-noir-spartan by Shamir parties: both sumchecks as Spartan groups (one fused bind + sums launch, one finishing launch and one "
+                "fetch per round for all senders, one public polynomial) against the per-poly calls per sender (COZK_SHAMIR_GP_GROUP=0)",
+        "log_n": args.log_n, "constraints": n, "parties": N, "degree": T, "senders": senders, "openers": T + 1, "seed": args.seed,
+        "device": torch.cuda.get_device_name(0),
+    }
+    if not args.only_group:
+        pcs, streams = party_contexts()
+        whole = lambda fn: whole_call(pcs, streams, fn)
+        base = [[cozk.Vec.random(pcs[p], n, seed=3000 + 10 * p + j) for j in range(3)] for p in range(senders)]
+        eq_base = [cozk.Vec.random(pcs[p], n, seed=2999) for p in range(senders)]
+        r = cozk.fr_to_mont_limbs([pow(3, 77, cozk.FR_MOD)])[0]
+        mk = lambda: [tuple(P.Rep3DensePolynomial.from_vec_shares(pcs[p], v) for v in base[p]) for p in range(senders)]
+
+        def run_g():
+            members, eq = mk(), P.Rep3DensePolynomial.from_vec_shares(pcs[0], eq_base[0])
+            g = cozk.SpartanGroup(pcs[0], 1, members, eq)
+            ms, out = whole(lambda: [g.round_raw(None), g.round_raw(r)])
+            g.free()
+            return ms, out
+
+        def run_s():
+            members, eqs = mk(), [P.Rep3DensePolynomial.from_vec_shares(pcs[p], eq_base[p]) for p in range(senders)]
+
+            def rounds():
+                outs = [np.zeros((senders, 4, 4), dtype=np.uint64) for _ in range(2)]
+                for j in range(2):
+                    for p in range(senders):
+                        c = pcs[p]
+                        if j:
+                            for q in members[p] + (eqs[p],):
+                                c.check(c._l.cozk_poly_bind(c.h, q.h, r.ctypes.data, L.LOW_TO_HIGH))
+                        za, zb, zc = members[p]
+                        c.check(c._l.cozk_spartan_first_round(c.h, za.h, zb.h, zc.h, eqs[p].h, outs[j][p].ctypes.data))
+                return outs
+            return whole(rounds)
+
+        og, os_ = run_g()[1], run_s()[1]
+        assert all(np.array_equal(x, y) for x, y in zip(og, os_)), "the group rounds and the per-sender rounds differ"
+        t_g, t_s = [], []
+        while sum(t_g) < args.min_seconds * 1e3 or sum(t_s) < args.min_seconds * 1e3 or len(t_g) < 6:
+            t_g.append(run_g()[0])
+            t_s.append(run_s()[0])
+        res["first_two_rounds"] = {"group_rounds": stats(t_g), "per_sender_rounds_same_run": stats(t_s),
+                                   "group_vs_per_sender_speedup": round(med(t_s) / med(t_g), 3), "outputs_equal": True}
+        for vs in base:
+            free(vs)
+        free(eq_base)
+        for pc in pcs:
+            pc.close()
+
+    h = cozk.ShamirSpartanHarness(log_n=args.log_n, parties=N, degree=T, devices=0, seed=args.seed)
+    split = ("t_zero_round_ms", "t_commit_ms", "t_masks_ms", "t_sumcheck1_ms", "t_matrix_build_ms", "t_sumcheck2_ms", "t_open_ms")
+
+    def leg(ungrouped):
+        if ungrouped:
+            os.environ[GROUP_SWITCH] = "0"  # read by the library on every prove
+        try:
+            r_ = h.prove(verify=False)
+            st = h.stats()
+            return r_, {k: int(getattr(st, k)) for k in ("group_rounds", "single_rounds", "group_finals", "single_finals")}
+        finally:
+            os.environ.pop(GROUP_SWITCH, None)
+
+    rg = h.prove(verify=True)  # warm-up and correctness
+    pg = (h.proof_bytes(rg), h.msgs(), h.finals())
+    os.environ[GROUP_SWITCH] = "0"
+    try:
+        ru = h.prove(verify=True)
+    finally:
+        os.environ.pop(GROUP_SWITCH, None)
+    pu = (h.proof_bytes(ru), h.msgs(), h.finals())
+    assert rg.verified == 1 and ru.verified == 1, "a Shamir Spartan proof was rejected: " + h.last_error()
+    assert rg.grouped == 1 and ru.grouped == 0, "the switch did not select the legs"
+    assert pg == pu, "the grouped and the ungrouped prove differ in proof, messages or final shares"
+    digest = bytes(rg.proof_digest)
+    legs = {False: [], True: []}
+    calls = {}
+    while sum(x.wall_ms for x in legs[False]) < args.min_seconds * 1e3 or sum(x.wall_ms for x in legs[True]) < args.min_seconds * 1e3 or len(legs[False]) < 6:
+        for u in (False, True):
+            r_, calls[u] = leg(u)
+            assert bytes(r_.proof_digest) == digest, "a repetition's proof differs"
+            legs[u].append(r_)
+    sums = lambda x: x.t_sumcheck1_ms + x.t_sumcheck2_ms
+    rep = lambda rs, c: dict(stats([x.wall_ms for x in rs]), driver_split={k: stats([getattr(x, k) for x in rs]) for k in split},
+                             sumchecks=stats([sums(x) for x in rs]), calls=c)
+    t_g, t_u = [x.wall_ms for x in legs[False]], [x.wall_ms for x in legs[True]]
+    spread_u = max(t_u) - min(t_u)
+    res["prover"] = {
+        "grouped_whole_prove": rep(legs[False], calls[False]),
+        "ungrouped_whole_prove_same_run": rep(legs[True], calls[True]),
+        "grouped_vs_ungrouped_speedup": round(med(t_u) / med(t_g), 3),
+        "sumchecks_grouped_vs_ungrouped_speedup": round(med([sums(x) for x in legs[True]]) / med([sums(x) for x in legs[False]]), 3),
+        "grouped_slower_than_ungrouped_by_ms": round(med(t_g) - med(t_u), 4),
+        "ungrouped_min_max_spread_ms": round(spread_u, 4),
+        "grouped_not_slower_beyond_ungrouped_spread": bool(med(t_g) - med(t_u) <= spread_u),
+        "proofs_messages_finals_equal": True,
+        "proof_sha256": digest.hex(),
+    }
+    res["timing"] = ("whole prove: the driver's host clock from every party's stream drained to every party's stream drained (one thread drives the "
+                     "parties in turn: sums over parties), setup (instance, SRS, sharing) outside; first two rounds: from an event on party 0's idle "
+                     "stream to the last of the events behind the parties' streams, polynomial and group creation outside; the grouped and the "
+                     "ungrouped leg alternating in one process, the ungrouped leg being the yardstick; the seed's keys and counters reused across "
+                     "repetitions (timing only)")
+    h.close()
+    emit(res)
+
+
+if args.spartan:
+    spartan_legs()
+    ctx.close()
+    raise SystemExit(0)
 
 if args.tgp:
     tgp_legs()
