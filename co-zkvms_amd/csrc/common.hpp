@@ -92,13 +92,10 @@ struct DevBuf {
 // what the sort phase of one MSM launch set produces (two of them: the sort of set k+1 overlaps the accumulation of set k)
 struct MsmSortWs {
     DevBuf hist, off0, refs, offA, ptrs;
-    uint32_t* max_pinned = nullptr;   // [0] fullest bucket (read back behind max_event); + 64: polynomial descriptors (H2D staging)
-    hipEvent_t max_event = nullptr, done = nullptr, consumed = nullptr;
+    hipEvent_t done = nullptr, consumed = nullptr;
     void release() {
         for (DevBuf* b : {&hist, &off0, &refs, &offA, &ptrs}) b->release();
-        if (max_pinned) (void)hipHostFree(max_pinned);
-        max_pinned = nullptr;
-        for (hipEvent_t* e : {&max_event, &done, &consumed}) {
+        for (hipEvent_t* e : {&done, &consumed}) {
             if (*e) (void)hipEventDestroy(*e);
             *e = nullptr;
         }
@@ -106,11 +103,18 @@ struct MsmSortWs {
 };
 struct MsmWorkspace {
     MsmSortWs sort[2];
-    DevBuf offB, offC, partA, partB, bsum, chunk, grp, out, ptrs, exc, blk, perm, offP;
+    DevBuf offB, offC, heavy, partA, partB, bsum, chunk, grp, out, ptrs, exc, blk, perm, offP, form, corr;
     hipEvent_t fork = nullptr;
+    // pinned staging of one batch: a slot per launch set (descriptors in, fullest bucket and reference total out), then
+    // the offset-form corrections.  Regrown only at the start of a batch, when nothing of the previous one is in flight.
+    void* pin = nullptr;
+    size_t pin_cap = 0;
     void release() {
         for (MsmSortWs& s : sort) s.release();
-        for (DevBuf* b : {&offB, &offC, &partA, &partB, &bsum, &chunk, &grp, &out, &ptrs, &exc, &blk, &perm, &offP}) b->release();
+        for (DevBuf* b : {&offB, &offC, &heavy, &partA, &partB, &bsum, &chunk, &grp, &out, &ptrs, &exc, &blk, &perm, &offP, &form, &corr}) b->release();
+        if (pin) (void)hipHostFree(pin);
+        pin = nullptr;
+        pin_cap = 0;
         if (fork) (void)hipEventDestroy(fork);
         fork = nullptr;
     }
@@ -259,6 +263,15 @@ struct cozk_bases {
     int nwin;           // 16 if a window table was precomputed, else 1
     g1_affine* table;   // [nwin][n]: table[w][i] = 2^(16 w) * G_i   (table[0] = the points themselves)
     bool has_inf = true;  // some table entry is the point at infinity (set by build_window_table; the gather kernel then tests for it)
+    // Offset-digit corrections (msm.hip): for a slice [off, off + n) with S = sum of its points, cS[j] = c_j S for the
+    // U16 / U32 / U64 constants c_j.  Computed the first time the slice is committed with such a column, kept with the
+    // handle (a short list, oldest entry replaced when full); sums_mu guards the list (a handle may serve several host threads).
+    struct SliceSum {
+        size_t off, n;
+        g1_affine cS[3];
+    };
+    std::mutex sums_mu;
+    std::vector<SliceSum> sums;
 };
 
 struct cozk_vec {       // device array of field elements / small scalars

@@ -15,12 +15,13 @@
 //     sorted references and adds the gathered affine points into an XYZZ accumulator
 //     (8M+2S, no inversion).  Segments, not buckets, are the unit of parallelism, so skewed
 //     scalars (0/1 flags, u8/u16 witness columns: one bucket holding n/2 points) cost the same as
-//     uniform ones; further levels fold the per-segment partial sums until one value per bucket.
+//     uniform ones; one fold level finishes the ordinary buckets, one launch the heavy ones (k_msm_fold_heavy).
 //   * a batch of P polynomials is just P x more groups in the same launches (amortises the
 //     latency-bound bucket-reduction tail).
 // Results are returned as affine points, so the output is bit-exact to any correct MSM.
 #include "common.hpp"
 #include "fq9.hip.hpp"
+#include <cstring>
 
 static constexpr uint32_t NB = 1u << 15;  // buckets per group
 static constexpr int CH = 16;             // buckets per reduction chunk
@@ -99,11 +100,41 @@ static inline int kind_nwin(int kind) {
     }
 }
 
+// Offset digit form (U16 / U32 / U64 columns on a window table): limb d_k of v is written (d_k - 32768) + 32768, so
+//   v G_i = sum_k (d_k - 32768) 2^(16k) G_i + c G_i,   c = 32768 sum_k 2^(16k) over the limbs of the kind.
+// Every d_k - 32768 is one signed digit in [-32768, 32767]: no carry, no top carry window, and a uniform limb costs one
+// reference instead of 1.5.  Over a column the second term sums to c S with S = the sum of the slice's SRS points, a
+// constant of the SRS that k_msm_finalize adds (msm_slice_sum).  Which form a column takes is decided on the device by
+// counting its references in both forms (k_msm_form_count): offset loses on columns of zeros and of values < 32768.
+template <int KIND>
+struct KindHasOffsetForm {
+    static constexpr bool value = KIND == COZK_SCALAR_U16 || KIND == COZK_SCALAR_U32 || KIND == COZK_SCALAR_U64;
+};
+static inline int kind_offset_slot(int kind) {  // index into cozk_bases::SliceSum::cS, -1 for kinds that are always plain
+    switch (kind) {
+        case COZK_SCALAR_U16: return 0;
+        case COZK_SCALAR_U32: return 1;
+        case COZK_SCALAR_U64: return 2;
+        default: return -1;
+    }
+}
+
 // Enumerate the non-zero signed digits of scalar i: calls f(window, bucket, negative).
 template <int KIND, class F>
-__device__ __forceinline__ void for_each_digit(const void* scalars, size_t i, F&& f) {
+__device__ __forceinline__ void for_each_digit(const void* scalars, size_t i, bool offset_form, F&& f) {
     uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     bool neg = ScalarKind<KIND>::load(scalars, i, w);
+    if constexpr (KindHasOffsetForm<KIND>::value) {
+        if (offset_form) {
+#pragma unroll
+            for (int k = 0; k < ScalarKind<KIND>::NWIN - 1; k++) {
+                uint32_t v = (w[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+                bool sub = v < 32768u;
+                f(k, sub ? 32768u - v : v - 32768u, sub);
+            }
+            return;
+        }
+    }
     uint32_t carry = 0;
 #pragma unroll
     for (int k = 0; k < ScalarKind<KIND>::NWIN; k++) {
@@ -145,7 +176,7 @@ __global__ void __launch_bounds__(TPB) k_msm_hist(const void* scalars, size_t n,
     size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
     bool inr = i < n;
     size_t ii = inr ? i : 0;
-    for_each_digit<KIND>(scalars, ii, [&](int k, uint32_t mag, bool) {
+    for_each_digit<KIND>(scalars, ii, false, [&](int k, uint32_t mag, bool) {
         bool act = inr && mag != 0;
         uint32_t key = (grouped ? (uint32_t)k * NB : 0u) + (mag - 1u);
         agg_atomic_add(hist, act ? key : 0u, act);
@@ -158,7 +189,7 @@ __global__ void __launch_bounds__(TPB) k_msm_scatter(const void* scalars, size_t
     size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
     bool inr = i < n;
     size_t ii = inr ? i : 0;
-    for_each_digit<KIND>(scalars, ii, [&](int k, uint32_t mag, bool negative) {
+    for_each_digit<KIND>(scalars, ii, false, [&](int k, uint32_t mag, bool negative) {
         bool act = inr && mag != 0;
         uint32_t key = (grouped ? (uint32_t)k * NB : 0u) + (mag - 1u);
         uint32_t pos = agg_atomic_add(cursor, act ? key : 0u, act);
@@ -185,15 +216,62 @@ struct MsmPolyDesc {
     uint32_t pad;
 };
 static constexpr int LTPB = 1024;  // launch bound of the LDS-histogram kernels; the launch width is chosen in msm_sort
+// launch width and workgroups-per-polynomial cap of a sort that runs alone (msm_sort)
+static constexpr int MSM_WIDE_LTPB = 1024;
+static constexpr int MSM_WIDE_WGS = 64;
+// what travels between the host and one launch set through pinned memory: the descriptors on their way in, the fullest
+// bucket and the reference total on their way out (read after the batch's final synchronisation)
+struct MsmSetPin {
+    uint32_t fullest, total, pad[14];
+    MsmPolyDesc descs[64];
+};
+
+// the digit form of column `group` (0 plain, 1 offset; form == nullptr: the whole batch is plain); kinds without an
+// offset form never read the word
+template <int KIND>
+static __device__ __forceinline__ bool column_form(const uint32_t* __restrict__ form, uint32_t group) {
+    if constexpr (KindHasOffsetForm<KIND>::value) return form && form[group] != 0;
+    return false;
+}
+
+// counts[2 g] / counts[2 g + 1] += the references column g places in plain / offset form
+template <int KIND>
+__global__ void __launch_bounds__(256) k_msm_form_count(const MsmPolyDesc* __restrict__ descs, uint32_t* __restrict__ counts) {
+    const MsmPolyDesc d = descs[blockIdx.y];
+    uint32_t cp = 0, co = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.n; i += (size_t)gridDim.x * blockDim.x) {
+        for_each_digit<KIND>(d.scalars, i, false, [&](int, uint32_t mag, bool) { cp += mag != 0; });
+        for_each_digit<KIND>(d.scalars, i, true, [&](int, uint32_t mag, bool) { co += mag != 0; });
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        cp += (uint32_t)__shfl_down((int)cp, o);
+        co += (uint32_t)__shfl_down((int)co, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (cp) atomicAdd(&counts[2 * d.group], cp);
+        if (co) atomicAdd(&counts[2 * d.group + 1], co);
+    }
+}
+// form[p] = 1 where column p may take the offset form (bit p of `elig`) and it is forced or places strictly fewer references
+__global__ void k_msm_form_pick(const uint32_t* __restrict__ counts, uint32_t* __restrict__ form, uint32_t P, uint64_t elig, int force) {
+    uint32_t p = threadIdx.x;
+    if (p >= P) return;
+    bool e = (elig >> p) & 1ull;
+    form[p] = (e && (force || counts[2 * p + 1] < counts[2 * p])) ? 1u : 0u;
+}
+// stats[1] = the set's reference total, next to the fullest bucket in stats[0]: one copy takes both to the host
+__global__ void k_msm_set_total(const uint32_t* __restrict__ total, uint32_t* __restrict__ stats) { stats[1] = *total; }
 
 template <int KIND>
-__global__ void __launch_bounds__(LTPB) k_msm_hist_lds(const MsmPolyDesc* __restrict__ descs, uint32_t* __restrict__ hist) {
+__global__ void __launch_bounds__(LTPB) k_msm_hist_lds(const MsmPolyDesc* __restrict__ descs, uint32_t* __restrict__ hist,
+                                                    const uint32_t* __restrict__ form) {
     __shared__ uint32_t lh[NB];
     const MsmPolyDesc d = descs[blockIdx.y];
+    const bool offs = column_form<KIND>(form, d.group);
     for (uint32_t b = threadIdx.x; b < NB; b += blockDim.x) lh[b] = 0;
     __syncthreads();
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.n; i += (size_t)gridDim.x * blockDim.x) {
-        for_each_digit<KIND>(d.scalars, i, [&](int, uint32_t mag, bool) {
+        for_each_digit<KIND>(d.scalars, i, offs, [&](int, uint32_t mag, bool) {
             if (mag != 0) atomicAdd(&lh[mag - 1u], 1u);
         });
     }
@@ -207,13 +285,14 @@ __global__ void __launch_bounds__(LTPB) k_msm_hist_lds(const MsmPolyDesc* __rest
 
 template <int KIND>
 __global__ void __launch_bounds__(LTPB) k_msm_scatter_lds(const MsmPolyDesc* __restrict__ descs, uint32_t* __restrict__ cursor,
-                                                       uint32_t* __restrict__ refs, uint32_t table_n) {
+                                                       uint32_t* __restrict__ refs, uint32_t table_n, const uint32_t* __restrict__ form) {
     __shared__ uint32_t lh[NB];
     const MsmPolyDesc d = descs[blockIdx.y];
+    const bool offs = column_form<KIND>(form, d.group);
     for (uint32_t b = threadIdx.x; b < NB; b += blockDim.x) lh[b] = 0;
     __syncthreads();
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.n; i += (size_t)gridDim.x * blockDim.x) {
-        for_each_digit<KIND>(d.scalars, i, [&](int, uint32_t mag, bool) {
+        for_each_digit<KIND>(d.scalars, i, offs, [&](int, uint32_t mag, bool) {
             if (mag != 0) atomicAdd(&lh[mag - 1u], 1u);
         });
     }
@@ -225,7 +304,7 @@ __global__ void __launch_bounds__(LTPB) k_msm_scatter_lds(const MsmPolyDesc* __r
     }
     __syncthreads();
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.n; i += (size_t)gridDim.x * blockDim.x) {
-        for_each_digit<KIND>(d.scalars, i, [&](int k, uint32_t mag, bool negative) {
+        for_each_digit<KIND>(d.scalars, i, offs, [&](int k, uint32_t mag, bool negative) {
             if (mag != 0) {
                 uint32_t pos = atomicAdd(&lh[mag - 1u], 1u);
                 uint32_t ref = (uint32_t)k * table_n + d.base_off + (uint32_t)i;
@@ -360,7 +439,7 @@ __global__ void __launch_bounds__(1024) k_scan(const uint32_t* in, uint32_t nb, 
     if (tid == 1023) off[nb] = sh[1023];
 }
 
-// *out = max(*out, max_i v[i]): the fullest bucket of a launch set decides how many fold levels it needs
+// *out = max(*out, max_i v[i]): the fullest bucket of a launch set, checked against the plan's bound after the batch
 __global__ void __launch_bounds__(256) k_max_u32(const uint32_t* __restrict__ v, uint32_t n, uint32_t* __restrict__ out) {
     uint32_t m = 0;
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) m = max(m, v[i]);
@@ -588,12 +667,44 @@ static __device__ __forceinline__ g1_xyzz bucket_value(const g1_xyzz* items, con
     return G1::identity();
 }
 
-// dense copy of the per-bucket sums of one launch set into the batch-wide [group][bucket] array
+// dense copy of the per-bucket sums of one launch set into the batch-wide [group][bucket] array.  A bucket that still
+// holds more than one partial sum after the first fold level is heavy: its first partial sum is copied like any other
+// and the bucket is appended to `heavy` ([0] = count, [1..] = bucket ids) for k_msm_fold_heavy to overwrite.
 __global__ void __launch_bounds__(TPB) k_msm_gather_buckets(const g1_xyzz* __restrict__ items, const uint32_t* __restrict__ off,
-                                                         uint32_t nb, g1_xyzz* __restrict__ dense) {
+                                                         uint32_t nb, g1_xyzz* __restrict__ dense, uint32_t* __restrict__ heavy) {
     uint32_t b = blockIdx.x * TPB + threadIdx.x;
     if (b >= nb) return;
     xyzz_store(dense + b, bucket_value(items, off, b));
+    if (off[b + 1] - off[b] > 1u) heavy[1 + atomicAdd(heavy, 1u)] = b;
+}
+// One launch finishes every heavy bucket (the n/2 references of a 0/1 flag column's bucket 1, a plain u16 column's carry
+// digit, skewed field elements): a fixed grid walks the list, one workgroup per bucket; each thread adds a strided share of
+// the bucket's partial sums, an LDS tree adds the 256 shares.  The trip count of the list loop depends on blockIdx alone,
+// so every barrier is met by the whole workgroup.  A bucket of c partial sums costs c / 256 + min(8, log2 c) serial additions.
+static constexpr uint32_t HEAVY_GRID = 1024;
+__global__ void __launch_bounds__(TPB) k_msm_fold_heavy(const g1_xyzz* __restrict__ items, const uint32_t* __restrict__ off,
+                                                     const uint32_t* __restrict__ heavy, g1_xyzz* __restrict__ dense) {
+    __shared__ g1_xyzz sh[TPB];
+    const uint32_t nh = heavy[0], tid = threadIdx.x;
+    for (uint32_t h = blockIdx.x; h < nh; h += gridDim.x) {
+        const uint32_t b = heavy[1 + h];
+        const uint32_t begin = off[b], end = off[b + 1];
+        g1_xyzz acc = G1::identity();
+        for (uint32_t e = begin + tid; e < end; e += TPB) acc = G1::add(acc, xyzz_load(items + e));
+        sh[tid] = acc;
+        __syncthreads();
+        // the tree is as deep as the bucket needs: threads past its partial sums hold the identity (workgroup-uniform bound)
+        uint32_t width = 2;
+        while (width < TPB && width < end - begin) width <<= 1;
+        for (uint32_t s = width / 2; s > 0; s >>= 1) {
+            if (tid < s) {
+                acc = G1::add(acc, sh[tid + s]);
+                sh[tid] = acc;
+            }
+            __syncthreads();
+        }
+        if (tid == 0) xyzz_store(dense + b, acc);
+    }
 }
 
 __global__ void __launch_bounds__(TPB) k_msm_reduce_chunks(const g1_xyzz* __restrict__ dense, uint32_t ngroups,
@@ -640,7 +751,9 @@ __global__ void __launch_bounds__(TPB) k_msm_reduce_groups(const g1_xyzz* __rest
 }
 
 // Horner over the G window groups of each polynomial (G = 1 with a window table) + to_affine
-__global__ void k_msm_finalize(const g1_xyzz* __restrict__ grp, uint32_t G, uint32_t npoly, g1_affine* __restrict__ out) {
+// + the offset form's correction c S of the columns whose form word says offset (form == nullptr: no such column)
+__global__ void k_msm_finalize(const g1_xyzz* __restrict__ grp, uint32_t G, uint32_t npoly, g1_affine* __restrict__ out,
+                               const uint32_t* __restrict__ form, const g1_affine* __restrict__ corr) {
     uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= npoly) return;
     g1_xyzz acc = xyzz_load(grp + (size_t)p * G + (G - 1));
@@ -648,6 +761,7 @@ __global__ void k_msm_finalize(const g1_xyzz* __restrict__ grp, uint32_t G, uint
         for (int d = 0; d < 16; d++) acc = G1::dbl(acc);
         acc = G1::add(acc, xyzz_load(grp + (size_t)p * G + w));
     }
+    if (form && form[p]) acc = G1::add_mixed(acc, affine_load(corr + p));
     affine_store(out + p, G1::to_affine(acc));
 }
 
@@ -728,8 +842,16 @@ static void build_window_table(cozk_ctx* ctx, cozk_bases* b) {
 // The phases stress different units, so the sort of set k+1 hides behind the accumulation of set k.
 struct MsmSetPlan {
     uint32_t P = 0, G = 1, nb = 0, L0 = 8;
+    uint32_t fold_levels = 1;  // fold levels queued before the heavy-bucket launch
     uint64_t M = 0, bound = 0, maxseg0 = 0;
     bool pre = false;
+    // filled in by msm_batch
+    MsmSetPin* pin = nullptr;     // this set's pinned slot
+    uint32_t* form = nullptr;     // device: digit form word per polynomial of the set (nullptr: every column plain)
+    uint32_t* counts = nullptr;   // device: reference counts in both forms, two words per polynomial
+    uint64_t elig = 0;            // bit p: polynomial p may take the offset form
+    bool force_offset = false;    // COZK_MSM_DIGIT_FORM=offset
+    bool alone = false;           // nothing runs beside this set's sort
 };
 
 static MsmSetPlan msm_plan(const cozk_bases* bases, const size_t* offsets, const size_t* ns, const int* kinds, size_t P) {
@@ -754,6 +876,19 @@ static MsmSetPlan msm_plan(const cozk_bases* bases, const size_t* offsets, const
     if (L0 > 127) L0 = 127;  // < SEGKEYS; measured with length-ordered segments: 127 beats 64 by 2 ms per proof (fewer partial sums)
     pl.L0 = L0;
     pl.maxseg0 = pl.M / L0 + pl.nb;
+    // Fold levels, sized from the plan and not from the data: enough 8-long levels for the buckets of the polynomial
+    // with the most references per bucket if its digits are uniform (n nwin / 2^15 with the table, n / 2^15 per window
+    // group without; + 25 % and one segment for the Poisson spread: 2^20 field elements give 512 per bucket, 5 segments
+    // of <= 127, one level; 2^22 give 2048, 17 segments, two levels; 2^24 three).  Buckets that are fuller than that
+    // (flag columns, carry digits, skewed scalars) are left to k_msm_fold_heavy.
+    uint64_t per = 0;
+    for (size_t p = 0; p < P; p++) {
+        uint64_t m = ((uint64_t)ns[p] * (pl.pre ? kind_nwin(kinds[p]) : 1) + NB - 1) / NB;
+        if (m > per) per = m;
+    }
+    uint64_t segs = (per * 5 + 4 * L0 - 1) / (4 * L0) + 1;
+    pl.fold_levels = 1;
+    while ((segs = (segs + 7) / 8) > 1) pl.fold_levels++;
     return pl;
 }
 
@@ -776,7 +911,7 @@ static void msm_sort(cozk_ctx* ctx, hipStream_t st, MsmSortWs& sw, const MsmSetP
                      const size_t* ns, const void* const* scalars, const int* kinds) {
     const uint32_t nb = pl.nb, G = pl.G;
     const size_t P = pl.P;
-    sw.hist.reserve((size_t)(nb + 2) * 4);
+    sw.hist.reserve((size_t)(nb + 3) * 4);
     sw.off0.reserve((size_t)(nb + 1) * 4);
     sw.offA.reserve((size_t)(nb + 1) * 4);
     sw.refs.reserve((size_t)pl.M * 4);
@@ -787,21 +922,19 @@ static void msm_sort(cozk_ctx* ctx, hipStream_t st, MsmSortWs& sw, const MsmSetP
     sw.ptrs.reserve((size_t)nscan_blocks * 4 + P * sizeof(MsmPolyDesc) + 64);
     uint32_t* bsums = sw.ptrs.as<uint32_t>();
     MsmPolyDesc* d_descs = reinterpret_cast<MsmPolyDesc*>(((uintptr_t)(bsums + nscan_blocks) + 15) & ~(uintptr_t)15);
-    HIP_TRY(hipMemsetAsync(hist, 0, (size_t)(nb + 2) * 4, st));
-    uint32_t* d_maxcnt = hist + nb + 1;  // not touched by the scans (they own hist[0..nb])
-    if (!sw.max_pinned) HIP_TRY(hipHostMalloc((void**)&sw.max_pinned, 64 + 64 * sizeof(MsmPolyDesc), hipHostMallocDefault));
-    if (!sw.max_event) HIP_TRY(hipEventCreateWithFlags(&sw.max_event, hipEventDisableTiming));
-    // after the histogram: fullest bucket -> pinned host word, behind an event the host waits on only when it
-    // sizes the fold levels (by then the GPU is inside the long gather pass, so the queue never drains)
-    auto read_back_max = [&] {
-        k_max_u32<<<std::min<uint32_t>(cdiv(nb, 256), 1024u), 256, 0, st>>>(hist, nb, d_maxcnt);
-        HIP_TRY(hipMemcpyAsync(sw.max_pinned, d_maxcnt, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipEventRecord(sw.max_event, st));
+    HIP_TRY(hipMemsetAsync(hist, 0, (size_t)(nb + 3) * 4, st));
+    uint32_t* d_stats = hist + nb + 1;  // [0] fullest bucket, [1] reference total; not touched by the scans (they own hist[0..nb])
+    // the fullest bucket (after the histogram) and the reference total (after the scan) go to the set's pinned slot in one
+    // copy; the host looks at them after the batch's final synchronisation
+    auto fullest_bucket = [&] { k_max_u32<<<std::min<uint32_t>(cdiv(nb, 256), 1024u), 256, 0, st>>>(hist, nb, d_stats); };
+    auto read_back_stats = [&] {
+        k_msm_set_total<<<1, 1, 0, st>>>(off0 + nb, d_stats);
+        HIP_TRY(hipMemcpyAsync(&pl.pin->fullest, d_stats, 8, hipMemcpyDeviceToHost, st));
     };
     if (pl.pre) {
         // LDS-privatised counting sort: one launch per scalar kind, grid = (workgroups per polynomial, polynomials).
         // The descriptors travel through pinned memory owned by the workspace (no host sync here).
-        MsmPolyDesc* h_descs = reinterpret_cast<MsmPolyDesc*>(reinterpret_cast<char*>(sw.max_pinned) + 64);
+        MsmPolyDesc* h_descs = pl.pin->descs;
         COZK_REQUIRE(P <= 64, "msm: too many polynomials in one launch set");
         uint32_t nd = 0;
         std::vector<std::pair<int, std::pair<uint32_t, uint32_t>>> runs;  // kind -> (first desc, count)
@@ -818,20 +951,38 @@ static void msm_sort(cozk_ctx* ctx, hipStream_t st, MsmSortWs& sw, const MsmSetP
         HIP_TRY(hipMemcpyAsync(d_descs, h_descs, nd * sizeof(MsmPolyDesc), hipMemcpyHostToDevice, st));
         // 256-thread workgroups (one wave per SIMD, 128 KiB of LDS each): narrow enough to slip into the CU slots that free
         // up under the register-heavy gather kernel of the previous launch set, so the sort really runs beside it (wider
-        // workgroups wait for the gather's grid to drain: measured 127.8 -> 123.5 ms per proof at 2^20, same box)
-        static const int ltpb = getenv("COZK_MSM_LTPB") ? atoi(getenv("COZK_MSM_LTPB")) : 256;
-        static const uint32_t wgs_max = getenv("COZK_MSM_WGS") ? (uint32_t)atoi(getenv("COZK_MSM_WGS")) : 64u;
+        // workgroups wait for the gather's grid to drain: measured 127.8 -> 123.5 ms per proof at 2^20, same box).
+        // A set with nothing beside it (the first of a batch, a single set, serial batches) takes the wide shape instead
+        // (measured at 2^20: 1024 x 64, 1024 x 32, 1024 x 16, 512 x 64 and 512 x 32 all within 0.2 ms of each other and
+        // 0.3-0.4 ms per commit ahead of 256 x 64; the first set of the bench's commit is a small one, see DESIGN):
+        // COZK_MSM_LTPB / COZK_MSM_WGS override both shapes.
+        static const int ltpb_env = getenv("COZK_MSM_LTPB") ? atoi(getenv("COZK_MSM_LTPB")) : 0;
+        static const int wgs_env = getenv("COZK_MSM_WGS") ? atoi(getenv("COZK_MSM_WGS")) : 0;
+        const int ltpb = ltpb_env ? ltpb_env : (pl.alone ? MSM_WIDE_LTPB : 256);
+        const uint32_t wgs_max = (uint32_t)(wgs_env ? wgs_env : (pl.alone ? MSM_WIDE_WGS : 64));
         COZK_REQUIRE(ltpb >= 64 && ltpb <= LTPB && ltpb % 64 == 0, "COZK_MSM_LTPB out of range");
         COZK_REQUIRE(wgs_max >= 1 && wgs_max <= 1024, "COZK_MSM_WGS out of range (1..1024)");
         uint32_t wgs = (uint32_t)((max_n + 4095) / 4096);  // >= 4096 scalars per workgroup (measured: 64 beats 16 workgroups 2x)
         if (wgs < 1) wgs = 1;
         if (wgs > wgs_max) wgs = wgs_max;
+        // digit form of the U16 / U32 / U64 columns: count both forms (one extra read of those columns), offset where it
+        // places strictly fewer references; forced offset needs no count.  Plain leaves the zeroed words alone.
+        if (pl.elig) {
+            if (!pl.force_offset)
+                for (auto& r : runs)
+                    if (kind_offset_slot(r.first) >= 0) {
+                        dim3 grid(std::min<uint32_t>(cdiv(max_n, 4096), 64u), r.second.second);
+                        KIND_DISPATCH(r.first, (k_msm_form_count<K><<<grid, 256, 0, st>>>(d_descs + r.second.first, pl.counts)));
+                    }
+            k_msm_form_pick<<<1, 64, 0, st>>>(pl.counts, pl.form, pl.P, pl.elig, pl.force_offset ? 1 : 0);
+        }
         for (auto& r : runs) {
             dim3 grid(wgs, r.second.second);
-            KIND_DISPATCH(r.first, (k_msm_hist_lds<K><<<grid, ltpb, 0, st>>>(d_descs + r.second.first, hist)));
+            KIND_DISPATCH(r.first, (k_msm_hist_lds<K><<<grid, ltpb, 0, st>>>(d_descs + r.second.first, hist, pl.form)));
         }
-        read_back_max();
+        fullest_bucket();
         msm_scan(st, bsums, nb, false, hist, 1, off0, hist);  // hist doubles as the scatter cursor after the scan
+        read_back_stats();
         for (auto& r : runs) {
             dim3 grid(wgs, r.second.second);
             // algorithmic bytes of the placement: every scalar read once + one 4-byte reference written per 16-bit window
@@ -842,15 +993,16 @@ static void msm_sort(cozk_ctx* ctx, hipStream_t st, MsmSortWs& sw, const MsmSetP
                 alg += (uint64_t)d.n * (sb + 4ull * ((sb * 8 + 15) / 16));
             }
             ProfScope prof(ctx, COZK_PROF_MSM_SCATTER, alg, st);
-            KIND_DISPATCH(r.first, (k_msm_scatter_lds<K><<<grid, ltpb, 0, st>>>(d_descs + r.second.first, hist, refs, (uint32_t)bases->n)));
+            KIND_DISPATCH(r.first, (k_msm_scatter_lds<K><<<grid, ltpb, 0, st>>>(d_descs + r.second.first, hist, refs, (uint32_t)bases->n, pl.form)));
         }
     } else {
         for (size_t p = 0; p < P; p++) {
             uint32_t* h = hist + (size_t)p * G * NB;
             if (ns[p]) KIND_DISPATCH(kinds[p], (k_msm_hist<K><<<cdiv(ns[p], TPB), TPB, 0, st>>>(scalars[p], ns[p], h, 1)));
         }
-        read_back_max();
+        fullest_bucket();
         msm_scan(st, bsums, nb, false, hist, 1, off0, hist);
+        read_back_stats();
         for (size_t p = 0; p < P; p++) {
             uint32_t* cur = hist + (size_t)p * G * NB;
             if (ns[p])
@@ -868,9 +1020,11 @@ static void msm_accumulate(cozk_ctx* ctx, MsmSortWs& sw, const MsmSetPlan& pl, c
     MsmWorkspace& ws = ctx->msm_ws;
     hipStream_t st = ctx->stream;
     const uint32_t nb = pl.nb, L0 = pl.L0;
-    // upper levels fold <= L1 partial sums per lane.  The chain is serial (a full XYZZ addition per step, ~25 us
-    // when a wave runs alone), so it is kept short: 64-long chains made the fold of the one heavy bucket of a
-    // u16 / u32 / flag column (the carry digit: n/2 references) cost as much as its whole gather pass.
+    // Upper levels fold <= L1 partial sums per lane; the chain is serial (a full XYZZ addition per step), so it is kept
+    // short.  pl.fold_levels of them (msm_plan: what uniform digits need, one at 2^20) finish every ordinary bucket.
+    // Whatever still holds more than one partial sum after them -- the one bucket of a 0/1 flag column, a plain u16 /
+    // u32 column's carry digit -- is finished by k_msm_fold_heavy in one launch.  The schedule does not depend on the
+    // data, so the host never waits for the histogram in the middle of a set.
     const uint32_t L1 = 8;
     const uint64_t maxseg0 = pl.maxseg0;
     // segment counts obey x_{k+1} = x_k / L1 + nb <= max(x_0, 2 nb): size both ping-pong buffers for that
@@ -879,6 +1033,7 @@ static void msm_accumulate(cozk_ctx* ctx, MsmSortWs& sw, const MsmSetPlan& pl, c
     ws.partB.reserve((size_t)maxpart * sizeof(g1_xyzz));
     ws.offB.reserve((size_t)(nb + 1) * 4);
     ws.offC.reserve((size_t)(nb + 1) * 4);
+    ws.heavy.reserve((size_t)(nb + 1) * 4);
     ws.ptrs.reserve((size_t)((nb + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK) * 4 + 64);
     uint32_t* refs = sw.refs.as<uint32_t>();
     uint32_t* off0 = sw.off0.as<uint32_t>();
@@ -920,14 +1075,11 @@ static void msm_accumulate(cozk_ctx* ctx, MsmSortWs& sw, const MsmSetPlan& pl, c
         HIP_TRY(hipEventRecord(e1, st));
         ctx->prof_events.push_back({e0, e1});
         ctx->prof_launches += 1;
-        ctx->prof_units += pl.M;
+        // prof_units (point additions) takes the set's real reference total once msm_batch has it
         for (size_t p = 0; p < pl.P; p++) ctx->prof_alg_bytes += (uint64_t)ns[p] * (64 + scalar_kind_bytes(kinds[p]));
     }
-    // further levels until the fullest bucket is down to one value
-    HIP_TRY(hipEventSynchronize(sw.max_event));
-    uint64_t fullest = *(volatile uint32_t*)sw.max_pinned;
-    COZK_REQUIRE(fullest <= pl.bound, "msm: histogram larger than the reference count");
-    uint64_t cnt = (fullest + L0 - 1) / L0;
+    uint32_t* heavy = ws.heavy.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(heavy, 0, 4, st));
     uint64_t maxseg = maxseg0;
     g1_xyzz* cur_items = ws.partA.as<g1_xyzz>();
     g1_xyzz* nxt_items = ws.partB.as<g1_xyzz>();
@@ -935,7 +1087,7 @@ static void msm_accumulate(cozk_ctx* ctx, MsmSortWs& sw, const MsmSetPlan& pl, c
     uint32_t* cur_off = offA;
     uint32_t* nxt_off = ws.offB.as<uint32_t>();
     uint32_t* spare_off = ws.offC.as<uint32_t>();
-    while (cnt > 1) {
+    for (uint32_t level = 0; level < pl.fold_levels; level++) {
         uint64_t nseg = maxseg / L1 + nb;
         msm_scan(st, ws.ptrs.as<uint32_t>(), nb, true, cur_off, L1, nxt_off, nullptr);
         const uint32_t nblkN = cdiv(nseg, TPB);
@@ -946,9 +1098,9 @@ static void msm_accumulate(cozk_ctx* ctx, MsmSortWs& sw, const MsmSetPlan& pl, c
         cur_off = nxt_off;
         nxt_off = (done == offA) ? spare_off : done;
         maxseg = nseg;
-        cnt = (cnt + L1 - 1) / L1;
     }
-    k_msm_gather_buckets<<<cdiv(nb, TPB), TPB, 0, st>>>(cur_items, cur_off, nb, dense_out);
+    k_msm_gather_buckets<<<cdiv(nb, TPB), TPB, 0, st>>>(cur_items, cur_off, nb, dense_out, heavy);
+    k_msm_fold_heavy<<<HEAVY_GRID, TPB, 0, st>>>(cur_items, cur_off, heavy, dense_out);
     HIP_TRY(hipGetLastError());
 }
 
@@ -975,6 +1127,69 @@ static g1_affine abi_to_affine(const uint64_t xy[8], int inf) {
     return a;
 }
 
+void msm_batch(cozk_ctx* ctx, const cozk_bases* bases, const size_t* offsets, const size_t* ns, const void* const* scalars,
+               const int* kinds, size_t k, uint64_t* out_xy, int* out_inf);
+
+// COZK_MSM_DIGIT_FORM = auto (default) | plain | offset; read at every call so that one process can compare the forms
+enum { MSM_FORM_AUTO = 0, MSM_FORM_PLAIN = 1, MSM_FORM_OFFSET = 2 };
+static int msm_digit_form_mode() {
+    const char* e = getenv("COZK_MSM_DIGIT_FORM");
+    if (!e || !*e || !strcmp(e, "auto")) return MSM_FORM_AUTO;
+    if (!strcmp(e, "plain")) return MSM_FORM_PLAIN;
+    if (!strcmp(e, "offset")) return MSM_FORM_OFFSET;
+    throw CozkError(COZK_ERR_INVALID_ARG, "COZK_MSM_DIGIT_FORM must be auto, plain or offset");
+}
+
+// c S for the slice [off, off + n) of `bases` and the three kinds with an offset form (kind_offset_slot), from the
+// handle's cache.  The first request computes S with the MSM itself on a constant all-ones U8 column (always plain, so
+// this does not come back here) and multiplies on the host: once per SRS slice, not per proof.  In `auto` mode the host
+// cannot know which form the device will pick, so S is computed for every slice that carries a U16 / U32 / U64 column.
+// A prover commits to a handful of slices of its SRS (whole, halves, chunk views), hence a short list searched
+// linearly; a caller whose slice changes from call to call gets the oldest entry replaced once the list holds
+// MSM_SLICE_SUMS entries and pays one one-column MSM per new slice.  The lock covers the list only, not the MSM: two
+// threads that miss on the same slice both compute it and the second finds it present.
+static constexpr size_t MSM_SLICE_SUMS = 32;
+static cozk_bases::SliceSum msm_slice_sum(cozk_ctx* ctx, const cozk_bases* bases, size_t off, size_t n) {
+    cozk_bases* b = const_cast<cozk_bases*>(bases);
+    {
+        std::lock_guard<std::mutex> lk(b->sums_mu);
+        for (const auto& e : b->sums)
+            if (e.off == off && e.n == n) return e;
+    }
+    void* ones = ctx_dev_alloc(ctx, n);
+    uint64_t xy[8];
+    int inf = 0;
+    try {
+        HIP_TRY(hipMemsetAsync(ones, 1, n, ctx->stream));
+        const void* p = ones;
+        int kind = COZK_SCALAR_U8;
+        msm_batch(ctx, bases, &off, &n, &p, &kind, 1, xy, &inf);  // ends with a stream synchronisation
+    } catch (...) {
+        ctx_dev_free(ctx, ones);
+        throw;
+    }
+    ctx_dev_free(ctx, ones);
+    const g1_affine S = abi_to_affine(xy, inf);
+    cozk_bases::SliceSum e;
+    e.off = off;
+    e.n = n;
+    const uint64_t c[3] = {0x8000ull, 0x80008000ull, 0x8000800080008000ull};
+    for (int j = 0; j < 3; j++) {
+        g1_xyzz acc = G1::identity();
+        for (int bit = 63; bit >= 0; bit--) {
+            acc = G1::dbl(acc);
+            if ((c[j] >> bit) & 1ull) acc = G1::add_mixed(acc, S);
+        }
+        e.cS[j] = G1::to_affine(acc);
+    }
+    std::lock_guard<std::mutex> lk(b->sums_mu);
+    for (const auto& have : b->sums)
+        if (have.off == off && have.n == n) return have;
+    if (b->sums.size() >= MSM_SLICE_SUMS) b->sums.erase(b->sums.begin());
+    b->sums.push_back(e);
+    return e;
+}
+
 // k MSMs with per-polynomial base slices; launch sets are cut so that one set holds at most 2^28 .. 2^30 point
 // references (1 GiB of refs) and at most 64 (window table) / 4 (16 window groups) polynomials
 void msm_batch(cozk_ctx* ctx, const cozk_bases* bases, const size_t* offsets, const size_t* ns, const void* const* scalars,
@@ -986,8 +1201,53 @@ void msm_batch(cozk_ctx* ctx, const cozk_bases* bases, const size_t* offsets, co
     // the bucket-reduction tail (running sums, Horner, to-affine) is latency-bound, so it runs ONCE over
     // the dense bucket sums of up to `tail_cap` polynomials instead of once per launch set
     const size_t tail_cap = 256 / G;
+    // digit forms: which columns may take the offset form, and their corrections c S (computed here, before this
+    // batch touches the workspace, because the first use of a slice runs an MSM of its own)
+    const int form_mode = msm_digit_form_mode();
+    std::vector<uint8_t> elig(k, 0);
+    std::vector<g1_affine> corr_h;
+    bool any_elig = false;
+    if (G == 1 && form_mode != MSM_FORM_PLAIN) {
+        for (size_t p = 0; p < k; p++) {
+            const int slot = kind_offset_slot(kinds[p]);
+            if (slot < 0 || ns[p] == 0) continue;
+            COZK_REQUIRE(offsets[p] + ns[p] <= bases->n, "msm: base slice out of range");
+            if (!any_elig) corr_h.assign(k, g1_affine{Fq::zero(), Fq::zero()});
+            any_elig = true;
+            elig[p] = 1;
+            if (p > 0 && elig[p - 1] && kinds[p - 1] == kinds[p] && offsets[p - 1] == offsets[p] && ns[p - 1] == ns[p]) corr_h[p] = corr_h[p - 1];
+            else corr_h[p] = msm_slice_sum(ctx, bases, offsets[p], ns[p]).cS[slot];
+        }
+    }
     ws.out.reserve(k * sizeof(g1_affine));
     g1_affine* d_out = ws.out.as<g1_affine>();
+    // pinned staging: one slot per launch set (at most k sets), then k corrections.  Every earlier batch ended with a
+    // stream synchronisation, so nothing still reads the old block when it is regrown here.
+    const size_t pin_need = k * (sizeof(MsmSetPin) + sizeof(g1_affine));
+    if (pin_need > ws.pin_cap) {
+        if (ws.pin) (void)hipHostFree(ws.pin);
+        ws.pin = nullptr;
+        ws.pin_cap = 0;
+        HIP_TRY(hipHostMalloc(&ws.pin, pin_need, hipHostMallocDefault));
+        ws.pin_cap = pin_need;
+    }
+    MsmSetPin* pins = reinterpret_cast<MsmSetPin*>(ws.pin);
+    size_t pins_used = 0;
+    std::vector<uint64_t> pin_bound;  // per used slot: the most references one polynomial of the set can place
+    // form[k] then counts[2 k], zeroed: plain unless a sort says otherwise
+    uint32_t *d_form = nullptr, *d_counts = nullptr;
+    g1_affine* d_corr = nullptr;
+    if (any_elig) {
+        ws.form.reserve(3 * k * 4);
+        d_form = ws.form.as<uint32_t>();
+        d_counts = d_form + k;
+        HIP_TRY(hipMemsetAsync(d_form, 0, 3 * k * 4, st));
+        ws.corr.reserve(k * sizeof(g1_affine));
+        d_corr = ws.corr.as<g1_affine>();
+        g1_affine* pc = reinterpret_cast<g1_affine*>(pins + k);
+        memcpy(pc, corr_h.data(), k * sizeof(g1_affine));
+        HIP_TRY(hipMemcpyAsync(d_corr, pc, k * sizeof(g1_affine), hipMemcpyHostToDevice, st));
+    }
     for (size_t t0 = 0; t0 < k; t0 += tail_cap) {
         size_t kt = k - t0 < tail_cap ? k - t0 : tail_cap;
         const uint32_t ngroups = (uint32_t)kt * G;
@@ -1074,6 +1334,17 @@ void msm_batch(cozk_ctx* ctx, const cozk_bases* bases, const size_t* offsets, co
             const SetRange& r = sets[i];
             plans[i] = msm_plan(bases, offsets + t0 + r.s, ns + t0 + r.s, kinds + t0 + r.s, r.P);
             if (plans[i].M == 0) return;
+            MsmSetPlan& pl = plans[i];
+            pl.pin = pins + pins_used++;
+            pl.pin->fullest = 0;
+            pl.pin->total = 0;
+            pin_bound.push_back(pl.bound);
+            pl.form = any_elig ? d_form + t0 + r.s : nullptr;
+            pl.counts = any_elig ? d_counts + 2 * (t0 + r.s) : nullptr;
+            for (size_t p = 0; p < r.P; p++)
+                if (elig[t0 + r.s + p]) pl.elig |= 1ull << p;
+            pl.force_offset = form_mode == MSM_FORM_OFFSET;
+            pl.alone = (i == 0 && t0 == 0) || side == st;
             MsmSortWs& sw = ws.sort[i & 1];
             if (i >= 2 && side != st) HIP_TRY(hipStreamWaitEvent(side, sw.consumed, 0));  // its previous user has finished reading it
             msm_sort(ctx, side, sw, plans[i], bases, offsets + t0 + r.s, ns + t0 + r.s, scalars + t0 + r.s, kinds + t0 + r.s);
@@ -1096,12 +1367,18 @@ void msm_batch(cozk_ctx* ctx, const cozk_bases* bases, const size_t* offsets, co
         }
         k_msm_reduce_chunks<<<cdiv((uint64_t)ngroups * (NB / CH), TPB), TPB, 0, st>>>(dense, ngroups, ws.chunk.as<g1_xyzz>());
         k_msm_reduce_groups<<<ngroups, TPB, 0, st>>>(ws.chunk.as<g1_xyzz>(), ws.grp.as<g1_xyzz>());
-        k_msm_finalize<<<cdiv(kt, 64), 64, 0, st>>>(ws.grp.as<g1_xyzz>(), G, (uint32_t)kt, d_out + t0);
+        k_msm_finalize<<<cdiv(kt, 64), 64, 0, st>>>(ws.grp.as<g1_xyzz>(), G, (uint32_t)kt, d_out + t0, d_form ? d_form + t0 : nullptr,
+                                                   d_corr ? d_corr + t0 : nullptr);
         HIP_TRY(hipGetLastError());
     }
     g1_affine* h = reinterpret_cast<g1_affine*>(ctx_pinned(ctx, k * sizeof(g1_affine)));
     HIP_TRY(hipMemcpyAsync(h, d_out, k * sizeof(g1_affine), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    // every set's read-back is visible now: no bucket may hold more than one polynomial can place
+    for (size_t i = 0; i < pins_used; i++) {
+        COZK_REQUIRE(pins[i].fullest <= pin_bound[i], "msm: histogram larger than the reference count");
+        if (ctx->prof_enabled) ctx->prof_units += pins[i].total;
+    }
     for (size_t i = 0; i < k; i++) affine_to_abi(h[i], out_xy + 8 * i, out_inf ? out_inf + i : nullptr);
 }
 
