@@ -19,6 +19,10 @@ MODE_PLAIN, MODE_REP3 = 1, 2
 LAYER_GROUP_MAX = 32
 SPARTAN_GROUP_FIRST, SPARTAN_GROUP_SECOND = 1, 2
 OP_ADD, OP_SUB, OP_MUL = 0, 1, 2
+# collation forms of the primary sumcheck's instruction table (include/cozk.h COZK_G_*)
+(G_CONCAT, G_PRODUCT, G_LTU, G_NOT_PRODUCT, G_NOT_LTU, G_SLT, G_NOT_SLT, G_LTE, G_NOT_FIRST, G_DIV0, G_UNSIGNED_REM, G_SIGNED_REM,
+ G_ZERO) = range(13)
+PRIMARY_MAX_MEMS = 20
 
 
 PRF_KEY_BYTES = 32

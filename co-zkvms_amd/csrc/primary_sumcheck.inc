@@ -781,7 +781,10 @@ int cozk_primary_round_begin(cozk_ctx* ctx, cozk_primary* p, const uint64_t* r, 
         COZK_REQUIRE(ctx && p && n_items && n_levels, "primary_round_begin: bad argument");
         const int NC = p->mode == COZK_MODE_REP3 ? 2 : 1;
         if (r) {
+            // every check before the bind: a refused call leaves the primary as it was.  With two entries left the last
+            // challenge belongs to cozk_primary_final_evals, a bind here would leave nothing to sum
             COZK_REQUIRE(p->n >= 2, "primary_round_begin: fully bound");
+            COZK_REQUIRE(p->n >= 4, "primary_round_begin: nothing left to sum");
             const int dst = 1 - p->cur;
             const size_t n_out = p->n / 2;
             dim3 g(grid_for(n_out), (unsigned)p->T);

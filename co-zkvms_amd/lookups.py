@@ -1,7 +1,7 @@
 """Instruction-lookups harness over the C ABI (`cozk_lookups_*`): SURVEY 8(f)1 restated synthetically -- the toggled /
 sparse batched grand product of Lasso's read / write memory checking (co-jolt/src/subprotocols/sparse_grand_product.rs)
 on the GPU(s), coordinator + verifier on the calling thread -- and thin wrappers of the toggle-layer entry points
-(`cozk_toggle_*`, `cozk_toggle_group_*`) for the kernel-level parity tests."""
+(`cozk_toggle_*`, `cozk_toggle_group_*`) and of the primary sumcheck's (`cozk_primary_*`) for the kernel-level parity tests."""
 import ctypes
 
 import numpy as np
@@ -26,7 +26,8 @@ class LookupsResult(ctypes.Structure):
 LOOKUPS_SYMBOLS = ["cozk_lookups_create", "cozk_lookups_error", "cozk_lookups_destroy", "cozk_lookups_prove", "cozk_lookups_proof_bytes",
                    "cozk_toggle_create", "cozk_toggle_free", "cozk_toggle_batch", "cozk_toggle_len", "cozk_toggle_layer_output", "cozk_toggle_bind",
                    "cozk_toggle_round", "cozk_toggle_final_claims", "cozk_toggle_download", "cozk_lookups_get_sparse_stats",
-                   "cozk_lookups_reset_sparse_stats"]
+                   "cozk_lookups_reset_sparse_stats", "cozk_primary_create", "cozk_primary_free", "cozk_primary_degree", "cozk_primary_len",
+                   "cozk_primary_round_begin", "cozk_primary_level", "cozk_primary_round_finish", "cozk_primary_final_evals"]
 
 _vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
 
@@ -51,6 +52,22 @@ def _decl():
     l.cozk_toggle_final_claims.argtypes = [_vp, _vp, _vp, _vp, _vp]
     l.cozk_toggle_download.restype = _i
     l.cozk_toggle_download.argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]
+    l.cozk_primary_create.restype = _i
+    l.cozk_primary_create.argtypes = [_vp, _i, _i, _vp, _sz, _vp, _vp, _sz, _vp, _vp, ctypes.POINTER(_vp)]
+    l.cozk_primary_free.restype = _i
+    l.cozk_primary_free.argtypes = [_vp]
+    l.cozk_primary_degree.restype = _i
+    l.cozk_primary_degree.argtypes = [_vp]
+    l.cozk_primary_len.restype = _sz
+    l.cozk_primary_len.argtypes = [_vp]
+    l.cozk_primary_round_begin.restype = _i
+    l.cozk_primary_round_begin.argtypes = [_vp, _vp, _vp, ctypes.POINTER(_sz), ctypes.POINTER(_i)]
+    l.cozk_primary_level.restype = _i
+    l.cozk_primary_level.argtypes = [_vp, _vp, _i, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_sz)]
+    l.cozk_primary_round_finish.restype = _i
+    l.cozk_primary_round_finish.argtypes = [_vp, _vp, _vp]
+    l.cozk_primary_final_evals.restype = _i
+    l.cozk_primary_final_evals.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp]
     return l
 
 
@@ -162,6 +179,94 @@ class ToggleLayer:
     def free(self):
         if getattr(self, "h", None):
             self._l.cozk_toggle_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class PrimaryInstr(ctypes.Structure):
+    """cozk_primary_instr: one row of the instruction table -- a collation form (L.G_*) over indices into the E polynomials"""
+    _fields_ = [("form", ctypes.c_int), ("n_mems", ctypes.c_int), ("mems", ctypes.c_int * L.PRIMARY_MAX_MEMS), ("bits", ctypes.c_int)]
+
+    @classmethod
+    def of(cls, form, mems, bits=0):
+        mems = list(mems)
+        row = cls(form=form, n_mems=len(mems), bits=bits)
+        for t, m in enumerate(mems[:L.PRIMARY_MAX_MEMS]):
+            row.mems[t] = m
+        return row
+
+
+class PrimarySumcheck:
+    """Lasso's primary sumcheck of the instruction lookups on the device (`cozk_primary`): one party's state and the three steps
+    of a round.  The exchange between the levels and the protocol around the rounds are the caller's"""
+
+    def __init__(self, ctx, h, mode, n_instr, n_mem):
+        self._l = _decl()
+        self.ctx, self.h, self.mode, self.n_instr, self.n_mem = ctx, h, mode, n_instr, n_mem
+
+    @classmethod
+    def create(cls, ctx, mode, party, instrs, flags, E, outputs, eq):
+        """`instrs` = PrimaryInstr rows, `flags` = one Vec per row (0/1 U8 columns, or FR vectors that are already bound), `E` =
+        the Rep3DensePolynomials the rows index, `outputs` = lookup_outputs, `eq` = an FR Vec; all of `mode` and one length.
+        Everything is copied: the arguments stay untouched and need not outlive the object"""
+        l = _decl()
+        rows = (PrimaryInstr * max(len(instrs), 1))(*instrs)
+        fl = (_vp * max(len(flags), 1))(*[None if v is None else v.h for v in flags])
+        Ep = (_vp * max(len(E), 1))(*[None if v is None else v.h for v in E])
+        h = _vp()
+        ctx.check(l.cozk_primary_create(ctx.h, mode, party, rows, len(instrs), fl, Ep, len(E), outputs.h, eq.h, ctypes.byref(h)))
+        return cls(ctx, h, mode, len(instrs), len(E))
+
+    def degree(self):
+        return self._l.cozk_primary_degree(self.h)
+
+    def __len__(self):
+        return self._l.cozk_primary_len(self.h)
+
+    def round_begin(self, r=None):
+        """bind with r (None in the first round), the linear pass and the item list -> (n_items, n_levels)"""
+        rr = fr_to_mont_limbs([r])[0] if r is not None else None
+        n_items, n_levels = _sz(), _i()
+        self.ctx.check(self._l.cozk_primary_round_begin(self.ctx.h, self.h, rr.ctypes.data if rr is not None else None, ctypes.byref(n_items),
+                                                        ctypes.byref(n_levels)))
+        return n_items.value, n_levels.value
+
+    def level(self, level, key_self=None, key_prev=None, counter=0):
+        """the local half of multiplication level `level` -> (send, recv, n_elems): device addresses (None: no buffer) of this
+        party's n_elems new additive shares and of where the previous party's must land before the next call"""
+        send, recv, n = _vp(), _vp(), _sz()
+        self.ctx.check(self._l.cozk_primary_level(self.ctx.h, self.h, level, L.prf_key(key_self), L.prf_key(key_prev), counter, ctypes.byref(send),
+                                                  ctypes.byref(recv), ctypes.byref(n)))
+        return send.value, recv.value, n.value
+
+    def round_finish(self):
+        """this party's additive evaluations at X = 0, 2, 3, .., degree"""
+        d = self.degree()
+        out = np.zeros((d, 4), dtype=np.uint64)
+        self.ctx.check(self._l.cozk_primary_round_finish(self.ctx.h, self.h, out.ctypes.data))
+        return mont_limbs_to_int(out)
+
+    def final_evals(self, r):
+        """bind with the last challenge -> (E(r) per memory, flag(r) per instruction, lookup_outputs(r), eq(r)); E and the outputs as
+        ints (plain) or (a, b) tuples (Rep3)"""
+        rr = fr_to_mont_limbs([r])[0]
+        Ee, Fe = np.zeros((2 * self.n_mem, 4), dtype=np.uint64), np.zeros((self.n_instr, 4), dtype=np.uint64)
+        oe, qe = np.zeros((2, 4), dtype=np.uint64), np.zeros((1, 4), dtype=np.uint64)
+        self.ctx.check(self._l.cozk_primary_final_evals(self.ctx.h, self.h, rr.ctypes.data, Ee.ctypes.data, Fe.ctypes.data, oe.ctypes.data,
+                                                        qe.ctypes.data))
+        ev, o = mont_limbs_to_int(Ee), mont_limbs_to_int(oe)
+        if self.mode == L.MODE_REP3:
+            return [(ev[2 * m], ev[2 * m + 1]) for m in range(self.n_mem)], mont_limbs_to_int(Fe), (o[0], o[1]), mont_limbs_to_int(qe)[0]
+        return [ev[2 * m] for m in range(self.n_mem)], mont_limbs_to_int(Fe), o[0], mont_limbs_to_int(qe)[0]
+
+    def free(self):
+        if getattr(self, "h", None):
+            self._l.cozk_primary_free(self.h)
             self.h = None
 
     def __del__(self):

@@ -863,7 +863,21 @@ int cozk_sparse_reset_stats(cozk_ctx* ctx);
  * The multiplicative forms multiply shared values: each level is ONE batched mul_vec / reshare_additive_many over all
  * active (index, instruction, point) items -- cozk_primary_level does the local half and names the device buffers of the
  * ring exchange, which the host runs (cozk_reshare / its own transport) before the next call.  The last multiplication of
- * every form stays additive (into_additive follows it in worker.rs:553): same totals, one ring round less. */
+ * every form stays additive (into_additive follows it in worker.rs:553): same totals, one ring round less.
+ *
+ * What cozk_primary_create admits (anything else is COZK_ERR_INVALID_ARG): the chunk count C follows from the form and
+ * n_mems, a table's sumcheck degree is the largest g degree + 2 and at most 8, every level is one exchange per round:
+ *   form                     n_mems    C      g degree   levels
+ *   CONCAT                   1..20     -      1          0          bits * (n_mems - 1) < 200
+ *   NOT_FIRST, ZERO          1..20     -      1          0          (only mems[0] is read / nothing is)
+ *   PRODUCT, NOT_PRODUCT     C         1..6   C          max(C - 2, 0)
+ *   LTU, NOT_LTU             2C - 1    1..6   C          max(C - 2, 0)
+ *   LTE                      2C        1..6   C          max(C - 2, 0)
+ *   DIV0                     2C        1..6   C          max(C - 2, 0)
+ *   UNSIGNED_REM             3C - 1    1..6   C          max(C - 2, 0)
+ *   SLT, NOT_SLT             2C + 1    2..4   C + 2      C - 1
+ *   SIGNED_REM               4C + 2    2..4   C + 2      C - 1
+ * At most 64 instructions, 32 of them multiplicative (neither CONCAT, NOT_FIRST nor ZERO). */
 #define COZK_G_CONCAT 0
 #define COZK_G_PRODUCT 1
 #define COZK_G_LTU 2
