@@ -851,8 +851,43 @@ struct MsmSetPlan {
     uint32_t* counts = nullptr;   // device: reference counts in both forms, two words per polynomial
     uint64_t elig = 0;            // bit p: polynomial p may take the offset form
     bool force_offset = false;    // COZK_MSM_DIGIT_FORM=offset
-    bool alone = false;           // nothing runs beside this set's sort
+    bool wide = false;            // sort shape (msm_sort_wide): nothing runs beside this set's sort that could hide it
+    int wg_digits_log2 = 0;       // digits per sort workgroup of the narrow kinds (msm_sort_wgs); 0: sized like FR columns
+    uint32_t index = 0;           // position in the batch's launch order (COZK_TRACE_MSM)
 };
+
+// ---- the two rules that size a set's sort (restated in tests/test_msm_schedule_model.py)
+//
+// Shape.  The 256-thread shape exists to slip a sort under the gather kernel of the set launched before it; wide
+// workgroups wait for that gather's grid to drain and then run with the chip to themselves.  Measured in place on the
+// bench's commit at 2^20 (profiles/msm_schedule_kernel_stats_{before,after}.txt), sort of a set of 18 field-element
+// columns whose own gather lasts 22.5 ms: beside a gather the narrow sort spans 18.9 ms (0.84 of its own gather) and slows
+// that gather by ~7 %; with nothing beside it the narrow sort takes 0.86 + 4.52 ms (0.24), the wide one 0.68 + 4.13 ms
+// (0.214: the scatter is bound by its 4-byte writes to random lines, not by the shape).  With x = predecessor's
+// references / own references (a gather lasts as long as its references), the narrow shape leaves
+// (1 - x / 0.84) x 0.24 + 0.07 x of the own gather's length exposed, the wide one 0.214: they meet at x ~ 0.12.  The rule
+// takes 1/8.  The sets of one batch are equal-sized apart from a small one, so nothing in the bench sits near the threshold.
+static bool msm_sort_wide(uint64_t pred_refs, uint64_t own_refs) { return 8 * pred_refs < own_refs; }
+
+// Workgroups per polynomial.  A sort workgroup pays for 2^15 LDS counters whatever the column holds (zeroing, the sweep, one
+// global atomic per non-empty bucket).  A field-element column of 2^20 scalars gives each of its 64 workgroups 2^18 digits
+// for them (measured on such columns: 64 beats 16 workgroups 2 x; they keep one workgroup per 4096 scalars).  The other
+// kinds place 1 to 5 digits per scalar: sized by scalars a u16 column hands each workgroup 2^14 digits and issues nearly
+// one global atomic per reference, so they are sized by digits.  Measured at 2^20 beside the gather (commit per step, median
+// of three alternated runs, shape rule on): one workgroup per 4096 scalars 95.90 ms; per 2^15 digits 95.68; 2^16 94.98 and
+// 95.25 (two sessions); 2^17 95.57; 2^18 96.08; 2^20 103.97 (too few workgroups for the slots the gather leaves free, and
+// a flag column serialises on one LDS counter per workgroup).  2^16: histogram of 32 u16 columns 5.4 -> 3.6 ms.
+static constexpr int MSM_WG_DIGITS_LOG2 = 16;
+static uint32_t msm_sort_wgs(int kind, size_t max_n, int wg_digits_log2, uint32_t wgs_max) {
+    uint64_t w = kind == COZK_SCALAR_FR || wg_digits_log2 == 0 ? ((uint64_t)max_n + 4095) / 4096
+                                                               : (((uint64_t)max_n * kind_nwin(kind) + (1ull << wg_digits_log2) - 1) >> wg_digits_log2);
+    if (w < 1) w = 1;
+    return (uint32_t)(w > wgs_max ? wgs_max : w);
+}
+static const char* kind_name(int kind) {
+    static const char* const names[] = {"FR", "U8", "U16", "U32", "U64", "I64"};
+    return kind >= 0 && kind <= COZK_SCALAR_I64 ? names[kind] : "?";
+}
 
 static MsmSetPlan msm_plan(const cozk_bases* bases, const size_t* offsets, const size_t* ns, const int* kinds, size_t P) {
     COZK_REQUIRE(P >= 1, "msm: empty batch");
@@ -937,63 +972,71 @@ static void msm_sort(cozk_ctx* ctx, hipStream_t st, MsmSortWs& sw, const MsmSetP
         MsmPolyDesc* h_descs = pl.pin->descs;
         COZK_REQUIRE(P <= 64, "msm: too many polynomials in one launch set");
         uint32_t nd = 0;
-        std::vector<std::pair<int, std::pair<uint32_t, uint32_t>>> runs;  // kind -> (first desc, count)
+        struct KindRun { int kind; uint32_t first, count; size_t max_n; uint32_t wgs; };  // descriptors [first, first + count)
+        std::vector<KindRun> runs;
         size_t max_n = 0;
         for (int kind = 0; kind <= COZK_SCALAR_I64; kind++) {
-            uint32_t first = nd;
+            KindRun r{kind, nd, 0, 0, 0};
             for (size_t p = 0; p < P; p++)
                 if (kinds[p] == kind && ns[p]) {
                     h_descs[nd++] = MsmPolyDesc{scalars[p], (uint32_t)ns[p], (uint32_t)offsets[p], (uint32_t)p, 0};
-                    if (ns[p] > max_n) max_n = ns[p];
+                    if (ns[p] > r.max_n) r.max_n = ns[p];
                 }
-            if (nd > first) runs.push_back({kind, {first, nd - first}});
+            r.count = nd - r.first;
+            if (r.max_n > max_n) max_n = r.max_n;
+            if (r.count) runs.push_back(r);
         }
         HIP_TRY(hipMemcpyAsync(d_descs, h_descs, nd * sizeof(MsmPolyDesc), hipMemcpyHostToDevice, st));
         // 256-thread workgroups (one wave per SIMD, 128 KiB of LDS each): narrow enough to slip into the CU slots that free
         // up under the register-heavy gather kernel of the previous launch set, so the sort really runs beside it (wider
         // workgroups wait for the gather's grid to drain: measured 127.8 -> 123.5 ms per proof at 2^20, same box).
-        // A set with nothing beside it (the first of a batch, a single set, serial batches) takes the wide shape instead
-        // (measured at 2^20: 1024 x 64, 1024 x 32, 1024 x 16, 512 x 64 and 512 x 32 all within 0.2 ms of each other and
-        // 0.3-0.4 ms per commit ahead of 256 x 64; the first set of the bench's commit is a small one, see DESIGN):
-        // COZK_MSM_LTPB / COZK_MSM_WGS override both shapes.
+        // A set whose predecessor cannot hide its sort (msm_sort_wide: the first of a batch, a single set, serial batches,
+        // a set behind a much smaller one) takes the wide shape instead (measured at 2^20: 1024 x 64, 1024 x 32, 1024 x 16,
+        // 512 x 64 and 512 x 32 all within 0.2 ms of each other): COZK_MSM_LTPB / COZK_MSM_WGS override both shapes.
         static const int ltpb_env = getenv("COZK_MSM_LTPB") ? atoi(getenv("COZK_MSM_LTPB")) : 0;
         static const int wgs_env = getenv("COZK_MSM_WGS") ? atoi(getenv("COZK_MSM_WGS")) : 0;
-        const int ltpb = ltpb_env ? ltpb_env : (pl.alone ? MSM_WIDE_LTPB : 256);
-        const uint32_t wgs_max = (uint32_t)(wgs_env ? wgs_env : (pl.alone ? MSM_WIDE_WGS : 64));
+        const int ltpb = ltpb_env ? ltpb_env : (pl.wide ? MSM_WIDE_LTPB : 256);
+        const uint32_t wgs_max = (uint32_t)(wgs_env ? wgs_env : (pl.wide ? MSM_WIDE_WGS : 64));
         COZK_REQUIRE(ltpb >= 64 && ltpb <= LTPB && ltpb % 64 == 0, "COZK_MSM_LTPB out of range");
         COZK_REQUIRE(wgs_max >= 1 && wgs_max <= 1024, "COZK_MSM_WGS out of range (1..1024)");
-        uint32_t wgs = (uint32_t)((max_n + 4095) / 4096);  // >= 4096 scalars per workgroup (measured: 64 beats 16 workgroups 2x)
-        if (wgs < 1) wgs = 1;
-        if (wgs > wgs_max) wgs = wgs_max;
+        for (auto& r : runs) r.wgs = msm_sort_wgs(r.kind, r.max_n, pl.wg_digits_log2, wgs_max);
+        // COZK_TRACE_MSM=1: one line per launch set on stderr -- index, polynomials, references, shape, then kind:columns:workgroups
+        static const bool trace = getenv("COZK_TRACE_MSM") != nullptr;
+        if (trace) {
+            std::string line;
+            for (auto& r : runs) line += " " + std::string(kind_name(r.kind)) + ":" + std::to_string(r.count) + ":" + std::to_string(r.wgs);
+            fprintf(stderr, "cozk msm set %u: polys %u refs %llu shape %s %dx%u kinds%s\n", pl.index, pl.P, (unsigned long long)pl.M,
+                    pl.wide ? "wide" : "narrow", ltpb, wgs_max, line.c_str());
+        }
         // digit form of the U16 / U32 / U64 columns: count both forms (one extra read of those columns), offset where it
         // places strictly fewer references; forced offset needs no count.  Plain leaves the zeroed words alone.
         if (pl.elig) {
             if (!pl.force_offset)
                 for (auto& r : runs)
-                    if (kind_offset_slot(r.first) >= 0) {
-                        dim3 grid(std::min<uint32_t>(cdiv(max_n, 4096), 64u), r.second.second);
-                        KIND_DISPATCH(r.first, (k_msm_form_count<K><<<grid, 256, 0, st>>>(d_descs + r.second.first, pl.counts)));
+                    if (kind_offset_slot(r.kind) >= 0) {
+                        dim3 grid(std::min<uint32_t>(cdiv(max_n, 4096), 64u), r.count);
+                        KIND_DISPATCH(r.kind, (k_msm_form_count<K><<<grid, 256, 0, st>>>(d_descs + r.first, pl.counts)));
                     }
             k_msm_form_pick<<<1, 64, 0, st>>>(pl.counts, pl.form, pl.P, pl.elig, pl.force_offset ? 1 : 0);
         }
         for (auto& r : runs) {
-            dim3 grid(wgs, r.second.second);
-            KIND_DISPATCH(r.first, (k_msm_hist_lds<K><<<grid, ltpb, 0, st>>>(d_descs + r.second.first, hist, pl.form)));
+            dim3 grid(r.wgs, r.count);
+            KIND_DISPATCH(r.kind, (k_msm_hist_lds<K><<<grid, ltpb, 0, st>>>(d_descs + r.first, hist, pl.form)));
         }
         fullest_bucket();
         msm_scan(st, bsums, nb, false, hist, 1, off0, hist);  // hist doubles as the scatter cursor after the scan
         read_back_stats();
         for (auto& r : runs) {
-            dim3 grid(wgs, r.second.second);
+            dim3 grid(r.wgs, r.count);
             // algorithmic bytes of the placement: every scalar read once + one 4-byte reference written per 16-bit window
             uint64_t alg = 0;
-            for (uint32_t q = 0; q < r.second.second; q++) {
-                const MsmPolyDesc& d = h_descs[r.second.first + q];
-                const uint64_t sb = scalar_kind_bytes(r.first);
+            for (uint32_t q = 0; q < r.count; q++) {
+                const MsmPolyDesc& d = h_descs[r.first + q];
+                const uint64_t sb = scalar_kind_bytes(r.kind);
                 alg += (uint64_t)d.n * (sb + 4ull * ((sb * 8 + 15) / 16));
             }
             ProfScope prof(ctx, COZK_PROF_MSM_SCATTER, alg, st);
-            KIND_DISPATCH(r.first, (k_msm_scatter_lds<K><<<grid, ltpb, 0, st>>>(d_descs + r.second.first, hist, refs, (uint32_t)bases->n, pl.form)));
+            KIND_DISPATCH(r.kind, (k_msm_scatter_lds<K><<<grid, ltpb, 0, st>>>(d_descs + r.first, hist, refs, (uint32_t)bases->n, pl.form)));
         }
     } else {
         for (size_t p = 0; p < P; p++) {
@@ -1140,6 +1183,23 @@ static int msm_digit_form_mode() {
     throw CozkError(COZK_ERR_INVALID_ARG, "COZK_MSM_DIGIT_FORM must be auto, plain or offset");
 }
 
+// A/B switches of the launch schedule, read at every call like the digit form; none of them changes a result.
+//   COZK_MSM_SHAPE_RULE=0      sort shape as before msm_sort_wide: wide for the first set of a batch and serial batches only
+//   COZK_MSM_WG_DIGITS_LOG2=d  digits per sort workgroup of the narrow kinds (10..24); 0: one workgroup per 4096 scalars
+struct MsmSchedule {
+    bool shape_rule = true;
+    int wg_digits_log2 = MSM_WG_DIGITS_LOG2;
+};
+static MsmSchedule msm_schedule_env() {
+    MsmSchedule s;
+    if (const char* e = getenv("COZK_MSM_SHAPE_RULE")) s.shape_rule = atoi(e) != 0;
+    if (const char* e = getenv("COZK_MSM_WG_DIGITS_LOG2")) {
+        s.wg_digits_log2 = atoi(e);
+        COZK_REQUIRE(s.wg_digits_log2 == 0 || (s.wg_digits_log2 >= 10 && s.wg_digits_log2 <= 24), "COZK_MSM_WG_DIGITS_LOG2 must be 0 or 10..24");
+    }
+    return s;
+}
+
 // c S for the slice [off, off + n) of `bases` and the three kinds with an offset form (kind_offset_slot), from the
 // handle's cache.  The first request computes S with the MSM itself on a constant all-ones U8 column (always plain, so
 // this does not come back here) and multiplies on the host: once per SRS slice, not per proof.  In `auto` mode the host
@@ -1204,6 +1264,7 @@ void msm_batch(cozk_ctx* ctx, const cozk_bases* bases, const size_t* offsets, co
     // digit forms: which columns may take the offset form, and their corrections c S (computed here, before this
     // batch touches the workspace, because the first use of a slice runs an MSM of its own)
     const int form_mode = msm_digit_form_mode();
+    const MsmSchedule sched = msm_schedule_env();
     std::vector<uint8_t> elig(k, 0);
     std::vector<g1_affine> corr_h;
     bool any_elig = false;
@@ -1262,11 +1323,12 @@ void msm_batch(cozk_ctx* ctx, const cozk_bases* bases, const size_t* offsets, co
         // k, within [2^28, 2^30] (the two sort workspaces hold 4 bytes per reference).  Measured: at 2^22 coefficients 2^30 beats 2^28
         // by 7 % of the commit (4 instead of 16 polynomials per set paid the per-set scans and the host's wait for the fullest bucket
         // 4 x as often); at 2^20 one 2^30 set would hold all 64 field-element polynomials and lose the overlap (+4 %).
-        // COZK_MSM_SET_REFS_LOG2 (24..31) pins the cap for A/B runs.
+        // COZK_MSM_SET_REFS_LOG2 (12..31) pins the cap for A/B runs and lets a test cut a small batch into many sets; like the
+        // schedule switches (msm_schedule_env) it is read at every call.
         uint64_t set_refs_cap;
         {
-            static const int pinned = getenv("COZK_MSM_SET_REFS_LOG2") ? atoi(getenv("COZK_MSM_SET_REFS_LOG2")) : 0;
-            if (pinned) set_refs_cap = 1ull << (pinned < 24 ? 24 : (pinned > 31 ? 31 : pinned));
+            const int pinned = getenv("COZK_MSM_SET_REFS_LOG2") ? atoi(getenv("COZK_MSM_SET_REFS_LOG2")) : 0;
+            if (pinned) set_refs_cap = 1ull << (pinned < 12 ? 12 : (pinned > 31 ? 31 : pinned));
             else {
                 uint64_t total = 0;
                 for (size_t p = 0; p < kt; p++) total += (uint64_t)ns[t0 + p] * kind_nwin(kinds[t0 + p]);
@@ -1344,7 +1406,12 @@ void msm_batch(cozk_ctx* ctx, const cozk_bases* bases, const size_t* offsets, co
             for (size_t p = 0; p < r.P; p++)
                 if (elig[t0 + r.s + p]) pl.elig |= 1ull << p;
             pl.force_offset = form_mode == MSM_FORM_OFFSET;
-            pl.alone = (i == 0 && t0 == 0) || side == st;
+            // what the sort runs beside: the accumulation of the set launched before it (none for the first set of a tail
+            // block, whose sort waits for everything queued so far, and in a serial batch)
+            const uint64_t pred_refs = i > 0 && side != st ? plans[i - 1].M : 0;
+            pl.wide = sched.shape_rule ? msm_sort_wide(pred_refs, pl.M) : (i == 0 && t0 == 0) || side == st;
+            pl.wg_digits_log2 = sched.wg_digits_log2;
+            pl.index = (uint32_t)i;
             MsmSortWs& sw = ws.sort[i & 1];
             if (i >= 2 && side != st) HIP_TRY(hipStreamWaitEvent(side, sw.consumed, 0));  // its previous user has finished reading it
             msm_sort(ctx, side, sw, plans[i], bases, offsets + t0 + r.s, ns + t0 + r.s, scalars + t0 + r.s, kinds + t0 + r.s);
