@@ -191,6 +191,7 @@ int cozk_prodlist_create(cozk_ctx* ctx, const cozk_vec* const* polys, size_t n_p
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(ctx && polys && n_polys >= 1 && n_polys <= PL_MAX_POLYS && coefs && counts && factor_idx && n_terms >= 1 && n_terms <= PL_MAX_TERMS && out,
                      "prodlist_create: bad argument");
+        COZK_REQUIRE(polys[0], "prodlist_create: null polynomial");
         const size_t n = polys[0]->n;
         COZK_REQUIRE(n >= 1 && (n & (n - 1)) == 0, "prodlist_create: power-of-two polynomials");
         struct Guard {  // argument checks follow the allocations: free what exists if one of them throws

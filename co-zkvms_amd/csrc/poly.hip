@@ -2012,6 +2012,7 @@ int cozk_open_quadratic_evals(cozk_ctx* ctx, const cozk_poly* const* polys, cons
                               uint64_t* out) {
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(ctx && polys && eqs && k > 0 && out, "open_quadratic: bad argument");
+        COZK_REQUIRE(polys[0], "open_quadratic: null polynomial");
         int mode = polys[0]->mode;
         std::vector<const fe*> ha(k), hb(k), he(k);
         std::vector<size_t> hh(k);
@@ -2065,6 +2066,7 @@ int cozk_open_quadratic_evals(cozk_ctx* ctx, const cozk_poly* const* polys, cons
 int cozk_prod_sumcheck_evals(cozk_ctx* ctx, const cozk_poly* const* polys, size_t m, int degree, uint64_t* out) {
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(ctx && polys && out && m >= 1 && m <= 4 && degree >= 1 && degree <= 4, "prod_sumcheck: bad argument");
+        COZK_REQUIRE(polys[0], "prod_sumcheck: null polynomial");
         size_t len = polys[0]->len;
         int shared = -1;
         const fe* ha[4] = {nullptr, nullptr, nullptr, nullptr};

@@ -96,6 +96,7 @@ int cozk_eq_plus_one_evals(cozk_ctx* ctx, const uint64_t* r, int nv, cozk_vec** 
 int cozk_poly_batch_dot_public(cozk_ctx* ctx, const cozk_poly* const* polys, size_t k, const cozk_vec* const* pubs, size_t n_pub, uint64_t* out) {
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(ctx && polys && k > 0 && pubs && (n_pub == 1 || n_pub == 2) && out, "batch_dot_public: bad argument (one or two public vectors)");
+        COZK_REQUIRE(polys[0], "batch_dot_public: null polynomial");
         const size_t n = polys[0]->len;
         for (size_t q = 0; q < n_pub; q++) COZK_REQUIRE(pubs[q] && pubs[q]->kind == COZK_SCALAR_FR && pubs[q]->n == n, "batch_dot_public: length mismatch (zip_eq)");
         std::vector<const fe*> ha(k), hb(k);

@@ -571,7 +571,9 @@ int cozk_spartan_second_round(cozk_ctx* ctx, const cozk_poly* z, const cozk_poly
                               const cozk_poly* c, const uint64_t coef[12], uint64_t out_a[12],
                               uint64_t out_b[12]);
 /* SpartanProverWorker::zero_round (co-spartan/src/worker.rs:153-182): (za, zb, zc) = (A, B, C) z on shares;
- * CSR rows: row_ptr (U32, nrows+1), col (U32, nnz), val_a/b/c (FR, nnz) */
+ * CSR rows: row_ptr (U32, nrows+1), col (U32, nnz), val_a/b/c (FR, nnz).
+ * PRECONDITIONS (not checked): row_ptr is non-decreasing from 0 to nnz and every col[e] < z's length.  The kernels read
+ * z[col[e]] as it stands, so a larger column is an out-of-bounds device read (the reference panics there). */
 int cozk_sparse_matvec3(cozk_ctx* ctx, const cozk_vec* row_ptr, const cozk_vec* col,
                         const cozk_vec* val_a, const cozk_vec* val_b, const cozk_vec* val_c,
                         const cozk_poly* z, cozk_poly** out_za, cozk_poly** out_zb, cozk_poly** out_zc);
@@ -973,7 +975,9 @@ int cozk_poly_batch_dot_public(cozk_ctx* ctx, const cozk_poly* const* polys, siz
 /* ---- co-noir-spartan's public lookup round (co-noir-spartan/co-spartan/src/worker.rs:400-575,694-724,836-846;
  * co-noir-spartan/spartan/src/logup.rs:31-80; co-spartan/src/sumcheck.rs:434-500): plain Fr data, no shares. */
 /* hash_tuple (worker.rs:836-846): out[j] = idx[j] + v_msg * eq[idx[j]] for the (pre-filtered) indices, the tail up to n_out
- * (a power of two) repeats entry 0 */
+ * (a power of two) repeats entry 0.
+ * PRECONDITION (not checked): every idx[j] < eq's length.  The kernel reads eq[idx[j]] as it stands, so a larger index is an
+ * out-of-bounds device read (the reference panics there). */
 int cozk_hash_tuple(cozk_ctx* ctx, const cozk_vec* idx_u32, const cozk_vec* eq, const uint64_t v_msg[4], size_t n_out,
                     cozk_vec** out);
 /* eq_tilde_{rx,ry}(_chunk) of third_round (worker.rs:296-343,376-391): out[j] = src[idx[j]] (0xffffffff = usize::MAX and the

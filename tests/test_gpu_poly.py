@@ -1,12 +1,11 @@
 """GPU parity of the polynomial seam (bind / evals / RLC / GKR layer ops) against oracle/pyref.py.
 Bit-exact bar; both share modes (Rep3 shares and plain values); ragged tails as the reference
 handles them (dense_interleaved_poly.rs:160-177,232-247)."""
-import numpy as np
 import pytest
 
-import prims_harness as H
 import pyref as O
 import reduction_ref as X
+from seam_ref import PERIOD as WIDE_PERIOD, tiled as _tiled, tiled_dot as _tiled_dot, wide_inputs as _wide_inputs, wide_poly as _wide_poly
 
 pytestmark = pytest.mark.gpu
 
@@ -421,46 +420,7 @@ def test_open_quadratic_and_pst_fold(cozk, ctx):
 # (28 (r - 1)^2 >= 2^512), so these run the smallest sizes at which a lane of the default grids holds that many, on RAW residues
 # (Vec.from_numpy: the device multiplies exactly these words).  A Montgomery product of residues x, y is x y / R and the result
 # is read back through another 1 / R, hence the RINV^2 in every big-int expectation.
-WIDE_PERIOD = 49  # coprime to every grid stride (a power of two times 3): a lane walks through the whole pattern
-
-
-def _wide_pattern(seed):
-    """r - 1, a primitive-harness edge, a random residue, ... : 16 triples and one more r - 1"""
-    rng = O.SplitMix64(seed)
-    pat = [v for e in H.edges(O.R) for v in (O.R - 1, e, rng.field())] + [O.R - 1]
-    assert len(pat) == WIDE_PERIOD
-    return pat
-
-
-def _tiled(ctx, cozk, pattern, n):
-    return cozk.Vec.from_numpy(ctx, np.resize(X.to_raw(pattern), (n, 4)))
-
-
-def _tiled_dot(n, *patterns):
-    """sum_{i < n} prod_k patterns[k][i mod period] for patterns of one period, the sum of products in big ints"""
-    period = len(patterns[0])
-    total = 0
-    for j in range(period):
-        term = (n // period) + (j < n % period)
-        for p in patterns:
-            term *= p[j]
-        total += term
-    return total
-
-
-def _wide_inputs(fill, mode, seed, eval_sum):
-    """(a, b, public) patterns: all r - 1, or mixed.  Where the kernel multiplies a + b (eval_sum) the all-(r - 1) run keeps b
-    at zero so that the factor itself is r - 1"""
-    one = [O.R - 1] * WIDE_PERIOD
-    if fill == "all_r_minus_1":
-        return one, ([0] * WIDE_PERIOD if eval_sum else one) if mode == "rep3" else None, one
-    a, b, pub = _wide_pattern(seed), _wide_pattern(seed + 1)[::-1], _wide_pattern(seed + 2)
-    pub = pub[5:] + pub[:5]  # r - 1 meets r - 1, an edge and a random value
-    return a, b if mode == "rep3" else None, pub
-
-
-def _wide_poly(cozk, ctx, a, b, n):
-    return cozk.Rep3DensePolynomial.from_vec_shares(ctx, _tiled(ctx, cozk, a, n), _tiled(ctx, cozk, b, n) if b is not None else None)
+# The periodic patterns and their exact sums live in tests/seam_ref.py (period 49, coprime to every grid stride).
 
 
 @pytest.mark.parametrize("fill", ["all_r_minus_1", "mixed"])
