@@ -20,3 +20,5 @@ from .spartan import SpartanHarness, SpartanConfig, SpartanResult
 from .lookups import SparseLayer, SparseStats, sparse_stats, sparse_reset_stats
 from . import shamir_spartan
 from .shamir_spartan import SpartanGroup, ShamirSpartanHarness, ShamirSpartanConfig, ShamirSpartanResult
+from . import shamir_jolt_spartan
+from .shamir_jolt_spartan import OuterGroup, ShiftGroup, ShamirJoltSpartanHarness, ShamirJoltSpartanConfig, ShamirJoltSpartanResult

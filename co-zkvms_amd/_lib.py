@@ -185,6 +185,17 @@ SIGNATURES = {
     "cozk_spartan_group_len": (_sz, [_vp]),
     "cozk_spartan_group_pub_download": (_i, [_vp, _vp]),
     "cozk_spartan_group_free": (_i, [_vp]),
+    "cozk_outer_group_create": (_i, [_vp, _vp, _i, _pp]),
+    "cozk_outer_group_round": (_i, [_vp, _vp, _vp, _vp]),
+    "cozk_outer_group_final": (_i, [_vp, _vp, _i, _vp]),
+    "cozk_outer_group_len": (_sz, [_vp]),
+    "cozk_outer_group_free": (_i, [_vp]),
+    "cozk_shift_group_create": (_i, [_vp, _vp, _i, _vp, _pp]),
+    "cozk_shift_group_round": (_i, [_vp, _vp, _vp]),
+    "cozk_shift_group_final": (_i, [_vp, _vp, _i, _vp]),
+    "cozk_shift_group_len": (_sz, [_vp]),
+    "cozk_shift_group_pub_download": (_i, [_vp, _vp]),
+    "cozk_shift_group_free": (_i, [_vp]),
     "cozk_toggle_group_create": (_i, [_vp, _vp, _sz, _vp, _i, _i, _pp]),
     "cozk_toggle_group_layer_outputs": (_i, [_vp, _vp, _vp]),
     "cozk_toggle_group_round": (_i, [_vp, _vp, _vp, _vp]),

@@ -911,3 +911,4 @@ int cozk_worker_spartan_second_sumcheck(cozk_ctx* ctx, const cozk_worker_params*
 #include "host/flow_harness.hpp"
 #include "host/shamir_gp.hpp"
 #include "host/shamir_spartan.hpp"
+#include "host/shamir_jolt_spartan.hpp"

@@ -2981,5 +2981,6 @@ int cozk_layer_claimed_outputs(cozk_ctx* ctx, const cozk_layer* l, uint64_t* out
 #include "sparse_layer.inc"
 #include "primary_sumcheck.inc"
 #include "spartan_outer.inc"
+#include "outer_group.inc"
 #include "spartan_inner.inc"
 #include "logup.inc"

@@ -508,6 +508,23 @@ int cozk_outer_download(cozk_ctx* ctx, const cozk_outer* st, uint64_t* az_a, uin
     });
 }
 
+// everything of one bind but the kernel: the layer moves on to its other ping-pong side and halves, and GruenSplitEqPolynomial::bind
+// folds eq(w_i, r) into the scalar and drops the last variable of E_in (then of E_out)
+static void outer_bind_state(cozk_outer* st, const fe& r) {
+    if (st->per_step > 1) {
+        st->per_step /= 2;
+        st->act_rows = (st->act_rows + 1) / 2;
+    }
+    st->cur = 1 - st->cur;
+    st->L /= 2;
+    const fe& w = st->w[st->current_index - 1];
+    fe wr = Fr::mul(w, r);
+    st->current_scalar = Fr::mul(st->current_scalar, Fr::add(Fr::sub(Fr::sub(Fr::one(), w), r), Fr::dbl(wr)));
+    st->current_index -= 1;
+    if ((int)(st->w.size() / 2) < st->current_index) st->n_in -= 1;
+    else if (0 < st->current_index) st->n_out -= 1;
+}
+
 static void outer_bind(cozk_ctx* ctx, cozk_outer* st, const fe& r) {
     const int NC = st->mode == COZK_MODE_REP3 ? 2 : 1;
     const int dst = 1 - st->cur;
@@ -529,19 +546,7 @@ static void outer_bind(cozk_ctx* ctx, cozk_outer* st, const fe& r) {
         k_outer_bind<<<g, PT, 0, ctx->stream>>>(a, n_out, r);
     }
     HIP_TRY(hipGetLastError());
-    if (st->per_step > 1) {
-        st->per_step /= 2;
-        st->act_rows = (st->act_rows + 1) / 2;
-    }
-    st->cur = dst;
-    st->L = n_out;
-    // GruenSplitEqPolynomial::bind: fold eq(w_i, r) into the scalar, drop the last variable of E_in (then of E_out)
-    const fe& w = st->w[st->current_index - 1];
-    fe wr = Fr::mul(w, r);
-    st->current_scalar = Fr::mul(st->current_scalar, Fr::add(Fr::sub(Fr::sub(Fr::one(), w), r), Fr::dbl(wr)));
-    st->current_index -= 1;
-    if ((int)(st->w.size() / 2) < st->current_index) st->n_in -= 1;
-    else if (0 < st->current_index) st->n_out -= 1;
+    outer_bind_state(st, r);
 }
 
 // The 9 x 29 kernel takes the rounds over compact (active-row) storage that are throughput-bound: OUTER_F9_MIN_PAIRS row pairs or

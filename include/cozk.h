@@ -692,6 +692,69 @@ int cozk_spartan_group_final(cozk_spartan_group* g, const uint64_t* r, int k_fin
 size_t cozk_spartan_group_len(const cozk_spartan_group* g);
 int cozk_spartan_group_pub_download(cozk_spartan_group* g, uint64_t* out);
 int cozk_spartan_group_free(cozk_spartan_group* g);
+/* Outer groups: one round of co-jolt's Spartan OUTER cubic sumcheck (cozk_outer_round below) for SEVERAL members with one
+ * challenge, as one unit of work -- the senders of a Shamir prover whose parties each hold a PLAIN cozk_outer over their shares of the
+ * witness columns.  Az, Bz, Cz are affine in the columns and t(0), t(infinity) multiply exactly two of them, so a party runs the PLAIN
+ * round on its shares.  A group has k members, 1 <= k <= COZK_LAYER_GROUP_MAX: PLAIN cozk_outer states made by cozk_outer_create from
+ * the same system and the same tau, all in the same state (round, length, rows per step), pairwise distinct, each of a context on the
+ * DRIVER's device (the contexts may differ).  The Gruen split-eq tables are public and identical: the group reads member 0's.  The
+ * group REFERS to its members: it does not own them, freeing it leaves them valid, they must outlive it; create drains the stream
+ * of every member's context once and allocates nothing on the device (a cozk_outer owns both ping-pong sides from its creation).
+ *   round  r == NULL in the first round (and only there): the sums of the members as they stand, t(0) = 0 as in cozk_outer_round.
+ *          r != NULL: every member is bound with r, then the sums are taken; with claims + 4 m as member m's share of the running claim
+ *          (the hint), member m's four coefficients, low to high, go to out_coeffs + 16 m: what cozk_outer_round(ctx_m, member m, r,
+ *          claims + 4 m, ..) writes.  The bind is fused with the sums in every storage regime (compact rows inside a step, the round
+ *          whose output rows are whole steps, dense rows): ONE launch of gx x k workgroups and ONE finishing launch whatever k is, ONE
+ *          fetch; members of <= 2048 (dense-equivalent) rows run as ONE launch of k workgroups.
+ *   final  the last bind with r (length 2) of members 0 .. k_final - 1; out + 12 m = Az(r), Bz(r), Cz(r) of member m, what
+ *          cozk_outer_final_evals writes.  One launch, one fetch; members from k_final upwards are left untouched.
+ *   len    the members' current (dense-equivalent) length.
+ * Every launch goes on the driver's stream and every call returns with that stream drained; when a call returns every member is in the
+ * state cozk_outer_round / cozk_outer_final_evals on its own context would have left it in (cozk_outer_download shows it).
+ * Refused on the host before any launch, with COZK_ERR_INVALID_ARG and the text left with the driver (*out is NULL), the members
+ * untouched: null arguments, k out of range, a member that is not PLAIN, members whose state or tau differ, a duplicate member, a
+ * member on another device, r == NULL after the first round or r != NULL in it, a round on fully bound members (or one whose bind
+ * leaves them so), k_final outside 0..k, a final on members whose length is not 2.
+ * Parity unpinned (the reference has no Shamir prover); restated in tests/ (tests/test_gpu_outer_group.py: twins driven by cozk_outer_round). */
+typedef struct cozk_outer cozk_outer;
+typedef struct cozk_outer_group cozk_outer_group;
+int cozk_outer_group_create(cozk_ctx* driver, cozk_outer* const* members, int k, cozk_outer_group** out);
+int cozk_outer_group_round(cozk_outer_group* g, const uint64_t* r /* NULL in round 0 */, const uint64_t* claims /* k x 4 */,
+                           uint64_t* out_coeffs /* k x 16 */);
+int cozk_outer_group_final(cozk_outer_group* g, const uint64_t r[4], int k_final, uint64_t* out /* k_final x 12 */);
+size_t cozk_outer_group_len(const cozk_outer_group* g);
+int cozk_outer_group_free(cozk_outer_group* g);
+/* Shift groups: one round of a (share, public) product sumcheck of prove_arbitrary_worker's shape -- the Spartan worker's shift
+ * sumcheck sum_t z_ry(t) eq_plus_one(rx_step, t) -- for k members of ONE PLAIN polynomial each against ONE public polynomial, binding
+ * COZK_HIGH_TO_LOW (pairs i, i + len / 2).  Member m's evaluations at X = 0 and X = 2 go to out_evals + 8 m: what
+ * cozk_prod_sumcheck_evals({z_m, pub}, 2, 2, ..) writes.  Members: 1 <= k <= COZK_LAYER_GROUP_MAX, all of one current length, a power of
+ * two >= 2, pairwise distinct, each of a context on the DRIVER's device.  Ownership is the Spartan groups': the group REFERS to the
+ * members and OWNS a copy of the public polynomial (len and len / 2 elements of ping-pong storage from the driver's pool; `pub` is only
+ * read, by create).  create drains the stream of every context involved once and sizes what the binds write (side 0 of a member that is
+ * still unbound; a bound member is bound in place, as cozk_poly_bind(.., COZK_HIGH_TO_LOW) binds it): later calls allocate nothing.
+ *   round  r == NULL (the first round): the sums of the members as they stand.  r != NULL: every member and the group's public
+ *          polynomial are bound with r, then the sums are taken.  The bind is fused with the sums (lane i < len / 4 reads i, i + len / 4,
+ *          i + len / 2, i + 3 len / 4 and writes i, i + len / 4; only member row 0 stores the bound public polynomial, into the side
+ *          no workgroup reads): ONE launch of gx x k workgroups and ONE finishing launch whatever k is, ONE fetch; members of <= 2048
+ *          elements run as ONE launch of k workgroups.
+ *   final  the last bind with r (len == 2; r == NULL: no bind, len == 1) of members 0 .. k_final - 1 and of the public polynomial; out =
+ *          the k_final member values, then the public value ((k_final + 1) x 4 u64).  One launch, one fetch; members from k_final upwards
+ *          are left untouched.
+ *   len / pub_download  the current length, and the group's public polynomial as it stands (len x 4 u64).
+ * Every launch goes on the driver's stream and every call returns with that stream drained; when a call returns every bound member is
+ * in the state cozk_poly_bind(.., COZK_HIGH_TO_LOW) on its own context would have left it in.
+ * Refused as for the Spartan groups (COZK_ERR_INVALID_ARG, text with the driver, *out NULL, nothing touched): null arguments, k out of
+ * range, a member or a pub that is not PLAIN, unequal lengths, a length that is not a power of two or is below 2, a duplicate member,
+ * a member or a pub on another device, a round on fully bound members or a binding round that would leave them so, k_final outside
+ * 0..k, a final that does not end at one element.
+ * Parity unpinned; restated in tests/ (tests/test_gpu_outer_group.py: twins driven by cozk_prod_sumcheck_evals and cozk_poly_bind). */
+typedef struct cozk_shift_group cozk_shift_group;
+int cozk_shift_group_create(cozk_ctx* driver, cozk_poly* const* members, int k, const cozk_poly* pub, cozk_shift_group** out);
+int cozk_shift_group_round(cozk_shift_group* g, const uint64_t* r, uint64_t* out_evals /* k x 2 x 4 */);
+int cozk_shift_group_final(cozk_shift_group* g, const uint64_t* r, int k_final, uint64_t* out /* (k_final + 1) x 4 */);
+size_t cozk_shift_group_len(const cozk_shift_group* g);
+int cozk_shift_group_pub_download(cozk_shift_group* g, uint64_t* out);
+int cozk_shift_group_free(cozk_shift_group* g);
 /* local half of layer_output -> mul_vec (dense_interleaved_poly.rs:122-141; local product
  * mpc-types/src/protocols/rep3/arithmetic/ops.rs:71-78): out[j] = L[j] x R[j] + mask_j, where
  * mask_j = PRF(key_self, counter + j) - PRF(key_prev, counter + j) when masked != 0 (key_self is shared with the
@@ -1349,6 +1412,74 @@ const char* cozk_outer_harness_error(const cozk_outer_harness* h);
 int cozk_outer_harness_destroy(cozk_outer_harness* h);
 int cozk_outer_harness_prove(cozk_outer_harness* h, int verify, cozk_outer_result* res);
 int cozk_outer_harness_proof_bytes(const cozk_outer_harness* h, uint8_t* out, size_t cap);
+
+/* ---------------------------------------------------------------- co-jolt's Spartan worker by n Shamir parties ---- */
+/* The whole Spartan worker of the outer harness (cfg.full = 1: outer + inner + shift sumchecks and the two claim exchanges) proved by n
+ * Shamir parties of degree t, semi-honest, all driven from the calling thread, which owns every party's context and plays the
+ * coordinator (csrc/host/shamir_jolt_spartan.hpp; the reference has no Shamir prover: parity unpinned; restated in tests/
+ * (tests/shamir_jolt_spartan_ref.py)).  The instance is the outer harness's own for (seed, log_steps, system).  Every step of the worker
+ * is linear in the witness share or multiplies exactly two secret factors, so each party runs the COZK_MODE_PLAIN calls on its shares:
+ * THE PROOF IS THE PLAIN PROVER'S, BYTE FOR BYTE (cozk_outer_harness with MODE_PLAIN and full = 1, oracle/pyspartan_outer.py run_full),
+ * accepted by the same verifier.
+ *   witness    a public column stays public at every party.  Shared column v is dealt once with cozk_shamir_share_vec's rule at
+ *              share_counter + v * num_steps; share key c = the harness key (seed ^ 0x53484152, c), c = 0 .. t - 1.
+ *   masks      M = 4 (log_steps + log2(rows per step)) openings of degree 2t: ONE dealing (cozk_shamir_rand_inproc's rule) of M elements
+ *              at rand_counter, pair 0 only, zero_p[m] = r2t_p^0[m] - rt_p^0[m].  Party p's (3t + 1) x 32 rand key bytes: key j = the
+ *              harness key (seed ^ 0x52414E44, 64 p + j).  As for the grand product A PAIR MUST NEVER BE USED TWICE: (seed,
+ *              rand_counter .. rand_counter + M) must not serve another proof -- the caller's contract.
+ *   outer      senders 0..2t each hold a PLAIN cozk_outer over their columns (a constant or a public column is added to every party's
+ *              Az, Bz, Cz: the constant sharing).  Per round sender p's four coefficients + zero_p[4 round + i] are opened with
+ *              lagrange(1..2t + 1); the opened claim is every sender's hint of the next round.  In the first round every party's t(0) is 0.
+ *              Az, Bz, Cz(r) are opened from parties 0..t with lagrange(1..t + 1), unmasked.
+ *   inner      on the host: parties 0..t run the plain round arithmetic on bind_z / bind_shift_z from ONE cozk_poly_batch_dot_public
+ *              each, with the opened claim as running claim; each of the three coefficients is opened with lagrange(1..t + 1).
+ *   shift      z_ry from cozk_poly_linear_combination per opener; shift_claim is opened from parties 0..t and not appended to the
+ *              transcript; the rounds (evaluations at 0 and 2, the opened running claim) are opened from parties 0..t, unmasked.
+ *   claims     two exchanges: cozk_poly_batch_evaluate_at_chi per opener at rx_step and at the shift point, every column's value opened
+ *              from parties 0..t (a public column's value opens to itself).
+ * When the senders' contexts are on one device the outer sumcheck runs as ONE cozk_outer_group on sender 0's context and the shift
+ * sumcheck as ONE cozk_shift_group over the openers with one eq_plus_one (stats: group_rounds = n_tau + log_steps with n_tau = log_steps
+ * + log2(rows per step), group_finals = 2, or 1 when log_steps = 0: there is no shift round and no shift group then); otherwise, or with
+ * COZK_SHAMIR_GP_GROUP=0 in the environment (read on every prove), every sender runs cozk_outer_round / cozk_prod_sumcheck_evals +
+ * cozk_poly_bind (single_rounds = (2t + 1) n_tau + (t + 1) log_steps, single_finals = 2 (t + 1), or t + 1 when log_steps = 0).  Proof,
+ * msgs and finals are the same bytes either way.
+ * Refused by create before any launch (the handle is returned with its error text): 1 <= t, 2t <= COZK_SHAMIR_MAX_DEGREE,
+ * 2t + 1 <= n <= COZK_SHAMIR_MAX_PARTIES, 0 <= log_steps <= 24, system 0 or 1.  Not built: the Lasso primary sumcheck by Shamir
+ * parties (its multiplicative collations exceed degree 2t), one party per process, groups over several GPUs. */
+typedef struct cozk_shamir_jolt_spartan cozk_shamir_jolt_spartan;
+typedef struct cozk_shamir_jolt_spartan_config {
+    int log_steps;
+    int system; /* 0: the toy system, 1: the Jolt constraint set (as cozk_outer_config) */
+    int degree, num_parties;
+    int devices[COZK_SHAMIR_MAX_PARTIES]; /* one per party */
+    uint64_t seed;
+    uint64_t share_counter, rand_counter;
+} cozk_shamir_jolt_spartan_config;
+typedef struct cozk_shamir_jolt_spartan_result {
+    int verified; /* 1 ok, 0 rejected, -1 not run: verify_spartan and the opened evaluations against the dealer's columns */
+    int grouped;  /* 1: the outer and shift sumchecks ran as groups */
+    uint64_t proof_len;
+    uint8_t proof_digest[32]; /* SHA-256 of the serialized proof */
+    uint64_t n_opened;        /* M */
+    /* host clock, every party's stream drained at both ends; one thread drives the parties in turn: SUMS over parties.  t_build: Az, Bz,
+     * Cz of every sender */
+    double wall_ms, t_build_ms, t_masks_ms, t_outer_ms, t_inner_ms, t_shift_ms, t_openings_ms;
+} cozk_shamir_jolt_spartan_result;
+int cozk_shamir_jolt_spartan_create(const cozk_shamir_jolt_spartan_config* cfg, cozk_shamir_jolt_spartan** out);
+const char* cozk_shamir_jolt_spartan_error(const cozk_shamir_jolt_spartan* h);
+int cozk_shamir_jolt_spartan_destroy(cozk_shamir_jolt_spartan* h);
+int cozk_shamir_jolt_spartan_prove(cozk_shamir_jolt_spartan* h, int verify, cozk_shamir_jolt_spartan_result* res);
+int cozk_shamir_jolt_spartan_proof_bytes(const cozk_shamir_jolt_spartan* h, uint8_t* out, size_t cap);
+/* the masked outer messages [m][p <= 2t], m = 4 round + coefficient (msgs_len = 4 n_tau (2t + 1) elements x 4 u64) */
+size_t cozk_shamir_jolt_spartan_msgs_len(const cozk_shamir_jolt_spartan* h);
+int cozk_shamir_jolt_spartan_msgs(const cozk_shamir_jolt_spartan* h, uint64_t* out, size_t cap);
+/* the t + 1 openers' shares [value][p <= t], in proof order: Az, Bz, Cz(r); 3 coefficients per inner round; shift_claim; 3 coefficients
+ * per shift round; the nvars witness evaluations; the nvars shift-witness evaluations
+ * (finals_len = (3 + 3 log2(4 V) + 1 + 3 log_steps + 2 nvars)(t + 1) elements; nvars = 14 / 78 columns, V = nvars rounded up to a
+ * power of two) */
+size_t cozk_shamir_jolt_spartan_finals_len(const cozk_shamir_jolt_spartan* h);
+int cozk_shamir_jolt_spartan_finals(const cozk_shamir_jolt_spartan* h, uint64_t* out, size_t cap);
+int cozk_shamir_jolt_spartan_get_stats(const cozk_shamir_jolt_spartan* h, cozk_shamir_gp_stats* stats);
 
 /* ---- ONE chained co-jolt worker flow (JoltRep3Prover::prove, co-jolt/src/jolt/vm/jolt/worker.rs:175-266, against its coordinator
  * jolt/vm/jolt/coordinator.rs:118-222): commit-all -> bytecode memory checking -> instruction lookups (primary sumcheck, toggled

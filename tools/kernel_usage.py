@@ -1,6 +1,9 @@
 """Registers / scratch / LDS / occupancy of the kernels of one translation unit, from hipcc -Rpass-analysis=kernel-resource-usage:
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -c co-zkvms_amd/csrc/poly.hip -o /tmp/poly.o -Rpass-analysis=kernel-resource-usage 2> usage.txt
-  python tools/kernel_usage.py usage.txt [name-regex]"""
+  python tools/kernel_usage.py usage.txt [name-regex]
+The group kernels of the Shamir provers (every one must report 0 bytes of scratch; DESIGN.md 4b quotes their lines):
+  python tools/kernel_usage.py usage.txt 'k_(layer|toggle|spartan)_group'
+  python tools/kernel_usage.py usage.txt 'k_(outer|shift)_group_(round|final)'"""
 import re, sys
 txt = open(sys.argv[1]).read()
 pat = sys.argv[2] if len(sys.argv) > 2 else "."

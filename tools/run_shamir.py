@@ -60,7 +60,16 @@ With --spartan, instead, co-noir-spartan of 2^log_n constraints proved by the Sh
   (xxiii) the whole prove with both sumchecks as Spartan groups against the whole prove with COZK_SHAMIR_GP_GROUP=0 (the per-poly calls),
           alternating in this process, proofs, messages and final shares compared; the ungrouped leg is the yardstick.
 --only-group runs nothing but (xxiii):
-  python tools/run_shamir.py --spartan --only-group --log-n 18 --parties 8 --degree 2 --out FILE"""
+  python tools/run_shamir.py --spartan --only-group --log-n 18 --parties 8 --degree 2 --out FILE
+With --jolt-spartan, instead, co-jolt's Spartan worker over 2^log_steps steps proved by the Shamir parties (cozk_shamir_jolt_spartan_*):
+  (xxiv)  the first two rounds of the outer sumcheck (the sums, then the bind with a challenge and the sums) as ONE cozk_outer_group over
+          the senders' cozk_outer states against the senders' cozk_outer_round calls, alternating in this process on fresh states over
+          random columns, outputs compared raw;
+  (xxv)   the whole prove with the outer and shift sumchecks as groups against the whole prove with COZK_SHAMIR_GP_GROUP=0 (the per-sender
+          calls), alternating in this process, >= 30 repetitions each, proofs, messages and final shares compared; the ungrouped leg is
+          the yardstick.
+--only-group runs nothing but (xxv):
+  python tools/run_shamir.py --jolt-spartan --only-group --system jolt --log-steps 18 --parties 8 --degree 2 --out FILE"""
 import argparse, ctypes, hashlib, importlib, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -79,10 +88,15 @@ ap.add_argument("--gp-batch", type=int, default=2, help="with --gp: circuits in 
 ap.add_argument("--only-group", action="store_true", help="with --gp: only the grouped against the ungrouped prove, resharing and king prover; with --tgp: only (xxi)")
 ap.add_argument("--tgp", action="store_true", help="time the toggled Shamir grand product prover instead (--king: the king construct)")
 ap.add_argument("--spartan", action="store_true", help="time co-noir-spartan proved by the Shamir parties instead (--only-group: only the whole prove)")
-ap.add_argument("--seed", type=int, default=2030, help="with --spartan: the instance's seed")
+ap.add_argument("--jolt-spartan", action="store_true", help="time co-jolt's Spartan worker proved by the Shamir parties instead (--only-group: only the whole prove)")
+ap.add_argument("--system", default="jolt", choices=["toy", "jolt"], help="with --jolt-spartan: the constraint system")
+ap.add_argument("--log-steps", type=int, default=18, help="with --jolt-spartan: log2 of the steps")
+ap.add_argument("--seed", type=int, default=2030, help="with --spartan / --jolt-spartan: the instance's seed")
 ap.add_argument("--pairs", type=int, default=8, help="with --tgp: flag columns (pairs of circuits)")
 ap.add_argument("--density", type=int, default=10, help="with --tgp: percent of the flags that are set")
 args = ap.parse_args()
+if args.jolt_spartan:
+    args.log_n = args.log_steps
 cozk = importlib.import_module("co-zkvms_amd")
 L = cozk._lib
 if not torch.cuda.is_available():
@@ -1008,6 +1022,133 @@ def spartan_legs():
     h.close()
     emit(res)
 
+
+def jolt_spartan_legs():
+    """--jolt-spartan: (xxiv) unless --only-group, then (xxv); the harness owns one context per party on this GPU"""
+    if 2 * T + 1 > N or 2 * T > 15:
+        raise SystemExit("run_shamir --jolt-spartan: needs 2 * degree + 1 <= parties and 2 * degree <= 15")
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
+    senders = 2 * T + 1
+    res = {
+        "what": "co-jolt's Spartan worker by Shamir parties: the outer and shift sumchecks as groups (one fused bind + sums launch, one finishing "
+                "launch and one fetch per round for all senders) against the per-sender calls (COZK_SHAMIR_GP_GROUP=0)",
+        "system": args.system, "log_steps": args.log_steps, "steps": n, "parties": N, "degree": T, "senders": senders, "openers": T + 1,
+        "seed": args.seed, "device": torch.cuda.get_device_name(0),
+    }
+    if not args.only_group:
+        OU = importlib.import_module("co-zkvms_amd.outer")
+        if args.system == "jolt":
+            import pyjolt_r1cs as J
+            (uniform, cross, padded), ncols = J.build_system(), J.NUM_INPUTS
+        else:
+            import pyspartan_outer as SO
+            (uniform, cross, padded), ncols = SO.synthetic_system(), 14
+        n_tau = args.log_steps + padded.bit_length() - 1
+        pcs, streams = party_contexts()
+        whole = lambda fn: whole_call(pcs, streams, fn)
+        cols = [[cozk.Rep3DensePolynomial.random(pcs[p], n, 3000 + 100 * p + v, mode=cozk.MODE_PLAIN) for v in range(ncols)] for p in range(senders)]
+        tau = [pow(5, 3 + i, cozk.FR_MOD) for i in range(n_tau)]
+        r = cozk.fr_to_mont_limbs([pow(3, 77, cozk.FR_MOD)])[0]
+        claims = np.ascontiguousarray(cozk.fr_to_mont_limbs([pow(7, 11 + p, cozk.FR_MOD) for p in range(senders)]))
+        mk = lambda: [OU.SpartanOuter(pcs[p], "plain", 0, uniform, cross, cols[p], padded, tau) for p in range(senders)]
+
+        def run_g():
+            members = mk()
+            g = cozk.OuterGroup(pcs[0], members)
+            ms, out = whole(lambda: [g.round_raw(None, claims), g.round_raw(r, claims)])
+            g.free()
+            for st in members:
+                st.free()
+            return ms, out
+
+        def run_s():
+            members = mk()
+
+            def rounds():
+                outs = [np.zeros((senders, 4, 4), dtype=np.uint64) for _ in range(2)]
+                for j in range(2):
+                    for p in range(senders):
+                        c = pcs[p]
+                        c.check(c._l.cozk_outer_round(c.h, members[p].h, r.ctypes.data if j else None, claims[p].ctypes.data, outs[j][p].ctypes.data))
+                return outs
+            out = whole(rounds)
+            for st in members:
+                st.free()
+            return out
+
+        og, os_ = run_g()[1], run_s()[1]
+        assert all(np.array_equal(x, y) for x, y in zip(og, os_)), "the group rounds and the per-sender rounds differ"
+        t_g, t_s = [], []
+        while sum(t_g) < args.min_seconds * 1e3 or sum(t_s) < args.min_seconds * 1e3 or len(t_g) < 6:
+            t_g.append(run_g()[0])
+            t_s.append(run_s()[0])
+        res["first_two_rounds"] = {"group_rounds": stats(t_g), "per_sender_rounds_same_run": stats(t_s),
+                                   "group_vs_per_sender_speedup": round(med(t_s) / med(t_g), 3), "outputs_equal": True}
+        cols = None
+        for pc in pcs:
+            pc.close()
+
+    h = cozk.ShamirJoltSpartanHarness(log_steps=args.log_steps, system=args.system, parties=N, degree=T, devices=0, seed=args.seed)
+    split = ("t_build_ms", "t_masks_ms", "t_outer_ms", "t_inner_ms", "t_shift_ms", "t_openings_ms")
+
+    def leg(ungrouped):
+        if ungrouped:
+            os.environ[GROUP_SWITCH] = "0"  # read by the library on every prove
+        try:
+            r_ = h.prove(verify=False)
+            st = h.stats()
+            return r_, {k: int(getattr(st, k)) for k in ("group_rounds", "single_rounds", "group_finals", "single_finals")}
+        finally:
+            os.environ.pop(GROUP_SWITCH, None)
+
+    rg = h.prove(verify=True)  # warm-up and correctness
+    pg = (h.proof_bytes(rg), h.msgs(), h.finals())
+    os.environ[GROUP_SWITCH] = "0"
+    try:
+        ru = h.prove(verify=True)
+    finally:
+        os.environ.pop(GROUP_SWITCH, None)
+    pu = (h.proof_bytes(ru), h.msgs(), h.finals())
+    assert rg.verified == 1 and ru.verified == 1, "a Shamir Jolt-Spartan proof was rejected: " + h.last_error()
+    assert rg.grouped == 1 and ru.grouped == 0, "the switch did not select the legs"
+    assert pg == pu, "the grouped and the ungrouped prove differ in proof, messages or final shares"
+    digest = bytes(rg.proof_digest)
+    legs = {False: [], True: []}
+    calls = {}
+    while sum(x.wall_ms for x in legs[False]) < args.min_seconds * 1e3 or sum(x.wall_ms for x in legs[True]) < args.min_seconds * 1e3 or len(legs[False]) < 30:
+        for u in (False, True):
+            r_, calls[u] = leg(u)
+            assert bytes(r_.proof_digest) == digest, "a repetition's proof differs"
+            legs[u].append(r_)
+    sums = lambda x: x.t_outer_ms + x.t_shift_ms
+    rep = lambda rs, c: dict(stats([x.wall_ms for x in rs]), driver_split={k: stats([getattr(x, k) for x in rs]) for k in split},
+                             outer_and_shift=stats([sums(x) for x in rs]), calls=c)
+    t_g, t_u = [x.wall_ms for x in legs[False]], [x.wall_ms for x in legs[True]]
+    spread_u = max(t_u) - min(t_u)
+    res["prover"] = {
+        "grouped_whole_prove": rep(legs[False], calls[False]),
+        "ungrouped_whole_prove_same_run": rep(legs[True], calls[True]),
+        "grouped_vs_ungrouped_speedup": round(med(t_u) / med(t_g), 3),
+        "outer_and_shift_grouped_vs_ungrouped_speedup": round(med([sums(x) for x in legs[True]]) / med([sums(x) for x in legs[False]]), 3),
+        "grouped_slower_than_ungrouped_by_ms": round(med(t_g) - med(t_u), 4),
+        "ungrouped_min_max_spread_ms": round(spread_u, 4),
+        "grouped_not_slower_beyond_ungrouped_spread": bool(med(t_g) - med(t_u) <= spread_u),
+        "proofs_messages_finals_equal": True,
+        "proof_sha256": digest.hex(),
+    }
+    res["timing"] = ("whole prove: the driver's host clock from every party's stream drained to every party's stream drained (one thread drives the "
+                     "parties in turn: sums over parties), setup (instance, sharing) outside, Az / Bz / Cz of every sender inside (t_build); first "
+                     "two rounds: from an event on party 0's idle stream to the last of the events behind the parties' streams, state and group "
+                     "creation outside; the grouped and the ungrouped leg alternating in one process, the ungrouped leg being the yardstick; the "
+                     "seed's keys and counters reused across repetitions (timing only)")
+    h.close()
+    emit(res)
+
+
+if args.jolt_spartan:
+    jolt_spartan_legs()
+    ctx.close()
+    raise SystemExit(0)
 
 if args.spartan:
     spartan_legs()
