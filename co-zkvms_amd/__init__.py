@@ -17,8 +17,10 @@ from .poly import (Rep3DensePolynomial, Rep3DenseInterleavedPolynomial, SplitEqP
                    sparse_matvec3, fingerprint_leaves, rep3_mul_vec_local)
 from .harness import Harness, HarnessConfig, HarnessResult
 from .spartan import SpartanHarness, SpartanConfig, SpartanResult
-from .lookups import SparseLayer, SparseStats, sparse_stats, sparse_reset_stats
+from .lookups import SparseLayer, SparseStats, sparse_stats, sparse_reset_stats, PrimaryGroup
 from . import shamir_spartan
 from .shamir_spartan import SpartanGroup, ShamirSpartanHarness, ShamirSpartanConfig, ShamirSpartanResult
 from . import shamir_jolt_spartan
 from .shamir_jolt_spartan import OuterGroup, ShiftGroup, ShamirJoltSpartanHarness, ShamirJoltSpartanConfig, ShamirJoltSpartanResult
+from . import shamir_primary
+from .shamir_primary import ShamirPrimary, ShamirPrimaryConfig, ShamirPrimaryResult

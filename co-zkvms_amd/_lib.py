@@ -190,6 +190,12 @@ SIGNATURES = {
     "cozk_outer_group_final": (_i, [_vp, _vp, _i, _vp]),
     "cozk_outer_group_len": (_sz, [_vp]),
     "cozk_outer_group_free": (_i, [_vp]),
+    "cozk_primary_group_create": (_i, [_vp, _vp, _i, ctypes.c_char_p, _pp]),
+    "cozk_primary_group_level": (_i, [_vp, _i, _u64, ctypes.POINTER(_sz)]),
+    "cozk_primary_group_round_finish": (_i, [_vp, _vp]),
+    "cozk_primary_group_len": (_sz, [_vp]),
+    "cozk_primary_group_level_buffer": (_i, [_vp, _i, _i, _pp, ctypes.POINTER(_sz)]),
+    "cozk_primary_group_free": (_i, [_vp]),
     "cozk_shift_group_create": (_i, [_vp, _vp, _i, _vp, _pp]),
     "cozk_shift_group_round": (_i, [_vp, _vp, _vp]),
     "cozk_shift_group_final": (_i, [_vp, _vp, _i, _vp]),

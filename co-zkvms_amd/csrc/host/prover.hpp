@@ -747,6 +747,20 @@ struct PrimarySumcheckProof {
     }
 };
 
+// The coordinator's arithmetic of one round (coordinator.rs:131-141), whoever summed the evaluations `ev` at X = 0, 2, .., degree (the
+// network coordinator below; the Shamir prover's Lagrange opening, shamir_primary.hpp): insert claim - e(0), interpolate, compress,
+// append, draw the challenge, move the claim on.
+static fe primary_coordinator_round(std::vector<fe> ev, fe& previous_claim, Transcript& tr, PrimarySumcheckProof& proof) {
+    ev.insert(ev.begin() + 1, Fr::sub(previous_claim, ev[0]));  // round_evals.insert(1, previous_claim - round_evals[0])
+    const std::vector<fe> poly = unipoly_from_evals_general(ev);
+    const std::vector<fe> comp = unipoly_compress(poly);
+    tr.append_scalars(comp);
+    proof.compressed_polys.push_back(comp);
+    const fe r_j = tr.challenge_scalar();
+    previous_claim = unipoly_eval(poly, r_j);
+    return r_j;
+}
+
 // prove_primary_sumcheck_rep3 (jolt/vm/instruction_lookups/coordinator.rs:97-150) + the final claims.  n_participants = parties x
 // workers (participant id = worker * parties + party); during the first num_rounds - log_workers rounds every worker
 // sub-net responds and the coordinator adds all of them (:112-128), afterwards only worker 0 of every party does (:107-111)
@@ -759,18 +773,11 @@ static PrimarySumcheckProof coordinate_primary_sumcheck(StarNetCoordinator& net,
     const int all = net.n_workers();
     for (int round = 0; round < num_rounds; round++) {
         const bool split_round = round < num_rounds - log_workers;
-        std::vector<fe> ev = gather_additive(net, split_round ? all : nparties);
-        ev.insert(ev.begin() + 1, Fr::sub(previous_claim, ev[0]));  // round_evals.insert(1, previous_claim - round_evals[0])
-        std::vector<fe> poly = unipoly_from_evals_general(ev);
-        std::vector<fe> comp = unipoly_compress(poly);
-        tr.append_scalars(comp);
-        proof.compressed_polys.push_back(comp);
-        fe r_j = tr.challenge_scalar();
+        const fe r_j = primary_coordinator_round(gather_additive(net, split_round ? all : nparties), previous_claim, tr, proof);
         Writer w;
         w.fr(r_j);
         for (int id = 0; id < (split_round ? all : nparties); id++) net.send_request(id, w.b);
         r_out.push_back(r_j);
-        previous_claim = unipoly_eval(poly, r_j);
     }
     proof.openings = gather_additive(net, nparties);
     tr.append_scalars(proof.openings);

@@ -23,8 +23,8 @@
 //             call): the outer sumcheck is ONE cozk_outer_group over the 2t + 1 senders on sender 0's context, the shift sumcheck ONE
 //             cozk_shift_group over the openers' z_ry against one eq_plus_one.  Otherwise every sender runs cozk_outer_round /
 //             cozk_prod_sumcheck_evals + cozk_poly_bind.  Same bytes either way.
-// Semi-honest.  Not built: the Lasso primary sumcheck by Shamir parties (its multiplicative collations exceed degree 2t), one party per
-// process, groups over several GPUs.
+// Semi-honest.  The Lasso primary sumcheck has a Shamir prover of its own (shamir_primary.hpp).  Not built: one party per process,
+// groups over several GPUs.
 #pragma once
 
 struct cozk_shamir_jolt_spartan : cozk::HarnessHandle {

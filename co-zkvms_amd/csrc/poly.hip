@@ -15,6 +15,7 @@
 #include "poly.hip.hpp"
 #include "prf.hip.hpp"
 #include "fr9.hip.hpp"
+#include "shamir_deal.hip.hpp"
 
 static constexpr int PT = 256;      // threads per block
 static constexpr int MAXBLK = 2048; // grid cap for reducing kernels (>= 8 blocks per CU)
@@ -2980,6 +2981,7 @@ int cozk_layer_claimed_outputs(cozk_ctx* ctx, const cozk_layer* l, uint64_t* out
 #include "spartan_group.inc"
 #include "sparse_layer.inc"
 #include "primary_sumcheck.inc"
+#include "primary_group.inc"
 #include "spartan_outer.inc"
 #include "outer_group.inc"
 #include "spartan_inner.inc"

@@ -3,45 +3,11 @@
 // 10-30), so a party's share vector is a plain FR cozk_vec and the local operators are the existing element-wise kernels.
 #include "poly.hip.hpp"
 #include "prf.hip.hpp"
+#include "shamir_deal.hip.hpp"
 
 #include <string.h>
 
 #include <vector>
-
-// ------------------------------------------------------------------ the small-multiplier Horner step
-// a * p + c mod r for canonical Montgomery residues a, c and a PLAIN integer p <= 32 (the evaluation point of party p):
-// the Montgomery residue of x * p is (x R) * p, so no Montgomery product is needed -- 8 multiply-adds give the 9-word value
-//   t = a p + c <= 32 (r - 1) + (r - 1) < 33 r < 2^260            (r < 2^254)
-// and one quotient estimate brings it back below r.  With T = floor(t / 2^228) (< 2^32) and D = floor(r / 2^228) + 1:
-//   q = floor(T / D) <= (t / 2^228) / (r / 2^228) = t / r, so q <= Q = floor(t / r) and t - q r >= 0;
-//   T > t / 2^228 - 1 and D <= r / 2^228 + 1 give t / r - T / D < (t / r + 1) / (r / 2^228) < 34 / (5 * 10^7) < 10^-6, so
-//   q > t / r - 1 - 10^-6, i.e. q >= Q - 1 and t - q r < 2 r < 2^255: it fits 8 words,
-// and ONE conditional subtraction (reduce_once) makes it canonical.  16 multiply-adds and 2 borrow chains instead of the
-// 128 multiply-adds of a Montgomery product.  Input bound: a, c < r and 0 <= p <= 32; output < r.
-static __device__ __forceinline__ fe fr_mul_small_add(const fe& a, uint32_t p, const fe& c) {
-    uint32_t t[9];
-    uint64_t carry = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        uint64_t m = (uint64_t)a.l[i] * p + c.l[i] + carry;  // < 2^32 * 32 + 2^32 + 2^38
-        t[i] = (uint32_t)m;
-        carry = m >> 32;
-    }
-    t[8] = (uint32_t)carry;
-    const uint32_t T = (t[8] << 28) | (t[7] >> 4);          // t >> 228 (t[7] holds bits 224..255); t < 2^260, so t[8] < 16
-    const uint32_t q = T / ((FrParams::MOD[7] >> 4) + 1u);  // <= 33
-    fe s;
-    uint64_t mc = 0, borrow = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        uint64_t m = (uint64_t)q * FrParams::MOD[i] + mc;
-        mc = m >> 32;
-        uint64_t d = (uint64_t)t[i] - (uint32_t)m - borrow;
-        s.l[i] = (uint32_t)d;
-        borrow = (d >> 63) & 1;
-    }
-    return Fr::reduce_once(s);  // word 8 of t - q r is zero (t - q r < 2^255)
-}
 
 // ------------------------------------------------------------------ share / eval: all parties in one pass
 // shares[p][i] = f_i(p + 1), f_i(x) = v[i] + sum_{c = 1..degree} coef_c[i] x^c (shamir.rs:190-207 `share`, :166-175
@@ -50,28 +16,8 @@ static __device__ __forceinline__ fe fr_mul_small_add(const fe& a, uint32_t p, c
 // (64 B read where the secret is the product of two share vectors, ShamirMulPrfSrc: the re-deal of a multiplication; the
 // same 64 B, contiguous per lane, where the two factors are the interleaved halves L[i] = v[2 i], R[i] = v[2 i + 1] of one GKR
 // layer, ShamirPairsPrfSrc: the re-deal of a tree level of the grand product).
-// prf_fr (prf.hip.hpp) with the two halves of the block read through constant indices: the same value, and fifteen inlined
-// copies of it keep their block words in registers
-static __device__ __forceinline__ fe shamir_prf_fr(const prf_key key, uint64_t j) {
-    for (uint32_t attempt = 0;; attempt++) {
-        uint32_t w[16];
-        chacha12_block(key, j, attempt, w);
-        fe lo, hi;
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            lo.l[i] = w[i];
-            hi.l[i] = w[8 + i];
-        }
-        lo.l[7] &= 0x3fffffffu;
-        hi.l[7] &= 0x3fffffffu;
-        const bool ok_lo = !Fr::geq_mod(lo), ok_hi = !Fr::geq_mod(hi);
-        fe v;
-#pragma unroll
-        for (int i = 0; i < 8; i++) v.l[i] = ok_lo ? lo.l[i] : hi.l[i];
-        if (ok_lo || ok_hi) return Fr::to_mont(v);
-    }
-}
-
+// fr_mul_small_add (the Horner step) and shamir_prf_fr (the coefficients) live in shamir_deal.hip.hpp, shared with the fused re-deal of
+// primary_group.inc.
 struct ShamirOut {
     fe* p[COZK_SHAMIR_MAX_PARTIES];
 };
@@ -292,21 +238,6 @@ static void require_points(const uint32_t* points, size_t k, const char* who) {
         COZK_REQUIRE(points[i] >= 1 && points[i] <= COZK_SHAMIR_MAX_PARTIES, w + ": points must lie in 1..COZK_SHAMIR_MAX_PARTIES");
         COZK_REQUIRE(!((seen >> points[i]) & 1), w + ": points must be distinct");
         seen |= (uint64_t)1 << points[i];
-    }
-}
-
-// lagrange_from_coeff (shamir.rs:273-291): lambda_i = prod_{j != i} x_j / (x_j - x_i), Montgomery form
-static void lagrange_host(const uint32_t* points, size_t k, fe* out) {
-    for (size_t i = 0; i < k; i++) {
-        fe num = Fr::one(), den = Fr::one();
-        const fe xi = Fr::from_u64(points[i]);
-        for (size_t j = 0; j < k; j++) {
-            if (j == i) continue;
-            const fe xj = Fr::from_u64(points[j]);
-            num = Fr::mul(num, xj);
-            den = Fr::mul(den, Fr::sub(xj, xi));
-        }
-        out[i] = Fr::mul(num, Fr::inv(den));
     }
 }
 

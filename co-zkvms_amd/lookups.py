@@ -276,6 +276,67 @@ class PrimarySumcheck:
             pass
 
 
+PRIMARY_GROUP_SYMBOLS = ["cozk_primary_group_create", "cozk_primary_group_level", "cozk_primary_group_round_finish", "cozk_primary_group_len",
+                         "cozk_primary_group_level_buffer", "cozk_primary_group_free"]
+PRIMARY_GROUP_MAX = 15
+
+
+class PrimaryGroup:
+    """k = 2t + 1 PLAIN `PrimarySumcheck` members of one table, one set of flags and one state -- the senders of a Shamir prover --
+    driven on the stream of the driver `ctx` (`cozk_primary_group_*`, csrc/primary_group.inc): one multiplication level with its
+    degree reduction in two launches, one grouped round_finish.  `keys[m]` = member m's t PRF keys (32 bytes each).  The members may
+    belong to other contexts on the same device; the group refers to them and they must outlive it."""
+
+    def __init__(self, ctx, members, keys):
+        self._l = L.lib()
+        self.ctx = ctx
+        self.members = list(members)
+        self.k = len(self.members)
+        arr = (_vp * max(1, self.k))(*[None if m is None else m.h for m in self.members])
+        blob = b"".join(bytes(k) for ks in keys for k in ks)
+        h = _vp()
+        ctx.check(self._l.cozk_primary_group_create(ctx.h, arr, self.k, blob, ctypes.byref(h)))
+        self.h = h
+
+    def __len__(self):
+        return self._l.cozk_primary_group_len(self.h)
+
+    def level(self, level, counter=0):
+        """multiplication level `level` of the current round for all members: every member's slot values re-dealt and combined into
+        every member's level buffer -> n_elems per (sender, receiver) pair (0: nothing launched, the counter stays)"""
+        n = _sz()
+        self.ctx.check(self._l.cozk_primary_group_level(self.h, level, counter, ctypes.byref(n)))
+        return n.value
+
+    def round_finish_raw(self, degree):
+        out = np.zeros((self.k, degree, 4), dtype=np.uint64)
+        self.ctx.check(self._l.cozk_primary_group_round_finish(self.h, out.ctypes.data))
+        return out
+
+    def round_finish(self):
+        """every member's evaluations at X = 0, 2, 3, .., degree: row m is member m's own round_finish"""
+        d = self.members[0].degree()
+        v = mont_limbs_to_int(self.round_finish_raw(d).reshape(-1, 4))
+        return [v[d * m:d * (m + 1)] for m in range(self.k)]
+
+    def level_buffer(self, member, level):
+        """(device address or None, n_elems) of a member's level buffer"""
+        buf, n = _vp(), _sz()
+        self.ctx.check(self._l.cozk_primary_group_level_buffer(self.h, member, level, ctypes.byref(buf), ctypes.byref(n)))
+        return buf.value, n.value
+
+    def free(self):
+        if getattr(self, "h", None):
+            self._l.cozk_primary_group_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class ToggleGroup:
     """ONE PLAIN toggle layer with k fingerprint planes over one copy of the public flags, driven on the stream of the driver `ctx`
     (`cozk_toggle_group_*`): the senders of a Shamir prover.  `flag_vecs` = one U8 Vec of N entries per pair of circuits,

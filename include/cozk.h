@@ -985,6 +985,57 @@ int cozk_primary_round_finish(cozk_ctx* ctx, cozk_primary* p, uint64_t* out_eval
  * out_eval = (a[4], b[4]), eq_eval[4] (may be NULL)  (worker.rs:427-452) */
 int cozk_primary_final_evals(cozk_ctx* ctx, cozk_primary* p, const uint64_t r[4], uint64_t* E_evals,
                              uint64_t* flag_evals, uint64_t out_eval[8], uint64_t eq_eval[4]);
+/* Level groups: one multiplication level, and the last local step of a round, of the primary sumcheck for the k = 2t + 1 SENDERS of a
+ * Shamir prover as one unit of work.  Every slot of a collation program is a sum of products of TWO affine forms, so a party that runs
+ * the PLAIN program on degree-t shares of the memories (and of the earlier slots) holds a point of a degree-2t sharing of the slot; where
+ * Rep3 reshares over the ring, Shamir reduces the degree: sender m re-deals its value z with cozk_shamir_mul_deal's rule
+ *     h[m -> q][pos] = z + sum_{c = 1..t} PRF(keys_m[c - 1], counter + pos) (q + 1)^c,   q = 0 .. 2t,
+ * pos = the element's position in the level buffer, and receiver q stores sum_{m <= 2t} lambda_m h[m -> q][pos], lambda =
+ * lagrange(1 .. 2t + 1), canonical, at pos of ITS level buffer.  Public constants enter every member's single component (PLAIN): the
+ * constant sharing.  Receivers are the 2t + 1 senders only: a party above 2t runs no program and would have no use for a slot value.
+ * A group has k = 2t + 1 members, 3 <= k <= COZK_PRIMARY_GROUP_MAX, k odd: PLAIN cozk_primary made from one instruction table, one set
+ * of public flags, one eq and one length, pairwise distinct, each of a context on the DRIVER's device, all driven through the same
+ * cozk_primary_round_begin calls (round_begin and final_evals stay per member).  keys = k x t x COZK_PRF_KEY_BYTES, member m's t keys at
+ * keys + m t 32; create uploads them to a device table.  The group REFERS to its members: it does not own them, freeing it leaves them
+ * valid, they must outlive it; create drains the stream of every member's context once.  The staging block [k][k][n_elems] of the level
+ * in flight ((2t + 1)^2 x n_elems x 32 bytes) belongs to the group, lives in the driver's pool and grows on demand.
+ *   level         level 1 .. n_levels of the current round for all members: TWO launches whatever k is (deal: item blocks x degree x k
+ *                 workgroups, each reading ONE member's secrets; combine: element blocks x k, the receiver's step).  *n_elems = the
+ *                 elements exchanged per (sender, receiver) pair; 0: nothing is launched and the caller does not advance its counter
+ *                 (which instructions are active where is public, as in the Rep3 path).  Otherwise the next exchange's counter is
+ *                 counter + n_elems.  When the call returns member q's level buffer holds what per-sender cozk_primary_level, one
+ *                 cozk_shamir_mul_deal-rule dealing per sender and one cozk_shamir_combine_vec per receiver would have left there.
+ *   round_finish  out = k x degree x 4 u64; row m is byte for byte cozk_primary_round_finish of member m.  One launch with the member on
+ *                 a grid axis, one finishing launch over all members' rows, one fetch (no launch when there are no items).
+ *   len           the members' current length.
+ *   level_buffer  the device address and element count of member `member`'s level buffer (NULL / 0 when the level holds nothing).
+ * Streams: round_begin and final_evals stay per member and run on the member's own stream, and cozk_primary_round_begin returns with
+ * its last launches (item list, bases) still enqueued there.  So level (when it launches) and round_finish (when there are items) drain,
+ * after their host checks and before their first launch, the stream of every distinct member context other than the driver's: nothing
+ * a member's stream still writes is read by the group's kernels.  Every launch goes on the driver's stream and every call returns with
+ * that stream drained, so a member call that follows sees what the group wrote.  The caller must not run a member's calls on another
+ * thread while a group call is in progress.
+ * Memory: the staging block of the largest level must fit the device beside the members ((2t + 1)^2 x n_elems x 32 bytes: 961 MB at 2^18
+ * cycles, t = 2, uniform mix); a level call that cannot allocate it fails with the allocator's error before any launch and leaves the
+ * members untouched.  The per-sender composition holds the same (2t + 1)^2 dealt vectors, so it is no way around that size; a level
+ * call that deals and combines a slice of the positions at a time is not built.
+ * Refused on the host before any launch,
+ * with COZK_ERR_INVALID_ARG and the text left with the driver (*out is NULL), the members untouched: null arguments, k even or out of
+ * range, a member that is not PLAIN, a duplicate member, a member on another device, members whose table, degree, n_mem or length
+ * differ (create and every call), members whose item counts or level sizes differ (every call), a level outside 1 .. n_levels or a
+ * level call without items.
+ * Not built: a king / double-random variant of the level exchange (its pair length would depend on the public item counts), groups
+ * over several GPUs, one public item list shared by the members.
+ * Parity unpinned (the reference has no Shamir prover); restated in tests/shamir_primary_ref.py. */
+#define COZK_PRIMARY_GROUP_MAX 15 /* 2t + 1 with 2t <= COZK_SHAMIR_MAX_DEGREE */
+typedef struct cozk_primary_group cozk_primary_group;
+int cozk_primary_group_create(cozk_ctx* driver, cozk_primary* const* members, int k, const uint8_t* keys /* k x t x 32 */,
+                              cozk_primary_group** out);
+int cozk_primary_group_level(cozk_primary_group* g, int level, uint64_t counter, size_t* n_elems);
+int cozk_primary_group_round_finish(cozk_primary_group* g, uint64_t* out /* k x degree x 4 */);
+size_t cozk_primary_group_len(const cozk_primary_group* g);
+int cozk_primary_group_level_buffer(const cozk_primary_group* g, int member, int level, const void** buf, size_t* n_elems);
+int cozk_primary_group_free(cozk_primary_group* g);
 
 /* ---- co-jolt's Spartan outer sumcheck over Az / Bz / Cz (co-jolt/src/poly/spartan_interleaved_poly.rs,
  * co-jolt/src/r1cs/spartan/worker.rs:63-120,277-300):  sum_x eq(tau, x) (Az(x) Bz(x) - Cz(x)) = 0.
@@ -1444,8 +1495,9 @@ int cozk_outer_harness_proof_bytes(const cozk_outer_harness* h, uint8_t* out, si
  * cozk_poly_bind (single_rounds = (2t + 1) n_tau + (t + 1) log_steps, single_finals = 2 (t + 1), or t + 1 when log_steps = 0).  Proof,
  * msgs and finals are the same bytes either way.
  * Refused by create before any launch (the handle is returned with its error text): 1 <= t, 2t <= COZK_SHAMIR_MAX_DEGREE,
- * 2t + 1 <= n <= COZK_SHAMIR_MAX_PARTIES, 0 <= log_steps <= 24, system 0 or 1.  Not built: the Lasso primary sumcheck by Shamir
- * parties (its multiplicative collations exceed degree 2t), one party per process, groups over several GPUs. */
+ * 2t + 1 <= n <= COZK_SHAMIR_MAX_PARTIES, 0 <= log_steps <= 24, system 0 or 1.  The Lasso primary sumcheck has a Shamir prover of its
+ * own (cozk_shamir_primary below: its multiplicative collations exceed degree 2t, so a degree reduction runs between their levels).
+ * Not built: one party per process, groups over several GPUs. */
 typedef struct cozk_shamir_jolt_spartan cozk_shamir_jolt_spartan;
 typedef struct cozk_shamir_jolt_spartan_config {
     int log_steps;
@@ -1480,6 +1532,81 @@ int cozk_shamir_jolt_spartan_msgs(const cozk_shamir_jolt_spartan* h, uint64_t* o
 size_t cozk_shamir_jolt_spartan_finals_len(const cozk_shamir_jolt_spartan* h);
 int cozk_shamir_jolt_spartan_finals(const cozk_shamir_jolt_spartan* h, uint64_t* out, size_t cap);
 int cozk_shamir_jolt_spartan_get_stats(const cozk_shamir_jolt_spartan* h, cozk_shamir_gp_stats* stats);
+
+/* ---------------------------------------------------------------- Lasso's primary sumcheck by n Shamir parties ---- */
+/* The primary sumcheck of the instruction lookups (cozk_primary above; the lookups harness's primary phase) proved by n Shamir parties
+ * of degree t, semi-honest, all driven from the calling thread, which owns every party's context and plays the coordinator
+ * (csrc/host/shamir_primary.hpp; the reference has no Shamir prover: parity unpinned; restated in tests/shamir_primary_ref.py).  The
+ * instance is the lookups harness's own for (seed, log_n, n_pairs = n_mem, mix): lookups_instr_table, the instruction of every cycle,
+ * the E streams at seed + 9000 (m + 1), lookup_outputs in the clear.  Every slot of a collation program multiplies two affine forms of
+ * degree-t values and the 2t + 1 senders reduce the degree between the levels (cozk_primary_group above), so each sender runs the
+ * COZK_MODE_PLAIN calls on its shares: THE PROOF IS THE PLAIN PROVER'S, BYTE FOR BYTE (the first proof_len bytes of cozk_lookups with
+ * MODE_PLAIN and primary = 1; oracle/pyprimary.prove under a "cozk-lookups" transcript whose first draw is r_eq), accepted by the same
+ * verifier.
+ *   witness    flags and eq are public.  Column v (E_v for v < n_mem, lookup_outputs = column n_mem) is dealt once with
+ *              cozk_shamir_share_vec's rule at share_counter + v 2^log_n; share key c = the harness key (seed ^ 0x53484152, c),
+ *              c = 0 .. t - 1.  Only parties 0..2t keep their shares: a party above 2t runs no program in this phase.
+ *   rounds     senders 0..2t each hold a PLAIN cozk_primary.  Per round: cozk_primary_round_begin on every sender; every level
+ *              1..n_levels through the exchange; round_finish; sender p's D evaluations + zero_p[D round + k] are opened with
+ *              lagrange(1..2t + 1); then coordinate_primary_sumcheck's arithmetic (claim - e(0) inserted, compressed, appended, the
+ *              challenge drawn).  The transcript has the label "cozk-lookups" and r_eq is drawn first.
+ *   exchange   the e-th exchange with n_elems > 0, in the order they happen, uses the counter mul_counter + (the sum of the earlier
+ *              exchanges' n_elems); sender p's t mul keys: key c = the harness key (seed ^ 0x4D554C54, 64 p + c).
+ *   masks      M = D log_n openings of degree 2t (D = the table's sumcheck degree): ONE dealing (cozk_shamir_rand_inproc's rule) of M
+ *              elements at rand_counter, pair 0 only, zero_p[m] = r2t_p^0[m] - rt_p^0[m]; party p's (3t + 1) rand keys: key j = the harness
+ *              key (seed ^ 0x52414E44, 64 p + j).  A PAIR MUST NEVER BE USED TWICE: the grand product's contract.
+ *   finals     after the last bind E_m(r) and lookup_outputs(r) are degree-t sharings, opened from parties 0..t with lagrange(1..t + 1),
+ *              unmasked; flags(r) are public.  The proof's openings are E, flags, outputs, in that order.
+ * When the senders' contexts are on one device the levels and the finishes run as ONE cozk_primary_group on sender 0's context; otherwise,
+ * or with COZK_SHAMIR_GP_GROUP=0 in the environment (read on every prove), every sender runs cozk_primary_level, deals its level buffer
+ * to the senders (cozk_shamir_scatter: the dealing launch and the peer copies of cozk_shamir_mul_inproc), every receiver runs
+ * cozk_shamir_combine_vec and copies the result into its level buffer, and every sender runs cozk_primary_round_finish.  Proof, msgs
+ * and finals are the same bytes either way.  Stats, with X = the exchanges made (those with n_elems > 0; result.n_exchanges) and
+ * L = the sum over the rounds of n_levels (public: 0 in a round without items):
+ *   grouped    group_rounds = X + log_n,  single_rounds = 0
+ *   per sender group_rounds = 0,          single_rounds = (2t + 1) (L + log_n)
+ *   group_finals = single_finals = 0 either way: the final evaluations are read per opener (cozk_primary_final_evals).
+ * Refused by create before any launch (the handle is returned with its error text): 1 <= t, 2t <= COZK_SHAMIR_MAX_DEGREE,
+ * 2t + 1 <= n <= COZK_SHAMIR_MAX_PARTIES, 1 <= log_n <= 24, 1 <= n_mem <= 128 (what lookups_instr_table admits), mix 0 or 1.
+ * Not built: a king / double-random variant of the level exchange (its pair length depends on the public item counts), one party per
+ * process, groups over several GPUs, one item list shared by the senders, worker sub-nets (log_workers), the primary inside a chained
+ * Shamir flow. */
+typedef struct cozk_shamir_primary cozk_shamir_primary;
+typedef struct cozk_shamir_primary_config {
+    int log_n;  /* cycles = 2^log_n */
+    int n_mem;  /* E polynomials (the lookups harness's n_pairs) */
+    int mix;    /* 0 uniform, 1 sha2-shaped (as cozk_lookups_config) */
+    int degree, num_parties;
+    int devices[COZK_SHAMIR_MAX_PARTIES]; /* one per party */
+    uint64_t seed;
+    uint64_t share_counter, mul_counter, rand_counter;
+    int tamper_final; /* tests: k > 0 adds 1 to element k - 1 of `finals` (an opener's share) before it is opened; verify must reject */
+} cozk_shamir_primary_config;
+typedef struct cozk_shamir_primary_result {
+    int verified; /* 1 ok, 0 rejected, -1 not run: verify_primary_sumcheck and the opened evaluations against the dealer's columns */
+    int grouped;  /* 1: the levels and finishes ran as a group */
+    int degree;   /* D */
+    uint64_t proof_len;
+    uint8_t proof_digest[32]; /* SHA-256 of the serialized proof */
+    uint64_t n_opened;        /* M = D log_n */
+    uint64_t n_exchanges;     /* X: exchanges with n_elems > 0 */
+    uint64_t n_exchanged;     /* the sum of their n_elems: the next free mul counter is mul_counter + n_exchanged */
+    /* host clock, every party's stream drained at both ends; one thread drives the parties in turn: SUMS over parties.  t_build: eq and
+     * cozk_primary_create of every sender */
+    double wall_ms, t_build_ms, t_masks_ms, t_rounds_ms, t_finals_ms;
+} cozk_shamir_primary_result;
+int cozk_shamir_primary_create(const cozk_shamir_primary_config* cfg, cozk_shamir_primary** out);
+const char* cozk_shamir_primary_error(const cozk_shamir_primary* h);
+int cozk_shamir_primary_destroy(cozk_shamir_primary* h);
+int cozk_shamir_primary_prove(cozk_shamir_primary* h, int verify, cozk_shamir_primary_result* res);
+int cozk_shamir_primary_proof_bytes(const cozk_shamir_primary* h, uint8_t* out, size_t cap);
+/* the masked round messages [D round + k][p <= 2t] (msgs_len = D log_n (2t + 1) elements x 4 u64) */
+size_t cozk_shamir_primary_msgs_len(const cozk_shamir_primary* h);
+int cozk_shamir_primary_msgs(const cozk_shamir_primary* h, uint64_t* out, size_t cap);
+/* the t + 1 openers' shares [value][p <= t]: E_0(r) .. E_{n_mem - 1}(r), lookup_outputs(r) (finals_len = (n_mem + 1)(t + 1) elements) */
+size_t cozk_shamir_primary_finals_len(const cozk_shamir_primary* h);
+int cozk_shamir_primary_finals(const cozk_shamir_primary* h, uint64_t* out, size_t cap);
+int cozk_shamir_primary_get_stats(const cozk_shamir_primary* h, cozk_shamir_gp_stats* stats);
 
 /* ---- ONE chained co-jolt worker flow (JoltRep3Prover::prove, co-jolt/src/jolt/vm/jolt/worker.rs:175-266, against its coordinator
  * jolt/vm/jolt/coordinator.rs:118-222): commit-all -> bytecode memory checking -> instruction lookups (primary sumcheck, toggled

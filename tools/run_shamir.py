@@ -69,7 +69,17 @@ With --jolt-spartan, instead, co-jolt's Spartan worker over 2^log_steps steps pr
           calls), alternating in this process, >= 30 repetitions each, proofs, messages and final shares compared; the ungrouped leg is
           the yardstick.
 --only-group runs nothing but (xxv):
-  python tools/run_shamir.py --jolt-spartan --only-group --system jolt --log-steps 18 --parties 8 --degree 2 --out FILE"""
+  python tools/run_shamir.py --jolt-spartan --only-group --system jolt --log-steps 18 --parties 8 --degree 2 --out FILE
+With --primary, instead, Lasso's primary sumcheck of 2^log_n cycles proved by the Shamir parties (cozk_shamir_primary_*):
+  (xxvi)  the first round's multiplication levels and its finish as ONE cozk_primary_group over the senders' PLAIN cozk_primary states
+          (two launches per level, two per finish) against the per-sender composition (cozk_primary_level, the level buffer copied into a
+          vector, cozk_shamir_scatter to the senders, cozk_shamir_combine_vec per receiver, the copy back, cozk_primary_round_finish),
+          alternating in this process on fresh states over random share columns, level buffers and messages compared raw;
+  (xxvii) the whole prove with the exchanges and finishes as level groups against the whole prove with COZK_SHAMIR_GP_GROUP=0 (the
+          per-sender composition), alternating in this process, >= 10 repetitions each, proofs, messages and final shares compared; the
+          ungrouped leg is the yardstick.  Also reported: the staging block's bytes, (2t + 1)^2 x the largest level's n_elems x 32.
+--only-group runs nothing but (xxvii):
+  python tools/run_shamir.py --primary --only-group --log-n 18 --mix uniform --parties 8 --degree 2 --out FILE"""
 import argparse, ctypes, hashlib, importlib, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -89,6 +99,9 @@ ap.add_argument("--only-group", action="store_true", help="with --gp: only the g
 ap.add_argument("--tgp", action="store_true", help="time the toggled Shamir grand product prover instead (--king: the king construct)")
 ap.add_argument("--spartan", action="store_true", help="time co-noir-spartan proved by the Shamir parties instead (--only-group: only the whole prove)")
 ap.add_argument("--jolt-spartan", action="store_true", help="time co-jolt's Spartan worker proved by the Shamir parties instead (--only-group: only the whole prove)")
+ap.add_argument("--primary", action="store_true", help="time Lasso's primary sumcheck proved by the Shamir parties instead (--only-group: only the whole prove)")
+ap.add_argument("--mix", default="uniform", choices=["uniform", "sha2"], help="with --primary: the instruction mix of the trace")
+ap.add_argument("--mems", type=int, default=54, help="with --primary: E polynomials")
 ap.add_argument("--system", default="jolt", choices=["toy", "jolt"], help="with --jolt-spartan: the constraint system")
 ap.add_argument("--log-steps", type=int, default=18, help="with --jolt-spartan: log2 of the steps")
 ap.add_argument("--seed", type=int, default=2030, help="with --spartan / --jolt-spartan: the instance's seed")
@@ -1144,6 +1157,182 @@ def jolt_spartan_legs():
     h.close()
     emit(res)
 
+
+def primary_legs():
+    """--primary: (xxvi) unless --only-group, then (xxvii); the harness owns one context per party on this GPU"""
+    if 2 * T + 1 > N or 2 * T > 15:
+        raise SystemExit("run_shamir --primary: needs 2 * degree + 1 <= parties and 2 * degree <= 15")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path[:0] = [os.path.join(root, "oracle"), os.path.join(root, "tests")]
+    senders = 2 * T + 1
+    res = {
+        "what": "Lasso's primary sumcheck by Shamir parties: the degree reduction between the multiplication levels and the round finishes as "
+                "level groups (two launches per exchange, two per finish, for all senders) against the per-sender composition "
+                "(COZK_SHAMIR_GP_GROUP=0)",
+        "log_n": args.log_n, "cycles": n, "n_mem": args.mems, "mix": args.mix, "parties": N, "degree": T, "senders": senders, "openers": T + 1,
+        "seed": args.seed, "device": torch.cuda.get_device_name(0),
+    }
+    if not args.only_group:
+        import pylookups, primary_ref as PR
+        LK = importlib.import_module("co-zkvms_amd.lookups")
+        import pyref as O
+        instrs = pylookups.instr_table(args.mems)
+        which = [pylookups.mix_instr(1 if args.mix == "sha2" else 0, v) for v in O.synthetic_small(args.seed + 1234567, n, 8)]
+        pcs, streams = party_contexts()
+        pcs, streams = pcs[:senders], streams[:senders]
+        whole = lambda fn: whole_call(pcs, streams, fn)
+        rows = PR.rows(LK, instrs)
+        flag_cols = [np.array([1 if w == i else 0 for w in which], dtype=np.uint8) for i in range(len(instrs))]
+        flags = [[cozk.Vec.from_numpy(pcs[p], c, kind=cozk.SCALAR_U8) for c in flag_cols] for p in range(senders)]
+        E = [[cozk.Rep3DensePolynomial.random(pcs[p], n, 3000 + 100 * p + m, mode=cozk.MODE_PLAIN) for m in range(args.mems)] for p in range(senders)]
+        outs = [cozk.Rep3DensePolynomial.random(pcs[p], n, 2900 + p, mode=cozk.MODE_PLAIN) for p in range(senders)]
+        eqs = [cozk.eq_evals(pcs[p], [pow(5, 3 + i, cozk.FR_MOD) for i in range(args.log_n)]) for p in range(senders)]
+        keys = [[key(16 * p + c) for c in range(T)] for p in range(senders)]
+        pts = list(range(1, senders + 1))
+
+        def mk():
+            prims = [LK.PrimarySumcheck.create(pcs[p], cozk.MODE_PLAIN, 0, rows, flags[p], E[p], outs[p], eqs[p]) for p in range(senders)]
+            begun = [pr.round_begin() for pr in prims]
+            assert all(b == begun[0] for b in begun)
+            return prims, begun[0][1]
+
+        def read(p, ptr, cnt):
+            return np.array(PR.read_fr(cozk, pcs[p], ptr, cnt), dtype=object)
+
+        def run_g(keep=False):
+            prims, n_levels = mk()
+            g = LK.PrimaryGroup(pcs[0], prims, keys)
+            D = prims[0].degree()
+
+            def body():
+                ctr, el = 0, []
+                for level in range(1, n_levels + 1):
+                    el.append(g.level(level, ctr))
+                    ctr += el[-1]
+                return el, g.round_finish_raw(D)
+            ms, (el, msg) = whole(body)
+            bufs = [[read(p, *g.level_buffer(p, lv)) for p in range(senders)] for lv in range(1, n_levels + 1) if el[lv - 1]] if keep else None
+            g.free()
+            for pr in prims:
+                pr.free()
+            return ms, (el, msg, bufs)
+
+        def run_s(keep=False):
+            prims, n_levels = mk()
+            D = prims[0].degree()
+
+            def body():
+                ctr, el, ptrs = 0, [], []
+                for level in range(1, n_levels + 1):
+                    out = [pr.level(level) for pr in prims]
+                    cnt = out[0][2]
+                    el.append(cnt)
+                    if not cnt:
+                        continue
+                    dealt = []
+                    for p in range(senders):
+                        v = cozk.Vec.alloc(pcs[p], cnt)
+                        PR._copy(cozk, pcs[p], v.device_ptr(), out[p][0], 32 * cnt)
+                        dealt.append(v.shamir_scatter(keys[p], T, pcs, counter=ctr))
+                        v.free()
+                    for q in range(senders):
+                        c = cozk.shamir_combine([dealt[p][q] for p in range(senders)], pts, 2 * T)
+                        PR._copy(cozk, pcs[q], out[q][0], c.device_ptr(), 32 * cnt)
+                        c.free()
+                    for d in dealt:
+                        free(d)
+                    ptrs.append([o[0] for o in out])
+                    ctr += cnt
+                msg = np.zeros((senders, D, 4), dtype=np.uint64)
+                for p in range(senders):
+                    pcs[p].check(pcs[p]._l.cozk_primary_round_finish(pcs[p].h, prims[p].h, msg[p].ctypes.data))
+                return el, msg, ptrs
+            ms, (el, msg, ptrs) = whole(body)
+            bufs = [[read(p, ptrs[i][p], cnt) for p in range(senders)] for i, cnt in enumerate(c for c in el if c)] if keep else None
+            for pr in prims:
+                pr.free()
+            return ms, (el, msg, bufs)
+
+        keep = n <= (1 << 12)  # the level buffers are compared as integers on the host: small sizes only; the messages always
+        og, os_ = run_g(keep)[1], run_s(keep)[1]
+        assert og[0] == os_[0] and np.array_equal(og[1], os_[1]), "the group round and the per-sender composition differ"
+        if keep:
+            assert all(np.array_equal(a, b) for la, lb in zip(og[2], os_[2]) for a, b in zip(la, lb)), "the level buffers differ"
+        t_g, t_s = [], []
+        while sum(t_g) < args.min_seconds * 1e3 or sum(t_s) < args.min_seconds * 1e3 or len(t_g) < 6:
+            t_g.append(run_g()[0])
+            t_s.append(run_s()[0])
+        res["first_round"] = {"group_levels_and_finish": stats(t_g), "per_sender_composition_same_run": stats(t_s),
+                              "group_vs_per_sender_speedup": round(med(t_s) / med(t_g), 3), "n_elems_per_level": og[0], "messages_equal": True,
+                              "staging_block_bytes": senders * senders * max(og[0] + [0]) * 32,
+                              "level_buffers_compared": bool(keep),
+                              "note": "the composition copies every level buffer into a vector before it deals it; the prover's own ungrouped path deals "
+                                      "a view of the buffer"}
+        flags = E = outs = eqs = None
+        for pc in pcs:
+            pc.close()
+
+    h = cozk.ShamirPrimary(log_n=args.log_n, n_mem=args.mems, mix=args.mix, parties=N, degree=T, devices=0, seed=args.seed)
+    split = ("t_build_ms", "t_masks_ms", "t_rounds_ms", "t_finals_ms")
+
+    def leg(ungrouped):
+        if ungrouped:
+            os.environ[GROUP_SWITCH] = "0"  # read by the library on every prove
+        try:
+            r_ = h.prove(verify=False)
+            st = h.stats()
+            return r_, {k: int(getattr(st, k)) for k in ("group_rounds", "single_rounds", "group_finals", "single_finals")}
+        finally:
+            os.environ.pop(GROUP_SWITCH, None)
+
+    rg = h.prove(verify=True)  # warm-up and correctness
+    pg = (h.proof_bytes(rg), h.msgs(), h.finals())
+    os.environ[GROUP_SWITCH] = "0"
+    try:
+        ru = h.prove(verify=True)
+    finally:
+        os.environ.pop(GROUP_SWITCH, None)
+    pu = (h.proof_bytes(ru), h.msgs(), h.finals())
+    assert rg.verified == 1 and ru.verified == 1, "a Shamir primary proof was rejected: " + h.last_error()
+    assert rg.grouped == 1 and ru.grouped == 0, "the switch did not select the legs"
+    assert pg == pu, "the grouped and the ungrouped prove differ in proof, messages or final shares"
+    digest = bytes(rg.proof_digest)
+    legs = {False: [], True: []}
+    calls = {}
+    while sum(x.wall_ms for x in legs[False]) < args.min_seconds * 1e3 or sum(x.wall_ms for x in legs[True]) < args.min_seconds * 1e3 or len(legs[False]) < 10:
+        for u in (False, True):
+            r_, calls[u] = leg(u)
+            assert bytes(r_.proof_digest) == digest, "a repetition's proof differs"
+            legs[u].append(r_)
+    rep = lambda rs, c: dict(stats([x.wall_ms for x in rs]), driver_split={k: stats([getattr(x, k) for x in rs]) for k in split}, calls=c)
+    t_g, t_u = [x.wall_ms for x in legs[False]], [x.wall_ms for x in legs[True]]
+    r_g, r_u = [x.t_rounds_ms for x in legs[False]], [x.t_rounds_ms for x in legs[True]]
+    spread_u = max(t_u) - min(t_u)
+    res["prover"] = {
+        "grouped_whole_prove": rep(legs[False], calls[False]),
+        "ungrouped_whole_prove_same_run": rep(legs[True], calls[True]),
+        "grouped_vs_ungrouped_speedup": round(med(t_u) / med(t_g), 3),
+        "rounds_grouped_vs_ungrouped_speedup": round(med(r_u) / med(r_g), 3),
+        "grouped_slower_than_ungrouped_by_ms": round(med(t_g) - med(t_u), 4),
+        "ungrouped_min_max_spread_ms": round(spread_u, 4),
+        "grouped_not_slower_beyond_ungrouped_spread": bool(med(t_g) - med(t_u) <= spread_u),
+        "proofs_messages_finals_equal": True,
+        "proof_sha256": digest.hex(),
+        "sumcheck_degree": int(rg.degree), "exchanges": int(rg.n_exchanges), "elements_exchanged_per_pair": int(rg.n_exchanged),
+    }
+    res["timing"] = ("whole prove: the driver's host clock from every party's stream drained to every party's stream drained (one thread drives the "
+                     "parties in turn: sums over parties), setup (instance, sharing) outside, eq and cozk_primary_create of every sender inside "
+                     "(t_build); first round: from an event on party 0's idle stream to the last of the events behind the senders' streams, state "
+                     "and group creation and round_begin outside; the grouped and the ungrouped leg alternating in one process, the ungrouped "
+                     "leg being the yardstick; the seed's keys and counters reused across repetitions (timing only)")
+    h.close()
+    emit(res)
+
+
+if args.primary:
+    primary_legs()
+    ctx.close()
+    raise SystemExit(0)
 
 if args.jolt_spartan:
     jolt_spartan_legs()
