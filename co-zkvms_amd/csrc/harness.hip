@@ -910,6 +910,7 @@ int cozk_worker_spartan_second_sumcheck(cozk_ctx* ctx, const cozk_worker_params*
 #include "host/outer_harness.hpp"
 #include "host/flow_harness.hpp"
 #include "host/shamir_gp.hpp"
+#include "host/shamir_harness.hpp"
 #include "host/shamir_spartan.hpp"
 #include "host/shamir_jolt_spartan.hpp"
 #include "host/shamir_primary.hpp"

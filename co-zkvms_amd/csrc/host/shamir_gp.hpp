@@ -67,6 +67,13 @@ static inline fe shamir_open(const std::vector<fe>& lambda, const fe* shares) {
     return acc;
 }
 
+// the read-back of recorded openings (*_msgs, *_finals): v = NULL stands for a null handle
+static inline int fe_copy_out(const std::vector<fe>* v, uint64_t* out, size_t cap) {
+    if (!v || !out || cap < v->size()) return COZK_ERR_INVALID_ARG;
+    for (size_t k = 0; k < v->size(); k++) fe_to_u64x4((*v)[k], out + 4 * k);
+    return COZK_OK;
+}
+
 static inline std::vector<fe> shamir_lagrange_first(int k) {
     std::vector<uint32_t> pts((size_t)k);
     for (int p = 0; p < k; p++) pts[(size_t)p] = (uint32_t)p + 1;
@@ -841,16 +848,7 @@ int cozk_shamir_gp_final(const cozk_shamir_gp* h, uint64_t claim[4], uint64_t* r
 size_t cozk_shamir_gp_msgs_len(const cozk_shamir_gp* h) { return h ? h->msgs.size() : 0; }
 size_t cozk_shamir_gp_finals_len(const cozk_shamir_gp* h) { return h ? h->finals.size() : 0; }
 
-int cozk_shamir_gp_msgs(const cozk_shamir_gp* h, uint64_t* out, size_t cap) {
-    if (!h || !out || cap < h->msgs.size()) return COZK_ERR_INVALID_ARG;
-    for (size_t k = 0; k < h->msgs.size(); k++) fe_to_u64x4(h->msgs[k], out + 4 * k);
-    return COZK_OK;
-}
-
-int cozk_shamir_gp_finals(const cozk_shamir_gp* h, uint64_t* out, size_t cap) {
-    if (!h || !out || cap < h->finals.size()) return COZK_ERR_INVALID_ARG;
-    for (size_t k = 0; k < h->finals.size(); k++) fe_to_u64x4(h->finals[k], out + 4 * k);
-    return COZK_OK;
-}
+int cozk_shamir_gp_msgs(const cozk_shamir_gp* h, uint64_t* out, size_t cap) { return cozk::fe_copy_out(h ? &h->msgs : nullptr, out, cap); }
+int cozk_shamir_gp_finals(const cozk_shamir_gp* h, uint64_t* out, size_t cap) { return cozk::fe_copy_out(h ? &h->finals : nullptr, out, cap); }
 
 }  // extern "C"

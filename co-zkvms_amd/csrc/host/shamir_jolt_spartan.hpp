@@ -1,7 +1,8 @@
 // co-jolt's Spartan worker (Rep3UniformSpartanProver::prove, spartan_jolt.hpp; BASELINE's co-jolt configuration) proved by n Shamir
 // parties, all driven from the one thread that owns their contexts and plays the coordinator, as co-noir-spartan is
 // (shamir_spartan.hpp).  The reference has no Shamir prover; tests/shamir_jolt_spartan_ref.py restates this file in big integers.
-// Included by harness.hip behind outer_harness.hpp (the instance, the verifier's view) and shamir_gp.hpp.
+// Included by harness.hip behind outer_harness.hpp (the instance, the verifier's view) and shamir_harness.hpp (the handle base, the keys
+// and the dealing, ShamirProve: the openings, the masks).
 //
 // Why the PLAIN kernels serve: every step of the worker is linear in the witness share or multiplies exactly two secret factors.
 //   Az, Bz, Cz       affine in the witness columns; a constant or a public column is the constant sharing, added to every party's value
@@ -17,8 +18,7 @@
 // Every party's running claim is the opened, public one (the plain worker's own additive claim is that value).  So the proof is the plain
 // prover's, byte for byte (OuterHarness(mode = plain, full = 1), oracle/pyspartan_outer.py run_full), accepted by verify_spartan.
 //
-//   masks     M = 4 (steps_bits + constr_bits) openings of degree 2t: ONE dealing of M elements at rand_counter, pair 0 only
-//             (shamir_gp_zero_masks), m = 4 round + coefficient.  The pair-reuse contract of the grand product applies.
+//   masks     M = 4 (steps_bits + constr_bits) openings of degree 2t (ShamirProve::deal_masks at rand_counter), m = 4 round + coefficient.
 //   grouped   when the senders' contexts are on one device (shamir_gp_grouped; COZK_SHAMIR_GP_GROUP=0 switches it off, read on every
 //             call): the outer sumcheck is ONE cozk_outer_group over the 2t + 1 senders on sender 0's context, the shift sumcheck ONE
 //             cozk_shift_group over the openers' z_ry against one eq_plus_one.  Otherwise every sender runs cozk_outer_round /
@@ -27,16 +27,11 @@
 // groups over several GPUs.
 #pragma once
 
-struct cozk_shamir_jolt_spartan : cozk::HarnessHandle {
+struct cozk_shamir_jolt_spartan : cozk::ShamirHarness {
     cozk_shamir_jolt_spartan_config cfg;
     cozk_outer_harness inst;  // the outer harness's instance of (seed, log_steps, system) and the verifier's view; it has no parties here
-    int t = 0, n = 0;
     std::vector<cozk::HarnessParty> parties;
     std::vector<std::vector<cozk::PolyH>> cols;  // [p][v]: party p's column v (public columns: the clear values), PLAIN, of its context
-    std::vector<std::vector<uint8_t>> rand_keys;
-    std::vector<fe> msgs;    // [m][p <= 2t], masked
-    std::vector<fe> finals;  // [value][p <= t], in proof order
-    cozk_shamir_gp_stats stats{};
 };
 
 namespace {
@@ -45,51 +40,23 @@ typedef Handle<cozk_outer_group, cozk_outer_group_free> OuterGroupH;
 typedef Handle<cozk_shift_group, cozk_shift_group_free> ShiftGroupH;
 
 static void shamir_jolt_spartan_prove(cozk_shamir_jolt_spartan* h, bool verify, cozk_shamir_jolt_spartan_result* res) {
-    const int t = h->t, n = h->n, senders = 2 * t + 1, openers = t + 1;
+    ShamirProve sp(h, verify);
+    const int senders = sp.senders, openers = sp.openers;
     const jolt::System& sys = h->inst.sys;
     const size_t N = h->inst.N, V = spartan_vars_padded(sys), nvars = (size_t)h->inst.ncols;
     const int steps_bits = h->cfg.log_steps, constr_bits = ceil_log2(sys.padded), n_tau = steps_bits + constr_bits;
-    std::vector<cozk_ctx*> pcs((size_t)n);
-    for (int p = 0; p < n; p++) pcs[(size_t)p] = h->parties[(size_t)p].ctx;
-    cozk_ctx* const c0 = pcs[0];
-    const ShamirGpArgs a{pcs.data(), nullptr, 0, t, n, nullptr, verify};
-    const bool grouped = shamir_gp_grouped(a);
-    const std::vector<fe> lam2t = shamir_lagrange_first(senders), lamt = shamir_lagrange_first(openers);
-    h->msgs.clear();
-    h->finals.clear();
-    h->stats = cozk_shamir_gp_stats{};
-    auto set_dev = [&](int p) { HIP_TRY(hipSetDevice(pcs[(size_t)p]->device)); };
-    auto open_t = [&](const fe* sh) {  // degree t, unmasked; the openers' shares are part of `finals`
-        for (int p = 0; p < openers; p++) h->finals.push_back(sh[p]);
-        return shamir_open(lamt, sh);
-    };
-    // one round message of a degree-2 sumcheck from the openers' (g(0), g(2)) and the public running claim: every coefficient is opened
-    auto open_quadratic = [&](fe (*e02)[2], fe& claim, std::vector<std::vector<fe>>& compressed, Transcript& tr) {
-        fe cf[COZK_SHAMIR_MAX_PARTIES][3];
-        for (int p = 0; p < openers; p++) {
-            const fe pts[3] = {e02[p][0], Fr::sub(claim, e02[p][0]), e02[p][1]};
-            unipoly_from_evals(pts, 3, cf[p]);
-        }
-        std::vector<fe> poly(3);
-        for (int i = 0; i < 3; i++) {
-            fe sh[COZK_SHAMIR_MAX_PARTIES];
-            for (int p = 0; p < openers; p++) sh[p] = cf[p][i];
-            poly[(size_t)i] = open_t(sh);
-        }
-        const std::vector<fe> comp = unipoly_compress(poly);
-        tr.append_scalars(comp);
-        const fe r = tr.challenge_scalar();
-        claim = unipoly_eval(poly, r);
-        compressed.push_back(comp);
-        return r;
-    };
+    const std::vector<cozk_ctx*>& pcs = sp.pcs;
+    cozk_ctx* const c0 = sp.c0;
+    const bool grouped = sp.grouped;
+    auto set_dev = [&](int p) { sp.set_dev(p); };
+    auto open_t = [&](const fe* sh) { return sp.open_t(sh); };
     auto col_ptrs = [&](int p) {
         std::vector<const cozk_poly*> cc;
         for (const PolyH& c : h->cols[(size_t)p]) cc.push_back(c.h);
         return cc;
     };
     JoltSpartanProof pf;
-    shamir_gp_sync_all(a);
+    sp.sync_all();
     const double t0 = now_ms();
     Transcript tr("cozk-spartan");
     const std::vector<fe> tau = tr.challenge_vector((size_t)n_tau);
@@ -104,13 +71,11 @@ static void shamir_jolt_spartan_prove(cozk_shamir_jolt_spartan* h, bool verify, 
                      "outer_create");
         }
     }
-    shamir_gp_sync_all(a);
+    sp.sync_all();
     const double t1 = now_ms();
     // ---- masks
     const size_t M = (size_t)4 * (size_t)n_tau;
-    std::vector<const uint8_t*> rk((size_t)n);
-    for (int p = 0; p < n; p++) rk[(size_t)p] = h->rand_keys[(size_t)p].data();
-    const std::vector<std::vector<fe>> zero = shamir_gp_zero_masks(a, rk.data(), h->cfg.rand_counter, M);
+    sp.deal_masks(h->cfg.rand_counter, M);
     const double t2 = now_ms();
     // ---- outer sumcheck
     std::vector<fe> outer_rs;
@@ -138,14 +103,7 @@ static void shamir_jolt_spartan_prove(cozk_shamir_jolt_spartan* h, bool verify, 
                 }
             }
             std::vector<fe> poly(4);
-            for (int i = 0; i < 4; i++) {
-                fe sh[COZK_SHAMIR_MAX_PARTIES];
-                for (int p = 0; p < senders; p++) {
-                    sh[p] = Fr::add(fe_from_u64x4(cf.data() + 16 * p + 4 * i), zero[(size_t)p][(size_t)(4 * j + i)]);
-                    h->msgs.push_back(sh[p]);
-                }
-                poly[(size_t)i] = shamir_open(lam2t, sh);
-            }
+            for (int i = 0; i < 4; i++) poly[(size_t)i] = sp.open_2t(cf.data() + 4 * i, 16, (size_t)(4 * j + i));
             const std::vector<fe> comp = unipoly_compress(poly);
             tr.append_scalars(comp);
             const fe r = tr.challenge_scalar();
@@ -172,12 +130,9 @@ static void shamir_jolt_spartan_prove(cozk_shamir_jolt_spartan* h, bool verify, 
         for (int q = 0; q < 3; q++) pf.outer.claims.push_back(open_t(fin[q]));
         tr.append_scalars(pf.outer.claims);
         g = OuterGroupH();
-        for (int p = 0; p < senders; p++) {
-            set_dev(p);
-            st[(size_t)p] = OuterH();
-        }
+        sp.release(st);
     }
-    shamir_gp_sync_all(a);
+    sp.sync_all();
     const double t3 = now_ms();
     // ---- inner sumcheck, on the host
     const std::vector<fe> outer_r(outer_rs.rbegin(), outer_rs.rend());
@@ -220,7 +175,7 @@ static void shamir_jolt_spartan_prove(cozk_shamir_jolt_spartan* h, bool verify, 
                 e02[p][0] = e0;
                 e02[p][1] = e2;
             }
-            const fe r_j = open_quadratic(e02, claim, pf.inner.compressed_polys, tr);
+            const fe r_j = sp.open_quadratic(e02, claim, pf.inner.compressed_polys, tr);
             inner_r.push_back(r_j);
             for (size_t i = 0; i < half; i++) abc[i] = Fr::add(abc[i], Fr::mul(Fr::sub(abc[i + half], abc[i]), r_j));
             abc.resize(half);
@@ -283,7 +238,7 @@ static void shamir_jolt_spartan_prove(cozk_shamir_jolt_spartan* h, bool verify, 
                 fe e02[COZK_SHAMIR_MAX_PARTIES][2];
                 for (int p = 0; p < openers; p++)
                     for (int e = 0; e < 2; e++) e02[p][e] = fe_from_u64x4(ev.data() + 8 * p + 4 * e);
-                const fe r_j = open_quadratic(e02, claim, pf.shift.compressed_polys, tr);
+                const fe r_j = sp.open_quadratic(e02, claim, pf.shift.compressed_polys, tr);
                 shift_r.push_back(r_j);
                 fe_to_u64x4(r_j, rr);
             }
@@ -300,17 +255,11 @@ static void shamir_jolt_spartan_prove(cozk_shamir_jolt_spartan* h, bool verify, 
                 }
             }
             g = ShiftGroupH();
-            for (size_t p = 0; p < ep.size(); p++) {
-                set_dev((int)p);
-                ep[p] = PolyH();
-            }
+            sp.release(ep);
         }
-        for (int p = 0; p < openers; p++) {
-            set_dev(p);
-            zry[(size_t)p] = PolyH();
-        }
+        sp.release(zry);
     }
-    shamir_gp_sync_all(a);
+    sp.sync_all();
     const double t5 = now_ms();
     // ---- the two claim exchanges: every column at rx_step, then at the shift point
     for (int which = 0; which < 2; which++) {
@@ -333,12 +282,8 @@ static void shamir_jolt_spartan_prove(cozk_shamir_jolt_spartan* h, bool verify, 
         }
         (void)tr.challenge_scalar();  // receive_claims draws rho for the batched opening that a whole Jolt proof reduces
     }
-    for (int p = 0; p < openers; p++) {
-        set_dev(p);
-        eq_step[(size_t)p] = VecH();
-        eqp1_step[(size_t)p] = VecH();
-    }
-    shamir_gp_sync_all(a);
+    sp.release(eq_step, eqp1_step);
+    sp.sync_all();
     const double t6 = now_ms();
     res->verified = -1;
     if (verify) {
@@ -398,7 +343,8 @@ int cozk_shamir_jolt_spartan_create(const cozk_shamir_jolt_spartan_config* cfg, 
         shamir_gp_require_parties(w, cfg->degree, cfg->num_parties);
         COZK_REQUIRE(cfg->log_steps >= 0 && cfg->log_steps <= 24, w + ": log_steps out of range (0..24)");
         COZK_REQUIRE(cfg->system == 0 || cfg->system == 1, w + ": system is 0 (toy) or 1 (the Jolt constraint set)");
-        const int t = h->t = cfg->degree, n = h->n = cfg->num_parties;
+        h->t = cfg->degree;
+        const int n = h->n = cfg->num_parties;
         // the outer harness's own instance
         cozk_outer_harness& in = h->inst;
         memset(&in.cfg, 0, sizeof in.cfg);
@@ -420,18 +366,13 @@ int cozk_shamir_jolt_spartan_create(const cozk_shamir_jolt_spartan_config* cfg, 
         }
         outer_build_clear(&in);
         h->parties.resize((size_t)n);
-        std::vector<cozk_ctx*> pcs((size_t)n);
         for (int p = 0; p < n; p++) {
             h->parties[(size_t)p].party = p;
             h->parties[(size_t)p].open_ctx(cfg->devices[p], "shamir_jolt_spartan: cannot create a context (no HIP device?)");
-            pcs[(size_t)p] = h->parties[(size_t)p].ctx;
+            h->pcs.push_back(h->parties[(size_t)p].ctx);
         }
-        std::vector<uint8_t> skeys((size_t)t * COZK_PRF_KEY_BYTES);
-        for (int c = 0; c < t; c++) harness_prf_key(cfg->seed ^ 0x53484152ull, (uint64_t)c, skeys.data() + (size_t)c * COZK_PRF_KEY_BYTES);
-        h->rand_keys.assign((size_t)n, std::vector<uint8_t>((size_t)(3 * t + 1) * COZK_PRF_KEY_BYTES));
-        for (int p = 0; p < n; p++)
-            for (int j = 0; j <= 3 * t; j++)
-                harness_prf_key(cfg->seed ^ 0x52414E44ull, (uint64_t)(64 * p + j), h->rand_keys[(size_t)p].data() + (size_t)j * COZK_PRF_KEY_BYTES);
+        const std::vector<cozk_ctx*>& pcs = h->pcs;
+        const std::vector<uint8_t> skeys = shamir_harness_keys(h, cfg->seed);
         // the witness: a public column stays public at every party, a shared one is dealt once, column v at share_counter + v num_steps
         h->cols.resize((size_t)n);
         for (int v = 0; v < in.ncols; v++) {
@@ -445,17 +386,8 @@ int cozk_shamir_jolt_spartan_create(const cozk_shamir_jolt_spartan_config* cfg, 
             }
             HIP_TRY(hipSetDevice(pcs[0]->device));
             VecH cv = upload_fe(pcs[0], in.clear[(size_t)v]);
-            std::vector<cozk_vec*> sh((size_t)n, nullptr);
-            rc_check(cozk_shamir_scatter(pcs[0], cv.h, skeys.data(), t, n, cfg->share_counter + (uint64_t)v * (uint64_t)in.N, pcs.data(), sh.data()), pcs[0],
-                     "shamir_scatter");
-            std::vector<VecH> own;
-            for (int p = 0; p < n; p++) own.emplace_back(sh[(size_t)p]);
-            for (int p = 0; p < n; p++) {
-                HIP_TRY(hipSetDevice(pcs[(size_t)p]->device));
-                h->cols[(size_t)p].push_back(plain_poly(pcs[(size_t)p], own[(size_t)p]));
-                HIP_TRY(hipStreamSynchronize(pcs[(size_t)p]->stream));
-            }
-            HIP_TRY(hipSetDevice(pcs[0]->device));
+            std::vector<PolyH> dealt = shamir_deal_column(h, cv, skeys, cfg->share_counter + (uint64_t)v * (uint64_t)in.N, n);
+            for (int p = 0; p < n; p++) h->cols[(size_t)p].push_back(std::move(dealt[(size_t)p]));
         }
     });
 }
@@ -470,26 +402,10 @@ int cozk_shamir_jolt_spartan_destroy(cozk_shamir_jolt_spartan* h) {
 }
 
 int cozk_shamir_jolt_spartan_prove(cozk_shamir_jolt_spartan* h, int verify, cozk_shamir_jolt_spartan_result* res) {
-    if (!h || !res) return COZK_ERR_INVALID_ARG;
-    memset(res, 0, sizeof *res);
-    res->verified = -1;
-    if ((int)h->parties.size() != h->n || h->cols.size() != (size_t)h->n || h->n == 0 || h->cols.back().size() != (size_t)h->inst.ncols) {
-        h->error = "shamir_jolt_spartan_prove: the harness was not built";
-        return COZK_ERR_INVALID_ARG;
-    }
-    h->error.clear();
-    try {
-        shamir_jolt_spartan_prove(h, verify != 0, res);
-    } catch (const CozkError& e) {
-        h->error = e.what();
-        for (auto& ps : h->parties)
-            if (ps.ctx) (void)hipStreamSynchronize(ps.ctx->stream);
-        return e.code;
-    } catch (const std::exception& e) {
-        h->error = e.what();
-        return COZK_ERR_INTERNAL;
-    }
-    return COZK_OK;
+    return shamir_harness_prove(
+        h, res, "shamir_jolt_spartan",
+        [](const cozk_shamir_jolt_spartan* x) { return x->cols.size() == (size_t)x->n && x->cols.back().size() == (size_t)x->inst.ncols; },
+        [&](cozk_shamir_jolt_spartan* x, cozk_shamir_jolt_spartan_result* r) { shamir_jolt_spartan_prove(x, verify != 0, r); });
 }
 
 int cozk_shamir_jolt_spartan_proof_bytes(const cozk_shamir_jolt_spartan* h, uint8_t* out, size_t cap) { return harness_proof_bytes(h, out, cap); }
@@ -497,22 +413,8 @@ int cozk_shamir_jolt_spartan_proof_bytes(const cozk_shamir_jolt_spartan* h, uint
 size_t cozk_shamir_jolt_spartan_msgs_len(const cozk_shamir_jolt_spartan* h) { return h ? h->msgs.size() : 0; }
 size_t cozk_shamir_jolt_spartan_finals_len(const cozk_shamir_jolt_spartan* h) { return h ? h->finals.size() : 0; }
 
-int cozk_shamir_jolt_spartan_msgs(const cozk_shamir_jolt_spartan* h, uint64_t* out, size_t cap) {
-    if (!h || !out || cap < h->msgs.size()) return COZK_ERR_INVALID_ARG;
-    for (size_t k = 0; k < h->msgs.size(); k++) fe_to_u64x4(h->msgs[k], out + 4 * k);
-    return COZK_OK;
-}
-
-int cozk_shamir_jolt_spartan_finals(const cozk_shamir_jolt_spartan* h, uint64_t* out, size_t cap) {
-    if (!h || !out || cap < h->finals.size()) return COZK_ERR_INVALID_ARG;
-    for (size_t k = 0; k < h->finals.size(); k++) fe_to_u64x4(h->finals[k], out + 4 * k);
-    return COZK_OK;
-}
-
-int cozk_shamir_jolt_spartan_get_stats(const cozk_shamir_jolt_spartan* h, cozk_shamir_gp_stats* stats) {
-    if (!h || !stats) return COZK_ERR_INVALID_ARG;
-    *stats = h->stats;
-    return COZK_OK;
-}
+int cozk_shamir_jolt_spartan_msgs(const cozk_shamir_jolt_spartan* h, uint64_t* out, size_t cap) { return fe_copy_out(h ? &h->msgs : nullptr, out, cap); }
+int cozk_shamir_jolt_spartan_finals(const cozk_shamir_jolt_spartan* h, uint64_t* out, size_t cap) { return fe_copy_out(h ? &h->finals : nullptr, out, cap); }
+int cozk_shamir_jolt_spartan_get_stats(const cozk_shamir_jolt_spartan* h, cozk_shamir_gp_stats* stats) { return shamir_harness_stats(h, stats); }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // lookups harness's primary phase) proved by n Shamir parties, all driven from the one thread that owns their contexts and plays the
 // coordinator, as the Spartan workers are (shamir_jolt_spartan.hpp).  The reference has no Shamir prover; tests/shamir_primary_ref.py
 // restates this file in big integers.  Included by harness.hip behind lookups_harness.hpp (the instance, the verifier's view) and
-// shamir_gp.hpp.
+// shamir_harness.hpp (the handle base, the keys and the dealing, ShamirProve: the openings, the masks).
 //
 // Why the PLAIN kernels serve.  csrc/primary_sumcheck.inc compiles every multiplicative collation into slots that are sums of products
 // of TWO affine forms, with a last step that stays local.  A party that runs the PLAIN program on degree-t shares therefore holds a
@@ -15,11 +15,10 @@
 // byte (LookupsHarness(mode = plain, primary = 1) up to proof_len; oracle/pyprimary.prove), accepted by verify_primary_sumcheck.
 //
 //   witness   flags and eq public.  E_m and lookup_outputs dealt by cozk_shamir_share_vec's rule, column v at share_counter + v 2^log_n,
-//             lookup_outputs = column n_mem; share key c = the harness key (seed ^ 0x53484152, c).  Only the senders keep their shares.
+//             lookup_outputs = column n_mem; the share keys are shamir_harness_keys'.  Only the senders keep their shares.
 //   exchange  e-th exchange with n_elems > 0, in the order they happen: counter mul_counter + sum of the earlier exchanges' n_elems;
 //             sender p's mul key c = the harness key (seed ^ 0x4D554C54, 64 p + c), c < t.
-//   masks     M = D log_n openings of degree 2t: ONE dealing at rand_counter, pair 0 (shamir_gp_zero_masks), m = D round + k.  The
-//             pair-reuse contract of the grand product applies.
+//   masks     M = D log_n openings of degree 2t (ShamirProve::deal_masks at rand_counter), m = D round + k.
 //   finals    E_m(r), lookup_outputs(r): degree t, opened from parties 0..t, unmasked; flags(r) public.
 //   grouped   senders' contexts on one device and shamir_gp_grouped (COZK_SHAMIR_GP_GROUP=0 switches it off, read on every prove): ONE
 //             cozk_primary_group on sender 0's context: a level call per exchange, a grouped finish per round.  Otherwise per sender
@@ -30,18 +29,15 @@
 // a chained Shamir flow.
 #pragma once
 
-struct cozk_shamir_primary : cozk::HarnessHandle {
+// msgs: [D round + k][p <= 2t]; finals: E_0 .. E_{n_mem - 1}, lookup_outputs
+struct cozk_shamir_primary : cozk::ShamirHarness {
     cozk_shamir_primary_config cfg;
     cozk_lookups inst;  // the lookups harness's instance of (seed, log_n, n_pairs = n_mem, mix) and the verifier's view; it has no parties here
-    int t = 0, n = 0;
     std::vector<cozk::HarnessParty> parties;
     std::vector<std::vector<cozk::VecH>> flags;  // [p <= 2t][instruction]: the public 0/1 columns on the sender's context
     std::vector<std::vector<cozk::PolyH>> E;     // [p <= 2t][m]: the sender's share of E_m, PLAIN
     std::vector<cozk::PolyH> outputs;            // [p <= 2t]
-    std::vector<std::vector<uint8_t>> rand_keys, mul_keys;
-    std::vector<fe> msgs;    // [D round + k][p <= 2t], masked
-    std::vector<fe> finals;  // [value][p <= t]: E_0 .. E_{n_mem - 1}, lookup_outputs
-    cozk_shamir_gp_stats stats{};
+    std::vector<std::vector<uint8_t>> mul_keys;  // [p][t]: the keys of sender p's re-deals
 };
 
 namespace {
@@ -49,20 +45,15 @@ namespace {
 typedef Handle<cozk_primary_group, cozk_primary_group_free> PrimaryGroupH;
 
 static void shamir_primary_prove(cozk_shamir_primary* h, bool verify, cozk_shamir_primary_result* res) {
-    const int t = h->t, n = h->n, senders = 2 * t + 1, openers = t + 1, log_n = h->cfg.log_n;
+    ShamirProve sp(h, verify);
+    const int t = sp.t, senders = sp.senders, openers = sp.openers, log_n = h->cfg.log_n;
     const size_t n_mem = (size_t)h->cfg.n_mem, n_instr = h->inst.instrs.size();
-    std::vector<cozk_ctx*> pcs((size_t)n);
-    for (int p = 0; p < n; p++) pcs[(size_t)p] = h->parties[(size_t)p].ctx;
-    cozk_ctx* const c0 = pcs[0];
-    const ShamirGpArgs a{pcs.data(), nullptr, 0, t, n, nullptr, verify};
-    const bool grouped = shamir_gp_grouped(a);
-    const std::vector<fe> lam2t = shamir_lagrange_first(senders), lamt = shamir_lagrange_first(openers);
-    h->msgs.clear();
-    h->finals.clear();
-    h->stats = cozk_shamir_gp_stats{};
-    auto set_dev = [&](int p) { HIP_TRY(hipSetDevice(pcs[(size_t)p]->device)); };
+    const std::vector<cozk_ctx*>& pcs = sp.pcs;
+    cozk_ctx* const c0 = sp.c0;
+    const bool grouped = sp.grouped;
+    auto set_dev = [&](int p) { sp.set_dev(p); };
     PrimarySumcheckProof pf;
-    shamir_gp_sync_all(a);
+    sp.sync_all();
     const double t0 = now_ms();
     Transcript tr("cozk-lookups");
     const std::vector<fe> r_eq = tr.challenge_vector((size_t)log_n);
@@ -85,13 +76,11 @@ static void shamir_primary_prove(cozk_shamir_primary* h, bool verify, cozk_shami
         }
     }
     const int D = cozk_primary_degree(prims[0].h);
-    shamir_gp_sync_all(a);
+    sp.sync_all();
     const double t1 = now_ms();
     // ---- masks
     const size_t M = (size_t)D * (size_t)log_n;
-    std::vector<const uint8_t*> rk((size_t)n);
-    for (int p = 0; p < n; p++) rk[(size_t)p] = h->rand_keys[(size_t)p].data();
-    const std::vector<std::vector<fe>> zero = shamir_gp_zero_masks(a, rk.data(), h->cfg.rand_counter, M);
+    sp.deal_masks(h->cfg.rand_counter, M);
     const double t2 = now_ms();
     // ---- rounds
     PrimaryGroupH g;
@@ -194,20 +183,13 @@ static void shamir_primary_prove(cozk_shamir_primary* h, bool verify, cozk_shami
             }
         }
         std::vector<fe> opened((size_t)D);
-        for (int k = 0; k < D; k++) {
-            fe sh[COZK_SHAMIR_MAX_PARTIES];
-            for (int p = 0; p < senders; p++) {
-                sh[p] = Fr::add(fe_from_u64x4(ev.data() + (size_t)4 * (D * p + k)), zero[(size_t)p][(size_t)(D * round + k)]);
-                h->msgs.push_back(sh[p]);
-            }
-            opened[(size_t)k] = shamir_open(lam2t, sh);
-        }
+        for (int k = 0; k < D; k++) opened[(size_t)k] = sp.open_2t(ev.data() + 4 * k, (size_t)4 * D, (size_t)(D * round + k));
         const fe r_j = primary_coordinator_round(opened, claim, tr, pf);
         rs.push_back(r_j);
         fe_to_u64x4(r_j, rr);
     }
     g = PrimaryGroupH();
-    shamir_gp_sync_all(a);
+    sp.sync_all();
     const double t3 = now_ms();
     // ---- the final claims: E(r) and lookup_outputs(r) from the openers, flags(r) public
     {
@@ -220,12 +202,10 @@ static void shamir_primary_prove(cozk_shamir_primary* h, bool verify, cozk_shami
                      pcs[(size_t)p], "primary_final_evals");
         }
         const size_t tamper = h->cfg.tamper_final > 0 ? (size_t)h->cfg.tamper_final - 1 : (size_t)-1;
-        auto open_t = [&](fe* sh) {
-            for (int p = 0; p < openers; p++) {
-                if (h->finals.size() == tamper) sh[p] = Fr::add(sh[p], Fr::one());
-                h->finals.push_back(sh[p]);
-            }
-            return shamir_open(lamt, sh);
+        auto open_t = [&](fe* sh) {  // tamper_final: one opener's share of one value is off by one, in `finals` and in the opening
+            for (int p = 0; p < openers; p++)
+                if (h->finals.size() + (size_t)p == tamper) sh[p] = Fr::add(sh[p], Fr::one());
+            return sp.open_t(sh);
         };
         for (size_t m = 0; m <= n_mem; m++) {
             fe sh[COZK_SHAMIR_MAX_PARTIES];
@@ -239,11 +219,8 @@ static void shamir_primary_prove(cozk_shamir_primary* h, bool verify, cozk_shami
         }
         tr.append_scalars(pf.openings);
     }
-    for (int p = 0; p < senders; p++) {
-        set_dev(p);
-        prims[(size_t)p] = PrimaryH();
-    }
-    shamir_gp_sync_all(a);
+    sp.release(prims);
+    sp.sync_all();
     const double t4 = now_ms();
     res->verified = -1;
     if (verify) {
@@ -343,22 +320,17 @@ int cozk_shamir_primary_create(const cozk_shamir_primary_config* cfg, cozk_shami
         lookups_setup_primary_clear(&in);
         const size_t N = in.N;
         h->parties.resize((size_t)n);
-        std::vector<cozk_ctx*> pcs((size_t)n);
         for (int p = 0; p < n; p++) {
             h->parties[(size_t)p].party = p;
             h->parties[(size_t)p].open_ctx(cfg->devices[p], "shamir_primary: cannot create a context (no HIP device?)");
-            pcs[(size_t)p] = h->parties[(size_t)p].ctx;
+            h->pcs.push_back(h->parties[(size_t)p].ctx);
         }
-        std::vector<uint8_t> skeys((size_t)t * COZK_PRF_KEY_BYTES);
-        for (int c = 0; c < t; c++) harness_prf_key(cfg->seed ^ 0x53484152ull, (uint64_t)c, skeys.data() + (size_t)c * COZK_PRF_KEY_BYTES);
-        h->rand_keys.assign((size_t)n, std::vector<uint8_t>((size_t)(3 * t + 1) * COZK_PRF_KEY_BYTES));
+        const std::vector<cozk_ctx*>& pcs = h->pcs;
+        const std::vector<uint8_t> skeys = shamir_harness_keys(h, cfg->seed);
         h->mul_keys.assign((size_t)n, std::vector<uint8_t>((size_t)t * COZK_PRF_KEY_BYTES));
-        for (int p = 0; p < n; p++) {
-            for (int j = 0; j <= 3 * t; j++)
-                harness_prf_key(cfg->seed ^ 0x52414E44ull, (uint64_t)(64 * p + j), h->rand_keys[(size_t)p].data() + (size_t)j * COZK_PRF_KEY_BYTES);
+        for (int p = 0; p < n; p++)
             for (int c = 0; c < t; c++)
                 harness_prf_key(cfg->seed ^ 0x4D554C54ull, (uint64_t)(64 * p + c), h->mul_keys[(size_t)p].data() + (size_t)c * COZK_PRF_KEY_BYTES);
-        }
         // the public flags, on every sender's context
         h->flags.resize((size_t)senders);
         h->E.resize((size_t)senders);
@@ -378,22 +350,11 @@ int cozk_shamir_primary_create(const cozk_shamir_primary_config* cfg, cozk_shami
             HIP_TRY(hipSetDevice(pcs[0]->device));
             VecH cv = v < cfg->n_mem ? make_vec_random(pcs[0], N, COZK_SCALAR_FR, cfg->seed + 9000ull * (uint64_t)(v + 1), 0)
                                      : upload_vec(pcs[0], in.outputs_plain.data(), N, COZK_SCALAR_FR, "vec_upload(outputs)");
-            std::vector<cozk_vec*> sh((size_t)n, nullptr);
-            rc_check(cozk_shamir_scatter(pcs[0], cv.h, skeys.data(), t, n, cfg->share_counter + (uint64_t)v * (uint64_t)N, pcs.data(), sh.data()), pcs[0],
-                     "shamir_scatter");
-            std::vector<VecH> own;
-            for (int p = 0; p < n; p++) own.emplace_back(sh[(size_t)p]);
-            for (int p = 0; p < n; p++) {
-                HIP_TRY(hipSetDevice(pcs[(size_t)p]->device));
-                if (p < senders) {
-                    PolyH poly = plain_poly(pcs[(size_t)p], own[(size_t)p]);
-                    if (v < cfg->n_mem) h->E[(size_t)p].push_back(std::move(poly));
-                    else h->outputs[(size_t)p] = std::move(poly);
-                }
-                HIP_TRY(hipStreamSynchronize(pcs[(size_t)p]->stream));
-                own[(size_t)p] = VecH();
+            std::vector<PolyH> dealt = shamir_deal_column(h, cv, skeys, cfg->share_counter + (uint64_t)v * (uint64_t)N, senders);
+            for (int p = 0; p < senders; p++) {
+                if (v < cfg->n_mem) h->E[(size_t)p].push_back(std::move(dealt[(size_t)p]));
+                else h->outputs[(size_t)p] = std::move(dealt[(size_t)p]);
             }
-            HIP_TRY(hipSetDevice(pcs[0]->device));
         }
     });
 }
@@ -408,27 +369,12 @@ int cozk_shamir_primary_destroy(cozk_shamir_primary* h) {
 }
 
 int cozk_shamir_primary_prove(cozk_shamir_primary* h, int verify, cozk_shamir_primary_result* res) {
-    if (!h || !res) return COZK_ERR_INVALID_ARG;
-    memset(res, 0, sizeof *res);
-    res->verified = -1;
-    const size_t senders = (size_t)(2 * h->t + 1);
-    if ((int)h->parties.size() != h->n || h->n == 0 || h->E.size() != senders || h->E.back().size() != (size_t)h->cfg.n_mem || !h->outputs.back().h) {
-        h->error = "shamir_primary_prove: the harness was not built";
-        return COZK_ERR_INVALID_ARG;
-    }
-    h->error.clear();
-    try {
-        shamir_primary_prove(h, verify != 0, res);
-    } catch (const CozkError& e) {
-        h->error = e.what();
-        for (auto& ps : h->parties)
-            if (ps.ctx) (void)hipStreamSynchronize(ps.ctx->stream);
-        return e.code;
-    } catch (const std::exception& e) {
-        h->error = e.what();
-        return COZK_ERR_INTERNAL;
-    }
-    return COZK_OK;
+    return shamir_harness_prove(
+        h, res, "shamir_primary",
+        [](const cozk_shamir_primary* x) {
+            return x->E.size() == (size_t)(2 * x->t + 1) && x->E.back().size() == (size_t)x->cfg.n_mem && x->outputs.back().h != nullptr;
+        },
+        [&](cozk_shamir_primary* x, cozk_shamir_primary_result* r) { shamir_primary_prove(x, verify != 0, r); });
 }
 
 int cozk_shamir_primary_proof_bytes(const cozk_shamir_primary* h, uint8_t* out, size_t cap) { return harness_proof_bytes(h, out, cap); }
@@ -436,22 +382,8 @@ int cozk_shamir_primary_proof_bytes(const cozk_shamir_primary* h, uint8_t* out, 
 size_t cozk_shamir_primary_msgs_len(const cozk_shamir_primary* h) { return h ? h->msgs.size() : 0; }
 size_t cozk_shamir_primary_finals_len(const cozk_shamir_primary* h) { return h ? h->finals.size() : 0; }
 
-int cozk_shamir_primary_msgs(const cozk_shamir_primary* h, uint64_t* out, size_t cap) {
-    if (!h || !out || cap < h->msgs.size()) return COZK_ERR_INVALID_ARG;
-    for (size_t k = 0; k < h->msgs.size(); k++) fe_to_u64x4(h->msgs[k], out + 4 * k);
-    return COZK_OK;
-}
-
-int cozk_shamir_primary_finals(const cozk_shamir_primary* h, uint64_t* out, size_t cap) {
-    if (!h || !out || cap < h->finals.size()) return COZK_ERR_INVALID_ARG;
-    for (size_t k = 0; k < h->finals.size(); k++) fe_to_u64x4(h->finals[k], out + 4 * k);
-    return COZK_OK;
-}
-
-int cozk_shamir_primary_get_stats(const cozk_shamir_primary* h, cozk_shamir_gp_stats* stats) {
-    if (!h || !stats) return COZK_ERR_INVALID_ARG;
-    *stats = h->stats;
-    return COZK_OK;
-}
+int cozk_shamir_primary_msgs(const cozk_shamir_primary* h, uint64_t* out, size_t cap) { return fe_copy_out(h ? &h->msgs : nullptr, out, cap); }
+int cozk_shamir_primary_finals(const cozk_shamir_primary* h, uint64_t* out, size_t cap) { return fe_copy_out(h ? &h->finals : nullptr, out, cap); }
+int cozk_shamir_primary_get_stats(const cozk_shamir_primary* h, cozk_shamir_gp_stats* stats) { return shamir_harness_stats(h, stats); }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // co-noir-spartan (BASELINE config 4, spartan_harness.hpp) proved by n Shamir parties, all driven from the one thread that owns their
 // contexts and plays the coordinator, as the Shamir grand products are (shamir_gp.hpp).  The reference has no Shamir prover;
-// tests/shamir_spartan_ref.py restates this file in big integers.  Included by harness.hip behind spartan_harness.hpp and shamir_gp.hpp.
+// tests/shamir_spartan_ref.py restates this file in big integers.  Included by harness.hip behind spartan_harness.hpp and
+// shamir_harness.hpp (the handle base, the keys and the dealing, ShamirProve: the openings, the masks).
 //
 // Why the PLAIN kernels serve: every step of the worker is linear in the witness share or multiplies at most two secret factors.
 //   zero_round       public CSR matrices times shared z: degree-t sharings of Az, Bz, Cz (cozk_sparse_matvec3 per sender)
@@ -13,8 +14,8 @@
 //                    sharing, opened from parties 0..t unmasked, as the grand product's final claims are
 // So the proof is the plain prover's, byte for byte (oracle/pyspartan.py, SpartanHarness(mode = plain)), accepted by spartan_verify.
 //
-//   masks     M = 4 log_n openings of degree 2t: ONE dealing of M elements at rand_counter, pair 0 only (shamir_gp_zero_masks), m = 4 round +
-//             evaluation index.  The pair-reuse contract of the grand product applies: (rand keys, rand_counter .. + M) must not be used again.
+//   masks     M = 4 log_n openings of degree 2t (ShamirProve::deal_masks at rand_counter), m = 4 round + evaluation index: (rand keys,
+//             rand_counter .. + M) must not be used again.
 //   grouped   when the senders' contexts are on one device (shamir_gp_grouped; COZK_SHAMIR_GP_GROUP=0 switches it off, read on every call):
 //             the first sumcheck is ONE cozk_spartan_group (FIRST) over the 2t + 1 senders with one eq on sender 0's context, the second
 //             ONE group (SECOND) over copies of the shares of parties 0..t against lin = alpha A + beta B + gamma C formed once; A, B,
@@ -25,15 +26,11 @@
 // several GPUs as groups, a king variant (there is no secret-by-secret multiplication to reshare, so a king has nothing to do).
 #pragma once
 
-struct cozk_shamir_spartan : cozk::HarnessHandle {
+// finals: za, zb, zc(rx); log_n x 3 second-sumcheck evaluations; z's final value; z(ry)
+struct cozk_shamir_spartan : cozk::ShamirHarness {
     cozk_shamir_spartan_config cfg;
     cozk_spartan inst;  // the instance of (seed, log_n) and the verifier's view; inst.parties[p] = party p (CSR, SRS: senders only)
-    int t = 0, n = 0;
     std::vector<cozk::VecH> zvec;  // party p's share vector of z, a vector of its context
-    std::vector<std::vector<uint8_t>> rand_keys;
-    std::vector<fe> msgs;    // [m][p <= 2t], masked
-    std::vector<fe> finals;  // [value][p <= t]: za, zb, zc(rx); log_n x 3 second-sumcheck evaluations; z's final value; z(ry)
-    cozk_shamir_gp_stats stats{};
 };
 
 namespace {
@@ -67,23 +64,15 @@ static fe shamir_spartan_coeff0(cozk_ctx* ctx, const cozk_poly* p) {
 }
 
 static void shamir_spartan_prove(cozk_shamir_spartan* h, bool verify, cozk_shamir_spartan_result* res) {
-    const int t = h->t, n = h->n, nv = h->cfg.log_n, senders = 2 * t + 1, openers = t + 1;
-    std::vector<cozk_ctx*> pcs((size_t)n);
-    for (int p = 0; p < n; p++) pcs[(size_t)p] = h->inst.parties[(size_t)p].ctx;
-    cozk_ctx* const c0 = pcs[0];
-    const ShamirGpArgs a{pcs.data(), nullptr, 0, t, n, nullptr, verify};
-    const bool grouped = shamir_gp_grouped(a);
-    const std::vector<fe> lam2t = shamir_lagrange_first(senders), lamt = shamir_lagrange_first(openers);
-    h->msgs.clear();
-    h->finals.clear();
-    h->stats = cozk_shamir_gp_stats{};
-    auto set_dev = [&](int p) { HIP_TRY(hipSetDevice(pcs[(size_t)p]->device)); };
-    auto open_t = [&](const fe* sh) {  // degree t, unmasked; the openers' shares are part of `finals`
-        for (int p = 0; p < openers; p++) h->finals.push_back(sh[p]);
-        return shamir_open(lamt, sh);
-    };
+    ShamirProve sp(h, verify);
+    const int t = sp.t, nv = h->cfg.log_n, senders = sp.senders, openers = sp.openers;
+    const std::vector<cozk_ctx*>& pcs = sp.pcs;
+    cozk_ctx* const c0 = sp.c0;
+    const bool grouped = sp.grouped;
+    auto set_dev = [&](int p) { sp.set_dev(p); };
+    auto open_t = [&](const fe* sh) { return sp.open_t(sh); };
     SpartanProof pf;
-    shamir_gp_sync_all(a);
+    sp.sync_all();
     const double t0 = now_ms();
     // ---- zero_round, per sender on its share
     std::vector<PolyH> za((size_t)senders), zb((size_t)senders), zc((size_t)senders);
@@ -93,7 +82,7 @@ static void shamir_spartan_prove(cozk_shamir_spartan* h, bool verify, cozk_shami
         rc_check(cozk_sparse_matvec3(pcs[(size_t)p], ps.row_ptr.h, ps.col.h, ps.va.h, ps.vb.h, ps.vc.h, ps.z.h, &za[(size_t)p].h, &zb[(size_t)p].h, &zc[(size_t)p].h),
                  pcs[(size_t)p], "zero_round");
     }
-    shamir_gp_sync_all(a);
+    sp.sync_all();
     const double t1 = now_ms();
     // ---- commit: parties 0..t commit to their share, the points are combined with lagrange(1..t + 1)
     Transcript tr("cozk-spartan");
@@ -110,9 +99,7 @@ static void shamir_spartan_prove(cozk_shamir_spartan* h, bool verify, cozk_shami
     const double t2 = now_ms();
     // ---- masks
     const size_t M = (size_t)4 * (size_t)nv;
-    std::vector<const uint8_t*> rk((size_t)n);
-    for (int p = 0; p < n; p++) rk[(size_t)p] = h->rand_keys[(size_t)p].data();
-    const std::vector<std::vector<fe>> zero = shamir_gp_zero_masks(a, rk.data(), h->cfg.rand_counter, M);
+    sp.deal_masks(h->cfg.rand_counter, M);
     const double t3 = now_ms();
     // ---- first sumcheck
     std::vector<fe> rx, ry;
@@ -148,14 +135,7 @@ static void shamir_spartan_prove(cozk_shamir_spartan* h, bool verify, cozk_shami
                 }
             }
             std::vector<fe> msg(4);
-            for (int e = 0; e < 4; e++) {
-                fe sh[COZK_SHAMIR_MAX_PARTIES];
-                for (int p = 0; p < senders; p++) {
-                    sh[p] = Fr::add(fe_from_u64x4(ev.data() + 16 * p + 4 * e), zero[(size_t)p][(size_t)(4 * j + e)]);
-                    h->msgs.push_back(sh[p]);
-                }
-                msg[(size_t)e] = shamir_open(lam2t, sh);
-            }
+            for (int e = 0; e < 4; e++) msg[(size_t)e] = sp.open_2t(ev.data() + 4 * e, 16, (size_t)(4 * j + e));
             tr.append_scalars(msg);
             const fe r = tr.challenge_scalar();
             rx.push_back(r);
@@ -186,20 +166,12 @@ static void shamir_spartan_prove(cozk_shamir_spartan* h, bool verify, cozk_shami
         for (int i = 0; i < 3; i++) pf.sc1_finals.push_back(open_t(fin[i]));
         pf.sc1_finals.push_back(eq_final);
         g = SpartanGroupH();
-        for (int p = 0; p < senders; p++) {
-            set_dev(p);
-            za[(size_t)p] = PolyH();
-            zb[(size_t)p] = PolyH();
-            zc[(size_t)p] = PolyH();
-        }
-        for (size_t p = 0; p < eqs.size(); p++) {
-            set_dev((int)p);
-            eqs[p] = PolyH();
-        }
+        sp.release(za, zb, zc);
+        sp.release(eqs);
     }
     tr.append_scalars({pf.sc1_finals[0], pf.sc1_finals[1], pf.sc1_finals[2]});
     const std::vector<fe> abc = tr.challenge_vector(3);
-    shamir_gp_sync_all(a);
+    sp.sync_all();
     const double t4 = now_ms();
     // ---- A(rx, .), B(rx, .), C(rx, .): public, the transposed mat-vec with eq(rx, .); grouped: ONCE on sender 0's context
     const int builders = grouped ? 1 : openers;
@@ -291,18 +263,10 @@ static void shamir_spartan_prove(cozk_shamir_spartan* h, bool verify, cozk_shami
         pf.sc2_finals.push_back(open_t(zf));
         for (int i = 0; i < 3; i++) pf.sc2_finals.push_back(mat[i]);
         g = SpartanGroupH();
-        for (int p = 0; p < openers; p++) {
-            set_dev(p);
-            zw[(size_t)p] = PolyH();
-        }
-        for (int p = 0; p < builders; p++) {
-            set_dev(p);
-            arx[(size_t)p] = PolyH();
-            brx[(size_t)p] = PolyH();
-            crx[(size_t)p] = PolyH();
-        }
+        sp.release(zw);
+        sp.release(arx, brx, crx);
     }
-    shamir_gp_sync_all(a);
+    sp.sync_all();
     const double t6 = now_ms();
     // ---- z(ry) and the opening, per opener on its share
     {
@@ -326,7 +290,7 @@ static void shamir_spartan_prove(cozk_shamir_spartan* h, bool verify, cozk_shami
             pf.opening.push_back(shamir_spartan_combine_points(c0, pts, t));
         }
     }
-    shamir_gp_sync_all(a);
+    sp.sync_all();
     const double t7 = now_ms();
     res->verified = -1;
     if (verify) {
@@ -381,33 +345,20 @@ int cozk_shamir_spartan_create(const cozk_shamir_spartan_config* cfg, cozk_shami
         std::vector<fe> z_plain;
         spartan_build_instance(&h->inst, z_plain);
         h->inst.parties.resize((size_t)n);
-        std::vector<cozk_ctx*> pcs((size_t)n);
         for (int p = 0; p < n; p++) {
             SpartanParty& ps = h->inst.parties[(size_t)p];
             ps.party = p;
             ps.open_ctx(cfg->devices[p], "shamir_spartan: cannot create a context (no HIP device?)");
-            pcs[(size_t)p] = ps.ctx;
+            h->pcs.push_back(ps.ctx);
             // the public instance and the SRS: the senders run zero_round, the openers among them commit and open
             if (p < senders) spartan_setup_party(&h->inst, ps, z_plain);
         }
         // the witness: degree-t shares dealt once, party p's as a vector and a PLAIN polynomial of its own context
-        std::vector<uint8_t> skeys((size_t)t * COZK_PRF_KEY_BYTES);
-        for (int c = 0; c < t; c++) harness_prf_key(cfg->seed ^ 0x53484152ull, (uint64_t)c, skeys.data() + (size_t)c * COZK_PRF_KEY_BYTES);
-        h->rand_keys.assign((size_t)n, std::vector<uint8_t>((size_t)(3 * t + 1) * COZK_PRF_KEY_BYTES));
-        for (int p = 0; p < n; p++)
-            for (int j = 0; j <= 3 * t; j++)
-                harness_prf_key(cfg->seed ^ 0x52414E44ull, (uint64_t)(64 * p + j), h->rand_keys[(size_t)p].data() + (size_t)j * COZK_PRF_KEY_BYTES);
-        HIP_TRY(hipSetDevice(pcs[0]->device));
-        VecH zv = upload_fe(pcs[0], z_plain);
-        std::vector<cozk_vec*> sh((size_t)n, nullptr);
-        rc_check(cozk_shamir_scatter(pcs[0], zv.h, skeys.data(), t, n, cfg->share_counter, pcs.data(), sh.data()), pcs[0], "shamir_scatter");
-        h->zvec.resize((size_t)n);
-        for (int p = 0; p < n; p++) h->zvec[(size_t)p] = VecH(sh[(size_t)p]);
-        for (int p = 0; p < n; p++) {
-            HIP_TRY(hipSetDevice(pcs[(size_t)p]->device));
-            h->inst.parties[(size_t)p].z = plain_poly(pcs[(size_t)p], h->zvec[(size_t)p]);
-            HIP_TRY(hipStreamSynchronize(pcs[(size_t)p]->stream));
-        }
+        const std::vector<uint8_t> skeys = shamir_harness_keys(h, cfg->seed);
+        HIP_TRY(hipSetDevice(h->pcs[0]->device));
+        VecH zv = upload_fe(h->pcs[0], z_plain);
+        std::vector<PolyH> z = shamir_deal_column(h, zv, skeys, cfg->share_counter, n, &h->zvec);
+        for (int p = 0; p < n; p++) h->inst.parties[(size_t)p].z = std::move(z[(size_t)p]);
     });
 }
 
@@ -421,26 +372,9 @@ int cozk_shamir_spartan_destroy(cozk_shamir_spartan* h) {
 }
 
 int cozk_shamir_spartan_prove(cozk_shamir_spartan* h, int verify, cozk_shamir_spartan_result* res) {
-    if (!h || !res) return COZK_ERR_INVALID_ARG;
-    memset(res, 0, sizeof *res);
-    res->verified = -1;
-    if ((int)h->inst.parties.size() != h->n || h->zvec.size() != (size_t)h->n) {
-        h->error = "shamir_spartan_prove: the harness was not built";
-        return COZK_ERR_INVALID_ARG;
-    }
-    h->error.clear();
-    try {
-        shamir_spartan_prove(h, verify != 0, res);
-    } catch (const CozkError& e) {
-        h->error = e.what();
-        for (auto& ps : h->inst.parties)
-            if (ps.ctx) (void)hipStreamSynchronize(ps.ctx->stream);
-        return e.code;
-    } catch (const std::exception& e) {
-        h->error = e.what();
-        return COZK_ERR_INTERNAL;
-    }
-    return COZK_OK;
+    return shamir_harness_prove(
+        h, res, "shamir_spartan", [](const cozk_shamir_spartan* x) { return (int)x->inst.parties.size() == x->n && x->zvec.size() == (size_t)x->n; },
+        [&](cozk_shamir_spartan* x, cozk_shamir_spartan_result* r) { shamir_spartan_prove(x, verify != 0, r); });
 }
 
 int cozk_shamir_spartan_proof_bytes(const cozk_shamir_spartan* h, uint8_t* out, size_t cap) { return harness_proof_bytes(h, out, cap); }
@@ -448,22 +382,8 @@ int cozk_shamir_spartan_proof_bytes(const cozk_shamir_spartan* h, uint8_t* out, 
 size_t cozk_shamir_spartan_msgs_len(const cozk_shamir_spartan* h) { return h ? h->msgs.size() : 0; }
 size_t cozk_shamir_spartan_finals_len(const cozk_shamir_spartan* h) { return h ? h->finals.size() : 0; }
 
-int cozk_shamir_spartan_msgs(const cozk_shamir_spartan* h, uint64_t* out, size_t cap) {
-    if (!h || !out || cap < h->msgs.size()) return COZK_ERR_INVALID_ARG;
-    for (size_t k = 0; k < h->msgs.size(); k++) fe_to_u64x4(h->msgs[k], out + 4 * k);
-    return COZK_OK;
-}
-
-int cozk_shamir_spartan_finals(const cozk_shamir_spartan* h, uint64_t* out, size_t cap) {
-    if (!h || !out || cap < h->finals.size()) return COZK_ERR_INVALID_ARG;
-    for (size_t k = 0; k < h->finals.size(); k++) fe_to_u64x4(h->finals[k], out + 4 * k);
-    return COZK_OK;
-}
-
-int cozk_shamir_spartan_get_stats(const cozk_shamir_spartan* h, cozk_shamir_gp_stats* stats) {
-    if (!h || !stats) return COZK_ERR_INVALID_ARG;
-    *stats = h->stats;
-    return COZK_OK;
-}
+int cozk_shamir_spartan_msgs(const cozk_shamir_spartan* h, uint64_t* out, size_t cap) { return fe_copy_out(h ? &h->msgs : nullptr, out, cap); }
+int cozk_shamir_spartan_finals(const cozk_shamir_spartan* h, uint64_t* out, size_t cap) { return fe_copy_out(h ? &h->finals : nullptr, out, cap); }
+int cozk_shamir_spartan_get_stats(const cozk_shamir_spartan* h, cozk_shamir_gp_stats* stats) { return shamir_harness_stats(h, stats); }
 
 }  // extern "C"

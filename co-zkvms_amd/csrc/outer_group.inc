@@ -100,11 +100,8 @@ struct cozk_outer_group {
 static void outer_group_check(cozk_ctx* driver, cozk_outer* const* members, int k, const std::string& what) {
     const cozk_outer* m0 = members[0];
     for (int i = 0; i < k; i++) {
+        group_member_check<true>(what, MEMBER, driver, members, i);
         const cozk_outer* m = members[i];
-        COZK_REQUIRE(m && m->ctx, what + ": null member");
-        COZK_REQUIRE(m->mode == COZK_MODE_PLAIN, what + ": every member must be PLAIN");
-        COZK_REQUIRE(m->ctx->device == driver->device, what + ": every member must live on the driver's device");
-        for (int j = 0; j < i; j++) COZK_REQUIRE(members[j] != m, what + ": duplicate member");
         if (i == 0) m0 = m;
         COZK_REQUIRE(m->L == m0->L && m->per_step == m0->per_step && m->act_rows == m0->act_rows && m->round == m0->round &&
                          m->current_index == m0->current_index && m->n_in == m0->n_in && m->n_out == m0->n_out,
@@ -161,14 +158,9 @@ int cozk_outer_group_create(cozk_ctx* driver, cozk_outer* const* members, int k,
         COZK_REQUIRE(driver && members && out, "outer_group_create: null argument");
         COZK_REQUIRE(k >= 1 && k <= COZK_LAYER_GROUP_MAX, "outer_group_create: 1 <= k <= COZK_LAYER_GROUP_MAX");
         outer_group_check(driver, members, k, "outer_group_create");
-        // whatever the members' own streams still do to them precedes the driver's launches
-        std::vector<cozk_ctx*> seen;
-        for (int i = 0; i < k; i++) {
-            cozk_ctx* c = members[i]->ctx;
-            if (std::find(seen.begin(), seen.end(), c) != seen.end()) continue;
-            seen.push_back(c);
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        }
+        std::vector<cozk_ctx*> owners;
+        for (int i = 0; i < k; i++) owners.push_back(members[i]->ctx);
+        drain_streams(owners);
         cozk_outer_group* g = new cozk_outer_group();
         g->driver = driver;
         g->k = k;
@@ -194,29 +186,21 @@ int cozk_outer_group_round(cozk_outer_group* g, const uint64_t* r, const uint64_
         const OuterGroupArgs a = outer_group_args(g, g->k);
         const size_t total = (size_t)shape.units * shape.pairs_unit;
         const unsigned k = (unsigned)g->k, rows = 2 * k;
-        // members of <= ROUND_SMALL_MAX (dense-equivalent) rows: ONE launch of k workgroups that write their sums straight to the pinned slot
-        const bool small = m0->L <= ROUND_SMALL_MAX;
-        const unsigned gx = small ? 1u : sum_grid(grid_capped(total, std::max(64u, 2048u / k)));
-        SumLaunch sl{};
-        fe* partial;
-        if (small) partial = result_slot(ctx, rows);
-        else {
-            sl = sum_launch(ctx, rows, gx, rows);
-            partial = sl.partial;
-        }
+        // small: members of <= ROUND_SMALL_MAX (dense-equivalent) rows
+        const GroupSums gs = group_sums(ctx, rows, total, m0->L <= ROUND_SMALL_MAX, std::max(64u, GROUP_GRID_MAX / k));
+        fe* const partial = gs.partial;
         // the members move on to the state of this round: the tables and the linear factor below are those AFTER the bind
         if (r)
             for (cozk_outer* st : g->members) outer_bind_state(st, rr);
         COZK_REQUIRE(m0->L / 2 == ((size_t)1 << (m0->n_in + m0->n_out)), "outer_group_round: split-eq tables out of step with the members");
         const fe* E_in = m0->E_in + (((size_t)1 << m0->n_in) - 1);
         const fe* E_out = m0->E_out + (((size_t)1 << m0->n_out) - 1);
-        const dim3 grid(gx, k);
+        const dim3 grid(gs.gx, k);
         if (r) k_outer_group_round<1><<<grid, PT, 0, ctx->stream>>>(a, shape, E_in, (int)m0->n_in, E_out, rr, partial);
         else k_outer_group_round<0><<<grid, PT, 0, ctx->stream>>>(a, shape, E_in, (int)m0->n_in, E_out, rr, partial);
         HIP_TRY(hipGetLastError());
         fe s[2 * COZK_LAYER_GROUP_MAX];
-        if (small) fetch_fe(ctx, partial, rows, s);
-        else finish_sums(ctx, sl, rows, gx, Fr::one(), 0, s);
+        gs.fetch(s);
         // UniPoly::from_linear_times_quadratic_with_hint([scalar - scalar w, 2 scalar w - scalar], t0, tinf, claim_m), as cozk_outer_round
         const fe sw = Fr::mul(m0->current_scalar, m0->w[m0->current_index - 1]);
         const fe l0 = Fr::sub(m0->current_scalar, sw), l1 = Fr::sub(Fr::dbl(sw), m0->current_scalar);
@@ -251,9 +235,7 @@ int cozk_outer_group_final(cozk_outer_group* g, const uint64_t r[4], int k_final
         fe* res = result_slot(ctx, n_res);
         k_outer_group_final<<<(unsigned)k_final, GFT, 0, ctx->stream>>>(a, stored, rr, res);
         HIP_TRY(hipGetLastError());
-        fe h[3 * COZK_LAYER_GROUP_MAX];
-        fetch_fe(ctx, res, n_res, h);
-        for (size_t i = 0; i < n_res; i++) fe_to_u64x4(h[i], out + 4 * i);
+        fetch_u64x4(ctx, res, n_res, out);
     });
 }
 
@@ -325,13 +307,11 @@ struct cozk_shift_group {
     cozk_ctx* driver;
     int k;
     std::vector<cozk_poly*> members;  // referred to
-    fe* pub[2];                       // the group's own copy of the public polynomial, ping-pong, from the driver's pool
-    int pub_cur;
-    size_t len;
+    GroupPub pub;                     // pub.len = the current length of every member
 };
 
 static void shift_group_check_len(const cozk_shift_group* g, int k, const char* what) {
-    for (int i = 0; i < k; i++) COZK_REQUIRE(g->members[(size_t)i]->len == g->len, std::string(what) + ": every member must have the group's current length");
+    for (int i = 0; i < k; i++) COZK_REQUIRE(g->members[(size_t)i]->len == g->pub.len, std::string(what) + ": every member must have the group's current length");
 }
 
 // the pointer tables of one launch over members 0 .. k - 1; bind: every member moves on as cozk_poly_bind(HIGH_TO_LOW) moves it -- to
@@ -357,7 +337,7 @@ extern "C" {
 
 int cozk_shift_group_free(cozk_shift_group* g) {
     if (!g) return COZK_OK;
-    for (int i = 0; i < 2; i++) ctx_dev_free(g->driver, g->pub[i]);
+    g->pub.free(g->driver);
     delete g;
     return COZK_OK;
 }
@@ -371,23 +351,15 @@ int cozk_shift_group_create(cozk_ctx* driver, cozk_poly* const* members, int k, 
         COZK_REQUIRE(pub->ctx->device == driver->device, "shift_group_create: the public polynomial must live on the driver's device");
         const size_t len = pub->len;
         COZK_REQUIRE(len >= 2 && (len & (len - 1)) == 0, "shift_group_create: the length must be a power of two >= 2");
+        std::vector<cozk_ctx*> owners{pub->ctx};
         for (int i = 0; i < k; i++) {
             const cozk_poly* p = members[i];
-            COZK_REQUIRE(p && p->ctx, "shift_group_create: null member");
-            COZK_REQUIRE(p->mode == COZK_MODE_PLAIN, "shift_group_create: every member must be PLAIN");
+            group_member_check<true>("shift_group_create", MEMBER, driver, members, i);
             COZK_REQUIRE(p->len == len, "shift_group_create: the members and the public polynomial must have one length");
-            COZK_REQUIRE(p->ctx->device == driver->device, "shift_group_create: every member must live on the driver's device");
             COZK_REQUIRE(p != pub, "shift_group_create: a member is the public polynomial");
-            for (int j = 0; j < i; j++) COZK_REQUIRE(members[j] != p, "shift_group_create: duplicate member");
+            owners.push_back(p->ctx);
         }
-        std::vector<cozk_ctx*> seen;
-        auto drain = [&](cozk_ctx* c) {
-            if (std::find(seen.begin(), seen.end(), c) != seen.end()) return;
-            seen.push_back(c);
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        };
-        drain(pub->ctx);
-        for (int i = 0; i < k; i++) drain(members[i]->ctx);
+        drain_streams(owners);
         // an unbound member is bound into side 0, a bound one in place: nothing else is ever written
         for (int i = 0; i < k; i++)
             if (members[i]->cur < 0) pingpong_ensure(members[i], 0, len / 2);
@@ -395,14 +367,8 @@ int cozk_shift_group_create(cozk_ctx* driver, cozk_poly* const* members, int k, 
         g->driver = driver;
         g->k = k;
         g->members.assign(members, members + k);
-        g->pub[0] = g->pub[1] = nullptr;
-        g->pub_cur = 0;
-        g->len = len;
         try {
-            g->pub[0] = (fe*)ctx_dev_alloc(driver, len * sizeof(fe));
-            g->pub[1] = (fe*)ctx_dev_alloc(driver, (len / 2) * sizeof(fe));
-            HIP_TRY(hipMemcpyAsync(g->pub[0], poly_a(pub), len * sizeof(fe), hipMemcpyDeviceToDevice, driver->stream));
-            HIP_TRY(hipStreamSynchronize(driver->stream));
+            g->pub.create(driver, pub);
         } catch (...) {
             cozk_shift_group_free(g);
             throw;
@@ -417,34 +383,23 @@ int cozk_shift_group_round(cozk_shift_group* g, const uint64_t* r, uint64_t* out
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(out_evals, "shift_group_round: null argument");
         shift_group_check_len(g, g->k, "shift_group_round");
-        COZK_REQUIRE(g->len >= 2, "shift_group_round: the members are fully bound");
-        if (r) COZK_REQUIRE(g->len >= 4, "shift_group_round: a binding round on members that the bind leaves fully bound");
-        const size_t len_in = g->len, half = r ? len_in / 4 : len_in / 2;
+        COZK_REQUIRE(g->pub.len >= 2, "shift_group_round: the members are fully bound");
+        if (r) COZK_REQUIRE(g->pub.len >= 4, "shift_group_round: a binding round on members that the bind leaves fully bound");
+        const size_t len_in = g->pub.len, half = r ? len_in / 4 : len_in / 2;
         const unsigned k = (unsigned)g->k, rows = 2 * k;
         const fe rr = r ? fe_from_u64x4(r) : Fr::zero();
-        const fe* pin = g->pub[g->pub_cur];
-        fe* pout = g->pub[1 - g->pub_cur];
-        const bool small = len_in <= ROUND_SMALL_MAX;
-        const unsigned gx = small ? 1u : sum_grid(grid_capped(half, std::max(64u, 2048u / k)));
-        SumLaunch sl{};
-        fe* partial;
-        if (small) partial = result_slot(ctx, rows);
-        else {
-            sl = sum_launch(ctx, rows, gx, rows);
-            partial = sl.partial;
-        }
+        const fe* pin = g->pub.in();
+        fe* pout = g->pub.out();
+        const GroupSums gs = group_sums(ctx, rows, half, len_in <= ROUND_SMALL_MAX, std::max(64u, GROUP_GRID_MAX / k));
+        fe* const partial = gs.partial;
         const ShiftGroupArgs a = shift_group_args(g, g->k, r != nullptr);
-        if (r) {
-            g->pub_cur = 1 - g->pub_cur;
-            g->len = len_in / 2;
-        }
-        const dim3 grid(gx, k);
+        if (r) g->pub.advance(len_in / 2);
+        const dim3 grid(gs.gx, k);
         if (r) k_shift_group_round<1><<<grid, PT, 0, ctx->stream>>>(a, pin, pout, half, rr, partial);
         else k_shift_group_round<0><<<grid, PT, 0, ctx->stream>>>(a, pin, pout, half, rr, partial);
         HIP_TRY(hipGetLastError());
         fe s[2 * COZK_LAYER_GROUP_MAX];
-        if (small) fetch_fe(ctx, partial, rows, s);
-        else finish_sums(ctx, sl, rows, gx, Fr::one(), 0, s);
+        gs.fetch(s);
         for (unsigned i = 0; i < rows; i++) fe_to_u64x4(s[i], out_evals + 4 * i);
     });
 }
@@ -456,36 +411,28 @@ int cozk_shift_group_final(cozk_shift_group* g, const uint64_t* r, int k_final, 
         COZK_REQUIRE(out, "shift_group_final: null argument");
         COZK_REQUIRE(k_final >= 0 && k_final <= g->k, "shift_group_final: 0 <= k_final <= k");
         shift_group_check_len(g, k_final, "shift_group_final");
-        COZK_REQUIRE(r ? g->len == 2 : g->len == 1, "shift_group_final: the bind must leave one element (len == 2 with r, len == 1 without)");
+        COZK_REQUIRE(r ? g->pub.len == 2 : g->pub.len == 1, "shift_group_final: the bind must leave one element (len == 2 with r, len == 1 without)");
         const fe rr = r ? fe_from_u64x4(r) : Fr::zero();
-        const fe* pin = g->pub[g->pub_cur];
-        fe* pout = g->pub[1 - g->pub_cur];
+        const fe* pin = g->pub.in();
+        fe* pout = g->pub.out();
         const size_t n_res = (size_t)k_final + 1;
         fe* res = result_slot(ctx, n_res);
         const ShiftGroupArgs a = shift_group_args(g, k_final, r != nullptr);
-        if (r) {
-            g->pub_cur = 1 - g->pub_cur;
-            g->len = 1;
-        }
+        if (r) g->pub.advance(1);
         k_shift_group_final<<<1, GFT, 0, ctx->stream>>>(a, pin, pout, k_final, r != nullptr, rr, res);
         HIP_TRY(hipGetLastError());
-        fe h[COZK_LAYER_GROUP_MAX + 1];
-        fetch_fe(ctx, res, n_res, h);
-        for (size_t i = 0; i < n_res; i++) fe_to_u64x4(h[i], out + 4 * i);
+        fetch_u64x4(ctx, res, n_res, out);
     });
 }
 
-size_t cozk_shift_group_len(const cozk_shift_group* g) { return g ? g->len : 0; }
+size_t cozk_shift_group_len(const cozk_shift_group* g) { return g ? g->pub.len : 0; }
 
 int cozk_shift_group_pub_download(cozk_shift_group* g, uint64_t* out) {
     if (!g) return COZK_ERR_INVALID_ARG;
     cozk_ctx* const ctx = g->driver;
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(out, "shift_group_pub_download: null argument");
-        std::vector<fe> h(g->len);
-        HIP_TRY(hipMemcpyAsync(h.data(), g->pub[g->pub_cur], g->len * sizeof(fe), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        for (size_t i = 0; i < g->len; i++) fe_to_u64x4(h[i], out + 4 * i);
+        g->pub.download(ctx, out);
     });
 }
 

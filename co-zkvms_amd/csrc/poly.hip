@@ -1592,6 +1592,102 @@ static void finish_sums(cozk_ctx* ctx, const SumLaunch& sl, unsigned rows, unsig
     fetch_fe(ctx, sl.res, sl.n_res, out);
 }
 
+// ------------------------------------------------------------------ what the group families share (host only)
+// A group (layer, toggle, spartan, outer, shift, primary) drives k members, each its owner's, with launches on the DRIVER's stream.
+
+// The stream-ordering rule of every group: what a member's own stream still does to it precedes the driver's launches (the rule of
+// cozk_shamir_scatter: the producer's stream is drained before another stream reads what it wrote).  Each distinct context of `owners`
+// is drained once, in the order given; `skip`: a context that is not waited for.
+static void drain_streams(const std::vector<cozk_ctx*>& owners, const cozk_ctx* skip = nullptr) {
+    for (size_t i = 0; i < owners.size(); i++) {
+        cozk_ctx* c = owners[i];
+        if (c == skip || std::find(owners.begin(), owners.end(), c) != owners.begin() + (long)i) continue;  // not its first mention
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+}
+
+// The checks on member i that the families share: there with a context, PLAIN (where the family asks for it), on the driver's device,
+// not given twice.  The refusal texts name the member with the family's nouns.
+struct MemberNouns {
+    const char *one, *on_device, *dup;  // "null <one>", "every <one> must be PLAIN", "every <on_device> must live ..", "duplicate <dup>"
+};
+static constexpr MemberNouns MEMBER{"member", "member", "member"};
+template <bool PLAIN, class T>
+static void group_member_check(const std::string& what, const MemberNouns& w, const cozk_ctx* driver, T* const* members, int i) {
+    const T* m = members[i];
+    COZK_REQUIRE(m && m->ctx, what + ": null " + w.one);
+    if constexpr (PLAIN) COZK_REQUIRE(m->mode == COZK_MODE_PLAIN, what + ": every " + w.one + " must be PLAIN");
+    COZK_REQUIRE(m->ctx->device == driver->device, what + ": every " + w.on_device + " must live on the driver's device");
+    for (int j = 0; j < i; j++) COZK_REQUIRE(members[j] != m, what + ": duplicate " + w.dup);
+}
+
+// A group's own copy of the public polynomial that its members are summed against, ping-pong, from the driver's pool: a binding round
+// reads in(), writes out() (half as long) and advances.
+struct GroupPub {
+    fe* buf[2] = {nullptr, nullptr};
+    int cur = 0;
+    size_t len = 0;  // current length = that of every member
+    // on a failure the caller frees what was allocated (free)
+    void create(cozk_ctx* driver, const cozk_poly* pub) {
+        len = pub->len;
+        buf[0] = (fe*)ctx_dev_alloc(driver, len * sizeof(fe));
+        buf[1] = (fe*)ctx_dev_alloc(driver, (len / 2) * sizeof(fe));
+        HIP_TRY(hipMemcpyAsync(buf[0], poly_a(pub), len * sizeof(fe), hipMemcpyDeviceToDevice, driver->stream));
+        HIP_TRY(hipStreamSynchronize(driver->stream));
+    }
+    void free(cozk_ctx* driver) {
+        for (int i = 0; i < 2; i++) ctx_dev_free(driver, buf[i]);
+    }
+    const fe* in() const { return buf[cur]; }
+    fe* out() const { return buf[1 - cur]; }
+    void advance(size_t new_len) {
+        cur = 1 - cur;
+        len = new_len;
+    }
+    void download(cozk_ctx* ctx, uint64_t* out) const {
+        std::vector<fe> h(len);
+        HIP_TRY(hipMemcpyAsync(h.data(), buf[cur], len * sizeof(fe), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (size_t i = 0; i < len; i++) fe_to_u64x4(h[i], out + 4 * i);
+    }
+};
+
+// The sum step of a round group: `rows` sums (a few per member) over `items` work items per member, blockIdx.y the member.  Small
+// members: ONE launch of one workgroup per member that writes its sums straight to the pinned slot.  Otherwise gx <= grid_cap
+// workgroups per member write block partials and k_finish_sums adds the rows up.  The caller launches into `partial` with grid.x = gx,
+// then fetches.
+static constexpr unsigned GROUP_GRID_MAX = 2048;  // workgroups of ONE group round launch over all its members (MAXBLK, shared: a member
+                                                  // gets GROUP_GRID_MAX / k of them, and never fewer than 64)
+struct GroupSums {
+    cozk_ctx* ctx;
+    unsigned rows, gx;
+    bool small;
+    SumLaunch sl;
+    fe* partial;
+    void fetch(fe* out) const {
+        if (small) fetch_fe(ctx, partial, rows, out);
+        else finish_sums(ctx, sl, rows, gx, Fr::one(), 0, out);
+    }
+};
+static GroupSums group_sums(cozk_ctx* ctx, unsigned rows, size_t items, bool small, unsigned grid_cap) {
+    GroupSums s{ctx, rows, 1u, small, SumLaunch{}, nullptr};
+    if (small) s.partial = result_slot(ctx, rows);
+    else {
+        s.gx = sum_grid(grid_capped(items, grid_cap));
+        s.sl = sum_launch(ctx, rows, s.gx, rows);
+        s.partial = s.sl.partial;
+    }
+    return s;
+}
+
+// the tail of a group's final call: n <= 4 COZK_LAYER_GROUP_MAX values from the result slot `res` to the caller, 4 words each
+static void fetch_u64x4(cozk_ctx* ctx, const fe* res, size_t n, uint64_t* out) {
+    fe h[4 * COZK_LAYER_GROUP_MAX];
+    COZK_REQUIRE(n <= sizeof h / sizeof h[0], "fetch_u64x4: more values than a group's final call returns");
+    fetch_fe(ctx, res, n, h);
+    for (size_t i = 0; i < n; i++) fe_to_u64x4(h[i], out + 4 * i);
+}
+
 // make ping-pong side `which` of a polynomial or layer hold n elements (both components of a Rep3 object), from and to the pool of
 // the object's own context, whichever context's call is running
 template <class P>
@@ -2769,20 +2865,15 @@ int cozk_layer_group_create(cozk_ctx* driver, cozk_layer* const* layers, int k, 
     return cozk_guard(driver, [&] {
         COZK_REQUIRE(driver && layers && out, "layer_group_create: null argument");
         COZK_REQUIRE(k >= 1 && k <= COZK_LAYER_GROUP_MAX, "layer_group_create: 1 <= k <= COZK_LAYER_GROUP_MAX");
+        std::vector<cozk_ctx*> owners;
         for (int i = 0; i < k; i++) {
             const cozk_layer* l = layers[i];
-            COZK_REQUIRE(l && l->ctx, "layer_group_create: null member");
+            group_member_check<false>("layer_group_create", MEMBER, driver, layers, i);
             COZK_REQUIRE(l->mode == layers[0]->mode, "layer_group_create: the members must have one mode");
             COZK_REQUIRE(l->len == layers[0]->len && l->len >= 2, "layer_group_create: the members must have one length >= 2");
-            COZK_REQUIRE(l->ctx->device == driver->device, "layer_group_create: every member must live on the driver's device");
-            for (int j = 0; j < i; j++) COZK_REQUIRE(layers[j] != l, "layer_group_create: duplicate member");
+            owners.push_back(l->ctx);
         }
-        // whatever the members' own streams still do to them precedes the driver's launches
-        for (int i = 0; i < k; i++) {
-            bool seen = false;
-            for (int j = 0; j < i; j++) seen = seen || layers[j]->ctx == layers[i]->ctx;
-            if (!seen) HIP_TRY(hipStreamSynchronize(layers[i]->ctx->stream));
-        }
+        drain_streams(owners);
         for (int i = 0; i < k; i++) {  // the other ping-pong side, once: later rounds allocate nothing
             cozk_layer* l = layers[i];
             pingpong_ensure(l, 1 - l->cur, 2 * ((l->len + 3) / 4));

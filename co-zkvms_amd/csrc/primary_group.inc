@@ -150,11 +150,8 @@ struct cozk_primary_group {
 static void primary_group_check(cozk_ctx* driver, cozk_primary* const* members, int k, const std::string& what, bool round) {
     const cozk_primary* m0 = members[0];
     for (int i = 0; i < k; i++) {
+        group_member_check<true>(what, MEMBER, driver, members, i);
         const cozk_primary* m = members[i];
-        COZK_REQUIRE(m && m->ctx, what + ": null member");
-        COZK_REQUIRE(m->mode == COZK_MODE_PLAIN, what + ": every member must be PLAIN");
-        COZK_REQUIRE(m->ctx->device == driver->device, what + ": every member must live on the driver's device");
-        for (int j = 0; j < i; j++) COZK_REQUIRE(members[j] != m, what + ": duplicate member");
         if (i == 0) m0 = m;
         COZK_REQUIRE(m->n_instr == m0->n_instr && m->n_mem == m0->n_mem && m->degree == m0->degree && m->mul == m0->mul && m->lin == m0->lin,
                      what + ": every member must have the same instruction table (n_instr, n_mem, degree)");
@@ -173,15 +170,12 @@ static void primary_group_check(cozk_ctx* driver, cozk_primary* const* members, 
 
 // round_begin and final_evals stay per member and run on the member's OWN stream; round_begin returns with its last launches (the item
 // list, the bases) still enqueued there.  So every group call that launches waits, after its host checks and before its first launch,
-// for every distinct member stream other than the driver's (the rule of cozk_shamir_scatter: the producer's stream is drained before
-// another stream reads what it wrote).  The way back is the calls' own drain of the driver's stream.
+// for every distinct member stream other than the driver's (drain_streams).  The way back is the calls' own drain of the driver's
+// stream.
 static void primary_group_wait_members(const cozk_primary_group* g) {
-    std::vector<cozk_ctx*> seen{g->driver};
-    for (const cozk_primary* p : g->members) {
-        if (std::find(seen.begin(), seen.end(), p->ctx) != seen.end()) continue;
-        seen.push_back(p->ctx);
-        HIP_TRY(hipStreamSynchronize(p->ctx->stream));
-    }
+    std::vector<cozk_ctx*> owners;
+    for (const cozk_primary* p : g->members) owners.push_back(p->ctx);
+    drain_streams(owners, g->driver);
 }
 
 static PrimGroupArgs primary_group_args(const cozk_primary_group* g) {
@@ -217,14 +211,9 @@ int cozk_primary_group_create(cozk_ctx* driver, cozk_primary* const* members, in
         COZK_REQUIRE(driver && members && keys && out, "primary_group_create: null argument");
         COZK_REQUIRE(k >= 3 && k <= PRIM_GROUP_MAX && k % 2 == 1, "primary_group_create: k = 2t + 1 with 1 <= t, k <= COZK_PRIMARY_GROUP_MAX");
         primary_group_check(driver, members, k, "primary_group_create", false);
-        // whatever the members' own streams still do to them precedes the driver's launches
-        std::vector<cozk_ctx*> seen;
-        for (int i = 0; i < k; i++) {
-            cozk_ctx* c = members[i]->ctx;
-            if (std::find(seen.begin(), seen.end(), c) != seen.end()) continue;
-            seen.push_back(c);
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        }
+        std::vector<cozk_ctx*> owners;
+        for (int i = 0; i < k; i++) owners.push_back(members[i]->ctx);
+        drain_streams(owners);
         cozk_primary_group* g = new cozk_primary_group();
         g->driver = driver;
         g->k = k;
@@ -309,13 +298,12 @@ int cozk_primary_group_round_finish(cozk_primary_group* g, uint64_t* out) {
         const unsigned k = (unsigned)g->k, rows = 2u * (unsigned)D * k;
         std::vector<fe> s((size_t)rows, Fr::zero());
         if (m0->n_items) {
-            const unsigned gx = sum_grid(grid_capped(m0->n_items, std::max(64u, ROUND_GRID_MAX / k)));
-            const SumLaunch sl = sum_launch(ctx, rows, gx, rows);
+            const GroupSums gs = group_sums(ctx, rows, m0->n_items, false, std::max(64u, ROUND_GRID_MAX / k));
             primary_group_wait_members(g);
             const PrimGroupArgs a = primary_group_args(g);
-            k_primary_group_final<<<dim3(gx, (unsigned)D, k), PT, 0, ctx->stream>>>(a, m0->cap[m0->cur], m0->n_instr, m0->n_mem, D, m0->n_items, sl.partial);
+            k_primary_group_final<<<dim3(gs.gx, (unsigned)D, k), PT, 0, ctx->stream>>>(a, m0->cap[m0->cur], m0->n_instr, m0->n_mem, D, m0->n_items, gs.partial);
             HIP_TRY(hipGetLastError());
-            finish_sums(ctx, sl, rows, gx, Fr::one(), 0, s.data());
+            gs.fetch(s.data());
         }
         for (unsigned m = 0; m < k; m++) {
             const cozk_primary* p = g->members[m];

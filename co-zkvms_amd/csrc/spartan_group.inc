@@ -90,15 +90,13 @@ struct cozk_spartan_group {
     cozk_ctx* driver;
     int kind, P, E, k;
     std::vector<cozk_poly*> planes;  // k x P, referred to
-    fe* pub[2];                      // the group's own copy of the public polynomial, ping-pong, from the driver's pool
-    int pub_cur;
-    size_t len;                      // current length of the public polynomial = of every member plane
+    GroupPub pub;                    // pub.len = the current length of every member plane
 };
 
 // the one current length of the planes of members 0 .. k - 1, which is the public polynomial's
 static void spartan_group_check_len(const cozk_spartan_group* g, int k, const char* what) {
     for (int i = 0; i < k * g->P; i++)
-        COZK_REQUIRE(g->planes[i]->len == g->len, std::string(what) + ": every member plane must have the group's current length");
+        COZK_REQUIRE(g->planes[i]->len == g->pub.len, std::string(what) + ": every member plane must have the group's current length");
 }
 
 // the pointer tables of one launch over members 0 .. k - 1; bind: every plane moves on to its other ping-pong side, as cozk_poly_bind
@@ -133,25 +131,15 @@ int cozk_spartan_group_create(cozk_ctx* driver, int kind, cozk_poly* const* plan
         COZK_REQUIRE(pub->ctx->device == driver->device, "spartan_group_create: the public polynomial must live on the driver's device");
         const size_t len = pub->len;
         COZK_REQUIRE(len >= 2 && (len & (len - 1)) == 0, "spartan_group_create: the length must be a power of two >= 2");
+        std::vector<cozk_ctx*> owners{pub->ctx};
         for (int i = 0; i < k * P; i++) {
             const cozk_poly* p = planes[i];
-            COZK_REQUIRE(p && p->ctx, "spartan_group_create: null member plane");
-            COZK_REQUIRE(p->mode == COZK_MODE_PLAIN, "spartan_group_create: every member plane must be PLAIN");
+            group_member_check<true>("spartan_group_create", MemberNouns{"member plane", "member", "plane"}, driver, planes, i);
             COZK_REQUIRE(p->len == len, "spartan_group_create: the member planes and the public polynomial must have one length");
-            COZK_REQUIRE(p->ctx->device == driver->device, "spartan_group_create: every member must live on the driver's device");
             COZK_REQUIRE(p != pub, "spartan_group_create: a member plane is the public polynomial");
-            for (int j = 0; j < i; j++) COZK_REQUIRE(planes[j] != p, "spartan_group_create: duplicate plane");
+            owners.push_back(p->ctx);
         }
-        // whatever the members' own streams still do to them precedes the driver's launches
-        std::vector<cozk_ctx*> seen;
-        auto drain = [&](cozk_ctx* c) {
-            for (cozk_ctx* s : seen)
-                if (s == c) return;
-            seen.push_back(c);
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        };
-        drain(pub->ctx);
-        for (int i = 0; i < k * P; i++) drain(planes[i]->ctx);
+        drain_streams(owners);
         // both ping-pong sides of every plane for all rounds to come, once: the first bind writes len / 2, the second len / 4
         for (int i = 0; i < k * P; i++) {
             cozk_poly* p = planes[i];
@@ -166,14 +154,8 @@ int cozk_spartan_group_create(cozk_ctx* driver, int kind, cozk_poly* const* plan
         g->E = P == 3 ? 4 : 3;
         g->k = k;
         g->planes.assign(planes, planes + (size_t)k * P);
-        g->pub[0] = g->pub[1] = nullptr;
-        g->pub_cur = 0;
-        g->len = len;
         try {
-            g->pub[0] = (fe*)ctx_dev_alloc(driver, len * sizeof(fe));
-            g->pub[1] = (fe*)ctx_dev_alloc(driver, (len / 2) * sizeof(fe));
-            HIP_TRY(hipMemcpyAsync(g->pub[0], poly_a(pub), len * sizeof(fe), hipMemcpyDeviceToDevice, driver->stream));
-            HIP_TRY(hipStreamSynchronize(driver->stream));
+            g->pub.create(driver, pub);
         } catch (...) {
             cozk_spartan_group_free(g);
             throw;
@@ -184,7 +166,7 @@ int cozk_spartan_group_create(cozk_ctx* driver, int kind, cozk_poly* const* plan
 
 int cozk_spartan_group_free(cozk_spartan_group* g) {
     if (!g) return COZK_OK;
-    for (int i = 0; i < 2; i++) ctx_dev_free(g->driver, g->pub[i]);
+    g->pub.free(g->driver);
     delete g;
     return COZK_OK;
 }
@@ -195,29 +177,18 @@ int cozk_spartan_group_round(cozk_spartan_group* g, const uint64_t* r, uint64_t*
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(out_evals, "spartan_group_round: null argument");
         spartan_group_check_len(g, g->k, "spartan_group_round");
-        COZK_REQUIRE(g->len >= 2, "spartan_group_round: the members are fully bound");
-        if (r) COZK_REQUIRE(g->len >= 4, "spartan_group_round: a binding round on members that the bind leaves fully bound");
-        const size_t len_in = g->len, pairs = r ? len_in / 4 : len_in / 2;
+        COZK_REQUIRE(g->pub.len >= 2, "spartan_group_round: the members are fully bound");
+        if (r) COZK_REQUIRE(g->pub.len >= 4, "spartan_group_round: a binding round on members that the bind leaves fully bound");
+        const size_t len_in = g->pub.len, pairs = r ? len_in / 4 : len_in / 2;
         const unsigned k = (unsigned)g->k, rows = k * (unsigned)g->E;
         const fe rr = r ? fe_from_u64x4(r) : Fr::zero();
-        const fe* pin = g->pub[g->pub_cur];
-        fe* pout = g->pub[1 - g->pub_cur];
-        // members of <= ROUND_SMALL_MAX elements: ONE launch of k workgroups that write their sums straight to the pinned slot
-        const bool small = len_in <= ROUND_SMALL_MAX;
-        const unsigned gx = small ? 1u : sum_grid(grid_capped(pairs, std::max(64u, 2048u / k)));
-        SumLaunch sl{};
-        fe* partial;
-        if (small) partial = result_slot(ctx, rows);
-        else {
-            sl = sum_launch(ctx, rows, gx, rows);
-            partial = sl.partial;
-        }
+        const fe* pin = g->pub.in();
+        fe* pout = g->pub.out();
+        const GroupSums gs = group_sums(ctx, rows, pairs, len_in <= ROUND_SMALL_MAX, std::max(64u, GROUP_GRID_MAX / k));
+        fe* const partial = gs.partial;
         const SpartanGroupArgs a = spartan_group_args(g, g->k, r != nullptr);
-        if (r) {
-            g->pub_cur = 1 - g->pub_cur;
-            g->len = len_in / 2;
-        }
-        const dim3 grid(gx, k);
+        if (r) g->pub.advance(len_in / 2);
+        const dim3 grid(gs.gx, k);
         if (g->P == 3) {
             if (r) k_spartan_group_round<3, 1><<<grid, PT, 0, ctx->stream>>>(a, pin, pout, pairs, rr, partial);
             else k_spartan_group_round<3, 0><<<grid, PT, 0, ctx->stream>>>(a, pin, pout, pairs, rr, partial);
@@ -227,8 +198,7 @@ int cozk_spartan_group_round(cozk_spartan_group* g, const uint64_t* r, uint64_t*
         }
         HIP_TRY(hipGetLastError());
         fe s[4 * COZK_LAYER_GROUP_MAX];
-        if (small) fetch_fe(ctx, partial, rows, s);
-        else finish_sums(ctx, sl, rows, gx, Fr::one(), 0, s);
+        gs.fetch(s);
         for (unsigned i = 0; i < rows; i++) fe_to_u64x4(s[i], out_evals + 4 * i);
     });
 }
@@ -240,38 +210,30 @@ int cozk_spartan_group_final(cozk_spartan_group* g, const uint64_t* r, int k_fin
         COZK_REQUIRE(out, "spartan_group_final: null argument");
         COZK_REQUIRE(k_final >= 0 && k_final <= g->k, "spartan_group_final: 0 <= k_final <= k");
         spartan_group_check_len(g, k_final, "spartan_group_final");
-        COZK_REQUIRE(r ? g->len == 2 : g->len == 1, "spartan_group_final: the bind must leave one element (len == 2 with r, len == 1 without)");
+        COZK_REQUIRE(r ? g->pub.len == 2 : g->pub.len == 1, "spartan_group_final: the bind must leave one element (len == 2 with r, len == 1 without)");
         const fe rr = r ? fe_from_u64x4(r) : Fr::zero();
-        const fe* pin = g->pub[g->pub_cur];
-        fe* pout = g->pub[1 - g->pub_cur];
+        const fe* pin = g->pub.in();
+        fe* pout = g->pub.out();
         const size_t n_res = (size_t)k_final * g->P + 1;
         fe* res = result_slot(ctx, n_res);
         const SpartanGroupArgs a = spartan_group_args(g, k_final, r != nullptr);
-        if (r) {
-            g->pub_cur = 1 - g->pub_cur;
-            g->len = 1;
-        }
+        if (r) g->pub.advance(1);
         const unsigned gx = (unsigned)(k_final ? k_final : 1);
         if (g->P == 3) k_spartan_group_final<3><<<gx, GFT, 0, ctx->stream>>>(a, pin, pout, k_final, r != nullptr, rr, res);
         else k_spartan_group_final<1><<<gx, GFT, 0, ctx->stream>>>(a, pin, pout, k_final, r != nullptr, rr, res);
         HIP_TRY(hipGetLastError());
-        fe h[3 * COZK_LAYER_GROUP_MAX + 1];
-        fetch_fe(ctx, res, n_res, h);
-        for (size_t i = 0; i < n_res; i++) fe_to_u64x4(h[i], out + 4 * i);
+        fetch_u64x4(ctx, res, n_res, out);
     });
 }
 
-size_t cozk_spartan_group_len(const cozk_spartan_group* g) { return g ? g->len : 0; }
+size_t cozk_spartan_group_len(const cozk_spartan_group* g) { return g ? g->pub.len : 0; }
 
 int cozk_spartan_group_pub_download(cozk_spartan_group* g, uint64_t* out) {
     if (!g) return COZK_ERR_INVALID_ARG;
     cozk_ctx* const ctx = g->driver;
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(out, "spartan_group_pub_download: null argument");
-        std::vector<fe> h(g->len);
-        HIP_TRY(hipMemcpyAsync(h.data(), g->pub[g->pub_cur], g->len * sizeof(fe), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        for (size_t i = 0; i < g->len; i++) fe_to_u64x4(h[i], out + 4 * i);
+        g->pub.download(ctx, out);
     });
 }
 

@@ -865,32 +865,24 @@ int cozk_toggle_group_create(cozk_ctx* driver, const cozk_vec* const* flags, siz
         COZK_REQUIRE(driver && flags && fingerprints && out && n_pairs > 0, "toggle_group_create: null argument");
         COZK_REQUIRE(k >= 1 && k <= COZK_LAYER_GROUP_MAX, "toggle_group_create: 1 <= k <= COZK_LAYER_GROUP_MAX");
         const size_t batch = 2 * n_pairs;
+        std::vector<cozk_ctx*> owners;
         for (int m = 0; m < k; m++) {
             const cozk_vec* v = fingerprints[m];
-            COZK_REQUIRE(v && v->ctx, "toggle_group_create: null fingerprint vector");
+            group_member_check<false>("toggle_group_create", MemberNouns{"fingerprint vector", "fingerprint vector", "fingerprint vector"}, driver, fingerprints, m);
             COZK_REQUIRE(v->kind == COZK_SCALAR_FR, "toggle_group_create: the fingerprints must be FR vectors");
             COZK_REQUIRE(v->n == fingerprints[0]->n, "toggle_group_create: the fingerprint vectors must have one length");
-            COZK_REQUIRE(v->ctx->device == driver->device, "toggle_group_create: every fingerprint vector must live on the driver's device");
-            for (int j = 0; j < m; j++) COZK_REQUIRE(fingerprints[j] != v, "toggle_group_create: duplicate fingerprint vector");
+            owners.push_back(v->ctx);
         }
         const size_t total = fingerprints[0]->n;
         COZK_REQUIRE(total % batch == 0, "toggle_group_create: fingerprints.len() must be 2 * n_pairs * N");
         const size_t n0 = total / batch;
         COZK_REQUIRE(n0 >= 2 && (n0 & (n0 - 1)) == 0, "toggle_group_create: fingerprints per circuit must be a power of two >= 2");
-        // whatever the inputs' own streams still do to them precedes the driver's launches
-        std::vector<cozk_ctx*> drained{driver};
-        auto drain = [&](cozk_ctx* c) {
-            for (cozk_ctx* d : drained)
-                if (d == c) return;
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            drained.push_back(c);
-        };
-        for (int m = 0; m < k; m++) drain(fingerprints[m]->ctx);
         for (size_t q = 0; q < n_pairs; q++) {  // a column that is missing or of another shape is toggle_pack_flags' to refuse
             if (!flags[q] || !flags[q]->ctx) continue;
             COZK_REQUIRE(flags[q]->ctx->device == driver->device, "toggle_group_create: every flag column must live on the driver's device");
-            drain(flags[q]->ctx);
+            owners.push_back(flags[q]->ctx);
         }
+        drain_streams(owners, driver);  // the inputs' own streams; the driver's own work is in order with its launches
         g = new cozk_toggle_group();  // value-initialised: k = 0, no buffers yet
         g->driver = driver;
         g->s.init(batch, n0);

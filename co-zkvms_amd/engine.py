@@ -478,6 +478,53 @@ class ShamirGpToggleStats(ctypes.Structure):
     _fields_ = [("toggle_group_rounds", ctypes.c_uint64), ("toggle_single_rounds", ctypes.c_uint64)]
 
 
+SHAMIR_MAX_PARTIES = 32  # COZK_SHAMIR_MAX_PARTIES
+
+
+class ShamirHarnessHandle(L.HarnessHandle):
+    """What the in-process Shamir prover harnesses share (csrc/host/shamir_harness.hpp): the read-back of what went over the star --
+    `PREFIX_msgs`, `_finals`, their `_len`, `_get_stats` -- and the device list of a config.  A subclass sets PREFIX, CONFIG, RESULT."""
+
+    def __init_subclass__(cls, **kw):
+        super().__init_subclass__(**kw)
+        vp, sz, i = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+        cls.EXTRA = {cls.PREFIX + "_msgs_len": (sz, [vp]), cls.PREFIX + "_msgs": (i, [vp, vp, sz]), cls.PREFIX + "_finals_len": (sz, [vp]),
+                     cls.PREFIX + "_finals": (i, [vp, vp, sz]), cls.PREFIX + "_get_stats": (i, [vp, ctypes.POINTER(ShamirGpStats)])}
+
+    @staticmethod
+    def _devices(devices):
+        """one device per party (an int: all on it), padded with device 0 to the config's array"""
+        devs = [devices] * SHAMIR_MAX_PARTIES if isinstance(devices, int) else list(devices) + [0] * (SHAMIR_MAX_PARTIES - len(devices))
+        return (ctypes.c_int * SHAMIR_MAX_PARTIES)(*devs[:SHAMIR_MAX_PARTIES])
+
+    def _fe_list(self, what):
+        n = self._f("_" + what + "_len")(self.h)
+        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        rc = self._f("_" + what)(self.h, out.ctypes.data, n)
+        if rc != L.OK:
+            raise L.CozkError(rc, what)
+        return mont_limbs_to_int(out[:n])
+
+    def _rows(self, what, k):
+        v = self._fe_list(what)
+        return [v[i:i + k] for i in range(0, len(v), k)]
+
+    def msgs(self):
+        """the masked messages of the degree-2t openings, [m][p <= 2t]"""
+        return self._rows("msgs", 2 * self.cfg.degree + 1)
+
+    def finals(self):
+        """the shares of the degree-t openings, [value][p <= t], in the order opened"""
+        return self._rows("finals", self.cfg.degree + 1)
+
+    def stats(self):
+        st = ShamirGpStats()
+        rc = self._f("_get_stats")(self.h, ctypes.byref(st))
+        if rc != L.OK:
+            raise L.CozkError(rc, "get_stats")
+        return st
+
+
 class ShamirGpProof:
     """what shamir_gp_prove returns: .proof_bytes, the final .claim and point .r (canonical ints), .result (ShamirGpResult), and
     what went over the star -- .msgs[m][p], sender p's masked message of opening m, and .finals[layer, top first][p] = (L, R),

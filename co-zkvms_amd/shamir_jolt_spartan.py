@@ -5,10 +5,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib as L
-from .engine import ShamirGpStats, fr_to_mont_limbs, mont_limbs_to_int
-
-MAX_PARTIES = 32
+from .engine import SHAMIR_MAX_PARTIES as MAX_PARTIES, ShamirHarnessHandle, fr_to_mont_limbs, mont_limbs_to_int
 
 
 class OuterGroup:
@@ -127,7 +124,6 @@ class ShamirJoltSpartanResult(ctypes.Structure):
                 ("t_openings_ms", ctypes.c_double)]
 
 
-_vp, _sz, _i = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
 OUTER_GROUP_SYMBOLS = ["cozk_outer_group_create", "cozk_outer_group_round", "cozk_outer_group_final", "cozk_outer_group_len",
                        "cozk_outer_group_free"]
 SHIFT_GROUP_SYMBOLS = ["cozk_shift_group_create", "cozk_shift_group_round", "cozk_shift_group_final", "cozk_shift_group_len",
@@ -138,13 +134,12 @@ SHAMIR_JOLT_SPARTAN_SYMBOLS = ["cozk_shamir_jolt_spartan_create", "cozk_shamir_j
                                "cozk_shamir_jolt_spartan_get_stats"]
 
 
-class ShamirJoltSpartanHarness(L.HarnessHandle):
+class ShamirJoltSpartanHarness(ShamirHarnessHandle):
     """n Shamir parties of degree t prove the whole Spartan worker on the outer harness's instance of (seed, log_steps, system); one
-    device per party (an int: all on it)"""
+    device per party (an int: all on it).  msgs(): the masked outer messages [m][p <= 2t], m = 4 round + coefficient.  finals():
+    [value][p <= t] in proof order: Az, Bz, Cz(r); the inner rounds' coefficients; shift_claim; the shift rounds' coefficients; the
+    witness evaluations; the shift-witness evaluations"""
     PREFIX, CONFIG, RESULT = "cozk_shamir_jolt_spartan", ShamirJoltSpartanConfig, ShamirJoltSpartanResult
-    EXTRA = {"cozk_shamir_jolt_spartan_msgs_len": (_sz, [_vp]), "cozk_shamir_jolt_spartan_msgs": (_i, [_vp, _vp, _sz]),
-             "cozk_shamir_jolt_spartan_finals_len": (_sz, [_vp]), "cozk_shamir_jolt_spartan_finals": (_i, [_vp, _vp, _sz]),
-             "cozk_shamir_jolt_spartan_get_stats": (_i, [_vp, ctypes.POINTER(ShamirGpStats)])}
 
     def __init__(self, log_steps=4, system="jolt", parties=3, degree=1, devices=0, seed=1, share_counter=0, rand_counter=0):
         cfg = ShamirJoltSpartanConfig()
@@ -152,37 +147,8 @@ class ShamirJoltSpartanHarness(L.HarnessHandle):
         cfg.system = system if isinstance(system, int) else (1 if system == "jolt" else 0)
         cfg.degree = degree
         cfg.num_parties = parties
-        devs = [devices] * MAX_PARTIES if isinstance(devices, int) else list(devices) + [0] * (MAX_PARTIES - len(devices))
-        cfg.devices = (ctypes.c_int * MAX_PARTIES)(*devs[:MAX_PARTIES])
+        cfg.devices = self._devices(devices)
         cfg.seed = seed
         cfg.share_counter = share_counter
         cfg.rand_counter = rand_counter
         self._open(cfg)
-
-    def _fe_list(self, what):
-        n = self._f("_" + what + "_len")(self.h)
-        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
-        rc = self._f("_" + what)(self.h, out.ctypes.data, n)
-        if rc != L.OK:
-            raise L.CozkError(rc, what)
-        return mont_limbs_to_int(out[:n])
-
-    def msgs(self):
-        """the masked outer messages [m][p <= 2t], m = 4 round + coefficient"""
-        k = 2 * self.cfg.degree + 1
-        v = self._fe_list("msgs")
-        return [v[i:i + k] for i in range(0, len(v), k)]
-
-    def finals(self):
-        """[value][p <= t] in proof order: Az, Bz, Cz(r); the inner rounds' coefficients; shift_claim; the shift rounds' coefficients;
-        the witness evaluations; the shift-witness evaluations"""
-        k = self.cfg.degree + 1
-        v = self._fe_list("finals")
-        return [v[i:i + k] for i in range(0, len(v), k)]
-
-    def stats(self):
-        st = ShamirGpStats()
-        rc = self._f("_get_stats")(self.h, ctypes.byref(st))
-        if rc != L.OK:
-            raise L.CozkError(rc, "get_stats")
-        return st

@@ -4,13 +4,8 @@ of the collation programs the 2t + 1 senders reduce the degree (`cozk_primary_gr
 prover's, byte for byte (LookupsHarness(mode="plain", primary=True) up to proof_len, oracle/pyprimary.py)."""
 import ctypes
 
-import numpy as np
-
-from . import _lib as L
-from .engine import ShamirGpStats, mont_limbs_to_int
+from .engine import SHAMIR_MAX_PARTIES as MAX_PARTIES, ShamirHarnessHandle
 from .lookups import PrimaryGroup, PRIMARY_GROUP_SYMBOLS  # noqa: F401  (the group the prover's levels run as)
-
-MAX_PARTIES = 32
 
 
 class ShamirPrimaryConfig(ctypes.Structure):
@@ -26,19 +21,16 @@ class ShamirPrimaryResult(ctypes.Structure):
                 ("t_rounds_ms", ctypes.c_double), ("t_finals_ms", ctypes.c_double)]
 
 
-_vp, _sz, _i = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
 SHAMIR_PRIMARY_SYMBOLS = ["cozk_shamir_primary_create", "cozk_shamir_primary_error", "cozk_shamir_primary_destroy", "cozk_shamir_primary_prove",
                           "cozk_shamir_primary_proof_bytes", "cozk_shamir_primary_msgs_len", "cozk_shamir_primary_msgs",
                           "cozk_shamir_primary_finals_len", "cozk_shamir_primary_finals", "cozk_shamir_primary_get_stats"]
 
 
-class ShamirPrimary(L.HarnessHandle):
+class ShamirPrimary(ShamirHarnessHandle):
     """n Shamir parties of degree t prove the primary sumcheck; one device per party (an int: all on it).  mix = "uniform" | "sha2"
-    (or 0 | 1).  tamper_final = k > 0 (tests): element k - 1 of `finals` is corrupted before it is opened"""
+    (or 0 | 1).  tamper_final = k > 0 (tests): element k - 1 of `finals` is corrupted before it is opened.  msgs(): the masked round
+    messages [D round + k][p <= 2t].  finals(): [value][p <= t]: E_0(r) .. E_{n_mem - 1}(r), lookup_outputs(r)"""
     PREFIX, CONFIG, RESULT = "cozk_shamir_primary", ShamirPrimaryConfig, ShamirPrimaryResult
-    EXTRA = {"cozk_shamir_primary_msgs_len": (_sz, [_vp]), "cozk_shamir_primary_msgs": (_i, [_vp, _vp, _sz]),
-             "cozk_shamir_primary_finals_len": (_sz, [_vp]), "cozk_shamir_primary_finals": (_i, [_vp, _vp, _sz]),
-             "cozk_shamir_primary_get_stats": (_i, [_vp, ctypes.POINTER(ShamirGpStats)])}
 
     def __init__(self, log_n=6, n_mem=54, mix="uniform", parties=3, degree=1, devices=0, seed=1, share_counter=0, mul_counter=0, rand_counter=0,
                  tamper_final=0):
@@ -48,38 +40,10 @@ class ShamirPrimary(L.HarnessHandle):
         cfg.mix = mix if isinstance(mix, int) else (1 if mix == "sha2" else 0)
         cfg.degree = degree
         cfg.num_parties = parties
-        devs = [devices] * MAX_PARTIES if isinstance(devices, int) else list(devices) + [0] * (MAX_PARTIES - len(devices))
-        cfg.devices = (ctypes.c_int * MAX_PARTIES)(*devs[:MAX_PARTIES])
+        cfg.devices = self._devices(devices)
         cfg.seed = seed
         cfg.share_counter = share_counter
         cfg.mul_counter = mul_counter
         cfg.rand_counter = rand_counter
         cfg.tamper_final = tamper_final
         self._open(cfg)
-
-    def _fe_list(self, what):
-        n = self._f("_" + what + "_len")(self.h)
-        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
-        rc = self._f("_" + what)(self.h, out.ctypes.data, n)
-        if rc != L.OK:
-            raise L.CozkError(rc, what)
-        return mont_limbs_to_int(out[:n])
-
-    def msgs(self):
-        """the masked round messages [D round + k][p <= 2t]"""
-        k = 2 * self.cfg.degree + 1
-        v = self._fe_list("msgs")
-        return [v[i:i + k] for i in range(0, len(v), k)]
-
-    def finals(self):
-        """[value][p <= t]: E_0(r) .. E_{n_mem - 1}(r), lookup_outputs(r)"""
-        k = self.cfg.degree + 1
-        v = self._fe_list("finals")
-        return [v[i:i + k] for i in range(0, len(v), k)]
-
-    def stats(self):
-        st = ShamirGpStats()
-        rc = self._f("_get_stats")(self.h, ctypes.byref(st))
-        if rc != L.OK:
-            raise L.CozkError(rc, "get_stats")
-        return st

@@ -6,10 +6,9 @@ import ctypes
 import numpy as np
 
 from . import _lib as L
-from .engine import ShamirGpStats, fr_to_mont_limbs, mont_limbs_to_int
+from .engine import SHAMIR_MAX_PARTIES as MAX_PARTIES, ShamirHarnessHandle, fr_to_mont_limbs, mont_limbs_to_int
 
 FIRST, SECOND = L.SPARTAN_GROUP_FIRST, L.SPARTAN_GROUP_SECOND
-MAX_PARTIES = 32
 
 
 class SpartanGroup:
@@ -84,18 +83,16 @@ class ShamirSpartanResult(ctypes.Structure):
                 ("t_sumcheck2_ms", ctypes.c_double), ("t_open_ms", ctypes.c_double)]
 
 
-_vp, _sz, _i = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
 SHAMIR_SPARTAN_SYMBOLS = ["cozk_shamir_spartan_create", "cozk_shamir_spartan_error", "cozk_shamir_spartan_destroy", "cozk_shamir_spartan_prove",
                           "cozk_shamir_spartan_proof_bytes", "cozk_shamir_spartan_msgs_len", "cozk_shamir_spartan_msgs",
                           "cozk_shamir_spartan_finals_len", "cozk_shamir_spartan_finals", "cozk_shamir_spartan_get_stats"]
 
 
-class ShamirSpartanHarness(L.HarnessHandle):
-    """n Shamir parties of degree t prove the co-noir-spartan instance of (seed, log_n); one device per party (an int: all on it)"""
+class ShamirSpartanHarness(ShamirHarnessHandle):
+    """n Shamir parties of degree t prove the co-noir-spartan instance of (seed, log_n); one device per party (an int: all on it).
+    msgs(): the masked first-sumcheck messages [m][p <= 2t], m = 4 round + evaluation index.  finals(): [value][p <= t]: za, zb,
+    zc(rx); round by round the second sumcheck's g(0..2); z's final value; z(ry)"""
     PREFIX, CONFIG, RESULT = "cozk_shamir_spartan", ShamirSpartanConfig, ShamirSpartanResult
-    EXTRA = {"cozk_shamir_spartan_msgs_len": (_sz, [_vp]), "cozk_shamir_spartan_msgs": (_i, [_vp, _vp, _sz]),
-             "cozk_shamir_spartan_finals_len": (_sz, [_vp]), "cozk_shamir_spartan_finals": (_i, [_vp, _vp, _sz]),
-             "cozk_shamir_spartan_get_stats": (_i, [_vp, ctypes.POINTER(ShamirGpStats)])}
 
     def __init__(self, log_n=10, parties=3, degree=1, devices=0, seed=1, precompute=True, share_counter=0, rand_counter=0):
         cfg = ShamirSpartanConfig()
@@ -103,36 +100,8 @@ class ShamirSpartanHarness(L.HarnessHandle):
         cfg.precompute = 1 if precompute else 0
         cfg.degree = degree
         cfg.num_parties = parties
-        devs = [devices] * MAX_PARTIES if isinstance(devices, int) else list(devices) + [0] * (MAX_PARTIES - len(devices))
-        cfg.devices = (ctypes.c_int * MAX_PARTIES)(*devs[:MAX_PARTIES])
+        cfg.devices = self._devices(devices)
         cfg.seed = seed
         cfg.share_counter = share_counter
         cfg.rand_counter = rand_counter
         self._open(cfg)
-
-    def _fe_list(self, what):
-        n = self._f("_" + what + "_len")(self.h)
-        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
-        rc = self._f("_" + what)(self.h, out.ctypes.data, n)
-        if rc != L.OK:
-            raise L.CozkError(rc, what)
-        return mont_limbs_to_int(out[:n])
-
-    def msgs(self):
-        """the masked first-sumcheck messages [m][p <= 2t], m = 4 round + evaluation index"""
-        k = 2 * self.cfg.degree + 1
-        v = self._fe_list("msgs")
-        return [v[i:i + k] for i in range(0, len(v), k)]
-
-    def finals(self):
-        """[value][p <= t]: za, zb, zc(rx); round by round the second sumcheck's g(0..2); z's final value; z(ry)"""
-        k = self.cfg.degree + 1
-        v = self._fe_list("finals")
-        return [v[i:i + k] for i in range(0, len(v), k)]
-
-    def stats(self):
-        st = ShamirGpStats()
-        rc = self._f("_get_stats")(self.h, ctypes.byref(st))
-        if rc != L.OK:
-            raise L.CozkError(rc, "get_stats")
-        return st
