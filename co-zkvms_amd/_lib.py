@@ -196,6 +196,11 @@ SIGNATURES = {
     "cozk_primary_group_len": (_sz, [_vp]),
     "cozk_primary_group_level_buffer": (_i, [_vp, _i, _i, _pp, ctypes.POINTER(_sz)]),
     "cozk_primary_group_free": (_i, [_vp]),
+    "cozk_primary_group_create_king": (_i, [_vp, _vp, _i, _pp]),
+    "cozk_primary_group_level_king": (_i, [_vp, _i, _vp, _vp, _sz, ctypes.POINTER(_sz)]),
+    "cozk_primary_group_staging_bytes": (_sz, [_vp]),
+    "cozk_primary_level_elems": (_sz, [_vp, _i]),
+    "cozk_primary_plan": (_i, [_vp, _vp, _sz, _vp, _i, _vp, ctypes.POINTER(_u64)]),
     "cozk_shift_group_create": (_i, [_vp, _vp, _i, _vp, _pp]),
     "cozk_shift_group_round": (_i, [_vp, _vp, _vp]),
     "cozk_shift_group_final": (_i, [_vp, _vp, _i, _vp]),

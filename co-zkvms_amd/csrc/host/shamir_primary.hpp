@@ -24,9 +24,23 @@
 //             cozk_primary_group on sender 0's context: a level call per exchange, a grouped finish per round.  Otherwise per sender
 //             cozk_primary_level, cozk_shamir_scatter of its level buffer to the senders (the dealing launch + peer copies), per
 //             receiver cozk_shamir_combine_vec, copied into its level buffer.  Same keys, counters and positions: same bytes.
-// Semi-honest.  Not built: a king / double-random variant of the exchange (its pair length depends on the public item counts), one
-// party per process, groups over several GPUs, one item list shared by the senders, worker sub-nets (log_workers), the primary inside
-// a chained Shamir flow.
+//
+// The KING construct (cozk_shamir_primary_prep + cozk_shamir_primary_prove_king; tests/shamir_primary_king_ref.py) moves everything that
+// needs fresh randomness in front of the witness.  Which (index, instruction) items are live in a round depends on the public flags
+// alone, so the sizes of all exchanges are known beforehand (cozk_primary_plan) and ONE double-random pair of their sum serves them,
+// exchange e at the element offset = the sum of the earlier exchanges' n_elems:
+//   prep      (A) the M opening masks at rand_counter, pair 0 -- the masks prove deals; (B) one cozk_shamir_rand_inproc-rule dealing of
+//             `total` elements at rand_counter + M, pair 0 only, both halves for parties 0..2t only (receivers are the senders).
+//   exchange  sender m sends z_m + r_2t,m[off + pos] to the king, who opens zed = slot + r with lagrange(1..2t + 1); receiver q keeps
+//             zed - r_t,q[off + pos].  Grouped: one cozk_primary_group_level_king on a keyless group.  Otherwise cozk_primary_level per
+//             sender, cozk_vec_binop adds the r_2t slice, the king's context runs cozk_shamir_king_finish for the senders of its device
+//             and each result is copied into that sender's level buffer; a sender on another device gets zed by peer copy and
+//             subtracts its slice on its own stream.  Same values, same offsets: same bytes.
+//   check     before a level launches anything its size is compared with the plan's (a bound flag that is zero would change it).
+// Transcript, masks, openings, finals and verifier are those of the resharing prover: the same proof bytes.
+// Semi-honest.  Not built: the other n - t - 1 pairs of the prep's dealing (one pair is extracted: `total` elements are dealt per
+// party for `total` pair elements), one party per process, groups over several GPUs, one item list shared by the senders, worker
+// sub-nets (log_workers), the primary inside a chained Shamir flow.
 #pragma once
 
 // msgs: [D round + k][p <= 2t]; finals: E_0 .. E_{n_mem - 1}, lookup_outputs
@@ -38,13 +52,119 @@ struct cozk_shamir_primary : cozk::ShamirHarness {
     std::vector<std::vector<cozk::PolyH>> E;     // [p <= 2t][m]: the sender's share of E_m, PLAIN
     std::vector<cozk::PolyH> outputs;            // [p <= 2t]
     std::vector<std::vector<uint8_t>> mul_keys;  // [p][t]: the keys of sender p's re-deals
+    // what cozk_shamir_primary_prep made, consumed by cozk_shamir_primary_prove_king
+    struct Prep {
+        bool made = false, used = false;
+        std::vector<uint64_t> plan;  // [round][COZK_PRIMARY_MAX_LEVELS]: cozk_primary_plan
+        uint64_t total = 0, n_exchanges = 0;
+        double t_offline_ms = 0;
+        std::vector<std::vector<fe>> zero;  // [p <= 2t][m < M]
+        std::vector<cozk_vec*> rt, r2t;     // [p <= 2t]: the halves of the exchanges' pair, `total` elements each
+    } prep;
 };
 
 namespace {
 
 typedef Handle<cozk_primary_group, cozk_primary_group_free> PrimaryGroupH;
 
-static void shamir_primary_prove(cozk_shamir_primary* h, bool verify, cozk_shamir_primary_result* res) {
+// frees the pair of a prep: every vector with its party's device current
+static void shamir_primary_release_pairs(cozk_shamir_primary* h) {
+    for (size_t p = 0; p < h->prep.rt.size(); p++) {
+        (void)hipSetDevice(h->pcs[p]->device);
+        cozk_vec_free(h->prep.rt[p]);
+        cozk_vec_free(h->prep.r2t[p]);
+    }
+    h->prep.rt.clear();
+    h->prep.r2t.clear();
+}
+
+static cozk_vec shamir_primary_view(cozk_ctx* c, const void* d, size_t n) {
+    cozk_vec v{};
+    v.ctx = c;
+    v.n = n;
+    v.kind = COZK_SCALAR_FR;
+    v.d = const_cast<void*>(d);
+    v.bytes = n * sizeof(fe);
+    v.owned = false;
+    return v;
+}
+
+// One king exchange composed of the existing calls: buf[p] = sender p's level buffer holding its n_el unmasked slot values, replaced by
+// its share of the reduced sharing.  Pair elements off .. off + n_el.
+static void shamir_primary_king_exchange(const ShamirProve& sp, cozk_shamir_primary* h, const std::vector<const void*>& buf, size_t n_el, size_t off,
+                                         int king) {
+    const int t = sp.t, senders = sp.senders;
+    const std::vector<cozk_ctx*>& pcs = sp.pcs;
+    cozk_ctx* const kc = pcs[(size_t)king];
+    const size_t bytes = n_el * sizeof(fe);
+    std::vector<VecH> masked((size_t)senders);  // m_p = z_p + r_2t,p on the king's device
+    for (int p = 0; p < senders; p++) {
+        cozk_ctx* c = pcs[(size_t)p];
+        sp.set_dev(p);
+        const cozk_vec zv = shamir_primary_view(c, buf[(size_t)p], n_el), rv = shamir_primary_view(c, (const fe*)h->prep.r2t[(size_t)p]->d + off, n_el);
+        cozk_vec* m = nullptr;
+        rc_check(cozk_vec_alloc(c, n_el, COZK_SCALAR_FR, &m), c, "vec_alloc");
+        VecH mh(m);
+        rc_check(cozk_vec_binop(c, COZK_OP_ADD, 0, &zv, &rv, m), c, "vec_binop(mask)");
+        if (c->device == kc->device) {
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            masked[(size_t)p] = std::move(mh);
+            continue;
+        }
+        cozk_vec* km = nullptr;
+        sp.set_dev(king);
+        rc_check(cozk_vec_alloc(kc, n_el, COZK_SCALAR_FR, &km), kc, "vec_alloc");
+        masked[(size_t)p] = VecH(km);
+        sp.set_dev(p);
+        HIP_TRY(hipMemcpyPeerAsync(km->d, kc->device, m->d, c->device, bytes, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    // the king opens zed and unmasks for the senders of its device in one launch; zed itself is kept only for senders elsewhere
+    std::vector<int> local, remote;
+    for (int q = 0; q < senders; q++) (pcs[(size_t)q]->device == kc->device ? local : remote).push_back(q);
+    std::vector<const cozk_vec*> mv, rt;
+    for (int p = 0; p < senders; p++) mv.push_back(masked[(size_t)p].h);
+    for (int q : local) rt.push_back(h->prep.rt[(size_t)q]);
+    sp.set_dev(king);
+    std::vector<cozk_vec*> out(local.size(), nullptr);
+    cozk_vec* z = nullptr;
+    if (!local.empty()) {
+        rc_check(cozk_shamir_king_finish(kc, mv.data(), t, rt.data(), off, (int)local.size(), out.data(), remote.empty() ? nullptr : &z), kc, "shamir_king_finish(level)");
+    } else {  // the king shares its device with no sender: the open alone
+        std::vector<uint32_t> pts((size_t)senders);
+        for (int p = 0; p < senders; p++) pts[(size_t)p] = (uint32_t)p + 1;
+        rc_check(cozk_shamir_combine_vec(kc, mv.data(), pts.data(), (size_t)senders, 2 * t, &z), kc, "shamir_combine_vec(level)");
+    }
+    VecH zh(z);
+    std::vector<VecH> outs;
+    for (cozk_vec* o : out) outs.emplace_back(o);
+    for (size_t i = 0; i < local.size(); i++)
+        HIP_TRY(hipMemcpyAsync(const_cast<void*>(buf[(size_t)local[i]]), cozk_vec_device_ptr(outs[i].h), bytes, hipMemcpyDeviceToDevice, kc->stream));
+    HIP_TRY(hipStreamSynchronize(kc->stream));
+    for (int q : remote) {
+        cozk_ctx* c = pcs[(size_t)q];
+        cozk_vec* zq = nullptr;
+        sp.set_dev(q);
+        rc_check(cozk_vec_alloc(c, n_el, COZK_SCALAR_FR, &zq), c, "vec_alloc");
+        VecH zqh(zq);
+        sp.set_dev(king);
+        HIP_TRY(hipMemcpyPeerAsync(zq->d, c->device, z->d, kc->device, bytes, kc->stream));
+        HIP_TRY(hipStreamSynchronize(kc->stream));
+        sp.set_dev(q);
+        const cozk_vec rv = shamir_primary_view(c, (const fe*)h->prep.rt[(size_t)q]->d + off, n_el);
+        cozk_vec ov = shamir_primary_view(c, buf[(size_t)q], n_el);
+        rc_check(cozk_vec_binop(c, COZK_OP_SUB, 0, zq, &rv, &ov), c, "vec_binop(unmask)");
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    sp.set_dev(king);  // the king's vectors go back to the king's pool
+    masked.clear();
+    outs.clear();
+    zh = VecH();
+}
+
+// king < 0: the resharing construct; otherwise the king construct on the prep's pair
+static void shamir_primary_prove(cozk_shamir_primary* h, bool verify, cozk_shamir_primary_result* res, int king = -1) {
+    const bool kingly = king >= 0;
     ShamirProve sp(h, verify);
     const int t = sp.t, senders = sp.senders, openers = sp.openers, log_n = h->cfg.log_n;
     const size_t n_mem = (size_t)h->cfg.n_mem, n_instr = h->inst.instrs.size();
@@ -80,7 +200,12 @@ static void shamir_primary_prove(cozk_shamir_primary* h, bool verify, cozk_shami
     const double t1 = now_ms();
     // ---- masks
     const size_t M = (size_t)D * (size_t)log_n;
-    sp.deal_masks(h->cfg.rand_counter, M);
+    if (kingly) {
+        COZK_REQUIRE(h->prep.zero.size() == (size_t)senders && h->prep.zero[0].size() == M, "shamir_primary_prove_king: the preprocessing holds other masks");
+        sp.zero = h->prep.zero;
+    } else {
+        sp.deal_masks(h->cfg.rand_counter, M);
+    }
     const double t2 = now_ms();
     // ---- rounds
     PrimaryGroupH g;
@@ -92,8 +217,10 @@ static void shamir_primary_prove(cozk_shamir_primary* h, bool verify, cozk_shami
             keys.insert(keys.end(), h->mul_keys[(size_t)p].begin(), h->mul_keys[(size_t)p].end());
         }
         set_dev(0);
-        rc_check(cozk_primary_group_create(c0, members.data(), senders, keys.data(), &g.h), c0, "primary_group_create");
+        if (kingly) rc_check(cozk_primary_group_create_king(c0, members.data(), senders, &g.h), c0, "primary_group_create_king");
+        else rc_check(cozk_primary_group_create(c0, members.data(), senders, keys.data(), &g.h), c0, "primary_group_create");
     }
+    std::vector<const cozk_vec*> k_rt(h->prep.rt.begin(), h->prep.rt.end()), k_r2t(h->prep.r2t.begin(), h->prep.r2t.end());
     std::vector<uint32_t> pts((size_t)senders);
     for (int p = 0; p < senders; p++) pts[(size_t)p] = (uint32_t)p + 1;
     uint64_t ctr = h->cfg.mul_counter, rr[4];
@@ -116,7 +243,17 @@ static void shamir_primary_prove(cozk_shamir_primary* h, bool verify, cozk_shami
         }
         for (int level = 1; level <= n_levels; level++) {
             size_t n_el = 0;
-            if (grouped) {
+            if (kingly) {  // the plan, before the level launches anything: exchange e lives at the offset the earlier ones' sizes give
+                const uint64_t have = cozk_primary_level_elems(prims[0].h, level), want = h->prep.plan[(size_t)COZK_PRIMARY_MAX_LEVELS * round + level - 1];
+                COZK_REQUIRE(have == want && n_exchanged + have <= h->prep.total,
+                             "shamir_primary_prove_king: round " + std::to_string(round) + " level " + std::to_string(level) + " holds " + std::to_string(have) +
+                                 " elements, the plan says " + std::to_string(want) + " (a bound flag is zero?)");
+            }
+            if (grouped && kingly) {
+                set_dev(0);
+                rc_check(cozk_primary_group_level_king(g.h, level, k_rt.data(), k_r2t.data(), (size_t)n_exchanged, &n_el), c0, "primary_group_level_king");
+                if (n_el) h->stats.group_rounds++;
+            } else if (grouped) {
                 set_dev(0);
                 rc_check(cozk_primary_group_level(g.h, level, ctr, &n_el), c0, "primary_group_level");
                 if (n_el) h->stats.group_rounds++;
@@ -131,7 +268,9 @@ static void shamir_primary_prove(cozk_shamir_primary* h, bool verify, cozk_shami
                     if (p == 0) n_el = ne;
                     COZK_REQUIRE(ne == n_el, "shamir_primary: the senders' level sizes differ (the flags are public)");
                 }
-                if (n_el) {
+                if (n_el && kingly) {
+                    shamir_primary_king_exchange(sp, h, buf, n_el, (size_t)n_exchanged, king);
+                } else if (n_el) {
                     // the degree reduction, composed: every sender deals its level buffer to the senders, every sender combines
                     std::vector<std::vector<VecH>> dealt((size_t)senders);  // [dealer][receiver], the receiver's vector
                     for (int m = 0; m < senders; m++) {
@@ -190,6 +329,7 @@ static void shamir_primary_prove(cozk_shamir_primary* h, bool verify, cozk_shami
     }
     g = PrimaryGroupH();
     sp.sync_all();
+    if (kingly) shamir_primary_release_pairs(h);  // consumed: every stream has drained behind the last exchange
     const double t3 = now_ms();
     // ---- the final claims: E(r) and lookup_outputs(r) from the openers, flags(r) public
     {
@@ -276,7 +416,45 @@ static void shamir_primary_prove(cozk_shamir_primary* h, bool verify, cozk_shami
     finish_proof(h, w.b, res);
 }
 
+// create went through
+static bool shamir_primary_built(const cozk_shamir_primary* x) {
+    return x->E.size() == (size_t)(2 * x->t + 1) && x->E.back().size() == (size_t)x->cfg.n_mem && x->outputs.back().h != nullptr;
+}
+
+// The preprocessing of one king prove: the plan from the public flags, (A) the opening masks, (B) the exchanges' pair.  Refused on a
+// handle that has been preprocessed: (rand_keys, rand_counter .. rand_counter + M + total) must never be used again.
+static void shamir_primary_prep(cozk_shamir_primary* h) {
+    const int t = h->t, n = h->n, senders = 2 * t + 1, log_n = h->cfg.log_n;
+    const std::vector<cozk_ctx*>& pcs = h->pcs;
+    COZK_REQUIRE(!h->prep.made, "shamir_primary_prep: the harness has been preprocessed (its key and counter range must never be used again)");
+    const ShamirGpArgs a{pcs.data(), nullptr, 0, t, n, nullptr, false};
+    cozk_shamir_primary::Prep pr;
+    shamir_gp_sync_all(a);
+    const double t0 = now_ms();
+    HIP_TRY(hipSetDevice(pcs[0]->device));
+    std::vector<const cozk_vec*> fl;
+    for (const VecH& f : h->flags[0]) fl.push_back(f.h);
+    pr.plan.assign((size_t)COZK_PRIMARY_MAX_LEVELS * log_n, 0);
+    rc_check(cozk_primary_plan(pcs[0], h->inst.instrs.data(), h->inst.instrs.size(), fl.data(), log_n, pr.plan.data(), &pr.total), pcs[0], "primary_plan");
+    for (uint64_t e : pr.plan) pr.n_exchanges += e ? 1 : 0;
+    const size_t M = (size_t)primary_sumcheck_degree(h->inst.instrs) * (size_t)log_n;
+    std::vector<const uint8_t*> rk((size_t)n);
+    for (int p = 0; p < n; p++) rk[(size_t)p] = h->rand_keys[(size_t)p].data();
+    pr.zero = shamir_gp_zero_masks(a, rk.data(), h->cfg.rand_counter, M);
+    if (pr.total) {
+        pr.rt.assign((size_t)senders, nullptr);
+        pr.r2t.assign((size_t)senders, nullptr);
+        rc_check(shamir_rand_pairs_inproc(pcs.data(), rk.data(), (size_t)pr.total, t, n, h->cfg.rand_counter + M, 1, senders, pr.rt.data(), pr.r2t.data()), pcs[0],
+                 "shamir_rand_pairs_inproc");
+    }
+    shamir_gp_sync_all(a);
+    pr.t_offline_ms = now_ms() - t0;
+    pr.made = true;
+    h->prep = std::move(pr);
+}
+
 static void shamir_primary_release(cozk_shamir_primary* h) {
+    shamir_primary_release_pairs(h);
     for (size_t p = 0; p < h->parties.size(); p++) {
         if (h->parties[p].ctx) (void)hipSetDevice(h->parties[p].ctx->device);
         if (p < h->flags.size()) h->flags[p].clear();
@@ -369,12 +547,52 @@ int cozk_shamir_primary_destroy(cozk_shamir_primary* h) {
 }
 
 int cozk_shamir_primary_prove(cozk_shamir_primary* h, int verify, cozk_shamir_primary_result* res) {
-    return shamir_harness_prove(
-        h, res, "shamir_primary",
-        [](const cozk_shamir_primary* x) {
-            return x->E.size() == (size_t)(2 * x->t + 1) && x->E.back().size() == (size_t)x->cfg.n_mem && x->outputs.back().h != nullptr;
-        },
-        [&](cozk_shamir_primary* x, cozk_shamir_primary_result* r) { shamir_primary_prove(x, verify != 0, r); });
+    return shamir_harness_prove(h, res, "shamir_primary", shamir_primary_built,
+                                [&](cozk_shamir_primary* x, cozk_shamir_primary_result* r) { shamir_primary_prove(x, verify != 0, r); });
+}
+
+int cozk_shamir_primary_prep_get_result(const cozk_shamir_primary* h, cozk_shamir_primary_prep_result* res) {
+    if (!h || !res) return COZK_ERR_INVALID_ARG;
+    memset(res, 0, sizeof *res);
+    if (!h->prep.made) return COZK_OK;
+    res->n_openings = h->prep.zero.empty() ? 0 : h->prep.zero[0].size();
+    res->pair_elems = h->prep.total;
+    res->n_exchanges = h->prep.n_exchanges;
+    res->used = h->prep.used ? 1 : 0;
+    res->t_offline_ms = h->prep.t_offline_ms;
+    return COZK_OK;
+}
+
+int cozk_shamir_primary_prep(cozk_shamir_primary* h, cozk_shamir_primary_prep_result* res) {
+    if (!h || !res) return COZK_ERR_INVALID_ARG;
+    memset(res, 0, sizeof *res);
+    if (h->n == 0 || h->pcs.size() != (size_t)h->n || !shamir_primary_built(h)) {
+        h->error = "shamir_primary_prep: the harness was not built";
+        return COZK_ERR_INVALID_ARG;
+    }
+    h->error.clear();
+    try {
+        shamir_primary_prep(h);
+    } catch (const CozkError& e) {
+        h->error = e.what();
+        for (cozk_ctx* c : h->pcs) (void)hipStreamSynchronize(c->stream);
+        return e.code;
+    } catch (const std::exception& e) {
+        h->error = e.what();
+        return COZK_ERR_INTERNAL;
+    }
+    return cozk_shamir_primary_prep_get_result(h, res);
+}
+
+int cozk_shamir_primary_prove_king(cozk_shamir_primary* h, int king, int verify, cozk_shamir_primary_result* res) {
+    return shamir_harness_prove(h, res, "shamir_primary_king", shamir_primary_built, [&](cozk_shamir_primary* x, cozk_shamir_primary_result* r) {
+        // everything is refused before the first launch; the prep is marked used before it
+        COZK_REQUIRE(king >= 0 && king < x->n, "shamir_primary_prove_king: 0 <= king < num_parties");
+        COZK_REQUIRE(x->prep.made, "shamir_primary_prove_king: no preprocessing (cozk_shamir_primary_prep)");
+        COZK_REQUIRE(!x->prep.used, "shamir_primary_prove_king: the preprocessing has been used (a pair must never be used twice)");
+        x->prep.used = true;
+        shamir_primary_prove(x, verify != 0, r, king);
+    });
 }
 
 int cozk_shamir_primary_proof_bytes(const cozk_shamir_primary* h, uint8_t* out, size_t cap) { return harness_proof_bytes(h, out, cap); }

@@ -19,6 +19,13 @@
 //   k_primary_group_final    k_primary_final<1> with the member on a grid axis; one k_finish_sums over all members' rows.
 // Two launches per level and two per finish whatever k is.  Receivers are the 2t + 1 senders only: a party above 2t holds no program
 // state and would have no use for a slot value.
+//
+// The KING form of the level (cozk_primary_group_level_king) reduces the degree on a preprocessed double-random pair ([r]_t, [r]_2t)
+// instead (Damgard-Nielsen; shamir.hip): sender m sends z + r_2t,m to the king, who opens zed = sum_m lambda_m (z_m + r_2t,m) = slot + r
+// and sends it to everyone; receiver q keeps zed - r_t,q.  No PRF runs online and the staging block is [k][level_elems].
+//   k_primary_group_mask     the deal kernel's grid and slot values; staging[m][pos] = z + r_2t[m][r_offset + pos].
+//   the finish               k_shamir_king_finish (shamir.hip: the one copy of the open-and-unmask step) over the table of the
+//                            members' level buffers, grid (element blocks): 2k x 32 B read, k x 32 B written per element.
 
 static constexpr int PRIM_GROUP_MAX = COZK_PRIMARY_GROUP_MAX;  // 2t + 1 with 2t <= COZK_SHAMIR_MAX_DEGREE
 static constexpr int PRIM_GROUP_MAX_T = (PRIM_GROUP_MAX - 1) / 2;
@@ -89,6 +96,29 @@ __global__ void __launch_bounds__(PT) k_primary_group_deal(PrimGroupArgs a, size
     }
 }
 
+struct PrimGroupMaskArgs {
+    const fe* r2t[PRIM_GROUP_MAX];  // member m's degree-2t half, advanced by the element offset
+};
+// k_primary_group_deal's walk over the slots of one (item, evaluation point, member); the value is masked, not dealt
+__global__ void __launch_bounds__(PT) k_primary_group_mask(PrimGroupArgs a, PrimGroupMaskArgs r, size_t cap, int n_instr, int n_mem, int D, size_t n_items,
+                                                        int level, fe* __restrict__ stage, size_t level_elems) {
+    const size_t j = (size_t)blockIdx.x * PT + threadIdx.x;
+    if (j >= n_items) return;
+    const unsigned m = blockIdx.z;
+    const PrimCtx<1> c = prim_group_ctx(a.m[m], cap, n_instr, n_mem, D, j, (int)blockIdx.y);
+    if (level > c.in->n_levels || c.in->nq[level - 1] == 0) return;  // this instruction has nothing at this level
+    const fe* mask = r.r2t[m];
+    fe* out = stage + (size_t)m * level_elems;
+    for (int q = 0; q < c.in->n_slots; q++) {
+        const PrimSlot& sl = c.in->slots[q];
+        if (sl.level != level) continue;
+        fe z = prim_products<1>(c, sl.prod, sl.n_prod);
+        if (sl.has_add) z = Fr::add(z, sh_ab_sum<1>(prim_lc<1>(c, sl.add)));
+        const size_t pos = prim_slot_pos<1>(c, level - 1, sl.q);
+        fe_store(out + pos, Fr::add(z, fe_load(mask + pos)));
+    }
+}
+
 struct PrimGroupCombineArgs {
     fe* out[PRIM_GROUP_MAX];  // receiver q's level buffer
     fe lambda[PRIM_GROUP_MAX];
@@ -139,8 +169,10 @@ struct cozk_primary_group {
     cozk_ctx* driver;
     int k, t;
     std::vector<cozk_primary*> members;  // referred to
-    prf_key* d_keys;                     // [k][t], from the driver's pool
-    fe* stage;                           // [k][k][stage_cap / k^2 ...]: the dealt values of the level in flight, from the driver's pool
+    bool keyless;                        // made by cozk_primary_group_create_king: king levels only
+    prf_key* d_keys;                     // [k][t], from the driver's pool; NULL in a keyless group
+    fe* stage;                           // [k][k][stage_cap / k^2 ...]: the dealt values of the level in flight ([k][..]: the masked values of a
+                                         // king level), from the driver's pool
     size_t stage_cap;                    // elements
     fe lambda[PRIM_GROUP_MAX];
 };
@@ -195,6 +227,59 @@ static PrimGroupArgs primary_group_args(const cozk_primary_group* g) {
     return a;
 }
 
+// the king's open and unmask (shamir.hip): z = sum_{j < k} lambda_j m[j], out[q] = z - (rt[q] + off) for q < count
+void shamir_launch_king_finish(hipStream_t st, const fe* const* m, int k, const fe* const* rt, size_t off, int count, fe* const* out, size_t n);
+
+// both creates: keys == NULL only in a keyless group
+static int primary_group_make(cozk_ctx* driver, cozk_primary* const* members, int k, const uint8_t* keys, bool keyless, const std::string& who,
+                              cozk_primary_group** out) {
+    if (out) *out = nullptr;
+    return cozk_guard(driver, [&] {
+        COZK_REQUIRE(driver && members && (keys || keyless) && out, who + ": null argument");
+        COZK_REQUIRE(k >= 3 && k <= PRIM_GROUP_MAX && k % 2 == 1, who + ": k = 2t + 1 with 1 <= t, k <= COZK_PRIMARY_GROUP_MAX");
+        primary_group_check(driver, members, k, who, false);
+        std::vector<cozk_ctx*> owners;
+        for (int i = 0; i < k; i++) owners.push_back(members[i]->ctx);
+        drain_streams(owners);
+        cozk_primary_group* g = new cozk_primary_group();
+        g->driver = driver;
+        g->k = k;
+        g->t = (k - 1) / 2;
+        g->members.assign(members, members + k);
+        g->keyless = keyless;
+        g->d_keys = nullptr;
+        g->stage = nullptr;
+        g->stage_cap = 0;
+        uint32_t pts[PRIM_GROUP_MAX];
+        for (int i = 0; i < k; i++) pts[i] = (uint32_t)i + 1;
+        lagrange_host(pts, (size_t)k, g->lambda);
+        try {
+            std::vector<prf_key> hk(keyless ? 0 : (size_t)k * g->t);
+            for (size_t i = 0; i < hk.size(); i++) hk[i] = prf_key_from_bytes(keys + (size_t)COZK_PRF_KEY_BYTES * i);
+            if (!keyless) {
+                g->d_keys = (prf_key*)ctx_dev_alloc(driver, hk.size() * sizeof(prf_key));
+                HIP_TRY(hipMemcpyAsync(g->d_keys, hk.data(), hk.size() * sizeof(prf_key), hipMemcpyHostToDevice, driver->stream));
+                HIP_TRY(hipStreamSynchronize(driver->stream));
+            }
+        } catch (...) {
+            ctx_dev_free(driver, g->d_keys);
+            delete g;
+            throw;
+        }
+        *out = g;
+    });
+}
+
+// the staging block of `need` elements, grown on demand
+static void primary_group_stage(cozk_primary_group* g, size_t need) {
+    if (need <= g->stage_cap) return;
+    ctx_dev_free(g->driver, g->stage);
+    g->stage = nullptr;
+    g->stage_cap = 0;
+    g->stage = (fe*)ctx_dev_alloc(g->driver, need * sizeof(fe));
+    g->stage_cap = need;
+}
+
 extern "C" {
 
 int cozk_primary_group_free(cozk_primary_group* g) {
@@ -206,37 +291,11 @@ int cozk_primary_group_free(cozk_primary_group* g) {
 }
 
 int cozk_primary_group_create(cozk_ctx* driver, cozk_primary* const* members, int k, const uint8_t* keys, cozk_primary_group** out) {
-    if (out) *out = nullptr;
-    return cozk_guard(driver, [&] {
-        COZK_REQUIRE(driver && members && keys && out, "primary_group_create: null argument");
-        COZK_REQUIRE(k >= 3 && k <= PRIM_GROUP_MAX && k % 2 == 1, "primary_group_create: k = 2t + 1 with 1 <= t, k <= COZK_PRIMARY_GROUP_MAX");
-        primary_group_check(driver, members, k, "primary_group_create", false);
-        std::vector<cozk_ctx*> owners;
-        for (int i = 0; i < k; i++) owners.push_back(members[i]->ctx);
-        drain_streams(owners);
-        cozk_primary_group* g = new cozk_primary_group();
-        g->driver = driver;
-        g->k = k;
-        g->t = (k - 1) / 2;
-        g->members.assign(members, members + k);
-        g->d_keys = nullptr;
-        g->stage = nullptr;
-        g->stage_cap = 0;
-        uint32_t pts[PRIM_GROUP_MAX];
-        for (int i = 0; i < k; i++) pts[i] = (uint32_t)i + 1;
-        lagrange_host(pts, (size_t)k, g->lambda);
-        try {
-            std::vector<prf_key> hk((size_t)k * g->t);
-            for (size_t i = 0; i < hk.size(); i++) hk[i] = prf_key_from_bytes(keys + (size_t)COZK_PRF_KEY_BYTES * i);
-            g->d_keys = (prf_key*)ctx_dev_alloc(driver, hk.size() * sizeof(prf_key));
-            HIP_TRY(hipMemcpyAsync(g->d_keys, hk.data(), hk.size() * sizeof(prf_key), hipMemcpyHostToDevice, driver->stream));
-            HIP_TRY(hipStreamSynchronize(driver->stream));
-        } catch (...) {
-            cozk_primary_group_free(g);
-            throw;
-        }
-        *out = g;
-    });
+    return primary_group_make(driver, members, k, keys, false, "primary_group_create", out);
+}
+
+int cozk_primary_group_create_king(cozk_ctx* driver, cozk_primary* const* members, int k, cozk_primary_group** out) {
+    return primary_group_make(driver, members, k, nullptr, true, "primary_group_create_king", out);
 }
 
 size_t cozk_primary_group_len(const cozk_primary_group* g) { return g ? g->members[0]->n : 0; }
@@ -246,6 +305,7 @@ int cozk_primary_group_level(cozk_primary_group* g, int level, uint64_t counter,
     cozk_ctx* const ctx = g->driver;
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(n_elems, "primary_group_level: null argument");
+        COZK_REQUIRE(!g->keyless, "primary_group_level: the group has no PRF keys (cozk_primary_group_create_king): cozk_primary_group_level_king");
         primary_group_check(ctx, g->members.data(), g->k, "primary_group_level", true);
         const cozk_primary* m0 = g->members[0];
         COZK_REQUIRE(level >= 1 && level <= m0->max_levels && m0->n_items, "primary_group_level: bad level / no items");
@@ -254,13 +314,7 @@ int cozk_primary_group_level(cozk_primary_group* g, int level, uint64_t counter,
         if (!n_el) return;  // nothing at this level: no launch, and the caller's counter stays
         const size_t k = (size_t)g->k, need = k * k * n_el;
         for (cozk_primary* p : g->members) COZK_REQUIRE(p->P[level - 1][0] && p->P_cap[level - 1] >= n_el, "primary_group_level: a member has no level buffer");
-        if (need > g->stage_cap) {
-            ctx_dev_free(ctx, g->stage);
-            g->stage = nullptr;
-            g->stage_cap = 0;
-            g->stage = (fe*)ctx_dev_alloc(ctx, need * sizeof(fe));
-            g->stage_cap = need;
-        }
+        primary_group_stage(g, need);
         primary_group_wait_members(g);
         const PrimGroupArgs a = primary_group_args(g);
         const size_t cap = m0->cap[m0->cur];
@@ -283,6 +337,50 @@ int cozk_primary_group_level(cozk_primary_group* g, int level, uint64_t counter,
         }
         k_primary_group_combine<<<dim3(grid_for(n_el), (unsigned)k), PT, 0, ctx->stream>>>(ca, g->stage, n_el);
         HIP_TRY(hipGetLastError());
+        stream_drain_by_flag(ctx);  // the members' own streams may go on
+    });
+}
+
+size_t cozk_primary_group_staging_bytes(const cozk_primary_group* g) { return g ? g->stage_cap * sizeof(fe) : 0; }
+
+int cozk_primary_group_level_king(cozk_primary_group* g, int level, const cozk_vec* const* r_t, const cozk_vec* const* r_2t, size_t r_offset,
+                                  size_t* n_elems) {
+    if (!g) return COZK_ERR_INVALID_ARG;
+    cozk_ctx* const ctx = g->driver;
+    return cozk_guard(ctx, [&] {
+        COZK_REQUIRE(n_elems && r_t && r_2t, "primary_group_level_king: null argument");
+        const size_t k = (size_t)g->k;
+        for (size_t i = 0; i < k; i++)
+            for (const cozk_vec* v : {r_t[i], r_2t[i]})
+                COZK_REQUIRE(v && v->kind == COZK_SCALAR_FR && v->ctx && v->ctx->device == ctx->device,
+                             "primary_group_level_king: 2 (2t + 1) FR halves of the pair on the driver's device");
+        primary_group_check(ctx, g->members.data(), g->k, "primary_group_level_king", true);
+        const cozk_primary* m0 = g->members[0];
+        COZK_REQUIRE(level >= 1 && level <= m0->max_levels && m0->n_items, "primary_group_level_king: bad level / no items");
+        const size_t n_el = m0->level_elems[level - 1];
+        for (size_t i = 0; i < k; i++)
+            for (const cozk_vec* v : {r_t[i], r_2t[i]})
+                COZK_REQUIRE(r_offset <= v->n && n_el <= v->n - r_offset, "primary_group_level_king: r_offset + n_elems <= len of every half of the pair");
+        *n_elems = n_el;
+        if (!n_el) return;  // nothing at this level: no launch, and no element of the pair is used
+        for (cozk_primary* p : g->members) COZK_REQUIRE(p->P[level - 1][0] && p->P_cap[level - 1] >= n_el, "primary_group_level_king: a member has no level buffer");
+        primary_group_stage(g, k * n_el);
+        primary_group_wait_members(g);
+        const PrimGroupArgs a = primary_group_args(g);
+        PrimGroupMaskArgs ra;
+        memset(&ra, 0, sizeof ra);
+        const fe *mp[PRIM_GROUP_MAX], *rt[PRIM_GROUP_MAX];
+        fe* o[PRIM_GROUP_MAX];
+        for (size_t i = 0; i < k; i++) {
+            ra.r2t[i] = (const fe*)r_2t[i]->d + r_offset;
+            mp[i] = g->stage + i * n_el;
+            rt[i] = (const fe*)r_t[i]->d;
+            o[i] = g->members[i]->P[level - 1][0];
+        }
+        const dim3 gd(grid_for(m0->n_items), (unsigned)m0->degree, (unsigned)k);
+        k_primary_group_mask<<<gd, PT, 0, ctx->stream>>>(a, ra, m0->cap[m0->cur], m0->n_instr, m0->n_mem, m0->degree, m0->n_items, level, g->stage, n_el);
+        HIP_TRY(hipGetLastError());
+        shamir_launch_king_finish(ctx->stream, mp, (int)k, rt, r_offset, (int)k, o, n_el);
         stream_drain_by_flag(ctx);  // the members' own streams may go on
     });
 }

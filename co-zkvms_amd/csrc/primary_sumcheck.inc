@@ -31,7 +31,7 @@
 
 static constexpr int PRIM_MAX_MEMS = COZK_PRIMARY_MAX_MEMS;
 static constexpr int PRIM_MAX_DEG = 8;
-static constexpr int PRIM_MAX_LEVELS = 4;
+static constexpr int PRIM_MAX_LEVELS = COZK_PRIMARY_MAX_LEVELS;
 static constexpr int PRIM_MAX_SLOTS = 12;
 static constexpr int PRIM_MAX_PROD = 4;
 static constexpr int PRIM_MAX_FINAL = 8;
@@ -630,6 +630,51 @@ __global__ void __launch_bounds__(PT) k_primary_final(const fe* __restrict__ st,
     if (threadIdx.x == 0) fe_store(partial + (size_t)(D + k) * gridDim.x + blockIdx.x, v);
 }
 
+// The instruction table compiled: the programs, which instructions are linear / multiplicative, the sumcheck degree and the deepest
+// program.  The one copy behind cozk_primary_create and cozk_primary_plan (n_mem == 0: the plan has no memories to check against).
+struct PrimTable {
+    std::vector<PrimInstrDev> instrs;
+    std::vector<int> lin, mul;
+    int degree = 0, max_levels = 0;
+};
+static PrimTable prim_compile_table(const cozk_primary_instr* instrs, size_t n_instr, size_t n_mem, int party_id, bool rep3, const std::string& who) {
+    PrimTable tb;
+    int gdeg = 1;
+    for (size_t i = 0; i < n_instr; i++) {
+        const cozk_primary_instr& si = instrs[i];
+        COZK_REQUIRE(si.form >= 0 && si.form <= COZK_G_ZERO && si.n_mems >= 1 && si.n_mems <= PRIM_MAX_MEMS, who + ": instruction form / memory count");
+        for (int t = 0; t < si.n_mems; t++) COZK_REQUIRE(si.mems[t] >= 0 && (!n_mem || (size_t)si.mems[t] < n_mem), who + ": memory index out of range");
+        PrimInstrDev d;
+        prim_compile(si, party_id, rep3, d);
+        if (d.linear) tb.lin.push_back((int)i);
+        else tb.mul.push_back((int)i);
+        if (d.g_degree > gdeg) gdeg = d.g_degree;
+        if (d.n_levels > tb.max_levels) tb.max_levels = d.n_levels;
+        tb.instrs.push_back(d);
+    }
+    COZK_REQUIRE(tb.mul.size() <= (size_t)PRIM_MAX_MUL, who + ": at most 32 multiplicative instructions");
+    tb.degree = gdeg + 2;  // sumcheck_poly_degree (worker.rs:701-708)
+    COZK_REQUIRE(tb.degree <= PRIM_MAX_DEG, who + ": degree too high");
+    return tb;
+}
+
+// Item counts -> level sizes: first[q] .. first[n_mul] are the first items of the instruction groups and the total; level t holds, group
+// after group, items x nq[t] x D elements.  hb (may be NULL) receives the groups' element offsets [t * PRIM_MAX_MUL + q].  The one copy
+// behind cozk_primary_round_begin and cozk_primary_plan.
+static void prim_level_layout(const std::vector<PrimInstrDev>& instrs, const std::vector<int>& mul, int max_levels, int D, const uint32_t* first,
+                              uint32_t* hb, size_t level_elems[PRIM_MAX_LEVELS], const std::string& who) {
+    for (int t = 0; t < PRIM_MAX_LEVELS; t++) level_elems[t] = 0;
+    for (int t = 0; t < max_levels; t++) {
+        uint64_t run = 0;
+        for (size_t q = 0; q < mul.size(); q++) {
+            if (hb) hb[t * PRIM_MAX_MUL + q] = (uint32_t)run;
+            run += (uint64_t)(first[q + 1] - first[q]) * (uint64_t)instrs[(size_t)mul[q]].nq[t] * (uint64_t)D;
+        }
+        COZK_REQUIRE(run < (1ull << 32), who + ": level buffer exceeds 2^32 elements");
+        level_elems[t] = (size_t)run;
+    }
+}
+
 extern "C" {
 
 int cozk_primary_create(cozk_ctx* ctx, int mode, int party_id, const cozk_primary_instr* instrs, size_t n_instr, const cozk_vec* const* flags,
@@ -661,23 +706,14 @@ int cozk_primary_create(cozk_ctx* ctx, int mode, int party_id, const cozk_primar
         p->n0 = p->n = n;
         const int NC = mode == COZK_MODE_REP3 ? 2 : 1;
         p->T = (int)n_instr + NC * (int)n_mem + NC + 1;
-        int gdeg = 1;
-        p->max_levels = 0;
-        for (size_t i = 0; i < n_instr; i++) {
-            const cozk_primary_instr& si = instrs[i];
-            COZK_REQUIRE(si.form >= 0 && si.form <= COZK_G_ZERO && si.n_mems >= 1 && si.n_mems <= PRIM_MAX_MEMS, "primary_create: instruction form / memory count");
-            for (int t = 0; t < si.n_mems; t++) COZK_REQUIRE(si.mems[t] >= 0 && (size_t)si.mems[t] < n_mem, "primary_create: memory index out of range");
-            PrimInstrDev d;
-            prim_compile(si, party_id, mode == COZK_MODE_REP3, d);
-            if (d.linear) p->lin.push_back((int)i);
-            else p->mul.push_back((int)i);
-            if (d.g_degree > gdeg) gdeg = d.g_degree;
-            if (d.n_levels > p->max_levels) p->max_levels = d.n_levels;
-            p->instrs.push_back(d);
+        {
+            PrimTable tb = prim_compile_table(instrs, n_instr, n_mem, party_id, mode == COZK_MODE_REP3, "primary_create");
+            p->instrs = std::move(tb.instrs);
+            p->lin = std::move(tb.lin);
+            p->mul = std::move(tb.mul);
+            p->degree = tb.degree;
+            p->max_levels = tb.max_levels;
         }
-        COZK_REQUIRE(p->mul.size() <= (size_t)PRIM_MAX_MUL, "primary_create: at most 32 multiplicative instructions");
-        p->degree = gdeg + 2;  // sumcheck_poly_degree (worker.rs:701-708)
-        COZK_REQUIRE(p->degree <= PRIM_MAX_DEG, "primary_create: degree too high");
         for (int w = 0; w < 2; w++) {
             p->cap[w] = w == 0 ? n : n / 2;
             p->store[w] = dev_alloc_fe((size_t)p->T * p->cap[w]);
@@ -773,6 +809,53 @@ int cozk_primary_free(cozk_primary* p) {
 
 int cozk_primary_degree(const cozk_primary* p) { return p ? p->degree : 0; }
 size_t cozk_primary_len(const cozk_primary* p) { return p ? p->n : 0; }
+size_t cozk_primary_level_elems(const cozk_primary* p, int level) {
+    return p && level >= 1 && level <= p->max_levels && p->n_items ? p->level_elems[level - 1] : 0;
+}
+
+// The public exchange plan: n_elems[PRIM_MAX_LEVELS * r + level - 1] of every round from the flag columns alone.  Instruction i is live
+// at index j of round r iff one of the 2^(r + 1) cycles below j carries its flag (a bound flag is non-zero iff one of its pair was,
+// up to a negligible probability): an OR pyramid over round 0's live masks, on the host -- the plan is made once, offline, over
+// n_instr bytes per cycle.
+int cozk_primary_plan(cozk_ctx* ctx, const cozk_primary_instr* instrs, size_t n_instr, const cozk_vec* const* flags, int log_n, uint64_t* n_elems_out,
+                      uint64_t* total_out) {
+    return cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && instrs && n_instr > 0 && n_instr <= 64 && flags && n_elems_out && total_out, "primary_plan: bad argument");
+        COZK_REQUIRE(log_n >= 1 && log_n <= 30, "primary_plan: log_n out of range (1..30)");
+        const size_t n = (size_t)1 << log_n;
+        for (size_t i = 0; i < n_instr; i++)
+            COZK_REQUIRE(flags[i] && flags[i]->kind == COZK_SCALAR_U8 && flags[i]->n == n, "primary_plan: every flag column is a U8 vector of 2^log_n entries");
+        const PrimTable tb = prim_compile_table(instrs, n_instr, 0, 0, false, "primary_plan");
+        std::vector<uint64_t> live(n / 2, 0);
+        {
+            std::vector<uint8_t> col(n);
+            for (size_t i = 0; i < n_instr; i++) {
+                HIP_TRY(hipMemcpyAsync(col.data(), flags[i]->d, n, hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(hipStreamSynchronize(ctx->stream));
+                for (size_t j = 0; j < n / 2; j++) live[j] |= (uint64_t)((col[2 * j] | col[2 * j + 1]) != 0) << i;
+            }
+        }
+        uint64_t total = 0;
+        size_t half = n / 2;
+        for (int r = 0; r < log_n; r++) {
+            if (r) {
+                half /= 2;
+                for (size_t j = 0; j < half; j++) live[j] = live[2 * j] | live[2 * j + 1];
+            }
+            uint32_t cnt[64] = {0}, first[PRIM_MAX_MUL + 1] = {0};
+            for (size_t j = 0; j < half; j++)
+                for (uint64_t m = live[j]; m; m &= m - 1) cnt[__builtin_ctzll(m)]++;
+            for (size_t s = 0; s < tb.mul.size(); s++) first[s + 1] = first[s] + cnt[tb.mul[s]];
+            size_t le[PRIM_MAX_LEVELS];
+            prim_level_layout(tb.instrs, tb.mul, tb.max_levels, tb.degree, first, nullptr, le, "primary_plan");
+            for (int t = 0; t < PRIM_MAX_LEVELS; t++) {
+                n_elems_out[(size_t)PRIM_MAX_LEVELS * r + t] = le[t];
+                total += le[t];
+            }
+        }
+        *total_out = total;
+    });
+}
 
 // first half of a round: bind everything with the previous challenge (NULL in the first round), the streaming pass over the
 // linear instructions, and the item list of the multiplicative ones.  n_items x degree products per level follow.
@@ -853,14 +936,8 @@ int cozk_primary_round_begin(cozk_ctx* ctx, cozk_primary* p, const uint64_t* r, 
                 HIP_TRY(hipGetLastError());
                 // where every instruction group's reshared values live in the level buffers
                 uint32_t hb[(PRIM_MAX_LEVELS + 1) * PRIM_MAX_MUL] = {0};
+                prim_level_layout(p->instrs, p->mul, p->max_levels, D, first, hb, p->level_elems, "primary_round_begin");
                 for (int t = 0; t < p->max_levels; t++) {
-                    uint64_t run = 0;
-                    for (size_t q = 0; q < n_mul; q++) {
-                        hb[t * PRIM_MAX_MUL + q] = (uint32_t)run;
-                        run += (uint64_t)(first[q + 1] - first[q]) * (uint64_t)p->instrs[p->mul[q]].nq[t] * (uint64_t)D;
-                    }
-                    COZK_REQUIRE(run < (1ull << 32), "primary_round_begin: level buffer exceeds 2^32 elements");
-                    p->level_elems[t] = (size_t)run;
                     if (p->level_elems[t] > p->P_cap[t]) {
                         for (int c = 0; c < NC; c++) {
                             ctx_dev_free(ctx, p->P[t][c]);

@@ -966,6 +966,12 @@ static void launch_king_finish(hipStream_t st, const fe* const* m, int k, const 
     HIP_TRY(hipGetLastError());
 }
 
+// the same launch for poly.hip's translation unit (cozk_primary_group_level_king, primary_group.inc): m = rows of its staging block, out =
+// the members' level buffers
+void shamir_launch_king_finish(hipStream_t st, const fe* const* m, int k, const fe* const* rt, size_t off, int count, fe* const* out, size_t n) {
+    launch_king_finish(st, m, k, rt, off, count, out, nullptr, n);
+}
+
 // off + len <= have without overflow
 static bool slice_fits(size_t off, size_t len, size_t have) { return off <= have && len <= have - off; }
 

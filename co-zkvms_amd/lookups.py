@@ -244,6 +244,10 @@ class PrimarySumcheck:
                                                   ctypes.byref(recv), ctypes.byref(n)))
         return send.value, recv.value, n.value
 
+    def level_elems(self, level):
+        """what `level` will report as n_elems in the current round (0: the level holds nothing)"""
+        return L.lib().cozk_primary_level_elems(self.h, level)
+
     def round_finish(self):
         """this party's additive evaluations at X = 0, 2, 3, .., degree"""
         d = self.degree()
@@ -279,6 +283,22 @@ class PrimarySumcheck:
 PRIMARY_GROUP_SYMBOLS = ["cozk_primary_group_create", "cozk_primary_group_level", "cozk_primary_group_round_finish", "cozk_primary_group_len",
                          "cozk_primary_group_level_buffer", "cozk_primary_group_free"]
 PRIMARY_GROUP_MAX = 15
+# the king level exchange and the public exchange plan (beside the lists above, whose lengths tests pin)
+PRIMARY_KING_SYMBOLS = ["cozk_primary_group_create_king", "cozk_primary_group_level_king", "cozk_primary_group_staging_bytes",
+                        "cozk_primary_level_elems", "cozk_primary_plan"]
+PRIMARY_MAX_LEVELS = 4
+
+
+def primary_plan(ctx, instrs, flags, log_n):
+    """the public exchange plan (`cozk_primary_plan`): from the instruction table and the U8 flag columns alone, the n_elems every
+    level of every round will exchange -> (rows[round][level - 1], total)"""
+    l = L.lib()
+    rows = (PrimaryInstr * max(len(instrs), 1))(*instrs)
+    fl = (_vp * max(len(flags), 1))(*[None if v is None else v.h for v in flags])
+    out = np.zeros((max(log_n, 1), PRIMARY_MAX_LEVELS), dtype=np.uint64)
+    total = ctypes.c_uint64()
+    ctx.check(l.cozk_primary_plan(ctx.h, rows, len(instrs), fl, log_n, out.ctypes.data, ctypes.byref(total)))
+    return [[int(x) for x in row] for row in out[:log_n]], int(total.value)
 
 
 class PrimaryGroup:
@@ -288,15 +308,33 @@ class PrimaryGroup:
     belong to other contexts on the same device; the group refers to them and they must outlive it."""
 
     def __init__(self, ctx, members, keys):
+        """keys = None: a group without PRF keys (`cozk_primary_group_create_king`): king levels only"""
         self._l = L.lib()
         self.ctx = ctx
         self.members = list(members)
         self.k = len(self.members)
         arr = (_vp * max(1, self.k))(*[None if m is None else m.h for m in self.members])
-        blob = b"".join(bytes(k) for ks in keys for k in ks)
         h = _vp()
-        ctx.check(self._l.cozk_primary_group_create(ctx.h, arr, self.k, blob, ctypes.byref(h)))
+        if keys is None:
+            ctx.check(self._l.cozk_primary_group_create_king(ctx.h, arr, self.k, ctypes.byref(h)))
+        else:
+            blob = b"".join(bytes(k) for ks in keys for k in ks)
+            ctx.check(self._l.cozk_primary_group_create(ctx.h, arr, self.k, blob, ctypes.byref(h)))
         self.h = h
+
+    def level_king(self, level, r_t, r_2t, r_offset=0):
+        """the king form of `level` on a preprocessed double-random pair: r_t[q] / r_2t[m] = member q's degree-t and member m's
+        degree-2t half (FR Vecs on the driver's device, None allowed only to provoke the refusal); pair element r_offset + pos serves
+        position pos once -> n_elems"""
+        n = _sz()
+        rt = (_vp * max(1, len(r_t)))(*[None if v is None else v.h for v in r_t])
+        r2t = (_vp * max(1, len(r_2t)))(*[None if v is None else v.h for v in r_2t])
+        self.ctx.check(self._l.cozk_primary_group_level_king(self.h, level, rt, r2t, r_offset, ctypes.byref(n)))
+        return n.value
+
+    def staging_bytes(self):
+        """the staging block's current size in bytes"""
+        return self._l.cozk_primary_group_staging_bytes(self.h)
 
     def __len__(self):
         return self._l.cozk_primary_group_len(self.h)

@@ -4,8 +4,9 @@ of the collation programs the 2t + 1 senders reduce the degree (`cozk_primary_gr
 prover's, byte for byte (LookupsHarness(mode="plain", primary=True) up to proof_len, oracle/pyprimary.py)."""
 import ctypes
 
+from ._lib import CozkError
 from .engine import SHAMIR_MAX_PARTIES as MAX_PARTIES, ShamirHarnessHandle
-from .lookups import PrimaryGroup, PRIMARY_GROUP_SYMBOLS  # noqa: F401  (the group the prover's levels run as)
+from .lookups import PrimaryGroup, PRIMARY_GROUP_SYMBOLS, PRIMARY_KING_SYMBOLS, primary_plan  # noqa: F401  (the group the prover's levels run as)
 
 
 class ShamirPrimaryConfig(ctypes.Structure):
@@ -24,6 +25,16 @@ class ShamirPrimaryResult(ctypes.Structure):
 SHAMIR_PRIMARY_SYMBOLS = ["cozk_shamir_primary_create", "cozk_shamir_primary_error", "cozk_shamir_primary_destroy", "cozk_shamir_primary_prove",
                           "cozk_shamir_primary_proof_bytes", "cozk_shamir_primary_msgs_len", "cozk_shamir_primary_msgs",
                           "cozk_shamir_primary_finals_len", "cozk_shamir_primary_finals", "cozk_shamir_primary_get_stats"]
+
+
+class ShamirPrimaryPrepResult(ctypes.Structure):
+    """cozk_shamir_primary_prep_result"""
+    _fields_ = [("n_openings", ctypes.c_uint64), ("pair_elems", ctypes.c_uint64), ("n_exchanges", ctypes.c_uint64), ("used", ctypes.c_int),
+                ("t_offline_ms", ctypes.c_double)]
+
+
+# the king construct's entry points (beside SHAMIR_PRIMARY_SYMBOLS, whose length tests pin)
+SHAMIR_PRIMARY_KING_SYMBOLS = ["cozk_shamir_primary_prep", "cozk_shamir_primary_prep_get_result", "cozk_shamir_primary_prove_king"]
 
 
 class ShamirPrimary(ShamirHarnessHandle):
@@ -47,3 +58,35 @@ class ShamirPrimary(ShamirHarnessHandle):
         cfg.rand_counter = rand_counter
         cfg.tamper_final = tamper_final
         self._open(cfg)
+
+    @classmethod
+    def _decl(cls):
+        l = super()._decl()
+        vp, i = ctypes.c_void_p, ctypes.c_int
+        for name, args in (("cozk_shamir_primary_prep", [vp, ctypes.POINTER(ShamirPrimaryPrepResult)]),
+                           ("cozk_shamir_primary_prep_get_result", [vp, ctypes.POINTER(ShamirPrimaryPrepResult)]),
+                           ("cozk_shamir_primary_prove_king", [vp, i, i, ctypes.POINTER(ShamirPrimaryResult)])):
+            fn = getattr(l, name)
+            fn.restype = i
+            fn.argtypes = args
+        return l
+
+    def _king_call(self, name, *args):
+        res = args[-1]
+        rc = getattr(self._l, name)(self.h, *args[:-1], ctypes.byref(res))
+        if rc != 0:
+            raise CozkError(rc, self.last_error() or "?")
+        return res
+
+    def prep(self):
+        """the preprocessing of ONE king prove (`cozk_shamir_primary_prep`): the exchange plan from the public flags, the opening masks
+        and the exchanges' double-random pair -> ShamirPrimaryPrepResult.  Once per handle"""
+        return self._king_call("cozk_shamir_primary_prep", ShamirPrimaryPrepResult())
+
+    def prep_result(self):
+        return self._king_call("cozk_shamir_primary_prep_get_result", ShamirPrimaryPrepResult())
+
+    def prove_king(self, king=0, verify=True):
+        """prove with the king level exchange on the prep's pair (`cozk_shamir_primary_prove_king`); consumes the prep.  The proof is
+        prove()'s, byte for byte"""
+        return self._king_call("cozk_shamir_primary_prove_king", king, 1 if verify else 0, ShamirPrimaryResult())

@@ -971,6 +971,20 @@ int cozk_primary_create(cozk_ctx* ctx, int mode, int party_id, const cozk_primar
 int cozk_primary_free(cozk_primary* p);
 int cozk_primary_degree(const cozk_primary* p); /* sumcheck_poly_degree (worker.rs:701-708): max g degree + 2 */
 size_t cozk_primary_len(const cozk_primary* p);
+/* what cozk_primary_level of `level` will report as n_elems in the current round; 0 when the level holds nothing, without items, for a
+ * level outside 1 .. n_levels or a NULL handle.  Host only. */
+size_t cozk_primary_level_elems(const cozk_primary* p, int level);
+/* The public exchange plan.  Which (index, instruction) items are live in a round depends on the public flags alone: an instruction is
+ * live at index j of round r iff one of the 2^(r + 1) cycles below j carries its flag (a bound flag is non-zero iff one of its pair
+ * was, up to a negligible probability) -- an OR pyramid over the per-index live masks cozk_primary_round_begin forms for round 0.  So
+ * the n_elems that cozk_primary_level / cozk_primary_group_level report can be computed before any share exists:
+ * n_elems_out[COZK_PRIMARY_MAX_LEVELS r + level - 1] for every round r < log_n, zero where a level holds nothing, and *total_out, their
+ * sum.  instrs, n_instr and flags (U8 columns of 2^log_n entries on ctx's device) are cozk_primary_create's; no E, lookup_outputs or eq
+ * is read and no cozk_primary is made.  The columns are downloaded and the pyramid runs on the host (offline work: n_instr bytes per
+ * cycle); item counts become level sizes through round_begin's own formula. */
+#define COZK_PRIMARY_MAX_LEVELS 4
+int cozk_primary_plan(cozk_ctx* ctx, const cozk_primary_instr* instrs, size_t n_instr, const cozk_vec* const* flags, int log_n,
+                      uint64_t* n_elems_out /* log_n x COZK_PRIMARY_MAX_LEVELS */, uint64_t* total_out);
 /* one round = primary_sumcheck_prover_message (worker.rs:454-598), in three steps:
  * round_begin: bind with the previous challenge r (NULL in the first round), the pass over the linear instructions, the
  *   item list of the multiplicative ones (*n_items; *n_levels mul_vec levels follow, 0 if there are no items);
@@ -1024,9 +1038,25 @@ int cozk_primary_final_evals(cozk_ctx* ctx, cozk_primary* p, const uint64_t r[4]
  * range, a member that is not PLAIN, a duplicate member, a member on another device, members whose table, degree, n_mem or length
  * differ (create and every call), members whose item counts or level sizes differ (every call), a level outside 1 .. n_levels or a
  * level call without items.
- * Not built: a king / double-random variant of the level exchange (its pair length would depend on the public item counts), groups
- * over several GPUs, one public item list shared by the members.
- * Parity unpinned (the reference has no Shamir prover); restated in tests/shamir_primary_ref.py. */
+ * The KING level (Damgard-Nielsen on a preprocessed double-random pair, as cozk_shamir_mul_king_pairs_inproc):
+ *   create_king   a group WITHOUT PRF keys; member rules, refusals and stream rules are create's.  cozk_primary_group_level on such a
+ *                 group is refused on the host.
+ *   level_king    on either kind of group.  r_t[q] / r_2t[m], q, m < k: member q's degree-t half and member m's degree-2t half of the
+ *                 pair, FR vectors on the driver's device (they may belong to other contexts there; they are read on the driver's
+ *                 stream and ordering that read behind their writers is the caller's job).  TWO launches whatever k is:
+ *                 k_primary_group_mask (level's grid; staging[m][pos] = z_m[pos] + r_2t[m][r_offset + pos], z never stored) and the
+ *                 king's finish (k_shamir_king_finish, the launch of cozk_shamir_king_finish: zed[pos] = sum_m lambda_m
+ *                 staging[m][pos], member q's level buffer[pos] = zed[pos] - r_t[q][r_offset + pos], canonical; 2k x 32 B read and
+ *                 k x 32 B written per element).  Pair element r_offset + pos serves position pos ONCE: no element of a pair may be
+ *                 used twice, so the next exchange's offset is r_offset + n_elems.  r_offset + n_elems <= len for all 2k halves is
+ *                 checked on the host before any launch; with n_elems == 0 nothing is launched; the call returns with the driver's
+ *                 stream drained.  No PRF runs: everything random was made offline.
+ *   staging_bytes the staging block's current size: it grows on demand and after a king level of n_elems it is k x n_elems x 32
+ *                 bytes, not k^2 x n_elems x 32 (192 MB instead of 961 MB for the largest level at 2^18 cycles, t = 2, uniform mix).
+ * level_king adds to the refusals above: a null half, a half that is not an FR vector of the driver's device, halves too short for
+ * r_offset + n_elems.  Every refusal leaves the members untouched.
+ * Not built: groups over several GPUs, one public item list shared by the members.
+ * Parity unpinned (the reference has no Shamir prover); restated in tests/shamir_primary_ref.py and tests/shamir_primary_king_ref.py. */
 #define COZK_PRIMARY_GROUP_MAX 15 /* 2t + 1 with 2t <= COZK_SHAMIR_MAX_DEGREE */
 typedef struct cozk_primary_group cozk_primary_group;
 int cozk_primary_group_create(cozk_ctx* driver, cozk_primary* const* members, int k, const uint8_t* keys /* k x t x 32 */,
@@ -1036,6 +1066,10 @@ int cozk_primary_group_round_finish(cozk_primary_group* g, uint64_t* out /* k x 
 size_t cozk_primary_group_len(const cozk_primary_group* g);
 int cozk_primary_group_level_buffer(const cozk_primary_group* g, int member, int level, const void** buf, size_t* n_elems);
 int cozk_primary_group_free(cozk_primary_group* g);
+int cozk_primary_group_create_king(cozk_ctx* driver, cozk_primary* const* members, int k, cozk_primary_group** out);
+int cozk_primary_group_level_king(cozk_primary_group* g, int level, const cozk_vec* const* r_t, const cozk_vec* const* r_2t,
+                                  size_t r_offset, size_t* n_elems);
+size_t cozk_primary_group_staging_bytes(const cozk_primary_group* g);
 
 /* ---- co-jolt's Spartan outer sumcheck over Az / Bz / Cz (co-jolt/src/poly/spartan_interleaved_poly.rs,
  * co-jolt/src/r1cs/spartan/worker.rs:63-120,277-300):  sum_x eq(tau, x) (Az(x) Bz(x) - Cz(x)) = 0.
@@ -1568,9 +1602,28 @@ int cozk_shamir_jolt_spartan_get_stats(const cozk_shamir_jolt_spartan* h, cozk_s
  *   group_finals = single_finals = 0 either way: the final evaluations are read per opener (cozk_primary_final_evals).
  * Refused by create before any launch (the handle is returned with its error text): 1 <= t, 2t <= COZK_SHAMIR_MAX_DEGREE,
  * 2t + 1 <= n <= COZK_SHAMIR_MAX_PARTIES, 1 <= log_n <= 24, 1 <= n_mem <= 128 (what lookups_instr_table admits), mix 0 or 1.
- * Not built: a king / double-random variant of the level exchange (its pair length depends on the public item counts), one party per
- * process, groups over several GPUs, one item list shared by the senders, worker sub-nets (log_workers), the primary inside a chained
- * Shamir flow. */
+ * The KING construct of the exchange (cozk_shamir_primary_prep + cozk_shamir_primary_prove_king; tests/shamir_primary_king_ref.py):
+ * the sizes of all exchanges follow from the public flags (cozk_primary_plan), so everything that needs fresh randomness is made
+ * before the witness is touched, as for the grand product (cozk_shamir_gp_prep_inproc):
+ *   prep        on a created handle, once.  (A) the M = D log_n opening masks at rand_counter, pair 0: the masks prove deals.  (B) ONE
+ *               dealing (cozk_shamir_rand_inproc's rule) of total = the plan's sum elements at rand_counter + M, pair 0 only, of which
+ *               the degree-t and the degree-2t halves are extracted for parties 0..2t only: receivers are the senders.
+ *               (rand_keys, rand_counter .. rand_counter + M + total) must never be used again: the caller's contract; a second prep of
+ *               a handle is refused.  Result: n_openings = M, pair_elems = total, n_exchanges = X, used, t_offline_ms (host clock
+ *               around the plan and both dealings, every party's stream drained at both ends).
+ *   prove_king  consumes the prep: it is marked used before the first launch, a second king prove and a king prove without a prep are
+ *               refused with COZK_ERR_INVALID_ARG and a text, 0 <= king < n.  Exchange e uses the pair at the element offset = the
+ *               sum of the earlier exchanges' n_elems: sender m sends z_m + r_2t,m to the king, who opens zed = slot + r and sends it
+ *               to everyone; receiver q keeps zed - r_t,q.  Before a level launches anything its size is compared with the plan's and
+ *               a difference (a bound flag that happens to be zero) fails the prove with a text naming the round and the level.
+ *               Transcript, masks, openings, finals, verifier, tamper_final, every getter and the result are those of prove: THE PROOF
+ *               IS THE PLAIN PROVER'S, BYTE FOR BYTE; n_exchanged = pair_elems.  Grouped: one cozk_primary_group_level_king per exchange
+ *               on a keyless group (group_rounds = X + log_n).  Otherwise every sender runs cozk_primary_level and adds its r_2t slice
+ *               (cozk_vec_binop), the king's context runs cozk_shamir_king_finish at the offset for the senders of its device, each
+ *               result is copied into that sender's level buffer, and a sender on another device gets zed by peer copy and subtracts
+ *               its r_t slice on its own stream (single_rounds as above).  The same bytes either way.
+ * Not built: the other n - t - 1 pairs of the prep's dealing (B) (only pair 0 is extracted), one party per process, groups over several
+ * GPUs, one item list shared by the senders, worker sub-nets (log_workers), the primary inside a chained Shamir flow. */
 typedef struct cozk_shamir_primary cozk_shamir_primary;
 typedef struct cozk_shamir_primary_config {
     int log_n;  /* cycles = 2^log_n */
@@ -1607,6 +1660,17 @@ int cozk_shamir_primary_msgs(const cozk_shamir_primary* h, uint64_t* out, size_t
 size_t cozk_shamir_primary_finals_len(const cozk_shamir_primary* h);
 int cozk_shamir_primary_finals(const cozk_shamir_primary* h, uint64_t* out, size_t cap);
 int cozk_shamir_primary_get_stats(const cozk_shamir_primary* h, cozk_shamir_gp_stats* stats);
+typedef struct cozk_shamir_primary_prep_result {
+    uint64_t n_openings;  /* M */
+    uint64_t pair_elems;  /* total: the elements of the exchanges' pair */
+    uint64_t n_exchanges; /* X: the plan's exchanges with n_elems > 0 */
+    int used;             /* 1 once a king prove has started with it */
+    double t_offline_ms;
+} cozk_shamir_primary_prep_result;
+int cozk_shamir_primary_prep(cozk_shamir_primary* h, cozk_shamir_primary_prep_result* res);
+/* all zero before a prep */
+int cozk_shamir_primary_prep_get_result(const cozk_shamir_primary* h, cozk_shamir_primary_prep_result* res);
+int cozk_shamir_primary_prove_king(cozk_shamir_primary* h, int king, int verify, cozk_shamir_primary_result* res);
 
 /* ---- ONE chained co-jolt worker flow (JoltRep3Prover::prove, co-jolt/src/jolt/vm/jolt/worker.rs:175-266, against its coordinator
  * jolt/vm/jolt/coordinator.rs:118-222): commit-all -> bytecode memory checking -> instruction lookups (primary sumcheck, toggled

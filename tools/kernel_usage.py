@@ -4,7 +4,9 @@
 The group kernels of the Shamir provers (every one must report 0 bytes of scratch; DESIGN.md 4b quotes their lines):
   python tools/kernel_usage.py usage.txt 'k_(layer|toggle|spartan)_group'
   python tools/kernel_usage.py usage.txt 'k_(outer|shift)_group_(round|final)'
-  python tools/kernel_usage.py usage.txt 'k_primary_group_(deal|combine|final)'   (144 bytes of scratch, as k_primary_level<1> and k_primary_final<1>)"""
+  python tools/kernel_usage.py usage.txt 'k_primary_group_(deal|combine|final)'   (144 bytes of scratch, as k_primary_level<1> and k_primary_final<1>)
+  python tools/kernel_usage.py usage.txt 'k_primary_group_mask'                   (the king level: the same 144 bytes, none of its own; its
+                                                                                   finish is shamir.hip's k_shamir_king_finish: 0 bytes)"""
 import re, sys
 txt = open(sys.argv[1]).read()
 pat = sys.argv[2] if len(sys.argv) > 2 else "."

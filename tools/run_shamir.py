@@ -79,7 +79,18 @@ With --primary, instead, Lasso's primary sumcheck of 2^log_n cycles proved by th
           per-sender composition), alternating in this process, >= 10 repetitions each, proofs, messages and final shares compared; the
           ungrouped leg is the yardstick.  Also reported: the staging block's bytes, (2t + 1)^2 x the largest level's n_elems x 32.
 --only-group runs nothing but (xxvii):
-  python tools/run_shamir.py --primary --only-group --log-n 18 --mix uniform --parties 8 --degree 2 --out FILE"""
+  python tools/run_shamir.py --primary --only-group --log-n 18 --mix uniform --parties 8 --degree 2 --out FILE
+With --primary --king, instead, the KING level exchange of that prover on a preprocessed double-random pair (cozk_primary_plan,
+cozk_primary_group_level_king, cozk_shamir_primary_prep, cozk_shamir_primary_prove_king):
+  (xxviii) the first round's levels as cozk_primary_group_level_king calls on a keyless group against the composed king exchange
+           (cozk_primary_level, the r_2t slice added with cozk_vec_binop, one cozk_shamir_king_finish at the offset, the copies back),
+           outputs compared raw, and against the same levels as cozk_primary_group_level calls (the resharing group), alternating; the
+           staging block's bytes of both forms;
+  (xxix)   the whole king prove grouped against COZK_SHAMIR_GP_GROUP=0: proofs, messages and final shares compared;
+  (xxx)    the grouped king prove against the grouped resharing prove -- the yardstick --, alternating in this process, a fresh handle
+           and a fresh preprocessing per king repetition; online time and offline preprocessing time reported apart.
+--only-group runs nothing but (xxix) and (xxx):
+  python tools/run_shamir.py --primary --king --log-n 18 --mix uniform --parties 8 --degree 2 --out profiles/shamir_primary_king_2p18_n8_t2_uniform.json"""
 import argparse, ctypes, hashlib, importlib, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -92,7 +103,7 @@ ap.add_argument("--degree", type=int, default=2)
 ap.add_argument("--out", default=None)
 ap.add_argument("--min-seconds", type=float, default=1.0)
 ap.add_argument("--mul", action="store_true", help="time the multiplication with degree reduction instead")
-ap.add_argument("--king", action="store_true", help="with --mul: time the king / double-random variant against the resharing; with --gp: the king construct")
+ap.add_argument("--king", action="store_true", help="with --mul: time the king / double-random variant against the resharing; with --gp / --tgp / --primary: the king construct")
 ap.add_argument("--gp", action="store_true", help="time the Shamir grand product prover instead")
 ap.add_argument("--gp-batch", type=int, default=2, help="with --gp: circuits in the grand product")
 ap.add_argument("--only-group", action="store_true", help="with --gp: only the grouped against the ungrouped prove, resharing and king prover; with --tgp: only (xxi)")
@@ -1328,6 +1339,211 @@ def primary_legs():
     h.close()
     emit(res)
 
+
+def primary_king_legs():
+    """--primary --king: (xxviii) unless --only-group, then (xxix) and (xxx); one context per party on this GPU"""
+    if 2 * T + 1 > N or 2 * T > 15:
+        raise SystemExit("run_shamir --primary --king: needs 2 * degree + 1 <= parties and 2 * degree <= 15")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path[:0] = [os.path.join(root, "oracle"), os.path.join(root, "tests")]
+    senders = 2 * T + 1
+    res = {
+        "what": "Lasso's primary sumcheck by Shamir parties, the KING level exchange on a preprocessed double-random pair "
+                "(cozk_primary_group_level_king, cozk_shamir_primary_prep + cozk_shamir_primary_prove_king) against the resharing exchange "
+                "(cozk_primary_group_level, cozk_shamir_primary_prove), which is the yardstick",
+        "log_n": args.log_n, "cycles": n, "n_mem": args.mems, "mix": args.mix, "parties": N, "degree": T, "senders": senders, "openers": T + 1,
+        "seed": args.seed, "device": torch.cuda.get_device_name(0),
+    }
+    if not args.only_group:
+        import pylookups, primary_ref as PR
+        LK = importlib.import_module("co-zkvms_amd.lookups")
+        import pyref as O
+        instrs = pylookups.instr_table(args.mems)
+        which = [pylookups.mix_instr(1 if args.mix == "sha2" else 0, v) for v in O.synthetic_small(args.seed + 1234567, n, 8)]
+        pcs, streams = party_contexts()
+        pcs, streams = pcs[:senders], streams[:senders]
+        whole = lambda fn: whole_call(pcs, streams, fn)
+        rows = PR.rows(LK, instrs)
+        flag_cols = [np.array([1 if w == i else 0 for w in which], dtype=np.uint8) for i in range(len(instrs))]
+        flags = [[cozk.Vec.from_numpy(pcs[p], c, kind=cozk.SCALAR_U8) for c in flag_cols] for p in range(senders)]
+        E = [[cozk.Rep3DensePolynomial.random(pcs[p], n, 3000 + 100 * p + m, mode=cozk.MODE_PLAIN) for m in range(args.mems)] for p in range(senders)]
+        outs = [cozk.Rep3DensePolynomial.random(pcs[p], n, 2900 + p, mode=cozk.MODE_PLAIN) for p in range(senders)]
+        eqs = [cozk.eq_evals(pcs[p], [pow(5, 3 + i, cozk.FR_MOD) for i in range(args.log_n)]) for p in range(senders)]
+        keys = [[key(16 * p + c) for c in range(T)] for p in range(senders)]
+        plan, total = LK.primary_plan(pcs[0], rows, flags[0], args.log_n)
+        first = sum(plan[0])  # the first round's exchanges use the pair's first elements
+        rt = [cozk.Vec.random(pcs[p], first, seed=5100 + p) for p in range(senders)]
+        r2t = [cozk.Vec.random(pcs[p], first, seed=5200 + p) for p in range(senders)]
+
+        def mk():
+            prims = [LK.PrimarySumcheck.create(pcs[p], cozk.MODE_PLAIN, 0, rows, flags[p], E[p], outs[p], eqs[p]) for p in range(senders)]
+            begun = [pr.round_begin() for pr in prims]
+            assert all(b == begun[0] for b in begun)
+            return prims, begun[0][1]
+
+        def raw(p, ptr, cnt):
+            host = np.zeros((max(cnt, 1), 4), dtype=np.uint64)
+            PR._copy(cozk, pcs[p], host.ctypes.data, ptr, 32 * cnt)
+            return host[:cnt]
+
+        def run_group(king, keep=False):
+            """the first round's levels as ONE group: king levels on a keyless group, or the resharing levels"""
+            prims, n_levels = mk()
+            g = LK.PrimaryGroup(pcs[0], prims, None if king else keys)
+
+            def body():
+                off, el = 0, []
+                for level in range(1, n_levels + 1):
+                    el.append(g.level_king(level, rt, r2t, off) if king else g.level(level, off))
+                    off += el[-1]
+                return el
+            ms, el = whole(body)
+            bufs = [[raw(p, *g.level_buffer(p, lv)) for p in range(senders)] for lv in range(1, n_levels + 1) if el[lv - 1]] if keep else None
+            staging = g.staging_bytes()
+            g.free()
+            for pr in prims:
+                pr.free()
+            return ms, (el, bufs, staging)
+
+        def run_composed(keep=False):
+            """the king exchange from the existing calls: cozk_primary_level per sender, its r_2t slice added (cozk_vec_binop), ONE
+            cozk_shamir_king_finish at the offset on the king's context, each result copied into that sender's level buffer"""
+            prims, n_levels = mk()
+
+            def body():
+                off, el, ptrs = 0, [], []
+                for level in range(1, n_levels + 1):
+                    out = [pr.level(level) for pr in prims]
+                    cnt = out[0][2]
+                    el.append(cnt)
+                    if not cnt:
+                        continue
+                    masked = []
+                    for p in range(senders):
+                        v, s = cozk.Vec.alloc(pcs[p], cnt), cozk.Vec.alloc(pcs[p], cnt)
+                        PR._copy(cozk, pcs[p], v.device_ptr(), out[p][0], 32 * cnt)
+                        PR._copy(cozk, pcs[p], s.device_ptr(), r2t[p].device_ptr() + 32 * off, 32 * cnt)
+                        masked.append(v.binop(cozk.OP_ADD, s))
+                        v.free(), s.free()
+                        pcs[p].synchronize()
+                    fin = cozk.shamir_king_finish(pcs[0], masked, T, rt, r_offset=off)
+                    for q in range(senders):
+                        PR._copy(cozk, pcs[0], out[q][0], fin[q].device_ptr(), 32 * cnt)
+                    pcs[0].synchronize()
+                    free(masked), free(fin)
+                    ptrs.append([o[0] for o in out])
+                    off += cnt
+                return el, ptrs
+            ms, (el, ptrs) = whole(body)
+            bufs = [[raw(p, ptrs[i][p], cnt) for p in range(senders)] for i, cnt in enumerate(c for c in el if c)] if keep else None
+            for pr in prims:
+                pr.free()
+            return ms, (el, bufs)
+
+        keep = n <= (1 << 14)  # the level buffers are compared raw on the host: small sizes only
+        ok, oc = run_group(True, keep)[1], run_composed(keep)[1]
+        assert ok[0] == oc[0] == plan[0][:len(ok[0])], "the first round's exchanges differ from the plan"
+        if keep:
+            assert all(np.array_equal(a, b) for la, lb in zip(ok[1], oc[1]) for a, b in zip(la, lb)), "the level buffers differ"
+        run_group(False)
+        t_k, t_c, t_r = [], [], []
+        staging = {}
+        while sum(t_k) < args.min_seconds * 1e3 or sum(t_r) < args.min_seconds * 1e3 or len(t_k) < 6:
+            ms, (_, _, staging["king"]) = run_group(True)
+            t_k.append(ms)
+            ms, (_, _, staging["resharing"]) = run_group(False)
+            t_r.append(ms)
+            t_c.append(run_composed()[0])
+        res["first_round"] = {"king_levels_one_group": stats(t_k), "resharing_levels_one_group_same_run": stats(t_r),
+                              "king_composed_per_sender_same_run": stats(t_c),
+                              "king_vs_resharing_group_speedup": round(med(t_r) / med(t_k), 3),
+                              "king_group_vs_composed_speedup": round(med(t_c) / med(t_k), 3), "n_elems_per_level": ok[0],
+                              "staging_block_bytes": staging, "level_buffers_compared": bool(keep),
+                              "note": "levels only (no round finish); random halves stand in for the preprocessed pair; the composition "
+                                      "copies every level buffer and every slice of a half into a vector before it adds them"}
+        free(rt), free(r2t)
+        flags = E = outs = eqs = None
+        for pc in pcs:
+            pc.close()
+
+    mkh = lambda: cozk.ShamirPrimary(log_n=args.log_n, n_mem=args.mems, mix=args.mix, parties=N, degree=T, devices=0, seed=args.seed)
+    split = ("t_build_ms", "t_masks_ms", "t_rounds_ms", "t_finals_ms")
+
+    def king_prove(ungrouped=False, verify=False, king=0):
+        """a fresh handle and a fresh preprocessing per repetition, both outside the timed prove"""
+        hk = mkh()
+        pre = hk.prep()
+        if ungrouped:
+            os.environ[GROUP_SWITCH] = "0"  # read by the library on every prove
+        try:
+            r_ = hk.prove_king(king=king, verify=verify)
+            st = hk.stats()
+            got = (hk.proof_bytes(r_), hk.msgs(), hk.finals()) if verify else None
+            return r_, pre, {k: int(getattr(st, k)) for k in ("group_rounds", "single_rounds", "group_finals", "single_finals")}, got
+        finally:
+            os.environ.pop(GROUP_SWITCH, None)
+            hk.close()
+
+    h = mkh()  # the resharing prover: the code as it stands without the king construct
+    rr = h.prove(verify=True)
+    assert rr.verified == 1 and rr.grouped == 1, "the resharing proof was rejected: " + h.last_error()
+    digest = bytes(rr.proof_digest)
+    kg, pre, _, got_g = king_prove(verify=True, king=N - 1)
+    ku, _, _, got_u = king_prove(ungrouped=True, verify=True, king=0)
+    assert kg.verified == 1 and ku.verified == 1 and kg.grouped == 1 and ku.grouped == 0, "a king proof was rejected or the switch did not select the legs"
+    assert got_g == got_u, "the grouped and the ungrouped king prove differ in proof, messages or final shares"
+    assert bytes(kg.proof_digest) == digest and got_g[2] == h.finals(), "the king proof is not the resharing prover's"
+    assert kg.n_exchanged == pre.pair_elems == rr.n_exchanged
+    legs = {"king": [], "king_ungrouped": [], "resharing": []}
+    offline, calls = [], {}
+    enough = lambda k: sum(x.wall_ms for x in legs[k]) >= args.min_seconds * 1e3 and len(legs[k]) >= 6
+    while not (enough("king") and enough("resharing")):
+        r_, p_, calls["king"], _ = king_prove()
+        legs["king"].append(r_)
+        offline.append(p_.t_offline_ms)
+        r_ = h.prove(verify=False)
+        st = h.stats()
+        calls["resharing"] = {k: int(getattr(st, k)) for k in ("group_rounds", "single_rounds", "group_finals", "single_finals")}
+        legs["resharing"].append(r_)
+        if len(legs["king_ungrouped"]) < 3:
+            r_, _, calls["king_ungrouped"], _ = king_prove(ungrouped=True)
+            legs["king_ungrouped"].append(r_)
+        assert all(bytes(x[-1].proof_digest) == digest for x in legs.values()), "a repetition's proof differs"
+    rep = lambda rs, c: dict(stats([x.wall_ms for x in rs]), driver_split={k: stats([getattr(x, k) for x in rs]) for k in split}, calls=c)
+    w = {k: [x.wall_ms for x in v] for k, v in legs.items()}
+    rounds = {k: [x.t_rounds_ms for x in v] for k, v in legs.items()}
+    spread_r = max(w["resharing"]) - min(w["resharing"])
+    res["prover"] = {
+        "king_online_whole_prove_grouped": rep(legs["king"], calls["king"]),
+        "resharing_whole_prove_grouped_same_run": rep(legs["resharing"], calls["resharing"]),
+        "king_online_whole_prove_ungrouped_same_run": rep(legs["king_ungrouped"], calls["king_ungrouped"]),
+        "king_offline_prep": stats(offline),
+        "king_online_vs_resharing_speedup": round(med(w["resharing"]) / med(w["king"]), 3),
+        "rounds_king_vs_resharing_speedup": round(med(rounds["resharing"]) / med(rounds["king"]), 3),
+        "king_grouped_vs_ungrouped_speedup": round(med(w["king_ungrouped"]) / med(w["king"]), 3),
+        "king_online_slower_than_resharing_by_ms": round(med(w["king"]) - med(w["resharing"]), 4),
+        "resharing_min_max_spread_ms": round(spread_r, 4),
+        "king_online_not_slower_beyond_resharing_spread": bool(med(w["king"]) - med(w["resharing"]) <= spread_r),
+        "proofs_equal_finals_equal_grouped_ungrouped_equal": True,
+        "proof_sha256": digest.hex(),
+        "sumcheck_degree": int(rr.degree), "exchanges": int(rr.n_exchanges), "pair_elems": int(pre.pair_elems),
+        "online_elements_per_slot_value": {"king": 2, "resharing": senders * senders},
+    }
+    res["timing"] = ("whole prove: the driver's host clock from every party's stream drained to every party's stream drained (one thread drives the "
+                     "parties in turn: sums over parties), setup (instance, sharing) outside, eq and cozk_primary_create of every sender inside "
+                     "(t_build); the king prove's preprocessing is OFFLINE and reported on its own (plan + both dealings, host clock, every "
+                     "stream drained at both ends), a fresh handle and preprocessing per repetition; first round: from an event on party 0's "
+                     "idle stream to the last of the events behind the senders' streams, state and group creation and round_begin outside; "
+                     "the legs alternate in one process, the grouped resharing prove being the yardstick; the seed's keys and counters "
+                     "reused across repetitions (timing only)")
+    h.close()
+    emit(res)
+
+
+if args.primary and args.king:
+    primary_king_legs()
+    ctx.close()
+    raise SystemExit(0)
 
 if args.primary:
     primary_legs()
