@@ -235,6 +235,7 @@ SIGNATURES = {
     "cozk_spliteq_free": (_i, [_vp]),
     "cozk_spliteq_lens": (_i, [_vp, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
     "cozk_spliteq_bind": (_i, [_vp, _vp, _vp]),
+    "cozk_spliteq_download": (_i, [_vp, _vp, _vp, _vp]),
     "cozk_prof_enable": (_i, [_vp, _i]),
     "cozk_prof_read": (_i, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "cozk_prof_kernel_name": (ctypes.c_char_p, [_i]),

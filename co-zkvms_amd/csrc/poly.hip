@@ -2308,6 +2308,8 @@ int cozk_pst_fold(cozk_ctx* ctx, const cozk_vec* r, const uint64_t p[4], cozk_ve
         COZK_REQUIRE(ctx && r && p && q && r_next && r->kind == COZK_SCALAR_FR && r->n >= 2 && r->n % 2 == 0 &&
                          q->n >= r->n / 2 && r_next->n >= r->n / 2,
                      "pst_fold: bad argument");
+        // the kernel stores r->n / 2 field elements into each: an element count alone would let a U8 vector of that many BYTES through
+        COZK_REQUIRE(q->kind == COZK_SCALAR_FR && r_next->kind == COZK_SCALAR_FR, "pst_fold: q and r_next must be FR vectors");
         size_t h = r->n / 2;
         k_pst_fold<<<grid_for(h), PT, 0, ctx->stream>>>((const fe*)r->d, (fe*)q->d, (fe*)r_next->d, h, fe_from_u64x4(p));
         HIP_TRY(hipGetLastError());
@@ -2449,6 +2451,17 @@ int cozk_spliteq_lens(const cozk_spliteq* e, size_t* e1_len, size_t* e2_len) {
     if (e1_len) *e1_len = e->E1_len;
     if (e2_len) *e2_len = e->E2_len;
     return COZK_OK;
+}
+
+// current tables -> host (tests): E1_len x 4 u64 and E2_len x 4 u64; either pointer may be null
+int cozk_spliteq_download(cozk_ctx* ctx, const cozk_spliteq* e, uint64_t* e1, uint64_t* e2) {
+    return cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && e, "spliteq_download: bad argument");
+        COZK_REQUIRE(e->ctx == ctx, "spliteq_download: the eq polynomial belongs to another context");
+        if (e1) HIP_TRY(hipMemcpyAsync(e1, e->E1[e->c1], e->E1_len * sizeof(fe), hipMemcpyDeviceToHost, ctx->stream));
+        if (e2) HIP_TRY(hipMemcpyAsync(e2, e->E2[e->c2], e->E2_len * sizeof(fe), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    });
 }
 
 // SplitEqPolynomial::bind(r)
@@ -3032,6 +3045,10 @@ int cozk_rep3_mul_vec_local(cozk_ctx* ctx, int mode, const cozk_vec* xa, const c
         COZK_REQUIRE(ctx && xa && ya && out && xa->n == ya->n && (mode == COZK_MODE_PLAIN || (xb && yb && xb->n == xa->n && yb->n == xa->n)) &&
                          (!masked || (key_self_b && key_prev_b)),
                      "mul_vec_local: bad argument");
+        // the kernel reads xa->n field elements from each: a narrow vector of that many entries is shorter than that
+        COZK_REQUIRE(xa->kind == COZK_SCALAR_FR && ya->kind == COZK_SCALAR_FR &&
+                         (mode == COZK_MODE_PLAIN || (xb->kind == COZK_SCALAR_FR && yb->kind == COZK_SCALAR_FR)),
+                     "mul_vec_local: the share components must be FR vectors");
         prf_key seed_self{}, seed_prev{};
         if (masked) {
             seed_self = prf_key_from_bytes(key_self_b);

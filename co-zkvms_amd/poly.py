@@ -237,6 +237,15 @@ class SplitEqPolynomial:
         rr = _fr(r)
         self.ctx.check(self.ctx._l.cozk_spliteq_bind(self.ctx.h, self.h, rr.ctypes.data))
 
+    def download(self, ctx=None):
+        """the current tables (E1[:E1_len], E2[:E2_len]) as canonical ints (tests); `ctx`: the context to ask, this one's by default"""
+        ctx = ctx or self.ctx
+        n1, n2 = self.lens()
+        e1 = np.empty((n1, 4), dtype=np.uint64)
+        e2 = np.empty((n2, 4), dtype=np.uint64)
+        ctx.check(ctx._l.cozk_spliteq_download(ctx.h, self.h, e1.ctypes.data, e2.ctypes.data))
+        return mont_limbs_to_int(e1), mont_limbs_to_int(e2)
+
     def free(self):
         if self.h:
             self.ctx._l.cozk_spliteq_free(self.h)

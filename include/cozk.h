@@ -1155,6 +1155,8 @@ int cozk_spliteq_new(cozk_ctx* ctx, const uint64_t* w, int nv, cozk_spliteq** ou
 int cozk_spliteq_free(cozk_spliteq* e);
 int cozk_spliteq_lens(const cozk_spliteq* e, size_t* e1_len, size_t* e2_len);
 int cozk_spliteq_bind(cozk_ctx* ctx, cozk_spliteq* e, const uint64_t r[4]);
+/* current tables -> host (tests): E1_len x 4 u64 and E2_len x 4 u64; either pointer may be NULL */
+int cozk_spliteq_download(cozk_ctx* ctx, const cozk_spliteq* e, uint64_t* e1, uint64_t* e2);
 
 /* the layer's current coefficients as a borrowed dense polynomial (for evaluating a layer's MLE) */
 int cozk_layer_as_poly(cozk_ctx* ctx, const cozk_layer* l, cozk_poly** out);
