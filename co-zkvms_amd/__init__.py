@@ -18,6 +18,8 @@ from .poly import (Rep3DensePolynomial, Rep3DenseInterleavedPolynomial, SplitEqP
 from .harness import Harness, HarnessConfig, HarnessResult
 from .spartan import SpartanHarness, SpartanConfig, SpartanResult
 from .lookups import SparseLayer, SparseStats, sparse_stats, sparse_reset_stats, PrimaryGroup
+from . import lasso
+from .lasso import lasso_witness
 from . import shamir_spartan
 from .shamir_spartan import SpartanGroup, ShamirSpartanHarness, ShamirSpartanConfig, ShamirSpartanResult
 from . import shamir_jolt_spartan

@@ -16,7 +16,10 @@
 // timestamps, v_init / v_final are seeded streams.  NOT part of the flow (out of this path's scope): party 0's public
 // TimestampValidityProof (jolt-core, read_write_memory/worker.rs:78-104) and the verifier's multiset-equality check of the hashes (the
 // synthetic counters are not a consistent offline-memory-checking instance; every sumcheck, GKR layer, fingerprint-vs-opening relation and
-// the batched PST13 opening ARE verified).  The Lasso lookup_outputs polynomial is generated from the E polynomials (sum_i flag_i g_i(E)),
+// the batched PST13 opening ARE verified).  cfg.lookups_witness = 1 replaces the instruction lookups' seeded read_cts / E / final_cts by a
+// consistent instance counted on the device (cozk_lasso_witness over the committed query chunks, the memory flags and the subtables),
+// and the verifier then DOES run the multiset-equality check of the lookups' hashes; the bytecode and the read-write memory keep
+// synthetic counters either way.  The Lasso lookup_outputs polynomial is generated from the E polynomials (sum_i flag_i g_i(E)),
 // independently of the R1CS LookupOutput column (a real trace identifies the two).  oracle/pyflow.py restates the flow; proofs are compared
 // byte for byte.
 #pragma once
@@ -125,6 +128,98 @@ inline bool flow_vec_eq(const std::vector<fe>& a, const std::vector<fe>& b) {
 }
 
 // ------------------------------------------------------------------------------------------------ the dealer's view
+// host threads over index ranges (the setup of a 2^20-cycle trace generates ~10^8 field elements)
+void flow_par_for(size_t n, const std::function<void(size_t, size_t)>& body) {
+    unsigned nt = std::thread::hardware_concurrency();
+    nt = nt == 0 ? 1 : (nt > 16 ? 16 : nt);
+    if (n < 4096 || nt == 1) {
+        body(0, n);
+        return;
+    }
+    std::vector<std::thread> ts;
+    for (unsigned k = 0; k < nt; k++) ts.emplace_back([&, k] { body(n * k / nt, n * (k + 1) / nt); });
+    for (auto& t : ts) t.join();
+}
+
+template <typename T>
+VecH flow_upload_ints(cozk_ctx* ctx, const std::vector<uint64_t>& v, int kind) {
+    std::vector<T> t(v.size());
+    for (size_t i = 0; i < v.size(); i++) t[i] = (T)v[i];
+    return upload_vec(ctx, t.data(), t.size(), kind, "vec_upload(compact column)");
+}
+VecH flow_upload_compact(cozk_ctx* ctx, const std::vector<uint64_t>& v, int bytes) {
+    if (bytes == 1) return flow_upload_ints<uint8_t>(ctx, v, COZK_SCALAR_U8);
+    if (bytes == 4) return flow_upload_ints<uint32_t>(ctx, v, COZK_SCALAR_U32);
+    return flow_upload_ints<uint64_t>(ctx, v, COZK_SCALAR_U64);
+}
+
+// memory_flag_indices as a dense 0/1 column: memory m is live at step t iff the step's instruction uses it
+std::vector<uint64_t> flow_mem_flag_column(const cozk_flow* h, int m) {
+    std::vector<uint64_t> col(h->N, 0);
+    for (int i = 0; i < jolt::N_INSTR; i++) {
+        const cozk_primary_instr& in = h->instrs[(size_t)i];
+        bool uses = false;
+        for (int j = 0; j < in.n_mems; j++) uses |= in.mems[j] == m;
+        if (!uses) continue;
+        const std::vector<fe>& fl = h->clear[(size_t)(jolt::V_INSTR + i)];
+        for (size_t t2 = 0; t2 < h->N; t2++)
+            if (!Fr::is_zero(fl[t2])) col[t2] = 1;
+    }
+    return col;
+}
+
+// cfg.lookups_witness: read_cts / E / final_cts of every memory as a consistent offline-memory-checking instance
+// (instruction_lookups/witness.rs:85-150), counted on party 0's device from the committed query chunks (memory m reads chunk m % 4,
+// as its leaves do), the memory flags and the subtables; the results come back as clear columns that are shared like any other
+void flow_lasso_witness(cozk_flow* h) {
+    const cozk_flow_config& c = h->cfg;
+    const FlowIdx& ix = h->ix;
+    cozk_ctx* ctx = h->parties[0].ctx;
+    const size_t N = h->N, M = h->M;
+    std::vector<VecH> dims, subs, flags;
+    for (int i = 0; i < 4; i++) {
+        const std::vector<fe>& col = h->clear[(size_t)(jolt::V_QUERY + i)];
+        std::vector<uint64_t> ints(N);
+        for (size_t t = 0; t < N; t++) ints[t] = Fr::from_mont(col[t]).l[0];
+        dims.push_back(flow_upload_compact(ctx, ints, 4));
+    }
+    for (auto& s : h->subtables_clear) subs.push_back(flow_upload_compact(ctx, s, 4));
+    for (int m = 0; m < c.n_mem; m++) flags.push_back(flow_upload_compact(ctx, flow_mem_flag_column(h, m), 1));
+    std::vector<const cozk_vec*> dv, sv, fv;
+    for (auto& v : dims) dv.push_back(v.h);
+    for (auto& v : subs) sv.push_back(v.h);
+    for (auto& v : flags) fv.push_back(v.h);
+    std::vector<int> mem_dim((size_t)c.n_mem), mem_sub((size_t)c.n_mem);
+    for (int m = 0; m < c.n_mem; m++) {
+        mem_dim[(size_t)m] = m % 4;
+        mem_sub[(size_t)m] = m % c.n_subtables;
+    }
+    std::vector<cozk_vec*> rc((size_t)c.n_mem), E((size_t)c.n_mem), fc((size_t)c.n_mem);
+    rc_check(cozk_lasso_witness(ctx, dv.data(), dv.size(), sv.data(), sv.size(), fv.data(), mem_dim.data(), mem_sub.data(), (size_t)c.n_mem, rc.data(), E.data(), fc.data()),
+             ctx, "lasso_witness");
+    std::vector<VecH> own;
+    for (auto* list : {&rc, &E, &fc})
+        for (cozk_vec* v : *list) own.push_back(VecH(v));
+    auto take = [&](cozk_vec* v, int idx, size_t n) {
+        std::vector<uint32_t> w(n);
+        rc_check(cozk_vec_download(ctx, v, w.data()), ctx, "vec_download(lookup witness)");
+        std::vector<fe>& col = h->clear[(size_t)idx];
+        col.resize(n);
+        flow_par_for(n, [&](size_t lo, size_t hi) {
+            for (size_t i = lo; i < hi; i++) col[i] = Fr::from_u64(w[i]);
+        });
+    };
+    for (int m = 0; m < c.n_mem; m++) {
+        take(rc[(size_t)m], ix.read_cts + m, N);
+        take(E[(size_t)m], ix.E + m, N);
+        take(fc[(size_t)m], ix.final_cts + m, M);
+    }
+    if (c.lookups_tamper > 0) {  // tests: an inconsistent final counter that every other relation of the proof still accepts
+        fe& v = h->clear[(size_t)ix.final_cts][(size_t)(c.lookups_tamper - 1)];
+        v = Fr::add(v, Fr::one());
+    }
+}
+
 void flow_build_clear(cozk_flow* h) {
     const cozk_flow_config& c = h->cfg;
     const uint64_t seed = c.seed;
@@ -149,18 +244,7 @@ void flow_build_clear(cozk_flow* h) {
         h->is_public[(size_t)idx] = 1;
         h->pub_bytes[(size_t)idx] = 4;
     };
-    // host threads over index ranges (the setup of a 2^20-cycle trace generates ~10^8 field elements)
-    auto par_for = [&](size_t n, const std::function<void(size_t, size_t)>& body) {
-        unsigned nt = std::thread::hardware_concurrency();
-        nt = nt == 0 ? 1 : (nt > 16 ? 16 : nt);
-        if (n < 4096 || nt == 1) {
-            body(0, n);
-            return;
-        }
-        std::vector<std::thread> ts;
-        for (unsigned k = 0; k < nt; k++) ts.emplace_back([&, k] { body(n * k / nt, n * (k + 1) / nt); });
-        for (auto& t : ts) t.join();
-    };
+    auto par_for = flow_par_for;
     // cfg.small_witness: the widths a real trace gives these columns (0 = uniform field elements, see include/cozk.h)
     const int cnt_bits = c.small_witness ? c.log_n : 0, val_bits = c.small_witness ? 32 : 0;
     h->device_bits.assign((size_t)ix.count, 0);
@@ -182,7 +266,7 @@ void flow_build_clear(cozk_flow* h) {
     sh(ix.rw_v_init, seed + 45000, MEM, val_bits);
     sh(ix.rw_v_final, seed + 46000, MEM, val_bits);
     pub(ix.rw_t_final, 47, MEM, 20);
-    for (int m = 0; m < c.n_mem; m++) {
+    for (int m = 0; m < c.n_mem && !c.lookups_witness; m++) {
         dev(ix.read_cts + m, seed + 11000ull * (uint64_t)(m + 1), N, cnt_bits);
         sh(ix.E + m, seed + 9000ull * (uint64_t)(m + 1), N, val_bits);
         dev(ix.final_cts + m, seed + 13000ull * (uint64_t)(m + 1), M, cnt_bits);
@@ -196,6 +280,7 @@ void flow_build_clear(cozk_flow* h) {
         for (size_t i = 0; i < M; i++) h->subtables_clear[(size_t)s][i] = synthetic_small_host(seed + 15000ull * (uint64_t)(s + 1), i, 32);
     // lookup_outputs = sum_i flag_i g_i(E) in the clear
     h->instrs = lookups_instr_table(c.n_mem);
+    if (c.lookups_witness) flow_lasso_witness(h);
     std::vector<fe>& outs = h->clear[(size_t)ix.lasso_out];
     outs.assign(N, Fr::zero());
     par_for(N, [&](size_t lo, size_t hi) {
@@ -230,18 +315,6 @@ uint64_t flow_share_seed(const cozk_flow* h, int idx) {
     if (idx >= ix.read_cts && idx < ix.E) return seed + 11000ull * (uint64_t)(idx - ix.read_cts + 1);
     if (idx >= ix.E && idx < ix.lasso_out) return seed + 9000ull * (uint64_t)(idx - ix.E + 1);
     return seed + 13000ull * (uint64_t)(idx - ix.final_cts + 1);
-}
-
-template <typename T>
-VecH flow_upload_ints(cozk_ctx* ctx, const std::vector<uint64_t>& v, int kind) {
-    std::vector<T> t(v.size());
-    for (size_t i = 0; i < v.size(); i++) t[i] = (T)v[i];
-    return upload_vec(ctx, t.data(), t.size(), kind, "vec_upload(compact column)");
-}
-VecH flow_upload_compact(cozk_ctx* ctx, const std::vector<uint64_t>& v, int bytes) {
-    if (bytes == 1) return flow_upload_ints<uint8_t>(ctx, v, COZK_SCALAR_U8);
-    if (bytes == 4) return flow_upload_ints<uint32_t>(ctx, v, COZK_SCALAR_U32);
-    return flow_upload_ints<uint64_t>(ctx, v, COZK_SCALAR_U64);
 }
 
 void flow_setup_party(cozk_flow* h, FlowParty& ps) {
@@ -307,20 +380,7 @@ void flow_setup_party(cozk_flow* h, FlowParty& ps) {
     static const int tab_bytes[6] = {4, 8, 1, 1, 1, 4};
     for (int k = 0; k < 6; k++) ps.bc_table.push_back(flow_upload_compact(ctx, h->bc_table_clear[(size_t)k], tab_bytes[k]));
     for (auto& s : h->subtables_clear) ps.subtables.push_back(flow_upload_compact(ctx, s, 4));
-    // memory_flag_indices: memory m is live at step t iff the step's instruction uses it
-    for (int m = 0; m < c.n_mem; m++) {
-        std::vector<uint64_t> col(h->N, 0);
-        for (int i = 0; i < jolt::N_INSTR; i++) {
-            const cozk_primary_instr& in = h->instrs[(size_t)i];
-            bool uses = false;
-            for (int j = 0; j < in.n_mems; j++) uses |= in.mems[j] == m;
-            if (!uses) continue;
-            const std::vector<fe>& fl = h->clear[(size_t)(jolt::V_INSTR + i)];
-            for (size_t t2 = 0; t2 < h->N; t2++)
-                if (!Fr::is_zero(fl[t2])) col[t2] = 1;
-        }
-        ps.mem_flags.push_back(flow_upload_compact(ctx, col, 1));
-    }
+    for (int m = 0; m < c.n_mem; m++) ps.mem_flags.push_back(flow_upload_compact(ctx, flow_mem_flag_column(h, m), 1));
     ps.io_range = upload_vec(ctx, h->io_range_clear.data(), h->MEM, COZK_SCALAR_FR, "vec_upload");
     ps.v_io = upload_vec(ctx, h->v_io_clear.data(), h->MEM, COZK_SCALAR_FR, "vec_upload");
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -872,6 +932,25 @@ bool flow_verify(cozk_flow* h, const FlowProof& proof, std::string& why) {
             why = "lookups: init / final fingerprints != the GKR claim";
             return false;
         }
+        if (c.lookups_witness) {  // check_multiset_equality (lasso/memory_checking/worker.rs:40-127): init * writes == reads * finals per memory
+            const std::vector<fe>& rwh = proof.lookups.rw_hashes;
+            const std::vector<fe>& ifh = proof.lookups.if_hashes;
+            std::vector<size_t> init_at((size_t)c.n_subtables), final_at((size_t)c.n_mem);
+            size_t at = 0;
+            for (int s = 0; s < c.n_subtables; s++) {  // if_hashes per subtable: the init, then the finals of its memories
+                init_at[(size_t)s] = at++;
+                for (int m = 0; m < c.n_mem; m++)
+                    if (m % c.n_subtables == s) final_at[(size_t)m] = at++;
+            }
+            for (int m = 0; m < c.n_mem; m++) {
+                const fe reads_finals = Fr::mul(rwh[(size_t)(2 * m)], ifh[final_at[(size_t)m]]);
+                const fe writes_init = Fr::mul(rwh[(size_t)(2 * m + 1)], ifh[init_at[(size_t)(m % c.n_subtables)]]);
+                if (!Fr::eq(reads_finals, writes_init)) {
+                    why = "lookups: multiset equality of the memory-checking hashes";
+                    return false;
+                }
+            }
+        }
     }
     // ---- 4. read-write memory
     {
@@ -959,14 +1038,20 @@ int cozk_flow_create(const cozk_flow_config* cfg, cozk_flow** out) {
         h->M = (size_t)1 << cfg->log_m;
         h->B = (size_t)1 << cfg->log_b;
         h->MEM = (size_t)1 << cfg->log_mem;
+        COZK_REQUIRE(!cfg->lookups_witness || cfg->log_m == 16,
+                     "flow: lookups_witness needs log_m == 16 (the addresses are the committed 16-bit query chunks), hence log_n >= 16");
+        COZK_REQUIRE(cfg->lookups_tamper >= 0 && (cfg->lookups_tamper == 0 || (cfg->lookups_witness && (size_t)cfg->lookups_tamper <= h->M)),
+                     "flow: lookups_tamper in 0..2^log_m, with lookups_witness");
         h->ix = FlowIdx(cfg->n_mem);
         jolt::build_system(h->sys);
-        flow_build_clear(h);
         h->parties.resize((size_t)h->nparties);
+        const char* no_ctx = "flow: cannot create a context (no HIP device?)";
+        if (cfg->lookups_witness) h->parties[0].open_ctx(cfg->devices[0], no_ctx);  // the dealer's counting pass runs on party 0's device
+        flow_build_clear(h);
         for (int p = 0; p < h->nparties; p++) {
             FlowParty& ps = h->parties[(size_t)p];
             ps.party = p;
-            ps.open_ctx(cfg->devices[p], "flow: cannot create a context (no HIP device?)");
+            if (!ps.ctx) ps.open_ctx(cfg->devices[p], no_ctx);
             cozk_ctx_set_resident_rounds(ps.ctx, h->nparties > 1 ? 0 : 1);
             flow_setup_party(h, ps);
         }

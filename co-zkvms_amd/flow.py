@@ -8,7 +8,7 @@ from . import _lib as L
 class FlowConfig(ctypes.Structure):
     _fields_ = [("mode", ctypes.c_int), ("log_n", ctypes.c_int), ("log_m", ctypes.c_int), ("log_b", ctypes.c_int), ("log_mem", ctypes.c_int),
                 ("n_mem", ctypes.c_int), ("n_subtables", ctypes.c_int), ("devices", ctypes.c_int * 3), ("seed", ctypes.c_uint64),
-                ("precompute", ctypes.c_int), ("small_witness", ctypes.c_int)]
+                ("precompute", ctypes.c_int), ("small_witness", ctypes.c_int), ("lookups_witness", ctypes.c_int), ("lookups_tamper", ctypes.c_int)]
 
 
 class FlowResult(ctypes.Structure):
@@ -26,7 +26,11 @@ class FlowHarness(L.HarnessHandle):
     PREFIX, CONFIG, RESULT = "cozk_flow", FlowConfig, FlowResult
     EXTRA = {"cozk_flow_num_polys": (_sz, [_vp]), "cozk_flow_ctx": (_vp, [_vp, _i])}
 
-    def __init__(self, mode="plain", log_n=4, log_m=3, log_b=3, log_mem=3, n_mem=6, n_subtables=3, devices=(0, 0, 0), seed=1, precompute=1, small_witness=0):
+    def __init__(self, mode="plain", log_n=4, log_m=3, log_b=3, log_mem=3, n_mem=6, n_subtables=3, devices=(0, 0, 0), seed=1, precompute=1, small_witness=0,
+                 lookups_witness=0, lookups_tamper=0):
+        """lookups_witness=1 (needs log_m == 16): read_cts / E / final_cts of the instruction lookups are a consistent instance made
+        on the device (cozk_lasso_witness) and the verifier runs the multiset-equality check of their hashes; lookups_tamper=k > 0
+        (tests) bumps final_cts[0][k - 1] so that only that check can reject"""
         cfg = FlowConfig()
         cfg.mode = L.MODE_PLAIN if mode == "plain" else L.MODE_REP3
         cfg.log_n, cfg.log_m, cfg.log_b, cfg.log_mem = log_n, log_m, log_b, log_mem
@@ -35,6 +39,7 @@ class FlowHarness(L.HarnessHandle):
         cfg.seed = seed
         cfg.precompute = precompute
         cfg.small_witness = small_witness
+        cfg.lookups_witness, cfg.lookups_tamper = lookups_witness, lookups_tamper
         self._open(cfg)
 
     def num_polys(self):

@@ -1674,11 +1674,35 @@ int cozk_shamir_primary_prep(cozk_shamir_primary* h, cozk_shamir_primary_prep_re
 int cozk_shamir_primary_prep_get_result(const cozk_shamir_primary* h, cozk_shamir_primary_prep_result* res);
 int cozk_shamir_primary_prove_king(cozk_shamir_primary* h, int king, int verify, cozk_shamir_primary_result* res);
 
+/* ---- the dealer's Lasso lookup witness (co-jolt/src/jolt/vm/instruction_lookups/witness.rs:85-150): the coordinator's walk over
+ * the trace that makes read_cts / final_cts / E of every memory, before stream_secret_shares (witness.rs:281-310) hands them to the
+ * witness scatter (cozk_rep3_scatter).  For memory m with addr = dims[mem_dim[m]], flag = flags[m], subtable = subtables[mem_subtable[m]]:
+ *   read_cts[m][j]  = #{ j' < j : flag[j'] = 1 and addr[j'] = addr[j] } if flag[j] = 1, else 0     (TIME order, deterministic)
+ *   final_cts[m][a] = #{ j : flag[j] = 1 and addr[j] = a }
+ *   E[m][j]         = subtable[addr[j]] if flag[j] = 1, else 0
+ * dims: n_dims U32 vectors of n addresses, 1 <= n < 2^32 (any n).  subtables: n_subtables U32 vectors of M entries, 1 <= M <= 65536.
+ * flags: n_mem U8 vectors of n entries (non-zero = the step uses the memory); a NULL entry = used at every step.  An unflagged step's
+ * address is never used as an index.  A flagged address >= M: COZK_ERR_INVALID_ARG, cozk_last_error names the first such (memory,
+ * step), no vector is returned (the kernels skip the address; nothing is read or written out of bounds).
+ * Outputs: n_mem NEW vectors each, U32[n], U32[n], U32[M] -- compact columns as the MSM's small-scalar path and
+ * cozk_fingerprint_leaves take them.  All memories go through one batched set of launches (tiles of COZK_LASSO_TILE steps x memories);
+ * the transient tile histograms are 6 bytes per (tile, memory, address) and the memories are processed in batches that keep them
+ * under 256 MiB.  The call returns after the device has finished. */
+#define COZK_LASSO_TILE 32768
+int cozk_lasso_witness(cozk_ctx* ctx, const cozk_vec* const* dims, size_t n_dims, const cozk_vec* const* subtables, size_t n_subtables,
+                       const cozk_vec* const* flags, const int* mem_dim, const int* mem_subtable, size_t n_mem, cozk_vec** read_cts,
+                       cozk_vec** E, cozk_vec** final_cts);
+size_t cozk_lasso_tile(void); /* COZK_LASSO_TILE of the loaded library */
+
 /* ---- ONE chained co-jolt worker flow (JoltRep3Prover::prove, co-jolt/src/jolt/vm/jolt/worker.rs:175-266, against its coordinator
  * jolt/vm/jolt/coordinator.rs:118-222): commit-all -> bytecode memory checking -> instruction lookups (primary sumcheck, toggled
  * read / write + dense init / final grand products) -> read-write memory checking + output check -> Spartan (outer + inner + shift) ->
  * ONE reduce_and_prove over all accumulated openings; one transcript, one opening accumulator, all leaves K11 fingerprints of
- * committed columns.  Synthetic Jolt-shaped witness (csrc/host/flow_harness.hpp); oracle/pyflow.py restates it. */
+ * committed columns.  Synthetic Jolt-shaped witness (csrc/host/flow_harness.hpp); oracle/pyflow.py restates it.
+ * By default the counters of all three memory-checking instances are seeded streams and the harness verifier skips the
+ * multiset-equality check of their hashes.  lookups_witness = 1 makes the instruction lookups a consistent instance (cozk_lasso_witness
+ * on the dealer's device, before sharing) and the verifier runs that check for them; the bytecode and the read-write memory keep
+ * synthetic counters.  With lookups_witness = 0 the proof bytes are what they were before the field existed. */
 typedef struct cozk_flow cozk_flow;
 typedef struct cozk_flow_config {
     int mode;
@@ -1695,6 +1719,14 @@ typedef struct cozk_flow_config {
                         * commits to (its share of every value is uniform) and an upper bound for a plain prover; 1: they are as wide
                         * as a real trace makes them (counters < 2^log_n, subtable entries and memory words 32 bits), so a PLAIN
                         * prover's commitments fill 2 of the 16 windows; Rep3 shares stay uniform either way */
+    int lookups_witness; /* 0: read_cts / E / final_cts of the instruction lookups are seeded streams and the verifier skips the
+                          * multiset-equality check of their memory-checking hashes.  1: they are a consistent offline-memory-checking
+                          * instance made on the device (cozk_lasso_witness over the committed query-chunk columns, the memory flags and
+                          * the subtables; needs log_m == 16), shared as ordinary columns, and the verifier checks, per memory m,
+                          * rw_hashes[2m] * final_hash(m) == rw_hashes[2m + 1] * init_hash(m % n_subtables)
+                          * (lasso/memory_checking/worker.rs:40-127).  The bytecode and the read-write memory keep synthetic counters. */
+    int lookups_tamper;  /* tests, with lookups_witness: k > 0 adds 1 to final_cts[0][k - 1] before sharing -- every sumcheck,
+                          * opening and fingerprint relation still holds, only the multiset check can reject */
 } cozk_flow_config;
 typedef struct cozk_flow_result {
     int verified;
