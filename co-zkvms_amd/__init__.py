@@ -20,6 +20,8 @@ from .spartan import SpartanHarness, SpartanConfig, SpartanResult
 from .lookups import SparseLayer, SparseStats, sparse_stats, sparse_reset_stats, PrimaryGroup
 from . import lasso
 from .lasso import lasso_witness
+from . import rw_memory
+from .rw_memory import rw_memory_witness, RW_MEMORY_SYMBOLS
 from . import shamir_spartan
 from .shamir_spartan import SpartanGroup, ShamirSpartanHarness, ShamirSpartanConfig, ShamirSpartanResult
 from . import shamir_jolt_spartan

@@ -24,6 +24,7 @@
 // A flagged address >= M is skipped by every kernel (no load or store leaves its buffer) and reported through one device word,
 // the smallest (memory, step) of a violation (an atomicMin: its result does not depend on the order of arrival).
 #include "common.hpp"
+#include "lasso_walk.hip.hpp"  // the wave step of the walk (shared with rw_memory_witness.hip)
 
 static constexpr int LW_TILE = COZK_LASSO_TILE;  // steps per tile: in-tile ranks and counts (<= 32768) fit 16 bits
 static constexpr uint32_t LW_MAX_M = 65536;
@@ -86,25 +87,9 @@ __global__ void __launch_bounds__(LW_PT) k_lasso_rank(const LwMem* __restrict__ 
         if (wave == 0) {
             for (uint32_t k0 = 0; k0 < cnt; k0 += 64) {
                 const bool valid = k0 + lane < cnt;
-                const uint32_t x = valid ? list[k0 + lane] : 0, av = x & 0xffff;
-                unsigned long long peers = __ballot(valid);
-                for (int bit = 0; bit < key_bits; bit++) {
-                    const bool set = (av >> bit) & 1;
-                    const unsigned long long bal = __ballot(set);
-                    peers &= set ? bal : ~bal;
-                }
-                if (!valid) peers = 1ull << lane;
-                const int leader = __ffsll((long long)peers) - 1;
-                uint32_t old = 0;
-                if (valid && leader == (int)lane) {
-                    old = tab[av];
-                    tab[av] = (uint16_t)(old + (uint32_t)__popcll(peers));
-                }
-                old = __shfl(old, leader);
-                if (valid) mm.rc[c0 + (x >> 16)] = old + (uint32_t)__popcll(peers & below);
-                // the next wave step reads what this one wrote: keep the table accesses in program order
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                const uint32_t x = valid ? list[k0 + lane] : 0;
+                const uint32_t rank = lw_walk_step(tab, valid, x & 0xffff, key_bits, lane);
+                if (valid) mm.rc[c0 + (x >> 16)] = rank;
             }
         }
         __syncthreads();  // the next chunk rewrites the list

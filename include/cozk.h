@@ -1694,6 +1694,37 @@ int cozk_lasso_witness(cozk_ctx* ctx, const cozk_vec* const* dims, size_t n_dims
                        cozk_vec** E, cozk_vec** final_cts);
 size_t cozk_lasso_tile(void); /* COZK_LASSO_TILE of the loaded library */
 
+/* ---- the dealer's read-write memory witness (jolt-core's ReadWriteMemoryPolynomials::generate_witness, the coordinator's walk
+ * before read_write_memory/witness.rs:34-93 shares its result): v_read / t_read / v_final / t_final of the register + RAM memory from
+ * the trace's addresses and written values.  The n * n_slots operations are ordered by (step j, slot s) -- for Jolt n_slots = 4 in the
+ * order rs1, rs2, rd, ram (read_write_memory/worker.rs:243-310): rs1 and rs2 only read, rd writes at every step, ram writes where
+ * the store flag is set -- and all slots share ONE memory of MEM = v_init->n words.  From v = v_init, t = 0, per operation with
+ * a = addr[s][j]:
+ *   v_read[s][j] = v[a];   t_read[s][j] = t[a];
+ *   w = (slot s writes at step j) ? v_write[s][j] : v[a];
+ *   v[a] = w;   t[a] = j;   (v_written[s][j] = w where that vector exists)           and at the end   v_final = v, t_final = t
+ * so t_read[s][j] <= j, the write fingerprint of every operation of step j carries j, and
+ *   prod_a h(a, v_init[a], 0) * prod_(j,s) h(a, w, j) == prod_(j,s) h(a, v_read, t_read) * prod_a h(a, v_final[a], t_final[a]).
+ * addr: n_slots vectors of n addresses, each U8 or U32.  v_write[s]: U32[n], or NULL = the slot only reads.  is_write[s]: U8[n],
+ * non-zero = the step writes, or NULL = every step writes (if v_write[s] is given); it must be NULL where v_write[s] is NULL.
+ * v_write / is_write may be NULL as a whole (= every entry NULL).  1 <= n, 1 <= n_slots <= COZK_RW_MEMORY_MAX_SLOTS,
+ * n * n_slots < 2^32, 1 <= MEM < 2^32 (Jolt's RAM is 2^20 words and more; no 65536 limit here).
+ * Outputs: v_read, t_read: n_slots NEW U32[n] each; v_written: n_slots entries, a NEW U32[n] for a slot with is_write flags, else
+ * NULL (there it is v_write[s] or v_read[s]); v_final, t_final: one NEW U32[MEM] each -- compact columns as cozk_fingerprint_leaves
+ * and the MSM's small-scalar path take them.  Bit-for-bit deterministic.
+ * An address >= MEM: COZK_ERR_INVALID_ARG, cozk_last_error names the smallest (step, slot); nothing is read or written out of
+ * bounds.  A wrong kind, a length other than n and is_write without v_write are refused with their own texts.  On any failure every
+ * output pointer is NULL (the per-slot ones if n_slots <= COZK_RW_MEMORY_MAX_SLOTS) and the context works on.
+ * The walk is a stable sort of the operations by address (16-bit radix passes over tiles of COZK_LASSO_TILE operations; one pass
+ * for MEM <= 65536, else two) and a sweep over the sorted operations.  Transient device memory, with N = n * n_slots,
+ * tiles = ceil(N / COZK_LASSO_TILE), D = max(min(MEM, 65536), MEM > 65536 ? ceil(MEM / 65536) : 0):
+ *   4 N (8 N for two passes) + 2 N + 6 tiles D + 4 D + N / 512 bytes
+ * = 72 MiB at n = 2^20 with 4 slots and MEM = 2^16, 88 MiB at MEM = 2^20.  The call returns after the device has finished. */
+#define COZK_RW_MEMORY_MAX_SLOTS 8
+int cozk_rw_memory_witness(cozk_ctx* ctx, const cozk_vec* const* addr, const cozk_vec* const* v_write, const cozk_vec* const* is_write,
+                           size_t n_slots, const cozk_vec* v_init, cozk_vec** v_read, cozk_vec** t_read, cozk_vec** v_written,
+                           cozk_vec** v_final, cozk_vec** t_final);
+
 /* ---- ONE chained co-jolt worker flow (JoltRep3Prover::prove, co-jolt/src/jolt/vm/jolt/worker.rs:175-266, against its coordinator
  * jolt/vm/jolt/coordinator.rs:118-222): commit-all -> bytecode memory checking -> instruction lookups (primary sumcheck, toggled
  * read / write + dense init / final grand products) -> read-write memory checking + output check -> Spartan (outer + inner + shift) ->
