@@ -22,6 +22,8 @@ from . import lasso
 from .lasso import lasso_witness
 from . import rw_memory
 from .rw_memory import rw_memory_witness, RW_MEMORY_SYMBOLS
+from . import ts_range
+from .ts_range import time_counters, timestamp_range_witness, TS_RANGE_SYMBOLS
 from . import shamir_spartan
 from .shamir_spartan import SpartanGroup, ShamirSpartanHarness, ShamirSpartanConfig, ShamirSpartanResult
 from . import shamir_jolt_spartan

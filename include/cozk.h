@@ -1725,6 +1725,41 @@ int cozk_rw_memory_witness(cozk_ctx* ctx, const cozk_vec* const* addr, const coz
                            size_t n_slots, const cozk_vec* v_init, cozk_vec** v_read, cozk_vec** t_read, cozk_vec** v_written,
                            cozk_vec** v_final, cozk_vec** t_final);
 
+/* ---- Lasso counters over an identity table of any length, and the dealer's timestamp range-check witness made of them (jolt-core's
+ * TimestampRangeCheckPolynomials::generate_witness, the coordinator's third walk before sharing: its four families
+ * read_cts_read_timestamp / read_cts_global_minus_read / final_cts_read_timestamp / final_cts_global_minus_read are shared as public
+ * vectors at co-jolt/src/jolt/vm/jolt/witness.rs:384-409 and timestamp_range_check.rs:31-58, and are the inputs of
+ * TimestampValidityProof::prove).  jolt-core is not in the reference tree: the recurrence below is restated from upstream knowledge
+ * (parity unpinned).  What pins it is the field names at witness.rs:384-409 and the multiset identity of the memory checking,
+ *   prod_a h(a, a, 0) * prod_j h(key_j, key_j, read_cts_j + 1) == prod_j h(key_j, key_j, read_cts_j) * prod_a h(a, a, final_cts[a]).
+ * cozk_time_counters: n_cols independent columns (1 <= n_cols <= COZK_TIME_COUNTERS_MAX_COLS) of n U32 keys each over an identity
+ * table of M entries, 1 <= n < 2^32, 1 <= M < 2^32 (no 65536 limit: the steps are sorted by key, not counted in LDS).  Per column:
+ *   read_cts[c][j]  = #{ j' < j : keys[c][j'] == keys[c][j] }          (TIME order, as in cozk_lasso_witness)
+ *   final_cts[c][a] = #{ j : keys[c][j] == a }
+ * Outputs: per column a NEW U32[n] and a NEW U32[M] -- compact columns as cozk_fingerprint_leaves and the MSM's small-scalar path
+ * take them.  Bit-for-bit deterministic.  A key >= M: COZK_ERR_INVALID_ARG, cozk_last_error names the smallest (column, step);
+ * every kernel uses such a key as 0, so nothing is read or written out of bounds.
+ * cozk_timestamp_range_witness: t_read[s] is U32[n] for 1 <= n_slots <= COZK_RW_MEMORY_MAX_SLOTS slots, exactly as
+ * cozk_rw_memory_witness returns it, and M >= n is the table's length (Jolt: the padded trace length).  The same launches over
+ * 2 * n_slots columns whose keys are derived where they are used and never stored:
+ *   key = t_read[s][j]       -> read_cts_read_timestamp[s],     final_cts_read_timestamp[s]
+ *   key = j - t_read[s][j]   -> read_cts_global_minus_read[s],  final_cts_global_minus_read[s]
+ * t_read[s][j] > j: COZK_ERR_INVALID_ARG, cozk_last_error names the smallest (step, slot).
+ * Both calls: a wrong kind, columns of unequal length and M < n (second call) are refused with their own texts before any launch;
+ * on any failure every output pointer is NULL (if the column / slot count is within its limit) and the context works on.
+ * A stable sort of each column's steps by key (16-bit radix passes over tiles of COZK_LASSO_TILE steps; one pass for M <= 65536,
+ * else two): with one pass the tile bases + in-tile ranks are read_cts and the digit counts final_cts; with two, a sweep over the
+ * sorted steps takes each step's position minus its segment's start, and a segment's length.  Transient device memory for B
+ * columns at a time, with tiles = ceil(n / COZK_LASSO_TILE), D = max(min(M, 65536), M > 65536 ? ceil(M / 65536) : 0):
+ *   B (6 tiles D + 2 n) bytes, and B (4 D + 12 n) more for two passes
+ * where B is the largest column count that keeps 6 tiles D B under 256 MiB (at least one column)
+ * = 210 MiB at n = 2^20 with 4 slots (8 columns) and M = 2^20.  Both calls return after the device has finished. */
+#define COZK_TIME_COUNTERS_MAX_COLS 16
+int cozk_time_counters(cozk_ctx* ctx, const cozk_vec* const* keys, size_t n_cols, size_t M, cozk_vec** read_cts, cozk_vec** final_cts);
+int cozk_timestamp_range_witness(cozk_ctx* ctx, const cozk_vec* const* t_read, size_t n_slots, size_t M, cozk_vec** read_cts_read_timestamp,
+                                 cozk_vec** read_cts_global_minus_read, cozk_vec** final_cts_read_timestamp,
+                                 cozk_vec** final_cts_global_minus_read);
+
 /* ---- ONE chained co-jolt worker flow (JoltRep3Prover::prove, co-jolt/src/jolt/vm/jolt/worker.rs:175-266, against its coordinator
  * jolt/vm/jolt/coordinator.rs:118-222): commit-all -> bytecode memory checking -> instruction lookups (primary sumcheck, toggled
  * read / write + dense init / final grand products) -> read-write memory checking + output check -> Spartan (outer + inner + shift) ->
