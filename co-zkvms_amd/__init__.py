@@ -24,6 +24,9 @@ from . import rw_memory
 from .rw_memory import rw_memory_witness, RW_MEMORY_SYMBOLS
 from . import ts_range
 from .ts_range import time_counters, timestamp_range_witness, TS_RANGE_SYMBOLS
+from . import ts_proof
+from .ts_proof import (compact_batch_evaluate_at_chi, compact_linear_combination, timestamp_range_leaves, TS_PROOF_SYMBOLS, TsProof,
+                       TsProofConfig, TsProofResult)
 from . import shamir_spartan
 from .shamir_spartan import SpartanGroup, ShamirSpartanHarness, ShamirSpartanConfig, ShamirSpartanResult
 from . import shamir_jolt_spartan

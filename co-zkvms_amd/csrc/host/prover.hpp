@@ -1196,21 +1196,33 @@ struct Rep3ProverOpeningAccumulator {
     void append(WorkerEnv& env, const std::vector<cozk_poly*>& polynomials, const cozk_vec* eq_evals, const std::vector<fe>& opening_point,
                 const std::vector<fe>& claims) {
         COZK_REQUIRE(polynomials.size() == claims.size() && !polynomials.empty(), "append: polynomials / claims mismatch");
+        fe batched_claim;
+        std::vector<fe> rho_powers = exchange_claims(env, claims, batched_claim);
+        std::vector<uint64_t> cf = to_abi(rho_powers);
+        cozk_poly* batched = nullptr;
+        rc_check(cozk_poly_linear_combination(env.ctx, polynomials.data(), cf.data(), polynomials.size(), env.mode, env.party, &batched),
+                 env.ctx, "linear_combination");
+        append_joint(env, PolyH(batched), eq_evals, opening_point, batched_claim);
+    }
+
+    // the claim exchange of append: send the claims, receive rho and the batched claim -> the rho powers, one per claim
+    static std::vector<fe> exchange_claims(WorkerEnv& env, const std::vector<fe>& claims, fe& batched_claim) {
         Writer w;
         w.vec_fr(claims);
         env.star->send_response(w.b);
         Bytes req = env.star->receive_request();
         Reader rd(req);
         fe rho = rd.fr();
-        fe batched_claim = rd.fr();
+        batched_claim = rd.fr();
         std::vector<fe> rho_powers(1, Fr::one());
-        for (size_t i = 1; i < polynomials.size(); i++) rho_powers.push_back(Fr::mul(rho_powers[i - 1], rho));
-        std::vector<uint64_t> cf = to_abi(rho_powers);
-        cozk_poly* batched = nullptr;
-        rc_check(cozk_poly_linear_combination(env.ctx, polynomials.data(), cf.data(), polynomials.size(), env.mode, env.party, &batched),
-                 env.ctx, "linear_combination");
+        for (size_t i = 1; i < claims.size(); i++) rho_powers.push_back(Fr::mul(rho_powers[i - 1], rho));
+        return rho_powers;
+    }
+
+    // the rest of append, for a caller that made the joint polynomial sum_i rho^i poly_i itself (from compact columns, say)
+    void append_joint(WorkerEnv& env, PolyH batched, const cozk_vec* eq_evals, const std::vector<fe>& opening_point, const fe& batched_claim) {
         Rep3ProverOpening op;
-        op.polynomial = PolyH(batched);
+        op.polynomial = std::move(batched);
         cozk_poly* eqp = nullptr;
         rc_check(cozk_poly_create(env.ctx, COZK_MODE_PLAIN, eq_evals, nullptr, &eqp), env.ctx, "poly_create(eq)");
         op.eq_poly = PolyH(eqp);

@@ -1,0 +1,402 @@
+// In-process harness of party 0's timestamp range-check proof (TimestampValidityProof::prove, called after the output check at
+// co-jolt/src/jolt/vm/read_write_memory/worker.rs:78-105; its single batched opening goes to the other parties through append_public /
+// receive_public_opening): over public data, every t_read[s][j] and every j - t_read[s][j] lies in [0, N) -- a Lasso memory check over
+// an identity table of N entries with ONE batched dense grand product and ONE batched opening.  jolt-core is not in the reference
+// tree, so the circuit order, the transcript order and the proof bytes are this project's: PARITY UNPINNED.  What pins them is the
+// plain verifier at the end of this file and the Python restatement tests/ts_proof_ref.py (include/cozk.h has the protocol).
+// Every polynomial is a compact U32 column on the device: the commit takes the MSM's small-scalar path, the leaves come from
+// cozk_timestamp_range_leaves, the claims and the joint polynomial from the compact opening calls; no Fr copy of a column exists.
+// Worker on the device, coordinator and verifier on the calling thread through run_in_process, one transcript.
+#pragma once
+
+struct TsProofParty : HarnessParty {
+    std::vector<VecH> t_read, rc_rt, rc_gmr, fc_rt, fc_gmr;  // n_slots U32[N] each
+    VecH iota;                                               // the composition's step column (leaves_fused = 0)
+    std::unique_ptr<PST13Setup> setup;
+    double t_commit = 0, t_leaves = 0, t_gp = 0, t_open = 0;
+};
+
+struct cozk_ts_proof : HarnessHandle {
+    cozk_ts_proof_config cfg;
+    size_t N = 0;
+    int ns = 0;
+    double t_witness = 0;
+    std::vector<TsProofParty> parties;  // party 0 alone
+};
+
+namespace {
+
+struct TsProof {
+    std::vector<PST13Commitment> commitments;
+    std::vector<fe> hashes;
+    GrandProductProof gp;
+    std::vector<fe> claims;
+    ReducedOpeningProof reduced;
+    Bytes serialize() const {
+        Writer w;
+        w.u64(commitments.size());
+        for (auto& c : commitments) c.write(w);
+        w.vec_fr(hashes);
+        gp.write(w);
+        w.vec_fr(claims);
+        reduced.write(w);
+        return w.b;
+    }
+};
+
+// SplitMix64 as oracle/pyref.py's class: one sequential stream
+struct TsSplitMix {
+    uint64_t s;
+    uint64_t next() {
+        s += 0x9E3779B97F4A7C15ull;
+        uint64_t z = s;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return z ^ (z >> 31);
+    }
+};
+
+// the committed columns in the proof's order: family-major, then t_read
+std::vector<const cozk_vec*> ts_proof_columns(const TsProofParty& ps) {
+    std::vector<const cozk_vec*> cols;
+    for (const std::vector<VecH>* fam : {&ps.rc_rt, &ps.rc_gmr, &ps.fc_rt, &ps.fc_gmr, &ps.t_read})
+        for (const VecH& v : *fam) cols.push_back(v.h);
+    return cols;
+}
+
+// create: tests/rw_witness_ref.py's jolt_instance(seed, N, MEM, store_pct = 30, n_regs = 32), both witness walks on the device
+void ts_proof_setup(cozk_ts_proof* h, TsProofParty& ps) {
+    const cozk_ts_proof_config& c = h->cfg;
+    cozk_ctx* ctx = ps.ctx;
+    const size_t N = h->N, MEM = (size_t)1 << c.log_mem;
+    const int ns = h->ns;
+    std::vector<fe> t((size_t)c.log_n);
+    for (int i = 0; i < c.log_n; i++) t[(size_t)i] = synthetic_fr_host(c.seed ^ 0x7A7A7A7Aull, (uint64_t)i);
+    ps.setup = PST13::setup(ctx, t, c.precompute);
+    TsSplitMix rng{c.seed};
+    const uint64_t n_regs = MEM < 32 ? MEM : 32;
+    std::vector<std::vector<uint32_t>> addr(4, std::vector<uint32_t>(N)), vw(2, std::vector<uint32_t>(N));
+    std::vector<uint8_t> iw(N);
+    std::vector<uint32_t> v_init(MEM);
+    for (int s = 0; s < 3; s++)
+        for (size_t j = 0; j < N; j++) addr[(size_t)s][j] = (uint32_t)(rng.next() % n_regs);
+    for (size_t j = 0; j < N; j++) addr[3][j] = (uint32_t)(rng.next() % MEM);
+    for (int k = 0; k < 2; k++)
+        for (size_t j = 0; j < N; j++) vw[(size_t)k][j] = (uint32_t)rng.next();
+    for (size_t j = 0; j < N; j++) iw[j] = rng.next() % 100 < 30 ? 1 : 0;
+    for (size_t a = 0; a < MEM; a++) v_init[a] = (uint32_t)rng.next();
+    double t0 = now_ms();
+    std::vector<VecH> d_addr, d_vw;
+    for (int s = 0; s < 4; s++) d_addr.push_back(upload_vec(ctx, addr[(size_t)s].data(), N, COZK_SCALAR_U32, "vec_upload(addresses)"));
+    for (int k = 0; k < 2; k++) d_vw.push_back(upload_vec(ctx, vw[(size_t)k].data(), N, COZK_SCALAR_U32, "vec_upload(written values)"));
+    VecH d_iw = upload_vec(ctx, iw.data(), N, COZK_SCALAR_U8, "vec_upload(store flags)");
+    VecH d_init = upload_vec(ctx, v_init.data(), MEM, COZK_SCALAR_U32, "vec_upload(v_init)");
+    const cozk_vec* pa[4] = {d_addr[0].h, d_addr[1].h, d_addr[2].h, d_addr[3].h};
+    const cozk_vec* pw[4] = {nullptr, nullptr, d_vw[0].h, d_vw[1].h};
+    const cozk_vec* pf[4] = {nullptr, nullptr, nullptr, d_iw.h};
+    cozk_vec *v_read[4] = {}, *t_read[4] = {}, *v_written[4] = {}, *v_final = nullptr, *t_final = nullptr;
+    rc_check(cozk_rw_memory_witness(ctx, pa, pw, pf, 4, d_init.h, v_read, t_read, v_written, &v_final, &t_final), ctx, "rw_memory_witness");
+    for (int s = 0; s < 4; s++) {
+        cozk_vec_free(v_read[s]);
+        cozk_vec_free(v_written[s]);
+        if (s < ns) ps.t_read.push_back(VecH(t_read[s]));
+        else cozk_vec_free(t_read[s]);
+    }
+    cozk_vec_free(v_final);
+    cozk_vec_free(t_final);
+    std::vector<const cozk_vec*> tr;
+    for (auto& v : ps.t_read) tr.push_back(v.h);
+    cozk_vec *a[COZK_RW_MEMORY_MAX_SLOTS] = {}, *b[COZK_RW_MEMORY_MAX_SLOTS] = {}, *cc[COZK_RW_MEMORY_MAX_SLOTS] = {}, *d[COZK_RW_MEMORY_MAX_SLOTS] = {};
+    rc_check(cozk_timestamp_range_witness(ctx, tr.data(), (size_t)ns, N, a, b, cc, d), ctx, "timestamp_range_witness");
+    for (int s = 0; s < ns; s++) {
+        ps.rc_rt.push_back(VecH(a[s]));
+        ps.rc_gmr.push_back(VecH(b[s]));
+        ps.fc_rt.push_back(VecH(cc[s]));
+        ps.fc_gmr.push_back(VecH(d[s]));
+    }
+    h->t_witness = now_ms() - t0;
+    if (c.tamper == 1) {  // one final counter of the read-timestamp family of slot 0 is bumped: every relation but the multiset's holds
+        std::vector<uint32_t> tr0(N), fc(N);
+        rc_check(cozk_vec_download(ctx, ps.t_read[0].h, tr0.data()), ctx, "vec_download");
+        rc_check(cozk_vec_download(ctx, ps.fc_rt[0].h, fc.data()), ctx, "vec_download");
+        fc[tr0[N / 2]] += 1;
+        ps.fc_rt[0] = upload_vec(ctx, fc.data(), N, COZK_SCALAR_U32, "vec_upload(tampered counters)");
+    }
+    if (!c.leaves_fused) {
+        std::vector<uint32_t> io(N);
+        for (size_t j = 0; j < N; j++) io[j] = (uint32_t)j;
+        ps.iota = upload_vec(ctx, io.data(), N, COZK_SCALAR_U32, "vec_upload(iota)");
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+}
+
+// the 6 n_slots + 1 circuits as 25 (at 4 slots) cozk_fingerprint_leaves calls: what cozk_timestamp_range_leaves replaces
+void ts_proof_leaves_composed(WorkerEnv& env, const TsProofParty& ps, int ns, size_t N, const fe& gamma, const fe& tau, LeafBuf& lb) {
+    const fe g1 = Fr::add(gamma, Fr::one()), g2 = Fr::mul(gamma, gamma), ntau = Fr::neg(tau), w = Fr::sub(g2, tau);
+    auto C = [](const VecH& v, const fe& coeff) {
+        LeafTerm t;
+        t.col = v.h;
+        t.coeff = coeff;
+        return t;
+    };
+    for (int s = 0; s < ns; s++) {
+        const size_t u = (size_t)s;
+        std::vector<LeafTerm> rt = {C(ps.t_read[u], g1), C(ps.rc_rt[u], g2)};
+        std::vector<LeafTerm> gmr = {C(ps.iota, g1), C(ps.t_read[u], Fr::neg(g1)), C(ps.rc_gmr[u], g2)};
+        flow_fingerprint(env, rt, ntau, lb, (4 * u) * N, N);
+        flow_fingerprint(env, rt, w, lb, (4 * u + 1) * N, N);
+        flow_fingerprint(env, gmr, ntau, lb, (4 * u + 2) * N, N);
+        flow_fingerprint(env, gmr, w, lb, (4 * u + 3) * N, N);
+        flow_fingerprint(env, {C(ps.iota, g1), C(ps.fc_rt[u], g2)}, ntau, lb, (4 * (size_t)ns + 1 + 2 * u) * N, N);
+        flow_fingerprint(env, {C(ps.iota, g1), C(ps.fc_gmr[u], g2)}, ntau, lb, (4 * (size_t)ns + 2 + 2 * u) * N, N);
+    }
+    flow_fingerprint(env, {C(ps.iota, g1)}, ntau, lb, (4 * (size_t)ns) * N, N);
+    rc_check(cozk_ctx_synchronize(env.ctx), env.ctx, "synchronize");
+}
+
+void ts_proof_worker_main(cozk_ts_proof* h, TsProofParty& ps, StarNetWorker* star) {
+    const cozk_ts_proof_config& c = h->cfg;
+    const int ns = h->ns;
+    const size_t N = h->N, circuits = 6 * (size_t)ns + 1;
+    WorkerEnv env;
+    env.ctx = ps.ctx;
+    env.mode = COZK_MODE_PLAIN;
+    env.party = 0;
+    env.star = star;
+    env.ring = nullptr;
+    HIP_TRY(hipSetDevice(ps.ctx->device));
+    const std::vector<const cozk_vec*> cols = ts_proof_columns(ps);
+    double t0 = now_ms();
+    // ---- 1. commit (the U32 small-scalar path)
+    {
+        std::vector<uint64_t> xy(8 * cols.size());
+        std::vector<int> inf(cols.size());
+        rc_check(cozk_batch_msm_vec(ps.ctx, ps.setup->powers_all, 0, cols.data(), cols.size(), xy.data(), inf.data()), ps.ctx, "batch_msm_vec");
+        Writer w;
+        w.u64(cols.size());
+        for (size_t i = 0; i < cols.size(); i++) PST13Commitment{(uint64_t)c.log_n, abi_to_g1(xy.data() + 8 * i, inf[i])}.write(w);
+        star->send_response(w.b);
+    }
+    double t1 = now_ms();
+    ps.t_commit = t1 - t0;
+    // ---- 2, 3. gamma, tau; the leaves
+    fe gamma, tau;
+    {
+        Bytes req = star->receive_request();
+        Reader rd(req);
+        gamma = rd.fr();
+        tau = rd.fr();
+    }
+    double t2 = now_ms();
+    LeafBuf lb = flow_leaf_alloc(env, circuits * N);
+    if (c.leaves_fused) {
+        std::vector<const cozk_vec*> f[5];
+        const std::vector<VecH>* fam[5] = {&ps.t_read, &ps.rc_rt, &ps.rc_gmr, &ps.fc_rt, &ps.fc_gmr};
+        for (int k = 0; k < 5; k++)
+            for (const VecH& v : *fam[k]) f[k].push_back(v.h);
+        uint64_t g[4], t[4];
+        fe_to_u64x4(gamma, g);
+        fe_to_u64x4(tau, t);
+        rc_check(cozk_timestamp_range_leaves(env.ctx, f[0].data(), f[1].data(), f[2].data(), f[3].data(), f[4].data(), (size_t)ns, g, t, lb.a.h, 0), env.ctx,
+                 "timestamp_range_leaves");
+    } else {
+        ts_proof_leaves_composed(env, ps, ns, N, gamma, tau, lb);
+    }
+    double t3 = now_ms();
+    ps.t_leaves = t3 - t2;
+    // ---- 4. ONE dense batched grand product; its claimed outputs are the multiset hashes
+    Rep3BatchedDenseGrandProduct gp = Rep3BatchedDenseGrandProduct::construct(env, flow_leaves_to_layer(env, lb), circuits);
+    {
+        Writer w;
+        w.vec_fr(gp.claimed_outputs(env));
+        star->send_response(w.b);
+    }
+    std::vector<fe> r = gp.prove_grand_product_worker(env);
+    std::vector<fe> r_lo(r.begin() + ceil_log2(circuits), r.end());
+    double t4 = now_ms();
+    ps.t_gp = t4 - t3;
+    // ---- 5. the claims at r_lo, one exchange, the joint polynomial from the compact columns
+    Rep3ProverOpeningAccumulator acc;
+    {
+        std::vector<uint64_t> rr = to_abi(r_lo);
+        cozk_vec* chi = nullptr;
+        rc_check(cozk_eq_evals(env.ctx, rr.data(), (int)r_lo.size(), &chi), env.ctx, "eq_evals");
+        VecH chih(chi);
+        std::vector<uint64_t> ev(4 * cols.size());
+        rc_check(cozk_compact_batch_evaluate_at_chi(env.ctx, cols.data(), cols.size(), chih.h, ev.data()), env.ctx, "compact_batch_evaluate");
+        std::vector<fe> claims(cols.size());
+        for (size_t i = 0; i < cols.size(); i++) claims[i] = fe_from_u64x4(ev.data() + 4 * i);
+        if (c.tamper == 2) claims[0] = Fr::add(claims[0], Fr::one());
+        fe batched_claim;
+        std::vector<fe> rho_powers = Rep3ProverOpeningAccumulator::exchange_claims(env, claims, batched_claim);
+        std::vector<uint64_t> cf = to_abi(rho_powers);
+        cozk_vec* jv = nullptr;
+        rc_check(cozk_compact_linear_combination(env.ctx, cols.data(), cf.data(), cols.size(), &jv), env.ctx, "compact_linear_combination");
+        VecH jvh(jv);
+        acc.append_joint(env, plain_poly(env.ctx, jvh), chih.h, r_lo, batched_claim);
+    }
+    // ---- 6. one reduce_and_prove
+    acc.reduce_and_prove_worker(env, *ps.setup);
+    ps.t_open = now_ms() - t4;
+    ps.record_net(star);
+}
+
+void ts_proof_coordinate(cozk_ts_proof* h, StarNetCoordinator& net, TsProof& proof) {
+    Transcript tr("cozk-ts-range");
+    {
+        Bytes m = net.receive_response(0);
+        Reader rd(m);
+        const uint64_t k = rd.u64();
+        rd.need_elems(k, 72);
+        for (uint64_t i = 0; i < k; i++) {
+            PST13Commitment cm;
+            cm.nv = rd.u64();
+            cm.g_product = rd.g1();
+            proof.commitments.push_back(cm);
+            tr.append_point(cm.g_product);
+        }
+    }
+    flow_broadcast_gamma_tau(net, tr);
+    proof.hashes = gather_additive(net);
+    tr.append_scalars(proof.hashes);
+    fe claim;
+    std::vector<fe> r;
+    proof.gp = coordinate_prove_grand_product(net, tr, (size_t)h->cfg.log_n, claim, r);
+    proof.claims = Rep3ProverOpeningAccumulator::receive_claims(net, tr);
+    std::vector<fe> r_red;
+    fe rho, gamma;
+    proof.reduced = Rep3ProverOpeningAccumulator::reduce_and_prove(net, tr, r_red, rho, gamma);
+}
+
+// the plain verifier: replays the transcript; the first check that fails names itself in `why`
+bool ts_proof_verify(cozk_ts_proof* h, const TsProof& proof, std::string& why) {
+    const size_t ns = (size_t)h->ns, circuits = 6 * ns + 1, ncols = 5 * ns;
+    Transcript vt("cozk-ts-range");
+    if (proof.commitments.size() != ncols || proof.hashes.size() != circuits || proof.claims.size() != ncols) {
+        why = "shape: commitments, hashes or claims";
+        return false;
+    }
+    for (auto& cm : proof.commitments) vt.append_point(cm.g_product);
+    const fe gamma = vt.challenge_scalar(), tau = vt.challenge_scalar();
+    const fe g1 = Fr::add(gamma, Fr::one()), g2 = Fr::mul(gamma, gamma);
+    vt.append_scalars(proof.hashes);
+    const std::vector<fe>& hs = proof.hashes;
+    for (size_t s = 0; s < ns; s++)
+        for (size_t kind = 0; kind < 2; kind++)
+            if (!Fr::eq(Fr::mul(hs[4 * ns], hs[4 * s + 2 * kind + 1]), Fr::mul(hs[4 * s + 2 * kind], hs[4 * ns + 1 + 2 * s + kind]))) {
+                why = "multiset equality: init * write != read * final (slot " + std::to_string(s) + (kind ? ", global minus read)" : ", read timestamp)");
+                return false;
+            }
+    fe claim;
+    std::vector<fe> r;
+    if (!flow_vec_eq(proof.gp.outputs, proof.hashes) || !verify_grand_product(proof.gp, vt, claim, r) || r.size() != (size_t)ceil_log2(circuits) + (size_t)h->cfg.log_n) {
+        why = "grand product: the hashes are not its outputs, or a round or a layer reduction does not hold";
+        return false;
+    }
+    const int k = ceil_log2(circuits);
+    std::vector<fe> hi(r.begin(), r.begin() + k), lo(r.begin() + k, r.end());
+    const std::vector<fe>& cl = proof.claims;
+    const fe iota = flow_iota_eval(lo), init = Fr::sub(Fr::mul(iota, g1), tau);
+    std::vector<fe> leaves(circuits);
+    for (size_t s = 0; s < ns; s++) {
+        const fe &rc_rt = cl[s], &rc_gmr = cl[ns + s], &fc_rt = cl[2 * ns + s], &fc_gmr = cl[3 * ns + s], &t_read = cl[4 * ns + s];
+        const fe xg = Fr::mul(t_read, g1);
+        leaves[4 * s] = Fr::add(Fr::sub(xg, tau), Fr::mul(rc_rt, g2));
+        leaves[4 * s + 1] = Fr::add(leaves[4 * s], g2);
+        leaves[4 * s + 2] = Fr::add(Fr::sub(init, xg), Fr::mul(rc_gmr, g2));
+        leaves[4 * s + 3] = Fr::add(leaves[4 * s + 2], g2);
+        leaves[4 * ns + 1 + 2 * s] = Fr::add(init, Fr::mul(fc_rt, g2));
+        leaves[4 * ns + 2 + 2 * s] = Fr::add(init, Fr::mul(fc_gmr, g2));
+    }
+    leaves[4 * ns] = init;
+    if (!Fr::eq(flow_batch_eval(leaves, hi, Fr::zero()), claim)) {
+        why = "leaf claim: the fingerprints of the claims != the grand product's final claim";
+        return false;
+    }
+    VerifierOpening o;
+    o.point = lo;
+    for (size_t i = 0; i < ncols; i++) o.polys.push_back(i);
+    o.claims = cl;
+    o.rho = vt.challenge_scalar();
+    std::string inner;
+    if (!verify_reduced_opening({o}, proof.commitments, vt, proof.reduced, *h->parties[0].setup, "reduction sumcheck: shape", "reduction sumcheck: final check", inner)) {
+        why = "opening: " + inner;
+        return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cozk_ts_proof_create(const cozk_ts_proof_config* cfg, cozk_ts_proof** out) {
+    return harness_create(cfg, out, [&](cozk_ts_proof* h) {
+        COZK_REQUIRE(cfg->mode == COZK_MODE_PLAIN, "ts_proof: the proof is party 0's public one: mode is COZK_MODE_PLAIN");
+        COZK_REQUIRE(cfg->log_n >= 1 && cfg->log_n <= 22, "ts_proof: log_n in 1..22");
+        COZK_REQUIRE(cfg->log_mem >= 5 && cfg->log_mem <= 24, "ts_proof: log_mem in 5..24");
+        COZK_REQUIRE(cfg->n_slots >= 1 && cfg->n_slots <= 4, "ts_proof: n_slots in 1..4");
+        COZK_REQUIRE(cfg->tamper >= 0 && cfg->tamper <= 2 && (cfg->leaves_fused == 0 || cfg->leaves_fused == 1), "ts_proof: tamper in 0..2, leaves_fused 0 or 1");
+        h->N = (size_t)1 << cfg->log_n;
+        h->ns = cfg->n_slots;
+        h->parties.resize(1);
+        TsProofParty& ps = h->parties[0];
+        ps.party = 0;
+        ps.open_ctx(cfg->device, "ts_proof: cannot create a context (no HIP device?)");
+        ts_proof_setup(h, ps);
+    });
+}
+
+const char* cozk_ts_proof_error(const cozk_ts_proof* h) { return harness_error(h); }
+
+int cozk_ts_proof_destroy(cozk_ts_proof* h) {
+    if (!h) return COZK_OK;
+    release_parties(h->parties, [](TsProofParty& ps) {
+        for (std::vector<VecH>* fam : {&ps.t_read, &ps.rc_rt, &ps.rc_gmr, &ps.fc_rt, &ps.fc_gmr}) fam->clear();
+        ps.iota = VecH();
+        ps.setup.reset();
+    });
+    delete h;
+    return COZK_OK;
+}
+
+int cozk_ts_proof_prove(cozk_ts_proof* h, int verify, cozk_ts_proof_result* res) {
+    if (!h || !res) return COZK_ERR_INVALID_ARG;
+    memset(res, 0, sizeof *res);
+    res->verified = -1;
+    if (h->parties.empty() || !h->parties[0].setup) return COZK_ERR_INVALID_ARG;  // create failed
+    InProcNets nets(1);
+    std::vector<Participant> parts;
+    add_participants(parts, "party", h->parties, [&](TsProofParty& ps, int) { ts_proof_worker_main(h, ps, nets.worker(0)); });
+    TsProof proof;
+    double wall_ms = 0;
+    int rc = run_in_process(nets, parts, [&] {
+        InProcStarCoordinator coord(&nets.star);
+        ts_proof_coordinate(h, coord, proof);
+    }, h->error, wall_ms);
+    if (rc != COZK_OK) return rc;
+    res->wall_ms = wall_ms;  // the verifier below is outside the clock
+    if (verify) {
+        std::string why;
+        try {
+            HIP_TRY(hipSetDevice(h->parties[0].ctx->device));
+            res->verified = ts_proof_verify(h, proof, why) ? 1 : 0;
+        } catch (const std::exception& e) {
+            why = e.what();
+            res->verified = 0;
+        }
+        if (res->verified == 0) h->error = "verification failed: " + why;
+    }
+    const TsProofParty& ps = h->parties[0];
+    res->t_witness_ms = h->t_witness;
+    res->t_commit_ms = ps.t_commit;
+    res->t_leaves_ms = ps.t_leaves;
+    res->t_gp_ms = ps.t_gp;
+    res->t_open_ms = ps.t_open;
+    finish_proof(h, proof.serialize(), res);
+    return COZK_OK;
+}
+
+int cozk_ts_proof_proof_bytes(const cozk_ts_proof* h, uint8_t* out, size_t cap) { return harness_proof_bytes(h, out, cap); }
+
+}  // extern "C"

@@ -2,6 +2,8 @@
 // witness (cozk_timestamp_range_witness; jolt-core's TimestampRangeCheckPolynomials::generate_witness, whose four families
 // co-jolt/src/jolt/vm/jolt/witness.rs:384-409 shares as public vectors).  jolt-core is not in the reference tree: the recurrence is
 // restated from upstream knowledge (parity unpinned); the field names and the multiset identity of the memory checking pin it.
+// cozk_timestamp_range_leaves, at the end of this file, turns those families and t_read into the leaves of the range check's
+// grand-product circuits in one launch (k_ts_range_leaves).
 // For one column of keys key[0..n) over a table of M entries:
 //
 //   read_cts[j]  = #{ j' < j : key[j'] = key[j] }      (TIME order)
@@ -324,7 +326,90 @@ static int ts_counters(cozk_ctx* ctx, int ts, const std::vector<const cozk_vec*>
     return rc;
 }
 
+// The leaves of the range check's 6 n_slots + 1 grand-product circuits (cozk_timestamp_range_leaves; the layout is in cozk.h).  A
+// thread makes the six leaves of one (slot, step) and, for slot 0, the init leaf: six products of a 32-bit integer with a constant
+// (g1r = (gamma + 1) R and g2r = gamma^2 R, Montgomery forms lifted once more, so that the product with a plain integer is a
+// Montgomery form), the rest additions.  The keys t_read and j - t_read and the step number j exist only in registers.
+struct TsLeafCols {
+    const uint32_t *t_read[COZK_RW_MEMORY_MAX_SLOTS], *rc_rt[COZK_RW_MEMORY_MAX_SLOTS], *rc_gmr[COZK_RW_MEMORY_MAX_SLOTS], *fc_rt[COZK_RW_MEMORY_MAX_SLOTS],
+        *fc_gmr[COZK_RW_MEMORY_MAX_SLOTS];
+};
+__device__ __forceinline__ fe ts_small(uint32_t v) {
+    fe x = Fr::zero();
+    x.l[0] = v;
+    return x;
+}
+__global__ void __launch_bounds__(TS_PT) k_ts_range_leaves(TsLeafCols a, uint32_t n_slots, size_t n, fe g1r, fe g2r, fe g2, fe tau, fe* __restrict__ out,
+                                                           unsigned long long* __restrict__ viol) {
+    const size_t j = (size_t)blockIdx.x * TS_PT + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t s = blockIdx.y;
+    uint32_t x = a.t_read[s][j];
+    if (x > (uint32_t)j) {
+        atomicMin(viol, ((unsigned long long)j << 32) | s);
+        x = 0;
+    }
+    const fe init = Fr::sub(Fr::mul(g1r, ts_small((uint32_t)j)), tau);  // h(j, 0)
+    const fe xg = Fr::mul(g1r, ts_small(x));
+    const fe rt = Fr::add(Fr::sub(xg, tau), Fr::mul(g2r, ts_small(a.rc_rt[s][j])));
+    const fe gmr = Fr::add(Fr::sub(init, xg), Fr::mul(g2r, ts_small(a.rc_gmr[s][j])));  // (j - x)(gamma + 1) = j (gamma + 1) - x (gamma + 1)
+    fe* o = out + j;
+    fe_store(o + (size_t)(4 * s) * n, rt);
+    fe_store(o + (size_t)(4 * s + 1) * n, Fr::add(rt, g2));
+    fe_store(o + (size_t)(4 * s + 2) * n, gmr);
+    fe_store(o + (size_t)(4 * s + 3) * n, Fr::add(gmr, g2));
+    if (s == 0) fe_store(o + (size_t)(4 * n_slots) * n, init);
+    fe_store(o + (size_t)(4 * n_slots + 1 + 2 * s) * n, Fr::add(init, Fr::mul(g2r, ts_small(a.fc_rt[s][j]))));
+    fe_store(o + (size_t)(4 * n_slots + 2 + 2 * s) * n, Fr::add(init, Fr::mul(g2r, ts_small(a.fc_gmr[s][j]))));
+}
+
 extern "C" {
+
+int cozk_timestamp_range_leaves(cozk_ctx* ctx, const cozk_vec* const* t_read, const cozk_vec* const* rc_rt, const cozk_vec* const* rc_gmr,
+                                const cozk_vec* const* fc_rt, const cozk_vec* const* fc_gmr, size_t n_slots, const uint64_t gamma[4],
+                                const uint64_t tau[4], cozk_vec* out, size_t offset) {
+    void* d_viol = nullptr;
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && t_read && rc_rt && rc_gmr && fc_rt && fc_gmr && gamma && tau && out, "timestamp_range_leaves: bad argument");
+        COZK_REQUIRE(n_slots >= 1 && n_slots <= COZK_RW_MEMORY_MAX_SLOTS, "timestamp_range_leaves: 1 <= n_slots <= 8");
+        TsLeafCols h{};
+        const cozk_vec* const* fam[5] = {t_read, rc_rt, rc_gmr, fc_rt, fc_gmr};
+        const uint32_t** dst[5] = {h.t_read, h.rc_rt, h.rc_gmr, h.fc_rt, h.fc_gmr};
+        for (int f = 0; f < 5; f++)
+            for (size_t s = 0; s < n_slots; s++) {
+                const cozk_vec* v = fam[f][s];
+                COZK_REQUIRE(v && v->kind == COZK_SCALAR_U32, "timestamp_range_leaves: every column is a U32 vector");
+                COZK_REQUIRE(v->n == t_read[0]->n, "timestamp_range_leaves: every column has n entries (the table is as long as the trace: M == n)");
+                dst[f][s] = (const uint32_t*)v->d;
+            }
+        const size_t n = t_read[0]->n;
+        COZK_REQUIRE(n >= 1 && n < ((size_t)1 << 32), "timestamp_range_leaves: 1 <= n < 2^32");
+        COZK_REQUIRE(out->kind == COZK_SCALAR_FR && offset <= out->n && (out->n - offset) / (6 * n_slots + 1) >= n,
+                     "timestamp_range_leaves: out is an FR vector with room for (6 n_slots + 1) n entries from offset");
+        fe g, t;
+        for (int i = 0; i < 4; i++) {
+            g.l[2 * i] = (uint32_t)gamma[i], g.l[2 * i + 1] = (uint32_t)(gamma[i] >> 32);
+            t.l[2 * i] = (uint32_t)tau[i], t.l[2 * i + 1] = (uint32_t)(tau[i] >> 32);
+        }
+        const fe g2 = Fr::mul(g, g);
+        d_viol = ctx_dev_alloc(ctx, sizeof(unsigned long long));
+        unsigned long long* pin = (unsigned long long*)ctx_pinned(ctx, sizeof(unsigned long long));
+        hipStream_t st = ctx->stream;
+        HIP_TRY(hipMemsetAsync(d_viol, 0xff, sizeof(unsigned long long), st));
+        k_ts_range_leaves<<<dim3((unsigned)((n + TS_PT - 1) / TS_PT), (unsigned)n_slots), TS_PT, 0, st>>>(
+            h, (uint32_t)n_slots, n, Fr::to_mont(Fr::add(g, Fr::one())), Fr::to_mont(g2), g2, t, (fe*)out->d + offset, (unsigned long long*)d_viol);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(pin, d_viol, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (*pin != ~0ull) {
+            char buf[160];
+            snprintf(buf, sizeof buf, "timestamp_range_leaves: step %llu, slot %llu: t_read is greater than the step", *pin >> 32, *pin & 0xffffffffull);
+            throw CozkError(COZK_ERR_INVALID_ARG, buf);
+        }
+    });
+    ctx_dev_free(ctx, d_viol);
+    return rc;
+}
 
 int cozk_time_counters(cozk_ctx* ctx, const cozk_vec* const* keys, size_t n_cols, size_t M, cozk_vec** read_cts, cozk_vec** final_cts) {
     if (!read_cts || !final_cts) return COZK_ERR_INVALID_ARG;

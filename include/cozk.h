@@ -1760,6 +1760,91 @@ int cozk_timestamp_range_witness(cozk_ctx* ctx, const cozk_vec* const* t_read, s
                                  cozk_vec** read_cts_global_minus_read, cozk_vec** final_cts_read_timestamp,
                                  cozk_vec** final_cts_global_minus_read);
 
+/* ---- The timestamp range-check proof's device calls (TimestampValidityProof::prove, which party 0 alone runs over public data after
+ * the output check, co-jolt/src/jolt/vm/read_write_memory/worker.rs:78-105).  Every polynomial of that proof is a public column of
+ * 32-bit integers, so its openings and its leaves are made from the compact columns and no Fr copy of a column exists.  jolt-core is
+ * not in the reference tree: the circuit order below is this project's (parity unpinned).  cozk_ts_proof_* below is the proof.
+ *
+ * cozk_compact_batch_evaluate_at_chi: out[c] (4 x u64, Montgomery) = sum_i chi[i] * cols[c][i] for 1 <= k <= COZK_COMPACT_MAX_COLS
+ * columns of kind U8 / U16 / U32 / U64 (mixed freely), all of one length 1 <= n < 2^32, n <= chi->n, chi an FR vector.  chi is read
+ * once per 8 columns (a workgroup row), not once per column or pair.  Bit for bit what cozk_poly_batch_evaluate_at_chi returns for PLAIN Fr polynomials of the same values.
+ * cozk_compact_linear_combination: *out_vec = a NEW FR vector, out[i] = sum_c coeffs[c] * cols[c][i]; coeffs: k x 4 u64 (Montgomery);
+ * the same kinds and limits.  Bit for bit cozk_poly_linear_combination (PLAIN) on the same values.
+ * Both: a wrong kind, columns of unequal length, k out of range or a chi that is too short is refused with COZK_ERR_INVALID_ARG and
+ * a text of its own before any launch, and the context works on.  The sums are exact integers reduced once (a Montgomery-form
+ * operand times a plain integer is a Montgomery form); an accumulator holds 2^32 terms, which n < 2^32 keeps out of reach.
+ *
+ * cozk_timestamp_range_leaves: the leaves of the 6 n_slots + 1 grand-product circuits of the range check in one launch, from the
+ * t_read columns and the four counter families of cozk_timestamp_range_witness with M == n (every column U32[n], 1 <= n < 2^32,
+ * 1 <= n_slots <= COZK_RW_MEMORY_MAX_SLOTS).  With h(key, count) = count gamma^2 + key (gamma + 1) - tau, the tuple (key, key, count)
+ * under a + v gamma + t gamma^2 - tau, circuit c is out[offset + c n + j] (FR, room for (6 n_slots + 1) n entries from offset;
+ * cozk_layer_create adopts it):
+ *   4 s + 0: h(t_read[s][j], rc_rt[s][j])          4 s + 1: circuit 4 s + 0 plus gamma^2
+ *   4 s + 2: h(j - t_read[s][j], rc_gmr[s][j])     4 s + 3: circuit 4 s + 2 plus gamma^2
+ *   4 n_slots: init, h(j, 0)
+ *   4 n_slots + 1 + 2 s: init plus fc_rt[s][j] gamma^2        4 n_slots + 2 + 2 s: init plus fc_gmr[s][j] gamma^2
+ * No iota column and no key column is stored.  gamma, tau: 4 x u64 (Montgomery).  Every leaf is bit for bit what the composition of
+ * cozk_fingerprint_leaves calls gives.  t_read[s][j] > j: COZK_ERR_INVALID_ARG, cozk_last_error names the smallest (step, slot);
+ * such an entry is used as 0 and nothing is read out of bounds.  Returns after the device has finished. */
+#define COZK_COMPACT_MAX_COLS 24
+int cozk_compact_batch_evaluate_at_chi(cozk_ctx* ctx, const cozk_vec* const* cols, size_t k, const cozk_vec* chi, uint64_t* out);
+int cozk_compact_linear_combination(cozk_ctx* ctx, const cozk_vec* const* cols, const uint64_t* coeffs, size_t k, cozk_vec** out_vec);
+int cozk_timestamp_range_leaves(cozk_ctx* ctx, const cozk_vec* const* t_read, const cozk_vec* const* rc_rt, const cozk_vec* const* rc_gmr,
+                                const cozk_vec* const* fc_rt, const cozk_vec* const* fc_gmr, size_t n_slots, const uint64_t gamma[4],
+                                const uint64_t tau[4], cozk_vec* out, size_t offset);
+
+/* ---- The timestamp range-check proof itself, as an in-process harness (csrc/host/ts_range_proof.hpp; modelled on cozk_lookups and
+ * cozk_outer_harness): party 0's public proof that every t_read[s][j] and every j - t_read[s][j] lies in [0, N), a Lasso memory check
+ * over an identity table of N entries with ONE batched dense grand product and ONE batched opening.  PLAIN only.  jolt-core is not in
+ * the reference tree: the circuit order, the transcript order and the proof bytes are this project's (parity unpinned); what pins them
+ * is the plain verifier below and the Python restatement tests/ts_proof_ref.py.  The chained flow does not call this proof (its
+ * t_read are seeded streams, which the witness call refuses).
+ * create: a Jolt-shaped trace from `seed` (tests/rw_witness_ref.py jolt_instance(seed, N, 2^log_mem, n_regs = 32): rs1, rs2 read, rd
+ * writes every step, ram writes where flagged), cozk_rw_memory_witness and cozk_timestamp_range_witness(M = N) on the device; the
+ * first n_slots slots' t_read and their 4 n_slots counter columns stay compact U32 vectors, no Fr copy of a column is made; the SRS
+ * as the other harnesses build it.
+ * prove (worker on the device, coordinator and verifier on the calling thread, transcript "cozk-ts-range"):
+ *   1. commit the 5 n_slots columns (cozk_batch_msm_vec, the U32 path): rc_rt[0..], rc_gmr[0..], fc_rt[0..], fc_gmr[0..], t_read[0..];
+ *      the commitments go into the transcript      2. gamma, tau      3. the leaves (cozk_timestamp_range_leaves, or with
+ *      leaves_fused = 0 the composition of cozk_fingerprint_leaves calls: the same bytes)
+ *   4. the claimed outputs (the multiset hashes) into the transcript, then one dense batched grand product over the 6 n_slots + 1
+ *      circuits; its point is r = (r_hi, r_lo), r_hi over the circuits padded to a power of two
+ *   5. the 5 n_slots claims at r_lo (cozk_eq_evals + cozk_compact_batch_evaluate_at_chi), one claim exchange (rho), the joint
+ *      polynomial by cozk_compact_linear_combination over the rho powers, appended as one opening
+ *   6. reduce_and_prove over that one opening: one PST13 opening.
+ * Proof bytes: commitments (count, then nv and point each), hashes, grand-product proof, claims, reduced opening proof.
+ * The verifier replays the transcript and checks, each with a reason of its own in cozk_ts_proof_error:
+ *   "multiset equality"  hash[init] * hash[write] == hash[read] * hash[final] for every slot and both kinds
+ *   "grand product"      verify_grand_product, and the hashes are its outputs
+ *   "leaf claim"         the final claim == the batched evaluation of the 6 n_slots + 1 leaf values rebuilt from the claims, the
+ *                        init term being iota(r_lo) (gamma + 1) - tau, missing circuits padded with zero
+ *   "opening"            the reduced opening against the rho-combined commitments
+ * tamper (tests): 1 adds 1 to fc_rt[0][t_read[0][N / 2]] before the commit -- every other relation holds, only the multiset check
+ * can reject; 2 makes the worker send claim 0 plus one -- the leaf check rejects. */
+typedef struct cozk_ts_proof cozk_ts_proof;
+typedef struct cozk_ts_proof_config {
+    int mode;         /* COZK_MODE_PLAIN; anything else is refused */
+    int device;
+    int log_n;        /* trace length N = 2^log_n, 1..22 */
+    int log_mem;      /* memory of 2^log_mem words, 5..24 (32 registers alias its low words) */
+    int n_slots;      /* 1..4: the first n_slots of rs1, rs2, rd, ram (Jolt: 4) */
+    uint64_t seed;
+    int precompute;   /* the SRS window table (cozk_bases_upload) */
+    int leaves_fused; /* 1: cozk_timestamp_range_leaves; 0: the composition of cozk_fingerprint_leaves (kept for the A/B) */
+    int tamper;       /* 0, 1, 2: see above */
+} cozk_ts_proof_config;
+typedef struct cozk_ts_proof_result {
+    int verified; /* 1 ok, 0 rejected, -1 not run */
+    double wall_ms, t_witness_ms, t_commit_ms, t_leaves_ms, t_gp_ms, t_open_ms;
+    uint64_t proof_len;
+    uint8_t proof_digest[32];
+} cozk_ts_proof_result;
+int cozk_ts_proof_create(const cozk_ts_proof_config* cfg, cozk_ts_proof** out);
+const char* cozk_ts_proof_error(const cozk_ts_proof* h);
+int cozk_ts_proof_destroy(cozk_ts_proof* h);
+int cozk_ts_proof_prove(cozk_ts_proof* h, int verify, cozk_ts_proof_result* res);
+int cozk_ts_proof_proof_bytes(const cozk_ts_proof* h, uint8_t* out, size_t cap);
+
 /* ---- ONE chained co-jolt worker flow (JoltRep3Prover::prove, co-jolt/src/jolt/vm/jolt/worker.rs:175-266, against its coordinator
  * jolt/vm/jolt/coordinator.rs:118-222): commit-all -> bytecode memory checking -> instruction lookups (primary sumcheck, toggled
  * read / write + dense init / final grand products) -> read-write memory checking + output check -> Spartan (outer + inner + shift) ->
