@@ -27,6 +27,8 @@ from .ts_range import time_counters, timestamp_range_witness, TS_RANGE_SYMBOLS
 from . import ts_proof
 from .ts_proof import (compact_batch_evaluate_at_chi, compact_linear_combination, timestamp_range_leaves, TS_PROOF_SYMBOLS, TsProof,
                        TsProofConfig, TsProofResult)
+from . import rw_proof
+from .rw_proof import rw_memory_leaves, rw_memory_init_final_leaves, RW_PROOF_SYMBOLS, RwProof, RwProofConfig, RwProofResult
 from . import shamir_spartan
 from .shamir_spartan import SpartanGroup, ShamirSpartanHarness, ShamirSpartanConfig, ShamirSpartanResult
 from . import shamir_jolt_spartan

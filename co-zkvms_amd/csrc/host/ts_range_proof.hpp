@@ -26,21 +26,41 @@ struct cozk_ts_proof : HarnessHandle {
 
 namespace {
 
-struct TsProof {
-    std::vector<PST13Commitment> commitments;
+// what the range check itself adds to a proof (steps 2-5): cozk_rw_proof chains it behind the memory check
+struct TsRangeProof {
     std::vector<fe> hashes;
     GrandProductProof gp;
     std::vector<fe> claims;
+    void write(Writer& w) const {
+        w.vec_fr(hashes);
+        gp.write(w);
+        w.vec_fr(claims);
+    }
+};
+
+struct TsProof {
+    std::vector<PST13Commitment> commitments;
+    TsRangeProof range;
     ReducedOpeningProof reduced;
     Bytes serialize() const {
         Writer w;
         w.u64(commitments.size());
         for (auto& c : commitments) c.write(w);
-        w.vec_fr(hashes);
-        gp.write(w);
-        w.vec_fr(claims);
+        range.write(w);
         reduced.write(w);
         return w.b;
+    }
+};
+
+// the range check's columns as the steps below take them: n_slots U32[N] handles per family; iota only for the composed leaves
+struct TsRangeCols {
+    std::vector<const cozk_vec*> t_read, rc_rt, rc_gmr, fc_rt, fc_gmr;
+    const cozk_vec* iota = nullptr;
+    // the order of the claims (and of cozk_ts_proof's commitments): family-major, then t_read
+    std::vector<const cozk_vec*> columns() const {
+        std::vector<const cozk_vec*> cols;
+        for (const std::vector<const cozk_vec*>* fam : {&rc_rt, &rc_gmr, &fc_rt, &fc_gmr, &t_read}) cols.insert(cols.end(), fam->begin(), fam->end());
+        return cols;
     }
 };
 
@@ -56,12 +76,50 @@ struct TsSplitMix {
     }
 };
 
-// the committed columns in the proof's order: family-major, then t_read
-std::vector<const cozk_vec*> ts_proof_columns(const TsProofParty& ps) {
-    std::vector<const cozk_vec*> cols;
-    for (const std::vector<VecH>* fam : {&ps.rc_rt, &ps.rc_gmr, &ps.fc_rt, &ps.fc_gmr, &ps.t_read})
-        for (const VecH& v : *fam) cols.push_back(v.h);
-    return cols;
+// P: a party that holds the five families as std::vector<VecH> (TsProofParty, RwProofParty)
+template <class P>
+TsRangeCols ts_range_columns(const P& ps, const VecH& iota) {
+    TsRangeCols c;
+    const std::vector<VecH>* fam[5] = {&ps.t_read, &ps.rc_rt, &ps.rc_gmr, &ps.fc_rt, &ps.fc_gmr};
+    std::vector<const cozk_vec*>* dst[5] = {&c.t_read, &c.rc_rt, &c.rc_gmr, &c.fc_rt, &c.fc_gmr};
+    for (int k = 0; k < 5; k++)
+        for (const VecH& v : *fam[k]) dst[k]->push_back(v.h);
+    c.iota = iota.h;
+    return c;
+}
+
+// tests/rw_witness_ref.py's jolt_instance(seed, N, MEM, store_pct = 30, n_regs = 32): the addresses of rs1, rs2, rd, ram, the written values
+// of rd and ram, ram's store flags and v_init
+struct TsTrace {
+    std::vector<std::vector<uint32_t>> addr, vw;
+    std::vector<uint8_t> iw;
+    std::vector<uint32_t> v_init;
+};
+TsTrace ts_trace(uint64_t seed, size_t N, size_t MEM) {
+    TsTrace t;
+    t.addr.assign(4, std::vector<uint32_t>(N));
+    t.vw.assign(2, std::vector<uint32_t>(N));
+    t.iw.resize(N);
+    t.v_init.resize(MEM);
+    TsSplitMix rng{seed};
+    const uint64_t n_regs = MEM < 32 ? MEM : 32;
+    for (int s = 0; s < 3; s++)
+        for (size_t j = 0; j < N; j++) t.addr[(size_t)s][j] = (uint32_t)(rng.next() % n_regs);
+    for (size_t j = 0; j < N; j++) t.addr[3][j] = (uint32_t)(rng.next() % MEM);
+    for (int k = 0; k < 2; k++)
+        for (size_t j = 0; j < N; j++) t.vw[(size_t)k][j] = (uint32_t)rng.next();
+    for (size_t j = 0; j < N; j++) t.iw[j] = rng.next() % 100 < 30 ? 1 : 0;
+    for (size_t a = 0; a < MEM; a++) t.v_init[a] = (uint32_t)rng.next();
+    return t;
+}
+
+// tamper 1: one final counter of the read-timestamp family of slot 0 is bumped: every relation but the multiset's holds
+void ts_tamper_final_counter(cozk_ctx* ctx, const VecH& t_read0, VecH& fc_rt0, size_t N) {
+    std::vector<uint32_t> tr0(N), fc(N);
+    rc_check(cozk_vec_download(ctx, t_read0.h, tr0.data()), ctx, "vec_download");
+    rc_check(cozk_vec_download(ctx, fc_rt0.h, fc.data()), ctx, "vec_download");
+    fc[tr0[N / 2]] += 1;
+    fc_rt0 = upload_vec(ctx, fc.data(), N, COZK_SCALAR_U32, "vec_upload(tampered counters)");
 }
 
 // create: tests/rw_witness_ref.py's jolt_instance(seed, N, MEM, store_pct = 30, n_regs = 32), both witness walks on the device
@@ -73,24 +131,13 @@ void ts_proof_setup(cozk_ts_proof* h, TsProofParty& ps) {
     std::vector<fe> t((size_t)c.log_n);
     for (int i = 0; i < c.log_n; i++) t[(size_t)i] = synthetic_fr_host(c.seed ^ 0x7A7A7A7Aull, (uint64_t)i);
     ps.setup = PST13::setup(ctx, t, c.precompute);
-    TsSplitMix rng{c.seed};
-    const uint64_t n_regs = MEM < 32 ? MEM : 32;
-    std::vector<std::vector<uint32_t>> addr(4, std::vector<uint32_t>(N)), vw(2, std::vector<uint32_t>(N));
-    std::vector<uint8_t> iw(N);
-    std::vector<uint32_t> v_init(MEM);
-    for (int s = 0; s < 3; s++)
-        for (size_t j = 0; j < N; j++) addr[(size_t)s][j] = (uint32_t)(rng.next() % n_regs);
-    for (size_t j = 0; j < N; j++) addr[3][j] = (uint32_t)(rng.next() % MEM);
-    for (int k = 0; k < 2; k++)
-        for (size_t j = 0; j < N; j++) vw[(size_t)k][j] = (uint32_t)rng.next();
-    for (size_t j = 0; j < N; j++) iw[j] = rng.next() % 100 < 30 ? 1 : 0;
-    for (size_t a = 0; a < MEM; a++) v_init[a] = (uint32_t)rng.next();
+    const TsTrace trace = ts_trace(c.seed, N, MEM);
     double t0 = now_ms();
     std::vector<VecH> d_addr, d_vw;
-    for (int s = 0; s < 4; s++) d_addr.push_back(upload_vec(ctx, addr[(size_t)s].data(), N, COZK_SCALAR_U32, "vec_upload(addresses)"));
-    for (int k = 0; k < 2; k++) d_vw.push_back(upload_vec(ctx, vw[(size_t)k].data(), N, COZK_SCALAR_U32, "vec_upload(written values)"));
-    VecH d_iw = upload_vec(ctx, iw.data(), N, COZK_SCALAR_U8, "vec_upload(store flags)");
-    VecH d_init = upload_vec(ctx, v_init.data(), MEM, COZK_SCALAR_U32, "vec_upload(v_init)");
+    for (int s = 0; s < 4; s++) d_addr.push_back(upload_vec(ctx, trace.addr[(size_t)s].data(), N, COZK_SCALAR_U32, "vec_upload(addresses)"));
+    for (int k = 0; k < 2; k++) d_vw.push_back(upload_vec(ctx, trace.vw[(size_t)k].data(), N, COZK_SCALAR_U32, "vec_upload(written values)"));
+    VecH d_iw = upload_vec(ctx, trace.iw.data(), N, COZK_SCALAR_U8, "vec_upload(store flags)");
+    VecH d_init = upload_vec(ctx, trace.v_init.data(), MEM, COZK_SCALAR_U32, "vec_upload(v_init)");
     const cozk_vec* pa[4] = {d_addr[0].h, d_addr[1].h, d_addr[2].h, d_addr[3].h};
     const cozk_vec* pw[4] = {nullptr, nullptr, d_vw[0].h, d_vw[1].h};
     const cozk_vec* pf[4] = {nullptr, nullptr, nullptr, d_iw.h};
@@ -115,13 +162,7 @@ void ts_proof_setup(cozk_ts_proof* h, TsProofParty& ps) {
         ps.fc_gmr.push_back(VecH(d[s]));
     }
     h->t_witness = now_ms() - t0;
-    if (c.tamper == 1) {  // one final counter of the read-timestamp family of slot 0 is bumped: every relation but the multiset's holds
-        std::vector<uint32_t> tr0(N), fc(N);
-        rc_check(cozk_vec_download(ctx, ps.t_read[0].h, tr0.data()), ctx, "vec_download");
-        rc_check(cozk_vec_download(ctx, ps.fc_rt[0].h, fc.data()), ctx, "vec_download");
-        fc[tr0[N / 2]] += 1;
-        ps.fc_rt[0] = upload_vec(ctx, fc.data(), N, COZK_SCALAR_U32, "vec_upload(tampered counters)");
-    }
+    if (c.tamper == 1) ts_tamper_final_counter(ctx, ps.t_read[0], ps.fc_rt[0], N);
     if (!c.leaves_fused) {
         std::vector<uint32_t> io(N);
         for (size_t j = 0; j < N; j++) io[j] = (uint32_t)j;
@@ -131,11 +172,11 @@ void ts_proof_setup(cozk_ts_proof* h, TsProofParty& ps) {
 }
 
 // the 6 n_slots + 1 circuits as 25 (at 4 slots) cozk_fingerprint_leaves calls: what cozk_timestamp_range_leaves replaces
-void ts_proof_leaves_composed(WorkerEnv& env, const TsProofParty& ps, int ns, size_t N, const fe& gamma, const fe& tau, LeafBuf& lb) {
+void ts_proof_leaves_composed(WorkerEnv& env, const TsRangeCols& ps, int ns, size_t N, const fe& gamma, const fe& tau, LeafBuf& lb) {
     const fe g1 = Fr::add(gamma, Fr::one()), g2 = Fr::mul(gamma, gamma), ntau = Fr::neg(tau), w = Fr::sub(g2, tau);
-    auto C = [](const VecH& v, const fe& coeff) {
+    auto C = [](const cozk_vec* v, const fe& coeff) {
         LeafTerm t;
-        t.col = v.h;
+        t.col = v;
         t.coeff = coeff;
         return t;
     };
@@ -154,10 +195,74 @@ void ts_proof_leaves_composed(WorkerEnv& env, const TsProofParty& ps, int ns, si
     rc_check(cozk_ctx_synchronize(env.ctx), env.ctx, "synchronize");
 }
 
+// one opening of compact columns of one length at `point`: the claims, one exchange, the joint polynomial over the rho powers
+void compact_open_worker(WorkerEnv& env, Rep3ProverOpeningAccumulator& acc, const std::vector<const cozk_vec*>& cols, const std::vector<fe>& point, bool tamper_claim) {
+    std::vector<uint64_t> rr = to_abi(point);
+    cozk_vec* chi = nullptr;
+    rc_check(cozk_eq_evals(env.ctx, rr.data(), (int)point.size(), &chi), env.ctx, "eq_evals");
+    VecH chih(chi);
+    std::vector<uint64_t> ev(4 * cols.size());
+    rc_check(cozk_compact_batch_evaluate_at_chi(env.ctx, cols.data(), cols.size(), chih.h, ev.data()), env.ctx, "compact_batch_evaluate");
+    std::vector<fe> claims(cols.size());
+    for (size_t i = 0; i < cols.size(); i++) claims[i] = fe_from_u64x4(ev.data() + 4 * i);
+    if (tamper_claim) claims[0] = Fr::add(claims[0], Fr::one());
+    fe batched_claim;
+    std::vector<fe> rho_powers = Rep3ProverOpeningAccumulator::exchange_claims(env, claims, batched_claim);
+    std::vector<uint64_t> cf = to_abi(rho_powers);
+    cozk_vec* jv = nullptr;
+    rc_check(cozk_compact_linear_combination(env.ctx, cols.data(), cf.data(), cols.size(), &jv), env.ctx, "compact_linear_combination");
+    VecH jvh(jv);
+    acc.append_joint(env, plain_poly(env.ctx, jvh), chih.h, point, batched_claim);
+}
+
+// steps 2-5 of the worker under the caller's transcript and accumulator (cozk_ts_proof after its commit, cozk_rw_proof after the memory
+// check): gamma and tau, the leaves, the batched grand product, the claims at r_lo and the joint opening.  tamper_claim: claim 0 plus one.
+// Returns the clock taken after the grand product: step 5 belongs to the opening phase of cozk_ts_proof (t_open_ms).
+double ts_range_check_worker(WorkerEnv& env, const TsRangeCols& rc, size_t N, bool leaves_fused, bool tamper_claim, Rep3ProverOpeningAccumulator& acc, double& t_leaves,
+                           double& t_gp) {
+    StarNetWorker* star = env.star;
+    const int ns = (int)rc.t_read.size();
+    const size_t circuits = 6 * (size_t)ns + 1;
+    const std::vector<const cozk_vec*> cols = rc.columns();
+    // ---- 2, 3. gamma, tau; the leaves
+    fe gamma, tau;
+    {
+        Bytes req = star->receive_request();
+        Reader rd(req);
+        gamma = rd.fr();
+        tau = rd.fr();
+    }
+    double t2 = now_ms();
+    LeafBuf lb = flow_leaf_alloc(env, circuits * N);
+    if (leaves_fused) {
+        uint64_t g[4], t[4];
+        fe_to_u64x4(gamma, g);
+        fe_to_u64x4(tau, t);
+        rc_check(cozk_timestamp_range_leaves(env.ctx, rc.t_read.data(), rc.rc_rt.data(), rc.rc_gmr.data(), rc.fc_rt.data(), rc.fc_gmr.data(), (size_t)ns, g, t, lb.a.h, 0),
+                 env.ctx, "timestamp_range_leaves");
+    } else {
+        ts_proof_leaves_composed(env, rc, ns, N, gamma, tau, lb);
+    }
+    double t3 = now_ms();
+    t_leaves = t3 - t2;
+    // ---- 4. ONE dense batched grand product; its claimed outputs are the multiset hashes
+    Rep3BatchedDenseGrandProduct gp = Rep3BatchedDenseGrandProduct::construct(env, flow_leaves_to_layer(env, lb), circuits);
+    {
+        Writer w;
+        w.vec_fr(gp.claimed_outputs(env));
+        star->send_response(w.b);
+    }
+    std::vector<fe> r = gp.prove_grand_product_worker(env);
+    std::vector<fe> r_lo(r.begin() + ceil_log2(circuits), r.end());
+    const double t4 = now_ms();
+    t_gp = t4 - t3;
+    // ---- 5. the claims at r_lo, one exchange, the joint polynomial from the compact columns
+    compact_open_worker(env, acc, cols, r_lo, tamper_claim);
+    return t4;
+}
+
 void ts_proof_worker_main(cozk_ts_proof* h, TsProofParty& ps, StarNetWorker* star) {
     const cozk_ts_proof_config& c = h->cfg;
-    const int ns = h->ns;
-    const size_t N = h->N, circuits = 6 * (size_t)ns + 1;
     WorkerEnv env;
     env.ctx = ps.ctx;
     env.mode = COZK_MODE_PLAIN;
@@ -165,7 +270,8 @@ void ts_proof_worker_main(cozk_ts_proof* h, TsProofParty& ps, StarNetWorker* sta
     env.star = star;
     env.ring = nullptr;
     HIP_TRY(hipSetDevice(ps.ctx->device));
-    const std::vector<const cozk_vec*> cols = ts_proof_columns(ps);
+    const TsRangeCols rc = ts_range_columns(ps, ps.iota);
+    const std::vector<const cozk_vec*> cols = rc.columns();
     double t0 = now_ms();
     // ---- 1. commit (the U32 small-scalar path)
     {
@@ -177,106 +283,59 @@ void ts_proof_worker_main(cozk_ts_proof* h, TsProofParty& ps, StarNetWorker* sta
         for (size_t i = 0; i < cols.size(); i++) PST13Commitment{(uint64_t)c.log_n, abi_to_g1(xy.data() + 8 * i, inf[i])}.write(w);
         star->send_response(w.b);
     }
-    double t1 = now_ms();
-    ps.t_commit = t1 - t0;
-    // ---- 2, 3. gamma, tau; the leaves
-    fe gamma, tau;
-    {
-        Bytes req = star->receive_request();
-        Reader rd(req);
-        gamma = rd.fr();
-        tau = rd.fr();
-    }
-    double t2 = now_ms();
-    LeafBuf lb = flow_leaf_alloc(env, circuits * N);
-    if (c.leaves_fused) {
-        std::vector<const cozk_vec*> f[5];
-        const std::vector<VecH>* fam[5] = {&ps.t_read, &ps.rc_rt, &ps.rc_gmr, &ps.fc_rt, &ps.fc_gmr};
-        for (int k = 0; k < 5; k++)
-            for (const VecH& v : *fam[k]) f[k].push_back(v.h);
-        uint64_t g[4], t[4];
-        fe_to_u64x4(gamma, g);
-        fe_to_u64x4(tau, t);
-        rc_check(cozk_timestamp_range_leaves(env.ctx, f[0].data(), f[1].data(), f[2].data(), f[3].data(), f[4].data(), (size_t)ns, g, t, lb.a.h, 0), env.ctx,
-                 "timestamp_range_leaves");
-    } else {
-        ts_proof_leaves_composed(env, ps, ns, N, gamma, tau, lb);
-    }
-    double t3 = now_ms();
-    ps.t_leaves = t3 - t2;
-    // ---- 4. ONE dense batched grand product; its claimed outputs are the multiset hashes
-    Rep3BatchedDenseGrandProduct gp = Rep3BatchedDenseGrandProduct::construct(env, flow_leaves_to_layer(env, lb), circuits);
-    {
-        Writer w;
-        w.vec_fr(gp.claimed_outputs(env));
-        star->send_response(w.b);
-    }
-    std::vector<fe> r = gp.prove_grand_product_worker(env);
-    std::vector<fe> r_lo(r.begin() + ceil_log2(circuits), r.end());
-    double t4 = now_ms();
-    ps.t_gp = t4 - t3;
-    // ---- 5. the claims at r_lo, one exchange, the joint polynomial from the compact columns
+    ps.t_commit = now_ms() - t0;
+    // ---- 2-5. the range check
     Rep3ProverOpeningAccumulator acc;
-    {
-        std::vector<uint64_t> rr = to_abi(r_lo);
-        cozk_vec* chi = nullptr;
-        rc_check(cozk_eq_evals(env.ctx, rr.data(), (int)r_lo.size(), &chi), env.ctx, "eq_evals");
-        VecH chih(chi);
-        std::vector<uint64_t> ev(4 * cols.size());
-        rc_check(cozk_compact_batch_evaluate_at_chi(env.ctx, cols.data(), cols.size(), chih.h, ev.data()), env.ctx, "compact_batch_evaluate");
-        std::vector<fe> claims(cols.size());
-        for (size_t i = 0; i < cols.size(); i++) claims[i] = fe_from_u64x4(ev.data() + 4 * i);
-        if (c.tamper == 2) claims[0] = Fr::add(claims[0], Fr::one());
-        fe batched_claim;
-        std::vector<fe> rho_powers = Rep3ProverOpeningAccumulator::exchange_claims(env, claims, batched_claim);
-        std::vector<uint64_t> cf = to_abi(rho_powers);
-        cozk_vec* jv = nullptr;
-        rc_check(cozk_compact_linear_combination(env.ctx, cols.data(), cf.data(), cols.size(), &jv), env.ctx, "compact_linear_combination");
-        VecH jvh(jv);
-        acc.append_joint(env, plain_poly(env.ctx, jvh), chih.h, r_lo, batched_claim);
-    }
-    // ---- 6. one reduce_and_prove
+    const double t4 = ts_range_check_worker(env, rc, h->N, c.leaves_fused != 0, c.tamper == 2, acc, ps.t_leaves, ps.t_gp);
+    // ---- 6. one reduce_and_prove (t_open: step 5 and this)
     acc.reduce_and_prove_worker(env, *ps.setup);
     ps.t_open = now_ms() - t4;
     ps.record_net(star);
 }
 
-void ts_proof_coordinate(cozk_ts_proof* h, StarNetCoordinator& net, TsProof& proof) {
-    Transcript tr("cozk-ts-range");
-    {
-        Bytes m = net.receive_response(0);
-        Reader rd(m);
-        const uint64_t k = rd.u64();
-        rd.need_elems(k, 72);
-        for (uint64_t i = 0; i < k; i++) {
-            PST13Commitment cm;
-            cm.nv = rd.u64();
-            cm.g_product = rd.g1();
-            proof.commitments.push_back(cm);
-            tr.append_point(cm.g_product);
-        }
+// the commitments a worker sent after its commit, into the proof and the transcript
+void ts_receive_commitments(StarNetCoordinator& net, Transcript& tr, std::vector<PST13Commitment>& out) {
+    Bytes m = net.receive_response(0);
+    Reader rd(m);
+    const uint64_t k = rd.u64();
+    rd.need_elems(k, 72);
+    for (uint64_t i = 0; i < k; i++) {
+        PST13Commitment cm;
+        cm.nv = rd.u64();
+        cm.g_product = rd.g1();
+        out.push_back(cm);
+        tr.append_point(cm.g_product);
     }
+}
+
+// the coordinator's half of ts_range_check_worker
+void ts_range_check_coordinate(StarNetCoordinator& net, Transcript& tr, size_t log_n, TsRangeProof& proof) {
     flow_broadcast_gamma_tau(net, tr);
     proof.hashes = gather_additive(net);
     tr.append_scalars(proof.hashes);
     fe claim;
     std::vector<fe> r;
-    proof.gp = coordinate_prove_grand_product(net, tr, (size_t)h->cfg.log_n, claim, r);
+    proof.gp = coordinate_prove_grand_product(net, tr, log_n, claim, r);
     proof.claims = Rep3ProverOpeningAccumulator::receive_claims(net, tr);
+}
+
+void ts_proof_coordinate(cozk_ts_proof* h, StarNetCoordinator& net, TsProof& proof) {
+    Transcript tr("cozk-ts-range");
+    ts_receive_commitments(net, tr, proof.commitments);
+    ts_range_check_coordinate(net, tr, (size_t)h->cfg.log_n, proof.range);
     std::vector<fe> r_red;
     fe rho, gamma;
     proof.reduced = Rep3ProverOpeningAccumulator::reduce_and_prove(net, tr, r_red, rho, gamma);
 }
 
-// the plain verifier: replays the transcript; the first check that fails names itself in `why`
-bool ts_proof_verify(cozk_ts_proof* h, const TsProof& proof, std::string& why) {
-    const size_t ns = (size_t)h->ns, circuits = 6 * ns + 1, ncols = 5 * ns;
-    Transcript vt("cozk-ts-range");
-    if (proof.commitments.size() != ncols || proof.hashes.size() != circuits || proof.claims.size() != ncols) {
+// The verifier's half of the range check after the commitments are in the transcript: the first three checks; `o` receives the
+// opening (point, claims, rho) whose commitment indices the caller fills in.
+bool ts_range_check_verify(Transcript& vt, size_t ns, size_t log_n, const TsRangeProof& proof, std::string& why, VerifierOpening& o) {
+    const size_t circuits = 6 * ns + 1, ncols = 5 * ns;
+    if (proof.hashes.size() != circuits || proof.claims.size() != ncols) {
         why = "shape: commitments, hashes or claims";
         return false;
     }
-    for (auto& cm : proof.commitments) vt.append_point(cm.g_product);
     const fe gamma = vt.challenge_scalar(), tau = vt.challenge_scalar();
     const fe g1 = Fr::add(gamma, Fr::one()), g2 = Fr::mul(gamma, gamma);
     vt.append_scalars(proof.hashes);
@@ -289,7 +348,7 @@ bool ts_proof_verify(cozk_ts_proof* h, const TsProof& proof, std::string& why) {
             }
     fe claim;
     std::vector<fe> r;
-    if (!flow_vec_eq(proof.gp.outputs, proof.hashes) || !verify_grand_product(proof.gp, vt, claim, r) || r.size() != (size_t)ceil_log2(circuits) + (size_t)h->cfg.log_n) {
+    if (!flow_vec_eq(proof.gp.outputs, proof.hashes) || !verify_grand_product(proof.gp, vt, claim, r) || r.size() != (size_t)ceil_log2(circuits) + log_n) {
         why = "grand product: the hashes are not its outputs, or a round or a layer reduction does not hold";
         return false;
     }
@@ -313,11 +372,24 @@ bool ts_proof_verify(cozk_ts_proof* h, const TsProof& proof, std::string& why) {
         why = "leaf claim: the fingerprints of the claims != the grand product's final claim";
         return false;
     }
-    VerifierOpening o;
     o.point = lo;
-    for (size_t i = 0; i < ncols; i++) o.polys.push_back(i);
     o.claims = cl;
     o.rho = vt.challenge_scalar();
+    return true;
+}
+
+// the plain verifier: replays the transcript; the first check that fails names itself in `why`
+bool ts_proof_verify(cozk_ts_proof* h, const TsProof& proof, std::string& why) {
+    const size_t ns = (size_t)h->ns, ncols = 5 * ns;
+    Transcript vt("cozk-ts-range");
+    if (proof.commitments.size() != ncols) {
+        why = "shape: commitments, hashes or claims";
+        return false;
+    }
+    for (auto& cm : proof.commitments) vt.append_point(cm.g_product);
+    VerifierOpening o;
+    if (!ts_range_check_verify(vt, ns, (size_t)h->cfg.log_n, proof.range, why, o)) return false;
+    for (size_t i = 0; i < ncols; i++) o.polys.push_back(i);
     std::string inner;
     if (!verify_reduced_opening({o}, proof.commitments, vt, proof.reduced, *h->parties[0].setup, "reduction sumcheck: shape", "reduction sumcheck: final check", inner)) {
         why = "opening: " + inner;

@@ -1845,6 +1845,94 @@ int cozk_ts_proof_destroy(cozk_ts_proof* h);
 int cozk_ts_proof_prove(cozk_ts_proof* h, int verify, cozk_ts_proof_result* res);
 int cozk_ts_proof_proof_bytes(const cozk_ts_proof* h, uint8_t* out, size_t cap);
 
+/* ---- The read-write memory proof's leaves (the dealer's side of ReadWriteMemoryProof over the consistent witness of
+ * cozk_rw_memory_witness).  With h(a, v, t) = a + v gamma + t gamma^2 - tau (the convention of the chained flow's phase 4):
+ * cozk_rw_memory_leaves: the 2 n_slots read / write circuits in one launch from the compact columns, circuit-major:
+ *   circuit 2 s     : out[offset + (2 s) n + j]     = h(addr[s][j], v_read[s][j], t_read[s][j])
+ *   circuit 2 s + 1 : out[offset + (2 s + 1) n + j] = h(addr[s][j], w, j),   w = v_written[s][j], or v_read[s][j] where v_written[s]
+ *                                                     is NULL (the slot only reads; v_written may be NULL as a whole)
+ * addr[s]: U8 or U32, exactly as cozk_rw_memory_witness takes it (the kinds mixed freely over the slots); v_read[s], t_read[s],
+ * v_written[s]: U32; every column of one length 1 <= n < 2^32 (any length), 1 <= n_slots <= COZK_RW_MEMORY_MAX_SLOTS.
+ * cozk_rw_memory_init_final_leaves: out[offset + a] = h(a, v_init[a], 0), out[offset + MEM + a] = h(a, v_final[a], t_final[a]);
+ * three U32 columns of one length 1 <= MEM < 2^32.
+ * Both: out is an FR vector with room for 2 n_slots n (2 MEM) entries from offset, which cozk_layer_create adopts; gamma, tau:
+ * 4 x u64 (Montgomery).  No iota column is stored: j and a exist only in registers.  Every leaf is bit for bit what the composition of
+ * cozk_fingerprint_leaves calls gives.  A wrong kind, columns of unequal length or an out that is too short is refused with
+ * COZK_ERR_INVALID_ARG and a text of its own before any launch, and the context works on.  The launch is asynchronous on the
+ * context's stream, as cozk_fingerprint_leaves is.
+ * A leaf is made as an exact 9-limb integer sum of 32 x 256-bit products reduced by a short Barrett quotient (a full Montgomery product
+ * per term measured 2.5 times as long: DESIGN 4). */
+int cozk_rw_memory_leaves(cozk_ctx* ctx, const cozk_vec* const* addr, const cozk_vec* const* v_read, const cozk_vec* const* t_read,
+                          const cozk_vec* const* v_written, size_t n_slots, const uint64_t gamma[4], const uint64_t tau[4], cozk_vec* out,
+                          size_t offset);
+int cozk_rw_memory_init_final_leaves(cozk_ctx* ctx, const cozk_vec* v_init, const cozk_vec* v_final, const cozk_vec* t_final,
+                                     const uint64_t gamma[4], const uint64_t tau[4], cozk_vec* out, size_t offset);
+
+/* ---- The read-write memory proof itself, as an in-process harness (csrc/host/rw_memory_proof.hpp, on the pattern of cozk_ts_proof):
+ * party 0's public proof of init * writes == reads * final over the consistent witness of cozk_rw_memory_witness, with the timestamp
+ * range check chained behind it under the same transcript and the same opening accumulator, as Jolt's ReadWriteMemoryProof has it:
+ * the t_read commitments are shared and there is ONE reduce_and_prove for everything.  PLAIN only.  jolt-core is not in the reference
+ * tree: the circuit order, the transcript order and the proof bytes are this project's (parity unpinned); what pins them is the plain
+ * verifier below and the Python restatement tests/rw_proof_ref.py.  Not built: the output check over the consistent v_final, the
+ * public-opening exchange to the other parties, and the chained flow's use of any of this.
+ * create: the trace of cozk_ts_proof (tests/rw_witness_ref.py jolt_instance(seed, N, MEM, n_regs = 32)) restricted to the first n_slots
+ * of rs1, rs2, rd, ram (with 1 or 2 nothing writes); the register address columns are U8, the RAM column U32; cozk_rw_memory_witness
+ * over exactly those slots and, with with_ts, cozk_timestamp_range_witness(M = N).  Every column stays compact: no Fr copy of a column
+ * is made.  The SRS has max(log_n, log_mem) variables.
+ * prove (worker on the device, coordinator and verifier on the calling thread, transcript "cozk-rw-memory"):
+ *   1. commit (PST13::batch_commit: mixed lengths and compact kinds), in this order: addr[0..ns), v_read[0..ns), v_written of the slots
+ *      that write (slot order), t_read[0..ns), v_final, t_final, and with with_ts rc_rt, rc_gmr, fc_rt, fc_gmr, each [0..ns); all
+ *      commitments go into the transcript.  v_init is public preprocessing and is not committed.
+ *   2. gamma, tau; the leaves: 2 ns circuits of N entries, 2 of MEM entries (the two calls above, or with leaves_fused = 0 the
+ *      composition of cozk_fingerprint_leaves calls with an iota column: the same bytes)
+ *   3. both hash vectors into the transcript, then the dense grand products (batch 2 ns, then batch 2): points r_rw and r_if
+ *   4. two openings from the compact columns (cozk_eq_evals, cozk_compact_batch_evaluate_at_chi, one claim exchange each,
+ *      cozk_compact_linear_combination over the rho powers, appended as one joint polynomial): at r_rw the N-long columns of step 1,
+ *      at r_if v_final and t_final
+ *   5. with with_ts the timestamp range check of cozk_ts_proof from its step 2 on (a gamma and tau of its own, the 6 ns + 1 circuits,
+ *      one batched grand product, the claims of the 4 ns counter columns and of t_read at its r_lo, a third joint opening); t_read is
+ *      not committed again
+ *   6. ONE reduce_and_prove over the two or three openings (their points differ in length when log_n != log_mem).
+ * Proof bytes: commitments, read-write hashes, init-final hashes, the two grand-product proofs, the claims at r_rw and at r_if, with
+ * with_ts the range check's hashes, grand-product proof and claims, then the reduced opening proof.
+ * The verifier replays the transcript; each check has a reason of its own in cozk_rw_proof_error:
+ *   "multiset equality"  hash[init] * prod_s hash[write_s] == prod_s hash[read_s] * hash[final]
+ *   "grand product"      both grand products, and the hashes are their outputs
+ *   "leaf claim"         the read / write leaves rebuilt from the claims (the write leaf's time is iota(r_rw)); the init / final leaves
+ *                        with iota(r_if) and the MLE of the public v_init at r_if (on the host); missing circuits padded with zero
+ *   "timestamp: ..."     the four checks of cozk_ts_proof, prefixed
+ *   "opening"            the reduced opening
+ * tamper (tests): 1 adds 1 to v_read[last slot][N / 2] before the commit -- a read that no write made: every other relation holds,
+ * only the multiset check can reject; 2 sends claim 0 at r_rw plus one -- the leaf check rejects; 3 (with with_ts) is cozk_ts_proof's
+ * tamper 1 on fc_rt[0] -- "timestamp: multiset equality". */
+typedef struct cozk_rw_proof cozk_rw_proof;
+typedef struct cozk_rw_proof_config {
+    int mode;         /* COZK_MODE_PLAIN; anything else is refused */
+    int device;
+    int log_n;        /* trace length N = 2^log_n, 1..22 */
+    int log_mem;      /* memory of 2^log_mem words, 5..24; either of log_n and log_mem may be the larger */
+    int n_slots;      /* 1..4: the first n_slots of rs1, rs2, rd, ram; with 1 or 2 nothing writes */
+    uint64_t seed;
+    int precompute;   /* the SRS window table (cozk_bases_upload) */
+    int with_ts;      /* 0 or 1: chain the timestamp range check */
+    int leaves_fused; /* 1: cozk_rw_memory_leaves + cozk_rw_memory_init_final_leaves (and cozk_timestamp_range_leaves); 0: the
+                       * composition of cozk_fingerprint_leaves (kept for the A/B); both give the same bytes */
+    int tamper;       /* 0..3: see above */
+} cozk_rw_proof_config;
+typedef struct cozk_rw_proof_result {
+    int verified; /* 1 ok, 0 rejected, -1 not run */
+    /* t_leaves_ms, t_gp_ms: the memory check's; t_ts_ms: the whole chained range check (its leaves, grand product and claims);
+     * t_open_ms: the two compact openings at r_rw and r_if plus reduce_and_prove */
+    double wall_ms, t_witness_ms, t_commit_ms, t_leaves_ms, t_gp_ms, t_ts_ms, t_open_ms;
+    uint64_t proof_len;
+    uint8_t proof_digest[32];
+} cozk_rw_proof_result;
+int cozk_rw_proof_create(const cozk_rw_proof_config* cfg, cozk_rw_proof** out);
+const char* cozk_rw_proof_error(const cozk_rw_proof* h);
+int cozk_rw_proof_destroy(cozk_rw_proof* h);
+int cozk_rw_proof_prove(cozk_rw_proof* h, int verify, cozk_rw_proof_result* res);
+int cozk_rw_proof_proof_bytes(const cozk_rw_proof* h, uint8_t* out, size_t cap);
+
 /* ---- ONE chained co-jolt worker flow (JoltRep3Prover::prove, co-jolt/src/jolt/vm/jolt/worker.rs:175-266, against its coordinator
  * jolt/vm/jolt/coordinator.rs:118-222): commit-all -> bytecode memory checking -> instruction lookups (primary sumcheck, toggled
  * read / write + dense init / final grand products) -> read-write memory checking + output check -> Spartan (outer + inner + shift) ->
