@@ -1,6 +1,6 @@
-// The time-ordered walk shared by the Lasso lookup witness (lasso_witness.hip) and the read-write memory witness
-// (rw_memory_witness.hip): ONE wave takes 64 keys in time order (lane = time) and ranks each among the earlier equal keys of its
-// tile, against a u16 table of per-key counts in LDS.
+// The time-ordered walk shared by the Lasso lookup witness (lasso_witness.hip) and, through the radix pass of radix_pass.hip.hpp,
+// by the read-write memory witness (rw_memory_witness.hip) and the time counters (ts_range_witness.hip): ONE wave takes 64 keys in
+// time order (lane = time) and ranks each among the earlier equal keys of its tile, against a u16 table of per-key counts in LDS.
 #pragma once
 #include "common.hpp"
 

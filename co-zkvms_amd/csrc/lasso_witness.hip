@@ -19,14 +19,15 @@
 //                   shuffle and adds the number of its lower lanes.  read_cts <- the in-tile rank of the flagged steps; the table
 //                   leaves as the tile's histogram.
 //   k_lasso_scan    per (memory, address): exclusive scan of the tile histograms over the tiles -> u32 tile bases; total -> final_cts
+//                   (rp_scan_tiles of radix_pass.hip.hpp, the scan of the read-write and timestamp witnesses' sort)
 //   k_lasso_finish  per (step, memory): read_cts += base[tile][addr], E <- subtable[addr]; both 0 where the flag is off
 //
 // A flagged address >= M is skipped by every kernel (no load or store leaves its buffer) and reported through one device word,
 // the smallest (memory, step) of a violation (an atomicMin: its result does not depend on the order of arrival).
 #include "common.hpp"
-#include "lasso_walk.hip.hpp"  // the wave step of the walk (shared with rw_memory_witness.hip)
+#include "radix_pass.hip.hpp"  // the wave step of the walk (lw_walk_step), the scan over the tiles, the pass plan, the violation word
 
-static constexpr int LW_TILE = COZK_LASSO_TILE;  // steps per tile: in-tile ranks and counts (<= 32768) fit 16 bits
+static constexpr int LW_TILE = RP_TILE;  // steps per tile: in-tile ranks and counts (<= 32768) fit 16 bits
 static constexpr uint32_t LW_MAX_M = 65536;
 static constexpr int LW_PT = 256;
 static constexpr int LW_WAVES = LW_PT / 64;
@@ -104,12 +105,7 @@ __global__ void __launch_bounds__(LW_PT) k_lasso_scan(const LwMem* __restrict__ 
     const uint32_t a = blockIdx.x * LW_PT + threadIdx.x;
     if (a >= M) return;
     const size_t row = (size_t)blockIdx.y * tiles * Mp + a;
-    uint32_t run = 0;
-    for (size_t t = 0; t < tiles; t++) {
-        bases[row + t * Mp] = run;
-        run += hist[row + t * Mp];
-    }
-    mems[blockIdx.y].fc[a] = run;
+    mems[blockIdx.y].fc[a] = rp_scan_tiles(tiles, Mp, hist + row, bases + row);
 }
 
 // the rank kernel wrote read_cts at the flagged steps only: this one writes every step
@@ -166,37 +162,30 @@ int cozk_lasso_witness(cozk_ctx* ctx, const cozk_vec* const* dims, size_t n_dims
         for (size_t m = 0; m < n_mem; m++)
             hm[m] = LwMem{(const uint32_t*)dims[mem_dim[m]]->d, flags[m] ? (const uint8_t*)flags[m]->d : nullptr, (const uint32_t*)subtables[mem_subtable[m]]->d,
                           (uint32_t*)read_cts[m]->d, (uint32_t*)E[m]->d, (uint32_t*)final_cts[m]->d};
-        const size_t tiles = (n + LW_TILE - 1) / LW_TILE;
-        const uint32_t Mp = ((uint32_t)M + 1) & ~1u;  // row stride of the histograms: whole 32-bit words
-        int key_bits = 0;
-        while (((size_t)1 << key_bits) < M) key_bits++;
-        // the memories go in batches whose histograms (u16) and bases (u32) stay under the cap; one memory is the least
-        const size_t per_mem = tiles * Mp * (sizeof(uint16_t) + sizeof(uint32_t));
-        size_t batch = LW_TRANSIENT_CAP / per_mem;
-        batch = batch < 1 ? 1 : (batch > n_mem ? n_mem : batch);
+        const RadixPlan plan(n, M);  // one pass: M <= 65536
+        const size_t tiles = plan.tiles;
+        const uint32_t Mp = plan.Dp(0);
+        const int key_bits = plan.key_bits(0);
+        const size_t batch = radix_batch(LW_TRANSIENT_CAP, tiles, Mp, n_mem);
         d_mems = ctx_dev_alloc(ctx, n_mem * sizeof(LwMem));
         d_hist = ctx_dev_alloc(ctx, batch * tiles * Mp * sizeof(uint16_t));
         d_bases = ctx_dev_alloc(ctx, batch * tiles * Mp * sizeof(uint32_t));
-        d_viol = ctx_dev_alloc(ctx, sizeof(unsigned long long));
-        unsigned long long* pin = (unsigned long long*)ctx_pinned(ctx, sizeof(unsigned long long));
+        unsigned long long* viol = viol_begin(ctx, &d_viol);
         HIP_TRY(hipMemcpyAsync(d_mems, hm.data(), n_mem * sizeof(LwMem), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemsetAsync(d_viol, 0xff, sizeof(unsigned long long), ctx->stream));
         for (size_t m0 = 0; m0 < n_mem; m0 += batch) {
             const unsigned nb = (unsigned)(n_mem - m0 < batch ? n_mem - m0 : batch);
             const LwMem* dm = (const LwMem*)d_mems + m0;
-            k_lasso_rank<<<dim3((unsigned)tiles, nb), LW_PT, 0, ctx->stream>>>(dm, n, (uint32_t)M, Mp, key_bits, (uint32_t)m0, (uint16_t*)d_hist,
-                                                                             (unsigned long long*)d_viol);
+            k_lasso_rank<<<dim3((unsigned)tiles, nb), LW_PT, 0, ctx->stream>>>(dm, n, (uint32_t)M, Mp, key_bits, (uint32_t)m0, (uint16_t*)d_hist, viol);
             HIP_TRY(hipGetLastError());
             k_lasso_scan<<<dim3((unsigned)((M + LW_PT - 1) / LW_PT), nb), LW_PT, 0, ctx->stream>>>(dm, (uint32_t)M, Mp, tiles, (const uint16_t*)d_hist, (uint32_t*)d_bases);
             HIP_TRY(hipGetLastError());
             k_lasso_finish<<<dim3((unsigned)((n + LW_PT - 1) / LW_PT), nb), LW_PT, 0, ctx->stream>>>(dm, n, (uint32_t)M, Mp, tiles, (const uint32_t*)d_bases);
             HIP_TRY(hipGetLastError());
         }
-        HIP_TRY(hipMemcpyAsync(pin, d_viol, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (*pin != ~0ull) {
+        const unsigned long long bad = viol_read(ctx, viol);
+        if (bad != ~0ull) {
             char buf[160];
-            snprintf(buf, sizeof buf, "lasso_witness: memory %llu, step %llu: a flagged address is >= M = %zu", *pin >> 32, *pin & 0xffffffffull, M);
+            snprintf(buf, sizeof buf, "lasso_witness: memory %llu, step %llu: a flagged address is >= M = %zu", bad >> 32, bad & 0xffffffffull, M);
             throw CozkError(COZK_ERR_INVALID_ARG, buf);
         }
     });

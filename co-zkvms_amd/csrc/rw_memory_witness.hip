@@ -13,14 +13,13 @@
 // operation i = j * n_slots + s:
 //
 //   sort: least-significant-digit radix passes of 16 bits, one for MEM <= 65536, else two (the second over the high digit's actual
-//   range).  Per pass, over tiles of RW_TILE positions and D digit values:
-//     k_rw_rank     one workgroup per tile, a u16 table of D counters in LDS.  The tile goes in chunks of RW_CHUNK positions: wave
-//                   0 walks a chunk's digits, staged in LDS, 64 at a time in position order (lw_walk_step, the walk of the Lasso
-//                   witness) -> u16 in-tile rank per position, while the other three waves stage the next chunk's digits (in
-//                   the second pass a gather through the first pass's order); the table leaves as the tile's histogram.  The
-//                   first pass also checks every address against MEM.
-//     k_rw_scan     per digit value: exclusive scan of the tile histograms over the tiles -> u32 tile bases; total -> count[digit]
-//     k_rw_offsets  one workgroup: exclusive scan of count[] over the digit values, in place
+//   range).  The pass itself -- the tile walk, the scan over the tiles, the offsets scan -- is radix_pass.hip.hpp's; here are its
+//   entry points and what is this witness's own, over tiles of RP_TILE positions and D digit values:
+//     k_rw_rank     rp_rank_tile with the digit of a position: the address of the operation there (in the second pass a gather
+//                   through the first pass's order), of one of n_slots interleaved columns of two widths.  The first pass also
+//                   checks every address against MEM.
+//     k_rw_scan     rp_scan_tiles per digit value; total -> count[digit]
+//     k_rw_offsets  rp_offsets over count[]
 //     k_rw_scatter  per position: order_out[offset[digit] + base[tile][digit] + rank] = the operation at the position
 //   sweep: an exclusive max-scan of one u32 per sorted position q, q + 1 where the operation writes and 0 otherwise, as reduce /
 //   scan / apply launches (no workgroup waits for another):
@@ -36,24 +35,17 @@
 // every kernel (no load or store leaves its buffer) and reported through one device word, the smallest (step, slot) of a violation
 // (an atomicMin: its result does not depend on the order of arrival); the call then returns no vector.
 //
-// Transient device memory, with tiles = ceil(N / RW_TILE), D1 = min(MEM, 65536), D2 = ceil(MEM / 65536) (0 for one pass),
+// Transient device memory, with tiles = ceil(N / RP_TILE), D1 = min(MEM, 65536), D2 = ceil(MEM / 65536) (0 for one pass),
 // D = max(D1, D2) rounded up to even, blocks = ceil(N / RW_BLOCK):
 //   4 N (8 N for two passes) sorted operation indices + 2 N ranks + 6 tiles D histograms and bases + 4 D counts + 8 blocks
 //   = 16 MiB + 8 MiB + 48 MiB at n = 2^20 with 4 slots and MEM = 2^16, 16 MiB more at MEM = 2^20.
 #include "common.hpp"
-#include "lasso_walk.hip.hpp"
+#include "radix_pass.hip.hpp"
 
-static constexpr int RW_TILE = COZK_LASSO_TILE;  // positions per tile: in-tile ranks (< 32768) and counts (<= 32768) fit 16 bits
-static constexpr int RW_PT = 256;
-static constexpr int RW_WAVES = RW_PT / 64;
-static constexpr int RW_CHUNK = 4096;            // digits staged in LDS at a time (two buffers: one walked, one being staged)
-static constexpr int RW_ROWS = 16;               // rows of RW_PT positions per sweep block
-static constexpr int RW_BLOCK = RW_PT * RW_ROWS;
-static constexpr int RW_SCAN_PT = 1024;          // the two one-workgroup scans
-static constexpr int RW_SCAN_ROWS = 65536 / RW_SCAN_PT;
-static_assert(RW_SCAN_ROWS * (RW_SCAN_PT / 64) == RW_SCAN_PT, "k_rw_offsets scans one (row, wave) total per thread");
+static constexpr int RW_WAVES = RP_PT / 64;
+static constexpr int RW_ROWS = 16;               // rows of RP_PT positions per sweep block
+static constexpr int RW_BLOCK = RP_PT * RW_ROWS;
 static constexpr size_t RW_MAX_SLOTS = COZK_RW_MEMORY_MAX_SLOTS;
-static_assert(RW_TILE <= 32768 && RW_TILE % RW_CHUNK == 0 && RW_CHUNK % 64 == 0, "in-tile counts must fit 16 bits");
 
 struct RwSlot {
     const void* addr;
@@ -74,133 +66,48 @@ __device__ __forceinline__ uint32_t rw_addr(const RwSlot& sl, uint32_t j, uint32
 __device__ __forceinline__ bool rw_writes(const RwSlot& sl, uint32_t j) { return sl.vw && (sl.iw ? sl.iw[j] != 0 : true); }
 
 // order: the operations in the order of the previous pass; null = operation i at position i
-__global__ void __launch_bounds__(RW_PT) k_rw_rank(const RwSlot* __restrict__ slots, uint32_t n_slots, uint32_t N, uint32_t MEM, const uint32_t* __restrict__ order,
+__global__ void __launch_bounds__(RP_PT) k_rw_rank(const RwSlot* __restrict__ slots, uint32_t n_slots, uint32_t N, uint32_t MEM, const uint32_t* __restrict__ order,
                                                    int shift, uint32_t Dp, int key_bits, uint16_t* __restrict__ rank, uint16_t* __restrict__ hist,
                                                    unsigned long long* __restrict__ viol) {
-    __shared__ uint16_t tab[65536];
-    __shared__ uint16_t keys[2][RW_CHUNK];
-    uint32_t* tab32 = reinterpret_cast<uint32_t*>(tab);
     const size_t tile = blockIdx.x;
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (uint32_t i = threadIdx.x; i < Dp / 2; i += RW_PT) tab32[i] = 0;
-    const size_t begin = tile * (size_t)RW_TILE, end = begin + RW_TILE < N ? begin + RW_TILE : (size_t)N;
-    // the digits of the chunk at c0, by the threads first, first + stride, ...
-    auto stage = [&](size_t c0, uint16_t* dst, unsigned first, unsigned stride) {
-#pragma unroll 4
-        for (uint32_t e = first; e < (uint32_t)RW_CHUNK; e += stride) {
-            const size_t p = c0 + e;
-            if (p < end) {
-                const uint32_t i = order ? order[p] : (uint32_t)p;
-                const uint32_t j = i / n_slots, s = i - j * n_slots;
-                const uint32_t raw = rw_raw_addr(slots[s], j);
-                if (!order && raw >= MEM) atomicMin(viol, ((unsigned long long)j << 32) | s);
-                dst[e] = (uint16_t)((raw < MEM ? raw : 0) >> shift);
-            }
-        }
+    auto digit = [&](size_t p) {
+        const uint32_t i = order ? order[p] : (uint32_t)p;
+        const uint32_t j = i / n_slots, s = i - j * n_slots;
+        const uint32_t raw = rw_raw_addr(slots[s], j);
+        if (!order && raw >= MEM) atomicMin(viol, ((unsigned long long)j << 32) | s);
+        return (uint16_t)((raw < MEM ? raw : 0) >> shift);
     };
-    stage(begin, keys[0], threadIdx.x, RW_PT);
-    __syncthreads();  // the first chunk's digits are staged and the table is clear
-    int cur = 0;
-    for (size_t c0 = begin; c0 < end; c0 += RW_CHUNK, cur ^= 1) {  // every bound of this loop is uniform over the workgroup
-        if (wave == 0) {
-            const uint32_t cnt = end - c0 < (size_t)RW_CHUNK ? (uint32_t)(end - c0) : (uint32_t)RW_CHUNK;
-            for (uint32_t k0 = 0; k0 < cnt; k0 += 64) {
-                const bool valid = k0 + lane < cnt;
-                const uint32_t r = lw_walk_step(tab, valid, valid ? keys[cur][k0 + lane] : 0, key_bits, lane);
-                if (valid) rank[c0 + k0 + lane] = (uint16_t)r;
-            }
-        } else if (c0 + RW_CHUNK < end) {  // the other waves stage the next chunk beside the walk
-            stage(c0 + RW_CHUNK, keys[cur ^ 1], threadIdx.x - 64, RW_PT - 64);
-        }
-        __syncthreads();  // the walk has left keys[cur], which the chunk after the next one rewrites; keys[cur ^ 1] is staged
-    }
-    uint32_t* out = reinterpret_cast<uint32_t*>(hist + tile * Dp);
-    for (uint32_t i = threadIdx.x; i < Dp / 2; i += RW_PT) out[i] = tab32[i];
+    rp_rank_tile(tile, (size_t)N, digit, Dp, key_bits, rank, hist + tile * Dp);
 }
 
-__global__ void __launch_bounds__(RW_PT) k_rw_scan(uint32_t D, uint32_t Dp, size_t tiles, const uint16_t* __restrict__ hist, uint32_t* __restrict__ bases,
+__global__ void __launch_bounds__(RP_PT) k_rw_scan(uint32_t D, uint32_t Dp, size_t tiles, const uint16_t* __restrict__ hist, uint32_t* __restrict__ bases,
                                                    uint32_t* __restrict__ count) {
-    const uint32_t d = blockIdx.x * RW_PT + threadIdx.x;
+    const uint32_t d = blockIdx.x * RP_PT + threadIdx.x;
     if (d >= D) return;
-    uint32_t run = 0;
-    for (size_t t = 0; t < tiles; t++) {
-        bases[t * Dp + d] = run;
-        run += hist[t * Dp + d];
-    }
-    count[d] = run;
+    count[d] = rp_scan_tiles(tiles, Dp, hist + d, bases + d);
 }
 
-// inclusive scan (sum, or max) over the RW_SCAN_PT threads of the workgroup; returns the exclusive value, *total = the whole
-template <bool MAX>
-__device__ __forceinline__ uint32_t rw_block_scan(uint32_t x, uint32_t* sh, uint32_t* total) {
-    const unsigned t = threadIdx.x;
-    sh[t] = x;
-    __syncthreads();
-    for (unsigned off = 1; off < RW_SCAN_PT; off <<= 1) {
-        const uint32_t y = t >= off ? sh[t - off] : 0;
-        __syncthreads();
-        x = MAX ? (x > y ? x : y) : x + y;
-        sh[t] = x;
-        __syncthreads();
-    }
-    *total = sh[RW_SCAN_PT - 1];
-    const uint32_t excl = t ? sh[t - 1] : 0;
-    __syncthreads();
-    return excl;
-}
+__global__ void __launch_bounds__(RP_SCAN_PT) k_rw_offsets(uint32_t D, uint32_t* __restrict__ count) { rp_offsets(D, count); }
 
-// count[0..D) -> its exclusive prefix sums, in place, D <= 65536: up to RW_SCAN_ROWS rows of RW_SCAN_PT values, a value per thread
-// and row (coalesced).  A wave scan per row leaves each value's prefix inside its wave in place; one workgroup scan over the
-// (row, wave) totals, which are in the order of the values; then every value takes the prefix of its wave.
-__global__ void __launch_bounds__(RW_SCAN_PT) k_rw_offsets(uint32_t D, uint32_t* __restrict__ count) {
-    __shared__ uint32_t sh[RW_SCAN_PT], pre[RW_SCAN_PT];
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int rows = (int)((D + RW_SCAN_PT - 1) / RW_SCAN_PT);  // uniform over the workgroup
-    pre[threadIdx.x] = 0;
-    __syncthreads();
-#pragma unroll 8
-    for (int r = 0; r < rows; r++) {
-        const uint32_t d = (uint32_t)r * RW_SCAN_PT + threadIdx.x;
-        const uint32_t x = d < D ? count[d] : 0;
-        uint32_t v = x;
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(v, off);
-            if ((int)lane >= off) v += y;
-        }
-        if (d < D) count[d] = v - x;
-        if (lane == 63) pre[r * (RW_SCAN_PT / 64) + wave] = v;
-    }
-    __syncthreads();
-    uint32_t total;
-    const uint32_t before = rw_block_scan<false>(pre[threadIdx.x], sh, &total);
-    pre[threadIdx.x] = before;  // every thread has read its total before rw_block_scan's first barrier
-    __syncthreads();
-#pragma unroll 8
-    for (int r = 0; r < rows; r++) {
-        const uint32_t d = (uint32_t)r * RW_SCAN_PT + threadIdx.x;
-        if (d < D) count[d] += pre[r * (RW_SCAN_PT / 64) + wave];
-    }
-}
-
-__global__ void __launch_bounds__(RW_PT) k_rw_scatter(const RwSlot* __restrict__ slots, uint32_t n_slots, uint32_t N, uint32_t MEM, const uint32_t* __restrict__ order,
+__global__ void __launch_bounds__(RP_PT) k_rw_scatter(const RwSlot* __restrict__ slots, uint32_t n_slots, uint32_t N, uint32_t MEM, const uint32_t* __restrict__ order,
                                                       int shift, uint32_t Dp, const uint16_t* __restrict__ rank, const uint32_t* __restrict__ bases,
                                                       const uint32_t* __restrict__ offset, uint32_t* __restrict__ order_out) {
-    const size_t p = (size_t)blockIdx.x * RW_PT + threadIdx.x;
+    const size_t p = (size_t)blockIdx.x * RP_PT + threadIdx.x;
     if (p >= N) return;
     const uint32_t i = order ? order[p] : (uint32_t)p;
     const uint32_t j = i / n_slots, s = i - j * n_slots;
     const uint32_t d = (rw_addr(slots[s], j, MEM) >> shift) & 0xffff;
-    order_out[offset[d] + bases[(p / RW_TILE) * Dp + d] + rank[p]] = i;  // a permutation of 0..N: the counts are of these same digits
+    order_out[offset[d] + bases[(p / RP_TILE) * Dp + d] + rank[p]] = i;  // a permutation of 0..N: the counts are of these same digits
 }
 
-__global__ void __launch_bounds__(RW_PT) k_rw_last_write(const RwSlot* __restrict__ slots, uint32_t n_slots, uint32_t N, const uint32_t* __restrict__ order,
+__global__ void __launch_bounds__(RP_PT) k_rw_last_write(const RwSlot* __restrict__ slots, uint32_t n_slots, uint32_t N, const uint32_t* __restrict__ order,
                                                          uint32_t* __restrict__ blast) {
     __shared__ uint32_t wmax[RW_WAVES];
     const size_t base = (size_t)blockIdx.x * RW_BLOCK;
     uint32_t m = 0;
 #pragma unroll 4
     for (int it = 0; it < RW_ROWS; it++) {
-        const size_t q = base + (size_t)(it * RW_PT) + threadIdx.x;
+        const size_t q = base + (size_t)(it * RP_PT) + threadIdx.x;
         if (q < N) {
             const uint32_t i = order[q], j = i / n_slots, s = i - j * n_slots;
             if (rw_writes(slots[s], j)) m = (uint32_t)q + 1;  // q grows with it
@@ -219,10 +126,10 @@ __global__ void __launch_bounds__(RW_PT) k_rw_last_write(const RwSlot* __restric
 }
 
 // blast[0..nb) -> bcarry: the last write before each block (exclusive max-scan)
-__global__ void __launch_bounds__(RW_SCAN_PT) k_rw_carry(size_t nb, const uint32_t* __restrict__ blast, uint32_t* __restrict__ bcarry) {
-    __shared__ uint32_t sh[RW_SCAN_PT];
+__global__ void __launch_bounds__(RP_SCAN_PT) k_rw_carry(size_t nb, const uint32_t* __restrict__ blast, uint32_t* __restrict__ bcarry) {
+    __shared__ uint32_t sh[RP_SCAN_PT];
     uint32_t carry = 0;
-    for (size_t c = 0; c < nb; c += RW_SCAN_PT) {  // uniform over the workgroup
+    for (size_t c = 0; c < nb; c += RP_SCAN_PT) {  // uniform over the workgroup
         const size_t b = c + threadIdx.x;
         uint32_t total;
         const uint32_t excl = rw_block_scan<true>(b < nb ? blast[b] : 0, sh, &total);
@@ -231,7 +138,7 @@ __global__ void __launch_bounds__(RW_SCAN_PT) k_rw_carry(size_t nb, const uint32
     }
 }
 
-__global__ void __launch_bounds__(RW_PT) k_rw_gather(const RwSlot* __restrict__ slots, uint32_t n_slots, uint32_t N, uint32_t MEM, const uint32_t* __restrict__ order,
+__global__ void __launch_bounds__(RP_PT) k_rw_gather(const RwSlot* __restrict__ slots, uint32_t n_slots, uint32_t N, uint32_t MEM, const uint32_t* __restrict__ order,
                                                      const uint32_t* __restrict__ bcarry, const uint32_t* __restrict__ v_init, uint32_t* __restrict__ v_final,
                                                      uint32_t* __restrict__ t_final) {
     __shared__ uint32_t wlast[2][RW_WAVES];
@@ -240,7 +147,7 @@ __global__ void __launch_bounds__(RW_PT) k_rw_gather(const RwSlot* __restrict__ 
     const size_t base = (size_t)blockIdx.x * RW_BLOCK;
     uint32_t carry = bcarry[blockIdx.x];  // the last write before the row, + 1 (0: none): the same value in every thread
     for (int it = 0; it < RW_ROWS; it++) {  // every bound of this loop is uniform over the workgroup
-        const size_t row = base + (size_t)(it * RW_PT);
+        const size_t row = base + (size_t)(it * RP_PT);
         if (row >= N) break;
         const size_t q = row + threadIdx.x;
         const bool valid = q < N;
@@ -342,55 +249,49 @@ int cozk_rw_memory_witness(cozk_ctx* ctx, const cozk_vec* const* addr, const coz
             hs[s] = RwSlot{addr[s]->d, v_write && v_write[s] ? (const uint32_t*)v_write[s]->d : nullptr, is_write && is_write[s] ? (const uint8_t*)is_write[s]->d : nullptr,
                            (uint32_t*)v_read[s]->d, (uint32_t*)t_read[s]->d, v_written[s] ? (uint32_t*)v_written[s]->d : nullptr, addr[s]->kind == COZK_SCALAR_U8};
         const uint32_t N = (uint32_t)(n * n_slots), ns = (uint32_t)n_slots, mem = (uint32_t)MEM;
-        const size_t tiles = ((size_t)N + RW_TILE - 1) / RW_TILE, nb = ((size_t)N + RW_BLOCK - 1) / RW_BLOCK;
-        const int passes = MEM > 65536 ? 2 : 1;
-        const uint32_t D[2] = {MEM < 65536 ? mem : 65536u, passes == 2 ? ((mem - 1) >> 16) + 1 : 0u};
-        const uint32_t Dmax = ((D[0] > D[1] ? D[0] : D[1]) + 1) & ~1u;
+        const RadixPlan plan(N, MEM);
+        const size_t tiles = plan.tiles, nb = ((size_t)N + RW_BLOCK - 1) / RW_BLOCK;
+        const int passes = plan.passes;
         d_slots = ctx_dev_alloc(ctx, n_slots * sizeof(RwSlot));
         for (int k = 0; k < passes; k++) d_ord[k] = ctx_dev_alloc(ctx, (size_t)N * sizeof(uint32_t));
         d_rank = ctx_dev_alloc(ctx, (size_t)N * sizeof(uint16_t));
-        d_hist = ctx_dev_alloc(ctx, tiles * Dmax * sizeof(uint16_t));
-        d_bases = ctx_dev_alloc(ctx, tiles * Dmax * sizeof(uint32_t));
-        d_count = ctx_dev_alloc(ctx, (size_t)Dmax * sizeof(uint32_t));
+        d_hist = ctx_dev_alloc(ctx, tiles * plan.Dmax * sizeof(uint16_t));
+        d_bases = ctx_dev_alloc(ctx, tiles * plan.Dmax * sizeof(uint32_t));
+        d_count = ctx_dev_alloc(ctx, (size_t)plan.Dmax * sizeof(uint32_t));
         d_blast = ctx_dev_alloc(ctx, nb * sizeof(uint32_t));
         d_bcarry = ctx_dev_alloc(ctx, nb * sizeof(uint32_t));
-        d_viol = ctx_dev_alloc(ctx, sizeof(unsigned long long));
-        unsigned long long* pin = (unsigned long long*)ctx_pinned(ctx, sizeof(unsigned long long));
+        unsigned long long* viol = viol_begin(ctx, &d_viol);
         const RwSlot* ds = (const RwSlot*)d_slots;
         hipStream_t st = ctx->stream;
         HIP_TRY(hipMemcpyAsync(d_slots, hs, n_slots * sizeof(RwSlot), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(d_viol, 0xff, sizeof(unsigned long long), st));
         HIP_TRY(hipMemcpyAsync((*v_final)->d, v_init->d, MEM * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemsetAsync((*t_final)->d, 0, MEM * sizeof(uint32_t), st));
-        const unsigned pos_grid = (unsigned)(((size_t)N + RW_PT - 1) / RW_PT);
+        const unsigned pos_grid = (unsigned)(((size_t)N + RP_PT - 1) / RP_PT);
         for (int k = 0; k < passes; k++) {
-            const uint32_t Dp = (D[k] + 1) & ~1u;  // row stride of the histograms: whole 32-bit words
+            const uint32_t D = plan.D[k], Dp = plan.Dp(k);
             const uint32_t* in = k ? (const uint32_t*)d_ord[0] : nullptr;
-            int key_bits = 0;
-            while (((uint32_t)1 << key_bits) < D[k]) key_bits++;
-            k_rw_rank<<<(unsigned)tiles, RW_PT, 0, st>>>(ds, ns, N, mem, in, 16 * k, Dp, key_bits, (uint16_t*)d_rank, (uint16_t*)d_hist, (unsigned long long*)d_viol);
+            k_rw_rank<<<(unsigned)tiles, RP_PT, 0, st>>>(ds, ns, N, mem, in, 16 * k, Dp, plan.key_bits(k), (uint16_t*)d_rank, (uint16_t*)d_hist, viol);
             HIP_TRY(hipGetLastError());
-            k_rw_scan<<<(D[k] + RW_PT - 1) / RW_PT, RW_PT, 0, st>>>(D[k], Dp, tiles, (const uint16_t*)d_hist, (uint32_t*)d_bases, (uint32_t*)d_count);
+            k_rw_scan<<<(D + RP_PT - 1) / RP_PT, RP_PT, 0, st>>>(D, Dp, tiles, (const uint16_t*)d_hist, (uint32_t*)d_bases, (uint32_t*)d_count);
             HIP_TRY(hipGetLastError());
-            k_rw_offsets<<<1, RW_SCAN_PT, 0, st>>>(D[k], (uint32_t*)d_count);
+            k_rw_offsets<<<1, RP_SCAN_PT, 0, st>>>(D, (uint32_t*)d_count);
             HIP_TRY(hipGetLastError());
-            k_rw_scatter<<<pos_grid, RW_PT, 0, st>>>(ds, ns, N, mem, in, 16 * k, Dp, (const uint16_t*)d_rank, (const uint32_t*)d_bases, (const uint32_t*)d_count,
+            k_rw_scatter<<<pos_grid, RP_PT, 0, st>>>(ds, ns, N, mem, in, 16 * k, Dp, (const uint16_t*)d_rank, (const uint32_t*)d_bases, (const uint32_t*)d_count,
                                                     (uint32_t*)d_ord[k]);
             HIP_TRY(hipGetLastError());
         }
         const uint32_t* sorted = (const uint32_t*)d_ord[passes - 1];
-        k_rw_last_write<<<(unsigned)nb, RW_PT, 0, st>>>(ds, ns, N, sorted, (uint32_t*)d_blast);
+        k_rw_last_write<<<(unsigned)nb, RP_PT, 0, st>>>(ds, ns, N, sorted, (uint32_t*)d_blast);
         HIP_TRY(hipGetLastError());
-        k_rw_carry<<<1, RW_SCAN_PT, 0, st>>>(nb, (const uint32_t*)d_blast, (uint32_t*)d_bcarry);
+        k_rw_carry<<<1, RP_SCAN_PT, 0, st>>>(nb, (const uint32_t*)d_blast, (uint32_t*)d_bcarry);
         HIP_TRY(hipGetLastError());
-        k_rw_gather<<<(unsigned)nb, RW_PT, 0, st>>>(ds, ns, N, mem, sorted, (const uint32_t*)d_bcarry, (const uint32_t*)v_init->d, (uint32_t*)(*v_final)->d,
+        k_rw_gather<<<(unsigned)nb, RP_PT, 0, st>>>(ds, ns, N, mem, sorted, (const uint32_t*)d_bcarry, (const uint32_t*)v_init->d, (uint32_t*)(*v_final)->d,
                                                    (uint32_t*)(*t_final)->d);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(pin, d_viol, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (*pin != ~0ull) {
+        const unsigned long long bad = viol_read(ctx, viol);
+        if (bad != ~0ull) {
             char buf[160];
-            snprintf(buf, sizeof buf, "rw_memory_witness: step %llu, slot %llu: the address is >= MEM = %zu", *pin >> 32, *pin & 0xffffffffull, MEM);
+            snprintf(buf, sizeof buf, "rw_memory_witness: step %llu, slot %llu: the address is >= MEM = %zu", bad >> 32, bad & 0xffffffffull, MEM);
             throw CozkError(COZK_ERR_INVALID_ARG, buf);
         }
     });

@@ -11,18 +11,18 @@
 //
 // and the witness is these counters for two columns per slot, key = t_read[s][j] and key = j - t_read[s][j], derived where a kernel
 // needs them and never stored.  cozk_lasso_witness keeps one u16 counter per table entry in LDS, which ends at M = 65536; here the
-// steps of a column are sorted by key with the stable 16-bit radix passes of the read-write witness (rw_memory_witness.hip), one
-// pass for M <= 65536 and two above, the second over the high digit's actual range.  The column is a grid dimension of every launch.
-// Per pass, over tiles of TS_TILE positions and D digit values:
-//   k_ts_rank       one workgroup per (tile, column), a u16 table of D counters in LDS.  The tile goes in chunks of TS_CHUNK positions:
-//                   wave 0 walks a chunk's digits, staged in LDS, 64 at a time in position order (lw_walk_step) -> u16 in-tile rank
-//                   per position, while the other three waves stage the next chunk's digits (in the second pass a gather through the
-//                   first pass's order); the table leaves as the tile's histogram.  The first pass also checks every key.
-//   k_ts_scan       per (digit value, column): exclusive scan of the tile histograms over the tiles -> u32 tile bases; total -> count
+// steps of a column are sorted by key with the stable 16-bit radix passes of radix_pass.hip.hpp (the tile walk, the scan over the
+// tiles, the offsets scan: shared with rw_memory_witness.hip), one pass for M <= 65536 and two above, the second over the high
+// digit's actual range.  The column is a grid dimension of every launch.  The pass's entry points and what is this file's own, per
+// pass, over tiles of RP_TILE positions and D digit values:
+//   k_ts_rank       rp_rank_tile per (tile, column) with the digit of a position: the key of the step there (in the second pass a
+//                   gather through the first pass's order), a column of the batch chosen by blockIdx.y.  The first pass also checks
+//                   every key.
+//   k_ts_scan       rp_scan_tiles per (digit value, column); total -> count
 //   one pass:  count IS final_cts (the scan writes it there), and
 //   k_ts_finish     per (step, column): read_cts = base[tile][key] + in-tile rank
 //   two passes, per pass:
-//   k_ts_offsets    one workgroup per column: exclusive scan of count[] over the digit values, in place
+//   k_ts_offsets    rp_offsets per column over count[]
 //   k_ts_scatter    per (position, column): order_out[offset[digit] + base[tile][digit] + rank] = the step at the position; the
 //                   second pass also leaves the key there, so the sweep below reads its neighbours' keys in place
 //   and a sweep over the sorted positions q of a column, final_cts starting as zeros:
@@ -36,26 +36,16 @@
 // buffer) and reported through one device word, the smallest (column, step) / (step, slot) of a violation (an atomicMin: its result
 // does not depend on the order of arrival); the call then returns no vector.
 //
-// The sort kernels stand beside k_rw_* and are not shared with them: there the key of a position is one of n_slots interleaved
-// address columns of two widths, here it is one of a batch of columns chosen by blockIdx.y, and k_rw_* keep the registers they have.
-//
-// Transient device memory for a batch of B columns, with tiles = ceil(n / TS_TILE), D1 = min(M, 65536), D2 = ceil(M / 65536)
+// Transient device memory for a batch of B columns, with tiles = ceil(n / RP_TILE), D1 = min(M, 65536), D2 = ceil(M / 65536)
 // (0 for one pass), D = max(D1, D2) rounded up to even:
 //   B (6 tiles D histograms and bases + 2 n ranks), and for two passes B (4 D counts + 8 n sorted steps + 4 n sorted keys) more.
 // B is the largest count that keeps 6 tiles D B under 256 MiB (one column at least):
 //   96 MiB + 16 MiB + 98 MiB at n = 2^20, 8 columns (4 slots) and M = 2^20.
 #include "common.hpp"
-#include "lasso_walk.hip.hpp"
+#include "radix_pass.hip.hpp"
 
-static constexpr int TS_TILE = COZK_LASSO_TILE;  // positions per tile: in-tile ranks (< 32768) and counts (<= 32768) fit 16 bits
-static constexpr int TS_PT = 256;
-static constexpr int TS_CHUNK = 4096;            // digits staged in LDS at a time (two buffers: one walked, one being staged)
-static constexpr int TS_SCAN_PT = 1024;          // the one-workgroup scan of a column's counts
-static constexpr int TS_SCAN_ROWS = 65536 / TS_SCAN_PT;
-static_assert(TS_SCAN_ROWS * (TS_SCAN_PT / 64) == TS_SCAN_PT, "k_ts_offsets scans one (row, wave) total per thread");
 static constexpr size_t TS_MAX_COLS = COZK_TIME_COUNTERS_MAX_COLS;
 static constexpr size_t TS_TRANSIENT_CAP = (size_t)256 << 20;  // tile histograms + tile bases of one batch of columns
-static_assert(TS_TILE <= 32768 && TS_TILE % TS_CHUNK == 0 && TS_CHUNK % 64 == 0, "in-tile counts must fit 16 bits");
 static_assert(2 * COZK_RW_MEMORY_MAX_SLOTS <= COZK_TIME_COUNTERS_MAX_COLS, "the witness is two columns per slot");
 
 struct TsCol {
@@ -73,157 +63,86 @@ __device__ __forceinline__ uint32_t ts_key(const TsCol& col, uint32_t j, uint32_
 }
 
 // order: the steps of every column of the batch in the order of the previous pass; null = step p at position p
-__global__ void __launch_bounds__(TS_PT) k_ts_rank(const TsCol* __restrict__ cols, size_t n, uint32_t M, int ts, uint32_t col0, const uint32_t* __restrict__ order,
+__global__ void __launch_bounds__(RP_PT) k_ts_rank(const TsCol* __restrict__ cols, size_t n, uint32_t M, int ts, uint32_t col0, const uint32_t* __restrict__ order,
                                                    int shift, uint32_t Dp, int key_bits, uint16_t* __restrict__ rank, uint16_t* __restrict__ hist,
                                                    unsigned long long* __restrict__ viol) {
-    __shared__ uint16_t tab[65536];
-    __shared__ uint16_t keys[2][TS_CHUNK];
-    uint32_t* tab32 = reinterpret_cast<uint32_t*>(tab);
     const TsCol col = cols[blockIdx.y];
     const size_t tile = blockIdx.x, at = (size_t)blockIdx.y * n;
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (uint32_t i = threadIdx.x; i < Dp / 2; i += TS_PT) tab32[i] = 0;
-    const size_t begin = tile * (size_t)TS_TILE, end = begin + TS_TILE < n ? begin + TS_TILE : n;
-    // the digits of the chunk at c0, by the threads first, first + stride, ...
-    auto stage = [&](size_t c0, uint16_t* dst, unsigned first, unsigned stride) {
-#pragma unroll 4
-        for (uint32_t e = first; e < (uint32_t)TS_CHUNK; e += stride) {
-            const size_t p = c0 + e;
-            if (p < end) {
-                const uint32_t j = order ? order[at + p] : (uint32_t)p;
-                bool bad;
-                const uint32_t key = ts_key(col, j, M, ts, &bad);
-                if (!order && bad) {
-                    const unsigned long long c = col0 + blockIdx.y;
-                    atomicMin(viol, ts ? ((unsigned long long)j << 32) | (c >> 1) : (c << 32) | j);
-                }
-                dst[e] = (uint16_t)(key >> shift);
-            }
+    auto digit = [&](size_t p) {
+        const uint32_t j = order ? order[at + p] : (uint32_t)p;
+        bool bad;
+        const uint32_t key = ts_key(col, j, M, ts, &bad);
+        if (!order && bad) {
+            const unsigned long long c = col0 + blockIdx.y;
+            atomicMin(viol, ts ? ((unsigned long long)j << 32) | (c >> 1) : (c << 32) | j);
         }
+        return (uint16_t)(key >> shift);
     };
-    stage(begin, keys[0], threadIdx.x, TS_PT);
-    __syncthreads();  // the first chunk's digits are staged and the table is clear
-    int cur = 0;
-    for (size_t c0 = begin; c0 < end; c0 += TS_CHUNK, cur ^= 1) {  // every bound of this loop is uniform over the workgroup
-        if (wave == 0) {
-            const uint32_t cnt = end - c0 < (size_t)TS_CHUNK ? (uint32_t)(end - c0) : (uint32_t)TS_CHUNK;
-            for (uint32_t k0 = 0; k0 < cnt; k0 += 64) {
-                const bool valid = k0 + lane < cnt;
-                const uint32_t r = lw_walk_step(tab, valid, valid ? keys[cur][k0 + lane] : 0, key_bits, lane);
-                if (valid) rank[at + c0 + k0 + lane] = (uint16_t)r;
-            }
-        } else if (c0 + TS_CHUNK < end) {  // the other waves stage the next chunk beside the walk
-            stage(c0 + TS_CHUNK, keys[cur ^ 1], threadIdx.x - 64, TS_PT - 64);
-        }
-        __syncthreads();  // the walk has left keys[cur], which the chunk after the next one rewrites; keys[cur ^ 1] is staged
-    }
-    uint32_t* out = reinterpret_cast<uint32_t*>(hist + ((size_t)blockIdx.y * gridDim.x + tile) * Dp);
-    for (uint32_t i = threadIdx.x; i < Dp / 2; i += TS_PT) out[i] = tab32[i];
+    rp_rank_tile(tile, n, digit, Dp, key_bits, rank + at, hist + ((size_t)blockIdx.y * gridDim.x + tile) * Dp);
 }
 
 // count: the batch's counts, `stride` words per column; null = the column's final_cts (one pass: D = M)
-__global__ void __launch_bounds__(TS_PT) k_ts_scan(const TsCol* __restrict__ cols, uint32_t D, uint32_t Dp, size_t tiles, const uint16_t* __restrict__ hist,
+__global__ void __launch_bounds__(RP_PT) k_ts_scan(const TsCol* __restrict__ cols, uint32_t D, uint32_t Dp, size_t tiles, const uint16_t* __restrict__ hist,
                                                    uint32_t* __restrict__ bases, uint32_t* __restrict__ count, uint32_t stride) {
-    const uint32_t d = blockIdx.x * TS_PT + threadIdx.x;
+    const uint32_t d = blockIdx.x * RP_PT + threadIdx.x;
     if (d >= D) return;
     const size_t row = (size_t)blockIdx.y * tiles * Dp + d;
-    uint32_t run = 0;
-    for (size_t t = 0; t < tiles; t++) {
-        bases[row + t * Dp] = run;
-        run += hist[row + t * Dp];
-    }
+    const uint32_t run = rp_scan_tiles(tiles, Dp, hist + row, bases + row);
     if (count)
         count[(size_t)blockIdx.y * stride + d] = run;
     else
         cols[blockIdx.y].fc[d] = run;
 }
 
-__global__ void __launch_bounds__(TS_PT) k_ts_finish(const TsCol* __restrict__ cols, size_t n, uint32_t M, int ts, uint32_t Dp, size_t tiles,
+__global__ void __launch_bounds__(RP_PT) k_ts_finish(const TsCol* __restrict__ cols, size_t n, uint32_t M, int ts, uint32_t Dp, size_t tiles,
                                                      const uint16_t* __restrict__ rank, const uint32_t* __restrict__ bases) {
-    const size_t j = (size_t)blockIdx.x * TS_PT + threadIdx.x;
+    const size_t j = (size_t)blockIdx.x * RP_PT + threadIdx.x;
     if (j >= n) return;
     const TsCol col = cols[blockIdx.y];
     bool bad;
     const uint32_t key = ts_key(col, (uint32_t)j, M, ts, &bad);
-    col.rc[j] = bases[((size_t)blockIdx.y * tiles + j / TS_TILE) * Dp + key] + rank[(size_t)blockIdx.y * n + j];
+    col.rc[j] = bases[((size_t)blockIdx.y * tiles + j / RP_TILE) * Dp + key] + rank[(size_t)blockIdx.y * n + j];
 }
 
-// a column's count[0..D) -> its exclusive prefix sums, in place, D <= 65536: up to TS_SCAN_ROWS rows of TS_SCAN_PT values, a value
-// per thread and row (coalesced).  A wave scan per row leaves each value's prefix inside its wave in place; one workgroup scan over
-// the (row, wave) totals, which are in the order of the values; then every value takes the prefix of its wave.
-__global__ void __launch_bounds__(TS_SCAN_PT) k_ts_offsets(uint32_t D, uint32_t* __restrict__ count, uint32_t stride) {
-    __shared__ uint32_t sh[TS_SCAN_PT], pre[TS_SCAN_PT];
-    const unsigned t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int rows = (int)((D + TS_SCAN_PT - 1) / TS_SCAN_PT);  // uniform over the workgroup
-    count += (size_t)blockIdx.x * stride;
-    pre[t] = 0;
-    __syncthreads();
-#pragma unroll 8
-    for (int r = 0; r < rows; r++) {
-        const uint32_t d = (uint32_t)r * TS_SCAN_PT + t;
-        const uint32_t x = d < D ? count[d] : 0;
-        uint32_t v = x;
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(v, off);
-            if ((int)lane >= off) v += y;
-        }
-        if (d < D) count[d] = v - x;
-        if (lane == 63) pre[r * (TS_SCAN_PT / 64) + wave] = v;
-    }
-    __syncthreads();
-    uint32_t x = pre[t];  // inclusive scan of the totals over the workgroup
-    sh[t] = x;
-    __syncthreads();
-    for (unsigned off = 1; off < TS_SCAN_PT; off <<= 1) {
-        const uint32_t y = t >= off ? sh[t - off] : 0;
-        __syncthreads();
-        x += y;
-        sh[t] = x;
-        __syncthreads();
-    }
-    pre[t] = t ? sh[t - 1] : 0;  // every thread read its own total before the first barrier of the scan
-    __syncthreads();
-#pragma unroll 8
-    for (int r = 0; r < rows; r++) {
-        const uint32_t d = (uint32_t)r * TS_SCAN_PT + t;
-        if (d < D) count[d] += pre[r * (TS_SCAN_PT / 64) + wave];
-    }
+// count: the batch's counts, `stride` words per column
+__global__ void __launch_bounds__(RP_SCAN_PT) k_ts_offsets(uint32_t D, uint32_t* __restrict__ count, uint32_t stride) {
+    rp_offsets(D, count + (size_t)blockIdx.x * stride);
 }
 
 // key_out: null, or where the keys go in the new order
-__global__ void __launch_bounds__(TS_PT) k_ts_scatter(const TsCol* __restrict__ cols, size_t n, uint32_t M, int ts, const uint32_t* __restrict__ order, int shift,
+__global__ void __launch_bounds__(RP_PT) k_ts_scatter(const TsCol* __restrict__ cols, size_t n, uint32_t M, int ts, const uint32_t* __restrict__ order, int shift,
                                                       uint32_t Dp, size_t tiles, const uint16_t* __restrict__ rank, const uint32_t* __restrict__ bases,
                                                       const uint32_t* __restrict__ offset, uint32_t stride, uint32_t* __restrict__ order_out,
                                                       uint32_t* __restrict__ key_out) {
-    const size_t p = (size_t)blockIdx.x * TS_PT + threadIdx.x, at = (size_t)blockIdx.y * n;
+    const size_t p = (size_t)blockIdx.x * RP_PT + threadIdx.x, at = (size_t)blockIdx.y * n;
     if (p >= n) return;
     const uint32_t j = order ? order[at + p] : (uint32_t)p;
     bool bad;
     const uint32_t key = ts_key(cols[blockIdx.y], j, M, ts, &bad);
     const uint32_t d = (key >> shift) & 0xffff;
     // a permutation of 0..n: the counts are of these same digits
-    const size_t pos = at + offset[(size_t)blockIdx.y * stride + d] + bases[((size_t)blockIdx.y * tiles + p / TS_TILE) * Dp + d] + rank[at + p];
+    const size_t pos = at + offset[(size_t)blockIdx.y * stride + d] + bases[((size_t)blockIdx.y * tiles + p / RP_TILE) * Dp + d] + rank[at + p];
     order_out[pos] = j;
     if (key_out) key_out[pos] = key;
 }
 
-__global__ void __launch_bounds__(TS_PT) k_ts_seg_start(const TsCol* __restrict__ cols, size_t n, const uint32_t* __restrict__ skey) {
-    const size_t q = (size_t)blockIdx.x * TS_PT + threadIdx.x;
+__global__ void __launch_bounds__(RP_PT) k_ts_seg_start(const TsCol* __restrict__ cols, size_t n, const uint32_t* __restrict__ skey) {
+    const size_t q = (size_t)blockIdx.x * RP_PT + threadIdx.x;
     if (q >= n) return;
     skey += (size_t)blockIdx.y * n;
     const uint32_t key = skey[q];
     if (q == 0 || skey[q - 1] != key) cols[blockIdx.y].fc[key] = (uint32_t)q;
 }
 
-__global__ void __launch_bounds__(TS_PT) k_ts_seg_rank(const TsCol* __restrict__ cols, size_t n, const uint32_t* __restrict__ skey, const uint32_t* __restrict__ order) {
-    const size_t q = (size_t)blockIdx.x * TS_PT + threadIdx.x, at = (size_t)blockIdx.y * n;
+__global__ void __launch_bounds__(RP_PT) k_ts_seg_rank(const TsCol* __restrict__ cols, size_t n, const uint32_t* __restrict__ skey, const uint32_t* __restrict__ order) {
+    const size_t q = (size_t)blockIdx.x * RP_PT + threadIdx.x, at = (size_t)blockIdx.y * n;
     if (q >= n) return;
     const TsCol col = cols[blockIdx.y];
     col.rc[order[at + q]] = (uint32_t)q - col.fc[skey[at + q]];
 }
 
-__global__ void __launch_bounds__(TS_PT) k_ts_seg_count(const TsCol* __restrict__ cols, size_t n, const uint32_t* __restrict__ skey) {
-    const size_t q = (size_t)blockIdx.x * TS_PT + threadIdx.x;
+__global__ void __launch_bounds__(RP_PT) k_ts_seg_count(const TsCol* __restrict__ cols, size_t n, const uint32_t* __restrict__ skey) {
+    const size_t q = (size_t)blockIdx.x * RP_PT + threadIdx.x;
     if (q >= n) return;
     skey += (size_t)blockIdx.y * n;
     const uint32_t key = skey[q];
@@ -249,13 +168,11 @@ static int ts_counters(cozk_ctx* ctx, int ts, const std::vector<const cozk_vec*>
         TsCol hc[TS_MAX_COLS];
         for (size_t c = 0; c < nc; c++) hc[c] = TsCol{(const uint32_t*)src[c]->d, (uint32_t*)(*rc_out[c])->d, (uint32_t*)(*fc_out[c])->d, gmr[c]};
         const uint32_t m = (uint32_t)M;
-        const size_t tiles = (n + TS_TILE - 1) / TS_TILE;
-        const int passes = M > 65536 ? 2 : 1;
-        const uint32_t D[2] = {M < 65536 ? m : 65536u, passes == 2 ? ((m - 1) >> 16) + 1 : 0u};
-        const uint32_t Dmax = ((D[0] > D[1] ? D[0] : D[1]) + 1) & ~1u;
-        // the columns go in batches whose histograms (u16) and bases (u32) stay under the cap; one column is the least
-        size_t batch = TS_TRANSIENT_CAP / (tiles * Dmax * (sizeof(uint16_t) + sizeof(uint32_t)));
-        batch = batch < 1 ? 1 : (batch > nc ? nc : batch);
+        const RadixPlan plan(n, M);
+        const size_t tiles = plan.tiles;
+        const int passes = plan.passes;
+        const uint32_t Dmax = plan.Dmax;
+        const size_t batch = radix_batch(TS_TRANSIENT_CAP, tiles, Dmax, nc);
         d_cols = ctx_dev_alloc(ctx, nc * sizeof(TsCol));
         d_rank = ctx_dev_alloc(ctx, batch * n * sizeof(uint16_t));
         d_hist = ctx_dev_alloc(ctx, batch * tiles * Dmax * sizeof(uint16_t));
@@ -265,54 +182,49 @@ static int ts_counters(cozk_ctx* ctx, int ts, const std::vector<const cozk_vec*>
             d_skey = ctx_dev_alloc(ctx, batch * n * sizeof(uint32_t));
             d_count = ctx_dev_alloc(ctx, batch * Dmax * sizeof(uint32_t));
         }
-        d_viol = ctx_dev_alloc(ctx, sizeof(unsigned long long));
-        unsigned long long* pin = (unsigned long long*)ctx_pinned(ctx, sizeof(unsigned long long));
+        unsigned long long* viol = viol_begin(ctx, &d_viol);
         hipStream_t st = ctx->stream;
         HIP_TRY(hipMemcpyAsync(d_cols, hc, nc * sizeof(TsCol), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(d_viol, 0xff, sizeof(unsigned long long), st));
-        const unsigned pos_grid = (unsigned)((n + TS_PT - 1) / TS_PT);
+        const unsigned pos_grid = (unsigned)((n + RP_PT - 1) / RP_PT);
         uint16_t *rank = (uint16_t*)d_rank, *hist = (uint16_t*)d_hist;
         uint32_t *bases = (uint32_t*)d_bases, *count = (uint32_t*)d_count, *skey = (uint32_t*)d_skey;
         for (size_t c0 = 0; c0 < nc; c0 += batch) {
             const unsigned nb = (unsigned)(nc - c0 < batch ? nc - c0 : batch);
             const TsCol* dc = (const TsCol*)d_cols + c0;
             for (int k = 0; k < passes; k++) {
-                const uint32_t Dp = (D[k] + 1) & ~1u;  // row stride of the histograms: whole 32-bit words
+                const uint32_t D = plan.D[k], Dp = plan.Dp(k);
                 const uint32_t* in = k ? (const uint32_t*)d_ord[0] : nullptr;
-                int key_bits = 0;
-                while (((uint32_t)1 << key_bits) < D[k]) key_bits++;
-                k_ts_rank<<<dim3((unsigned)tiles, nb), TS_PT, 0, st>>>(dc, n, m, ts, (uint32_t)c0, in, 16 * k, Dp, key_bits, rank, hist, (unsigned long long*)d_viol);
+                k_ts_rank<<<dim3((unsigned)tiles, nb), RP_PT, 0, st>>>(dc, n, m, ts, (uint32_t)c0, in, 16 * k, Dp, plan.key_bits(k), rank, hist, viol);
                 HIP_TRY(hipGetLastError());
-                k_ts_scan<<<dim3((D[k] + TS_PT - 1) / TS_PT, nb), TS_PT, 0, st>>>(dc, D[k], Dp, tiles, hist, bases, count, Dmax);
+                k_ts_scan<<<dim3((D + RP_PT - 1) / RP_PT, nb), RP_PT, 0, st>>>(dc, D, Dp, tiles, hist, bases, count, Dmax);
                 HIP_TRY(hipGetLastError());
                 if (passes == 1) {
-                    k_ts_finish<<<dim3(pos_grid, nb), TS_PT, 0, st>>>(dc, n, m, ts, Dp, tiles, rank, bases);
+                    k_ts_finish<<<dim3(pos_grid, nb), RP_PT, 0, st>>>(dc, n, m, ts, Dp, tiles, rank, bases);
                     HIP_TRY(hipGetLastError());
                     break;
                 }
-                k_ts_offsets<<<nb, TS_SCAN_PT, 0, st>>>(D[k], count, Dmax);
+                k_ts_offsets<<<nb, RP_SCAN_PT, 0, st>>>(D, count, Dmax);
                 HIP_TRY(hipGetLastError());
-                k_ts_scatter<<<dim3(pos_grid, nb), TS_PT, 0, st>>>(dc, n, m, ts, in, 16 * k, Dp, tiles, rank, bases, count, Dmax, (uint32_t*)d_ord[k], k ? skey : nullptr);
+                k_ts_scatter<<<dim3(pos_grid, nb), RP_PT, 0, st>>>(dc, n, m, ts, in, 16 * k, Dp, tiles, rank, bases, count, Dmax, (uint32_t*)d_ord[k], k ? skey : nullptr);
                 HIP_TRY(hipGetLastError());
             }
             if (passes == 2) {
                 for (unsigned c = 0; c < nb; c++) HIP_TRY(hipMemsetAsync(hc[c0 + c].fc, 0, M * sizeof(uint32_t), st));
-                k_ts_seg_start<<<dim3(pos_grid, nb), TS_PT, 0, st>>>(dc, n, skey);
+                k_ts_seg_start<<<dim3(pos_grid, nb), RP_PT, 0, st>>>(dc, n, skey);
                 HIP_TRY(hipGetLastError());
-                k_ts_seg_rank<<<dim3(pos_grid, nb), TS_PT, 0, st>>>(dc, n, skey, (const uint32_t*)d_ord[1]);
+                k_ts_seg_rank<<<dim3(pos_grid, nb), RP_PT, 0, st>>>(dc, n, skey, (const uint32_t*)d_ord[1]);
                 HIP_TRY(hipGetLastError());
-                k_ts_seg_count<<<dim3(pos_grid, nb), TS_PT, 0, st>>>(dc, n, skey);
+                k_ts_seg_count<<<dim3(pos_grid, nb), RP_PT, 0, st>>>(dc, n, skey);
                 HIP_TRY(hipGetLastError());
             }
         }
-        HIP_TRY(hipMemcpyAsync(pin, d_viol, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (*pin != ~0ull) {
+        const unsigned long long bad = viol_read(ctx, viol);
+        if (bad != ~0ull) {
             char buf[160];
             if (ts)
-                snprintf(buf, sizeof buf, "timestamp_range_witness: step %llu, slot %llu: t_read is greater than the step", *pin >> 32, *pin & 0xffffffffull);
+                snprintf(buf, sizeof buf, "timestamp_range_witness: step %llu, slot %llu: t_read is greater than the step", bad >> 32, bad & 0xffffffffull);
             else
-                snprintf(buf, sizeof buf, "time_counters: column %llu, step %llu: the key is >= M = %zu", *pin >> 32, *pin & 0xffffffffull, M);
+                snprintf(buf, sizeof buf, "time_counters: column %llu, step %llu: the key is >= M = %zu", bad >> 32, bad & 0xffffffffull, M);
             throw CozkError(COZK_ERR_INVALID_ARG, buf);
         }
     });
@@ -339,9 +251,9 @@ __device__ __forceinline__ fe ts_small(uint32_t v) {
     x.l[0] = v;
     return x;
 }
-__global__ void __launch_bounds__(TS_PT) k_ts_range_leaves(TsLeafCols a, uint32_t n_slots, size_t n, fe g1r, fe g2r, fe g2, fe tau, fe* __restrict__ out,
+__global__ void __launch_bounds__(RP_PT) k_ts_range_leaves(TsLeafCols a, uint32_t n_slots, size_t n, fe g1r, fe g2r, fe g2, fe tau, fe* __restrict__ out,
                                                            unsigned long long* __restrict__ viol) {
-    const size_t j = (size_t)blockIdx.x * TS_PT + threadIdx.x;
+    const size_t j = (size_t)blockIdx.x * RP_PT + threadIdx.x;
     if (j >= n) return;
     const uint32_t s = blockIdx.y;
     uint32_t x = a.t_read[s][j];
@@ -392,18 +304,15 @@ int cozk_timestamp_range_leaves(cozk_ctx* ctx, const cozk_vec* const* t_read, co
             t.l[2 * i] = (uint32_t)tau[i], t.l[2 * i + 1] = (uint32_t)(tau[i] >> 32);
         }
         const fe g2 = Fr::mul(g, g);
-        d_viol = ctx_dev_alloc(ctx, sizeof(unsigned long long));
-        unsigned long long* pin = (unsigned long long*)ctx_pinned(ctx, sizeof(unsigned long long));
+        unsigned long long* viol = viol_begin(ctx, &d_viol);
         hipStream_t st = ctx->stream;
-        HIP_TRY(hipMemsetAsync(d_viol, 0xff, sizeof(unsigned long long), st));
-        k_ts_range_leaves<<<dim3((unsigned)((n + TS_PT - 1) / TS_PT), (unsigned)n_slots), TS_PT, 0, st>>>(
-            h, (uint32_t)n_slots, n, Fr::to_mont(Fr::add(g, Fr::one())), Fr::to_mont(g2), g2, t, (fe*)out->d + offset, (unsigned long long*)d_viol);
+        k_ts_range_leaves<<<dim3((unsigned)((n + RP_PT - 1) / RP_PT), (unsigned)n_slots), RP_PT, 0, st>>>(
+            h, (uint32_t)n_slots, n, Fr::to_mont(Fr::add(g, Fr::one())), Fr::to_mont(g2), g2, t, (fe*)out->d + offset, viol);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(pin, d_viol, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (*pin != ~0ull) {
+        const unsigned long long bad = viol_read(ctx, viol);
+        if (bad != ~0ull) {
             char buf[160];
-            snprintf(buf, sizeof buf, "timestamp_range_leaves: step %llu, slot %llu: t_read is greater than the step", *pin >> 32, *pin & 0xffffffffull);
+            snprintf(buf, sizeof buf, "timestamp_range_leaves: step %llu, slot %llu: t_read is greater than the step", bad >> 32, bad & 0xffffffffull);
             throw CozkError(COZK_ERR_INVALID_ARG, buf);
         }
     });

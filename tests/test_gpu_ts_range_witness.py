@@ -124,6 +124,21 @@ def test_sixteen_columns_in_two_batches(cozk, ctx, TS, T):
     _refused(cozk, "column 15, step 5:", lambda: TS.time_counters(ctx, vecs, M))
 
 
+@pytest.mark.parametrize("M", [3, 65536])
+def test_time_counters_meet_the_lasso_witness_on_one_key_column(cozk, ctx, TS, T, M):
+    """Both routes to a Lasso counter run through one scan of the tile histograms: the same keys as a column of cozk_time_counters and
+    as the one dimension of cozk_lasso_witness (one memory used at every step, an identity subtable of M entries) give equal
+    read_cts and final_cts.  n = T + 65: two tiles, the last wave step partial; M = 65536 is the largest table both accept and the
+    counters' one-pass path."""
+    n = T + 65
+    keys = np.random.default_rng(335).integers(0, M, size=n, dtype=np.uint32)
+    col = _u32(cozk, ctx, keys)
+    rc, fc = TS.time_counters(ctx, [col], M)
+    l_rc, l_E, l_fc = cozk.lasso_witness(ctx, [col], [_u32(cozk, ctx, np.arange(M))], [None], [0], [0])
+    assert np.array_equal(rc[0].to_numpy(), l_rc[0].to_numpy()) and np.array_equal(fc[0].to_numpy(), l_fc[0].to_numpy())
+    assert rc[0].to_numpy().shape == (n,) and fc[0].to_numpy().shape == (M,) and int(fc[0].to_numpy().sum()) == n
+
+
 def _jolt(seed, n, MEM, store_pct=30, n_regs=32):
     """the Jolt-shaped instance of tests/test_gpu_rw_witness.py: rs1, rs2 read; rd writes at every step; ram writes where the store
     flag is set"""
