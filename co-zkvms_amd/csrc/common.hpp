@@ -128,6 +128,11 @@ struct DevPool {
     std::unordered_map<size_t, std::vector<void*>> parked;
     std::unordered_map<void*, size_t> live;  // block -> size class
     size_t parked_bytes = 0;
+    size_t live_bytes = 0, peak_bytes = 0;  // handed out now, and the most since a caller last set peak_bytes = live_bytes (a phase's peak)
+    void count(size_t c) {
+        live_bytes += c;
+        if (live_bytes > peak_bytes) peak_bytes = live_bytes;
+    }
     static size_t size_class(size_t bytes) {  // four classes per octave: <= 25 % slack
         if (bytes <= 256) return 256;
         size_t top = (size_t)1 << (63 - __builtin_clzll((unsigned long long)bytes));
@@ -148,6 +153,7 @@ struct DevPool {
             it->second.pop_back();
             parked_bytes -= c;
             live[p] = c;
+            count(c);
             return p;
         }
         void* p = nullptr;
@@ -158,6 +164,7 @@ struct DevPool {
             HIP_TRY(hipMalloc(&p, c));
         }
         live[p] = c;
+        count(c);
         return p;
     }
     // false: not one of ours
@@ -166,6 +173,7 @@ struct DevPool {
         if (it == live.end()) return false;
         parked[it->second].push_back(p);
         parked_bytes += it->second;
+        live_bytes -= it->second;
         live.erase(it);
         return true;
     }

@@ -911,6 +911,7 @@ int cozk_worker_spartan_second_sumcheck(cozk_ctx* ctx, const cozk_worker_params*
 #include "host/flow_harness.hpp"
 #include "host/ts_range_proof.hpp"
 #include "host/rw_memory_proof.hpp"
+#include "host/memory_proof.hpp"
 #include "host/shamir_gp.hpp"
 #include "host/shamir_harness.hpp"
 #include "host/shamir_spartan.hpp"

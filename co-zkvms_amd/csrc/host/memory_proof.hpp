@@ -1,0 +1,283 @@
+// In-process harness of party 0's whole ReadWriteMemoryProof in the reference's order (Rep3ReadWriteMemoryProver::prove,
+// co-jolt/src/jolt/vm/read_write_memory/worker.rs:54-180): the memory check, the output check (prove_outputs, :110-175), the timestamp
+// range check, under one transcript and one opening accumulator, with ONE reduce_and_prove.  The memory check and the range check
+// are the steps of rw_memory_proof.hpp, called as they stand, so everything up to and including the claims at r_if is byte for byte
+// cozk_rw_proof's proof at the same config.  New here is the output check over the CONSISTENT v_final:
+//     sum_x eq(r_eq, x) io_range(x) (v_final(x) - v_io(x)) = 0,   degree 3, HighToLow, then one opening of v_final at the sumcheck's point.
+// The io window is [io_start, io_start + io_len) words and v_io is v_final over it, so an honest run verifies.  windowed = 1: the rounds
+// are cozk_output_check_* over the compact columns (output_check.inc); windowed = 0: the chained flow's composition (flow_harness.hpp)
+// on Fr copies of eq, io_range, v_io and v_final -- three MEM-entry Fr polynomials bound every round -- kept for the A/B, the same bytes.
+// Either way the messages are prove_arbitrary_worker's (prove_arbitrary_rounds, the one round loop) and coordinate_prove_arbitrary serves
+// them.  jolt-core is not in the reference tree: PARITY UNPINNED, pinned by the verifier below and tests/memory_proof_ref.py.
+#pragma once
+
+struct cozk_memory_proof : HarnessHandle {
+    cozk_memory_proof_config cfg;
+    cozk_rw_proof rw;                  // the trace, the witness, party 0 and the SRS: what cozk_rw_proof_create builds for the same fields
+    std::vector<uint32_t> v_io_clear;  // the program's public output: the verifier evaluates it itself
+    VecH v_io;                         // U32, io_len words
+    VecH io_range_fr, v_io_fr, v_final_fr;  // windowed = 0: the Fr copies of MEM entries (made in create, as the flow's setup makes its own)
+    double t_out = 0;
+    uint64_t out_peak_bytes = 0;
+};
+
+namespace {
+
+struct OutputCheckH {
+    cozk_output_check* h = nullptr;
+    OutputCheckH() = default;
+    OutputCheckH(const OutputCheckH&) = delete;
+    OutputCheckH& operator=(const OutputCheckH&) = delete;
+    ~OutputCheckH() { cozk_output_check_free(h); }
+};
+
+struct MemoryProof {
+    std::vector<PST13Commitment> commitments;
+    MemCheckProof mem;
+    SumcheckProof outputs;
+    std::vector<fe> outputs_claims;
+    bool with_ts = false;
+    TsRangeProof range;
+    ReducedOpeningProof reduced;
+    size_t prefix_len = 0;
+    Bytes serialize() {
+        Writer w;
+        w.u64(commitments.size());
+        for (auto& c : commitments) c.write(w);
+        mem.write(w);
+        prefix_len = w.b.size();
+        outputs.write(w);
+        w.vec_fr(outputs_claims);
+        if (with_ts) range.write(w);
+        reduced.write(w);
+        return w.b;
+    }
+};
+
+// what the phase holds on the device beyond what it found: the pool's peak over the phase plus the growth of the two scratch buffers
+struct PhasePeak {
+    cozk_ctx* ctx;
+    size_t live0, scratch0;
+    explicit PhasePeak(cozk_ctx* c) : ctx(c), live0(c->pool.live_bytes), scratch0(c->scratch.cap + c->scratch2.cap) { c->pool.peak_bytes = c->pool.live_bytes; }
+    uint64_t bytes() const { return (uint64_t)(ctx->pool.peak_bytes - live0) + (uint64_t)(ctx->scratch.cap + ctx->scratch2.cap - scratch0); }
+};
+
+// the output check's sumcheck, windowed: the device calls bind inside the next round call, so the loop's bind step only keeps r
+std::vector<fe> memory_proof_outputs_windowed(cozk_memory_proof* h, WorkerEnv& env, const RwProofParty& ps, const std::vector<fe>& r_eq) {
+    const std::vector<uint64_t> wabi = to_abi(r_eq);
+    OutputCheckH oc;
+    rc_check(cozk_output_check_create(env.ctx, ps.v_final.h, h->v_io.h, (size_t)h->cfg.io_start, wabi.data(), &oc.h), env.ctx, "output_check_create");
+    uint64_t pending[4];
+    bool have = false;
+    std::vector<fe> r = prove_arbitrary_rounds(
+        env, Fr::zero(), h->cfg.log_mem, 3, false,
+        [&](uint64_t* ev) { rc_check(cozk_output_check_round(oc.h, have ? pending : nullptr, ev), env.ctx, "output_check_round"); },
+        [&](const uint64_t rr[4]) {
+            memcpy(pending, rr, sizeof pending);
+            have = true;
+        });
+    uint64_t fin[12];
+    rc_check(cozk_output_check_final(oc.h, pending, fin), env.ctx, "output_check_final");  // the last bind, as prove_arbitrary_worker leaves its polynomials
+    return r;
+}
+
+// ... dense: the flow's composition on Fr copies (flow_harness.hpp, phase 4)
+std::vector<fe> memory_proof_outputs_dense(cozk_memory_proof* h, WorkerEnv& env, const std::vector<fe>& r_eq) {
+    const std::vector<uint64_t> wabi = to_abi(r_eq);
+    cozk_vec* eqv = nullptr;
+    rc_check(cozk_eq_evals(env.ctx, wabi.data(), (int)r_eq.size(), &eqv), env.ctx, "eq_evals");
+    VecH eqh(eqv);
+    PolyH pe = plain_poly(env.ctx, eqh), pr = plain_poly(env.ctx, h->io_range_fr), pio = plain_poly(env.ctx, h->v_io_fr), pvf = plain_poly(env.ctx, h->v_final_fr);
+    const cozk_poly* two[2] = {pvf.h, pio.h};
+    const std::vector<uint64_t> cfa = to_abi({Fr::one(), Fr::neg(Fr::one())});
+    cozk_poly* pd = nullptr;
+    rc_check(cozk_poly_linear_combination(env.ctx, two, cfa.data(), 2, env.mode, env.party, &pd), env.ctx, "v_final - v_io");
+    PolyH pdh(pd);
+    std::vector<cozk_poly*> sp = {pe.h, pr.h, pdh.h};
+    return prove_arbitrary_worker(env, Fr::zero(), h->cfg.log_mem, sp, 3).r;
+}
+
+void memory_proof_worker_main(cozk_memory_proof* h, RwProofParty& ps, StarNetWorker* star) {
+    WorkerEnv env = rw_proof_env(ps, star);
+    const TsRangeCols range = ts_range_columns(ps, ps.iota_n);
+    Rep3ProverOpeningAccumulator acc;
+    // ---- 1-4. the memory check: cozk_rw_proof's steps
+    const double t4 = rw_proof_memory_check_worker(&h->rw, ps, env, range, acc);
+    const double t5 = now_ms();
+    // ---- the output check: r_eq, log_mem rounds, one opening of v_final at the sumcheck's point
+    {
+        Bytes req = star->receive_request();
+        Reader rd(req);
+        const std::vector<fe> r_eq = rd.vec_fr();
+        const double t0 = now_ms();
+        std::vector<fe> r;
+        {
+            PhasePeak peak(env.ctx);
+            r = h->cfg.windowed ? memory_proof_outputs_windowed(h, env, ps, r_eq) : memory_proof_outputs_dense(h, env, r_eq);
+            h->out_peak_bytes = peak.bytes();
+        }
+        compact_open_worker(env, acc, {ps.v_final.h}, r, false);
+        h->t_out = now_ms() - t0;
+    }
+    // ---- 5, 6. the range check and ONE reduce_and_prove: cozk_rw_proof's steps
+    rw_proof_range_check_and_open_worker(&h->rw, ps, env, range, acc, t5 - t4);
+}
+
+void memory_proof_coordinate(cozk_memory_proof* h, StarNetCoordinator& net, MemoryProof& proof) {
+    const cozk_rw_proof_config& c = h->rw.cfg;
+    Transcript tr("cozk-rw-memory");
+    rw_proof_coordinate_memory_check(c, net, tr, proof.commitments, proof.mem);
+    {
+        std::vector<fe> r_eq = tr.challenge_vector((size_t)c.log_mem);
+        Writer w;
+        w.vec_fr(r_eq);
+        net.broadcast_request(w.b);
+        (void)coordinate_prove_arbitrary(net, tr, c.log_mem, proof.outputs.compressed_polys);
+        proof.outputs_claims = Rep3ProverOpeningAccumulator::receive_claims(net, tr);
+    }
+    rw_proof_coordinate_range_check_and_open(c, net, tr, proof.with_ts, proof.range, proof.reduced);
+}
+
+// io_range(r) and v_io(r) over the window only: O(W m), not MEM
+void memory_proof_window_evals(const cozk_memory_proof* h, const std::vector<fe>& r, fe& range_r, fe& v_io_r) {
+    const size_t m = r.size(), lo = (size_t)h->cfg.io_start;
+    const fe one = Fr::one();
+    std::vector<fe> omr(m);
+    for (size_t i = 0; i < m; i++) omr[i] = Fr::sub(one, r[i]);
+    range_r = v_io_r = Fr::zero();
+    for (size_t j = 0; j < h->v_io_clear.size(); j++) {
+        const size_t x = lo + j;
+        fe e = one;
+        for (size_t i = 0; i < m; i++) e = Fr::mul(e, ((x >> (m - 1 - i)) & 1) ? r[i] : omr[i]);
+        range_r = Fr::add(range_r, e);
+        v_io_r = Fr::add(v_io_r, Fr::mul(e, Fr::from_u64(h->v_io_clear[j])));
+    }
+}
+
+bool memory_proof_verify(cozk_memory_proof* h, const MemoryProof& proof, std::string& why) {
+    const cozk_rw_proof_config& c = h->rw.cfg;
+    const RwProofIdx ix((size_t)h->rw.ns, c.with_ts != 0);
+    Transcript vt("cozk-rw-memory");
+    std::vector<VerifierOpening> opens;
+    if (!rw_proof_verify_memory_check(&h->rw, proof.commitments, proof.mem, vt, opens, why)) return false;
+    {
+        const std::vector<fe> r_eq = vt.challenge_vector((size_t)c.log_mem);
+        std::vector<fe> r_out;
+        fe claim = Fr::zero();
+        if (!verify_sumcheck_rounds(proof.outputs.compressed_polys, (size_t)c.log_mem, 3, claim, vt, r_out) || proof.outputs_claims.size() != 1) {
+            why = "output check: shape";
+            return false;
+        }
+        fe range_r, v_io_r;
+        memory_proof_window_evals(h, r_out, range_r, v_io_r);
+        if (!Fr::eq(Fr::mul(Fr::mul(eq_eval(r_eq, r_out), range_r), Fr::sub(proof.outputs_claims[0], v_io_r)), claim)) {
+            why = "output check: final claim";
+            return false;
+        }
+        VerifierOpening o;
+        o.point = r_out;
+        o.polys = {ix.v_final};
+        o.claims = proof.outputs_claims;
+        o.rho = vt.challenge_scalar();
+        opens.push_back(o);
+    }
+    return rw_proof_verify_range_check_and_open(&h->rw, proof.commitments, proof.range, proof.reduced, vt, opens, why);
+}
+
+void memory_proof_setup(cozk_memory_proof* h) {
+    const cozk_memory_proof_config& c = h->cfg;
+    RwProofParty& ps = h->rw.parties[0];
+    cozk_ctx* ctx = ps.ctx;
+    const size_t MEM = h->rw.MEM, lo = (size_t)c.io_start, W = (size_t)c.io_len;
+    std::vector<uint32_t> vf(MEM);
+    rc_check(cozk_vec_download(ctx, ps.v_final.h, vf.data()), ctx, "vec_download(v_final)");
+    h->v_io_clear.assign(vf.begin() + (long)lo, vf.begin() + (long)(lo + W));
+    if (c.tamper == 4) h->v_io_clear[W / 2] += 1;  // the program's claimed output is wrong (a U32 word: 0xFFFFFFFF wraps to 0)
+    h->v_io = upload_vec(ctx, h->v_io_clear.data(), W, COZK_SCALAR_U32, "vec_upload(v_io)");
+    if (!c.windowed) {
+        std::vector<fe> rng(MEM, Fr::zero()), vio(MEM, Fr::zero()), vff(MEM);
+        for (size_t x = 0; x < MEM; x++) vff[x] = Fr::from_u64(vf[x]);
+        for (size_t j = 0; j < W; j++) rng[lo + j] = Fr::one(), vio[lo + j] = Fr::from_u64(h->v_io_clear[j]);
+        h->io_range_fr = upload_vec(ctx, rng.data(), MEM, COZK_SCALAR_FR, "vec_upload(io_range)");
+        h->v_io_fr = upload_vec(ctx, vio.data(), MEM, COZK_SCALAR_FR, "vec_upload(v_io)");
+        h->v_final_fr = upload_vec(ctx, vff.data(), MEM, COZK_SCALAR_FR, "vec_upload(v_final)");
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+}
+
+}  // namespace
+
+extern "C" {
+
+int cozk_memory_proof_create(const cozk_memory_proof_config* cfg, cozk_memory_proof** out) {
+    return harness_create(cfg, out, [&](cozk_memory_proof* h) {
+        cozk_rw_proof_config& rc = h->rw.cfg;
+        rc.mode = cfg->mode, rc.device = cfg->device, rc.log_n = cfg->log_n, rc.log_mem = cfg->log_mem, rc.n_slots = cfg->n_slots, rc.seed = cfg->seed;
+        rc.precompute = cfg->precompute, rc.with_ts = cfg->with_ts, rc.leaves_fused = cfg->leaves_fused, rc.tamper = cfg->tamper;
+        rw_proof_check_config(rc, "memory_proof", 4);
+        COZK_REQUIRE(cfg->io_len >= 1, "memory_proof: io_len is at least 1 word");
+        const uint64_t MEM = (uint64_t)1 << cfg->log_mem;
+        COZK_REQUIRE(cfg->io_start <= MEM && cfg->io_len <= MEM - cfg->io_start, "memory_proof: io_start + io_len > MEM");
+        COZK_REQUIRE(cfg->windowed == 0 || cfg->windowed == 1, "memory_proof: windowed is 0 or 1");
+        if (rc.tamper == 4) rc.tamper = 0;  // tamper 4 is the output check's: the witness is honest
+        rw_proof_build(&h->rw, "memory_proof");
+        memory_proof_setup(h);
+    });
+}
+
+const char* cozk_memory_proof_error(const cozk_memory_proof* h) { return harness_error(h); }
+
+int cozk_memory_proof_destroy(cozk_memory_proof* h) {
+    if (!h) return COZK_OK;
+    if (!h->rw.parties.empty() && h->rw.parties[0].ctx) (void)hipSetDevice(h->rw.parties[0].ctx->device);
+    for (VecH* v : {&h->v_io, &h->io_range_fr, &h->v_io_fr, &h->v_final_fr}) *v = VecH();
+    rw_proof_release(&h->rw);
+    delete h;
+    return COZK_OK;
+}
+
+int cozk_memory_proof_prove(cozk_memory_proof* h, int verify, cozk_memory_proof_result* res) {
+    if (!h || !res) return COZK_ERR_INVALID_ARG;
+    memset(res, 0, sizeof *res);
+    res->verified = -1;
+    if (h->rw.parties.empty() || !h->rw.parties[0].setup || !h->v_io.h) return COZK_ERR_INVALID_ARG;  // create failed
+    InProcNets nets(1);
+    std::vector<Participant> parts;
+    add_participants(parts, "party", h->rw.parties, [&](RwProofParty& ps, int) { memory_proof_worker_main(h, ps, nets.worker(0)); });
+    MemoryProof proof;
+    double wall_ms = 0;
+    int rc = run_in_process(nets, parts, [&] {
+        InProcStarCoordinator coord(&nets.star);
+        memory_proof_coordinate(h, coord, proof);
+    }, h->error, wall_ms);
+    if (rc != COZK_OK) return rc;
+    res->wall_ms = wall_ms;  // the verifier below is outside the clock
+    if (verify) {
+        std::string why;
+        try {
+            HIP_TRY(hipSetDevice(h->rw.parties[0].ctx->device));
+            res->verified = memory_proof_verify(h, proof, why) ? 1 : 0;
+        } catch (const std::exception& e) {
+            why = e.what();
+            res->verified = 0;
+        }
+        if (res->verified == 0) h->error = "verification failed: " + why;
+    }
+    const RwProofParty& ps = h->rw.parties[0];
+    res->t_witness_ms = h->rw.t_witness;
+    res->t_commit_ms = ps.t_commit;
+    res->t_leaves_ms = ps.t_leaves;
+    res->t_gp_ms = ps.t_gp;
+    res->t_out_ms = h->t_out;
+    res->t_ts_ms = ps.t_ts;
+    res->t_open_ms = ps.t_open;
+    res->out_peak_bytes = h->out_peak_bytes;
+    Bytes bytes = proof.serialize();
+    res->prefix_len = proof.prefix_len;
+    finish_proof(h, std::move(bytes), res);
+    return COZK_OK;
+}
+
+int cozk_memory_proof_proof_bytes(const cozk_memory_proof* h, uint8_t* out, size_t cap) { return harness_proof_bytes(h, out, cap); }
+
+}  // extern "C"

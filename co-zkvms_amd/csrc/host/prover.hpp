@@ -1483,16 +1483,17 @@ struct ArbitraryResult {
     std::vector<fe> r;
     std::vector<fe> final_evals;
 };
-static ArbitraryResult prove_arbitrary_worker(WorkerEnv& env, const fe& claim, int num_rounds, std::vector<cozk_poly*>& polys,
-                                              int combined_degree) {
-    COZK_REQUIRE(combined_degree >= 1 && combined_degree <= 3 && !polys.empty() && polys.size() <= 4, "prove_arbitrary: unsupported shape");
-    ArbitraryResult res;
+// The round loop, the ONE copy: evaluate(ev) writes the round's combined_degree evaluations at x = 0, 2, .. (4 x u64 each), bind(rr)
+// binds the round's variable with the challenge.  Returns r.  The callers own what is evaluated and bound: the polynomials of
+// prove_arbitrary_worker below, the windowed output check of memory_proof.hpp.
+template <class Evaluate, class Bind>
+static std::vector<fe> prove_arbitrary_rounds(WorkerEnv& env, const fe& claim, int num_rounds, int combined_degree, bool any_shared, Evaluate evaluate, Bind bind) {
+    COZK_REQUIRE(combined_degree >= 1 && combined_degree <= 3, "prove_arbitrary: unsupported shape");
+    std::vector<fe> r;
     fe previous_claim = claim;
-    bool any_shared = false;
-    for (auto* p : polys) any_shared |= cozk_poly_mode(p) == COZK_MODE_REP3;
     for (int round = 0; round < num_rounds; round++) {
         std::vector<uint64_t> ev(4 * (size_t)combined_degree);
-        rc_check(cozk_prod_sumcheck_evals(env.ctx, polys.data(), polys.size(), combined_degree, ev.data()), env.ctx, "prod_sumcheck_evals");
+        evaluate(ev.data());
         std::vector<fe> pts((size_t)combined_degree + 1);
         for (int e = 0; e < combined_degree; e++) {
             fe v = fe_from_u64x4(ev.data() + 4 * e);
@@ -1515,12 +1516,27 @@ static ArbitraryResult prove_arbitrary_worker(WorkerEnv& env, const fe& claim, i
         Reader rd(req);
         fe r_j = rd.fr();
         fe next_claim = rd.fr();
-        res.r.push_back(r_j);
+        r.push_back(r_j);
         uint64_t rr[4];
         fe_to_u64x4(r_j, rr);
-        for (auto* p : polys) rc_check(cozk_poly_bind(env.ctx, p, rr, COZK_HIGH_TO_LOW), env.ctx, "bind");
+        bind(rr);
         previous_claim = env.additive_trivial(next_claim);
     }
+    return r;
+}
+
+static ArbitraryResult prove_arbitrary_worker(WorkerEnv& env, const fe& claim, int num_rounds, std::vector<cozk_poly*>& polys,
+                                              int combined_degree) {
+    COZK_REQUIRE(combined_degree >= 1 && combined_degree <= 3 && !polys.empty() && polys.size() <= 4, "prove_arbitrary: unsupported shape");
+    ArbitraryResult res;
+    bool any_shared = false;
+    for (auto* p : polys) any_shared |= cozk_poly_mode(p) == COZK_MODE_REP3;
+    res.r = prove_arbitrary_rounds(
+        env, claim, num_rounds, combined_degree, any_shared,
+        [&](uint64_t* ev) { rc_check(cozk_prod_sumcheck_evals(env.ctx, polys.data(), polys.size(), combined_degree, ev), env.ctx, "prod_sumcheck_evals"); },
+        [&](const uint64_t rr[4]) {
+            for (auto* p : polys) rc_check(cozk_poly_bind(env.ctx, p, rr, COZK_HIGH_TO_LOW), env.ctx, "bind");
+        });
     for (auto* p : polys) {
         uint64_t a[4], b[4] = {0, 0, 0, 0};
         rc_check(cozk_poly_get_coeff(env.ctx, p, 0, a, b), env.ctx, "get_coeff");

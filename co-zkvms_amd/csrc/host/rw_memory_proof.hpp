@@ -159,10 +159,7 @@ void rw_proof_leaves_composed(WorkerEnv& env, const RwProofParty& ps, int ns, si
     flow_fingerprint(env, {C(ps.v_final, gamma), C(ps.t_final, g2), C(ps.iota_mem, one)}, ntau, inf, MEM, MEM);
 }
 
-void rw_proof_worker_main(cozk_rw_proof* h, RwProofParty& ps, StarNetWorker* star) {
-    const cozk_rw_proof_config& c = h->cfg;
-    const int ns = h->ns;
-    const size_t N = h->N, MEM = h->MEM;
+WorkerEnv rw_proof_env(RwProofParty& ps, StarNetWorker* star) {
     WorkerEnv env;
     env.ctx = ps.ctx;
     env.mode = COZK_MODE_PLAIN;
@@ -170,9 +167,19 @@ void rw_proof_worker_main(cozk_rw_proof* h, RwProofParty& ps, StarNetWorker* sta
     env.star = star;
     env.ring = nullptr;
     HIP_TRY(hipSetDevice(ps.ctx->device));
+    return env;
+}
+
+// Steps 1-4 of the worker, shared with cozk_memory_proof (memory_proof.hpp): the commit, gamma and tau, the leaves, the two grand
+// products and the two openings from the compact columns into `acc`.  Sets t_commit, t_leaves and t_gp; returns the clock taken after
+// the grand products (the openings belong to t_open).
+double rw_proof_memory_check_worker(cozk_rw_proof* h, RwProofParty& ps, WorkerEnv& env, const TsRangeCols& range, Rep3ProverOpeningAccumulator& acc) {
+    const cozk_rw_proof_config& c = h->cfg;
+    const int ns = h->ns;
+    const size_t N = h->N, MEM = h->MEM;
+    StarNetWorker* star = env.star;
     const std::vector<const cozk_vec*> rw_cols = rw_proof_rw_columns(ps);
     const std::vector<const cozk_vec*> if_cols = {ps.v_final.h, ps.t_final.h};
-    const TsRangeCols range = ts_range_columns(ps, ps.iota_n);
     double t0 = now_ms();
     // ---- 1. commit: mixed lengths and compact kinds
     {
@@ -222,48 +229,68 @@ void rw_proof_worker_main(cozk_rw_proof* h, RwProofParty& ps, StarNetWorker* sta
     double t4 = now_ms();
     ps.t_gp = t4 - t3;
     // ---- 4. two openings from the compact columns
-    Rep3ProverOpeningAccumulator acc;
     compact_open_worker(env, acc, rw_cols, r_rw, c.tamper == 2);
     compact_open_worker(env, acc, if_cols, r_if, false);
+    return t4;
+}
+
+// Steps 5 and 6, shared likewise: with with_ts the timestamp range check, chained (t_read is not committed again), then ONE
+// reduce_and_prove.  t45: what the openings before this call took.  Sets t_ts and t_open.
+void rw_proof_range_check_and_open_worker(cozk_rw_proof* h, RwProofParty& ps, WorkerEnv& env, const TsRangeCols& range, Rep3ProverOpeningAccumulator& acc, double t45) {
+    const cozk_rw_proof_config& c = h->cfg;
     double t5 = now_ms();
-    // ---- 5. the timestamp range check, chained: t_read is not committed again
     if (c.with_ts) {
         double tl = 0, tg = 0;
-        ts_range_check_worker(env, range, N, c.leaves_fused != 0, false, acc, tl, tg);
+        ts_range_check_worker(env, range, h->N, c.leaves_fused != 0, false, acc, tl, tg);
     }
     double t6 = now_ms();
     ps.t_ts = t6 - t5;
-    // ---- 6. ONE reduce_and_prove
     acc.reduce_and_prove_worker(env, *ps.setup);
-    ps.t_open = (t5 - t4) + (now_ms() - t6);
-    ps.record_net(star);
+    ps.t_open = t45 + (now_ms() - t6);
+    ps.record_net(env.star);
+}
+
+void rw_proof_worker_main(cozk_rw_proof* h, RwProofParty& ps, StarNetWorker* star) {
+    WorkerEnv env = rw_proof_env(ps, star);
+    const TsRangeCols range = ts_range_columns(ps, ps.iota_n);
+    Rep3ProverOpeningAccumulator acc;
+    const double t4 = rw_proof_memory_check_worker(h, ps, env, range, acc);
+    rw_proof_range_check_and_open_worker(h, ps, env, range, acc, now_ms() - t4);
+}
+
+// the coordinator's halves of the two worker steps above, under the caller's transcript
+void rw_proof_coordinate_memory_check(const cozk_rw_proof_config& c, StarNetCoordinator& net, Transcript& tr, std::vector<PST13Commitment>& commitments, MemCheckProof& mem) {
+    ts_receive_commitments(net, tr, commitments);
+    flow_broadcast_gamma_tau(net, tr);
+    flow_coordinate_memory_checking(net, tr, mem, (size_t)c.log_n, false, (size_t)c.log_mem);
+}
+void rw_proof_coordinate_range_check_and_open(const cozk_rw_proof_config& c, StarNetCoordinator& net, Transcript& tr, bool& with_ts, TsRangeProof& range, ReducedOpeningProof& reduced) {
+    with_ts = c.with_ts != 0;
+    if (c.with_ts) ts_range_check_coordinate(net, tr, (size_t)c.log_n, range);
+    std::vector<fe> r_red;
+    fe rho, gamma;
+    reduced = Rep3ProverOpeningAccumulator::reduce_and_prove(net, tr, r_red, rho, gamma);
 }
 
 void rw_proof_coordinate(cozk_rw_proof* h, StarNetCoordinator& net, RwProof& proof) {
     const cozk_rw_proof_config& c = h->cfg;
     Transcript tr("cozk-rw-memory");
-    ts_receive_commitments(net, tr, proof.commitments);
-    flow_broadcast_gamma_tau(net, tr);
-    flow_coordinate_memory_checking(net, tr, proof.mem, (size_t)c.log_n, false, (size_t)c.log_mem);
-    proof.with_ts = c.with_ts != 0;
-    if (c.with_ts) ts_range_check_coordinate(net, tr, (size_t)c.log_n, proof.range);
-    std::vector<fe> r_red;
-    fe rho, gamma;
-    proof.reduced = Rep3ProverOpeningAccumulator::reduce_and_prove(net, tr, r_red, rho, gamma);
+    rw_proof_coordinate_memory_check(c, net, tr, proof.commitments, proof.mem);
+    rw_proof_coordinate_range_check_and_open(c, net, tr, proof.with_ts, proof.range, proof.reduced);
 }
 
-// the plain verifier: replays the transcript; the first check that fails names itself in `why`
-bool rw_proof_verify(cozk_rw_proof* h, const RwProof& proof, std::string& why) {
+// The plain verifier, in the two steps of the worker (shared with cozk_memory_proof): it replays the transcript `vt`; the first check that
+// fails names itself in `why`.  The memory check leaves its two openings in `opens`.
+bool rw_proof_verify_memory_check(cozk_rw_proof* h, const std::vector<PST13Commitment>& commitments, const MemCheckProof& mp, Transcript& vt, std::vector<VerifierOpening>& opens,
+                                  std::string& why) {
     const cozk_rw_proof_config& c = h->cfg;
     const size_t ns = (size_t)h->ns;
     const RwProofIdx ix(ns, c.with_ts != 0);
-    const MemCheckProof& mp = proof.mem;
-    Transcript vt("cozk-rw-memory");
-    if (proof.commitments.size() != ix.count || mp.rw_hashes.size() != 2 * ns || mp.if_hashes.size() != 2 || mp.rw_claims.size() != ix.n_rw || mp.if_claims.size() != 2) {
+    if (commitments.size() != ix.count || mp.rw_hashes.size() != 2 * ns || mp.if_hashes.size() != 2 || mp.rw_claims.size() != ix.n_rw || mp.if_claims.size() != 2) {
         why = "shape: commitments, hashes or claims";
         return false;
     }
-    for (auto& cm : proof.commitments) vt.append_point(cm.g_product);
+    for (auto& cm : commitments) vt.append_point(cm.g_product);
     const fe gamma = vt.challenge_scalar(), tau = vt.challenge_scalar();
     const fe g2 = Fr::mul(gamma, gamma);
     vt.append_scalars(mp.rw_hashes);
@@ -286,7 +313,7 @@ bool rw_proof_verify(cozk_rw_proof* h, const RwProof& proof, std::string& why) {
     }
     const int k = ceil_log2(2 * ns);
     std::vector<fe> hi(r_rw.begin(), r_rw.begin() + k), lo(r_rw.begin() + k, r_rw.end()), hi2(r_if.begin(), r_if.begin() + 1), lo2(r_if.begin() + 1, r_if.end());
-    std::vector<VerifierOpening> opens(2);
+    opens.assign(2, VerifierOpening());
     opens[0].point = lo;
     for (size_t i = 0; i < ix.n_rw; i++) opens[0].polys.push_back(i);
     opens[0].claims = mp.rw_claims;
@@ -315,10 +342,18 @@ bool rw_proof_verify(cozk_rw_proof* h, const RwProof& proof, std::string& why) {
             return false;
         }
     }
+    return true;
+}
+// the range check (with with_ts) and the reduced opening over `opens` and the range check's own
+bool rw_proof_verify_range_check_and_open(cozk_rw_proof* h, const std::vector<PST13Commitment>& commitments, const TsRangeProof& range, const ReducedOpeningProof& reduced,
+                                          Transcript& vt, std::vector<VerifierOpening>& opens, std::string& why) {
+    const cozk_rw_proof_config& c = h->cfg;
+    const size_t ns = (size_t)h->ns;
+    const RwProofIdx ix(ns, c.with_ts != 0);
     if (c.with_ts) {
         VerifierOpening o;
         std::string inner;
-        if (!ts_range_check_verify(vt, ns, (size_t)c.log_n, proof.range, inner, o)) {
+        if (!ts_range_check_verify(vt, ns, (size_t)c.log_n, range, inner, o)) {
             why = "timestamp: " + inner;
             return false;
         }
@@ -328,11 +363,45 @@ bool rw_proof_verify(cozk_rw_proof* h, const RwProof& proof, std::string& why) {
         opens.push_back(o);
     }
     std::string inner;
-    if (!verify_reduced_opening(opens, proof.commitments, vt, proof.reduced, *h->parties[0].setup, "reduction sumcheck: shape", "reduction sumcheck: final check", inner)) {
+    if (!verify_reduced_opening(opens, commitments, vt, reduced, *h->parties[0].setup, "reduction sumcheck: shape", "reduction sumcheck: final check", inner)) {
         why = "opening: " + inner;
         return false;
     }
     return true;
+}
+bool rw_proof_verify(cozk_rw_proof* h, const RwProof& proof, std::string& why) {
+    Transcript vt("cozk-rw-memory");
+    std::vector<VerifierOpening> opens;
+    return rw_proof_verify_memory_check(h, proof.commitments, proof.mem, vt, opens, why) &&
+           rw_proof_verify_range_check_and_open(h, proof.commitments, proof.range, proof.reduced, vt, opens, why);
+}
+
+// what create checks of a config and builds from it, for both harnesses (`who` names the harness in the refusals; max_tamper: its last tamper)
+void rw_proof_check_config(const cozk_rw_proof_config& c, const std::string& who, int max_tamper) {
+    COZK_REQUIRE(c.mode == COZK_MODE_PLAIN, who + ": the proof is party 0's public one: mode is COZK_MODE_PLAIN");
+    COZK_REQUIRE(c.log_n >= 1 && c.log_n <= 22, who + ": log_n in 1..22");
+    COZK_REQUIRE(c.log_mem >= 5 && c.log_mem <= 24, who + ": log_mem in 5..24");
+    COZK_REQUIRE(c.n_slots >= 1 && c.n_slots <= 4, who + ": n_slots in 1..4");
+    COZK_REQUIRE((c.with_ts == 0 || c.with_ts == 1) && (c.leaves_fused == 0 || c.leaves_fused == 1), who + ": with_ts and leaves_fused are 0 or 1");
+    COZK_REQUIRE(c.tamper >= 0 && c.tamper <= max_tamper && (c.tamper != 3 || c.with_ts), who + ": tamper in 0.." + std::to_string(max_tamper) + ", 3 only with with_ts");
+}
+void rw_proof_build(cozk_rw_proof* h, const std::string& who) {
+    const cozk_rw_proof_config& c = h->cfg;
+    h->N = (size_t)1 << c.log_n;
+    h->MEM = (size_t)1 << c.log_mem;
+    h->ns = c.n_slots;
+    h->parties.resize(1);
+    RwProofParty& ps = h->parties[0];
+    ps.party = 0;
+    ps.open_ctx(c.device, (who + ": cannot create a context (no HIP device?)").c_str());
+    rw_proof_setup(h, ps);
+}
+void rw_proof_release(cozk_rw_proof* h) {
+    release_parties(h->parties, [](RwProofParty& ps) {
+        for (std::vector<VecH>* fam : {&ps.addr, &ps.v_read, &ps.t_read, &ps.v_written, &ps.rc_rt, &ps.rc_gmr, &ps.fc_rt, &ps.fc_gmr}) fam->clear();
+        for (VecH* v : {&ps.v_init, &ps.v_final, &ps.t_final, &ps.iota_n, &ps.iota_mem}) *v = VecH();
+        ps.setup.reset();
+    });
 }
 
 }  // namespace
@@ -341,20 +410,8 @@ extern "C" {
 
 int cozk_rw_proof_create(const cozk_rw_proof_config* cfg, cozk_rw_proof** out) {
     return harness_create(cfg, out, [&](cozk_rw_proof* h) {
-        COZK_REQUIRE(cfg->mode == COZK_MODE_PLAIN, "rw_proof: the proof is party 0's public one: mode is COZK_MODE_PLAIN");
-        COZK_REQUIRE(cfg->log_n >= 1 && cfg->log_n <= 22, "rw_proof: log_n in 1..22");
-        COZK_REQUIRE(cfg->log_mem >= 5 && cfg->log_mem <= 24, "rw_proof: log_mem in 5..24");
-        COZK_REQUIRE(cfg->n_slots >= 1 && cfg->n_slots <= 4, "rw_proof: n_slots in 1..4");
-        COZK_REQUIRE((cfg->with_ts == 0 || cfg->with_ts == 1) && (cfg->leaves_fused == 0 || cfg->leaves_fused == 1), "rw_proof: with_ts and leaves_fused are 0 or 1");
-        COZK_REQUIRE(cfg->tamper >= 0 && cfg->tamper <= 3 && (cfg->tamper != 3 || cfg->with_ts), "rw_proof: tamper in 0..3, 3 only with with_ts");
-        h->N = (size_t)1 << cfg->log_n;
-        h->MEM = (size_t)1 << cfg->log_mem;
-        h->ns = cfg->n_slots;
-        h->parties.resize(1);
-        RwProofParty& ps = h->parties[0];
-        ps.party = 0;
-        ps.open_ctx(cfg->device, "rw_proof: cannot create a context (no HIP device?)");
-        rw_proof_setup(h, ps);
+        rw_proof_check_config(*cfg, "rw_proof", 3);
+        rw_proof_build(h, "rw_proof");
     });
 }
 
@@ -362,11 +419,7 @@ const char* cozk_rw_proof_error(const cozk_rw_proof* h) { return harness_error(h
 
 int cozk_rw_proof_destroy(cozk_rw_proof* h) {
     if (!h) return COZK_OK;
-    release_parties(h->parties, [](RwProofParty& ps) {
-        for (std::vector<VecH>* fam : {&ps.addr, &ps.v_read, &ps.t_read, &ps.v_written, &ps.rc_rt, &ps.rc_gmr, &ps.fc_rt, &ps.fc_gmr}) fam->clear();
-        for (VecH* v : {&ps.v_init, &ps.v_final, &ps.t_final, &ps.iota_n, &ps.iota_mem}) *v = VecH();
-        ps.setup.reset();
-    });
+    rw_proof_release(h);
     delete h;
     return COZK_OK;
 }

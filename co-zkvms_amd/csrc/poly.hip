@@ -3095,3 +3095,4 @@ int cozk_layer_claimed_outputs(cozk_ctx* ctx, const cozk_layer* l, uint64_t* out
 #include "spartan_inner.inc"
 #include "logup.inc"
 #include "compact_open.inc"
+#include "output_check.inc"

@@ -1873,8 +1873,9 @@ int cozk_rw_memory_init_final_leaves(cozk_ctx* ctx, const cozk_vec* v_init, cons
  * range check chained behind it under the same transcript and the same opening accumulator, as Jolt's ReadWriteMemoryProof has it:
  * the t_read commitments are shared and there is ONE reduce_and_prove for everything.  PLAIN only.  jolt-core is not in the reference
  * tree: the circuit order, the transcript order and the proof bytes are this project's (parity unpinned); what pins them is the plain
- * verifier below and the Python restatement tests/rw_proof_ref.py.  Not built: the output check over the consistent v_final, the
- * public-opening exchange to the other parties, and the chained flow's use of any of this.
+ * verifier below and the Python restatement tests/rw_proof_ref.py.  The output check over the consistent v_final is not part of this
+ * proof: cozk_memory_proof_* below runs it between these steps.  Not built: the public-opening exchange to the other parties, and the
+ * chained flow's use of any of this.
  * create: the trace of cozk_ts_proof (tests/rw_witness_ref.py jolt_instance(seed, N, MEM, n_regs = 32)) restricted to the first n_slots
  * of rs1, rs2, rd, ram (with 1 or 2 nothing writes); the register address columns are U8, the RAM column U32; cozk_rw_memory_witness
  * over exactly those slots and, with with_ts, cozk_timestamp_range_witness(M = N).  Every column stays compact: no Fr copy of a column
@@ -1932,6 +1933,84 @@ const char* cozk_rw_proof_error(const cozk_rw_proof* h);
 int cozk_rw_proof_destroy(cozk_rw_proof* h);
 int cozk_rw_proof_prove(cozk_rw_proof* h, int verify, cozk_rw_proof_result* res);
 int cozk_rw_proof_proof_bytes(const cozk_rw_proof* h, uint8_t* out, size_t cap);
+
+/* ---- The output check of the read-write memory proof on the device (prove_outputs, co-jolt/src/jolt/vm/read_write_memory/worker.rs:
+ * 110-175; csrc/output_check.inc):
+ *     sum_x eq(r_eq, x) * io_range(x) * (v_final(x) - v_io(x)) = 0,   degree 3, binding HighToLow,
+ * from the compact columns.  v_final: U32, MEM = 2^m entries, 1 <= m < 32; v_io: U32, io_len >= 1 entries, the public io words of the
+ * window [io_start, io_start + io_len) ONLY; r_eq: m x 4 u64 (Montgomery).  With W' the power of two at or above io_len, the rounds
+ * whose half length is at least W' need four windowed dot products each and host scalars (eq is never a table of MEM entries, the
+ * range never a vector), only d = v_final - v_io is folded whole, and the last log2 W' rounds are the dense product sumcheck on
+ * W'-entry vectors; W' = MEM: d is materialised once and every round is dense.
+ * cozk_output_check_round: with r != NULL it first binds the previous variable with r; out = the round polynomial at X = 0, 2, 3,
+ *   exactly what cozk_prod_sumcheck_evals({eq, io_range, v_final - v_io}, 3, 3, ..) writes for the dense Fr vectors in the same state.
+ * cozk_output_check_final: the last bind; out = eq(r), io_range(r), (v_final - v_io)(r), what cozk_poly_get_coeff(.., 0, ..) of the
+ *   three bound polynomials gives.  m = 1: round(NULL), then final(r).
+ * cozk_output_check_len: the current length 2^(variables left).
+ * Each call returns with the stream drained and the values on the host.  v_final and v_io are only read and must outlive the handle.
+ * Device memory, all taken in create from the context's pool: W' < MEM: MEM / 2 Fr entries for the folds plus two W'-entry Fr vectors;
+ * W' = MEM: three MEM-entry Fr vectors.  No Fr vector of MEM entries exists unless W' = MEM.
+ * Refused with COZK_ERR_INVALID_ARG and a text of its own before any launch, *out NULL, the context working on: a null argument; a
+ * v_final that is not U32 or whose length is not a power of two of at least 2 (and below 2^32); a v_io that is not U32; io_len == 0;
+ * io_start + io_len > MEM; a vector on another device; a round with r == NULL after round 0 or with r != NULL in round 0; a round
+ * when one variable is left; a final when more than one is left. */
+typedef struct cozk_output_check cozk_output_check;
+int cozk_output_check_create(cozk_ctx* ctx, const cozk_vec* v_final, const cozk_vec* v_io, size_t io_start, const uint64_t* r_eq,
+                             cozk_output_check** out);
+int cozk_output_check_round(cozk_output_check* oc, const uint64_t* r, uint64_t out[12]);
+int cozk_output_check_final(cozk_output_check* oc, const uint64_t r[4], uint64_t out[12]);
+size_t cozk_output_check_len(const cozk_output_check* oc);
+int cozk_output_check_free(cozk_output_check* oc);
+
+/* ---- The whole ReadWriteMemoryProof in the reference's order, as an in-process harness (csrc/host/memory_proof.hpp): the memory
+ * check, the output check, the timestamp range check, under one transcript ("cozk-rw-memory") and one opening accumulator, with ONE
+ * reduce_and_prove.  PLAIN only; the trace and the witness of cozk_rw_proof_create for the same fields.  Parity unpinned: pinned by the
+ * verifier below and tests/memory_proof_ref.py.
+ * prove: steps 1-4 are cozk_rw_proof_prove's, so everything up to and including the claims at r_if is byte for byte cozk_rw_proof's proof
+ * at the same config.  Then the output check: the coordinator draws r_eq (log_mem challenges) and sends it, log_mem rounds in the
+ * messages of prove_arbitrary_worker (windowed = 1: cozk_output_check_*; windowed = 0: the chained flow's composition on Fr copies of
+ * MEM entries, the same bytes, kept for the A/B), then a third opening: v_final from the compact column at the sumcheck's point.  v_io is
+ * v_final over the io window [io_start, io_start + io_len) words, so an honest run verifies.  Then cozk_rw_proof's steps 5 and 6.
+ * Proof bytes: commitments, the memory-check part, the output sumcheck's compressed polynomials and the v_final claim, the range-check
+ * part, the reduced opening.  prefix_len: the offset at which the output check's part begins.
+ * The verifier: cozk_rw_proof's checks, and between "leaf claim" and "timestamp: ...":
+ *   "output check: shape"        log_mem compressed cubics, one claim
+ *   "output check: final claim"  s_last(r_last) == eq(r_eq, r) * io_range(r) * (claim - v_io(r)); io_range(r) and v_io(r) are evaluated
+ *                                on the host over the window only, in O(io_len log_mem)
+ * tamper: 1-3 are cozk_rw_proof's; 4 adds 1 to v_io[io_len / 2] -- the program's claimed output is wrong, and only the output check's
+ * final claim can reject.
+ * Refused: whatever cozk_rw_proof_create refuses, io_len < 1, io_start + io_len > MEM, windowed outside 0..1, tamper outside 0..4. */
+typedef struct cozk_memory_proof cozk_memory_proof;
+typedef struct cozk_memory_proof_config {
+    int mode;         /* COZK_MODE_PLAIN; anything else is refused */
+    int device;
+    int log_n;        /* trace length N = 2^log_n, 1..22 */
+    int log_mem;      /* memory of 2^log_mem words, 5..24 */
+    int n_slots;      /* 1..4 */
+    uint64_t seed;
+    int precompute;
+    int with_ts;      /* 0 or 1: chain the timestamp range check */
+    int leaves_fused; /* as cozk_rw_proof_config */
+    int tamper;       /* 0..4: see above */
+    uint64_t io_start; /* first word of the io window */
+    uint64_t io_len;   /* its length in words, >= 1 */
+    int windowed;     /* 1: cozk_output_check_*; 0: the dense composition on Fr copies */
+} cozk_memory_proof_config;
+typedef struct cozk_memory_proof_result {
+    int verified; /* 1 ok, 0 rejected, -1 not run */
+    /* as cozk_rw_proof_result; t_out_ms: the output check (its rounds and the v_final opening) */
+    double wall_ms, t_witness_ms, t_commit_ms, t_leaves_ms, t_gp_ms, t_out_ms, t_ts_ms, t_open_ms;
+    uint64_t proof_len;
+    uint64_t prefix_len;     /* proof[0 .. prefix_len) is cozk_rw_proof's prefix: the commitments and the memory-check part */
+    uint64_t out_peak_bytes; /* device memory the output sumcheck held at its peak beyond what it found (the context's allocator's
+                              * count plus the growth of its scratch buffers), the v_final opening after it not included */
+    uint8_t proof_digest[32];
+} cozk_memory_proof_result;
+int cozk_memory_proof_create(const cozk_memory_proof_config* cfg, cozk_memory_proof** out);
+const char* cozk_memory_proof_error(const cozk_memory_proof* h);
+int cozk_memory_proof_destroy(cozk_memory_proof* h);
+int cozk_memory_proof_prove(cozk_memory_proof* h, int verify, cozk_memory_proof_result* res);
+int cozk_memory_proof_proof_bytes(const cozk_memory_proof* h, uint8_t* out, size_t cap);
 
 /* ---- ONE chained co-jolt worker flow (JoltRep3Prover::prove, co-jolt/src/jolt/vm/jolt/worker.rs:175-266, against its coordinator
  * jolt/vm/jolt/coordinator.rs:118-222): commit-all -> bytecode memory checking -> instruction lookups (primary sumcheck, toggled

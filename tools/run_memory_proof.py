@@ -1,0 +1,142 @@
+"""Time the output check of the read-write memory proof and the whole proof at 2^log_n steps over a memory of 2^log_mem words, 4 slots, an
+io window of --io-len words at word --io-start (default 2050 at 64: not a power of two, W' = 4096, the order of Jolt's default layout;
+jolt-core is not in the reference tree, so the shape is this project's choice), in one process, the variants of each comparison
+alternating, outputs compared equal at the measured size:
+  calls   the device calls alone: OutputCheck (create, log_mem rounds, final, free) against its dense twin, the chained flow's
+          composition on Fr vectors of MEM entries (eq_evals, three poly_create, the linear combination v_final - v_io, log_mem rounds
+          of prod_sumcheck_evals + three binds, three get_coeff); random challenges, every round's evaluations and the finals compared;
+          a host clock around calls that each end with the stream drained
+  prove   the whole proof (cozk_memory_proof_*, seed --seed) with windowed 1 and 0: two handles alternating, each verified once, digests
+          compared: wall and per phase (commit, leaves, grand products, output check, timestamp check, open), and the peak device
+          allocation of the output sumcheck on either path as the context's allocator counted it (first prove of each handle)
+--warmup runs, then the median and spread of --runs runs.  Prints one JSON line.
+  python tools/run_memory_proof.py --log-n 20 --log-mem 20 --runs 7 [--out profiles/memory_proof_2p20.json]
+--bench <file> adds recorded bench.py lines ({"this_change": {...}, "parent": {...}})."""
+import argparse, importlib, json, os, statistics, sys, time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--log-n", type=int, default=20)
+ap.add_argument("--log-mem", type=int, default=20)
+ap.add_argument("--io-start", type=int, default=64)
+ap.add_argument("--io-len", type=int, default=2050)
+ap.add_argument("--seed", type=int, default=2026)
+ap.add_argument("--runs", type=int, default=7)
+ap.add_argument("--warmup", type=int, default=2)
+ap.add_argument("--skip-prove", action="store_true")
+ap.add_argument("--bench", default=None)
+ap.add_argument("--out", default=None)
+args = ap.parse_args()
+M, MEM, LO, W = args.log_mem, 1 << args.log_mem, args.io_start, args.io_len
+
+Z = importlib.import_module("co-zkvms_amd")
+R = Z.FR_MOD
+ctx = Z.Context(0)
+
+
+def stats(xs):
+    return {"runs": [round(x, 4) for x in xs], "median": round(statistics.median(xs), 4), "min": round(min(xs), 4), "max": round(max(xs), 4)}
+
+
+def ab(variants):
+    """variants: {name: call}; alternating rounds -> ({name: ms list}, {name: last output})"""
+    ms, out = {k: [] for k in variants}, {}
+    for it in range(args.warmup + args.runs):
+        for name, call in variants.items():
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            out[name] = call()
+            ctx.synchronize()
+            if it >= args.warmup:
+                ms[name].append((time.perf_counter() - t0) * 1e3)
+    return ms, out
+
+
+# ---- the device calls alone against the dense twin
+rng = np.random.default_rng(args.seed)
+sm = np.random.default_rng(args.seed + 1)
+fr = lambda: int.from_bytes(sm.bytes(40), "little") % R
+vf = rng.integers(0, 1 << 32, size=MEM, dtype=np.uint64).astype(np.uint32)
+vio = vf[LO:LO + W].copy()
+d_vf, d_vio = Z.Vec.from_numpy(ctx, vf, Z.SCALAR_U32), Z.Vec.from_numpy(ctx, vio, Z.SCALAR_U32)
+r_eq, rs = [fr() for _ in range(M)], [fr() for _ in range(M)]
+one = Z.fr_to_mont_limbs([1])[0]
+rng_l, vio_l = np.zeros((MEM, 4), dtype=np.uint64), np.zeros((MEM, 4), dtype=np.uint64)
+rng_l[LO:LO + W] = one
+vio_l[LO:LO + W] = Z.fr_to_mont_limbs([int(x) for x in vio])
+d_rng, d_vio_fr = Z.Vec.from_numpy(ctx, rng_l), Z.Vec.from_numpy(ctx, vio_l)
+p_vf = Z.Rep3DensePolynomial.from_vec_shares(ctx, Z.compact_linear_combination(ctx, [d_vf], [1]))  # the flow holds v_final as an Fr polynomial
+rng_l = vio_l = None
+
+
+def windowed():
+    oc = Z.OutputCheck(ctx, d_vf, d_vio, LO, r_eq)
+    out = [oc.round(rs[k - 1] if k else None) for k in range(M)]
+    out.append(oc.final(rs[-1]))
+    oc.free()
+    return out
+
+
+def dense():
+    P = Z.Rep3DensePolynomial
+    pe, pr, pio = P.from_vec_shares(ctx, Z.eq_evals(ctx, r_eq)), P.from_vec_shares(ctx, d_rng), P.from_vec_shares(ctx, d_vio_fr)
+    polys = [pe, pr, P.linear_combination([p_vf, pio], [1, R - 1])]
+    out = []
+    for k in range(M):
+        if k:
+            for p in polys:
+                p.bind(rs[k - 1], Z.HIGH_TO_LOW)
+        out.append(Z.prod_sumcheck_evals(polys, 3))
+    for p in polys:
+        p.bind(rs[-1], Z.HIGH_TO_LOW)
+    out.append(tuple(p.get_bound_coeff(0) for p in polys))
+    for p in polys + [pio]:
+        p.free()
+    return out
+
+
+ms, out = ab({"windowed": windowed, "dense": dense})
+assert out["windowed"] == out["dense"], "the windowed output check differs from the dense composition"
+lw = max(W - 1, 0).bit_length()
+res = {"what": "the output check: the device calls against the dense composition, the proof's phase on either path, the prove per phase",
+       "log_n": args.log_n, "log_mem": M, "io_start": LO, "io_len": W, "W_prime": 1 << lw, "sparse_rounds": max(M - lw, 0), "runs": args.runs, "warmup": args.warmup,
+       "calls": {"windowed_ms": stats(ms["windowed"]), "dense_ms": stats(ms["dense"]),
+                 "dense_over_windowed": round(statistics.median(ms["dense"]) / statistics.median(ms["windowed"]), 3), "outputs_equal": True,
+                 "includes": "create / the Fr polynomials' creation, every round, the final values, free; python call overhead on either side",
+                 "windowed_fr_entries": (MEM // 2 + 2 * (1 << lw)) if lw < M else 3 * MEM, "dense_fr_entries": 4 * MEM}}
+d_vf = d_vio = d_rng = d_vio_fr = p_vf = None
+
+# ---- the whole proof, per phase, windowed against dense
+if args.skip_prove:
+    res["prove"] = "not measured"
+else:
+    handles = {w: Z.MemoryProof(log_n=args.log_n, log_mem=M, seed=args.seed, io_start=LO, io_len=W, windowed=(w == "windowed")) for w in ("windowed", "dense")}
+    phases = ("wall_ms", "t_commit_ms", "t_leaves_ms", "t_gp_ms", "t_out_ms", "t_ts_ms", "t_open_ms")
+    pm = {k: {ph: [] for ph in phases} for k in handles}
+    digest, peak, extra = {}, {}, {}
+    for it in range(args.warmup + args.runs):
+        for k, hd in handles.items():
+            r = hd.prove(verify=(it == 0))
+            assert it > 0 or r.verified == 1, hd.last_error()
+            assert digest.setdefault(k, bytes(r.proof_digest)) == bytes(r.proof_digest)
+            peak.setdefault(k, int(r.out_peak_bytes))
+            extra[k] = {"t_witness_ms_of_create": round(r.t_witness_ms, 3), "proof_bytes": int(r.proof_len), "prefix_len": int(r.prefix_len)}
+            if it >= args.warmup:
+                for ph in phases:
+                    pm[k][ph].append(getattr(r, ph))
+    assert digest["windowed"] == digest["dense"], "the two output-check paths give different proofs"
+    res["prove"] = {k: dict({ph: stats(pm[k][ph]) for ph in phases}, out_peak_bytes_first_prove=peak[k], **extra[k]) for k in handles}
+    res["prove"].update({"verified": True, "digests_equal": True,
+                         "dense_over_windowed_t_out": round(statistics.median(pm["dense"]["t_out_ms"]) / statistics.median(pm["windowed"]["t_out_ms"]), 3),
+                         "clock": "host clock around each phase of the worker; every phase ends in a device synchronise or a host exchange; t_out_ms is the "
+                                  "output sumcheck plus the compact opening of v_final at its point; the dense path's Fr copies are made in create"})
+    for hd in handles.values():
+        hd.close()
+res["bench_py_gpus1_steps3_warmup1"] = json.load(open(args.bench)) if args.bench else "not measured"
+print(json.dumps(res), flush=True)
+if args.out:
+    open(args.out, "w").write(json.dumps(res, indent=1) + "\n")
