@@ -649,17 +649,25 @@ struct Field {
 typedef Field<FrParams> Fr;
 typedef Field<FqParams> Fq;
 
-// 16-byte vector load/store of one field element (2 x dwordx4)
-static __device__ __forceinline__ fe fe_load(const fe* p) {
+// 16-byte vector load/store of one field element (2 x dwordx4); on the host (the layer tail, host/layer_tail.hpp) a plain copy
+static FF_HD fe fe_load(const fe* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
     const uint4* q = reinterpret_cast<const uint4*>(p);
     uint4 lo = q[0], hi = q[1];
     fe r;
     r.l[0] = lo.x; r.l[1] = lo.y; r.l[2] = lo.z; r.l[3] = lo.w;
     r.l[4] = hi.x; r.l[5] = hi.y; r.l[6] = hi.z; r.l[7] = hi.w;
     return r;
+#else
+    return *p;
+#endif
 }
-static __device__ __forceinline__ void fe_store(fe* p, const fe& v) {
+static FF_HD void fe_store(fe* p, const fe& v) {
+#if defined(__HIP_DEVICE_COMPILE__)
     uint4* q = reinterpret_cast<uint4*>(p);
     q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
     q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
+#else
+    *p = v;
+#endif
 }

@@ -16,6 +16,7 @@
 #include "prf.hip.hpp"
 #include "fr9.hip.hpp"
 #include "shamir_deal.hip.hpp"
+#include "host/layer_tail.hpp"
 
 static constexpr int PT = 256;      // threads per block
 static constexpr int MAXBLK = 2048; // grid cap for reducing kernels (>= 8 blocks per CU)
@@ -382,54 +383,9 @@ __global__ void __launch_bounds__(PT) k_pst_fold(const fe* __restrict__ r, fe* _
 }
 
 // ------------------------------------------------------------------ kernels: interleaved GKR layer
-// The steps every Fr layer kernel below is made of (the 9 x 29 kernels have their own: layer9_terms .. layer9_finish).  Their shape
-// is the one at which every kernel keeps the registers, scratch and occupancy it had with the steps written out in its body; the
-// notes say where that decided something.
-// bind 4 -> 2 with a zero-padded ragged tail (dense_interleaved_poly.rs:155-195): input chunk ci becomes the bound elements
-// 2 ci and 2 ci + 1, stored (lo before hi is computed) and handed back
-template <int NC>
-static __device__ __forceinline__ void layer_bind_chunk(const fe* ia, const fe* ib, size_t len_in, size_t ci, const fe& r, fe* oa, fe* ob, Sh<NC>& lo,
-                                                        Sh<NC>& hi) {
-    Sh<NC> u0 = sh_load_or_zero<NC>(ia, ib, 4 * ci, len_in), u1 = sh_load_or_zero<NC>(ia, ib, 4 * ci + 1, len_in);
-    Sh<NC> u2 = sh_load_or_zero<NC>(ia, ib, 4 * ci + 2, len_in), u3 = sh_load_or_zero<NC>(ia, ib, 4 * ci + 3, len_in);
-    lo = sh_lerp<NC>(u0, u2, r);
-    sh_store<NC>(oa, ob, 2 * ci, lo);
-    hi = sh_lerp<NC>(u1, u3, r);
-    sh_store<NC>(oa, ob, 2 * ci + 1, hi);
-}
-
-// eq evaluations at 0, 2, 3 of the linear factor through (e0, e1)
-static __device__ __forceinline__ void eq3(const fe& e0, const fe& e1, fe out[3]) {
-    fe m = Fr::sub(e1, e0);
-    out[0] = e0;
-    out[1] = Fr::add(e1, m);
-    out[2] = Fr::add(out[1], m);
-}
-
-// chunks of 4 elements that a round sums over: zip() stops at the shorter side of the layer and the eq table
-static __device__ __forceinline__ size_t layer_chunk_count(size_t len, bool nested, size_t E1_half, size_t E2_len) {
-    size_t nch = (len + 3) / 4;
-    size_t limit = nested ? E1_half * E2_len : E2_len / 2;
-    return nch > limit ? limit : nch;
-}
-
-// the eq pair of item c at 0, 2, 3 from split-eq tables, for the dense layers, the toggle layers and the sparse pair layers alike.
-// Not nested: E1 fully bound, the pair comes from E2 (dense_interleaved_poly.rs:218-268).  Nested: Dao-Thaler split, item c
-// belongs to x2 = c >> log_E1_half, x1 = c % E1_half (:269-356); `scale` = E2[x2] multiplies its terms -- handed back on its own,
-// so that a caller multiplies it into the weights or into its products, whichever keeps fewer values live.
-static __device__ __forceinline__ void split_eq_at(bool nested, const fe* E1, int log_E1_half, const fe* E2, size_t c, fe e[3], fe& scale) {
-    if (nested) {
-        size_t x2 = c >> log_E1_half, x1 = c & (((size_t)1 << log_E1_half) - 1);
-        eq3(fe_load(E1 + 2 * x1), fe_load(E1 + 2 * x1 + 1), e);
-        scale = fe_load(E2 + x2);
-    } else {
-        eq3(fe_load(E2 + 2 * c), fe_load(E2 + 2 * c + 1), e);
-    }
-}
-// the dense layer kernels carry E1_half itself, a power of two
-static __device__ __forceinline__ void layer_eq_at(bool nested, const fe* E1, size_t E1_half, const fe* E2, size_t c, fe e[3], fe& scale) {
-    split_eq_at(nested, E1, __ffsll((long long)E1_half) - 1, E2, c, e, scale);
-}
+// The steps every Fr layer kernel below is made of (the 9 x 29 kernels have their own: layer9_terms .. layer9_finish): those that
+// the host tail shares are in host/layer_tail.hpp (layer_bind_chunk, eq3, layer_chunk_count, split_eq_at, layer_eq_at, layer_terms,
+// fold_pair), the reductions of a workgroup are here.
 // items a round over split-eq tables sums: zip() stops at the shorter side of the layer and the eq table
 template <int NESTED>
 static __device__ __forceinline__ size_t split_eq_limit(size_t E2_len, int log_E1_half) {
@@ -439,24 +395,6 @@ static __device__ __forceinline__ size_t split_eq_limit(size_t E2_len, int log_E
 static __device__ __forceinline__ void partial_row_sum(fe v, fe* sh, fe* __restrict__ partial, size_t row) {
     v = fr_block_sum(v, sh);
     if (threadIdx.x == 0) fe_store(partial + row * gridDim.x + blockIdx.x, v);
-}
-
-// the three terms of one chunk (l0, r0, l1, r1): t_X = (L(X) x R(X)) e_X [scale] at X = 0, 2, 3.  The caller adds them to its sums
-// (with the sums taken by reference here, k_layer_cubic<2, 1> and k_layer_bind_cubic<1, 1> allocate other registers).
-template <int NC>
-static __device__ __forceinline__ void layer_terms(const Sh<NC>& l0, const Sh<NC>& r0, const Sh<NC>& l1, const Sh<NC>& r1, const fe e[3], bool nested,
-                                                   const fe& scale, fe& t0, fe& t2, fe& t3) {
-    Sh<NC> ml = sh_sub<NC>(l1, l0), mr = sh_sub<NC>(r1, r0);
-    Sh<NC> l2 = sh_add<NC>(l1, ml), r2 = sh_add<NC>(r1, mr);
-    Sh<NC> l3 = sh_add<NC>(l2, ml), r3 = sh_add<NC>(r2, mr);
-    t0 = Fr::mul(sh_local_mul<NC>(l0, r0), e[0]);
-    t2 = Fr::mul(sh_local_mul<NC>(l2, r2), e[1]);
-    t3 = Fr::mul(sh_local_mul<NC>(l3, r3), e[2]);
-    if (nested) {
-        t0 = Fr::mul(t0, scale);
-        t2 = Fr::mul(t2, scale);
-        t3 = Fr::mul(t3, scale);
-    }
 }
 
 // the workgroup's three sums, one after the other through `sh` (fr_block_sum); sum k = 0, 1, 2 goes to out(k), which is evaluated
@@ -469,12 +407,6 @@ static __device__ __forceinline__ void layer_finish(fe s0, fe s2, fe s3, fe* sh,
     if (threadIdx.x == 0) fe_store(out(1), s2);
     s3 = fr_block_sum(s3, sh);
     if (threadIdx.x == 0) fe_store(out(2), s3);
-}
-
-// SplitEqPolynomial::bind of one pair: lo + (hi - lo) r
-static __device__ __forceinline__ fe fold_pair(const fe* in, size_t i, const fe& r) {
-    fe lo = fe_load(in + 2 * i), hi = fe_load(in + 2 * i + 1);
-    return Fr::add(lo, Fr::mul(Fr::sub(hi, lo), r));
 }
 
 template <int NC>
@@ -964,6 +896,8 @@ __global__ void __launch_bounds__(GFT) k_layer_group_final(LayerGroupArgs a, siz
 // and goes on -- a PCIe round trip (~3 us) per round instead of a launch.  After the last challenge it binds once
 // more and publishes the final claims.  Every wait is bounded by the wall clock (resident_timeout_s() seconds of the
 // 100 MHz counter): a host that never answers makes the kernel raise `status` and return, so the grid always drains.
+static constexpr size_t HOST_TAIL_CAP = 2048;                 // longest layer a host tail starts from (COZK_HOST_TAIL_MAX is capped here)
+static constexpr size_t HOST_TAIL_AREA = 3 * HOST_TAIL_CAP;  // entries of the mailbox's tail area
 struct alignas(64) RoundMailbox {
     // host -> device, ONE 64-byte line read by one load instruction (four lanes x 16 B = one PCIe read instead of a poll of the
     // sequence number followed by a read of the challenge): pieces 0..2 = three limbs of the challenge + the challenge's number
@@ -973,9 +907,14 @@ struct alignas(64) RoundMailbox {
     uint32_t pad0[16];
     uint32_t res_seq;  // device -> host: result number k is ready
     uint32_t status;   // device -> host: 0 ok, 1 timed out waiting for the host, 2 aborted
-    uint32_t pad2[14];
+    uint32_t tail_n[3];  // device -> host, with a handed-over tail: its layer length, E1_len, E2_len (the host checks its own count)
+    uint32_t pad2[11];
     fe res[4];         // device -> host: cubic sums g(0), g(2), g(3); final: left.a, left.b, right.a, right.b
     unsigned long long dbg[8];  // device -> host: 100 MHz ticks spent waiting / binding / in the cubic sums / publishing
+    // device -> host: the tail handed over to the host (layout of LayerTailView: layer a, layer b, E1, E2), from the resident
+    // kernel's last stage or from k_layer_tail_out; the host binds it in place.  A layer of HOST_TAIL_CAP elements in both
+    // components and as many eq entries.
+    fe tail[HOST_TAIL_AREA];
 };
 static constexpr long long MB_TICKS_PER_S = 100000000ll;  // wall_clock64() runs at 100 MHz
 // watchdog of the resident kernel, seconds (COZK_RESIDENT_TIMEOUT_S, default 10, 1..600): raise it when the round
@@ -987,10 +926,40 @@ static int resident_timeout_s() {
 }
 static constexpr size_t ROUND_PERSIST_MAX = 2048;
 
+// A layer and its live eq tables, copied by one workgroup of nt threads into a host area in the layout of LayerTailView
+// (host/layer_tail.hpp): what the host tail of cozk_layer_prove_rounds starts from.  The caller has checked that they fit.
+template <int NC>
+static __device__ __forceinline__ void layer_tail_out(const fe* la, const fe* lb, size_t len, const fe* E1, size_t E1_len, const fe* E2, size_t E2_len,
+                                                      fe* area, int nt) {
+    for (size_t i = threadIdx.x; i < len; i += nt) {
+        fe_store(area + i, fe_load(la + i));
+        if (NC == 2) fe_store(area + len + i, fe_load(lb + i));
+    }
+    fe* eq = area + NC * len;
+    for (size_t i = threadIdx.x; i < E1_len; i += nt) fe_store(eq + i, fe_load(E1 + i));
+    for (size_t i = threadIdx.x; i < E2_len; i += nt) fe_store(eq + E1_len + i, fe_load(E2 + i));
+}
+// the same for a layer that no resident kernel holds (per-round launches, or a layer that starts at the tail's length)
+template <int NC>
+__global__ void __launch_bounds__(RT) k_layer_tail_out(const fe* la, const fe* lb, size_t len, const fe* E1, size_t E1_len, const fe* E2, size_t E2_len,
+                                                    fe* area) {
+    layer_tail_out<NC>(la, lb, len, E1, E1_len, E2, E2_len, area, RT);
+}
+// what a host tail leaves behind, back on the device: the bound layer (2 elements per component) and the live eq entries, at most
+// TAIL_BACK_MAX values that travel in the kernel arguments -- no source buffer has to outlive the launch
+static constexpr int TAIL_BACK_MAX = 8;
+struct TailBackArgs {
+    fe v[TAIL_BACK_MAX];
+    fe* dst[TAIL_BACK_MAX];
+};
+__global__ void __launch_bounds__(64) k_layer_tail_back(TailBackArgs a, int n) {
+    if ((int)threadIdx.x < n) fe_store(a.dst[threadIdx.x], a.v[threadIdx.x]);
+}
+
 template <int NC, int TRACE>
 __global__ void __launch_bounds__(RT) k_layer_rounds_persistent(fe* la0, fe* lb0, fe* la1, fe* lb1, int lcur, size_t len, fe* e1_0, fe* e1_1,
                                                              int c1, size_t E1_len, fe* e2_0, fe* e2_1, int c2, size_t E2_len, int nrounds,
-                                                             int bind_first, fe r_first, RoundMailbox* mb, long long timeout_ticks) {
+                                                             int bind_first, fe r_first, RoundMailbox* mb, long long timeout_ticks, int tail_out) {
     __shared__ fe sh16[16];
     __shared__ fe sh_r;
     __shared__ int sh_ok;
@@ -1000,7 +969,8 @@ __global__ void __launch_bounds__(RT) k_layer_rounds_persistent(fe* la0, fe* lb0
     fe* e2[2] = {e2_0, e2_1};
     uint32_t seq = 0;
     long long tk0 = TRACE ? wall_clock64() : 0, tk_wait = 0, tk_bind = 0, tk_cubic = 0, tk_pub = 0;  // TRACE: per-phase device times (COZK_TRACE_ROUNDS)
-    // rounds 0 .. nrounds-1 publish cubic sums; "round" nrounds only binds and publishes the final claims
+    // rounds 0 .. nrounds-1 publish cubic sums; "round" nrounds only binds and publishes the final claims, or, with tail_out, the
+    // bound layer and the live eq tables, whose remaining rounds the host runs itself (the host has checked that they fit mb->tail)
     for (int round = 0; round <= nrounds; round++) {
         bool do_bind = round > 0 || bind_first;
         fe r = r_first;
@@ -1091,14 +1061,25 @@ __global__ void __launch_bounds__(RT) k_layer_rounds_persistent(fe* la0, fe* lb0
             tk0 = t;
         }
         if (round == nrounds) {  // final claims: coeffs[0], coeffs[1] of the fully bound layer
+            if (tail_out) {  // all threads, plain vector stores; the binds above are behind a barrier
+                layer_tail_out<NC>(la[lcur], lb[lcur], len, e1[c1], E1_len, e2[c2], E2_len, mb->tail, RT);
+                __threadfence_system();
+                __syncthreads();
+            }
             if (threadIdx.x == 0) {
                 mb->dbg[0] = (unsigned long long)tk_wait;
                 mb->dbg[1] = (unsigned long long)tk_bind;
                 mb->dbg[2] = (unsigned long long)tk_cubic;
                 mb->dbg[3] = (unsigned long long)tk_pub;
-                fe z = Fr::zero();
-                fe v[4] = {fe_load(la[lcur]), NC == 2 ? fe_load(lb[lcur]) : z, fe_load(la[lcur] + 1), NC == 2 ? fe_load(lb[lcur] + 1) : z};
-                for (int k = 0; k < 4; k++) fe_store(&mb->res[k], v[k]);
+                if (tail_out) {
+                    mb->tail_n[0] = (uint32_t)len;
+                    mb->tail_n[1] = (uint32_t)E1_len;
+                    mb->tail_n[2] = (uint32_t)E2_len;
+                } else {
+                    fe z = Fr::zero();
+                    fe v[4] = {fe_load(la[lcur]), NC == 2 ? fe_load(lb[lcur]) : z, fe_load(la[lcur] + 1), NC == 2 ? fe_load(lb[lcur] + 1) : z};
+                    for (int k = 0; k < 4; k++) fe_store(&mb->res[k], v[k]);
+                }
                 __threadfence_system();
                 __hip_atomic_store(&mb->res_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
             }
@@ -1448,6 +1429,17 @@ __global__ void __launch_bounds__(PT) k_eq_expand(const fe* __restrict__ in, fe*
     fe_store(out + 2 * i + 1, hi);
 }
 
+// a table above 2^13 entries as the outer product of two small ones: out[i] = hi[i >> m] x lo[i & (2^m - 1)], hi over the first
+// variables (r[0] stays in the most significant index bit), lo over the last m.  Each workgroup takes one contiguous range, 256
+// consecutive entries per step, so that a wave reads ONE hi entry (2^m >= 128); both factors and the product are canonical
+// (Fr::mul reduces fully), so the bytes are those of the level-by-level table.
+__global__ void __launch_bounds__(PT) k_eq_outer(const fe* __restrict__ hi, const fe* __restrict__ lo, int m, size_t n, fe* __restrict__ out) {
+    const size_t per = ((n / PT + gridDim.x - 1) / gridDim.x) * PT;  // n is a multiple of PT
+    const size_t first = (size_t)blockIdx.x * per, end = first + per < n ? first + per : n;
+    const size_t mask = ((size_t)1 << m) - 1;
+    for (size_t i = first + threadIdx.x; i < end; i += PT) fe_store(out + i, Fr::mul(fe_load(hi + (i >> m)), fe_load(lo + (i & mask))));
+}
+
 // whole EqPolynomial::evals table in one launch (one workgroup; tables here are <= 2^13 entries:
 // the two halves of a split-eq): level j doubles the table in place from the top index down
 __global__ void k_store_fe(fe* out, fe v) { fe_store(out, v); }
@@ -1729,15 +1721,40 @@ static void cubic_coeffs_out(const fe s[3], const uint64_t prev_claim[4], uint64
     for (int i = 0; i < 4; i++) fe_to_u64x4(cf[i], out_coeffs + 4 * i);
 }
 
-// build an eq table on device: out (len 2^nv) from point r (host), big-endian
+// build an eq table on device: out (len 2^nv) from point r (host), big-endian.  Up to 2^13 entries: one launch.  Up to 2^26: three
+// launches, the tables of the first nv - m and of the last m = ceil(nv / 2) variables, then their outer product (k_eq_outer); `tmp`
+// holds the two small tables (eq_tmp_entries).  Above that, or with COZK_EQ_LEVELS set (read per call: the A/B switch and the
+// tests' second opinion): level by level through `tmp` as a second table of 2^nv entries.
+static constexpr int EQ_BUILD_MAX_NV = 13, EQ_OUTER_MAX_NV = 2 * EQ_BUILD_MAX_NV;
+static bool eq_by_levels(int nv) { return nv > EQ_OUTER_MAX_NV || getenv("COZK_EQ_LEVELS") != nullptr; }
+// entries of `tmp` that eq_evals_device needs for a table of nv variables
+static size_t eq_tmp_entries(int nv) {
+    if (nv <= EQ_BUILD_MAX_NV) return 0;
+    if (eq_by_levels(nv)) return (size_t)1 << nv;
+    const int m = (nv + 1) / 2;
+    return ((size_t)1 << m) + ((size_t)1 << (nv - m));
+}
+static void eq_build_launch(cozk_ctx* ctx, const fe* r, int nv, fe* out) {
+    // the point in the kernel arguments
+    EqBuildPoint pt;
+    for (int j = 0; j < nv; j++) pt.r[j] = r[j];
+    for (int j = nv; j < EQ_BUILD_MAX_NV; j++) pt.r[j] = Fr::zero();
+    k_eq_build<<<1, 1024, 0, ctx->stream>>>(pt, nv, out);
+}
 static void eq_evals_device(cozk_ctx* ctx, const fe* r, int nv, fe* out, fe* tmp) {
-    if (nv <= 13) {
-        // small table: one launch, the point in the kernel arguments
+    if (nv <= EQ_BUILD_MAX_NV) {
         (void)tmp;
-        EqBuildPoint pt;
-        for (int j = 0; j < nv; j++) pt.r[j] = r[j];
-        for (int j = nv; j < 13; j++) pt.r[j] = Fr::zero();
-        k_eq_build<<<1, 1024, 0, ctx->stream>>>(pt, nv, out);
+        eq_build_launch(ctx, r, nv, out);
+        HIP_TRY(hipGetLastError());
+        return;
+    }
+    if (!eq_by_levels(nv)) {
+        const int m = (nv + 1) / 2;
+        const size_t n = (size_t)1 << nv;
+        fe *lo = tmp, *hi = tmp + ((size_t)1 << m);
+        eq_build_launch(ctx, r + (nv - m), m, lo);
+        eq_build_launch(ctx, r, nv - m, hi);
+        k_eq_outer<<<grid_capped(n), PT, 0, ctx->stream>>>(hi, lo, m, n, out);
         HIP_TRY(hipGetLastError());
         return;
     }
@@ -1883,7 +1900,7 @@ int cozk_eq_evals(cozk_ctx* ctx, const uint64_t* r, int nv, cozk_vec** out) {
         std::vector<fe> rr(nv);
         for (int j = 0; j < nv; j++) rr[j] = fe_from_u64x4(r + 4 * j);
         fe* d = dev_alloc_fe(n);
-        ctx->scratch2.reserve(n * sizeof(fe));
+        ctx->scratch2.reserve(eq_tmp_entries(nv) * sizeof(fe));  // two half tables, not a second table (512 MiB at nv = 24)
         eq_evals_device(ctx, rr.data(), nv, d, ctx->scratch2.as<fe>());
         *out = new cozk_vec{ctx, n, COZK_SCALAR_FR, d, n * sizeof(fe), true};
     });
@@ -2671,6 +2688,117 @@ int cozk_layer_round(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const uint64
 // final claims run inside ONE resident kernel that exchanges sums and challenges with this thread through a
 // pinned mailbox (k_layer_rounds_persistent).  cb returns 0 on success; `next_claim` must already be this party's
 // additive share.  out_r = num_rounds x 4; final_claims = left.a, left.b, right.a, right.b.
+//
+// The host tail.  Once the layer is at most host_tail_max() elements long, the remaining rounds, the last bind and the final claims
+// run on this thread (layer_tail_rounds, host/layer_tail.hpp) on a copy of the layer and the live eq tables in the mailbox's tail
+// area: the resident kernel is asked for only as many rounds as it takes to get there and publishes the bound tail in its last
+// stage; a layer that no resident kernel holds is gathered by one launch (k_layer_tail_out).  Afterwards the layer and the eq
+// polynomial are left as the device rounds leave them: sides and lengths through layer_advance / spliteq_advance, the values by
+// one small launch (k_layer_tail_back).
+// COZK_HOST_TAIL_MAX=n, read on every call: the longest layer the host takes over, for calls that may use the resident kernel and
+// for calls that may not alike (0: no host tail; capped at HOST_TAIL_CAP).  The defaults are measured ("Host tails"): a
+// resident round costs ~19 us and a launched one ~38 us whatever the length, a host round the callback and its field products.
+extern "C++" {
+static constexpr size_t HOST_TAIL_RESIDENT = 256, HOST_TAIL_LAUNCHED = 512;
+static size_t host_tail_max(bool resident) {
+    const char* s = getenv("COZK_HOST_TAIL_MAX");
+    const long n = s ? atol(s) : (long)(resident ? HOST_TAIL_RESIDENT : HOST_TAIL_LAUNCHED);
+    return n <= 0 ? 0 : ((size_t)n > HOST_TAIL_CAP ? HOST_TAIL_CAP : (size_t)n);
+}
+static RoundMailbox* ctx_mailbox(cozk_ctx* ctx) {
+    if (!ctx->mailbox) HIP_TRY(hipHostMalloc(&ctx->mailbox, sizeof(RoundMailbox), hipHostMallocMapped | hipHostMallocCoherent));
+    return (RoundMailbox*)ctx->mailbox;
+}
+// binds the eq polynomial can still take (its tables are powers of two long)
+static int spliteq_binds_left(size_t E1_len, size_t E2_len) {
+    int n = 0;
+    for (size_t v = E1_len; v > 1; v >>= 1) n++;
+    for (size_t v = E2_len; v > 1; v >>= 1) n++;
+    return n;
+}
+// may the host take over a layer of this shape with `binds` binds to go?  (A call that would bind an exhausted eq polynomial is
+// refused by the device path's own checks: it stays there.)
+static bool host_tail_takes(LayerTailShape s, int nc, size_t tail_max, int binds) {
+    return s.len >= 2 && s.len <= tail_max && layer_tail_entries(nc, s.len, s.E1_len, s.E2_len) <= HOST_TAIL_AREA &&
+           spliteq_binds_left(s.E1_len, s.E2_len) >= binds;
+}
+// The rounds `round` .. num_rounds - 1 of the call on the tail in `area` (the layer and the eq polynomial stand at its shape), and
+// the state they leave behind.
+template <int NC>
+static void layer_host_tail(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, fe* area, bool have_r, uint64_t rr[4], uint64_t pc[4], int round, int num_rounds,
+                            cozk_round_cb cb, void* user, uint64_t* out_r, uint64_t final_claims[16]) {
+    using clk = std::chrono::steady_clock;
+    const bool trace = trace_rounds();
+    LayerTailView t = layer_tail_view(area, NC, l->len, e->E1_len, e->E2_len);
+    double us_cb = 0;
+    const clk::time_point t_start = trace ? clk::now() : clk::time_point();
+    fe fin[4];
+    const int binds = layer_tail_rounds<NC>(
+        t, have_r, have_r ? fe_from_u64x4(rr) : Fr::zero(), num_rounds - round,
+        [&](int j, const fe s[3]) {
+            uint64_t coeffs[16], nc[4];
+            cubic_coeffs_out(s, pc, coeffs);
+            const clk::time_point t0 = trace ? clk::now() : clk::time_point();
+            if (cb(user, round + j, coeffs, rr, nc) != 0) throw CozkError(COZK_ERR_INTERNAL, "layer_prove_rounds: round callback failed");
+            if (trace) us_cb += std::chrono::duration<double, std::micro>(clk::now() - t0).count();
+            memcpy(out_r + 4 * (round + j), rr, 4 * sizeof(uint64_t));
+            memcpy(pc, nc, 4 * sizeof(uint64_t));
+            return fe_from_u64x4(rr);
+        },
+        fin);
+    COZK_REQUIRE(t.len == 2, "final_claims: layer must be fully bound (len == 2)");
+    for (int k = 0; k < 4; k++) fe_to_u64x4(fin[k], final_claims + 4 * k);
+    if (trace && num_rounds > round) {
+        const double us = std::chrono::duration<double, std::micro>(clk::now() - t_start).count();
+        fprintf(stderr, "[host tail] %d rounds from %zu elements: host us/round: callback %.1f compute %.1f\n", num_rounds - round, (size_t)l->len,
+                us_cb / (num_rounds - round), (us - us_cb) / (num_rounds - round));
+    }
+    // the device state: sides and lengths as the launchers move them, then the values
+    for (int b = 0; b < binds; b++) {
+        (void)layer_advance(l);
+        (void)spliteq_advance(e);
+    }
+    COZK_REQUIRE(l->len == t.len && e->E1_len == t.E1_len && e->E2_len == t.E2_len, "layer_prove_rounds: host tail out of step with the layer");
+    if (!binds) return;
+    const size_t nback = layer_tail_entries(NC, t.len, t.E1_len, t.E2_len);
+    if (nback <= (size_t)TAIL_BACK_MAX) {
+        TailBackArgs a{};
+        int n = 0;
+        auto put = [&](fe* dst, const fe* src, size_t cnt) {
+            for (size_t i = 0; i < cnt; i++, n++) {
+                a.v[n] = src[i];
+                a.dst[n] = dst + i;
+            }
+        };
+        put(l->buf[l->cur][0], t.la, t.len);
+        if (NC == 2) put(l->buf[l->cur][1], t.lb, t.len);
+        put(e->E1[e->c1], t.E1, t.E1_len);
+        put(e->E2[e->c2], t.E2, t.E2_len);
+        k_layer_tail_back<<<1, 64, 0, ctx->stream>>>(a, n);
+        HIP_TRY(hipGetLastError());
+    } else {  // an eq polynomial of more variables than the layer binds: copies from the tail area, which the next call reuses
+        HIP_TRY(hipMemcpyAsync(l->buf[l->cur][0], t.la, t.len * sizeof(fe), hipMemcpyHostToDevice, ctx->stream));
+        if (NC == 2) HIP_TRY(hipMemcpyAsync(l->buf[l->cur][1], t.lb, t.len * sizeof(fe), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(e->E1[e->c1], t.E1, t.E1_len * sizeof(fe), hipMemcpyHostToDevice, ctx->stream));
+        if (t.E2_len) HIP_TRY(hipMemcpyAsync(e->E2[e->c2], t.E2, t.E2_len * sizeof(fe), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+}
+// the same for a layer that is on the device alone: one launch gathers it into the tail area, one drain
+static void layer_host_tail_gathered(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, bool have_r, uint64_t rr[4], uint64_t pc[4], int round, int num_rounds,
+                                     cozk_round_cb cb, void* user, uint64_t* out_r, uint64_t final_claims[16]) {
+    RoundMailbox* mb = ctx_mailbox(ctx);
+    const bool rep3 = l->mode == COZK_MODE_REP3;
+    auto* const kernel = rep3 ? k_layer_tail_out<2> : k_layer_tail_out<1>;
+    kernel<<<1, RT, 0, ctx->stream>>>(l->buf[l->cur][0], l->buf[l->cur][1], l->len, e->E1[e->c1], e->E1_len, e->E2[e->c2], e->E2_len, mb->tail);
+    HIP_TRY(hipGetLastError());
+    stream_drain_by_flag(ctx);
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (rep3) layer_host_tail<2>(ctx, l, e, mb->tail, have_r, rr, pc, round, num_rounds, cb, user, out_r, final_claims);
+    else layer_host_tail<1>(ctx, l, e, mb->tail, have_r, rr, pc, round, num_rounds, cb, user, out_r, final_claims);
+}
+}  // extern "C++"
+
 int cozk_layer_prove_rounds(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const uint64_t claim[4], int num_rounds, cozk_round_cb cb,
                             void* user, uint64_t* out_r, uint64_t final_claims[16]) {
     if (!ctx || !l || !e || !claim || !cb || !final_claims || num_rounds < 0 || (num_rounds > 0 && !out_r)) return COZK_ERR_INVALID_ARG;
@@ -2679,13 +2807,18 @@ int cozk_layer_prove_rounds(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const
     memcpy(pc, claim, sizeof pc);
     bool have_r = false;
     int round = 0;
+    const int nc_layer = l->mode == COZK_MODE_REP3 ? 2 : 1;
     // the resident kernel is used when the context allows it (cozk_ctx_set_resident_rounds; by default only while this
     // is the one live context on its device in the process) and is abandoned for the rest of the call once its watchdog
     // has fired (a round callback that took longer than COZK_RESIDENT_TIMEOUT_S): the loop then goes on with one launch
     // per round, from exactly the state the kernel left
     bool allow_resident = !no_persist && ctx_resident_rounds_enabled(ctx);
     for (;;) {
+        bool host_tail = false;
         for (; round < num_rounds; round++) {
+            host_tail = host_tail_takes(LayerTailShape{l->len, e->E1_len, e->E2_len}, nc_layer, host_tail_max(allow_resident),
+                                        num_rounds - round + (have_r ? 1 : 0));
+            if (host_tail) break;
             if (allow_resident && l->len <= ROUND_PERSIST_MAX && l->len >= 2) break;
             int rc = cozk_layer_round(ctx, l, e, have_r ? rr : nullptr, pc, coeffs);
             if (rc != COZK_OK) return rc;
@@ -2706,22 +2839,40 @@ int cozk_layer_prove_rounds(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const
             }
             return cozk_layer_final_claims(ctx, l, final_claims);
         }
+        if (host_tail)  // the layer is short enough already: no resident kernel in between
+            return cozk_guard(ctx, [&] { layer_host_tail_gathered(ctx, l, e, have_r, rr, pc, round, num_rounds, cb, user, out_r, final_claims); });
         int rounds_done = -1;  // >= 0: the resident kernel timed out after that many of its rounds; fall back
         int rc = cozk_guard(ctx, [&] {
             const int nrem = num_rounds - round;
             // both ping-pong buffers of the layer must hold the current length
             pingpong_ensure(l, 1 - l->cur, l->len);
-            if (!ctx->mailbox) HIP_TRY(hipHostMalloc(&ctx->mailbox, sizeof(RoundMailbox), hipHostMallocMapped | hipHostMallocCoherent));
-            RoundMailbox* mb = (RoundMailbox*)ctx->mailbox;
-            memset(mb, 0, sizeof *mb);
+            RoundMailbox* mb = ctx_mailbox(ctx);
+            memset(mb, 0, offsetof(RoundMailbox, tail));
             std::atomic_thread_fence(std::memory_order_seq_cst);
+            const int bind_first = have_r ? 1 : 0;
+            // rounds the kernel keeps: all of them, or, with a host tail, as many as it takes until the layer it has bound is short
+            // enough (at least one: a layer that is short enough before its first round never gets here)
+            int nker = nrem;
+            {
+                const size_t tail_max = host_tail_max(true);
+                LayerTailShape sh{l->len, e->E1_len, e->E2_len};
+                if (bind_first) sh = layer_tail_shape_bound(sh);
+                for (int k = 1; k < nrem && tail_max; k++) {
+                    sh = layer_tail_shape_bound(sh);
+                    if (host_tail_takes(sh, nc_layer, tail_max, nrem - k)) {
+                        nker = k;
+                        break;
+                    }
+                }
+            }
+            const bool tail_out = nker < nrem;
             fe r_first = have_r ? fe_from_u64x4(rr) : Fr::zero();
             const long long ticks = (long long)resident_timeout_s() * MB_TICKS_PER_S;
             const bool rep3 = l->mode == COZK_MODE_REP3;
             auto* const kernel = rep3 ? (trace_rounds() ? k_layer_rounds_persistent<2, 1> : k_layer_rounds_persistent<2, 0>)
                                       : (trace_rounds() ? k_layer_rounds_persistent<1, 1> : k_layer_rounds_persistent<1, 0>);
             kernel<<<1, RT, 0, ctx->stream>>>(l->buf[0][0], l->buf[0][1], l->buf[1][0], l->buf[1][1], l->cur, l->len, e->E1[0], e->E1[1], e->c1, e->E1_len,
-                                              e->E2[0], e->E2[1], e->c2, e->E2_len, nrem, have_r ? 1 : 0, r_first, mb, ticks);
+                                              e->E2[0], e->E2[1], e->c2, e->E2_len, nker, bind_first, r_first, mb, ticks, tail_out ? 1 : 0);
             HIP_TRY(hipGetLastError());
             volatile uint32_t* res_seq = &mb->res_seq;
             volatile uint32_t* status = &mb->status;
@@ -2753,10 +2904,9 @@ int cozk_layer_prove_rounds(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const
                     (void)spliteq_advance(e);
                 }
             };
-            const int bind_first = have_r ? 1 : 0;
             int j = 0;
             bool alive = true;
-            for (; j < nrem; j++) {
+            for (; j < nker; j++) {
                 if (!(alive = wait_result((uint32_t)j + 1))) break;
                 const fe sres[3] = {mb->res[0], mb->res[1], mb->res[2]};
                 cubic_coeffs_out(sres, pc, coeffs);
@@ -2777,7 +2927,7 @@ int cozk_layer_prove_rounds(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const
                     }
                 }
             }
-            if (alive) alive = wait_result((uint32_t)nrem + 1);
+            if (alive) alive = wait_result((uint32_t)nker + 1);
             if (!alive) {
                 // the kernel left while the host was inside the callback of round j - 1 (or before the first result):
                 // it published j results and bound j - 1 (+ bind_first) times; the challenge of round j - 1 is pending
@@ -2786,11 +2936,19 @@ int cozk_layer_prove_rounds(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const
                 rounds_done = j;
                 return;
             }
-            for (int k = 0; k < 4; k++) fe_to_u64x4(mb->res[k], final_claims + 4 * k);
             if (trace_rounds())
-                fprintf(stderr, "[mailbox] %d rounds: device us/round: wait %.1f bind %.1f cubic %.1f publish %.1f\n", nrem,
-                        mb->dbg[0] / 100.0 / (nrem + 1), mb->dbg[1] / 100.0 / (nrem + 1), mb->dbg[2] / 100.0 / nrem, mb->dbg[3] / 100.0 / nrem);
-            mirror_binds(nrem + bind_first);
+                fprintf(stderr, "[mailbox] %d rounds: device us/round: wait %.1f bind %.1f cubic %.1f publish %.1f\n", nker,
+                        mb->dbg[0] / 100.0 / (nker + 1), mb->dbg[1] / 100.0 / (nker + 1), mb->dbg[2] / 100.0 / nker, mb->dbg[3] / 100.0 / nker);
+            mirror_binds(nker + bind_first);
+            if (!tail_out) {
+                for (int k = 0; k < 4; k++) fe_to_u64x4(mb->res[k], final_claims + 4 * k);
+                return;
+            }
+            // the kernel has left the bound tail in the mailbox: the remaining rounds run here
+            COZK_REQUIRE(mb->tail_n[0] == l->len && mb->tail_n[1] == e->E1_len && mb->tail_n[2] == e->E2_len,
+                         "layer_prove_rounds: the resident kernel handed over another tail than expected");
+            if (rep3) layer_host_tail<2>(ctx, l, e, mb->tail, false, rr, pc, round + nker, num_rounds, cb, user, out_r, final_claims);
+            else layer_host_tail<1>(ctx, l, e, mb->tail, false, rr, pc, round + nker, num_rounds, cb, user, out_r, final_claims);
         });
         if (rc != COZK_OK || rounds_done < 0) return rc;
         round += rounds_done;

@@ -23,21 +23,21 @@ static FF_HD fe fr_two_inv() {
 }
 
 template <int NC>
-static __device__ __forceinline__ Sh<NC> sh_load(const fe* a, const fe* b, size_t i) {
+static FF_HD Sh<NC> sh_load(const fe* a, const fe* b, size_t i) {
     Sh<NC> s;
     s.c[0] = fe_load(a + i);
     if (NC == 2) s.c[NC - 1] = fe_load(b + i);
     return s;
 }
 template <int NC>
-static __device__ __forceinline__ Sh<NC> sh_load_or_zero(const fe* a, const fe* b, size_t i, size_t len) {
+static FF_HD Sh<NC> sh_load_or_zero(const fe* a, const fe* b, size_t i, size_t len) {
     if (i < len) return sh_load<NC>(a, b, i);
     Sh<NC> s;
     for (int k = 0; k < NC; k++) s.c[k] = Fr::zero();
     return s;
 }
 template <int NC>
-static __device__ __forceinline__ void sh_store(fe* a, fe* b, size_t i, const Sh<NC>& s) {
+static FF_HD void sh_store(fe* a, fe* b, size_t i, const Sh<NC>& s) {
     fe_store(a + i, s.c[0]);
     if (NC == 2) fe_store(b + i, s.c[NC - 1]);
 }
