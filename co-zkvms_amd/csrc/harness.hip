@@ -157,6 +157,8 @@ static void make_share_vectors(cozk_ctx* ctx, size_t n, uint64_t seed, int party
     b = std::move(sh.second);
 }
 
+#include "host/memcheck_steps.hpp"
+
 static void setup_party(cozk_harness* h, PartyState& ps) {
     const cozk_harness_config& c = h->cfg;
     cozk_ctx* ctx = ps.ctx;
@@ -241,15 +243,7 @@ static void put_commitments(Writer& w, const std::vector<PST13Commitment>& cs, c
 
 static void worker_main(cozk_harness* h, PartyState& ps, StarNetWorker* star, RingNet* ring) {
     const cozk_harness_config& c = h->cfg;
-    WorkerEnv env;
-    env.ctx = ps.ctx;
-    env.mode = c.mode;
-    env.party = ps.party;
-    env.star = star;
-    env.ring = ring;
-    harness_prf_key(c.seed, (uint64_t)ps.party, env.key_self);
-    harness_prf_key(c.seed, (uint64_t)((ps.party + 2) % 3), env.key_prev);
-    HIP_TRY(hipSetDevice(ps.ctx->device));
+    WorkerEnv env = make_worker_env(ps.ctx, c.mode, ps.party, star, ring, &c.seed);
     double t_start = now_ms();
     // ---- 1. commit (Rep3JoltPolynomials::commit, jolt/vm/jolt/witness.rs:304-382): every party MSMs
     //         every polynomial; only P0's public commitments are kept (pst13.rs:165-229)
@@ -828,12 +822,7 @@ int cozk_wire_g1_decode(const uint8_t in[64], uint64_t xy[8], int* infinity) {
 // The C++ round loops of csrc/host/prover.hpp with the host's own transport plugged in (cozk_star_net /
 // cozk_ring_net): what a Rust host calls when it wants the loop, not just the per-round kernels.
 static WorkerEnv make_env(cozk_ctx* ctx, const cozk_worker_params* wp, StarNetWorker* star, RingNet* ring) {
-    WorkerEnv env;
-    env.ctx = ctx;
-    env.mode = wp->mode;
-    env.party = wp->party;
-    env.star = star;
-    env.ring = ring;
+    WorkerEnv env = make_worker_env(ctx, wp->mode, wp->party, star, ring);
     env.set_keys(wp->key_self, wp->key_prev);
     env.mask_ctr = wp->mask_counter;
     return env;

@@ -80,20 +80,6 @@ struct cozk_flow : HarnessHandle {
 
 namespace {
 
-struct MemCheckProof {
-    std::vector<fe> rw_hashes, if_hashes;
-    GrandProductProof rw, init_final;
-    std::vector<fe> rw_claims, if_claims;
-    void write(Writer& w) const {
-        w.vec_fr(rw_hashes);
-        w.vec_fr(if_hashes);
-        rw.write(w);
-        init_final.write(w);
-        w.vec_fr(rw_claims);
-        w.vec_fr(if_claims);
-    }
-};
-
 struct FlowProof {
     std::vector<PST13Commitment> commitments;
     MemCheckProof bytecode, lookups, rw;
@@ -119,13 +105,6 @@ struct FlowProof {
         return w.b;
     }
 };
-
-inline bool flow_vec_eq(const std::vector<fe>& a, const std::vector<fe>& b) {
-    if (a.size() != b.size()) return false;
-    for (size_t i = 0; i < a.size(); i++)
-        if (!Fr::eq(a[i], b[i])) return false;
-    return true;
-}
 
 // ------------------------------------------------------------------------------------------------ the dealer's view
 // host threads over index ranges (the setup of a 2^20-cycle trace generates ~10^8 field elements)
@@ -387,335 +366,203 @@ void flow_setup_party(cozk_flow* h, FlowParty& ps) {
 }
 
 // ------------------------------------------------------------------------------------------------ worker
-struct LeafTerm {
-    const cozk_vec* col = nullptr;    // a compact public column ...
-    const cozk_poly* poly = nullptr;  // ... or a polynomial (shared, or public as Fr)
-    fe coeff;
-};
-struct LeafBuf {
-    VecH a, b;
-};
-
-LeafBuf flow_leaf_alloc(WorkerEnv& env, size_t n) {
-    LeafBuf lb;
-    cozk_vec* v = nullptr;
-    rc_check(cozk_vec_alloc(env.ctx, n, COZK_SCALAR_FR, &v), env.ctx, "vec_alloc(leaves)");
-    lb.a = VecH(v);
-    if (env.mode == COZK_MODE_REP3) {
-        rc_check(cozk_vec_alloc(env.ctx, n, COZK_SCALAR_FR, &v), env.ctx, "vec_alloc(leaves)");
-        lb.b = VecH(v);
-    }
-    return lb;
-}
-void flow_fingerprint(WorkerEnv& env, const std::vector<LeafTerm>& terms, const fe& constant, LeafBuf& out, size_t offset, size_t n) {
-    std::vector<const cozk_vec*> cols;
-    std::vector<const cozk_poly*> polys;
-    std::vector<fe> cc, pc;
-    for (auto& t : terms) {
-        if (t.col) {
-            cols.push_back(t.col);
-            cc.push_back(t.coeff);
-        } else {
-            polys.push_back(t.poly);
-            pc.push_back(t.coeff);
-        }
-    }
-    std::vector<uint64_t> ccw = to_abi(cc), pcw = to_abi(pc);
-    uint64_t cst[4];
-    fe_to_u64x4(constant, cst);
-    rc_check(cozk_fingerprint_leaves(env.ctx, cols.data(), ccw.data(), cols.size(), polys.data(), pcw.data(), polys.size(), cst, env.mode, env.party, out.a.h,
-                                     out.b.h, offset, n),
-             env.ctx, "fingerprint_leaves");
-}
-LayerH flow_leaves_to_layer(WorkerEnv& env, LeafBuf& lb) {
-    cozk_layer* l = nullptr;
-    rc_check(cozk_layer_create(env.ctx, env.mode, lb.a.h, lb.b.h, 1, &l), env.ctx, "layer_create");
-    return LayerH(l);
-}
-
 // batch_evaluate + append of one opening group (compute_openings, lasso/memory_checking/worker.rs:132-176)
 void flow_open(WorkerEnv& env, Rep3ProverOpeningAccumulator& acc, const std::vector<cozk_poly*>& polys, const std::vector<fe>& point) {
-    std::vector<uint64_t> rr = to_abi(point);
-    cozk_vec* chi = nullptr;
-    rc_check(cozk_eq_evals(env.ctx, rr.data(), (int)point.size(), &chi), env.ctx, "eq_evals");
-    VecH chih(chi);
+    VecH chih = mc_eq_table(env, point);
     std::vector<fe> claims = spartan_batch_evaluate(env, polys, chih.h);
     acc.append(env, polys, chih.h, point, claims);
 }
 
-// prove_memory_checking after compute_leaves (lasso/memory_checking/worker.rs:40-127): construct both circuits, send the hashes,
-// prove both, return (r_read_write_opening, r_init_final_opening).  toggle != null: the read / write circuit is toggled.
-void flow_memory_checking(WorkerEnv& env, LayerH rw_leaves, size_t rw_batch, ToggleH toggle, LayerH if_leaves, size_t if_batch, std::vector<fe>& r_rw_open,
-                          std::vector<fe>& r_if_open) {
-    Rep3ToggledBatchedGrandProduct tgp;
-    Rep3BatchedDenseGrandProduct rw;
-    std::vector<fe> rw_hashes;
-    if (toggle.h) {
-        rw_batch = cozk_toggle_batch(toggle.h);
-        tgp = Rep3ToggledBatchedGrandProduct::construct(env, std::move(toggle));
-        rw_hashes = tgp.sparse_layers.claimed_outputs(env);
-    } else {
-        rw = Rep3BatchedDenseGrandProduct::construct(env, std::move(rw_leaves), rw_batch);
-        rw_hashes = rw.claimed_outputs(env);
+// One party across the phases.  A phase reads the committed polynomials through P / CV / T, receives its challenges off env.star and
+// leaves its openings in acc, the ONE accumulator that the last phase reduces; nothing else passes from phase to phase.
+struct FlowWorker {
+    cozk_flow* h;
+    FlowParty& ps;
+    WorkerEnv env;
+    Rep3ProverOpeningAccumulator acc;
+    FlowWorker(cozk_flow* h_, FlowParty& ps_, StarNetWorker* star, RingNet* ring)
+        : h(h_), ps(ps_), env(make_worker_env(ps_.ctx, h_->cfg.mode, ps_.party, star, ring, &h_->cfg.seed)) {}
+    cozk_poly* P(int idx) const { return ps.polys[(size_t)idx].h; }
+    const cozk_vec* CV(int idx) const { return ps.commit_vecs[(size_t)idx].h; }
+    std::vector<cozk_poly*> Ps(int first, int count) const {
+        std::vector<cozk_poly*> v;
+        for (int i = 0; i < count; i++) v.push_back(P(first + i));
+        return v;
     }
-    Rep3BatchedDenseGrandProduct inf = Rep3BatchedDenseGrandProduct::construct(env, std::move(if_leaves), if_batch);
-    std::vector<fe> if_hashes = inf.claimed_outputs(env);
-    {
-        Writer w;
-        w.vec_fr(rw_hashes);
-        w.vec_fr(if_hashes);
-        env.star->send_response(w.b);
+    // a committed polynomial as a leaf term: public ones through their compact column, shared ones through their shares
+    LeafTerm T(int idx, const fe& coeff = Fr::zero()) const { return h->is_public[(size_t)idx] ? LeafTerm{CV(idx), nullptr, coeff} : LeafTerm{nullptr, P(idx), coeff}; }
+    LeafTerm TC(const VecH& col, const fe& coeff = Fr::zero()) const { return mc_col_term(col.h, coeff); }
+    void gammas(int k, std::vector<fe>& g, fe& tau) {  // receive (gamma, tau); g[j] = gamma^j
+        fe gamma;
+        mc_receive_gamma_tau(env.star, gamma, tau);
+        g.assign(1, Fr::one());
+        for (int j = 0; j < k; j++) g.push_back(Fr::mul(g.back(), gamma));
     }
-    std::vector<fe> r_rw = tgp.toggle_layer.h ? tgp.prove_grand_product_worker(env) : rw.prove_grand_product_worker(env);
-    std::vector<fe> r_if = inf.prove_grand_product_worker(env);
-    r_rw_open.assign(r_rw.begin() + ceil_log2(rw_batch), r_rw.end());
-    r_if_open.assign(r_if.begin() + ceil_log2(if_batch), r_if.end());
+    void open(const std::vector<cozk_poly*>& polys, const std::vector<fe>& point) { flow_open(env, acc, polys, point); }
+};
+
+// ---- 1. commit-all: every party MSMs every polynomial; only P0's public commitments are kept (pst13.rs:165-229)
+void flow_commit_worker(FlowWorker& w) {
+    FlowParty& ps = w.ps;
+    std::vector<cozk_vec*> vs;
+    for (size_t i = 0; i < ps.commit_vecs.size(); i++) vs.push_back(ps.msm_vecs[i].h ? ps.msm_vecs[i].h : ps.commit_vecs[i].h);
+    std::vector<PST13Commitment> cm = PST13::batch_commit(ps.ctx, *ps.setup, vs);
+    Writer wr;
+    put_commitments(wr, cm, w.h->is_public, ps.party);
+    w.env.star->send_response(wr.b);
+}
+
+// ---- 2. bytecode (bytecode/worker.rs:43-142): read = a g + v_address g^2 + .. + v_rs2 g^6 + t g^7 + imm - tau, write = read + g^7
+void flow_bytecode_worker(FlowWorker& w) {
+    const FlowIdx& ix = w.h->ix;
+    const size_t N = w.h->N, B = w.h->B;
+    const fe one = Fr::one();
+    std::vector<fe> g, r_rw, r_if;
+    fe tau;
+    w.gammas(7, g, tau);
+    static const int bcv[5] = {jolt::V_ELF, jolt::V_BITFLAGS, jolt::V_BC_RD, jolt::V_BC_RS1, jolt::V_BC_RS2};
+    std::vector<LeafTerm> read = {w.T(jolt::V_BYTECODE_A, g[1])};
+    for (int k = 0; k < 5; k++) read.push_back(w.T(bcv[k], g[(size_t)(2 + k)]));
+    read.push_back(w.T(ix.bc_t_read, g[7]));
+    read.push_back(w.T(jolt::V_IMM, one));
+    LeafBuf rw = mc_leaf_alloc(w.env, 2 * N), inf = mc_leaf_alloc(w.env, 2 * B);
+    mc_fingerprint_leaves(w.env, read, Fr::neg(tau), rw, 0, N);
+    mc_fingerprint_leaves(w.env, read, Fr::sub(g[7], tau), rw, N, N);
+    std::vector<LeafTerm> init = {w.TC(w.ps.iota, g[1])};
+    for (int k = 0; k < 5; k++) init.push_back(w.TC(w.ps.bc_table[(size_t)k], g[(size_t)(2 + k)]));
+    init.push_back(w.TC(w.ps.bc_table[5], one));
+    mc_fingerprint_leaves(w.env, init, Fr::neg(tau), inf, 0, B);
+    init.push_back(w.T(ix.bc_t_final, g[7]));
+    mc_fingerprint_leaves(w.env, init, Fr::neg(tau), inf, B, B);
+    mc_memory_checking(w.env, mc_leaves_to_layer(w.env, rw), 2, ToggleH(), mc_leaves_to_layer(w.env, inf), 2, r_rw, r_if);
+    std::vector<cozk_poly*> rwp = {w.P(jolt::V_BYTECODE_A)};
+    for (int k = 0; k < 5; k++) rwp.push_back(w.P(bcv[k]));
+    rwp.push_back(w.P(jolt::V_IMM));
+    rwp.push_back(w.P(ix.bc_t_read));
+    w.open(rwp, r_rw);
+    w.open({w.P(ix.bc_t_final)}, r_if);
+}
+
+// ---- 3a. instruction lookups, the primary sumcheck (instruction_lookups/worker.rs:95-141)
+void flow_primary_worker(FlowWorker& w) {
+    cozk_flow* h = w.h;
+    const cozk_flow_config& c = h->cfg;
+    const FlowIdx& ix = h->ix;
+    const std::vector<cozk_poly*> E_polys = w.Ps(ix.E, c.n_mem), iflag_polys = w.Ps(jolt::V_INSTR, jolt::N_INSTR);
+    VecH eqh = mc_eq_table(w.env, mc_receive_point(w.env.star));
+    std::vector<const cozk_vec*> fl;
+    for (int i = 0; i < jolt::N_INSTR; i++) fl.push_back(w.CV(jolt::V_INSTR + i));
+    std::vector<const cozk_poly*> Ec(E_polys.begin(), E_polys.end());
+    cozk_primary* pr = nullptr;
+    rc_check(cozk_primary_create(w.env.ctx, c.mode, w.ps.party, h->instrs.data(), h->instrs.size(), fl.data(), Ec.data(), (size_t)c.n_mem, w.P(ix.lasso_out), eqh.h, &pr),
+             w.env.ctx, "primary_create");
+    PrimaryH prh(pr);
+    std::vector<fe> rs = prove_primary_sumcheck_worker(w.env, pr, c.log_n, (size_t)c.n_mem, h->instrs.size());
+    std::vector<fe> r_primary(rs.rbegin(), rs.rend());
+    std::vector<cozk_poly*> pp(E_polys);
+    pp.insert(pp.end(), iflag_polys.begin(), iflag_polys.end());
+    pp.push_back(w.P(ix.lasso_out));
+    w.open(pp, r_primary);
+}
+
+// ---- 3b. instruction lookups, memory checking with the TOGGLED read / write grand product (instruction_lookups/worker.rs:742-860)
+void flow_lookups_worker(FlowWorker& w) {
+    const cozk_flow_config& c = w.h->cfg;
+    const FlowIdx& ix = w.h->ix;
+    const size_t N = w.h->N, M = w.h->M;
+    const fe one = Fr::one();
+    std::vector<fe> g, r_rw, r_if;
+    fe tau;
+    w.gammas(2, g, tau);
+    LeafBuf rw = mc_leaf_alloc(w.env, 2 * (size_t)c.n_mem * N), inf = mc_leaf_alloc(w.env, (size_t)(c.n_subtables + c.n_mem) * M);
+    for (int m = 0; m < c.n_mem; m++) {  // read = t g^2 + v g + a - tau, write = read + g^2 (:776-800)
+        std::vector<LeafTerm> terms = {w.T(ix.read_cts + m, g[2]), w.T(ix.E + m, g[1]), w.T(jolt::V_QUERY + m % 4, one)};
+        mc_fingerprint_leaves(w.env, terms, Fr::neg(tau), rw, (size_t)(2 * m) * N, N);
+        mc_fingerprint_leaves(w.env, terms, Fr::sub(g[2], tau), rw, (size_t)(2 * m + 1) * N, N);
+    }
+    size_t off = 0;
+    for (int s = 0; s < c.n_subtables; s++) {  // per subtable: init, then the finals of its memories (:803-833)
+        std::vector<LeafTerm> init = {w.TC(w.ps.subtables[(size_t)s], g[1]), w.TC(w.ps.iota, one)};
+        mc_fingerprint_leaves(w.env, init, Fr::neg(tau), inf, off, M);
+        off += M;
+        for (int m = 0; m < c.n_mem; m++) {
+            if (m % c.n_subtables != s) continue;
+            std::vector<LeafTerm> fin(init);
+            fin.push_back(w.T(ix.final_cts + m, g[2]));
+            mc_fingerprint_leaves(w.env, fin, Fr::neg(tau), inf, off, M);
+            off += M;
+        }
+    }
+    std::vector<const cozk_vec*> mf;
+    for (auto& f : w.ps.mem_flags) mf.push_back(f.h);
+    cozk_toggle* tg = nullptr;
+    rc_check(cozk_toggle_create(w.env.ctx, c.mode, mf.data(), mf.size(), rw.a.h, rw.b.h, 1, &tg), w.env.ctx, "toggle_create");
+    mc_memory_checking(w.env, LayerH(), 0, ToggleH(tg), mc_leaves_to_layer(w.env, inf), (size_t)(c.n_subtables + c.n_mem), r_rw, r_if);
+    std::vector<cozk_poly*> rwp = w.Ps(jolt::V_QUERY, 4);
+    for (const std::vector<cozk_poly*>& part : {w.Ps(ix.read_cts, c.n_mem), w.Ps(ix.E, c.n_mem), w.Ps(jolt::V_INSTR, jolt::N_INSTR)}) rwp.insert(rwp.end(), part.begin(), part.end());
+    rwp.push_back(w.P(ix.lasso_out));
+    w.open(rwp, r_rw);
+    w.open(w.Ps(ix.final_cts, c.n_mem), r_if);
+}
+
+// ---- 4a. read-write memory (read_write_memory/worker.rs:196-344): the shared leaves over the committed polynomials
+void flow_rw_memory_worker(FlowWorker& w) {
+    const FlowIdx& ix = w.h->ix;
+    const size_t N = w.h->N, MEM = w.h->MEM;
+    std::vector<fe> g, r_rw, r_if;
+    fe tau;
+    w.gammas(2, g, tau);
+    // rs1, rs2, rd, ram as {a, v_read, v_write, index of t_read}: the read timestamps are committed in the order rd, rs1, rs2, ram
+    static const int regs[4][4] = {{jolt::V_BC_RS1, jolt::V_RS1, jolt::V_RS1, 1}, {jolt::V_BC_RS2, jolt::V_RS2, jolt::V_RS2, 2}, {jolt::V_BC_RD, jolt::V_RD_READ, jolt::V_RD_WRITE, 0},
+                                   {jolt::V_RAM_ADDR, jolt::V_RAM_READ, jolt::V_RAM_WRITE, 3}};
+    std::vector<RwSlotLeaves> slots;
+    for (const int* r : regs) slots.push_back({w.T(r[0]), w.T(r[1]), w.T(r[2]), w.T(ix.rw_t_read + r[3])});
+    LeafBuf rw = mc_leaf_alloc(w.env, 8 * N), inf = mc_leaf_alloc(w.env, 2 * MEM);
+    rw_memory_leaves_composed(w.env, slots, w.T(ix.rw_v_init), w.T(ix.rw_v_final), w.T(ix.rw_t_final), w.TC(w.ps.iota), w.TC(w.ps.iota), N, MEM, g[1], tau, rw, inf);
+    mc_memory_checking(w.env, mc_leaves_to_layer(w.env, rw), 8, ToggleH(), mc_leaves_to_layer(w.env, inf), 2, r_rw, r_if);
+    std::vector<cozk_poly*> rwp = {w.P(jolt::V_RAM_ADDR), w.P(jolt::V_RD_READ), w.P(jolt::V_RS1), w.P(jolt::V_RS2), w.P(jolt::V_RAM_READ), w.P(jolt::V_RD_WRITE), w.P(jolt::V_RAM_WRITE)};
+    for (int k = 0; k < 4; k++) rwp.push_back(w.P(ix.rw_t_read + k));
+    rwp.push_back(w.P(jolt::V_BC_RD));
+    rwp.push_back(w.P(jolt::V_BC_RS1));
+    rwp.push_back(w.P(jolt::V_BC_RS2));
+    w.open(rwp, r_rw);
+    w.open({w.P(ix.rw_v_final), w.P(ix.rw_t_final)}, r_if);
+}
+
+// ---- 4b. prove_outputs (read_write_memory/worker.rs:109-180), then v_final opened at the sumcheck's point
+void flow_outputs_worker(FlowWorker& w) {
+    const int v_final = w.h->ix.rw_v_final;
+    const std::vector<fe> r_eq = mc_receive_point(w.env.star);
+    w.open({w.P(v_final)}, prove_outputs_dense_worker(w.env, w.P(v_final), w.ps.io_range, w.ps.v_io, w.h->cfg.log_mem, r_eq));
 }
 
 void flow_worker_main(cozk_flow* h, FlowParty& ps, StarNetWorker* star, RingNet* ring) {
-    const cozk_flow_config& c = h->cfg;
-    const FlowIdx& ix = h->ix;
-    const size_t N = h->N, M = h->M, B = h->B, MEM = h->MEM;
-    WorkerEnv env;
-    env.ctx = ps.ctx;
-    env.mode = c.mode;
-    env.party = ps.party;
-    env.star = star;
-    env.ring = ring;
-    harness_prf_key(c.seed, (uint64_t)ps.party, env.key_self);
-    harness_prf_key(c.seed, (uint64_t)((ps.party + 2) % 3), env.key_prev);
-    HIP_TRY(hipSetDevice(ps.ctx->device));
-    auto P = [&](int idx) { return ps.polys[(size_t)idx].h; };
-    auto CV = [&](int idx) { return (const cozk_vec*)ps.commit_vecs[(size_t)idx].h; };
-    // a committed polynomial as a leaf term: public ones through their compact column, shared ones through their shares
-    auto T = [&](int idx, const fe& coeff) {
-        LeafTerm t;
-        if (h->is_public[(size_t)idx]) t.col = CV(idx);
-        else t.poly = P(idx);
-        t.coeff = coeff;
-        return t;
-    };
-    auto TC = [&](const VecH& col, const fe& coeff) {
-        LeafTerm t;
-        t.col = col.h;
-        t.coeff = coeff;
-        return t;
-    };
-    auto gammas = [&](int k, std::vector<fe>& g, fe& tau) {  // receive (gamma, tau); g[j] = gamma^j
-        Bytes req = star->receive_request();
-        Reader rd(req);
-        fe gamma = rd.fr();
-        tau = rd.fr();
-        g.assign(1, Fr::one());
-        for (int j = 0; j < k; j++) g.push_back(Fr::mul(g.back(), gamma));
-    };
-    const fe one = Fr::one();
-    double t0 = now_ms();
-    // ---- 1. commit-all: every party MSMs every polynomial; only P0's public commitments are kept (pst13.rs:165-229)
-    {
-        std::vector<cozk_vec*> vs;
-        for (size_t i = 0; i < ps.commit_vecs.size(); i++) vs.push_back(ps.msm_vecs[i].h ? ps.msm_vecs[i].h : ps.commit_vecs[i].h);
-        std::vector<PST13Commitment> cm = PST13::batch_commit(ps.ctx, *ps.setup, vs);
-        Writer w;
-        put_commitments(w, cm, h->is_public, ps.party);
-        star->send_response(w.b);
-    }
-    double t1 = now_ms();
-    ps.t_commit = t1 - t0;
-    Rep3ProverOpeningAccumulator acc;
-    std::vector<fe> g, r_rw, r_if;
-    fe tau;
-    // ---- 2. bytecode (bytecode/worker.rs:43-142): read = a g + v_address g^2 + .. + v_rs2 g^6 + t g^7 + imm - tau, write = read + g^7
-    {
-        gammas(7, g, tau);
-        static const int bcv[5] = {jolt::V_ELF, jolt::V_BITFLAGS, jolt::V_BC_RD, jolt::V_BC_RS1, jolt::V_BC_RS2};
-        std::vector<LeafTerm> read = {T(jolt::V_BYTECODE_A, g[1])};
-        for (int k = 0; k < 5; k++) read.push_back(T(bcv[k], g[(size_t)(2 + k)]));
-        read.push_back(T(ix.bc_t_read, g[7]));
-        read.push_back(T(jolt::V_IMM, one));
-        LeafBuf rw = flow_leaf_alloc(env, 2 * N), inf = flow_leaf_alloc(env, 2 * B);
-        flow_fingerprint(env, read, Fr::neg(tau), rw, 0, N);
-        flow_fingerprint(env, read, Fr::sub(g[7], tau), rw, N, N);
-        std::vector<LeafTerm> init = {TC(ps.iota, g[1])};
-        for (int k = 0; k < 5; k++) init.push_back(TC(ps.bc_table[(size_t)k], g[(size_t)(2 + k)]));
-        init.push_back(TC(ps.bc_table[5], one));
-        flow_fingerprint(env, init, Fr::neg(tau), inf, 0, B);
-        init.push_back(T(ix.bc_t_final, g[7]));
-        flow_fingerprint(env, init, Fr::neg(tau), inf, B, B);
-        flow_memory_checking(env, flow_leaves_to_layer(env, rw), 2, ToggleH(), flow_leaves_to_layer(env, inf), 2, r_rw, r_if);
-        std::vector<cozk_poly*> rwp = {P(jolt::V_BYTECODE_A)};
-        for (int k = 0; k < 5; k++) rwp.push_back(P(bcv[k]));
-        rwp.push_back(P(jolt::V_IMM));
-        rwp.push_back(P(ix.bc_t_read));
-        flow_open(env, acc, rwp, r_rw);
-        flow_open(env, acc, {P(ix.bc_t_final)}, r_if);
-    }
-    double t2 = now_ms();
-    ps.t_bytecode = t2 - t1;
-    // ---- 3. instruction lookups (instruction_lookups/worker.rs:95-176)
-    std::vector<cozk_poly*> iflag_polys, E_polys, rc_polys, fc_polys, dims;
-    for (int i = 0; i < jolt::N_INSTR; i++) iflag_polys.push_back(P(jolt::V_INSTR + i));
-    for (int m = 0; m < c.n_mem; m++) {
-        E_polys.push_back(P(ix.E + m));
-        rc_polys.push_back(P(ix.read_cts + m));
-        fc_polys.push_back(P(ix.final_cts + m));
-    }
-    for (int i = 0; i < 4; i++) dims.push_back(P(jolt::V_QUERY + i));
-    {
-        Bytes req = star->receive_request();
-        Reader rd(req);
-        std::vector<fe> r_eq = rd.vec_fr();
-        std::vector<uint64_t> wabi = to_abi(r_eq);
-        cozk_vec* eqv = nullptr;
-        rc_check(cozk_eq_evals(env.ctx, wabi.data(), (int)r_eq.size(), &eqv), env.ctx, "eq_evals");
-        VecH eqh(eqv);
-        std::vector<const cozk_vec*> fl;
-        for (int i = 0; i < jolt::N_INSTR; i++) fl.push_back(CV(jolt::V_INSTR + i));
-        std::vector<const cozk_poly*> Ec(E_polys.begin(), E_polys.end());
-        cozk_primary* pr = nullptr;
-        rc_check(cozk_primary_create(env.ctx, c.mode, ps.party, h->instrs.data(), h->instrs.size(), fl.data(), Ec.data(), (size_t)c.n_mem, P(ix.lasso_out), eqh.h, &pr),
-                 env.ctx, "primary_create");
-        PrimaryH prh(pr);
-        std::vector<fe> rs = prove_primary_sumcheck_worker(env, pr, c.log_n, (size_t)c.n_mem, h->instrs.size());
-        std::vector<fe> r_primary(rs.rbegin(), rs.rend());
-        std::vector<cozk_poly*> pp(E_polys);
-        pp.insert(pp.end(), iflag_polys.begin(), iflag_polys.end());
-        pp.push_back(P(ix.lasso_out));
-        flow_open(env, acc, pp, r_primary);
-    }
-    double t3 = now_ms();
-    ps.t_primary = t3 - t2;
-    {
-        gammas(2, g, tau);
-        LeafBuf rw = flow_leaf_alloc(env, 2 * (size_t)c.n_mem * N), inf = flow_leaf_alloc(env, (size_t)(c.n_subtables + c.n_mem) * M);
-        for (int m = 0; m < c.n_mem; m++) {  // read = t g^2 + v g + a - tau, write = read + g^2 (:776-800)
-            std::vector<LeafTerm> terms = {T(ix.read_cts + m, g[2]), T(ix.E + m, g[1]), T(jolt::V_QUERY + m % 4, one)};
-            flow_fingerprint(env, terms, Fr::neg(tau), rw, (size_t)(2 * m) * N, N);
-            flow_fingerprint(env, terms, Fr::sub(g[2], tau), rw, (size_t)(2 * m + 1) * N, N);
-        }
-        size_t off = 0;
-        for (int s = 0; s < c.n_subtables; s++) {  // per subtable: init, then the finals of its memories (:803-833)
-            std::vector<LeafTerm> init = {TC(ps.subtables[(size_t)s], g[1]), TC(ps.iota, one)};
-            flow_fingerprint(env, init, Fr::neg(tau), inf, off, M);
-            off += M;
-            for (int m = 0; m < c.n_mem; m++) {
-                if (m % c.n_subtables != s) continue;
-                std::vector<LeafTerm> fin(init);
-                fin.push_back(T(ix.final_cts + m, g[2]));
-                flow_fingerprint(env, fin, Fr::neg(tau), inf, off, M);
-                off += M;
-            }
-        }
-        std::vector<const cozk_vec*> mf;
-        for (auto& f : ps.mem_flags) mf.push_back(f.h);
-        cozk_toggle* tg = nullptr;
-        rc_check(cozk_toggle_create(env.ctx, c.mode, mf.data(), mf.size(), rw.a.h, rw.b.h, 1, &tg), env.ctx, "toggle_create");
-        flow_memory_checking(env, LayerH(), 0, ToggleH(tg), flow_leaves_to_layer(env, inf), (size_t)(c.n_subtables + c.n_mem), r_rw, r_if);
-        std::vector<cozk_poly*> rwp(dims);
-        rwp.insert(rwp.end(), rc_polys.begin(), rc_polys.end());
-        rwp.insert(rwp.end(), E_polys.begin(), E_polys.end());
-        rwp.insert(rwp.end(), iflag_polys.begin(), iflag_polys.end());
-        rwp.push_back(P(ix.lasso_out));
-        flow_open(env, acc, rwp, r_rw);
-        flow_open(env, acc, fc_polys, r_if);
-    }
-    double t4 = now_ms();
-    ps.t_lookups_gp = t4 - t3;
-    // ---- 4. read-write memory (read_write_memory/worker.rs:196-344, :109-180)
-    {
-        gammas(2, g, tau);
-        struct Reg {
-            int a, v_read, v_write, t;
-        };
-        static const Reg regs[4] = {{jolt::V_BC_RS1, jolt::V_RS1, jolt::V_RS1, 1}, {jolt::V_BC_RS2, jolt::V_RS2, jolt::V_RS2, 2}, {jolt::V_BC_RD, jolt::V_RD_READ, jolt::V_RD_WRITE, 0},
-                                    {jolt::V_RAM_ADDR, jolt::V_RAM_READ, jolt::V_RAM_WRITE, 3}};
-        LeafBuf rw = flow_leaf_alloc(env, 8 * N), inf = flow_leaf_alloc(env, 2 * MEM);
-        for (int k = 0; k < 4; k++) {
-            flow_fingerprint(env, {T(regs[k].v_read, g[1]), T(ix.rw_t_read + regs[k].t, g[2]), T(regs[k].a, one)}, Fr::neg(tau), rw, (size_t)(2 * k) * N, N);
-            flow_fingerprint(env, {T(regs[k].v_write, g[1]), TC(ps.iota, g[2]), T(regs[k].a, one)}, Fr::neg(tau), rw, (size_t)(2 * k + 1) * N, N);
-        }
-        flow_fingerprint(env, {T(ix.rw_v_init, g[1]), TC(ps.iota, one)}, Fr::neg(tau), inf, 0, MEM);
-        flow_fingerprint(env, {T(ix.rw_v_final, g[1]), T(ix.rw_t_final, g[2]), TC(ps.iota, one)}, Fr::neg(tau), inf, MEM, MEM);
-        flow_memory_checking(env, flow_leaves_to_layer(env, rw), 8, ToggleH(), flow_leaves_to_layer(env, inf), 2, r_rw, r_if);
-        std::vector<cozk_poly*> rwp = {P(jolt::V_RAM_ADDR), P(jolt::V_RD_READ), P(jolt::V_RS1), P(jolt::V_RS2), P(jolt::V_RAM_READ), P(jolt::V_RD_WRITE), P(jolt::V_RAM_WRITE)};
-        for (int k = 0; k < 4; k++) rwp.push_back(P(ix.rw_t_read + k));
-        rwp.push_back(P(jolt::V_BC_RD));
-        rwp.push_back(P(jolt::V_BC_RS1));
-        rwp.push_back(P(jolt::V_BC_RS2));
-        flow_open(env, acc, rwp, r_rw);
-        flow_open(env, acc, {P(ix.rw_v_final), P(ix.rw_t_final)}, r_if);
-        // prove_outputs: sum_x eq(r_eq, x) io_range(x) (v_final(x) - v_io(x)) = 0, degree 3, HighToLow
-        Bytes req = star->receive_request();
-        Reader rd(req);
-        std::vector<fe> r_eq = rd.vec_fr();
-        std::vector<uint64_t> wabi = to_abi(r_eq);
-        cozk_vec* eqv = nullptr;
-        rc_check(cozk_eq_evals(env.ctx, wabi.data(), (int)r_eq.size(), &eqv), env.ctx, "eq_evals");
-        VecH eqh(eqv);
-        cozk_poly *pe = nullptr, *pr = nullptr, *pio = nullptr, *pd = nullptr;
-        rc_check(cozk_poly_create(env.ctx, COZK_MODE_PLAIN, eqh.h, nullptr, &pe), env.ctx, "poly_create");
-        PolyH peh(pe);
-        rc_check(cozk_poly_create(env.ctx, COZK_MODE_PLAIN, ps.io_range.h, nullptr, &pr), env.ctx, "poly_create");
-        PolyH prh(pr);
-        rc_check(cozk_poly_create(env.ctx, COZK_MODE_PLAIN, ps.v_io.h, nullptr, &pio), env.ctx, "poly_create");
-        PolyH pioh(pio);
-        const cozk_poly* two[2] = {P(ix.rw_v_final), pioh.h};
-        fe cf[2] = {one, Fr::neg(one)};
-        std::vector<uint64_t> cfa = to_abi(std::vector<fe>(cf, cf + 2));
-        rc_check(cozk_poly_linear_combination(env.ctx, two, cfa.data(), 2, env.mode, env.party, &pd), env.ctx, "v_final - v_io");
-        PolyH pdh(pd);
-        std::vector<cozk_poly*> sp = {peh.h, prh.h, pdh.h};
-        ArbitraryResult ar = prove_arbitrary_worker(env, Fr::zero(), c.log_mem, sp, 3);
-        flow_open(env, acc, {P(ix.rw_v_final)}, ar.r);
-    }
-    double t5 = now_ms();
-    ps.t_rw = t5 - t4;
+    FlowWorker w(h, ps, star, ring);
+    const double t0 = now_ms();
+    flow_commit_worker(w);
+    const double t1 = now_ms();
+    flow_bytecode_worker(w);
+    const double t2 = now_ms();
+    flow_primary_worker(w);
+    const double t3 = now_ms();
+    flow_lookups_worker(w);
+    const double t4 = now_ms();
+    flow_rw_memory_worker(w);
+    flow_outputs_worker(w);
+    const double t5 = now_ms();
     // ---- 5. Spartan
-    {
-        std::vector<cozk_poly*> cols;
-        for (int v = 0; v < jolt::NUM_INPUTS; v++) cols.push_back(P(v));
-        ps.sp_times = SpartanTimes();
-        prove_spartan_worker(env, h->sys, cols, N, acc, &ps.sp_times);
-    }
-    double t6 = now_ms();
-    ps.t_spartan = t6 - t5;
+    ps.sp_times = SpartanTimes();
+    prove_spartan_worker(w.env, h->sys, w.Ps(0, jolt::NUM_INPUTS), h->N, w.acc, &ps.sp_times);
+    const double t6 = now_ms();
     // ---- 6. one reduce_and_prove over everything
-    acc.reduce_and_prove_worker(env, *ps.setup);
-    double t7 = now_ms();
-    ps.t_open = t7 - t6;
-    ps.t_total = t7 - t0;
+    w.acc.reduce_and_prove_worker(w.env, *ps.setup);
+    const double t7 = now_ms();
+    ps.t_commit = t1 - t0, ps.t_bytecode = t2 - t1, ps.t_primary = t3 - t2, ps.t_lookups_gp = t4 - t3;
+    ps.t_rw = t5 - t4, ps.t_spartan = t6 - t5, ps.t_open = t7 - t6, ps.t_total = t7 - t0;
     ps.record_net(star, ring);
 }
 
 // ------------------------------------------------------------------------------------------------ coordinator
-void flow_coordinate_memory_checking(StarNetCoordinator& net, Transcript& tr, MemCheckProof& mp, size_t rw_layers, bool toggled, size_t if_layers) {
-    std::vector<std::vector<fe>> a, b;
-    for (Bytes& m : net.receive_responses()) {
-        Reader rd(m);
-        a.push_back(rd.vec_fr());
-        b.push_back(rd.vec_fr());
-    }
-    mp.rw_hashes = combine_additive(a);
-    mp.if_hashes = combine_additive(b);
-    tr.append_scalars(mp.rw_hashes);
-    tr.append_scalars(mp.if_hashes);
-    fe claim;
-    std::vector<fe> r;
-    if (toggled) mp.rw = coordinate_prove_toggled_grand_product(net, tr, rw_layers, r);
-    else mp.rw = coordinate_prove_grand_product(net, tr, rw_layers, claim, r);
-    mp.init_final = coordinate_prove_grand_product(net, tr, if_layers, claim, r);
-    mp.rw_claims = Rep3ProverOpeningAccumulator::receive_claims(net, tr);
-    mp.if_claims = Rep3ProverOpeningAccumulator::receive_claims(net, tr);
-}
-
-void flow_broadcast_gamma_tau(StarNetCoordinator& net, Transcript& tr) {
-    fe gamma = tr.challenge_scalar(), tau = tr.challenge_scalar();
-    Writer w;
-    w.fr(gamma);
-    w.fr(tau);
-    net.broadcast_request(w.b);
-}
-
 void flow_coordinate(cozk_flow* h, StarNetCoordinator& net, FlowProof& proof) {
     const cozk_flow_config& c = h->cfg;
     Transcript tr("cozk-jolt");
@@ -726,28 +573,19 @@ void flow_coordinate(cozk_flow* h, StarNetCoordinator& net, FlowProof& proof) {
         proof.commitments = combine_commitments_from_parties(rds, h->nparties);
         for (auto& cm : proof.commitments) tr.append_point(cm.g_product);
     }
-    flow_broadcast_gamma_tau(net, tr);
-    flow_coordinate_memory_checking(net, tr, proof.bytecode, (size_t)c.log_n, false, (size_t)c.log_b);
+    mc_broadcast_gamma_tau(net, tr);
+    mc_coordinate_memory_checking(net, tr, proof.bytecode, (size_t)c.log_n, false, (size_t)c.log_b);
     {
-        std::vector<fe> r_eq = tr.challenge_vector((size_t)c.log_n), r_primary;
-        Writer w;
-        w.vec_fr(r_eq);
-        net.broadcast_request(w.b);
+        std::vector<fe> r_primary;
+        (void)broadcast_challenge_vector(net, tr, (size_t)c.log_n);
         proof.primary = coordinate_primary_sumcheck(net, tr, c.log_n, r_primary, h->nparties, 0);
         proof.primary_claims = Rep3ProverOpeningAccumulator::receive_claims(net, tr);
     }
-    flow_broadcast_gamma_tau(net, tr);
-    flow_coordinate_memory_checking(net, tr, proof.lookups, (size_t)c.log_n + 1, true, (size_t)c.log_m);
-    flow_broadcast_gamma_tau(net, tr);
-    flow_coordinate_memory_checking(net, tr, proof.rw, (size_t)c.log_n, false, (size_t)c.log_mem);
-    {
-        std::vector<fe> r_eq = tr.challenge_vector((size_t)c.log_mem);
-        Writer w;
-        w.vec_fr(r_eq);
-        net.broadcast_request(w.b);
-        (void)coordinate_prove_arbitrary(net, tr, c.log_mem, proof.outputs.compressed_polys);
-        proof.outputs_claims = Rep3ProverOpeningAccumulator::receive_claims(net, tr);
-    }
+    mc_broadcast_gamma_tau(net, tr);
+    mc_coordinate_memory_checking(net, tr, proof.lookups, (size_t)c.log_n + 1, true, (size_t)c.log_m);
+    mc_broadcast_gamma_tau(net, tr);
+    mc_coordinate_memory_checking(net, tr, proof.rw, (size_t)c.log_n, false, (size_t)c.log_mem);
+    coordinate_outputs(net, tr, c.log_mem, proof.outputs, proof.outputs_claims);
     proof.spartan = coordinate_spartan(net, tr, h->sys, h->N);
     std::vector<fe> r_red;
     fe rho, gamma;
@@ -755,271 +593,247 @@ void flow_coordinate(cozk_flow* h, StarNetCoordinator& net, FlowProof& proof) {
 }
 
 // ------------------------------------------------------------------------------------------------ plain verifier
-fe flow_mle_host(const std::vector<fe>& vals, const std::vector<fe>& r) {
-    std::vector<fe> eq = eq_evals_host(r);
-    fe acc = Fr::zero();
-    for (size_t i = 0; i < vals.size(); i++) acc = Fr::add(acc, Fr::mul(eq[i], vals[i]));
-    return acc;
-}
-// the identity column 0, 1, 2, .. at a big-endian point
-fe flow_iota_eval(const std::vector<fe>& r) {
-    fe acc = Fr::zero();
-    for (size_t j = 0; j < r.size(); j++) acc = Fr::add(Fr::dbl(acc), r[j]);
-    return acc;
-}
-// MLE of circuit-major leaves at r = (r_hi over the circuits, padded to a power of two with `pad`) x r_lo
-fe flow_batch_eval(const std::vector<fe>& per_circuit, const std::vector<fe>& r_hi, const fe& pad) {
-    std::vector<fe> eq = eq_evals_host(r_hi);
-    fe acc = Fr::zero();
-    for (size_t cidx = 0; cidx < eq.size(); cidx++) acc = Fr::add(acc, Fr::mul(eq[cidx], cidx < per_circuit.size() ? per_circuit[cidx] : pad));
-    return acc;
+// The verifier across the phases: a phase replays its part of the transcript vt, leaves its openings in opens and names the first
+// check that fails in why; nothing else passes from phase to phase.
+struct FlowVerifier {
+    cozk_flow* h;
+    const FlowProof& proof;
+    Transcript vt;
+    VerifierOpenings opens;
+    std::string& why;
+    FlowVerifier(cozk_flow* h_, const FlowProof& p, std::string& w) : h(h_), proof(p), vt("cozk-jolt"), opens(vt), why(w) {}
+    void gammas(int k, std::vector<fe>& g, fe& tau) {  // (gamma, tau) off the transcript; g[j] = gamma^j
+        fe gamma = vt.challenge_scalar();
+        tau = vt.challenge_scalar();
+        g.assign(1, Fr::one());
+        for (int j = 0; j < k; j++) g.push_back(Fr::mul(g.back(), gamma));
+    }
+};
+
+// ---- 2. bytecode
+bool flow_verify_bytecode(FlowVerifier& v) {
+    cozk_flow* h = v.h;
+    const FlowIdx& ix = h->ix;
+    const MemCheckProof& mp = v.proof.bytecode;
+    std::vector<fe> g;
+    fe tau;
+    v.gammas(7, g, tau);
+    MemCheckPoints p;
+    if (!mc_verify_grand_products(mp, false, 2, 2, (size_t)h->cfg.log_n, (size_t)h->cfg.log_b, v.vt, p)) {
+        v.why = "bytecode: grand products";
+        return false;
+    }
+    std::vector<int> rwp = {jolt::V_BYTECODE_A, jolt::V_ELF, jolt::V_BITFLAGS, jolt::V_BC_RD, jolt::V_BC_RS1, jolt::V_BC_RS2, jolt::V_IMM, ix.bc_t_read};
+    if (!v.opens.take(rwp, p.lo, mp.rw_claims) || !v.opens.take(std::vector<int>{ix.bc_t_final}, p.lo2, mp.if_claims)) {
+        v.why = "bytecode: claims";
+        return false;
+    }
+    const std::vector<fe>& cl = mp.rw_claims;
+    fe read = Fr::sub(cl[6], tau);
+    for (int k = 0; k < 6; k++) read = Fr::add(read, Fr::mul(g[(size_t)(1 + k)], cl[(size_t)k]));
+    read = Fr::add(read, Fr::mul(g[7], cl[7]));
+    if (!Fr::eq(mc_batch_eval({read, Fr::add(read, g[7])}, p.hi, Fr::zero()), p.rw_claim)) {
+        v.why = "bytecode: read / write fingerprints != the GKR claim";
+        return false;
+    }
+    std::vector<fe> initv(h->B);
+    for (size_t i = 0; i < h->B; i++) {
+        fe x = Fr::sub(Fr::add(Fr::from_u64(h->bc_table_clear[5][i]), Fr::mul(g[1], Fr::from_u64(i))), tau);
+        for (int k = 0; k < 5; k++) x = Fr::add(x, Fr::mul(g[(size_t)(2 + k)], Fr::from_u64(h->bc_table_clear[(size_t)k][i])));
+        initv[i] = x;
+    }
+    fe init = mc_mle_host(initv, p.lo2);
+    if (!Fr::eq(mc_batch_eval({init, Fr::add(init, Fr::mul(g[7], mp.if_claims[0]))}, p.hi2, Fr::zero()), p.if_claim)) {
+        v.why = "bytecode: init / final fingerprints != the GKR claim";
+        return false;
+    }
+    return true;
 }
 
-bool flow_verify(cozk_flow* h, const FlowProof& proof, std::string& why) {
+// ---- 3a. instruction lookups, the primary sumcheck
+bool flow_verify_primary(FlowVerifier& v) {
+    cozk_flow* h = v.h;
+    const cozk_flow_config& c = h->cfg;
+    std::vector<fe> r_eq = v.vt.challenge_vector((size_t)c.log_n), rs;
+    const int degree = primary_sumcheck_degree(h->instrs);
+    if (!verify_primary_sumcheck(v.proof.primary, h->instrs, (size_t)c.n_mem, degree, r_eq, v.vt, rs)) {
+        v.why = "primary sumcheck";
+        return false;
+    }
+    if (!mc_vec_eq(v.proof.primary_claims, v.proof.primary.openings)) {
+        v.why = "primary sumcheck: openings != the accumulator's claims";
+        return false;
+    }
+    std::vector<int> pp;
+    for (int m = 0; m < c.n_mem; m++) pp.push_back(h->ix.E + m);
+    for (int i = 0; i < jolt::N_INSTR; i++) pp.push_back(jolt::V_INSTR + i);
+    pp.push_back(h->ix.lasso_out);
+    v.opens.take(pp, std::vector<fe>(rs.rbegin(), rs.rend()), v.proof.primary_claims);
+    return true;
+}
+
+// check_multiset_equality (lasso/memory_checking/worker.rs:40-127): init * writes == reads * finals per memory.  The one check of a
+// CONSISTENT witness: it holds for the counters of cfg.lookups_witness, not for seeded streams.
+bool flow_lookups_multiset_holds(const cozk_flow_config& c, const MemCheckProof& mp) {
+    const std::vector<fe>& rwh = mp.rw_hashes;
+    const std::vector<fe>& ifh = mp.if_hashes;
+    std::vector<size_t> init_at((size_t)c.n_subtables), final_at((size_t)c.n_mem);
+    size_t at = 0;
+    for (int s = 0; s < c.n_subtables; s++) {  // if_hashes per subtable: the init, then the finals of its memories
+        init_at[(size_t)s] = at++;
+        for (int m = 0; m < c.n_mem; m++)
+            if (m % c.n_subtables == s) final_at[(size_t)m] = at++;
+    }
+    for (int m = 0; m < c.n_mem; m++) {
+        const fe reads_finals = Fr::mul(rwh[(size_t)(2 * m)], ifh[final_at[(size_t)m]]);
+        const fe writes_init = Fr::mul(rwh[(size_t)(2 * m + 1)], ifh[init_at[(size_t)(m % c.n_subtables)]]);
+        if (!Fr::eq(reads_finals, writes_init)) return false;
+    }
+    return true;
+}
+
+// ---- 3b. instruction lookups, memory checking
+bool flow_verify_lookups(FlowVerifier& v) {
+    cozk_flow* h = v.h;
     const cozk_flow_config& c = h->cfg;
     const FlowIdx& ix = h->ix;
-    const size_t N = h->N, M = h->M, B = h->B, MEM = h->MEM;
-    const fe one = Fr::one();
-    Transcript vt("cozk-jolt");
-    if ((int)proof.commitments.size() != ix.count) {
+    const MemCheckProof& mp = v.proof.lookups;
+    std::vector<fe> g;
+    fe tau;
+    v.gammas(2, g, tau);
+    const size_t rw_batch = 2 * (size_t)c.n_mem, if_batch = (size_t)(c.n_subtables + c.n_mem);
+    MemCheckPoints p;
+    if (!mc_verify_grand_products(mp, true, rw_batch, if_batch, (size_t)c.log_n + 1, (size_t)c.log_m, v.vt, p)) {
+        v.why = "lookups: grand products";
+        return false;
+    }
+    std::vector<int> rwp, fcp;
+    for (int i = 0; i < 4; i++) rwp.push_back(jolt::V_QUERY + i);
+    for (int m = 0; m < c.n_mem; m++) rwp.push_back(ix.read_cts + m);
+    for (int m = 0; m < c.n_mem; m++) rwp.push_back(ix.E + m);
+    for (int i = 0; i < jolt::N_INSTR; i++) rwp.push_back(jolt::V_INSTR + i);
+    rwp.push_back(ix.lasso_out);
+    for (int m = 0; m < c.n_mem; m++) fcp.push_back(ix.final_cts + m);
+    if (!v.opens.take(rwp, p.lo, mp.rw_claims) || !v.opens.take(fcp, p.lo2, mp.if_claims)) {
+        v.why = "lookups: claims";
+        return false;
+    }
+    const std::vector<fe>& cl = mp.rw_claims;
+    const size_t o_rc = 4, o_E = 4 + (size_t)c.n_mem, o_fl = 4 + 2 * (size_t)c.n_mem;
+    std::vector<fe> fps, fls;
+    for (int m = 0; m < c.n_mem; m++) {
+        fe read = Fr::sub(Fr::add(Fr::add(Fr::mul(g[2], cl[o_rc + (size_t)m]), Fr::mul(g[1], cl[o_E + (size_t)m])), cl[(size_t)(m % 4)]), tau);
+        fps.push_back(read);
+        fps.push_back(Fr::add(read, g[2]));
+        fe fl = Fr::zero();  // the memory's flag = sum of the (one-hot) instruction flags that use it
+        for (int i = 0; i < jolt::N_INSTR; i++) {
+            const cozk_primary_instr& in = h->instrs[(size_t)i];
+            bool uses = false;
+            for (int j = 0; j < in.n_mems; j++) uses |= in.mems[j] == m;
+            if (uses) fl = Fr::add(fl, cl[o_fl + (size_t)i]);
+        }
+        fls.push_back(fl);
+        fls.push_back(fl);
+    }
+    if (!Fr::eq(mc_batch_eval(fls, p.hi, Fr::one()), p.flag_claim) || !Fr::eq(mc_batch_eval(fps, p.hi, Fr::zero()), p.rw_claim)) {
+        v.why = "lookups: toggle layer's flag / fingerprint claims != the opened values";
+        return false;
+    }
+    std::vector<fe> leaves;
+    fe io = mc_iota_eval(p.lo2);
+    for (int s = 0; s < c.n_subtables; s++) {
+        std::vector<fe> sv(h->M);
+        for (size_t i = 0; i < h->M; i++) sv[i] = Fr::from_u64(h->subtables_clear[(size_t)s][i]);
+        fe init = Fr::sub(Fr::add(Fr::mul(g[1], mc_mle_host(sv, p.lo2)), io), tau);
+        leaves.push_back(init);
+        for (int m = 0; m < c.n_mem; m++)
+            if (m % c.n_subtables == s) leaves.push_back(Fr::add(init, Fr::mul(g[2], mp.if_claims[(size_t)m])));
+    }
+    if (!Fr::eq(mc_batch_eval(leaves, p.hi2, Fr::zero()), p.if_claim)) {
+        v.why = "lookups: init / final fingerprints != the GKR claim";
+        return false;
+    }
+    if (c.lookups_witness && !flow_lookups_multiset_holds(c, mp)) {
+        v.why = "lookups: multiset equality of the memory-checking hashes";
+        return false;
+    }
+    return true;
+}
+
+// ---- 4a. read-write memory: the verifier of rw_memory_proof.hpp's memory check, minus the multiset check (seeded counters)
+bool flow_verify_rw_memory(FlowVerifier& v) {
+    cozk_flow* h = v.h;
+    const FlowIdx& ix = h->ix;
+    const MemCheckProof& mp = v.proof.rw;
+    std::vector<fe> g;
+    fe tau;
+    v.gammas(2, g, tau);
+    MemCheckPoints p;
+    if (!mc_verify_grand_products(mp, false, 8, 2, (size_t)h->cfg.log_n, (size_t)h->cfg.log_mem, v.vt, p)) {
+        v.why = "read-write memory: grand products";
+        return false;
+    }
+    std::vector<int> rwp = {jolt::V_RAM_ADDR, jolt::V_RD_READ, jolt::V_RS1, jolt::V_RS2, jolt::V_RAM_READ, jolt::V_RD_WRITE, jolt::V_RAM_WRITE,
+                            ix.rw_t_read, ix.rw_t_read + 1, ix.rw_t_read + 2, ix.rw_t_read + 3, jolt::V_BC_RD, jolt::V_BC_RS1, jolt::V_BC_RS2};
+    if (!v.opens.take(rwp, p.lo, mp.rw_claims) || !v.opens.take(std::vector<int>{ix.rw_v_final, ix.rw_t_final}, p.lo2, mp.if_claims)) {
+        v.why = "read-write memory: claims";
+        return false;
+    }
+    // claims: a_ram 0, v_read_rd 1, v_read_rs1 2, v_read_rs2 3, v_read_ram 4, v_write_rd 5, v_write_ram 6, t_read rd 7 rs1 8 rs2 9 ram 10, a_rd 11, a_rs1 12, a_rs2 13
+    static const std::vector<RwSlotClaims> regs = {{12, 2, 2, 8}, {13, 3, 3, 9}, {11, 1, 5, 7}, {0, 4, 6, 10}};
+    fe rw_claim, if_claim;  // VerifierComputedOpening of v_init
+    rw_memory_verify_leaves(mp.rw_claims, mp.if_claims, regs, mc_mle_host(h->clear[(size_t)ix.rw_v_init], p.lo2), g[1], tau, p, rw_claim, if_claim);
+    if (!Fr::eq(rw_claim, p.rw_claim)) {
+        v.why = "read-write memory: read / write fingerprints != the GKR claim";
+        return false;
+    }
+    if (!Fr::eq(if_claim, p.if_claim)) {
+        v.why = "read-write memory: init / final fingerprints != the GKR claim";
+        return false;
+    }
+    return true;
+}
+
+// ---- 4b. the output check, io_range and v_io evaluated over all of memory
+bool flow_verify_outputs(FlowVerifier& v) {
+    cozk_flow* h = v.h;
+    std::vector<fe> r_eq, r_out;
+    fe claim;
+    if (!verify_outputs(v.vt, h->cfg.log_mem, v.proof.outputs, v.proof.outputs_claims, r_eq, r_out, claim)) {
+        v.why = "output check: shape";
+        return false;
+    }
+    if (!outputs_final_holds(r_eq, r_out, mc_mle_host(h->io_range_clear, r_out), mc_mle_host(h->v_io_clear, r_out), v.proof.outputs_claims[0], claim)) {
+        v.why = "output check: final claim";
+        return false;
+    }
+    v.opens.take(std::vector<int>{h->ix.rw_v_final}, r_out, v.proof.outputs_claims);
+    return true;
+}
+
+// ---- 5. Spartan
+bool flow_verify_spartan(FlowVerifier& v) {
+    std::vector<fe> rx_step, shift_r;
+    fe rho[2];
+    if (!verify_spartan(v.proof.spartan, v.h->sys, v.h->N, v.vt, rx_step, shift_r, rho, v.why)) return false;
+    std::vector<int> cols;
+    for (int i = 0; i < jolt::NUM_INPUTS; i++) cols.push_back(i);
+    v.opens.take(cols, rx_step, v.proof.spartan.witness_evals, &rho[0]);
+    v.opens.take(cols, shift_r, v.proof.spartan.shift_witness_evals, &rho[1]);
+    return true;
+}
+
+// The phases in the transcript's order, then 6. the batched opening (opening_proof.rs:181-235 + the verifier's reduce_and_verify, out of
+// tree): the reduction sumcheck over all openings and ONE PST13 check of the joint polynomial (pairing-free, trapdoor known)
+bool flow_verify(cozk_flow* h, const FlowProof& proof, std::string& why) {
+    FlowVerifier v(h, proof, why);
+    if ((int)proof.commitments.size() != h->ix.count) {
         why = "commitment count";
         return false;
     }
-    for (auto& cm : proof.commitments) vt.append_point(cm.g_product);
-    std::vector<VerifierOpening> opens;
-    // one claim exchange (receive_claims): the batching challenge is drawn right after it (rho given: already drawn)
-    auto take_claims = [&](const std::vector<int>& polys, const std::vector<fe>& point, const std::vector<fe>& claims, const fe* rho = nullptr) {
-        VerifierOpening o;
-        o.polys.assign(polys.begin(), polys.end());
-        o.point = point;
-        o.claims = claims;
-        o.rho = rho ? *rho : vt.challenge_scalar();
-        opens.push_back(o);
-        return polys.size() == claims.size();
-    };
-    std::vector<fe> g;
-    fe tau;
-    auto gammas = [&](int k) {
-        fe gamma = vt.challenge_scalar();
-        tau = vt.challenge_scalar();
-        g.assign(1, one);
-        for (int j = 0; j < k; j++) g.push_back(Fr::mul(g.back(), gamma));
-    };
-    // dense memory checking: both GKR proofs; returns the final claims and points
-    auto verify_dense = [&](const MemCheckProof& mp, bool toggled, size_t rw_batch, size_t if_batch, fe& rw_claim, fe& flag_claim, std::vector<fe>& r_rw, fe& if_claim,
-                            std::vector<fe>& r_if) {
-        vt.append_scalars(mp.rw_hashes);
-        vt.append_scalars(mp.if_hashes);
-        if (!flow_vec_eq(mp.rw.outputs, mp.rw_hashes) || !flow_vec_eq(mp.init_final.outputs, mp.if_hashes) || mp.rw_hashes.size() != rw_batch || mp.if_hashes.size() != if_batch) return false;
-        if (toggled) {
-            if (!verify_toggled_grand_product(mp.rw, vt, flag_claim, rw_claim, r_rw)) return false;
-        } else if (!verify_grand_product(mp.rw, vt, rw_claim, r_rw)) {
-            return false;
-        }
-        return verify_grand_product(mp.init_final, vt, if_claim, r_if);
-    };
-    auto split = [&](const std::vector<fe>& r, size_t batch, std::vector<fe>& hi, std::vector<fe>& lo) {
-        int k = ceil_log2(batch);
-        hi.assign(r.begin(), r.begin() + k);
-        lo.assign(r.begin() + k, r.end());
-    };
-    auto fr_u64 = [](uint64_t v) { return Fr::from_u64(v); };
-    fe rw_claim, flag_claim, if_claim;
-    std::vector<fe> r_rw, r_if, hi, lo, hi2, lo2;
-    // ---- 2. bytecode
-    {
-        gammas(7);
-        if (!verify_dense(proof.bytecode, false, 2, 2, rw_claim, flag_claim, r_rw, if_claim, r_if)) {
-            why = "bytecode: grand products";
-            return false;
-        }
-        split(r_rw, 2, hi, lo);
-        split(r_if, 2, hi2, lo2);
-        std::vector<int> rwp = {jolt::V_BYTECODE_A, jolt::V_ELF, jolt::V_BITFLAGS, jolt::V_BC_RD, jolt::V_BC_RS1, jolt::V_BC_RS2, jolt::V_IMM, ix.bc_t_read};
-        if (!take_claims(rwp, lo, proof.bytecode.rw_claims) || !take_claims({ix.bc_t_final}, lo2, proof.bytecode.if_claims)) {
-            why = "bytecode: claims";
-            return false;
-        }
-        const std::vector<fe>& cl = proof.bytecode.rw_claims;
-        fe read = Fr::sub(cl[6], tau);
-        for (int k = 0; k < 6; k++) read = Fr::add(read, Fr::mul(g[(size_t)(1 + k)], cl[(size_t)k]));
-        read = Fr::add(read, Fr::mul(g[7], cl[7]));
-        if (!Fr::eq(flow_batch_eval({read, Fr::add(read, g[7])}, hi, Fr::zero()), rw_claim)) {
-            why = "bytecode: read / write fingerprints != the GKR claim";
-            return false;
-        }
-        std::vector<fe> initv(B);
-        for (size_t i = 0; i < B; i++) {
-            fe v = Fr::sub(Fr::add(fr_u64(h->bc_table_clear[5][i]), Fr::mul(g[1], fr_u64(i))), tau);
-            for (int k = 0; k < 5; k++) v = Fr::add(v, Fr::mul(g[(size_t)(2 + k)], fr_u64(h->bc_table_clear[(size_t)k][i])));
-            initv[i] = v;
-        }
-        fe init = flow_mle_host(initv, lo2);
-        if (!Fr::eq(flow_batch_eval({init, Fr::add(init, Fr::mul(g[7], proof.bytecode.if_claims[0]))}, hi2, Fr::zero()), if_claim)) {
-            why = "bytecode: init / final fingerprints != the GKR claim";
-            return false;
-        }
-    }
-    // ---- 3. instruction lookups
-    {
-        std::vector<fe> r_eq = vt.challenge_vector((size_t)c.log_n), rs;
-        const int degree = primary_sumcheck_degree(h->instrs);
-        if (!verify_primary_sumcheck(proof.primary, h->instrs, (size_t)c.n_mem, degree, r_eq, vt, rs)) {
-            why = "primary sumcheck";
-            return false;
-        }
-        if (!flow_vec_eq(proof.primary_claims, proof.primary.openings)) {
-            why = "primary sumcheck: openings != the accumulator's claims";
-            return false;
-        }
-        std::vector<int> pp;
-        for (int m = 0; m < c.n_mem; m++) pp.push_back(ix.E + m);
-        for (int i = 0; i < jolt::N_INSTR; i++) pp.push_back(jolt::V_INSTR + i);
-        pp.push_back(ix.lasso_out);
-        take_claims(pp, std::vector<fe>(rs.rbegin(), rs.rend()), proof.primary_claims);
-        gammas(2);
-        const size_t rw_batch = 2 * (size_t)c.n_mem, if_batch = (size_t)(c.n_subtables + c.n_mem);
-        if (!verify_dense(proof.lookups, true, rw_batch, if_batch, rw_claim, flag_claim, r_rw, if_claim, r_if)) {
-            why = "lookups: grand products";
-            return false;
-        }
-        split(r_rw, rw_batch, hi, lo);
-        split(r_if, if_batch, hi2, lo2);
-        std::vector<int> rwp;
-        for (int i = 0; i < 4; i++) rwp.push_back(jolt::V_QUERY + i);
-        for (int m = 0; m < c.n_mem; m++) rwp.push_back(ix.read_cts + m);
-        for (int m = 0; m < c.n_mem; m++) rwp.push_back(ix.E + m);
-        for (int i = 0; i < jolt::N_INSTR; i++) rwp.push_back(jolt::V_INSTR + i);
-        rwp.push_back(ix.lasso_out);
-        std::vector<int> fcp;
-        for (int m = 0; m < c.n_mem; m++) fcp.push_back(ix.final_cts + m);
-        if (!take_claims(rwp, lo, proof.lookups.rw_claims) || !take_claims(fcp, lo2, proof.lookups.if_claims)) {
-            why = "lookups: claims";
-            return false;
-        }
-        const std::vector<fe>& cl = proof.lookups.rw_claims;
-        const size_t o_rc = 4, o_E = 4 + (size_t)c.n_mem, o_fl = 4 + 2 * (size_t)c.n_mem;
-        std::vector<fe> fps, fls;
-        for (int m = 0; m < c.n_mem; m++) {
-            fe read = Fr::sub(Fr::add(Fr::add(Fr::mul(g[2], cl[o_rc + (size_t)m]), Fr::mul(g[1], cl[o_E + (size_t)m])), cl[(size_t)(m % 4)]), tau);
-            fps.push_back(read);
-            fps.push_back(Fr::add(read, g[2]));
-            fe fl = Fr::zero();  // the memory's flag = sum of the (one-hot) instruction flags that use it
-            for (int i = 0; i < jolt::N_INSTR; i++) {
-                const cozk_primary_instr& in = h->instrs[(size_t)i];
-                bool uses = false;
-                for (int j = 0; j < in.n_mems; j++) uses |= in.mems[j] == m;
-                if (uses) fl = Fr::add(fl, cl[o_fl + (size_t)i]);
-            }
-            fls.push_back(fl);
-            fls.push_back(fl);
-        }
-        if (!Fr::eq(flow_batch_eval(fls, hi, one), flag_claim) || !Fr::eq(flow_batch_eval(fps, hi, Fr::zero()), rw_claim)) {
-            why = "lookups: toggle layer's flag / fingerprint claims != the opened values";
-            return false;
-        }
-        std::vector<fe> leaves;
-        fe io = flow_iota_eval(lo2);
-        for (int s = 0; s < c.n_subtables; s++) {
-            std::vector<fe> sv(M);
-            for (size_t i = 0; i < M; i++) sv[i] = fr_u64(h->subtables_clear[(size_t)s][i]);
-            fe init = Fr::sub(Fr::add(Fr::mul(g[1], flow_mle_host(sv, lo2)), io), tau);
-            leaves.push_back(init);
-            for (int m = 0; m < c.n_mem; m++)
-                if (m % c.n_subtables == s) leaves.push_back(Fr::add(init, Fr::mul(g[2], proof.lookups.if_claims[(size_t)m])));
-        }
-        if (!Fr::eq(flow_batch_eval(leaves, hi2, Fr::zero()), if_claim)) {
-            why = "lookups: init / final fingerprints != the GKR claim";
-            return false;
-        }
-        if (c.lookups_witness) {  // check_multiset_equality (lasso/memory_checking/worker.rs:40-127): init * writes == reads * finals per memory
-            const std::vector<fe>& rwh = proof.lookups.rw_hashes;
-            const std::vector<fe>& ifh = proof.lookups.if_hashes;
-            std::vector<size_t> init_at((size_t)c.n_subtables), final_at((size_t)c.n_mem);
-            size_t at = 0;
-            for (int s = 0; s < c.n_subtables; s++) {  // if_hashes per subtable: the init, then the finals of its memories
-                init_at[(size_t)s] = at++;
-                for (int m = 0; m < c.n_mem; m++)
-                    if (m % c.n_subtables == s) final_at[(size_t)m] = at++;
-            }
-            for (int m = 0; m < c.n_mem; m++) {
-                const fe reads_finals = Fr::mul(rwh[(size_t)(2 * m)], ifh[final_at[(size_t)m]]);
-                const fe writes_init = Fr::mul(rwh[(size_t)(2 * m + 1)], ifh[init_at[(size_t)(m % c.n_subtables)]]);
-                if (!Fr::eq(reads_finals, writes_init)) {
-                    why = "lookups: multiset equality of the memory-checking hashes";
-                    return false;
-                }
-            }
-        }
-    }
-    // ---- 4. read-write memory
-    {
-        gammas(2);
-        if (!verify_dense(proof.rw, false, 8, 2, rw_claim, flag_claim, r_rw, if_claim, r_if)) {
-            why = "read-write memory: grand products";
-            return false;
-        }
-        split(r_rw, 8, hi, lo);
-        split(r_if, 2, hi2, lo2);
-        std::vector<int> rwp = {jolt::V_RAM_ADDR, jolt::V_RD_READ, jolt::V_RS1, jolt::V_RS2, jolt::V_RAM_READ, jolt::V_RD_WRITE, jolt::V_RAM_WRITE,
-                                ix.rw_t_read, ix.rw_t_read + 1, ix.rw_t_read + 2, ix.rw_t_read + 3, jolt::V_BC_RD, jolt::V_BC_RS1, jolt::V_BC_RS2};
-        if (!take_claims(rwp, lo, proof.rw.rw_claims) || !take_claims({ix.rw_v_final, ix.rw_t_final}, lo2, proof.rw.if_claims)) {
-            why = "read-write memory: claims";
-            return false;
-        }
-        const std::vector<fe>& cl = proof.rw.rw_claims;
-        // claims: a_ram 0, v_read_rd 1, v_read_rs1 2, v_read_rs2 3, v_read_ram 4, v_write_rd 5, v_write_ram 6, t_read rd 7 rs1 8 rs2 9 ram 10, a_rd 11, a_rs1 12, a_rs2 13
-        struct R4 {
-            int a, vr, vw, t;
-        };
-        static const R4 regs[4] = {{12, 2, 2, 8}, {13, 3, 3, 9}, {11, 1, 5, 7}, {0, 4, 6, 10}};
-        fe ident = flow_iota_eval(lo);
-        std::vector<fe> leaves;
-        for (int k = 0; k < 4; k++) {
-            leaves.push_back(Fr::sub(Fr::add(Fr::add(Fr::mul(g[1], cl[(size_t)regs[k].vr]), Fr::mul(g[2], cl[(size_t)regs[k].t])), cl[(size_t)regs[k].a]), tau));
-            leaves.push_back(Fr::sub(Fr::add(Fr::add(Fr::mul(g[1], cl[(size_t)regs[k].vw]), Fr::mul(g[2], ident)), cl[(size_t)regs[k].a]), tau));
-        }
-        if (!Fr::eq(flow_batch_eval(leaves, hi, Fr::zero()), rw_claim)) {
-            why = "read-write memory: read / write fingerprints != the GKR claim";
-            return false;
-        }
-        fe io = flow_iota_eval(lo2);
-        fe init = Fr::sub(Fr::add(Fr::mul(g[1], flow_mle_host(h->clear[(size_t)ix.rw_v_init], lo2)), io), tau);  // VerifierComputedOpening of v_init
-        fe fin = Fr::sub(Fr::add(Fr::add(Fr::mul(g[1], proof.rw.if_claims[0]), Fr::mul(g[2], proof.rw.if_claims[1])), io), tau);
-        if (!Fr::eq(flow_batch_eval({init, fin}, hi2, Fr::zero()), if_claim)) {
-            why = "read-write memory: init / final fingerprints != the GKR claim";
-            return false;
-        }
-        std::vector<fe> r_eq = vt.challenge_vector((size_t)c.log_mem), r_out;
-        fe claim = Fr::zero();
-        if (!verify_sumcheck_rounds(proof.outputs.compressed_polys, (size_t)c.log_mem, 3, claim, vt, r_out) || proof.outputs_claims.size() != 1) {
-            why = "output check: shape";
-            return false;
-        }
-        fe e = eq_eval(r_eq, r_out);
-        fe want = Fr::mul(Fr::mul(e, flow_mle_host(h->io_range_clear, r_out)), Fr::sub(proof.outputs_claims[0], flow_mle_host(h->v_io_clear, r_out)));
-        if (!Fr::eq(want, claim)) {
-            why = "output check: final claim";
-            return false;
-        }
-        take_claims({ix.rw_v_final}, r_out, proof.outputs_claims);
-    }
-    // ---- 5. Spartan
-    {
-        std::vector<fe> rx_step, shift_r;
-        fe rho[2];
-        if (!verify_spartan(proof.spartan, h->sys, N, vt, rx_step, shift_r, rho, why)) return false;
-        std::vector<int> cols;
-        for (int v = 0; v < jolt::NUM_INPUTS; v++) cols.push_back(v);
-        take_claims(cols, rx_step, proof.spartan.witness_evals, &rho[0]);
-        take_claims(cols, shift_r, proof.spartan.shift_witness_evals, &rho[1]);
-    }
-    // ---- 6. the batched opening (opening_proof.rs:181-235 + the verifier's reduce_and_verify, out of tree): reduction sumcheck over
-    //      all openings, then ONE PST13 check of the joint polynomial (pairing-free, trapdoor known)
-    if (!verify_reduced_opening(opens, proof.commitments, vt, proof.reduced, *h->parties[0].setup, "opening reduction: shape", "opening reduction: final check", why))
-        return false;
-    (void)M;
-    return true;
+    for (auto& cm : proof.commitments) v.vt.append_point(cm.g_product);
+    return flow_verify_bytecode(v) && flow_verify_primary(v) && flow_verify_lookups(v) && flow_verify_rw_memory(v) && flow_verify_outputs(v) && flow_verify_spartan(v) &&
+           verify_reduced_opening(v.opens.list, proof.commitments, v.vt, proof.reduced, *h->parties[0].setup, "opening reduction: shape", "opening reduction: final check", why);
 }
 
 }  // namespace
@@ -1083,9 +897,7 @@ size_t cozk_flow_num_polys(const cozk_flow* h) { return h ? (size_t)h->ix.count 
 cozk_ctx* cozk_flow_ctx(cozk_flow* h, int party) { return h ? party_ctx(h->parties, party) : nullptr; }
 
 int cozk_flow_prove(cozk_flow* h, int verify, cozk_flow_result* res) {
-    if (!h || !res) return COZK_ERR_INVALID_ARG;
-    memset(res, 0, sizeof *res);
-    res->verified = -1;
+    if (!harness_prove_begin(h, res)) return COZK_ERR_INVALID_ARG;
     const int np = h->nparties;
     InProcNets nets(np, np == 3);
     std::vector<Participant> parts;
@@ -1098,17 +910,7 @@ int cozk_flow_prove(cozk_flow* h, int verify, cozk_flow_result* res) {
     }, h->error, wall_ms);
     if (rc != COZK_OK) return rc;
     res->wall_ms = wall_ms;  // the verifier below is outside the clock
-    if (verify) {
-        std::string why;
-        try {
-            HIP_TRY(hipSetDevice(h->parties[0].ctx->device));
-            res->verified = flow_verify(h, proof, why) ? 1 : 0;
-        } catch (const std::exception& e) {
-            why = e.what();
-            res->verified = 0;
-        }
-        if (res->verified == 0) h->error = "verification failed: " + why;
-    }
+    if (verify) harness_verify(h, res, h->parties[0].ctx->device, [&](std::string& why) { return flow_verify(h, proof, why); });
     for (const FlowParty& ps : h->parties) {
         res->t_commit_ms = std::max(res->t_commit_ms, ps.t_commit);
         res->t_bytecode_ms = std::max(res->t_bytecode_ms, ps.t_bytecode);

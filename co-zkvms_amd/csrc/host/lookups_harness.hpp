@@ -211,30 +211,15 @@ struct LookupsProof {
 // star: this party's channel of the grand-product phase; pstars: its 2^log_workers channels of the primary sumcheck
 void lookups_worker_main(cozk_lookups* h, LookupsParty& ps, StarNetWorker* star, const std::vector<StarNetWorker*>& pstars, RingNet* ring) {
     const cozk_lookups_config& c = h->cfg;
-    WorkerEnv env;
-    env.ctx = ps.ctx;
-    env.mode = c.mode;
-    env.party = ps.party;
-    env.star = star;
-    env.ring = ring;
-    harness_prf_key(c.seed, (uint64_t)ps.party, env.key_self);
-    harness_prf_key(c.seed, (uint64_t)((ps.party + 2) % 3), env.key_prev);
-    HIP_TRY(hipSetDevice(ps.ctx->device));
+    WorkerEnv env = make_worker_env(ps.ctx, c.mode, ps.party, star, ring, &c.seed);
     double tp0 = now_ms();
     if (c.primary) {
         // ---- Lasso primary sumcheck (jolt/vm/instruction_lookups/worker.rs:95-141): r_eq from the coordinator, eq table,
         //      then prove_primary_sumcheck (:180-373), split over 2^log_workers worker sub-nets
         const int W = 1 << c.log_workers;
         std::vector<fe> r_eq;
-        for (int w = 0; w < W; w++) {
-            Bytes req = pstars[w]->receive_request();
-            Reader rd(req);
-            r_eq = rd.vec_fr();
-        }
-        std::vector<uint64_t> wabi = to_abi(r_eq);
-        cozk_vec* eqv = nullptr;
-        rc_check(cozk_eq_evals(env.ctx, wabi.data(), (int)r_eq.size(), &eqv), env.ctx, "eq_evals");
-        VecH eqh(eqv);
+        for (int w = 0; w < W; w++) r_eq = mc_receive_point(pstars[w]);
+        VecH eqh = mc_eq_table(env, r_eq);
         const size_t n_mem = ps.E.size(), n_instr = h->instrs.size();
         const size_t chunk = h->N >> c.log_workers;
         // split_poly (worker.rs:213-235): worker w gets the w-th high-variable chunk of every polynomial -- zero-copy views
@@ -418,10 +403,7 @@ int lookups_coordinator_main(cozk_lookups* h, StarNetCoordinator& net, StarNetCo
     Transcript tr("cozk-lookups");
     std::vector<fe> r_eq, r_primary;
     if (h->cfg.primary) {
-        r_eq = tr.challenge_vector((size_t)h->cfg.log_n);
-        Writer w;
-        w.vec_fr(r_eq);
-        pnet.broadcast_request(w.b);
+        r_eq = broadcast_challenge_vector(pnet, tr, (size_t)h->cfg.log_n);
         proof.has_primary = true;
         proof.primary = coordinate_primary_sumcheck(pnet, tr, h->cfg.log_n, r_primary, h->nparties, h->cfg.log_workers);
     }

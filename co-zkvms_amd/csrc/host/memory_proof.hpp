@@ -5,8 +5,8 @@
 // cozk_rw_proof's proof at the same config.  New here is the output check over the CONSISTENT v_final:
 //     sum_x eq(r_eq, x) io_range(x) (v_final(x) - v_io(x)) = 0,   degree 3, HighToLow, then one opening of v_final at the sumcheck's point.
 // The io window is [io_start, io_start + io_len) words and v_io is v_final over it, so an honest run verifies.  windowed = 1: the rounds
-// are cozk_output_check_* over the compact columns (output_check.inc); windowed = 0: the chained flow's composition (flow_harness.hpp)
-// on Fr copies of eq, io_range, v_io and v_final -- three MEM-entry Fr polynomials bound every round -- kept for the A/B, the same bytes.
+// are cozk_output_check_* over the compact columns (output_check.inc); windowed = 0: the chained flow's composition (prove_outputs_dense_worker,
+// memcheck_steps.hpp) on Fr copies of eq, io_range, v_io and v_final -- three MEM-entry Fr polynomials bound every round -- kept for the A/B, the same bytes.
 // Either way the messages are prove_arbitrary_worker's (prove_arbitrary_rounds, the one round loop) and coordinate_prove_arbitrary serves
 // them.  jolt-core is not in the reference tree: PARITY UNPINNED, pinned by the verifier below and tests/memory_proof_ref.py.
 #pragma once
@@ -81,24 +81,14 @@ std::vector<fe> memory_proof_outputs_windowed(cozk_memory_proof* h, WorkerEnv& e
     return r;
 }
 
-// ... dense: the flow's composition on Fr copies (flow_harness.hpp, phase 4)
+// ... dense: the flow's composition on Fr copies
 std::vector<fe> memory_proof_outputs_dense(cozk_memory_proof* h, WorkerEnv& env, const std::vector<fe>& r_eq) {
-    const std::vector<uint64_t> wabi = to_abi(r_eq);
-    cozk_vec* eqv = nullptr;
-    rc_check(cozk_eq_evals(env.ctx, wabi.data(), (int)r_eq.size(), &eqv), env.ctx, "eq_evals");
-    VecH eqh(eqv);
-    PolyH pe = plain_poly(env.ctx, eqh), pr = plain_poly(env.ctx, h->io_range_fr), pio = plain_poly(env.ctx, h->v_io_fr), pvf = plain_poly(env.ctx, h->v_final_fr);
-    const cozk_poly* two[2] = {pvf.h, pio.h};
-    const std::vector<uint64_t> cfa = to_abi({Fr::one(), Fr::neg(Fr::one())});
-    cozk_poly* pd = nullptr;
-    rc_check(cozk_poly_linear_combination(env.ctx, two, cfa.data(), 2, env.mode, env.party, &pd), env.ctx, "v_final - v_io");
-    PolyH pdh(pd);
-    std::vector<cozk_poly*> sp = {pe.h, pr.h, pdh.h};
-    return prove_arbitrary_worker(env, Fr::zero(), h->cfg.log_mem, sp, 3).r;
+    PolyH pvf = plain_poly(env.ctx, h->v_final_fr);
+    return prove_outputs_dense_worker(env, pvf.h, h->io_range_fr, h->v_io_fr, h->cfg.log_mem, r_eq);
 }
 
 void memory_proof_worker_main(cozk_memory_proof* h, RwProofParty& ps, StarNetWorker* star) {
-    WorkerEnv env = rw_proof_env(ps, star);
+    WorkerEnv env = make_worker_env(ps.ctx, COZK_MODE_PLAIN, 0, star, nullptr);
     const TsRangeCols range = ts_range_columns(ps, ps.iota_n);
     Rep3ProverOpeningAccumulator acc;
     // ---- 1-4. the memory check: cozk_rw_proof's steps
@@ -106,9 +96,7 @@ void memory_proof_worker_main(cozk_memory_proof* h, RwProofParty& ps, StarNetWor
     const double t5 = now_ms();
     // ---- the output check: r_eq, log_mem rounds, one opening of v_final at the sumcheck's point
     {
-        Bytes req = star->receive_request();
-        Reader rd(req);
-        const std::vector<fe> r_eq = rd.vec_fr();
+        const std::vector<fe> r_eq = mc_receive_point(star);
         const double t0 = now_ms();
         std::vector<fe> r;
         {
@@ -127,14 +115,7 @@ void memory_proof_coordinate(cozk_memory_proof* h, StarNetCoordinator& net, Memo
     const cozk_rw_proof_config& c = h->rw.cfg;
     Transcript tr("cozk-rw-memory");
     rw_proof_coordinate_memory_check(c, net, tr, proof.commitments, proof.mem);
-    {
-        std::vector<fe> r_eq = tr.challenge_vector((size_t)c.log_mem);
-        Writer w;
-        w.vec_fr(r_eq);
-        net.broadcast_request(w.b);
-        (void)coordinate_prove_arbitrary(net, tr, c.log_mem, proof.outputs.compressed_polys);
-        proof.outputs_claims = Rep3ProverOpeningAccumulator::receive_claims(net, tr);
-    }
+    coordinate_outputs(net, tr, c.log_mem, proof.outputs, proof.outputs_claims);
     rw_proof_coordinate_range_check_and_open(c, net, tr, proof.with_ts, proof.range, proof.reduced);
 }
 
@@ -158,29 +139,20 @@ bool memory_proof_verify(cozk_memory_proof* h, const MemoryProof& proof, std::st
     const cozk_rw_proof_config& c = h->rw.cfg;
     const RwProofIdx ix((size_t)h->rw.ns, c.with_ts != 0);
     Transcript vt("cozk-rw-memory");
-    std::vector<VerifierOpening> opens;
+    VerifierOpenings opens(vt);
     if (!rw_proof_verify_memory_check(&h->rw, proof.commitments, proof.mem, vt, opens, why)) return false;
-    {
-        const std::vector<fe> r_eq = vt.challenge_vector((size_t)c.log_mem);
-        std::vector<fe> r_out;
-        fe claim = Fr::zero();
-        if (!verify_sumcheck_rounds(proof.outputs.compressed_polys, (size_t)c.log_mem, 3, claim, vt, r_out) || proof.outputs_claims.size() != 1) {
-            why = "output check: shape";
-            return false;
-        }
-        fe range_r, v_io_r;
-        memory_proof_window_evals(h, r_out, range_r, v_io_r);
-        if (!Fr::eq(Fr::mul(Fr::mul(eq_eval(r_eq, r_out), range_r), Fr::sub(proof.outputs_claims[0], v_io_r)), claim)) {
-            why = "output check: final claim";
-            return false;
-        }
-        VerifierOpening o;
-        o.point = r_out;
-        o.polys = {ix.v_final};
-        o.claims = proof.outputs_claims;
-        o.rho = vt.challenge_scalar();
-        opens.push_back(o);
+    std::vector<fe> r_eq, r_out;
+    fe claim, range_r, v_io_r;
+    if (!verify_outputs(vt, c.log_mem, proof.outputs, proof.outputs_claims, r_eq, r_out, claim)) {
+        why = "output check: shape";
+        return false;
     }
+    memory_proof_window_evals(h, r_out, range_r, v_io_r);
+    if (!outputs_final_holds(r_eq, r_out, range_r, v_io_r, proof.outputs_claims[0], claim)) {
+        why = "output check: final claim";
+        return false;
+    }
+    opens.take(std::vector<size_t>{ix.v_final}, r_out, proof.outputs_claims);
     return rw_proof_verify_range_check_and_open(&h->rw, proof.commitments, proof.range, proof.reduced, vt, opens, why);
 }
 
@@ -237,9 +209,7 @@ int cozk_memory_proof_destroy(cozk_memory_proof* h) {
 }
 
 int cozk_memory_proof_prove(cozk_memory_proof* h, int verify, cozk_memory_proof_result* res) {
-    if (!h || !res) return COZK_ERR_INVALID_ARG;
-    memset(res, 0, sizeof *res);
-    res->verified = -1;
+    if (!harness_prove_begin(h, res)) return COZK_ERR_INVALID_ARG;
     if (h->rw.parties.empty() || !h->rw.parties[0].setup || !h->v_io.h) return COZK_ERR_INVALID_ARG;  // create failed
     InProcNets nets(1);
     std::vector<Participant> parts;
@@ -252,17 +222,7 @@ int cozk_memory_proof_prove(cozk_memory_proof* h, int verify, cozk_memory_proof_
     }, h->error, wall_ms);
     if (rc != COZK_OK) return rc;
     res->wall_ms = wall_ms;  // the verifier below is outside the clock
-    if (verify) {
-        std::string why;
-        try {
-            HIP_TRY(hipSetDevice(h->rw.parties[0].ctx->device));
-            res->verified = memory_proof_verify(h, proof, why) ? 1 : 0;
-        } catch (const std::exception& e) {
-            why = e.what();
-            res->verified = 0;
-        }
-        if (res->verified == 0) h->error = "verification failed: " + why;
-    }
+    if (verify) harness_verify(h, res, h->rw.parties[0].ctx->device, [&](std::string& why) { return memory_proof_verify(h, proof, why); });
     const RwProofParty& ps = h->rw.parties[0];
     res->t_witness_ms = h->rw.t_witness;
     res->t_commit_ms = ps.t_commit;

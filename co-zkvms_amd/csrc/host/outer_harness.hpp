@@ -119,13 +119,7 @@ struct OuterProofBundle {
 };
 
 void outer_worker_main(cozk_outer_harness* h, OuterParty& ps, StarNetWorker* star) {
-    WorkerEnv env;
-    env.ctx = ps.ctx;
-    env.mode = h->cfg.mode;
-    env.party = ps.party;
-    env.star = star;
-    env.ring = nullptr;  // Az (x) Bz is summed, never reshared: no ring on this path
-    HIP_TRY(hipSetDevice(ps.ctx->device));
+    WorkerEnv env = make_worker_env(ps.ctx, h->cfg.mode, ps.party, star, nullptr);  // Az (x) Bz is summed, never reshared: no ring, no keys
     double t0 = now_ms();
     if (h->cfg.full) {
         std::vector<cozk_poly*> cols;

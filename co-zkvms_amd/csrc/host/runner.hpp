@@ -88,6 +88,30 @@ inline int harness_proof_bytes(const HarnessHandle* h, uint8_t* out, size_t cap)
     return COZK_OK;
 }
 
+// the start of every prove: false on a null argument, else a zeroed result with verified = -1 (not verified)
+template <class H, class R>
+bool harness_prove_begin(const H* h, R* res) {
+    if (!h || !res) return false;
+    memset(res, 0, sizeof *res);
+    res->verified = -1;
+    return true;
+}
+
+// The plain verifier after a prove, outside its clock: f(why) -> bool runs with `device` current.  A refusal, or an exception in f,
+// sets verified = 0 and leaves "verification failed: <why>" as the harness's error.
+template <class R, class F>
+void harness_verify(HarnessHandle* h, R* res, int device, F f) {
+    std::string why;
+    try {
+        HIP_TRY(hipSetDevice(device));
+        res->verified = f(why) ? 1 : 0;
+    } catch (const std::exception& e) {
+        why = e.what();
+        res->verified = 0;
+    }
+    if (res->verified == 0) h->error = "verification failed: " + why;
+}
+
 // the end of every prove: keep the serialized proof for *_proof_bytes, report its length and SHA-256
 template <class R>
 void finish_proof(HarnessHandle* h, Bytes proof, R* res) {

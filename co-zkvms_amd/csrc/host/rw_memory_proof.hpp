@@ -1,10 +1,11 @@
 // In-process harness of party 0's read-write memory proof over a consistent witness (the dealer's side of Jolt's ReadWriteMemoryProof:
 // the memory check init * writes == reads * final of read_write_memory/worker.rs:196-344 with the timestamp range check of
 // ts_range_proof.hpp chained behind it under the same transcript and the same opening accumulator, ONE reduce_and_prove for
-// everything).  The chained flow's phase 4 (flow_harness.hpp) runs the same check on seeded streams, whose multiset check cannot
-// hold; here the witness comes from cozk_rw_memory_witness, so the verifier runs it.  jolt-core is not in the reference tree, so the
-// circuit order, the transcript order and the proof bytes are this project's: PARITY UNPINNED.  What pins them is the plain verifier
-// at the end of this file and the Python restatement tests/rw_proof_ref.py (include/cozk.h has the protocol).
+// everything).  The chained flow (flow_rw_memory_worker, flow_verify_rw_memory) runs the same shared steps of
+// memcheck_steps.hpp -- rw_memory_leaves_composed, mc_memory_checking, mc_verify_grand_products, rw_memory_verify_leaves -- on seeded
+// streams, whose multiset check cannot hold; here the witness comes from cozk_rw_memory_witness, so the verifier runs it.  jolt-core
+// is not in the reference tree, so the circuit order, the transcript order and the proof bytes are this project's: PARITY UNPINNED.
+// What pins them is the plain verifier at the end of this file and tests/rw_proof_ref.py (include/cozk.h has the protocol).
 // Every polynomial is a compact column on the device (U8 register addresses, U32 everything else): the commit takes the MSM's
 // small-scalar path, the leaves come from cozk_rw_memory_leaves / cozk_rw_memory_init_final_leaves, the claims and the joint
 // polynomials from the compact opening calls; no Fr copy of a column exists.
@@ -140,34 +141,15 @@ void rw_proof_setup(cozk_rw_proof* h, RwProofParty& ps) {
     HIP_TRY(hipStreamSynchronize(ctx->stream));
 }
 
-// the 2 n_slots + 2 circuits as cozk_fingerprint_leaves calls (ten at 4 slots, as flow_harness.hpp's phase 4): what the two fused calls replace
-void rw_proof_leaves_composed(WorkerEnv& env, const RwProofParty& ps, int ns, size_t N, size_t MEM, const fe& gamma, const fe& tau, LeafBuf& rw, LeafBuf& inf) {
-    const fe one = Fr::one(), g2 = Fr::mul(gamma, gamma), ntau = Fr::neg(tau);
-    auto C = [](const VecH& v, const fe& coeff) {
-        LeafTerm t;
-        t.col = v.h;
-        t.coeff = coeff;
-        return t;
-    };
-    for (int s = 0; s < ns; s++) {
-        const size_t u = (size_t)s;
+// the 2 n_slots + 2 circuits as cozk_fingerprint_leaves calls (rw_memory_leaves_composed, ten at 4 slots): what the two fused calls replace
+void rw_proof_leaves_composed(WorkerEnv& env, const RwProofParty& ps, size_t N, size_t MEM, const fe& gamma, const fe& tau, LeafBuf& rw, LeafBuf& inf) {
+    std::vector<RwSlotLeaves> slots;
+    for (size_t u = 0; u < ps.addr.size(); u++) {
         const VecH& w = ps.v_written[u].h ? ps.v_written[u] : ps.v_read[u];
-        flow_fingerprint(env, {C(ps.v_read[u], gamma), C(ps.t_read[u], g2), C(ps.addr[u], one)}, ntau, rw, (2 * u) * N, N);
-        flow_fingerprint(env, {C(w, gamma), C(ps.iota_n, g2), C(ps.addr[u], one)}, ntau, rw, (2 * u + 1) * N, N);
+        slots.push_back({mc_col_term(ps.addr[u].h), mc_col_term(ps.v_read[u].h), mc_col_term(w.h), mc_col_term(ps.t_read[u].h)});
     }
-    flow_fingerprint(env, {C(ps.v_init, gamma), C(ps.iota_mem, one)}, ntau, inf, 0, MEM);
-    flow_fingerprint(env, {C(ps.v_final, gamma), C(ps.t_final, g2), C(ps.iota_mem, one)}, ntau, inf, MEM, MEM);
-}
-
-WorkerEnv rw_proof_env(RwProofParty& ps, StarNetWorker* star) {
-    WorkerEnv env;
-    env.ctx = ps.ctx;
-    env.mode = COZK_MODE_PLAIN;
-    env.party = 0;
-    env.star = star;
-    env.ring = nullptr;
-    HIP_TRY(hipSetDevice(ps.ctx->device));
-    return env;
+    rw_memory_leaves_composed(env, slots, mc_col_term(ps.v_init.h), mc_col_term(ps.v_final.h), mc_col_term(ps.t_final.h), mc_col_term(ps.iota_n.h),
+                              mc_col_term(ps.iota_mem.h), N, MEM, gamma, tau, rw, inf);
 }
 
 // Steps 1-4 of the worker, shared with cozk_memory_proof (memory_proof.hpp): the commit, gamma and tau, the leaves, the two grand
@@ -198,14 +180,9 @@ double rw_proof_memory_check_worker(cozk_rw_proof* h, RwProofParty& ps, WorkerEn
     ps.t_commit = t1 - t0;
     // ---- 2. gamma, tau; the leaves
     fe gamma, tau;
-    {
-        Bytes req = star->receive_request();
-        Reader rd(req);
-        gamma = rd.fr();
-        tau = rd.fr();
-    }
+    mc_receive_gamma_tau(star, gamma, tau);
     double t2 = now_ms();
-    LeafBuf rw = flow_leaf_alloc(env, 2 * (size_t)ns * N), inf = flow_leaf_alloc(env, 2 * MEM);
+    LeafBuf rw = mc_leaf_alloc(env, 2 * (size_t)ns * N), inf = mc_leaf_alloc(env, 2 * MEM);
     if (c.leaves_fused) {
         std::vector<const cozk_vec*> a, vr, tr, vw;
         for (int s = 0; s < ns; s++) {
@@ -218,14 +195,14 @@ double rw_proof_memory_check_worker(cozk_rw_proof* h, RwProofParty& ps, WorkerEn
         rc_check(cozk_rw_memory_leaves(env.ctx, a.data(), vr.data(), tr.data(), vw.data(), (size_t)ns, g, t, rw.a.h, 0), env.ctx, "rw_memory_leaves");
         rc_check(cozk_rw_memory_init_final_leaves(env.ctx, ps.v_init.h, ps.v_final.h, ps.t_final.h, g, t, inf.a.h, 0), env.ctx, "rw_memory_init_final_leaves");
     } else {
-        rw_proof_leaves_composed(env, ps, ns, N, MEM, gamma, tau, rw, inf);
+        rw_proof_leaves_composed(env, ps, N, MEM, gamma, tau, rw, inf);
     }
     rc_check(cozk_ctx_synchronize(env.ctx), env.ctx, "synchronize");
     double t3 = now_ms();
     ps.t_leaves = t3 - t2;
     // ---- 3. the two grand products; their claimed outputs are the multiset hashes
     std::vector<fe> r_rw, r_if;
-    flow_memory_checking(env, flow_leaves_to_layer(env, rw), 2 * (size_t)ns, ToggleH(), flow_leaves_to_layer(env, inf), 2, r_rw, r_if);
+    mc_memory_checking(env, mc_leaves_to_layer(env, rw), 2 * (size_t)ns, ToggleH(), mc_leaves_to_layer(env, inf), 2, r_rw, r_if);
     double t4 = now_ms();
     ps.t_gp = t4 - t3;
     // ---- 4. two openings from the compact columns
@@ -251,7 +228,7 @@ void rw_proof_range_check_and_open_worker(cozk_rw_proof* h, RwProofParty& ps, Wo
 }
 
 void rw_proof_worker_main(cozk_rw_proof* h, RwProofParty& ps, StarNetWorker* star) {
-    WorkerEnv env = rw_proof_env(ps, star);
+    WorkerEnv env = make_worker_env(ps.ctx, COZK_MODE_PLAIN, 0, star, nullptr);
     const TsRangeCols range = ts_range_columns(ps, ps.iota_n);
     Rep3ProverOpeningAccumulator acc;
     const double t4 = rw_proof_memory_check_worker(h, ps, env, range, acc);
@@ -260,9 +237,9 @@ void rw_proof_worker_main(cozk_rw_proof* h, RwProofParty& ps, StarNetWorker* sta
 
 // the coordinator's halves of the two worker steps above, under the caller's transcript
 void rw_proof_coordinate_memory_check(const cozk_rw_proof_config& c, StarNetCoordinator& net, Transcript& tr, std::vector<PST13Commitment>& commitments, MemCheckProof& mem) {
-    ts_receive_commitments(net, tr, commitments);
-    flow_broadcast_gamma_tau(net, tr);
-    flow_coordinate_memory_checking(net, tr, mem, (size_t)c.log_n, false, (size_t)c.log_mem);
+    mc_receive_commitments(net, tr, commitments);
+    mc_broadcast_gamma_tau(net, tr);
+    mc_coordinate_memory_checking(net, tr, mem, (size_t)c.log_n, false, (size_t)c.log_mem);
 }
 void rw_proof_coordinate_range_check_and_open(const cozk_rw_proof_config& c, StarNetCoordinator& net, Transcript& tr, bool& with_ts, TsRangeProof& range, ReducedOpeningProof& reduced) {
     with_ts = c.with_ts != 0;
@@ -281,8 +258,7 @@ void rw_proof_coordinate(cozk_rw_proof* h, StarNetCoordinator& net, RwProof& pro
 
 // The plain verifier, in the two steps of the worker (shared with cozk_memory_proof): it replays the transcript `vt`; the first check that
 // fails names itself in `why`.  The memory check leaves its two openings in `opens`.
-bool rw_proof_verify_memory_check(cozk_rw_proof* h, const std::vector<PST13Commitment>& commitments, const MemCheckProof& mp, Transcript& vt, std::vector<VerifierOpening>& opens,
-                                  std::string& why) {
+bool rw_proof_verify_memory_check(cozk_rw_proof* h, const std::vector<PST13Commitment>& commitments, const MemCheckProof& mp, Transcript& vt, VerifierOpenings& opens, std::string& why) {
     const cozk_rw_proof_config& c = h->cfg;
     const size_t ns = (size_t)h->ns;
     const RwProofIdx ix(ns, c.with_ts != 0);
@@ -292,9 +268,6 @@ bool rw_proof_verify_memory_check(cozk_rw_proof* h, const std::vector<PST13Commi
     }
     for (auto& cm : commitments) vt.append_point(cm.g_product);
     const fe gamma = vt.challenge_scalar(), tau = vt.challenge_scalar();
-    const fe g2 = Fr::mul(gamma, gamma);
-    vt.append_scalars(mp.rw_hashes);
-    vt.append_scalars(mp.if_hashes);
     fe lhs = mp.if_hashes[0], rhs = mp.if_hashes[1];
     for (size_t s = 0; s < ns; s++) {
         lhs = Fr::mul(lhs, mp.rw_hashes[2 * s + 1]);
@@ -304,66 +277,46 @@ bool rw_proof_verify_memory_check(cozk_rw_proof* h, const std::vector<PST13Commi
         why = "multiset equality: init * writes != reads * final";
         return false;
     }
-    fe rw_claim, if_claim;
-    std::vector<fe> r_rw, r_if;
-    if (!flow_vec_eq(mp.rw.outputs, mp.rw_hashes) || !flow_vec_eq(mp.init_final.outputs, mp.if_hashes) || !verify_grand_product(mp.rw, vt, rw_claim, r_rw) ||
-        !verify_grand_product(mp.init_final, vt, if_claim, r_if) || r_rw.size() != (size_t)ceil_log2(2 * ns) + (size_t)c.log_n || r_if.size() != 1 + (size_t)c.log_mem) {
+    MemCheckPoints pts;
+    if (!mc_verify_grand_products(mp, false, 2 * ns, 2, (size_t)c.log_n, (size_t)c.log_mem, vt, pts)) {
         why = "grand product: the hashes are not the outputs, or a round or a layer reduction does not hold";
         return false;
     }
-    const int k = ceil_log2(2 * ns);
-    std::vector<fe> hi(r_rw.begin(), r_rw.begin() + k), lo(r_rw.begin() + k, r_rw.end()), hi2(r_if.begin(), r_if.begin() + 1), lo2(r_if.begin() + 1, r_if.end());
-    opens.assign(2, VerifierOpening());
-    opens[0].point = lo;
-    for (size_t i = 0; i < ix.n_rw; i++) opens[0].polys.push_back(i);
-    opens[0].claims = mp.rw_claims;
-    opens[0].rho = vt.challenge_scalar();
-    opens[1].point = lo2;
-    opens[1].polys = {ix.v_final, ix.t_final};
-    opens[1].claims = mp.if_claims;
-    opens[1].rho = vt.challenge_scalar();
-    {
-        const std::vector<fe>& cl = mp.rw_claims;
-        auto h3 = [&](const fe& a, const fe& v, const fe& t) { return Fr::sub(Fr::add(Fr::add(a, Fr::mul(v, gamma)), Fr::mul(t, g2)), tau); };
-        const fe step = flow_iota_eval(lo);
-        std::vector<fe> leaves;
-        for (size_t s = 0; s < ns; s++) {
-            const fe& w = rw_slot_writes((int)s) ? cl[ix.v_written + (s - 2)] : cl[ix.v_read + s];
-            leaves.push_back(h3(cl[ix.addr + s], cl[ix.v_read + s], cl[ix.t_read + s]));
-            leaves.push_back(h3(cl[ix.addr + s], w, step));
-        }
-        std::vector<fe> vi(h->v_init_clear.size());
-        for (size_t a = 0; a < vi.size(); a++) vi[a] = Fr::from_u64(h->v_init_clear[a]);
-        const fe io = flow_iota_eval(lo2);
-        const fe init = h3(io, flow_mle_host(vi, lo2), Fr::zero());  // VerifierComputedOpening of the public v_init
-        const fe fin = h3(io, mp.if_claims[0], mp.if_claims[1]);
-        if (!Fr::eq(flow_batch_eval(leaves, hi, Fr::zero()), rw_claim) || !Fr::eq(flow_batch_eval({init, fin}, hi2, Fr::zero()), if_claim)) {
-            why = "leaf claim: the fingerprints of the claims != a grand product's final claim";
-            return false;
-        }
+    std::vector<size_t> rw_polys(ix.n_rw);
+    for (size_t i = 0; i < ix.n_rw; i++) rw_polys[i] = i;
+    opens.take(rw_polys, pts.lo, mp.rw_claims);
+    opens.take(std::vector<size_t>{ix.v_final, ix.t_final}, pts.lo2, mp.if_claims);
+    std::vector<RwSlotClaims> slots;
+    for (size_t s = 0; s < ns; s++) slots.push_back({ix.addr + s, ix.v_read + s, rw_slot_writes((int)s) ? ix.v_written + (s - 2) : ix.v_read + s, ix.t_read + s});
+    std::vector<fe> vi(h->v_init_clear.size());
+    for (size_t a = 0; a < vi.size(); a++) vi[a] = Fr::from_u64(h->v_init_clear[a]);
+    fe rw_claim, if_claim;  // VerifierComputedOpening of the public v_init
+    rw_memory_verify_leaves(mp.rw_claims, mp.if_claims, slots, mc_mle_host(vi, pts.lo2), gamma, tau, pts, rw_claim, if_claim);
+    if (!Fr::eq(rw_claim, pts.rw_claim) || !Fr::eq(if_claim, pts.if_claim)) {
+        why = "leaf claim: the fingerprints of the claims != a grand product's final claim";
+        return false;
     }
     return true;
 }
 // the range check (with with_ts) and the reduced opening over `opens` and the range check's own
 bool rw_proof_verify_range_check_and_open(cozk_rw_proof* h, const std::vector<PST13Commitment>& commitments, const TsRangeProof& range, const ReducedOpeningProof& reduced,
-                                          Transcript& vt, std::vector<VerifierOpening>& opens, std::string& why) {
+                                          Transcript& vt, VerifierOpenings& opens, std::string& why) {
     const cozk_rw_proof_config& c = h->cfg;
     const size_t ns = (size_t)h->ns;
     const RwProofIdx ix(ns, c.with_ts != 0);
     if (c.with_ts) {
-        VerifierOpening o;
+        std::vector<size_t> polys;
+        for (size_t f = 0; f < 4; f++)
+            for (size_t s = 0; s < ns; s++) polys.push_back(ix.rc_rt + f * ns + s);
+        for (size_t s = 0; s < ns; s++) polys.push_back(ix.t_read + s);  // the step-1 commitments
         std::string inner;
-        if (!ts_range_check_verify(vt, ns, (size_t)c.log_n, range, inner, o)) {
+        if (!ts_range_check_verify(vt, ns, (size_t)c.log_n, range, polys, inner, opens)) {
             why = "timestamp: " + inner;
             return false;
         }
-        for (size_t f = 0; f < 4; f++)
-            for (size_t s = 0; s < ns; s++) o.polys.push_back(ix.rc_rt + f * ns + s);
-        for (size_t s = 0; s < ns; s++) o.polys.push_back(ix.t_read + s);  // the step-1 commitments
-        opens.push_back(o);
     }
     std::string inner;
-    if (!verify_reduced_opening(opens, commitments, vt, reduced, *h->parties[0].setup, "reduction sumcheck: shape", "reduction sumcheck: final check", inner)) {
+    if (!verify_reduced_opening(opens.list, commitments, vt, reduced, *h->parties[0].setup, "reduction sumcheck: shape", "reduction sumcheck: final check", inner)) {
         why = "opening: " + inner;
         return false;
     }
@@ -371,7 +324,7 @@ bool rw_proof_verify_range_check_and_open(cozk_rw_proof* h, const std::vector<PS
 }
 bool rw_proof_verify(cozk_rw_proof* h, const RwProof& proof, std::string& why) {
     Transcript vt("cozk-rw-memory");
-    std::vector<VerifierOpening> opens;
+    VerifierOpenings opens(vt);
     return rw_proof_verify_memory_check(h, proof.commitments, proof.mem, vt, opens, why) &&
            rw_proof_verify_range_check_and_open(h, proof.commitments, proof.range, proof.reduced, vt, opens, why);
 }
@@ -425,9 +378,7 @@ int cozk_rw_proof_destroy(cozk_rw_proof* h) {
 }
 
 int cozk_rw_proof_prove(cozk_rw_proof* h, int verify, cozk_rw_proof_result* res) {
-    if (!h || !res) return COZK_ERR_INVALID_ARG;
-    memset(res, 0, sizeof *res);
-    res->verified = -1;
+    if (!harness_prove_begin(h, res)) return COZK_ERR_INVALID_ARG;
     if (h->parties.empty() || !h->parties[0].setup) return COZK_ERR_INVALID_ARG;  // create failed
     InProcNets nets(1);
     std::vector<Participant> parts;
@@ -440,17 +391,7 @@ int cozk_rw_proof_prove(cozk_rw_proof* h, int verify, cozk_rw_proof_result* res)
     }, h->error, wall_ms);
     if (rc != COZK_OK) return rc;
     res->wall_ms = wall_ms;  // the verifier below is outside the clock
-    if (verify) {
-        std::string why;
-        try {
-            HIP_TRY(hipSetDevice(h->parties[0].ctx->device));
-            res->verified = rw_proof_verify(h, proof, why) ? 1 : 0;
-        } catch (const std::exception& e) {
-            why = e.what();
-            res->verified = 0;
-        }
-        if (res->verified == 0) h->error = "verification failed: " + why;
-    }
+    if (verify) harness_verify(h, res, h->parties[0].ctx->device, [&](std::string& why) { return rw_proof_verify(h, proof, why); });
     const RwProofParty& ps = h->parties[0];
     res->t_witness_ms = h->t_witness;
     res->t_commit_ms = ps.t_commit;

@@ -477,15 +477,8 @@ static void spartan_worker_main(cozk_spartan* h, SpartanParty& ps, StarNetWorker
     const cozk_spartan_config& c = h->cfg;
     cozk_ctx* ctx = ps.ctx;
     int nv = c.log_n;
-    WorkerEnv env;
-    env.ctx = ctx;
-    env.mode = c.mode;
-    env.party = ps.party;
-    env.star = star;
-    env.ring = nullptr;  // neither sumcheck multiplies two secrets across parties: no reshare on this path
-    harness_prf_key(c.seed, (uint64_t)ps.party, env.key_self);
-    harness_prf_key(c.seed, (uint64_t)((ps.party + 2) % 3), env.key_prev);
-    HIP_TRY(hipSetDevice(ctx->device));
+    // neither sumcheck multiplies two secrets across parties: no reshare on this path, no ring
+    WorkerEnv env = make_worker_env(ctx, c.mode, ps.party, star, nullptr, &c.seed);
     double t0 = now_ms();
     // ---- zero_round (worker.rs:153-182)
     cozk_poly *za = nullptr, *zb = nullptr, *zc = nullptr;

@@ -87,17 +87,12 @@ static void setup_participant_split(cozk_harness* h, PartyState& ps, int worker)
 static void worker_main_split(cozk_harness* h, PartyState& ps, int worker, StarNetWorker* star, RingNet* ring) {
     const cozk_harness_config& c = h->cfg;
     SplitEnv se;
-    se.env.ctx = ps.ctx;
-    se.env.mode = c.mode;
-    se.env.party = ps.party;
-    se.env.star = star;
-    se.env.ring = ring;
+    se.env = make_worker_env(ps.ctx, c.mode, ps.party, star, ring);  // the keys are per worker sub-net
     harness_prf_key(c.seed, (uint64_t)ps.party + 16ull * (uint64_t)worker, se.env.key_self);
     harness_prf_key(c.seed, (uint64_t)((ps.party + 2) % 3) + 16ull * (uint64_t)worker, se.env.key_prev);
     se.worker = worker;
     se.k = c.log_workers;
     WorkerEnv& env = se.env;
-    HIP_TRY(hipSetDevice(ps.ctx->device));
     double t_start = now_ms();
     {
         std::vector<cozk_vec*> vs;

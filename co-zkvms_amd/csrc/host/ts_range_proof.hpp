@@ -174,45 +174,19 @@ void ts_proof_setup(cozk_ts_proof* h, TsProofParty& ps) {
 // the 6 n_slots + 1 circuits as 25 (at 4 slots) cozk_fingerprint_leaves calls: what cozk_timestamp_range_leaves replaces
 void ts_proof_leaves_composed(WorkerEnv& env, const TsRangeCols& ps, int ns, size_t N, const fe& gamma, const fe& tau, LeafBuf& lb) {
     const fe g1 = Fr::add(gamma, Fr::one()), g2 = Fr::mul(gamma, gamma), ntau = Fr::neg(tau), w = Fr::sub(g2, tau);
-    auto C = [](const cozk_vec* v, const fe& coeff) {
-        LeafTerm t;
-        t.col = v;
-        t.coeff = coeff;
-        return t;
-    };
     for (int s = 0; s < ns; s++) {
         const size_t u = (size_t)s;
-        std::vector<LeafTerm> rt = {C(ps.t_read[u], g1), C(ps.rc_rt[u], g2)};
-        std::vector<LeafTerm> gmr = {C(ps.iota, g1), C(ps.t_read[u], Fr::neg(g1)), C(ps.rc_gmr[u], g2)};
-        flow_fingerprint(env, rt, ntau, lb, (4 * u) * N, N);
-        flow_fingerprint(env, rt, w, lb, (4 * u + 1) * N, N);
-        flow_fingerprint(env, gmr, ntau, lb, (4 * u + 2) * N, N);
-        flow_fingerprint(env, gmr, w, lb, (4 * u + 3) * N, N);
-        flow_fingerprint(env, {C(ps.iota, g1), C(ps.fc_rt[u], g2)}, ntau, lb, (4 * (size_t)ns + 1 + 2 * u) * N, N);
-        flow_fingerprint(env, {C(ps.iota, g1), C(ps.fc_gmr[u], g2)}, ntau, lb, (4 * (size_t)ns + 2 + 2 * u) * N, N);
+        std::vector<LeafTerm> rt = {mc_col_term(ps.t_read[u], g1), mc_col_term(ps.rc_rt[u], g2)};
+        std::vector<LeafTerm> gmr = {mc_col_term(ps.iota, g1), mc_col_term(ps.t_read[u], Fr::neg(g1)), mc_col_term(ps.rc_gmr[u], g2)};
+        mc_fingerprint_leaves(env, rt, ntau, lb, (4 * u) * N, N);
+        mc_fingerprint_leaves(env, rt, w, lb, (4 * u + 1) * N, N);
+        mc_fingerprint_leaves(env, gmr, ntau, lb, (4 * u + 2) * N, N);
+        mc_fingerprint_leaves(env, gmr, w, lb, (4 * u + 3) * N, N);
+        mc_fingerprint_leaves(env, {mc_col_term(ps.iota, g1), mc_col_term(ps.fc_rt[u], g2)}, ntau, lb, (4 * (size_t)ns + 1 + 2 * u) * N, N);
+        mc_fingerprint_leaves(env, {mc_col_term(ps.iota, g1), mc_col_term(ps.fc_gmr[u], g2)}, ntau, lb, (4 * (size_t)ns + 2 + 2 * u) * N, N);
     }
-    flow_fingerprint(env, {C(ps.iota, g1)}, ntau, lb, (4 * (size_t)ns) * N, N);
+    mc_fingerprint_leaves(env, {mc_col_term(ps.iota, g1)}, ntau, lb, (4 * (size_t)ns) * N, N);
     rc_check(cozk_ctx_synchronize(env.ctx), env.ctx, "synchronize");
-}
-
-// one opening of compact columns of one length at `point`: the claims, one exchange, the joint polynomial over the rho powers
-void compact_open_worker(WorkerEnv& env, Rep3ProverOpeningAccumulator& acc, const std::vector<const cozk_vec*>& cols, const std::vector<fe>& point, bool tamper_claim) {
-    std::vector<uint64_t> rr = to_abi(point);
-    cozk_vec* chi = nullptr;
-    rc_check(cozk_eq_evals(env.ctx, rr.data(), (int)point.size(), &chi), env.ctx, "eq_evals");
-    VecH chih(chi);
-    std::vector<uint64_t> ev(4 * cols.size());
-    rc_check(cozk_compact_batch_evaluate_at_chi(env.ctx, cols.data(), cols.size(), chih.h, ev.data()), env.ctx, "compact_batch_evaluate");
-    std::vector<fe> claims(cols.size());
-    for (size_t i = 0; i < cols.size(); i++) claims[i] = fe_from_u64x4(ev.data() + 4 * i);
-    if (tamper_claim) claims[0] = Fr::add(claims[0], Fr::one());
-    fe batched_claim;
-    std::vector<fe> rho_powers = Rep3ProverOpeningAccumulator::exchange_claims(env, claims, batched_claim);
-    std::vector<uint64_t> cf = to_abi(rho_powers);
-    cozk_vec* jv = nullptr;
-    rc_check(cozk_compact_linear_combination(env.ctx, cols.data(), cf.data(), cols.size(), &jv), env.ctx, "compact_linear_combination");
-    VecH jvh(jv);
-    acc.append_joint(env, plain_poly(env.ctx, jvh), chih.h, point, batched_claim);
 }
 
 // steps 2-5 of the worker under the caller's transcript and accumulator (cozk_ts_proof after its commit, cozk_rw_proof after the memory
@@ -226,14 +200,9 @@ double ts_range_check_worker(WorkerEnv& env, const TsRangeCols& rc, size_t N, bo
     const std::vector<const cozk_vec*> cols = rc.columns();
     // ---- 2, 3. gamma, tau; the leaves
     fe gamma, tau;
-    {
-        Bytes req = star->receive_request();
-        Reader rd(req);
-        gamma = rd.fr();
-        tau = rd.fr();
-    }
+    mc_receive_gamma_tau(star, gamma, tau);
     double t2 = now_ms();
-    LeafBuf lb = flow_leaf_alloc(env, circuits * N);
+    LeafBuf lb = mc_leaf_alloc(env, circuits * N);
     if (leaves_fused) {
         uint64_t g[4], t[4];
         fe_to_u64x4(gamma, g);
@@ -246,7 +215,7 @@ double ts_range_check_worker(WorkerEnv& env, const TsRangeCols& rc, size_t N, bo
     double t3 = now_ms();
     t_leaves = t3 - t2;
     // ---- 4. ONE dense batched grand product; its claimed outputs are the multiset hashes
-    Rep3BatchedDenseGrandProduct gp = Rep3BatchedDenseGrandProduct::construct(env, flow_leaves_to_layer(env, lb), circuits);
+    Rep3BatchedDenseGrandProduct gp = Rep3BatchedDenseGrandProduct::construct(env, mc_leaves_to_layer(env, lb), circuits);
     {
         Writer w;
         w.vec_fr(gp.claimed_outputs(env));
@@ -263,13 +232,7 @@ double ts_range_check_worker(WorkerEnv& env, const TsRangeCols& rc, size_t N, bo
 
 void ts_proof_worker_main(cozk_ts_proof* h, TsProofParty& ps, StarNetWorker* star) {
     const cozk_ts_proof_config& c = h->cfg;
-    WorkerEnv env;
-    env.ctx = ps.ctx;
-    env.mode = COZK_MODE_PLAIN;
-    env.party = 0;
-    env.star = star;
-    env.ring = nullptr;
-    HIP_TRY(hipSetDevice(ps.ctx->device));
+    WorkerEnv env = make_worker_env(ps.ctx, COZK_MODE_PLAIN, 0, star, nullptr);
     const TsRangeCols rc = ts_range_columns(ps, ps.iota);
     const std::vector<const cozk_vec*> cols = rc.columns();
     double t0 = now_ms();
@@ -293,24 +256,9 @@ void ts_proof_worker_main(cozk_ts_proof* h, TsProofParty& ps, StarNetWorker* sta
     ps.record_net(star);
 }
 
-// the commitments a worker sent after its commit, into the proof and the transcript
-void ts_receive_commitments(StarNetCoordinator& net, Transcript& tr, std::vector<PST13Commitment>& out) {
-    Bytes m = net.receive_response(0);
-    Reader rd(m);
-    const uint64_t k = rd.u64();
-    rd.need_elems(k, 72);
-    for (uint64_t i = 0; i < k; i++) {
-        PST13Commitment cm;
-        cm.nv = rd.u64();
-        cm.g_product = rd.g1();
-        out.push_back(cm);
-        tr.append_point(cm.g_product);
-    }
-}
-
 // the coordinator's half of ts_range_check_worker
 void ts_range_check_coordinate(StarNetCoordinator& net, Transcript& tr, size_t log_n, TsRangeProof& proof) {
-    flow_broadcast_gamma_tau(net, tr);
+    mc_broadcast_gamma_tau(net, tr);
     proof.hashes = gather_additive(net);
     tr.append_scalars(proof.hashes);
     fe claim;
@@ -321,16 +269,16 @@ void ts_range_check_coordinate(StarNetCoordinator& net, Transcript& tr, size_t l
 
 void ts_proof_coordinate(cozk_ts_proof* h, StarNetCoordinator& net, TsProof& proof) {
     Transcript tr("cozk-ts-range");
-    ts_receive_commitments(net, tr, proof.commitments);
+    mc_receive_commitments(net, tr, proof.commitments);
     ts_range_check_coordinate(net, tr, (size_t)h->cfg.log_n, proof.range);
     std::vector<fe> r_red;
     fe rho, gamma;
     proof.reduced = Rep3ProverOpeningAccumulator::reduce_and_prove(net, tr, r_red, rho, gamma);
 }
 
-// The verifier's half of the range check after the commitments are in the transcript: the first three checks; `o` receives the
-// opening (point, claims, rho) whose commitment indices the caller fills in.
-bool ts_range_check_verify(Transcript& vt, size_t ns, size_t log_n, const TsRangeProof& proof, std::string& why, VerifierOpening& o) {
+// The verifier's half of the range check after the commitments are in the transcript: the first three checks; `opens` takes the
+// opening of the commitments `polys` (family-major, then t_read).
+bool ts_range_check_verify(Transcript& vt, size_t ns, size_t log_n, const TsRangeProof& proof, const std::vector<size_t>& polys, std::string& why, VerifierOpenings& opens) {
     const size_t circuits = 6 * ns + 1, ncols = 5 * ns;
     if (proof.hashes.size() != circuits || proof.claims.size() != ncols) {
         why = "shape: commitments, hashes or claims";
@@ -346,16 +294,14 @@ bool ts_range_check_verify(Transcript& vt, size_t ns, size_t log_n, const TsRang
                 why = "multiset equality: init * write != read * final (slot " + std::to_string(s) + (kind ? ", global minus read)" : ", read timestamp)");
                 return false;
             }
-    fe claim;
-    std::vector<fe> r;
-    if (!flow_vec_eq(proof.gp.outputs, proof.hashes) || !verify_grand_product(proof.gp, vt, claim, r) || r.size() != (size_t)ceil_log2(circuits) + log_n) {
+    fe claim, unused;
+    std::vector<fe> hi, lo;
+    if (!mc_verify_grand_product(proof.gp, proof.hashes, false, circuits, log_n, vt, claim, unused, hi, lo)) {
         why = "grand product: the hashes are not its outputs, or a round or a layer reduction does not hold";
         return false;
     }
-    const int k = ceil_log2(circuits);
-    std::vector<fe> hi(r.begin(), r.begin() + k), lo(r.begin() + k, r.end());
     const std::vector<fe>& cl = proof.claims;
-    const fe iota = flow_iota_eval(lo), init = Fr::sub(Fr::mul(iota, g1), tau);
+    const fe iota = mc_iota_eval(lo), init = Fr::sub(Fr::mul(iota, g1), tau);
     std::vector<fe> leaves(circuits);
     for (size_t s = 0; s < ns; s++) {
         const fe &rc_rt = cl[s], &rc_gmr = cl[ns + s], &fc_rt = cl[2 * ns + s], &fc_gmr = cl[3 * ns + s], &t_read = cl[4 * ns + s];
@@ -368,13 +314,11 @@ bool ts_range_check_verify(Transcript& vt, size_t ns, size_t log_n, const TsRang
         leaves[4 * ns + 2 + 2 * s] = Fr::add(init, Fr::mul(fc_gmr, g2));
     }
     leaves[4 * ns] = init;
-    if (!Fr::eq(flow_batch_eval(leaves, hi, Fr::zero()), claim)) {
+    if (!Fr::eq(mc_batch_eval(leaves, hi, Fr::zero()), claim)) {
         why = "leaf claim: the fingerprints of the claims != the grand product's final claim";
         return false;
     }
-    o.point = lo;
-    o.claims = cl;
-    o.rho = vt.challenge_scalar();
+    opens.take(polys, lo, cl);
     return true;
 }
 
@@ -387,11 +331,12 @@ bool ts_proof_verify(cozk_ts_proof* h, const TsProof& proof, std::string& why) {
         return false;
     }
     for (auto& cm : proof.commitments) vt.append_point(cm.g_product);
-    VerifierOpening o;
-    if (!ts_range_check_verify(vt, ns, (size_t)h->cfg.log_n, proof.range, why, o)) return false;
-    for (size_t i = 0; i < ncols; i++) o.polys.push_back(i);
+    std::vector<size_t> polys(ncols);
+    for (size_t i = 0; i < ncols; i++) polys[i] = i;
+    VerifierOpenings opens(vt);
+    if (!ts_range_check_verify(vt, ns, (size_t)h->cfg.log_n, proof.range, polys, why, opens)) return false;
     std::string inner;
-    if (!verify_reduced_opening({o}, proof.commitments, vt, proof.reduced, *h->parties[0].setup, "reduction sumcheck: shape", "reduction sumcheck: final check", inner)) {
+    if (!verify_reduced_opening(opens.list, proof.commitments, vt, proof.reduced, *h->parties[0].setup, "reduction sumcheck: shape", "reduction sumcheck: final check", inner)) {
         why = "opening: " + inner;
         return false;
     }
@@ -433,9 +378,7 @@ int cozk_ts_proof_destroy(cozk_ts_proof* h) {
 }
 
 int cozk_ts_proof_prove(cozk_ts_proof* h, int verify, cozk_ts_proof_result* res) {
-    if (!h || !res) return COZK_ERR_INVALID_ARG;
-    memset(res, 0, sizeof *res);
-    res->verified = -1;
+    if (!harness_prove_begin(h, res)) return COZK_ERR_INVALID_ARG;
     if (h->parties.empty() || !h->parties[0].setup) return COZK_ERR_INVALID_ARG;  // create failed
     InProcNets nets(1);
     std::vector<Participant> parts;
@@ -448,17 +391,7 @@ int cozk_ts_proof_prove(cozk_ts_proof* h, int verify, cozk_ts_proof_result* res)
     }, h->error, wall_ms);
     if (rc != COZK_OK) return rc;
     res->wall_ms = wall_ms;  // the verifier below is outside the clock
-    if (verify) {
-        std::string why;
-        try {
-            HIP_TRY(hipSetDevice(h->parties[0].ctx->device));
-            res->verified = ts_proof_verify(h, proof, why) ? 1 : 0;
-        } catch (const std::exception& e) {
-            why = e.what();
-            res->verified = 0;
-        }
-        if (res->verified == 0) h->error = "verification failed: " + why;
-    }
+    if (verify) harness_verify(h, res, h->parties[0].ctx->device, [&](std::string& why) { return ts_proof_verify(h, proof, why); });
     const TsProofParty& ps = h->parties[0];
     res->t_witness_ms = h->t_witness;
     res->t_commit_ms = ps.t_commit;
