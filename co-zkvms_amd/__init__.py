@@ -31,6 +31,9 @@ from . import rw_proof
 from .rw_proof import rw_memory_leaves, rw_memory_init_final_leaves, RW_PROOF_SYMBOLS, RwProof, RwProofConfig, RwProofResult
 from . import memory_proof
 from .memory_proof import OutputCheck, MemoryProof, MemoryProofConfig, MemoryProofResult, MEMORY_PROOF_SYMBOLS
+from . import bytecode
+from .bytecode import (bytecode_witness, bytecode_leaves, bytecode_init_final_leaves, BYTECODE_SYMBOLS, BytecodeProof, BytecodeProofConfig,
+                       BytecodeProofResult)
 from . import shamir_spartan
 from .shamir_spartan import SpartanGroup, ShamirSpartanHarness, ShamirSpartanConfig, ShamirSpartanResult
 from . import shamir_jolt_spartan

@@ -412,6 +412,32 @@ void flow_commit_worker(FlowWorker& w) {
     w.env.star->send_response(wr.b);
 }
 
+// COZK_BYTECODE_FUSED=1 (read on every prove, as COZK_TOGGLE_SPARSE is; unset or 0: the four cozk_fingerprint_leaves launches of
+// flow_bytecode_worker, untouched): the bytecode leaves come from cozk_bytecode_leaves and cozk_bytecode_init_final_leaves over the
+// same compact columns and the V_IMM polynomial, no iota column read.  The leaves, hence the proof bytes, are the same.
+static inline bool flow_bytecode_fused_enabled() {
+    const char* e = getenv("COZK_BYTECODE_FUSED");
+    return e && atoi(e) == 1;
+}
+void flow_bytecode_leaves_fused(FlowWorker& w, const int (&bcv)[5], const fe& gamma, const fe& tau, LeafBuf& rw, LeafBuf& inf) {
+    const FlowIdx& ix = w.h->ix;
+    const int pub[7] = {jolt::V_BYTECODE_A, bcv[0], bcv[1], bcv[2], bcv[3], bcv[4], ix.bc_t_read};
+    for (int idx : pub)
+        if (!w.h->is_public[(size_t)idx]) throw std::runtime_error("COZK_BYTECODE_FUSED: a bytecode read column is not a public compact column");
+    if (w.h->is_public[(size_t)jolt::V_IMM] || !w.h->is_public[(size_t)ix.bc_t_final])
+        throw std::runtime_error("COZK_BYTECODE_FUSED: v_imm is a polynomial and t_final a public compact column");
+    const cozk_vec *v[5], *table[6];
+    for (int k = 0; k < 5; k++) v[k] = w.CV(bcv[k]);
+    for (int k = 0; k < 6; k++) table[k] = w.ps.bc_table[(size_t)k].h;
+    uint64_t gw[4], tw[4];
+    fe_to_u64x4(gamma, gw);
+    fe_to_u64x4(tau, tw);
+    rc_check(cozk_bytecode_leaves(w.env.ctx, w.CV(jolt::V_BYTECODE_A), v, w.CV(ix.bc_t_read), w.P(jolt::V_IMM), gw, tw, w.env.mode, w.env.party, rw.a.h, rw.b.h, 0),
+             w.env.ctx, "bytecode_leaves");
+    rc_check(cozk_bytecode_init_final_leaves(w.env.ctx, table, w.CV(ix.bc_t_final), gw, tw, w.env.mode, w.env.party, inf.a.h, inf.b.h, 0), w.env.ctx,
+             "bytecode_init_final_leaves");
+}
+
 // ---- 2. bytecode (bytecode/worker.rs:43-142): read = a g + v_address g^2 + .. + v_rs2 g^6 + t g^7 + imm - tau, write = read + g^7
 void flow_bytecode_worker(FlowWorker& w) {
     const FlowIdx& ix = w.h->ix;
@@ -426,14 +452,18 @@ void flow_bytecode_worker(FlowWorker& w) {
     read.push_back(w.T(ix.bc_t_read, g[7]));
     read.push_back(w.T(jolt::V_IMM, one));
     LeafBuf rw = mc_leaf_alloc(w.env, 2 * N), inf = mc_leaf_alloc(w.env, 2 * B);
-    mc_fingerprint_leaves(w.env, read, Fr::neg(tau), rw, 0, N);
-    mc_fingerprint_leaves(w.env, read, Fr::sub(g[7], tau), rw, N, N);
-    std::vector<LeafTerm> init = {w.TC(w.ps.iota, g[1])};
-    for (int k = 0; k < 5; k++) init.push_back(w.TC(w.ps.bc_table[(size_t)k], g[(size_t)(2 + k)]));
-    init.push_back(w.TC(w.ps.bc_table[5], one));
-    mc_fingerprint_leaves(w.env, init, Fr::neg(tau), inf, 0, B);
-    init.push_back(w.T(ix.bc_t_final, g[7]));
-    mc_fingerprint_leaves(w.env, init, Fr::neg(tau), inf, B, B);
+    if (flow_bytecode_fused_enabled()) {
+        flow_bytecode_leaves_fused(w, bcv, g[1], tau, rw, inf);
+    } else {
+        mc_fingerprint_leaves(w.env, read, Fr::neg(tau), rw, 0, N);
+        mc_fingerprint_leaves(w.env, read, Fr::sub(g[7], tau), rw, N, N);
+        std::vector<LeafTerm> init = {w.TC(w.ps.iota, g[1])};
+        for (int k = 0; k < 5; k++) init.push_back(w.TC(w.ps.bc_table[(size_t)k], g[(size_t)(2 + k)]));
+        init.push_back(w.TC(w.ps.bc_table[5], one));
+        mc_fingerprint_leaves(w.env, init, Fr::neg(tau), inf, 0, B);
+        init.push_back(w.T(ix.bc_t_final, g[7]));
+        mc_fingerprint_leaves(w.env, init, Fr::neg(tau), inf, B, B);
+    }
     mc_memory_checking(w.env, mc_leaves_to_layer(w.env, rw), 2, ToggleH(), mc_leaves_to_layer(w.env, inf), 2, r_rw, r_if);
     std::vector<cozk_poly*> rwp = {w.P(jolt::V_BYTECODE_A)};
     for (int k = 0; k < 5; k++) rwp.push_back(w.P(bcv[k]));

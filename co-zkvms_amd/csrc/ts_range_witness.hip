@@ -2,6 +2,7 @@
 // witness (cozk_timestamp_range_witness; jolt-core's TimestampRangeCheckPolynomials::generate_witness, whose four families
 // co-jolt/src/jolt/vm/jolt/witness.rs:384-409 shares as public vectors).  jolt-core is not in the reference tree: the recurrence is
 // restated from upstream knowledge (parity unpinned); the field names and the multiset identity of the memory checking pin it.
+// cozk_bytecode_witness is the same counters over one column, the bytecode trace over a table of B rows, plus one gather (k_bc_gather).
 // cozk_timestamp_range_leaves, at the end of this file, turns those families and t_read into the leaves of the range check's
 // grand-product circuits in one launch (k_ts_range_leaves).
 // For one column of keys key[0..n) over a table of M entries:
@@ -153,9 +154,12 @@ __global__ void __launch_bounds__(RP_PT) k_ts_seg_count(const TsCol* __restrict_
 }
 
 // The counters of the columns src[c] (gmr[c]: the key is j - src[c][j]) into NEW vectors at *rc[c] (U32[n]) and *fc[c] (U32[M]); on
-// any failure all of them are null.  ts: the columns are t_read columns, two per slot (see ts_key).
-static int ts_counters(cozk_ctx* ctx, int ts, const std::vector<const cozk_vec*>& src, const std::vector<uint32_t>& gmr, size_t n, size_t M,
+// any failure all of them are null.  who names the caller: it words a violation, and TS_RANGE says that the columns are t_read columns,
+// two per slot (see ts_key).
+enum TsCaller { TS_TIME_COUNTERS, TS_RANGE, TS_BYTECODE };
+static int ts_counters(cozk_ctx* ctx, TsCaller who, const std::vector<const cozk_vec*>& src, const std::vector<uint32_t>& gmr, size_t n, size_t M,
                        const std::vector<cozk_vec**>& rc_out, const std::vector<cozk_vec**>& fc_out) {
+    const int ts = who == TS_RANGE;
     const size_t nc = src.size();
     int rc = COZK_OK;
     for (size_t c = 0; c < nc && rc == COZK_OK; c++) {
@@ -223,6 +227,8 @@ static int ts_counters(cozk_ctx* ctx, int ts, const std::vector<const cozk_vec*>
             char buf[160];
             if (ts)
                 snprintf(buf, sizeof buf, "timestamp_range_witness: step %llu, slot %llu: t_read is greater than the step", bad >> 32, bad & 0xffffffffull);
+            else if (who == TS_BYTECODE)
+                snprintf(buf, sizeof buf, "bytecode_witness: step %llu: a[step] is >= B = %zu", bad & 0xffffffffull, M);
             else
                 snprintf(buf, sizeof buf, "time_counters: column %llu, step %llu: the key is >= M = %zu", bad >> 32, bad & 0xffffffffull, M);
             throw CozkError(COZK_ERR_INVALID_ARG, buf);
@@ -236,6 +242,41 @@ static int ts_counters(cozk_ctx* ctx, int ts, const std::vector<const cozk_vec*>
                 *v = nullptr;
             }
     return rc;
+}
+
+// The gather of cozk_bytecode_witness: a thread per step reads row a[j] of the six table columns (address U32 or U64, bitflags U64, rd,
+// rs1, rs2 U8, imm I64) into v_read[0..4], each in its column's kind, and v_imm[j] = from_i64(imm), the Montgomery word of the signed
+// value (|v| lifted by one product, negated where v < 0).  It runs after the counters have checked every a[j] < B.
+struct BcGather {
+    const void* address;
+    const uint64_t* bitflags;
+    const uint8_t* reg[3];
+    const int64_t* imm;
+    void* v_address;
+    uint64_t* v_bitflags;
+    uint8_t* v_reg[3];
+    fe* v_imm;
+    int address_u64;
+};
+__global__ void __launch_bounds__(RP_PT) k_bc_gather(const uint32_t* __restrict__ a, size_t n, uint32_t B, BcGather g) {
+    const size_t j = (size_t)blockIdx.x * RP_PT + threadIdx.x;
+    if (j >= n) return;
+    uint32_t x = a[j];
+    if (x >= B) x = 0;  // refused by the counters before this launch; no load leaves its buffer
+    if (g.address_u64)
+        ((uint64_t*)g.v_address)[j] = ((const uint64_t*)g.address)[x];
+    else
+        ((uint32_t*)g.v_address)[j] = ((const uint32_t*)g.address)[x];
+    g.v_bitflags[j] = g.bitflags[x];
+#pragma unroll
+    for (int k = 0; k < 3; k++) g.v_reg[k][j] = g.reg[k][x];
+    const int64_t v = g.imm[x];
+    const uint64_t mag = v < 0 ? 0 - (uint64_t)v : (uint64_t)v;
+    fe m = Fr::zero();
+    m.l[0] = (uint32_t)mag;
+    m.l[1] = (uint32_t)(mag >> 32);
+    m = Fr::to_mont(m);
+    fe_store(g.v_imm + j, v < 0 ? Fr::neg(m) : m);
 }
 
 // The leaves of the range check's 6 n_slots + 1 grand-product circuits (cozk_timestamp_range_leaves; the layout is in cozk.h).  A
@@ -337,7 +378,47 @@ int cozk_time_counters(cozk_ctx* ctx, const cozk_vec* const* keys, size_t n_cols
     std::vector<const cozk_vec*> src(keys, keys + n_cols);
     std::vector<cozk_vec**> rc_out(n_cols), fc_out(n_cols);
     for (size_t c = 0; c < n_cols; c++) rc_out[c] = &read_cts[c], fc_out[c] = &final_cts[c];
-    return ts_counters(ctx, 0, src, std::vector<uint32_t>(n_cols, 0), keys[0]->n, M, rc_out, fc_out);
+    return ts_counters(ctx, TS_TIME_COUNTERS, src, std::vector<uint32_t>(n_cols, 0), keys[0]->n, M, rc_out, fc_out);
+}
+
+int cozk_bytecode_witness(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* const* table, cozk_vec** v_read, cozk_vec** v_imm, cozk_vec** t_read,
+                          cozk_vec** t_final) {
+    if (!v_read || !v_imm || !t_read || !t_final) return COZK_ERR_INVALID_ARG;
+    cozk_vec** outs[8] = {&v_read[0], &v_read[1], &v_read[2], &v_read[3], &v_read[4], v_imm, t_read, t_final};
+    for (cozk_vec** o : outs) *o = nullptr;
+    int rc = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && a && table, "bytecode_witness: bad argument");
+        COZK_REQUIRE(a->kind == COZK_SCALAR_U32, "bytecode_witness: a is a U32 vector");
+        COZK_REQUIRE(a->n >= 1 && a->n < ((size_t)1 << 32), "bytecode_witness: 1 <= n < 2^32");
+        for (int k = 0; k < 6; k++) COZK_REQUIRE(table[k], "bytecode_witness: six table columns");
+        COZK_REQUIRE(table[0]->kind == COZK_SCALAR_U32 || table[0]->kind == COZK_SCALAR_U64, "bytecode_witness: table[0] (address) is a U32 or U64 vector");
+        COZK_REQUIRE(table[1]->kind == COZK_SCALAR_U64, "bytecode_witness: table[1] (bitflags) is a U64 vector");
+        for (int k = 2; k < 5; k++) COZK_REQUIRE(table[k]->kind == COZK_SCALAR_U8, "bytecode_witness: table[2..4] (rd, rs1, rs2) are U8 vectors");
+        COZK_REQUIRE(table[5]->kind == COZK_SCALAR_I64, "bytecode_witness: table[5] (imm) is an I64 vector");
+        for (int k = 1; k < 6; k++) COZK_REQUIRE(table[k]->n == table[0]->n, "bytecode_witness: every table column has B entries");
+        COZK_REQUIRE(table[0]->n >= 1 && table[0]->n < ((size_t)1 << 32), "bytecode_witness: 1 <= B < 2^32");
+    });
+    if (rc != COZK_OK) return rc;
+    const size_t n = a->n, B = table[0]->n;
+    rc = ts_counters(ctx, TS_BYTECODE, {a}, {0}, n, B, {t_read}, {t_final});
+    for (int k = 0; k < 5 && rc == COZK_OK; k++) rc = cozk_vec_alloc(ctx, n, table[k]->kind, &v_read[k]);
+    if (rc == COZK_OK) rc = cozk_vec_alloc(ctx, n, COZK_SCALAR_FR, v_imm);
+    if (rc == COZK_OK) rc = cozk_guard(ctx, [&] {
+        BcGather g{};
+        g.address = table[0]->d, g.bitflags = (const uint64_t*)table[1]->d, g.imm = (const int64_t*)table[5]->d;
+        g.v_address = v_read[0]->d, g.v_bitflags = (uint64_t*)v_read[1]->d, g.v_imm = (fe*)(*v_imm)->d;
+        for (int k = 0; k < 3; k++) g.reg[k] = (const uint8_t*)table[2 + k]->d, g.v_reg[k] = (uint8_t*)v_read[2 + k]->d;
+        g.address_u64 = table[0]->kind == COZK_SCALAR_U64;
+        k_bc_gather<<<(unsigned)((n + RP_PT - 1) / RP_PT), RP_PT, 0, ctx->stream>>>((const uint32_t*)a->d, n, (uint32_t)B, g);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    });
+    if (rc != COZK_OK)
+        for (cozk_vec** o : outs) {
+            cozk_vec_free(*o);
+            *o = nullptr;
+        }
+    return rc;
 }
 
 int cozk_timestamp_range_witness(cozk_ctx* ctx, const cozk_vec* const* t_read, size_t n_slots, size_t M, cozk_vec** read_cts_read_timestamp,
@@ -366,7 +447,7 @@ int cozk_timestamp_range_witness(cozk_ctx* ctx, const cozk_vec* const* t_read, s
         rc_out[2 * s] = &read_cts_read_timestamp[s], rc_out[2 * s + 1] = &read_cts_global_minus_read[s];
         fc_out[2 * s] = &final_cts_read_timestamp[s], fc_out[2 * s + 1] = &final_cts_global_minus_read[s];
     }
-    return ts_counters(ctx, 1, src, gmr, t_read[0]->n, M, rc_out, fc_out);
+    return ts_counters(ctx, TS_RANGE, src, gmr, t_read[0]->n, M, rc_out, fc_out);
 }
 
 }  // extern "C"

@@ -1868,6 +1868,89 @@ int cozk_rw_memory_leaves(cozk_ctx* ctx, const cozk_vec* const* addr, const cozk
 int cozk_rw_memory_init_final_leaves(cozk_ctx* ctx, const cozk_vec* v_init, const cozk_vec* v_final, const cozk_vec* t_final,
                                      const uint64_t gamma[4], const uint64_t tau[4], cozk_vec* out, size_t offset);
 
+/* ---- The bytecode memory check's device calls (Rep3BytecodeProver, co-jolt/src/jolt/vm/bytecode/worker.rs:43-142): a consistent
+ * witness over the six public table columns (preprocessing.v_init_final: address, bitflags, rd, rs1, rs2, imm), and the leaves of its
+ * four grand-product circuits from seven compact public columns plus the one shared field column v_imm.
+ *
+ * cozk_bytecode_witness: a is a U32 vector of 1 <= n < 2^32 entries, the table row each step reads; table[0..5] are the columns of
+ * 1 <= B < 2^32 rows: address U32 or U64, bitflags U64, rd / rs1 / rs2 U8, imm I64.  Outputs, all NEW vectors:
+ *   v_read[k][j] = table[k][a[j]], k = 0..4, in the table column's own kind (n entries)
+ *   v_imm[j]     = F::from_i64(table[5][a[j]]) as an FR vector: the canonical Montgomery word; a negative value v is r - |v|
+ *   t_read[j]    = #{ j' < j : a[j'] == a[j] }    U32[n]
+ *   t_final[i]   = #{ j : a[j] == i }             U32[B]
+ * The counters are the launches of cozk_time_counters (one column, M = B: its transient memory); the gather is one kernel over the six
+ * columns.  a[j] >= B: COZK_ERR_INVALID_ARG, cozk_last_error names the smallest such step; nothing is read out of bounds.  A wrong
+ * kind or table columns of unequal length are refused with texts of their own before any launch.  On any failure every output
+ * pointer is NULL and the context works on.  Bit-for-bit deterministic; returns after the device has finished.
+ *
+ * With g^k the powers of gamma, the convention of the chained flow's phase 2 and of the reference:
+ *   read = a g + v[0] g^2 + v[1] g^3 + v[2] g^4 + v[3] g^5 + v[4] g^6 + t g^7 + imm - tau,   write = read + g^7
+ * cozk_bytecode_leaves: ONE launch makes circuit 0 (read) at out[offset + j] and circuit 1 (write) at out[offset + n + j].  a, v[0..4]
+ * and t_read are U8 / U16 / U32 / U64 vectors, mixed freely, of one length 1 <= n < 2^32; imm is a polynomial of at least n entries,
+ * PLAIN or REP3 (REP3 only with mode == COZK_MODE_REP3).  With COZK_MODE_REP3 the public part enters through add_public exactly as in
+ * cozk_fingerprint_leaves: party 0's a, party 1's b, and party 2 carries the imm share alone; out_b is required for REP3 and NULL for
+ * PLAIN.
+ * cozk_bytecode_init_final_leaves: out[offset + i] = i g + table[0][i] g^2 + .. + table[4][i] g^6 + from_i64(table[5][i]) - tau and
+ * out[offset + B + i] the same plus t_final[i] g^7, in ONE launch.  The row number i exists only in registers: no iota column is
+ * stored.  table[0..4] and t_final: U8 / U16 / U32 / U64; table[5]: those or I64; one length 1 <= B < 2^32.  In REP3 the leaves are
+ * the trivial shares cozk_fingerprint_leaves gives for a columns-only call.
+ * Both: out_a (and out_b) are FR vectors with room for 2 n (2 B) entries from offset, which cozk_layer_create adopts; gamma, tau:
+ * 4 x u64 (Montgomery); asynchronous on the context's stream; every refusal comes before any launch with a text of its own.  Every
+ * leaf is bit for bit what the composition of cozk_fingerprint_leaves calls gives in the same mode for the same party.
+ * A leaf's public part is the exact 11-limb integer sum of its 64 x 256-bit products (Montgomery-form coefficients, plain-integer
+ * entries), below 2^68 r, reduced once by a 69-bit Barrett quotient (csrc/bytecode_leaves.hip has the bounds). */
+int cozk_bytecode_witness(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* const* table, cozk_vec** v_read, cozk_vec** v_imm,
+                          cozk_vec** t_read, cozk_vec** t_final);
+int cozk_bytecode_leaves(cozk_ctx* ctx, const cozk_vec* a, const cozk_vec* const* v, const cozk_vec* t_read, const cozk_poly* imm,
+                         const uint64_t gamma[4], const uint64_t tau[4], int mode, int party_id, cozk_vec* out_a, cozk_vec* out_b,
+                         size_t offset);
+int cozk_bytecode_init_final_leaves(cozk_ctx* ctx, const cozk_vec* const* table, const cozk_vec* t_final, const uint64_t gamma[4],
+                                    const uint64_t tau[4], int mode, int party_id, cozk_vec* out_a, cozk_vec* out_b, size_t offset);
+
+/* ---- The bytecode proof itself, as an in-process harness (csrc/host/bytecode_proof.hpp, on the pattern of cozk_rw_proof and built
+ * from memcheck_steps.hpp): party 0's public proof of init * writes == reads * final over the consistent witness of
+ * cozk_bytecode_witness.  PLAIN only.  The transcript label is "cozk-bytecode".  jolt-core is not in the reference tree: the transcript
+ * order and the proof bytes are this project's (parity unpinned); what pins them is the plain verifier below and tests/bytecode_ref.py.
+ * create: the instance of tests/bytecode_ref.py bytecode_instance(seed, N = 2^log_n, B = 2^log_b) restated on the host (row 0 the no-op
+ * row; address 0x80000000 + 4 i as U64; a seeded 64-bit bitflags word, the top bit set in every third row; rd, rs1, rs2 below 32; a
+ * seeded I64 imm, -2^63 and 2^63 - 1 in rows 1 and 2 where B > 2; the trace starts at row 1 % B, jumps with probability 1/8 to a seeded
+ * row in [1, B), else steps on and wraps to 1; the last N / 8 steps are padding at row 0), then cozk_bytecode_witness on the device.
+ * The SRS has max(log_n, log_b) variables.
+ * prove: (1) PST13::batch_commit of a, v_address, v_bitflags, v_rd, v_rs1, v_rs2, t_read, v_imm (FR), t_final in that order (mixed
+ * lengths and kinds; the table is public preprocessing and is not committed), the commitments into the transcript; (2) gamma, tau,
+ * the leaves by the two calls above (leaves_fused = 0: the four cozk_fingerprint_leaves launches with an iota column: the same bytes);
+ * (3) the two grand products, batch 2 and 2, giving r_rw and r_if; (4) at r_rw eight claims in the commit order -- the seven compact
+ * columns by cozk_compact_batch_evaluate_at_chi, v_imm by the Fr evaluation on the same eq table -- ONE claim exchange, the joint
+ * polynomial cozk_compact_linear_combination over rho^0..rho^6 plus rho^7 v_imm appended as ONE opening; at r_if t_final opened alone;
+ * (5) ONE reduce_and_prove.  Proof bytes: the commitments, the MemCheckProof, the reduced opening.
+ * The plain verifier replays the transcript; each check has its own reason (cozk_bytecode_proof_error after a rejected prove):
+ * "multiset equality" (hash[init] * hash[write] == hash[read] * hash[final]), "grand product", "leaf claim" (read and write rebuilt
+ * from the eight claims; init and final from iota(r_if), the six table MLEs at r_if evaluated on the host, and the t_final claim),
+ * "opening".  tamper (tests): 1 adds 1 to v_rd[N / 2] before the commit (only the multiset check can reject); 2 sends claim 0 plus one
+ * (the leaf check rejects); 3 adds 1 to t_final[a[N / 2]] (the multiset check rejects). */
+typedef struct cozk_bytecode_proof cozk_bytecode_proof;
+typedef struct cozk_bytecode_proof_config {
+    int mode;         /* COZK_MODE_PLAIN; anything else is refused */
+    int device;
+    int log_n;        /* trace length N = 2^log_n, 1..22 */
+    int log_b;        /* table of 2^log_b rows, 1..22; either of log_n and log_b may be the larger */
+    uint64_t seed;
+    int precompute;   /* the SRS window table (cozk_bases_upload) */
+    int leaves_fused; /* 1: cozk_bytecode_leaves + cozk_bytecode_init_final_leaves; 0: the composition (kept for the A/B) */
+    int tamper;       /* 0..3: see above */
+} cozk_bytecode_proof_config;
+typedef struct cozk_bytecode_proof_result {
+    int verified; /* 1 ok, 0 rejected, -1 not run */
+    double wall_ms, t_witness_ms, t_commit_ms, t_leaves_ms, t_gp_ms, t_open_ms; /* t_open_ms: the two openings plus reduce_and_prove */
+    uint64_t proof_len;
+    uint8_t proof_digest[32];
+} cozk_bytecode_proof_result;
+int cozk_bytecode_proof_create(const cozk_bytecode_proof_config* cfg, cozk_bytecode_proof** out);
+const char* cozk_bytecode_proof_error(const cozk_bytecode_proof* h);
+int cozk_bytecode_proof_destroy(cozk_bytecode_proof* h);
+int cozk_bytecode_proof_prove(cozk_bytecode_proof* h, int verify, cozk_bytecode_proof_result* res);
+int cozk_bytecode_proof_proof_bytes(const cozk_bytecode_proof* h, uint8_t* out, size_t cap);
+
 /* ---- The read-write memory proof itself, as an in-process harness (csrc/host/rw_memory_proof.hpp, on the pattern of cozk_ts_proof):
  * party 0's public proof of init * writes == reads * final over the consistent witness of cozk_rw_memory_witness, with the timestamp
  * range check chained behind it under the same transcript and the same opening accumulator, as Jolt's ReadWriteMemoryProof has it:
@@ -2020,7 +2103,9 @@ int cozk_memory_proof_proof_bytes(const cozk_memory_proof* h, uint8_t* out, size
  * By default the counters of all three memory-checking instances are seeded streams and the harness verifier skips the
  * multiset-equality check of their hashes.  lookups_witness = 1 makes the instruction lookups a consistent instance (cozk_lasso_witness
  * on the dealer's device, before sharing) and the verifier runs that check for them; the bytecode and the read-write memory keep
- * synthetic counters.  With lookups_witness = 0 the proof bytes are what they were before the field existed. */
+ * synthetic counters.  With lookups_witness = 0 the proof bytes are what they were before the field existed.
+ * COZK_BYTECODE_FUSED=1 in the environment (read on every prove; unset or 0: four cozk_fingerprint_leaves launches) makes the leaves
+ * of the bytecode phase with cozk_bytecode_leaves and cozk_bytecode_init_final_leaves, in PLAIN and REP3; the proof bytes are the same. */
 typedef struct cozk_flow cozk_flow;
 typedef struct cozk_flow_config {
     int mode;

@@ -1,0 +1,378 @@
+"""Plain-Python restatement of the bytecode memory check (co-zkvms_amd/bytecode.py, csrc/bytecode_leaves.hip, the bytecode part of
+csrc/ts_range_witness.hip, csrc/host/bytecode_proof.hpp), shared by tests/test_bytecode_model.py (CPU) and the GPU tests:
+
+  * `bytecode_instance(seed, N, B)`: a table of B rows (row 0 the no-op row, imm extremes in rows 1 and 2) and a trace of N steps that
+    walks it with seeded jumps and ends in N / 8 padding steps at row 0.
+  * `witness`: v_read / v_imm / t_read / t_final by the sequential loop; `multiset_holds` is init * writes == reads * final.
+  * `from_i64`, `read_write_leaves`, `init_final_leaves`: the four grand-product circuits in the layout of cozk_bytecode_leaves and
+    cozk_bytecode_init_final_leaves, from big-int arithmetic:
+        read = a g + v[0] g^2 + .. + v[4] g^6 + t g^7 + imm - tau,   write = read + g^7.
+  * `leaf_word_model`: the word arithmetic of the exact-sum kernels (bc_mac, bc_reduce): the public part of a leaf as an exact 11-limb
+    integer sum of 64 x 256-bit products reduced by a 69-bit Barrett quotient, with the carry and quotient bounds the kernel's comment
+    claims as asserts; `init_final_word_model` the same for a table row.  Expected VALUES in the tests come from big-int arithmetic,
+    never from the model.
+  * `prove` / `verify`: the whole proof of csrc/host/bytecode_proof.hpp -- prover with its coordinator under one transcript, the proof
+    bytes, the plain verifier with the harness's reasons -- from oracle/pyflow.py, oracle/pyharness.py and tests/rw_proof_ref.py's
+    opening.  jolt-core is not in the reference tree: this file and the harness's verifier are what pins the protocol (parity unpinned)."""
+import pyref as O
+
+R = O.R
+MONT = 1 << 256
+M32 = (1 << 32) - 1
+M64 = (1 << 64) - 1
+BC_LIMBS = 11
+BC_MU = (1 << 322) // R  # 69 bits
+I64_MIN, I64_MAX = -(1 << 63), (1 << 63) - 1
+TABLE_NAMES = ("address", "bitflags", "rd", "rs1", "rs2", "imm")
+
+
+def from_i64(v):
+    """F::from_i64: a negative value v is r - |v|"""
+    assert I64_MIN <= v <= I64_MAX
+    return v % R
+
+
+def mont(x):
+    return x % R * MONT % R
+
+
+# ------------------------------------------------------------------------------------------------ the instance and its witness
+def bytecode_instance(seed, N, B):
+    """(a, table): a[j] the row step j reads, table = six columns of B rows (address, bitflags, rd, rs1, rs2, imm; imm signed)"""
+    sm = O.SplitMix64(seed)
+    table = [[0] * B for _ in range(6)]
+    for i in range(1, B):
+        table[0][i] = 0x80000000 + 4 * i
+        table[1][i] = sm.next()
+        if i % 3 == 0:
+            table[1][i] |= 1 << 63
+        w = sm.next()
+        table[2][i], table[3][i], table[4][i] = w & 31, (w >> 5) & 31, (w >> 10) & 31
+        x = sm.next()
+        table[5][i] = x - (1 << 64) if x >> 63 else x
+    if B > 2:
+        table[5][1], table[5][2] = I64_MIN, I64_MAX
+    pad = N // 8
+    a, pc = [], 1 % B
+    for _ in range(N - pad):
+        a.append(pc)
+        w = sm.next()
+        if B > 1 and w & 7 == 0:
+            pc = 1 + (w >> 3) % (B - 1)
+        else:
+            pc = pc + 1 if pc + 1 < B else 1 % B
+    return a + [0] * pad, table
+
+
+def witness(a, table):
+    """(v_read[5], v_imm, t_read, t_final): the gathers and the counters, by the sequential loop"""
+    B = len(table[0])
+    t_final, t_read = [0] * B, []
+    for x in a:
+        assert 0 <= x < B
+        t_read.append(t_final[x])
+        t_final[x] += 1
+    return [[table[k][x] for x in a] for k in range(5)], [from_i64(table[5][x]) for x in a], t_read, t_final
+
+
+# ------------------------------------------------------------------------------------------------ the leaves, big-int
+def _powers(g):
+    p = [1]
+    for _ in range(7):
+        p.append(p[-1] * g % R)
+    return p
+
+
+def read_write_leaves(a, v, t_read, imm, g, tau):
+    """a, v[0..4], t_read: integer columns; imm: field elements (canonical) -> [read leaves, write leaves]"""
+    p = _powers(g)
+    read = [(a[j] * p[1] + sum(v[k][j] * p[2 + k] for k in range(5)) + t_read[j] * p[7] + imm[j] - tau) % R for j in range(len(a))]
+    return [read, [(x + p[7]) % R for x in read]]
+
+
+def init_final_leaves(table, t_final, g, tau):
+    """table[0..4] integer columns, table[5] signed (an I64 column, through from_i64) or unsigned below 2^64 -> [init leaves, final
+    leaves]"""
+    p = _powers(g)
+    assert all(I64_MIN <= v <= M64 for v in table[5])
+    init = [(i * p[1] + sum(table[k][i] * p[2 + k] for k in range(5)) + table[5][i] - tau) % R for i in range(len(table[0]))]
+    return [init, [(x + t_final[i] * p[7]) % R for i, x in enumerate(init)]]
+
+
+def multiset_holds(rw_hashes, if_hashes):
+    return if_hashes[0] * rw_hashes[1] % R == rw_hashes[0] * if_hashes[1] % R
+
+
+def product(xs):
+    acc = 1
+    for x in xs:
+        acc = acc * x % R
+    return acc
+
+
+# ------------------------------------------------------------------------------------------------ bytecode_leaves.hip, exact form
+def _limbs32(x, n):
+    return [(x >> (32 * i)) & M32 for i in range(n)]
+
+
+def _value(limbs):
+    return sum(w << (32 * i) for i, w in enumerate(limbs))
+
+
+def _mac(acc, coeff, v, off):
+    """bc_mac<OFF>: acc += coeff * v * 2^(32 off) on 32-bit words, the carry walked to the top limb"""
+    assert 0 <= coeff < MONT and 0 <= v <= M32
+    c, carry = _limbs32(coeff, 8), 0
+    for k in range(8):
+        t = c[k] * v + acc[off + k] + carry
+        assert t < 1 << 64  # (2^32 - 1)^2 + 2 (2^32 - 1) = 2^64 - 1
+        acc[off + k], carry = t & M32, t >> 32
+    for k in range(off + 8, BC_LIMBS):
+        t = acc[k] + carry
+        acc[k], carry = t & M32, t >> 32
+    assert carry == 0  # the sum stays below 2^352
+
+
+def _term(acc, coeff, v, wide=True):
+    """bc_term: the low half of an entry, and the high half where the column has one (a U64 / I64 column)"""
+    assert 0 <= v <= (M64 if wide else M32)
+    _mac(acc, coeff, v & M32, 0)
+    if wide:
+        _mac(acc, coeff, v >> 32, 1)
+
+
+def _mul_words(x, y):
+    """schoolbook product of two little-endian 32-bit word lists with 32 x 32 + 64 multiply-adds"""
+    out = [0] * (len(x) + len(y))
+    for i, xi in enumerate(x):
+        carry = 0
+        for k, yk in enumerate(y):
+            t = xi * yk + out[i + k] + carry
+            assert t < 1 << 64
+            out[i + k], carry = t & M32, t >> 32
+        out[i + len(y)] = carry
+    return out
+
+
+def _reduce(acc):
+    """bc_reduce: S mod r by qh = floor(floor(S / 2^253) MU / 2^69), q - 2 <= qh <= q, then T = S - qh r on 8 limbs and two
+    conditional subtractions"""
+    S = _value(acc)
+    assert S < R << 68 and S < 1 << 322
+    x = [((acc[7] >> 29) | (acc[8] << 3)) & M32, ((acc[8] >> 29) | (acc[9] << 3)) & M32, ((acc[9] >> 29) | (acc[10] << 3)) & M32]
+    assert acc[10] < 4 and _value(x) == S >> 253 and x[2] < 1 << 5 and BC_MU < 1 << 69
+    p = _mul_words(x, _limbs32(BC_MU, 3))
+    assert _value(p) == (S >> 253) * BC_MU and p[5] == 0 and p[4] < 1 << 10  # the product is below 2^138
+    q = [((p[2] >> 5) | (p[3] << 27)) & M32, ((p[3] >> 5) | (p[4] << 27)) & M32, p[4] >> 5]
+    qv = _value(q)
+    assert qv == ((S >> 253) * BC_MU) >> 69 and S // R - 2 <= qv <= S // R and q[2] < 1 << 5
+    m = _limbs32(R, 8)
+    pr = [0] * 8  # qh r mod 2^256: 8 + 7 + 6 multiply-adds
+    for i in range(3):
+        carry = 0
+        for k in range(8 - i):
+            t = m[k] * q[i] + pr[i + k] + carry
+            assert t < 1 << 64
+            pr[i + k], carry = t & M32, t >> 32
+    assert _value(pr) == qv * R % MONT
+    d, borrow = [0] * 8, 0
+    for k in range(8):
+        t = acc[k] - pr[k] - borrow
+        d[k], borrow = t & M32, 1 if t < 0 else 0
+    T = _value(d)
+    assert T == S - qv * R and 0 <= T < 3 * R < MONT
+    for _ in range(2):  # reduce_once twice
+        if T >= R:
+            T -= R
+    assert T < R
+    return T
+
+
+def leaf_word_model(cols, imm_word, g, tau, wide=(True,) * 7):
+    """the 256-bit words k_bc_leaves stores for one step of a PLAIN call: cols = the seven public entries (a, v[0..4], t_read), each
+    below 2^64 (below 2^32 where wide[k] is false: a U8 / U16 / U32 column), imm_word the Montgomery word of the imm entry.  Returns
+    (read word, write word)."""
+    assert len(cols) == 7 and 0 <= imm_word < R
+    p = _powers(g)
+    acc = _limbs32(mont(R - tau), 8) + [0] * (BC_LIMBS - 8)
+    for k in range(7):
+        _term(acc, mont(p[1 + k]), cols[k], wide[k])
+    pub = _reduce(acc)
+    read = (pub + imm_word) % R       # Fr::add of two canonical words
+    return read, (read + mont(p[7])) % R
+
+
+def init_final_word_model(i, row, t_final, g, tau, wide=(True,) * 7, imm_signed=None):
+    """the words k_bc_if_leaves stores for row i < 2^32: row = the six table entries, t_final the seventh; wide as in leaf_word_model;
+    imm_signed (default: row[5] < 0): row[5] is an I64 entry, which enters as |v| times ONE or NEG_ONE and always has a high half"""
+    imm_signed = row[5] < 0 if imm_signed is None else imm_signed
+    p = _powers(g)
+    acc = _limbs32(mont(R - tau), 8) + [0] * (BC_LIMBS - 8)
+    _mac(acc, mont(p[1]), i, 0)  # bc_mac<0>: the row number has no high half
+    for k in range(5):
+        _term(acc, mont(p[2 + k]), row[k], wide[k])
+    _term(acc, mont(1) if row[5] >= 0 else mont(R - 1), abs(row[5]), wide[5] or imm_signed)
+    init = _reduce(list(acc))
+    _term(acc, mont(p[7]), t_final, wide[6])
+    return init, _reduce(acc)
+
+
+# ------------------------------------------------------------------------------------------------ the whole proof
+LABEL = b"cozk-bytecode"
+REASON_MULTISET = "multiset equality"
+REASON_GP = "grand product"
+REASON_LEAF = "leaf claim"
+REASON_OPENING = "opening"
+ORDER = [REASON_MULTISET, REASON_GP, REASON_LEAF, REASON_OPENING]
+
+
+def default_cfg(**kw):
+    cfg = dict(log_n=3, log_b=2, seed=1, tamper=0)
+    cfg.update(kw)
+    return cfg
+
+
+def proof_witness(cfg):
+    """the harness's instance and its witness columns in the commit order, tampers 1 and 3 applied: (a, table, the eight columns at r_rw,
+    t_final)"""
+    N, B = 1 << cfg["log_n"], 1 << cfg["log_b"]
+    a, table = bytecode_instance(cfg["seed"], N, B)
+    v_read, v_imm, t_read, t_final = witness(a, table)
+    if cfg["tamper"] == 1:
+        v_read[2][N // 2] += 1  # v_rd: below 32, no wrap of the U8 word
+    if cfg["tamper"] == 3:
+        t_final[a[N // 2]] += 1
+    return a, table, [a] + v_read + [t_read, v_imm], t_final
+
+
+def prove(cfg):
+    """-> dict(proof_bytes, commitments, rw_hashes, if_hashes, rw_gp, if_gp, rw_claims, if_claims, reduced, reduced_claims, joint_proofs);
+    the steps of csrc/host/bytecode_proof.hpp from oracle/pyflow.py, oracle/pyharness.py and tests/rw_proof_ref.py's opening"""
+    import pyflow as F
+    import pyharness as H
+    import rw_proof_ref as RP
+    cfg = default_cfg(**cfg)
+    nv = max(cfg["log_n"], cfg["log_b"])
+    a, table, rw_cols, t_final = proof_witness(cfg)
+    ck = H._pst_setup(cfg["seed"], nv)
+    tr = O.Transcript(LABEL)
+    committed = rw_cols[:7] + [rw_cols[7], t_final]  # a, v_address .. v_rs2, t_read, v_imm, t_final
+    commitments = [H._commit(ck, c) for c in committed]
+    for c in commitments:
+        tr.append_point(c)
+    out = O.ser_u64(len(committed)) + b"".join(O.ser_u64(RP._bits(len(col))) + O.ser_g1(c) for col, c in zip(committed, commitments))
+    g, tau = tr.challenge_scalar(), tr.challenge_scalar()
+    rwl = [x for c in read_write_leaves(rw_cols[0], rw_cols[1:6], rw_cols[6], rw_cols[7], g, tau) for x in c]
+    ifl = [x for c in init_final_leaves(table, t_final, g, tau) for x in c]
+    rw_layers, rw_hashes = F.dense_gp([rwl], 2, tr)
+    if_layers, if_hashes = F.dense_gp([ifl], 2, tr)
+    tr.append_scalars(rw_hashes)
+    tr.append_scalars(if_hashes)
+    rw_gp, r_rw = O.gp_prove(rw_layers, tr)
+    if_gp, r_if = O.gp_prove(if_layers, tr)
+    openings = []
+    rw_claims, op = RP._open(rw_cols, r_rw[1:], tr, cfg["tamper"] == 2)  # ONE opening: seven compact columns and v_imm over rho^0..rho^7
+    openings.append(op)
+    if_claims, op = RP._open([t_final], r_if[1:], tr)
+    openings.append(op)
+    out += O.ser_vec_fr(rw_hashes) + O.ser_vec_fr(if_hashes) + F.ser_gp(rw_gp) + F.ser_gp(if_gp) + O.ser_vec_fr(rw_claims) + O.ser_vec_fr(if_claims)
+    r_red, red_claims, red = O.opening_reduce([openings], tr)
+    gamma = tr.challenge_scalar()
+    joint, pw = [0] * (1 << nv), 1
+    for op in openings:
+        for i, v in enumerate(op["poly"]):
+            joint[i] = (joint[i] + v * pw) % R
+        pw = pw * gamma % R
+    proofs, _ = O.pst_open(ck, joint, list(reversed(r_red)))
+    out += O.ser_u64(len(red["round_polys"])) + b"".join(O.ser_vec_fr(c) for c in red["round_polys"]) + O.ser_vec_fr(red_claims)
+    out += O.ser_u64(len(proofs)) + b"".join(O.ser_g1(p) for p in proofs)
+    return dict(proof_bytes=out, commitments=commitments, rw_hashes=rw_hashes, if_hashes=if_hashes, rw_gp=rw_gp, if_gp=if_gp, rw_claims=rw_claims,
+                if_claims=if_claims, reduced=red, reduced_claims=red_claims, joint_proofs=proofs)
+
+
+def verify(proof, cfg):
+    """the plain verifier: replays the transcript and runs every check -> (ok, reason of the first that fails or None, {check: bool}); a
+    check after a failed grand product cannot be replayed and counts as failed"""
+    import pyharness as H
+    import rw_proof_ref as RP
+    cfg = default_cfg(**cfg)
+    nv = max(cfg["log_n"], cfg["log_b"])
+    ck = H._pst_setup(cfg["seed"], nv)
+    tr = O.Transcript(LABEL)
+    checks = {k: False for k in ORDER}
+
+    def result():
+        first = next((k for k in ORDER if not checks[k]), None)
+        return first is None, first, checks
+    assert len(proof["commitments"]) == 9 and len(proof["rw_hashes"]) == 2 and len(proof["if_hashes"]) == 2
+    assert len(proof["rw_claims"]) == 8 and len(proof["if_claims"]) == 1
+    for c in proof["commitments"]:
+        tr.append_point(c)
+    g, tau = tr.challenge_scalar(), tr.challenge_scalar()
+    tr.append_scalars(proof["rw_hashes"])
+    tr.append_scalars(proof["if_hashes"])
+    checks[REASON_MULTISET] = multiset_holds(proof["rw_hashes"], proof["if_hashes"])
+    if proof["rw_gp"]["outputs"] != proof["rw_hashes"] or proof["if_gp"]["outputs"] != proof["if_hashes"]:
+        return result()
+    out_rw = O.gp_verify(proof["rw_gp"], 2, tr)
+    out_if = O.gp_verify(proof["if_gp"], 2, tr) if out_rw is not None else None
+    if out_rw is None or out_if is None:
+        return result()
+    checks[REASON_GP] = True
+    (rw_claim, r_rw), (if_claim, r_if) = out_rw, out_if
+    hi, lo, hi2, lo2 = r_rw[:1], r_rw[1:], r_if[:1], r_if[1:]
+    opens = [dict(point=lo, polys=list(range(8)), claims=proof["rw_claims"], rho=tr.challenge_scalar())]
+    opens.append(dict(point=lo2, polys=[8], claims=proof["if_claims"], rho=tr.challenge_scalar()))
+    p, cl = _powers(g), proof["rw_claims"]
+    read = (sum(cl[k] * p[1 + k] for k in range(7)) + cl[7] - tau) % R
+    table = bytecode_instance(cfg["seed"], 1 << cfg["log_n"], 1 << cfg["log_b"])[1]  # public preprocessing
+    eq2 = O.eq_evals(lo2)
+    mle = [sum(e * v for e, v in zip(eq2, col)) % R for col in table]
+    init = (RP._iota(lo2) * p[1] + sum(mle[k] * p[2 + k] for k in range(5)) + mle[5] - tau) % R
+    fin = (init + proof["if_claims"][0] * p[7]) % R
+    checks[REASON_LEAF] = RP._batch_eval([read, (read + p[7]) % R], hi) == rw_claim and RP._batch_eval([init, fin], hi2) == if_claim
+    # the reduced opening: the reduction sumcheck over both openings, then one PST13 check with the trapdoor (as tests/rw_proof_ref.py)
+    pws, batched = [], []
+    for o in opens:
+        pw = [1]
+        for _ in range(1, len(o["claims"])):
+            pw.append(pw[-1] * o["rho"] % R)
+        pws.append(pw)
+        batched.append(sum(x * c for x, c in zip(pw, o["claims"])) % R)
+    rho2 = tr.challenge_scalar()
+    coeffs = [1, rho2]
+    e = sum(c * b * (1 << (nv - len(o["point"]))) for c, b, o in zip(coeffs, batched, opens)) % R
+    rs, ok = [], len(proof["reduced"]["round_polys"]) == nv and len(proof["reduced_claims"]) == len(opens)
+    for comp in proof["reduced"]["round_polys"] if ok else []:
+        poly = [comp[0], (e - 2 * comp[0] - sum(comp[1:])) % R] + list(comp[1:])
+        tr.append_scalars(comp)
+        rj = tr.challenge_scalar()
+        rs.append(rj)
+        e = O.unipoly_eval(poly, rj)
+    if ok:
+        expect = 0
+        for c, o, rc in zip(coeffs, opens, proof["reduced_claims"]):
+            eqv = 1
+            for x, y in zip(o["point"], rs[nv - len(o["point"]):]):
+                eqv = eqv * ((x * y + (1 - x) * (1 - y)) % R) % R
+            expect = (expect + c * eqv * rc) % R
+        ok = expect == e
+    if ok:
+        tr.append_scalars(proof["reduced_claims"])
+        gamma = tr.challenge_scalar()
+        scal, gpw, joint_claim = [0] * 9, 1, 0
+        for o, pw, rc in zip(opens, pws, proof["reduced_claims"]):
+            for idx, x in zip(o["polys"], pw):
+                scal[idx] = (scal[idx] + gpw * x) % R
+            sc = 1
+            for j in range(nv - len(o["point"])):
+                sc = sc * (1 - rs[j]) % R
+            joint_claim = (joint_claim + gpw * sc * rc) % R
+            gpw = gpw * gamma % R
+        joint_c = None
+        for c, sc in zip(proof["commitments"], scal):
+            if sc:
+                joint_c = O.g1_add(joint_c, O.g1_mul(c, sc))
+        ok = O.pst_check_with_trapdoor(ck, joint_c, list(reversed(rs)), joint_claim, proof["joint_proofs"])
+    checks[REASON_OPENING] = ok
+    return result()
