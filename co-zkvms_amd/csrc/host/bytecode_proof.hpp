@@ -160,14 +160,10 @@ void bytecode_proof_worker_main(cozk_bytecode_proof* h, BytecodeProofParty& ps, 
     double t0 = now_ms();
     // ---- 1. commit: a, v_address, v_bitflags, v_rd, v_rs1, v_rs2, t_read, v_imm (FR), t_final
     {
-        std::vector<cozk_vec*> all;
-        for (const cozk_vec* v : rc) all.push_back(const_cast<cozk_vec*>(v));
+        std::vector<const cozk_vec*> all = rc;
         all.push_back(ps.v_imm_view.h);
         all.push_back(ps.t_final.h);
-        Writer w;
-        w.u64(all.size());
-        for (const PST13Commitment& cm : PST13::batch_commit(ps.ctx, *ps.setup, all)) cm.write(w);
-        star->send_response(w.b);
+        mc_commit_worker(env, *ps.setup, all);
     }
     double t1 = now_ms();
     ps.t_commit = t1 - t0;
@@ -236,9 +232,7 @@ void bytecode_proof_coordinate(cozk_bytecode_proof* h, StarNetCoordinator& net, 
     mc_receive_commitments(net, tr, proof.commitments);
     mc_broadcast_gamma_tau(net, tr);
     mc_coordinate_memory_checking(net, tr, proof.mem, (size_t)c.log_n, false, (size_t)c.log_b);
-    std::vector<fe> r_red;
-    fe rho, gamma;
-    proof.reduced = Rep3ProverOpeningAccumulator::reduce_and_prove(net, tr, r_red, rho, gamma);
+    proof.reduced = mc_coordinate_reduce_and_prove(net, tr);
 }
 
 // The plain verifier: it replays the transcript; the first check that fails names itself in `why`.
@@ -287,12 +281,7 @@ bool bytecode_proof_verify(cozk_bytecode_proof* h, const BytecodeProof& proof, s
         why = "leaf claim: the fingerprints of the claims != a grand product's final claim";
         return false;
     }
-    std::string inner;
-    if (!verify_reduced_opening(opens.list, proof.commitments, vt, proof.reduced, *h->parties[0].setup, "reduction sumcheck: shape", "reduction sumcheck: final check", inner)) {
-        why = "opening: " + inner;
-        return false;
-    }
-    return true;
+    return mc_verify_opening(opens, proof.commitments, proof.reduced, *h->parties[0].setup, why);
 }
 
 }  // namespace
@@ -335,18 +324,11 @@ int cozk_bytecode_proof_destroy(cozk_bytecode_proof* h) {
 int cozk_bytecode_proof_prove(cozk_bytecode_proof* h, int verify, cozk_bytecode_proof_result* res) {
     if (!harness_prove_begin(h, res)) return COZK_ERR_INVALID_ARG;
     if (h->parties.empty() || !h->parties[0].setup) return COZK_ERR_INVALID_ARG;  // create failed
-    InProcNets nets(1);
-    std::vector<Participant> parts;
-    add_participants(parts, "party", h->parties, [&](BytecodeProofParty& ps, int) { bytecode_proof_worker_main(h, ps, nets.worker(0)); });
     BytecodeProof proof;
-    double wall_ms = 0;
-    int rc = run_in_process(nets, parts, [&] {
-        InProcStarCoordinator coord(&nets.star);
-        bytecode_proof_coordinate(h, coord, proof);
-    }, h->error, wall_ms);
+    int rc = prove_by_one_party(
+        h, h->parties, verify, res, [&](BytecodeProofParty& ps, StarNetWorker* star) { bytecode_proof_worker_main(h, ps, star); },
+        [&](StarNetCoordinator& net) { bytecode_proof_coordinate(h, net, proof); }, [&](std::string& why) { return bytecode_proof_verify(h, proof, why); });
     if (rc != COZK_OK) return rc;
-    res->wall_ms = wall_ms;  // the verifier below is outside the clock
-    if (verify) harness_verify(h, res, h->parties[0].ctx->device, [&](std::string& why) { return bytecode_proof_verify(h, proof, why); });
     const BytecodeProofParty& ps = h->parties[0];
     res->t_witness_ms = h->t_witness;
     res->t_commit_ms = ps.t_commit;

@@ -2,7 +2,7 @@
 // range check (ts_range_proof.hpp), the read-write memory proof (rw_memory_proof.hpp) and the whole ReadWriteMemoryProof
 // (memory_proof.hpp) call them under their own transcripts, and each keeps the reason string it reports a failure under.  Plain
 // functions and small structs, as prover.hpp: a party's env, then the worker's, the coordinator's and the plain verifier's steps.
-// Included by harness.hip after its upload helpers, ahead of every harness.
+// tests/memcheck_ref.py holds the same steps for the plain-Python restatements of the four proofs.  Included by harness.hip after its upload helpers, ahead of every harness.
 #pragma once
 
 namespace {
@@ -48,6 +48,15 @@ inline bool mc_vec_eq(const std::vector<fe>& a, const std::vector<fe>& b) {
 }
 
 // ------------------------------------------------------------------------------------------------ worker
+// the commit of columns of any lengths and kinds, sent as the count and the commitments (mc_receive_commitments takes them)
+void mc_commit_worker(WorkerEnv& env, const PST13Setup& setup, const std::vector<const cozk_vec*>& cols) {
+    std::vector<cozk_vec*> all;
+    for (const cozk_vec* v : cols) all.push_back(const_cast<cozk_vec*>(v));
+    Writer w;
+    w.u64(all.size());
+    for (const PST13Commitment& cm : PST13::batch_commit(env.ctx, setup, all)) cm.write(w);
+    env.star->send_response(w.b);
+}
 void mc_receive_gamma_tau(StarNetWorker* star, fe& gamma, fe& tau) {
     Bytes req = star->receive_request();
     Reader rd(req);
@@ -253,6 +262,13 @@ void coordinate_outputs(StarNetCoordinator& net, Transcript& tr, int log_mem, Su
     claims = Rep3ProverOpeningAccumulator::receive_claims(net, tr);
 }
 
+// the coordinator's ending: ONE reduce_and_prove over every opening the workers accumulated
+ReducedOpeningProof mc_coordinate_reduce_and_prove(StarNetCoordinator& net, Transcript& tr) {
+    std::vector<fe> r_red;
+    fe rho, gamma;
+    return Rep3ProverOpeningAccumulator::reduce_and_prove(net, tr, r_red, rho, gamma);
+}
+
 // ------------------------------------------------------------------------------------------------ plain verifier
 fe mc_mle_host(const std::vector<fe>& vals, const std::vector<fe>& r) {
     std::vector<fe> eq = eq_evals_host(r);
@@ -286,6 +302,15 @@ struct VerifierOpenings {
         return polys.size() == claims.size();
     }
 };
+
+// the verifier's ending: the reduced opening over everything `opens` took, its refusals under "opening: "
+bool mc_verify_opening(const VerifierOpenings& opens, const std::vector<PST13Commitment>& commitments, const ReducedOpeningProof& reduced, const PST13Setup& setup,
+                       std::string& why) {
+    std::string inner;
+    if (verify_reduced_opening(opens.list, commitments, opens.vt, reduced, setup, "reduction sumcheck: shape", "reduction sumcheck: final check", inner)) return true;
+    why = "opening: " + inner;
+    return false;
+}
 
 // One grand product: its outputs are the `batch` hashes, every round and layer reduction holds, and the final point has
 // ceil_log2(batch) circuit variables (hi) over `layers` leaf variables (lo; a toggled product's last layer adds none).

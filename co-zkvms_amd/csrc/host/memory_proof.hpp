@@ -211,18 +211,11 @@ int cozk_memory_proof_destroy(cozk_memory_proof* h) {
 int cozk_memory_proof_prove(cozk_memory_proof* h, int verify, cozk_memory_proof_result* res) {
     if (!harness_prove_begin(h, res)) return COZK_ERR_INVALID_ARG;
     if (h->rw.parties.empty() || !h->rw.parties[0].setup || !h->v_io.h) return COZK_ERR_INVALID_ARG;  // create failed
-    InProcNets nets(1);
-    std::vector<Participant> parts;
-    add_participants(parts, "party", h->rw.parties, [&](RwProofParty& ps, int) { memory_proof_worker_main(h, ps, nets.worker(0)); });
     MemoryProof proof;
-    double wall_ms = 0;
-    int rc = run_in_process(nets, parts, [&] {
-        InProcStarCoordinator coord(&nets.star);
-        memory_proof_coordinate(h, coord, proof);
-    }, h->error, wall_ms);
+    int rc = prove_by_one_party(
+        h, h->rw.parties, verify, res, [&](RwProofParty& ps, StarNetWorker* star) { memory_proof_worker_main(h, ps, star); },
+        [&](StarNetCoordinator& net) { memory_proof_coordinate(h, net, proof); }, [&](std::string& why) { return memory_proof_verify(h, proof, why); });
     if (rc != COZK_OK) return rc;
-    res->wall_ms = wall_ms;  // the verifier below is outside the clock
-    if (verify) harness_verify(h, res, h->rw.parties[0].ctx->device, [&](std::string& why) { return memory_proof_verify(h, proof, why); });
     const RwProofParty& ps = h->rw.parties[0];
     res->t_witness_ms = h->rw.t_witness;
     res->t_commit_ms = ps.t_commit;

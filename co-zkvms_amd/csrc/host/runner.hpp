@@ -203,4 +203,23 @@ inline int run_in_process(InProcNets& nets, std::vector<Participant>& parts, con
     return rc;
 }
 
+// One proof by party 0 alone over a star of one end: worker(party, its end) on a thread of its own, coordinate(net) on the calling
+// thread; then res->wall_ms and, with `verify`, verifier(why) on the party's device, outside the clock.  Returns run_in_process's
+// code, and on a failure leaves res as harness_prove_begin made it.
+template <class P, class R, class W, class C, class V>
+int prove_by_one_party(HarnessHandle* h, std::vector<P>& parties, int verify, R* res, W worker, C coordinate, V verifier) {
+    InProcNets nets(1);
+    std::vector<Participant> parts;
+    add_participants(parts, "party", parties, [&](P& ps, int) { worker(ps, nets.worker(0)); });
+    double wall_ms = 0;
+    int rc = run_in_process(nets, parts, [&] {
+        InProcStarCoordinator coord(&nets.star);
+        coordinate(coord);
+    }, h->error, wall_ms);
+    if (rc != COZK_OK) return rc;
+    res->wall_ms = wall_ms;
+    if (verify) harness_verify(h, res, parties[0].ctx->device, verifier);
+    return COZK_OK;
+}
+
 }  // namespace cozk

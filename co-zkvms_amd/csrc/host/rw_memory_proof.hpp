@@ -165,16 +165,11 @@ double rw_proof_memory_check_worker(cozk_rw_proof* h, RwProofParty& ps, WorkerEn
     double t0 = now_ms();
     // ---- 1. commit: mixed lengths and compact kinds
     {
-        std::vector<cozk_vec*> all;
-        for (const cozk_vec* v : rw_cols) all.push_back(const_cast<cozk_vec*>(v));
-        for (const cozk_vec* v : if_cols) all.push_back(const_cast<cozk_vec*>(v));
+        std::vector<const cozk_vec*> all = rw_cols;
+        all.insert(all.end(), if_cols.begin(), if_cols.end());
         if (c.with_ts)
-            for (const std::vector<const cozk_vec*>* fam : {&range.rc_rt, &range.rc_gmr, &range.fc_rt, &range.fc_gmr})
-                for (const cozk_vec* v : *fam) all.push_back(const_cast<cozk_vec*>(v));
-        Writer w;
-        w.u64(all.size());
-        for (const PST13Commitment& cm : PST13::batch_commit(ps.ctx, *ps.setup, all)) cm.write(w);
-        star->send_response(w.b);
+            for (const std::vector<const cozk_vec*>* fam : {&range.rc_rt, &range.rc_gmr, &range.fc_rt, &range.fc_gmr}) all.insert(all.end(), fam->begin(), fam->end());
+        mc_commit_worker(env, *ps.setup, all);
     }
     double t1 = now_ms();
     ps.t_commit = t1 - t0;
@@ -244,9 +239,7 @@ void rw_proof_coordinate_memory_check(const cozk_rw_proof_config& c, StarNetCoor
 void rw_proof_coordinate_range_check_and_open(const cozk_rw_proof_config& c, StarNetCoordinator& net, Transcript& tr, bool& with_ts, TsRangeProof& range, ReducedOpeningProof& reduced) {
     with_ts = c.with_ts != 0;
     if (c.with_ts) ts_range_check_coordinate(net, tr, (size_t)c.log_n, range);
-    std::vector<fe> r_red;
-    fe rho, gamma;
-    reduced = Rep3ProverOpeningAccumulator::reduce_and_prove(net, tr, r_red, rho, gamma);
+    reduced = mc_coordinate_reduce_and_prove(net, tr);
 }
 
 void rw_proof_coordinate(cozk_rw_proof* h, StarNetCoordinator& net, RwProof& proof) {
@@ -315,12 +308,7 @@ bool rw_proof_verify_range_check_and_open(cozk_rw_proof* h, const std::vector<PS
             return false;
         }
     }
-    std::string inner;
-    if (!verify_reduced_opening(opens.list, commitments, vt, reduced, *h->parties[0].setup, "reduction sumcheck: shape", "reduction sumcheck: final check", inner)) {
-        why = "opening: " + inner;
-        return false;
-    }
-    return true;
+    return mc_verify_opening(opens, commitments, reduced, *h->parties[0].setup, why);
 }
 bool rw_proof_verify(cozk_rw_proof* h, const RwProof& proof, std::string& why) {
     Transcript vt("cozk-rw-memory");
@@ -380,18 +368,11 @@ int cozk_rw_proof_destroy(cozk_rw_proof* h) {
 int cozk_rw_proof_prove(cozk_rw_proof* h, int verify, cozk_rw_proof_result* res) {
     if (!harness_prove_begin(h, res)) return COZK_ERR_INVALID_ARG;
     if (h->parties.empty() || !h->parties[0].setup) return COZK_ERR_INVALID_ARG;  // create failed
-    InProcNets nets(1);
-    std::vector<Participant> parts;
-    add_participants(parts, "party", h->parties, [&](RwProofParty& ps, int) { rw_proof_worker_main(h, ps, nets.worker(0)); });
     RwProof proof;
-    double wall_ms = 0;
-    int rc = run_in_process(nets, parts, [&] {
-        InProcStarCoordinator coord(&nets.star);
-        rw_proof_coordinate(h, coord, proof);
-    }, h->error, wall_ms);
+    int rc = prove_by_one_party(
+        h, h->parties, verify, res, [&](RwProofParty& ps, StarNetWorker* star) { rw_proof_worker_main(h, ps, star); },
+        [&](StarNetCoordinator& net) { rw_proof_coordinate(h, net, proof); }, [&](std::string& why) { return rw_proof_verify(h, proof, why); });
     if (rc != COZK_OK) return rc;
-    res->wall_ms = wall_ms;  // the verifier below is outside the clock
-    if (verify) harness_verify(h, res, h->parties[0].ctx->device, [&](std::string& why) { return rw_proof_verify(h, proof, why); });
     const RwProofParty& ps = h->parties[0];
     res->t_witness_ms = h->t_witness;
     res->t_commit_ms = ps.t_commit;

@@ -236,7 +236,8 @@ void ts_proof_worker_main(cozk_ts_proof* h, TsProofParty& ps, StarNetWorker* sta
     const TsRangeCols rc = ts_range_columns(ps, ps.iota);
     const std::vector<const cozk_vec*> cols = rc.columns();
     double t0 = now_ms();
-    // ---- 1. commit (the U32 small-scalar path)
+    // ---- 1. commit (the U32 small-scalar path).  Not mc_commit_worker: this is cozk_batch_msm_vec, which refuses columns of unequal
+    // length and names itself in a failure, where PST13::batch_commit calls cozk_batch_msm_slices
     {
         std::vector<uint64_t> xy(8 * cols.size());
         std::vector<int> inf(cols.size());
@@ -271,9 +272,7 @@ void ts_proof_coordinate(cozk_ts_proof* h, StarNetCoordinator& net, TsProof& pro
     Transcript tr("cozk-ts-range");
     mc_receive_commitments(net, tr, proof.commitments);
     ts_range_check_coordinate(net, tr, (size_t)h->cfg.log_n, proof.range);
-    std::vector<fe> r_red;
-    fe rho, gamma;
-    proof.reduced = Rep3ProverOpeningAccumulator::reduce_and_prove(net, tr, r_red, rho, gamma);
+    proof.reduced = mc_coordinate_reduce_and_prove(net, tr);
 }
 
 // The verifier's half of the range check after the commitments are in the transcript: the first three checks; `opens` takes the
@@ -334,13 +333,8 @@ bool ts_proof_verify(cozk_ts_proof* h, const TsProof& proof, std::string& why) {
     std::vector<size_t> polys(ncols);
     for (size_t i = 0; i < ncols; i++) polys[i] = i;
     VerifierOpenings opens(vt);
-    if (!ts_range_check_verify(vt, ns, (size_t)h->cfg.log_n, proof.range, polys, why, opens)) return false;
-    std::string inner;
-    if (!verify_reduced_opening(opens.list, proof.commitments, vt, proof.reduced, *h->parties[0].setup, "reduction sumcheck: shape", "reduction sumcheck: final check", inner)) {
-        why = "opening: " + inner;
-        return false;
-    }
-    return true;
+    return ts_range_check_verify(vt, ns, (size_t)h->cfg.log_n, proof.range, polys, why, opens) &&
+           mc_verify_opening(opens, proof.commitments, proof.reduced, *h->parties[0].setup, why);
 }
 
 }  // namespace
@@ -380,18 +374,11 @@ int cozk_ts_proof_destroy(cozk_ts_proof* h) {
 int cozk_ts_proof_prove(cozk_ts_proof* h, int verify, cozk_ts_proof_result* res) {
     if (!harness_prove_begin(h, res)) return COZK_ERR_INVALID_ARG;
     if (h->parties.empty() || !h->parties[0].setup) return COZK_ERR_INVALID_ARG;  // create failed
-    InProcNets nets(1);
-    std::vector<Participant> parts;
-    add_participants(parts, "party", h->parties, [&](TsProofParty& ps, int) { ts_proof_worker_main(h, ps, nets.worker(0)); });
     TsProof proof;
-    double wall_ms = 0;
-    int rc = run_in_process(nets, parts, [&] {
-        InProcStarCoordinator coord(&nets.star);
-        ts_proof_coordinate(h, coord, proof);
-    }, h->error, wall_ms);
+    int rc = prove_by_one_party(
+        h, h->parties, verify, res, [&](TsProofParty& ps, StarNetWorker* star) { ts_proof_worker_main(h, ps, star); },
+        [&](StarNetCoordinator& net) { ts_proof_coordinate(h, net, proof); }, [&](std::string& why) { return ts_proof_verify(h, proof, why); });
     if (rc != COZK_OK) return rc;
-    res->wall_ms = wall_ms;  // the verifier below is outside the clock
-    if (verify) harness_verify(h, res, h->parties[0].ctx->device, [&](std::string& why) { return ts_proof_verify(h, proof, why); });
     const TsProofParty& ps = h->parties[0];
     res->t_witness_ms = h->t_witness;
     res->t_commit_ms = ps.t_commit;

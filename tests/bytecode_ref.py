@@ -12,13 +12,14 @@ csrc/ts_range_witness.hip, csrc/host/bytecode_proof.hpp), shared by tests/test_b
     claims as asserts; `init_final_word_model` the same for a table row.  Expected VALUES in the tests come from big-int arithmetic,
     never from the model.
   * `prove` / `verify`: the whole proof of csrc/host/bytecode_proof.hpp -- prover with its coordinator under one transcript, the proof
-    bytes, the plain verifier with the harness's reasons -- from oracle/pyflow.py, oracle/pyharness.py and tests/rw_proof_ref.py's
-    opening.  jolt-core is not in the reference tree: this file and the harness's verifier are what pins the protocol (parity unpinned)."""
+    bytes, the plain verifier with the harness's reasons -- on the shared steps of tests/memcheck_ref.py; what is this file's own
+    is the leaf check over the six table columns and the order of the eight claims at r_rw.  jolt-core is not in the reference tree:
+    this file and the harness's verifier are what pins the protocol (parity unpinned)."""
+import memcheck_ref as MC
 import pyref as O
 
 R = O.R
-MONT = 1 << 256
-M32 = (1 << 32) - 1
+MONT, M32, mont = MC.MONT, MC.M32, MC.mont
 M64 = (1 << 64) - 1
 BC_LIMBS = 11
 BC_MU = (1 << 322) // R  # 69 bits
@@ -30,10 +31,6 @@ def from_i64(v):
     """F::from_i64: a negative value v is r - |v|"""
     assert I64_MIN <= v <= I64_MAX
     return v % R
-
-
-def mont(x):
-    return x % R * MONT % R
 
 
 # ------------------------------------------------------------------------------------------------ the instance and its witness
@@ -111,10 +108,6 @@ def product(xs):
 
 
 # ------------------------------------------------------------------------------------------------ bytecode_leaves.hip, exact form
-def _limbs32(x, n):
-    return [(x >> (32 * i)) & M32 for i in range(n)]
-
-
 def _value(limbs):
     return sum(w << (32 * i) for i, w in enumerate(limbs))
 
@@ -122,7 +115,7 @@ def _value(limbs):
 def _mac(acc, coeff, v, off):
     """bc_mac<OFF>: acc += coeff * v * 2^(32 off) on 32-bit words, the carry walked to the top limb"""
     assert 0 <= coeff < MONT and 0 <= v <= M32
-    c, carry = _limbs32(coeff, 8), 0
+    c, carry = MC.limbs32(coeff, 8), 0
     for k in range(8):
         t = c[k] * v + acc[off + k] + carry
         assert t < 1 << 64  # (2^32 - 1)^2 + 2 (2^32 - 1) = 2^64 - 1
@@ -161,12 +154,12 @@ def _reduce(acc):
     assert S < R << 68 and S < 1 << 322
     x = [((acc[7] >> 29) | (acc[8] << 3)) & M32, ((acc[8] >> 29) | (acc[9] << 3)) & M32, ((acc[9] >> 29) | (acc[10] << 3)) & M32]
     assert acc[10] < 4 and _value(x) == S >> 253 and x[2] < 1 << 5 and BC_MU < 1 << 69
-    p = _mul_words(x, _limbs32(BC_MU, 3))
+    p = _mul_words(x, MC.limbs32(BC_MU, 3))
     assert _value(p) == (S >> 253) * BC_MU and p[5] == 0 and p[4] < 1 << 10  # the product is below 2^138
     q = [((p[2] >> 5) | (p[3] << 27)) & M32, ((p[3] >> 5) | (p[4] << 27)) & M32, p[4] >> 5]
     qv = _value(q)
     assert qv == ((S >> 253) * BC_MU) >> 69 and S // R - 2 <= qv <= S // R and q[2] < 1 << 5
-    m = _limbs32(R, 8)
+    m = MC.limbs32(R, 8)
     pr = [0] * 8  # qh r mod 2^256: 8 + 7 + 6 multiply-adds
     for i in range(3):
         carry = 0
@@ -194,7 +187,7 @@ def leaf_word_model(cols, imm_word, g, tau, wide=(True,) * 7):
     (read word, write word)."""
     assert len(cols) == 7 and 0 <= imm_word < R
     p = _powers(g)
-    acc = _limbs32(mont(R - tau), 8) + [0] * (BC_LIMBS - 8)
+    acc = MC.limbs32(mont(R - tau), 8) + [0] * (BC_LIMBS - 8)
     for k in range(7):
         _term(acc, mont(p[1 + k]), cols[k], wide[k])
     pub = _reduce(acc)
@@ -207,7 +200,7 @@ def init_final_word_model(i, row, t_final, g, tau, wide=(True,) * 7, imm_signed=
     imm_signed (default: row[5] < 0): row[5] is an I64 entry, which enters as |v| times ONE or NEG_ONE and always has a high half"""
     imm_signed = row[5] < 0 if imm_signed is None else imm_signed
     p = _powers(g)
-    acc = _limbs32(mont(R - tau), 8) + [0] * (BC_LIMBS - 8)
+    acc = MC.limbs32(mont(R - tau), 8) + [0] * (BC_LIMBS - 8)
     _mac(acc, mont(p[1]), i, 0)  # bc_mac<0>: the row number has no high half
     for k in range(5):
         _term(acc, mont(p[2 + k]), row[k], wide[k])
@@ -219,10 +212,7 @@ def init_final_word_model(i, row, t_final, g, tau, wide=(True,) * 7, imm_signed=
 
 # ------------------------------------------------------------------------------------------------ the whole proof
 LABEL = b"cozk-bytecode"
-REASON_MULTISET = "multiset equality"
-REASON_GP = "grand product"
-REASON_LEAF = "leaf claim"
-REASON_OPENING = "opening"
+REASON_MULTISET, REASON_GP, REASON_LEAF, REASON_OPENING = MC.REASON_MULTISET, MC.REASON_GP, MC.REASON_LEAF, MC.REASON_OPENING
 ORDER = [REASON_MULTISET, REASON_GP, REASON_LEAF, REASON_OPENING]
 
 
@@ -247,132 +237,53 @@ def proof_witness(cfg):
 
 def prove(cfg):
     """-> dict(proof_bytes, commitments, rw_hashes, if_hashes, rw_gp, if_gp, rw_claims, if_claims, reduced, reduced_claims, joint_proofs);
-    the steps of csrc/host/bytecode_proof.hpp from oracle/pyflow.py, oracle/pyharness.py and tests/rw_proof_ref.py's opening"""
-    import pyflow as F
+    the steps of csrc/host/bytecode_proof.hpp as tests/memcheck_ref.py has them"""
     import pyharness as H
-    import rw_proof_ref as RP
     cfg = default_cfg(**cfg)
     nv = max(cfg["log_n"], cfg["log_b"])
     a, table, rw_cols, t_final = proof_witness(cfg)
     ck = H._pst_setup(cfg["seed"], nv)
     tr = O.Transcript(LABEL)
-    committed = rw_cols[:7] + [rw_cols[7], t_final]  # a, v_address .. v_rs2, t_read, v_imm, t_final
-    commitments = [H._commit(ck, c) for c in committed]
-    for c in commitments:
-        tr.append_point(c)
-    out = O.ser_u64(len(committed)) + b"".join(O.ser_u64(RP._bits(len(col))) + O.ser_g1(c) for col, c in zip(committed, commitments))
+    commitments, out = MC.commit_columns(ck, rw_cols + [t_final], tr)  # a, v_address .. v_rs2, t_read, v_imm, t_final
     g, tau = tr.challenge_scalar(), tr.challenge_scalar()
     rwl = [x for c in read_write_leaves(rw_cols[0], rw_cols[1:6], rw_cols[6], rw_cols[7], g, tau) for x in c]
     ifl = [x for c in init_final_leaves(table, t_final, g, tau) for x in c]
-    rw_layers, rw_hashes = F.dense_gp([rwl], 2, tr)
-    if_layers, if_hashes = F.dense_gp([ifl], 2, tr)
-    tr.append_scalars(rw_hashes)
-    tr.append_scalars(if_hashes)
-    rw_gp, r_rw = O.gp_prove(rw_layers, tr)
-    if_gp, r_if = O.gp_prove(if_layers, tr)
-    openings = []
-    rw_claims, op = RP._open(rw_cols, r_rw[1:], tr, cfg["tamper"] == 2)  # ONE opening: seven compact columns and v_imm over rho^0..rho^7
-    openings.append(op)
-    if_claims, op = RP._open([t_final], r_if[1:], tr)
-    openings.append(op)
-    out += O.ser_vec_fr(rw_hashes) + O.ser_vec_fr(if_hashes) + F.ser_gp(rw_gp) + F.ser_gp(if_gp) + O.ser_vec_fr(rw_claims) + O.ser_vec_fr(if_claims)
-    r_red, red_claims, red = O.opening_reduce([openings], tr)
-    gamma = tr.challenge_scalar()
-    joint, pw = [0] * (1 << nv), 1
-    for op in openings:
-        for i, v in enumerate(op["poly"]):
-            joint[i] = (joint[i] + v * pw) % R
-        pw = pw * gamma % R
-    proofs, _ = O.pst_open(ck, joint, list(reversed(r_red)))
-    out += O.ser_u64(len(red["round_polys"])) + b"".join(O.ser_vec_fr(c) for c in red["round_polys"]) + O.ser_vec_fr(red_claims)
-    out += O.ser_u64(len(proofs)) + b"".join(O.ser_g1(p) for p in proofs)
-    return dict(proof_bytes=out, commitments=commitments, rw_hashes=rw_hashes, if_hashes=if_hashes, rw_gp=rw_gp, if_gp=if_gp, rw_claims=rw_claims,
-                if_claims=if_claims, reduced=red, reduced_claims=red_claims, joint_proofs=proofs)
+    res, r_rw, r_if, part = MC.memory_checking(rwl, 2, ifl, 2, tr)
+    rw_claims, op_rw = MC.open_columns(rw_cols, r_rw, tr, cfg["tamper"] == 2)  # ONE opening: seven compact columns and v_imm over rho^0..rho^7
+    if_claims, op_if = MC.open_columns([t_final], r_if, tr)
+    ending, last = MC.reduce_and_prove(ck, [op_rw, op_if], nv, tr)
+    res.update(ending, proof_bytes=out + part + O.ser_vec_fr(rw_claims) + O.ser_vec_fr(if_claims) + last, commitments=commitments, rw_claims=rw_claims,
+               if_claims=if_claims)
+    return res
 
 
 def verify(proof, cfg):
     """the plain verifier: replays the transcript and runs every check -> (ok, reason of the first that fails or None, {check: bool}); a
     check after a failed grand product cannot be replayed and counts as failed"""
     import pyharness as H
-    import rw_proof_ref as RP
     cfg = default_cfg(**cfg)
     nv = max(cfg["log_n"], cfg["log_b"])
-    ck = H._pst_setup(cfg["seed"], nv)
     tr = O.Transcript(LABEL)
-    checks = {k: False for k in ORDER}
-
-    def result():
-        first = next((k for k in ORDER if not checks[k]), None)
-        return first is None, first, checks
+    checks = MC.Checks(ORDER)
     assert len(proof["commitments"]) == 9 and len(proof["rw_hashes"]) == 2 and len(proof["if_hashes"]) == 2
     assert len(proof["rw_claims"]) == 8 and len(proof["if_claims"]) == 1
     for c in proof["commitments"]:
         tr.append_point(c)
     g, tau = tr.challenge_scalar(), tr.challenge_scalar()
-    tr.append_scalars(proof["rw_hashes"])
-    tr.append_scalars(proof["if_hashes"])
     checks[REASON_MULTISET] = multiset_holds(proof["rw_hashes"], proof["if_hashes"])
-    if proof["rw_gp"]["outputs"] != proof["rw_hashes"] or proof["if_gp"]["outputs"] != proof["if_hashes"]:
-        return result()
-    out_rw = O.gp_verify(proof["rw_gp"], 2, tr)
-    out_if = O.gp_verify(proof["if_gp"], 2, tr) if out_rw is not None else None
-    if out_rw is None or out_if is None:
-        return result()
+    pts = MC.verify_grand_products(proof, 2, 2, tr)
+    if pts is None:
+        return checks.result()
     checks[REASON_GP] = True
-    (rw_claim, r_rw), (if_claim, r_if) = out_rw, out_if
-    hi, lo, hi2, lo2 = r_rw[:1], r_rw[1:], r_if[:1], r_if[1:]
-    opens = [dict(point=lo, polys=list(range(8)), claims=proof["rw_claims"], rho=tr.challenge_scalar())]
-    opens.append(dict(point=lo2, polys=[8], claims=proof["if_claims"], rho=tr.challenge_scalar()))
-    p, cl = _powers(g), proof["rw_claims"]
+    (rw_claim, hi, lo), (if_claim, hi2, lo2) = pts
+    opens = [MC.take_opening(list(range(8)), lo, proof["rw_claims"], tr), MC.take_opening([8], lo2, proof["if_claims"], tr)]
+    p, cl = _powers(g), proof["rw_claims"]  # the claims in the commit order: a, v_address .. v_rs2, t_read, v_imm
     read = (sum(cl[k] * p[1 + k] for k in range(7)) + cl[7] - tau) % R
     table = bytecode_instance(cfg["seed"], 1 << cfg["log_n"], 1 << cfg["log_b"])[1]  # public preprocessing
     eq2 = O.eq_evals(lo2)
     mle = [sum(e * v for e, v in zip(eq2, col)) % R for col in table]
-    init = (RP._iota(lo2) * p[1] + sum(mle[k] * p[2 + k] for k in range(5)) + mle[5] - tau) % R
+    init = (MC.iota_eval(lo2) * p[1] + sum(mle[k] * p[2 + k] for k in range(5)) + mle[5] - tau) % R
     fin = (init + proof["if_claims"][0] * p[7]) % R
-    checks[REASON_LEAF] = RP._batch_eval([read, (read + p[7]) % R], hi) == rw_claim and RP._batch_eval([init, fin], hi2) == if_claim
-    # the reduced opening: the reduction sumcheck over both openings, then one PST13 check with the trapdoor (as tests/rw_proof_ref.py)
-    pws, batched = [], []
-    for o in opens:
-        pw = [1]
-        for _ in range(1, len(o["claims"])):
-            pw.append(pw[-1] * o["rho"] % R)
-        pws.append(pw)
-        batched.append(sum(x * c for x, c in zip(pw, o["claims"])) % R)
-    rho2 = tr.challenge_scalar()
-    coeffs = [1, rho2]
-    e = sum(c * b * (1 << (nv - len(o["point"]))) for c, b, o in zip(coeffs, batched, opens)) % R
-    rs, ok = [], len(proof["reduced"]["round_polys"]) == nv and len(proof["reduced_claims"]) == len(opens)
-    for comp in proof["reduced"]["round_polys"] if ok else []:
-        poly = [comp[0], (e - 2 * comp[0] - sum(comp[1:])) % R] + list(comp[1:])
-        tr.append_scalars(comp)
-        rj = tr.challenge_scalar()
-        rs.append(rj)
-        e = O.unipoly_eval(poly, rj)
-    if ok:
-        expect = 0
-        for c, o, rc in zip(coeffs, opens, proof["reduced_claims"]):
-            eqv = 1
-            for x, y in zip(o["point"], rs[nv - len(o["point"]):]):
-                eqv = eqv * ((x * y + (1 - x) * (1 - y)) % R) % R
-            expect = (expect + c * eqv * rc) % R
-        ok = expect == e
-    if ok:
-        tr.append_scalars(proof["reduced_claims"])
-        gamma = tr.challenge_scalar()
-        scal, gpw, joint_claim = [0] * 9, 1, 0
-        for o, pw, rc in zip(opens, pws, proof["reduced_claims"]):
-            for idx, x in zip(o["polys"], pw):
-                scal[idx] = (scal[idx] + gpw * x) % R
-            sc = 1
-            for j in range(nv - len(o["point"])):
-                sc = sc * (1 - rs[j]) % R
-            joint_claim = (joint_claim + gpw * sc * rc) % R
-            gpw = gpw * gamma % R
-        joint_c = None
-        for c, sc in zip(proof["commitments"], scal):
-            if sc:
-                joint_c = O.g1_add(joint_c, O.g1_mul(c, sc))
-        ok = O.pst_check_with_trapdoor(ck, joint_c, list(reversed(rs)), joint_claim, proof["joint_proofs"])
-    checks[REASON_OPENING] = ok
-    return result()
+    checks[REASON_LEAF] = MC.batch_eval([read, (read + p[7]) % R], hi) == rw_claim and MC.batch_eval([init, fin], hi2) == if_claim
+    checks[REASON_OPENING] = MC.reduced_opening_holds(proof, opens, nv, H._pst_setup(cfg["seed"], nv), tr)
+    return checks.result()

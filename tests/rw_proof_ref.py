@@ -8,24 +8,24 @@ csrc/rw_memory_leaves.hip), shared by tests/test_rw_proof_model.py (CPU) and the
     32 x 256-bit products reduced by a short Barrett quotient, with the carry and quotient bounds the kernel's comment claims as
     asserts.  Expected VALUES in the tests come from big-int arithmetic, never from the model.
   * `prove` / `verify`: the whole proof -- prover with its coordinator under one transcript, the proof bytes, the plain verifier with
-    the harness's reasons -- from oracle/pyflow.py, oracle/pyharness.py and tests/ts_proof_ref.py.  jolt-core is not in the reference
-    tree: this file and the harness's verifier are what pins the protocol (parity unpinned)."""
+    the harness's reasons -- in the two steps of csrc/host/rw_memory_proof.hpp, which tests/memory_proof_ref.py calls as they stand
+    around its output check: `prove_memory_check` / `verify_memory_check` (the commit through the two openings) and
+    `prove_range_check_and_open` / `verify_range_check_and_open` (the range check of tests/ts_proof_ref.py and the ending), on the
+    shared steps of tests/memcheck_ref.py.  jolt-core is not in the reference tree: this file and the harness's verifier are what
+    pins the protocol (parity unpinned)."""
+import memcheck_ref as MC
 import pyref as O
 import rw_witness_ref as W
 import ts_proof_ref as TP
 import ts_range_ref as TR
 
 R = O.R
-MONT = 1 << 256
-M32 = (1 << 32) - 1
+MONT, M32, mont = MC.MONT, MC.M32, MC.mont
 RL_LIMBS = 9
 RL_MU = (1 << 288) // R
 LABEL = b"cozk-rw-memory"
-REASON_MULTISET = "multiset equality"
-REASON_GP = "grand product"
-REASON_LEAF = "leaf claim"
+REASON_MULTISET, REASON_GP, REASON_LEAF, REASON_OPENING = MC.REASON_MULTISET, MC.REASON_GP, MC.REASON_LEAF, MC.REASON_OPENING
 REASON_TS = "timestamp: "
-REASON_OPENING = "opening"
 
 h = W.fingerprint
 
@@ -53,14 +53,10 @@ def multiset_holds(rw_hashes, if_hashes):
 
 
 # ------------------------------------------------------------------------------------------------ rw_memory_leaves.hip, exact form
-def _limbs32(x, n):
-    return [(x >> (32 * i)) & M32 for i in range(n)]
-
-
 def _term(acc, coeff, v):
     """rl_term: acc += coeff * v on 32-bit words, the carry walked into limb 8"""
     assert 0 <= coeff < MONT and 0 <= v <= M32
-    c, carry = _limbs32(coeff, 8), 0
+    c, carry = MC.limbs32(coeff, 8), 0
     for k in range(8):
         t = c[k] * v + acc[k] + carry
         assert t < 1 << 64  # (2^32 - 1)^2 + 2 (2^32 - 1) = 2^64 - 1
@@ -83,7 +79,7 @@ def _reduce(acc):
     assert q == prod >> 35 and S // R - 2 <= q <= S // R
     q_lo, q_hi = q & M32, q >> 32
     assert q_hi < 8
-    m = _limbs32(R, 8)
+    m = MC.limbs32(R, 8)
     p, carry = [0] * 8, 0
     for k in range(8):
         t = m[k] * q_lo + carry
@@ -111,15 +107,11 @@ def _reduce(acc):
 def leaf_word_model(a, v, t, g, tau):
     """the 256-bit word the exact-sum kernels store for h(a, v, t): Montgomery form of the leaf"""
     one, g1, g2, c = MONT % R, g * MONT % R, g * g % R * MONT % R, (R - tau) % R * MONT % R
-    acc = _limbs32(c, 8) + [0]
+    acc = MC.limbs32(c, 8) + [0]
     _term(acc, one, a)
     _term(acc, g1, v)
     _term(acc, g2, t)
     return _reduce(acc)
-
-
-def mont(x):
-    return x % R * MONT % R
 
 
 # ------------------------------------------------------------------------------------------------ the whole proof
@@ -149,220 +141,117 @@ def witness(cfg):
     return wit
 
 
-def _bits(n):
-    k = 0
-    while (1 << k) < n:
-        k += 1
-    return k
+def slot_index(ns):
+    """RwProofIdx: where each committed column sits in the proof's order (v_written: the writing slots 2.. only)"""
+    nw = max(0, ns - 2)
+    n_rw = 3 * ns + nw
+    return dict(n_rw=n_rw, addr=0, v_read=ns, v_written=2 * ns, t_read=2 * ns + nw, v_final=n_rw, t_final=n_rw + 1, rc_rt=n_rw + 2)
 
 
-def _open(cols, point, tr, tamper_claim=False):
-    """compact_open_worker + receive_claims: -> (claims, the opening for the accumulator)"""
-    import pyspartan_outer as S
-    eq = O.eq_evals(point)
-    claims = [sum(a * b for a, b in zip(c, eq)) % R for c in cols]
-    if tamper_claim:
-        claims[0] = (claims[0] + 1) % R
-    claims, rho, batched = S.receive_claims([claims], tr)
-    joint, pw = [0] * len(cols[0]), 1
-    for c in cols:
-        for i, v in enumerate(c):
-            joint[i] = (joint[i] + v * pw) % R
-        pw = pw * rho % R
-    return claims, {"poly": joint, "eq": list(eq), "point": list(point), "claim": batched}
+def _ts_families(cfg, wit):
+    return [wit[k] for k in ("rc_rt", "rc_gmr", "fc_rt", "fc_gmr")] if cfg["with_ts"] else []
+
+
+def prove_memory_check(cfg, wit, ck, tr):
+    """steps 1-4 (rw_proof_memory_check_worker + rw_proof_coordinate_memory_check): the commit, gamma and tau, the leaves, the two grand
+    products and the two openings -> (the proof's values so far, its openings, its bytes)"""
+    ns = cfg["n_slots"]
+    rw_cols = wit["addr"] + wit["v_read"] + wit["v_written"][2:] + wit["t_read"]
+    if_cols = [wit["v_final"], wit["t_final"]]
+    commitments, out = MC.commit_columns(ck, rw_cols + if_cols + [c for fam in _ts_families(cfg, wit) for c in fam], tr)
+    g, tau = tr.challenge_scalar(), tr.challenge_scalar()
+    w = [wit["v_written"][s] if s >= 2 else None for s in range(ns)]
+    rwl = [x for c in rw_leaves(wit["addr"], wit["v_read"], wit["t_read"], w, g, tau) for x in c]
+    ifl = [x for c in if_leaves(wit["v_init"], wit["v_final"], wit["t_final"], g, tau) for x in c]
+    res, r_rw, r_if, part = MC.memory_checking(rwl, 2 * ns, ifl, 2, tr)
+    rw_claims, op_rw = MC.open_columns(rw_cols, r_rw, tr, cfg["tamper"] == 2)
+    if_claims, op_if = MC.open_columns(if_cols, r_if, tr)
+    res.update(commitments=commitments, rw_claims=rw_claims, if_claims=if_claims)
+    return res, [op_rw, op_if], out + part + O.ser_vec_fr(rw_claims) + O.ser_vec_fr(if_claims)
+
+
+def prove_range_check_and_open(cfg, wit, ck, tr, res, openings, out):
+    """steps 5 and 6 (rw_proof_range_check_and_open_worker + its coordinator): with with_ts the timestamp range check under the same
+    transcript (t_read is not committed again), then ONE reduce_and_prove -> res, completed with proof_bytes"""
+    if cfg["with_ts"]:
+        hashes, gp, ts_claims, op, part = TP.range_check_prove(wit["t_read"], *_ts_families(cfg, wit), tr)
+        openings, out = openings + [op], out + part
+        res.update(ts_hashes=hashes, ts_gp=gp, ts_claims=ts_claims)
+    ending, part = MC.reduce_and_prove(ck, openings, max(cfg["log_n"], cfg["log_mem"]), tr)
+    res.update(ending, proof_bytes=out + part)
+    return res
 
 
 def prove(cfg):
     """-> dict(proof_bytes, commitments, rw_hashes, if_hashes, rw_gp, if_gp, rw_claims, if_claims, [ts_hashes, ts_gp, ts_claims],
     reduced, reduced_claims, joint_proofs)"""
-    import pyflow as F
     import pyharness as H
     cfg = default_cfg(**cfg)
-    ns, N, MEM = cfg["n_slots"], 1 << cfg["log_n"], 1 << cfg["log_mem"]
-    nv = max(cfg["log_n"], cfg["log_mem"])
     wit = witness(cfg)
-    writers = [wit["v_written"][s] for s in range(ns) if s >= 2]
-    rw_cols = wit["addr"] + wit["v_read"] + writers + wit["t_read"]
-    if_cols = [wit["v_final"], wit["t_final"]]
-    ts_fams = wit["rc_rt"] + wit["rc_gmr"] + wit["fc_rt"] + wit["fc_gmr"] if cfg["with_ts"] else []
-    ck = H._pst_setup(cfg["seed"], nv)
+    ck = H._pst_setup(cfg["seed"], max(cfg["log_n"], cfg["log_mem"]))
     tr = O.Transcript(LABEL)
-    # 1. commit
-    committed = rw_cols + if_cols + ts_fams
-    commitments = [H._commit(ck, c) for c in committed]
-    for c in commitments:
-        tr.append_point(c)
-    out = O.ser_u64(len(committed)) + b"".join(O.ser_u64(_bits(len(col))) + O.ser_g1(c) for col, c in zip(committed, commitments))
-    # 2. gamma, tau, leaves
-    g, tau = tr.challenge_scalar(), tr.challenge_scalar()
-    w = [wit["v_written"][s] if s >= 2 else None for s in range(ns)]
-    rwl = [x for c in rw_leaves(wit["addr"], wit["v_read"], wit["t_read"], w, g, tau) for x in c]
-    ifl = [x for c in if_leaves(wit["v_init"], wit["v_final"], wit["t_final"], g, tau) for x in c]
-    # 3. the two grand products
-    rw_layers, rw_hashes = F.dense_gp([rwl], 2 * ns, tr)
-    if_layers, if_hashes = F.dense_gp([ifl], 2, tr)
-    tr.append_scalars(rw_hashes)
-    tr.append_scalars(if_hashes)
-    rw_gp, r_rw = O.gp_prove(rw_layers, tr)
-    if_gp, r_if = O.gp_prove(if_layers, tr)
-    # 4. two openings
-    openings = []
-    rw_claims, op = _open(rw_cols, r_rw[_bits(2 * ns):], tr, cfg["tamper"] == 2)
-    openings.append(op)
-    if_claims, op = _open(if_cols, r_if[1:], tr)
-    openings.append(op)
-    out += O.ser_vec_fr(rw_hashes) + O.ser_vec_fr(if_hashes) + F.ser_gp(rw_gp) + F.ser_gp(if_gp) + O.ser_vec_fr(rw_claims) + O.ser_vec_fr(if_claims)
-    res = {"commitments": commitments, "rw_hashes": rw_hashes, "if_hashes": if_hashes, "rw_gp": rw_gp, "if_gp": if_gp, "rw_claims": rw_claims, "if_claims": if_claims}
-    # 5. the timestamp range check under the same transcript
-    if cfg["with_ts"]:
-        tg, ttau = tr.challenge_scalar(), tr.challenge_scalar()
-        circuits = 6 * ns + 1
-        leaves = [x for c in TP.range_leaves(wit["t_read"], wit["rc_rt"], wit["rc_gmr"], wit["fc_rt"], wit["fc_gmr"], tg, ttau) for x in c]
-        layers, hashes = F.dense_gp([leaves], circuits, tr)
-        tr.append_scalars(hashes)
-        gp, r = O.gp_prove(layers, tr)
-        ts_claims, op = _open(ts_fams + wit["t_read"], r[_bits(circuits):], tr)
-        openings.append(op)
-        out += O.ser_vec_fr(hashes) + F.ser_gp(gp) + O.ser_vec_fr(ts_claims)
-        res.update(ts_hashes=hashes, ts_gp=gp, ts_claims=ts_claims)
-    # 6. ONE reduce_and_prove
-    r_red, red_claims, red = O.opening_reduce([openings], tr)
-    gamma = tr.challenge_scalar()
-    joint, pw = [0] * (1 << nv), 1
-    for op in openings:
-        for i, v in enumerate(op["poly"]):
-            joint[i] = (joint[i] + v * pw) % R
-        pw = pw * gamma % R
-    proofs, _ = O.pst_open(ck, joint, list(reversed(r_red)))
-    out += O.ser_u64(len(red["round_polys"])) + b"".join(O.ser_vec_fr(c) for c in red["round_polys"]) + O.ser_vec_fr(red_claims)
-    out += O.ser_u64(len(proofs)) + b"".join(O.ser_g1(p) for p in proofs)
-    res.update(proof_bytes=out, reduced=red, reduced_claims=red_claims, joint_proofs=proofs)
-    return res
+    res, openings, out = prove_memory_check(cfg, wit, ck, tr)
+    return prove_range_check_and_open(cfg, wit, ck, tr, res, openings, out)
 
 
-def _iota(point):
-    acc = 0
-    for rj in point:
-        acc = (2 * acc + rj) % R
-    return acc
+def check_order(with_ts, between=()):
+    """the verifier's checks in the order it runs them; `between`: what a caller checks between the memory check and the range check"""
+    ts = [REASON_TS + k for k in (TP.REASON_MULTISET, TP.REASON_GP, TP.REASON_LEAF)] if with_ts else []
+    return [REASON_MULTISET, REASON_GP, REASON_LEAF] + list(between) + ts + [REASON_OPENING]
 
 
-def _batch_eval(values, hi):
-    return sum(e * v for e, v in zip(O.eq_evals(hi), values + [0] * ((1 << len(hi)) - len(values)))) % R
-
-
-def verify(proof, cfg):
-    """the plain verifier: replays the transcript and runs every check -> (ok, reason of the first that fails or None, {check: bool});
-    a check after a failed grand product cannot be replayed and counts as failed.  The timestamp reasons are prefixed."""
-    import pyharness as H
-    cfg = default_cfg(**cfg)
-    ns, with_ts = cfg["n_slots"], cfg["with_ts"]
-    nw = max(0, ns - 2)
-    n_rw = 3 * ns + nw
-    ix = dict(addr=0, v_read=ns, v_written=2 * ns, t_read=2 * ns + nw, v_final=n_rw, t_final=n_rw + 1, rc_rt=n_rw + 2)
-    nv = max(cfg["log_n"], cfg["log_mem"])
-    ck = H._pst_setup(cfg["seed"], nv)
-    tr = O.Transcript(LABEL)
-    order = [REASON_MULTISET, REASON_GP, REASON_LEAF]
-    if with_ts:
-        order += [REASON_TS + k for k in (TP.REASON_MULTISET, TP.REASON_GP, TP.REASON_LEAF)]
-    order.append(REASON_OPENING)
-    checks = {k: False for k in order}
-
-    def result():
-        first = next((k for k in order if not checks[k]), None)
-        return first is None, first, checks
-    assert len(proof["commitments"]) == n_rw + 2 + (4 * ns if with_ts else 0)
-    assert len(proof["rw_hashes"]) == 2 * ns and len(proof["if_hashes"]) == 2 and len(proof["rw_claims"]) == n_rw and len(proof["if_claims"]) == 2
+def verify_memory_check(proof, cfg, tr, checks):
+    """rw_proof_verify_memory_check: sets the first three checks -> its two openings, or None after a failed grand product"""
+    ns = cfg["n_slots"]
+    ix = slot_index(ns)
+    assert len(proof["commitments"]) == ix["n_rw"] + 2 + (4 * ns if cfg["with_ts"] else 0)
+    assert len(proof["rw_hashes"]) == 2 * ns and len(proof["if_hashes"]) == 2 and len(proof["rw_claims"]) == ix["n_rw"] and len(proof["if_claims"]) == 2
     for c in proof["commitments"]:
         tr.append_point(c)
     g, tau = tr.challenge_scalar(), tr.challenge_scalar()
-    tr.append_scalars(proof["rw_hashes"])
-    tr.append_scalars(proof["if_hashes"])
     checks[REASON_MULTISET] = multiset_holds(proof["rw_hashes"], proof["if_hashes"])
-    if proof["rw_gp"]["outputs"] != proof["rw_hashes"] or proof["if_gp"]["outputs"] != proof["if_hashes"]:
-        return result()
-    out_rw = O.gp_verify(proof["rw_gp"], 2 * ns, tr)
-    out_if = O.gp_verify(proof["if_gp"], 2, tr) if out_rw is not None else None
-    if out_rw is None or out_if is None:
-        return result()
+    pts = MC.verify_grand_products(proof, 2 * ns, 2, tr)
+    if pts is None:
+        return None
     checks[REASON_GP] = True
-    (rw_claim, r_rw), (if_claim, r_if) = out_rw, out_if
-    k = _bits(2 * ns)
-    hi, lo, hi2, lo2 = r_rw[:k], r_rw[k:], r_if[:1], r_if[1:]
-    opens = [dict(point=lo, polys=list(range(n_rw)), claims=proof["rw_claims"], rho=tr.challenge_scalar())]
-    opens.append(dict(point=lo2, polys=[ix["v_final"], ix["t_final"]], claims=proof["if_claims"], rho=tr.challenge_scalar()))
+    (rw_claim, hi, lo), (if_claim, hi2, lo2) = pts
     cl = proof["rw_claims"]
-    step, leaves = _iota(lo), []
+    opens = [MC.take_opening(list(range(ix["n_rw"])), lo, cl, tr), MC.take_opening([ix["v_final"], ix["t_final"]], lo2, proof["if_claims"], tr)]
+    step, leaves = MC.iota_eval(lo), []
     for s in range(ns):
         w = cl[ix["v_written"] + s - 2] if s >= 2 else cl[ix["v_read"] + s]
         leaves.append(h(cl[ix["addr"] + s], cl[ix["v_read"] + s], cl[ix["t_read"] + s], g, tau))
         leaves.append(h(cl[ix["addr"] + s], w, step, g, tau))
     v_init = W.jolt_instance(cfg["seed"], 1 << cfg["log_n"], 1 << cfg["log_mem"], store_pct=30, n_regs=32)[3]  # public preprocessing
-    io = _iota(lo2)
+    io = MC.iota_eval(lo2)
     init = h(io, sum(a * b for a, b in zip(v_init, O.eq_evals(lo2))) % R, 0, g, tau)
     fin = h(io, proof["if_claims"][0], proof["if_claims"][1], g, tau)
-    checks[REASON_LEAF] = _batch_eval(leaves, hi) == rw_claim and _batch_eval([init, fin], hi2) == if_claim
-    if with_ts:
-        circuits = 6 * ns + 1
-        assert len(proof["ts_hashes"]) == circuits and len(proof["ts_claims"]) == 5 * ns
-        tg, ttau = tr.challenge_scalar(), tr.challenge_scalar()
-        tr.append_scalars(proof["ts_hashes"])
-        checks[REASON_TS + TP.REASON_MULTISET] = TP.multiset_holds(proof["ts_hashes"], ns)
-        out = O.gp_verify(proof["ts_gp"], circuits, tr) if proof["ts_gp"]["outputs"] == proof["ts_hashes"] else None
-        if out is None:
-            return result()
-        checks[REASON_TS + TP.REASON_GP] = True
-        claim, r = out
-        kk = _bits(circuits)
-        lv = TP.leaf_values(proof["ts_claims"], ns, _iota(r[kk:]), tg, ttau)
-        checks[REASON_TS + TP.REASON_LEAF] = _batch_eval(lv, r[:kk]) == claim
+    checks[REASON_LEAF] = MC.batch_eval(leaves, hi) == rw_claim and MC.batch_eval([init, fin], hi2) == if_claim
+    return opens
+
+
+def verify_range_check_and_open(proof, cfg, tr, checks, opens):
+    """rw_proof_verify_range_check_and_open: the range check (with with_ts, its reasons prefixed) and the reduced opening over `opens`
+    and the range check's own"""
+    import pyharness as H
+    ns, nv = cfg["n_slots"], max(cfg["log_n"], cfg["log_mem"])
+    if cfg["with_ts"]:
+        ix = slot_index(ns)
         polys = [ix["rc_rt"] + i for i in range(4 * ns)] + [ix["t_read"] + s for s in range(ns)]  # t_read: the step-1 commitments
-        opens.append(dict(point=r[kk:], polys=polys, claims=proof["ts_claims"], rho=tr.challenge_scalar()))
-    # the reduced opening: the reduction sumcheck over all openings, then one PST13 check with the trapdoor
-    pws, batched = [], []
-    for o in opens:
-        pw = [1]
-        for _ in range(1, len(o["claims"])):
-            pw.append(pw[-1] * o["rho"] % R)
-        pws.append(pw)
-        batched.append(sum(p * c for p, c in zip(pw, o["claims"])) % R)
-    rho2 = tr.challenge_scalar()
-    coeffs = [1]
-    for _ in range(1, len(opens)):
-        coeffs.append(coeffs[-1] * rho2 % R)
-    e = sum(c * b * (1 << (nv - len(o["point"]))) for c, b, o in zip(coeffs, batched, opens)) % R
-    rs, ok = [], len(proof["reduced"]["round_polys"]) == nv and len(proof["reduced_claims"]) == len(opens)
-    for comp in proof["reduced"]["round_polys"] if ok else []:
-        poly = [comp[0], (e - 2 * comp[0] - sum(comp[1:])) % R] + list(comp[1:])
-        tr.append_scalars(comp)
-        rj = tr.challenge_scalar()
-        rs.append(rj)
-        e = O.unipoly_eval(poly, rj)
-    if ok:
-        expect = 0
-        for c, o, rc in zip(coeffs, opens, proof["reduced_claims"]):
-            eqv = 1
-            for a, b in zip(o["point"], rs[nv - len(o["point"]):]):
-                eqv = eqv * ((a * b + (1 - a) * (1 - b)) % R) % R
-            expect = (expect + c * eqv * rc) % R
-        ok = expect == e
-    if ok:
-        tr.append_scalars(proof["reduced_claims"])
-        gamma = tr.challenge_scalar()
-        scal, gp, joint_claim = [0] * len(proof["commitments"]), 1, 0
-        for o, pw, rc in zip(opens, pws, proof["reduced_claims"]):
-            for idx, p in zip(o["polys"], pw):
-                scal[idx] = (scal[idx] + gp * p) % R
-            sc = 1
-            for j in range(nv - len(o["point"])):
-                sc = sc * (1 - rs[j]) % R
-            joint_claim = (joint_claim + gp * sc * rc) % R
-            gp = gp * gamma % R
-        joint_c = None
-        for c, sc in zip(proof["commitments"], scal):
-            if sc:
-                joint_c = O.g1_add(joint_c, O.g1_mul(c, sc))
-        ok = O.pst_check_with_trapdoor(ck, joint_c, list(reversed(rs)), joint_claim, proof["joint_proofs"])
-    checks[REASON_OPENING] = ok
-    return result()
+        opening = TP.range_check_verify(proof["ts_hashes"], proof["ts_gp"], proof["ts_claims"], ns, polys, tr, checks, REASON_TS)
+        if opening is None:
+            return
+        opens = opens + [opening]
+    checks[REASON_OPENING] = MC.reduced_opening_holds(proof, opens, nv, H._pst_setup(cfg["seed"], nv), tr)
+
+
+def verify(proof, cfg):
+    """the plain verifier: replays the transcript and runs every check -> (ok, reason of the first that fails or None, {check: bool});
+    a check after a failed grand product cannot be replayed and counts as failed.  The timestamp reasons are prefixed."""
+    cfg = default_cfg(**cfg)
+    tr = O.Transcript(LABEL)
+    checks = MC.Checks(check_order(cfg["with_ts"]))
+    opens = verify_memory_check(proof, cfg, tr, checks)
+    if opens is not None:
+        verify_range_check_and_open(proof, cfg, tr, checks, opens)
+    return checks.result()

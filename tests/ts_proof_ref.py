@@ -1,8 +1,9 @@
 """Plain-Python restatement of the timestamp range-check proof (co-zkvms_amd/ts_proof.py, csrc/host/ts_range_proof.hpp), shared by
 tests/test_ts_proof_model.py (CPU) and the GPU tests:
 
-  * `prove` / `verify` (second half of the file): the whole proof -- prover with its coordinator, proof bytes, plain verifier with
-    the harness's reasons -- from oracle/pyflow.py and oracle/pyharness.py.
+  * `range_check_prove` / `range_check_verify` and `prove` / `verify` (second half of the file): the range check as a step under a
+    caller's transcript, and the whole proof -- prover with its coordinator, proof bytes, plain verifier with the harness's
+    reasons -- on the shared steps of tests/memcheck_ref.py.
 
   * `range_leaves`: the 6 n_slots + 1 grand-product circuits of the range check, circuit-major, in the layout of
     cozk_timestamp_range_leaves.  h(key, count) = count g^2 + key (g + 1) - tau is ts_range_ref.fingerprint of the tuple
@@ -12,13 +13,13 @@ tests/test_ts_proof_model.py (CPU) and the GPU tests:
     operands times plain column entries, every carry propagated with its term, reduced once as to_mont(from_mont(T0)) + to_mont(T1).
     It asserts the invariants the kernel's comment claims.  Expected VALUES in the tests come from big-int arithmetic, never from
     the model."""
+import memcheck_ref as MC
 import pyref as O
 import ts_range_ref as TR
 
 R = O.R
-MONT = 1 << 256
+MONT, M32, mont = MC.MONT, MC.M32, MC.mont
 RINV = pow(MONT, -1, R)
-M32 = (1 << 32) - 1
 CO_LIMBS = 11
 CO_TERMS_BOUND = 1 << 32  # terms an accumulator holds: (2^32) * 2^320 = 2^352
 
@@ -63,10 +64,6 @@ def multiset_holds(hashes, ns):
 
 
 # ------------------------------------------------------------------------------------------------ compact_open.inc
-def _limbs32(x, n):
-    return [(x >> (32 * i)) & M32 for i in range(n)]
-
-
 def _mac(acc, a_limbs, v, off):
     """co_mac<off>: acc += a * v * 2^(32 off) on 32-bit words, the carry walked to the top limb"""
     carry = 0
@@ -89,7 +86,7 @@ def compact_sum_model(operands, entries, bits):
     acc = [0] * CO_LIMBS
     for a, v in zip(operands, entries):
         assert 0 <= a < MONT and 0 <= v < 1 << bits
-        A = _limbs32(a, 8)
+        A = MC.limbs32(a, 8)
         _mac(acc, A, v & M32, 0)
         if bits == 64:
             _mac(acc, A, v >> 32, 1)
@@ -101,19 +98,12 @@ def compact_sum_model(operands, entries, bits):
     return (from_mont_t0 * MONT + t1 * MONT) % R  # to_mont(from_mont(T0)) + to_mont(T1)
 
 
-def mont(x):
-    return x % R * MONT % R
-
-
 # ------------------------------------------------------------------------------------------------ the whole proof
-# csrc/host/ts_range_proof.hpp restated from what oracle/pyflow.py and oracle/pyharness.py offer (imported where they are used: they
-# pull in the whole flow oracle): the prover with its coordinator under one transcript, the proof bytes, and the plain verifier with
-# the same reasons.  jolt-core is not in the reference tree: this file and that verifier are what pins the protocol.
+# csrc/host/ts_range_proof.hpp restated on the steps of tests/memcheck_ref.py: the range check as a step under a caller's transcript
+# (tests/rw_proof_ref.py chains it behind the memory check), then the proof around it.  jolt-core is not in the reference tree: this
+# file and the harness's verifier are what pins the protocol.
 LABEL = b"cozk-ts-range"
-REASON_MULTISET = "multiset equality"
-REASON_GP = "grand product"
-REASON_LEAF = "leaf claim"
-REASON_OPENING = "opening"
+REASON_MULTISET, REASON_GP, REASON_LEAF, REASON_OPENING = MC.REASON_MULTISET, MC.REASON_GP, MC.REASON_LEAF, MC.REASON_OPENING
 
 
 def default_cfg(**kw):
@@ -135,13 +125,6 @@ def witness(cfg):
     return t_read, rc_rt, rc_gmr, fc_rt, fc_gmr
 
 
-def _bits(n):
-    k = 0
-    while (1 << k) < n:
-        k += 1
-    return k
-
-
 def leaf_values(claims, ns, iota, g, tau):
     """the 6 ns + 1 leaf values at a point from the 5 ns claims there and the identity column's value"""
     g1, g2 = (g + 1) % R, g * g % R
@@ -159,52 +142,49 @@ def leaf_values(claims, ns, iota, g, tau):
     return out
 
 
-def prove(cfg):
-    """-> dict(proof_bytes, commitments, hashes, gp, claims, reduced, joint_proofs)"""
+def range_check_prove(t_read, rc_rt, rc_gmr, fc_rt, fc_gmr, tr, tamper_claim=False):
+    """ts_range_check_worker + ts_range_check_coordinate, after the commit: gamma and tau, the leaves, ONE dense batched grand product
+    whose claimed outputs are the multiset hashes, ONE opening of the families and t_read -> (hashes, gp, claims, the opening, bytes)"""
     import pyflow as F
-    import pyharness as H
-    import pyspartan_outer as S
-    cfg = default_cfg(**cfg)
-    nv, ns = cfg["log_n"], cfg["n_slots"]
-    N, circuits = 1 << nv, 6 * ns + 1
-    t_read, rc_rt, rc_gmr, fc_rt, fc_gmr = witness(cfg)
-    cols = rc_rt + rc_gmr + fc_rt + fc_gmr + t_read
-    ck = H._pst_setup(cfg["seed"], nv)
-    tr = O.Transcript(LABEL)
-    # 1. commit
-    commitments = [H._commit(ck, c) for c in cols]
-    for c in commitments:
-        tr.append_point(c)
-    # 2, 3. gamma, tau, leaves
+    circuits = 6 * len(t_read) + 1
     g, tau = tr.challenge_scalar(), tr.challenge_scalar()
     leaves = [x for c in range_leaves(t_read, rc_rt, rc_gmr, fc_rt, fc_gmr, g, tau) for x in c]
-    # 4. one dense batched grand product; its claimed outputs are the multiset hashes
     layers, hashes = F.dense_gp([leaves], circuits, tr)
     tr.append_scalars(hashes)
     gp, r = O.gp_prove(layers, tr)
-    r_lo = r[_bits(circuits):]
-    # 5. claims at r_lo, one exchange, the joint polynomial
-    eq = O.eq_evals(r_lo)
-    claims = [sum(a * b for a, b in zip(c, eq)) % R for c in cols]
-    if cfg["tamper"] == 2:
-        claims[0] = (claims[0] + 1) % R
-    claims, rho, batched = S.receive_claims([claims], tr)
-    joint, pw = [0] * N, 1
-    for c in cols:
-        for i, v in enumerate(c):
-            joint[i] = (joint[i] + v * pw) % R
-        pw = pw * rho % R
-    openings = [[{"poly": joint, "eq": list(eq), "point": list(r_lo), "claim": batched}]]
-    # 6. reduce_and_prove over the one opening
-    r_red, red_claims, red = O.opening_reduce(openings, tr)
-    tr.challenge_scalar()  # gamma of the joint polynomial: one opening, gamma^0 = 1
-    proofs, _ = O.pst_open(ck, joint, list(reversed(r_red)))
-    out = O.ser_u64(len(cols)) + b"".join(O.ser_u64(nv) + O.ser_g1(c) for c in commitments)
-    out += O.ser_vec_fr(hashes) + F.ser_gp(gp) + O.ser_vec_fr(claims)
-    out += O.ser_u64(len(red["round_polys"])) + b"".join(O.ser_vec_fr(c) for c in red["round_polys"]) + O.ser_vec_fr(red_claims)
-    out += O.ser_u64(len(proofs)) + b"".join(O.ser_g1(p) for p in proofs)
-    return {"proof_bytes": out, "commitments": commitments, "hashes": hashes, "gp": gp, "claims": claims, "reduced": red, "reduced_claims": red_claims,
-            "joint_proofs": proofs}
+    claims, op = MC.open_columns(rc_rt + rc_gmr + fc_rt + fc_gmr + t_read, r[MC.bits(circuits):], tr, tamper_claim)
+    return hashes, gp, claims, op, O.ser_vec_fr(hashes) + F.ser_gp(gp) + O.ser_vec_fr(claims)
+
+
+def range_check_verify(hashes, gp, claims, ns, polys, tr, checks, prefix=""):
+    """ts_range_check_verify, after the commitments are in the transcript: sets the first three checks (their reasons behind `prefix`)
+    -> the opening of the commitments `polys` (family-major, then t_read), or None after a failed grand product"""
+    circuits = 6 * ns + 1
+    assert len(hashes) == circuits and len(claims) == 5 * ns
+    g, tau = tr.challenge_scalar(), tr.challenge_scalar()
+    tr.append_scalars(hashes)
+    checks[prefix + REASON_MULTISET] = multiset_holds(hashes, ns)
+    out = MC.verify_grand_product(gp, hashes, circuits, tr)
+    if out is None:
+        return None
+    checks[prefix + REASON_GP] = True
+    claim, hi, lo = out
+    checks[prefix + REASON_LEAF] = MC.batch_eval(leaf_values(claims, ns, MC.iota_eval(lo), g, tau), hi) == claim
+    return MC.take_opening(polys, lo, claims, tr)
+
+
+def prove(cfg):
+    """-> dict(proof_bytes, commitments, hashes, gp, claims, reduced, reduced_claims, joint_proofs)"""
+    import pyharness as H
+    cfg = default_cfg(**cfg)
+    t_read, rc_rt, rc_gmr, fc_rt, fc_gmr = witness(cfg)
+    ck = H._pst_setup(cfg["seed"], cfg["log_n"])
+    tr = O.Transcript(LABEL)
+    commitments, out = MC.commit_columns(ck, rc_rt + rc_gmr + fc_rt + fc_gmr + t_read, tr)
+    hashes, gp, claims, op, part = range_check_prove(t_read, rc_rt, rc_gmr, fc_rt, fc_gmr, tr, cfg["tamper"] == 2)
+    res, ending = MC.reduce_and_prove(ck, [op], cfg["log_n"], tr)
+    res.update(proof_bytes=out + part + ending, commitments=commitments, hashes=hashes, gp=gp, claims=claims)
+    return res
 
 
 def verify(proof, cfg):
@@ -212,58 +192,13 @@ def verify(proof, cfg):
     {check: bool}); a check after a failed grand product cannot be replayed and counts as failed"""
     import pyharness as H
     cfg = default_cfg(**cfg)
-    nv, ns = cfg["log_n"], cfg["n_slots"]
-    circuits, ncols = 6 * ns + 1, 5 * ns
-    ck = H._pst_setup(cfg["seed"], nv)
+    nv, ncols = cfg["log_n"], 5 * cfg["n_slots"]
     tr = O.Transcript(LABEL)
-    checks = {REASON_MULTISET: False, REASON_GP: False, REASON_LEAF: False, REASON_OPENING: False}
-
-    def result():
-        first = next((k for k in (REASON_MULTISET, REASON_GP, REASON_LEAF, REASON_OPENING) if not checks[k]), None)
-        return first is None, first, checks
-    assert len(proof["commitments"]) == ncols and len(proof["hashes"]) == circuits and len(proof["claims"]) == ncols
+    checks = MC.Checks([REASON_MULTISET, REASON_GP, REASON_LEAF, REASON_OPENING])
+    assert len(proof["commitments"]) == ncols
     for c in proof["commitments"]:
         tr.append_point(c)
-    g, tau = tr.challenge_scalar(), tr.challenge_scalar()
-    tr.append_scalars(proof["hashes"])
-    checks[REASON_MULTISET] = multiset_holds(proof["hashes"], ns)
-    out = O.gp_verify(proof["gp"], circuits, tr) if proof["gp"]["outputs"] == proof["hashes"] else None
-    if out is None:
-        return result()
-    checks[REASON_GP] = True
-    claim, r = out
-    k = _bits(circuits)
-    hi, lo = r[:k], r[k:]
-    iota = 0
-    for rj in lo:
-        iota = (2 * iota + rj) % R
-    lv = leaf_values(proof["claims"], ns, iota, g, tau)
-    checks[REASON_LEAF] = sum(e * v for e, v in zip(O.eq_evals(hi), lv + [0] * ((1 << k) - circuits))) % R == claim
-    # the opening: one claim exchange, the reduction sumcheck over the one opening, one PST13 check with the trapdoor
-    rho = tr.challenge_scalar()
-    pw, batched = [], 0
-    for c in proof["claims"]:
-        pw.append(pw[-1] * rho % R if pw else 1)
-        batched = (batched + pw[-1] * c) % R
-    tr.challenge_scalar()  # rho of the reduction: one opening, rho^0 = 1
-    e, rs, ok = batched, [], len(proof["reduced"]["round_polys"]) == nv and len(proof["reduced_claims"]) == 1
-    for comp in proof["reduced"]["round_polys"] if ok else []:
-        poly = [comp[0], (e - 2 * comp[0] - sum(comp[1:])) % R] + list(comp[1:])
-        tr.append_scalars(comp)
-        rj = tr.challenge_scalar()
-        rs.append(rj)
-        e = O.unipoly_eval(poly, rj)
-    if ok:
-        eqv = 1
-        for a, b in zip(lo, rs):
-            eqv = eqv * ((a * b + (1 - a) * (1 - b)) % R) % R
-        ok = eqv * proof["reduced_claims"][0] % R == e
-    if ok:
-        tr.append_scalars(proof["reduced_claims"])
-        tr.challenge_scalar()  # gamma
-        joint_c = None
-        for c, p in zip(proof["commitments"], pw):
-            joint_c = O.g1_add(joint_c, O.g1_mul(c, p))
-        ok = O.pst_check_with_trapdoor(ck, joint_c, list(reversed(rs)), proof["reduced_claims"][0], proof["joint_proofs"])
-    checks[REASON_OPENING] = ok
-    return result()
+    opening = range_check_verify(proof["hashes"], proof["gp"], proof["claims"], cfg["n_slots"], list(range(ncols)), tr, checks)
+    if opening is not None:
+        checks[REASON_OPENING] = MC.reduced_opening_holds(proof, [opening], nv, H._pst_setup(cfg["seed"], nv), tr)
+    return checks.result()
