@@ -76,7 +76,8 @@ def test_grand_product_harness_equals_c_oracle(cozk, shape, mode):
         (csrc/msm.hip:930);
       * GKR layers of len / 4 >= 1024 run the 9 x 29 kernels k_layer_cubic9 (LAYER_F9_MIN_CHUNKS); the plain prover's grouped
         split-eq variant k_layer_cubic9<1, 2> once E1_len / 2 >= 512 (layer_variant) -- reached by the 2^16 shape's
-        first round (8 x 2^17 leaves; one dispatch in a kernel trace);
+        first round (8 x 2^17 leaves; one dispatch in a kernel trace); tests/test_gpu_layer_grouped.py holds that variant and
+        k_layer_bind_cubic9<1, 2> to the Python oracle at ragged lengths and pinned grids;
       * the resident round kernel below ROUND_PERSIST_MAX = 2048 elements (cozk_layer_prove_rounds);
       * batch_evaluate over 2^14 / 2^16-element columns: k_poly_eval_chi capped at 192 workgroups (EVAL_GRID_MAX), so
         lanes hold several elements above 49 152."""
