@@ -264,11 +264,11 @@ static void prodlist_fix(cozk_ctx* ctx, cozk_prodlist* pl, const fe& r) {
 int cozk_prodlist_round(cozk_ctx* ctx, cozk_prodlist* pl, const uint64_t* r, uint64_t* out_evals) {
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(ctx && pl && out_evals, "prodlist_round: bad argument");
-        if (r) {
-            COZK_REQUIRE(pl->n >= 2, "prodlist_round: fully fixed");
-            prodlist_fix(ctx, pl, fe_from_u64x4(r));
-        }
+        // every check before the fix: a refused call leaves the list as it was, and launches nothing
+        COZK_REQUIRE(!r || pl->n >= 2, "prodlist_round: fully fixed");
         COZK_REQUIRE(pl->n >= 2, "prodlist_round: no variable left");
+        COZK_REQUIRE(!r || pl->n >= 4, "prodlist_round: nothing left to sum after this fix (the last randomness goes to cozk_prodlist_final)");
+        if (r) prodlist_fix(ctx, pl, fe_from_u64x4(r));
         for (int p = 0; p < pl->n_polys; p++) pl->desc.poly[p] = pl->store[pl->cur] + (size_t)p * pl->cap[pl->cur];
         HIP_TRY(hipMemcpyAsync(pl->d_desc, &pl->desc, sizeof(ProdListDev), hipMemcpyHostToDevice, ctx->stream));
         const size_t half = pl->n / 2;

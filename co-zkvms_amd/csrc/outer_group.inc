@@ -181,6 +181,8 @@ int cozk_outer_group_round(cozk_outer_group* g, const uint64_t* r, const uint64_
         COZK_REQUIRE(m0->round > 0 || !r, "outer_group_round: the first round takes no challenge (r must be NULL)");
         COZK_REQUIRE(m0->round == 0 || r, "outer_group_round: every round after the first binds with the previous challenge (r is NULL)");
         COZK_REQUIRE(m0->L >= (r ? 4u : 2u) && m0->current_index >= (r ? 2 : 1), "outer_group_round: the members are fully bound");
+        // the last check, still before the bind below (outer_group_check holds every member to m0's counts): a refused call leaves the members as they were
+        COZK_REQUIRE(outer_eq_in_step(m0, r != nullptr), "outer_group_round: split-eq tables out of step with the members");
         const fe rr = r ? fe_from_u64x4(r) : Fr::zero();
         const OuterGroupShape shape = outer_group_shape(m0, r != nullptr);
         const OuterGroupArgs a = outer_group_args(g, g->k);
@@ -192,7 +194,6 @@ int cozk_outer_group_round(cozk_outer_group* g, const uint64_t* r, const uint64_
         // the members move on to the state of this round: the tables and the linear factor below are those AFTER the bind
         if (r)
             for (cozk_outer* st : g->members) outer_bind_state(st, rr);
-        COZK_REQUIRE(m0->L / 2 == ((size_t)1 << (m0->n_in + m0->n_out)), "outer_group_round: split-eq tables out of step with the members");
         const fe* E_in = m0->E_in + (((size_t)1 << m0->n_in) - 1);
         const fe* E_out = m0->E_out + (((size_t)1 << m0->n_out) - 1);
         const dim3 grid(gs.gx, k);

@@ -2483,6 +2483,8 @@ int cozk_spliteq_download(cozk_ctx* ctx, const cozk_spliteq* e, uint64_t* e1, ui
 
 // SplitEqPolynomial::bind(r)
 static bool spliteq_bound(const cozk_spliteq* e) { return e->E1_len == 1 && e->E2_len < 2; }
+// one variable left: the next bind leaves the polynomial fully bound (the table lengths are powers of two)
+static bool spliteq_last_bind(const cozk_spliteq* e) { return !spliteq_bound(e) && e->E1_len * e->E2_len == 2; }
 // One bind, everything but the kernels, and the ONE place that does it: E1 folds until it is a single value, then E2; the folded
 // table flips its ping-pong side and halves.  The launcher gets the fold, and, when E1 has just collapsed, the vector that its last
 // value fold_out[0] multiplies from now on (E2).  The resident kernel does the same steps on the device; the host follows it with
@@ -2802,6 +2804,15 @@ static void layer_host_tail_gathered(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq*
 int cozk_layer_prove_rounds(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* e, const uint64_t claim[4], int num_rounds, cozk_round_cb cb,
                             void* user, uint64_t* out_r, uint64_t final_claims[16]) {
     if (!ctx || !l || !e || !claim || !cb || !final_claims || num_rounds < 0 || (num_rounds > 0 && !out_r)) return COZK_ERR_INVALID_ARG;
+    // What the rounds, the last bind and the final claims below would refuse half-way, asked before the first round: a refused call
+    // leaves the layer and the eq polynomial as they were, and the callback is not called.  The call binds num_rounds times.
+    int rc0 = cozk_guard(ctx, [&] {
+        COZK_REQUIRE(spliteq_binds_left(e->E1_len, e->E2_len) >= num_rounds, "layer_prove_rounds: the eq polynomial has fewer unbound variables than the call has rounds");
+        size_t len = l->len;
+        for (int j = 0; j < num_rounds && len > 2; j++) len = 2 * ((len + 3) / 4);  // as layer_advance
+        COZK_REQUIRE(l->len >= 2 && len == 2, "layer_prove_rounds: num_rounds binds must leave the layer fully bound (len == 2)");
+    });
+    if (rc0 != COZK_OK) return rc0;
     static const bool no_persist = getenv("COZK_NO_PERSIST") != nullptr;  // set to anything: every round is its own launch
     uint64_t pc[4], rr[4], coeffs[16], nc[4];
     memcpy(pc, claim, sizeof pc);

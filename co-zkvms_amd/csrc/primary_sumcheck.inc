@@ -863,11 +863,15 @@ int cozk_primary_round_begin(cozk_ctx* ctx, cozk_primary* p, const uint64_t* r, 
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(ctx && p && n_items && n_levels, "primary_round_begin: bad argument");
         const int NC = p->mode == COZK_MODE_REP3 ? 2 : 1;
+        // every check before the bind: a refused call leaves the primary as it was.  With two entries left the last
+        // challenge belongs to cozk_primary_final_evals, a bind here would leave nothing to sum
         if (r) {
-            // every check before the bind: a refused call leaves the primary as it was.  With two entries left the last
-            // challenge belongs to cozk_primary_final_evals, a bind here would leave nothing to sum
             COZK_REQUIRE(p->n >= 2, "primary_round_begin: fully bound");
             COZK_REQUIRE(p->n >= 4, "primary_round_begin: nothing left to sum");
+        }
+        COZK_REQUIRE(p->n >= 2, "primary_round_begin: nothing left to sum");
+        COZK_REQUIRE(p->mul.size() * ((r ? p->n / 2 : p->n) / 2) < ((size_t)1 << 31), "primary sumcheck: activity array too long for the 32-bit item scan");
+        if (r) {
             const int dst = 1 - p->cur;
             const size_t n_out = p->n / 2;
             dim3 g(grid_for(n_out), (unsigned)p->T);
@@ -876,7 +880,6 @@ int cozk_primary_round_begin(cozk_ctx* ctx, cozk_primary* p, const uint64_t* r, 
             p->cur = dst;
             p->n = n_out;
         }
-        COZK_REQUIRE(p->n >= 2, "primary_round_begin: nothing left to sum");
         const size_t half = p->n / 2;
         const fe* st = p->store[p->cur];
         const size_t cap = p->cap[p->cur];
@@ -903,8 +906,7 @@ int cozk_primary_round_begin(cozk_ctx* ctx, cozk_primary* p, const uint64_t* r, 
         if (n_mul) {
             dim3 ga(grid_for(half), (unsigned)n_mul);
             k_primary_active<<<ga, PT, 0, ctx->stream>>>(p->d_live, half, p->d_mul, p->d_act);
-            const size_t n_act = n_mul * half;
-            COZK_REQUIRE(n_act < ((size_t)1 << 31), "primary sumcheck: activity array too long for the 32-bit item scan");
+            const size_t n_act = n_mul * half;  // < 2^31: checked above
             uint32_t* off = p->d_act + n_mul * p->idx_cap + 1;
             size_t tmp_bytes = 0;
             HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, p->d_act, off, (int)n_act, ctx->stream));

@@ -626,22 +626,25 @@ int cozk_sparse_layer_round(cozk_ctx* ctx, cozk_sparse_layer* s, cozk_spliteq* e
     int rc = cozk_guard(ctx, [&] {
         COZK_REQUIRE(ctx && s && e && out_evals, "sparse_layer_round: null argument");
         COZK_REQUIRE(s->ctx == ctx, "sparse_layer_round: the layer belongs to another context");
-        COZK_REQUIRE(sparse_party_ok(s, party_id), "sparse_layer_round: the party must be 0..2 and the one the layer was built for");
         COZK_REQUIRE(e->ctx == ctx, "sparse_layer_round: the eq polynomial belongs to another context");
         COZK_REQUIRE(!spliteq_bound(e), "sparse_layer_round: eq polynomial already fully bound");
+        COZK_REQUIRE(!r || !spliteq_last_bind(e), "sparse_layer_round: the bind would leave no round to run (the eq polynomial has one variable left)");
         const size_t n_round = r ? s->n / 2 : s->n;
         COZK_REQUIRE(!r || s->n >= 4, "sparse_layer_round: the bind would leave fewer than one pair");
         COZK_REQUIRE(s->n % 4 == 0 && n_round % 4 == 0, "sparse_layer_round: the dense length must be a multiple of 4 (in a binding round, of 8)");
+        // the last check: it gives a layer that has no party yet this one, and a refused call leaves the layer as it was
+        COZK_REQUIRE(sparse_party_ok(s, party_id), "sparse_layer_round: the party must be 0..2 and the one the layer was built for");
     });
     if (rc != COZK_OK) return rc;
     if (r) {
+        // neither bind can refuse from here: each of their checks (the context, a known party, n >= 4 and a multiple of 4; an eq
+        // polynomial that is not fully bound) is among the ones above, and the eq polynomial keeps a variable for the round below
         rc = cozk_sparse_layer_bind(ctx, s, r);
         if (rc != COZK_OK) return rc;
         rc = cozk_spliteq_bind(ctx, e, r);
         if (rc != COZK_OK) return rc;
     }
     return cozk_guard(ctx, [&] {
-        COZK_REQUIRE(!spliteq_bound(e), "sparse_layer_round: the bind left no round to run");
         const size_t nquads = s->n / 4;
         const EqView v = eq_view(e);
         fe sums[6];  // D(0), D(2), D(3), S_all(0), S_all(2), S_all(3)

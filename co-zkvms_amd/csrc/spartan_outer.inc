@@ -525,6 +525,19 @@ static void outer_bind_state(cozk_outer* st, const fe& r) {
     else if (0 < st->current_index) st->n_out -= 1;
 }
 
+// Would the split-eq tables cover the row pairs of the round that follows -- after one more bind, if `bind` -- exactly?  Asked BEFORE
+// that bind (the counts move as outer_bind_state moves them), so a refusal finds the handle as it was.  An internal invariant: create
+// sets L = 2^n_tau, current_index = n_tau and n_in + n_out = n_tau - 1, and every bind with current_index >= 2 halves L and takes one
+// variable off n_in or n_out, so no sequence of calls through the API makes it false.  Needs current_index >= (bind ? 2 : 1).
+static bool outer_eq_in_step(const cozk_outer* st, bool bind) {
+    size_t n_in = st->n_in, n_out = st->n_out;
+    if (bind) {
+        if ((int)(st->w.size() / 2) < st->current_index - 1) n_in -= 1;
+        else n_out -= 1;
+    }
+    return (bind ? st->L / 4 : st->L / 2) == ((size_t)1 << (n_in + n_out));
+}
+
 static void outer_bind(cozk_ctx* ctx, cozk_outer* st, const fe& r) {
     const int NC = st->mode == COZK_MODE_REP3 ? 2 : 1;
     const int dst = 1 - st->cur;
@@ -563,10 +576,13 @@ static bool outer_use_f9(size_t act_pairs) {
 int cozk_outer_round(cozk_ctx* ctx, cozk_outer* st, const uint64_t* r, const uint64_t claim[4], uint64_t out_coeffs[16]) {
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(ctx && st && claim && out_coeffs, "outer_round: bad argument");
-        if (r) outer_bind(ctx, st, fe_from_u64x4(r));
+        // every check before the bind: a refused call leaves the handle as it was, and launches nothing
         COZK_REQUIRE(st->L >= 2 && st->current_index >= 1, "outer_round: fully bound");
+        COZK_REQUIRE(!r || (st->L >= 4 && st->current_index >= 2),
+                     "outer_round: nothing left to sum after this bind (the last challenge goes to cozk_outer_final_evals)");
+        COZK_REQUIRE(outer_eq_in_step(st, r != nullptr), "outer_round: split-eq tables out of step with the layer");
+        if (r) outer_bind(ctx, st, fe_from_u64x4(r));
         const size_t npairs = st->L / 2;
-        COZK_REQUIRE(npairs == ((size_t)1 << (st->n_in + st->n_out)), "outer_round: split-eq tables out of step with the layer");
         const bool act = st->per_step > 1;
         const size_t num_steps = st->L / st->per_step;
         const size_t act_pairs = num_steps * ((st->act_rows + 1) / 2);

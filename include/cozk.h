@@ -603,7 +603,10 @@ int cozk_layer_round(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* eq, const uint6
  * per round cb(user, round, coeffs[4x4], r_out[4], next_claim_out[4]) sends the round polynomial's coefficient
  * shares and returns the challenge and this party's additive share of the next claim (0 = ok).  Large rounds
  * are one launch each; the tail of the layer (<= 2048 elements) runs in one resident kernel that trades sums and
- * challenges with the host through pinned memory.  out_r = num_rounds x 4; final_claims = L.a, L.b, R.a, R.b */
+ * challenges with the host through pinned memory.  out_r = num_rounds x 4; final_claims = L.a, L.b, R.a, R.b.
+ * The call binds num_rounds times.  What its rounds would refuse half-way is asked before the first one -- eq must have at
+ * least num_rounds unbound variables, and num_rounds binds must leave the layer at 2 elements -- so a refused call
+ * (COZK_ERR_INVALID_ARG) has not called cb and leaves the layer and eq as they were. */
 typedef int (*cozk_round_cb)(void* user, int round, const uint64_t coeffs[16], uint64_t r_out[4],
                              uint64_t next_claim_out[4]);
 int cozk_layer_prove_rounds(cozk_ctx* ctx, cozk_layer* l, cozk_spliteq* eq, const uint64_t claim[4],
@@ -884,7 +887,9 @@ int cozk_sparse_layer_from_output(cozk_ctx* ctx, cozk_sparse_layer* s, cozk_vec*
 int cozk_sparse_layer_bind(cozk_ctx* ctx, cozk_sparse_layer* s, const uint64_t r[4]);
 /* one round of prove_sumcheck over the layer (compute_cubic, :415-715), the contract of cozk_toggle_round: bind layer and eq with
  * r when non-NULL, then this party's additive g(0), g(2), g(3) in delta form: the all-ones sums in closed form over the layer's
- * n / 4 quads + sum over the merged groups of eq_t(q) (L_t R_t - 1) */
+ * n / 4 quads + sum over the merged groups of eq_t(q) (L_t R_t - 1).  Every check comes before the two binds and before a layer
+ * without a party takes party_id: a refused call leaves the layer and eq as they were.  With r, eq needs two unbound variables
+ * (the bind takes one, the round the other). */
 int cozk_sparse_layer_round(cozk_ctx* ctx, cozk_sparse_layer* s, cozk_spliteq* eq, const uint64_t* r, int party_id,
                             uint64_t out_evals[12]);
 /* coalesce (:91-103): the dense interleaved layer (filled with trivial ones, then the stored pairs), an ordinary cozk_layer */
@@ -1106,9 +1111,15 @@ int cozk_outer_download(cozk_ctx* ctx, const cozk_outer* st, uint64_t* az_a, uin
                         uint64_t* bz_b, uint64_t* cz_a, uint64_t* cz_b);
 /* first_sumcheck_round / subsequent_sumcheck_round (spartan_interleaved_poly.rs:189-612) without the network leg: bind with
  * the previous challenge r (NULL in the first round), then the cubic round polynomial of
- * process_eq_sumcheck_round_worker (subprotocols/sumcheck_spartan.rs:44-79) as 4 additive coefficient shares */
+ * process_eq_sumcheck_round_worker (subprotocols/sumcheck_spartan.rs:44-79) as 4 additive coefficient shares.
+ * Every check comes before the bind: a refused call (COZK_ERR_INVALID_ARG) launches nothing and leaves the handle as it was, so
+ * the call the message names can follow on the same handle.  Refused: a NULL ctx, st, claim or out_coeffs ("outer_round: bad
+ * argument"); a fully bound handle (cozk_outer_len == 1), with or without r ("outer_round: fully bound"); r with one unbound
+ * variable left (cozk_outer_len == 2), where the bind would leave nothing to sum -- that challenge belongs to
+ * cozk_outer_final_evals ("outer_round: nothing left to sum after this bind"). */
 int cozk_outer_round(cozk_ctx* ctx, cozk_outer* st, const uint64_t* r, const uint64_t claim[4], uint64_t out_coeffs[16]);
-/* final_sumcheck_evals (:648-664) after binding with the last challenge: additive Az(r), Bz(r), Cz(r) */
+/* final_sumcheck_evals (:648-664) after binding with the last challenge: additive Az(r), Bz(r), Cz(r).  Refused before the bind,
+ * the handle unchanged, unless exactly one unbound variable is left (cozk_outer_len == 2). */
 int cozk_outer_final_evals(cozk_ctx* ctx, cozk_outer* st, const uint64_t r[4], uint64_t out[12]);
 /* ---- Spartan inner / shift sumchecks (co-jolt/src/r1cs/spartan/worker.rs:100-275).
  * EqPlusOnePolynomial::evals(r, None).1 (jolt-core, used worker.rs:116): out[y] = eq_plus_one(r, y), big-endian, 2^nv entries;
@@ -1145,9 +1156,15 @@ int cozk_prodlist_create(cozk_ctx* ctx, const cozk_vec* const* polys, size_t n_p
 int cozk_prodlist_free(cozk_prodlist* pl);
 int cozk_prodlist_degree(const cozk_prodlist* pl); /* max_multiplicands */
 /* prove_round: fix_variables with the previous randomness r (NULL in the first round), then out_evals =
- * (degree + 1) x 4 u64: the evaluations at t = 0 .. degree */
+ * (degree + 1) x 4 u64: the evaluations at t = 0 .. degree.
+ * Every check comes before the fix: a refused call (COZK_ERR_INVALID_ARG) launches nothing and leaves the list as it was.
+ * Refused: a NULL ctx, pl or out_evals ("prodlist_round: bad argument"); a fully fixed list (one element per polynomial), with r
+ * ("prodlist_round: fully fixed") or without ("prodlist_round: no variable left"); r with one variable left (two elements per
+ * polynomial), where the fix would leave nothing to sum -- that randomness belongs to cozk_prodlist_final ("prodlist_round:
+ * nothing left to sum after this fix"). */
 int cozk_prodlist_round(cozk_ctx* ctx, cozk_prodlist* pl, const uint64_t* r, uint64_t* out_evals);
-/* the last fix_variables + obtain_distrbuted_sumcheck_prover_state (sumcheck.rs:434-452): n_polys x 4 u64 */
+/* the last fix_variables + obtain_distrbuted_sumcheck_prover_state (sumcheck.rs:434-452): n_polys x 4 u64.  Refused before the
+ * fix, the list unchanged, unless exactly one variable is left. */
 int cozk_prodlist_final(cozk_ctx* ctx, cozk_prodlist* pl, const uint64_t r[4], uint64_t* out_vals);
 
 /* SplitEqPolynomial::{new, bind} */

@@ -199,6 +199,49 @@ def test_layer_round_refusal_leaves_layer_and_eq_untouched(cozk, ctx, mode):
 
 @pytest.mark.parametrize("resident", [True, False])
 @pytest.mark.parametrize("mode", ["rep3", "plain"])
+@pytest.mark.parametrize("length", [8, 4096 + 8])
+def test_layer_prove_rounds_refusal_comes_before_the_first_round(cozk, ctx, mode, length, resident):
+    """what the rounds of cozk_layer_prove_rounds would refuse half-way is asked before the first one: an eq polynomial with fewer
+    unbound variables than the call has rounds (asked round by round, the rounds run, callbacks included, until the eq polynomial is used
+    up, and the last bind moves the layer without it), and a number of rounds that does not leave the layer at two elements (refused
+    by the final claims, after every round).  The callback is not called, layer and eq tables stay, and the good call that follows
+    gives what a twin gives that saw no refusal.  8 elements: the host tail; 4104: launched rounds first (above 2048 elements)."""
+    ctx.set_resident_rounds(resident)
+    try:
+        rng = O.SplitMix64(length + (mode == "plain"))
+        coeffs = _shares(rng, length, mode)
+        nv = ((length + 1) // 2 - 1).bit_length()
+        w = [rng.field() for _ in range(nv)]
+        rs, claims = [rng.field() for _ in range(nv)], [rng.field() for _ in range(nv)]
+        layer, twin = (cozk.Rep3DenseInterleavedPolynomial.new(ctx, coeffs) for _ in range(2))
+        eq, eq_twin, short = cozk.SplitEqPolynomial(ctx, w), cozk.SplitEqPolynomial(ctx, w), cozk.SplitEqPolynomial(ctx, w[1:])
+        calls = []
+
+        def exchange(rnd, cf):
+            calls.append(rnd)
+            return rs[rnd], claims[rnd]
+
+        def state():
+            return layer.coeffs(), eq.lens(), eq.download(), short.lens(), short.download()
+
+        before = state()
+        for text, e, rounds in [("layer_prove_rounds: the eq polynomial has fewer unbound variables than the call has rounds", short, nv),
+                                ("layer_prove_rounds: num_rounds binds must leave the layer fully bound (len == 2)", eq, nv - 1),
+                                ("layer_prove_rounds: num_rounds binds must leave the layer fully bound (len == 2)", eq, 0)]:
+            with pytest.raises(cozk.CozkError) as err:
+                layer.prove_rounds(e, claims[0], rounds, exchange)
+            assert err.value.code == -1 and text in str(err.value), str(err.value)
+            assert calls == [] and state() == before
+        got = layer.prove_rounds(eq, claims[0], nv, exchange)
+        assert calls == list(range(nv))
+        assert got == twin.prove_rounds(eq_twin, claims[0], nv, exchange)
+        assert layer.coeffs() == twin.coeffs() and (eq.lens(), eq.download()) == (eq_twin.lens(), eq_twin.download())
+    finally:
+        ctx.set_resident_rounds(None)
+
+
+@pytest.mark.parametrize("resident", [True, False])
+@pytest.mark.parametrize("mode", ["rep3", "plain"])
 @pytest.mark.parametrize("length", [4, 6, 96, 2048, 4096 + 8, 1 << 14])
 def test_layer_prove_rounds_matches_separate_calls(cozk, ctx, mode, length, resident):
     """cozk_layer_prove_rounds (whole round loop behind the ABI; per-round launches above 2048 elements, then -- with

@@ -384,6 +384,8 @@ def test_level_and_final_evals_out_of_turn_are_refused(cozk, LK, ctxs):
         assert len(pr) == 4
         for level in (1, 2):
             pr.level(level)
+        # cozk_primary_round_finish without an output: its one refusal, and the whole message follows
+        _refused(cozk, "primary_round_finish: bad argument", lambda: pr.ctx.check(pr._l.cozk_primary_round_finish(pr.ctx.h, pr.h, None)))
         assert pr.round_finish() == ref.total()
         ref.bind(r0)
         msgs, _, _, _ = run.round(r0)

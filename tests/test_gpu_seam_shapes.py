@@ -272,6 +272,7 @@ def test_prodlist_refusals_leave_the_context_usable(cozk, ctx):
         with pytest.raises(cozk.CozkError) as e:
             call()
         assert e.value.code == ERR_INVALID_ARG
+        return str(e.value)
 
     # final with two variables left, then the same object goes through its rounds
     pl = LG.ProdList(ctx, vecs, good)
@@ -282,11 +283,13 @@ def test_prodlist_refusals_leave_the_context_usable(cozk, ctx):
     assert pl.round(r) == G.prove_round(ref1, good, 2)
     r = rng.field()
     finals = [p[0] for p in G.fix_variables(ref1, r)]
+    # one variable left: its randomness belongs to final; a round with it is refused and leaves the list to the final below
+    assert "prodlist_round: nothing left to sum after this fix" in refused_call(lambda: pl.round(r))
     assert pl.final(r) == finals
     # fully fixed: no round with a challenge, none without, no second final; the context goes on
-    refused_call(lambda: pl.round(rng.field()))
-    refused_call(lambda: pl.round())
-    refused_call(lambda: pl.final(rng.field()))
+    assert "prodlist_round: fully fixed" in refused_call(lambda: pl.round(rng.field()))
+    assert "prodlist_round: no variable left" in refused_call(lambda: pl.round())
+    assert "prodlist_final: one variable must be left" in refused_call(lambda: pl.final(rng.field()))
     pl.free()
     pl = LG.ProdList(ctx, vecs, good)
     assert pl.round() == G.prove_round(ref, good, 2)

@@ -303,10 +303,12 @@ def test_refusals_leave_out_null_and_the_object_usable(cozk, ctx):
     assert (len(sp), sp.count) == (4, 2)
     sp.bind(r)                                          # 4 -> 2: one pair
     assert (len(sp), sp.count) == (2, 1)
+    stored = sp.download()
     refused(sp.bind, r)                                 # fewer than one pair
     refused(sp.round, cozk.SplitEqPolynomial(ctx, w), r)
     refused(sp.output_local)                            # a length that is no multiple of 4
     assert (len(sp), sp.count) == (2, 1)
+    assert sp.download() == stored                      # the refused bind and round moved no value
     dense = sp.to_dense()
     assert len(dense.coeffs()) == 2
     dense.free()
@@ -316,3 +318,62 @@ def test_refusals_leave_out_null_and_the_object_usable(cozk, ctx):
     refused(sp.round, cozk.SplitEqPolynomial(ctx, w), party=5)
     assert sp.round(cozk.SplitEqPolynomial(ctx, w)) == first
     sp.free()
+
+
+@pytest.mark.parametrize("mode", ["plain", "rep3"])
+def test_round_refusals_leave_layer_eq_and_party_untouched(cozk, ctx, mode):
+    """every refusal of cozk_sparse_layer_round comes before the layer's bind, the eq polynomial's bind and the adoption of the party:
+    a subject and a twin that sees no refused call, 16 dense entries (8 pairs, 4 stored) over an eq polynomial of three variables.
+    Refused before the first round and after every round, each time with (length, count, stored pairs) and the eq tables unmoved:
+      * a binding round over an eq polynomial with ONE variable left -- the bind would leave no round to run (a check behind
+        the binds would move the layer and that eq polynomial and refuse afterwards);
+      * a fully bound eq polynomial, asked as party 1: a Rep3 layer from explicit lists has no party yet and must not take this one
+        (a layer that did would refuse the rounds of party 2 from then on);
+      * a party out of range; at 4 entries, a binding round (the length would be no multiple of 4).
+    Every round of the subject then equals the twin's, and so do the layers at the end."""
+    LK = _lk()
+    rng = O.SplitMix64(41 + (mode == "rep3"))
+    n, idx, party = 16, [0, 2, 3, 6], (2 if mode == "rep3" else 0)
+    val = (lambda: (rng.field(), rng.field())) if mode == "rep3" else rng.field
+    pairs = [(val(), val()) for _ in idx]
+    sp, twin = (LK.SparseLayer.from_lists(ctx, n, idx, pairs) for _ in range(2))
+    w = [rng.field() for _ in range(3)]
+    eq, eq_twin = cozk.SplitEqPolynomial(ctx, w), cozk.SplitEqPolynomial(ctx, w)
+    one_left = cozk.SplitEqPolynomial(ctx, w[:1])
+    bound = cozk.SplitEqPolynomial(ctx, w[:1])
+    bound.bind(rng.field())
+    spare = cozk.SplitEqPolynomial(ctx, w)  # never bound: three variables at every point
+    assert one_left.lens() == (2, 1) and bound.lens() == (1, 1)
+
+    def refused(text, *a, **k):
+        with pytest.raises(cozk.CozkError) as ei:
+            sp.round(*a, **k)
+        assert ei.value.code == -1 and text in str(ei.value), str(ei.value)
+
+    def state():
+        return (len(sp), sp.count, sp.download(), eq.lens(), eq.download(), one_left.lens(), one_left.download(), bound.lens(), spare.lens())
+
+    r = None
+    for rnd in range(4):  # before round `rnd`: 16, 16, 8, 4 entries
+        before = state()
+        assert before[0] == (16, 16, 8, 4)[rnd]
+        if rnd < 3:
+            refused("sparse_layer_round: the bind would leave no round to run", one_left, rng.field(), party=party)
+        refused("sparse_layer_round: eq polynomial already fully bound", bound, party=1)
+        refused("sparse_layer_round: eq polynomial already fully bound", bound, rng.field(), party=1)
+        refused("sparse_layer_round: the party must be 0..2", eq, None, party=5)
+        assert sp._l.cozk_sparse_layer_round(ctx.h, sp.h, eq.h, None, party, None) == -1  # a NULL output
+        if rnd == 3:
+            refused("sparse_layer_round: the dense length must be a multiple of 4", spare, r, party=party)
+        assert state() == before
+        if rnd == 3:
+            break
+        assert sp.round(eq, r, party=party) == twin.round(eq_twin, r, party=party), rnd
+        r = rng.field()
+    assert (len(sp), sp.count, sp.download()) == (len(twin), twin.count, twin.download())
+    assert (eq.lens(), eq.download()) == (eq_twin.lens(), eq_twin.download())
+    sp.bind(r)
+    twin.bind(r)
+    assert (len(sp), sp.download()) == (2, twin.download())
+    for x in (sp, twin, eq, eq_twin, one_left, bound, spare):
+        x.free()

@@ -212,17 +212,29 @@ def test_refusals_leave_no_handle(cozk, ctx, party_ctxs):
     _expect_invalid(cozk, p0, l.cozk_toggle_group_final_claims(g.h, None, fp12.ctypes.data, 3), "toggle_group_final_claims: null argument")
     # nothing ran: the group still proves from the start, and equals a fresh one
     first = g.round(eq0)
-    fresh = lk.ToggleGroup(p0, F, good)
-    assert first == fresh.round(cozk.SplitEqPolynomial(p0, [3, 5, 7]))
-    g.round(eq0, 11)
+    fresh = lk.ToggleGroup(p0, F, good)  # the twin: it sees no refused call
+    eq_f = cozk.SplitEqPolynomial(p0, [3, 5, 7])
+    assert first == fresh.round(eq_f)
+    # a fully bound eq polynomial: refused before the group or that eq polynomial binds -- the next round equals the twin's
+    eq_b = cozk.SplitEqPolynomial(p0, [3])
+    eq_b.bind(5)
+    _expect_invalid(cozk, p0, l.cozk_toggle_group_round(g.h, eq_b.h, r.ctypes.data, out.ctypes.data), "toggle_group_round: eq polynomial already fully bound")
+    assert eq_b.lens() == (1, 1) and eq0.lens() == eq_f.lens()
+    assert g.round(eq0, 11) == fresh.round(eq_f, 11)
     _expect_invalid(cozk, p0, l.cozk_toggle_group_layer_outputs(g.h, (ctypes.c_void_p * 3)(p0.h, p0.h, p0.h), o), "toggle_group_layer_outputs: needs an unbound group")
-    g.round(eq0, 13)
+    assert g.round(eq0, 13) == fresh.round(eq_f, 13)
+    _expect_invalid(cozk, p0, l.cozk_toggle_group_round(g.h, eq0.h, r.ctypes.data, out.ctypes.data), "toggle_group_round: the bind leaves the group fully bound")
+    assert eq0.lens() == eq_f.lens()
     g.bind(17)
+    fresh.bind(17)
+    claims = g.final_claims(3)
+    assert claims == fresh.final_claims(3)
     _expect_invalid(cozk, p0, l.cozk_toggle_group_round(g.h, eq0.h, r.ctypes.data, out.ctypes.data), "toggle_group_round: the group is fully bound")
     _expect_invalid(cozk, p0, l.cozk_toggle_group_round(g.h, eq0.h, None, out.ctypes.data), "toggle_group_round: the group is fully bound")
     _expect_invalid(cozk, p0, l.cozk_toggle_group_bind(g.h, r.ctypes.data), "toggle_group_bind: the group is fully bound")
     _expect_invalid(cozk, p0, l.cozk_toggle_group_final_claims(g.h, fl4.ctypes.data, fp12.ctypes.data, 4), "toggle_group_final_claims: 0 <= k_final <= k")
     assert len(g.final_claims(3)[1]) == 3
+    assert g.final_claims(3) == claims and eq0.lens() == eq_f.lens()  # the refused calls on the fully bound group changed nothing
     assert [v.to_ints() for v in good] == [list(range(1, 9))] * 3
 
 
