@@ -14,6 +14,7 @@ import pytest
 
 import pyref as O
 import pysparse as S
+from sparse_tiles_ref import opened as _opened, sumcheck as _sumcheck  # the round driver, shared with test_gpu_sparse_tiles.py
 
 pytestmark = pytest.mark.gpu
 R = O.R
@@ -50,70 +51,6 @@ def _lk():
 
 def _stored_pairs(cols, batch, n):
     return [b * (n // 2) + i // 2 for b in range(batch) for i in range(0, n, 2) if cols[b // 2][i] | cols[b // 2][i + 1]]
-
-
-def _opened(coeffs):
-    """the values a Rep3 vector of one party per row opens to: a_0 + a_1 + a_2"""
-    return [sum(c[0] for c in col) % R for col in zip(*coeffs)]
-
-
-def _sumcheck(cozk, ctx, devs, refs, seed, exact):
-    """every round of a sumcheck over one layer held by len(devs) parties.  exact: per party the round values and the bound layer equal
-    the oracle's bit for bit; else the sums over the parties and the opened layers do.  Returns the eq forms the rounds went through."""
-    nparties = len(devs)
-    n = refs[0].dense_len
-    assert len(devs[0]) == n
-    nv = max(1, (n // 2 - 1).bit_length())
-    rng = O.SplitMix64(seed)
-    w = [rng.field() for _ in range(nv)]
-    eq_refs = [O.SplitEq(w) for _ in range(nparties)]
-    eq_devs = [cozk.SplitEqPolynomial(ctx, w) for _ in range(nparties)]
-    claim = rng.field()
-    forms = set()
-
-    def check_dense():
-        got = [devs[p].to_dense(party=p) for p in range(nparties)]
-        want = [refs[p].coalesce() for p in range(nparties)]
-        if exact:
-            for p in range(nparties):
-                assert got[p].coeffs() == want[p], p
-        else:
-            assert _opened([g.coeffs() for g in got]) == _opened(want)
-        for g in got:
-            g.free()
-
-    pending = None
-    rounds = 0
-    while True:
-        n_round = n // 2 if pending is not None else n
-        if n_round < 4 or n_round % 4:
-            break
-        forms.add("flat" if eq_refs[0].E1_len == 1 else "nested")
-        evs = [refs[p].compute_cubic_evals(eq_refs[p], claim) for p in range(nparties)]
-        gots = [devs[p].round(eq_devs[p], pending, party=p) for p in range(nparties)]
-        n = n_round
-        if exact:
-            for p in range(nparties):
-                assert gots[p] == [evs[p][0], evs[p][2], evs[p][3]], (p, rounds)
-        else:
-            for k, kk in enumerate((0, 2, 3)):
-                assert sum(g[k] for g in gots) % R == sum(e[kk] for e in evs) % R, (rounds, kk)
-        if pending is not None:
-            assert len(devs[0]) == refs[0].dense_len
-            check_dense()
-        pending = rng.field()
-        for p in range(nparties):
-            refs[p].bind(pending)
-            eq_refs[p].bind(pending)
-        rounds += 1
-    assert rounds >= 1
-    if n >= 4 and n % 4 == 0:  # the bind after the last sparse round
-        for p in range(nparties):
-            devs[p].bind(pending)
-        check_dense()
-    for e in eq_devs:
-        e.free()
-    return forms
 
 
 @pytest.mark.parametrize("batch,n,density,nparties", SHAPES)
