@@ -21,11 +21,10 @@
 // Results are returned as affine points, so the output is bit-exact to any correct MSM.
 #include "common.hpp"
 #include "fq9.hip.hpp"
+#include "host/msm_schedule.hpp"  // NB, TPB, LTPB, the window count per kind and everything that decides a launch
 #include <cstring>
 
-static constexpr uint32_t NB = 1u << 15;  // buckets per group
-static constexpr int CH = 16;             // buckets per reduction chunk
-static constexpr int TPB = 256;
+static constexpr int CH = 16;  // buckets per reduction chunk
 
 // ------------------------------------------------------------------ scalar -> signed digits
 template <int KIND>
@@ -90,15 +89,10 @@ struct ScalarKind<COZK_SCALAR_I64> {
     }
 };
 
-static inline int kind_nwin(int kind) {
-    switch (kind) {
-        case COZK_SCALAR_FR: return 16;
-        case COZK_SCALAR_U8: return 1;
-        case COZK_SCALAR_U16: return 2;
-        case COZK_SCALAR_U32: return 3;
-        default: return 5;
-    }
-}
+template <int... K>
+constexpr bool nwin_as_scheduled() { return ((ScalarKind<K>::NWIN == MSM_KIND_NWIN[K]) && ...); }
+static_assert(nwin_as_scheduled<COZK_SCALAR_FR, COZK_SCALAR_U8, COZK_SCALAR_U16, COZK_SCALAR_U32, COZK_SCALAR_U64, COZK_SCALAR_I64>(),
+              "host/msm_schedule.hpp counts other windows per kind than the kernels place");
 
 // Offset digit form (U16 / U32 / U64 columns on a window table): limb d_k of v is written (d_k - 32768) + 32768, so
 //   v G_i = sum_k (d_k - 32768) 2^(16k) G_i + c G_i,   c = 32768 sum_k 2^(16k) over the limbs of the kind.
@@ -110,14 +104,6 @@ template <int KIND>
 struct KindHasOffsetForm {
     static constexpr bool value = KIND == COZK_SCALAR_U16 || KIND == COZK_SCALAR_U32 || KIND == COZK_SCALAR_U64;
 };
-static inline int kind_offset_slot(int kind) {  // index into cozk_bases::SliceSum::cS, -1 for kinds that are always plain
-    switch (kind) {
-        case COZK_SCALAR_U16: return 0;
-        case COZK_SCALAR_U32: return 1;
-        case COZK_SCALAR_U64: return 2;
-        default: return -1;
-    }
-}
 
 // Enumerate the non-zero signed digits of scalar i: calls f(window, bucket, negative).
 template <int KIND, class F>
@@ -215,10 +201,6 @@ struct MsmPolyDesc {
     uint32_t group;     // bucket group (= polynomial index inside the launch set)
     uint32_t pad;
 };
-static constexpr int LTPB = 1024;  // launch bound of the LDS-histogram kernels; the launch width is chosen in msm_sort
-// launch width and workgroups-per-polynomial cap of a sort that runs alone (msm_sort)
-static constexpr int MSM_WIDE_LTPB = 1024;
-static constexpr int MSM_WIDE_WGS = 64;
 // what travels between the host and one launch set through pinned memory: the descriptors on their way in, the fullest
 // bucket and the reference total on their way out (read after the batch's final synchronisation)
 struct MsmSetPin {
@@ -835,121 +817,27 @@ static void build_window_table(cozk_ctx* ctx, cozk_bases* b) {
         default: throw CozkError(COZK_ERR_INVALID_ARG, "unknown scalar kind");    \
     }
 
-// One launch set = P MSMs (polynomial p runs over bases[offsets[p] .. offsets[p]+ns[p]); scalars[p] = device
-// pointer of kinds[p]) in two phases that msm_batch pipelines on two streams:
-//   msm_sort        digits -> histogram -> offsets -> sorted point references (LDS atomics, HBM writes)
-//   msm_accumulate  gather + fold levels -> one XYZZ sum per bucket in `dense_out` (integer ALU)
-// The phases stress different units, so the sort of set k+1 hides behind the accumulation of set k.
-struct MsmSetPlan {
-    uint32_t P = 0, G = 1, nb = 0, L0 = 8;
-    uint32_t fold_levels = 1;  // fold levels queued before the heavy-bucket launch
-    uint64_t M = 0, bound = 0, maxseg0 = 0;
-    bool pre = false;
-    // filled in by msm_batch
-    MsmSetPin* pin = nullptr;     // this set's pinned slot
-    uint32_t* form = nullptr;     // device: digit form word per polynomial of the set (nullptr: every column plain)
-    uint32_t* counts = nullptr;   // device: reference counts in both forms, two words per polynomial
-    uint64_t elig = 0;            // bit p: polynomial p may take the offset form
-    bool force_offset = false;    // COZK_MSM_DIGIT_FORM=offset
-    bool wide = false;            // sort shape (msm_sort_wide): nothing runs beside this set's sort that could hide it
-    int wg_digits_log2 = 0;       // digits per sort workgroup of the narrow kinds (msm_sort_wgs); 0: sized like FR columns
-    uint32_t index = 0;           // position in the batch's launch order (COZK_TRACE_MSM)
-};
-
-// ---- the two rules that size a set's sort (restated in tests/test_msm_schedule_model.py)
-//
-// Shape.  The 256-thread shape exists to slip a sort under the gather kernel of the set launched before it; wide
-// workgroups wait for that gather's grid to drain and then run with the chip to themselves.  Measured in place on the
-// bench's commit at 2^20 (profiles/msm_schedule_kernel_stats_{before,after}.txt), sort of a set of 18 field-element
-// columns whose own gather lasts 22.5 ms: beside a gather the narrow sort spans 18.9 ms (0.84 of its own gather) and slows
-// that gather by ~7 %; with nothing beside it the narrow sort takes 0.86 + 4.52 ms (0.24), the wide one 0.68 + 4.13 ms
-// (0.214: the scatter is bound by its 4-byte writes to random lines, not by the shape).  With x = predecessor's
-// references / own references (a gather lasts as long as its references), the narrow shape leaves
-// (1 - x / 0.84) x 0.24 + 0.07 x of the own gather's length exposed, the wide one 0.214: they meet at x ~ 0.12.  The rule
-// takes 1/8.  The sets of one batch are equal-sized apart from a small one, so nothing in the bench sits near the threshold.
-static bool msm_sort_wide(uint64_t pred_refs, uint64_t own_refs) { return 8 * pred_refs < own_refs; }
-
-// Workgroups per polynomial.  A sort workgroup pays for 2^15 LDS counters whatever the column holds (zeroing, the sweep, one
-// global atomic per non-empty bucket).  A field-element column of 2^20 scalars gives each of its 64 workgroups 2^18 digits
-// for them (measured on such columns: 64 beats 16 workgroups 2 x; they keep one workgroup per 4096 scalars).  The other
-// kinds place 1 to 5 digits per scalar: sized by scalars a u16 column hands each workgroup 2^14 digits and issues nearly
-// one global atomic per reference, so they are sized by digits.  Measured at 2^20 beside the gather (commit per step, median
-// of three alternated runs, shape rule on): one workgroup per 4096 scalars 95.90 ms; per 2^15 digits 95.68; 2^16 94.98 and
-// 95.25 (two sessions); 2^17 95.57; 2^18 96.08; 2^20 103.97 (too few workgroups for the slots the gather leaves free, and
-// a flag column serialises on one LDS counter per workgroup).  2^16: histogram of 32 u16 columns 5.4 -> 3.6 ms.
-static constexpr int MSM_WG_DIGITS_LOG2 = 16;
-static uint32_t msm_sort_wgs(int kind, size_t max_n, int wg_digits_log2, uint32_t wgs_max) {
-    uint64_t w = kind == COZK_SCALAR_FR || wg_digits_log2 == 0 ? ((uint64_t)max_n + 4095) / 4096
-                                                               : (((uint64_t)max_n * kind_nwin(kind) + (1ull << wg_digits_log2) - 1) >> wg_digits_log2);
-    if (w < 1) w = 1;
-    return (uint32_t)(w > wgs_max ? wgs_max : w);
-}
-static const char* kind_name(int kind) {
-    static const char* const names[] = {"FR", "U8", "U16", "U32", "U64", "I64"};
-    return kind >= 0 && kind <= COZK_SCALAR_I64 ? names[kind] : "?";
-}
-
-static MsmSetPlan msm_plan(const cozk_bases* bases, const size_t* offsets, const size_t* ns, const int* kinds, size_t P) {
-    COZK_REQUIRE(P >= 1, "msm: empty batch");
-    COZK_REQUIRE((uint64_t)bases->n * (uint64_t)bases->nwin < (1ull << 31), "msm: table too large for 31-bit refs");
-    MsmSetPlan pl;
-    pl.P = (uint32_t)P;
-    pl.pre = bases->nwin == 16;
-    pl.G = pl.pre ? 1u : 16u;
-    pl.nb = (uint32_t)P * pl.G * NB;
-    for (size_t p = 0; p < P; p++) {
-        COZK_REQUIRE(offsets[p] + ns[p] <= bases->n, "msm: base slice out of range");
-        uint64_t m = (uint64_t)ns[p] * kind_nwin(kinds[p]);
-        pl.M += m;
-        if (m > pl.bound) pl.bound = m;
-    }
-    COZK_REQUIRE(pl.M < (1ull << 32), "msm: batch too large (reference count exceeds 32 bits)");
-    // segment length of level 0: aim at >= ~2^18 lanes, clamp to [8, 127] (measured: 256-long segments leave
-    // too few waves per SIMD and run the gather kernel 14 % slower)
-    uint32_t L0 = (uint32_t)(pl.M >> 18);
-    if (L0 < 8) L0 = 8;
-    if (L0 > 127) L0 = 127;  // < SEGKEYS; measured with length-ordered segments: 127 beats 64 by 2 ms per proof (fewer partial sums)
-    pl.L0 = L0;
-    pl.maxseg0 = pl.M / L0 + pl.nb;
-    // Fold levels, sized from the plan and not from the data: enough 8-long levels for the buckets of the polynomial
-    // with the most references per bucket if its digits are uniform (n nwin / 2^15 with the table, n / 2^15 per window
-    // group without; + 25 % and one segment for the Poisson spread: 2^20 field elements give 512 per bucket, 5 segments
-    // of <= 127, one level; 2^22 give 2048, 17 segments, two levels; 2^24 three).  Buckets that are fuller than that
-    // (flag columns, carry digits, skewed scalars) are left to k_msm_fold_heavy.
-    uint64_t per = 0;
-    for (size_t p = 0; p < P; p++) {
-        uint64_t m = ((uint64_t)ns[p] * (pl.pre ? kind_nwin(kinds[p]) : 1) + NB - 1) / NB;
-        if (m > per) per = m;
-    }
-    uint64_t segs = (per * 5 + 4 * L0 - 1) / (4 * L0) + 1;
-    pl.fold_levels = 1;
-    while ((segs = (segs + 7) / 8) > 1) pl.fold_levels++;
-    return pl;
-}
-
-static void msm_scan(hipStream_t st, uint32_t* bsums, uint32_t nb, bool from_offsets, const uint32_t* in, uint32_t L, uint32_t* off, uint32_t* cursor,
+template <bool FROM_OFFSETS>
+static void msm_scan(hipStream_t st, uint32_t* bsums, uint32_t nb, const uint32_t* in, uint32_t L, uint32_t* off, uint32_t* cursor,
                      const uint32_t* perm = nullptr) {
     const uint32_t nscan_blocks = (nb + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK;
-    if (from_offsets) {
-        k_scan_sums<true><<<nscan_blocks, 256, 0, st>>>(in, nb, L, bsums, perm);
-        k_scan_top<<<1, 1024, 0, st>>>(bsums, nscan_blocks, off + nb);
-        k_scan_final<true><<<nscan_blocks, 256, 0, st>>>(in, nb, L, bsums, off, cursor, perm);
-    } else {
-        k_scan_sums<false><<<nscan_blocks, 256, 0, st>>>(in, nb, L, bsums, nullptr);
-        k_scan_top<<<1, 1024, 0, st>>>(bsums, nscan_blocks, off + nb);
-        k_scan_final<false><<<nscan_blocks, 256, 0, st>>>(in, nb, L, bsums, off, cursor, nullptr);
-    }
+    k_scan_sums<FROM_OFFSETS><<<nscan_blocks, 256, 0, st>>>(in, nb, L, bsums, perm);
+    k_scan_top<<<1, 1024, 0, st>>>(bsums, nscan_blocks, off + nb);
+    k_scan_final<FROM_OFFSETS><<<nscan_blocks, 256, 0, st>>>(in, nb, L, bsums, off, cursor, perm);
 }
 
-// sort phase on stream `st` into the sort workspace `sw`
-static void msm_sort(cozk_ctx* ctx, hipStream_t st, MsmSortWs& sw, const MsmSetPlan& pl, const cozk_bases* bases, const size_t* offsets,
-                     const size_t* ns, const void* const* scalars, const int* kinds) {
-    const uint32_t nb = pl.nb, G = pl.G;
-    const size_t P = pl.P;
+// sort phase of set `s` on stream `st` into the sort workspace `sw`; offsets / ns / scalars / kinds are the batch's arrays.  pin: the
+// set's pinned slot; form, counts: device, the digit form word and the reference counts in both forms (two words) per polynomial of the
+// set (nullptr: every column plain)
+static void msm_sort(cozk_ctx* ctx, hipStream_t st, MsmSortWs& sw, const MsmSetSchedule& s, MsmSetPin* pin, uint32_t* form, uint32_t* counts,
+                     const cozk_bases* bases, const size_t* offsets, const size_t* ns, const void* const* scalars, const int* kinds) {
+    const uint32_t nb = s.nb, G = s.G;
+    const size_t P = s.P;
+    offsets += s.first, ns += s.first, scalars += s.first, kinds += s.first;
     sw.hist.reserve((size_t)(nb + 3) * 4);
     sw.off0.reserve((size_t)(nb + 1) * 4);
     sw.offA.reserve((size_t)(nb + 1) * 4);
-    sw.refs.reserve((size_t)pl.M * 4);
+    sw.refs.reserve((size_t)s.M * 4);
     uint32_t* hist = sw.hist.as<uint32_t>();
     uint32_t* off0 = sw.off0.as<uint32_t>();
     uint32_t* refs = sw.refs.as<uint32_t>();
@@ -964,79 +852,42 @@ static void msm_sort(cozk_ctx* ctx, hipStream_t st, MsmSortWs& sw, const MsmSetP
     auto fullest_bucket = [&] { k_max_u32<<<std::min<uint32_t>(cdiv(nb, 256), 1024u), 256, 0, st>>>(hist, nb, d_stats); };
     auto read_back_stats = [&] {
         k_msm_set_total<<<1, 1, 0, st>>>(off0 + nb, d_stats);
-        HIP_TRY(hipMemcpyAsync(&pl.pin->fullest, d_stats, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&pin->fullest, d_stats, 8, hipMemcpyDeviceToHost, st));
     };
-    if (pl.pre) {
-        // LDS-privatised counting sort: one launch per scalar kind, grid = (workgroups per polynomial, polynomials).
-        // The descriptors travel through pinned memory owned by the workspace (no host sync here).
-        MsmPolyDesc* h_descs = pl.pin->descs;
-        COZK_REQUIRE(P <= 64, "msm: too many polynomials in one launch set");
+    if (s.table) {
+        // LDS-privatised counting sort: one launch per kind run (msm_set_sort_shape).  The descriptors travel through pinned
+        // memory owned by the workspace (no host sync here).
+        MsmPolyDesc* h_descs = pin->descs;
         uint32_t nd = 0;
-        struct KindRun { int kind; uint32_t first, count; size_t max_n; uint32_t wgs; };  // descriptors [first, first + count)
-        std::vector<KindRun> runs;
-        size_t max_n = 0;
-        for (int kind = 0; kind <= COZK_SCALAR_I64; kind++) {
-            KindRun r{kind, nd, 0, 0, 0};
-            for (size_t p = 0; p < P; p++)
-                if (kinds[p] == kind && ns[p]) {
-                    h_descs[nd++] = MsmPolyDesc{scalars[p], (uint32_t)ns[p], (uint32_t)offsets[p], (uint32_t)p, 0};
-                    if (ns[p] > r.max_n) r.max_n = ns[p];
-                }
-            r.count = nd - r.first;
-            if (r.max_n > max_n) max_n = r.max_n;
-            if (r.count) runs.push_back(r);
-        }
+        for (const auto& r : s.runs)
+            for (uint32_t p : r.cols) h_descs[nd++] = MsmPolyDesc{scalars[p], (uint32_t)ns[p], (uint32_t)offsets[p], p, 0};
         HIP_TRY(hipMemcpyAsync(d_descs, h_descs, nd * sizeof(MsmPolyDesc), hipMemcpyHostToDevice, st));
-        // 256-thread workgroups (one wave per SIMD, 128 KiB of LDS each): narrow enough to slip into the CU slots that free
-        // up under the register-heavy gather kernel of the previous launch set, so the sort really runs beside it (wider
-        // workgroups wait for the gather's grid to drain: measured 127.8 -> 123.5 ms per proof at 2^20, same box).
-        // A set whose predecessor cannot hide its sort (msm_sort_wide: the first of a batch, a single set, serial batches,
-        // a set behind a much smaller one) takes the wide shape instead (measured at 2^20: 1024 x 64, 1024 x 32, 1024 x 16,
-        // 512 x 64 and 512 x 32 all within 0.2 ms of each other): COZK_MSM_LTPB / COZK_MSM_WGS override both shapes.
-        static const int ltpb_env = getenv("COZK_MSM_LTPB") ? atoi(getenv("COZK_MSM_LTPB")) : 0;
-        static const int wgs_env = getenv("COZK_MSM_WGS") ? atoi(getenv("COZK_MSM_WGS")) : 0;
-        const int ltpb = ltpb_env ? ltpb_env : (pl.wide ? MSM_WIDE_LTPB : 256);
-        const uint32_t wgs_max = (uint32_t)(wgs_env ? wgs_env : (pl.wide ? MSM_WIDE_WGS : 64));
-        COZK_REQUIRE(ltpb >= 64 && ltpb <= LTPB && ltpb % 64 == 0, "COZK_MSM_LTPB out of range");
-        COZK_REQUIRE(wgs_max >= 1 && wgs_max <= 1024, "COZK_MSM_WGS out of range (1..1024)");
-        for (auto& r : runs) r.wgs = msm_sort_wgs(r.kind, r.max_n, pl.wg_digits_log2, wgs_max);
-        // COZK_TRACE_MSM=1: one line per launch set on stderr -- index, polynomials, references, shape, then kind:columns:workgroups
-        static const bool trace = getenv("COZK_TRACE_MSM") != nullptr;
-        if (trace) {
-            std::string line;
-            for (auto& r : runs) line += " " + std::string(kind_name(r.kind)) + ":" + std::to_string(r.count) + ":" + std::to_string(r.wgs);
-            fprintf(stderr, "cozk msm set %u: polys %u refs %llu shape %s %dx%u kinds%s\n", pl.index, pl.P, (unsigned long long)pl.M,
-                    pl.wide ? "wide" : "narrow", ltpb, wgs_max, line.c_str());
-        }
         // digit form of the U16 / U32 / U64 columns: count both forms (one extra read of those columns), offset where it
         // places strictly fewer references; forced offset needs no count.  Plain leaves the zeroed words alone.
-        if (pl.elig) {
-            if (!pl.force_offset)
-                for (auto& r : runs)
+        if (s.elig) {
+            if (!s.force_offset)
+                for (const auto& r : s.runs)
                     if (kind_offset_slot(r.kind) >= 0) {
-                        dim3 grid(std::min<uint32_t>(cdiv(max_n, 4096), 64u), r.count);
-                        KIND_DISPATCH(r.kind, (k_msm_form_count<K><<<grid, 256, 0, st>>>(d_descs + r.first, pl.counts)));
+                        dim3 grid(r.form_grid, (uint32_t)r.cols.size());
+                        KIND_DISPATCH(r.kind, (k_msm_form_count<K><<<grid, 256, 0, st>>>(d_descs + r.first, counts)));
                     }
-            k_msm_form_pick<<<1, 64, 0, st>>>(pl.counts, pl.form, pl.P, pl.elig, pl.force_offset ? 1 : 0);
+            k_msm_form_pick<<<1, 64, 0, st>>>(counts, form, s.P, s.elig, s.force_offset ? 1 : 0);
         }
-        for (auto& r : runs) {
-            dim3 grid(r.wgs, r.count);
-            KIND_DISPATCH(r.kind, (k_msm_hist_lds<K><<<grid, ltpb, 0, st>>>(d_descs + r.first, hist, pl.form)));
+        for (const auto& r : s.runs) {
+            dim3 grid(r.wgs, (uint32_t)r.cols.size());
+            KIND_DISPATCH(r.kind, (k_msm_hist_lds<K><<<grid, s.ltpb, 0, st>>>(d_descs + r.first, hist, form)));
         }
         fullest_bucket();
-        msm_scan(st, bsums, nb, false, hist, 1, off0, hist);  // hist doubles as the scatter cursor after the scan
+        msm_scan<false>(st, bsums, nb, hist, 1, off0, hist);  // hist doubles as the scatter cursor after the scan
         read_back_stats();
-        for (auto& r : runs) {
-            dim3 grid(r.wgs, r.count);
+        for (const auto& r : s.runs) {
+            dim3 grid(r.wgs, (uint32_t)r.cols.size());
             // algorithmic bytes of the placement: every scalar read once + one 4-byte reference written per 16-bit window
             uint64_t alg = 0;
-            for (uint32_t q = 0; q < r.count; q++) {
-                const MsmPolyDesc& d = h_descs[r.first + q];
-                const uint64_t sb = scalar_kind_bytes(r.kind);
-                alg += (uint64_t)d.n * (sb + 4ull * ((sb * 8 + 15) / 16));
-            }
+            const uint64_t sb = scalar_kind_bytes(r.kind);
+            for (uint32_t p : r.cols) alg += (uint64_t)ns[p] * (sb + 4ull * ((sb * 8 + 15) / 16));
             ProfScope prof(ctx, COZK_PROF_MSM_SCATTER, alg, st);
-            KIND_DISPATCH(r.kind, (k_msm_scatter_lds<K><<<grid, ltpb, 0, st>>>(d_descs + r.first, hist, refs, (uint32_t)bases->n, pl.form)));
+            KIND_DISPATCH(r.kind, (k_msm_scatter_lds<K><<<grid, s.ltpb, 0, st>>>(d_descs + r.first, hist, refs, (uint32_t)bases->n, form)));
         }
     } else {
         for (size_t p = 0; p < P; p++) {
@@ -1044,7 +895,7 @@ static void msm_sort(cozk_ctx* ctx, hipStream_t st, MsmSortWs& sw, const MsmSetP
             if (ns[p]) KIND_DISPATCH(kinds[p], (k_msm_hist<K><<<cdiv(ns[p], TPB), TPB, 0, st>>>(scalars[p], ns[p], h, 1)));
         }
         fullest_bucket();
-        msm_scan(st, bsums, nb, false, hist, 1, off0, hist);
+        msm_scan<false>(st, bsums, nb, hist, 1, off0, hist);
         read_back_stats();
         for (size_t p = 0; p < P; p++) {
             uint32_t* cur = hist + (size_t)p * G * NB;
@@ -1053,27 +904,25 @@ static void msm_sort(cozk_ctx* ctx, hipStream_t st, MsmSortWs& sw, const MsmSetP
                                                                                          (uint32_t)offsets[p])));
         }
     }
-    msm_scan(st, bsums, nb, true, off0, pl.L0, sw.offA.as<uint32_t>(), nullptr);  // level-0 segment offsets
+    msm_scan<true>(st, bsums, nb, off0, s.L0, sw.offA.as<uint32_t>(), nullptr);  // level-0 segment offsets
     HIP_TRY(hipGetLastError());
 }
 
-// accumulate phase on the context's stream; reads the sort workspace `sw` (its producer must have been waited for)
-static void msm_accumulate(cozk_ctx* ctx, MsmSortWs& sw, const MsmSetPlan& pl, const cozk_bases* bases, const size_t* ns, const int* kinds,
+// accumulate phase of set `s` on the context's stream; reads the sort workspace `sw` (its producer must have been waited for)
+static void msm_accumulate(cozk_ctx* ctx, MsmSortWs& sw, const MsmSetSchedule& s, const cozk_bases* bases, const size_t* ns, const int* kinds,
                            g1_xyzz* dense_out) {
     MsmWorkspace& ws = ctx->msm_ws;
     hipStream_t st = ctx->stream;
-    const uint32_t nb = pl.nb, L0 = pl.L0;
+    const uint32_t nb = s.nb, L0 = s.L0;
     // Upper levels fold <= L1 partial sums per lane; the chain is serial (a full XYZZ addition per step), so it is kept
-    // short.  pl.fold_levels of them (msm_plan: what uniform digits need, one at 2^20) finish every ordinary bucket.
+    // short.  s.fold_levels of them (msm_set_counts: what uniform digits need, one at 2^20) finish every ordinary bucket.
     // Whatever still holds more than one partial sum after them -- the one bucket of a 0/1 flag column, a plain u16 /
     // u32 column's carry digit -- is finished by k_msm_fold_heavy in one launch.  The schedule does not depend on the
     // data, so the host never waits for the histogram in the middle of a set.
     const uint32_t L1 = 8;
-    const uint64_t maxseg0 = pl.maxseg0;
-    // segment counts obey x_{k+1} = x_k / L1 + nb <= max(x_0, 2 nb): size both ping-pong buffers for that
-    const uint64_t maxpart = maxseg0 > 2ull * nb ? maxseg0 : 2ull * nb;
-    ws.partA.reserve((size_t)maxpart * sizeof(g1_xyzz));
-    ws.partB.reserve((size_t)maxpart * sizeof(g1_xyzz));
+    const uint64_t maxseg0 = s.maxseg0;
+    ws.partA.reserve((size_t)s.part_entries * sizeof(g1_xyzz));
+    ws.partB.reserve((size_t)s.part_entries * sizeof(g1_xyzz));
     ws.offB.reserve((size_t)(nb + 1) * 4);
     ws.offC.reserve((size_t)(nb + 1) * 4);
     ws.heavy.reserve((size_t)(nb + 1) * 4);
@@ -1087,10 +936,10 @@ static void msm_accumulate(cozk_ctx* ctx, MsmSortWs& sw, const MsmSetPlan& pl, c
         HIP_TRY(hipEventCreate(&e1));
         HIP_TRY(hipEventRecord(e0, st));
     }
-    ws.blk.reserve((size_t)(cdiv(maxpart, TPB) + 2) * 4);
+    ws.blk.reserve((size_t)s.blk_entries * 4);
     uint32_t* blk = ws.blk.as<uint32_t>();
-    if (pl.pre) {
-        ws.exc.reserve((size_t)(maxseg0 + 2) * 4);
+    if (s.table) {
+        ws.exc.reserve((size_t)s.exc_entries * 4);
         uint32_t* exc = ws.exc.as<uint32_t>();
         HIP_TRY(hipMemsetAsync(exc, 0, 4, st));
         // walk the buckets in order of their segment length (see "segments in order of their length")
@@ -1103,7 +952,7 @@ static void msm_accumulate(cozk_ctx* ctx, MsmSortWs& sw, const MsmSetPlan& pl, c
         k_seg_hist<<<cdiv(nb, 1024), 1024, 0, st>>>(off0, offA, nb, bins);
         k_seg_bins<<<1, 1, 0, st>>>(bins);
         k_seg_perm<<<cdiv(nb, 1024), 1024, 0, st>>>(off0, offA, nb, bins, perm);
-        msm_scan(st, ws.ptrs.as<uint32_t>(), nb, true, offA, 1, offP, nullptr, perm);  // segment offsets in walking order
+        msm_scan<true>(st, ws.ptrs.as<uint32_t>(), nb, offA, 1, offP, nullptr, perm);  // segment offsets in walking order
         const uint32_t nblk0 = cdiv(maxseg0, TPB);
         k_block_buckets<<<cdiv(nblk0 + 1, 256), 256, 0, st>>>(offP, nb, nblk0, blk);
         if (bases->has_inf)
@@ -1119,7 +968,7 @@ static void msm_accumulate(cozk_ctx* ctx, MsmSortWs& sw, const MsmSetPlan& pl, c
         ctx->prof_events.push_back({e0, e1});
         ctx->prof_launches += 1;
         // prof_units (point additions) takes the set's real reference total once msm_batch has it
-        for (size_t p = 0; p < pl.P; p++) ctx->prof_alg_bytes += (uint64_t)ns[p] * (64 + scalar_kind_bytes(kinds[p]));
+        for (size_t p = s.first; p < s.first + s.P; p++) ctx->prof_alg_bytes += (uint64_t)ns[p] * (64 + scalar_kind_bytes(kinds[p]));
     }
     uint32_t* heavy = ws.heavy.as<uint32_t>();
     HIP_TRY(hipMemsetAsync(heavy, 0, 4, st));
@@ -1130,9 +979,9 @@ static void msm_accumulate(cozk_ctx* ctx, MsmSortWs& sw, const MsmSetPlan& pl, c
     uint32_t* cur_off = offA;
     uint32_t* nxt_off = ws.offB.as<uint32_t>();
     uint32_t* spare_off = ws.offC.as<uint32_t>();
-    for (uint32_t level = 0; level < pl.fold_levels; level++) {
+    for (uint32_t level = 0; level < s.fold_levels; level++) {
         uint64_t nseg = maxseg / L1 + nb;
-        msm_scan(st, ws.ptrs.as<uint32_t>(), nb, true, cur_off, L1, nxt_off, nullptr);
+        msm_scan<true>(st, ws.ptrs.as<uint32_t>(), nb, cur_off, L1, nxt_off, nullptr);
         const uint32_t nblkN = cdiv(nseg, TPB);
         k_block_buckets<<<cdiv(nblkN + 1, 256), 256, 0, st>>>(nxt_off, nb, nblkN, blk);
         k_msm_accumN<<<nblkN, TPB, 0, st>>>(cur_items, cur_off, nxt_off, nb, L1, nxt_items, blk);
@@ -1172,33 +1021,6 @@ static g1_affine abi_to_affine(const uint64_t xy[8], int inf) {
 
 void msm_batch(cozk_ctx* ctx, const cozk_bases* bases, const size_t* offsets, const size_t* ns, const void* const* scalars,
                const int* kinds, size_t k, uint64_t* out_xy, int* out_inf);
-
-// COZK_MSM_DIGIT_FORM = auto (default) | plain | offset; read at every call so that one process can compare the forms
-enum { MSM_FORM_AUTO = 0, MSM_FORM_PLAIN = 1, MSM_FORM_OFFSET = 2 };
-static int msm_digit_form_mode() {
-    const char* e = getenv("COZK_MSM_DIGIT_FORM");
-    if (!e || !*e || !strcmp(e, "auto")) return MSM_FORM_AUTO;
-    if (!strcmp(e, "plain")) return MSM_FORM_PLAIN;
-    if (!strcmp(e, "offset")) return MSM_FORM_OFFSET;
-    throw CozkError(COZK_ERR_INVALID_ARG, "COZK_MSM_DIGIT_FORM must be auto, plain or offset");
-}
-
-// A/B switches of the launch schedule, read at every call like the digit form; none of them changes a result.
-//   COZK_MSM_SHAPE_RULE=0      sort shape as before msm_sort_wide: wide for the first set of a batch and serial batches only
-//   COZK_MSM_WG_DIGITS_LOG2=d  digits per sort workgroup of the narrow kinds (10..24); 0: one workgroup per 4096 scalars
-struct MsmSchedule {
-    bool shape_rule = true;
-    int wg_digits_log2 = MSM_WG_DIGITS_LOG2;
-};
-static MsmSchedule msm_schedule_env() {
-    MsmSchedule s;
-    if (const char* e = getenv("COZK_MSM_SHAPE_RULE")) s.shape_rule = atoi(e) != 0;
-    if (const char* e = getenv("COZK_MSM_WG_DIGITS_LOG2")) {
-        s.wg_digits_log2 = atoi(e);
-        COZK_REQUIRE(s.wg_digits_log2 == 0 || (s.wg_digits_log2 >= 10 && s.wg_digits_log2 <= 24), "COZK_MSM_WG_DIGITS_LOG2 must be 0 or 10..24");
-    }
-    return s;
-}
 
 // c S for the slice [off, off + n) of `bases` and the three kinds with an offset form (kind_offset_slot), from the
 // handle's cache.  The first request computes S with the MSM itself on a constant all-ones U8 column (always plain, so
@@ -1250,36 +1072,29 @@ static cozk_bases::SliceSum msm_slice_sum(cozk_ctx* ctx, const cozk_bases* bases
     return e;
 }
 
-// k MSMs with per-polynomial base slices; launch sets are cut so that one set holds at most 2^28 .. 2^30 point
-// references (1 GiB of refs) and at most 64 (window table) / 4 (16 window groups) polynomials
+// k MSMs with per-polynomial base slices.  Everything that is decided about the launches is decided by msm_schedule()
+// (host/msm_schedule.hpp) before the first of them: a batch it refuses has enqueued and reserved nothing.
 void msm_batch(cozk_ctx* ctx, const cozk_bases* bases, const size_t* offsets, const size_t* ns, const void* const* scalars,
                const int* kinds, size_t k, uint64_t* out_xy, int* out_inf) {
     MsmWorkspace& ws = ctx->msm_ws;
     hipStream_t st = ctx->stream;
     const uint32_t G = bases->nwin == 16 ? 1u : 16u;
-    const size_t maxP = bases->nwin == 16 ? 64 : 4;  // measured: 64 small-scalar polynomials per set beat 16 by 1.7 ms per proof
-    // the bucket-reduction tail (running sums, Horner, to-affine) is latency-bound, so it runs ONCE over
-    // the dense bucket sums of up to `tail_cap` polynomials instead of once per launch set
-    const size_t tail_cap = 256 / G;
+    const MsmOptions opt = msm_options_env();
     // digit forms: which columns may take the offset form, and their corrections c S (computed here, before this
     // batch touches the workspace, because the first use of a slice runs an MSM of its own)
-    const int form_mode = msm_digit_form_mode();
-    const MsmSchedule sched = msm_schedule_env();
     std::vector<uint8_t> elig(k, 0);
     std::vector<g1_affine> corr_h;
     bool any_elig = false;
-    if (G == 1 && form_mode != MSM_FORM_PLAIN) {
-        for (size_t p = 0; p < k; p++) {
-            const int slot = kind_offset_slot(kinds[p]);
-            if (slot < 0 || ns[p] == 0) continue;
-            COZK_REQUIRE(offsets[p] + ns[p] <= bases->n, "msm: base slice out of range");
-            if (!any_elig) corr_h.assign(k, g1_affine{Fq::zero(), Fq::zero()});
-            any_elig = true;
-            elig[p] = 1;
-            if (p > 0 && elig[p - 1] && kinds[p - 1] == kinds[p] && offsets[p - 1] == offsets[p] && ns[p - 1] == ns[p]) corr_h[p] = corr_h[p - 1];
-            else corr_h[p] = msm_slice_sum(ctx, bases, offsets[p], ns[p]).cS[slot];
-        }
+    for (size_t p = 0; p < k; p++) {
+        if (!msm_column_eligible(bases->nwin, opt, kinds[p], ns[p])) continue;
+        COZK_REQUIRE(offsets[p] + ns[p] <= bases->n, "msm: base slice out of range");
+        if (!any_elig) corr_h.assign(k, g1_affine{Fq::zero(), Fq::zero()});
+        any_elig = true;
+        elig[p] = 1;
+        if (p > 0 && elig[p - 1] && kinds[p - 1] == kinds[p] && offsets[p - 1] == offsets[p] && ns[p - 1] == ns[p]) corr_h[p] = corr_h[p - 1];
+        else corr_h[p] = msm_slice_sum(ctx, bases, offsets[p], ns[p]).cS[kind_offset_slot(kinds[p])];
     }
+    const MsmBatchSchedule sched = msm_schedule(bases->nwin, bases->n, offsets, ns, kinds, k, elig.data(), opt);
     ws.out.reserve(k * sizeof(g1_affine));
     g1_affine* d_out = ws.out.as<g1_affine>();
     // pinned staging: one slot per launch set (at most k sets), then k corrections.  Every earlier batch ended with a
@@ -1309,66 +1124,17 @@ void msm_batch(cozk_ctx* ctx, const cozk_bases* bases, const size_t* offsets, co
         memcpy(pc, corr_h.data(), k * sizeof(g1_affine));
         HIP_TRY(hipMemcpyAsync(d_corr, pc, k * sizeof(g1_affine), hipMemcpyHostToDevice, st));
     }
-    for (size_t t0 = 0; t0 < k; t0 += tail_cap) {
-        size_t kt = k - t0 < tail_cap ? k - t0 : tail_cap;
-        const uint32_t ngroups = (uint32_t)kt * G;
+    for (const MsmTailBlock& blk : sched.blocks) {
+        const size_t t0 = blk.first, kt = blk.count;
+        const uint32_t ngroups = blk.ngroups;
+        const std::vector<MsmSetSchedule>& sets = blk.sets;
         ws.bsum.reserve((size_t)ngroups * NB * sizeof(g1_xyzz));
         ws.chunk.reserve((size_t)ngroups * (NB / CH) * sizeof(g1_xyzz));
         ws.grp.reserve((size_t)ngroups * sizeof(g1_xyzz));
         g1_xyzz* dense = ws.bsum.as<g1_xyzz>();
-        // cut the launch sets, then pipeline: sort(k + 1) on the side stream while accumulate(k) runs on the main one
-        struct SetRange { size_t s, P; };
-        std::vector<SetRange> sets;
-        // References per launch set: a quarter of the batch, so that the sort of set k + 1 still hides behind the accumulation of set
-        // k, within [2^28, 2^30] (the two sort workspaces hold 4 bytes per reference).  Measured: at 2^22 coefficients 2^30 beats 2^28
-        // by 7 % of the commit (4 instead of 16 polynomials per set paid the per-set scans and the host's wait for the fullest bucket
-        // 4 x as often); at 2^20 one 2^30 set would hold all 64 field-element polynomials and lose the overlap (+4 %).
-        // COZK_MSM_SET_REFS_LOG2 (12..31) pins the cap for A/B runs and lets a test cut a small batch into many sets; like the
-        // schedule switches (msm_schedule_env) it is read at every call.
-        uint64_t set_refs_cap;
-        {
-            const int pinned = getenv("COZK_MSM_SET_REFS_LOG2") ? atoi(getenv("COZK_MSM_SET_REFS_LOG2")) : 0;
-            if (pinned) set_refs_cap = 1ull << (pinned < 12 ? 12 : (pinned > 31 ? 31 : pinned));
-            else {
-                uint64_t total = 0;
-                for (size_t p = 0; p < kt; p++) total += (uint64_t)ns[t0 + p] * kind_nwin(kinds[t0 + p]);
-                set_refs_cap = total / 4;
-                if (set_refs_cap < (1ull << 28)) set_refs_cap = 1ull << 28;
-                if (set_refs_cap > (1ull << 30)) set_refs_cap = 1ull << 30;
-            }
-        }
-        {
-            size_t s = 0;
-            while (s < kt) {
-                size_t P = 0;
-                uint64_t M = 0;
-                while (s + P < kt && P < maxP) {
-                    uint64_t m = (uint64_t)ns[t0 + s + P] * kind_nwin(kinds[t0 + s + P]);
-                    if (P > 0 && M + m > set_refs_cap) break;
-                    M += m;
-                    P++;
-                }
-                sets.push_back({s, P});
-                s += P;
-            }
-        }
-        // the first set's sort has nothing to hide behind: start with the cheapest one (fewest references)
-        if (sets.size() > 2) {
-            size_t best = 0;
-            uint64_t best_m = ~0ull;
-            for (size_t i = 0; i < sets.size(); i++) {
-                uint64_t m = 0;
-                for (size_t p = 0; p < sets[i].P; p++) m += (uint64_t)ns[t0 + sets[i].s + p] * kind_nwin(kinds[t0 + sets[i].s + p]);
-                if (m < best_m) {
-                    best_m = m;
-                    best = i;
-                }
-            }
-            std::rotate(sets.begin(), sets.begin() + best, sets.begin() + best + 1);
-        }
-        static const bool pipeline = getenv("COZK_MSM_SERIAL") == nullptr;
+        // pipeline: sort(k + 1) on the side stream while accumulate(k) runs on the main one
         hipStream_t side = st;
-        if (pipeline && sets.size() > 1) {
+        if (blk.pipelined) {
             if (!ctx->stream2) {
                 // the sort stream outranks the main stream: its memory-bound workgroups take the CU slots that free up
                 // under the ALU-bound gather kernel instead of queueing behind that kernel's own next workgroups
@@ -1391,44 +1157,33 @@ void msm_batch(cozk_ctx* ctx, const cozk_bases* bases, const size_t* offsets, co
             HIP_TRY(hipEventRecord(ws.fork, st));
             HIP_TRY(hipStreamWaitEvent(side, ws.fork, 0));
         }
-        std::vector<MsmSetPlan> plans(sets.size());
         auto launch_sort = [&](size_t i) {
-            const SetRange& r = sets[i];
-            plans[i] = msm_plan(bases, offsets + t0 + r.s, ns + t0 + r.s, kinds + t0 + r.s, r.P);
-            if (plans[i].M == 0) return;
-            MsmSetPlan& pl = plans[i];
-            pl.pin = pins + pins_used++;
-            pl.pin->fullest = 0;
-            pl.pin->total = 0;
-            pin_bound.push_back(pl.bound);
-            pl.form = any_elig ? d_form + t0 + r.s : nullptr;
-            pl.counts = any_elig ? d_counts + 2 * (t0 + r.s) : nullptr;
-            for (size_t p = 0; p < r.P; p++)
-                if (elig[t0 + r.s + p]) pl.elig |= 1ull << p;
-            pl.force_offset = form_mode == MSM_FORM_OFFSET;
-            // what the sort runs beside: the accumulation of the set launched before it (none for the first set of a tail
-            // block, whose sort waits for everything queued so far, and in a serial batch)
-            const uint64_t pred_refs = i > 0 && side != st ? plans[i - 1].M : 0;
-            pl.wide = sched.shape_rule ? msm_sort_wide(pred_refs, pl.M) : (i == 0 && t0 == 0) || side == st;
-            pl.wg_digits_log2 = sched.wg_digits_log2;
-            pl.index = (uint32_t)i;
-            MsmSortWs& sw = ws.sort[i & 1];
+            const MsmSetSchedule& s = sets[i];
+            if (s.M == 0) return;
+            MsmSetPin* pin = pins + pins_used++;
+            pin->fullest = 0;
+            pin->total = 0;
+            pin_bound.push_back(s.bound);
+            uint32_t* form = any_elig ? d_form + s.first : nullptr;
+            uint32_t* counts = any_elig ? d_counts + 2 * s.first : nullptr;
+            if (opt.trace && s.table) fprintf(stderr, "%s\n", msm_set_trace_line(s).c_str());
+            MsmSortWs& sw = ws.sort[s.ws];
             if (i >= 2 && side != st) HIP_TRY(hipStreamWaitEvent(side, sw.consumed, 0));  // its previous user has finished reading it
-            msm_sort(ctx, side, sw, plans[i], bases, offsets + t0 + r.s, ns + t0 + r.s, scalars + t0 + r.s, kinds + t0 + r.s);
+            msm_sort(ctx, side, sw, s, pin, form, counts, bases, offsets, ns, scalars, kinds);
             if (side != st) HIP_TRY(hipEventRecord(sw.done, side));
         };
         if (!sets.empty()) launch_sort(0);
         for (size_t i = 0; i < sets.size(); i++) {
             if (side != st && i + 1 < sets.size()) launch_sort(i + 1);
-            const SetRange& r = sets[i];
-            g1_xyzz* out_i = dense + (size_t)r.s * G * NB;
-            if (plans[i].M != 0) {
-                MsmSortWs& sw = ws.sort[i & 1];
+            const MsmSetSchedule& s = sets[i];
+            g1_xyzz* out_i = dense + (size_t)(s.first - t0) * G * NB;
+            if (s.M != 0) {
+                MsmSortWs& sw = ws.sort[s.ws];
                 if (side != st) HIP_TRY(hipStreamWaitEvent(st, sw.done, 0));
-                msm_accumulate(ctx, sw, plans[i], bases, ns + t0 + r.s, kinds + t0 + r.s, out_i);
+                msm_accumulate(ctx, sw, s, bases, ns, kinds, out_i);
                 if (side != st) HIP_TRY(hipEventRecord(sw.consumed, st));
             } else {
-                HIP_TRY(hipMemsetAsync(out_i, 0, (size_t)plans[i].nb * sizeof(g1_xyzz), st));  // all buckets = identity (zz = 0)
+                HIP_TRY(hipMemsetAsync(out_i, 0, (size_t)s.nb * sizeof(g1_xyzz), st));  // all buckets = identity (zz = 0)
             }
             if (side == st && i + 1 < sets.size()) launch_sort(i + 1);
         }
@@ -1449,6 +1204,25 @@ void msm_batch(cozk_ctx* ctx, const cozk_bases* bases, const size_t* offsets, co
     for (size_t i = 0; i < k; i++) affine_to_abi(h[i], out_xy + 8 * i, out_inf ? out_inf + i : nullptr);
 }
 
+// A new handle over n points: `fill(points)` puts the points themselves (window 0) there on the context's stream, the other
+// windows follow from them.  Nothing is left behind when a step throws.
+template <class Fill>
+static cozk_bases* bases_create(cozk_ctx* ctx, size_t n, int precompute, Fill&& fill) {
+    cozk_bases* b = new cozk_bases{ctx, n, precompute ? 16 : 1, nullptr};
+    try {
+        HIP_TRY(hipMalloc((void**)&b->table, (size_t)b->nwin * n * sizeof(g1_affine)));
+        fill(b->table);
+        HIP_TRY(hipGetLastError());
+        build_window_table(ctx, b);
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    } catch (...) {
+        if (b->table) (void)hipFree(b->table);
+        delete b;
+        throw;
+    }
+    return b;
+}
+
 // ------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -1456,62 +1230,31 @@ int cozk_bases_upload(cozk_ctx* ctx, const uint64_t* xy, const uint8_t* infinity
                       cozk_bases** out) {
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(ctx && xy && out && n > 0, "bases_upload: bad argument");
-        cozk_bases* b = new cozk_bases{ctx, n, precompute ? 16 : 1, nullptr};
-        try {
-            HIP_TRY(hipMalloc((void**)&b->table, (size_t)b->nwin * n * sizeof(g1_affine)));
+        *out = bases_create(ctx, n, precompute, [&](g1_affine* points) {
             std::vector<g1_affine> h(n);
             for (size_t i = 0; i < n; i++) h[i] = abi_to_affine(xy + 8 * i, infinity ? infinity[i] : 0);
-            HIP_TRY(hipMemcpyAsync(b->table, h.data(), n * sizeof(g1_affine), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(points, h.data(), n * sizeof(g1_affine), hipMemcpyHostToDevice, ctx->stream));
             HIP_TRY(hipStreamSynchronize(ctx->stream));
-            build_window_table(ctx, b);
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-        } catch (...) {
-            if (b->table) (void)hipFree(b->table);
-            delete b;
-            throw;
-        }
-        *out = b;
+        });
     });
 }
 
 int cozk_bases_from_scalars(cozk_ctx* ctx, const cozk_vec* s, const uint64_t* g_xy, int precompute, cozk_bases** out) {
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(ctx && s && g_xy && out && s->kind == COZK_SCALAR_FR && s->n > 0, "bases_from_scalars: bad argument");
-        size_t n = s->n;
-        cozk_bases* b = new cozk_bases{ctx, n, precompute ? 16 : 1, nullptr};
-        try {
-            HIP_TRY(hipMalloc((void**)&b->table, (size_t)b->nwin * n * sizeof(g1_affine)));
-            g1_affine g = abi_to_affine(g_xy, 0);
-            k_fixed_base_mul<<<cdiv(n, TPB), TPB, 0, ctx->stream>>>(reinterpret_cast<const fe*>(s->d), g, b->table, n);
-            HIP_TRY(hipGetLastError());
-            build_window_table(ctx, b);
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-        } catch (...) {
-            if (b->table) (void)hipFree(b->table);
-            delete b;
-            throw;
-        }
-        *out = b;
+        const size_t n = s->n;
+        const g1_affine g = abi_to_affine(g_xy, 0);
+        *out = bases_create(ctx, n, precompute, [&](g1_affine* points) {
+            k_fixed_base_mul<<<cdiv(n, TPB), TPB, 0, ctx->stream>>>(reinterpret_cast<const fe*>(s->d), g, points, n);
+        });
     });
 }
 
 int cozk_bases_pair_sums(cozk_ctx* ctx, const cozk_bases* src, int precompute, cozk_bases** out) {
     return cozk_guard(ctx, [&] {
         COZK_REQUIRE(ctx && src && out && src->n >= 2 && src->n % 2 == 0, "bases_pair_sums: bad argument");
-        size_t n = src->n / 2;
-        cozk_bases* b = new cozk_bases{ctx, n, precompute ? 16 : 1, nullptr};
-        try {
-            HIP_TRY(hipMalloc((void**)&b->table, (size_t)b->nwin * n * sizeof(g1_affine)));
-            k_pair_sums<<<cdiv(n, TPB), TPB, 0, ctx->stream>>>(src->table, b->table, n);
-            HIP_TRY(hipGetLastError());
-            build_window_table(ctx, b);
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-        } catch (...) {
-            if (b->table) (void)hipFree(b->table);
-            delete b;
-            throw;
-        }
-        *out = b;
+        const size_t n = src->n / 2;
+        *out = bases_create(ctx, n, precompute, [&](g1_affine* points) { k_pair_sums<<<cdiv(n, TPB), TPB, 0, ctx->stream>>>(src->table, points, n); });
     });
 }
 

@@ -1,5 +1,5 @@
 // Stand-alone host program around the host tail of the dense layer rounds (co-zkvms_amd/csrc/host/layer_tail.hpp): no device code
-// runs and no GPU is needed.  Built by co-zkvms_amd/build.py (build_layer_tail) and driven by tests/test_layer_tail_host.py.
+// runs and no GPU is needed.  Built by co-zkvms_amd/build.py (build_host_program) and driven by tests/test_layer_tail_host.py.
 //
 //   layer_tail_check            cases on stdin, results on stdout (both binary, little-endian):
 //       in : u64 ncases; per case u64 {NC, len, E1_len, E2_len, have_r, nrounds}, then Montgomery elements of 32 bytes:

@@ -1,4 +1,4 @@
-"""GPU: the launch schedule of the batched MSM (csrc/msm.hip) -- which sets are sorted wide and how many sort workgroups a
+"""GPU: the launch schedule of the batched MSM (csrc/host/msm_schedule.hpp, executed by csrc/msm.hip) -- which sets are sorted wide and how many sort workgroups a
 column of each kind gets -- changes no commitment.  Bar: bit-exact against the big-int oracle.
 
 Bases are s_i * G generated on the device from known scalars (as in test_gpu_msm_digit_forms.py), so the expected point of
@@ -55,7 +55,8 @@ def make_vecs(cozk, ctx, cols, seed):
             for p, (kind, n) in enumerate(cols)]
 
 
-CASES = {"many": M.MANY, "flag_first": M.small_large(True), "flag_last": M.small_large(False)}
+CASES = {"many": M.MANY, "flag_first": M.small_large(True), "flag_last": M.small_large(False),
+         "tail_blocks": [("FR", 64)] * 200 + [("U8", 64)] * 57}
 
 
 def case_points(cozk, ctx, B, name, with_ints=False):
@@ -196,3 +197,18 @@ def test_small_set_beside_a_large_one(cozk, ctx, srs, case, cap_log2, digits_log
     for t in trace:
         assert (t[4], t[5]) == ((1024, 64) if t[3] == M.WIDE else (256, 64))
     assert M.WIDE in [t[3] for t in trace[1:]] or cap_log2 == 19
+
+
+def test_two_tail_blocks_on_a_window_table(cozk, ctx, srs):
+    """257 columns of 64 scalars: the smallest batch that crosses the 256 bucket groups of one reduction tail on a window table.  The
+    first block is four launch sets of 64 columns, the second a single flag column, sorted wide because nothing runs beside it; the
+    set index starts again in every block.  Commitments from the big-int oracle, the trace from the model applied block by block."""
+    B, _ = srs
+    cols = CASES["tail_blocks"]
+    assert [len(b) for b in M.blocks(cols)] == [256, 1]
+    points, trace = run_child("tail_blocks")
+    got, ints = case_points(cozk, ctx, B, "tail_blocks", with_ints=True)
+    want = [_expect(v) for v in ints]
+    assert got == want and points == as_json(want)
+    assert [(t[0], t[1], t[2], t[3], t[6]) for t in trace] == [m for blk in M.blocks(cols) for m in model_trace(blk, None)]
+    assert [t[1] for t in trace] == [64, 64, 64, 64, 1] and trace[-1][0] == 0 and trace[-1][3] == M.WIDE

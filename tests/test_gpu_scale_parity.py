@@ -71,9 +71,9 @@ def test_grand_product_harness_equals_c_oracle(cozk, shape, mode):
     """commit -> dense grand product -> batch_evaluate -> reduce_and_prove -> PST open, byte for byte == orc_pipeline.
     Thresholds crossed (bench mix, n = 2^log_n, gp leaves 2^(log_n + 1) in 8 circuits):
       * MSM commit of 2^12..2^16 scalars per column: k_msm_hist_lds / k_msm_scatter_lds on ceil(n / 4096) > 1 workgroups
-        (csrc/msm.hip:826); 64 FR + 64 small-value columns = 128 polynomials, so two launch sets of 64 pipelined on the
-        second stream (csrc/msm.hip:985, 1047); fold levels k_msm_accumN once a bucket holds more than L0 = 8 references
-        (csrc/msm.hip:930);
+        (host/msm_schedule.hpp: msm_sort_wgs); 64 FR + 64 small-value columns = 128 polynomials, so two launch sets of 64 pipelined on the
+        second stream (host/msm_schedule.hpp: MsmTailBlock::pipelined); fold levels k_msm_accumN once a bucket holds more than L0 = 8 references
+        (host/msm_schedule.hpp: msm_set_counts);
       * GKR layers of len / 4 >= 1024 run the 9 x 29 kernels k_layer_cubic9 (LAYER_F9_MIN_CHUNKS); the plain prover's grouped
         split-eq variant k_layer_cubic9<1, 2> once E1_len / 2 >= 512 (layer_variant) -- reached by the 2^16 shape's
         first round (8 x 2^17 leaves; one dispatch in a kernel trace); tests/test_gpu_layer_grouped.py holds that variant and
@@ -90,9 +90,9 @@ def test_grand_product_harness_equals_c_oracle(cozk, shape, mode):
 
 def test_grand_product_harness_without_window_table_equals_c_oracle(cozk):
     """precompute=False: the 16-window-group MSM (k_msm_hist / k_msm_scatter / k_msm_accum0, G = 16 bucket groups; at most 4
-    polynomials per launch set and 16 per tail chunk, csrc/msm.hip:985-988), so the 128 commit polynomials of the bench mix run
+    polynomials per launch set and 16 per tail chunk, host/msm_schedule.hpp: msm_schedule), so the 128 commit polynomials of the bench mix run
     as tail chunks of at most 16 and launch sets of at most 4 polynomials, the cheapest set of a chunk rotated to the
-    front (csrc/msm.hip:1033).  Same bytes as with the table."""
+    front (host/msm_schedule.hpp: msm_schedule).  Same bytes as with the table."""
     cfg = GP_SHAPES["bench_2p14"]
     for mode in ("plain", "rep3"):
         h = cozk.Harness(mode=mode, precompute=False, **cfg)
@@ -112,7 +112,7 @@ def _scale_row(log_n):
 def test_production_sizes_equal_committed_c_oracle_digests(cozk, log_n, mode):
     """the bench workload itself (2^20 cycles, bench.py) and the same mix at 2^18: digest and length == the C oracle's
     (tests/golden/scale_pipelines.json).  Beyond (a): the level-0 MSM segment length L0 = M >> 18 grows past 8 once a launch set
-    holds more than 2^21 references (csrc/msm.hip:752) -- 64 FR columns x 2^18 scalars x 16 windows -- and the reducing
+    holds more than 2^21 references (host/msm_schedule.hpp: msm_set_counts) -- 64 FR columns x 2^18 scalars x 16 windows -- and the reducing
     kernels stride their grid past MAXBLK = 2048 workgroups x 256 lanes = 2^19 elements (grid_capped)."""
     row = _scale_row(log_n)
     cfg = dict(row["cfg"])
@@ -128,7 +128,7 @@ def test_spartan_2p10_equals_python_oracle(cozk):
     """co-noir Spartan at log_n = 10 (oracle/pyspartan.py, live), plain and Rep3 == the oracle's bytes.  Over the log_n = 6
     check this size adds multi-workgroup grids: round 0 of both sumchecks (k_spartan_first / k_spartan_second, BATCH_GRID_MAX)
     on 2 workgroups and the transposed sparse mat-vec (k_sparse_matvec3_rows / _items) on about 50; the commit of z sorts its
-    1024 scalars on one workgroup (csrc/msm.hip:826).  No 9 x 29 kernel runs at this size (kernel trace of one prove)."""
+    1024 scalars on one workgroup (host/msm_schedule.hpp: msm_sort_wgs).  No 9 x 29 kernel runs at this size (kernel trace of one prove)."""
     import pyspartan
     ref = pyspartan.run(dict(log_n=10, seed=2026))
     assert ref["verified"]
@@ -193,7 +193,7 @@ def test_flow_2p8_jolt_memories_equals_committed_oracle_digest(cozk):
     here, so its digest is committed (tests/golden/scale_pipelines.json, "flow").  Plain and Rep3 == that digest and length
     (Rep3 == plain: tests/test_gpu_flow.py).  The lookup toggle layer has 54 x 2^7 >= 4096 pairs under a nested split-eq
     (k_toggle_cubic9, TOGGLE_F9_MIN_PAIRS), its Spartan outer rounds run k_outer_round_act9 (OUTER_F9_MIN_PAIRS),
-    and its MSMs run the fold levels k_msm_accumN (csrc/msm.hip:930) -- all seen in a kernel trace of one prove."""
+    and its MSMs run the fold levels k_msm_accumN (host/msm_schedule.hpp: msm_set_counts) -- all seen in a kernel trace of one prove."""
     FL = importlib.import_module("co-zkvms_amd.flow")
     rows = SCALE_GOLD["flow"]
     assert len(rows) == 1
@@ -265,9 +265,9 @@ def _edge_scalars(sc_mont, n):
 @pytest.mark.parametrize("n,offset", [(4097, 5), ((1 << 16) + 3, 61), (1 << 18, 0)])
 def test_msm_equals_c_pippenger(cozk, ctx, srs, n, offset, precompute):
     """one MSM over bases[offset .. offset + n), random scalars with edge values at both ends of every 4096-scalar range.
-    With the table: k_msm_hist_lds / k_msm_scatter_lds on ceil(n / 4096) = 2, 17, 64 workgroups (csrc/msm.hip:826, capped at
-    64); k_msm_accumN fold levels once a bucket holds more than L0 references (csrc/msm.hip:930: 16 n / 2^15 per bucket on
-    average); L0 = M >> 18 = 16 at 2^18 (csrc/msm.hip:752).  Without it: the 16-window-group kernels (k_msm_hist /
+    With the table: k_msm_hist_lds / k_msm_scatter_lds on ceil(n / 4096) = 2, 17, 64 workgroups (host/msm_schedule.hpp: msm_sort_wgs, capped at
+    64); k_msm_accumN fold levels once a bucket holds more than L0 references (host/msm_schedule.hpp: msm_set_counts: 16 n / 2^15 per bucket on
+    average); L0 = M >> 18 = 16 at 2^18 (host/msm_schedule.hpp: msm_set_counts).  Without it: the 16-window-group kernels (k_msm_hist /
     k_msm_scatter / k_msm_accum0) on cdiv(n, 256) workgroups."""
     Bs, xy, inf = srs
     s = _edge_scalars(cozk.Vec.random(ctx, n, seed=n + 7 * offset).to_numpy(), n)
@@ -281,7 +281,7 @@ def test_msm_equals_c_pippenger(cozk, ctx, srs, n, offset, precompute):
 @pytest.mark.parametrize("precompute", [True, False])
 def test_msm_bases_with_infinity_2p16(cozk, ctx, precompute):
     """2^16 bases of which every 97th (and the first and last) is the point at infinity (a zero SRS scalar): the window table
-    marks has_inf and the gather runs k_msm_accum0_f9<true> with the k_msm_accum0_fix fix-up pass (csrc/msm.hip:914-916);
+    marks has_inf and the gather runs k_msm_accum0_f9<true> with the k_msm_accum0_fix fix-up pass (csrc/msm.hip: msm_accumulate);
     without the table k_msm_accum0 skips them.  Exact == the C Pippenger."""
     n = 1 << 16
     s = cozk.Vec.random(ctx, n, seed=4141).to_numpy()
@@ -329,9 +329,9 @@ def batch_points(cozk, ctx, B, vecs, offs, lens):
 
 
 # (k, precompute, longest polynomial): 70 with the table = launch sets of 64 + 6 on two streams, polynomials of up to 9000
-# scalars sorted by up to 3 workgroups each (csrc/msm.hip:826); 20 without = tail chunks of
+# scalars sorted by up to 3 workgroups each (host/msm_schedule.hpp: msm_sort_wgs); 20 without = tail chunks of
 # 16 + 4 (tail_cap = 256 / 16), the first cut into 4 launch sets of 4 and rotated; 300 with the table = tail chunks of 256 + 44,
-# the first cut into 4 launch sets of 64 and rotated (csrc/msm.hip:985-1036)
+# the first cut into 4 launch sets of 64 and rotated (host/msm_schedule.hpp: msm_schedule)
 BATCHES = {"k70_table": (70, True, 9000), "k20_groups": (20, False, 5000), "k300_table": (300, True, 600)}
 
 
@@ -356,7 +356,7 @@ def test_batch_msm_mixed_kinds_and_slices_equal_c_pippenger(cozk, ctx, srs, name
 
 
 # 12 FR polynomials of up to 2^18 scalars (2^22 references each): one launch set by default; 3 sets of 4 under a 2^24-reference
-# cap (COZK_MSM_SET_REFS_LOG2=24, csrc/msm.hip:1008), the cheapest set rotated to the front
+# cap (COZK_MSM_SET_REFS_LOG2=24, host/msm_schedule.hpp: MsmOptions::set_refs_log2), the cheapest set rotated to the front
 BIG_LENS = [(1 << 18) - 17 * i for i in range(11)] + [(1 << 16) + 5]
 
 
@@ -383,8 +383,8 @@ ctx.close()
 
 
 def test_batch_msm_serial_and_small_launch_sets_in_a_fresh_process(cozk, ctx, srs):
-    """COZK_MSM_SERIAL=1 (no second stream, csrc/msm.hip:1047) and COZK_MSM_SET_REFS_LOG2=24 (launch sets cut at 2^24
-    references, csrc/msm.hip:1008) are read once per process, so this leg runs in a child: its points of every batch above and
+    """COZK_MSM_SERIAL=1 (no second stream, host/msm_schedule.hpp: MsmOptions::serial) and COZK_MSM_SET_REFS_LOG2=24 (launch sets cut at 2^24
+    references, host/msm_schedule.hpp: MsmOptions::set_refs_log2) are read once per process, so this leg runs in a child: its points of every batch above and
     of a 12 x 2^18 batch (one launch set by default, 3 rotated sets under the cap) == the default run's; the default run of the
     big batch == the C Pippenger."""
     Bs, xy, inf = srs

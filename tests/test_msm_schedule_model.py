@@ -1,4 +1,4 @@
-"""CPU: the launch schedule of the batched MSM (csrc/msm.hip: msm_batch, msm_sort), restated in a few lines of Python.
+"""CPU: the launch schedule of the batched MSM (csrc/host/msm_schedule.hpp: msm_schedule), restated in a few lines of Python.
 
 Two rules decide how a launch set is sorted:
   shape       a set's sort takes the wide shape (1024 threads) when the set launched before it places fewer than an eighth
@@ -6,11 +6,16 @@ Two rules decide how a launch set is sorted:
               the 256-thread shape that slips under the running gather;
   workgroups  per run of columns of one kind: FR columns one workgroup per 4096 scalars, every other kind one per 2^16
               digits (n x windows of the kind), at least 1, at most 64.
-The GPU tests (test_gpu_msm_schedule.py) compare the COZK_TRACE_MSM lines of the library with what these functions say, so
-the numbers expected there do not come from the code under test."""
+plan() restates what a set needs beyond that (segment length, segment count, fold levels), blocks() the cut into tail blocks, and
+batch() puts all of it together.  test_msm_schedule_host.py holds the library's own schedule function to batch() on the CPU, at the
+benchmark's sizes too; the GPU tests (test_gpu_msm_schedule.py) compare the COZK_TRACE_MSM lines of the library with what these
+functions say.  Nothing here is derived from the C++, so the numbers expected there do not come from the code under test."""
 NWIN = {"FR": 16, "U8": 1, "U16": 2, "U32": 3, "U64": 5, "I64": 5}
-KIND_ORDER = ["FR", "U8", "U16", "U32", "U64", "I64"]  # the order in which msm_sort launches the kind runs
-MAX_POLYS = 64
+KIND_ORDER = ["FR", "U8", "U16", "U32", "U64", "I64"]  # the order in which the kind runs of a set are launched
+MAX_POLYS = 64         # per launch set on a window table
+MAX_POLYS_GROUPS = 4   # ... and without one, where every column is 16 bucket groups
+TAIL_GROUPS = 256      # bucket groups per tail block
+BUCKETS = 1 << 15
 WGS_MAX = 64
 WG_DIGITS_LOG2 = 16
 WIDE, NARROW = "wide", "narrow"
@@ -21,11 +26,11 @@ def refs(col):
     return n * NWIN[kind]
 
 
-def cut_sets(cols, cap):
+def cut_sets(cols, cap, max_polys=MAX_POLYS):
     """cols: [(kind, n)] in the caller's order; a set takes columns while it stays within `cap` references (one column always fits)"""
     sets, cur, m = [], [], 0
     for c in cols:
-        if cur and (m + refs(c) > cap or len(cur) == MAX_POLYS):
+        if cur and (m + refs(c) > cap or len(cur) == max_polys):
             sets.append(cur)
             cur, m = [], 0
         cur.append(c)
@@ -57,7 +62,7 @@ def shapes(ordered):
     return out
 
 
-def workgroups(s, digits_log2=WG_DIGITS_LOG2):
+def workgroups(s, digits_log2=WG_DIGITS_LOG2, wgs_max=WGS_MAX):
     """[(kind, columns, workgroups per column)] of a set, in launch order"""
     out = []
     for kind in KIND_ORDER:
@@ -68,7 +73,7 @@ def workgroups(s, digits_log2=WG_DIGITS_LOG2):
             w = -(-max(ns) // 4096)
         else:
             w = -(-max(ns) * NWIN[kind] // (1 << digits_log2))
-        out.append((kind, len(ns), min(max(w, 1), WGS_MAX)))
+        out.append((kind, len(ns), min(max(w, 1), wgs_max)))
     return out
 
 
@@ -76,6 +81,58 @@ def schedule(cols, cap=None, digits_log2=WG_DIGITS_LOG2):
     """[(columns, references, shape, workgroups)] per launch set, in launch order"""
     ordered = launch_order(cut_sets(cols, default_cap(cols) if cap is None else cap))
     return [(len(s), sum(refs(c) for c in s), sh, workgroups(s, digits_log2)) for s, sh in zip(ordered, shapes(ordered))]
+
+
+def blocks(cols, table=True):
+    """the bucket-reduction tail runs once per block of 256 bucket groups: 256 columns on a window table, 16 without"""
+    cap = TAIL_GROUPS if table else TAIL_GROUPS // 16
+    return [cols[i:i + cap] for i in range(0, len(cols), cap)]
+
+
+def plan(s, table=True):
+    """what one launch set needs.  L0: level-0 segments are refs / 2^18 long, within [8, 127].  Fold levels: the fullest ordinary
+    bucket holds the references of the longest column spread over 2^15 buckets (all its windows on a table, one window without),
+    a quarter more for the spread, in segments of L0, plus one; every level folds 8 into 1 and there is at least one level."""
+    groups = 1 if table else 16
+    nb = len(s) * groups * BUCKETS
+    m = sum(refs(c) for c in s)
+    L0 = min(max(m >> 18, 8), 127)
+    per = max(-(-(n * (NWIN[kind] if table else 1)) // BUCKETS) for kind, n in s)
+    segs = -(-(per * 5) // (4 * L0)) + 1
+    levels = 1
+    while -(-segs // 8) > 1:
+        segs = -(-segs // 8)
+        levels += 1
+    maxseg0 = m // L0 + nb
+    part = max(maxseg0, 2 * nb)
+    return dict(G=groups, nb=nb, refs=m, bound=max(refs(c) for c in s), L0=L0, maxseg0=maxseg0, fold_levels=levels, part=part, exc=maxseg0 + 2,
+                blk=-(-part // 256) + 2)
+
+
+def batch(cols, table=True, cap=None, digits_log2=WG_DIGITS_LOG2, shape_rule=True, serial=False, offset_forms=True):
+    """[[set, ...] per tail block], sets in launch order: plan() of the set plus its first column in the caller's order, its index,
+    its sort workspace, shape, kind runs and the columns that may take the offset digit form (bit p: column p of the set).  A block
+    of more than one set pipelines unless the batch is serial; only then does a sort run beside the set in front.  shape_rule=False
+    is the rule before: wide for the first set of the batch and wherever nothing is pipelined."""
+    out, start = [], 0
+    for b, bc in enumerate(blocks(cols, table)):
+        cut = cut_sets(bc, default_cap(bc) if cap is None else cap, MAX_POLYS if table else MAX_POLYS_GROUPS)
+        first = {}
+        for s in cut:
+            first[id(s)] = start
+            start += len(s)
+        ordered = launch_order(cut)
+        pipelined = len(ordered) > 1 and not serial
+        sets, pred = [], 0
+        for i, s in enumerate(ordered):
+            p = plan(s, table)
+            wide = 8 * pred < p["refs"] if shape_rule else (b == 0 and i == 0) or not pipelined
+            pred = p["refs"] if pipelined else 0
+            elig = sum(1 << j for j, (kind, n) in enumerate(s) if table and offset_forms and n and kind in ("U16", "U32", "U64"))
+            sets.append(dict(p, first=first[id(s)], polys=len(s), index=i, ws=i % 2, shape=WIDE if wide else NARROW, pipelined=pipelined,
+                             groups=len(bc) * p["G"], kinds=workgroups(s, digits_log2) if table and p["refs"] else [], elig=elig))
+        out.append(sets)
+    return out
 
 
 def bench_mix(n):
