@@ -29,6 +29,9 @@ from .ts_proof import (compact_batch_evaluate_at_chi, compact_linear_combination
                        TsProofConfig, TsProofResult)
 from . import rw_proof
 from .rw_proof import rw_memory_leaves, rw_memory_init_final_leaves, RW_PROOF_SYMBOLS, RwProof, RwProofConfig, RwProofResult
+from . import rw_proof_rep3
+from .rw_proof_rep3 import (rw_memory_shared_leaves, rw_memory_shared_init_final_leaves, RW_PROOF_REP3_SYMBOLS, RwProofRep3, RwProofRep3Config,
+                            RwProofRep3Result)
 from . import memory_proof
 from .memory_proof import OutputCheck, MemoryProof, MemoryProofConfig, MemoryProofResult, MEMORY_PROOF_SYMBOLS
 from . import bytecode

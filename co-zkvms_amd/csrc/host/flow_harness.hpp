@@ -535,6 +535,40 @@ void flow_lookups_worker(FlowWorker& w) {
     w.open(w.Ps(ix.final_cts, c.n_mem), r_if);
 }
 
+// COZK_RW_FUSED=1 (read on every prove, as COZK_BYTECODE_FUSED is; unset or 0: the ten cozk_fingerprint_leaves launches of
+// flow_rw_memory_worker, untouched): the read-write memory leaves come from cozk_rw_memory_shared_leaves and
+// cozk_rw_memory_shared_init_final_leaves over the same compact address and timestamp columns and the value polynomials (a public value
+// column goes in as its PLAIN polynomial), no iota column read.  The leaves, hence the proof bytes, are the same.
+static inline bool flow_rw_fused_enabled() {
+    const char* e = getenv("COZK_RW_FUSED");
+    return e && atoi(e) == 1;
+}
+// regs: the four slots as {a, v_read, v_write, index of t_read}
+void flow_rw_leaves_fused(FlowWorker& w, const int (&regs)[4][4], const fe& gamma, const fe& tau, LeafBuf& rw, LeafBuf& inf) {
+    const FlowIdx& ix = w.h->ix;
+    auto compact = [&](int idx, bool u8_too) {
+        if (!w.h->is_public[(size_t)idx]) return false;
+        const int kind = w.CV(idx)->kind;
+        return kind == COZK_SCALAR_U32 || (u8_too && kind == COZK_SCALAR_U8);
+    };
+    const cozk_vec *a[4], *tr[4];
+    const cozk_poly *vr[4], *vw[4];
+    for (int s = 0; s < 4; s++) {
+        const int* r = regs[s];
+        if (!compact(r[0], true)) throw std::runtime_error("COZK_RW_FUSED: an address column is not a public U8 or U32 column");
+        if (!compact(ix.rw_t_read + r[3], false)) throw std::runtime_error("COZK_RW_FUSED: a read timestamp column is not a public U32 column");
+        a[s] = w.CV(r[0]), tr[s] = w.CV(ix.rw_t_read + r[3]);
+        vr[s] = w.P(r[1]), vw[s] = r[2] == r[1] ? nullptr : w.P(r[2]);
+    }
+    if (!compact(ix.rw_t_final, false)) throw std::runtime_error("COZK_RW_FUSED: t_final is not a public U32 column");
+    uint64_t gw[4], tw[4];
+    fe_to_u64x4(gamma, gw);
+    fe_to_u64x4(tau, tw);
+    rc_check(cozk_rw_memory_shared_leaves(w.env.ctx, a, vr, tr, vw, 4, gw, tw, w.env.mode, w.env.party, rw.a.h, rw.b.h, 0), w.env.ctx, "rw_memory_shared_leaves");
+    rc_check(cozk_rw_memory_shared_init_final_leaves(w.env.ctx, w.P(ix.rw_v_init), w.P(ix.rw_v_final), w.CV(ix.rw_t_final), gw, tw, w.env.mode, w.env.party, inf.a.h, inf.b.h, 0),
+             w.env.ctx, "rw_memory_shared_init_final_leaves");
+}
+
 // ---- 4a. read-write memory (read_write_memory/worker.rs:196-344): the shared leaves over the committed polynomials
 void flow_rw_memory_worker(FlowWorker& w) {
     const FlowIdx& ix = w.h->ix;
@@ -548,7 +582,8 @@ void flow_rw_memory_worker(FlowWorker& w) {
     std::vector<RwSlotLeaves> slots;
     for (const int* r : regs) slots.push_back({w.T(r[0]), w.T(r[1]), w.T(r[2]), w.T(ix.rw_t_read + r[3])});
     LeafBuf rw = mc_leaf_alloc(w.env, 8 * N), inf = mc_leaf_alloc(w.env, 2 * MEM);
-    rw_memory_leaves_composed(w.env, slots, w.T(ix.rw_v_init), w.T(ix.rw_v_final), w.T(ix.rw_t_final), w.TC(w.ps.iota), w.TC(w.ps.iota), N, MEM, g[1], tau, rw, inf);
+    if (flow_rw_fused_enabled()) flow_rw_leaves_fused(w, regs, g[1], tau, rw, inf);
+    else rw_memory_leaves_composed(w.env, slots, w.T(ix.rw_v_init), w.T(ix.rw_v_final), w.T(ix.rw_t_final), w.TC(w.ps.iota), w.TC(w.ps.iota), N, MEM, g[1], tau, rw, inf);
     mc_memory_checking(w.env, mc_leaves_to_layer(w.env, rw), 8, ToggleH(), mc_leaves_to_layer(w.env, inf), 2, r_rw, r_if);
     std::vector<cozk_poly*> rwp = {w.P(jolt::V_RAM_ADDR), w.P(jolt::V_RD_READ), w.P(jolt::V_RS1), w.P(jolt::V_RS2), w.P(jolt::V_RAM_READ), w.P(jolt::V_RD_WRITE), w.P(jolt::V_RAM_WRITE)};
     for (int k = 0; k < 4; k++) rwp.push_back(w.P(ix.rw_t_read + k));

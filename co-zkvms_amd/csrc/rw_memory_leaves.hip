@@ -4,6 +4,13 @@
 //   k_rw_leaves     a thread per (slot, step): the read leaf h(addr, v_read, t_read) and the write leaf h(addr, w, j)
 //   k_rw_if_leaves  a thread per address: the init leaf h(a, v_init, 0) and the final leaf h(a, v_final, t_final)
 //
+// and the same circuits with the values as polynomials, plain or Rep3 shares (cozk_rw_memory_shared_leaves,
+// cozk_rw_memory_shared_init_final_leaves; Rep3ReadWriteMemoryProver::compute_leaves, co-jolt/src/jolt/vm/read_write_memory/worker.rs:196-344:
+// every leaf is add_public(mul_public(v_share, gamma), t gamma^2 + a - tau, party_id)):
+//
+//   k_rws_leaves<NC>     a thread per (slot, step), NC components per leaf
+//   k_rws_if_leaves<NC>  a thread per address
+//
 // The step number j and the address a exist only in registers.  Every leaf is the canonical Montgomery word of its value, so it
 // equals bit for bit what cozk_fingerprint_leaves gives for the same columns.
 //
@@ -18,6 +25,13 @@
 // is computed on the low 8 limbs alone (qh r mod 2^256 by 8 + 7 multiply-adds, qh = qh_hi 2^32 + qh_lo with qh_hi < 8) and two
 // conditional subtractions of r leave the canonical word.  tests/rw_proof_ref.py (leaf_word_model) restates these words with the
 // bounds as asserts.
+//
+// The shared kernels keep the value term apart: the public part a ONE + t G2 + C is the same exact sum with two terms (S < 2 * 2^32 r),
+// reduced once per leaf, and each share component is one Fr::mul by gamma and one Fr::add of the public part where the component
+// carries it (party 0's a, party 1's b; a plain prover's only component).  Party 2 computes no public part, and a public polynomial
+// in a REP3 call is read only by the party whose component carries it: both branches are uniform over the launch.  A slot that only
+// reads uses one v gamma product per component for both of its leaves.  Every word is canonical, so the leaves equal bit for bit what
+// the composition of cozk_fingerprint_leaves calls gives (rw_memory_leaves_composed with polynomial terms).
 //
 // Measured and not kept: a full Fr::mul per term, as k_ts_range_leaves has it (five products per (slot, step), 128
 // multiply-adds each) took 2.5 times as long at 2^20 steps with 4 slots; a thread per step over all slots, which makes j gamma^2
@@ -132,6 +146,76 @@ __global__ void __launch_bounds__(RL_PT) k_rw_if_leaves(const uint32_t* __restri
     fe_store(out + MEM + i, rl_reduce(base));
 }
 
+// ---- the values as polynomials: component pointers, null where the component takes nothing from the polynomial
+struct RwSharedCols {
+    const void* addr[RL_MAX_SLOTS];
+    const uint32_t* t_read[RL_MAX_SLOTS];
+    const fe* v_read[2][RL_MAX_SLOTS];     // [component][slot]
+    const fe* v_written[2][RL_MAX_SLOTS];  // read only where writes[s]
+    uint8_t addr_u8[RL_MAX_SLOTS], writes[RL_MAX_SLOTS];
+};
+struct RwSharedIfCols {
+    const fe *v_init[2], *v_final[2];
+    const uint32_t* t_final;
+};
+static __device__ __forceinline__ uint32_t rl_addr(const RwSharedCols& a, uint32_t s, size_t j) {
+    return a.addr_u8[s] ? (uint32_t)((const uint8_t*)a.addr[s])[j] : ((const uint32_t*)a.addr[s])[j];
+}
+// gamma v, zero where the component takes nothing
+static __device__ __forceinline__ fe rl_share_term(const fe* p, size_t j, const fe& gamma) { return p ? Fr::mul(fe_load(p + j), gamma) : Fr::zero(); }
+
+// o[c][(2 s) n + j] = gamma v_read_c + [pub[c]] (addr + t_read gamma^2 - tau), o[c][(2 s + 1) n + j] = gamma w_c + [pub[c]] (addr + j gamma^2 - tau);
+// blockIdx.y is the slot.  cf.v is gamma itself (the share term is a field product), cf.a, cf.t, cf.c as in k_rw_leaves.
+template <int NC>
+__global__ void __launch_bounds__(RL_PT) k_rws_leaves(RwSharedCols a, size_t n, RwLeafCoeffs cf, int pub_a, int pub_b, fe* __restrict__ oa, fe* __restrict__ ob) {
+    const size_t j = (size_t)blockIdx.x * RL_PT + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t s = blockIdx.y;
+    fe pub_r = Fr::zero(), pub_w = Fr::zero();
+    if (pub_a || pub_b) {  // uniform over the launch
+        RlAcc base = rl_start(cf.c);
+        rl_term(base, cf.a, rl_addr(a, s, j));
+        RlAcc rd = base;
+        rl_term(rd, cf.t, a.t_read[s][j]);
+        pub_r = rl_reduce(rd);
+        rl_term(base, cf.t, (uint32_t)j);
+        pub_w = rl_reduce(base);
+    }
+    const size_t ir = (size_t)(2 * s) * n + j, iw = ir + n;
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        const int pub = c == 0 ? pub_a : pub_b;
+        fe* o = c == 0 ? oa : ob;
+        const fe x = rl_share_term(a.v_read[c][s], j, cf.v);
+        const fe y = a.writes[s] ? rl_share_term(a.v_written[c][s], j, cf.v) : x;  // uniform over the workgroup
+        fe_store(o + ir, pub ? Fr::add(x, pub_r) : x);
+        fe_store(o + iw, pub ? Fr::add(y, pub_w) : y);
+    }
+}
+
+// o[c][i] = gamma v_init_c + [pub[c]] (i - tau), o[c][MEM + i] = gamma v_final_c + [pub[c]] (i + t_final gamma^2 - tau)
+template <int NC>
+__global__ void __launch_bounds__(RL_PT) k_rws_if_leaves(RwSharedIfCols a, size_t MEM, RwLeafCoeffs cf, int pub_a, int pub_b, fe* __restrict__ oa, fe* __restrict__ ob) {
+    const size_t i = (size_t)blockIdx.x * RL_PT + threadIdx.x;
+    if (i >= MEM) return;
+    fe pub_i = Fr::zero(), pub_f = Fr::zero();
+    if (pub_a || pub_b) {  // uniform over the launch
+        RlAcc base = rl_start(cf.c);
+        rl_term(base, cf.a, (uint32_t)i);
+        pub_i = rl_reduce(base);
+        rl_term(base, cf.t, a.t_final[i]);
+        pub_f = rl_reduce(base);
+    }
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        const int pub = c == 0 ? pub_a : pub_b;
+        fe* o = c == 0 ? oa : ob;
+        const fe x = rl_share_term(a.v_init[c], i, cf.v), y = rl_share_term(a.v_final[c], i, cf.v);
+        fe_store(o + i, pub ? Fr::add(x, pub_i) : x);
+        fe_store(o + MEM + i, pub ? Fr::add(y, pub_f) : y);
+    }
+}
+
 namespace {
 
 fe rl_fe(const uint64_t w[4]) {
@@ -142,6 +226,45 @@ fe rl_fe(const uint64_t w[4]) {
 RwLeafCoeffs rl_coeffs(const uint64_t gamma[4], const uint64_t tau[4]) {
     const fe g = rl_fe(gamma);
     return RwLeafCoeffs{Fr::one(), g, Fr::mul(g, g), Fr::neg(rl_fe(tau))};
+}
+
+// ---- the shared calls' argument checks
+void rl_shared_outputs(const std::string& w, int mode, int party_id, const cozk_vec* out_a, const cozk_vec* out_b, size_t offset, size_t circuits, size_t len,
+                       const std::string& room) {
+    COZK_REQUIRE(mode == COZK_MODE_PLAIN || mode == COZK_MODE_REP3, w + ": mode is COZK_MODE_PLAIN or COZK_MODE_REP3");
+    COZK_REQUIRE(party_id >= 0 && party_id < 3, w + ": 0 <= party_id < 3");
+    COZK_REQUIRE(out_a && out_a->kind == COZK_SCALAR_FR && offset <= out_a->n && (out_a->n - offset) / circuits >= len,
+                 w + ": out_a is an FR vector with room for " + room + " entries from offset");
+    if (mode == COZK_MODE_REP3)
+        COZK_REQUIRE(out_b && out_b != out_a && out_b->d != out_a->d && out_b->kind == COZK_SCALAR_FR && offset <= out_b->n && (out_b->n - offset) / circuits >= len,
+                     w + ": REP3 needs out_b, another FR vector with room for " + room + " entries from offset");
+    else
+        COZK_REQUIRE(!out_b, w + ": out_b is NULL for PLAIN");
+}
+// The component pointers of one value polynomial (what cozk_fingerprint_leaves does with a polynomial term): a shared one gives both
+// components; a public one in a REP3 call enters through add_public, party 0's a and party 1's b; a plain call reads component a.
+// The views go into `views`, which the caller frees: the polynomial keeps its buffers.
+struct RlViews {
+    std::vector<cozk_vec*> v;
+    ~RlViews() {
+        for (cozk_vec* w : v) cozk_vec_free(w);
+    }
+};
+void rl_poly_components(cozk_ctx* ctx, const std::string& w, const cozk_poly* p, int mode, int party_id, RlViews& views, const fe*& a, const fe*& b) {
+    const fe* c[2] = {nullptr, nullptr};
+    const int pm = cozk_poly_mode(p);
+    for (int k = 0; k < (pm == COZK_MODE_REP3 ? 2 : 1); k++) {
+        cozk_vec* view = nullptr;
+        if (cozk_poly_share_view(ctx, p, k, &view) != COZK_OK) throw CozkError(COZK_ERR_INVALID_ARG, w + ": " + ctx->last_error);
+        views.v.push_back(view);
+        c[k] = (const fe*)view->d;
+    }
+    if (pm == COZK_MODE_REP3 || mode == COZK_MODE_PLAIN) {
+        a = c[0], b = c[1];
+    } else {
+        a = party_id == 0 ? c[0] : nullptr;
+        b = party_id == 1 ? c[0] : nullptr;
+    }
 }
 
 }  // namespace
@@ -189,6 +312,76 @@ int cozk_rw_memory_init_final_leaves(cozk_ctx* ctx, const cozk_vec* v_init, cons
                      "rw_memory_init_final_leaves: out is an FR vector with room for 2 MEM entries from offset");
         k_rw_if_leaves<<<(unsigned)((MEM + RL_PT - 1) / RL_PT), RL_PT, 0, ctx->stream>>>((const uint32_t*)v_init->d, (const uint32_t*)v_final->d,
                                                                                          (const uint32_t*)t_final->d, MEM, rl_coeffs(gamma, tau), (fe*)out->d + offset);
+        HIP_TRY(hipGetLastError());
+    });
+}
+
+int cozk_rw_memory_shared_leaves(cozk_ctx* ctx, const cozk_vec* const* addr, const cozk_poly* const* v_read, const cozk_vec* const* t_read,
+                                 const cozk_poly* const* v_written, size_t n_slots, const uint64_t gamma[4], const uint64_t tau[4], int mode, int party_id,
+                                 cozk_vec* out_a, cozk_vec* out_b, size_t offset) {
+    return cozk_guard(ctx, [&] {
+        const std::string w = "rw_memory_shared_leaves";
+        COZK_REQUIRE(ctx && addr && v_read && t_read && gamma && tau, w + ": bad argument");
+        COZK_REQUIRE(n_slots >= 1 && n_slots <= RL_MAX_SLOTS, w + ": 1 <= n_slots <= " RL_STR(COZK_RW_MEMORY_MAX_SLOTS));
+        COZK_REQUIRE(mode == COZK_MODE_PLAIN || mode == COZK_MODE_REP3, w + ": mode is COZK_MODE_PLAIN or COZK_MODE_REP3");
+        for (size_t s = 0; s < n_slots; s++) {
+            const cozk_vec *a = addr[s], *tr = t_read[s];
+            const cozk_poly *vr = v_read[s], *vw = v_written ? v_written[s] : nullptr;
+            COZK_REQUIRE(a && (a->kind == COZK_SCALAR_U8 || a->kind == COZK_SCALAR_U32), w + ": addr[s] is a U8 or U32 vector");
+            COZK_REQUIRE(tr && tr->kind == COZK_SCALAR_U32, w + ": t_read[s] is a U32 vector");
+            COZK_REQUIRE(addr[0] && a->n == addr[0]->n && tr->n == a->n, w + ": every column has n entries");
+            COZK_REQUIRE(vr, w + ": v_read[s] is a polynomial");
+            COZK_REQUIRE(cozk_poly_len(vr) >= a->n && (!vw || cozk_poly_len(vw) >= a->n), w + ": a value polynomial is shorter than n");
+            COZK_REQUIRE(mode == COZK_MODE_REP3 || (cozk_poly_mode(vr) == COZK_MODE_PLAIN && (!vw || cozk_poly_mode(vw) == COZK_MODE_PLAIN)),
+                         w + ": a shared value polynomial needs mode COZK_MODE_REP3");
+        }
+        const size_t n = addr[0]->n;
+        COZK_REQUIRE(n >= 1 && n < ((size_t)1 << 32), w + ": 1 <= n < 2^32");
+        rl_shared_outputs(w, mode, party_id, out_a, out_b, offset, 2 * n_slots, n, "2 n_slots n");
+        RwSharedCols h{};
+        RlViews views;
+        for (size_t s = 0; s < n_slots; s++) {
+            h.addr[s] = addr[s]->d;
+            h.addr_u8[s] = addr[s]->kind == COZK_SCALAR_U8;
+            h.t_read[s] = (const uint32_t*)t_read[s]->d;
+            rl_poly_components(ctx, w, v_read[s], mode, party_id, views, h.v_read[0][s], h.v_read[1][s]);
+            if (v_written && v_written[s]) {
+                h.writes[s] = 1;
+                rl_poly_components(ctx, w, v_written[s], mode, party_id, views, h.v_written[0][s], h.v_written[1][s]);
+            }
+        }
+        const dim3 grid((unsigned)((n + RL_PT - 1) / RL_PT), (unsigned)n_slots);
+        const RwLeafCoeffs cf = rl_coeffs(gamma, tau);  // cf.v = gamma in Montgomery form: the factor of the share products
+        fe* oa = (fe*)out_a->d + offset;
+        if (mode == COZK_MODE_REP3) k_rws_leaves<2><<<grid, RL_PT, 0, ctx->stream>>>(h, n, cf, party_id == 0, party_id == 1, oa, (fe*)out_b->d + offset);
+        else k_rws_leaves<1><<<grid, RL_PT, 0, ctx->stream>>>(h, n, cf, 1, 0, oa, nullptr);
+        HIP_TRY(hipGetLastError());
+    });
+}
+
+int cozk_rw_memory_shared_init_final_leaves(cozk_ctx* ctx, const cozk_poly* v_init, const cozk_poly* v_final, const cozk_vec* t_final, const uint64_t gamma[4],
+                                            const uint64_t tau[4], int mode, int party_id, cozk_vec* out_a, cozk_vec* out_b, size_t offset) {
+    return cozk_guard(ctx, [&] {
+        const std::string w = "rw_memory_shared_init_final_leaves";
+        COZK_REQUIRE(ctx && v_init && v_final && t_final && gamma && tau, w + ": bad argument");
+        COZK_REQUIRE(mode == COZK_MODE_PLAIN || mode == COZK_MODE_REP3, w + ": mode is COZK_MODE_PLAIN or COZK_MODE_REP3");
+        COZK_REQUIRE(t_final->kind == COZK_SCALAR_U32, w + ": t_final is a U32 vector");
+        const size_t MEM = t_final->n;
+        COZK_REQUIRE(MEM >= 1 && MEM < ((size_t)1 << 32), w + ": 1 <= MEM < 2^32");
+        COZK_REQUIRE(cozk_poly_len(v_init) >= MEM && cozk_poly_len(v_final) >= MEM, w + ": a value polynomial is shorter than MEM");
+        COZK_REQUIRE(mode == COZK_MODE_REP3 || (cozk_poly_mode(v_init) == COZK_MODE_PLAIN && cozk_poly_mode(v_final) == COZK_MODE_PLAIN),
+                     w + ": a shared value polynomial needs mode COZK_MODE_REP3");
+        rl_shared_outputs(w, mode, party_id, out_a, out_b, offset, 2, MEM, "2 MEM");
+        RwSharedIfCols h{};
+        RlViews views;
+        h.t_final = (const uint32_t*)t_final->d;
+        rl_poly_components(ctx, w, v_init, mode, party_id, views, h.v_init[0], h.v_init[1]);
+        rl_poly_components(ctx, w, v_final, mode, party_id, views, h.v_final[0], h.v_final[1]);
+        const unsigned grid = (unsigned)((MEM + RL_PT - 1) / RL_PT);
+        const RwLeafCoeffs cf = rl_coeffs(gamma, tau);  // cf.v = gamma in Montgomery form: the factor of the share products
+        fe* oa = (fe*)out_a->d + offset;
+        if (mode == COZK_MODE_REP3) k_rws_if_leaves<2><<<grid, RL_PT, 0, ctx->stream>>>(h, MEM, cf, party_id == 0, party_id == 1, oa, (fe*)out_b->d + offset);
+        else k_rws_if_leaves<1><<<grid, RL_PT, 0, ctx->stream>>>(h, MEM, cf, 1, 0, oa, nullptr);
         HIP_TRY(hipGetLastError());
     });
 }

@@ -1885,6 +1885,32 @@ int cozk_rw_memory_leaves(cozk_ctx* ctx, const cozk_vec* const* addr, const cozk
 int cozk_rw_memory_init_final_leaves(cozk_ctx* ctx, const cozk_vec* v_init, const cozk_vec* v_final, const cozk_vec* t_final,
                                      const uint64_t gamma[4], const uint64_t tau[4], cozk_vec* out, size_t offset);
 
+/* ---- The same circuits with the values as polynomials, plain or Rep3 shares (Rep3ReadWriteMemoryProver::compute_leaves,
+ * co-jolt/src/jolt/vm/read_write_memory/worker.rs:196-344: the addresses and the timestamps are public compact columns, v_read, v_write,
+ * v_init and v_final are shares, and every leaf is add_public(mul_public(v_share, gamma), t gamma^2 + a - tau, party_id)).  The layout
+ * and h are those of cozk_rw_memory_leaves.
+ * cozk_rw_memory_shared_leaves: ONE launch, a thread per (slot, step).  addr[s]: U8 or U32; t_read[s]: U32; one length 1 <= n < 2^32;
+ * v_read[s], and v_written[s] where it is not NULL (v_written may be NULL as a whole), are polynomials of at least n entries, PLAIN or
+ * REP3; 1 <= n_slots <= COZK_RW_MEMORY_MAX_SLOTS.  A slot that only reads makes one gamma v product per component for both leaves.
+ * cozk_rw_memory_shared_init_final_leaves: ONE launch, a thread per address.  t_final: U32 of 1 <= MEM < 2^32 entries; v_init and
+ * v_final: polynomials of at least MEM entries, PLAIN or REP3.
+ * Both: a REP3 polynomial is accepted only with mode == COZK_MODE_REP3.  With COZK_MODE_REP3, out_a / out_b take the two components
+ * of the party's leaf shares: gamma times the components of the value, and the public part a + t gamma^2 - tau through add_public
+ * exactly as in cozk_fingerprint_leaves, party 0's a and party 1's b; party 2 computes no public part.  A PLAIN polynomial in a REP3
+ * call is a public polynomial and joins the public part (only parties 0 and 1 read it).  With COZK_MODE_PLAIN out_a takes the leaf
+ * and out_b is NULL.  out_a (and out_b, another vector) are FR vectors with room for 2 n_slots n (2 MEM) entries from offset, which
+ * cozk_layer_create adopts; gamma, tau: 4 x u64 (Montgomery); asynchronous on the context's stream; every refusal comes before any
+ * launch with a text of its own and COZK_ERR_INVALID_ARG, and the context works on.  Every leaf is bit for bit what the composition of
+ * cozk_fingerprint_leaves calls gives in the same mode for the same party.
+ * The public part is the exact 9-limb sum of cozk_rw_memory_leaves with two terms; each share component takes one Montgomery product
+ * by gamma and one addition (csrc/rw_memory_leaves.hip). */
+int cozk_rw_memory_shared_leaves(cozk_ctx* ctx, const cozk_vec* const* addr, const cozk_poly* const* v_read, const cozk_vec* const* t_read,
+                                 const cozk_poly* const* v_written, size_t n_slots, const uint64_t gamma[4], const uint64_t tau[4], int mode,
+                                 int party_id, cozk_vec* out_a, cozk_vec* out_b, size_t offset);
+int cozk_rw_memory_shared_init_final_leaves(cozk_ctx* ctx, const cozk_poly* v_init, const cozk_poly* v_final, const cozk_vec* t_final,
+                                            const uint64_t gamma[4], const uint64_t tau[4], int mode, int party_id, cozk_vec* out_a,
+                                            cozk_vec* out_b, size_t offset);
+
 /* ---- The bytecode memory check's device calls (Rep3BytecodeProver, co-jolt/src/jolt/vm/bytecode/worker.rs:43-142): a consistent
  * witness over the six public table columns (preprocessing.v_init_final: address, bitflags, rd, rs1, rs2, imm), and the leaves of its
  * four grand-product circuits from seven compact public columns plus the one shared field column v_imm.
@@ -2034,6 +2060,57 @@ int cozk_rw_proof_destroy(cozk_rw_proof* h);
 int cozk_rw_proof_prove(cozk_rw_proof* h, int verify, cozk_rw_proof_result* res);
 int cozk_rw_proof_proof_bytes(const cozk_rw_proof* h, uint8_t* out, size_t cap);
 
+/* ---- The same memory check proved by three Rep3 parties, as an in-process harness (csrc/host/rw_memory_proof_rep3.hpp;
+ * Rep3ReadWriteMemoryProver, co-jolt/src/jolt/vm/read_write_memory/worker.rs:196-344): the addresses and the timestamps are public
+ * compact columns, v_read, v_written and v_final are Rep3 shares, v_init is public preprocessing.  The instance, the column order, the
+ * transcript ("cozk-rw-memory"), the proof bytes and the verifier are cozk_rw_proof's with with_ts = 0: the proof is byte for byte the
+ * plain proof of the same seed, and the verifier (the same code) runs the multiset check and reports the same reasons.
+ * create (all of it outside prove's clock): cozk_rw_proof's instance on party 0's context (devices[0]); every party gets the public
+ * columns addr, t_read, t_final and v_init, the last as a PLAIN polynomial; each secret column -- v_read[s], the v_written of the slots
+ * that write, v_final -- is widened to Fr (cozk_compact_linear_combination with coefficient 1) and shared under the harness keys, a
+ * seed per column; every party holds an SRS of its own.
+ * prove (three workers on threads of their own with a ring between them, coordinator and verifier on the calling thread):
+ *   1. commit in the plain order addr, v_read, v_written, t_read, v_final, t_final: each party the a components of its shares and the
+ *      public columns; the coordinator adds the share commitments and keeps party 0's public ones
+ *   2. gamma, tau; the leaves in REP3: cozk_rw_memory_shared_leaves + cozk_rw_memory_shared_init_final_leaves (leaves_fused = 1), or
+ *      the composition of ten (at 4 slots) cozk_fingerprint_leaves calls with an iota column (leaves_fused = 0): the same bytes
+ *   3. both hash vectors, then the two dense grand products in REP3: points r_rw and r_if
+ *   4. the openings at r_rw and at r_if, each ONE claim exchange and ONE joint polynomial: the claims of public columns from
+ *      cozk_compact_batch_evaluate_at_chi, reported by party 0 (the convention of the chained flow's openings), those of shared columns
+ *      additive from cozk_poly_batch_evaluate_at_chi; the joint polynomial is the compact combination of the public columns over their
+ *      rho powers, as a PLAIN polynomial, plus the shared polynomials over theirs (cozk_poly_linear_combination)
+ *   5. ONE reduce_and_prove.
+ * tamper: 1 adds 1 to v_read[last slot][N / 2] before the sharing ("multiset equality"); 2: party 0 adds one to its share of claim 0 at
+ * r_rw ("leaf claim").
+ * Refused by create before any context exists: log_n outside 1..22, log_mem outside 5..24, n_slots outside 1..4, leaves_fused outside
+ * 0..1, tamper outside 0..2.
+ * Not built: the timestamp range check and the output check by Rep3 parties, one party per process. */
+typedef struct cozk_rw_proof_rep3 cozk_rw_proof_rep3;
+typedef struct cozk_rw_proof_rep3_config {
+    int devices[3];   /* one device per party */
+    int log_n;        /* 1..22 */
+    int log_mem;      /* 5..24 */
+    int n_slots;      /* 1..4, as cozk_rw_proof_config */
+    uint64_t seed;    /* the instance seed: the same seed gives cozk_rw_proof's instance */
+    int precompute;   /* as cozk_rw_proof_config */
+    int leaves_fused; /* 1: the two shared calls; 0: the composition (kept for the A/B); both give the same bytes */
+    int tamper;       /* 0..2: see above */
+} cozk_rw_proof_rep3_config;
+typedef struct cozk_rw_proof_rep3_result {
+    int verified; /* 1 ok, 0 rejected, -1 not run */
+    /* t_witness_ms: the dealer's witness walks (create); t_share_ms: uploading, widening and sharing the columns (create), and the
+     * phases of prove, each the maximum over the parties; t_open_ms: the two openings plus reduce_and_prove */
+    double wall_ms, t_witness_ms, t_share_ms, t_commit_ms, t_leaves_ms, t_gp_ms, t_open_ms;
+    uint64_t ring_bytes; /* sent over the ring by the three parties together */
+    uint64_t proof_len;
+    uint8_t proof_digest[32];
+} cozk_rw_proof_rep3_result;
+int cozk_rw_proof_rep3_create(const cozk_rw_proof_rep3_config* cfg, cozk_rw_proof_rep3** out);
+const char* cozk_rw_proof_rep3_error(const cozk_rw_proof_rep3* h);
+int cozk_rw_proof_rep3_destroy(cozk_rw_proof_rep3* h);
+int cozk_rw_proof_rep3_prove(cozk_rw_proof_rep3* h, int verify, cozk_rw_proof_rep3_result* res);
+int cozk_rw_proof_rep3_proof_bytes(const cozk_rw_proof_rep3* h, uint8_t* out, size_t cap);
+
 /* ---- The output check of the read-write memory proof on the device (prove_outputs, co-jolt/src/jolt/vm/read_write_memory/worker.rs:
  * 110-175; csrc/output_check.inc):
  *     sum_x eq(r_eq, x) * io_range(x) * (v_final(x) - v_io(x)) = 0,   degree 3, binding HighToLow,
@@ -2122,7 +2199,11 @@ int cozk_memory_proof_proof_bytes(const cozk_memory_proof* h, uint8_t* out, size
  * on the dealer's device, before sharing) and the verifier runs that check for them; the bytecode and the read-write memory keep
  * synthetic counters.  With lookups_witness = 0 the proof bytes are what they were before the field existed.
  * COZK_BYTECODE_FUSED=1 in the environment (read on every prove; unset or 0: four cozk_fingerprint_leaves launches) makes the leaves
- * of the bytecode phase with cozk_bytecode_leaves and cozk_bytecode_init_final_leaves, in PLAIN and REP3; the proof bytes are the same. */
+ * of the bytecode phase with cozk_bytecode_leaves and cozk_bytecode_init_final_leaves, in PLAIN and REP3; the proof bytes are the same.
+ * COZK_RW_FUSED=1 (read on every prove; unset or 0: ten cozk_fingerprint_leaves launches) makes the leaves of the read-write memory
+ * phase with cozk_rw_memory_shared_leaves and cozk_rw_memory_shared_init_final_leaves over the flow's own columns (U8 and U32
+ * addresses, U32 timestamps, shared or plain value polynomials, the shared v_init), in PLAIN and REP3; the proof bytes are the same.
+ * A column of another kind than the calls take fails the prove with a text that names the switch. */
 typedef struct cozk_flow cozk_flow;
 typedef struct cozk_flow_config {
     int mode;

@@ -12,7 +12,10 @@ stay on the device.  --warmup runs, then the median and spread of --runs runs.  
 HBM rates of the MI355X (8.0 TB/s datasheet, 6.29 TB/s measured copy).  Prints one JSON line.
   python tools/run_rw_proof.py --log-n 20 --log-mem 20 --runs 7 [--out profiles/rw_proof_2p20.json]
 Per-kernel times: rocprofv3 --kernel-trace --stats --output-format csv -- python tools/run_rw_proof.py ..., in a run of its own; merge
-with --kernel-stats <the stats csv>.  --bench <file> adds recorded bench.py lines ({"this_change": {...}, "parent": {...}})."""
+with --kernel-stats <the stats csv>.  --bench <file> adds recorded bench.py lines ({"this_change": {...}, "parent": {...}}).
+--rep3 measures the three-party form instead and prints its own JSON line (without the flag the output is unchanged): the shared fused
+leaves against the composition in REP3 for a party of each kind, and the whole three-party prove with either leaves path (run_rep3):
+  python tools/run_rw_proof.py --rep3 --log-n 20 --log-mem 20 --runs 7 [--out profiles/rw_proof_rep3_2p20.json]"""
 import argparse, csv, ctypes, importlib, json, os, statistics, sys
 
 import numpy as np
@@ -27,6 +30,7 @@ ap.add_argument("--seed", type=int, default=2026)
 ap.add_argument("--runs", type=int, default=7)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--skip-prove", action="store_true")
+ap.add_argument("--rep3", action="store_true")
 ap.add_argument("--kernel-stats", default=None)
 ap.add_argument("--bench", default=None)
 ap.add_argument("--out", default=None)
@@ -85,6 +89,98 @@ sm = np.random.default_rng(args.seed + 1)
 fr = lambda: int.from_bytes(sm.bytes(40), "little") % R
 gamma, tau = fr(), fr()
 g2 = gamma * gamma % R
+
+
+def run_rep3():
+    """--rep3: the shared leaves (cozk_rw_memory_shared_leaves + cozk_rw_memory_shared_init_final_leaves) against the ten
+    cozk_fingerprint_leaves calls they replace, in REP3 for one party of each kind (0: the public part in a, 1: in b, 2: none), the two
+    paths alternating and their outputs compared; then the whole three-party prove (cozk_rw_proof_rep3_*) with either leaves path, two
+    handles alternating, per phase (the maximum over the parties).  The address and timestamp columns are the witness's; the value
+    polynomials are random share components of N (MEM) entries, v_init a public polynomial, as the harness passes them."""
+    MODE_REP3 = Z._lib.MODE_REP3
+    widen = lambda col: Z.Rep3DensePolynomial.from_vec_shares(ctx, Z.compact_linear_combination(ctx, [col], [1]))
+    shared = lambda n, seed: Z.Rep3DensePolynomial.random(ctx, n, seed, MODE_REP3)
+    p_read = [shared(N, 100 + s) for s in range(NS)]
+    p_written = [None, None, shared(N, 200), shared(N, 201)]
+    p_init, p_final = widen(v_init), shared(MEM, 300)
+    iota_n, iota_mem = u32(np.arange(N)), u32(np.arange(MEM))
+    outs = lambda n: [Z.Vec.alloc(ctx, n), Z.Vec.alloc(ctx, n)]
+    rw_fused, rw_comp, if_fused, if_comp = outs(2 * NS * N), outs(2 * NS * N), outs(2 * MEM), outs(2 * MEM)
+    out = {"what": "the read-write memory proof by three Rep3 parties: the shared fused leaves against the composition for a party of each kind, the three-party prove per phase",
+           "log_n": args.log_n, "log_mem": args.log_mem, "slots": NS, "circuits": 2 * NS + 2, "runs": args.runs, "warmup": args.warmup, "leaves": {}, "launch_alone": {}}
+    for party in (0, 1, 2):
+        def fused_rw():
+            Z.rw_memory_shared_leaves(ctx, addr, p_read, t_read, p_written, gamma, tau, "rep3", party, *rw_fused)
+
+        def fused_if():
+            Z.rw_memory_shared_init_final_leaves(ctx, p_init, p_final, t_final, gamma, tau, "rep3", party, *if_fused)
+
+        def fused():
+            fused_rw()
+            fused_if()
+            ctx.synchronize()
+
+        def composed():
+            leaf = lambda o, off, n, cols, coeffs, poly: Z.fingerprint_leaves(ctx, cols, coeffs, [poly], [gamma], -tau % R, "rep3", party, *o, offset=off, n=n)
+            for s in range(NS):
+                leaf(rw_comp, 2 * s * N, N, [t_read[s], addr[s]], [g2, 1], p_read[s])
+                leaf(rw_comp, (2 * s + 1) * N, N, [iota_n, addr[s]], [g2, 1], p_read[s] if p_written[s] is None else p_written[s])
+            leaf(if_comp, 0, MEM, [iota_mem], [1], p_init)
+            leaf(if_comp, MEM, MEM, [t_final, iota_mem], [g2, 1], p_final)
+            ctx.synchronize()
+
+        ms = ab({"fused": fused, "composition": composed})
+        equal = all(bool(np.array_equal(x.to_numpy(), y.to_numpy())) for x, y in zip(rw_fused + if_fused, rw_comp + if_comp))
+        assert equal, "party %d: the fused shared leaves differ from the composition" % party
+        # in: the public columns (a party that adds no public part reads none; only parties 0 and 1 read the public v_init), both
+        # components of the 6 shared columns of N entries and of v_final; out: both components of every circuit
+        pub = party < 2
+        rw_bytes = ((3 * 1 + 1 * 4 + 4 * NS) * pub + 2 * 32 * (NS + 2)) * N + 2 * 2 * NS * 32 * N
+        if_bytes = ((4 + 32) * pub + 2 * 32) * MEM + 2 * 2 * 32 * MEM
+        # the composition: every launch reads its own columns (every party, the iota columns among them) and one polynomial, writes one circuit
+        comp_bytes = (2 * (3 * 1 + 1 * 4) + (4 + 4) * NS + 2 * NS * 2 * 32 + 2 * NS * 2 * 32) * N + (4 + 4 + 4 + 32 * pub + 2 * 32 + 2 * 2 * 32) * MEM
+        out["leaves"]["party_%d" % party] = {
+            "fused_ms": stats(ms["fused"], rw_bytes + if_bytes), "composition_ms": stats(ms["composition"], comp_bytes),
+            "composition_launches": 2 * NS + 2, "fused_launches": 2, "composition_over_fused": round(statistics.median(ms["composition"]) / statistics.median(ms["fused"]), 3),
+            "outputs_equal": equal, "includes": "one context synchronise on either side"}
+        ms = ab({"rw": fused_rw, "init_final": fused_if})
+        out["launch_alone"]["party_%d" % party] = {"rw_memory_shared_leaves_ms": stats(ms["rw"], rw_bytes), "rw_memory_shared_init_final_leaves_ms": stats(ms["init_final"], if_bytes)}
+    if args.skip_prove:
+        out["prove"] = "not measured"
+    else:
+        rw_fused = rw_comp = if_fused = if_comp = p_read = p_written = p_init = p_final = None
+        handles = {lv: Z.RwProofRep3(log_n=args.log_n, log_mem=args.log_mem, seed=args.seed, leaves_fused=(lv == "fused")) for lv in ("fused", "composition")}
+        phases = ("wall_ms", "t_commit_ms", "t_leaves_ms", "t_gp_ms", "t_open_ms")
+        pm = {k: {ph: [] for ph in phases} for k in handles}
+        digest, last = {}, {}
+        for it in range(args.warmup + args.runs):
+            for k, hd in handles.items():
+                r = hd.prove(verify=(it == 0))
+                assert it > 0 or r.verified == 1, hd.last_error()
+                assert digest.setdefault(k, bytes(r.proof_digest)) == bytes(r.proof_digest)
+                last[k] = r
+                if it >= args.warmup:
+                    for ph in phases:
+                        pm[k][ph].append(getattr(r, ph))
+        assert digest["fused"] == digest["composition"], "the two leaves paths give different proofs"
+        plain = Z.RwProof(log_n=args.log_n, log_mem=args.log_mem, seed=args.seed, with_ts=False)
+        plain_digest = bytes(plain.prove(verify=False).proof_digest)
+        plain.close()
+        assert plain_digest == digest["fused"], "the Rep3 proof differs from the plain proof of the same seed"
+        out["prove"] = {lv: dict({ph: stats(pm[lv][ph]) for ph in phases}, t_witness_ms_of_create=round(last[lv].t_witness_ms, 3), t_share_ms_of_create=round(last[lv].t_share_ms, 3),
+                                 ring_bytes=int(last[lv].ring_bytes), proof_bytes=int(last[lv].proof_len)) for lv in handles}
+        out["prove"].update({"verified": True, "digests_equal": True, "equal_to_the_plain_proof": True, "parties": "three contexts on one device",
+                             "clock": "host clock around each phase of a worker, the maximum over the three parties; t_open_ms is the two joint openings plus reduce_and_prove"})
+        for hd in handles.values():
+            hd.close()
+    print(json.dumps(out), flush=True)
+    if args.out:
+        open(args.out, "w").write(json.dumps(out, indent=1) + "\n")
+
+
+if args.rep3:
+    run_rep3()
+    sys.exit(0)
 
 # ---- leaves: the two fused calls against the ten calls of the composition
 iota_n, iota_mem = u32(np.arange(N)), u32(np.arange(MEM))
