@@ -34,6 +34,8 @@ from .rw_proof_rep3 import (rw_memory_shared_leaves, rw_memory_shared_init_final
                             RwProofRep3Result)
 from . import memory_proof
 from .memory_proof import OutputCheck, MemoryProof, MemoryProofConfig, MemoryProofResult, MEMORY_PROOF_SYMBOLS
+from . import memory_proof_rep3
+from .memory_proof_rep3 import MemoryProofRep3, MemoryProofRep3Config, MemoryProofRep3Result, MEMORY_PROOF_REP3_SYMBOLS
 from . import bytecode
 from .bytecode import (bytecode_witness, bytecode_leaves, bytecode_init_final_leaves, BYTECODE_SYMBOLS, BytecodeProof, BytecodeProofConfig,
                        BytecodeProofResult)

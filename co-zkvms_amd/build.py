@@ -18,7 +18,7 @@ NATIVE = os.path.join(os.path.dirname(HERE), "tests", "native")
 HOST_PROGRAMS = {"--layer-tail": "layer_tail_check", "--bytecode-leaf-check": "bytecode_leaf_check", "--msm-schedule-check": "msm_schedule_check"}
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 SOURCES = ["capi.hip", "msm.hip", "poly.hip", "harness.hip", "shm_hub.hip", "ring.hip", "shamir.hip", "lasso_witness.hip", "rw_memory_witness.hip", "rw_memory_leaves.hip", "ts_range_witness.hip", "bytecode_leaves.hip"]
-HEADERS = ["bytecode_arith.hip.hpp", os.path.join("host", "layer_tail.hpp"), os.path.join("host", "msm_schedule.hpp"), os.path.join("host", "spartan_pub_workers.hpp"), "fr9.hip.hpp", "fr9_consts.inc", os.path.join("host", "memcheck_steps.hpp"), os.path.join("host", "flow_harness.hpp"), os.path.join("host", "ts_range_proof.hpp"), os.path.join("host", "rw_memory_proof.hpp"), os.path.join("host", "rw_memory_proof_rep3.hpp"), os.path.join("host", "bytecode_proof.hpp"), os.path.join("host", "jolt_r1cs.hpp"), os.path.join("host", "spartan_jolt.hpp"), "spartan_inner.inc", "ff.hip.hpp", "prf.hip.hpp", "ff_macc.inc", "ff_mul2.inc", "ec.hip.hpp", "fq9.hip.hpp", "fq9_consts.inc", "fq9_mac.inc", "fq9_mul.inc", "common.hpp", "lasso_walk.hip.hpp", "radix_pass.hip.hpp", "poly.hip.hpp", "toggle_layer.inc", "spartan_group.inc", "sparse_layer.inc", "primary_sumcheck.inc", "primary_group.inc", "shamir_deal.hip.hpp", "spartan_outer.inc", "outer_group.inc", "logup.inc", "compact_open.inc", "output_check.inc", os.path.join("host", "memory_proof.hpp"), os.path.join("host", "wire.hpp"), os.path.join("host", "net.hpp"), os.path.join("host", "prover.hpp"), os.path.join("host", "sparse_rule.hpp"), os.path.join("host", "split.hpp"), os.path.join("host", "split_harness.hpp"), os.path.join("host", "spartan_harness.hpp"), os.path.join("host", "lookups_harness.hpp"), os.path.join("host", "outer_harness.hpp"), os.path.join("host", "runner.hpp"), os.path.join("host", "shamir_gp.hpp"), os.path.join("host", "shamir_harness.hpp"), os.path.join("host", "shamir_spartan.hpp"), os.path.join("host", "shamir_jolt_spartan.hpp"), os.path.join("host", "shamir_primary.hpp"), os.path.join("..", "..", "include", "cozk.h")]
+HEADERS = ["bytecode_arith.hip.hpp", os.path.join("host", "layer_tail.hpp"), os.path.join("host", "msm_schedule.hpp"), os.path.join("host", "spartan_pub_workers.hpp"), "fr9.hip.hpp", "fr9_consts.inc", os.path.join("host", "memcheck_steps.hpp"), os.path.join("host", "flow_harness.hpp"), os.path.join("host", "ts_range_proof.hpp"), os.path.join("host", "rw_memory_proof.hpp"), os.path.join("host", "rw_memory_proof_rep3.hpp"), os.path.join("host", "bytecode_proof.hpp"), os.path.join("host", "jolt_r1cs.hpp"), os.path.join("host", "spartan_jolt.hpp"), "spartan_inner.inc", "ff.hip.hpp", "prf.hip.hpp", "ff_macc.inc", "ff_mul2.inc", "ec.hip.hpp", "fq9.hip.hpp", "fq9_consts.inc", "fq9_mac.inc", "fq9_mul.inc", "common.hpp", "lasso_walk.hip.hpp", "radix_pass.hip.hpp", "poly.hip.hpp", "toggle_layer.inc", "spartan_group.inc", "sparse_layer.inc", "primary_sumcheck.inc", "primary_group.inc", "shamir_deal.hip.hpp", "spartan_outer.inc", "outer_group.inc", "logup.inc", "compact_open.inc", "output_check.inc", os.path.join("host", "memory_proof.hpp"), os.path.join("host", "memory_proof_rep3.hpp"), os.path.join("host", "wire.hpp"), os.path.join("host", "net.hpp"), os.path.join("host", "prover.hpp"), os.path.join("host", "sparse_rule.hpp"), os.path.join("host", "split.hpp"), os.path.join("host", "split_harness.hpp"), os.path.join("host", "spartan_harness.hpp"), os.path.join("host", "lookups_harness.hpp"), os.path.join("host", "outer_harness.hpp"), os.path.join("host", "runner.hpp"), os.path.join("host", "shamir_gp.hpp"), os.path.join("host", "shamir_harness.hpp"), os.path.join("host", "shamir_spartan.hpp"), os.path.join("host", "shamir_jolt_spartan.hpp"), os.path.join("host", "shamir_primary.hpp"), os.path.join("..", "..", "include", "cozk.h")]
 
 
 def _newer(target, deps):

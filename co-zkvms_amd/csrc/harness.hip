@@ -902,6 +902,7 @@ int cozk_worker_spartan_second_sumcheck(cozk_ctx* ctx, const cozk_worker_params*
 #include "host/rw_memory_proof.hpp"
 #include "host/rw_memory_proof_rep3.hpp"
 #include "host/memory_proof.hpp"
+#include "host/memory_proof_rep3.hpp"
 #include "host/bytecode_proof.hpp"
 #include "host/shamir_gp.hpp"
 #include "host/shamir_harness.hpp"

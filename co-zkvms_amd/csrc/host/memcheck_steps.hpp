@@ -187,6 +187,31 @@ std::vector<fe> prove_outputs_dense_worker(WorkerEnv& env, const cozk_poly* v_fi
     return prove_arbitrary_worker(env, Fr::zero(), log_mem, sp, 3).r;
 }
 
+struct OutputCheckH {
+    cozk_output_check* h = nullptr;
+    OutputCheckH() = default;
+    OutputCheckH(const OutputCheckH&) = delete;
+    OutputCheckH& operator=(const OutputCheckH&) = delete;
+    ~OutputCheckH() { cozk_output_check_free(h); }
+};
+
+// ... windowed: the same rounds by cozk_output_check_round / _final on a created handle (cozk_output_check_create on the compact column,
+// cozk_output_check_shared_create on a party's polynomial).  The device calls bind inside the next round call, so the loop's bind step
+// only keeps r.  any_shared: the handle is a REP3 party's, its round values are additive shares already.
+std::vector<fe> prove_outputs_windowed_worker(WorkerEnv& env, cozk_output_check* oc, int log_mem, bool any_shared) {
+    uint64_t pending[4];
+    bool have = false;
+    std::vector<fe> r = prove_arbitrary_rounds(
+        env, Fr::zero(), log_mem, 3, any_shared, [&](uint64_t* ev) { rc_check(cozk_output_check_round(oc, have ? pending : nullptr, ev), env.ctx, "output_check_round"); },
+        [&](const uint64_t rr[4]) {
+            memcpy(pending, rr, sizeof pending);
+            have = true;
+        });
+    uint64_t fin[12];
+    rc_check(cozk_output_check_final(oc, pending, fin), env.ctx, "output_check_final");  // the last bind, as prove_arbitrary_worker leaves its polynomials
+    return r;
+}
+
 // one opening of compact columns of one length at `point`: the claims, one exchange, the joint polynomial over the rho powers
 void compact_open_worker(WorkerEnv& env, Rep3ProverOpeningAccumulator& acc, const std::vector<const cozk_vec*>& cols, const std::vector<fe>& point, bool tamper_claim) {
     VecH chih = mc_eq_table(env, point);

@@ -23,14 +23,6 @@ struct cozk_memory_proof : HarnessHandle {
 
 namespace {
 
-struct OutputCheckH {
-    cozk_output_check* h = nullptr;
-    OutputCheckH() = default;
-    OutputCheckH(const OutputCheckH&) = delete;
-    OutputCheckH& operator=(const OutputCheckH&) = delete;
-    ~OutputCheckH() { cozk_output_check_free(h); }
-};
-
 struct MemoryProof {
     std::vector<PST13Commitment> commitments;
     MemCheckProof mem;
@@ -62,23 +54,12 @@ struct PhasePeak {
     uint64_t bytes() const { return (uint64_t)(ctx->pool.peak_bytes - live0) + (uint64_t)(ctx->scratch.cap + ctx->scratch2.cap - scratch0); }
 };
 
-// the output check's sumcheck, windowed: the device calls bind inside the next round call, so the loop's bind step only keeps r
+// the output check's sumcheck, windowed: the shared round loop (prove_outputs_windowed_worker, memcheck_steps.hpp) on the compact column's handle
 std::vector<fe> memory_proof_outputs_windowed(cozk_memory_proof* h, WorkerEnv& env, const RwProofParty& ps, const std::vector<fe>& r_eq) {
     const std::vector<uint64_t> wabi = to_abi(r_eq);
     OutputCheckH oc;
     rc_check(cozk_output_check_create(env.ctx, ps.v_final.h, h->v_io.h, (size_t)h->cfg.io_start, wabi.data(), &oc.h), env.ctx, "output_check_create");
-    uint64_t pending[4];
-    bool have = false;
-    std::vector<fe> r = prove_arbitrary_rounds(
-        env, Fr::zero(), h->cfg.log_mem, 3, false,
-        [&](uint64_t* ev) { rc_check(cozk_output_check_round(oc.h, have ? pending : nullptr, ev), env.ctx, "output_check_round"); },
-        [&](const uint64_t rr[4]) {
-            memcpy(pending, rr, sizeof pending);
-            have = true;
-        });
-    uint64_t fin[12];
-    rc_check(cozk_output_check_final(oc.h, pending, fin), env.ctx, "output_check_final");  // the last bind, as prove_arbitrary_worker leaves its polynomials
-    return r;
+    return prove_outputs_windowed_worker(env, oc.h, h->cfg.log_mem, false);
 }
 
 // ... dense: the flow's composition on Fr copies
@@ -177,33 +158,46 @@ void memory_proof_setup(cozk_memory_proof* h) {
     HIP_TRY(hipStreamSynchronize(ctx->stream));
 }
 
+// what create checks of h->cfg and builds from it, for this harness and the three-party one (`who` names the harness in the refusals)
+void memory_proof_build(cozk_memory_proof* h, const std::string& who) {
+    const cozk_memory_proof_config* cfg = &h->cfg;
+    cozk_rw_proof_config& rc = h->rw.cfg;
+    rc.mode = cfg->mode, rc.device = cfg->device, rc.log_n = cfg->log_n, rc.log_mem = cfg->log_mem, rc.n_slots = cfg->n_slots, rc.seed = cfg->seed;
+    rc.precompute = cfg->precompute, rc.with_ts = cfg->with_ts, rc.leaves_fused = cfg->leaves_fused, rc.tamper = cfg->tamper;
+    rw_proof_check_config(rc, who, 4);
+    COZK_REQUIRE(cfg->io_len >= 1, who + ": io_len is at least 1 word");
+    const uint64_t MEM = (uint64_t)1 << cfg->log_mem;
+    COZK_REQUIRE(cfg->io_start <= MEM && cfg->io_len <= MEM - cfg->io_start, who + ": io_start + io_len > MEM");
+    COZK_REQUIRE(cfg->windowed == 0 || cfg->windowed == 1, who + ": windowed is 0 or 1");
+    if (rc.tamper == 4) rc.tamper = 0;  // tamper 4 is the output check's: the witness is honest
+    rw_proof_build(&h->rw, who);
+    memory_proof_setup(h);
+}
+
+// destroy, in two steps: the harness's own vectors while party 0's context stands (the three-party harness releases its parties between
+// the two), then the read-write proof's state
+void memory_proof_release_vectors(cozk_memory_proof* h) {
+    if (!h->rw.parties.empty() && h->rw.parties[0].ctx) (void)hipSetDevice(h->rw.parties[0].ctx->device);
+    for (VecH* v : {&h->v_io, &h->io_range_fr, &h->v_io_fr, &h->v_final_fr}) *v = VecH();
+}
+void memory_proof_release(cozk_memory_proof* h) {
+    memory_proof_release_vectors(h);
+    rw_proof_release(&h->rw);
+}
+
 }  // namespace
 
 extern "C" {
 
 int cozk_memory_proof_create(const cozk_memory_proof_config* cfg, cozk_memory_proof** out) {
-    return harness_create(cfg, out, [&](cozk_memory_proof* h) {
-        cozk_rw_proof_config& rc = h->rw.cfg;
-        rc.mode = cfg->mode, rc.device = cfg->device, rc.log_n = cfg->log_n, rc.log_mem = cfg->log_mem, rc.n_slots = cfg->n_slots, rc.seed = cfg->seed;
-        rc.precompute = cfg->precompute, rc.with_ts = cfg->with_ts, rc.leaves_fused = cfg->leaves_fused, rc.tamper = cfg->tamper;
-        rw_proof_check_config(rc, "memory_proof", 4);
-        COZK_REQUIRE(cfg->io_len >= 1, "memory_proof: io_len is at least 1 word");
-        const uint64_t MEM = (uint64_t)1 << cfg->log_mem;
-        COZK_REQUIRE(cfg->io_start <= MEM && cfg->io_len <= MEM - cfg->io_start, "memory_proof: io_start + io_len > MEM");
-        COZK_REQUIRE(cfg->windowed == 0 || cfg->windowed == 1, "memory_proof: windowed is 0 or 1");
-        if (rc.tamper == 4) rc.tamper = 0;  // tamper 4 is the output check's: the witness is honest
-        rw_proof_build(&h->rw, "memory_proof");
-        memory_proof_setup(h);
-    });
+    return harness_create(cfg, out, [&](cozk_memory_proof* h) { memory_proof_build(h, "memory_proof"); });
 }
 
 const char* cozk_memory_proof_error(const cozk_memory_proof* h) { return harness_error(h); }
 
 int cozk_memory_proof_destroy(cozk_memory_proof* h) {
     if (!h) return COZK_OK;
-    if (!h->rw.parties.empty() && h->rw.parties[0].ctx) (void)hipSetDevice(h->rw.parties[0].ctx->device);
-    for (VecH* v : {&h->v_io, &h->io_range_fr, &h->v_io_fr, &h->v_final_fr}) *v = VecH();
-    rw_proof_release(&h->rw);
+    memory_proof_release(h);
     delete h;
     return COZK_OK;
 }

@@ -6,7 +6,8 @@
 // rw_proof_verify checks it, so the proof is byte for byte the plain proof of the same seed and the multiset check runs.  Every step is
 // one of memcheck_steps.hpp / prover.hpp; what is new is the sharing of the secret columns at create, the leaves from
 // cozk_rw_memory_shared_leaves / cozk_rw_memory_shared_init_final_leaves, and the openings that join public compact columns with
-// shared polynomials.  Not here: the timestamp range check and the output check by Rep3 parties, one party per process.
+// shared polynomials.  cozk_memory_proof_rep3 (memory_proof_rep3.hpp) runs the same steps with the output check behind them.  Not here
+// (DESIGN 7): the timestamp range check by Rep3 parties, one party per process.
 #pragma once
 
 struct RwRep3Party : HarnessParty {
@@ -62,10 +63,9 @@ PolyH rw3_share_column(RwRep3Party& ps, const cozk_vec* col, uint64_t seed) {
 }
 
 // create, after party 0's plain harness stands: every party gets the public columns and its shares of the secret ones
-void rw3_setup(cozk_rw_proof_rep3* h) {
-    const cozk_rw_proof_rep3_config& c = h->cfg;
-    RwProofParty& p0 = h->plain.parties[0];
-    const size_t ns = (size_t)h->plain.ns;
+void rw3_setup(cozk_rw_proof& plain, const cozk_rw_proof_rep3_config& c, std::vector<RwRep3Party>& parties) {
+    RwProofParty& p0 = plain.parties[0];
+    const size_t ns = (size_t)plain.ns;
     // the dealer's columns on the host, once: public ones for parties 1 and 2, secret ones for every party's sharing
     std::vector<Rw3HostCol> addr, t_read, v_read, v_written(ns);
     for (size_t s = 0; s < ns; s++) {
@@ -75,9 +75,9 @@ void rw3_setup(cozk_rw_proof_rep3* h) {
         if (p0.v_written[s].h) v_written[s] = rw3_download(p0.ctx, p0.v_written[s].h);
     }
     const Rw3HostCol t_final = rw3_download(p0.ctx, p0.t_final.h), v_final = rw3_download(p0.ctx, p0.v_final.h), v_init = rw3_download(p0.ctx, p0.v_init.h);
-    h->parties.resize(3);
+    parties.resize(3);
     for (int p = 0; p < 3; p++) {
-        RwRep3Party& ps = h->parties[(size_t)p];
+        RwRep3Party& ps = parties[(size_t)p];
         ps.party = p;
         if (p == 0) {
             ps.ctx = p0.ctx;  // the plain harness owns it
@@ -124,10 +124,10 @@ void rw3_setup(cozk_rw_proof_rep3* h) {
             if (p == 0) {
                 ps.iota_n = p0.iota_n.h, ps.iota_mem = p0.iota_mem.h;
             } else {
-                std::vector<uint32_t> io(std::max(h->plain.N, h->plain.MEM));
+                std::vector<uint32_t> io(std::max(plain.N, plain.MEM));
                 for (size_t j = 0; j < io.size(); j++) io[j] = (uint32_t)j;
-                ps.iota_n = keep(upload_vec(ps.ctx, io.data(), h->plain.N, COZK_SCALAR_U32, "vec_upload(iota)"));
-                ps.iota_mem = keep(upload_vec(ps.ctx, io.data(), h->plain.MEM, COZK_SCALAR_U32, "vec_upload(iota)"));
+                ps.iota_n = keep(upload_vec(ps.ctx, io.data(), plain.N, COZK_SCALAR_U32, "vec_upload(iota)"));
+                ps.iota_mem = keep(upload_vec(ps.ctx, io.data(), plain.MEM, COZK_SCALAR_U32, "vec_upload(iota)"));
             }
         }
         HIP_TRY(hipStreamSynchronize(ps.ctx->stream));
@@ -184,11 +184,12 @@ void rw3_open_worker(WorkerEnv& env, Rep3ProverOpeningAccumulator& acc, const st
     acc.append_joint(env, PolyH(batched), chih.h, point, batched_claim);
 }
 
-void rw3_worker_main(cozk_rw_proof_rep3* h, RwRep3Party& ps, StarNetWorker* star, RingNet* ring) {
-    const cozk_rw_proof_rep3_config& c = h->cfg;
-    const size_t ns = (size_t)h->plain.ns, N = h->plain.N, MEM = h->plain.MEM;
-    WorkerEnv env = make_worker_env(ps.ctx, COZK_MODE_REP3, ps.party, star, ring, &c.seed);
-    Rep3ProverOpeningAccumulator acc;
+// Steps 1-4 of the worker, shared with cozk_memory_proof_rep3 (memory_proof_rep3.hpp): the commit, gamma and tau, the leaves, the two
+// grand products and the two openings into `acc`.  Sets t_commit, t_leaves and t_gp; returns the clock taken after the grand products
+// (the openings belong to t_open).
+double rw3_memory_check_worker(cozk_rw_proof& plain, const cozk_rw_proof_rep3_config& c, RwRep3Party& ps, WorkerEnv& env, Rep3ProverOpeningAccumulator& acc) {
+    const size_t ns = (size_t)plain.ns, N = plain.N, MEM = plain.MEM;
+    StarNetWorker* star = env.star;
     // the plain proof's column order: addr, v_read, v_written (the slots that write), t_read | v_final, t_final
     std::vector<LeafTerm> rw_order, if_order;
     for (size_t s = 0; s < ns; s++) rw_order.push_back(mc_col_term(ps.addr[s]));
@@ -248,32 +249,48 @@ void rw3_worker_main(cozk_rw_proof_rep3* h, RwRep3Party& ps, StarNetWorker* star
     mc_memory_checking(env, mc_leaves_to_layer(env, rw), 2 * ns, ToggleH(), mc_leaves_to_layer(env, inf), 2, r_rw, r_if);
     const double t4 = now_ms();
     ps.t_gp = t4 - t3;
-    // ---- 4. the two openings, 5. ONE reduce_and_prove
+    // ---- 4. the two openings
     rw3_open_worker(env, acc, rw_order, r_rw, c.tamper == 2);
     rw3_open_worker(env, acc, if_order, r_if, false);
+    return t4;
+}
+
+// Step 5, shared likewise: ONE reduce_and_prove over every opening in `acc`.  t45: what the openings before this call took.  Sets t_open.
+void rw3_open_and_finish_worker(RwRep3Party& ps, WorkerEnv& env, Rep3ProverOpeningAccumulator& acc, double t45) {
+    const double t5 = now_ms();
     acc.reduce_and_prove_worker(env, *ps.setup);
-    ps.t_open = now_ms() - t4;
-    ps.record_net(star, ring);
+    ps.t_open = t45 + (now_ms() - t5);
+    ps.record_net(env.star, env.ring);
+}
+
+void rw3_worker_main(cozk_rw_proof_rep3* h, RwRep3Party& ps, StarNetWorker* star, RingNet* ring) {
+    WorkerEnv env = make_worker_env(ps.ctx, COZK_MODE_REP3, ps.party, star, ring, &h->cfg.seed);
+    Rep3ProverOpeningAccumulator acc;
+    const double t4 = rw3_memory_check_worker(h->plain, h->cfg, ps, env, acc);
+    rw3_open_and_finish_worker(ps, env, acc, now_ms() - t4);
+}
+
+// the commitments combined over the three parties, into the proof and the transcript
+void rw3_coordinate_commitments(StarNetCoordinator& net, Transcript& tr, std::vector<PST13Commitment>& commitments) {
+    std::vector<Bytes> msgs = net.receive_responses();
+    std::vector<Reader> rds;
+    for (auto& m : msgs) rds.emplace_back(m);
+    commitments = combine_commitments_from_parties(rds, 3);
+    for (auto& cm : commitments) tr.append_point(cm.g_product);
 }
 
 // the coordinator: cozk_rw_proof's with the commitments combined over the three parties
 void rw3_coordinate(cozk_rw_proof_rep3* h, StarNetCoordinator& net, RwProof& proof) {
     const cozk_rw_proof_config& c = h->plain.cfg;
     Transcript tr("cozk-rw-memory");
-    {
-        std::vector<Bytes> msgs = net.receive_responses();
-        std::vector<Reader> rds;
-        for (auto& m : msgs) rds.emplace_back(m);
-        proof.commitments = combine_commitments_from_parties(rds, 3);
-        for (auto& cm : proof.commitments) tr.append_point(cm.g_product);
-    }
+    rw3_coordinate_commitments(net, tr, proof.commitments);
     mc_broadcast_gamma_tau(net, tr);
     mc_coordinate_memory_checking(net, tr, proof.mem, (size_t)c.log_n, false, (size_t)c.log_mem);
     rw_proof_coordinate_range_check_and_open(c, net, tr, proof.with_ts, proof.range, proof.reduced);
 }
 
-void rw3_release(cozk_rw_proof_rep3* h) {
-    for (RwRep3Party& ps : h->parties) {
+void rw3_release(cozk_rw_proof& plain, std::vector<RwRep3Party>& parties) {
+    for (RwRep3Party& ps : parties) {
         if (ps.ctx) (void)hipSetDevice(ps.ctx->device);
         ps.v_init = PolyH(), ps.v_final = PolyH();
         ps.v_read.clear(), ps.v_written.clear(), ps.commit_views.clear(), ps.own.clear();
@@ -281,8 +298,8 @@ void rw3_release(cozk_rw_proof_rep3* h) {
         if (ps.own_ctx && ps.ctx) cozk_ctx_destroy(ps.ctx);
         ps.ctx = nullptr;
     }
-    h->parties.clear();
-    rw_proof_release(&h->plain);
+    parties.clear();
+    rw_proof_release(&plain);
 }
 
 }  // namespace
@@ -297,7 +314,7 @@ int cozk_rw_proof_rep3_create(const cozk_rw_proof_rep3_config* cfg, cozk_rw_proo
         pc.precompute = cfg->precompute, pc.with_ts = 0, pc.leaves_fused = cfg->leaves_fused, pc.tamper = cfg->tamper;
         rw_proof_check_config(pc, "rw_proof_rep3", 2);
         rw_proof_build(&h->plain, "rw_proof_rep3");  // the instance on party 0's context, tamper 1 included
-        rw3_setup(h);
+        rw3_setup(h->plain, h->cfg, h->parties);
         h->built = true;
     });
 }
@@ -306,7 +323,7 @@ const char* cozk_rw_proof_rep3_error(const cozk_rw_proof_rep3* h) { return harne
 
 int cozk_rw_proof_rep3_destroy(cozk_rw_proof_rep3* h) {
     if (!h) return COZK_OK;
-    rw3_release(h);
+    rw3_release(h->plain, h->parties);
     delete h;
     return COZK_OK;
 }

@@ -44,6 +44,21 @@
 // Device memory of a handle (from the context's pool, allocated in create, nothing later): lw < m: MEM / 2 Fr entries for the folds
 // plus two W'-entry Fr vectors (Llow, which becomes E, and R); lw == m: three MEM-entry Fr vectors (the dense composition's).  No Fr
 // vector of MEM entries exists unless W' = MEM.  v_final and v_io are only read and must outlive the handle.
+//
+// The shared form (cozk_output_check_shared_create): v_final is a polynomial, PLAIN (one Fr component a) or a party's REP3 share (a, b).
+// Everything the check sends is linear in the share and a party's message is the additive share (a + b) 2^-1 (into_additive; k_prod_round<2, M>
+// with finish_sums' TWO_INV), so the party needs ONE Fr vector
+//     T[x] = a[x] + b[x] (REP3), a[x] (PLAIN);   d[x] = T[x] - sub v_io[x - lo] inside the window, T[x] outside,
+// sub = 1 for PLAIN and REP3 parties 0 and 1, 0 for REP3 party 2: cozk_poly_linear_combination puts a public term into party 0's a and
+// party 1's b, so a + b loses v_io once for parties 0 and 1 and never for party 2; over the three parties the sum is 2 (v_final - v_io).
+// On d everything above applies unchanged; for REP3 the host multiplies the three round values and d's final value by 2^-1.  Every value
+// is canonical, so a party's bytes are those of cozk_prod_sumcheck_evals / cozk_poly_bind / into_additive on the dense polynomials.
+//   k_ocs_dots0<NC>        round 0: per side sum Llow T[y], sum Llow T[y + h] (Fr::mul), sum Llow v_io (exact)   reads W (32 + NC 64 + 4) B
+//   k_ocs_first_fold<NC>   D_1 from the components                              reads MEM NC 32 B (+ W 4 B), writes MEM / 2 * 32 B
+//   k_ocs_materialise<NC>  W' = MEM: d and the range as Fr                              reads MEM NC 32 B (+ W 4 B), writes MEM 64 B
+// NC the components; every later round runs the kernels above on the Fr fold.  With sub = 0 no v_io entry is read and the kernels get a
+// null v_io: the branch is uniform over the launch (as pub_a / pub_b of k_bc_if_leaves).  The exact v_io row of k_ocs_dots0 adds fewer
+// than 2^32 terms below 2^288 each: below 2^320 in CO_LIMBS = 11 limbs; k_ocs_first_fold's at most two terms stay below 2^289.
 
 struct OcSides {
     size_t lo[2], hi[2];  // side s = [lo[s], hi[s]); an unused side is empty
@@ -52,6 +67,9 @@ struct OcSides {
 struct cozk_output_check {
     cozk_ctx* ctx = nullptr;
     const uint32_t *vf = nullptr, *vio = nullptr;  // borrowed
+    const fe *ta = nullptr, *tb = nullptr;         // the shared form: v_final's components, borrowed (tb null: one component); vf is null
+    bool sub = true;                               // the shared form: this party's d loses v_io inside the window
+    bool rep3 = false;                             // REP3: the round values and d's final value are times 2^-1
     int m = 0, lw = 0, k = 0;                      // k variables are bound
     bool started = false;                          // round 0 has been asked for
     size_t lo = 0, hi = 0, len = 0;                // len = 2^(m - k)
@@ -158,6 +176,76 @@ __global__ void __launch_bounds__(PT) k_oc_dots_fr(const fe* __restrict__ D, con
     if (threadIdx.x == 0) fe_store(partial + (2 * (size_t)blockIdx.y + 1) * gridDim.x + blockIdx.x, sb);
 }
 
+// ---- the shared form: v_final as NC Fr components, T = a (+ b)
+template <int NC>
+static __device__ __forceinline__ fe ocs_T(const fe* __restrict__ ta, const fe* __restrict__ tb, size_t x) {
+    const fe a = fe_load(ta + x);
+    if (NC == 1) return a;
+    return Fr::add(a, fe_load(tb + x));
+}
+
+// round 0.  Side s = blockIdx.y: partial rows 3 s + {0, 1, 2} = sum Llow[x mod W'] {T[x mod h], T[(x mod h) + h], v_io[x - lo]} over the
+// side's words x; the T rows as k_oc_dots_fr, the v_io row exact as k_oc_dots_u32 (0 with sub = 0: vio is null and is not read).
+// x < MEM = 2 h, so (x mod h) + h < MEM; x - lo < W; x mod W' < W'.
+template <int NC>
+__global__ void __launch_bounds__(PT) k_ocs_dots0(const fe* __restrict__ ta, const fe* __restrict__ tb, const uint32_t* __restrict__ vio, int sub,
+                                                  const fe* __restrict__ Llow, size_t lo, OcSides sides, size_t h, size_t wmask, fe* __restrict__ partial) {
+    __shared__ fe sh4[4];
+    __shared__ uint32_t raw[PT / 64][1][CO_LIMBS];
+    fe A = Fr::zero(), B = Fr::zero();
+    uint32_t acc[1][CO_LIMBS];
+#pragma unroll
+    for (int l = 0; l < CO_LIMBS; l++) acc[0][l] = 0;
+    const size_t end = sides.hi[blockIdx.y];
+    for (size_t x = sides.lo[blockIdx.y] + (size_t)blockIdx.x * PT + threadIdx.x; x < end; x += (size_t)gridDim.x * PT) {
+        const fe L = fe_load(Llow + (x & wmask));
+        const size_t y = x & (h - 1);
+        A = Fr::add(A, Fr::mul(L, ocs_T<NC>(ta, tb, y)));
+        B = Fr::add(B, Fr::mul(L, ocs_T<NC>(ta, tb, y + h)));
+        if (sub) co_mac<0>(acc[0], L, vio[x - lo]);
+    }
+    const fe sa = fr_block_sum(A, sh4);
+    if (threadIdx.x == 0) fe_store(partial + (3 * (size_t)blockIdx.y) * gridDim.x + blockIdx.x, sa);
+    const fe sb = fr_block_sum(B, sh4);
+    if (threadIdx.x == 0) fe_store(partial + (3 * (size_t)blockIdx.y + 1) * gridDim.x + blockIdx.x, sb);
+    oc_exact_block_sums<1>(acc, raw, partial, 3 * (size_t)blockIdx.y + 2);
+}
+
+// D_1[y] = T[y] + r (T[y + h] - T[y]) minus the window terms (1 - r) v_io[y - lo] where y is in the window and r v_io[y + h - lo] where
+// y + h is, y < h = MEM / 2: a = 1 - r, b = r (Montgomery).  One lane per entry; y + h < 2 h = MEM, and an index into v_io is taken only
+// inside [lo, hi), so it is below W.  sub = 0: no window term (vio is null and is not read).
+template <int NC>
+__global__ void __launch_bounds__(PT) k_ocs_first_fold(const fe* __restrict__ ta, const fe* __restrict__ tb, const uint32_t* __restrict__ vio, int sub, size_t lo,
+                                                       size_t hi, size_t h, fe a, fe b, fe* __restrict__ D) {
+    const size_t y = (size_t)blockIdx.x * PT + threadIdx.x;
+    if (y >= h) return;
+    const fe t0 = ocs_T<NC>(ta, tb, y), t1 = ocs_T<NC>(ta, tb, y + h);
+    fe v = Fr::add(t0, Fr::mul(Fr::sub(t1, t0), b));
+    const bool in_lo = y >= lo && y < hi, in_hi = y + h >= lo && y + h < hi;
+    if (sub && (in_lo || in_hi)) {
+        uint32_t neg[CO_LIMBS];
+#pragma unroll
+        for (int l = 0; l < CO_LIMBS; l++) neg[l] = 0;
+        if (in_lo) co_mac<0>(neg, a, vio[y - lo]);
+        if (in_hi) co_mac<0>(neg, b, vio[y + h - lo]);
+        v = Fr::sub(v, co_reduce(neg));
+    }
+    fe_store(D + y, v);
+}
+
+// W' = MEM: D[x] = d[x], R[x] = io_range(x) as Fr; x < n = MEM, and x - lo < W inside the window
+template <int NC>
+__global__ void __launch_bounds__(PT) k_ocs_materialise(const fe* __restrict__ ta, const fe* __restrict__ tb, const uint32_t* __restrict__ vio, int sub, size_t lo,
+                                                        size_t hi, size_t n, fe* __restrict__ D, fe* __restrict__ Rg) {
+    const size_t x = (size_t)blockIdx.x * PT + threadIdx.x;
+    if (x >= n) return;
+    const bool in = x >= lo && x < hi;
+    fe v = ocs_T<NC>(ta, tb, x);
+    if (sub && in) v = Fr::sub(v, Fr::from_u64(vio[x - lo]));
+    fe_store(D + x, v);
+    fe_store(Rg + x, in ? Fr::one() : Fr::zero());
+}
+
 // a side lies inside one W'-aligned block: its positions mod W' are [lo mod W', lo mod W' + (hi - lo))
 static __device__ __forceinline__ int oc_side_at(const OcSides& sides, size_t i, size_t wmask) {
 #pragma unroll
@@ -236,19 +324,22 @@ static void oc_round_evals(cozk_output_check* oc, uint64_t out[12]) {
         tab.a[0] = oc->E, tab.a[1] = oc->Rg, tab.a[2] = oc->D;
         k_prod_round<1, 3><<<gx, PT, 0, ctx->stream>>>(tab, -1, h, 3, sl.partial);
         HIP_TRY(hipGetLastError());
-        finish_sums(ctx, sl, 3, gx, Fr::one(), 0, ev);
+        finish_sums(ctx, sl, 3, gx, oc->rep3 ? fr_two_inv() : Fr::one(), oc->rep3 ? 1 : 0, ev);
     } else {
         const int k = oc->k;
         const size_t wmask = ((size_t)1 << oc->lw) - 1;
         fe A[2] = {Fr::zero(), Fr::zero()}, B[2] = {Fr::zero(), Fr::zero()};
         if (oc->d_is_cols) {
-            const unsigned gx = oc_longest_side(oc, CO_LANE_TERMS);
+            const unsigned gx = oc_longest_side(oc, oc->ta ? 1 : CO_LANE_TERMS);  // the shared form's T rows are k_oc_dots_fr's
             const SumLaunch sl = sum_launch(ctx, 6, gx, 6);
-            k_oc_dots_u32<<<dim3(gx, 2), PT, 0, ctx->stream>>>(oc->vf, oc->vio, oc->E, oc->lo, oc->sides, h, wmask, sl.partial);
+            const uint32_t* vio = oc->sub ? oc->vio : nullptr;
+            if (oc->tb) k_ocs_dots0<2><<<dim3(gx, 2), PT, 0, ctx->stream>>>(oc->ta, oc->tb, vio, oc->sub, oc->E, oc->lo, oc->sides, h, wmask, sl.partial);
+            else if (oc->ta) k_ocs_dots0<1><<<dim3(gx, 2), PT, 0, ctx->stream>>>(oc->ta, nullptr, vio, oc->sub, oc->E, oc->lo, oc->sides, h, wmask, sl.partial);
+            else k_oc_dots_u32<<<dim3(gx, 2), PT, 0, ctx->stream>>>(oc->vf, oc->vio, oc->E, oc->lo, oc->sides, h, wmask, sl.partial);
             HIP_TRY(hipGetLastError());
             fe s[6];
             finish_sums(ctx, sl, 6, gx, Fr::one(), 0, s);
-            for (int sd = 0; sd < oc->nside; sd++) {  // the window's own half loses the v_io sum
+            for (int sd = 0; sd < oc->nside; sd++) {  // the window's own half loses the v_io sum (0 in the shared form with sub = 0)
                 const bool up = oc_bit(oc, sd, 0) != 0;
                 A[sd] = up ? s[3 * sd] : Fr::sub(s[3 * sd], s[3 * sd + 2]);
                 B[sd] = up ? Fr::sub(s[3 * sd + 1], s[3 * sd + 2]) : s[3 * sd + 1];
@@ -279,6 +370,7 @@ static void oc_round_evals(cozk_output_check* oc, uint64_t out[12]) {
                 acc = Fr::add(acc, Fr::mul(Fr::mul(HR[sd], oc_bit(oc, sd, k) ? t : omt), line));
             }
             ev[e] = Fr::mul(Fr::mul(oc->c, l), acc);
+            if (oc->rep3) ev[e] = Fr::mul(ev[e], fr_two_inv());
         }
     }
     for (int e = 0; e < 3; e++) fe_to_u64x4(ev[e], out + 4 * e);
@@ -292,7 +384,10 @@ static void oc_bind(cozk_output_check* oc, const fe& r) {
     if (oc_sparse(oc)) {
         const int k = oc->k;
         const fe omr = Fr::sub(one, r);
-        if (oc->d_is_cols) k_oc_first_fold<<<grid_for(h), PT, 0, ctx->stream>>>(oc->vf, oc->vio, oc->lo, oc->hi, h, omr, r, oc->D);
+        const uint32_t* vio = oc->sub ? oc->vio : nullptr;
+        if (oc->d_is_cols && oc->tb) k_ocs_first_fold<2><<<grid_for(h), PT, 0, ctx->stream>>>(oc->ta, oc->tb, vio, oc->sub, oc->lo, oc->hi, h, omr, r, oc->D);
+        else if (oc->d_is_cols && oc->ta) k_ocs_first_fold<1><<<grid_for(h), PT, 0, ctx->stream>>>(oc->ta, nullptr, vio, oc->sub, oc->lo, oc->hi, h, omr, r, oc->D);
+        else if (oc->d_is_cols) k_oc_first_fold<<<grid_for(h), PT, 0, ctx->stream>>>(oc->vf, oc->vio, oc->lo, oc->hi, h, omr, r, oc->D);
         else k_fold_halves<<<grid_for(h), PT, 0, ctx->stream>>>(oc->D, h, r);
         HIP_TRY(hipGetLastError());
         oc->d_is_cols = false;
@@ -313,6 +408,46 @@ static void oc_bind(cozk_output_check* oc, const fe& r) {
     }
 }
 
+// What both creates do once their arguments stand: the window's geometry, the handle's device memory, Llow, and with W' = MEM the dense
+// vectors.  `src` carries the borrowed sources (vf and vio, or ta, tb and vio with sub and rep3) and nothing else.
+static cozk_output_check* oc_build(cozk_ctx* ctx, const cozk_output_check& src, size_t MEM, size_t W, size_t io_start, const uint64_t* r_eq) {
+    cozk_output_check* oc = new cozk_output_check(src);
+    oc->ctx = ctx;
+    oc->m = __builtin_ctzll(MEM);
+    while (((size_t)1 << oc->lw) < W) oc->lw++;
+    oc->lo = io_start, oc->hi = io_start + W, oc->len = MEM;
+    const size_t Wp = (size_t)1 << oc->lw;
+    const size_t c = (io_start / Wp + 1) * Wp;  // the one multiple of W' the window can hold inside
+    oc->nside = c < oc->hi ? 2 : 1;
+    oc->sides.lo[0] = io_start, oc->sides.hi[0] = c < oc->hi ? c : oc->hi;
+    oc->sides.lo[1] = oc->sides.hi[1] = oc->hi;
+    if (oc->nside == 2) oc->sides.lo[1] = c;
+    oc->r_eq.resize((size_t)oc->m);
+    for (int i = 0; i < oc->m; i++) oc->r_eq[(size_t)i] = fe_from_u64x4(r_eq + 4 * i);
+    oc->c = oc->rho[0] = oc->rho[1] = Fr::one();
+    try {
+        const bool dense = oc->lw == oc->m;
+        oc->D = dev_alloc_fe(dense ? MEM : MEM / 2);
+        oc->E = dev_alloc_fe(Wp);
+        oc->Rg = dev_alloc_fe(Wp);
+        if (oc->lw > 13) ctx->scratch2.reserve(Wp * sizeof(fe));
+        eq_evals_device(ctx, oc->r_eq.data() + (oc->m - oc->lw), oc->lw, oc->E, ctx->scratch2.as<fe>());  // Llow; with lw == m it is E
+        if (dense) {
+            const uint32_t* vio = oc->sub ? oc->vio : nullptr;
+            if (oc->tb) k_ocs_materialise<2><<<grid_for(MEM), PT, 0, ctx->stream>>>(oc->ta, oc->tb, vio, oc->sub, oc->lo, oc->hi, MEM, oc->D, oc->Rg);
+            else if (oc->ta) k_ocs_materialise<1><<<grid_for(MEM), PT, 0, ctx->stream>>>(oc->ta, nullptr, vio, oc->sub, oc->lo, oc->hi, MEM, oc->D, oc->Rg);
+            else k_oc_materialise<<<grid_for(MEM), PT, 0, ctx->stream>>>(oc->vf, oc->vio, oc->lo, oc->hi, MEM, oc->D, oc->Rg);
+            HIP_TRY(hipGetLastError());
+            oc->d_is_cols = false;
+        }
+    } catch (...) {
+        oc_release(oc);
+        delete oc;
+        throw;
+    }
+    return oc;
+}
+
 extern "C" {
 
 int cozk_output_check_create(cozk_ctx* ctx, const cozk_vec* v_final, const cozk_vec* v_io, size_t io_start, const uint64_t* r_eq, cozk_output_check** out) {
@@ -328,39 +463,32 @@ int cozk_output_check_create(cozk_ctx* ctx, const cozk_vec* v_final, const cozk_
         COZK_REQUIRE(io_start <= MEM && W <= MEM - io_start, "output_check_create: io_start + io_len > MEM");
         COZK_REQUIRE(v_final->ctx && v_io->ctx && v_final->ctx->device == ctx->device && v_io->ctx->device == ctx->device,
                      "output_check_create: v_final and v_io live on the context's device");
-        cozk_output_check* oc = new cozk_output_check();
-        oc->ctx = ctx;
-        oc->vf = (const uint32_t*)v_final->d, oc->vio = (const uint32_t*)v_io->d;
-        oc->m = __builtin_ctzll(MEM);
-        while (((size_t)1 << oc->lw) < W) oc->lw++;
-        oc->lo = io_start, oc->hi = io_start + W, oc->len = MEM;
-        const size_t Wp = (size_t)1 << oc->lw;
-        const size_t c = (io_start / Wp + 1) * Wp;  // the one multiple of W' the window can hold inside
-        oc->nside = c < oc->hi ? 2 : 1;
-        oc->sides.lo[0] = io_start, oc->sides.hi[0] = c < oc->hi ? c : oc->hi;
-        oc->sides.lo[1] = oc->sides.hi[1] = oc->hi;
-        if (oc->nside == 2) oc->sides.lo[1] = c;
-        oc->r_eq.resize((size_t)oc->m);
-        for (int i = 0; i < oc->m; i++) oc->r_eq[(size_t)i] = fe_from_u64x4(r_eq + 4 * i);
-        oc->c = oc->rho[0] = oc->rho[1] = Fr::one();
-        try {
-            const bool dense = oc->lw == oc->m;
-            oc->D = dev_alloc_fe(dense ? MEM : MEM / 2);
-            oc->E = dev_alloc_fe(Wp);
-            oc->Rg = dev_alloc_fe(Wp);
-            if (oc->lw > 13) ctx->scratch2.reserve(Wp * sizeof(fe));
-            eq_evals_device(ctx, oc->r_eq.data() + (oc->m - oc->lw), oc->lw, oc->E, ctx->scratch2.as<fe>());  // Llow; with lw == m it is E
-            if (dense) {
-                k_oc_materialise<<<grid_for(MEM), PT, 0, ctx->stream>>>(oc->vf, oc->vio, oc->lo, oc->hi, MEM, oc->D, oc->Rg);
-                HIP_TRY(hipGetLastError());
-                oc->d_is_cols = false;
-            }
-        } catch (...) {
-            oc_release(oc);
-            delete oc;
-            throw;
-        }
-        *out = oc;
+        cozk_output_check src;
+        src.vf = (const uint32_t*)v_final->d, src.vio = (const uint32_t*)v_io->d;
+        *out = oc_build(ctx, src, MEM, W, io_start, r_eq);
+    });
+}
+
+int cozk_output_check_shared_create(cozk_ctx* ctx, const cozk_poly* v_final, const cozk_vec* v_io, size_t io_start, const uint64_t* r_eq, int party,
+                                    cozk_output_check** out) {
+    if (out) *out = nullptr;
+    return cozk_guard(ctx, [&] {
+        COZK_REQUIRE(ctx && v_final && v_io && r_eq && out, "output_check_shared_create: null argument");
+        const size_t MEM = v_final->len;
+        COZK_REQUIRE(MEM >= 2 && (MEM & (MEM - 1)) == 0 && MEM < ((size_t)1 << 32), "output_check_shared_create: v_final has 2^m entries, 1 <= m < 32");
+        COZK_REQUIRE(v_final->cur < 0, "output_check_shared_create: v_final is bound");
+        const bool rep3 = v_final->mode == COZK_MODE_REP3;
+        COZK_REQUIRE(party >= 0 && party <= (rep3 ? 2 : 0), "output_check_shared_create: party is 0..2 for a REP3 v_final and 0 for a PLAIN one");
+        COZK_REQUIRE(v_io->kind == COZK_SCALAR_U32, "output_check_shared_create: v_io is a U32 vector");
+        const size_t W = v_io->n;
+        COZK_REQUIRE(W >= 1, "output_check_shared_create: io_len is 0");
+        COZK_REQUIRE(io_start <= MEM && W <= MEM - io_start, "output_check_shared_create: io_start + io_len > MEM");
+        COZK_REQUIRE(v_final->ctx && v_io->ctx && v_final->ctx->device == ctx->device && v_io->ctx->device == ctx->device,
+                     "output_check_shared_create: v_final and v_io live on the context's device");
+        cozk_output_check src;
+        src.ta = v_final->a0, src.tb = rep3 ? v_final->b0 : nullptr, src.vio = (const uint32_t*)v_io->d;
+        src.rep3 = rep3, src.sub = !(rep3 && party == 2);
+        *out = oc_build(ctx, src, MEM, W, io_start, r_eq);
     });
 }
 
@@ -388,6 +516,7 @@ int cozk_output_check_final(cozk_output_check* oc, const uint64_t r[4], uint64_t
         HIP_TRY(hipGetLastError());
         fe h[3];
         fetch_fe(oc->ctx, res, 3, h);
+        if (oc->rep3) h[2] = Fr::mul(h[2], fr_two_inv());  // the additive share of (v_final - v_io)(r)
         for (int e = 0; e < 3; e++) fe_to_u64x4(h[e], out + 4 * e);
     });
 }

@@ -18,6 +18,8 @@ def _decl():
     l = L.lib()
     l.cozk_output_check_create.restype = _i
     l.cozk_output_check_create.argtypes = [_vp, _vp, _vp, _sz, _vp, ctypes.POINTER(_vp)]
+    l.cozk_output_check_shared_create.restype = _i
+    l.cozk_output_check_shared_create.argtypes = [_vp, _vp, _vp, _sz, _vp, _i, ctypes.POINTER(_vp)]
     l.cozk_output_check_round.restype = _i
     l.cozk_output_check_round.argtypes = [_vp, _vp, _vp]
     l.cozk_output_check_final.restype = _i
@@ -35,14 +37,25 @@ class OutputCheck:
     0, round(r) binds the previous variable and gives the next round, final(r) the last bind; v_final and v_io are only read and must
     outlive the handle (it keeps them alive).  A refused argument raises CozkError with the call's text."""
 
-    def __init__(self, ctx, v_final, v_io, io_start, r_eq):
+    def __init__(self, ctx, v_final, v_io, io_start, r_eq, party=None):
         self.ctx, self._l, self.h = ctx, _decl(), None
         self._keep = (v_final, v_io)
         rr = None if r_eq is None else fr_to_mont_limbs(list(r_eq)) if len(r_eq) else np.zeros((1, 4), dtype=np.uint64)
         h = _vp()
-        ctx.check(self._l.cozk_output_check_create(ctx.h, None if v_final is None else v_final.h, None if v_io is None else v_io.h, io_start,
-                                                   None if rr is None else rr.ctypes.data, ctypes.byref(h)))
+        args = (ctx.h, None if v_final is None else v_final.h, None if v_io is None else v_io.h, io_start, None if rr is None else rr.ctypes.data)
+        if party is None:
+            ctx.check(self._l.cozk_output_check_create(*args, ctypes.byref(h)))
+        else:
+            ctx.check(self._l.cozk_output_check_shared_create(*args, party, ctypes.byref(h)))
         self.h = h
+
+    @classmethod
+    def shared(cls, ctx, v_final, v_io, io_start, r_eq, party=0):
+        """The same check on a v_final that is a `Rep3DensePolynomial` of 2^m unbound entries, plain or a Rep3 party's share
+        (cozk_output_check_shared_create); party 0..2 for Rep3, 0 for plain.  Every round value of a Rep3 party is its additive share
+        (a + b) / 2 of the dense rounds on linear_combination([v_final, v_io], [1, -1], mode, party), and final(r)[2] the additive share of
+        (v_final - v_io)(r); the three parties' values sum to the plain ones."""
+        return cls(ctx, v_final, v_io, io_start, r_eq, party=party)
 
     def __len__(self):
         return self._l.cozk_output_check_len(self.h)

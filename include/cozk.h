@@ -2084,7 +2084,8 @@ int cozk_rw_proof_proof_bytes(const cozk_rw_proof* h, uint8_t* out, size_t cap);
  * r_rw ("leaf claim").
  * Refused by create before any context exists: log_n outside 1..22, log_mem outside 5..24, n_slots outside 1..4, leaves_fused outside
  * 0..1, tamper outside 0..2.
- * Not built: the timestamp range check and the output check by Rep3 parties, one party per process. */
+ * The output check by the same parties behind these steps: cozk_memory_proof_rep3_* below.
+ * Not built: the timestamp range check by Rep3 parties, one party per process. */
 typedef struct cozk_rw_proof_rep3 cozk_rw_proof_rep3;
 typedef struct cozk_rw_proof_rep3_config {
     int devices[3];   /* one device per party */
@@ -2138,6 +2139,22 @@ int cozk_output_check_round(cozk_output_check* oc, const uint64_t* r, uint64_t o
 int cozk_output_check_final(cozk_output_check* oc, const uint64_t r[4], uint64_t out[12]);
 size_t cozk_output_check_len(const cozk_output_check* oc);
 int cozk_output_check_free(cozk_output_check* oc);
+/* The same check on a v_final that is a polynomial: PLAIN (one Fr component) or a party's REP3 share; the mode is the polynomial's own.
+ * v_final: exactly 2^m unbound entries, 1 <= m < 32; party: 0..2 for REP3, 0 for PLAIN; v_io, io_start and r_eq as above.  The handle
+ * is the same type: cozk_output_check_round / _final / _len / _free serve it, with their refusals.  Everything the check sends is linear
+ * in the share, and a party's message is the additive share (a + b) * 2^-1 of its two components, so the device works on ONE Fr vector
+ *     T[x] = a[x] + b[x] (REP3), a[x] (PLAIN);   d[x] = T[x] - sub * v_io[x - io_start] inside the window, T[x] outside,
+ * sub = 1 for PLAIN and for REP3 parties 0 and 1, 0 for REP3 party 2 (cozk_poly_linear_combination puts a public term into party 0's a
+ * and party 1's b), and for REP3 the three round values and d's final value are multiplied by 2^-1.  Every value is canonical:
+ * _round's out is byte for byte cozk_prod_sumcheck_evals({eq, io_range, cozk_poly_linear_combination({v_final, v_io}, {1, -1}, mode,
+ * party)}, 3, 3, ..) in the same state, and _final's out = eq(r), io_range(r) and, for REP3, the additive share (a + b) * 2^-1 of
+ * cozk_poly_get_coeff(d, 0, ..) -- the three parties' values sum to the PLAIN ones.  Device memory as above; v_final and v_io are only
+ * read and must outlive the handle; a party with sub = 0 reads no v_io entry.
+ * Refused with COZK_ERR_INVALID_ARG and a text of its own before any launch, *out NULL, the context working on: a null argument; a
+ * length that is not a power of two of at least 2 (and below 2^32); a bound polynomial; party outside its range; a v_io that is not
+ * U32; io_len == 0; io_start + io_len > MEM; a vector or polynomial on another device. */
+int cozk_output_check_shared_create(cozk_ctx* ctx, const cozk_poly* v_final, const cozk_vec* v_io, size_t io_start, const uint64_t* r_eq,
+                                    int party, cozk_output_check** out);
 
 /* ---- The whole ReadWriteMemoryProof in the reference's order, as an in-process harness (csrc/host/memory_proof.hpp): the memory
  * check, the output check, the timestamp range check, under one transcript ("cozk-rw-memory") and one opening accumulator, with ONE
@@ -2188,6 +2205,49 @@ const char* cozk_memory_proof_error(const cozk_memory_proof* h);
 int cozk_memory_proof_destroy(cozk_memory_proof* h);
 int cozk_memory_proof_prove(cozk_memory_proof* h, int verify, cozk_memory_proof_result* res);
 int cozk_memory_proof_proof_bytes(const cozk_memory_proof* h, uint8_t* out, size_t cap);
+
+/* ---- The memory check and the output check of ReadWriteMemoryProof by three Rep3 parties, as an in-process harness
+ * (csrc/host/memory_proof_rep3.hpp): cozk_rw_proof_rep3's sharing and steps with prove_outputs on each party's share of v_final behind
+ * them, under one transcript and one opening accumulator.  The instance, v_io, the proof bytes and the verifier are cozk_memory_proof's
+ * with with_ts = 0: the proof is byte for byte that harness's PLAIN proof of the same seed and window, for windowed 0 and 1 and
+ * leaves_fused 0 and 1 alike, and proof[0 .. prefix_len) is cozk_rw_proof_rep3's proof prefix.
+ * prove: cozk_rw_proof_rep3's steps 1-4 (the memory check with its two openings); the coordinator draws r_eq and sends it; log_mem rounds
+ * in the messages of prove_arbitrary_worker, every party's round message an additive share (windowed = 1: cozk_output_check_shared_create
+ * on the party's polynomial, then cozk_output_check_round / _final; windowed = 0: the dense composition in REP3 on each party's
+ * polynomials -- an eq table and two public vectors of MEM entries and the two-component difference, all bound every round); one
+ * opening of the shared v_final at the sumcheck's point, its claim additive; ONE reduce_and_prove.
+ * tamper: 1 and 2 are cozk_rw_proof_rep3's; 4 adds 1 to v_io[io_len / 2] ("output check: final claim").
+ * Refused: whatever cozk_rw_proof_rep3_create refuses, io_len < 1, io_start + io_len > MEM, windowed outside 0..1, tamper 3 and above 4.
+ * Not built: the timestamp range check by Rep3 parties, one party per process. */
+typedef struct cozk_memory_proof_rep3 cozk_memory_proof_rep3;
+typedef struct cozk_memory_proof_rep3_config {
+    int devices[3];    /* one device per party */
+    int log_n;         /* 1..22 */
+    int log_mem;       /* 5..24 */
+    int n_slots;       /* 1..4 */
+    uint64_t seed;     /* the instance seed: the same seed gives cozk_memory_proof's instance */
+    int precompute;
+    int leaves_fused;  /* as cozk_rw_proof_rep3_config */
+    int tamper;        /* 0, 1, 2 or 4: see above */
+    uint64_t io_start; /* first word of the io window */
+    uint64_t io_len;   /* its length in words, >= 1 */
+    int windowed;      /* 1: the shared device calls; 0: the dense composition in REP3 */
+} cozk_memory_proof_rep3_config;
+typedef struct cozk_memory_proof_rep3_result {
+    int verified; /* 1 ok, 0 rejected, -1 not run */
+    /* as cozk_rw_proof_rep3_result; t_out_ms: the output check (its rounds and the v_final opening), the maximum over the parties */
+    double wall_ms, t_witness_ms, t_share_ms, t_commit_ms, t_leaves_ms, t_gp_ms, t_out_ms, t_open_ms;
+    uint64_t ring_bytes; /* sent over the ring by the three parties together */
+    uint64_t proof_len;
+    uint64_t prefix_len;     /* proof[0 .. prefix_len) is cozk_rw_proof_rep3's prefix: the commitments and the memory-check part */
+    uint64_t out_peak_bytes; /* as cozk_memory_proof_result, the maximum over the parties */
+    uint8_t proof_digest[32];
+} cozk_memory_proof_rep3_result;
+int cozk_memory_proof_rep3_create(const cozk_memory_proof_rep3_config* cfg, cozk_memory_proof_rep3** out);
+const char* cozk_memory_proof_rep3_error(const cozk_memory_proof_rep3* h);
+int cozk_memory_proof_rep3_destroy(cozk_memory_proof_rep3* h);
+int cozk_memory_proof_rep3_prove(cozk_memory_proof_rep3* h, int verify, cozk_memory_proof_rep3_result* res);
+int cozk_memory_proof_rep3_proof_bytes(const cozk_memory_proof_rep3* h, uint8_t* out, size_t cap);
 
 /* ---- ONE chained co-jolt worker flow (JoltRep3Prover::prove, co-jolt/src/jolt/vm/jolt/worker.rs:175-266, against its coordinator
  * jolt/vm/jolt/coordinator.rs:118-222): commit-all -> bytecode memory checking -> instruction lookups (primary sumcheck, toggled
